@@ -218,6 +218,49 @@ def sample_rows(n, m=4096):
     return numpy.unique(numpy.concatenate([numpy.arange(a), mid, numpy.arange(n - a, n)]))
 
 
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 20261015          # --dump-outputs: the row sample when not every row fits
+
+
+def dump_rows(n, row_bytes, n_files, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """rows written by --dump-outputs: every row when they fit in ``budget``, else as many as fit, a sample drawn with a
+    fixed seed -- always including row 0 and row n - 1 -- in ascending order.  Depends only on its arguments."""
+    import numpy
+    m = min(n, (budget - 256 * n_files) // row_bytes)         # 256 B per file: room for the .npy header
+    if m >= n:
+        return numpy.arange(n, dtype=numpy.int64)
+    inner = numpy.random.default_rng(seed).choice(numpy.arange(1, n - 1), size=m - 2, replace=False)
+    return numpy.sort(numpy.concatenate([[0, n - 1], inner])).astype(numpy.int64)
+
+
+def dump_outputs(out_dir, fplan, bplan, budget=DUMP_BYTES):
+    """`--dump-outputs DIR`: every array the forward and the backward plan hand their caller, as DIR/<name>.npy -- float
+    outputs in their own type (float64; float32 for --dtype f32), the int32 index map as float64 (exact) -- for the rows
+    of ``dump_rows``.  Returns what the JSON line reports about the dump."""
+    import numpy
+    import torch
+    outs = dict(fplan.outputs)
+    outs.update(bplan.outputs)
+    n = int(next(iter(outs.values())).shape[0])
+    types = {k: (numpy.float32 if v.dtype == torch.float32 else numpy.float64) for k, v in outs.items()}
+    row_bytes = sum(v[0].numel() * numpy.dtype(types[k]).itemsize for k, v in outs.items())
+    rows = dump_rows(n, row_bytes, len(outs), budget)
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None
+    total = 0
+    for k, v in outs.items():
+        if len(rows) < n:
+            if idx is None:
+                idx = torch.from_numpy(rows).to(v.device)
+            v = v.index_select(0, idx)
+        path = os.path.join(out_dir, k + ".npy")
+        numpy.save(path, numpy.ascontiguousarray(v.cpu().numpy(), dtype=types[k]))
+        total += os.path.getsize(path)
+    return {"dir": os.path.abspath(out_dir), "arrays": sorted(outs), "rows": int(len(rows)), "rows_in_block": n,
+            "row_sample": None if len(rows) == n else "numpy.random.default_rng(%d), rows 0 and %d always" % (DUMP_SEED, n - 1),
+            "bytes": total}
+
+
 # fp32 arithmetic variant (BASELINE config 5's tolerance sweep): outputs against the fp64 oracle ON THE SAME (rounded) INPUTS.
 # A forcing / tendency is factor (x_interpolated - x_model) / dt, a difference of nearly equal numbers, so its fp32 error is
 # set by the PROFILE's scale: the statistic is max |err| dt / (|factor| max |profile|).  Bars = 5-10x what
@@ -842,7 +885,12 @@ def main():
     ap.add_argument("--check-rows", type=int, default=4096, help="rows per rank / device in the N > 1 output check (sample_check)")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="N>1 launch mechanics only (rendezvous, sharding, barrier, max-reduction over gloo; no GPU work): CPU tests")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (every output of its forward and backward "
+                         "plans) as DIR/<name>.npy, at most 64 MB in all (a seeded row sample when they do not fit); N > 1: rank 0's block")
     args = ap.parse_args()
+    if args.dump_outputs is not None and (args.steps < 1 or args.rehearse_cpu):
+        ap.error("--dump-outputs needs a timed step on the GPU (--steps >= 1, no --rehearse-cpu)")
 
     # `python bench.py --gpus N` launched plainly (no torchrun around it): start the N ranks as FRESH CHILD PROCESSES
     # before this process has imported torch or touched the GPU, let rank 0's JSON line through, return their exit code.
@@ -951,6 +999,10 @@ def main():
         tt = torch.tensor([elapsed], device=eng.device if args.backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        last = (args.steps - 1) % rotate                 # the batch the last timed step launched (Workload.step)
+        dumped = dict(dump_outputs(args.dump_outputs, wl.fplans[last], wl.bplans[last]), batch=last)
 
     # spread of the headline: the same W + K region four more times (each behind Workload.heat like the official one);
     # the official `value` stays the FIRST region, timed exactly as the contract says
@@ -1184,6 +1236,8 @@ def main():
     if dropin is not None:
         out["dropin"] = dropin
         out["dropin_value"] = dropin.get("batched_protocol", {}).get("value")
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     out["verified"] = None
     if per_rank:
         out["verified"] = all(r["verified"] for r in per_rank)

@@ -1,8 +1,29 @@
-"""Helpers shared by the -m gpu parity tests."""
+"""Helpers shared by the -m gpu parity tests, and the no-device rerun of CPU tests that walk fallbacks."""
+import os
+import subprocess
+import sys
+
 import numpy
+import pytest
 import torch
 
 EPS = 2.220446049250313e-16
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def ran_without_a_device(request):
+    """For a CPU test of what happens WITHOUT a HIP device (the library's occupancy / CU-count fallbacks, bench.py's live
+    PMC pass giving up): False when this process sees no GPU -- the test runs here; True when it does, after the same
+    test has passed in a child pytest that sees none (HIP_VISIBLE_DEVICES=-1) -- the test then returns."""
+    if not torch.cuda.is_available():
+        return False
+    if os.environ.get("SPC_TEST_CHILD_WITHOUT_DEVICE"):
+        pytest.fail("HIP_VISIBLE_DEVICES=-1 left a device visible to the child process")
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", SPC_TEST_CHILD_WITHOUT_DEVICE="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "%s::%s" % (request.node.path, request.node.name)],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    return True
 
 
 def to_dev(d, device, dtype=torch.float64):
