@@ -536,6 +536,8 @@ constexpr int cfloor_pow2(int n) { int p = 1; while (p * 2 <= n) p *= 2; return 
 //      with PRE = false: those ~20 registers are live across phase 1, whose pow() sets the kernel's register peak, and
 //      without them K1 fits 6 waves per SIMD instead of 5 (75 vs 94 VGPRs) -- K1's rate follows its resident waves
 //      (profiles/r02_occupancy_ab_hot.log): -7 % at 35 718 columns, +12 % at 1024 (profiles/r02_k1_occupancy6_ab.log).
+//      PRE = false is also the REACH form (phase 1 split at the LES interpolation's reach, below): one more dependent
+//      round trip per workgroup, which a multi-round launch hides behind its other resident workgroups.
 template <typename T, bool FULL, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true>
 __global__ __launch_bounds__(BLK, SPC_K1_WAVES) void k_forward(const FwdP<T, FULL> p)
 {
@@ -554,6 +556,7 @@ __global__ __launch_bounds__(BLK, SPC_K1_WAVES) void k_forward(const FwdP<T, FUL
     T *const lzh = lds + (size_t)cb * 6 * nG;
     // work items after the barrier: [0, n2) LES levels to interpolate, [n2, n2 + nI) index-map entries
     const int n1 = ncol * nG, n2 = ncol * nL, nI = p.idx ? n1 : 0, nitems = n2 + nI;
+    constexpr bool REACH = !PRE;
     STAMP(0);
 
     // ---- prologue: issue every load that depends on nothing, so ONE memory round trip covers the
@@ -590,21 +593,72 @@ __global__ __launch_bounds__(BLK, SPC_K1_WAVES) void k_forward(const FwdP<T, FUL
     STAMP(1);
 
     // ---- phase 1: load GCM levels (flat over the [ncol x nG] slab), convert, stage reversed ----
-    for (int e = tid; e < n1; e += BLK) {
-        const int c = e / nG, k = e - c * nG;
+    // REACH (multi-round launches, PRE = false): phase 1 is split in two.  Phase A stages Zf for every level and takes the
+    // largest non-NaN LES height of the slab; one search of that height in each column's Zf then bounds every bracket
+    // phase 2 can form (reach_top), and phase B loads and converts the other 7 fields only for the levels 0 ... top (in
+    // ascending-height order).  Exact for any input: upper_count is monotone in x for ANY xp (a lane with the larger x
+    // takes every branch the smaller one takes), so j0(x) <= j0(hmax) and j1(x) <= min(j0(hmax) + 1, nG - 1) for every
+    // non-NaN x <= hmax, and a NaN height takes level 0.  LDS above the reach is never written nor read.
+    int nR = nG;                                   // levels staged per column: the nR lowest (REACH) or all
+    if constexpr (REACH) {
+        __shared__ T s_wmax[BLK / 64];
+        __shared__ int s_top;
+        if (tid == 0) s_top = 0;
+        for (int e = tid; e < n1; e += BLK) {
+            const int c = e / nG, k = e - c * nG;
+            const int64_t col = col0 + c, g = col * pitchG + k;
+            const T zf_k = div_grav(ldg(&p.Zgfull[g]) - ldg(&p.Zghalf[col * pitchGh + nG]));   // spcpl.py:198
+            lds[(size_t)c * 6 * nG + (nG - 1 - k)] = zf_k;                                     // [::-1], spcpl.py:224
+            if constexpr (FULL)
+                if (OPT(Zf)) OPT(Zf)[g] = zf_k;                                                 // spcpl.py:200
+        }
+        T hmax = T(-__builtin_huge_val());
+        for (int e = tid, nz = d.shared_grid ? nL : n2; e < nz; e += BLK) {
+            const int c = e / nL, l = e - c * nL;
+            const T h = d.shared_grid ? ldg(&p.zf[e]) : ldg(&p.zf[(col0 + c) * pitchL + l]);
+            hmax = h > hmax ? h : hmax;                                                          // NaN never wins
+        }
+        for (int m = 32; m > 0; m >>= 1) {
+            const T o = __shfl_xor(hmax, m, 64);
+            hmax = o > hmax ? o : hmax;
+        }
+        if ((tid & 63) == 0) s_wmax[tid >> 6] = hmax;
+        __syncthreads();
+        if (tid < ncol) {
+            for (int w = 0; w < BLK / 64; ++w) hmax = s_wmax[w] > hmax ? s_wmax[w] : hmax;
+            const Br<T> b = bracket2(lds + (size_t)tid * 6 * nG, nG, p2G, hmax);
+            atomicMax(&s_top, (SPC_EXP == 2 || b.j0 + 1 >= nG) ? nG - 1 : b.j0 + 1);   // (SPC_EXP 2: searches replaced)
+        }
+        __syncthreads();
+        nR = s_top + 1;
+    }
+    const float rcp_nR = 1.0f / (float)nR;
+    for (int e = tid; e < ncol * nR; e += BLK) {
+        int c, k;
+        if constexpr (REACH) {         // e -> (column, level) for a run-time nR: float quotient, off by at most one
+            c = (int)((float)e * rcp_nR);
+            int r = e - c * nR;
+            if (r < 0) { --c; r += nR; } else if (r >= nR) { ++c; r -= nR; }
+            k = nG - nR + r;
+        } else {
+            c = e / nG; k = e - c * nG;
+        }
         const int64_t col = col0 + c, g = col * pitchG + k;
-        const T zsurf = ldg(&p.Zghalf[col * pitchGh + nG]);
-        const T tt = ldg(&p.Tm[g]), sh = ldg(&p.SH[g]), ql = ldg(&p.QL[g]), qi = ldg(&p.QI[g]), pf = ldg(&p.Pf[g]), zg = ldg(&p.Zgfull[g]);
+        const T zsurf = REACH ? T(0) : ldg(&p.Zghalf[col * pitchGh + nG]);
+        const T tt = ldg(&p.Tm[g]), sh = ldg(&p.SH[g]), ql = ldg(&p.QL[g]), qi = ldg(&p.QI[g]), pf = ldg(&p.Pf[g]);
+        const T zg = REACH ? T(0) : ldg(&p.Zgfull[g]);
         const T uu = ldg(&p.U[g]), vv = ldg(&p.V[g]);
-        const T zf_k = div_grav(zg - zsurf);                                          // spcpl.py:198
         T *const s = lds + (size_t)c * 6 * nG + (nG - 1 - k);                         // [::-1], spcpl.py:224
-        s[0] = zf_k;
+        if constexpr (!REACH) {
+            const T zf_k = div_grav(zg - zsurf);                                      // spcpl.py:198
+            s[0] = zf_k;
+            if constexpr (FULL)
+                if (OPT(Zf)) OPT(Zf)[g] = zf_k;                                         // spcpl.py:200
+        }
         s[2 * nG] = SPC_MUT(12, sh + ql, sh + ql + qi);                               // spcpl.py:215
         s[3 * nG] = ql;
         SPC_MUT(6, lds + (size_t)c * 6 * nG + k, s)[4 * nG] = uu;
         s[5 * nG] = vv;
-        if constexpr (FULL)
-            if (OPT(Zf)) OPT(Zf)[g] = zf_k;                                             // spcpl.py:200
         const T iex = spc_pow(div_pref0(pf), SPC_MUT(1, K<T>::rd, -K<T>::rd) / K<T>::cp);   // sputils.py:34
         s[nG] = SPC_MUT(8, tt + div_cp(K<T>::rlv * (ql + qi)), tt - div_cp(K<T>::rlv * (ql + qi))) * iex;   // spcpl.py:214
     }
@@ -1883,7 +1937,11 @@ int spc_describe_launch(const spc_dims *d, int pass, int flags, int elem_size, c
         snprintf(name, sizeof(name), "k_diag<%s,%d,%d,wt=%d>", ty, GEO_NG[c.geo], GEO_NL[c.geo], c.wt);
     else
         snprintf(name, sizeof(name), "%s<%s>", c.kernel, ty);
-    return snprintf(buf, (size_t)buflen, "%s cb=%d grid=%u block=%d lds=%lld cus=%d", name, c.cb, c.grid, c.blk, (long long)c.smem, device_cus());
+    // K1's phase structure: "reach" = the PRE = false kernels (GCM fields loaded only up to the LES interpolation's reach),
+    // "whole" = one phase over every level (PRE = true), "vec" = k_forward_f32v (every level)
+    const char *form = pass != 0 ? "" : (c.vec ? " form=vec" : (c.pre ? " form=whole" : " form=reach"));
+    return snprintf(buf, (size_t)buflen, "%s cb=%d grid=%u block=%d lds=%lld cus=%d%s", name, c.cb, c.grid, c.blk, (long long)c.smem,
+                    device_cus(), form);
 }
 
 int spc_pick_cols_per_block(const spc_dims *d, int pass)
