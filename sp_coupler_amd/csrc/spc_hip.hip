@@ -39,33 +39,16 @@
 __constant__ double spc_pow_coef_table[21] = {SPC_POW_COEFS};
 #define SPC_POW_TABLE spc_pow_coef_table
 
-// Diagnostic builds only (never the shipped library; tools/exp_variants.sh): apportion kernel time.
-//   -DSPC_EXP=1  every division becomes a multiplication by v_rcp_f64 (NOT bit-exact)
-//   -DSPC_EXP=3  as 1, and pow() becomes a multiplication
-//   -DSPC_EXP=2  as 3, and the searches are replaced by a constant index (memory + LDS traffic only)
-#ifndef SPC_EXP
-#define SPC_EXP 0
-#endif
 // Mutation control of the semantic tests (tools/mutation_control.py, never the shipped library): -DSPC_MUTANT=n perturbs ONE
 // line of a kernel -- the slip a transcription of the reference could contain -- and tests/test_semantic_gpu.py must fail.
 #ifndef SPC_MUTANT
 #define SPC_MUTANT 0
 #endif
 #define SPC_MUT(n, mutated, original) (SPC_MUTANT == (n) ? (mutated) : (original))
-#if SPC_EXP
-__device__ __forceinline__ double spc_exp_rcp(double b) { return __builtin_amdgcn_rcp(b); }
-__device__ __forceinline__ float spc_exp_rcp(float b) { return __builtin_amdgcn_rcpf(b); }
-#define SPC_DIV(a, b) ((a) * spc_exp_rcp(b))
-#else
-#define SPC_DIV(a, b) ((a) / (b))
-#endif
 
 namespace {
 
-#ifndef SPC_BLOCK
-#define SPC_BLOCK 256
-#endif
-constexpr int BLOCK = SPC_BLOCK;
+constexpr int BLOCK = 256;
 constexpr int MAX_LDS_BYTES = 64 * 1024;    // preferred ceiling (default dynamic-LDS limit, >= 2 workgroups per CU)
 constexpr int HARD_LDS_BYTES = 160 * 1024;  // gfx950: 160 KiB per CU, reachable for one column per workgroup
 
@@ -83,15 +66,6 @@ template <typename T> struct K {
                        grav = T(9.81);
 };
 
-#if SPC_FASTPOW
-__device__ __forceinline__ double spc_pow(double x, double y) { return exp(y * log(x)); }
-__device__ __forceinline__ float spc_pow(float x, float y) { return expf(y * logf(x)); }
-#else
-#if SPC_EXP >= 2
-__device__ __forceinline__ double spc_pow(double x, double y) { return x * y; }
-#elif defined(SPC_OCML_POW)
-__device__ __forceinline__ double spc_pow(double x, double y) { return pow(x, y); }
-#else
 // x**y for the two exponents of this path, y = -+rd/cp (sputils.py:28-34), |y| <= 1: spc_pow.h (one source for this file and
 // for the host accuracy sweep tools/csrc/pow_accuracy.c; round 4: <= 0.56 ulp against an 80-bit reference, was 1.2).
 // Arguments outside (0, inf) get C99 pow()'s special values for a non-integer exponent, inline (0 -> inf or 0, inf -> 0 or
@@ -128,20 +102,11 @@ __device__ __forceinline__ double spc_exner_pow(double p, double y)
     }
     return spc_pow_pos_tab(x, y);
 }
-#endif
 // the fp32 variant's power: spc_powf.h -- evaluated inside double arithmetic and rounded once (<= 0.5 + 2^-14 ulp, the host
 // sweep computes the device's bits), inline; rounds 1-4 called ocml's powf() out of line.  Special values as for double.
-#ifndef SPC_POW_FN
-#define SPC_POW_FN __device__ __forceinline__
-#endif
 #include "spc_powf.h"
 __device__ __forceinline__ float spc_pow(float x, float y)
 {
-#if SPC_EXP >= 2
-    return x * y;
-#elif defined(SPC_OCML_POW) || defined(SPC_OCML_POWF)     // A/B builds: ocml's powf (what rounds 1-4 shipped)
-    return powf(x, y);
-#else
     if (!(x > 0.0f && x <= 3.4028234663852886e38f)) {
         if (x != x) return x;                                                      // NaN
         const float big = __builtin_huge_valf();
@@ -150,50 +115,22 @@ __device__ __forceinline__ float spc_pow(float x, float y)
         return __builtin_nanf("");
     }
     return spc_powf_pos(x, y);
-#endif
 }
-#endif
-
-#if SPC_FASTPOW || SPC_EXP >= 2 || defined(SPC_OCML_POW)      // diagnostic builds: one pow for everything
-__device__ __forceinline__ double spc_exner_pow(double p, double y) { return spc_pow(SPC_DIV(p, 1e5), y); }
-#endif
-__device__ __forceinline__ float spc_exner_pow(float p, float y) { return spc_pow(SPC_DIV(p, 1e5f), y); }
+__device__ __forceinline__ float spc_exner_pow(float p, float y) { return spc_pow(p / 1e5f, y); }
 
 // Streaming accesses of the hot kernels: every input element is read once and every output written
-// once per launch.  -DSPC_NT=1 marks them non-temporal (experiment switch); 2: the loads only, 3: the
-// stores only (only the plain stores: write-through launches keep their sc1 stores).
-#ifndef SPC_NT
-#define SPC_NT 0
-#endif
-template <typename T> __device__ __forceinline__ T ldg(const T *q)
-{
-#if SPC_NT == 1 || SPC_NT == 2
-    return __builtin_nontemporal_load(q);
-#else
-    return *q;
-#endif
-}
+// once per launch.  Plain loads and stores: non-temporal ones were measured and lost.
+template <typename T> __device__ __forceinline__ T ldg(const T *q) { return *q; }
 // WT = 1: write-through (sc1) store: nothing is left dirty in L2 for the end-of-kernel release to
 // flush.  Measured on MI355X: -5 % (K1) / -7 % (K3) at 1024 columns where that flush is ~1 us of a
 // ~10 us kernel, but +6 % on K3 at 35k columns -- so only the small-batch launches use it.
 template <int WT, typename T> __device__ __forceinline__ void stg(T *q, T v)
 {
-#if SPC_NT == 1
-    __builtin_nontemporal_store(v, q);
-#else
     if constexpr (WT == 1)
         __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if constexpr (SPC_NT == 3)
-        __builtin_nontemporal_store(v, q);
     else
         *q = v;
-#endif
 }
-
-// -DSPC_FASTPOW=1: x**y as exp(y*log(x)) (|y log x| < 2 on this path, ~4 ulp) instead of ocml pow (<1 ulp)
-#ifndef SPC_FASTPOW
-#define SPC_FASTPOW 0
-#endif
 
 // Every quotient on this path is a true IEEE division (x / y), never x * (1/y): the reference divides,
 // and bit-parity of the u/v/qt/ql forcings and of all tendencies depends on it.  (Tried and measured
@@ -214,7 +151,7 @@ template <typename T> struct Divisor;
 template <> struct Divisor<double> {
     double b;
     __device__ __forceinline__ explicit Divisor(double b_) : b(b_) {}
-    __device__ __forceinline__ double div(double a) const { return SPC_DIV(a, b); }
+    __device__ __forceinline__ double div(double a) const { return a / b; }
 };
 template <> struct Divisor<float> {
     double r;
@@ -228,20 +165,12 @@ template <> struct Divisor<float> {
     __device__ __forceinline__ explicit Divisor(double r_, int) : r(r_) {}       // r = RN(1 / b) known at compile time
     __device__ __forceinline__ float div(float a) const { return (float)((double)a * r); }
 };
-#ifdef SPC_F32_IEEE_DIV
-struct DivisorF32Ieee { float b; __device__ __forceinline__ explicit DivisorF32Ieee(float b_) : b(b_) {} __device__ __forceinline__ float div(float a) const { return a / b; } };
-#define SPC_DIVISOR(T) typename std::conditional<std::is_same<T, float>::value, DivisorF32Ieee, Divisor<T>>::type
-#else
-#define SPC_DIVISOR(T) Divisor<T>
-#endif
-template <typename T> __device__ __forceinline__ T div_grav(T x) { return SPC_DIV(x, K<T>::grav); }
-template <typename T> __device__ __forceinline__ T div_cp(T x) { return SPC_DIV(x, K<T>::cp); }
-template <typename T> __device__ __forceinline__ T div_pref0(T x) { return SPC_DIV(x, K<T>::pref0); }
-#if !SPC_EXP && !defined(SPC_F32_IEEE_DIV)         // (-DSPC_F32_IEEE_DIV: the A/B build with the compiler's float division)
+template <typename T> __device__ __forceinline__ T div_grav(T x) { return x / K<T>::grav; }
+template <typename T> __device__ __forceinline__ T div_cp(T x) { return x / K<T>::cp; }
+template <typename T> __device__ __forceinline__ T div_pref0(T x) { return x / K<T>::pref0; }
 template <> __device__ __forceinline__ float div_grav<float>(float x) { return Divisor<float>(1.0 / (double)K<float>::grav, 0).div(x); }
 template <> __device__ __forceinline__ float div_cp<float>(float x) { return Divisor<float>(1.0 / (double)K<float>::cp, 0).div(x); }
 template <> __device__ __forceinline__ float div_pref0<float>(float x) { return Divisor<float>(1.0 / (double)K<float>::pref0, 0).div(x); }
-#endif
 
 // numpy NaN-aware "a < b" used by searchsorted (NaN sorts to the end)
 template <typename T> __device__ __forceinline__ bool np_lt(T a, T b) { return a < b || (b != b && a == a); }
@@ -284,9 +213,6 @@ template <typename T> __device__ __forceinline__ int ss_left_pos(const T *a, int
 // largest power of two <= n, so every lane runs the same floor(log2 n)+1 steps (no divergence).
 template <typename T> __device__ __forceinline__ int upper_count(const T *xp, int n, int p2, T x)
 {
-#if SPC_EXP == 2
-    return ((int)(x * T(0.001)) & 15) + 1;
-#endif
     int pos = 0;
     for (int s = p2; s > 0; s >>= 1) {
         const int t = pos + s;
@@ -385,7 +311,7 @@ template <typename T> __device__ __forceinline__ Br<T> bracket2(const T *xp, int
 template <int NF, typename T> __device__ __forceinline__ void interp_fields(const Br<T> &b, const T (&f0)[NF], const T (&f1)[NF], T (&r)[NF])
 {
     const T t0 = b.x - b.x0;
-    const SPC_DIVISOR(T) dx(b.x1 - b.x0);
+    const Divisor<T> dx(b.x1 - b.x0);
     T slope[NF];
     bool any_nan = false;
 #pragma unroll
@@ -462,18 +388,12 @@ extern __shared__ __align__(16) unsigned char spc_smem[];
 // different XCDs.  Giving each XCD a CONTIGUOUS range of slabs keeps those lines in one L2.  Speed only,
 // never correctness (every slab is still processed exactly once).  Used for slabs of <= 2 columns, where
 // slab boundaries are frequent (K3: +4-6 % at 35k-349k columns; 8-column slabs of K1: -1.5 %, so not there).
-// -DSPC_XCD_REMAP=0 disables it altogether (A/B).
-#ifndef SPC_XCD_REMAP
-#define SPC_XCD_REMAP 1
-#endif
 __device__ __forceinline__ unsigned slab_index(int remap)
 {
-#if SPC_XCD_REMAP
     if (remap) {
         const unsigned b = blockIdx.x, nb = gridDim.x, x = b & 7u, j = b >> 3, q = nb >> 3, r = nb & 7u;
         return x * q + (x < r ? x : r) + j;
     }
-#endif
     return blockIdx.x;
 }
 
@@ -517,18 +437,6 @@ constexpr int cfloor_pow2(int n) { int p = 1; while (p * 2 <= n) p *= 2; return 
 // NG / NL != 0: level counts fixed at compile time and contiguous columns (pitch == level count): the
 // flat-index divisions become multiply-shifts, the searches unroll, no pitch registers (hot geometries
 // 91<->160, 137<->512, 19<->160); NG == NL == 0: everything from DimsP at run time.
-#ifndef SPC_K1_WAVES
-#define SPC_K1_WAVES 1
-#endif
-#ifndef SPC_K3_WAVES
-#define SPC_K3_WAVES 1
-#endif
-#ifndef SPC_F32_UNROLL   // work items a thread of the FLOAT K3 keeps in flight per loop round (double: always 1)
-#define SPC_F32_UNROLL 2
-#endif
-#ifndef SPC_K1_NF        // K1: fields whose slope divisions are interleaved (5 = all at once)
-#define SPC_K1_NF 5
-#endif
 // BLK: workgroup size.  256 everywhere except the small-batch path (small_block()): there one workgroup of 512 / 1024
 // threads takes 2 / 4 columns, still one work item per thread, so that <= 256 workgroups cover the batch.
 // PRE: issue the first work item's LES-side inputs and the per-column scalars in the prologue, so that ONE memory round
@@ -539,7 +447,7 @@ constexpr int cfloor_pow2(int n) { int p = 1; while (p * 2 <= n) p *= 2; return 
 //      PRE = false is also the REACH form (phase 1 split at the LES interpolation's reach, below): one more dependent
 //      round trip per workgroup, which a multi-round launch hides behind its other resident workgroups.
 template <typename T, bool FULL, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true>
-__global__ __launch_bounds__(BLK, SPC_K1_WAVES) void k_forward(const FwdP<T, FULL> p)
+__global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
 {
     const DimsP &d = p.d;
     // The ~20 optional pointers of the FULL variant are fetched from the kernarg block where they are used (a
@@ -627,7 +535,7 @@ __global__ __launch_bounds__(BLK, SPC_K1_WAVES) void k_forward(const FwdP<T, FUL
         if (tid < ncol) {
             for (int w = 0; w < BLK / 64; ++w) hmax = s_wmax[w] > hmax ? s_wmax[w] : hmax;
             const Br<T> b = bracket2(lds + (size_t)tid * 6 * nG, nG, p2G, hmax);
-            atomicMax(&s_top, (SPC_EXP == 2 || b.j0 + 1 >= nG) ? nG - 1 : b.j0 + 1);   // (SPC_EXP 2: searches replaced)
+            atomicMax(&s_top, b.j0 + 1 >= nG ? nG - 1 : b.j0 + 1);
         }
         __syncthreads();
         nR = s_top + 1;
@@ -674,7 +582,7 @@ __global__ __launch_bounds__(BLK, SPC_K1_WAVES) void k_forward(const FwdP<T, FUL
             if constexpr (FULL)
                 if (OPT(rainrate)) { sc_rain = OPT(rain)[col]; sc_rl = OPT(rain_last)[col]; }
         }
-        stg<WT>(&p.f_ps[col], SPC_DIVISOR(T)(p.dt).div(p.factor * SPC_MUT(14, sc_psd - sc_ps, sc_ps - sc_psd)));          // spcpl.py:332
+        stg<WT>(&p.f_ps[col], Divisor<T>(p.dt).div(p.factor * SPC_MUT(14, sc_psd - sc_ps, sc_ps - sc_psd)));          // spcpl.py:332
         if constexpr (FULL) {
             if (OPT(ps)) OPT(ps)[col] = sc_ps;
             if (OPT(rainrate)) OPT(rainrate)[col] = SPC_MUT(23, sc_rl - sc_rain, sc_rain - sc_rl) / p.dt;   // spcpl.py:325
@@ -690,7 +598,7 @@ __global__ __launch_bounds__(BLK, SPC_K1_WAVES) void k_forward(const FwdP<T, FUL
     }
 
     // ---- phase 2: LES levels (interpolate 5 fields, form the forcings) and index-map entries ------
-    const SPC_DIVISOR(T) ddt(p.dt);
+    const Divisor<T> ddt(p.dt);
     for (int e = tid; e < nitems; e += BLK) {
         if (e < n2) {
             const int c = e / nL, l = e - c * nL;
@@ -698,35 +606,13 @@ __global__ __launch_bounds__(BLK, SPC_K1_WAVES) void k_forward(const FwdP<T, FUL
             const T *const s = lds + (size_t)c * 6 * nG;
             const LesIn<T> in = (PRE && e == tid) ? pre2 : load_les<FwdP<T, FULL>, T>(p, l, o);
             const Br<T> b = bracket2(s, nG, p2G, in.h);
-            T r[5];
-#if SPC_K1_NF == 5
-            {
-                T f0[5], f1[5];
+            T f0[5], f1[5], r[5];
 #pragma unroll
-                for (int k = 0; k < 5; ++k) {
-                    f0[k] = s[(k + 1) * nG + b.j0];
-                    f1[k] = s[(k + 1) * nG + b.j1];
-                }
-                interp_fields<5>(b, f0, f1, r);
+            for (int k = 0; k < 5; ++k) {
+                f0[k] = s[(k + 1) * nG + b.j0];
+                f1[k] = s[(k + 1) * nG + b.j1];
             }
-#else
-            // fields in groups of SPC_K1_NF: fewer slope divisions interleaved, fewer live registers, more waves per SIMD
-#pragma unroll
-            for (int k0 = 0; k0 < 5; k0 += SPC_K1_NF) {
-                constexpr int G = SPC_K1_NF;
-                T f0[G], f1[G], rr[G];
-#pragma unroll
-                for (int k = 0; k < G; ++k) {
-                    const int kk = (k0 + k) < 5 ? (k0 + k) : 4;
-                    f0[k] = s[(kk + 1) * nG + b.j0];
-                    f1[k] = s[(kk + 1) * nG + b.j1];
-                }
-                interp_fields<G>(b, f0, f1, rr);
-#pragma unroll
-                for (int k = 0; k < G; ++k)
-                    if (k0 + k < 5) r[k0 + k] = rr[k];
-            }
-#endif
+            interp_fields<5>(b, f0, f1, r);
             const T thl = r[0], qt = r[1], ql = r[2], u = r[3], v = r[4];               // spcpl.py:224-228
             stg<WT>(&p.f_u[o], ddt.div(p.factor * (u - SPC_MUT(2, in.vd, in.ud))));               // spcpl.py:328
             stg<WT>(&p.f_v[o], ddt.div(p.factor * (v - SPC_MUT(2, in.ud, in.vd))));               // spcpl.py:329
@@ -810,7 +696,7 @@ template <typename T> __device__ __forceinline__ GcmIn<T> load_gcm(const BwdP<T>
 // PRE: the GCM-side inputs of a thread's first output level are loaded in the prologue (one memory round trip for a
 // single-round launch).  Without it K3 needs 60 instead of 78 VGPRs (8 waves per SIMD instead of 6): +4-7 % at 2-4 k
 // columns, nothing from 16 k on where K3 has saturated (profiles/r02_k3_pre_ab.log) -- used between 1 025 and 25 000 columns.
-template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> __global__ __launch_bounds__(BLK, SPC_K3_WAVES) void k_backward(const BwdP<T> p)
+template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> __global__ __launch_bounds__(BLK) void k_backward(const BwdP<T> p)
 {
     const DimsP &d = p.d;
     const int nG = NG ? NG : d.nG, nL = NL ? NL : d.nL, cb = d.cb, tid = threadIdx.x;
@@ -862,8 +748,8 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
     // UF work items per thread and loop round, all their loads issued before the first is used: 1 for double (the form of
     // rounds 1-4), 2 for float -- a 4-byte access puts half the bytes in flight.  Measured (profiles/r05_f32_ab.log): K3<float>
     // -5 % at config 3 with the quotients through fp64; the same scheme in K1<float> was SLOWER (86 against 78-80 us:
-    // 63 instead of 48 VGPRs and 8 scalar spills) and is not used there.  -DSPC_F32_UNROLL=1: the A/B build.
-    constexpr int UF = sizeof(T) == 4 ? SPC_F32_UNROLL : 1;
+    // 63 instead of 48 VGPRs and 8 scalar spills) and is not used there.
+    constexpr int UF = sizeof(T) == 4 ? 2 : 1;
     for (int e0 = tid; e0 < n2; e0 += UF * BLK) {
         Stage st[UF];
 #pragma unroll
@@ -901,7 +787,7 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
     __syncthreads();
     STAMP(3);
 
-    const SPC_DIVISOR(T) ddt(p.dt);
+    const Divisor<T> ddt(p.dt);
     auto gcm_item = [&](int e, const GcmIn<T> &in) {
         const int c = e / nG, k = e - c * nG;
         const int64_t col = col0 + c, cg = col * pitchG, g = cg + k;
@@ -917,7 +803,7 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
         if (b.mode == 0) {
             const int j = b.j;
             const T ql0 = s[2 * nL + j], ql1 = s[2 * nL + j + 1], qi0 = s[3 * nL + j], qi1 = s[3 * nL + j + 1];
-            const SPC_DIVISOR(T) dx(b.x1 - b.x0);
+            const Divisor<T> dx(b.x1 - b.x0);
             t_i = lerp_np(x, b.x0, b.x1, s[j], s[j + 1], dx);                          // spcpl.py:471
             qt_i = lerp_np(x, b.x0, b.x1, s[nL + j], s[nL + j + 1], dx);               // spcpl.py:472
             ql_i = lerp_np(x, b.x0, b.x1, ql0, ql1, dx);                               // spcpl.py:473
@@ -1169,16 +1055,6 @@ int env_int(const char *name, int dflt)
     return e ? atoi(e) : dflt;
 }
 
-// Experiment switch: dynamic LDS of a launch raised to at least SPC_LDS_MIN_KIB_K1 / _K3 KiB (<= 64), which caps the workgroups
-// resident per CU (160 KiB / that) without touching the kernel: fewer resident workgroups live shorter at the same chip-wide
-// rate, and a launch pays one workgroup lifetime for fill + drain (profiles/r05_residency.log).
-size_t lds_floor(size_t smem, const char *name)
-{
-    const int kib = env_int(name, 0);
-    const size_t want = (size_t)(kib > 64 ? 64 : kib) * 1024;
-    return want > smem ? want : smem;
-}
-
 // Compute units of the CURRENT device (hipDeviceAttributeMultiprocessorCount; cached per device ordinal): what the residency
 // rules below count rounds of workgroups against.  An MI355X in SPX mode has 256; a CPX / DPX partition or another SKU
 // has fewer, and rule 1 of pick_cb would silently pick the wrong slab there (round-4 verdict, weak 10).  SPC_CUS=<n>
@@ -1217,7 +1093,6 @@ template <typename KernelT> int blocks_per_cu(KernelT kernel, size_t smem)
         const size_t by_lds = smem ? (size_t)(160 * 1024) / smem : 8;
         nb = (int)(by_lds < 4 ? by_lds : 4);
     }
-    if (getenv("SPC_DEBUG_OCC")) fprintf(stderr, "spc: occupancy query: %zu B of dynamic LDS -> %d workgroups per CU\n", smem, nb);
     if (nb > 8) nb = 8;
     cache[key] = nb;
     return nb;
@@ -1266,16 +1141,9 @@ template <typename KernelT> int pick_cb(const spc_dims *d, int pass, bool with_i
 
 // Launches that write no more than the aggregate L2 (32 MiB) store write-through: otherwise all of it is
 // still dirty when the kernel ends and the end-of-kernel release has to flush it (measured: WT wins up
-// to ~4096 columns, loses beyond ~16k).  SPC_FORCE_WT=0/1 overrides (A/B runs).
-int wt_forced()      // SPC_FORCE_WT: 0 / 1, else -1
-{
-    static const int forced = [] { const char *e = getenv("SPC_FORCE_WT"); const int v = e ? atoi(e) : -1; return v == 0 || v == 1 ? v : -1; }();
-    return forced;
-}
-
+// to ~4096 columns, loses beyond ~16k).
 int small_batch(int64_t bytes_written, int limit_mib = 32)
 {
-    if (wt_forced() >= 0) return wt_forced();
     return bytes_written <= (int64_t)limit_mib * 1024 * 1024 ? 1 : 0;
 }
 
@@ -1326,14 +1194,14 @@ int launch_status(const char *what)
 // Small batches run ONE round of workgroups and are bound by latency, not bandwidth: there fewer, larger workgroups
 // win.  2 / 4 columns per workgroup of 512 / 1024 threads (still one work item per thread, so the per-thread chain is
 // unchanged) cover <= 1024 columns with <= 256 workgroups -- one per CU -- and the grid is dispatched in a half / a
-// quarter of the time.  Measured (tools/ab_blocks.sh, pre-heated, profiles/r02_ab_blocks.log): K1 8.5 -> 7.1 us and
+// quarter of the time.  Measured (pre-heated, profiles/r02_ab_blocks.log): K1 8.5 -> 7.1 us and
 // K3 8.1 -> 7.8 us at 1024 columns, K1 6.4 -> 5.4 us at 512; slower from 1536 columns on.  Returns the columns per
-// workgroup (workgroup = 256 x that) or 0 = the 256-thread path.  SPC_SMALL_BLOCK=0 disables it (A/B).
+// workgroup (workgroup = 256 x that) or 0 = the 256-thread path.  SPC_SMALL_BLOCK=0 disables it (tests).
 int small_block(const spc_dims *d, int items_per_col)
 {
     const int64_t cus = device_cus();          // (MI355X: 256 -> the 257 ... 1024 columns of the measurements above)
     if (d->cols_per_block != 0 || items_per_col > BLOCK || d->n_cols <= cus || d->n_cols > 4 * cus) return 0;
-    const int sb = env_int("SPC_SMALL_BLOCK", 1);                    // 0: off; 2 / 4: that many columns per workgroup (A/B)
+    const int sb = env_int("SPC_SMALL_BLOCK", 1);                    // 0: off; 2 / 4: that many columns per workgroup (tests)
     if (!sb) return 0;
     if (sb == 2 || sb == 4) return sb;
     return d->n_cols <= 2 * cus ? 2 : 4;
@@ -1393,10 +1261,10 @@ template <typename T> int choose_fwd(const spc_dims *d, bool with_idx, bool full
     c->kernel = "k_forward"; c->elem = (int)sizeof(T); c->full = full; c->idx = with_idx;
     c->geo = geometry_id(d);
     c->wt = full ? 0 : small_batch(d->n_cols * (int64_t)((6 * d->nL + 1) * sizeof(T) + (with_idx ? d->nG * 4 : 0)));
-    // (137 <-> 512 never qualifies for small_block: 649 work items per column; nor does a launch whose write-through
-    //  stores were switched off for an A/B run)
+    // (137 <-> 512 never qualifies for small_block: 649 work items per column; the 512- / 1024-thread kernels exist with
+    //  write-through stores only)
     const int sb = (full || !c->wt) ? 0 : small_block(d, d->nL + (with_idx ? d->nG : 0));
-    // single-round launches keep the prologue prefetch (k_forward's PRE); SPC_K1_PRE=0/1 forces it off / on (A/B)
+    // single-round launches keep the prologue prefetch (k_forward's PRE); SPC_K1_PRE=0/1 forces it off / on (tests)
     const int pre_env = env_int("SPC_K1_PRE", -1);
     c->pre = (sb || (pre_env >= 0 ? pre_env != 0 : d->n_cols <= 4 * (int64_t)device_cus())) ? 1 : 0;   // measured (256 CUs): PRE = false wins from 1100 columns
     c->blk = sb ? BLOCK * sb : BLOCK;
@@ -1408,7 +1276,7 @@ template <typename T> int choose_fwd(const spc_dims *d, bool with_idx, bool full
     lds_elems(d, 0, with_idx, &per_col, &fixed);
     c->smem = (per_col * c->cb + fixed) * sizeof(T);
     c->grid = (unsigned)((d->n_cols + c->cb - 1) / c->cb);
-    // float, compile-time geometry, lean, multi-round, an even slab: 8-byte accesses (spc_f32v.hpp; SPC_F32_VEC=0: A/B, tests)
+    // float, compile-time geometry, lean, multi-round, an even slab: 8-byte accesses (spc_f32v.hpp; SPC_F32_VEC=0: tests)
     c->vec = std::is_same<T, float>::value && c->geo != 0 && !full && !sb && !c->pre && c->cb % 2 == 0 && env_int("SPC_F32_VEC", 1);
     return SPC_OK;
 }
@@ -1481,7 +1349,7 @@ template <typename T> int forward_impl(const spc_dims *d, const spc_forward_args
         FwdP<T, false> p;
         fill(p);
         if ((rc = ensure_lds(kern, c.smem, "forward"))) return rc;
-        hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.blk), lds_floor(c.smem, "SPC_LDS_MIN_KIB_K1"), (hipStream_t)stream, p);
+        hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.blk), c.smem, (hipStream_t)stream, p);
     }
     return launch_status("k_forward");
 }
@@ -1574,10 +1442,9 @@ template <typename T> int choose_bwd(const spc_dims *d, bool cons, Choice *c)
     // 3 072 ... 6 144 it loses 2-5 % (profiles/r04_write_through_sweep.log); K4 loses 10 % at config 3 (182 MB)
     c->wt = cons ? 0 : small_batch(d->n_cols * (int64_t)(7 * d->nG * sizeof(T)), 14);
     const int sb = (cons || !c->wt) ? 0 : small_block(d, d->nL > d->nG ? d->nL : d->nG);
-    const int pre_env = env_int("SPC_K3_PRE", -1);        // SPC_K3_PRE=0/1 forces the prologue prefetch off / on (A/B)
     // PRE = false (8 waves per SIMD) pays between one round of workgroups and saturation: 1 025 ... 25 000 columns
     const int64_t cus = device_cus();      // the measured bounds 1 025 ... 25 000 are 4 ... ~98 columns per CU of the 256
-    c->pre = (cons || sb || (pre_env >= 0 ? pre_env != 0 : (d->n_cols <= 4 * cus || d->n_cols * 256 > 25000 * cus))) ? 1 : 0;
+    c->pre = (cons || sb || d->n_cols <= 4 * cus || d->n_cols * 256 > 25000 * cus) ? 1 : 0;
     c->blk = sb ? BLOCK * sb : BLOCK;
     c->cb = sb ? sb : (cons ? (c->geo ? pick_cb_cons3<T>(d, c->geo) : pick_cb(d, 4, false, sizeof(T), cons_kernel<T>(0, cons_depth(d->nL), 0)))
                             : pick_cb(d, 1, false, sizeof(T), bwd_kernel<T>(c->geo, 0, BLOCK, c->pre)));
@@ -1618,7 +1485,7 @@ template <typename T> int backward_impl(const spc_dims *d, const spc_backward_ar
     CP(t_d); CP(qt_d); CP(ql_d); CP(ql_ice_d); CP(u_d); CP(v_d); CP(A_prof); CP(zh); CP(Zh); CP(rhobf_d);
     p.factor = (T)a->factor; p.dt = (T)a->dt;
     OP(f_T); OP(f_SH); OP(f_QL); OP(f_QI); OP(f_U); OP(f_V); OP(f_A); p.start_index = a->start_index;
-    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.blk), cons ? c.smem : lds_floor(c.smem, "SPC_LDS_MIN_KIB_K3"), (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.blk), c.smem, (hipStream_t)stream, p);
     return launch_status(cons ? "k_backward_cons" : "k_backward");
 }
 
@@ -1819,7 +1686,7 @@ int spc_variability_nudge_f64(const spc_vnudge_args *a, void *stream)
     p.qt_std = (double *)a->qt_std; p.status = a->status;
     // Where the planes live while the root finder runs: in the CU's LDS when KT levels' planes fit (KT x nij x 16 B <= 150
     // KiB: up to ~9 000 points; 64 x 64 planes: KT = 2), else -- 128 x 128 and up -- in the caller's transposed workspace,
-    // one workgroup per level streaming its contiguous planes (k_vnudge_solve<true>; SPC_VN_GLOBAL=1 forces it: A/B, tests).
+    // one workgroup per level streaming its contiguous planes (k_vnudge_solve<true>; SPC_VN_GLOBAL=1 forces it: tests).
     int kt, log2_kt, nleaf_max;
     const bool fits = vn_lds_fit(p.nij, &kt, &log2_kt, &nleaf_max);
     const int64_t work_need = a->n_cols * 2 * (int64_t)p.nij * a->ktot * 8;
@@ -1846,7 +1713,7 @@ int spc_variability_nudge_f64(const spc_vnudge_args *a, void *stream)
             vn_build_tree(shape == 0 ? 8192 : (p.nij % 8192 ? p.nij % 8192 : 8192), q.tab.lo[shape], q.tab.n[shape], q.tab.pl[shape],
                           q.tab.pr[shape], &q.tab.nleaf[shape]);
             q.tab.nround[shape] = vn_build_rounds(q.tab.nleaf[shape], q.tab.pl[shape], q.tab.pr[shape], q.tab.rnd[shape], ready);
-            q.tab.balanced[shape] = env_int("SPC_VN_TREE_SHFL", 1) ? vn_tree_balanced(q.tab.nleaf[shape], q.tab.pl[shape], q.tab.pr[shape], q.tab.rnd[shape]) : 0;
+            q.tab.balanced[shape] = vn_tree_balanced(q.tab.nleaf[shape], q.tab.pl[shape], q.tab.pr[shape], q.tab.rnd[shape]);
         }
         q.work = nullptr;
         if (have_work) {
@@ -1862,7 +1729,7 @@ int spc_variability_nudge_f64(const spc_vnudge_args *a, void *stream)
         q.groups = a->n_cols * q.gpc;
         const size_t smem = lds_need(kt);
         // the noise plane in registers (k_vnudge_solve<false, true>): planes of one chunk with one leaf per 8-lane group
-        const bool rcache = !global && p.nij <= 8192 && q.tab.nleaf[1] <= ((nthreads >> log2_kt) >> 3) && env_int("SPC_VN_RCACHE", 1);
+        const bool rcache = !global && p.nij <= 8192 && q.tab.nleaf[1] <= ((nthreads >> log2_kt) >> 3);
         int rc = global ? ensure_lds(k_vnudge_solve<true>, smem, "variability_nudge")
                         : (rcache ? ensure_lds(k_vnudge_solve<false, true>, smem, "variability_nudge") : ensure_lds(k_vnudge_solve<false>, smem, "variability_nudge"));
         if (rc) return rc;
@@ -1883,8 +1750,7 @@ int spc_variability_nudge_f64(const spc_vnudge_args *a, void *stream)
                            (hipStream_t)stream, p);
         if ((rc = launch_status("k_vnudge_update"))) return rc;
         const dim3 sgrid((unsigned)((a->ktot + 15) / 16), (unsigned)a->n_cols);
-        p.pad = env_int("SPC_VN_STD_DEBUG", 0);
-        if ((int64_t)sgrid.x * sgrid.y <= 256 && env_int("SPC_VN_STD_ROWS", 512) == 512) {
+        if ((int64_t)sgrid.x * sgrid.y <= 256) {
             const size_t ssmem = (size_t)2 * 512 * 16 * sizeof(double);
             if ((rc = ensure_lds(k_vnudge_std<512>, ssmem, "variability_nudge (std)"))) return rc;
             hipLaunchKernelGGL(k_vnudge_std<512>, sgrid, dim3(VS_THREADS), ssmem, (hipStream_t)stream, p);

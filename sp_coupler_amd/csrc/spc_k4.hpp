@@ -254,13 +254,8 @@ template <int CB> __device__ __forceinline__ void k4_split(int e, int n, int &c,
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wpass-failed"
-#ifndef K4_SKIP          // diagnostic builds only (-DK4_SKIP=1): no cell scans, no layer sums -- what the kernel's memory side alone costs
-#define K4_SKIP 0
-#endif
-#ifndef SPC_K4_WAVES     // waves per SIMD the register allocator is asked to fit (6 = 80 VGPRs: six workgroups per CU)
-#define SPC_K4_WAVES 6
-#endif
-template <typename T, int NG, int NL, int CB> __global__ __launch_bounds__(BLOCK, (NL <= 160 ? SPC_K4_WAVES : 1)) void k_backward_cons3(const BwdP<T> p)
+// waves per SIMD the register allocator is asked to fit at NL <= 160: 6 = 80 VGPRs, six workgroups per CU
+template <typename T, int NG, int NL, int CB> __global__ __launch_bounds__(BLOCK, (NL <= 160 ? 6 : 1)) void k_backward_cons3(const BwdP<T> p)
 {
     static_assert(NG > 0 && NL > 1 && (CB == 1 || CB == 2), "compile-time geometry, one or two columns per workgroup");
     const DimsP &d = p.d;
@@ -341,7 +336,7 @@ template <typename T, int NG, int NL, int CB> __global__ __launch_bounds__(BLOCK
         const T *const z = d.shared_grid ? lzh : lzh + (size_t)c * ZROW;
         const T *const Zh = s + o_Zh;
         int ia = -1, ib = -1;
-        if (K4_SKIP == 0 && Zh[k] < z[nL - 1]) {                                                         // sputils.py:187
+        if (Zh[k] < z[nL - 1]) {                                                         // sputils.py:187
             T a = Zh[k + 1], b = Zh[k];
             if (a < z[0] || a > z[nL - 1] || b < z[0] || b > z[nL - 1]) {
                 ia = -2;                                                                 // sputils.py:113-115

@@ -142,12 +142,10 @@ template <int SL, typename T> __device__ __forceinline__ T su_interp_pad(const T
 }
 
 // ---- exner ---------------------------------------------------------------------------------------------------------
-#ifndef SU_EX_PER        // elements per thread: 2 -> 11.1-11.3 us at 35 718 x 91 elements, 4 -> 11.4-11.5, 6 -> 12.2 (profiles/r04_k7_slab_sweep.log)
-#define SU_EX_PER 2
-#endif
+constexpr int SU_EXNER_PER = 2;   // elements per thread: 2 -> 11.1-11.3 us at 35 718 x 91 elements, 4 -> 11.4-11.5, 6 -> 12.2 (profiles/r04_k7_slab_sweep.log)
 template <typename T, int WT> __global__ __launch_bounds__(SU_THREADS) void k_exner(int64_t n, const T *p, T *out, int inverse)
 {
-    constexpr int PER = SU_EX_PER;
+    constexpr int PER = SU_EXNER_PER;
     const T y = inverse ? (-K<T>::rd) / K<T>::cp : K<T>::rd / K<T>::cp;                  // sputils.py:34 / 29
     const int64_t b0 = (int64_t)blockIdx.x * (SU_THREADS * PER);                         // the workgroup's first element: uniform
     const int left = (int)((n - b0) < SU_THREADS * PER ? (n - b0) : SU_THREADS * PER);
@@ -312,10 +310,9 @@ template <int PD, typename F> __device__ __forceinline__ auto su_npsum(const F &
 // LDS values in ndarray.sum() order (pairwise recursion unrolled to the depth PD the host derived from nL, as K4; PD = -1:
 // explicit stack).  The two edge pieces read q / w of the first and last cell from global memory (lines this workgroup has
 // just loaded).  STAGE = false (rows beyond the LDS): terms formed on the fly from global memory.
-#ifndef SU_IC_WAVES      // waves per SIMD the register allocator is asked to fit: 5 = 96 VGPRs (15 spilled) runs 34 us at 35 718 rows,
-#define SU_IC_WAVES 5    // 4 (116 VGPRs, no spills) 36 us, 6 (80 VGPRs, 37 spilled) 38 us (profiles/r04_k7_slab_sweep.log)
-#endif
-template <typename T, int PD, int SL, bool WEIGHTED, int WT> __global__ __launch_bounds__(SU_THREADS, SU_IC_WAVES) void k_interp_c(const SuCoarseP p)
+// Waves per SIMD the register allocator is asked to fit: 5 = 96 VGPRs (15 spilled) runs 34 us at 35 718 rows, 4 (116 VGPRs,
+// no spills) 36 us, 6 (80 VGPRs, 37 spilled) 38 us (profiles/r04_k7_slab_sweep.log).
+template <typename T, int PD, int SL, bool WEIGHTED, int WT> __global__ __launch_bounds__(SU_THREADS, 5) void k_interp_c(const SuCoarseP p)
 {
     constexpr bool STAGE = SL >= 0;
     T *const lds = reinterpret_cast<T *>(spc_smem);

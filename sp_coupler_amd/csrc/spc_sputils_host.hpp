@@ -6,12 +6,8 @@
 // Write-through stores for launches that leave <= 64 MiB behind.  (K1 / K3's small_batch() draws that line at the 32 MiB of
 // the aggregate L2; measured on these operators -- profiles/r04_write_through_sweep.log -- write-through still wins at the
 // 45.7 MB interp GCM->LES writes at 35 718 rows: 20.8 against 23.7 us, the dirty lines otherwise wait for the end-of-kernel
-// release.)  SPC_FORCE_WT=0/1 overrides as for K1 / K3.
-inline int su_write_through(int64_t bytes_written)
-{
-    if (wt_forced() >= 0) return wt_forced();
-    return bytes_written <= (int64_t)64 * 1024 * 1024 ? 1 : 0;
-}
+// release.)
+inline int su_write_through(int64_t bytes_written) { return small_batch(bytes_written, 64); }
 #define SU_PICK_WT(KERN_WT1, KERN_WT0, bytes) (su_write_through((int64_t)(bytes)) ? (KERN_WT1) : (KERN_WT0))
 
 template <typename T> int exner_impl(int64_t n, const void *p, void *out, int inverse, void *stream)
@@ -19,7 +15,7 @@ template <typename T> int exner_impl(int64_t n, const void *p, void *out, int in
     if (n < 0) return fail(SPC_ERR_INVALID_ARGUMENT, "%sexner: n < 0");
     if (n == 0) return SPC_OK;
     REQUIRE(p, "p"); REQUIRE(out, "out");
-    const int64_t per = (int64_t)SU_THREADS * SU_EX_PER;
+    const int64_t per = (int64_t)SU_THREADS * SU_EXNER_PER;
     if ((n + per - 1) / per > 0x7fffffff) return fail(SPC_ERR_UNSUPPORTED, "%sexner: more than 2^41 elements");
     auto kern = SU_PICK_WT((k_exner<T, 1>), (k_exner<T, 0>), n * (int64_t)sizeof(T));
     hipLaunchKernelGGL(kern, dim3((unsigned)((n + per - 1) / per)), dim3(SU_THREADS), 0, (hipStream_t)stream, n, (const T *)p, (T *)out, inverse);
@@ -28,27 +24,25 @@ template <typename T> int exner_impl(int64_t n, const void *p, void *out, int in
 
 // Rows per workgroup (the slab): enough rows for ~`target` outputs per workgroup -- 4-5 per thread, the shape of K1's
 // 8-column slabs -- within the LDS budget, but never so many that the grid drops under four workgroups per CU (small
-// batches are latency-bound: more, smaller workgroups).  SPC_SU_TARGET overrides for A/B runs.
+// batches are latency-bound: more, smaller workgroups).
 // `max_pitch`: the largest row pitch (elements) of the launch -- the kernels address a slab with 32-bit BYTE offsets r * pitch + i
-// off uniform bases, so rb * max_pitch * 8 must stay below 2^32 whatever chose rb (the SPC_SU_RB override included): rows
+// off uniform bases, so rb * max_pitch * 8 must stay below 2^32 whatever chose rb: rows
 // padded to millions of elements get fewer rows per workgroup (round-4 advisor: the bound was a comment, not a check).
 inline int su_rows(int64_t n_rows, int n_out, size_t lds_per_row, size_t lds_fixed, size_t esize, int *stage, int64_t max_pitch, int lds_kib = 16,
                    bool fit_rounds = true)
 {
-    static const int target = [] { const char *e = getenv("SPC_SU_TARGET"); const int v = e ? atoi(e) : 1100; return v < 1 ? 1 : v; }();
-    static const int cap_env = [] { const char *e = getenv("SPC_SU_LDS_KIB"); return e ? atoi(e) : 0; }();
-    const size_t cap = (size_t)(cap_env > 0 ? cap_env : lds_kib) * 1024;
+    const int target = 1100;
+    const size_t cap = (size_t)lds_kib * 1024;
     int rb = n_out > 0 ? (target + n_out - 1) / n_out : 1;
     if (rb < 1) rb = 1;
     if (rb > 64) rb = 64;
     const int64_t most = n_rows / (4 * (int64_t)device_cus());   // >= 4 workgroups per CU (MI355X: 1024)
     if (rb > most) rb = most < 1 ? 1 : (int)most;
-    while (rb > 1 && (lds_per_row * rb + lds_fixed) * esize > cap) --rb;      // 16 KiB: >= 8 workgroups per CU (SPC_SU_LDS_KIB: A/B runs)
+    while (rb > 1 && (lds_per_row * rb + lds_fixed) * esize > cap) --rb;      // 16 KiB: >= 8 workgroups per CU
     // every wave of a workgroup runs ceil(rb n_out / 256) rounds of the output loop, the last one partly idle: among the
     // slab heights within two rows of that choice take the one that wastes the fewest lane-rounds (91 -> 160 levels: 8 rows =
     // exactly 5 rounds instead of 7 rows = 4.4 rounds paid as 5; the operators are bound by VALU issue)
-    static const bool fit = [] { const char *e = getenv("SPC_SU_FIT"); return !e || atoi(e) != 0; }();
-    if (fit && fit_rounds && n_out > 0) {
+    if (fit_rounds && n_out > 0) {
         auto waste = [&](int c) { const int64_t o = (int64_t)c * n_out, rounds = (o + SU_THREADS - 1) / SU_THREADS; return (double)(rounds * SU_THREADS - o) / (double)(rounds * SU_THREADS); };
         int best = rb;
         for (int c = rb > 2 ? rb - 2 : 1; c <= rb + 2 && c <= 64; ++c) {
@@ -58,8 +52,6 @@ inline int su_rows(int64_t n_rows, int n_out, size_t lds_per_row, size_t lds_fix
         }
         rb = best;
     }
-    static const int forced = [] { const char *e = getenv("SPC_SU_RB"); return e ? atoi(e) : 0; }();      // A/B runs
-    if (forced > 0 && forced <= 64) rb = forced;
     while (rb > 1 && (int64_t)rb * max_pitch * 8 >= ((int64_t)1 << 32)) --rb;      // (8: the widest element; output rows of searchsorted are int64)
     *stage = (lds_per_row * rb + lds_fixed) * esize <= SU_MAX_LDS;
     return rb;

@@ -15,13 +15,9 @@
 // Included by spc_hip.hip.
 #pragma once
 
-#ifndef VN_LEAF_UNROLL
-#define VN_LEAF_UNROLL 3      // K6: x 8 terms whose loads are issued together (its plane sweeps are load-latency bound)
-#endif
-
 struct VnP {
     int64_t n_cols;
-    int nij, ktot, constantT, pad;
+    int nij, ktot, constantT, pad;      // pad: explicit padding, always 0
     const double *qsat, *R, *ql_av, *qt_av, *presf, *ql_ref, *ql;
     double *qt, *thl, *beta, *a_add, *qt_std;
     int32_t *status;

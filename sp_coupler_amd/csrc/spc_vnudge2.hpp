@@ -657,9 +657,7 @@ template <int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(c
     const double *const qt = p.qt + base;
     const int ntile = (nij + ROWS - 1) / ROWS;
     double w[U];
-    const int dbg = p.pad;                               // experiments only (SPC_VN_STD_DEBUG): 1 no adds, 2 no loads
     auto load_tile = [&](int t) {                        // rows past the plane's end re-read its last row: never added
-        if (dbg & 2) return;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int ij = t * ROWS + row + 16 * u;
@@ -687,7 +685,7 @@ template <int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(c
         __syncthreads();
         for (int t = 0; t < ntile; ++t) {
             if (adder) {
-                if (row == 0 && !(dbg & 1)) {
+                if (row == 0) {
                     const int nr = (nij - t * ROWS) < ROWS ? (nij - t * ROWS) : ROWS;
                     acc = vs_sum_tile<false, ROWS>(s_tile[t & 1], lane, nr, mean, acc);
                 }

@@ -40,7 +40,6 @@ def main():
     ap.add_argument("--sputils", action="store_true", help="also time the K7 operators (sputils helpers on their own) at every size")
     ap.add_argument("--k4-cbs", default="0", help="cols_per_block settings for K4 (0 = the library's choice)")
     ap.add_argument("--vn-shapes", default="64x64x160", help="LES field extents itot x jtot x ktot, comma separated")
-    ap.add_argument("--vn-modes", default="default", help="default (LDS / streamed planes), sweep (SPC_VN_LDS=0: the sweeping kernel)")
     ap.add_argument("--vn-iters", type=int, default=20)
     a = ap.parse_args()
     nG, nL = (int(x) for x in a.levels.split(","))
@@ -111,13 +110,10 @@ def main():
             def run():
                 qt.copy_(qt0)
                 eng.variability_nudge(qt, qsat, R, prof["ql_av"], prof["qt_av"], prof["ql_ref"])
-            for mode in a.vn_modes.split(","):
-                os.environ["SPC_VN_LDS"] = "0" if mode == "sweep" else "1"
-                t = timed(run, a.vn_iters)
-                tc = timed(lambda: qt.copy_(qt0), a.vn_iters)
-                print("K6 variability nudge [%s]: %d LES of %dx%dx%d: %.0f us per launch (%.0f us of it the qt reset copy)"
-                      % (mode, ncol, it, jt, kt, t, tc), flush=True)
-            os.environ.pop("SPC_VN_LDS", None)
+            t = timed(run, a.vn_iters)
+            tc = timed(lambda: qt.copy_(qt0), a.vn_iters)
+            print("K6 variability nudge: %d LES of %dx%dx%d: %.0f us per launch (%.0f us of it the qt reset copy)"
+                  % (ncol, it, jt, kt, t, tc), flush=True)
             del qt0, qsat, qt, R, prof
             eng._vn_work = None
             torch.cuda.empty_cache()
