@@ -18,6 +18,7 @@
  *                           sputils.interp_c / integral   splib/sputils.py:94-189 (conservative=1)
  *   spc_surface_fluxes_* <- spcpl.convert_surface_fluxes  splib/spcpl.py:136-167 (columns without LES)
  *   spc_variability_nudge_f64 <- spcpl.variability_nudge  splib/spcpl.py:613-744 (qt_forcing == 'variance')
+ *   spc_variability_nudge_f32    (the same on float32 fields)
  *   spc_diagnostics_*    <- spifs.nc diagnostics          splib/spcpl.py:176,214-215,408-409;
  *                           spcpl.output_column_conversion splib/spcpl.py:251-267
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
@@ -163,7 +164,7 @@ int spc_surface_fluxes_f32(int64_t n, const void *Ph_s, const void *T_s, const v
                            const void *SHflux, const void *TSflux, void *wthl, void *wqt, void *stream);
 
 /* ---- variability nudge (qt_forcing == 'variance'): spcpl.variability_nudge, splib/spcpl.py:613-744 ------------ */
-/* 3-D LES fields in the reference's layout [n_cols][itot][jtot][ktot] (k fastest), float64.  For every level the
+/* 3-D LES fields in the reference's layout [n_cols][itot][jtot][ktot] (k fastest), float64 (float32: below).  For every level the
  * kernel finds beta (multiplicative, brentq on [0,5]) or a (additive noise a*R, brentq on [0,5]) such that the plane
  * mean of max(qt' - qsat, 0) equals ql_ref[k], updates qt in place (and thl with constantT), and returns beta, a,
  * qt.std(axis=(0,1)) and a status word per (column, level):
@@ -175,7 +176,13 @@ int spc_surface_fluxes_f32(int64_t n, const void *Ph_s, const void *T_s, const v
  * LDS, e.g. 64 x 64, 90 x 90) are solved from the CU's LDS and larger ones (96 x 96, 128 x 128, 256 x 256 ...) by one
  * workgroup per level streaming its contiguous transposed planes; the update and qt.std are two further launches.
  * Without the workspace planes that fit the LDS are loaded strided (slower) and larger ones are refused
- * (SPC_ERR_INVALID_ARGUMENT); results are bit-identical on every path.                                            */
+ * (SPC_ERR_INVALID_ARGUMENT); results are bit-identical on every path.
+ * spc_variability_nudge_f32: the same struct for float32 fields.  qt, qsat, thl, ql, ql_av, qt_av, presf, ql_ref and
+ * qt_std point to float; R, beta and a_add stay double; status is int32_t.  It equals the reference's lines evaluated by
+ * NumPy (2.x promotion rules) on float32 arrays: the multiplicative plane sums in float32 (brentq's iterate rounded to
+ * float), the additive ones in float64 (a*R is float64), the qt increments in float64 rounded back to float, the constantT
+ * correction and qt.std in float32.  beta, a, status, qt and qt_std are bit-identical to that; thl agrees to a few float
+ * ulp (exner's powf).  Float planes take half the LDS: planes of up to ~18 000 points (128 x 128) are solved from LDS. */
 typedef struct spc_vnudge_args {
     int64_t n_cols;
     int32_t itot, jtot, ktot;
@@ -194,6 +201,7 @@ typedef struct spc_vnudge_args {
 } spc_vnudge_args;
 
 int spc_variability_nudge_f64(const spc_vnudge_args *args, void *stream);
+int spc_variability_nudge_f32(const spc_vnudge_args *args, void *stream);
 
 /* ---- the helpers of splib/sputils.py as standalone batched operators (kernel family K7) ---------------------- */
 /* The fused kernels above contain this arithmetic already; these entry points serve callers that use a helper on its
@@ -287,6 +295,8 @@ int spc_describe_launch(const spc_dims *dims, int pass, int flags, int elem_size
  * qsat transposed to contiguous planes; required for planes of more than ~9 000 points); negative spc_status on bad
  * extents. */
 int64_t spc_vnudge_workspace_bytes(int64_t n_cols, int32_t itot, int32_t jtot, int32_t ktot);
+/* The same for spc_variability_nudge_f32 (float planes: n_cols*2*itot*jtot*ktot*4, half the f64 value). */
+int64_t spc_vnudge_workspace_bytes_f32(int64_t n_cols, int32_t itot, int32_t jtot, int32_t ktot);
 
 #ifdef __cplusplus
 }

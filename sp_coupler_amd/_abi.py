@@ -99,6 +99,7 @@ PROTOTYPES = {
     "spc_surface_fluxes_f64": (ctypes.c_int, [c_int64] + [c_void_p] * 9),
     "spc_surface_fluxes_f32": (ctypes.c_int, [c_int64] + [c_void_p] * 9),
     "spc_variability_nudge_f64": (ctypes.c_int, [ctypes.POINTER(VnudgeArgs), c_void_p]),
+    "spc_variability_nudge_f32": (ctypes.c_int, [ctypes.POINTER(VnudgeArgs), c_void_p]),
     "spc_exner_f64": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
     "spc_exner_f32": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
     "spc_interp_f64": (ctypes.c_int, [ctypes.POINTER(InterpArgs), c_void_p]),
@@ -116,6 +117,7 @@ PROTOTYPES = {
     "spc_describe_launch": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
                                            ctypes.c_int]),
     "spc_vnudge_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    "spc_vnudge_workspace_bytes_f32": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
 }
 
 _lib = None

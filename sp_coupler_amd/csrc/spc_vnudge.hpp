@@ -8,20 +8,28 @@
 // accumulators, halves split at multiples of 8, chunks of 8192, result = 0.0 + chunk sums) and the root finder is
 // scipy's brentq.c restated statement by statement (oracle/vnudge_oracle.py holds the same restatements and checks
 // them against scipy / numpy bit for bit), so beta, a and the updated qt are BIT-identical to the NumPy/SciPy
-// evaluation; thl (through exner's pow) agrees to a few ulp.  This file: the numpy-ordered sums (vn_leaf, vn_npsum --
-// also used by K4), brentq as a resumable step function, and the host-side flattening of numpy's pairwise tree; the
+// evaluation; thl (through exner's pow) agrees to a few ulp.  The float instantiations (spc_variability_nudge_f32) are
+// bit-identical to the same lines evaluated by NumPy on float32 arrays.
+// This file: the numpy-ordered sums (vn_leaf, vn_npsum -- also used by K4), brentq as a resumable step function, and the host-side flattening of numpy's pairwise tree; the
 // kernels are in spc_vnudge2.hpp.  (Rounds 1-2 also had a kernel that swept the planes from memory in every evaluation;
 // k_vnudge_solve<true> replaced it: 7-9 x faster on 128 x 128 and 256 x 256 planes, profiles/r03_k6.log.)
 // Included by spc_hip.hip.
 #pragma once
 
-struct VnP {
+// T: the type of the LES fields and profiles (double, or float for spc_variability_nudge_f32); the noise plane R and the
+// roots beta / a are double in both
+template <typename T> struct VnPT {
     int64_t n_cols;
     int nij, ktot, constantT, pad;      // pad: explicit padding, always 0
-    const double *qsat, *R, *ql_av, *qt_av, *presf, *ql_ref, *ql;
-    double *qt, *thl, *beta, *a_add, *qt_std;
+    const T *qsat;
+    const double *R;
+    const T *ql_av, *qt_av, *presf, *ql_ref, *ql;
+    T *qt, *thl;
+    double *beta, *a_add;
+    T *qt_std;
     int32_t *status;
 };
+using VnP = VnPT<double>;
 
 enum { VN_NONE = 0, VN_MULT = 1, VN_UNSAT = 2, VN_ADD = 4, VN_ADD_SKIPPED = 8, VN_NO_BRACKET = 16,
        VN_ERR_SIGN = 256, VN_ERR_CONV = 512 };

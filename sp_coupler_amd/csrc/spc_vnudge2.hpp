@@ -12,6 +12,11 @@
 // workspace instead, one workgroup per level (k_vnudge_solve<true>).  The solve leaves beta / a and the apply code in
 // `status`; k_vnudge_update rewrites qt (thl with constantT) elementwise and k_vnudge_std takes qt.std(axis=(0,1)) in
 // numpy's sequential order.  Bit-identical to the NumPy / SciPy oracle on every path (tests/test_vnudge.py).
+// Every kernel is templated on the field type T.  T = float (spc_variability_nudge_f32) evaluates the reference's lines as
+// NumPy does on float32 arrays (tests/vnudge_f32_ref.py): the multiplicative sum in float (float terms, float accumulators,
+// float leaf sums and tree), the additive one in double over widened planes (a R is float64), brentq in double on the widened
+// value.  The planes take half the LDS: planes of up to ~18 000 points (128 x 128) stay LDS-resident; where double planes fit
+// too, a float launch keeps the double launch's KT (spc_hip.hip: vnudge_impl).
 #pragma once
 
 constexpr int VN2_THREADS = 512;
@@ -20,7 +25,12 @@ enum { VN2_APPLY_MULT = 1 << 20, VN2_APPLY_ADD = 1 << 21, VN2_TOUCHED = 1 << 22,
 
 // LDS position of plane element e: 8 doubles of skew per 128 elements, so that the 8 leaf groups of a wave (leaf starts
 // 128 elements = 1 KiB apart, i.e. on the SAME banks) read 8 different 64-B bank ranges (measured without it: 8 us per
-// evaluation round, LDS-conflict bound)
+// evaluation round, LDS-conflict bound).
+// Float planes, derived for ds_read_b32 (cdna_hip_programming.md §LDS: bank (a / 4) % 32, conflicts inside a 32-lane half):
+// a half holds 4 leaf groups, each reading 8 consecutive floats = 8 banks; unskewed, leaf starts 128 floats = 512 B apart
+// are all = 0 mod 128 B, i.e. the 4 groups hit banks 0-7 (4-way).  Shifting block b of 128 elements by 8 b dwords puts the 4
+// groups of a half on banks 0-7, 8-15, 16-23, 24-31: conflict-free.  The skew is again 8 ELEMENTS per 128 (32 B instead of
+// 64 B), so both element types use this function.
 __device__ __forceinline__ int vn2_pos(int e) { return e + ((e >> 7) << 3); }
 __host__ __device__ inline int vn2_plane(int nij) { return nij + ((nij >> 7) << 3) + 8; }
 
@@ -51,32 +61,33 @@ __host__ inline int vn_tree_balanced(int nleaf, const unsigned short *pl, const 
     return 1;
 }
 
-struct Vn2P {
-    VnP p;
+template <typename T> struct Vn2PT {
+    VnPT<T> p;
     int kt, log2_kt, tiles, gpc, tg;    // levels per workgroup, tiles per column, line groups per column, tiles per group
     int64_t groups;
     int nleaf_max;
-    const double *work;                  // planes transposed to [col][field][k][ij] by k_vnudge_transpose, or NULL
+    const T *work;                       // planes transposed to [col][field][k][ij] by k_vnudge_transpose, or NULL
     Vn2Tables tab;
 };
+using Vn2P = Vn2PT<double>;
 
 // K6t: qt and qsat of every column from the reference's [ij][k] order into contiguous planes [col][field][k][ij] of the
 // caller's workspace: the solve then fills its LDS with coalesced loads (128 KiB = 1 024 line requests) instead of one
 // 128-B line request per (ij, field) for 16 useful bytes (8 192 requests, 90 us per workgroup at the per-CU limit of
 // outstanding requests).  Tile = 64 rows x 16 levels through LDS; reads and writes are whole 128-B segments.
-__global__ __launch_bounds__(256) void k_vnudge_transpose(const VnP p, double *work)
+template <typename T> __global__ __launch_bounds__(256) void k_vnudge_transpose(const VnPT<T> p, T *work)
 {
-    __shared__ double s_t[16][65];
+    __shared__ T s_t[16][65];
     const int lane = threadIdx.x & 15, row = threadIdx.x >> 4;
     const int ij0 = blockIdx.x * 64, k0 = blockIdx.y * 16, nij = p.nij, ktot = p.ktot;
     const int64_t col = blockIdx.z >> 1;
     const int field = blockIdx.z & 1;
-    const double *const src = (field ? p.qsat : (const double *)p.qt) + col * (int64_t)nij * ktot;
-    double *const dst = work + (col * 2 + field) * (int64_t)ktot * nij;
+    const T *const src = (field ? p.qsat : (const T *)p.qt) + col * (int64_t)nij * ktot;
+    T *const dst = work + (col * 2 + field) * (int64_t)ktot * nij;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int ij = ij0 + row + 16 * u, k = k0 + lane;
-        s_t[lane][row + 16 * u] = (ij < nij && k < ktot) ? src[(int64_t)ij * ktot + k] : 0.0;
+        s_t[lane][row + 16 * u] = (ij < nij && k < ktot) ? src[(int64_t)ij * ktot + k] : T(0);
     }
     __syncthreads();
 #pragma unroll
@@ -109,6 +120,11 @@ template <int N> __device__ __forceinline__ double vn_row_shl(double v)
     hi = __builtin_amdgcn_update_dpp(hi, hi, 0x100 | N, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
+template <int N> __device__ __forceinline__ float vn_row_shl(float v)
+{
+    const int b = __float_as_int(v);
+    return __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0x100 | N, 0xf, 0xf, false));
+}
 
 // GLOBAL = false: the planes of the workgroup's KT levels are copied into LDS once and every evaluation runs from there
 // (planes of up to ~9 000 points).  GLOBAL = true: planes too large for the LDS (128 x 128 and up -- ordinary DALES sizes)
@@ -118,9 +134,10 @@ template <int N> __device__ __forceinline__ double vn_row_shl(double v)
 // RCACHE (LDS form only, planes of <= 8192 points with one leaf per 8-lane group -- 64 x 64 and smaller): every lane keeps its
 // share of the noise plane R in registers (32 more VGPRs; an instantiation of its own, so that the general form keeps its
 // registers and schedule: with the cache compiled into it the 92 x 92 planes ran 12-18 % slower, profiles/r05_k6_stamps.log).
-template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THREADS, RCACHE ? 2 : 4) void k_vnudge_solve(const Vn2P q)
+template <typename T, bool GLOBAL, bool RCACHE = false>
+__global__ __launch_bounds__(VN2_THREADS, RCACHE ? 2 : 4) void k_vnudge_solve(const Vn2PT<T> q)
 {
-    const VnP &p = q.p;
+    const VnPT<T> &p = q.p;
     extern __shared__ __align__(16) unsigned char vn2_smem[];
     __shared__ Vn2Tables s_tab;
     __shared__ int s_flag;
@@ -148,22 +165,22 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
     const bool valid = k < ktot;
     const bool own = tl == 0;
     const int npl = vn2_plane(nij);                                            // skewed plane length
-    double *const s_qt = reinterpret_cast<double *>(vn2_smem);               // [KT][npl]   (GLOBAL: no planes in LDS)
-    double *const s_qs = s_qt + (GLOBAL ? 0 : (size_t)KT * npl);                // [KT][npl]
-    double *const s_leaf = s_qs + (GLOBAL ? 0 : (size_t)KT * npl);              // [KT][nleaf_max]
-    double *const s_part = s_leaf + (size_t)KT * q.nleaf_max;                  // [VN2_THREADS] argmax values
+    T *const s_qt = reinterpret_cast<T *>(vn2_smem);                         // [KT][npl]   (GLOBAL: no planes in LDS)
+    T *const s_qs = s_qt + (GLOBAL ? 0 : (size_t)KT * npl);                     // [KT][npl]
+    double *const s_leaf = reinterpret_cast<double *>(s_qs + (GLOBAL ? 0 : (size_t)KT * npl));   // [KT][nleaf_max] (8-B slots)
+    T *const s_part = reinterpret_cast<T *>(s_leaf + (size_t)KT * q.nleaf_max);  // [VN2_THREADS] argmax values
     int *const s_parti = reinterpret_cast<int *>(s_part + VN2_THREADS);        // [VN2_THREADS] argmax indices
     double *const my_leaf = s_leaf + (size_t)kl * q.nleaf_max;
     const int kq_ = (k < ktot) ? k : ktot - 1;
     // this level's planes: LDS copies (skewed, vn2_pos) or the contiguous planes of the transposed workspace
-    const double *const my_qt = GLOBAL ? q.work + ((col * 2 + 0) * (int64_t)ktot + kq_) * nij : s_qt + (size_t)kl * npl;
-    const double *const my_qs = GLOBAL ? q.work + ((col * 2 + 1) * (int64_t)ktot + kq_) * nij : s_qs + (size_t)kl * npl;
+    const T *const my_qt = GLOBAL ? q.work + ((col * 2 + 0) * (int64_t)ktot + kq_) * nij : s_qt + (size_t)kl * npl;
+    const T *const my_qs = GLOBAL ? q.work + ((col * 2 + 1) * (int64_t)ktot + kq_) * nij : s_qs + (size_t)kl * npl;
     auto POS = [](int e) { return GLOBAL ? e : vn2_pos(e); };
 
     {   // the host-built tree tables: argument block -> LDS, one 4-byte word per lane
         static_assert(sizeof(Vn2Tables) % 4 == 0, "Vn2Tables is copied by words");
         const unsigned __attribute__((address_space(4))) *const src = (const unsigned __attribute__((address_space(4))) *)(
-            (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(Vn2P, tab));
+            (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(Vn2PT<T>, tab));
         unsigned *const dstw = reinterpret_cast<unsigned *>(&s_tab);
         for (int i = threadIdx.x; i < (int)(sizeof(Vn2Tables) / 4); i += blockDim.x) dstw[i] = src[i];
     }
@@ -172,9 +189,9 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
     if constexpr (GLOBAL) {
     } else if (q.work) {                            // transposed workspace: every level's group streams its own planes
         const int kq = valid ? k : ktot - 1;
-        const double *const wq = q.work + ((col * 2 + 0) * (int64_t)ktot + kq) * nij;
-        const double *const ws = q.work + ((col * 2 + 1) * (int64_t)ktot + kq) * nij;
-        double *const dq = s_qt + (size_t)kl * npl, *const ds = s_qs + (size_t)kl * npl;
+        const T *const wq = q.work + ((col * 2 + 0) * (int64_t)ktot + kq) * nij;
+        const T *const ws = q.work + ((col * 2 + 1) * (int64_t)ktot + kq) * nij;
+        T *const dq = s_qt + (size_t)kl * npl, *const ds = s_qs + (size_t)kl * npl;
 #pragma unroll 4
         for (int ij = tl; ij < nij; ij += TL) {
             dq[vn2_pos(ij)] = wq[ij];
@@ -195,7 +212,7 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
     const int kk = valid ? k : ktot - 1;
     const int64_t lev = col * ktot + kk;
     const double *const R = p.R + col * (int64_t)nij;
-    const double qt_av = p.qt_av[lev], ql_ref = p.ql_ref[lev], ql_av = p.ql_av[lev];
+    const T qt_av = p.qt_av[lev], ql_ref = p.ql_ref[lev], ql_av = p.ql_av[lev];
 
     // ---- per-level state (lane 0 of each level's group) ----------------------------------------------------------------
     int stage = VS_DONE, st = VN_NONE, err = 0, apply = 0;
@@ -204,6 +221,7 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
     VnBrent br = {};
     if (own) {
         if (valid) {
+            // (float ql_ref: the double compare equals numpy's float32 one, whose weak 1e-9 rounds DOWN to float)
             if (ql_ref > SPC_MUT(20, 1e-6, 1e-9)) { stage = VS_M0; touched = true; }  // spcpl.py:665
             else if (ql_av > ql_ref) { want_argmax = true; touched = true; }         // spcpl.py:679
         }
@@ -217,26 +235,26 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
     // ---- "barely unsaturated" branch (spcpl.py:679-695): numpy.argmax(qt - qsat), first maximum, a NaN wins -------------
     if (s_flag) {
         const int seg = (nij + TL - 1) / TL, lo = tl * seg, hi = (lo + seg) < nij ? (lo + seg) : nij;
-        double bv = 0.0;
+        T bv = T(0);
         int bi = -1;
         if (s_mode[kl] == 3 && lo < hi) {
             bi = lo; bv = my_qt[POS(lo)] - my_qs[POS(lo)];
             for (int ij = lo + 1; ij < hi && !(bv != bv); ++ij) {
-                const double v = my_qt[POS(ij)] - my_qs[POS(ij)];
+                const T v = my_qt[POS(ij)] - my_qs[POS(ij)];
                 if (v > bv || v != v) { bv = v; bi = ij; }
             }
         }
         s_part[tid] = bv; s_parti[tid] = bi;
         __syncthreads();
         if (own && want_argmax) {
-            double best = s_part[tid];
+            T best = s_part[tid];
             int idx = s_parti[tid];
             for (int w = 1; w < TL && !(best != best); ++w) {
                 const int qi = s_parti[tid + w];
-                const double v = s_part[tid + w];
+                const T v = s_part[tid + w];
                 if (qi >= 0 && (v > best || v != v)) { best = v; idx = qi; }
             }
-            beta = (my_qs[POS(idx)] - qt_av) / (my_qt[POS(idx)] - qt_av);          // spcpl.py:683
+            beta = (my_qs[POS(idx)] - qt_av) / (my_qt[POS(idx)] - qt_av);          // spcpl.py:683 (float: IEEE quotient)
             if (beta < 0) beta = 1.0;                                                // spcpl.py:692-695
             st = VN_UNSAT;
         }
@@ -258,7 +276,6 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
     // dependency rounds -- LDS operations of one wave execute in order, so no barrier between them -- and its lane 0 runs
     // the level's state machine on the result.
     const int CW = TL < 64 ? TL : 64;
-    volatile double *const vleaf = my_leaf;
     // this lane's steps of the combine program are the same in every evaluation round: read them from the LDS tables ONCE
     // (up to two steps per lane and chunk shape: trees of <= 2 CW + 1 leaves, i.e. every plane the LDS path takes and the
     // 128-leaf chunks of the streamed path); taller trees walk the tables
@@ -337,17 +354,20 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
             const int shape = (c0 + cn < nij) ? 0 : 1;
             const int nleaf = s_nleaf[shape];
             // one leaf per 8-lane group: lane j carries numpy's accumulator r[j]; `term` reads the planes from LDS
+            // (the accumulator type A is the term's: double, or float for the multiplicative sum of float planes)
             auto leaves = [&](auto term) {
+                using A = decltype(term(0));
+                A *const leaf_a = reinterpret_cast<A *>(my_leaf);
                 for (int li = grp; li < nleaf; li += ngrp) {        // uniform inside every 8-lane group
                     const int lo = (int)s_lo[shape][li], n = (int)s_n[shape][li];
-                    double res;
+                    A res;
                     if (n < 8) {
-                        res = 0.0;
+                        res = A(0);
                         if (acc == 0)
                             for (int i = 0; i < n; ++i) res += term(lo + i);
                     } else {
                         const int cnt = n >> 3, n8 = cnt << 3;
-                        double r = term(lo + acc);
+                        A r = term(lo + acc);
                         if constexpr (GLOBAL) {
 #pragma unroll 15
                             for (int i = 1; i < cnt; ++i) r += term(lo + 8 * i + acc);
@@ -362,7 +382,7 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
                         if (acc == 0)
                             for (int i = n8; i < n; ++i) res += term(lo + i);
                     }
-                    if (acc == 0) my_leaf[li] = res;
+                    if (acc == 0) leaf_a[li] = res;
                 }
             };
             // RCACHE, a FULL leaf (128 elements, 16 per lane -- every leaf of a 64 x 64 plane): all 32 LDS reads of the lane are
@@ -373,44 +393,47 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
             const bool fast_leaf = RCACHE && r_cached && grp < nleaf && (int)s_n[shape][grp] == 8 * RC && ((int)s_lo[shape][grp] & 127) == 0;
             auto full_leaf = [&](auto term) {
                 const int e0 = POS((int)s_lo[shape][grp] + acc);
-                const double *const pa = my_qt + e0, *const pb = my_qs + e0;
-                double qa[RC], qb[RC];
+                const T *const pa = my_qt + e0, *const pb = my_qs + e0;
+                T qa[RC], qb[RC];
 #pragma unroll
                 for (int i = 0; i < RC; ++i) {
                     qa[i] = pa[8 * i];
                     qb[i] = pb[8 * i];
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                double r = term(0, qa[0], qb[0]);
+                auto r = term(0, qa[0], qb[0]);
 #pragma unroll
                 for (int i = 1; i < RC; ++i) r += term(i, qa[i], qb[i]);
                 r = r + __shfl_down(r, 1, 8);
                 r = r + __shfl_down(r, 2, 8);
                 r = r + __shfl_down(r, 4, 8);
-                if (acc == 0) my_leaf[grp] = r;
+                if (acc == 0) reinterpret_cast<decltype(r) *>(my_leaf)[grp] = r;
             };
+            // multiplicative terms in the field type (brentq's iterate rounded to it: a weak Python float in NumPy), additive
+            // ones in double (a R is float64: the planes are widened)
+            const T xm = (T)x;
             if (fast_leaf && mode == 1)
-                full_leaf([&](int, double a_, double b_) {
-                    const double t = ((x * (a_ - qt_av)) + qt_av) - b_;
-                    return (t >= 0.0 || t != t) ? t : 0.0;
+                full_leaf([&](int, T a_, T b_) {
+                    const T t = ((xm * (a_ - qt_av)) + qt_av) - b_;
+                    return (t >= T(0) || t != t) ? t : T(0);
                 });
             else if (fast_leaf && mode == 2)
-                full_leaf([&](int i, double a_, double b_) {
-                    const double t = (a_ + (x * Rreg[i])) - b_;
+                full_leaf([&](int i, T a_, T b_) {
+                    const double t = ((double)a_ + (x * Rreg[i])) - (double)b_;
                     return (t >= 0.0 || t != t) ? t : 0.0;
                 });
             else if (mode == 1)
                 leaves([&](int ij) {
                     const int e = POS(c0 + ij);
-                    const double t = ((x * (my_qt[e] - qt_av)) + qt_av) - my_qs[e];
-                    return (t >= 0.0 || t != t) ? t : 0.0;                           // numpy.maximum(t, 0)
+                    const T t = ((xm * (my_qt[e] - qt_av)) + qt_av) - my_qs[e];
+                    return (t >= T(0) || t != t) ? t : T(0);                         // numpy.maximum(t, 0)
                 });
             else if (RCACHE && mode == 2 && r_cached) {                // (one chunk, one leaf per group: li = grp)
                 if (grp < nleaf) {
                     const int lo = (int)s_lo[shape][grp], n = (int)s_n[shape][grp];
                     const auto term_g = [&](int ij) {
                         const int e = POS(ij);
-                        const double t = (my_qt[e] + (x * R[ij])) - my_qs[e];
+                        const double t = ((double)my_qt[e] + (x * R[ij])) - (double)my_qs[e];
                         return (t >= 0.0 || t != t) ? t : 0.0;
                     };
                     double res;
@@ -422,7 +445,7 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
                         const int cnt = n >> 3, n8 = cnt << 3;
                         const auto term_r = [&](int i) {
                             const int e = POS(lo + 8 * i + acc);
-                            const double t = (my_qt[e] + (x * Rreg[i])) - my_qs[e];
+                            const double t = ((double)my_qt[e] + (x * Rreg[i])) - (double)my_qs[e];
                             return (t >= 0.0 || t != t) ? t : 0.0;
                         };
                         double r = term_r(0);                       // (a short leaf: the last one of a plane that is no multiple of 128)
@@ -441,7 +464,7 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
             } else if (mode == 2)
                 leaves([&](int ij) {
                     const int e = POS(c0 + ij);
-                    const double t = (my_qt[e] + (x * R[c0 + ij])) - my_qs[e];
+                    const double t = ((double)my_qt[e] + (x * R[c0 + ij])) - (double)my_qs[e];
                     return (t >= 0.0 || t != t) ? t : 0.0;
                 });
 #ifdef SPC_STAMPS
@@ -449,43 +472,57 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
 #endif
             __syncthreads();
             K6_STAMP(2);                                            // barrier: every wave's leaves are in LDS
-            if (tl < CW && mode != 0 && s_tab.balanced[shape] && nleaf <= CW) {      // the balanced tree: in registers (vn_tree_balanced);
-                double v = tl < nleaf ? my_leaf[tl] : 0.0;                            // lanes tl .. tl + nleaf - 1 are this level's
-                // lane i + lane i + d: inside a row of 16 lanes by DPP row shifts (a register move), beyond by ds_bpermute
-                if (nleaf > 1) v = v + vn_row_shl<1>(v);
-                if (nleaf > 2) v = v + vn_row_shl<2>(v);
-                if (nleaf > 4) v = v + vn_row_shl<4>(v);
-                if (nleaf > 8) v = v + vn_row_shl<8>(v);
-                for (int sft = 16; sft < nleaf; sft <<= 1) v = v + __shfl_down(v, sft);
-                if (own) total += v;
-            } else if (tl < CW && mode != 0) {                      // numpy's tree, one dependency round at a time
-                const int nround = s_nround[shape];
-                if (shape ? tq_fast[1] : tq_fast[0]) {
-                    const int r0 = shape ? tq_rnd[1][0] : tq_rnd[0][0], r1 = shape ? tq_rnd[1][1] : tq_rnd[0][1];
-                    const int l0 = shape ? tq_l[1][0] : tq_l[0][0], l1 = shape ? tq_l[1][1] : tq_l[0][1];
-                    const int p0 = shape ? tq_r[1][0] : tq_r[0][0], p1 = shape ? tq_r[1][1] : tq_r[0][1];
-                    for (int rd = 1; rd <= nround; ++rd) {
-                        if (r0 == rd) vleaf[l0] = vleaf[l0] + vleaf[p0];
-                        if (r1 == rd) vleaf[l1] = vleaf[l1] + vleaf[p1];
-                        __builtin_amdgcn_wave_barrier();
+            // the chunk's leaf sums combined in the accumulator type A; the chunk total joins `total` in A (numpy's float32
+            // sum adds its chunk sums in float32; a float total is exact in the double variable)
+            auto combine = [&](auto zero) {
+                using A = decltype(zero);
+                A *const leaf_a = reinterpret_cast<A *>(my_leaf);
+                volatile A *const vleaf = leaf_a;
+                if (tl < CW && mode != 0 && s_tab.balanced[shape] && nleaf <= CW) {      // the balanced tree: in registers (vn_tree_balanced);
+                    A v = tl < nleaf ? leaf_a[tl] : A(0);                                 // lanes tl .. tl + nleaf - 1 are this level's
+                    // lane i + lane i + d: inside a row of 16 lanes by DPP row shifts (a register move), beyond by ds_bpermute
+                    if (nleaf > 1) v = v + vn_row_shl<1>(v);
+                    if (nleaf > 2) v = v + vn_row_shl<2>(v);
+                    if (nleaf > 4) v = v + vn_row_shl<4>(v);
+                    if (nleaf > 8) v = v + vn_row_shl<8>(v);
+                    for (int sft = 16; sft < nleaf; sft <<= 1) v = v + __shfl_down(v, sft);
+                    if (own) total = (double)((A)total + v);
+                } else if (tl < CW && mode != 0) {                      // numpy's tree, one dependency round at a time
+                    const int nround = s_nround[shape];
+                    if (shape ? tq_fast[1] : tq_fast[0]) {
+                        const int r0 = shape ? tq_rnd[1][0] : tq_rnd[0][0], r1 = shape ? tq_rnd[1][1] : tq_rnd[0][1];
+                        const int l0 = shape ? tq_l[1][0] : tq_l[0][0], l1 = shape ? tq_l[1][1] : tq_l[0][1];
+                        const int p0 = shape ? tq_r[1][0] : tq_r[0][0], p1 = shape ? tq_r[1][1] : tq_r[0][1];
+                        for (int rd = 1; rd <= nround; ++rd) {
+                            if (r0 == rd) vleaf[l0] = vleaf[l0] + vleaf[p0];
+                            if (r1 == rd) vleaf[l1] = vleaf[l1] + vleaf[p1];
+                            __builtin_amdgcn_wave_barrier();
+                        }
+                    } else {
+                        for (int rd = 1; rd <= nround; ++rd) {
+                            for (int t = tl; t + 1 < nleaf; t += CW)
+                                if (s_rnd[shape][t] == rd) {
+                                    const int l = s_pl[shape][t], r = s_pr[shape][t];
+                                    vleaf[l] = vleaf[l] + vleaf[r];
+                                }
+                            __builtin_amdgcn_wave_barrier();
+                        }
                     }
-                } else {
-                    for (int rd = 1; rd <= nround; ++rd) {
-                        for (int t = tl; t + 1 < nleaf; t += CW)
-                            if (s_rnd[shape][t] == rd) {
-                                const int l = s_pl[shape][t], r = s_pr[shape][t];
-                                vleaf[l] = vleaf[l] + vleaf[r];
-                            }
-                        __builtin_amdgcn_wave_barrier();
-                    }
+                    if (own) total = (double)((A)total + vleaf[0]);
                 }
-                if (own) total += vleaf[0];
-            }
+            };
+            if constexpr (std::is_same<T, double>::value) combine(0.0);
+            else if (mode == 1) combine(T(0));
+            else combine(0.0);
             if (c0 + 8192 < nij) __syncthreads();                   // the next chunk's leaves reuse the slots
         }
         K6_STAMP(3);                                                // tree combine (dependency rounds of one wave)
         if (own && stage != VS_DONE) {
-            const double f = total / (double)nij - ql_ref;                           // spcpl.py:646-648 / 653-656
+            // spcpl.py:646-648 / 653-656; float fields: the multiplicative difference in float (/ the weak int itot * jtot, -
+            // ql_ref[k]), the additive one in double
+            double f;
+            if constexpr (std::is_same<T, double>::value) f = total / (double)nij - ql_ref;
+            else f = mode == 1 ? (double)((T)total / (T)nij - ql_ref) : total / (double)nij - (double)ql_ref;
             double root = 0.0;
             int rc = 0;
             switch (stage) {
@@ -543,14 +580,16 @@ template <bool GLOBAL, bool RCACHE = false> __global__ __launch_bounds__(VN2_THR
 // K6b: qt (and thl with constantT) of every touched level (spcpl.py:716-733).  Elementwise, no order constraint: as many
 // workgroups as the data allows (a workgroup takes VU_ROWS (i, j) rows of one column; 32 lanes along k, the fastest
 // index of the reference's [ij][k] layout, 8 rows at a time), levels that need nothing are neither read nor written.
+// Float fields: the increments (beta - 1) (qt - qt_av) and a R are float64 (beta[k] is a numpy.float64 scalar, R a float64
+// array), so qt is widened, incremented in double and rounded back; qt - qt_av, the constantT terms and exner are float.
 constexpr int VU_ROWS = 64;
-__global__ __launch_bounds__(256) void k_vnudge_update(const VnP p)
+template <typename T> __global__ __launch_bounds__(256) void k_vnudge_update(const VnPT<T> p)
 {
     extern __shared__ __align__(16) unsigned char vu_smem[];
     const int ktot = p.ktot, nij = p.nij, tid = threadIdx.x;
     double *const s_coef = reinterpret_cast<double *>(vu_smem);          // [ktot] beta - 1 or a
-    double *const s_av = s_coef + ktot;                                    // [ktot] qt_av
-    double *const s_tc = s_av + ktot;                                      // [ktot] -rlv / (cp exner(presf)), constantT
+    T *const s_av = reinterpret_cast<T *>(s_coef + ktot);                  // [ktot] qt_av
+    T *const s_tc = s_av + ktot;                                           // [ktot] -rlv / (cp exner(presf)), constantT
     int *const s_ap = reinterpret_cast<int *>(s_tc + ktot);               // [ktot] 0 nothing, 1 multiplicative, 2 additive, +4 thl
     __shared__ int s_any;
     const int64_t col = blockIdx.y;
@@ -563,7 +602,8 @@ __global__ __launch_bounds__(256) void k_vnudge_update(const VnP p)
         const bool th = p.constantT && (stv & VN2_TOUCHED);
         s_coef[k] = ap == 1 ? p.beta[lev] - 1 : p.a_add[lev];
         s_av[k] = p.qt_av[lev];
-        s_tc[k] = th ? SPC_MUT(19, K<double>::rlv, -K<double>::rlv) / (K<double>::cp * spc_pow(div_pref0(p.presf[lev]), K<double>::rd / K<double>::cp)) : 0.0;   // spcpl.py:731
+        // (float: rd / cp in float equals NumPy's float32(287.04 / 1004.), the weak Python quotient)
+        s_tc[k] = th ? SPC_MUT(19, K<T>::rlv, -K<T>::rlv) / (K<T>::cp * spc_pow(div_pref0(p.presf[lev]), K<T>::rd / K<T>::cp)) : T(0);   // spcpl.py:731
         s_ap[k] = ap | (th ? 4 : 0);
         if (ap | (th ? 4 : 0)) s_any = 1;
     }
@@ -576,16 +616,17 @@ __global__ __launch_bounds__(256) void k_vnudge_update(const VnP p)
     for (int k = kq; k < ktot; k += 32) {
         const int ap = s_ap[k];
         if (!ap) continue;
-        const double coef = s_coef[k], qt_av = s_av[k], tc = s_tc[k];
+        const double coef = s_coef[k];
+        const T qt_av = s_av[k], tc = s_tc[k];
 #pragma unroll 4
         for (int ij = ij0 + rq; ij < ij1; ij += 8) {
             const int64_t g = base + (int64_t)ij * ktot + k;
-            double v = p.qt[g];
-            if ((ap & 3) == 1) { v = v + coef * SPC_MUT(18, v, (v - qt_av)); p.qt[g] = v; } // spcpl.py:724-725
-            else if ((ap & 3) == 2) { v = SPC_MUT(21, v - coef * R[ij], v + coef * R[ij]); p.qt[g] = v; }   // spcpl.py:716-719
+            T v = p.qt[g];
+            if ((ap & 3) == 1) { v = (T)((double)v + coef * (double)SPC_MUT(18, v, (v - qt_av))); p.qt[g] = v; } // spcpl.py:724-725
+            else if ((ap & 3) == 2) { v = (T)SPC_MUT(21, (double)v - coef * R[ij], (double)v + coef * R[ij]); p.qt[g] = v; }   // spcpl.py:716-719
             if (ap & 4) {                                                                   // spcpl.py:726-733
-                const double tt = v - p.qsat[g];
-                const double ql_target = (tt >= 0.0 || tt != tt) ? tt : 0.0;
+                const T tt = v - p.qsat[g];
+                const T ql_target = (tt >= T(0) || tt != tt) ? tt : T(0);
                 p.thl[g] += tc * (ql_target - p.ql[g]);
             }
         }
@@ -604,13 +645,13 @@ __global__ __launch_bounds__(256) void k_vnudge_update(const VnP p)
 // rows [0, nr) of one LDS tile added IN ORDER to `acc` (SQ: their squared deviations from `mean`): the reads of the next G
 // rows are in flight while the current G are added.  Separate instantiations for the two passes keep the loop body free of
 // selects and register copies.
-template <bool SQ, int ROWS> __device__ __forceinline__ double vs_sum_tile(const double (*tl)[16], int lane, int nr, double mean, double acc)
+template <bool SQ, int ROWS, typename T> __device__ __forceinline__ T vs_sum_tile(const T (*tl)[16], int lane, int nr, T mean, T acc)
 {
     constexpr int G = 16;
     if (nr == ROWS) {
         // a full tile: the whole tile unrolled, group g + 1 read from LDS while group g is added (no loop-carried registers,
         // hence no copies between them); sched_barrier keeps the reads IN FRONT of the chain they overlap
-        double v[2][G];
+        T v[2][G];
 #pragma unroll
         for (int i = 0; i < G; ++i) v[0][i] = tl[i][lane];
 #pragma unroll
@@ -622,7 +663,7 @@ template <bool SQ, int ROWS> __device__ __forceinline__ double vs_sum_tile(const
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (SQ) {
 #pragma unroll
-                for (int i = 0; i < G; ++i) { const double dlt = v[g & 1][i] - mean; v[g & 1][i] = dlt * dlt; }
+                for (int i = 0; i < G; ++i) { const T dlt = v[g & 1][i] - mean; v[g & 1][i] = dlt * dlt; }
             }
 #pragma unroll
             for (int i = 0; i < G; ++i) acc += v[g & 1][i];
@@ -631,19 +672,21 @@ template <bool SQ, int ROWS> __device__ __forceinline__ double vs_sum_tile(const
         return acc;
     }
     for (int r0 = 0; r0 < nr; ++r0) {                         // the ragged last tile
-        const double x = tl[r0][lane];
-        if constexpr (SQ) { const double dlt = x - mean; acc += dlt * dlt; }
+        const T x = tl[r0][lane];
+        if constexpr (SQ) { const T dlt = x - mean; acc += dlt * dlt; }
         else acc += x;
     }
     return acc;
 }
 
+// Float fields: float sums and squares (numpy's float32 reduction); the quotients by the count are numpy's true_divide of the
+// float32 sum by an intp, i.e. a float64 quotient rounded to float (the same as float division wherever the count is exact).
 constexpr int VS_THREADS = 320;
-template <int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(const VnP p)
+template <typename T, int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(const VnPT<T> p)
 {
     extern __shared__ __align__(16) unsigned char vs_smem[];
-    double (*const s_tile)[ROWS][16] = reinterpret_cast<double (*)[ROWS][16]>(vs_smem);      // [2][ROWS][16]
-    __shared__ double s_mean[16];
+    T (*const s_tile)[ROWS][16] = reinterpret_cast<T (*)[ROWS][16]>(vs_smem);      // [2][ROWS][16]
+    __shared__ T s_mean[16];
     constexpr int U = ROWS / 16;                         // rows per loader thread and tile, all in flight together
     const int tid = threadIdx.x;
     const bool adder = tid < 64;                         // wave 0; its lanes 0..15 carry one level each
@@ -654,9 +697,9 @@ template <int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(c
     const bool valid = k < p.ktot;
     const int kk = valid ? k : p.ktot - 1;               // in-bounds addresses for the lanes past the last level
     const int64_t lev = col * p.ktot + kk, ks = p.ktot, base = col * (int64_t)nij * ks + kk;
-    const double *const qt = p.qt + base;
+    const T *const qt = p.qt + base;
     const int ntile = (nij + ROWS - 1) / ROWS;
-    double w[U];
+    T w[U];
     auto load_tile = [&](int t) {                        // rows past the plane's end re-read its last row: never added
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -664,7 +707,7 @@ template <int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(c
             w[u] = qt[(int64_t)(ij < nij ? ij : nij - 1) * ks];
         }
     };
-    double mean = 0.0, acc = 0.0;
+    T mean = T(0), acc = T(0);
     int pass = 0;
     auto store_tile = [&](int t) {                       // pass 1: the LOADER waves square the deviations, the adder only adds
         if (pass == 0) {
@@ -672,11 +715,11 @@ template <int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(c
             for (int u = 0; u < U; ++u) s_tile[t & 1][row + 16 * u][lane] = w[u];
         } else {
 #pragma unroll
-            for (int u = 0; u < U; ++u) { const double dlt = w[u] - mean; s_tile[t & 1][row + 16 * u][lane] = dlt * dlt; }
+            for (int u = 0; u < U; ++u) { const T dlt = w[u] - mean; s_tile[t & 1][row + 16 * u][lane] = dlt * dlt; }
         }
     };
     for (pass = 0; pass < 2; ++pass) {                   // pass 0: sum -> mean; pass 1: sum of squared deviations
-        acc = 0.0;
+        acc = T(0);
         if (!adder) {
             load_tile(0);
             store_tile(0);
@@ -687,7 +730,7 @@ template <int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(c
             if (adder) {
                 if (row == 0) {
                     const int nr = (nij - t * ROWS) < ROWS ? (nij - t * ROWS) : ROWS;
-                    acc = vs_sum_tile<false, ROWS>(s_tile[t & 1], lane, nr, mean, acc);
+                    acc = vs_sum_tile<false, ROWS, T>(s_tile[t & 1], lane, nr, mean, acc);
                 }
             } else if (t + 1 < ntile) {
                 store_tile(t + 1);                        // the other buffer: its last reader (tile t - 1) finished before the last barrier
@@ -696,13 +739,13 @@ template <int ROWS> __global__ __launch_bounds__(VS_THREADS) void k_vnudge_std(c
             __syncthreads();
         }
         if (pass == 0) {
-            if (adder && row == 0) s_mean[lane] = acc / (double)nij;
+            if (adder && row == 0) s_mean[lane] = (T)((double)acc / (double)nij);
             __syncthreads();
             mean = s_mean[lane];
         }
     }
     if (adder && row == 0 && valid) {
-        p.qt_std[lev] = sqrt(acc / (double)nij);
+        p.qt_std[lev] = sqrt((T)((double)acc / (double)nij));
         p.status[lev] = p.status[lev] & ~VN2_INTERNAL;
     }
 }

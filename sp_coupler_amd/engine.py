@@ -58,12 +58,15 @@ class _Checker:
         self.device, self.dtype = device, dtype
         self.keep = []
 
-    def mat(self, name, t, n, m, pitch=None):
+    def mat(self, name, t, n, m, pitch=None, dtype=None):
+        """``dtype``: an argument whose type is fixed whatever the engine's (the float64 R of the nudge)"""
         if not isinstance(t, torch.Tensor):
             raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
         if t.device != self.device:
             raise ValueError("%s is on %s, engine is on %s" % (name, t.device, self.device))
-        if t.dtype != self.dtype:
+        if dtype is not None and t.dtype != dtype:
+            raise ValueError("%s has dtype %s, must be %s" % (name, t.dtype, dtype))
+        if dtype is None and t.dtype != self.dtype:
             raise ValueError("%s has dtype %s, engine computes in %s" % (name, t.dtype, self.dtype))
         if t.dim() != 2 or t.shape[0] != n or t.shape[1] != m:
             raise ValueError("%s must have shape [%d x %d], got %s" % (name, n, m, tuple(t.shape)))
@@ -250,10 +253,11 @@ class Engine:
         from .transfer import Arena
         return Arena(self.device, specs, stream=self.stream)
 
-    def to_devices(self, host_array, rows=None, n_cols=None):
+    def to_devices(self, host_array, rows=None, n_cols=None, dtype=None):
+        """the host array on this engine's device, in the engine's dtype or ``dtype`` (variability_nudge's R: float64)"""
         import numpy
         with self.on_stream():
-            return torch.from_numpy(numpy.ascontiguousarray(host_array)).to(self.device, self.dtype)
+            return torch.from_numpy(numpy.ascontiguousarray(host_array)).to(self.device, dtype or self.dtype)
 
     # -- K1 (+K2) ---------------------------------------------------------------------------
     @_on_engine_stream
@@ -487,45 +491,57 @@ class Engine:
     def variability_nudge(self, qt, qsat, R, ql_av, qt_av, ql_ref, presf=None, thl=None, ql=None, constantT=False,
                           stream=None):
         """spcpl.variability_nudge (splib/spcpl.py:613-744) for all columns: ``qt`` [n x itot x jtot x k] is updated
-        IN PLACE (``thl`` too with ``constantT``); returns dict beta, a, qt_std [n x k] and status [n x k] int32."""
-        if self.dtype != torch.float64:
-            raise ValueError("variability_nudge computes in float64 only (bit parity with numpy / scipy)")
+        IN PLACE (``thl`` too with ``constantT``); returns dict beta, a, qt_std [n x k] and status [n x k] int32.
+        float64 engine: every tensor float64, bit-identical to NumPy / SciPy.  float32 engine: the fields (qt, qsat, thl,
+        ql) and profiles (ql_av, qt_av, ql_ref, presf) float32, R float64; beta and a come back float64, qt_std float32 --
+        the reference's lines evaluated by NumPy on float32 arrays (INTEGRATION.md "float32")."""
+        f32 = self.dtype == torch.float32
+        if self.dtype not in (torch.float64, torch.float32):
+            raise ValueError("variability_nudge computes in float64 or float32, engine has %s" % self.dtype)
         if qt.dim() != 4:
             raise ValueError("qt must be [n x itot x jtot x ktot]")
         n, itot, jtot, ktot = (int(x) for x in qt.shape)
         ck = _Checker(self.device, self.dtype)
+        fname = "float32" if f32 else "float64"
 
         def field(name, t):
             if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != self.dtype or \
                     tuple(t.shape) != (n, itot, jtot, ktot) or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous float64 [%d x %d x %d x %d] tensor on %s" % (name, n, itot, jtot, ktot, self.device))
+                raise ValueError("%s must be a contiguous %s [%d x %d x %d x %d] tensor on %s" % (name, fname, n, itot, jtot, ktot, self.device))
             ck.keep.append(t)
             return t.data_ptr()
         a = _abi.VnudgeArgs()
         a.n_cols, a.itot, a.jtot, a.ktot, a.constantT = n, itot, jtot, ktot, 1 if constantT else 0
         a.qt, a.qsat = field("qt", qt), field("qsat", qsat)
-        a.R, _ = ck.mat("R", R.reshape(n, itot * jtot), n, itot * jtot)
+        # the noise plane is float64 on either engine (spcpl.py:620-621 draws it in float64) and the kernels read it as
+        # [n][itot*jtot] with that row pitch: a view of other strides is packed into a copy, which ck keeps alive until
+        # the launch along with every other tensor whose pointer it hands out
+        if not isinstance(R, torch.Tensor):
+            raise TypeError("R must be a torch.Tensor, got %s" % type(R).__name__)
+        a.R, _ = ck.mat("R", R.reshape(n, itot * jtot).contiguous(), n, itot * jtot, itot * jtot, dtype=torch.float64)
         for name, t in (("ql_av", ql_av), ("qt_av", qt_av), ("ql_ref", ql_ref)):
             ptr, _ = ck.mat(name, t, n, ktot, ktot)
             setattr(a, name, ptr)
         if constantT:
             a.thl, a.ql = field("thl", thl), field("ql", ql)
             a.presf, _ = ck.mat("presf", presf, n, ktot, ktot)
-        res = {k: self.empty(n, ktot) for k in ("beta", "a", "qt_std")}
+        res = {k: self.empty(n, ktot, dtype=torch.float64) for k in ("beta", "a")}
+        res["qt_std"] = self.empty(n, ktot)
         res["status"] = self.empty(n, ktot, dtype=torch.int32)
         a.beta, a.a_add, a.qt_std, a.status = (res["beta"].data_ptr(), res["a"].data_ptr(), res["qt_std"].data_ptr(),
                                                res["status"].data_ptr())
         # scratch for the transposed qt / qsat planes (include/spc.h: spc_vnudge_args.work), kept between calls and sized
         # by the library
-        need = int(self.lib.spc_vnudge_workspace_bytes(n, itot, jtot, ktot))
+        need = int((self.lib.spc_vnudge_workspace_bytes_f32 if f32 else self.lib.spc_vnudge_workspace_bytes)(n, itot, jtot, ktot))
         if need < 0:
             _abi.check(self.lib, need)
         if self._vn_work is None or self._vn_work.numel() < need:
             self._vn_work = None
             self._vn_work = torch.empty(need, dtype=torch.uint8, device=self.device)
         a.work, a.work_bytes = self._vn_work.data_ptr(), self._vn_work.numel()
+        fn = self.lib.spc_variability_nudge_f32 if f32 else self.lib.spc_variability_nudge_f64
         with torch.cuda.device(self.device):
-            rc = self.lib.spc_variability_nudge_f64(ctypes.byref(a), _stream_ptr(stream if stream is not None else self.stream, self.device))
+            rc = fn(ctypes.byref(a), _stream_ptr(stream if stream is not None else self.stream, self.device))
         _abi.check(self.lib, rc)
         return res
 

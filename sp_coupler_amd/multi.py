@@ -88,17 +88,18 @@ class MultiDeviceEngine:
         return ShardedArena([e.device for e in self.engines], self.bounds_for(rows), specs, rows,
                             streams=[getattr(e, "stream", None) for e in self.engines])
 
-    def to_devices(self, host_array, rows=None, n_cols=None):
-        """a host array on every device: replicated (``rows`` None: the shared LES grid) or row-sharded.  A batch that
-        stays on the primary engine (``n_cols`` / ``rows`` below the threshold) gets a plain tensor."""
+    def to_devices(self, host_array, rows=None, n_cols=None, dtype=None):
+        """a host array on every device: replicated (``rows`` None: the shared LES grid) or row-sharded, in the engines'
+        dtype or ``dtype`` (variability_nudge's R: float64 on any engine).  A batch that stays on the primary engine
+        (``n_cols`` / ``rows`` below the threshold) gets a plain tensor."""
         if self.devices_for(rows if rows is not None else (n_cols if n_cols is not None else self.min_cols_per_device * 2)) == 1:
-            return self.primary.to_devices(host_array, rows)
+            return self.primary.to_devices(host_array, rows, dtype=dtype)
         t = torch.from_numpy(host_array)
         if rows is None:
-            out = Sharded([t.to(e.device, e.dtype) for e in self.engines], None)
+            out = Sharded([t.to(e.device, dtype or e.dtype) for e in self.engines], None)
         else:
             b = self.bounds_for(rows)
-            out = Sharded([t[b[i]:b[i + 1]].to(e.device, e.dtype) for i, e in enumerate(self.engines)], b)
+            out = Sharded([t[b[i]:b[i + 1]].to(e.device, dtype or e.dtype) for i, e in enumerate(self.engines)], b)
         self.synchronize()                            # made on the current streams, used on the engines' own
         return out
 
@@ -216,7 +217,8 @@ class MultiDeviceEngine:
 
     def variability_nudge(self, *a, **kw):
         """K6 on every device's LES (spcpl.py:377-382 nudges one LES at a time; columns are independent): Sharded fields in,
-        Sharded results out, ``qt`` / ``thl`` updated in place block by block"""
+        Sharded results out, ``qt`` / ``thl`` updated in place block by block.  R is float64 on every engine: shard it with
+        ``to_devices(R, rows=n, dtype=torch.float64)`` (the fields and profiles in the engines' dtype)"""
         return self._run("variability_nudge", *a, **kw)
 
     # the helpers of splib/sputils.py (K7) on row-sharded arguments: each device runs the operator on its rows; an argument

@@ -1172,9 +1172,11 @@ def _vnudge_chunk(eng, n, itot, jtot, ktot, constantT):
     dev = getattr(eng, "device", None)
     if dev is not None and dev.type == "cuda":
         lib = getattr(eng, "lib", None)
-        per_col = (4 if constantT else 2) * itot * jtot * ktot * 8 + itot * jtot * 8 + 8 * ktot * 8
+        f32 = getattr(eng, "dtype", torch.float64) == torch.float32
+        esize = 4 if f32 else 8                    # the fields, profiles and workspace in the engine's type; R is float64
+        per_col = (4 if constantT else 2) * itot * jtot * ktot * esize + itot * jtot * 8 + 8 * ktot * 8
         if lib is not None:
-            per_col += max(0, int(lib.spc_vnudge_workspace_bytes(1, itot, jtot, ktot)))
+            per_col += max(0, int((lib.spc_vnudge_workspace_bytes_f32 if f32 else lib.spc_vnudge_workspace_bytes)(1, itot, jtot, ktot)))
         free, _ = torch.cuda.mem_get_info(dev)
         free += max(0, torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
         chunk = max(1, min(chunk, int(0.8 * free) // max(per_col, 1)))
@@ -1189,7 +1191,9 @@ def _vnudge_launch(F, Rs, constantT):
     ``F``: dict of [n x ...] arrays.  With several engines (multi.MultiDeviceEngine) the LES are dealt out in contiguous row
     blocks, one per device (sharding.shard_bounds, as every other array of the batch), and each device nudges ITS LES: the 3-D
     fields -- the largest objects in the system -- never meet on one card.  Chunks are issued in rounds, one chunk per device
-    and round: uploads and launches of a round go out device by device (asynchronous), then the results come back."""
+    and round: uploads and launches of a round go out device by device (asynchronous), then the results come back.  The fields
+    and profiles go up in the engine's dtype (a float32 engine rounds them once), R always as float64; qt / thl come back in
+    the engine's dtype and every result array in its own (beta, a float64; qt_std in the engine's dtype)."""
     from .sharding import shard_bounds
     eng = get_engine()
     engines = list(getattr(eng, "engines", None) or [eng])
@@ -1202,8 +1206,9 @@ def _vnudge_launch(F, Rs, constantT):
         chunk = _vnudge_chunk(engines[d], hi - lo, itot, jtot, ktot, constantT) if hi > lo else 1
         queues.append([(c, min(hi, c + chunk)) for c in range(lo, hi, chunk)])
     host = None
-    qt_out = numpy.empty_like(F["qt"])
-    thl_out = numpy.empty_like(F["thl"]) if constantT else None
+    fdt = torch.empty(0, dtype=engines[0].dtype).numpy().dtype
+    qt_out = numpy.empty(F["qt"].shape, dtype=fdt)
+    thl_out = numpy.empty(F["thl"].shape, dtype=fdt) if constantT else None
     for rnd in range(max(len(q) for q in queues)):
         live = []
         for d, q in enumerate(queues):
@@ -1213,7 +1218,8 @@ def _vnudge_launch(F, Rs, constantT):
             up = lambda a, e=e: torch.from_numpy(numpy.ascontiguousarray(a)).to(e.device, e.dtype)      # noqa: E731
             with e.on_stream():
                 T = {key: up(v[lo:hi]) for key, v in F.items() if v is not None}
-                res = e.variability_nudge(T["qt"], T["qsat"], up(Rs[lo:hi]), T["ql_av"], T["qt_av"], T["ql_ref"], presf=T["presf"],
+                R = torch.from_numpy(numpy.ascontiguousarray(Rs[lo:hi])).to(e.device, torch.float64)
+                res = e.variability_nudge(T["qt"], T["qsat"], R, T["ql_av"], T["qt_av"], T["ql_ref"], presf=T["presf"],
                                           thl=T.get("thl"), ql=T.get("ql"), constantT=constantT)
             live.append((e, lo, hi, T, res))
         for e, lo, hi, T, res in live:
