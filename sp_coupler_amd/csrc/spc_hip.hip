@@ -942,7 +942,9 @@ template <typename T, int NG, int NL, int WT> __global__ __launch_bounds__(BLOCK
     const int64_t col0 = (int64_t)slab_index(d.xcd_remap) * cb;
     const int ncol = (int)((d.n_cols - col0) < cb ? (d.n_cols - col0) : cb);
     T *const lds = reinterpret_cast<T *>(spc_smem);
-    const T cc = K<T>::rv / K<T>::rd - T(1);                                           // spcpl.py:175
+    // spcpl.py:175: c = rv / rd - 1 of Python floats, rounded to T once (a NEP 50 weak scalar on float32 arrays); the float
+    // quotient f32(rv) / f32(rd) - 1 would be 2 ulp off it
+    const T cc = T(461.5 / 287.04 - 1.0);
     const bool les = p.zf && (p.pf || p.t || p.ql_water);
     for (int e = tid; e < ncol * nG; e += BLOCK) {
         const int c = e / nG, k = e - c * nG;

@@ -10,7 +10,7 @@ import torch
 
 from oracle import spcpl_oracle as orc
 from sp_coupler_amd import synthetic
-from tests import oracle_c
+from tests import f32_ref, oracle_c
 from tests.gpu_util import EPS, assert_bits, assert_close_scaled, host, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -86,14 +86,17 @@ def test_t159_sized_batch_vs_c_oracle(eng):
     check_backward(bwd, ref_b)
 
 
-def _ulp_search(target, denom):
-    """a double z with z / denom == target exactly (so Zf hits an LES level bit-for-bit)"""
+def _ulp_search(target, denom, must=True):
+    """a z of target's type with z / denom == target exactly in that type (so Zf hits an LES level bit-for-bit); None when
+    there is none and not ``must`` (in float32 a quotient by 9.81 skips some values)"""
     z = target * denom
     for _ in range(64):
         q = z / denom
         if q == target:
             return z
         z = numpy.nextafter(z, numpy.inf if q < target else -numpy.inf)
+        if not must and (z / denom > target) != (q > target) and z / denom != target:
+            return None
     raise AssertionError("no exact preimage")
 
 
@@ -142,6 +145,39 @@ def make_edge_batch():
     return gcm, zf, zh, prof, Zf1, Zh1, exact_full, exact_half
 
 
+def make_edge_batch_f32():
+    """make_edge_batch rounded to float32, its quirks re-imposed IN float32: exact hits where (Zgfull - Zghalf[-1]) / 9.81
+    computed in float32 equals an LES level (and half levels on LES half levels), QL = QI = 0 with -0.0 among them, NaN and
+    +-inf inputs, the GCM column wholly below / above the LES, and (col 6) two adjacent GCM full levels with the same float32
+    height, so that the slope between them is 0 / 0."""
+    gcm, zf, zh, prof, _, _, exact_full, exact_half = make_edge_batch()
+    f4 = numpy.float32
+    gcm = {k: v.astype(f4) for k, v in gcm.items()}
+    prof = {k: v.astype(f4) for k, v in prof.items()}
+    zf, zh = zf.astype(f4), zh.astype(f4)
+    g9 = f4(9.81)
+    Zf1 = (gcm["Zgfull"][1] - gcm["Zghalf"][1, -1]) / g9
+    for k in exact_full:
+        z = _ulp_search(zf[numpy.argmin(numpy.abs(zf - Zf1[k]))], g9, must=False)
+        if z is not None:
+            gcm["Zgfull"][1, k] = z
+    Zh1 = (gcm["Zghalf"][1] - gcm["Zghalf"][1, -1]) / g9
+    for k in exact_half:
+        z = _ulp_search(zh[numpy.argmin(numpy.abs(zh - Zh1[k]))], g9, must=False)
+        if z is not None:
+            gcm["Zghalf"][1, k] = z
+    gcm["QI"][0, ::2] = -0.0
+    prof["QL"][4, :7] = -0.0
+    gcm["SH"][7, 3] = -0.0
+    k6 = int(numpy.nonzero((gcm["Zgfull"][6] - gcm["Zghalf"][6, -1]) / g9 < zf[-1] * 0.5)[0][0])
+    gcm["Zgfull"][6, k6] = gcm["Zgfull"][6, k6 + 1]
+    Zf1 = (gcm["Zgfull"][1] - gcm["Zghalf"][1, -1]) / g9
+    Zh1 = (gcm["Zghalf"][1] - gcm["Zghalf"][1, -1]) / g9
+    exact_full = [k for k in range(gcm["T"].shape[1]) if Zf1[k] in zf]
+    exact_half = [k for k in range(gcm["T"].shape[1]) if Zh1[k] in zh]
+    return gcm, zf, zh, prof, exact_full, exact_half, k6
+
+
 def test_edge_columns(eng):
     """Quirks of SURVEY.md section 7: end clamping both ways, x == xp[j] exact hits, QL=QI=0 columns,
     LES top above every GCM level / below the lowest one, NaN and +-0 handling."""
@@ -162,6 +198,44 @@ def test_edge_columns(eng):
     assert numpy.array_equal(numpy.isfinite(fwd["thl"]), ok)
     assert numpy.abs(fwd["thl"][ok] - ref_f["thl"][ok]).max() <= 8 * EPS * numpy.abs(ref_f["thl"][ok]).max()
     check_backward(bwd, ref_b)
+
+
+def test_edge_columns_float32_bit_for_bit():
+    """make_edge_batch_f32 through every float kernel -- K1 full with surface coupling, K3 (Zf from K1 and recomputed), K4,
+    K5, the standalone K2 and k_surface -- against the float32 C oracle, bit for bit, -0.0 and NaN positions included"""
+    from sp_coupler_amd.engine import Engine
+    e32 = Engine("cuda:0", dtype=torch.float32)
+    gcm, zf, zh, prof, exact_full, exact_half, k6 = make_edge_batch_f32()
+    n = gcm["T"].shape[0]
+    with numpy.errstate(all="ignore"):
+        ref_f = oracle_c.forward(gcm, zf, zh, prof, FACTOR, DT, couple_surface=True)
+        ref_b = oracle_c.backward(gcm, ref_f["Zf"], zf, prof, FACTOR, DT)
+        ref_b0 = oracle_c.backward(gcm, None, zf, prof, FACTOR, DT)
+        ref_c = oracle_c.backward(gcm, None, zf, prof, FACTOR, DT, conservative=True, zh=zh)
+        ref_d = oracle_c.diagnostics(gcm, zf, prof)
+    assert len(exact_full) >= 8 and len(exact_half) >= 3 and ref_f["Zf"][6, k6] == ref_f["Zf"][6, k6 + 1]
+    assert ref_b["start_index"][2] == 0 and ref_b["start_index"][3] == 91
+    assert numpy.isnan(ref_b["f_T"][4, 0]) and numpy.signbit(ref_b["f_U"][4]).any()
+    g, p = to_dev(gcm, e32.device, torch.float32), to_dev(prof, e32.device, torch.float32)
+    zf_d, zh_d = torch.from_numpy(zf).to(e32.device), torch.from_numpy(zh).to(e32.device)
+    fwd = e32.forward(g, zf_d, p, FACTOR, DT, zh=zh_d, want_profiles=True, couple_surface=True)
+    bwd = e32.backward(g, zf_d, p, FACTOR, DT, Zf=fwd["Zf"])
+    bwd0 = e32.backward(g, zf_d, p, FACTOR, DT, Zf=None)
+    cons = e32.backward(g, zf_d, p, FACTOR, DT, Zf=None, conservative=True, zh=zh_d)
+    diag = e32.diagnostics(g, zf_d, p)
+    idx = e32.cloud_indices(zh_d, fwd["Zh"])
+    wthl, wqt = e32.surface_fluxes(g["Phalf"][:, -1].contiguous(), g["T"][:, -1].contiguous(), g["QLflux"], g["QIflux"],
+                                   g["SHflux"], g["TSflux"])
+    torch.cuda.synchronize()
+    for k, v in fwd.items():
+        assert_bits("K1 " + k, host(v), ref_f[k])
+    for name, got, ref in (("K3", bwd, ref_b), ("K3 recomputed Zf", bwd0, ref_b0), ("K4", cons, ref_c), ("K5", diag, ref_d)):
+        for k, v in got.items():
+            assert_bits("%s %s" % (name, k), host(v), ref[k])
+    assert_bits("K2 idx", host(idx), ref_f["idx"])
+    assert_bits("k_surface wthl", host(wthl), ref_f["wthl"])
+    assert_bits("k_surface wqt", host(wqt), ref_f["wqt"])
+    assert n == 8 and numpy.isnan(host(cons["f_T"])).sum() == numpy.isnan(ref_c["f_T"]).sum()
 
 
 def test_standalone_cloud_indices(eng):
@@ -515,6 +589,36 @@ def test_conservative_coarsening_thick_layers_compile_time_geometries(eng, nG, n
         assert_bits(k, host(got[k])[cols], ref_np[k])
 
 
+@pytest.mark.parametrize("nG,nL,scale", [(91, 160, None), (137, 512, None), (19, 160, None), (91, 2000, 0.1),
+                                          (91, 240, 0.01), (91, 480, 0.004), (91, 960, 0.002)])
+def test_conservative_coarsening_thick_layers_float32_bit_for_bit(nG, nL, scale):
+    """The two thick-layer tests above on a float32 engine: layers of > 128 LES cells, so that the float K4 kernels' sums
+    really recurse (compile-time geometries: vn_pw's fixed depth; run-time geometry: pd = 1, 2, 3 and the explicit stack),
+    every tendency bit for bit against the float32 C oracle (numpy's pairwise tree with float32 adds)."""
+    from sp_coupler_amd.engine import Engine
+    e32 = Engine("cuda:0", dtype=torch.float32)
+    f4 = numpy.float32
+    gcm, zf, zh, prof = synthetic.make_batch(16, nG, nL, seed=61 + nG if scale is None else 52)
+    if scale is None:                                   # lowest layer ~ 0.9 nL cells thick
+        dz = float(numpy.median(oracle_c.forward(gcm, zf, zh, prof, FACTOR, DT)["Zh"][:, nG - 1])) / (0.9 * nL)
+        zh = numpy.arange(nL, dtype=numpy.float64) * dz
+        zf = zh + 0.5 * dz
+    else:                                               # 1 m / 0.1 m LES cells
+        zf, zh = zf * scale, zh * scale
+    gcm, prof = ({k: numpy.ascontiguousarray(v, f4) for k, v in d.items()} for d in (gcm, prof))
+    zf, zh = numpy.ascontiguousarray(zf, f4), numpy.ascontiguousarray(zh, f4)
+    g, p = to_dev(gcm, e32.device, torch.float32), to_dev(prof, e32.device, torch.float32)
+    got = e32.backward(g, torch.from_numpy(zf).cuda(), p, FACTOR, DT, Zf=None, conservative=True, zh=torch.from_numpy(zh).cuda())
+    torch.cuda.synchronize()
+    ref_f = oracle_c.forward(gcm, zf, zh, prof, FACTOR, DT)
+    ref = oracle_c.backward(gcm, None, zf, prof, FACTOR, DT, conservative=True, zh=zh)
+    inside = ref_f["Zh"][:, nG - 1] <= zh[-1]
+    cells = numpy.diff(numpy.searchsorted(zh, ref_f["Zh"][inside][:, ::-1]), axis=1)
+    assert inside.sum() >= 3 and cells.max() > 128, (inside.sum(), cells.max() if inside.any() else None)
+    for k, v in got.items():
+        assert_bits("f32 K4 %d<->%d %s" % (nG, nL, k), host(v), ref[k])
+
+
 def test_fp32_variant_is_the_float32_evaluation_of_the_reference_lines():
     """The fp32 arithmetic variant (BASELINE config 5's sweep) forms its quotients through fp64 -- (float)((double)a * r), r = 1 /
     (double)b (csrc/spc_hip.hip: Divisor<float>, round 5) -- which is the CORRECTLY ROUNDED float quotient: the kernels' u, v,
@@ -538,17 +642,9 @@ def test_fp32_variant_is_the_float32_evaluation_of_the_reference_lines():
         assert_bits("Zf", host(r["Zf"]), Zf)
         assert_bits("Zh", host(r["Zh"]), Zh)
 
-        def interp32(x, xp, fp):                     # numpy's arr_interp, every operation in float32
-            j = numpy.searchsorted(xp, x, side="right") - 1
-            jc = numpy.clip(j, 0, len(xp) - 2)
-            slope = (fp[jc + 1] - fp[jc]) / (xp[jc + 1] - xp[jc])
-            out = slope * (x - xp[jc]) + fp[jc]
-            out = numpy.where(xp[jc] == x, fp[jc], out)
-            out = numpy.where(j < 0, fp[0], out)
-            return numpy.where(j >= len(xp) - 1, fp[-1], out).astype(f4)
         qt_ = g32["SH"] + g32["QL"] + g32["QI"]                                           # spcpl.py:215
         for name, src, les in (("u", g32["U"], "U"), ("v", g32["V"], "V"), ("qt", qt_, "QT"), ("ql_ref", g32["QL"], "QL")):
-            want = numpy.stack([interp32(zf32, Zf[c, ::-1], src[c, ::-1]) for c in range(n)])       # spcpl.py:224-228
+            want = numpy.stack([f32_ref.interp(zf32, Zf[c, ::-1], src[c, ::-1]) for c in range(n)])  # spcpl.py:224-228
             assert want.dtype == f4
             assert_bits(name, host(r[name]), want)
             fname = {"u": "f_u", "v": "f_v", "qt": "f_qt", "ql_ref": "f_ql"}[name]

@@ -14,6 +14,7 @@ import torch
 
 from oracle import spcpl_oracle as orc
 from sp_coupler_amd import synthetic
+from tests import f32_ref
 from tests.gpu_util import EPS, assert_bits
 
 pytestmark = pytest.mark.gpu
@@ -391,10 +392,95 @@ def test_float32_engine_runs_the_helpers():
     got = eng.interp(torch.from_numpy(x).cuda(), torch.from_numpy(xp).cuda(), torch.from_numpy(fp).cuda()).cpu().numpy()
     want = _interp_rows(x.astype(float), xp.astype(float), fp.astype(float))
     assert numpy.abs(got - want).max() <= 1e-4 * numpy.abs(want).max()
+    assert_bits("float32 interp", got, numpy.stack([f32_ref.interp(x[r], xp[r], fp[r]) for r in range(50)]))
     idx = eng.searchsorted(torch.from_numpy(xp).cuda(), torch.from_numpy(x).cuda(), side="right").cpu().numpy()
     assert numpy.array_equal(idx, numpy.stack([numpy.searchsorted(xp[r], x[r], side="right") for r in range(50)]))
     p = torch.from_numpy(rng.uniform(1e4, 1.05e5, size=1000).astype(numpy.float32)).cuda()
     assert numpy.allclose(eng.exner(p).cpu().numpy(), orc.exner(p.cpu().numpy().astype(float)), rtol=2e-6)
+
+
+def _f32_dev(a, pad=0):
+    """a float32 device copy of ``a``; with ``pad``, a view into rows ``pad`` elements longer (NaN-filled), i.e. a padded pitch"""
+    t = torch.from_numpy(numpy.ascontiguousarray(a, dtype=numpy.float32)).cuda()
+    if pad == 0 or t.dim() != 2:
+        return t
+    buf = torch.full((t.shape[0], t.shape[1] + pad), float("nan"), device=t.device, dtype=t.dtype)
+    buf[:, :t.shape[1]] = t
+    return buf[:, :t.shape[1]]
+
+
+@pytest.mark.parametrize("n", [1, 2, 5, 40, 64, 91, 127, 128, 130, 300, 600, 1100, 5000])
+def test_float32_interp_and_searchsorted_at_every_search_depth(n):
+    """test_every_search_depth_and_the_unstaged_rows on a float32 engine (its twin runs the run-time descent): interp and
+    searchsorted bit for bit against tests/f32_ref.py (numpy.interp restated in float32, numpy.searchsorted on float32)"""
+    from sp_coupler_amd.engine import Engine
+    eng = Engine("cuda:0", dtype=torch.float32)
+    f4 = numpy.float32
+    rng = numpy.random.default_rng(100 + n)
+    rows = 37
+    xp = numpy.sort(rng.uniform(0, 1e4, size=(rows, n)), axis=1).astype(f4)
+    fp = rng.normal(size=(rows, n)).astype(f4)
+    x = rng.uniform(-50, 1.005e4, size=(rows, 23)).astype(f4)
+    x[:, 0], x[:, 1], x[:, 2] = xp[:, 0], xp[:, -1], xp[:, n // 2]
+    x[3, 5], x[4, 6], x[5, 7] = numpy.nan, numpy.inf, -numpy.inf
+    with numpy.errstate(all="ignore"):
+        for shared in (False, True):
+            xps = xp[0] if shared else xp
+            want = numpy.stack([f32_ref.interp(x[r], xps if shared else xp[r], fp[r]) for r in range(rows)])
+            got = host_(eng.interp(_f32_dev(x), _f32_dev(xps), _f32_dev(fp)))
+            assert_bits("f32 interp n=%d shared=%s" % (n, shared), got, want)
+            for side in ("left", "right"):
+                want = numpy.stack([f32_ref.searchsorted(xps if shared else xp[r], x[r], side=side) for r in range(rows)])
+                got = host_(eng.searchsorted(_f32_dev(xps), _f32_dev(x), side=side))
+                assert numpy.array_equal(got, want), (n, side, shared)
+
+
+def host_(t):
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+@pytest.mark.parametrize("nG,nL,per_col,pad", [(91, 160, False, 0), (19, 160, True, 3), (31, 2000, False, 1),
+                                               (137, 512, False, 2)])
+def test_float32_interp_c_interp_rho_integral_and_rms(nG, nL, per_col, pad):
+    """the float32 K7 helpers on padded pitches and multi-row slabs (300 rows), against tests/f32_ref.py bit for bit:
+    interp_c / interp_rho (splib/sputils.py:173-197), integral with and without weights (94-161), rms (23-24, NumPy's own
+    lines on float32 data)"""
+    from sp_coupler_amd.engine import Engine
+    eng = Engine("cuda:0", dtype=torch.float32)
+    f4 = numpy.float32
+    n = 300
+    Zh, zh, q, rho = (numpy.ascontiguousarray(a, dtype=f4) for a in _coarse_inputs(n, nG, nL, seed=78, per_column_grid=per_col))
+    Zh[5, nG // 2] = -3.0                                   # an end point below zh[0]: NaN
+    z = lambda c: zh[c] if zh.ndim == 2 else zh             # noqa: E731
+    with numpy.errstate(all="ignore"):
+        want_c = numpy.stack([f32_ref.interp_c(Zh[c], z(c), q[c], rho[c]) for c in range(n)])
+        Zr = Zh.copy()
+        Zr[5] = Zr[4]                                       # interp_rho divides None by a number in the reference
+        want_r = numpy.stack([f32_ref.interp_rho(Zr[c], z(c), rho[c]) for c in range(n)])
+    zd = _f32_dev(zh, pad)
+    got_c = host_(eng.interp_c(_f32_dev(Zh, pad), zd, _f32_dev(q, pad), _f32_dev(rho, pad), mode="interp_c"))
+    got_r = host_(eng.interp_c(_f32_dev(Zr, pad), zd, _f32_dev(rho, pad), None, mode="interp_rho"))
+    assert_bits("f32 interp_c", got_c, want_c)
+    assert_bits("f32 interp_rho", got_r, want_r)
+    assert numpy.isnan(got_c[5]).any() and (got_c != 0).any()
+    # integral: one interval per row, the weighted and the unweighted form
+    rng = numpy.random.default_rng(nG)
+    lo, hi = z(0)[0] if zh.ndim == 1 else zh[:, 0], z(0)[-1] if zh.ndim == 1 else zh[:, -1]
+    a = (lo + (hi - lo) * rng.uniform(0, 1, n)).astype(f4)
+    b = (lo + (hi - lo) * rng.uniform(0, 1, n)).astype(f4)
+    a[7] = b[7]
+    for w in (rho, None):
+        Zab = numpy.ascontiguousarray(numpy.stack([b, a], axis=1))
+        got = host_(eng.interp_c(_f32_dev(Zab), zd, _f32_dev(q, pad), None if w is None else _f32_dev(w, pad), mode="integral"))[:, 0]
+        with numpy.errstate(all="ignore"):
+            want = numpy.array([f32_ref.integral(a[c], b[c], z(c), q[c], None if w is None else w[c]) for c in range(n)], dtype=f4)
+        assert_bits("f32 integral weighted=%s" % (w is not None), got, want)
+    # rms of every row, and of one long row (numpy's chunked pairwise order beyond 8192 elements)
+    v = (rng.normal(size=(n, nL)) * rng.uniform(1e-3, 1e3, size=(n, 1))).astype(f4)
+    assert_bits("f32 rms rows", host_(eng.rms(_f32_dev(v, pad))), numpy.array([f32_ref.rms(v[r]) for r in range(n)], dtype=f4))
+    long = rng.normal(size=20011).astype(f4)
+    assert host_(eng.rms(_f32_dev(long))) == f32_ref.rms(long)
 
 
 def test_fuzz_random_shapes_sharing_and_pitches(sputils):
