@@ -18,9 +18,14 @@ Byte model (LES grid SHARED by all columns as bench.py packs it 
 traffic): K1+K2 (9 nG + 5 nL + 3) reads + (6 nL + 1) writes fp64 + nG int32; K3 (9 nG + 6 nL) reads + 7 nG writes.
 91<->160: 21 028 B + 19 328 B = 40 356 B per column-exchange.
 
-Prints ONE JSON line on rank 0 (contract: see the task statement) with the extra objects `roofline`,
-`cpu_baseline`, `small_batch`, and `verified` (outputs of batch 0 after the timed region, bit-compared with the
-CPU oracle's outputs that the cpu_baseline leg produced).
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: it builds the workload, runs W warm-up
+and K timed steps (behind Workload.heat), writes the outputs of the last timed step if --dump-outputs is given, and prints
+ONE JSON line on rank 0 (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) with `verified: null`.
+`--full` adds everything else this file measures or checks, in the same process: the per-kernel HIP-event pass and the
+copy-rate probe before the timed region, and after it `value_spread`, `cold_clock`, `small_batch`, `scaling_anchor`,
+`config5`, `per_column_grid`, `in_process_all_gpus`, `dropin`, `roofline` (with PMC traffic measured in child
+processes), `cpu_baseline`, and `verified` (outputs of batch 0 bit-compared with the CPU oracle's outputs that the
+cpu_baseline leg produced; at N > 1 every rank's `sample_check`).  The `--no-*` switches below trim a `--full` run.
 """
 import argparse
 import ctypes
@@ -862,27 +867,30 @@ def main():
     ap.add_argument("--cols", type=int, default=None, help="override the TOTAL column count of the workload")
     ap.add_argument("--rotate", type=int, default=None, help="distinct batches cycled through (default 2; 8 for <= 4096 cols)")
     ap.add_argument("--cols-per-block", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip; also skips `verified`)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip the per-kernel HIP-event pass")
-    ap.add_argument("--no-cpu-multicore", action="store_true", help="skip the all-cores cpu_baseline extra")
-    ap.add_argument("--no-small-batch", action="store_true", help="skip the config-2 extra at N=1")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in API (Coupler.step) rate at N=1")
+    ap.add_argument("--full", action="store_true", help="besides the headline, run every extra measurement and check of this file "
+                    "(per-kernel pass, roofline, spread, cold clock, other configs / layouts / arithmetic, drop-in rate, CPU baselines, "
+                    "`verified` against the oracle); without it a run only sets up, warms up, times, dumps and prints its line")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 = skip; also skips `verified`)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip the per-kernel HIP-event pass (and the legs that need it)")
+    ap.add_argument("--no-cpu-multicore", action="store_true", help="--full: skip the all-cores cpu_baseline extra")
+    ap.add_argument("--no-small-batch", action="store_true", help="--full: skip the config-2 extra at N=1")
+    ap.add_argument("--no-dropin", action="store_true", help="--full: skip the drop-in API (Coupler.step) rate at N=1")
     ap.add_argument("--backend", default="nccl", help="process-group backend for N>1 (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--force-dist", action="store_true", help="rehearsal on a one-GPU box: initialise the process group (RCCL), run the "
                     "barrier and the max-reduction of the N > 1 path with ONE rank under torch.distributed.run; the line says so")
     ap.add_argument("--device", type=int, default=None, help="force this HIP device for every rank (rehearsal on a 1-GPU box)")
-    ap.add_argument("--no-anchor", action="store_true", help="skip the config-4-on-one-GPU `scaling_anchor` extra at N=1")
+    ap.add_argument("--no-anchor", action="store_true", help="--full: skip the config-4-on-one-GPU `scaling_anchor` extra at N=1")
     ap.add_argument("--multi-devices", default=None,
-                    help="N=1 extra `in_process_all_gpus`: config 4 through multi.MultiDeviceEngine on these device ids (default: every "
+                    help="--full, N=1 extra `in_process_all_gpus`: config 4 through multi.MultiDeviceEngine on these device ids (default: every "
                          "visible GPU when there is more than one; '0,0' rehearses the path with two engines on one GPU; 'none' skips)")
     ap.add_argument("--dtype", choices=("f64", "f32"), default="f64", help="arithmetic type of the headline workload (f64 as the reference; "
                     "f32: the tolerance-sweep variant, checked against the fp64 oracle within F32_TOL)")
     ap.add_argument("--per-column-grid", action="store_true", help="headline workload with the LES grid packed per column [n_cols x n_lev]")
-    ap.add_argument("--no-config5", action="store_true", help="skip the `config5` extra (88 838 columns 137<->512, f64 and f32) at N=1")
-    ap.add_argument("--no-per-column-grid-leg", action="store_true", help="skip the `per_column_grid` extra (config 3, grid per column) at N=1")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not measure `roofline.traffic` in this run (two rocprofv3 --pmc child "
+    ap.add_argument("--no-config5", action="store_true", help="--full: skip the `config5` extra (88 838 columns 137<->512, f64 and f32) at N=1")
+    ap.add_argument("--no-per-column-grid-leg", action="store_true", help="--full: skip the `per_column_grid` extra (config 3, grid per column) at N=1")
+    ap.add_argument("--no-live-traffic", action="store_true", help="--full: do not measure `roofline.traffic` in this run (two rocprofv3 --pmc child "
                     "processes after the timed regions, ~1 minute); report the constant of profiles/traffic.json instead")
-    ap.add_argument("--check-rows", type=int, default=4096, help="rows per rank / device in the N > 1 output check (sample_check)")
+    ap.add_argument("--check-rows", type=int, default=4096, help="--full: rows per rank / device in the N > 1 output check (sample_check)")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="N>1 launch mechanics only (rendezvous, sharding, barrier, max-reduction over gloo; no GPU work): CPU tests")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -948,8 +956,10 @@ def main():
     stream = torch.cuda.current_stream(eng.device)
     sptr = ctypes.c_void_p(stream.cuda_stream)
 
+    full = args.full                            # everything beyond the headline (see the module docstring)
+    kev = full and not args.no_kernel_events    # the per-kernel pass and the extra legs that share its switch
     wl = Workload(eng, n_cols, nG, nL, seed + 1000 * rank, rotate, factor, dt_gcm, args.cols_per_block,
-                  keep_host=(rank == 0 and world == 1), per_column_grid=args.per_column_grid)
+                  keep_host=(full and rank == 0 and world == 1), per_column_grid=args.per_column_grid)
 
     def fence():
         torch.cuda.synchronize()
@@ -957,7 +967,7 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # The per-kernel HIP-event pass and the copy-rate probe run BEFORE the timed region, each behind Workload.heat():
+    # --full: the per-kernel HIP-event pass and the copy-rate probe run BEFORE the timed region, each behind Workload.heat():
     # after an idle gap (>= 50 ms, e.g. the host-side batch generation above) an MI355X runs the first ~20 ms of work
     # 10-13 % slower than steady state (profiles/r02_shortrun_clock_ramp.log, tools/shortrun.py), which is longer than
     # the driver's whole `--warmup 5 --steps 20` region.  `cold_clock` below reports the same W + K taken straight
@@ -967,7 +977,7 @@ def main():
     kdiag = {}
     copy_gbs = None
     fence()                                  # N > 1: line the ranks up first, so no rank idles (and cools) at the next fence
-    if not args.no_kernel_events:
+    if kev:
         k1_us, k3_us = wl.kernel_times(stream, sptr)
         # measured device-to-device copy rate of this box (16 B/lane streaming copy, 256 MiB, read + write bytes):
         # the practical HBM ceiling reported next to the 8 TB/s spec peak
@@ -1007,7 +1017,7 @@ def main():
     # spread of the headline: the same W + K region four more times (each behind Workload.heat like the official one);
     # the official `value` stays the FIRST region, timed exactly as the contract says
     spread = None
-    if world == 1 and not args.no_kernel_events:
+    if world == 1 and kev:
         vals = [total_cols * args.steps / elapsed]
         for _ in range(4):
             wl.heat(sptr)
@@ -1023,7 +1033,7 @@ def main():
         spread = {"regions": len(vals), "min": sv[0], "median": sv[len(sv) // 2], "max": sv[-1], "first_is_value": True}
 
     cold = None
-    if world == 1 and not args.no_kernel_events:
+    if world == 1 and kev:
         # the same W + K protocol straight after 0.5 s of idle GPU (clocks ramped down): what a short region costs cold
         time.sleep(0.5)
         for i in range(args.warmup):
@@ -1038,7 +1048,7 @@ def main():
                 "note": "same warmup+steps after 0.5 s of idle GPU; `value` above is taken with the per-kernel pass run first"}
 
     small = None
-    if world == 1 and not args.no_small_batch and not args.no_kernel_events and cfg != 2:
+    if world == 1 and not args.no_small_batch and kev and cfg != 2:
         n2, nG2, nL2, seed2 = synthetic.CONFIGS[2]
         w2 = Workload(eng, n2, nG2, nL2, seed2, 8, factor, dt_gcm, args.cols_per_block)
         w2.heat(sptr)
@@ -1060,7 +1070,7 @@ def main():
         del w2
 
     anchor = None
-    if world == 1 and cfg == 3 and not args.cols and not args.no_anchor and not args.no_kernel_events:
+    if world == 1 and cfg == 3 and not args.cols and not args.no_anchor and kev:
         # the N = 1 point of the series the N > 1 runs measure (config 4, 348 528 columns, strong scaling): the whole of
         # config 4 on this ONE GPU (14 GB live; one batch -- 55x the Infinity Cache -- so no rotation is needed)
         n4, nG4, nL4, seed4 = synthetic.CONFIGS[4]
@@ -1088,17 +1098,17 @@ def main():
         torch.cuda.empty_cache()
 
     # BASELINE config 5 (137 <-> 512, the high-vertical-resolution case) in both arithmetic types, and config 3 with the LES
-    # grid packed per column: measured on the shipped library in EVERY default N = 1 line (round-4 verdict, items 1 and 3)
+    # grid packed per column: measured on the shipped library in every --full N = 1 line of the default workload
     config5 = percol = None
-    plain = world == 1 and cfg == 3 and not args.cols and not f32 and not args.per_column_grid and not args.no_kernel_events
-    if plain and not args.no_config5:
+    stock = world == 1 and cfg == 3 and not args.cols and not f32 and not args.per_column_grid and kev
+    if stock and not args.no_config5:
         config5 = {}
         for dn in ("f64", "f32"):
             try:
                 config5[dn] = config_leg(eng.device, 5, dn, False, factor, dt_gcm, steps=60, launches=60, check_rows=args.check_rows)
             except Exception as e:                   # a reported extra, never fatal for the headline
                 config5[dn] = {"error": repr(e)}
-    if plain and not args.no_per_column_grid_leg:
+    if stock and not args.no_per_column_grid_leg:
         try:
             percol = config_leg(eng.device, 3, "f64", True, factor, dt_gcm, steps=200, launches=KERNEL_LAUNCHES, check_rows=args.check_rows)
             if k1_us:
@@ -1109,7 +1119,7 @@ def main():
 
     inproc = None
     ids = None
-    if world == 1 and args.multi_devices != "none" and not args.no_kernel_events:
+    if world == 1 and args.multi_devices != "none" and kev:
         if args.multi_devices:
             ids = [int(x) for x in args.multi_devices.split(",")]
         elif torch.cuda.device_count() > 1:
@@ -1121,24 +1131,27 @@ def main():
             inproc = {"error": repr(e)}
 
     dropin = None
-    if world == 1 and not args.no_dropin:
+    if world == 1 and full and not args.no_dropin:
         try:
             dropin = dropin_rate(eng)
         except Exception as e:                       # a reported extra, never fatal for the headline
             dropin = {"error": repr(e)}
 
-    # N > 1: every rank proves ITS outputs and says who it is (a line whose ranks all sat on one GPU, or whose shards were
-    # never checked, proves nothing): a sample of >= 4096 rows of the rank's block incl. its first and last row, inputs
-    # read back from the device, plain-C oracle on the host, compared with what the timed plans left in HBM
+    # N > 1: every rank says who it is and, with --full, proves ITS outputs (a line whose ranks all sat on one GPU, or whose
+    # shards were never checked, proves nothing): a sample of >= 4096 rows of the rank's block incl. its first and last row,
+    # inputs read back from the device, plain-C oracle on the host, compared with what the timed plans left in HBM
     per_rank = None
     if dist is not None:
-        g0, zf0, zh0, p0 = wl.inputs0
-        try:
-            ok_r, det_r = sample_check(wl.fplans[0].outputs, wl.bplans[0].outputs, g0, p0, zf0, zh0, factor, dt_gcm,
-                                       m=max(4096, args.check_rows))
-        except Exception as e:                          # a rank that cannot check reports that, it does not hang the others
-            ok_r, det_r = False, {"failures": ["sample_check raised %r" % (e,)]}
-        mine = {"rank": rank, "local_rank": local, "rows": [int(lo), int(hi)], "device": device_identity(local), "verified": bool(ok_r),
+        ok_r = det_r = None
+        if full:
+            g0, zf0, zh0, p0 = wl.inputs0
+            try:
+                ok_r, det_r = sample_check(wl.fplans[0].outputs, wl.bplans[0].outputs, g0, p0, zf0, zh0, factor, dt_gcm,
+                                           m=max(4096, args.check_rows))
+                ok_r = bool(ok_r)
+            except Exception as e:                      # a rank that cannot check reports that, it does not hang the others
+                ok_r, det_r = False, {"failures": ["sample_check raised %r" % (e,)]}
+        mine = {"rank": rank, "local_rank": local, "rows": [int(lo), int(hi)], "device": device_identity(local), "verified": ok_r,
                 "check": det_r, "ms_per_step": own_elapsed / args.steps * 1e3, "k1_avg_launch_us": k1_us, "k3_avg_launch_us": k3_us,
                 "pid": os.getpid()}
         per_rank = [None] * world
@@ -1168,7 +1181,7 @@ def main():
                    "rotate": rotate, "launches_per_step": 2, "parallelism": "columns sharded, no collective"},
         "backend": (args.backend if dist is not None else None),
         "series_note": ("ONE workload per scaling series: `--gpus N` (N > 1) shards config 4 (348 528 columns) over N GPUs -- strong "
-                        "scaling; its N = 1 point is `scaling_anchor` of the N = 1 line (config 4 on one GPU).  The N = 1 headline "
+                        "scaling; its N = 1 point is `scaling_anchor` of the N = 1 --full line (config 4 on one GPU).  The N = 1 headline "
                         "`value` is config 3 (35 718 columns, the largest config BASELINE.json places on ONE GPU): do not divide "
                         "value(N) by value(1)"),
         "bytes_per_exchange": ab["exchange"],
@@ -1176,6 +1189,7 @@ def main():
         "ranks": (dist.get_world_size() if dist is not None else 1),
         "force_dist": (True if (args.force_dist and world == 1 and dist is not None) else None),   # a ONE-rank rehearsal of the N > 1 machinery
         "devices": ([r["device"] for r in per_rank] if per_rank else [device_identity(local)]),
+        "full": full,                            # False: the headline alone, every extra leg and check skipped (`verified: null`)
     }
     roof_rank = 0
     if per_rank:
@@ -1190,7 +1204,7 @@ def main():
             n_cols = per_rank[roof_rank]["rows"][1] - per_rank[roof_rank]["rows"][0]
     if k1_us is not None:
         traffic, tsrc, traffic_k3, live_note = None, None, None, None
-        if plain and not args.no_live_traffic:
+        if stock and not args.no_live_traffic:
             live, live_note = live_pmc_traffic(n_cols)
             if live is not None:
                 traffic, traffic_k3, tsrc = live["k_forward_bytes_per_launch"], live["k_backward_bytes_per_launch"], live_note
@@ -1239,13 +1253,13 @@ def main():
     if dumped is not None:
         out["dump_outputs"] = dumped
     out["verified"] = None
-    if per_rank:
+    if per_rank and full:
         out["verified"] = all(r["verified"] for r in per_rank)
         out["verified_detail"] = {"method": "every rank: sample_check (>= 4096 rows of its block incl. first and last row, inputs read "
                                             "back from its device, plain-C oracle) after the timed region; AND over ranks",
                                   "bit_exact": BIT_EXACT,
                                   "failures": [("rank %d: " % r["rank"]) + f for r in per_rank for f in r["check"].get("failures", [])]}
-    if args.cpu_seconds > 0 and world == 1:
+    if full and args.cpu_seconds > 0 and world == 1:
         gcm, zf, zh, prof = wl.host0
         m = min(n_cols, 8192)             # bounded sample: the first m columns of batch 0, whole passes
         gs = {k: numpy.ascontiguousarray(v[:m]) for k, v in gcm.items()}
@@ -1273,7 +1287,7 @@ def main():
                 out["cpu_baseline"]["all_cores"] = cpu_baseline_multicore(gs, zf, zh, ps, min(6.0, args.cpu_seconds), workers)
             except Exception as e:                       # a reported extra, never fatal
                 out["cpu_baseline"]["all_cores"] = {"error": repr(e)}
-    elif args.cpu_seconds > 0:
+    elif full and args.cpu_seconds > 0:
         out["cpu_baseline"] = None   # reported at N=1 only
     print(json.dumps(out))
     if dist is not None:
