@@ -39,13 +39,6 @@
 __constant__ double spc_pow_coef_table[21] = {SPC_POW_COEFS};
 #define SPC_POW_TABLE spc_pow_coef_table
 
-// Mutation control of the semantic tests (tools/mutation_control.py, never the shipped library): -DSPC_MUTANT=n perturbs ONE
-// line of a kernel -- the slip a transcription of the reference could contain -- and tests/test_semantic_gpu.py must fail.
-#ifndef SPC_MUTANT
-#define SPC_MUTANT 0
-#endif
-#define SPC_MUT(n, mutated, original) (SPC_MUTANT == (n) ? (mutated) : (original))
-
 namespace {
 
 constexpr int BLOCK = 256;
@@ -186,6 +179,17 @@ template <typename T> __device__ __forceinline__ int ss_right(const T *a, int n,
     return lo;
 }
 
+// numpy.searchsorted(a, v, side='left'): first i with !(a[i] < v)   (splib/sputils.py:88-91)
+template <typename T> __device__ __forceinline__ int ss_left(const T *a, int n, T key)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (np_lt(a[mid], key)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // numpy.searchsorted(-a, -v) (side='left'): first i with !(-a[i] < -v)   (splib/spcpl.py:498)
 template <typename T> __device__ __forceinline__ int ss_left_neg(const T *a, int n, T v)
 {
@@ -194,17 +198,6 @@ template <typename T> __device__ __forceinline__ int ss_left_neg(const T *a, int
     while (lo < hi) {
         int mid = lo + ((hi - lo) >> 1);
         if (np_lt(-a[mid], key)) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// numpy.searchsorted(a, key) (side='left'): first i with !(a[i] < key) -- only the mutation control uses it (SPC_MUTANT 5)
-template <typename T> __device__ __forceinline__ int ss_left_pos(const T *a, int n, T key)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int mid = lo + ((hi - lo) >> 1);
-        if (np_lt(a[mid], key)) lo = mid + 1; else hi = mid;
     }
     return lo;
 }
@@ -563,12 +556,12 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
             if constexpr (FULL)
                 if (OPT(Zf)) OPT(Zf)[g] = zf_k;                                         // spcpl.py:200
         }
-        s[2 * nG] = SPC_MUT(12, sh + ql, sh + ql + qi);                               // spcpl.py:215
+        s[2 * nG] = sh + ql + qi;                                                       // spcpl.py:215
         s[3 * nG] = ql;
-        SPC_MUT(6, lds + (size_t)c * 6 * nG + k, s)[4 * nG] = uu;
+        s[4 * nG] = uu;
         s[5 * nG] = vv;
-        const T iex = spc_pow(div_pref0(pf), SPC_MUT(1, K<T>::rd, -K<T>::rd) / K<T>::cp);   // sputils.py:34
-        s[nG] = SPC_MUT(8, tt + div_cp(K<T>::rlv * (ql + qi)), tt - div_cp(K<T>::rlv * (ql + qi))) * iex;   // spcpl.py:214
+        const T iex = spc_pow(div_pref0(pf), (-K<T>::rd) / K<T>::cp);                   // sputils.py:34
+        s[nG] = (tt - div_cp(K<T>::rlv * (ql + qi))) * iex;                             // spcpl.py:214
     }
     STAMP(2);
     __syncthreads();
@@ -582,14 +575,14 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
             if constexpr (FULL)
                 if (OPT(rainrate)) { sc_rain = OPT(rain)[col]; sc_rl = OPT(rain_last)[col]; }
         }
-        stg<WT>(&p.f_ps[col], Divisor<T>(p.dt).div(p.factor * SPC_MUT(14, sc_psd - sc_ps, sc_ps - sc_psd)));          // spcpl.py:332
+        stg<WT>(&p.f_ps[col], Divisor<T>(p.dt).div(p.factor * (sc_ps - sc_psd)));          // spcpl.py:332
         if constexpr (FULL) {
             if (OPT(ps)) OPT(ps)[col] = sc_ps;
-            if (OPT(rainrate)) OPT(rainrate)[col] = SPC_MUT(23, sc_rl - sc_rain, sc_rain - sc_rl) / p.dt;   // spcpl.py:325
+            if (OPT(rainrate)) OPT(rainrate)[col] = (sc_rain - sc_rl) / p.dt;           // spcpl.py:325
             if (OPT(wthl)) {                                                            // spcpl.py:136-167
-                const T rho = sc_ps / (K<T>::rd * ldg(&p.Tm[col * pitchG + SPC_MUT(15, 0, nG - 1)]));      // spcpl.py:153
+                const T rho = sc_ps / (K<T>::rd * ldg(&p.Tm[col * pitchG + (nG - 1)]));      // spcpl.py:153
                 OPT(wqt)[col] = -(OPT(QLflux)[col] + OPT(QIflux)[col] + OPT(SHflux)[col]) / rho;     // spcpl.py:159
-                OPT(wthl)[col] = -OPT(TSflux)[col] * spc_pow(div_pref0(sc_ps), SPC_MUT(17, K<T>::rd, -K<T>::rd) / K<T>::cp)
+                OPT(wthl)[col] = -OPT(TSflux)[col] * spc_pow(div_pref0(sc_ps), (-K<T>::rd) / K<T>::cp)
                                 / (K<T>::cp * rho);                                    // spcpl.py:161
                 if (OPT(z0m)) OPT(z0m)[col] = OPT(Z0M)[col];
                 if (OPT(z0h)) OPT(z0h)[col] = OPT(Z0H)[col];
@@ -614,8 +607,8 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
             }
             interp_fields<5>(b, f0, f1, r);
             const T thl = r[0], qt = r[1], ql = r[2], u = r[3], v = r[4];               // spcpl.py:224-228
-            stg<WT>(&p.f_u[o], ddt.div(p.factor * (u - SPC_MUT(2, in.vd, in.ud))));               // spcpl.py:328
-            stg<WT>(&p.f_v[o], ddt.div(p.factor * (v - SPC_MUT(2, in.ud, in.vd))));               // spcpl.py:329
+            stg<WT>(&p.f_u[o], ddt.div(p.factor * (u - in.ud)));               // spcpl.py:328
+            stg<WT>(&p.f_v[o], ddt.div(p.factor * (v - in.vd)));               // spcpl.py:329
             stg<WT>(&p.f_thl[o], ddt.div(p.factor * (thl - in.thld)));         // spcpl.py:330
             stg<WT>(&p.f_qt[o], ddt.div(p.factor * (qt - in.qtd)));            // spcpl.py:331
             stg<WT>(&p.f_ql[o], ddt.div(p.factor * (ql - in.qld)));            // spcpl.py:333
@@ -633,7 +626,7 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
             const T zs = (PRE && e == tid) ? pre_zs : ldg(&p.Zghalf[gh + nG]);
             const T Zh_k = div_grav(zgh - zs);                                        // spcpl.py:197
             const T *const zh = d.shared_grid ? lzh : lzh + (size_t)c * nL;
-            p.idx[col * pitchG + m] = SPC_MUT(5, ss_left_pos(zh, nL, Zh_k), ss_right(zh, nL, Zh_k));
+            p.idx[col * pitchG + m] = ss_right(zh, nL, Zh_k);
         }
     }
     STAMP(4);
@@ -741,7 +734,7 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
     if (PRE && tid < n1) {
         const int c = tid / nG, k = tid - c * nG;
         const int64_t cg = (col0 + c) * pitchG;
-        pre = load_gcm(p, cg + k, SPC_MUT(9, (col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG, cg) + (nG - 1 - k));
+        pre = load_gcm(p, cg + k, cg + (nG - 1 - k));
     }
     STAMP(1);
 
@@ -823,14 +816,14 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
         } else {
             t_i = qt_i = ql_i = qlw_i = qli_i = u_i = v_i = x;
         }
-        T f_T = ddt.div(p.factor * SPC_MUT(24, in.tt - t_i, t_i - in.tt));               // spcpl.py:518
-        T f_SH = ddt.div(p.factor * (SPC_MUT(13, qt_i, qt_i - ql_i) - in.sh));                            // spcpl.py:519
-        T f_QL = ddt.div(p.factor * (SPC_MUT(3, ql_i, qlw_i) - in.ql));                                    // spcpl.py:520
+        T f_T = ddt.div(p.factor * (t_i - in.tt));                                        // spcpl.py:518
+        T f_SH = ddt.div(p.factor * ((qt_i - ql_i) - in.sh));                            // spcpl.py:519
+        T f_QL = ddt.div(p.factor * (qlw_i - in.ql));                                    // spcpl.py:520
         T f_QI = ddt.div(p.factor * (qli_i - in.qi));                                    // spcpl.py:521
-        T f_U = ddt.div(p.factor * (SPC_MUT(22, v_i, u_i) - in.u));                      // spcpl.py:524
+        T f_U = ddt.div(p.factor * (u_i - in.u));                                         // spcpl.py:524
         T f_V = ddt.div(p.factor * (v_i - in.v));                                        // spcpl.py:525
         T f_A = ddt.div(p.factor * (in.a_d - in.a));                                     // spcpl.py:526
-        if (SPC_MUT(4, k <= start_index, k < start_index)) {  // `f[0:start_index] *= 0` (spcpl.py:527-533): -x -> -0, NaN stays NaN
+        if (k < start_index) {  // `f[0:start_index] *= 0` (spcpl.py:527-533): -x -> -0, NaN stays NaN
             const T zero = T(0);
             f_T *= zero; f_SH *= zero; f_QL *= zero; f_QI *= zero; f_U *= zero; f_V *= zero; f_A *= zero;
         }
@@ -852,7 +845,7 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
                 const int c = e / nG, k = e - c * nG;
                 const int64_t cg = (col0 + c) * pitchG;
                 in[u] = (PRE && e == tid) ? pre
-                                          : load_gcm(p, cg + k, SPC_MUT(9, (col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG, cg) + (nG - 1 - k));
+                                          : load_gcm(p, cg + k, cg + (nG - 1 - k));
             }
         }
 #pragma unroll
@@ -957,8 +950,8 @@ template <typename T, int NG, int NL, int WT> __global__ __launch_bounds__(BLOCK
             s[0] = zf_k;
             s[nG] = pf;
         }
-        if (p.Tv) stg<WT>(&p.Tv[g], tt * (T(1) + cc * sh - SPC_MUT(25, -(ql + qi), (ql + qi))));   // spcpl.py:176
-        if (p.QT) stg<WT>(&p.QT[g], sh + ql + SPC_MUT(26, T(0), qi));
+        if (p.Tv) stg<WT>(&p.Tv[g], tt * (T(1) + cc * sh - (ql + qi)));                 // spcpl.py:176
+        if (p.QT) stg<WT>(&p.QT[g], sh + ql + qi);
         if (p.Zf) stg<WT>(&p.Zf[g], zf_k);
         if (p.THL) stg<WT>(&p.THL[g], (tt - div_cp(K<T>::rlv * (ql + qi))) * spc_pow(div_pref0(pf), (-K<T>::rd) / K<T>::cp));
     }
@@ -966,7 +959,7 @@ template <typename T, int NG, int NL, int WT> __global__ __launch_bounds__(BLOCK
         for (int e = tid; e < ncol * (nG + 1); e += BLOCK) {
             const int c = e / (nG + 1), k = e - c * (nG + 1);
             const int64_t gh = (col0 + c) * pitchGh;
-            stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + SPC_MUT(27, nG - 1, nG)])));   // spcpl.py:197
+            stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + nG])));   // spcpl.py:197
         }
     }
     if (!les) return;                                                                  // (uniform: no barrier is skipped by part of a workgroup)
@@ -986,7 +979,7 @@ template <typename T, int NG, int NL, int WT> __global__ __launch_bounds__(BLOCK
         const T pf = r[0];                                                             // spcpl.py:408
         if (p.pf) stg<WT>(&p.pf[o], pf);
         if (p.t)                                                                       // spcpl.py:409
-            stg<WT>(&p.t[o], thl * spc_pow(div_pref0(pf), SPC_MUT(10, -K<T>::rd, K<T>::rd) / K<T>::cp) + div_cp(K<T>::rlv * qld));
+            stg<WT>(&p.t[o], thl * spc_pow(div_pref0(pf), K<T>::rd / K<T>::cp) + div_cp(K<T>::rlv * qld));
         if (p.ql_water) stg<WT>(&p.ql_water[o], qld - qid);                            // spcpl.py:402
     }
 }
@@ -1000,7 +993,7 @@ __global__ __launch_bounds__(BLOCK) void k_surface(int64_t n, const T *Ph_s, con
     for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
         const T ps = Ph_s[i];
         const T rho = ps / (K<T>::rd * T_s[i]);                                        // spcpl.py:153
-        wqt[i] = -(QLflux[i] + SPC_MUT(16, T(0), QIflux[i]) + SHflux[i]) / rho;       // spcpl.py:159
+        wqt[i] = -(QLflux[i] + QIflux[i] + SHflux[i]) / rho;                            // spcpl.py:159
         wthl[i] = -TSflux[i] * spc_pow(div_pref0(ps), (-K<T>::rd) / K<T>::cp) / (K<T>::cp * rho);   // spcpl.py:161
     }
 }

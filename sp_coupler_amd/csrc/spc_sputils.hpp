@@ -5,7 +5,7 @@
 //   integral / interp_c / interp_rho   splib/sputils.py:94-161, 173-189, 191-197
 //   rms                 splib/sputils.py:23-24
 // The fused kernels K1 / K3 / K4 contain the same arithmetic (and share the device functions: spc_pow, bracket /
-// interp_at, ss_right, scan_cell, vn_leaf / vn_pw); these entry points serve callers that use a helper on its own -- the
+// interp_at, ss_right / ss_left, scan_cell, vn_leaf / vn_pw); these entry points serve callers that use a helper on its own -- the
 // commented-out alternatives of spcpl.py:435-466, diagnostics, tests written against sputils -- for ALL rows (columns) at
 // once.  A "row" is one independent 1-D problem; arrays are [n_rows x n] with an element pitch between rows, pitch 0 =
 // one row shared by all.
@@ -218,17 +218,6 @@ template <typename T, int SL, int WT> __global__ __launch_bounds__(SU_THREADS) v
     }
 }
 
-// numpy.searchsorted(a, v, side='left'): first i with !(a[i] < v)   (splib/sputils.py:88-91)
-template <typename T> __device__ __forceinline__ int ss_left(const T *a, int n, T key)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (np_lt(a[mid], key)) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // ---- searchsorted --------------------------------------------------------------------------------------------------
 struct SuSearchP {
     int64_t n_rows, pitch_a, pitch_v, pitch_out;
@@ -354,7 +343,7 @@ template <typename T, int PD, int SL, bool WEIGHTED, int WT> __global__ __launch
                 const int e = e0 + u * SU_THREADS;
                 if (e < total) {
                     const T dz = z1[u] - z0[u];
-                    ltn[e] = (WEIGHTED && SPC_MUTANT != 7) ? (wv[u] * qv[u]) * dz : qv[u] * dz;             // sputils.py:154 / 146
+                    ltn[e] = WEIGHTED ? (wv[u] * qv[u]) * dz : qv[u] * dz;             // sputils.py:154 / 146
                     if constexpr (WEIGHTED) ltd[e] = wv[u] * dz;                       // sputils.py:159
                 }
             }

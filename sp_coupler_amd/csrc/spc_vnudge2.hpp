@@ -222,7 +222,7 @@ __global__ __launch_bounds__(VN2_THREADS, RCACHE ? 2 : 4) void k_vnudge_solve(co
     if (own) {
         if (valid) {
             // (float ql_ref: the double compare equals numpy's float32 one, whose weak 1e-9 rounds DOWN to float)
-            if (ql_ref > SPC_MUT(20, 1e-6, 1e-9)) { stage = VS_M0; touched = true; }  // spcpl.py:665
+            if (ql_ref > 1e-9) { stage = VS_M0; touched = true; }                     // spcpl.py:665
             else if (ql_av > ql_ref) { want_argmax = true; touched = true; }         // spcpl.py:679
         }
         s_mode[kl] = want_argmax ? 3 : 0;
@@ -603,7 +603,7 @@ template <typename T> __global__ __launch_bounds__(256) void k_vnudge_update(con
         s_coef[k] = ap == 1 ? p.beta[lev] - 1 : p.a_add[lev];
         s_av[k] = p.qt_av[lev];
         // (float: rd / cp in float equals NumPy's float32(287.04 / 1004.), the weak Python quotient)
-        s_tc[k] = th ? SPC_MUT(19, K<T>::rlv, -K<T>::rlv) / (K<T>::cp * spc_pow(div_pref0(p.presf[lev]), K<T>::rd / K<T>::cp)) : T(0);   // spcpl.py:731
+        s_tc[k] = th ? (-K<T>::rlv) / (K<T>::cp * spc_pow(div_pref0(p.presf[lev]), K<T>::rd / K<T>::cp)) : T(0);   // spcpl.py:731
         s_ap[k] = ap | (th ? 4 : 0);
         if (ap | (th ? 4 : 0)) s_any = 1;
     }
@@ -622,8 +622,8 @@ template <typename T> __global__ __launch_bounds__(256) void k_vnudge_update(con
         for (int ij = ij0 + rq; ij < ij1; ij += 8) {
             const int64_t g = base + (int64_t)ij * ktot + k;
             T v = p.qt[g];
-            if ((ap & 3) == 1) { v = (T)((double)v + coef * (double)SPC_MUT(18, v, (v - qt_av))); p.qt[g] = v; } // spcpl.py:724-725
-            else if ((ap & 3) == 2) { v = (T)SPC_MUT(21, (double)v - coef * R[ij], (double)v + coef * R[ij]); p.qt[g] = v; }   // spcpl.py:716-719
+            if ((ap & 3) == 1) { v = (T)((double)v + coef * (double)(v - qt_av)); p.qt[g] = v; } // spcpl.py:724-725
+            else if ((ap & 3) == 2) { v = (T)((double)v + coef * R[ij]); p.qt[g] = v; }   // spcpl.py:716-719
             if (ap & 4) {                                                                   // spcpl.py:726-733
                 const T tt = v - p.qsat[g];
                 const T ql_target = (tt >= T(0) || tt != tt) ? tt : T(0);

@@ -1,46 +1,143 @@
 #!/usr/bin/env python3
 """Mutation control of the semantic tests (round-4 verdict, next 2: "each property fails when the corresponding line of the
-kernel is perturbed").  For the shipped library and for every mutant build/mutants/libspc_mutantN.so (tools/build_mutants.sh:
-ONE kernel line perturbed each, -DSPC_MUTANT=N) the properties of tests/semantic_props.py run through the HIP kernels, in ONE
-process (Engine(lib_path=...)).  Expected: the shipped library passes all, every mutant fails at least the property that
-guards its line.  Prints a table; exit status 1 if a mutant survives or the shipped library fails.
-usage: python tools/mutation_control.py > profiles/r05_mutation_control.log"""
+kernel is perturbed").  Each mutant is ONE slip a transcription of the reference could contain, kept here as text edits of the
+kernel sources (MUTANTS); the shipped sources hold only the shipped code.  --build copies sp_coupler_amd/csrc/ to
+build/mutants/src<n>/, applies mutant n's edits and compiles build/mutants/libspc_mutant<n>.so (on any host: hipcc
+cross-compiles gfx950).  A run without --build (GPU) runs the properties of tests/semantic_props.py through the HIP kernels of
+the shipped library and of every mutant library, in ONE process (Engine(lib_path=...)).  Expected: the shipped library passes
+all, every mutant fails at least the property that guards its line.  Prints a table; exit status 1 if a mutant survives or
+the shipped library fails.  tests/test_mutation_table.py checks on the CPU that every edit still applies to the tree.
+usage: python tools/mutation_control.py --build [n ...] [-j N]
+       python tools/mutation_control.py > profiles/mutation_control.log"""
+import argparse
 import os
+import shutil
+import subprocess
 import sys
 import traceback
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from __graft_entry__ import HIPCC, HIP_FLAGS  # noqa: E402  (the shipped library's compiler and flags)
 
+CSRC = os.path.join(ROOT, "sp_coupler_amd", "csrc")
+OUT = os.path.join(ROOT, "build", "mutants")
+H, K4, VN2, SU = "spc_hip.hip", "spc_k4.hpp", "spc_vnudge2.hpp", "spc_sputils.hpp"
+A9 = "(col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG"     # the neighbouring column of the slab (mutant 9)
+
+# n: (the slip, the property of tests/semantic_props.py that guards it,
+#     edits: (file under csrc/, exact old text, new text[, occurrences of the old text, default 1]), applied in order)
 MUTANTS = {
-    1: ("K1 thl: exponent +rd/cp instead of -rd/cp (exner for iexner, sputils.py:28-34)", "isentropic_column_has_constant_thl"),
-    2: ("K1 forcings: u_d and v_d swapped (spcpl.py:328-329)", "zero_forcings_when_the_les_equals_the_interpolated_gcm_profile"),
-    3: ("K3 f_QL from ql instead of ql_water = ql - ql_ice (spcpl.py:402, 520)", "total_water_tendency_closes"),
-    4: ("K3 masking one level too far: k <= start_index (spcpl.py:527-533)", "masking_above_the_les_top"),
-    5: ("K2 index map with side='left' instead of 'right' (spcpl.py:764)", "index_map_is_a_count"),
-    6: ("K1 staging: U not reversed (spcpl.py:227)", "reversal_is_index_arithmetic_only"),
-    7: ("K7 interp_c: numerator without the weight rho (sputils.py:152-154)", "conservative_coarsening_conserves"),
-    8: ("K1 thl: latent term added instead of subtracted (spcpl.py:214)", "isentropic_column_has_constant_thl"),
-    9: ("K3 cloud fraction A_d read from the neighbouring column of the slab (spcpl.py:404)", "columns_are_independent"),
-    10: ("K5 t: exponent -rd/cp instead of +rd/cp (spcpl.py:409)", "isentropic_column_has_constant_thl"),
-    11: ("K4 f_T: numerator without the weight rho (spcpl.py:482, sputils.py:152)", "conservative_coarsening_conserves"),
-    12: ("K1 qt_ = SH + QL, the ice forgotten (spcpl.py:215)", "reversal_is_index_arithmetic_only"),
-    13: ("K3 f_SH from qt instead of qt - ql (spcpl.py:519: SH is vapour only)", "total_water_tendency_closes"),
-    14: ("K1 f_ps with the opposite sign (spcpl.py:332)", "zero_forcings_when_the_les_equals_the_interpolated_gcm_profile"),
-    15: ("K1 surface branch: density from T at the model top instead of the lowest level (spcpl.py:153)", "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density"),
-    16: ("k_surface: wqt without the ice flux QIflux (spcpl.py:159)", "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density"),
-    17: ("K1 surface branch: wthl with exner instead of iexner (spcpl.py:161)", "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density"),
-    18: ("K6 update: qt += (beta - 1) qt, the level mean forgotten (spcpl.py:724)", "variability_nudge_reaches_the_gcm_cloud_amount"),
-    19: ("K6 constantT: dTHL with the opposite sign (spcpl.py:731)", "variability_nudge_reaches_the_gcm_cloud_amount"),
-    20: ("K6: 'significant cloud' threshold 1e-6 instead of 1e-9 (spcpl.py:665)", "variability_nudge_reaches_the_gcm_cloud_amount"),
-    21: ("K6 additive noise subtracted instead of added (spcpl.py:716-719)", "variability_nudge_reaches_the_gcm_cloud_amount"),
-    22: ("K3 f_U from the LES v instead of u (spcpl.py:524)", "tendencies_relax_the_gcm_towards_the_les_profile"),
-    23: ("K1 rainrate with the opposite sign (spcpl.py:325)", "tendencies_relax_the_gcm_towards_the_les_profile"),
-    24: ("K3 f_T with the opposite sign (spcpl.py:518)", "tendencies_relax_the_gcm_towards_the_les_profile"),
-    25: ("K5 Tv: the condensate load added instead of subtracted (spcpl.py:176)", "gcm_level_diagnostics_mean_what_their_names_say"),
-    26: ("K5 QT without the ice (spcpl.py:215)", "gcm_level_diagnostics_mean_what_their_names_say"),
-    27: ("K5 Zh above the lowest FULL-level interface instead of the surface (spcpl.py:197)", "gcm_level_diagnostics_mean_what_their_names_say"),
+    1: ("K1 thl: exponent +rd/cp instead of -rd/cp (exner for iexner, sputils.py:28-34)", "isentropic_column_has_constant_thl",
+        [(H, "const T iex = spc_pow(div_pref0(pf), (-K<T>::rd) / K<T>::cp);", "const T iex = spc_pow(div_pref0(pf), K<T>::rd / K<T>::cp);")]),
+    2: ("K1 forcings: u_d and v_d swapped (spcpl.py:328-329)", "zero_forcings_when_the_les_equals_the_interpolated_gcm_profile",
+        [(H, "ddt.div(p.factor * (u - in.ud))", "ddt.div(p.factor * (u - in.vd))"),
+         (H, "ddt.div(p.factor * (v - in.vd))", "ddt.div(p.factor * (v - in.ud))")]),
+    3: ("K3 f_QL from ql instead of ql_water = ql - ql_ice (spcpl.py:402, 520)", "total_water_tendency_closes",
+        [(H, "T f_QL = ddt.div(p.factor * (qlw_i - in.ql));", "T f_QL = ddt.div(p.factor * (ql_i - in.ql));")]),
+    4: ("K3 masking one level too far: k <= start_index (spcpl.py:527-533)", "masking_above_the_les_top",
+        [(H, "if (k < start_index) {", "if (k <= start_index) {")]),
+    5: ("K2 index map with side='left' instead of 'right' (spcpl.py:764)", "index_map_is_a_count",
+        [(H, "p.idx[col * pitchG + m] = ss_right(zh, nL, Zh_k);", "p.idx[col * pitchG + m] = ss_left(zh, nL, Zh_k);")]),
+    6: ("K1 staging: U not reversed (spcpl.py:227)", "reversal_is_index_arithmetic_only",
+        [(H, "s[4 * nG] = uu;", "(lds + (size_t)c * 6 * nG + k)[4 * nG] = uu;")]),
+    7: ("K7 interp_c: numerator without the weight rho (sputils.py:152-154)", "conservative_coarsening_conserves",
+        [(SU, "ltn[e] = WEIGHTED ? (wv[u] * qv[u]) * dz : qv[u] * dz;", "ltn[e] = qv[u] * dz;")]),
+    8: ("K1 thl: latent term added instead of subtracted (spcpl.py:214)", "isentropic_column_has_constant_thl",
+        [(H, "s[nG] = (tt - div_cp(K<T>::rlv * (ql + qi))) * iex;", "s[nG] = (tt + div_cp(K<T>::rlv * (ql + qi))) * iex;")]),
+    9: ("K3 cloud fraction A_d read from the neighbouring column of the slab (spcpl.py:404)", "columns_are_independent",
+        [(H, "load_gcm(p, cg + k, cg + (nG - 1 - k))", "load_gcm(p, cg + k, " + A9 + " + (nG - 1 - k))", 2)]),
+    10: ("K5 t: exponent -rd/cp instead of +rd/cp (spcpl.py:409)", "isentropic_column_has_constant_thl",
+         [(H, "thl * spc_pow(div_pref0(pf), K<T>::rd / K<T>::cp)", "thl * spc_pow(div_pref0(pf), (-K<T>::rd) / K<T>::cp)")]),
+    11: ("K4 f_T: numerator without the weight rho (spcpl.py:482, sputils.py:152)", "conservative_coarsening_conserves",
+         [(K4, "s[0] = w * t;", "s[0] = t;")]),
+    12: ("K1 qt_ = SH + QL, the ice forgotten (spcpl.py:215)", "reversal_is_index_arithmetic_only",
+         [(H, "s[2 * nG] = sh + ql + qi;", "s[2 * nG] = sh + ql;")]),
+    13: ("K3 f_SH from qt instead of qt - ql (spcpl.py:519: SH is vapour only)", "total_water_tendency_closes",
+         [(H, "T f_SH = ddt.div(p.factor * ((qt_i - ql_i) - in.sh));", "T f_SH = ddt.div(p.factor * (qt_i - in.sh));")]),
+    14: ("K1 f_ps with the opposite sign (spcpl.py:332)", "zero_forcings_when_the_les_equals_the_interpolated_gcm_profile",
+         [(H, "Divisor<T>(p.dt).div(p.factor * (sc_ps - sc_psd))", "Divisor<T>(p.dt).div(p.factor * (sc_psd - sc_ps))")]),
+    15: ("K1 surface branch: density from T at the model top instead of the lowest level (spcpl.py:153)",
+         "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density",
+         [(H, "ldg(&p.Tm[col * pitchG + (nG - 1)])", "ldg(&p.Tm[col * pitchG + 0])")]),
+    16: ("k_surface: wqt without the ice flux QIflux (spcpl.py:159)", "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density",
+         [(H, "wqt[i] = -(QLflux[i] + QIflux[i] + SHflux[i]) / rho;", "wqt[i] = -(QLflux[i] + T(0) + SHflux[i]) / rho;")]),
+    17: ("K1 surface branch: wthl with exner instead of iexner (spcpl.py:161)", "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density",
+         [(H, "spc_pow(div_pref0(sc_ps), (-K<T>::rd) / K<T>::cp)", "spc_pow(div_pref0(sc_ps), K<T>::rd / K<T>::cp)")]),
+    18: ("K6 update: qt += (beta - 1) qt, the level mean forgotten (spcpl.py:724)", "variability_nudge_reaches_the_gcm_cloud_amount",
+         [(VN2, "v = (T)((double)v + coef * (double)(v - qt_av));", "v = (T)((double)v + coef * (double)v);")]),
+    19: ("K6 constantT: dTHL with the opposite sign (spcpl.py:731)", "variability_nudge_reaches_the_gcm_cloud_amount",
+         [(VN2, "s_tc[k] = th ? (-K<T>::rlv) / (", "s_tc[k] = th ? K<T>::rlv / (")]),
+    20: ("K6: 'significant cloud' threshold 1e-6 instead of 1e-9 (spcpl.py:665)", "variability_nudge_reaches_the_gcm_cloud_amount",
+         [(VN2, "if (ql_ref > 1e-9) {", "if (ql_ref > 1e-6) {")]),
+    21: ("K6 additive noise subtracted instead of added (spcpl.py:716-719)", "variability_nudge_reaches_the_gcm_cloud_amount",
+         [(VN2, "v = (T)((double)v + coef * R[ij]);", "v = (T)((double)v - coef * R[ij]);")]),
+    22: ("K3 f_U from the LES v instead of u (spcpl.py:524)", "tendencies_relax_the_gcm_towards_the_les_profile",
+         [(H, "T f_U = ddt.div(p.factor * (u_i - in.u));", "T f_U = ddt.div(p.factor * (v_i - in.u));")]),
+    23: ("K1 rainrate with the opposite sign (spcpl.py:325)", "tendencies_relax_the_gcm_towards_the_les_profile",
+         [(H, "OPT(rainrate)[col] = (sc_rain - sc_rl) / p.dt;", "OPT(rainrate)[col] = (sc_rl - sc_rain) / p.dt;")]),
+    24: ("K3 f_T with the opposite sign (spcpl.py:518)", "tendencies_relax_the_gcm_towards_the_les_profile",
+         [(H, "T f_T = ddt.div(p.factor * (t_i - in.tt));", "T f_T = ddt.div(p.factor * (in.tt - t_i));")]),
+    25: ("K5 Tv: the condensate load added instead of subtracted (spcpl.py:176)", "gcm_level_diagnostics_mean_what_their_names_say",
+         [(H, "tt * (T(1) + cc * sh - (ql + qi))", "tt * (T(1) + cc * sh - (-(ql + qi)))")]),
+    26: ("K5 QT without the ice (spcpl.py:215)", "gcm_level_diagnostics_mean_what_their_names_say",
+         [(H, "stg<WT>(&p.QT[g], sh + ql + qi);", "stg<WT>(&p.QT[g], sh + ql + T(0));")]),
+    27: ("K5 Zh above the lowest FULL-level interface instead of the surface (spcpl.py:197)",
+         "gcm_level_diagnostics_mean_what_their_names_say",
+         [(H, "stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + nG])));",
+           "stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + (nG - 1)])));")]),
 }
+
+
+def patched(n, src=CSRC):
+    """{file: text} of the files mutant n changes, its edits applied to the sources under `src`; ValueError when an edit's
+    old text does not occur exactly the expected number of times (the tree has drifted from the table)"""
+    files = {}
+    for edit in MUTANTS[n][2]:
+        name, old, new = edit[:3]
+        want = edit[3] if len(edit) > 3 else 1
+        if name not in files:
+            with open(os.path.join(src, name)) as f:
+                files[name] = f.read()
+        got = files[name].count(old)
+        if got != want:
+            raise ValueError("mutant %d: %r occurs %d times in %s, expected %d" % (n, old, got, name, want))
+        files[name] = files[name].replace(old, new)
+    return files
+
+
+def build_one(n):
+    src = os.path.join(OUT, "src%d" % n)
+    shutil.rmtree(src, ignore_errors=True)
+    shutil.copytree(CSRC, src)
+    for name, text in patched(n).items():
+        with open(os.path.join(src, name), "w") as f:
+            f.write(text)
+    lib = os.path.join(OUT, "libspc_mutant%d.so" % n)
+    r = subprocess.run([HIPCC] + HIP_FLAGS + [os.path.join(src, "spc_hip.hip"), "-o", lib], cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode:
+        raise RuntimeError("mutant %d: hipcc exit status %d\n%s" % (n, r.returncode, r.stdout[-2000:]))
+    return lib
+
+
+def build(ns, jobs):
+    os.makedirs(OUT, exist_ok=True)
+    bad = 0
+
+    def one(n):
+        try:
+            build_one(n)
+            return "mutant %d built" % n, 0
+        except (ValueError, RuntimeError) as e:
+            return "mutant %d FAILED: %s" % (n, e), 1
+
+    with ThreadPoolExecutor(max(1, min(jobs, 16))) as pool:
+        for line, failed in pool.map(one, ns):
+            print(line, flush=True)
+            bad += failed
+    return 1 if bad else 0
 
 
 def run(lib_path):
@@ -66,8 +163,8 @@ def main():
     from tests import semantic_props as sp
     print("shipped library: %d properties, failed: %s" % (len(sp.PROPERTIES), clean or "none"))
     bad += bool(clean)
-    for n, (what, guard) in sorted(MUTANTS.items()):
-        path = os.path.join(ROOT, "build", "mutants", "libspc_mutant%d.so" % n)
+    for n, (what, guard, _) in sorted(MUTANTS.items()):
+        path = os.path.join(OUT, "libspc_mutant%d.so" % n)
         if not os.path.exists(path):
             print("mutant %2d: NOT BUILT (%s)" % (n, path))
             bad += 1
@@ -81,4 +178,14 @@ def main():
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description="mutation control of the semantic tests")
+    ap.add_argument("--build", nargs="*", type=int, metavar="n",
+                    help="build the mutant libraries n ... (default: all) instead of running the control")
+    ap.add_argument("-j", type=int, default=4, help="parallel compiles for --build (at most 16)")
+    args = ap.parse_args()
+    if args.build is not None:
+        unknown = sorted(set(args.build) - set(MUTANTS))
+        if unknown:
+            ap.error("no mutant %s" % unknown)
+        sys.exit(build(args.build or sorted(MUTANTS), args.j))
     sys.exit(main())
