@@ -272,6 +272,38 @@ int spc_interp_c_f32(const spc_interp_c_args *args, void *stream);
 int spc_rms_f64(int64_t n_rows, int64_t n, int64_t pitch, const void *a, void *out, void *stream);
 int spc_rms_f32(int64_t n_rows, int64_t n, int64_t pitch, const void *a, void *out, void *stream);
 
+/* ---- geometry of sputils.get_mask_indices, splib/sputils.py:46-73 (kernel family K8) ------------------------- */
+/* Which GCM columns get an LES.  Everything is double, whatever the engine's dtype.
+ * spc_point_in_polygon_f64: the location of every point p = (lon, lat) and of its image q = ((lon - 180) % 360 - 180,
+ * lat) (Python's float %) in every polygon of the launch, in exact arithmetic, by GEOS's ray-crossing and point-locator
+ * rules.  The vertices of all rings are concatenated in vx / vy; ring r is vertices
+ * ring_start[r] ... ring_start[r+1]-1, CLOSED (last vertex == first).  Rings are grouped by polygon: ring_poly is
+ * non-decreasing, and every polygon's first ring is its shell (SPC_RING_SHELL, or SPC_RING_RECTANGLE for an axis-aligned
+ * rectangle without holes: strictly-inside rule of GEOS's RectangleContains), its holes follow (SPC_RING_HOLE).
+ * out[k * n_points + i] = code of p | code of q << 8 in polygon k, codes SPC_LOC_*.  A layout that breaks these rules gives
+ * undefined codes, never an access outside the arrays.  All arrays are device memory.
+ * spc_haversine_f64: out[i] = great-circle distance in km from (lon[i], lat[i]) to (lon0, lat0), splib/haversine.py:12-36
+ * operation by operation (R = 6371 km).                                                                              */
+#define SPC_RING_SHELL 0
+#define SPC_RING_HOLE 1
+#define SPC_RING_RECTANGLE 2
+#define SPC_LOC_EXTERIOR 0
+#define SPC_LOC_BOUNDARY 1
+#define SPC_LOC_INTERIOR 2
+typedef struct spc_pip_args {
+    int64_t n_points;
+    int64_t n_vertices;
+    int32_t n_rings, n_polys;
+    const double *lon, *lat;       /* [n_points] grid point coordinates (degrees)                   */
+    const double *vx, *vy;         /* [n_vertices] ring vertices, rings one after another, closed   */
+    const int64_t *ring_start;     /* [n_rings + 1] first vertex of each ring; ring_start[n_rings] == n_vertices */
+    const int32_t *ring_role;      /* [n_rings] SPC_RING_SHELL / SPC_RING_HOLE / SPC_RING_RECTANGLE  */
+    const int32_t *ring_poly;      /* [n_rings] polygon id 0 ... n_polys-1, non-decreasing          */
+    uint16_t *out;                 /* [n_polys x n_points] location codes                           */
+} spc_pip_args;
+int spc_point_in_polygon_f64(const spc_pip_args *args, void *stream);
+int spc_haversine_f64(int64_t n, const void *lon, const void *lat, double lon0, double lat0, void *out, void *stream);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */
 const char *spc_last_error(void);   /* text of the calling thread's last failure ("" if none)     */

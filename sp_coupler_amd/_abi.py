@@ -86,6 +86,15 @@ class InterpCArgs(ctypes.Structure):
                 + [("mode", c_int32), ("reserved", c_int32)])
 
 
+class PipArgs(ctypes.Structure):
+    _fields_ = ([("n_points", c_int64), ("n_vertices", c_int64), ("n_rings", c_int32), ("n_polys", c_int32)]
+                + _ptrs("lon", "lat", "vx", "vy", "ring_start", "ring_role", "ring_poly", "out"))
+
+
+SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
+SPC_LOC_EXTERIOR, SPC_LOC_BOUNDARY, SPC_LOC_INTERIOR = 0, 1, 2
+
+
 #: every symbol include/spc.h declares: name -> (restype, argtypes)
 PROTOTYPES = {
     "spc_forward_f64": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.POINTER(ForwardArgs), c_void_p]),
@@ -110,6 +119,8 @@ PROTOTYPES = {
     "spc_interp_c_f32": (ctypes.c_int, [ctypes.POINTER(InterpCArgs), c_void_p]),
     "spc_rms_f64": (ctypes.c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "spc_rms_f32": (ctypes.c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "spc_point_in_polygon_f64": (ctypes.c_int, [ctypes.POINTER(PipArgs), c_void_p]),
+    "spc_haversine_f64": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

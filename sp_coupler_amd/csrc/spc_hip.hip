@@ -10,6 +10,7 @@
 //   K4 k_backward_cons  the same with conservative (rho-weighted layer-mean) coarsening
 //   K5 k_diag      spifs.nc diagnostics
 //   K6 k_vnudge_*  variability nudge (qt_forcing == 'variance'): spc_vnudge.hpp, spc_vnudge2.hpp
+//   K8 k_point_in_polygon, k_haversine  column selection of sputils.get_mask_indices: spc_geo.hpp
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
 // a 256-thread workgroup owns CB consecutive columns; the source profiles of those columns are
 // loaded with flat, fully coalesced accesses over the contiguous [CB x n_lev] slab, converted and
@@ -917,6 +918,7 @@ template <int SL, typename T, typename Pred> __device__ __forceinline__ int su_c
 
 #include "spc_k4.hpp"
 #include "spc_sputils.hpp"
+#include "spc_geo.hpp"
 
 // =================================================================================================
 // K5 diagnostics: splib/spcpl.py:176, 197-198, 214-215 (GCM levels); 402, 408-409 (LES levels)
@@ -1720,6 +1722,40 @@ template <typename T> static int vnudge_impl(const spc_vnudge_args *a, void *str
     }
 }
 
+// ---- K8: geometry of sputils.get_mask_indices (kernels: spc_geo.hpp) ---------------------------
+int pip_impl(const spc_pip_args *a, void *stream)
+{
+    REQUIRE(a, "args");
+    if (a->n_points < 0 || a->n_vertices < 0 || a->n_rings < 0 || a->n_polys < 0)
+        return fail(SPC_ERR_INVALID_ARGUMENT, "%spoint_in_polygon: negative count");
+    if (a->n_points == 0 || a->n_polys == 0) return SPC_OK;
+    if (a->n_rings < 1) return fail(SPC_ERR_INVALID_ARGUMENT, "%spoint_in_polygon: %lld polygons but no ring", "", a->n_polys);
+    REQUIRE(a->lon, "lon"); REQUIRE(a->lat, "lat"); REQUIRE(a->ring_start, "ring_start"); REQUIRE(a->ring_role, "ring_role");
+    REQUIRE(a->ring_poly, "ring_poly"); REQUIRE(a->out, "out");
+    if (a->n_vertices > 0) { REQUIRE(a->vx, "vx"); REQUIRE(a->vy, "vy"); }
+    if ((uintptr_t)a->out % alignof(uint16_t) != 0) return fail(SPC_ERR_INVALID_ARGUMENT, "%spoint_in_polygon: out is not 2-byte aligned");
+    const int64_t grid = (a->n_points + GEO_THREADS - 1) / GEO_THREADS;
+    if (grid > 0x7fffffff) return fail(SPC_ERR_UNSUPPORTED, "%spoint_in_polygon: more than 2^39 points");
+    GeoP p;
+    p.n_points = a->n_points; p.n_vertices = a->n_vertices; p.n_rings = a->n_rings; p.n_polys = a->n_polys;
+    p.lon = a->lon; p.lat = a->lat; p.vx = a->vx; p.vy = a->vy;
+    p.ring_start = a->ring_start; p.ring_role = a->ring_role; p.ring_poly = a->ring_poly; p.out = a->out;
+    hipLaunchKernelGGL(k_point_in_polygon, dim3((unsigned)grid), dim3(GEO_THREADS), 0, (hipStream_t)stream, p);
+    return launch_status("k_point_in_polygon");
+}
+
+int haversine_impl(int64_t n, const void *lon, const void *lat, double lon0, double lat0, void *out, void *stream)
+{
+    if (n < 0) return fail(SPC_ERR_INVALID_ARGUMENT, "%shaversine: n < 0");
+    if (n == 0) return SPC_OK;
+    REQUIRE(lon, "lon"); REQUIRE(lat, "lat"); REQUIRE(out, "out");
+    const int64_t grid = (n + GEO_THREADS - 1) / GEO_THREADS;
+    if (grid > 0x7fffffff) return fail(SPC_ERR_UNSUPPORTED, "%shaversine: more than 2^39 points");
+    hipLaunchKernelGGL(k_haversine, dim3((unsigned)grid), dim3(GEO_THREADS), 0, (hipStream_t)stream, n, (const double *)lon,
+                       (const double *)lat, lon0, lat0, (double *)out);
+    return launch_status("k_haversine");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1756,6 +1792,12 @@ int spc_interp_c_f64(const spc_interp_c_args *a, void *s) { return interp_c_impl
 int spc_interp_c_f32(const spc_interp_c_args *a, void *s) { return interp_c_impl<float>(a, s); }
 int spc_rms_f64(int64_t nr, int64_t n, int64_t pitch, const void *a, void *out, void *s) { return rms_impl<double>(nr, n, pitch, a, out, s); }
 int spc_rms_f32(int64_t nr, int64_t n, int64_t pitch, const void *a, void *out, void *s) { return rms_impl<float>(nr, n, pitch, a, out, s); }
+
+int spc_point_in_polygon_f64(const spc_pip_args *a, void *s) { return pip_impl(a, s); }
+int spc_haversine_f64(int64_t n, const void *lon, const void *lat, double lon0, double lat0, void *out, void *s)
+{
+    return haversine_impl(n, lon, lat, lon0, lat0, out, s);
+}
 
 int spc_surface_fluxes_f64(int64_t n, const void *Ph_s, const void *T_s, const void *QLflux, const void *QIflux,
                            const void *SHflux, const void *TSflux, void *wthl, void *wqt, void *stream)

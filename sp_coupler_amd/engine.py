@@ -741,3 +741,46 @@ class Engine:
     def surface_fluxes(self, Ph_s, T_s, QLflux, QIflux, SHflux, TSflux, stream=None):
         r = self.plan_surface_fluxes(Ph_s, T_s, QLflux, QIflux, SHflux, TSflux).launch(stream)
         return r["wthl"], r["wqt"]
+
+    # -- K8: the geometry of sputils.get_mask_indices (splib/sputils.py:46-73); float64 on every engine ---------------
+    def _vector(self, name, t, n=None, dtype=torch.float64):
+        """``t`` as a contiguous 1-D ``dtype`` tensor on the engine's device (converted / copied where it is not one)"""
+        t = torch.as_tensor(t, dtype=dtype)
+        if t.dim() != 1 or (n is not None and t.shape[0] != n):
+            raise ValueError("%s must be a vector%s, got %s" % (name, "" if n is None else " of %d" % n, tuple(t.shape)))
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    @_on_engine_stream
+    def point_in_polygon(self, lon, lat, vx, vy, ring_start, ring_role, ring_poly, n_polys=None, stream=None):
+        """Location (include/spc.h SPC_LOC_*) of every grid point (lon[i], lat[i]) and of its image
+        ((lon - 180) % 360 - 180, lat) in every polygon: a uint8 tensor [n_polys x n x 2] ([..., 0] the point, [..., 1] its
+        image).  Rings: vertices vx / vy concatenated, ring r = vx[ring_start[r]:ring_start[r+1]], closed, grouped by
+        polygon (ring_poly non-decreasing, shell first); ring_role SPC_RING_SHELL / _HOLE / _RECTANGLE.  float64 whatever
+        the engine's dtype: an fp32 engine takes the same decisions."""
+        lon = self._vector("lon", lon)
+        n = int(lon.shape[0])
+        lat = self._vector("lat", lat, n)
+        vx = self._vector("vx", vx)
+        nv = int(vx.shape[0])
+        vy = self._vector("vy", vy, nv)
+        ring_role = self._vector("ring_role", ring_role, dtype=torch.int32)
+        nr = int(ring_role.shape[0])
+        ring_start = self._vector("ring_start", ring_start, nr + 1, dtype=torch.int64)
+        ring_poly = self._vector("ring_poly", ring_poly, nr, dtype=torch.int32)
+        if n_polys is None:
+            n_polys = int(ring_poly.max()) + 1 if nr else 0
+        out = torch.zeros(n_polys, n, 2, dtype=torch.uint8, device=self.device)
+        a = _abi.PipArgs(n, nv, nr, n_polys, lon.data_ptr(), lat.data_ptr(), vx.data_ptr(), vy.data_ptr(), ring_start.data_ptr(),
+                         ring_role.data_ptr(), ring_poly.data_ptr(), out.data_ptr())
+        self._call(self.lib.spc_point_in_polygon_f64, ctypes.byref(a), stream=stream)
+        return out
+
+    @_on_engine_stream
+    def haversine(self, lon, lat, lon0, lat0, stream=None):
+        """great-circle distance in km of every (lon[i], lat[i]) to (lon0, lat0), splib/haversine.py:12-36; float64"""
+        lon = self._vector("lon", lon)
+        n = int(lon.shape[0])
+        lat = self._vector("lat", lat, n)
+        out = torch.empty(n, dtype=torch.float64, device=self.device)
+        self._call(self.lib.spc_haversine_f64, n, lon.data_ptr(), lat.data_ptr(), float(lon0), float(lat0), out.data_ptr(), stream=stream)
+        return out

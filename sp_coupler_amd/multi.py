@@ -238,6 +238,13 @@ class MultiDeviceEngine:
     def rms(self, a, **kw):
         return self._run("rms", a, **kw)
 
+    # the geometry of sputils.get_mask_indices (K8): once at start-up, on the primary engine
+    def point_in_polygon(self, *a, **kw):
+        return self.primary.point_in_polygon(*a, **kw)
+
+    def haversine(self, *a, **kw):
+        return self.primary.haversine(*a, **kw)
+
     def on_stream(self):
         """the slow paths run on the primary engine: its stream context (Engine.on_stream)"""
         return self.primary.on_stream()

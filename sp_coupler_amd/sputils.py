@@ -10,8 +10,13 @@ download); device tensors in -> device tensors out (no transfer).  Results equal
 ``exner`` / ``iexner`` (own ``pow``: <= 2 ulp of ``numpy.power``).
 
 The fused step kernels (K1 / K3 / K4) contain the same arithmetic and do not call these; they serve callers that use a
-helper on its own.  Host-only helpers of the reference's module that are not arithmetic on columns
-(``get_mask_indices``, ``link_dir``: shapely / file system, run once at start-up) are out of scope.
+helper on its own.
+
+``get_mask_indices`` (sputils.py:46-73), the column selection of ``splib.initialize``, runs on the K8 kernels
+(``spc_point_in_polygon_f64``, ``spc_haversine_f64``) in float64 on any engine, with the masks of
+``sp_coupler_amd.geometry`` (shapely's ``Point`` / ``Polygon`` / ``box`` / ``shape``) or shapely's own objects; shapely
+itself is not needed.  ``find_closest_points`` is plain host code.  ``link_dir`` (file system, start-up) is out of scope
+(DESIGN.md section 7).
 """
 import numpy
 import torch
@@ -257,3 +262,74 @@ def find_closest_points(points, target):
     lng2, lat2 = numpy.radians(numpy.asarray(target, dtype=numpy.float64))
     d = numpy.sin((lat2 - lat1) * 0.5) ** 2 + numpy.cos(lat1) * numpy.cos(lat2) * numpy.sin((lng2 - lng1) * 0.5) ** 2
     return numpy.argsort(2 * 6371 * numpy.arcsin(numpy.sqrt(d)))
+
+
+def _lonlat(points, eng):
+    """(lon, lat) float64 vectors on the engine's device from a list of (lon, lat) tuples, an [n x 2] array or an [n x 2]
+    tensor; and whether the caller's points were on a device"""
+    if isinstance(points, torch.Tensor):
+        on_device = points.device.type == "cuda"
+        t = points.reshape(-1, 2)
+    else:
+        on_device = False
+        t = torch.from_numpy(numpy.asarray(points, dtype=numpy.float64).reshape(-1, 2))
+    t = t.to(device=eng.device, dtype=torch.float64)
+    return t[:, 0].contiguous(), t[:, 1].contiguous(), on_device
+
+
+SPC_LOC_BOUNDARY, SPC_LOC_INTERIOR = 1, 2          # include/spc.h SPC_LOC_*
+
+
+def _contains(codes):
+    """[n x 2] bool: where ``contains`` holds for the point and for its image, from the location codes [n_polys x n x 2] of
+    the polygons of ONE geometry -- GEOS's point locator with the Mod-2 boundary rule: an odd number of boundaries is the
+    boundary, else interior where any polygon holds the point or a boundary was hit; contains == interior"""
+    nb = (codes == SPC_LOC_BOUNDARY).sum(dim=0)
+    inside = (codes == SPC_LOC_INTERIOR).any(dim=0)
+    return (nb % 2 == 0) & (inside | (nb > 0))
+
+
+
+def get_mask_indices(points, mask_geoms, nmax=-1):
+    """The grid columns a set of mask geometries selects, splib/sputils.py:46-73 step by step, on the GPU: which points
+    (``(lon, lat)`` tuples as splib.initialize passes them, an [n x 2] array, or an [n x 2] device tensor) lie in the
+    polygons, or lie nearest to the points, of ``mask_geoms`` (sp_coupler_amd.geometry, or shapely's own objects).
+
+    * ``nmax == 0``: ``[]``.
+    * ONE Point: the ``nmax`` nearest columns (great-circle distance, splib/haversine.py) as an int64 array (a device tensor
+      for device points) in a STABLE order -- the reference's ``numpy.argsort`` is not stable, so among exactly equal
+      distances its order is NumPy's, ours the index order; ``nmax < 0``: ``[argmin]``, the first of the nearest.
+    * otherwise (``nmax`` ignored, as in the reference): a Point adds the argmin of its distances, a polygon every ``i``
+      whose point ``p`` or image ``q = ((lon - 180) % 360 - 180, lat)`` it contains, ascending; the result is
+      ``list(set(result))`` of ints, built as the reference builds it, so its order (the order in which the LES are
+      created) is the reference's.
+    ``contains`` is GEOS's point locator in exact arithmetic: a point on a polygon's boundary is
+    not contained."""
+    from . import geometry
+    if nmax == 0:
+        return []                                   # requested no points
+    eng = _engine()
+    eng = getattr(eng, "primary", eng)
+    masks = [geometry.as_mask(g) for g in mask_geoms]
+    lon, lat, on_device = _lonlat(points, eng)
+
+    def nearest(g):
+        if lon.shape[0] == 0:
+            raise ValueError("attempt to get argmin of an empty sequence")
+        return eng.haversine(lon, lat, g.x, g.y)
+
+    if len(masks) == 1 and isinstance(masks[0], geometry.Point):
+        d = nearest(masks[0])
+        if nmax > 0:
+            with eng.on_stream():
+                idx = torch.sort(d, stable=True).indices[:nmax]
+            return idx if on_device else idx.cpu().numpy()
+        return [int(torch.argmin(d))]
+    result = []
+    for m in masks:
+        if isinstance(m, geometry.Point):
+            result.append(int(torch.argmin(nearest(m))))
+        else:
+            codes = eng.point_in_polygon(lon, lat, *geometry.pack(*m))
+            result.extend(torch.nonzero(_contains(codes).any(dim=1)).flatten().tolist())
+    return list(set(result))                        # remove duplicates, in the reference's order
