@@ -304,6 +304,45 @@ typedef struct spc_pip_args {
 int spc_point_in_polygon_f64(const spc_pip_args *args, void *stream);
 int spc_haversine_f64(int64_t n, const void *lon, const void *lat, double lon0, double lat0, void *out, void *stream);
 
+/* ---- initial LES state of spcpl.set_les_state, splib/spcpl.py:274-294 (kernel family K9) ------------------------- */
+/* For every LES l in list order and every field f = U, V, THL, QT in that order:
+ *   out[f][elem_off[l] + idx] = amp[f] * numpy.random.uniform(-1., 1.)[idx] + prof[f][l * pitch_prof + idx % ktot[l]]
+ * for idx = 0 ... elem_off[l+1] - elem_off[l] - 1 (C order, ktot fastest), drawn from NumPy's legacy MT19937 state
+ * (key_in, pos_in) exactly as the reference loop draws them, in float64, bit for bit.  Also returns the state NumPy holds
+ * afterwards (key_out, pos_out; has_gauss / cached_gaussian are not touched).  The substream starts are computed on the
+ * device by jump-ahead; the final state is the generation the launch twisted last, so it equals
+ * NumPy's in every bit.  key_in / elem_off / ktot / key_out / pos_out are HOST memory, prof / out / work device memory.
+ * The call is synchronous: it returns once the fields are written and the final state is on the host.
+ * gens_per_substream: 0 = chosen from the device's compute units; > 0 forces it (tests: many substream boundaries).      */
+typedef struct spc_les_state_args {
+    int64_t n_les;
+    const int64_t *elem_off;       /* host [n_les + 1], elem_off[0] == 0, non-decreasing: itot*jtot*ktot per LES  */
+    const int32_t *ktot;           /* host [n_les] >= 1, dividing the LES's element count                         */
+    const double *prof[4];         /* device [n_les x pitch_prof] u, v, thl, qt profiles (ktot[l] <= pitch_prof)   */
+    int64_t pitch_prof;
+    double amp[4];                 /* 0.5, 0.5, 0.1, 2.5e-5 in the reference (spcpl.py:285-287)                   */
+    double *out[4];                /* device [elem_off[n_les]] each                                               */
+    const uint32_t *key_in;        /* host [624] numpy.random.get_state()[1]                                      */
+    int32_t pos_in;                /* 0 ... 624                                                                    */
+    int32_t reserved;
+    uint32_t *key_out;             /* host [624]                                                                   */
+    int32_t *pos_out;              /* host                                                                         */
+    int64_t gens_per_substream;
+    void *work;                    /* device scratch of work_bytes >= spc_les_state_workspace_bytes()              */
+    int64_t work_bytes;
+} spc_les_state_args;
+int spc_les_state_f64(const spc_les_state_args *args, void *stream);
+/* Bytes of spc_les_state_args.work for n_les LES holding n_elems = elem_off[n_les] elements per field, on the current
+ * device; negative spc_status on bad extents. */
+int64_t spc_les_state_workspace_bytes(int64_t n_les, int64_t n_elems, int32_t pos_in, int64_t gens_per_substream);
+/* NumPy's MT19937 state after drawing n_words 32-bit words from (key_in, pos_in), computed on the host by jump-ahead
+ * (Berlekamp-Massey for the characteristic polynomial, x^J mod phi by square-and-multiply); no device needed.  Equal to
+ * NumPy's state in every bit (the last generation is twisted for real).  pos_in 0 ... 624, n_words >= 0. */
+int spc_mt19937_jump(const uint32_t *key_in, int32_t pos_in, int64_t n_words, uint32_t *key_out, int32_t *pos_out);
+/* x^J mod phi as 312 little-endian 64-bit words (bit i = coefficient of x^i); J = 0 ... 2^63 - 1.  J = 19937 gives phi
+ * minus its leading term: tests re-derive phi from it. */
+int spc_mt19937_jump_poly(uint64_t J, uint64_t *out);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */
 const char *spc_last_error(void);   /* text of the calling thread's last failure ("" if none)     */

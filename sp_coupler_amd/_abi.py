@@ -91,6 +91,12 @@ class PipArgs(ctypes.Structure):
                 + _ptrs("lon", "lat", "vx", "vy", "ring_start", "ring_role", "ring_poly", "out"))
 
 
+class LesStateArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64)] + _ptrs("elem_off", "ktot") + [("prof", c_void_p * 4), ("pitch_prof", c_int64),
+                ("amp", c_double * 4), ("out", c_void_p * 4)] + _ptrs("key_in") + [("pos_in", c_int32), ("reserved", c_int32)]
+                + _ptrs("key_out", "pos_out") + [("gens_per_substream", c_int64)] + _ptrs("work") + [("work_bytes", c_int64)])
+
+
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
 SPC_LOC_EXTERIOR, SPC_LOC_BOUNDARY, SPC_LOC_INTERIOR = 0, 1, 2
 
@@ -121,6 +127,10 @@ PROTOTYPES = {
     "spc_rms_f32": (ctypes.c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "spc_point_in_polygon_f64": (ctypes.c_int, [ctypes.POINTER(PipArgs), c_void_p]),
     "spc_haversine_f64": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p]),
+    "spc_les_state_f64": (ctypes.c_int, [ctypes.POINTER(LesStateArgs), c_void_p]),
+    "spc_les_state_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int64]),
+    "spc_mt19937_jump": (ctypes.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    "spc_mt19937_jump_poly": (ctypes.c_int, [ctypes.c_uint64, c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),
@@ -183,3 +193,30 @@ def check(lib, rc):
     if rc == SPC_ERR_INVALID_ARGUMENT:
         raise SpcInvalidArgument(rc, text)
     raise SpcError(rc, text)
+
+
+MT_N = 624          # words of NumPy's MT19937 key
+MT_PW = 312         # 64-bit words of a jump polynomial (include/spc.h spc_mt19937_jump_poly)
+
+
+def mt19937_jump(key, pos, n_words, lib=None):
+    """NumPy's legacy MT19937 state (key, pos) after drawing ``n_words`` 32-bit words from (key, pos): the host jump-ahead
+    of the library (spc_mt19937_jump), no device needed.  Returns (uint32 key [624], pos)."""
+    import numpy
+    lib = lib or load_library()
+    k = numpy.ascontiguousarray(key, dtype=numpy.uint32)
+    if k.shape != (MT_N,):
+        raise ValueError("key must hold 624 words, got %s" % (k.shape,))
+    out = numpy.empty(MT_N, dtype=numpy.uint32)
+    p = ctypes.c_int32()
+    check(lib, lib.spc_mt19937_jump(k.ctypes.data, int(pos), int(n_words), out.ctypes.data, ctypes.byref(p)))
+    return out, int(p.value)
+
+
+def mt19937_jump_poly(J, lib=None):
+    """x^J mod phi (phi: MT19937's characteristic polynomial) as 312 uint64 words, bit i = coefficient of x^i"""
+    import numpy
+    lib = lib or load_library()
+    out = numpy.empty(MT_PW, dtype=numpy.uint64)
+    check(lib, lib.spc_mt19937_jump_poly(int(J), out.ctypes.data))
+    return out

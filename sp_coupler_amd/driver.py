@@ -6,6 +6,8 @@ in-process synthetic pair).  The orchestration around it (process launch, config
 out of scope."""
 import time
 
+import numpy
+
 from . import spcpl
 from .models import RequestsPool
 
@@ -128,6 +130,34 @@ class Coupler:
         if self.write and spcpl.writer is not None:                           # splib/splib.py:388-391
             spcpl.write_les_profiles_batched(self.les_models)
         self.firststep = False
+
+    # splib/splib.py:180-204 (initialize, init_les_state branch): seed, the GCM's first half step, gather WITH surface
+    # fields, then convert_profiles + set_les_state for every LES -- here one forward launch and one K9 launch per device
+    def init_les_state(self, seed=42, les_spinup_steps=1):
+        """Initial LES state from the GCM as splib.initialize makes it.  numpy's global generator is seeded with ``seed``
+        (splib.py:182) and left where the reference's loop leaves it.  The GCM's first half step runs unless it has run
+        already (``first_half_step_done``; step() then skips it, splib.py:186-190, 281-285).  The spin-up the reference
+        starts right after (splib.py:205-206 when les_spinup > 0) is ``run_spinup``."""
+        numpy.random.seed(seed)                                               # splib.py:182
+        gcm = self.gcm
+        if not gcm.first_half_step_done:                                      # splib.py:186-190
+            gcm.evolve_model_until_cloud_scheme()
+            gcm.evolve_model_cloud_scheme()
+            gcm.first_half_step_done = True
+        if self.write and spcpl.writer is not None:                           # splib.py:192-193
+            self.initialize_output(les_spinup_steps)
+        spcpl.gather_gcm_data(gcm, self.les_models, True, write=self.write)   # splib.py:197
+        spcpl.set_les_state_batched(self.les_models)                          # splib.py:201-203
+
+    # splib/splib.py:233-250
+    def run_spinup(self, spinup_length, spinup_steps=1):
+        """``spinup_steps`` calls of step_spinup over ``spinup_length`` seconds; the last one takes what the others left,
+        spinup_length - (spinup_steps - 1) * (spinup_length / spinup_steps), as the reference computes it."""
+        iteration_length = spinup_length / spinup_steps
+        for s in range(spinup_steps):
+            if s == spinup_steps - 1:
+                iteration_length = spinup_length - (spinup_steps - 1) * iteration_length
+            self.step_spinup(spinup_length=iteration_length)
 
     def run(self, nsteps):
         for _ in range(nsteps):

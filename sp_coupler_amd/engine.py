@@ -20,6 +20,8 @@ FWD_LES = ("U", "V", "THL", "QT", "QL")                               # profile[
 BWD_LES = ("T", "QT", "QL", "QL_ice", "U", "V")                       # profile[...] spcpl.py:393-411
 
 _DTYPES = {torch.float64: "f64", torch.float32: "f32"}
+LES_STATE_FIELDS = ("U", "V", "THL", "QT")                            # the order set_les_state draws them (spcpl.py:288-291)
+LES_STATE_AMPS = (0.5, 0.5, 0.1, 2.5e-5)                              # vabsmax, vabsmax, thlabsmax, qabsmax (spcpl.py:285-287)
 
 
 def _stream_ptr(stream, device=None):
@@ -784,3 +786,57 @@ class Engine:
         out = torch.empty(n, dtype=torch.float64, device=self.device)
         self._call(self.lib.spc_haversine_f64, n, lon.data_ptr(), lat.data_ptr(), float(lon0), float(lat0), out.data_ptr(), stream=stream)
         return out
+
+    # -- K9: the initial LES state of spcpl.set_les_state (splib/spcpl.py:274-294); float64 on every engine ---------------
+    @_on_engine_stream
+    def les_state(self, shapes, u, v, thl, qt, state, amps=LES_STATE_AMPS, gens_per_substream=0, stream=None):
+        """``amp[f] * numpy.random.uniform(-1., 1., (itot, jtot, ktot)) + profile`` for the fields U, V, THL, QT of every LES
+        in list order, drawn from NumPy's legacy MT19937 state ``state`` ((key, pos) or what ``numpy.random.get_state()``
+        returns) as the reference loop draws them, bit for bit.  ``shapes``: (itot, jtot, ktot) per LES; ``u`` ... ``qt``:
+        profiles [n x >= ktot] (device tensors or host arrays, any float type: promoted to float64 exactly).  Returns
+        (fields, (key, pos)): fields[name] a float64 tensor [n x itot x jtot x ktot] on this device when all LES have one
+        shape, else a list of n tensors; (key, pos) the state NumPy holds after the same draws.  The call returns once the
+        launch has finished (the state comes back to the host)."""
+        import numpy
+        n = len(shapes)
+        sizes = [int(i) * int(j) * int(k) for i, j, k in shapes]
+        ktot = numpy.array([int(s[2]) for s in shapes], dtype=numpy.int32)
+        elem_off = numpy.zeros(n + 1, dtype=numpy.int64)
+        numpy.cumsum(sizes, out=elem_off[1:])
+        key, pos = (state[1], state[2]) if len(state) == 5 else state
+        key = numpy.ascontiguousarray(key, dtype=numpy.uint32)
+        if key.shape != (_abi.MT_N,):
+            raise ValueError("MT19937 key must hold 624 words, got %s" % (key.shape,))
+        prof = []
+        for name, p in (("u", u), ("v", v), ("thl", thl), ("qt", qt)):
+            t = torch.as_tensor(p).to(device=self.device, dtype=torch.float64)
+            if t.dim() != 2 or t.shape[0] != n or (n and t.shape[1] < int(ktot.max())):
+                raise ValueError("%s must be [%d x >= %d], got %s" % (name, n, int(ktot.max()) if n else 0, tuple(t.shape)))
+            prof.append(t.contiguous())
+        pitch = int(prof[0].shape[1]) if n else 1
+        if any(int(p.shape[1]) != pitch for p in prof):
+            raise ValueError("the four profiles must have one level count")
+        total = int(elem_off[-1])
+        flat = [torch.empty(max(total, 1), dtype=torch.float64, device=self.device) for _ in range(4)]
+        wb = int(self.lib.spc_les_state_workspace_bytes(n, total, int(pos), int(gens_per_substream)))
+        if wb < 0:
+            _abi.check(self.lib, wb)
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=self.device)
+        key_out = numpy.empty(_abi.MT_N, dtype=numpy.uint32)
+        pos_out = ctypes.c_int32()
+        a = _abi.LesStateArgs()
+        a.n_les, a.elem_off, a.ktot, a.pitch_prof = n, elem_off.ctypes.data, ktot.ctypes.data, pitch
+        for f in range(4):
+            a.prof[f], a.out[f], a.amp[f] = prof[f].data_ptr(), flat[f].data_ptr(), float(amps[f])
+        a.key_in, a.pos_in, a.key_out = key.ctypes.data, int(pos), key_out.ctypes.data
+        a.pos_out = ctypes.cast(ctypes.byref(pos_out), ctypes.c_void_p)
+        a.gens_per_substream, a.work, a.work_bytes = int(gens_per_substream), work.data_ptr(), wb
+        self._call(self.lib.spc_les_state_f64, ctypes.byref(a), stream=stream)
+        fields = {}
+        uniform = len(set(tuple(int(x) for x in s) for s in shapes)) <= 1
+        for name, t in zip(LES_STATE_FIELDS, flat):
+            if uniform and n:
+                fields[name] = t[:total].view(n, *[int(x) for x in shapes[0]])
+            else:
+                fields[name] = [t[elem_off[l]:elem_off[l + 1]].view(*[int(x) for x in shapes[l]]) for l in range(n)]
+        return fields, (key_out, int(pos_out.value))

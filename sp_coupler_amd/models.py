@@ -287,7 +287,9 @@ def make_models(n_les, npoints=None, nG=91, nL=160, seed=1):
 #   LES   an ENSEMBLE object passed as `les_models` with batched = True, list-like over per-column LES objects:
 #         grid_indices, zf_cache, zh_cache, get_profiles_batched(keys, out), get_cloudfraction_batched(indices, out),
 #         set_forcings_batched(**arrays), evolve_model_batched(t); for qt_forcing='variance' additionally
-#         get_fields_batched(name) -> [n x itot x jtot x ktot], set_fields_batched(name, array), model_time
+#         get_fields_batched(name) -> [n x itot x jtot x ktot], set_fields_batched(name, array), model_time;
+#         for spcpl.set_les_state_batched: set_fields_batched, and per-column faces with get_itot / get_jtot / get_ktot
+#         (and set_surface_pressure where ps is set)
 # ---------------------------------------------------------------------------------------------
 import time as _time
 
@@ -393,6 +395,13 @@ class _LESRow:
     def get_cloudfraction(self, indices, return_request=False):
         v = self._e.A_lev[self._i].take(indices, mode="clip")          # like splib/spdummy.py:319-321
         return ImmediateRequest(v) if return_request else v
+
+    def set_field(self, name, values):
+        """les.set_field (splib/spcpl.py:288-291) on row i of the ensemble's 3-D fields"""
+        self._e.set_field_row(self._i, name, values)
+
+    def set_surface_pressure(self, ps):
+        self._e.p["PS"][self._i] = float(getattr(ps, "number", ps))
 
     def evolve_model(self, t, exactEnd=True):
         self._e.evolve_model_batched(t)         # the ensemble advances as one; later rows find it already there
@@ -524,7 +533,22 @@ class SyntheticLESEnsemble:
         return self.fields3d[name].copy()
 
     def set_fields_batched(self, name, values):
+        if self.fields3d is None:               # the first fields an ensemble gets (spcpl.set_les_state_batched)
+            self.fields3d = {}
         self.fields3d[name] = numpy.array(getattr(values, "number", values), dtype=numpy.float64)
+
+    def set_field_row(self, i, name, values):
+        """row i of field ``name`` (what les.set_field does for one LES); the field is created, zero, on first use"""
+        v = numpy.asarray(getattr(values, "number", values), dtype=numpy.float64)
+        if self.fields3d is None:
+            self.fields3d = {}
+        f = self.fields3d.get(name)
+        if f is None:
+            f = self.fields3d[name] = numpy.zeros((self.n,) + v.shape)
+        elif f.shape[1:] != v.shape:
+            raise ValueError("field %s of this ensemble has rows of shape %s, got %s: an ensemble holds one shape"
+                             % (name, f.shape[1:], v.shape))
+        f[i] = v
 
     @_timed
     def evolve_model_batched(self, t):

@@ -11,6 +11,7 @@ Same function names, argument meaning and return values as the reference module,
     get_cloud_fraction(les)                                                                    spcpl.py:22
     set_gcm_tendencies(gcm, les, profile, dt_gcm, factor=1, write=True, conservative=False)    spcpl.py:388
     write_les_profiles(les) / set_les_state(les, u, v, thl, qt, ps=None)                       spcpl.py:574/274
+    set_les_state_batched(les_models, u=None, v=None, thl=None, qt=None, ps=None)  the loop of splib.py:199-201 (K9)
     set_gcm_tendencies_from_file(gcm, les)                                                     spcpl.py:558
     convert_surface_fluxes(les) / output_column_conversion(profile)                            spcpl.py:136/251
 
@@ -32,7 +33,7 @@ import numpy
 import torch
 
 from . import transfer
-from .engine import Engine
+from .engine import Engine, LES_STATE_FIELDS as _LES_STATE_NAMES
 from .transfer import Arena, StepTrace  # noqa: F401  (re-exported: spcpl.Arena)
 
 log = logging.getLogger(__name__)
@@ -839,6 +840,149 @@ def set_les_state(les, u, v, thl, qt, ps=None):
     les.set_field('QT', _wrap("qt", qabsmax * numpy.random.uniform(-1., 1., (itot, jtot, ktot)) + _num(qt)))
     if ps:
         les.set_surface_pressure(ps)
+
+
+def _les_state_budget(eng):
+    """bytes of device memory one K9 launch on ``eng`` may fill: 80 % of what is available now, counted as _vnudge_chunk
+    counts it (free memory plus what torch's caching allocator holds unused)"""
+    dev = getattr(eng, "device", None)
+    if dev is None or dev.type != "cuda":
+        return 1 << 62
+    free, _ = torch.cuda.mem_get_info(dev)
+    free += max(0, torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
+    return int(0.8 * free)
+
+
+def _les_state_chunks(eng, sizes, nL, lo, hi):
+    """LES lo ... hi-1 of one device in launches that fit its memory: four float64 fields and four profiles per LES; at
+    least one LES per launch.  Where the chunks fall changes no bit: every launch starts from NumPy's exact state."""
+    budget = _les_state_budget(eng)
+    chunks, c0, acc = [], lo, 0
+    for l in range(lo, hi):
+        need = 4 * 8 * (sizes[l] + nL)
+        if l > c0 and acc + need > budget:
+            chunks.append((c0, l))
+            c0, acc = l, 0
+        acc += need
+    chunks.append((c0, hi))
+    if len(chunks) > 1:
+        log.info("sp_coupler_amd: initial state of %d LES on %s in %d launches", hi - lo, getattr(eng, "device", "?"), len(chunks))
+    return chunks
+
+
+def _profile_rows(name, x, shapes):
+    """host profiles for set_les_state_batched: [n x ktot] or a list of n rows; each row's length must be its LES's ktot"""
+    n = len(shapes)
+    rows = [_num(r) for r in x] if not isinstance(x, numpy.ndarray) or x.ndim != 2 else list(_num(x))
+    if len(rows) != n:
+        raise ValueError("set_les_state_batched: %s holds %d profiles for %d LES" % (name, len(rows), n))
+    out = numpy.zeros((n, max(s[2] for s in shapes)))
+    for l, (r, s) in enumerate(zip(rows, shapes)):
+        if r.ndim != 1 or r.shape[0] != s[2]:
+            raise ValueError("set_les_state_batched: %s profile of LES %d has shape %s, the LES has ktot = %d"
+                             % (name, l, r.shape, s[2]))
+        out[l] = 0.0
+        out[l, :s[2]] = r
+    return out
+
+
+def set_les_state_batched(les_models, u=None, v=None, thl=None, qt=None, ps=None, gens_per_substream=0):
+    """Batched twin of set_les_state for a whole LES list -- the loop of splib/splib.py:199-201 (convert_profiles +
+    set_les_state per LES) in one launch per device (K9).  Draws from numpy's GLOBAL generator exactly what the loop draws,
+    in its order (LES by LES; U, V, THL, QT), gives every LES the same fields bit for bit and leaves
+    ``numpy.random.get_state()`` where the loop leaves it (has_gauss / cached_gaussian untouched), so the variability nudge's
+    later draws are unchanged.
+
+    Profiles: with none given, u, v, thl, qt and ps come from the forward launch convert_profiles makes, on the batch of
+    the last gather_gcm_data(); its rows stay on the device(s), and ps reaches the models as convert_profiles returns it
+    (``_wrap("ps", ...)``: under a unit wrapper a quantity).  Otherwise u, v, thl, qt are all given, per LES ([n x ktot]
+    or a list of n rows), and ps is None, one value, or one value per LES, handed to the models as given.  ``les_models``: a list (each LES gets set_field('U'/'V'/
+    'THL'/'QT') in the reference's order, then set_surface_pressure where ps is truthy, spcpl.py:293-294) or an ensemble
+    (set_fields_batched(name, [n x itot x jtot x ktot]); one field shape).  Differs from the loop in one corner only: a
+    ktot that does not match the profile length raises ValueError BEFORE anything is drawn (the loop would have drawn the
+    first field of that LES), so the generator state is unchanged then.  ``gens_per_substream``: test hook (K9's substream
+    length in MT19937 generations; 0 = chosen from the device)."""
+    from . import _abi
+    ens = les_models if _is_ensemble(les_models) else None
+    rows = [les_models[i] for i in range(len(les_models))] if ens is not None else list(les_models)
+    n = len(rows)
+    if n == 0:
+        return
+    shapes = [(int(_num(m.get_itot())), int(_num(m.get_jtot())), int(_num(m.get_ktot()))) for m in rows]
+    if ens is not None and len(set(shapes)) != 1:
+        raise ValueError("set_les_state_batched: an ensemble takes [n x itot x jtot x ktot] fields of ONE shape, got %s" % sorted(set(shapes)))
+    given = [x is not None for x in (u, v, thl, qt)]
+    eng = get_engine()
+    if not any(given):
+        batch = _batch_of(ens if ens is not None else rows[0])
+        if batch.n != n:
+            raise ValueError("set_les_state_batched: the current batch holds %d LES, got %d" % (batch.n, n))
+        nL = int(batch.zf.shape[-1])
+        bad = [l for l, s in enumerate(shapes) if s[2] != nL]
+        if bad:
+            raise ValueError("set_les_state_batched: LES %d has ktot = %d, its profiles have %d levels" % (bad[0], shapes[bad[0]][2], nL))
+        eng = batch.engine
+        with eng.on_stream():              # the forward launch of convert_profiles (spcpl.py:171-246), rows kept on the device
+            z = eng.to_devices(numpy.zeros((batch.n, nL)), rows=batch.n)
+            dummy = {"U": z, "V": z, "THL": z, "QT": z, "QL": z, "PS": eng.to_devices(numpy.zeros(batch.n), rows=batch.n)}
+        _inputs_ready(batch)
+        with eng.on_stream():
+            res = eng.forward(batch.gcm, batch.zf, dummy, 0.0, 1.0, want_profiles=True, want_heights=True)
+            prof = [res[k] for k in ("u", "v", "thl", "qt")]
+            if ps is None:                   # what convert_profiles returns: the wrapped row (spcpl.py:246)
+                ps_host = _to_host(res["ps"])
+                ps = [_wrap("ps", ps_host[l]) for l in range(n)]
+        if ens is None:
+            for i, les in enumerate(rows):
+                _attach_heights(batch, les, i)                               # what convert_profiles caches (spcpl.py:200-201)
+    elif not all(given):
+        raise TypeError("set_les_state_batched: give all of u, v, thl, qt or none of them")
+    else:
+        nL = max(s[2] for s in shapes)
+        prof = [_profile_rows(name, x, shapes) for name, x in (("u", u), ("v", v), ("thl", thl), ("qt", qt))]
+    if ps is not None and not isinstance(ps, list):  # as given: one value for every LES, or one per LES
+        ps = [ps[l] for l in range(n)] if numpy.ndim(_num(ps)) else [ps] * n
+    state = numpy.random.get_state()
+    if state[0] != "MT19937":
+        raise ValueError("set_les_state_batched: the global generator is %s, not MT19937" % state[0])
+    key, pos = numpy.asarray(state[1], dtype=numpy.uint32), int(state[2])
+    sizes = [i * j * k for i, j, k in shapes]
+    words = numpy.zeros(n + 1, dtype=numpy.int64)
+    numpy.cumsum([8 * x for x in sizes], out=words[1:])
+    engines = list(getattr(eng, "engines", None) or [eng])
+    bounds = eng.bounds_for(n) if hasattr(eng, "bounds_for") else [0, n]
+    lib = getattr(engines[0], "lib", None)
+    host = {name: numpy.empty((n,) + shapes[0]) for name in _LES_STATE_NAMES} if ens is not None else None
+    final = (key, pos)
+    for d, e in enumerate(engines):
+        lo, hi = bounds[d], bounds[d + 1]
+        for c0, c1 in (_les_state_chunks(e, sizes, nL, lo, hi) if hi > lo else ()):
+            start = (key, pos) if c0 == 0 else _abi.mt19937_jump(key, pos, int(words[c0]), lib=lib)
+            part = [(p.parts[d] if isinstance(p, transfer.Sharded) else p) for p in prof]
+            off = lo if any(isinstance(p, transfer.Sharded) for p in prof) else 0
+            part = [p[c0 - off:c1 - off] for p in part]
+            fields, final = e.les_state(shapes[c0:c1], *part, start, gens_per_substream=gens_per_substream)
+            with e.on_stream():
+                got = {name: ([t.cpu().numpy() for t in f] if isinstance(f, list) else f.cpu().numpy()) for name, f in fields.items()}
+            del fields
+            for l in range(c0, c1):
+                if ens is not None:
+                    for name in _LES_STATE_NAMES:
+                        host[name][l] = got[name][l - c0]
+                    continue
+                les = rows[l]
+                for name, wname in zip(_LES_STATE_NAMES, ("u", "v", "thl", "qt")):    # spcpl.py:288-291
+                    les.set_field(name, _wrap(wname, got[name][l - c0]))
+                if ps is not None and ps[l]:                                          # spcpl.py:293-294
+                    les.set_surface_pressure(ps[l])
+    if ens is not None:
+        for name, wname in zip(_LES_STATE_NAMES, ("u", "v", "thl", "qt")):
+            ens.set_fields_batched(name, _wrap(wname, host[name]))
+        if ps is not None:
+            for l, row in enumerate(rows):
+                if ps[l]:
+                    row.set_surface_pressure(ps[l])
+    numpy.random.set_state(("MT19937", numpy.asarray(final[0], dtype=numpy.uint32), int(final[1]), state[3], state[4]))
 
 
 # ---------------------------------------------------------------------------------------------
