@@ -1,5 +1,5 @@
 // spc_f32v.hpp -- K1 of the fp32 arithmetic variant with 8-BYTE accesses (two adjacent elements per lane); included by
-// spc_hip.hip after k_forward, whose device functions (bracket2, interp_fields, Divisor, ss_right, spc_pow, stg) it uses unchanged.
+// spc_hip.hip after spc_k1.hpp (k_forward), whose device functions (bracket2, interp_fields, Divisor, ss_right, spc_pow, stg) it uses unchanged.
 //
 // Why: a 256-MiB device copy runs at 4.3-4.7 TB/s with 4 bytes per lane and at 5.7-5.8 TB/s with 8 (tools/copy_width.py,
 // profiles/r05_copy_width.log), and the scalar float kernels sat AT the 4-byte rate (K1 4.85, K3 5.2 TB/s at config 3), which

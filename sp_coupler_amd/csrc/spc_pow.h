@@ -1,5 +1,5 @@
 /* spc_pow.h -- x**y for the two exponents of the coupling path, y = -+rd/cp (splib/sputils.py:28-34): |y| <= 1, x = p / pref0.
- * ONE source for the device (spc_hip.hip includes it with SPC_POW_FN = __device__ __forceinline__) and for the host
+ * ONE source for the device (spc_device.hpp includes it with SPC_POW_FN = __device__ __forceinline__) and for the host
  * accuracy sweep (tools/csrc/pow_accuracy.c: the same IEEE operations, checked against powl in 80-bit arithmetic).
  *
  * ocml's general pow() is 245 instructions and an out-of-line call (which made every K1 wave reserve its 100 registers);

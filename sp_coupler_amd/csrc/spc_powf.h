@@ -1,9 +1,9 @@
 /* spc_powf.h -- x**y of the fp32 arithmetic variant (BASELINE config 5's tolerance sweep) for the two exponents of the coupling
- * path, y = -+rd/cp (splib/sputils.py:28-34), x = p / pref0.  ONE source for the device (spc_hip.hip includes it with SPC_POW_FN =
+ * path, y = -+rd/cp (splib/sputils.py:28-34), x = p / pref0.  ONE source for the device (spc_device.hpp includes it with SPC_POW_FN =
  * __device__ __forceinline__) and for the host sweep (tools/csrc/pow_accuracy.c, mode `f`).
  *
  * Rounds 1-4 called ocml's powf(): an out-of-line call, so every K1<float> wave reserved the callee's registers (the form
- * that cost the fp64 K1 two waves per SIMD, spc_hip.hip).  Here the power is evaluated INSIDE double arithmetic (v_fma_f64
+ * that cost the fp64 K1 two waves per SIMD, spc_device.hpp).  Here the power is evaluated INSIDE double arithmetic (v_fma_f64
  * issues at the rate of v_fma_f32 on gfx950) to ~2^-39 relative and rounded ONCE to float:
  *   log x = e ln2 + 2 atanh f,  f = (m - 1) / (m + 1),  m in [sqrt 1/2, sqrt 2)  (|f| <= 0.1716: Taylor up to f^13, 1.3e-12)
  *   t = y log x;  n = rint(t log2 e);  r = t - n ln2  (|r| <= 0.347: Taylor of exp up to r^10, 2.2e-13);  2^n by ldexp

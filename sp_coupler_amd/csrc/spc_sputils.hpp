@@ -27,7 +27,7 @@
 //   * exner: 4 elements per thread, loads up front, 4 independent pow chains, one pass over an uncapped grid; the pow's 21
 //     polynomial coefficients come from a __constant__ table, i.e. scalar registers (spc_exner_pow: a 64-bit literal costs
 //     two v_mov per use, 26 % of the instructions of a pow; the operator is bound by VALU issue);
-//   * the searches run on NaN-padded LDS rows with a fixed trip count (su_count, spc_hip.hip), addresses are a uniform base + a
+//   * the searches run on NaN-padded LDS rows with a fixed trip count (su_count, spc_device.hpp), addresses are a uniform base + a
 //     32-bit byte offset (su_at).
 #pragma once
 
@@ -92,7 +92,7 @@ template <int U, typename T> __device__ __forceinline__ void su_stage_slab(T *ds
     }
 }
 
-// (su_pad / su_seek / su_count -- the fixed-trip searches on NaN-padded LDS rows -- live in spc_hip.hip: K4 uses them too)
+// (su_pad / su_seek / su_count -- the fixed-trip searches on NaN-padded LDS rows -- live in spc_device.hpp: K4 uses them too)
 
 // nrow rows of n elements (row r at src + r * pitch) into LDS rows of `stride` entries, the tail of every row NaN;
 // U entries of a thread in flight before its first LDS store; (row, entry) stepped, never divided

@@ -1,5 +1,5 @@
 // spc_sputils_host.hpp -- argument checks and launches of the K7 operators (kernels: spc_sputils.hpp); included by
-// spc_hip.hip after its host helpers (fail, REQUIRE, launch_status, floor_pow2).
+// spc_hip.hip after spc_launch.hpp (fail, REQUIRE, launch_status, floor_pow2, small_batch).
 #pragma once
 
 // ---- host side ----------------------------------------------------------------------------------

@@ -16,7 +16,7 @@
 // NumPy does on float32 arrays (tests/vnudge_f32_ref.py): the multiplicative sum in float (float terms, float accumulators,
 // float leaf sums and tree), the additive one in double over widened planes (a R is float64), brentq in double on the widened
 // value.  The planes take half the LDS: planes of up to ~18 000 points (128 x 128) stay LDS-resident; where double planes fit
-// too, a float launch keeps the double launch's KT (spc_hip.hip: vnudge_impl).
+// too, a float launch keeps the double launch's KT (spc_vnudge_host.hpp: vnudge_impl).
 #pragma once
 
 constexpr int VN2_THREADS = 512;

@@ -1,7 +1,7 @@
 """Host launcher for the HIP coupling kernels: torch tensors in HBM -> C ABI (include/spc.h).
 
 PyTorch is plumbing here (device memory, streams); every number is produced by the hand-written
-kernels in csrc/spc_hip.hip.  There is no CPU fallback: constructing an ``Engine`` without the built
+kernels of csrc/ (one translation unit, spc_hip.hip).  There is no CPU fallback: constructing an ``Engine`` without the built
 extension or without a GPU raises.
 
 A *plan* (``ForwardPlan`` / ``BackwardPlan``) validates shapes once, freezes the ctypes argument block

@@ -502,7 +502,7 @@ def test_exner_power_accuracy_and_special_values(eng):
 @pytest.mark.parametrize("nG,nL,per_col,pad", [(91, 160, False, 0), (19, 160, False, 0), (60, 100, False, 0),
                                               (91, 160, True, 0), (91, 160, False, 3), (120, 136, False, 0)])
 def test_small_batch_large_workgroups(eng, nG, nL, per_col, pad, monkeypatch):
-    """257..1024 columns run 2 / 4 columns per workgroup of 512 / 1024 threads (spc_hip.hip:small_block): every size
+    """257..1024 columns run 2 / 4 columns per workgroup of 512 / 1024 threads (spc_launch.hpp:small_block): every size
     class, ragged last workgroups, compile-time and run-time geometries, per-column grids, padded pitches -- bit-checked
     against the plain-C oracle, and bit-equal to the 256-thread path (SPC_SMALL_BLOCK=0)."""
     import ctypes
@@ -621,7 +621,7 @@ def test_conservative_coarsening_thick_layers_float32_bit_for_bit(nG, nL, scale)
 
 def test_fp32_variant_is_the_float32_evaluation_of_the_reference_lines():
     """The fp32 arithmetic variant (BASELINE config 5's sweep) forms its quotients through fp64 -- (float)((double)a * r), r = 1 /
-    (double)b (csrc/spc_hip.hip: Divisor<float>, round 5) -- which is the CORRECTLY ROUNDED float quotient: the kernels' u, v,
+    (double)b (csrc/spc_device.hpp: Divisor<float>, round 5) -- which is the CORRECTLY ROUNDED float quotient: the kernels' u, v,
     qt, ql and their forcings equal the reference's lines (spcpl.py:197-198, 215, 224-228, 328-333) evaluated by NumPy in
     float32 arithmetic, bit for bit.  (thl passes through pow: csrc/spc_powf.h, tests/test_sputils_gpu.py.)"""
     from sp_coupler_amd.engine import Engine

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What does one vector instruction occupy its SIMD for on this GPU?  (tools/csrc/spc_tools.hip: k_issue -- one wave per SIMD,
 8 independent copies of the instruction per round.)  Used to price the fp32 arithmetic variant's quotients, which go through
-fp64 (csrc/spc_hip.hip: the fp32 path), against v_fma_f32 = 4 cycles."""
+fp64 (csrc/spc_device.hpp: Divisor<float>, the fp32 path), against v_fma_f32 = 4 cycles."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

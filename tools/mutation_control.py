@@ -23,48 +23,48 @@ from __graft_entry__ import HIPCC, HIP_FLAGS  # noqa: E402  (the shipped library
 
 CSRC = os.path.join(ROOT, "sp_coupler_amd", "csrc")
 OUT = os.path.join(ROOT, "build", "mutants")
-H, K4, VN2, SU = "spc_hip.hip", "spc_k4.hpp", "spc_vnudge2.hpp", "spc_sputils.hpp"
+K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp", "spc_vnudge2.hpp", "spc_sputils.hpp"
 A9 = "(col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG"     # the neighbouring column of the slab (mutant 9)
 
 # n: (the slip, the property of tests/semantic_props.py that guards it,
 #     edits: (file under csrc/, exact old text, new text[, occurrences of the old text, default 1]), applied in order)
 MUTANTS = {
     1: ("K1 thl: exponent +rd/cp instead of -rd/cp (exner for iexner, sputils.py:28-34)", "isentropic_column_has_constant_thl",
-        [(H, "const T iex = spc_pow(div_pref0(pf), (-K<T>::rd) / K<T>::cp);", "const T iex = spc_pow(div_pref0(pf), K<T>::rd / K<T>::cp);")]),
+        [(K1, "const T iex = spc_pow(div_pref0(pf), (-K<T>::rd) / K<T>::cp);", "const T iex = spc_pow(div_pref0(pf), K<T>::rd / K<T>::cp);")]),
     2: ("K1 forcings: u_d and v_d swapped (spcpl.py:328-329)", "zero_forcings_when_the_les_equals_the_interpolated_gcm_profile",
-        [(H, "ddt.div(p.factor * (u - in.ud))", "ddt.div(p.factor * (u - in.vd))"),
-         (H, "ddt.div(p.factor * (v - in.vd))", "ddt.div(p.factor * (v - in.ud))")]),
+        [(K1, "ddt.div(p.factor * (u - in.ud))", "ddt.div(p.factor * (u - in.vd))"),
+         (K1, "ddt.div(p.factor * (v - in.vd))", "ddt.div(p.factor * (v - in.ud))")]),
     3: ("K3 f_QL from ql instead of ql_water = ql - ql_ice (spcpl.py:402, 520)", "total_water_tendency_closes",
-        [(H, "T f_QL = ddt.div(p.factor * (qlw_i - in.ql));", "T f_QL = ddt.div(p.factor * (ql_i - in.ql));")]),
+        [(K3, "T f_QL = ddt.div(p.factor * (qlw_i - in.ql));", "T f_QL = ddt.div(p.factor * (ql_i - in.ql));")]),
     4: ("K3 masking one level too far: k <= start_index (spcpl.py:527-533)", "masking_above_the_les_top",
-        [(H, "if (k < start_index) {", "if (k <= start_index) {")]),
+        [(K3, "if (k < start_index) {", "if (k <= start_index) {")]),
     5: ("K2 index map with side='left' instead of 'right' (spcpl.py:764)", "index_map_is_a_count",
-        [(H, "p.idx[col * pitchG + m] = ss_right(zh, nL, Zh_k);", "p.idx[col * pitchG + m] = ss_left(zh, nL, Zh_k);")]),
+        [(K1, "p.idx[col * pitchG + m] = ss_right(zh, nL, Zh_k);", "p.idx[col * pitchG + m] = ss_left(zh, nL, Zh_k);")]),
     6: ("K1 staging: U not reversed (spcpl.py:227)", "reversal_is_index_arithmetic_only",
-        [(H, "s[4 * nG] = uu;", "(lds + (size_t)c * 6 * nG + k)[4 * nG] = uu;")]),
+        [(K1, "s[4 * nG] = uu;", "(lds + (size_t)c * 6 * nG + k)[4 * nG] = uu;")]),
     7: ("K7 interp_c: numerator without the weight rho (sputils.py:152-154)", "conservative_coarsening_conserves",
         [(SU, "ltn[e] = WEIGHTED ? (wv[u] * qv[u]) * dz : qv[u] * dz;", "ltn[e] = qv[u] * dz;")]),
     8: ("K1 thl: latent term added instead of subtracted (spcpl.py:214)", "isentropic_column_has_constant_thl",
-        [(H, "s[nG] = (tt - div_cp(K<T>::rlv * (ql + qi))) * iex;", "s[nG] = (tt + div_cp(K<T>::rlv * (ql + qi))) * iex;")]),
+        [(K1, "s[nG] = (tt - div_cp(K<T>::rlv * (ql + qi))) * iex;", "s[nG] = (tt + div_cp(K<T>::rlv * (ql + qi))) * iex;")]),
     9: ("K3 cloud fraction A_d read from the neighbouring column of the slab (spcpl.py:404)", "columns_are_independent",
-        [(H, "load_gcm(p, cg + k, cg + (nG - 1 - k))", "load_gcm(p, cg + k, " + A9 + " + (nG - 1 - k))", 2)]),
+        [(K3, "load_gcm(p, cg + k, cg + (nG - 1 - k))", "load_gcm(p, cg + k, " + A9 + " + (nG - 1 - k))", 2)]),
     10: ("K5 t: exponent -rd/cp instead of +rd/cp (spcpl.py:409)", "isentropic_column_has_constant_thl",
-         [(H, "thl * spc_pow(div_pref0(pf), K<T>::rd / K<T>::cp)", "thl * spc_pow(div_pref0(pf), (-K<T>::rd) / K<T>::cp)")]),
+         [(K5, "thl * spc_pow(div_pref0(pf), K<T>::rd / K<T>::cp)", "thl * spc_pow(div_pref0(pf), (-K<T>::rd) / K<T>::cp)")]),
     11: ("K4 f_T: numerator without the weight rho (spcpl.py:482, sputils.py:152)", "conservative_coarsening_conserves",
          [(K4, "s[0] = w * t;", "s[0] = t;")]),
     12: ("K1 qt_ = SH + QL, the ice forgotten (spcpl.py:215)", "reversal_is_index_arithmetic_only",
-         [(H, "s[2 * nG] = sh + ql + qi;", "s[2 * nG] = sh + ql;")]),
+         [(K1, "s[2 * nG] = sh + ql + qi;", "s[2 * nG] = sh + ql;")]),
     13: ("K3 f_SH from qt instead of qt - ql (spcpl.py:519: SH is vapour only)", "total_water_tendency_closes",
-         [(H, "T f_SH = ddt.div(p.factor * ((qt_i - ql_i) - in.sh));", "T f_SH = ddt.div(p.factor * (qt_i - in.sh));")]),
+         [(K3, "T f_SH = ddt.div(p.factor * ((qt_i - ql_i) - in.sh));", "T f_SH = ddt.div(p.factor * (qt_i - in.sh));")]),
     14: ("K1 f_ps with the opposite sign (spcpl.py:332)", "zero_forcings_when_the_les_equals_the_interpolated_gcm_profile",
-         [(H, "Divisor<T>(p.dt).div(p.factor * (sc_ps - sc_psd))", "Divisor<T>(p.dt).div(p.factor * (sc_psd - sc_ps))")]),
+         [(K1, "Divisor<T>(p.dt).div(p.factor * (sc_ps - sc_psd))", "Divisor<T>(p.dt).div(p.factor * (sc_psd - sc_ps))")]),
     15: ("K1 surface branch: density from T at the model top instead of the lowest level (spcpl.py:153)",
          "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density",
-         [(H, "ldg(&p.Tm[col * pitchG + (nG - 1)])", "ldg(&p.Tm[col * pitchG + 0])")]),
+         [(K1, "ldg(&p.Tm[col * pitchG + (nG - 1)])", "ldg(&p.Tm[col * pitchG + 0])")]),
     16: ("k_surface: wqt without the ice flux QIflux (spcpl.py:159)", "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density",
-         [(H, "wqt[i] = -(QLflux[i] + QIflux[i] + SHflux[i]) / rho;", "wqt[i] = -(QLflux[i] + T(0) + SHflux[i]) / rho;")]),
+         [(K5, "wqt[i] = -(QLflux[i] + QIflux[i] + SHflux[i]) / rho;", "wqt[i] = -(QLflux[i] + T(0) + SHflux[i]) / rho;")]),
     17: ("K1 surface branch: wthl with exner instead of iexner (spcpl.py:161)", "surface_fluxes_are_the_ifs_fluxes_over_the_surface_density",
-         [(H, "spc_pow(div_pref0(sc_ps), (-K<T>::rd) / K<T>::cp)", "spc_pow(div_pref0(sc_ps), K<T>::rd / K<T>::cp)")]),
+         [(K1, "spc_pow(div_pref0(sc_ps), (-K<T>::rd) / K<T>::cp)", "spc_pow(div_pref0(sc_ps), K<T>::rd / K<T>::cp)")]),
     18: ("K6 update: qt += (beta - 1) qt, the level mean forgotten (spcpl.py:724)", "variability_nudge_reaches_the_gcm_cloud_amount",
          [(VN2, "v = (T)((double)v + coef * (double)(v - qt_av));", "v = (T)((double)v + coef * (double)v);")]),
     19: ("K6 constantT: dTHL with the opposite sign (spcpl.py:731)", "variability_nudge_reaches_the_gcm_cloud_amount",
@@ -74,18 +74,18 @@ MUTANTS = {
     21: ("K6 additive noise subtracted instead of added (spcpl.py:716-719)", "variability_nudge_reaches_the_gcm_cloud_amount",
          [(VN2, "v = (T)((double)v + coef * R[ij]);", "v = (T)((double)v - coef * R[ij]);")]),
     22: ("K3 f_U from the LES v instead of u (spcpl.py:524)", "tendencies_relax_the_gcm_towards_the_les_profile",
-         [(H, "T f_U = ddt.div(p.factor * (u_i - in.u));", "T f_U = ddt.div(p.factor * (v_i - in.u));")]),
+         [(K3, "T f_U = ddt.div(p.factor * (u_i - in.u));", "T f_U = ddt.div(p.factor * (v_i - in.u));")]),
     23: ("K1 rainrate with the opposite sign (spcpl.py:325)", "tendencies_relax_the_gcm_towards_the_les_profile",
-         [(H, "OPT(rainrate)[col] = (sc_rain - sc_rl) / p.dt;", "OPT(rainrate)[col] = (sc_rl - sc_rain) / p.dt;")]),
+         [(K1, "OPT(rainrate)[col] = (sc_rain - sc_rl) / p.dt;", "OPT(rainrate)[col] = (sc_rl - sc_rain) / p.dt;")]),
     24: ("K3 f_T with the opposite sign (spcpl.py:518)", "tendencies_relax_the_gcm_towards_the_les_profile",
-         [(H, "T f_T = ddt.div(p.factor * (t_i - in.tt));", "T f_T = ddt.div(p.factor * (in.tt - t_i));")]),
+         [(K3, "T f_T = ddt.div(p.factor * (t_i - in.tt));", "T f_T = ddt.div(p.factor * (in.tt - t_i));")]),
     25: ("K5 Tv: the condensate load added instead of subtracted (spcpl.py:176)", "gcm_level_diagnostics_mean_what_their_names_say",
-         [(H, "tt * (T(1) + cc * sh - (ql + qi))", "tt * (T(1) + cc * sh - (-(ql + qi)))")]),
+         [(K5, "tt * (T(1) + cc * sh - (ql + qi))", "tt * (T(1) + cc * sh - (-(ql + qi)))")]),
     26: ("K5 QT without the ice (spcpl.py:215)", "gcm_level_diagnostics_mean_what_their_names_say",
-         [(H, "stg<WT>(&p.QT[g], sh + ql + qi);", "stg<WT>(&p.QT[g], sh + ql + T(0));")]),
+         [(K5, "stg<WT>(&p.QT[g], sh + ql + qi);", "stg<WT>(&p.QT[g], sh + ql + T(0));")]),
     27: ("K5 Zh above the lowest FULL-level interface instead of the surface (spcpl.py:197)",
          "gcm_level_diagnostics_mean_what_their_names_say",
-         [(H, "stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + nG])));",
+         [(K5, "stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + nG])));",
            "stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + (nG - 1)])));")]),
 }
 
