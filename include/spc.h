@@ -21,6 +21,9 @@
  *   spc_variability_nudge_f32    (the same on float32 fields)
  *   spc_diagnostics_*    <- spifs.nc diagnostics          splib/spcpl.py:176,214-215,408-409;
  *                           spcpl.output_column_conversion splib/spcpl.py:251-267
+ *   spc_slab_means_* / spc_slab_cloud_fraction_*
+ *                        <- les.get_profile_U/V/THL/QT/QL/... and les.get_cloudfraction(indices) as get_les_profiles calls
+ *                           them (splib/spcpl.py:748-765, 629-630), from device-resident 3-D fields
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -342,6 +345,43 @@ int spc_mt19937_jump(const uint32_t *key_in, int32_t pos_in, int64_t n_words, ui
 /* x^J mod phi as 312 little-endian 64-bit words (bit i = coefficient of x^i); J = 0 ... 2^63 - 1.  J = 19937 gives phi
  * minus its leading term: tests re-derive phi from it. */
 int spc_mt19937_jump_poly(uint64_t J, uint64_t *out);
+
+/* ---- horizontal reductions of the LES 3-D fields (kernel family K10) --------------------------------------------- */
+/* What les.get_profile_U/V/THL/QT/QL/... (splib/spcpl.py:748-759, 629-630) and les.get_cloudfraction(indices)
+ * (spcpl.py:764-765) return, computed from device-resident fields [n_les][itot][jtot][ktot] (C order, ktot contiguous,
+ * element type of the entry point).  A field may exceed 4 GiB: offsets are 64-bit.
+ * spc_slab_means_*: out[f][l * pitch_out + k] = numpy.mean(fields[f][l], axis=(0, 1))[k] for f < n_fields, bit for bit:
+ * the sequential sum over (i, j) in row-major order in the element type, then one division by itot * jtot.  All fields of
+ * a launch have one shape; 1 <= n_fields <= SPC_SLAB_MAX_FIELDS.
+ * spc_slab_cloud_fraction_*: idx [n_les x nG] is K2's index map (spc_cloud_indices_*: idx[r] = LES half levels at or below
+ * the upper boundary of GCM layer r counted from the ground).  Layer r holds the LES levels [hi[r-1], hi[r]),
+ * hi[r] = clip(idx[r], 0, ktot), hi[-1] = 0, and
+ *   out[l * pitch_out + r] = (number of (i, j) with ql[l][i][j][k] > 0 for some k of layer r) / (itot * jtot), 0 for an empty
+ * layer; NaN and -0.0 are not cloudy.  The count is an integer: the result is exact.  At most 65 535 LES, 2 048 layers per
+ * launch.  This rule is the project's definition (the reference reaches DALES's routine through OMUSE).   */
+#define SPC_SLAB_MAX_FIELDS 16
+typedef struct spc_slab_means_args {
+    int64_t n_les;                 /* 0 is allowed: no-op                                                  */
+    int32_t itot, jtot, ktot;
+    int32_t n_fields;
+    const void *fields[SPC_SLAB_MAX_FIELDS]; /* device [n_les][itot][jtot][ktot] each                      */
+    void *out[SPC_SLAB_MAX_FIELDS];          /* device [n_les x ktot] each, rows pitch_out apart           */
+    int64_t pitch_out;             /* >= ktot                                                              */
+} spc_slab_means_args;
+int spc_slab_means_f64(const spc_slab_means_args *args, void *stream);
+int spc_slab_means_f32(const spc_slab_means_args *args, void *stream);
+
+typedef struct spc_slab_cloud_args {
+    int64_t n_les;
+    int32_t itot, jtot, ktot;
+    int32_t nG;
+    const void *ql;                /* device [n_les][itot][jtot][ktot]                                     */
+    const int32_t *idx;            /* device [n_les x nG], rows pitch_idx apart                            */
+    void *out;                     /* device [n_les x nG], rows pitch_out apart, element type of the field */
+    int64_t pitch_idx, pitch_out;  /* >= nG                                                                */
+} spc_slab_cloud_args;
+int spc_slab_cloud_fraction_f64(const spc_slab_cloud_args *args, void *stream);
+int spc_slab_cloud_fraction_f32(const spc_slab_cloud_args *args, void *stream);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

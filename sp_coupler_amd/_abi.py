@@ -97,6 +97,19 @@ class LesStateArgs(ctypes.Structure):
                 + _ptrs("key_out", "pos_out") + [("gens_per_substream", c_int64)] + _ptrs("work") + [("work_bytes", c_int64)])
 
 
+SLAB_MAX_FIELDS = 16      # SPC_SLAB_MAX_FIELDS
+
+
+class SlabMeansArgs(ctypes.Structure):
+    _fields_ = [("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32),
+                ("fields", c_void_p * SLAB_MAX_FIELDS), ("out", c_void_p * SLAB_MAX_FIELDS), ("pitch_out", c_int64)]
+
+
+class SlabCloudArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("nG", c_int32)]
+                + _ptrs("ql", "idx", "out") + [("pitch_idx", c_int64), ("pitch_out", c_int64)])
+
+
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
 SPC_LOC_EXTERIOR, SPC_LOC_BOUNDARY, SPC_LOC_INTERIOR = 0, 1, 2
 
@@ -131,6 +144,10 @@ PROTOTYPES = {
     "spc_les_state_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int64]),
     "spc_mt19937_jump": (ctypes.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     "spc_mt19937_jump_poly": (ctypes.c_int, [ctypes.c_uint64, c_void_p]),
+    "spc_slab_means_f64": (ctypes.c_int, [ctypes.POINTER(SlabMeansArgs), c_void_p]),
+    "spc_slab_means_f32": (ctypes.c_int, [ctypes.POINTER(SlabMeansArgs), c_void_p]),
+    "spc_slab_cloud_fraction_f64": (ctypes.c_int, [ctypes.POINTER(SlabCloudArgs), c_void_p]),
+    "spc_slab_cloud_fraction_f32": (ctypes.c_int, [ctypes.POINTER(SlabCloudArgs), c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

@@ -15,6 +15,8 @@
 //   K8 k_point_in_polygon, k_haversine  column selection of sputils.get_mask_indices: spc_geo.hpp; host: spc_geo_host.hpp
 //   K9 k_mt_jump, k_les_state  initial LES state of spcpl.set_les_state (NumPy's MT19937, jump-ahead): spc_lesstate.hpp;
 //                  host: spc_lesstate_host.hpp
+//   K10 k_slab_means, k_slab_cloud_*  slab means and cloud fraction of device-resident LES fields (les.get_profile_*,
+//                  les.get_cloudfraction): spc_slab.hpp, kernels and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -62,6 +64,7 @@ namespace {
 #include "spc_sputils.hpp"
 #include "spc_geo.hpp"
 #include "spc_lesstate.hpp"
+#include "spc_slab.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -69,6 +72,9 @@ namespace {
 #include "spc_vnudge_host.hpp"
 #include "spc_geo_host.hpp"
 #include "spc_lesstate_host.hpp"
+#define SPC_SLAB_HOST
+#include "spc_slab.hpp"
+#undef SPC_SLAB_HOST
 
 }  // namespace
 
@@ -127,6 +133,11 @@ int spc_les_state_f64(const spc_les_state_args *a, void *s) { return les_state_i
 int64_t spc_les_state_workspace_bytes(int64_t n_les, int64_t n_elems, int32_t pos, int64_t gens) { return les_state_workspace_impl(n_les, n_elems, pos, gens); }
 int spc_mt19937_jump(const uint32_t *key, int32_t pos, int64_t n_words, uint32_t *key_out, int32_t *pos_out) { return mt_jump_impl(key, pos, n_words, key_out, pos_out); }
 int spc_mt19937_jump_poly(uint64_t J, uint64_t *out) { return mt_jump_poly_impl(J, out); }
+
+int spc_slab_means_f64(const spc_slab_means_args *a, void *s) { return slab_means_impl<double>(a, s); }
+int spc_slab_means_f32(const spc_slab_means_args *a, void *s) { return slab_means_impl<float>(a, s); }
+int spc_slab_cloud_fraction_f64(const spc_slab_cloud_args *a, void *s) { return slab_cloud_impl<double>(a, s); }
+int spc_slab_cloud_fraction_f32(const spc_slab_cloud_args *a, void *s) { return slab_cloud_impl<float>(a, s); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

@@ -547,6 +547,67 @@ class Engine:
         _abi.check(self.lib, rc)
         return res
 
+    # -- K10: horizontal reductions of device-resident LES fields (les.get_profile_*, les.get_cloudfraction) ----------
+    def _field4(self, name, t, shape=None):
+        """a contiguous [n x itot x jtot x ktot] tensor of the engine's dtype on its device (as variability_nudge asks)"""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+        if t.device != self.device or t.dtype != self.dtype or t.dim() != 4 or not t.is_contiguous() or \
+                (shape is not None and tuple(t.shape) != tuple(shape)):
+            raise ValueError("%s must be a contiguous %s [n x itot x jtot x ktot] tensor%s on %s, got %s %s on %s"
+                             % (name, self.dtype, "" if shape is None else " of shape %s" % (tuple(shape),), self.device,
+                                t.dtype, tuple(t.shape), t.device))
+        return t
+
+    @_on_engine_stream
+    def slab_means(self, fields, out=None, stream=None):
+        """``{name: numpy.mean(field[l], axis=(0, 1)) for every LES l}`` of device fields [n x itot x jtot x ktot] of ONE
+        shape, bit for bit, in ONE launch for all of them (at most ``_abi.SLAB_MAX_FIELDS``): dict name -> [n x ktot].
+        ``out``: dict name -> [n x ktot] tensors to write into (rows may be pitched, all with one pitch)."""
+        names = list(fields)
+        if not 1 <= len(names) <= _abi.SLAB_MAX_FIELDS:
+            raise ValueError("slab_means takes 1 ... %d fields per launch, got %d" % (_abi.SLAB_MAX_FIELDS, len(names)))
+        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("slab_means: empty field shape %s" % (shape,))
+        a = _abi.SlabMeansArgs()
+        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
+        res, pitch = {}, None
+        for f, name in enumerate(names):
+            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            o, p = self._out(None if out is None else out[name], n, ktot)
+            if pitch is not None and n > 1 and p != pitch:
+                raise ValueError("slab_means: out[%s] has row pitch %d, the others %d" % (name, p, pitch))
+            pitch = p
+            a.out[f] = o.data_ptr()
+            res[name] = o
+        a.pitch_out = pitch
+        fn = self.lib.spc_slab_means_f32 if self.dtype == torch.float32 else self.lib.spc_slab_means_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
+    @_on_engine_stream
+    def slab_cloud_fraction(self, ql, idx, out=None, stream=None):
+        """les.get_cloudfraction(indices) (splib/spcpl.py:764-765) of every LES from its device-resident QL field
+        [n x itot x jtot x ktot] and K2's index map ``idx`` [n x nG] int32 (``cloud_indices`` / the fused K1 output): the
+        fraction of (i, j) columns with ql > 0 at some LES level of GCM layer r (include/spc.h), [n x nG], exact."""
+        n, itot, jtot, ktot = (int(x) for x in self._field4("ql", ql).shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("slab_cloud_fraction: empty field shape %s" % (tuple(ql.shape),))
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.shape[0] != n:
+            raise ValueError("idx must be an [n x nG] tensor with n = %d" % n)
+        nG = int(idx.shape[1])
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.SlabCloudArgs()
+        a.n_les, a.itot, a.jtot, a.ktot, a.nG = n, itot, jtot, ktot, nG
+        a.idx, a.pitch_idx = ck.mat("idx", idx, n, nG, dtype=torch.int32)
+        o, a.pitch_out = self._out(out, n, nG)
+        a.ql, a.out = ql.data_ptr(), o.data_ptr()
+        fn = self.lib.spc_slab_cloud_fraction_f32 if self.dtype == torch.float32 else self.lib.spc_slab_cloud_fraction_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return o
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

@@ -289,7 +289,8 @@ def make_models(n_les, npoints=None, nG=91, nL=160, seed=1):
 #         set_forcings_batched(**arrays), evolve_model_batched(t); for qt_forcing='variance' additionally
 #         get_fields_batched(name) -> [n x itot x jtot x ktot], set_fields_batched(name, array), model_time;
 #         for spcpl.set_les_state_batched: set_fields_batched, and per-column faces with get_itot / get_jtot / get_ktot
-#         (and set_surface_pressure where ps is set)
+#         (and set_surface_pressure where ps is set); fields_on_device = True (optional, DeviceLESEnsemble below): the 3-D
+#         fields are device tensors, get_fields_batched hands them out and set_fields_batched takes them as they are
 # ---------------------------------------------------------------------------------------------
 import time as _time
 
@@ -627,3 +628,183 @@ def make_batched_models(n_les, npoints=None, nG=91, nL=160, seed=1):
     gcm = BatchedSyntheticGCM(npoints, nG, seed)
     ens = SyntheticLESEnsemble.for_gcm(gcm, numpy.arange(1, n_les + 1), nL, seed)
     return gcm, ens
+
+
+# ---------------------------------------------------------------------------------------------
+# An LES ensemble whose 3-D fields live on the GPU (fields_on_device)
+# ---------------------------------------------------------------------------------------------
+class _DeviceLESRow(_LESRow):
+    """per-column face of a DeviceLESEnsemble: the field extents are the ensemble's; single rows of a device field are not
+    handed out (the fields never leave the GPU through the library)"""
+
+    def get_itot(self):
+        return self._e.itot
+
+    def get_jtot(self):
+        return self._e.jtot
+
+    def get_cloudfraction(self, indices, return_request=False):
+        raise NotImplementedError("a DeviceLESEnsemble answers get_cloudfraction_batched (all columns, one launch)")
+
+    def set_field(self, name, values):
+        raise NotImplementedError("a DeviceLESEnsemble takes whole fields: set_fields_batched")
+
+
+class DeviceLESEnsemble(SyntheticLESEnsemble):
+    """SyntheticLESEnsemble whose 3-D fields are device tensors [n x itot x jtot x nL] in the engine's dtype
+    (``transfer.Sharded`` row blocks under a ``multi.MultiDeviceEngine``) from ``set_les_state_batched`` through every
+    variability nudge: the library never copies them to the host.  The 3-D state is the truth and the profiles follow from
+    it: U, V, THL, QT, QL are the slab means of the fields (K10, ``Engine.slab_means``: ONE launch for all of them per
+    change of the fields), the cloud fraction is ``Engine.slab_cloud_fraction`` of the QL field.  ``Qsat`` is an attached
+    field, constant in time; the QL field is ``max(QT - Qsat, 0)``.  tests/slab_ref.py holds the NumPy twin of this class."""
+
+    fields_on_device = True
+    MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
+
+    def __init__(self, grid_indices, zf, zh, prof, itot=8, jtot=8, engine=None):
+        super().__init__(grid_indices, zf, zh, prof)
+        self.itot, self.jtot = int(itot), int(jtot)
+        self.engine = engine                            # None: spcpl.get_engine() when first needed
+        self.fields3d = {}
+        self._means = None                              # host slab means of the fields as they are now, or None
+
+    @classmethod
+    def for_gcm(cls, gcm, grid_indices, nL=160, seed=0, itot=8, jtot=8, engine=None):
+        ens = super().for_gcm(gcm, grid_indices, nL, seed)
+        ens.itot, ens.jtot, ens.engine = int(itot), int(jtot), engine
+        return ens
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(self.n))]
+        if self._rows[i] is None:
+            self._rows[i] = _DeviceLESRow(self, i)
+        return self._rows[i]
+
+    # -- plumbing: one engine or one engine per device ------------------------------------------------------------------
+    def _eng(self):
+        if self.engine is None:
+            from . import spcpl
+            self.engine = spcpl.get_engine()
+        return self.engine
+
+    def _per_device(self, fn, *xs):
+        """``fn(x, ...)`` on the engine's stream; with Sharded arguments on every device's block, on that engine's stream"""
+        from .transfer import Sharded
+        eng = self._eng()
+        ex = next((x for x in xs if isinstance(x, Sharded) and x.bounds is not None), None)
+        if ex is None:
+            with eng.on_stream():
+                return fn(*xs)
+        parts = []
+        for d, e in enumerate(eng.engines):
+            with e.on_stream():
+                parts.append(fn(*[(x.parts[d] if isinstance(x, Sharded) else x) for x in xs]))
+        return Sharded(parts, ex.bounds)
+
+    def _upload(self, a, dtype=None):
+        eng = self._eng()
+        with eng.on_stream():
+            return eng.to_devices(numpy.ascontiguousarray(a), rows=self.n, dtype=dtype or eng.dtype)
+
+    @staticmethod
+    def _host(t):
+        from .transfer import Sharded
+        return t.to_host() if isinstance(t, Sharded) else t.cpu().numpy()
+
+    # -- 3-D fields --------------------------------------------------------------------------------------------------
+    def attach_fields(self, fields):
+        for k, v in fields.items():
+            self.set_fields_batched(k, v)
+
+    def get_fields_batched(self, name):
+        """the device tensor itself (no copy): what K6 and K10 work on"""
+        if name == "QL":
+            self._ensure_ql()
+        return self.fields3d[name]
+
+    def set_fields_batched(self, name, values):
+        """a device tensor (Sharded) of the engine's is kept as it is; a NumPy array is uploaded once"""
+        import torch
+        from .transfer import Sharded
+        values = getattr(values, "number", values)
+        dt = self._eng().dtype
+        if isinstance(values, (torch.Tensor, Sharded)):
+            conv = lambda t: t if t.dtype == dt else t.to(dt)                              # noqa: E731
+            values = self._per_device(conv, values)
+        else:
+            values = self._upload(numpy.asarray(values))
+        shape = tuple(values.shape)
+        if len(shape) != 4 or shape[0] != self.n or shape[3] != self.nL:
+            raise ValueError("field %s must be [%d x itot x jtot x %d], got %s" % (name, self.n, self.nL, shape))
+        self.itot, self.jtot = int(shape[1]), int(shape[2])
+        self.fields3d[name] = values
+        self._means = None
+
+    def set_field_row(self, i, name, values):
+        raise NotImplementedError("a DeviceLESEnsemble takes whole fields: set_fields_batched")
+
+    def _ensure_ql(self):
+        import torch
+        f = self.fields3d
+        if "QL" not in f:
+            f["QL"] = self._per_device(lambda qt, qs: torch.clamp_min(qt - qs, 0.0), f["QT"], f["Qsat"])
+            self._means = None
+
+    def _slab_means(self):
+        """host [n x nL] slab means of every field in MEAN_KEYS: one launch, cached until a field changes"""
+        if self._means is None:
+            if "QT" in self.fields3d and "Qsat" in self.fields3d:
+                self._ensure_ql()
+            eng = self._eng()
+            dev = eng.slab_means({k: self.fields3d[k] for k in self.MEAN_KEYS if k in self.fields3d})
+            with eng.on_stream():
+                self._means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
+            self.p.update(self._means)
+        return self._means
+
+    # -- batched protocol ----------------------------------------------------------------------------------------------
+    @_timed
+    def get_profiles_batched(self, keys, out):
+        means = self._slab_means() if any(k in self.MEAN_KEYS and k in self.fields3d for k in keys) else {}
+        for k in keys:
+            numpy.copyto(out[k], means[k] if k in means else self.p[k])
+
+    @_timed
+    def get_cloudfraction_batched(self, indices, out):
+        import torch
+        self._ensure_ql()
+        eng = self._eng()
+        idx = self._upload(numpy.asarray(indices, dtype=numpy.int32), dtype=torch.int32)
+        A = eng.slab_cloud_fraction(self.fields3d["QL"], idx)
+        with eng.on_stream():
+            numpy.copyto(out, self._host(A))
+
+    @_timed
+    def evolve_model_batched(self, t):
+        import torch
+        dt = float(t) - self.model_time
+        if dt <= 0:
+            return
+        f, p = self.fields3d, self.p
+        for key in ("U", "V", "THL", "QT"):
+            if key in self.tend and key in f:
+                def step(field, tend):
+                    inc = tend * dt                       # two separate ops: nothing contracts to an fma
+                    return field.add_(inc[:, None, None, :])
+                self._per_device(step, f[key], self._upload(self.tend[key]))
+        if "QL" in f or ("QT" in f and "Qsat" in f):
+            self._ensure_ql()
+
+            def saturate(ql, qt, qs):
+                torch.sub(qt, qs, out=ql)
+                return ql.clamp_min_(0.0)
+            self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
+        self._means = None
+        self._slab_means()                                # p[U, V, THL, QT, QL] = the slab means of the new fields
+        if "PS" in self.tend:
+            p["PS"] = p["PS"] + dt * self.tend["PS"]
+        p["QL_ice"] = numpy.minimum(p["QL_ice"], p["QL"])
+        p["T"] = p["THL"] * (p["presf"] / 1e5) ** (287.04 / 1004.) + 2.53e6 * p["QL"] / 1004.
+        p["Rain"] = p["Rain"] + 1e-6 * dt
+        self.model_time = float(t)

@@ -221,6 +221,14 @@ class MultiDeviceEngine:
         ``to_devices(R, rows=n, dtype=torch.float64)`` (the fields and profiles in the engines' dtype)"""
         return self._run("variability_nudge", *a, **kw)
 
+    def slab_means(self, fields, out=None, **kw):
+        """K10 on every device's LES: dict of Sharded fields [n x itot x jtot x ktot] in, dict of Sharded [n x ktot] out"""
+        return self._run("slab_means", fields, out=out, **kw)
+
+    def slab_cloud_fraction(self, ql, idx, out=None, **kw):
+        """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
+        return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)
+
     # the helpers of splib/sputils.py (K7) on row-sharded arguments: each device runs the operator on its rows; an argument
     # shared by all rows (a 1-D grid) is a replicated Sharded (``to_devices(host)``) or a plain tensor on the primary device
     def exner(self, p, inverse=False, **kw):

@@ -886,6 +886,16 @@ def _profile_rows(name, x, shapes):
     return out
 
 
+def _device_blocks(parts, engines, bounds, shape, multi):
+    """per-device field blocks (None where a device holds no LES) -> the one tensor of a single engine, or a
+    transfer.Sharded over the engines of a multi-device engine (empty blocks on the devices without rows)"""
+    if not multi or bounds[1] == bounds[-1]:        # (a small batch stays on the primary engine: a plain tensor, as to_devices gives)
+        return parts[0]
+    parts = [p if p is not None else torch.empty((0,) + tuple(shape), dtype=torch.float64, device=e.device)
+             for p, e in zip(parts, engines)]
+    return transfer.Sharded(parts, list(bounds))
+
+
 def set_les_state_batched(les_models, u=None, v=None, thl=None, qt=None, ps=None, gens_per_substream=0):
     """Batched twin of set_les_state for a whole LES list -- the loop of splib/splib.py:199-201 (convert_profiles +
     set_les_state per LES) in one launch per device (K9).  Draws from numpy's GLOBAL generator exactly what the loop draws,
@@ -952,16 +962,23 @@ def set_les_state_batched(les_models, u=None, v=None, thl=None, qt=None, ps=None
     engines = list(getattr(eng, "engines", None) or [eng])
     bounds = eng.bounds_for(n) if hasattr(eng, "bounds_for") else [0, n]
     lib = getattr(engines[0], "lib", None)
-    host = {name: numpy.empty((n,) + shapes[0]) for name in _LES_STATE_NAMES} if ens is not None else None
+    on_device = ens is not None and getattr(ens, "fields_on_device", False)
+    host = {name: numpy.empty((n,) + shapes[0]) for name in _LES_STATE_NAMES} if ens is not None and not on_device else None
+    kept = {name: [None] * len(engines) for name in _LES_STATE_NAMES}       # on_device: every device's block, left where it is
     final = (key, pos)
     for d, e in enumerate(engines):
         lo, hi = bounds[d], bounds[d + 1]
-        for c0, c1 in (_les_state_chunks(e, sizes, nL, lo, hi) if hi > lo else ()):
+        # an ensemble that keeps its fields on the GPU needs a device's whole block resident anyway: one launch per device
+        for c0, c1 in (([(lo, hi)] if on_device else _les_state_chunks(e, sizes, nL, lo, hi)) if hi > lo else ()):
             start = (key, pos) if c0 == 0 else _abi.mt19937_jump(key, pos, int(words[c0]), lib=lib)
             part = [(p.parts[d] if isinstance(p, transfer.Sharded) else p) for p in prof]
             off = lo if any(isinstance(p, transfer.Sharded) for p in prof) else 0
             part = [p[c0 - off:c1 - off] for p in part]
             fields, final = e.les_state(shapes[c0:c1], *part, start, gens_per_substream=gens_per_substream)
+            if on_device:                                  # the tensors go to the ensemble as they are: no host copy
+                for name in _LES_STATE_NAMES:
+                    kept[name][d] = fields[name]
+                continue
             with e.on_stream():
                 got = {name: ([t.cpu().numpy() for t in f] if isinstance(f, list) else f.cpu().numpy()) for name, f in fields.items()}
             del fields
@@ -977,7 +994,10 @@ def set_les_state_batched(les_models, u=None, v=None, thl=None, qt=None, ps=None
                     les.set_surface_pressure(ps[l])
     if ens is not None:
         for name, wname in zip(_LES_STATE_NAMES, ("u", "v", "thl", "qt")):
-            ens.set_fields_batched(name, _wrap(wname, host[name]))
+            if on_device:
+                ens.set_fields_batched(name, _device_blocks(kept[name], engines, bounds, shapes[0], hasattr(eng, "engines")))
+            else:
+                ens.set_fields_batched(name, _wrap(wname, host[name]))
         if ps is not None:
             for l, row in enumerate(rows):
                 if ps[l]:
@@ -1449,6 +1469,8 @@ def variability_nudge_ensemble(ens, DT, constantT=False, write=True):
     from ``ens.get_fields_batched(name) -> [n x itot x jtot x ktot]`` ("Qsat", "QT"; "THL", "QL" with constantT) and go
     back through ``ens.set_fields_batched(name, array)``; slab means from ``get_profiles_batched``; ``ens.ql_ref`` is
     what set_les_forcings_batched stored (spcpl.py:348).  R is drawn per column in column order like the per-LES loop."""
+    if getattr(ens, "fields_on_device", False):
+        return _variability_nudge_on_device(ens, DT, constantT, write)
     dtv = float(_num(DT))
     n = len(ens)
     qt = _num(ens.get_fields_batched("QT"))
@@ -1467,6 +1489,58 @@ def variability_nudge_ensemble(ens, DT, constantT=False, write=True):
     ens.set_fields_batched("QT", _wrap("qt", qt_new))                         # spcpl.py:735
     if constantT:
         ens.set_fields_batched("THL", _wrap("thl", thl_new))                  # spcpl.py:736-737
+    return _vnudge_finish(host, list(range(n)), dtv, write)
+
+
+def _variability_nudge_on_device(ens, DT, constantT, write):
+    """variability_nudge_ensemble for an ensemble whose fields live on the GPU (``fields_on_device``): K6 runs IN PLACE on the
+    ensemble's QT (THL) tensors with its Qsat (QL) tensors, ql_av / qt_av are K10's slab means and never leave the device;
+    only R (drawn on the host from numpy's global generator, as on the host path), presf, ql_ref and the [n x ktot] results
+    cross PCIe.  Nothing is uploaded per LES, so there is no memory-driven chunking; launches of more than VN_MAX_COLS LES
+    are split.  Same bits as the host path on the same fields."""
+    dtv = float(_num(DT))
+    n = len(ens)
+    eng = getattr(ens, "engine", None) or get_engine()
+    qt = ens.get_fields_batched("QT")
+    _, itot, jtot, ktot = (int(x) for x in qt.shape)
+    Rs = numpy.empty((n, itot, jtot))
+    for i in range(n):
+        R = numpy.random.normal(size=(itot, jtot))                            # spcpl.py:620
+        R -= R.sum() / (itot * jtot)                                          # spcpl.py:621
+        Rs[i] = R
+    presf = numpy.empty((n, ktot))
+    ens.get_profiles_batched(("presf",), {"presf": presf})
+    qsat = ens.get_fields_batched("Qsat")
+    ql = ens.get_fields_batched("QL")
+    thl = ens.get_fields_batched("THL") if constantT else None
+    sharded = isinstance(qt, transfer.Sharded)
+    engines = list(eng.engines) if sharded else [getattr(eng, "primary", eng)]
+    bounds = list(qt.bounds) if sharded else [0, n]
+    part = lambda x, d: x.parts[d] if sharded else x                                     # noqa: E731
+    ql_ref = numpy.ascontiguousarray(_num(ens.ql_ref))
+    live = []
+    for d, e in enumerate(engines):
+        lo, hi = bounds[d], bounds[d + 1]
+        for c0 in range(lo, hi, VN_MAX_COLS):
+            c1 = min(hi, c0 + VN_MAX_COLS)
+            s = slice(c0 - lo, c1 - lo)
+            up = lambda a, dt=None, e=e: torch.from_numpy(numpy.ascontiguousarray(a[c0:c1])).to(e.device, dt or e.dtype)   # noqa: E731
+            with e.on_stream():
+                av = e.slab_means({"QL": part(ql, d)[s], "QT": part(qt, d)[s]})            # les.get_profile("QL"/"QT")
+                res = e.variability_nudge(part(qt, d)[s], part(qsat, d)[s], up(Rs, torch.float64), av["QL"], av["QT"], up(ql_ref),
+                                          presf=up(presf), thl=part(thl, d)[s] if constantT else None,
+                                          ql=part(ql, d)[s] if constantT else None, constantT=constantT)
+            live.append((e, c0, c1, res))
+    host = None
+    for e, c0, c1, res in live:
+        with e.on_stream():
+            if host is None:
+                host = {key: numpy.empty((n,) + tuple(v.shape[1:]), dtype=torch.empty(0, dtype=v.dtype).numpy().dtype) for key, v in res.items()}
+            for key, v in res.items():
+                host[key][c0:c1] = v.cpu().numpy()
+    ens.set_fields_batched("QT", qt)                                          # spcpl.py:735: the same tensor, nudged in place
+    if constantT:
+        ens.set_fields_batched("THL", thl)                                    # spcpl.py:736-737
     return _vnudge_finish(host, list(range(n)), dtv, write)
 
 
