@@ -109,8 +109,8 @@ class OracleEngine:
         x = a.numpy()
         return torch.from_numpy(numpy.asarray(orc.rms(x) if x.ndim == 1 else numpy.array([orc.rms(r) for r in x])))
 
-    def to_devices(self, host_array, rows=None, n_cols=None):
-        return torch.from_numpy(numpy.ascontiguousarray(host_array)).to(self.device, self.dtype)
+    def to_devices(self, host_array, rows=None, n_cols=None, dtype=None):
+        return torch.from_numpy(numpy.ascontiguousarray(host_array)).to(self.device, dtype or self.dtype)
 
     def plan_forward(self, g, zf, p, factor, dt, zh=None, **kw):
         return _OraclePlan(lambda f, d: self.forward(g, zf, p, f, d, zh=zh, **kw), factor, dt)
@@ -213,3 +213,29 @@ class OracleEngine:
         wqt = -(QLflux.numpy() + QIflux.numpy() + SHflux.numpy()) / rho
         wthl = -TSflux.numpy() * orc.iexner(Ph_s.numpy()) / (orc.cp * rho)
         return torch.from_numpy(wthl), torch.from_numpy(wqt)
+
+    # -- K10 and K9 for a device-resident ensemble (models.DeviceLESEnsemble): the NumPy oracles of tests/slab_ref.py ------
+    def slab_means(self, fields, out=None, **kw):
+        from tests import slab_ref
+        return _t({k: slab_ref.slab_means(v.numpy()) for k, v in fields.items()}, out)
+
+    def slab_cloud_fraction(self, ql, idx, out=None, **kw):
+        from tests import slab_ref
+        res = _t({"A": slab_ref.cloud_fraction(ql.numpy(), idx.numpy())}, None if out is None else {"A": out})
+        return res["A"]
+
+    def les_state(self, shapes, u, v, thl, qt, state, amps=(0.5, 0.5, 0.1, 2.5e-5), gens_per_substream=0, **kw):
+        """Engine.les_state by the reference's own loop (splib/spcpl.py:274-294): a numpy.random.RandomState set to
+        ``state`` draws uniform(-1, 1, (itot, jtot, ktot)) per LES for U, V, THL, QT in that order; one field shape"""
+        key, pos = (state[1], state[2]) if len(state) == 5 else state
+        rs = numpy.random.RandomState()
+        rs.set_state(("MT19937", numpy.asarray(key, dtype=numpy.uint32), int(pos), 0, 0.0))
+        assert len({tuple(int(x) for x in s) for s in shapes}) == 1, "the test engine takes one field shape"
+        prof = [numpy.asarray(p.numpy() if isinstance(p, torch.Tensor) else p, dtype=numpy.float64) for p in (u, v, thl, qt)]
+        names = ("U", "V", "THL", "QT")
+        fields = {name: numpy.empty((len(shapes),) + tuple(int(x) for x in shapes[0])) for name in names}
+        for l, (itot, jtot, ktot) in enumerate(shapes):
+            for name, amp, p in zip(names, amps, prof):
+                fields[name][l] = amp * rs.uniform(-1., 1., (int(itot), int(jtot), int(ktot))) + p[l, :int(ktot)]
+        st = rs.get_state()
+        return {k: torch.from_numpy(v) for k, v in fields.items()}, (numpy.asarray(st[1], dtype=numpy.uint32), int(st[2]))

@@ -1,5 +1,6 @@
 """The mutation control's table (tools/mutation_control.py) against the current kernel sources, on the CPU: the shipped
-sources carry no mutant switch, every mutant is present and guarded by a property of tests/semantic_props.py, and every
+sources carry no mutant switch, every mutant is present and guarded by a property of tests/semantic_props.py (K10's by a
+body of tests/slab_edges.py), and every
 edit still finds its line -- a kernel edit that drops or moves a mutant's line fails here, not as a SURVIVED mutant on the
 GPU box."""
 import os
@@ -21,11 +22,16 @@ def test_no_mutant_switch_in_the_shipped_sources(repo_root):
 
 
 def test_every_mutant_is_guarded_by_a_property():
-    assert sorted(mc.MUTANTS) == list(range(1, 28))
+    assert sorted(mc.MUTANTS) == list(range(1, 36))
     names = {p.__name__[5:] for p in sp.PROPERTIES}
+    from tests import slab_edges
     for n, (what, guard, edits) in mc.MUTANTS.items():
         assert what and edits, n
-        assert guard in names, (n, guard)
+        if n < 28:
+            assert guard in names, (n, guard)
+        else:                                        # K10: a body of tests/slab_edges.py, run on the engines of the mutant library
+            assert callable(guard) and all(e[0] == mc.SLAB for e in edits), n
+            assert hasattr(slab_edges, "check_" + guard.__name__.split(".", 1)[1]), (n, guard.__name__)
 
 
 @pytest.mark.parametrize("n", sorted(mc.MUTANTS))

@@ -7,7 +7,7 @@ import pytest
 
 import __graft_entry__ as ge
 from sp_coupler_amd import _abi
-from tests import slab_ref
+from tests import slab_edges, slab_ref
 
 
 @pytest.fixture(scope="module")
@@ -132,3 +132,96 @@ def test_device_ensemble_class_and_protocol_flag():
     assert issubclass(models.DeviceLESEnsemble, models.SyntheticLESEnsemble)
     assert models.DeviceLESEnsemble.fields_on_device is True and models.DeviceLESEnsemble.batched is True
     assert not getattr(models.SyntheticLESEnsemble, "fields_on_device", False)
+
+
+# -- the inputs of the edge tests of tests/test_slab_gpu.py (tests/slab_edges.py): what they cover, and that the oracle's
+#    answer to each is one a wrong kernel would miss ------------------------------------------------------------------------
+def test_edge_inputs_cover_what_they_claim():
+    nij = [i * j for i, j in slab_edges.PLANES]
+    assert {x % 4 for x in nij} == set(range(4)) and {x % 8 for x in nij} == set(range(8))
+    assert {1, 2, 3, 4, 5, 6, 7} <= set(nij) and any(256 < x < 260 for x in nij) and 260 in nij and 255 in nij
+    assert set(slab_edges.NGS) >= {1, 5, 63, 64, 65, 257, 600} and set(slab_edges.KTOTS) >= {1, 7, 63, 64, 65, 128, 130, 512}
+    assert set(slab_edges.K1_SIZES) >= {1, 7, 8, 9, 127, 128, 129, 255, 256, 257, 8191, 8192, 8193, 20000}
+    for ktot in slab_edges.KTOTS:                              # the layer bounds the index maps put on the word boundaries
+        idx = slab_edges.index_map(600, ktot, 1)
+        ranges = set(slab_ref.layer_ranges(idx[0], ktot)) | set(slab_ref.layer_ranges(idx[1], ktot))
+        for b in (63, 64, 65, 127, 128):
+            if b < ktot:
+                assert any(hi == b and lo < hi for lo, hi in ranges) and any(lo == b and lo < hi for lo, hi in ranges), (ktot, b)
+        assert any(hi == ktot and lo < hi for lo, hi in ranges)
+        if ktot >= 128:
+            assert (64, 128) in ranges and (0, 64) in ranges
+        assert (idx < 0).any() and (idx > ktot).any() and (numpy.diff(idx, axis=1) < 0).any() and (numpy.diff(idx, axis=1) == 0).any()
+
+
+@pytest.mark.parametrize("dtype", [numpy.float64, numpy.float32])
+@pytest.mark.parametrize("plane", slab_edges.PLANES)
+def test_edge_planes_have_answers_a_miscounted_row_changes(plane, dtype):
+    nij = plane[0] * plane[1]
+    ql, idx = slab_edges.plane_case(plane, "all", dtype)
+    want = slab_ref.cloud_fraction(ql, idx)
+    full = numpy.array([[hi > lo for lo, hi in slab_ref.layer_ranges(r, ql.shape[-1])] for r in idx])
+    assert full.any() and not full.all() and (want[full] == 1).all() and (want[~full] == 0).all()      # exactly 1: a row twice is > 1
+    ql, idx = slab_edges.plane_case(plane, "last", dtype)
+    want = slab_ref.cloud_fraction(ql, idx)
+    assert numpy.count_nonzero(want) == 3 and (want[want != 0] == dtype(1) / dtype(nij)).all()          # one column of one layer per LES
+    ql, idx = slab_edges.plane_case(plane, "sparse", dtype)
+    want = slab_ref.cloud_fraction(ql, idx)
+    assert (want == 0).any() and want.max() <= 1
+    if nij >= 35:
+        assert ((want > 0) & (want < 1)).any()
+
+
+@pytest.mark.parametrize("ktot", slab_edges.KTOTS)
+@pytest.mark.parametrize("nG", slab_edges.NGS)
+def test_edge_layer_maps_have_answers_of_every_kind(nG, ktot):
+    ql, idx = slab_edges.layers_case(nG, ktot, numpy.float64)
+    want = slab_ref.cloud_fraction(ql, idx)
+    assert want.shape == (2, nG) and want.max() > 0 and want.max() <= 1
+    if nG >= 5:
+        assert (want == 0).any() and ((want > 0) & (want < 1)).any()
+    if nG > 256:
+        assert want[:, 256:].max() > 0                          # a layer of the second trip of the per-layer loops counts something
+    if nG > 520:
+        assert want[:, 512:].max() > 0
+    # the two hand-set columns make the levels next to a boundary matter: moving a bound by one level changes the answer
+    for shift in (-1, 1):
+        moved = numpy.where((idx > 0) & (idx < ktot), idx + shift, idx).astype(numpy.int32)
+        if nG >= 63 and ktot >= 63:
+            assert not numpy.array_equal(slab_ref.cloud_fraction(ql, moved), want), shift
+
+
+def test_edge_lds_case_and_its_refusal(lib):
+    for dtype in (numpy.float64, numpy.float32):
+        ql, idx, counts = slab_edges.lds_case(dtype)
+        assert numpy.array_equal(slab_ref.cloud_fraction(ql, idx), counts.astype(dtype) / dtype(6)) and counts.max() == 2
+    assert 4 * 4 * (32768 // 64) * 8 + 5 * 8 + 4 * 5 * 4 > 64 * 1024                # masks + bounds + counters: above the default limit
+    assert 4 * 4 * (65536 // 64) * 8 + 2048 * 8 + 4 * 2048 * 4 == 180224 > 160 * 1024
+    for sfx in ("f64", "f32"):                                                      # the host check needs no device
+        a = _abi.SlabCloudArgs(1, 2, 3, 65536, 2048, 64, 64, 64, 2048, 2048)
+        assert getattr(lib, "spc_slab_cloud_fraction_" + sfx)(ctypes.byref(a), None) == _abi.SPC_ERR_UNSUPPORTED
+        assert b"slab_cloud_fraction needs 180224 B of LDS per workgroup (gfx950 has 163840)" in lib.spc_last_error()
+
+
+@pytest.mark.parametrize("dtype", [numpy.float64, numpy.float32])
+def test_edge_one_level_planes_tell_pairwise_from_sequential(dtype):
+    differ = []
+    for size in slab_edges.K1_SIZES:
+        f = slab_edges.k1_field(size, dtype)
+        want = slab_ref.slab_means(f)
+        assert want.shape == (3, 1) and numpy.array_equal(want[:, 0], [x.ravel().sum() / dtype(size) for x in f])
+        if not numpy.array_equal(want, numpy.stack([slab_ref.sequential_mean(x.reshape(size, 1, 1)) for x in f])):
+            differ.append(size)
+    assert differ and max(differ) > 8192 and min(differ) <= 257, differ
+
+
+@pytest.mark.parametrize("dtype", [numpy.float64, numpy.float32])
+def test_edge_means_notice_a_dropped_row(dtype):
+    """the fields of the remainder tests: leaving out the last row of a plane changes every mean"""
+    for plane in slab_edges.PLANES:
+        f = slab_edges.means_fields(plane + (33,), 3, 2, dtype, seed=1)["f1"]
+        rows = f.reshape(3, -1, 33)
+        if rows.shape[1] > 1:
+            short = numpy.stack([slab_ref.sequential_mean(r[:-1, None, :]) * dtype(rows.shape[1] - 1) / dtype(rows.shape[1]) for r in rows])
+            assert (short != slab_ref.slab_means(f)).all(), plane
+

@@ -8,7 +8,7 @@ import torch
 from sp_coupler_amd import synthetic
 from sp_coupler_amd.engine import Engine
 from sp_coupler_amd.multi import MultiDeviceEngine
-from tests import slab_ref
+from tests import slab_edges, slab_ref
 from tests.gpu_util import assert_bits
 
 pytestmark = pytest.mark.gpu
@@ -169,3 +169,60 @@ def test_two_engines_on_one_card_equal_one_engine():
     for k in host:
         assert numpy.array_equal(got[k].to_host(), want[k].cpu().numpy()) and numpy.array_equal(got[k].to_host(), slab_ref.slab_means(host[k]))
     assert numpy.array_equal(got_A.to_host(), want_A.cpu().numpy()) and numpy.array_equal(got_A.to_host(), slab_ref.cloud_fraction(ql, idx))
+
+
+# -- the edges of the kernels (tests/slab_edges.py holds the inputs and the bodies; tests/test_slab_cpu.py states that the
+#    oracle's answers to these inputs are not trivial; tools/mutation_control.py shows that wrong kernels fail them) ----------
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+@pytest.mark.parametrize("kind", slab_edges.QL_KINDS)
+@pytest.mark.parametrize("plane", slab_edges.PLANES)
+def test_cloud_fraction_with_fewer_rows_left_than_a_wave_takes(plane, kind, dtype):
+    slab_edges.check_cloud_plane(Engine("cuda:0", dtype=dtype), plane, kind)
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+@pytest.mark.parametrize("ktot", slab_edges.KTOTS)
+@pytest.mark.parametrize("nG", slab_edges.NGS)
+def test_cloud_fraction_layer_counts_level_counts_and_word_boundaries(nG, ktot, dtype):
+    slab_edges.check_cloud_layers(Engine("cuda:0", dtype=dtype), nG, ktot)
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+def test_cloud_fraction_with_opt_in_lds(dtype):
+    slab_edges.check_cloud_opt_in_lds(Engine("cuda:0", dtype=dtype))
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+def test_cloud_fraction_refuses_more_lds_than_the_device_has(dtype):
+    slab_edges.check_cloud_lds_refusal(Engine("cuda:0", dtype=dtype))
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+@pytest.mark.parametrize("ktot", slab_edges.MEANS_KTOTS)
+@pytest.mark.parametrize("plane", slab_edges.PLANES)
+def test_slab_means_of_every_remainder_of_rows(plane, ktot, dtype):
+    slab_edges.check_means_plane(Engine("cuda:0", dtype=dtype), plane, ktot)
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+@pytest.mark.parametrize("lead,lead_out", [(1, 0), (0, 1), (1, 1), (2, 0), (0, 2), (3, 3)])
+def test_slab_means_from_and_into_views_off_the_16_byte_grid(lead, lead_out, dtype):
+    slab_edges.check_means_unaligned_base(Engine("cuda:0", dtype=dtype), lead, lead_out)
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+@pytest.mark.parametrize("n", [1, 3, 129, 300])
+@pytest.mark.parametrize("ktot", [2, 4, 8, 16])
+def test_slab_means_with_few_lanes_per_les_and_idle_lanes(ktot, n, dtype):
+    slab_edges.check_means_lanes(Engine("cuda:0", dtype=dtype), ktot, n)
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+def test_slab_means_of_sixteen_fields_and_not_seventeen(dtype):
+    slab_edges.check_means_field_count(Engine("cuda:0", dtype=dtype))
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+@pytest.mark.parametrize("size", slab_edges.K1_SIZES)
+def test_slab_means_of_one_level_at_the_pairwise_block_sizes(size, dtype):
+    slab_edges.check_means_k1(Engine("cuda:0", dtype=dtype), size)

@@ -7,8 +7,11 @@ cross-compiles gfx950).  A run without --build (GPU) runs the properties of test
 the shipped library and of every mutant library, in ONE process (Engine(lib_path=...)).  Expected: the shipped library passes
 all, every mutant fails at least the property that guards its line.  Prints a table; exit status 1 if a mutant survives or
 the shipped library fails.  tests/test_mutation_table.py checks on the CPU that every edit still applies to the tree.
+Mutants 28 ... are slips of K10 (spc_slab.hpp); their guards are the bodies of tests/slab_edges.py, which the GPU tests of
+tests/test_slab_gpu.py run on the shipped library.
 usage: python tools/mutation_control.py --build [n ...] [-j N]
-       python tools/mutation_control.py > profiles/mutation_control.log"""
+       python tools/mutation_control.py > profiles/mutation_control.log
+       python tools/mutation_control.py --only 28 29 30 31 32 33 34 35 > profiles/mutation_control_slab.log"""
 import argparse
 import os
 import shutil
@@ -24,9 +27,23 @@ from __graft_entry__ import HIPCC, HIP_FLAGS  # noqa: E402  (the shipped library
 CSRC = os.path.join(ROOT, "sp_coupler_amd", "csrc")
 OUT = os.path.join(ROOT, "build", "mutants")
 K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp", "spc_vnudge2.hpp", "spc_sputils.hpp"
+SLAB = "spc_slab.hpp"
 A9 = "(col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG"     # the neighbouring column of the slab (mutant 9)
 
-# n: (the slip, the property of tests/semantic_props.py that guards it,
+def slab_edges(name):
+    """guard of a K10 mutant: the body ``name`` of tests/slab_edges.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import slab_edges as se
+        failed = []
+        for dtype in se.DTYPES:
+            failed += se.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "slab_edges." + name
+    return guard
+
+
+# n: (the slip, the property of tests/semantic_props.py that guards it -- or a callable guard(engine_of) -> (detected, names of
+#     everything that failed), engine_of(dtype) an Engine on the library under test,
 #     edits: (file under csrc/, exact old text, new text[, occurrences of the old text, default 1]), applied in order)
 MUTANTS = {
     1: ("K1 thl: exponent +rd/cp instead of -rd/cp (exner for iexner, sputils.py:28-34)", "isentropic_column_has_constant_thl",
@@ -87,6 +104,39 @@ MUTANTS = {
          "gcm_level_diagnostics_mean_what_their_names_say",
          [(K5, "stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + nG])));",
            "stg<WT>(&p.Zh[gh + k], div_grav(ldg(&p.Zghalf[gh + k]) - ldg(&p.Zghalf[gh + (nG - 1)])));")]),
+    # K10 (spc_slab.hpp).  Every mutant only computes wrong numbers: none reads or writes outside what the shipped kernel
+    # touches.  The guards `b < nb` of the loads and `q < nb` of the count loop of k_slab_cloud_count are a redundant pair:
+    # dropping either ALONE changes no output (rows past nb load as 0 and count nothing; masks of rows past nb are never
+    # counted), and dropping only the load guard reads past the field.  Mutant 28 is the slip both of them guard against, with
+    # the row index clamped so that it stays inside the field: the last row is loaded and counted for the missing ones.
+    28: ("K10 cloud count: a wave with fewer than SLAB_CF_RB rows left loads and counts SLAB_CF_RB rows (the last one again)",
+         slab_edges("cloud_plane"),
+         [(SLAB, "x[b] = (b < nb && k < ktot) ? base[(int64_t)(row + b) * ktot + k] : (T)0;",
+           "x[b] = (k < ktot) ? base[(int64_t)min(row + b, row1 - 1) * ktot + k] : (T)0;"),
+          (SLAB, "for (int q = 0; q < nb; ++q) c +=", "for (int q = 0; q < SLAB_CF_RB; ++q) c +=")]),
+    29: ("K10 slab_any_bit: a layer that ends ON a 64-level word boundary masks the whole word away (hi <= b0 + 64)",
+         slab_edges("cloud_layers"),
+         [(SLAB, "if (hi < b0 + 64) m &= (1ull << (hi - b0)) - 1ull;", "if (hi <= b0 + 64) m &= (1ull << (hi - b0)) - 1ull;")]),
+    30: ("K10 cloud count: the final sum over the waves runs once, layers r >= 256 never reach the output",
+         slab_edges("cloud_layers"),
+         [(SLAB, "    for (int r = tid; r < nG; r += SLAB_THREADS) {\n        int c = 0;",
+           "    for (int r = tid; r < min(nG, SLAB_THREADS); r += SLAB_THREADS) {\n        int c = 0;")]),
+    31: ("K10 layer bounds: a negative index clipped as an unsigned number (to ktot instead of 0)",
+         slab_edges("cloud_layers"),
+         [(SLAB, "const int hi = min(max(idx[r], 0), ktot);", "const int hi = (int)min((unsigned)idx[r], (unsigned)ktot);")]),
+    32: ("K10 slab means: the remainder loop starts at r + 1 (the last row of a plane with nij % 8 != 0 left out)",
+         slab_edges("means_plane"),
+         [(SLAB, "    for (; r < p.nij; ++r) {", "    for (++r; r < p.nij; ++r) {")]),
+    33: ("K10 slab means, ktot == 1: a sequential sum instead of numpy's pairwise one", slab_edges("means_k1"),
+         [(SLAB, "const T sum = vn_npsum([&](int i) { return src[i]; }, p.nij);",
+           "T sum = (T)0;\n    for (int i = 0; i < p.nij; ++i) sum += src[i];")]),
+    34: ("K10 slab_any_bit: the first level of a layer that starts inside a word is masked away (lo - b0 + 1)",
+         slab_edges("cloud_layers"),
+         [(SLAB, "if (lo > b0) m &= ~0ull << (lo - b0);", "if (lo > b0) m &= (~0ull << (lo - b0)) << 1;")]),
+    35: ("K10 cloud count: the per-wave counters of layers r >= 256 are added to the counters of wave 0 only",
+         slab_edges("cloud_layers"),
+         [(SLAB, "for (int w = 0; w < SLAB_CF_WAVES; ++w) c += cnt[w * nG + r];",
+           "for (int w = 0; w < (r < SLAB_THREADS ? SLAB_CF_WAVES : 1); ++w) c += cnt[w * nG + r];")]),
 }
 
 
@@ -140,6 +190,12 @@ def build(ns, jobs):
     return 1 if bad else 0
 
 
+def run_guard(guard, lib_path):
+    """a callable guard on the engines of one library -> (detected, what failed)"""
+    from sp_coupler_amd.engine import Engine
+    return guard(lambda dtype: Engine("cuda:0", dtype=dtype, lib_path=lib_path))
+
+
 def run(lib_path):
     from tests import semantic_props as sp
     from tests.test_semantic_gpu import HipImpl
@@ -155,24 +211,36 @@ def run(lib_path):
     return failed
 
 
-def main():
+def main(only=None):
     import torch
-    print("mutation control of tests/test_semantic_gpu.py on %s" % torch.cuda.get_device_name(0))
+    print("mutation control of tests/test_semantic_gpu.py and tests/slab_edges.py on %s" % torch.cuda.get_device_name(0))
     bad = 0
-    clean = run(None)
-    from tests import semantic_props as sp
-    print("shipped library: %d properties, failed: %s" % (len(sp.PROPERTIES), clean or "none"))
-    bad += bool(clean)
-    for n, (what, guard, _) in sorted(MUTANTS.items()):
+    chosen = sorted(n for n in MUTANTS if only is None or n in only)
+    if any(not callable(MUTANTS[n][1]) for n in chosen):
+        clean = run(None)
+        from tests import semantic_props as sp
+        print("shipped library: %d properties, failed: %s" % (len(sp.PROPERTIES), clean or "none"))
+        bad += bool(clean)
+    slab = [MUTANTS[n][1] for n in chosen if callable(MUTANTS[n][1])]
+    if slab:
+        slab_clean = run_guard(slab[0], None)[1]
+        print("shipped library: the bodies of tests/slab_edges.py on both engines, failed: %s" % (slab_clean or "none"), flush=True)
+        bad += bool(slab_clean)
+    for n in chosen:
+        what, guard, _ = MUTANTS[n]
         path = os.path.join(OUT, "libspc_mutant%d.so" % n)
         if not os.path.exists(path):
             print("mutant %2d: NOT BUILT (%s)" % (n, path))
             bad += 1
             continue
-        failed = run(path)
-        ok = guard in [f.split(" ")[0] for f in failed]
+        if callable(guard):
+            ok, failed = run_guard(guard, path)
+            guard = guard.__name__
+        else:
+            failed = run(path)
+            ok = guard in [f.split(" ")[0] for f in failed]
         bad += not ok
-        print("mutant %2d: %s\n           guarded by %s: %s; all failing: %s" % (n, what, guard, "DETECTED" if ok else "SURVIVED", failed or "none"))
+        print("mutant %2d: %s\n           guarded by %s: %s; all failing: %s" % (n, what, guard, "DETECTED" if ok else "SURVIVED", failed or "none"), flush=True)
     print("result: %s" % ("every mutant detected, shipped library clean" if not bad else "%d problem(s)" % bad))
     return 1 if bad else 0
 
@@ -181,6 +249,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description="mutation control of the semantic tests")
     ap.add_argument("--build", nargs="*", type=int, metavar="n",
                     help="build the mutant libraries n ... (default: all) instead of running the control")
+    ap.add_argument("--only", nargs="+", type=int, metavar="n", help="run the control for the mutants n ... only")
     ap.add_argument("-j", type=int, default=4, help="parallel compiles for --build (at most 16)")
     args = ap.parse_args()
     if args.build is not None:
@@ -188,4 +257,4 @@ if __name__ == "__main__":
         if unknown:
             ap.error("no mutant %s" % unknown)
         sys.exit(build(args.build or sorted(MUTANTS), args.j))
-    sys.exit(main())
+    sys.exit(main(set(args.only) if args.only else None))
