@@ -24,6 +24,8 @@
  *   spc_slab_means_* / spc_slab_cloud_fraction_*
  *                        <- les.get_profile_U/V/THL/QT/QL/... and les.get_cloudfraction(indices) as get_les_profiles calls
  *                           them (splib/spcpl.py:748-765, 629-630), from device-resident 3-D fields
+ *   spc_les_advance_*    <- the step of a device-resident LES ensemble: forcings applied to the 3-D fields in place,
+ *                           ql = max(qt - qsat, 0), and the slab means of the stepped fields, in one pass
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -382,6 +384,41 @@ typedef struct spc_slab_cloud_args {
 } spc_slab_cloud_args;
 int spc_slab_cloud_fraction_f64(const spc_slab_cloud_args *args, void *stream);
 int spc_slab_cloud_fraction_f32(const spc_slab_cloud_args *args, void *stream);
+
+/* ---- one step of the device-resident LES fields, with the slab means of the stepped fields (kernel family K11) --- */
+/* The forcings applied to fields [n_les][itot][jtot][ktot] of one shape (layout and offsets as K10), the saturation
+ * adjustment of the ensemble (ql = max(qt - qsat, 0)) and the slab means of the NEW fields, in one pass over the fields:
+ *   for f < n_fields, where tend[f] != NULL:                       (a field without a tendency keeps its bits)
+ *       inc[l][k]             = tend[f][l * pitch_tend + k] * (T)dt             one rounding in the element type T
+ *       fields[f][l][i][j][k] = fields[f][l][i][j][k] + inc[l][k]               one rounding, IN PLACE, never an fma
+ *   if sat_field >= 0:                                             (fields[sat_field] is QT, AFTER its update)
+ *       d = fields[sat_field][l][i][j][k] - qsat[l][i][j][k]
+ *       q = d > 0 ? d : (d != d ? d : +0.0)                        NaN stays NaN; -0.0 and negatives give +0.0
+ *       ql[l][i][j][k] = q  where ql != NULL
+ *   mean[f][l * pitch_mean + k] = numpy.mean(new fields[f][l], axis=(0, 1))[k]  where mean[f] != NULL, and ql_mean of q:
+ *       spc_slab_means_*'s rule, bit for bit (sequential sum from +0 over (i, j) in row-major order in T, one division).
+ * qsat, ql and ql_mean are ignored when sat_field == -1.  ql must not be a field or qsat; qsat must not be a field; the
+ * fields must differ.  ktot == 1 is SPC_ERR_UNSUPPORTED (numpy reduces a one-level plane pairwise: step the field and call
+ * spc_slab_means_*).  The q rule is this library's definition; it equals numpy.maximum(d, 0) and differs from torch's
+ * clamp_min on the CPU only for d == -0.0.  tend and mean are device pointers with a row pitch, so the
+ * launch can read K1's outputs and write K1 / K3's inputs in place.                                                   */
+#define SPC_ADVANCE_MAX_FIELDS 8
+typedef struct spc_les_advance_args {
+    int64_t n_les;                 /* 0 is allowed: no-op                                                  */
+    int32_t itot, jtot, ktot;
+    int32_t n_fields;              /* 1 ... SPC_ADVANCE_MAX_FIELDS                                         */
+    void *fields[8];               /* device [n_les][itot][jtot][ktot] each, updated in place              */
+    const void *tend[8];           /* device [n_les x ktot] each, rows pitch_tend apart, or NULL           */
+    void *mean[8];                 /* device [n_les x ktot] each, rows pitch_mean apart, or NULL           */
+    int64_t pitch_tend, pitch_mean; /* >= ktot                                                             */
+    double dt;                     /* rounded to the element type once                                     */
+    int32_t sat_field, reserved;   /* index of QT in fields, or -1: no saturation adjustment               */
+    const void *qsat;              /* device [n_les][itot][jtot][ktot]; required when sat_field >= 0       */
+    void *ql;                      /* device [n_les][itot][jtot][ktot], or NULL                            */
+    void *ql_mean;                 /* device [n_les x ktot], rows pitch_mean apart, or NULL                */
+} spc_les_advance_args;
+int spc_les_advance_f64(const spc_les_advance_args *args, void *stream);
+int spc_les_advance_f32(const spc_les_advance_args *args, void *stream);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

@@ -110,6 +110,16 @@ class SlabCloudArgs(ctypes.Structure):
                 + _ptrs("ql", "idx", "out") + [("pitch_idx", c_int64), ("pitch_out", c_int64)])
 
 
+ADVANCE_MAX_FIELDS = 8    # SPC_ADVANCE_MAX_FIELDS
+
+
+class LesAdvanceArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32),
+                 ("fields", c_void_p * ADVANCE_MAX_FIELDS), ("tend", c_void_p * ADVANCE_MAX_FIELDS),
+                 ("mean", c_void_p * ADVANCE_MAX_FIELDS), ("pitch_tend", c_int64), ("pitch_mean", c_int64), ("dt", c_double),
+                 ("sat_field", c_int32), ("reserved", c_int32)] + _ptrs("qsat", "ql", "ql_mean"))
+
+
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
 SPC_LOC_EXTERIOR, SPC_LOC_BOUNDARY, SPC_LOC_INTERIOR = 0, 1, 2
 
@@ -148,6 +158,8 @@ PROTOTYPES = {
     "spc_slab_means_f32": (ctypes.c_int, [ctypes.POINTER(SlabMeansArgs), c_void_p]),
     "spc_slab_cloud_fraction_f64": (ctypes.c_int, [ctypes.POINTER(SlabCloudArgs), c_void_p]),
     "spc_slab_cloud_fraction_f32": (ctypes.c_int, [ctypes.POINTER(SlabCloudArgs), c_void_p]),
+    "spc_les_advance_f64": (ctypes.c_int, [ctypes.POINTER(LesAdvanceArgs), c_void_p]),
+    "spc_les_advance_f32": (ctypes.c_int, [ctypes.POINTER(LesAdvanceArgs), c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

@@ -17,6 +17,8 @@
 //                  host: spc_lesstate_host.hpp
 //   K10 k_slab_means, k_slab_cloud_*  slab means and cloud fraction of device-resident LES fields (les.get_profile_*,
 //                  les.get_cloudfraction): spc_slab.hpp, kernels and host side
+//   K11 k_les_advance  one step of those fields in place (forcings, ql = max(qt - qsat, 0)) and the slab means of the stepped
+//                  fields in one pass: spc_advance.hpp, kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -65,6 +67,7 @@ namespace {
 #include "spc_geo.hpp"
 #include "spc_lesstate.hpp"
 #include "spc_slab.hpp"
+#include "spc_advance.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -75,6 +78,9 @@ namespace {
 #define SPC_SLAB_HOST
 #include "spc_slab.hpp"
 #undef SPC_SLAB_HOST
+#define SPC_ADVANCE_HOST
+#include "spc_advance.hpp"
+#undef SPC_ADVANCE_HOST
 
 }  // namespace
 
@@ -138,6 +144,9 @@ int spc_slab_means_f64(const spc_slab_means_args *a, void *s) { return slab_mean
 int spc_slab_means_f32(const spc_slab_means_args *a, void *s) { return slab_means_impl<float>(a, s); }
 int spc_slab_cloud_fraction_f64(const spc_slab_cloud_args *a, void *s) { return slab_cloud_impl<double>(a, s); }
 int spc_slab_cloud_fraction_f32(const spc_slab_cloud_args *a, void *s) { return slab_cloud_impl<float>(a, s); }
+
+int spc_les_advance_f64(const spc_les_advance_args *a, void *s) { return les_advance_impl<double>(a, s); }
+int spc_les_advance_f32(const spc_les_advance_args *a, void *s) { return les_advance_impl<float>(a, s); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

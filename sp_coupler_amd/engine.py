@@ -608,6 +608,69 @@ class Engine:
         self._call(fn, ctypes.byref(a), stream=stream)
         return o
 
+    # -- K11: one step of device-resident LES fields and the slab means of the stepped fields, one launch ---------------
+    @_on_engine_stream
+    def les_advance(self, fields, tend, dt, qsat=None, sat=None, ql=None, means=None, ql_mean=True, stream=None):
+        """``field += (tend * dt)[:, None, None, :]`` IN PLACE for every name of ``fields`` (dict name -> contiguous
+        [n x itot x jtot x ktot] tensor, at most ``_abi.ADVANCE_MAX_FIELDS`` of one shape) that ``tend`` (dict name ->
+        [n x ktot], rows may be pitched, all with one pitch) holds; a field without a tendency keeps its bits.  With
+        ``sat`` (the name of the QT field) and ``qsat``: ``q = max(fields[sat] - qsat, 0)`` of the UPDATED field (NaN stays
+        NaN, -0.0 gives +0.0: include/spc.h), written to ``ql`` where given.  Returns the slab means of the new fields,
+        dict name -> [n x ktot] (``Engine.slab_means``' rule, bit for bit), with ``"QL"`` = the mean of q when ``sat`` is
+        given and ``ql_mean`` is true.  ``means``: dict name -> [n x ktot] tensors to write into (``"QL"`` included), pitched
+        as in ``slab_means``.  One launch; a field of one level (ktot == 1) is refused (SPC_ERR_UNSUPPORTED)."""
+        names = list(fields)
+        if not 1 <= len(names) <= _abi.ADVANCE_MAX_FIELDS:
+            raise ValueError("les_advance takes 1 ... %d fields per launch, got %d" % (_abi.ADVANCE_MAX_FIELDS, len(names)))
+        unknown = [k for k in tend if k not in fields]
+        if unknown:
+            raise ValueError("les_advance: tendencies %s have no field" % unknown)
+        if (sat is None) != (qsat is None):
+            raise ValueError("les_advance: sat (the name of the QT field) and qsat come together")
+        if sat is not None and sat not in fields:
+            raise ValueError("les_advance: sat = %r is not one of the fields %s" % (sat, names))
+        if sat is None and ql is not None:
+            raise ValueError("les_advance: ql needs sat and qsat")
+        if sat is not None and ql_mean and "QL" in fields:
+            raise ValueError("les_advance: the mean of q is returned as 'QL', which is also the name of a field")
+        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_advance: empty field shape %s" % (shape,))
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.LesAdvanceArgs()
+        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields, a.dt = n, itot, jtot, ktot, len(names), float(dt)
+        a.pitch_tend = a.pitch_mean = ktot
+        res, pitch, pitch_t = {}, None, None
+
+        def mean_of(name):
+            nonlocal pitch
+            o, p = self._out(None if means is None or name not in means else means[name], n, ktot)
+            if pitch is not None and n > 1 and p != pitch:
+                raise ValueError("les_advance: means[%s] has row pitch %d, the others %d" % (name, p, pitch))
+            pitch = p
+            res[name] = o
+            return o.data_ptr()
+        for f, name in enumerate(names):
+            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            if name in tend:
+                a.tend[f], pitch_t = ck.mat("tend[%s]" % name, tend[name], n, ktot, pitch=pitch_t)
+            a.mean[f] = mean_of(name)
+        a.sat_field = -1
+        if sat is not None:
+            a.sat_field = names.index(sat)
+            a.qsat = self._field4("qsat", qsat, shape).data_ptr()
+            if ql is not None:
+                a.ql = self._field4("ql", ql, shape).data_ptr()
+            if ql_mean:
+                a.ql_mean = mean_of("QL")
+        a.pitch_mean = pitch
+        if pitch_t is not None:
+            a.pitch_tend = pitch_t
+        fn = self.lib.spc_les_advance_f32 if self.dtype == torch.float32 else self.lib.spc_les_advance_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

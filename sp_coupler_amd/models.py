@@ -660,6 +660,9 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
+    STEP_KEYS = ("U", "V", "THL", "QT")                # fields a step applies a tendency to
+    fused_advance = True                               # evolve_model_batched: one K11 launch (False: torch ops + K10)
+    FUSED_MIN_LES = 128                                # ... where a launch holds at least so many LES
 
     def __init__(self, grid_indices, zf, zh, prof, itot=8, jtot=8, engine=None):
         super().__init__(grid_indices, zf, zh, prof)
@@ -780,6 +783,30 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         with eng.on_stream():
             numpy.copyto(out, self._host(A))
 
+    def _fused_step(self, dt):
+        """the step of the fields, the QL field and the slab means of the new fields from ONE launch per device (K11,
+        ``Engine.les_advance``); False -- nothing done -- where the engine has no such method, the LES have one level (numpy
+        reduces a one-level plane pairwise: K10's own kernel), nothing is stepped or saturated, or ``fused_advance`` is off"""
+        import torch
+        eng, f = self._eng(), self.fields3d
+        keys = [k for k in self.STEP_KEYS if k in f]
+        sat = "QT" in f and "Qsat" in f
+        if not (self.fused_advance and self.nL > 1 and self.n > 0 and keys and (sat or any(k in self.tend for k in keys))):
+            return False
+        if max(int(part.shape[0]) for part in getattr(f[keys[0]], "parts", [f[keys[0]]])) < self.FUSED_MIN_LES:
+            return False                                  # a launch of few LES is a latency chain: the torch path is faster
+        if ("QL" in f and not sat) or not all(callable(getattr(e, "les_advance", None)) for e in getattr(eng, "engines", [eng])):
+            return False
+        tend = {k: self._upload(self.tend[k]) for k in keys if k in self.tend}
+        if sat and "QL" not in f:
+            f["QL"] = self._per_device(torch.empty_like, f["QT"])          # written whole by the launch
+        dev = eng.les_advance({k: f[k] for k in keys}, tend, dt, qsat=f["Qsat"] if sat else None, sat="QT" if sat else None,
+                              ql=f["QL"] if sat else None)
+        with eng.on_stream():
+            self._means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
+        self.p.update(self._means)
+        return True
+
     @_timed
     def evolve_model_batched(self, t):
         import torch
@@ -787,21 +814,24 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if dt <= 0:
             return
         f, p = self.fields3d, self.p
-        for key in ("U", "V", "THL", "QT"):
-            if key in self.tend and key in f:
-                def step(field, tend):
-                    inc = tend * dt                       # two separate ops: nothing contracts to an fma
-                    return field.add_(inc[:, None, None, :])
-                self._per_device(step, f[key], self._upload(self.tend[key]))
-        if "QL" in f or ("QT" in f and "Qsat" in f):
-            self._ensure_ql()
+        if self._fused_step(dt):
+            pass                                          # K11: fields, QL and p[U, V, THL, QT, QL] from one launch
+        else:
+            for key in self.STEP_KEYS:
+                if key in self.tend and key in f:
+                    def step(field, tend):
+                        inc = tend * dt                   # two separate ops: nothing contracts to an fma
+                        return field.add_(inc[:, None, None, :])
+                    self._per_device(step, f[key], self._upload(self.tend[key]))
+            if "QL" in f or ("QT" in f and "Qsat" in f):
+                self._ensure_ql()
 
-            def saturate(ql, qt, qs):
-                torch.sub(qt, qs, out=ql)
-                return ql.clamp_min_(0.0)
-            self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
-        self._means = None
-        self._slab_means()                                # p[U, V, THL, QT, QL] = the slab means of the new fields
+                def saturate(ql, qt, qs):
+                    torch.sub(qt, qs, out=ql)
+                    return ql.clamp_min_(0.0)
+                self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
+            self._means = None
+            self._slab_means()                            # p[U, V, THL, QT, QL] = the slab means of the new fields
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
         p["QL_ice"] = numpy.minimum(p["QL_ice"], p["QL"])

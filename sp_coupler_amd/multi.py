@@ -225,6 +225,11 @@ class MultiDeviceEngine:
         """K10 on every device's LES: dict of Sharded fields [n x itot x jtot x ktot] in, dict of Sharded [n x ktot] out"""
         return self._run("slab_means", fields, out=out, **kw)
 
+    def les_advance(self, fields, tend, dt, qsat=None, sat=None, ql=None, means=None, ql_mean=True, **kw):
+        """K11 on every device's LES: dicts of Sharded fields and tendencies in (the fields stepped in place, block by block),
+        dict of Sharded [n x ktot] slab means of the stepped fields out; one launch per device that holds rows"""
+        return self._run("les_advance", fields, tend, dt, qsat=qsat, sat=sat, ql=ql, means=means, ql_mean=ql_mean, **kw)
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

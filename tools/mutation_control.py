@@ -9,9 +9,12 @@ all, every mutant fails at least the property that guards its line.  Prints a ta
 the shipped library fails.  tests/test_mutation_table.py checks on the CPU that every edit still applies to the tree.
 Mutants 28 ... are slips of K10 (spc_slab.hpp); their guards are the bodies of tests/slab_edges.py, which the GPU tests of
 tests/test_slab_gpu.py run on the shipped library.
+ADVANCE_MUTANTS is the table of K11 (spc_advance.hpp), numbered on its own and chosen with --advance; its guards are the
+bodies of tests/les_advance_ref.py, which tests/test_les_advance_gpu.py runs on the shipped library.
 usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py > profiles/mutation_control.log
-       python tools/mutation_control.py --only 28 29 30 31 32 33 34 35 > profiles/mutation_control_slab.log"""
+       python tools/mutation_control.py --only 28 29 30 31 32 33 34 35 > profiles/mutation_control_slab.log
+       python tools/mutation_control.py --advance --build && python tools/mutation_control.py --advance > profiles/mutation_control_advance.log"""
 import argparse
 import os
 import shutil
@@ -28,6 +31,7 @@ CSRC = os.path.join(ROOT, "sp_coupler_amd", "csrc")
 OUT = os.path.join(ROOT, "build", "mutants")
 K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp", "spc_vnudge2.hpp", "spc_sputils.hpp"
 SLAB = "spc_slab.hpp"
+ADVANCE = "spc_advance.hpp"
 A9 = "(col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG"     # the neighbouring column of the slab (mutant 9)
 
 def slab_edges(name):
@@ -140,11 +144,48 @@ MUTANTS = {
 }
 
 
-def patched(n, src=CSRC):
-    """{file: text} of the files mutant n changes, its edits applied to the sources under `src`; ValueError when an edit's
-    old text does not occur exactly the expected number of times (the tree has drifted from the table)"""
+def advance_body(name):
+    """guard of a K11 mutant: the body ``name`` of tests/les_advance_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_advance_ref as lar
+        failed = []
+        for dtype in lar.DTYPES:
+            failed += lar.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_advance_ref." + name
+    return guard
+
+
+# K11 (spc_advance.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 6 stores the rows of the batch before once more, inside the field).
+_OLD = [(ADVANCE, "    if (upd) {\n#pragma unroll\n        for (int v = 0; v < V; ++v) x.v[v] = x.v[v] + inc.v[v];",
+         "    const SlabVec<T, V> old = x;\n    if (upd) {\n#pragma unroll\n        for (int v = 0; v < V; ++v) x.v[v] = x.v[v] + inc.v[v];")]
+ADVANCE_MUTANTS = {
+    1: ("K11 update: tend * dt contracted into the add (one rounding, an fma, instead of two)", advance_body("parity"),
+        [(ADVANCE, "for (int v = 0; v < V; ++v) inc.v[v] = t.v[v] * p.dt;", "for (int v = 0; v < V; ++v) inc.v[v] = t.v[v];"),
+         (ADVANCE, "const SlabVec<T, V> &inc, bool upd, T *dst, T *ql,", "const SlabVec<T, V> &inc, bool upd, T dtm, T *dst, T *ql,"),
+         (ADVANCE, "inc, upd, dst", "inc, upd, p.dt, dst", 2),
+         (ADVANCE, "x.v[v] = x.v[v] + inc.v[v];", "x.v[v] = __builtin_fma(inc.v[v], dtm, x.v[v]);")]),
+    2: ("K11 update: the last row (itot-1, jtot-1) of a plane that ends in single rows is summed but not updated",
+        advance_body("parity"),
+        [(ADVANCE, "adv_row<T, V, SAT>(x1, s1, inc, upd, dst, ql, acc, accq);", "adv_row<T, V, SAT>(x1, s1, inc, upd && r + 1 < nij, dst, ql, acc, accq);")]),
+    3: ("K11 saturation: q taken from QT before its update", advance_body("parity"),
+        _OLD + [(ADVANCE, "const T d = x.v[v] - s.v[v];", "const T d = old.v[v] - s.v[v];")]),
+    4: ("K11 saturation: d >= 0 keeps d, so d == -0.0 gives -0.0", advance_body("special"),
+        [(ADVANCE, "q.v[v] = d > (T)0 ? d : (d != d ? d : (T)0);", "q.v[v] = d >= (T)0 ? d : (d != d ? d : (T)0);")]),
+    5: ("K11 means: the sum taken of the field before its update", advance_body("parity"),
+        _OLD + [(ADVANCE, "for (int v = 0; v < V; ++v) acc.v[v] += x.v[v];", "for (int v = 0; v < V; ++v) acc.v[v] += old.v[v];")]),
+    6: ("K11 look-ahead: the guard of the next batch off by one (r + 2 U < nij): the last whole batch is not loaded", advance_body("planes"),
+        [(ADVANCE, "const bool more = r + 2 * U <= nij;", "const bool more = r + 2 * U < nij;")]),
+}
+
+
+def patched(n, src=CSRC, table=None):
+    """{file: text} of the files mutant n (of ``table``, default MUTANTS) changes, its edits applied to the sources under
+    `src`; ValueError when an edit's old text does not occur exactly the expected number of times (the tree has drifted from
+    the table)"""
     files = {}
-    for edit in MUTANTS[n][2]:
+    for edit in (table or MUTANTS)[n][2]:
         name, old, new = edit[:3]
         want = edit[3] if len(edit) > 3 else 1
         if name not in files:
@@ -157,14 +198,18 @@ def patched(n, src=CSRC):
     return files
 
 
-def build_one(n):
-    src = os.path.join(OUT, "src%d" % n)
+def lib_of(n, table=None):
+    return os.path.join(OUT, "libspc_%smutant%d.so" % ("advance_" if table is ADVANCE_MUTANTS else "", n))
+
+
+def build_one(n, table=None):
+    src = os.path.join(OUT, "src%s%d" % ("adv" if table is ADVANCE_MUTANTS else "", n))
     shutil.rmtree(src, ignore_errors=True)
     shutil.copytree(CSRC, src)
-    for name, text in patched(n).items():
+    for name, text in patched(n, table=table).items():
         with open(os.path.join(src, name), "w") as f:
             f.write(text)
-    lib = os.path.join(OUT, "libspc_mutant%d.so" % n)
+    lib = lib_of(n, table)
     r = subprocess.run([HIPCC] + HIP_FLAGS + [os.path.join(src, "spc_hip.hip"), "-o", lib], cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode:
@@ -172,13 +217,13 @@ def build_one(n):
     return lib
 
 
-def build(ns, jobs):
+def build(ns, jobs, table=None):
     os.makedirs(OUT, exist_ok=True)
     bad = 0
 
     def one(n):
         try:
-            build_one(n)
+            build_one(n, table)
             return "mutant %d built" % n, 0
         except (ValueError, RuntimeError) as e:
             return "mutant %d FAILED: %s" % (n, e), 1
@@ -209,6 +254,29 @@ def run(lib_path):
         except Exception:
             failed.append(prop.__name__[5:] + " (raised: %s)" % traceback.format_exc().strip().splitlines()[-1])
     return failed
+
+
+def main_advance(only=None):
+    """the control of ADVANCE_MUTANTS: the bodies of tests/les_advance_ref.py on the shipped library, then on every mutant"""
+    import torch
+    print("mutation control of tests/les_advance_ref.py (tests/test_les_advance_gpu.py) on %s" % torch.cuda.get_device_name(0))
+    chosen = sorted(n for n in ADVANCE_MUTANTS if only is None or n in only)
+    clean = run_guard(ADVANCE_MUTANTS[chosen[0]][1], None)[1]
+    print("shipped library: the bodies of tests/les_advance_ref.py on both engines, failed: %s" % (clean or "none"), flush=True)
+    bad = int(bool(clean))
+    for n in chosen:
+        what, guard, _ = ADVANCE_MUTANTS[n]
+        path = lib_of(n, ADVANCE_MUTANTS)
+        if not os.path.exists(path):
+            print("K11 mutant %2d: NOT BUILT (%s)" % (n, path))
+            bad += 1
+            continue
+        ok, failed = run_guard(guard, path)
+        bad += not ok
+        print("K11 mutant %2d: %s\n           guarded by %s: %s; all failing: %s"
+              % (n, what, guard.__name__, "DETECTED" if ok else "SURVIVED", failed or "none"), flush=True)
+    print("result: %s" % ("every mutant detected, shipped library clean" if not bad else "%d problem(s)" % bad))
+    return 1 if bad else 0
 
 
 def main(only=None):
@@ -251,10 +319,12 @@ if __name__ == "__main__":
                     help="build the mutant libraries n ... (default: all) instead of running the control")
     ap.add_argument("--only", nargs="+", type=int, metavar="n", help="run the control for the mutants n ... only")
     ap.add_argument("-j", type=int, default=4, help="parallel compiles for --build (at most 16)")
+    ap.add_argument("--advance", action="store_true", help="the table of K11 (ADVANCE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
+    table = ADVANCE_MUTANTS if args.advance else MUTANTS
     if args.build is not None:
-        unknown = sorted(set(args.build) - set(MUTANTS))
+        unknown = sorted(set(args.build) - set(table))
         if unknown:
             ap.error("no mutant %s" % unknown)
-        sys.exit(build(args.build or sorted(MUTANTS), args.j))
-    sys.exit(main(set(args.only) if args.only else None))
+        sys.exit(build(args.build or sorted(table), args.j, table))
+    sys.exit((main_advance if args.advance else main)(set(args.only) if args.only else None))
