@@ -26,6 +26,9 @@
  *                           them (splib/spcpl.py:748-765, 629-630), from device-resident 3-D fields
  *   spc_les_advance_*    <- the step of a device-resident LES ensemble: forcings applied to the 3-D fields in place,
  *                           ql = max(qt - qsat, 0), and the slab means of the stepped fields, in one pass
+ *   spc_les_thermo_*     <- the saturation adjustment of that ensemble (nothing of it is in the reference): Qsat, QL and
+ *                           T of every cell from THL, QT and the pressure by a Newton iteration over a
+ *                           saturation-pressure table, with the slab means of QL and T, in one pass
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -419,6 +422,51 @@ typedef struct spc_les_advance_args {
 } spc_les_advance_args;
 int spc_les_advance_f64(const spc_les_advance_args *args, void *stream);
 int spc_les_advance_f32(const spc_les_advance_args *args, void *stream);
+
+/* ---- saturation adjustment of the device-resident LES fields, with the slab means of QL and T (kernel family K12) --- */
+/* Per cell (l, i, j, k) of fields [n_les][itot][jtot][ktot] (layout and offsets as K10), in the element type T, one rounding
+ * per operation, never an fma.  Constants: eps = T(rd) / T(rv), om = T(1) - eps, c = T(rlv) / T(cp) (rd 287.04, rv 461.5,
+ * cp 1004, rlv 2.53e6), lo = T(t_lo), s = T(inv_step), hi = T(t_lo + (n_tab - 1) / inv_step) (formed in double);
+ * p = presf[l * pitch_prof + k]:
+ *   Tl = thl * ex[l * pitch_prof + k]
+ *   sat(Tk):  Tc  = Tk < lo ? lo : (Tk > hi ? hi : Tk)                        (NaN passes through)
+ *             x   = (Tc - lo) * s
+ *             m   = x >= 0 ? min((int)x, n_tab - 2) : 0                       (truncation; NaN gives m = 0)
+ *             w   = x - T(m);   d = es_tab[m + 1] - es_tab[m];   e = es_tab[m] + w * d
+ *             den = p - om * e
+ *             qs  = (eps * e) / den
+ *             dqs = ((eps * p) * (d * s)) / (den * den)
+ *   Tk = Tl
+ *   n_iter times:  qs, dqs = sat(Tk)
+ *                  Tk = qt > qs ? Tk - ((Tk - Tl) - c * (qt - qs)) / (T(1) + c * dqs) : Tl
+ *   qs, _ = sat(Tk)
+ *   dq = qt - qs;   q = dq > 0 ? dq : (dq != dq ? dq : +0.0)                   (the q rule of spc_les_advance_*)
+ *   t  = Tl + (T(rlv) * q) / T(cp)
+ *   qsat[l][i][j][k] = qs;   ql[l][i][j][k] = q;   temp[l][i][j][k] = t  where temp != NULL
+ *   ql_mean, t_mean [l * pitch_mean + k] = the slab means of q and t by spc_slab_means_*'s rule, bit for bit (sequential sum
+ *       from +0 over (i, j) in row-major order in T, one division); each where its pointer != NULL.
+ * den <= 0 is not guarded: IEEE decides.  The kernel calls no transcendental function: es_tab (saturation pressure over
+ * water at t_lo + m / inv_step, sp_coupler_amd/thermo.py) and ex (the Exner factor (presf / 1e5) ** (rd / cp)) are inputs.
+ * thl and qt are read only; no output may be one of the inputs or another output.  ktot == 1 is SPC_ERR_UNSUPPORTED, as in
+ * spc_les_advance_*.  The rule is this library's definition.                                           */
+typedef struct spc_les_thermo_args {
+    int64_t n_les;                 /* 0 is allowed: no-op                                                  */
+    int32_t itot, jtot, ktot;
+    int32_t n_iter;                /* >= 0 Newton iterations                                               */
+    const void *thl, *qt;          /* device [n_les][itot][jtot][ktot], read only                          */
+    const void *presf, *ex;        /* device [n_les x ktot] each, rows pitch_prof apart                    */
+    int64_t pitch_prof;            /* >= ktot                                                              */
+    const void *es_tab;            /* device [n_tab], element type of the fields                           */
+    int32_t n_tab;                 /* >= 2                                                                 */
+    int32_t table_mode;            /* tuning: 0 library's choice, 1 table staged in LDS, 2 read from global memory */
+    double t_lo, inv_step;         /* temperature of es_tab[0]; entries per kelvin                         */
+    void *qsat, *ql;               /* device [n_les][itot][jtot][ktot]                                     */
+    void *temp;                    /* device [n_les][itot][jtot][ktot], or NULL                            */
+    void *ql_mean, *t_mean;        /* device [n_les x ktot] each, rows pitch_mean apart, or NULL           */
+    int64_t pitch_mean;            /* >= ktot                                                              */
+} spc_les_thermo_args;
+int spc_les_thermo_f64(const spc_les_thermo_args *args, void *stream);
+int spc_les_thermo_f32(const spc_les_thermo_args *args, void *stream);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

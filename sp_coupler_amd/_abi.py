@@ -120,6 +120,15 @@ class LesAdvanceArgs(ctypes.Structure):
                  ("sat_field", c_int32), ("reserved", c_int32)] + _ptrs("qsat", "ql", "ql_mean"))
 
 
+class LesThermoArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_iter", c_int32)]
+                + _ptrs("thl", "qt", "presf", "ex") + [("pitch_prof", c_int64)] + _ptrs("es_tab")
+                + [("n_tab", c_int32), ("table_mode", c_int32), ("t_lo", c_double), ("inv_step", c_double)]
+                + _ptrs("qsat", "ql", "temp", "ql_mean", "t_mean") + [("pitch_mean", c_int64)])
+
+
+THERMO_TABLE_LIBRARY, THERMO_TABLE_LDS, THERMO_TABLE_GLOBAL = 0, 1, 2      # spc_les_thermo_args.table_mode
+
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
 SPC_LOC_EXTERIOR, SPC_LOC_BOUNDARY, SPC_LOC_INTERIOR = 0, 1, 2
 
@@ -160,6 +169,8 @@ PROTOTYPES = {
     "spc_slab_cloud_fraction_f32": (ctypes.c_int, [ctypes.POINTER(SlabCloudArgs), c_void_p]),
     "spc_les_advance_f64": (ctypes.c_int, [ctypes.POINTER(LesAdvanceArgs), c_void_p]),
     "spc_les_advance_f32": (ctypes.c_int, [ctypes.POINTER(LesAdvanceArgs), c_void_p]),
+    "spc_les_thermo_f64": (ctypes.c_int, [ctypes.POINTER(LesThermoArgs), c_void_p]),
+    "spc_les_thermo_f32": (ctypes.c_int, [ctypes.POINTER(LesThermoArgs), c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

@@ -19,6 +19,8 @@
 //                  les.get_cloudfraction): spc_slab.hpp, kernels and host side
 //   K11 k_les_advance  one step of those fields in place (forcings, ql = max(qt - qsat, 0)) and the slab means of the stepped
 //                  fields in one pass: spc_advance.hpp, kernel and host side
+//   K12 k_les_thermo  saturation adjustment of those fields (Qsat, QL, T per cell by a Newton iteration over a
+//                  saturation-pressure table) and the slab means of QL and T in one pass: spc_thermo.hpp, kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -68,6 +70,7 @@ namespace {
 #include "spc_lesstate.hpp"
 #include "spc_slab.hpp"
 #include "spc_advance.hpp"
+#include "spc_thermo.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -81,6 +84,9 @@ namespace {
 #define SPC_ADVANCE_HOST
 #include "spc_advance.hpp"
 #undef SPC_ADVANCE_HOST
+#define SPC_THERMO_HOST
+#include "spc_thermo.hpp"
+#undef SPC_THERMO_HOST
 
 }  // namespace
 
@@ -147,6 +153,9 @@ int spc_slab_cloud_fraction_f32(const spc_slab_cloud_args *a, void *s) { return 
 
 int spc_les_advance_f64(const spc_les_advance_args *a, void *s) { return les_advance_impl<double>(a, s); }
 int spc_les_advance_f32(const spc_les_advance_args *a, void *s) { return les_advance_impl<float>(a, s); }
+
+int spc_les_thermo_f64(const spc_les_thermo_args *a, void *s) { return les_thermo_impl<double>(a, s); }
+int spc_les_thermo_f32(const spc_les_thermo_args *a, void *s) { return les_thermo_impl<float>(a, s); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

@@ -225,6 +225,7 @@ class Engine:
         self.dtype = dtype
         sfx = _DTYPES[dtype]
         self._vn_work = None                    # variability_nudge's transposed-plane scratch, grown on demand
+        self._es_tab = None                     # les_thermo's saturation-pressure table on the device, uploaded on first use
         self._fwd = getattr(self.lib, "spc_forward_" + sfx)
         self._bwd = getattr(self.lib, "spc_backward_" + sfx)
         self._idx = getattr(self.lib, "spc_cloud_indices_" + sfx)
@@ -668,6 +669,54 @@ class Engine:
         if pitch_t is not None:
             a.pitch_tend = pitch_t
         fn = self.lib.spc_les_advance_f32 if self.dtype == torch.float32 else self.lib.spc_les_advance_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
+    # -- K12: saturation adjustment of device-resident LES fields and the slab means of QL and T, one launch -------------
+    @_on_engine_stream
+    def les_thermo(self, thl, qt, presf, ex, n_iter=None, qsat=None, ql=None, temp=None, means=True, stream=None, table_mode=0):
+        """Qsat, QL (and T where ``temp`` is given) of every cell of the device fields ``thl`` and ``qt`` (contiguous
+        [n x itot x jtot x ktot], read only) at the pressures ``presf`` [n x ktot] with the Exner factors ``ex`` [n x ktot]
+        (``thermo.exner(presf)``; rows may be pitched, both with one pitch): ``n_iter`` Newton iterations (default
+        ``thermo.DEFAULT_N_ITER``) over the saturation-pressure table of ``thermo.saturation_table`` (include/spc.h has the
+        rule).  ``qsat`` and ``ql`` are written where given (else scratch tensors of the call receive them).  Returns
+        ``{"QL": ..., "T": ...}``, the slab means [n x ktot] of QL and T (``Engine.slab_means``' rule, bit for bit);
+        ``means``: True, a dict of tensors to write into (pitched as in ``slab_means``), or False (no means: {}).
+        ``table_mode``: ``_abi.THERMO_TABLE_*`` (0: the library's choice).  One launch; ktot == 1 is refused
+        (SPC_ERR_UNSUPPORTED)."""
+        from . import thermo
+        shape = tuple(self._field4("thl", thl).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_thermo: empty field shape %s" % (shape,))
+        n_iter = thermo.DEFAULT_N_ITER if n_iter is None else int(n_iter)
+        if n_iter < 0:
+            raise ValueError("les_thermo: n_iter = %d < 0" % n_iter)
+        if self._es_tab is None:
+            self._es_tab = torch.from_numpy(thermo.saturation_table(self.dtype)).to(self.device)
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.LesThermoArgs()
+        a.n_les, a.itot, a.jtot, a.ktot, a.n_iter, a.table_mode = n, itot, jtot, ktot, n_iter, int(table_mode)
+        a.thl, a.qt = thl.data_ptr(), self._field4("qt", qt, shape).data_ptr()
+        a.presf, a.pitch_prof = ck.mat("presf", presf, n, ktot)
+        a.ex, _ = ck.mat("ex", ex, n, ktot, pitch=a.pitch_prof)
+        a.es_tab, a.n_tab, a.t_lo, a.inv_step = self._es_tab.data_ptr(), int(self._es_tab.numel()), thermo.T_LO, thermo.INV_STEP
+        keep = [torch.empty_like(thl) if t is None else self._field4(name, t, shape) for name, t in (("qsat", qsat), ("ql", ql))]
+        a.qsat, a.ql = keep[0].data_ptr(), keep[1].data_ptr()
+        if temp is not None:
+            a.temp = self._field4("temp", temp, shape).data_ptr()
+        res, a.pitch_mean = {}, ktot
+        if means is not False and means is not None:
+            given = means if isinstance(means, dict) else {}
+            unknown = [k for k in given if k not in ("QL", "T")]
+            if unknown:
+                raise ValueError("les_thermo: means of %s are not computed (QL and T are)" % unknown)
+            res["QL"], pitch = self._out(given.get("QL"), n, ktot)
+            res["T"], pitch_t = self._out(given.get("T"), n, ktot)
+            if n > 1 and pitch != pitch_t:
+                raise ValueError("les_thermo: means[T] has row pitch %d, means[QL] %d" % (pitch_t, pitch))
+            a.ql_mean, a.t_mean, a.pitch_mean = res["QL"].data_ptr(), res["T"].data_ptr(), pitch
+        fn = self.lib.spc_les_thermo_f32 if self.dtype == torch.float32 else self.lib.spc_les_thermo_f64
         self._call(fn, ctypes.byref(a), stream=stream)
         return res
 

@@ -656,7 +656,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     variability nudge: the library never copies them to the host.  The 3-D state is the truth and the profiles follow from
     it: U, V, THL, QT, QL are the slab means of the fields (K10, ``Engine.slab_means``: ONE launch for all of them per
     change of the fields), the cloud fraction is ``Engine.slab_cloud_fraction`` of the QL field.  ``Qsat`` is an attached
-    field, constant in time; the QL field is ``max(QT - Qsat, 0)``.  tests/slab_ref.py holds the NumPy twin of this class."""
+    field, constant in time; the QL field is ``max(QT - Qsat, 0)``.  tests/slab_ref.py holds the NumPy twin of this class.
+    After ``enable_thermo()`` Qsat and QL are instead the saturation adjustment of THL and QT at ``presf`` (K12,
+    ``Engine.les_thermo``: DESIGN.md 7.3), redone whenever THL or QT has changed, and ``p["T"]`` is K12's slab mean of the
+    cells' temperature; tests/les_thermo_ref.py holds the NumPy twin of that mode."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
@@ -670,6 +673,47 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.engine = engine                            # None: spcpl.get_engine() when first needed
         self.fields3d = {}
         self._means = None                              # host slab means of the fields as they are now, or None
+
+    # -- saturation adjustment (K12), opt-in -------------------------------------------------------------------------
+    thermo = False                                     # enable_thermo(): Qsat and QL follow THL, QT and presf
+    thermo_n_iter = None
+    _thermo_stale = True                               # THL or QT changed since K12 last ran
+    _thermo_prof = None                                # (host presf the upload was made from, device presf, device ex)
+    _thermo_means = None                               # host slab means {"QL", "T"} of K12's last launch
+
+    def enable_thermo(self, n_iter=None):
+        """from now on the Qsat and QL fields are K12's saturation adjustment of THL and QT (``n_iter`` Newton iterations,
+        default ``thermo.DEFAULT_N_ITER``), run again before their next use whenever THL or QT has changed, and ``p["T"]`` is
+        the slab mean of the adjusted temperature.  Without this call every path of the ensemble is unchanged."""
+        if self.nL == 1:
+            raise ValueError("the saturation adjustment (K12) does not take LES of one level")
+        if not all(callable(getattr(e, "les_thermo", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
+            raise ValueError("the engine has no les_thermo (K12)")
+        self.thermo, self.thermo_n_iter = True, n_iter
+        self._thermo_stale, self._means = True, None
+
+    def _ensure_thermo(self):
+        """K12 where THL or QT has changed since its last launch: the Qsat and QL fields, p["QL"] and p["T"]"""
+        import torch
+        from . import thermo
+        f = self.fields3d
+        if not self._thermo_stale or "THL" not in f or "QT" not in f:
+            return
+        eng = self._eng()
+        presf = numpy.asarray(self.p["presf"], dtype=numpy.float64)
+        if self._thermo_prof is None or not numpy.array_equal(self._thermo_prof[0], presf):
+            self._thermo_prof = (presf.copy(), self._upload(presf), self._upload(thermo.exner(presf)))
+        for k in ("Qsat", "QL"):
+            if k not in f:
+                f[k] = self._per_device(torch.empty_like, f["QT"])          # written whole by the launch
+        dev = eng.les_thermo(f["THL"], f["QT"], self._thermo_prof[1], self._thermo_prof[2], n_iter=self.thermo_n_iter,
+                             qsat=f["Qsat"], ql=f["QL"])
+        with eng.on_stream():
+            self._thermo_means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
+        self.p.update(self._thermo_means)
+        if self._means is not None:
+            self._means["QL"] = self._thermo_means["QL"]
+        self._thermo_stale = False
 
     @classmethod
     def for_gcm(cls, gcm, grid_indices, nL=160, seed=0, itot=8, jtot=8, engine=None):
@@ -722,7 +766,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
 
     def get_fields_batched(self, name):
         """the device tensor itself (no copy): what K6 and K10 work on"""
-        if name == "QL":
+        if name == "QL" or (self.thermo and name == "Qsat"):
             self._ensure_ql()
         return self.fields3d[name]
 
@@ -743,12 +787,15 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.itot, self.jtot = int(shape[1]), int(shape[2])
         self.fields3d[name] = values
         self._means = None
+        self._thermo_stale = True                       # (K12 writes Qsat and QL in place, not through here)
 
     def set_field_row(self, i, name, values):
         raise NotImplementedError("a DeviceLESEnsemble takes whole fields: set_fields_batched")
 
     def _ensure_ql(self):
         import torch
+        if self.thermo:
+            return self._ensure_thermo()
         f = self.fields3d
         if "QL" not in f:
             f["QL"] = self._per_device(lambda qt, qs: torch.clamp_min(qt - qs, 0.0), f["QT"], f["Qsat"])
@@ -756,19 +803,26 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
 
     def _slab_means(self):
         """host [n x nL] slab means of every field in MEAN_KEYS: one launch, cached until a field changes"""
+        if self.thermo:
+            self._ensure_thermo()
         if self._means is None:
             if "QT" in self.fields3d and "Qsat" in self.fields3d:
                 self._ensure_ql()
             eng = self._eng()
-            dev = eng.slab_means({k: self.fields3d[k] for k in self.MEAN_KEYS if k in self.fields3d})
+            own = self.thermo and self._thermo_means is not None      # the mean of QL came with K12's launch
+            dev = eng.slab_means({k: self.fields3d[k] for k in self.MEAN_KEYS if k in self.fields3d and not (own and k == "QL")})
             with eng.on_stream():
                 self._means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
+            if own:
+                self._means["QL"] = self._thermo_means["QL"]
             self.p.update(self._means)
         return self._means
 
     # -- batched protocol ----------------------------------------------------------------------------------------------
     @_timed
     def get_profiles_batched(self, keys, out):
+        if self.thermo:
+            self._ensure_thermo()                         # p["T"] and p["QL"] of the fields as they are now
         means = self._slab_means() if any(k in self.MEAN_KEYS and k in self.fields3d for k in keys) else {}
         for k in keys:
             numpy.copyto(out[k], means[k] if k in means else self.p[k])
@@ -790,12 +844,12 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         import torch
         eng, f = self._eng(), self.fields3d
         keys = [k for k in self.STEP_KEYS if k in f]
-        sat = "QT" in f and "Qsat" in f
+        sat = "QT" in f and "Qsat" in f and not self.thermo          # (thermo: QL is K12's, after the step)
         if not (self.fused_advance and self.nL > 1 and self.n > 0 and keys and (sat or any(k in self.tend for k in keys))):
             return False
         if max(int(part.shape[0]) for part in getattr(f[keys[0]], "parts", [f[keys[0]]])) < self.FUSED_MIN_LES:
             return False                                  # a launch of few LES is a latency chain: the torch path is faster
-        if ("QL" in f and not sat) or not all(callable(getattr(e, "les_advance", None)) for e in getattr(eng, "engines", [eng])):
+        if ("QL" in f and not sat and not self.thermo) or not all(callable(getattr(e, "les_advance", None)) for e in getattr(eng, "engines", [eng])):
             return False
         tend = {k: self._upload(self.tend[k]) for k in keys if k in self.tend}
         if sat and "QL" not in f:
@@ -805,6 +859,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         with eng.on_stream():
             self._means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
         self.p.update(self._means)
+        self._thermo_stale = True
         return True
 
     @_timed
@@ -823,7 +878,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                         inc = tend * dt                   # two separate ops: nothing contracts to an fma
                         return field.add_(inc[:, None, None, :])
                     self._per_device(step, f[key], self._upload(self.tend[key]))
-            if "QL" in f or ("QT" in f and "Qsat" in f):
+            self._thermo_stale = True
+            if not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
                 self._ensure_ql()
 
                 def saturate(ql, qt, qs):
@@ -834,7 +890,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             self._slab_means()                            # p[U, V, THL, QT, QL] = the slab means of the new fields
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
+        if self.thermo:
+            self._ensure_thermo()                         # one K12 launch: the Qsat and QL fields, p["QL"] and p["T"]
         p["QL_ice"] = numpy.minimum(p["QL_ice"], p["QL"])
-        p["T"] = p["THL"] * (p["presf"] / 1e5) ** (287.04 / 1004.) + 2.53e6 * p["QL"] / 1004.
+        if not (self.thermo and self._thermo_means is not None):
+            p["T"] = p["THL"] * (p["presf"] / 1e5) ** (287.04 / 1004.) + 2.53e6 * p["QL"] / 1004.
         p["Rain"] = p["Rain"] + 1e-6 * dt
         self.model_time = float(t)

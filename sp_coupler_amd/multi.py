@@ -230,6 +230,11 @@ class MultiDeviceEngine:
         dict of Sharded [n x ktot] slab means of the stepped fields out; one launch per device that holds rows"""
         return self._run("les_advance", fields, tend, dt, qsat=qsat, sat=sat, ql=ql, means=means, ql_mean=ql_mean, **kw)
 
+    def les_thermo(self, thl, qt, presf, ex, n_iter=None, qsat=None, ql=None, temp=None, means=True, **kw):
+        """K12 on every device's LES: Sharded fields and [n x ktot] profiles in (``qsat``, ``ql`` and ``temp`` written block by
+        block), dict of Sharded [n x ktot] slab means of QL and T out; one launch per device that holds rows"""
+        return self._run("les_thermo", thl, qt, presf, ex, n_iter=n_iter, qsat=qsat, ql=ql, temp=temp, means=means, **kw)
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

@@ -1,0 +1,354 @@
+"""K12 without a GPU: the NumPy oracle of tests/les_thermo_ref.py against properties of the rule, the chosen n_iter against 30
+iterations, the struct layout of spc_les_thermo_args and the host-side refusals of spc_les_thermo_*, and the closed loop of
+models.DeviceLESEnsemble's thermo mode on oracle-backed engines against its host twin."""
+import ctypes
+import inspect
+import os
+import subprocess
+
+import numpy
+import pytest
+
+import __graft_entry__ as ge
+from sp_coupler_amd import _abi, models, spcpl, sputils, thermo
+from tests import les_thermo_ref as ltr
+from tests.fake_engine import OracleEngine
+from tools import mutation_control as mc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DT = [numpy.float64, numpy.float32]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    ge.build_hip()
+    return _abi.load_library()
+
+
+@pytest.fixture(autouse=True)
+def _restore():
+    saved = numpy.random.get_state()
+    yield
+    spcpl.set_engine(None)
+    numpy.random.set_state(saved)
+
+
+# -- the table and the oracle ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DT)
+def test_table_is_the_stated_formula_rounded_once(dtype):
+    tab = thermo.saturation_table(dtype)
+    assert tab.dtype == dtype and tab.shape == (2000,) and thermo.N_TAB == 2000 and thermo.T_LO == 150.0 and thermo.INV_STEP * thermo.STEP == 1.0
+    for m in (0, 1, 616, 1999):
+        t = 150.0 + 0.2 * m
+        assert tab[m] == dtype(610.78 * numpy.exp(17.2694 * (t - 273.16) / (t - 35.86)))
+    assert (numpy.diff(tab.astype(numpy.float64)) > 0).all() and 610.78 < float(tab[616]) < 614.0      # 273.2 K, just above the 610.78 Pa of 273.16 K
+    import torch
+    assert numpy.array_equal(thermo.saturation_table({numpy.float64: torch.float64, numpy.float32: torch.float32}[dtype]), tab)
+    # the top of the table as the library forms it (t_lo + (n_tab - 1) / inv_step in double) is the stated t_lo + 0.2 (n_tab - 1)
+    assert ltr.table_top(dtype, 2000, 150.0, 5.0) == thermo.t_hi(dtype) == dtype(150.0 + 0.2 * 1999)
+    assert numpy.array_equal(thermo.exner(numpy.array([1e5, 5e4])), (numpy.array([1e5, 5e4]) / 1e5) ** (287.04 / 1004.))
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_an_unsaturated_cell_keeps_its_temperature(dtype):
+    tab = thermo.saturation_table(dtype)
+    T = dtype
+    thl, ex, p = numpy.array([285.0, 300.0], dtype), numpy.array([0.97, 1.0], dtype), numpy.array([9e4, 1e5], dtype)
+    qt = numpy.array([1e-3, -0.0], dtype)
+    for n_iter in (0, 1, 6):
+        qs, ql, temp = ltr.cells(thl, qt, p, ex, tab, n_iter)
+        Tl = thl * ex
+        assert (ql == 0).all() and not numpy.signbit(ql).any()
+        assert numpy.array_equal(temp, Tl) and numpy.array_equal(qs, ltr.sat(Tl, p, tab, want_dqs=False)[0]) and (qs > qt).all()
+    # by hand at Tl = 300 K, p = 1e5: knot 750 itself, w == 0
+    eps = T(sputils.rd) / T(sputils.rv)
+    assert qs[1] == (eps * tab[750]) / (T(1e5) - (T(1) - eps) * tab[750])
+    # a saturated cell is warmer than Tl, holds cloud water and sits on the saturation curve of its own temperature
+    qs, ql, temp = ltr.cells(numpy.array([290.0], dtype), numpy.array([2e-2], dtype), T(1e5), T(1.0), tab, 6)
+    assert ql[0] > 0 and temp[0] > 290 and qs[0] == T(2e-2) - ql[0] or abs(float(qs[0] + ql[0]) - 2e-2) < 1e-8
+    assert abs(float(ltr.sat(temp, T(1e5), tab, want_dqs=False)[0][0] - qs[0])) < (1e-9 if dtype == numpy.float64 else 1e-6)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_qs_does_not_decrease_across_any_knot(dtype):
+    """just below, on and just above every knot, and beyond both ends of the table -- as far as p - om * es stays positive
+    (den <= 0 is not guarded: above about 380 K at 5e4 Pa and 400 K at 1.05e5 Pa IEEE gives a negative qs)"""
+    tab = thermo.saturation_table(dtype)
+    knots = (150.0 + 0.2 * numpy.arange(2000)).astype(dtype)
+    Tk = numpy.sort(numpy.concatenate([numpy.nextafter(knots, dtype(0)), knots, numpy.nextafter(knots, dtype(1e4)),
+                                       numpy.array([100.0, 149.9, 549.9, 700.0], dtype)]))
+    for p in (5e4, 1.05e5):
+        qs, dqs = ltr.sat(Tk, dtype(p), tab)
+        top = int(numpy.argmax(qs < 0))                           # the first temperature with den < 0
+        assert 375 < Tk[top] < 405 and (qs[top:] < 0).all()
+        assert (numpy.diff(qs[:top].astype(numpy.float64)) >= 0).all() and (qs[:top] > 0).all() and (dqs[:top][Tk[:top] > 150] > 0).all()
+        assert len(numpy.unique(qs[:top])) > 3 * 1000             # (the knots and their neighbours are distinct cells of the check)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_table_ends_and_nan_follow_the_rule(dtype):
+    tab = thermo.saturation_table(dtype)
+    p = dtype(1e5)
+    q = lambda t: ltr.sat(numpy.array([t], dtype), p, tab, want_dqs=False)[0][0]          # noqa: E731
+    assert q(100.0) == q(150.0) == q(-numpy.inf) and q(700.0) == q(thermo.t_hi(dtype)) == q(numpy.inf)       # clamped
+    eps = dtype(sputils.rd) / dtype(sputils.rv)
+    assert q(100.0) == (eps * tab[0]) / (p - (dtype(1) - eps) * tab[0])
+    w = (thermo.t_hi(dtype) - dtype(150)) * dtype(5) - dtype(1998)                        # the last segment; 1 or just below it
+    assert 0.999 < w <= 1
+    top = tab[1998] + w * (tab[1999] - tab[1998])
+    assert q(700.0) == (eps * top) / (p - (dtype(1) - eps) * top)
+    assert numpy.isnan(q(numpy.nan))
+    for thl, qt in ((numpy.nan, 1e-2), (290.0, numpy.nan)):
+        qs, ql, temp = ltr.cells(numpy.array([thl], dtype), numpy.array([qt], dtype), p, dtype(1), tab, 3)
+        assert numpy.isnan(ql[0]) and numpy.isnan(temp[0]) and numpy.isnan(qs[0]) == numpy.isnan(thl)
+    # den <= 0 is not guarded: at the top of the table es > p / om, and IEEE gives a negative qs
+    assert q(549.8) < 0
+
+
+def _grid(nT, nP, nQ):
+    Tl = numpy.linspace(230.0, 310.0, nT)[:, None, None]
+    p = numpy.linspace(5e4, 1.05e5, nP)[None, :, None]
+    qt = numpy.linspace(0.0, 0.03, nQ)[None, None, :]
+    return numpy.broadcast_arrays(Tl, p, qt)
+
+
+def test_the_default_n_iter_is_the_smallest_within_1e_9_of_30_iterations():
+    """section 2 of the issue on Tl 230 ... 310 K, p 5e4 ... 1.05e5 Pa, qt 0 ... 0.03 (DESIGN.md 7.3 has the table of a denser
+    grid): the bound is the reference's significance bound for cloud water (splib/spcpl.py:661)"""
+    tab = thermo.saturation_table(numpy.float64)
+    Tl, p, qt = _grid(161, 12, 121)
+    one = numpy.float64(1.0)
+    ref = ltr.cells(Tl, qt, p, one, tab, 30)[1]
+    err = {n: float(numpy.abs(ltr.cells(Tl, qt, p, one, tab, n)[1] - ref).max()) for n in range(1, 7)}
+    print("max |ql(n_iter) - ql(30)|:", {n: "%.3e" % e for n, e in err.items()})
+    assert thermo.DEFAULT_N_ITER == 6
+    assert err[thermo.DEFAULT_N_ITER] <= 1e-9
+    assert all(err[n] > 1e-9 for n in range(1, thermo.DEFAULT_N_ITER))
+    assert (ref > 0).mean() > 0.3 and (ref == 0).mean() > 0.1
+
+
+def test_cells_the_iteration_does_not_settle_in():
+    """what the bound above does NOT say: where the first Newton step from Tl overshoots beyond qs == qt, the rule's branch
+    returns to Tl and the pair repeats for ever (qt at least about twice qs(Tl): no state an LES holds).  There every even
+    count gives the unadjusted cell and every odd count ql == 0, so 30 iterations are no better than 6"""
+    tab = thermo.saturation_table(numpy.float64)
+    Tl, p, qt = _grid(81, 6, 61)
+    one = numpy.float64(1.0)
+    q = {n: ltr.cells(Tl, qt, p, one, tab, n)[1] for n in (6, 7, 30, 31)}
+    cyc = numpy.abs(q[30] - q[31]) > 1e-9
+    assert 0.05 < cyc.mean() < 0.3
+    qs0 = ltr.sat(Tl, p, tab, want_dqs=False)[0]
+    assert (qt[cyc] > 1.9 * qs0[cyc]).all()
+    assert numpy.array_equal(q[30][cyc], (qt - qs0)[cyc]) and (q[31][cyc] == 0).all() and numpy.array_equal(q[6][cyc], q[30][cyc])
+    assert numpy.abs(q[6] - q[7])[~cyc].max() < 1e-9
+
+
+# -- ABI ---------------------------------------------------------------------------------------------------------------------
+def test_struct_layout_of_the_thermo_arguments(tmp_path):
+    """sizeof / offsetof as gcc sees include/spc.h == the ctypes mirror"""
+    cls, cname = _abi.LesThermoArgs, "spc_les_thermo_args"
+    fields = ["n_les", "itot", "jtot", "ktot", "n_iter", "thl", "qt", "presf", "ex", "pitch_prof", "es_tab", "n_tab", "table_mode",
+              "t_lo", "inv_step", "qsat", "ql", "temp", "ql_mean", "t_mean", "pitch_mean"]
+    assert [f[0] for f in cls._fields_] == fields
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "spc.h"', 'int main(void){',
+             'printf("%%zu\\n", sizeof(%s));' % cname, 'printf("%d\\n", SPC_ABI_VERSION);']
+    want = [ctypes.sizeof(cls), 4]
+    for f in fields:
+        lines.append('printf("%%zu\\n", offsetof(%s, %s));' % (cname, f))
+        want.append(getattr(cls, f).offset)
+    lines.append('return 0;}')
+    src = tmp_path / "probe.c"
+    src.write_text("\n".join(lines))
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "probe")], check=True)
+    got = [int(x) for x in subprocess.run([str(tmp_path / "probe")], check=True, capture_output=True, text=True).stdout.split()]
+    assert got == want
+
+
+def _args(n=4, itot=8, jtot=8, ktot=20, pitch_prof=20, pitch_mean=20, n_tab=2000, n_iter=6, table_mode=0, inv_step=5.0, **ptr):
+    a = _abi.LesThermoArgs()
+    a.n_les, a.itot, a.jtot, a.ktot, a.n_iter = n, itot, jtot, ktot, n_iter
+    a.pitch_prof, a.pitch_mean, a.n_tab, a.table_mode, a.t_lo, a.inv_step = pitch_prof, pitch_mean, n_tab, table_mode, 150.0, inv_step
+    names = ("thl", "qt", "presf", "ex", "es_tab", "qsat", "ql", "temp", "ql_mean", "t_mean")
+    for i, name in enumerate(names):                             # distinct, 16-byte aligned, never dereferenced
+        setattr(a, name, ptr.get(name, 4096 * (i + 1)))
+    return a
+
+
+@pytest.mark.parametrize("sfx", ["f64", "f32"])
+def test_thermo_entry_points_validate_on_the_host(lib, sfx):
+    """every refusal is made before any launch: none of these calls needs a device"""
+    E, U = _abi.SPC_ERR_INVALID_ARGUMENT, _abi.SPC_ERR_UNSUPPORTED
+    fn = getattr(lib, "spc_les_thermo_" + sfx)
+    assert lib.spc_abi_version() == 4 == _abi.ABI_VERSION
+
+    def call(**kw):
+        return fn(ctypes.byref(_args(**kw)), None), lib.spc_last_error()
+    assert fn(None, None) == E and b"NULL" in lib.spc_last_error()
+    for name in ("thl", "qt", "presf", "ex", "es_tab", "qsat", "ql"):
+        assert call(**{name: None}) == (E, b"required pointer " + name.encode() + b" is NULL")
+    assert call(n=-1)[0] == E
+    for bad in (dict(itot=0), dict(jtot=-3), dict(ktot=0)):
+        rc, text = call(**bad)
+        assert rc == E and b">= 1" in text
+    rc, text = call(itot=65536, jtot=32768)
+    assert rc == U and b"2^31 - 1 points per plane" in text
+    for bad in (dict(pitch_prof=19), dict(pitch_mean=19)):
+        rc, text = call(**bad)
+        assert rc == E and b"pitch" in text and b"smaller than ktot" in text
+    for bad in (1, 0, -5):
+        rc, text = call(n_tab=bad)
+        assert rc == E and b"n_tab" in text
+    rc, text = call(n_iter=-1)
+    assert rc == E and b"n_iter" in text
+    for bad in (-1, 3):
+        rc, text = call(table_mode=bad)
+        assert rc == E and b"table_mode" in text
+    for bad in (0.0, -5.0, float("nan")):
+        assert call(inv_step=bad)[0] == E
+    ins = {"thl": 4096, "qt": 8192, "presf": 12288, "ex": 16384, "es_tab": 20480}
+    for out in ("qsat", "ql", "temp", "ql_mean", "t_mean"):
+        for name, p in ins.items():
+            rc, text = call(**{out: p})
+            assert rc == E and b"an output is also an input" in text, (out, name)
+    rc, text = call(ql=4096 * 6)                                  # qsat
+    assert rc == E and b"two outputs are the same array" in text
+    rc, text = call(t_mean=4096 * 9)
+    assert rc == E and b"two outputs are the same array" in text
+    rc, text = call(thl=4100 if sfx == "f64" else 4098)
+    assert rc == E and b"not aligned" in text
+    rc, text = call(n=1 << 40, ktot=3, pitch_prof=3, pitch_mean=3)
+    assert rc == U and b"too many workgroups" in text
+    rc, text = call(ktot=1, pitch_prof=1, pitch_mean=1)
+    assert rc == U and b"ktot == 1" in text
+    rc, text = call(table_mode=_abi.THERMO_TABLE_LDS, n_tab=1 << 20)
+    assert rc == U and b"LDS" in text                             # a table beyond the LDS of a CU, asked to be staged there
+    assert call(n=0, thl=None, qsat=None)[0] == 0                 # an empty ensemble is a no-op
+    assert call(n=0)[0] == 0
+
+
+def test_engines_have_the_method_and_the_other_fake_engines_do_not():
+    from sp_coupler_amd.engine import Engine
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    sig = inspect.signature(Engine.les_thermo)
+    assert list(sig.parameters)[:11] == ["self", "thl", "qt", "presf", "ex", "n_iter", "qsat", "ql", "temp", "means", "stream"]
+    assert sig.parameters["n_iter"].default is None and sig.parameters["means"].default is True
+    assert callable(MultiDeviceEngine.les_thermo) and not hasattr(OracleEngine, "les_thermo")
+    assert models.DeviceLESEnsemble.thermo is False
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_inputs_of_the_gpu_bodies_reach_what_they_name(dtype):
+    """the special field holds every kind of cell the issue lists, and the tables of the test's own reach the exact
+    coincidences (qt == qs on a knot after one Newton step; dq == -0.0) in the oracle"""
+    thl, qt, presf, ex = ltr.case((3, 3, 5, 7), dtype, seed=1, special=True)
+    tab = thermo.saturation_table(dtype)
+    r = ltr.les_thermo(thl, qt, presf, ex)
+    Tl = thl * ex[:, None, None, :]
+    assert (presf[:, 0] == 1e5).all() and (ex[:, 0] == 1).all()
+    assert (r["ql"][:, 0, 0, :-1] == 0).all() and (qt[:, 0, 0, :-1] == ltr.sat(Tl, presf[:, None, None, :], tab, want_dqs=False)[0][:, 0, 0, :-1]).all()
+    assert (Tl[:, 0, 1] < 150).all() and (Tl[:, 0, 2] > thermo.t_hi(dtype)).all()
+    x = (thl[:, 0, 3, 0] - dtype(150)) * dtype(5)
+    assert (x == numpy.floor(x)).sum() >= 2                       # Tl on knots (level 0: ex == 1)
+    assert numpy.isnan(r["ql"][:, 1, 0]).all() and numpy.isnan(r["ql"][:, 1, 1]).all() and numpy.isnan(r["qsat"][:, 1, 0]).all()
+    assert numpy.signbit(qt[:, 1, 2]).all() and (r["ql"][:, 1, 2] == 0).all() and not numpy.signbit(r["ql"][:, 1, 2]).any()
+    rest = r["ql"][:, 2]
+    assert (rest > 0).any() and (rest == 0).any()
+    # the knot case: after ONE step Tk is knot 2 itself and qs == qt there, so the second iteration returns to Tl
+    thl, qt, presf, ex, tab = ltr.knot_case(dtype)
+    r1, r2 = (ltr.les_thermo(thl, qt, presf, ex, n, tab, ltr.TAB_T_LO, ltr.TAB_INV_STEP) for n in (1, 2))
+    assert (r1["qsat"][..., 0] == qt[..., 0]).all() and (r1["ql"][..., 0] == 0).all() and (r1["temp"][..., 0] == thl[..., 0]).all()
+    assert (r2["qsat"][..., 0] < qt[..., 0]).all() and (r2["ql"][..., 0] > 0).all()
+    # the zero table: dq == -0.0 is reached and gives +0.0
+    thl, qt, presf, ex, tab = ltr.zero_case(dtype)
+    r = ltr.les_thermo(thl, qt, presf, ex, 2, tab, ltr.TAB_T_LO, ltr.TAB_INV_STEP)
+    assert (r["qsat"][..., :2] == 0).all() and not numpy.signbit(r["qsat"][..., :2]).any()
+    with numpy.errstate(invalid="ignore"):
+        dq = qt - r["qsat"]
+    assert numpy.signbit(dq[0, 0, 0, :2]).all() and (dq[0, 0, 0, :2] == 0).all()
+    assert (r["ql"][0, 0, 0] == 0).all() and not numpy.signbit(r["ql"][0, 0, 0]).any() and (r["ql"][0, 0, 1, :2] == dtype(2e-3)).all()
+
+
+# -- the ensemble ------------------------------------------------------------------------------------------------------------
+def _counted(engine, calls):
+    inner = engine.les_thermo
+
+    def les_thermo(*a, **kw):
+        calls.append(int(a[0].shape[0]))
+        return inner(*a, **kw)
+    engine.les_thermo = les_thermo
+    return engine
+
+
+def test_closed_loop_on_one_engine_equals_the_host_twin():
+    calls = []
+    ltr.check_closed_loop(OracleEngine(), [_counted(ltr.ThermoOracleEngine(), calls)], 4)
+    assert len(calls) >= 5 and set(calls) == {4}                  # (spin-up, three steps, the nudges in between)
+
+
+def test_closed_loop_fused_step_and_row_blocks_with_an_empty_device(monkeypatch):
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    from sp_coupler_amd.transfer import Sharded
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)      # K11 steps the fields, K12 follows
+    calls, steps = [], []
+    engines = [_counted(ltr.ThermoOracleEngine(), calls) for _ in range(3)]
+    inner = engines[0].les_advance
+    engines[0].les_advance = lambda *a, **kw: (steps.append(kw.get("sat")), inner(*a, **kw))[1]
+    multi = MultiDeviceEngine(engines, min_cols_per_device=1)
+    one = _counted(ltr.ThermoOracleEngine(), [])
+    host = ltr.check_closed_loop(OracleEngine(), [one, multi], 2)
+    assert calls and set(calls) == {1}                            # blocks 1 + 1 + 0: the empty device is skipped
+    assert steps and set(steps) == {None}                         # K11 ran without its own saturation
+    spcpl.set_engine(multi)
+    dev = ltr.loop(multi, models.DeviceLESEnsemble, 2)[0]
+    assert all(isinstance(dev.fields3d[k], Sharded) for k in ("THL", "QT", "Qsat", "QL"))
+    assert host[0].fields3d["Qsat"].shape == (2, 4, 4, 24)
+
+
+def test_thermo_is_opt_in_and_marks_its_fields_stale():
+    eng = ltr.ThermoOracleEngine()
+    spcpl.set_engine(eng)
+    gcm = models.BatchedSyntheticGCM(6, 19, 3)
+    one = models.DeviceLESEnsemble.for_gcm(gcm, [1, 2], nL=1, seed=4, itot=3, jtot=3, engine=eng)
+    with pytest.raises(ValueError):
+        one.enable_thermo()
+    with pytest.raises(ValueError):
+        models.DeviceLESEnsemble.for_gcm(gcm, [1, 2], nL=8, seed=4, itot=3, jtot=3, engine=OracleEngine()).enable_thermo()
+    calls = []
+    ens = models.DeviceLESEnsemble.for_gcm(gcm, [1, 2], nL=8, seed=4, itot=3, jtot=3, engine=_counted(eng, calls))
+    rng = numpy.random.default_rng(2)
+    thl = 290.0 + rng.standard_normal((2, 3, 3, 8))
+    qt = 8e-3 + 4e-3 * rng.random((2, 3, 3, 8))
+    ens.attach_fields({"THL": thl, "QT": qt})
+    ens.enable_thermo(n_iter=4)
+    presf = numpy.asarray(ens.p["presf"], dtype=numpy.float64)
+    want = ltr.les_thermo(thl, qt, presf, thermo.exner(presf), 4)
+    assert not calls
+    assert numpy.array_equal(ens.get_fields_batched("Qsat").numpy(), want["qsat"]) and len(calls) == 1
+    assert numpy.array_equal(ens.get_fields_batched("QL").numpy(), want["ql"]) and len(calls) == 1           # not stale: no launch
+    assert numpy.array_equal(ens.p["T"], want["t_mean"]) and numpy.array_equal(ens._slab_means()["QL"], want["ql_mean"])
+    up = ens._thermo_prof
+    ens.set_fields_batched("THL", thl + 1.0)                      # THL changed: the next use of QL runs K12 again
+    out = numpy.empty((2, 19))
+    ens.get_cloudfraction_batched(numpy.tile(numpy.arange(19, dtype=numpy.int32), (2, 1)), out)
+    assert len(calls) == 2 and ens._thermo_prof is up             # presf unchanged: not uploaded again
+    want = ltr.les_thermo(thl + 1.0, qt, presf, thermo.exner(presf), 4)
+    assert numpy.array_equal(ens.get_fields_batched("Qsat").numpy(), want["qsat"]) and (want["qsat"] != 0).all()
+    ens.p["presf"] = presf * 0.99                                 # presf changed: uploaded again with its Exner factor
+    ens.set_fields_batched("QT", qt)
+    prof = {"T": numpy.empty((2, 8))}
+    ens.get_profiles_batched(("T",), prof)
+    want = ltr.les_thermo(thl + 1.0, qt, presf * 0.99, thermo.exner(presf * 0.99), 4)
+    assert len(calls) == 3 and ens._thermo_prof is not up and numpy.array_equal(prof["T"], want["t_mean"])
+
+
+# -- the mutant table of K12 -------------------------------------------------------------------------------------------------
+def test_thermo_mutants_apply_to_the_tree_and_name_their_guards():
+    assert sorted(mc.MUTANTS) == list(range(1, 36)) and len(mc.ADVANCE_MUTANTS) >= 6          # the other tables are as they were
+    assert sorted(mc.THERMO_MUTANTS) == list(range(1, 9))
+    for n, (what, guard, edits) in mc.THERMO_MUTANTS.items():
+        assert what and callable(guard) and all(e[0] == mc.THERMO for e in edits), n
+        assert guard.__name__.split(".", 1)[1] in ltr.BODIES and hasattr(ltr, "check_" + guard.__name__.split(".", 1)[1]), guard.__name__
+        files = mc.patched(n, table=mc.THERMO_MUTANTS)
+        for name, text in files.items():
+            with open(os.path.join(mc.CSRC, name)) as f:
+                assert text != f.read(), (n, name)

@@ -11,10 +11,13 @@ Mutants 28 ... are slips of K10 (spc_slab.hpp); their guards are the bodies of t
 tests/test_slab_gpu.py run on the shipped library.
 ADVANCE_MUTANTS is the table of K11 (spc_advance.hpp), numbered on its own and chosen with --advance; its guards are the
 bodies of tests/les_advance_ref.py, which tests/test_les_advance_gpu.py runs on the shipped library.
+THERMO_MUTANTS is the table of K12 (spc_thermo.hpp), chosen with --thermo; its guards are the bodies of
+tests/les_thermo_ref.py, which tests/test_les_thermo_gpu.py runs on the shipped library.
 usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py > profiles/mutation_control.log
        python tools/mutation_control.py --only 28 29 30 31 32 33 34 35 > profiles/mutation_control_slab.log
-       python tools/mutation_control.py --advance --build && python tools/mutation_control.py --advance > profiles/mutation_control_advance.log"""
+       python tools/mutation_control.py --advance --build && python tools/mutation_control.py --advance > profiles/mutation_control_advance.log
+       python tools/mutation_control.py --thermo --build && python tools/mutation_control.py --thermo > profiles/mutation_control_thermo.log"""
 import argparse
 import os
 import shutil
@@ -32,6 +35,7 @@ OUT = os.path.join(ROOT, "build", "mutants")
 K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp", "spc_vnudge2.hpp", "spc_sputils.hpp"
 SLAB = "spc_slab.hpp"
 ADVANCE = "spc_advance.hpp"
+THERMO = "spc_thermo.hpp"
 A9 = "(col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG"     # the neighbouring column of the slab (mutant 9)
 
 def slab_edges(name):
@@ -180,6 +184,42 @@ ADVANCE_MUTANTS = {
 }
 
 
+def thermo_body(name):
+    """guard of a K12 mutant: the body ``name`` of tests/les_thermo_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_thermo_ref as ltr
+        failed = []
+        for dtype in ltr.DTYPES:
+            failed += ltr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_thermo_ref." + name
+    return guard
+
+
+# K12 (spc_thermo.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 1 keeps the index inside the table).
+THERMO_MUTANTS = {
+    1: ("K12 lookup: the knot index off by one (the segment above the one that holds Tc)", thermo_body("parity"),
+        [(THERMO, "const int m = x >= (T)0 ? min((int)x, P.n_tab - 2) : 0;", "const int m = x >= (T)0 ? min((int)x + 1, P.n_tab - 2) : 0;")]),
+    2: ("K12 lookup: the weight w taken from the unclamped Tk (extrapolation beyond the ends of the table)", thermo_body("special"),
+        [(THERMO, "const T w = x - (T)m;", "const T w = (Tk - P.t_lo) * P.inv_step - (T)m;")]),
+    3: ("K12 qs: om = 1 - eps replaced by eps in the denominator", thermo_body("parity"),
+        [(THERMO, "const T den = p - ThermoK<T>::om * e;", "const T den = p - ThermoK<T>::eps * e;")]),
+    4: ("K12 Newton: the branch taken with qt >= qs instead of qt > qs", thermo_body("table"),
+        [(THERMO, "Tk = qt > s ? Tk - step : Tl;", "Tk = qt >= s ? Tk - step : Tl;")]),
+    5: ("K12: the final sat call dropped, qs is the one of the last iteration's Tk", thermo_body("parity"),
+        [(THERMO, "T Tk = Tl, dqs;", "T Tk = Tl, dqs, last = (T)0;"),
+         (THERMO, "const T s = th_sat<T, true>(P, es, Tk, p, epsp, dqs);", "const T s = last = th_sat<T, true>(P, es, Tk, p, epsp, dqs);"),
+         (THERMO, "qs = th_sat<T, false>(P, es, Tk, p, epsp, dqs);", "qs = P.n_iter > 0 ? last : th_sat<T, false>(P, es, Tk, p, epsp, dqs);")]),
+    6: ("K12 q rule: dq >= 0 keeps dq, so dq == -0.0 gives -0.0", thermo_body("table"),
+        [(THERMO, "q = dq > (T)0 ? dq : (dq != dq ? dq : (T)0);", "q = dq >= (T)0 ? dq : (dq != dq ? dq : (T)0);")]),
+    7: ("K12 means: the sums divided by itot * jtot + 1", thermo_body("parity"),
+        [(THERMO, "const T cnt = (T)nij;", "const T cnt = (T)(nij + 1);")]),
+    8: ("K12 dqs: the factor inv_step (5 entries per kelvin) missing from the slope", thermo_body("parity"),
+        [(THERMO, "if (DQS) dqs = (epsp * (d * P.inv_step)) / (den * den);", "if (DQS) dqs = (epsp * d) / (den * den);")]),
+}
+
+
 def patched(n, src=CSRC, table=None):
     """{file: text} of the files mutant n (of ``table``, default MUTANTS) changes, its edits applied to the sources under
     `src`; ValueError when an edit's old text does not occur exactly the expected number of times (the tree has drifted from
@@ -199,11 +239,11 @@ def patched(n, src=CSRC, table=None):
 
 
 def lib_of(n, table=None):
-    return os.path.join(OUT, "libspc_%smutant%d.so" % ("advance_" if table is ADVANCE_MUTANTS else "", n))
+    return os.path.join(OUT, "libspc_%smutant%d.so" % ("advance_" if table is ADVANCE_MUTANTS else "thermo_" if table is THERMO_MUTANTS else "", n))
 
 
 def build_one(n, table=None):
-    src = os.path.join(OUT, "src%s%d" % ("adv" if table is ADVANCE_MUTANTS else "", n))
+    src = os.path.join(OUT, "src%s%d" % ("adv" if table is ADVANCE_MUTANTS else "thermo" if table is THERMO_MUTANTS else "", n))
     shutil.rmtree(src, ignore_errors=True)
     shutil.copytree(CSRC, src)
     for name, text in patched(n, table=table).items():
@@ -256,25 +296,27 @@ def run(lib_path):
     return failed
 
 
-def main_advance(only=None):
-    """the control of ADVANCE_MUTANTS: the bodies of tests/les_advance_ref.py on the shipped library, then on every mutant"""
+def main_advance(only=None, table=None, kernel="K11", ref="les_advance"):
+    """the control of ADVANCE_MUTANTS (or of THERMO_MUTANTS): the bodies of tests/les_advance_ref.py (tests/les_thermo_ref.py)
+    on the shipped library, then on every mutant"""
     import torch
-    print("mutation control of tests/les_advance_ref.py (tests/test_les_advance_gpu.py) on %s" % torch.cuda.get_device_name(0))
-    chosen = sorted(n for n in ADVANCE_MUTANTS if only is None or n in only)
-    clean = run_guard(ADVANCE_MUTANTS[chosen[0]][1], None)[1]
-    print("shipped library: the bodies of tests/les_advance_ref.py on both engines, failed: %s" % (clean or "none"), flush=True)
+    table = ADVANCE_MUTANTS if table is None else table
+    print("mutation control of tests/%s_ref.py (tests/test_%s_gpu.py) on %s" % (ref, ref, torch.cuda.get_device_name(0)))
+    chosen = sorted(n for n in table if only is None or n in only)
+    clean = run_guard(table[chosen[0]][1], None)[1]
+    print("shipped library: the bodies of tests/%s_ref.py on both engines, failed: %s" % (ref, clean or "none"), flush=True)
     bad = int(bool(clean))
     for n in chosen:
-        what, guard, _ = ADVANCE_MUTANTS[n]
-        path = lib_of(n, ADVANCE_MUTANTS)
+        what, guard, _ = table[n]
+        path = lib_of(n, table)
         if not os.path.exists(path):
-            print("K11 mutant %2d: NOT BUILT (%s)" % (n, path))
+            print("%s mutant %2d: NOT BUILT (%s)" % (kernel, n, path))
             bad += 1
             continue
         ok, failed = run_guard(guard, path)
         bad += not ok
-        print("K11 mutant %2d: %s\n           guarded by %s: %s; all failing: %s"
-              % (n, what, guard.__name__, "DETECTED" if ok else "SURVIVED", failed or "none"), flush=True)
+        print("%s mutant %2d: %s\n           guarded by %s: %s; all failing: %s"
+              % (kernel, n, what, guard.__name__, "DETECTED" if ok else "SURVIVED", failed or "none"), flush=True)
     print("result: %s" % ("every mutant detected, shipped library clean" if not bad else "%d problem(s)" % bad))
     return 1 if bad else 0
 
@@ -320,11 +362,15 @@ if __name__ == "__main__":
     ap.add_argument("--only", nargs="+", type=int, metavar="n", help="run the control for the mutants n ... only")
     ap.add_argument("-j", type=int, default=4, help="parallel compiles for --build (at most 16)")
     ap.add_argument("--advance", action="store_true", help="the table of K11 (ADVANCE_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--thermo", action="store_true", help="the table of K12 (THERMO_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
-    table = ADVANCE_MUTANTS if args.advance else MUTANTS
+    table = ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else MUTANTS
     if args.build is not None:
         unknown = sorted(set(args.build) - set(table))
         if unknown:
             ap.error("no mutant %s" % unknown)
         sys.exit(build(args.build or sorted(table), args.j, table))
-    sys.exit((main_advance if args.advance else main)(set(args.only) if args.only else None))
+    only = set(args.only) if args.only else None
+    if args.thermo:
+        sys.exit(main_advance(only, THERMO_MUTANTS, "K12", "les_thermo"))
+    sys.exit((main_advance if args.advance else main)(only))
