@@ -288,7 +288,10 @@ int spc_rms_f32(int64_t n_rows, int64_t n, int64_t pitch, const void *a, void *o
  * ring_start[r] ... ring_start[r+1]-1, CLOSED (last vertex == first).  Rings are grouped by polygon: ring_poly is
  * non-decreasing, and every polygon's first ring is its shell (SPC_RING_SHELL, or SPC_RING_RECTANGLE for an axis-aligned
  * rectangle without holes: strictly-inside rule of GEOS's RectangleContains), its holes follow (SPC_RING_HOLE).
- * out[k * n_points + i] = code of p | code of q << 8 in polygon k, codes SPC_LOC_*.  A layout that breaks these rules gives
+ * out[k * n_points + i] = code of p | code of q << 8 in polygon k, codes SPC_LOC_*.  A point whose lon or lat is NaN or
+ * +-inf is SPC_LOC_EXTERIOR to every polygon, as p and as q, under the ray rule and under the rectangle rule alike (no
+ * arithmetic is done on it).  A polygon id that comes back after another polygon's rings starts that polygon anew, shell
+ * first, and its codes replace the ones written for the id before.  Any other layout that breaks these rules gives
  * undefined codes, never an access outside the arrays.  All arrays are device memory.
  * spc_haversine_f64: out[i] = great-circle distance in km from (lon[i], lat[i]) to (lon0, lat0), splib/haversine.py:12-36
  * operation by operation (R = 6371 km).                                                                              */

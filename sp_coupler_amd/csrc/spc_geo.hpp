@@ -8,6 +8,8 @@
 // where Shewchuk's error bound proves its sign, else by an exact expansion (TwoDiff / fma-TwoProduct / Grow-Expansion).
 // The bound assumes the -ffp-contract=off of the build: no FMA may change a rounding of the filter.
 //
+// A point whose lon or lat is NaN or +-inf is EXTERIOR to every polygon, as p and as q (include/spc.h).
+//
 // One lane per grid point tests both of its images p = (lon, lat) and q = ((lon - 180) % 360 - 180, lat) against every
 // edge.  The ring vertices are staged through LDS in tiles; every lane of a workgroup reads the same vertex at the same
 // time (broadcast reads, no bank conflicts).
@@ -164,7 +166,11 @@ __global__ __launch_bounds__(GEO_THREADS) void k_point_in_polygon(const GeoP p)
     __shared__ double sx[GEO_TILE + 1], sy[GEO_TILE + 1];
     const int64_t i = (int64_t)blockIdx.x * GEO_THREADS + threadIdx.x;
     const bool live = i < p.n_points;
-    const double px = live ? p.lon[i] : 0.0, py = live ? p.lat[i] : 0.0;
+    const double lon = live ? p.lon[i] : 0.0, lat = live ? p.lat[i] : 0.0;
+    // a point with a NaN or infinite coordinate is exterior to every polygon, as p and as q (the image of +-inf is NaN):
+    // decided here, before any arithmetic -- a NaN determinant would read as "collinear", that is as BOUNDARY
+    const bool finite = isfinite(lon) && isfinite(lat);
+    const double px = finite ? lon : 0.0, py = finite ? lat : 0.0;
     const double qx = geo_image_lon(px);
     int code_p = GEO_EXTERIOR, code_q = GEO_EXTERIOR;
     int cur_poly = -1;
@@ -176,7 +182,7 @@ __global__ __launch_bounds__(GEO_THREADS) void k_point_in_polygon(const GeoP p)
         const int role = p.ring_role[r], poly = p.ring_poly[r];
         if (poly != cur_poly) {
             if (live && cur_poly >= 0 && cur_poly < p.n_polys)
-                p.out[(int64_t)cur_poly * p.n_points + i] = (uint16_t)(code_p | (code_q << 8));
+                p.out[(int64_t)cur_poly * p.n_points + i] = finite ? (uint16_t)(code_p | (code_q << 8)) : (uint16_t)GEO_EXTERIOR;
             cur_poly = poly;
             code_p = code_q = GEO_EXTERIOR;
         }
@@ -217,7 +223,7 @@ __global__ __launch_bounds__(GEO_THREADS) void k_point_in_polygon(const GeoP p)
         code_q = geo_fold(code_q, rq, role);
     }
     if (live && cur_poly >= 0 && cur_poly < p.n_polys)
-        p.out[(int64_t)cur_poly * p.n_points + i] = (uint16_t)(code_p | (code_q << 8));
+        p.out[(int64_t)cur_poly * p.n_points + i] = finite ? (uint16_t)(code_p | (code_q << 8)) : (uint16_t)GEO_EXTERIOR;
 }
 
 // splib/haversine.py:24-31 in its order: radians(x) = x * (pi / 180), dlat = lat2 - lat1, dlng = lng2 - lng1,

@@ -4,11 +4,13 @@ sharing code with the kernel or with sp_coupler_amd.geometry:
 * ``locations``: the location codes of the C ABI (include/spc.h spc_pip_args: [n_polys x n x 2], 0 exterior, 1 boundary,
   2 interior; [..., 0] the point, [..., 1] its image ((lon - 180) % 360 - 180, lat)) in NumPy, one edge at a time over the
   points whose latitude the edge spans; orientations from the GEOS-form double determinant where a generous error bound
-  proves its sign, else from ``fractions.Fraction``;
+  proves its sign, else from ``fractions.Fraction``; a point whose lon or lat is NaN or +-inf is exterior (0) to every
+  polygon, as p and as q, decided before any arithmetic touches it;
 * ``brute_locations``: the same codes point by point, every orientation in ``Fraction`` (small inputs only);
 * ``reference_mask_indices``: splib/sputils.py:50-73 restated loop for loop, with a ``contains`` predicate passed in;
 * ``haversine``: splib/haversine.py:24-31 in NumPy.
 """
+import math
 from fractions import Fraction
 
 import numpy
@@ -86,6 +88,12 @@ def locations(lon, lat, vx, vy, ring_start, ring_role, ring_poly, n_polys):
     lon, lat = numpy.asarray(lon, dtype=numpy.float64), numpy.asarray(lat, dtype=numpy.float64)
     n = len(lon)
     out = numpy.zeros((n_polys, n, 2), dtype=numpy.uint8)
+    finite = numpy.isfinite(lon) & numpy.isfinite(lat)
+    if not finite.all():                 # the non-finite points stay exterior; only the finite ones reach the arithmetic
+        keep = numpy.flatnonzero(finite)
+        if len(keep):
+            out[:, keep, :] = locations(lon[keep], lat[keep], vx, vy, ring_start, ring_role, ring_poly, n_polys)
+        return out
     order = numpy.argsort(lat, kind="stable")
     pys = lat[order]
     for img, px in enumerate((lon, image_lon(lon))):
@@ -107,6 +115,8 @@ def brute_locations(lon, lat, vx, vy, ring_start, ring_role, ring_poly, n_polys)
     F = Fraction
     out = numpy.zeros((n_polys, len(lon), 2), dtype=numpy.uint8)
     for i in range(len(lon)):
+        if not (math.isfinite(lon[i]) and math.isfinite(lat[i])):
+            continue                                                   # NaN / +-inf: exterior to everything
         for img, x in enumerate((float(lon[i]), (float(lon[i]) - 180) % 360 - 180)):
             y = float(lat[i])
             code = EXT
@@ -208,7 +218,6 @@ def naive_sign(ax, ay, bx, by, cx, cy):
 def naive_flips(a, b, count=64):
     """points within a few ulps of the segment a-b (strictly between its end latitudes) where the naive determinant has
     the WRONG sign (both non-zero) or calls the point collinear when it is not"""
-    import math
     pts = []
     for t in numpy.linspace(0.05, 0.95, count):
         cx, cy = float(a[0] + t * (b[0] - a[0])), float(a[1] + t * (b[1] - a[1]))

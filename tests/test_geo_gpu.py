@@ -2,13 +2,14 @@
 
 Location codes are compared bit for bit with the exact oracle of tests/geo_ref.py (itself checked against a pure-Fraction
 brute force on the CPU, test_geometry_cpu.py); get_mask_indices element for element, in order, with the reference loop
-restated over that oracle."""
+restated over that oracle.  The bodies that tools/mutation_control.py --geo also runs on its mutant libraries live in
+tests/geo_edges.py."""
 import numpy
 import pytest
 import torch
 
 from sp_coupler_amd import geometry
-from tests import geo_ref
+from tests import geo_edges, geo_ref
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
@@ -29,54 +30,47 @@ def su(request):
     spcpl.set_engine(None)
 
 
-def _codes(eng, lon, lat, lay):
-    return eng.point_in_polygon(torch.from_numpy(numpy.ascontiguousarray(lon)).cuda(), torch.from_numpy(numpy.ascontiguousarray(lat)).cuda(),
-                                *lay).cpu().numpy()
-
-
 @pytest.mark.parametrize("case", geo_ref.adversarial(), ids=lambda c: c[0])
 def test_adversarial_codes_equal_exact_oracle(eng, case):
-    name, lon, lat, lay = case
-    got = _codes(eng, lon, lat, lay)
-    assert got.dtype == numpy.uint8 and got.shape == (lay[5], len(lon), 2)
-    want = geo_ref.locations(lon, lat, *lay)
-    assert numpy.array_equal(got, want), "%s: %d of %d codes differ" % (name, (got != want).sum(), want.size)
+    geo_edges.check_adversarial(eng, case[0])
 
 
 def test_exact_path_decides_where_the_naive_determinant_is_wrong(eng):
-    a, b = (0.5, 0.5), (17.3, 24.25)
-    pts = numpy.array(geo_ref.naive_flips(a, b))
-    naive = numpy.array([geo_ref.naive_sign(*a, *b, x, y) for x, y in pts])
-    exact = numpy.array([geo_ref._orient_fraction(*a, *b, x, y) for x, y in pts])
-    assert (naive == -exact).any() and (naive != exact).all()
-    lay = geo_ref.layout([geo_ref.rings_of([a, b, (-20.0, 30.0), a])])
-    got = _codes(eng, pts[:, 0], pts[:, 1], lay)[0, :, 0]
-    # the point is inside the triangle exactly when it is left of a -> b (the triangle is counter-clockwise)
-    assert numpy.array_equal(got == geo_ref.INT, exact > 0) and not (got == geo_ref.BND).any()
+    geo_edges.check_naive_flips(eng)
 
 
 def test_scale_reduced_gaussian_against_star_polygon(eng):
-    lon, lat = geo_ref.reduced_gaussian(1 << 20)
-    assert len(lon) == 1 << 20
-    ring = geo_ref.star(4096)
-    assert len(ring) >= 4000
-    lay = geo_ref.layout([geo_ref.rings_of(ring)])
-    got = _codes(eng, lon, lat, lay)
-    want = geo_ref.locations(lon, lat, *lay)
-    assert numpy.array_equal(got, want), "%d of %d codes differ" % ((got != want).sum(), want.size)
-    counts = numpy.bincount(want.ravel(), minlength=3)
-    assert counts[geo_ref.INT] > 1000 and counts[geo_ref.BND] > 0
+    geo_edges.check_scale(eng)
 
 
 def test_haversine_matches_reference_formula(eng):
-    rng = numpy.random.default_rng(7)
-    lon, lat = rng.uniform(0, 360, 200_000), rng.uniform(-90, 90, 200_000)
-    for lon0, lat0 in ((4.9, 52.3), (-120.0, -45.0), (179.5, 0.0)):
-        want = geo_ref.haversine(lon, lat, lon0, lat0)
-        keep = want < numpy.pi * 6371 - 111.0                              # more than ~1 degree from the antipode
-        got = eng.haversine(torch.from_numpy(lon).cuda(), torch.from_numpy(lat).cuda(), lon0, lat0).cpu().numpy()
-        rel = numpy.abs(got - want)[keep] / numpy.maximum(want[keep], 1e-300)
-        assert rel.max() <= 1e-12, rel.max()
+    geo_edges.check_haversine(eng)
+
+
+def test_exact_stage_decides_by_the_tails_of_its_differences(eng):
+    """orientations that only the tail x head and tail x tail products of the exact stage get right, one of them collinear"""
+    geo_edges.check_exact_tails(eng)
+
+
+def test_rings_whose_edges_end_on_the_lds_tile(eng):
+    """rings of 1024, 1025, 2048, 2049 edges, as shells and as holes: the seam vertex, the edges on either side of it, a
+    last tile of one edge"""
+    geo_edges.check_tile_seams(eng)
+
+
+def test_image_longitude_at_and_next_to_the_multiples_of_180(eng):
+    geo_edges.check_image_lon(eng)
+
+
+@pytest.mark.parametrize("n", geo_edges.POINT_COUNTS)
+def test_point_counts_around_the_workgroup_size(eng, n):
+    """two polygons in one launch, a polygon id that comes back; nothing behind the output is written"""
+    geo_edges.check_point_counts(eng, (n,))
+
+
+def test_non_finite_points_are_exterior(eng):
+    """NaN / +-inf in lon or lat: exterior of every polygon as p and as q, never selected through an area mask"""
+    geo_edges.check_non_finite_points(eng)
 
 
 def _expected(points, masks, nmax):

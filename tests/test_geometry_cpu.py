@@ -14,7 +14,7 @@ import torch
 
 import __graft_entry__ as ge
 from sp_coupler_amd import _abi, geometry
-from tests import geo_ref
+from tests import geo_edges, geo_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = float("inf")
@@ -124,6 +124,106 @@ def test_adversarial_set_covers_the_rules():
     inside = geo_ref.contains(geo_ref.locations(lon, lat, *lay))
     assert not inside[:, 0].any() and inside[:, 1].any() and set(lon[inside[:, 1]]) == set(numpy.arange(332.5, 350.0, 2.5))
     assert geo_ref.contains(geo_ref.locations(*cases["infinite_box"][1:3], *cases["infinite_box"][3])).all()
+
+
+# ---- the inputs of tests/geo_edges.py: the oracle pinned by the brute force, and what they were built to hold --------------
+def _brute_equals(lon, lat, lay, want, pick):
+    pick = numpy.asarray(pick)
+    assert numpy.array_equal(geo_ref.brute_locations(lon[pick], lat[pick], *lay), want[:, pick, :])
+
+
+def test_exact_tails_case_conditions_and_oracle():
+    a, b, apex, pts, exact, head, tails = geo_edges.exact_tails_case()
+    deciding = tails & (exact != 0) & (head != exact)
+    assert deciding.sum() >= 32                                   # the sign of the head-only expansion is wrong there
+    col = numpy.flatnonzero(tails & (exact == 0))
+    assert len(col) >= 1 and (head[col] != 0).all()               # exactly collinear, and the head-only expansion denies it
+    assert all(not geo_edges.filter_decides(*a, *b, x, y) for x, y in pts)
+    want = geo_edges.exact_tails_want()
+    assert numpy.array_equal(want[0, :, 0] == geo_ref.INT, exact > 0) and numpy.array_equal(want[0, :, 0] == geo_ref.BND, exact == 0)
+    lay = geo_ref.layout([geo_ref.rings_of([a, b, apex, a])])
+    _brute_equals(pts[:, 0], pts[:, 1], lay, want, list(range(0, len(pts), 7)) + col.tolist())
+    print(geo_edges.exact_tails_counts())
+
+
+def test_tile_seam_rings_and_points():
+    for edges in geo_edges.SEAM_EDGES:
+        ring, of_edge = geo_edges.seam_ring(edges)
+        assert len(ring) == edges + 1 and (ring[0] == ring[-1]).all() and (ring * 2 == numpy.round(ring * 2)).all()
+        assert len({tuple(v) for v in ring[:-1]}) == edges      # no repeated vertex
+        assert of_edge[-geo_edges.SEAM_START:] == list(range(geo_edges.SEAM_START))     # the last ring edges are chain edges
+        for s in range(geo_edges.TILE, edges, geo_edges.TILE):   # the edges on both sides of a seam are chain edges
+            assert of_edge[s - 1] >= 0 and of_edge[s] >= 0
+    assert geo_edges.seam_ring(1025)[1][1024] == 3 and geo_edges.seam_ring(2049)[1][2048] == 3   # the one-edge last tiles
+    lon, lat, lay, want = geo_edges.tile_seams_case()
+    assert 250 <= len(lon) <= 350 and lay[5] == 8
+    assert (numpy.diff(lay[2])[[0, 1, 2, 3]] == numpy.array(geo_edges.SEAM_EDGES) + 1).all()
+    for k, edges in enumerate(geo_edges.SEAM_EDGES):
+        ring, of_edge = geo_edges.seam_ring(edges)
+        at = lambda x, y: want[k, numpy.flatnonzero((lon == x) & (lat == y))[0], 0]       # noqa: E731
+        for r in [s + d for s in range(geo_edges.TILE, edges + 1, geo_edges.TILE) for d in (-1, 0)] + [edges - 1]:
+            if r < edges:
+                y = 0.5 * of_edge[r] + 0.25
+                # inside: the ray crosses ring edge r only; left of the ring: the left side and edge r; right: nothing
+                assert (at(50.0, y), at(-5.0, y), at(150.0, y)) == (geo_ref.INT, geo_ref.EXT, geo_ref.EXT), (edges, r)
+                assert at(*((ring[r] + ring[r + 1]) / 2)) == geo_ref.BND
+        for s in range(geo_edges.TILE, edges, geo_edges.TILE):
+            assert at(*ring[s]) == geo_ref.BND                    # the seam vertex
+        # as the hole of the square: interior and exterior change places, the boundary stays
+        swap = numpy.array([geo_ref.INT, geo_ref.BND, geo_ref.EXT])
+        inside_square = (lon > -100) & (lon < 2000) & (lat > -100) & (lat < 2000)
+        assert inside_square.all() and numpy.array_equal(want[4 + k], swap[want[k]])
+    _brute_equals(lon, lat, lay, want, range(0, len(lon), 23))
+
+
+def test_image_lon_case():
+    for lon in geo_edges.IMAGE_LONS:
+        assert float(geo_ref.image_lon(lon)) == (lon - 180) % 360 - 180
+        assert -180.0 <= float(geo_ref.image_lon(lon)) <= 180.0
+    assert len(geo_edges.IMAGE_LONS) == 15
+    lon, lat, lay, want = geo_edges.image_lon_case()
+    _brute_equals(lon, lat, lay, want, range(len(lon)))
+    at = lambda k, x, img: want[k, numpy.flatnonzero((lon == x) & (lat == 0.0))[0], img]      # noqa: E731
+    up, down = math.nextafter(180.0, INF), math.nextafter(180.0, -INF)
+    assert (at(2, up, 1), at(2, 180.0, 1), at(2, down, 1)) == (geo_ref.INT, geo_ref.BND, geo_ref.EXT)   # the strip -180 ... -170
+    assert at(0, 720.5, 1) == geo_ref.INT and at(0, 720.5, 0) == geo_ref.EXT and at(1, 360.0, 0) == geo_ref.BND
+    assert set(numpy.unique(want)) == {geo_ref.EXT, geo_ref.BND, geo_ref.INT}
+
+
+def test_point_counts_case():
+    for n in geo_edges.POINT_COUNTS:
+        lon, lat, two, want_two, inter, want_inter = geo_edges.point_counts_case(n)
+        assert len(lon) == n and want_two.shape == want_inter.shape == (2, n, 2)
+        pick = range(0, n, max(1, n // 12))
+        _brute_equals(lon, lat, two, want_two, pick)
+        _brute_equals(lon, lat, inter, want_inter, pick)
+        assert inter[4].tolist() == [0, 1, 0]
+        # row 0 of the interleaved layout is the square that came back under id 0, not the triangle
+        sq = geo_ref.locations(lon, lat, *geo_ref.layout([geo_ref.rings_of([(-5, -5), (5, -5), (5, 5), (-5, 5), (-5, -5)])]))
+        assert numpy.array_equal(want_inter[0], sq[0]) and want_two[1, -1, 0] == geo_ref.BND
+    assert not numpy.array_equal(want_inter[0], want_two[0])
+
+
+def test_non_finite_points_are_exterior_in_the_oracle():
+    lon, lat, finite, cases = geo_edges.non_finite_case()
+    assert (~finite).sum() == 18 and finite.sum() >= 5
+    for name, lay, want in cases:
+        assert (want[:, ~finite, :] == geo_ref.EXT).all(), name
+        assert numpy.array_equal(geo_ref.brute_locations(lon, lat, *lay), want), name
+        assert not geo_ref.contains(want)[~finite].any()
+        assert geo_ref.contains(want)[finite].any()
+    assert geo_ref.contains(dict((c[0], c[2]) for c in cases)["infinite_box"])[finite].all()
+    # two parts of a MultiPolygon span latitude 0: were a NaN longitude "collinear" with an edge of each, the point would
+    # be on two boundaries and GEOS's mod-2 rule would call it contained
+    assert geo_ref.contains(numpy.full((2, 1, 2), geo_ref.BND)).all()
+
+
+def test_non_finite_points_never_selected_through_the_stand_in_engine(su):
+    lon, lat, finite, cases = geo_edges.non_finite_case()
+    points = list(zip(lon.tolist(), lat.tolist()))
+    for name, g in geo_edges.non_finite_masks().items():
+        sel = su.get_mask_indices(points, [g])
+        assert sel and all(finite[i] for i in sel), (name, sel)
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------

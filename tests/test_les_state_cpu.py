@@ -112,6 +112,83 @@ def test_jumps_compose(a, b):
     assert numpy.array_equal(_next_outputs(k1, p1), _next_outputs(k2, p2))
 
 
+@pytest.mark.parametrize("T", [1, 2, 33, 34, 1000])
+def test_jump_vs_numpy_by_generations(T):
+    """n words that need exactly T twists: none of them jumped over (1), one (2), the jump polynomial of degree below and
+    above the 33 generations of the stream the correlation reads (33, 34), a long jump (1000).  The jump this asks for is
+    J = 624 (T - 1) words, always even: an odd J, the multiplication by x after the last squaring, cannot be reached through
+    mt19937_jump and is checked on the polynomial itself in the two test_odd_jump_polynomials_* below"""
+    for start, extra in ((0, 1), (311, 624)):
+        rs = _state(4242, start)
+        s0 = rs.get_state()
+        n = N * T + extra - start
+        assert (start + n - 1) // N == T
+        key, pos = _abi.mt19937_jump(s0[1], s0[2], n)
+        _draw_words(rs, n)
+        s1 = rs.get_state()
+        assert pos == s1[2] and numpy.array_equal(key, s1[1])
+
+
+def test_jump_vs_numpy_from_both_branches_of_the_polynomial_cache():
+    """x^J from the cached x^(J/2) (one squaring) and from nothing (square-and-multiply over the bits of J): J = 624 (T - 1)
+    for T = 1001 after T = 501, and for T = 1203 before T = 602"""
+    for T in (501, 1001, 1203, 602):
+        rs = _state(77, 5)
+        s0 = rs.get_state()
+        n = N * T + 3 - 5
+        key, pos = _abi.mt19937_jump(s0[1], s0[2], n)
+        _draw_words(rs, n)
+        s1 = rs.get_state()
+        assert pos == s1[2] == 3 and numpy.array_equal(key, s1[1]), T
+
+
+def _poly_int(J):
+    return int.from_bytes(_abi.mt19937_jump_poly(J).tobytes(), "little")
+
+
+def test_odd_jump_polynomials_multiply_by_x():
+    """odd J: the multiplication by x after the last squaring, from a cached x^(J div 2) and from nothing.  x^J mod phi must
+    be x * (x^(J-1) mod phi) reduced once by phi, here in Python integers"""
+    phi = _poly_int(19937) | 1 << 19937
+    for J, warm in ((624 * 1000 + 1, True), (624 * 1234 + 1, False), (2 ** 41 + 12345, True), (2 ** 41 + 54321, False)):
+        assert J % 2 == 1
+        if warm:
+            _abi.mt19937_jump_poly(J // 2)                       # x^J then comes from the cache: one squaring, one mulx
+        got = _poly_int(J)
+        want = _poly_int(J - 1) << 1
+        if want >> 19937:
+            want ^= phi
+        assert got == want and got >> 19937 == 0, J
+
+
+def test_odd_jump_polynomials_compose_to_a_jump_numpy_confirms():
+    """mt19937_jump only ever asks for J = 624 (T - 1), which is even, so the multiplication by x after the LAST squaring
+    cannot be reached through it (the ones after earlier squarings are: every set bit of J but the lowest); and the test
+    above takes its reference from the same routine at J - 1.  Here two odd powers are multiplied in Python integers:
+    x^J1 * x^J2 mod phi must be x^(624 * 1000), the polynomial of the jump over 1000 generations, which is then applied to a
+    state and compared with NumPy drawing the words"""
+    phi = _poly_int(19937) | 1 << 19937
+    for J1 in (624 * 1000 - 1, 311 * 1000 + 1, 12345):
+        J2 = 624 * 1000 - J1
+        assert J1 % 2 == 1 and J2 % 2 == 1
+        a, b, prod = _poly_int(J1), _poly_int(J2), 0
+        while b:
+            low = b & -b
+            prod ^= a << (low.bit_length() - 1)
+            b ^= low
+        for i in range(prod.bit_length() - 1, 19936, -1):
+            if prod >> i & 1:
+                prod ^= phi << (i - 19937)
+        assert prod == _poly_int(624 * 1000), J1
+    rs = _state(31, 100)
+    s0 = rs.get_state()
+    n = N * 1001 + 1 - 100                                       # T = 1001: the jump applies x^(624 * 1000)
+    key, pos = _abi.mt19937_jump(s0[1], s0[2], n)
+    _draw_words(rs, n)
+    s1 = rs.get_state()
+    assert pos == s1[2] == 1 and numpy.array_equal(key, s1[1])
+
+
 def _bits(poly):
     return numpy.unpackbits(poly.view(numpy.uint8), bitorder="little")
 

@@ -1,39 +1,19 @@
 """K9 on the MI355X: spcpl.set_les_state_batched / Engine.les_state against the unchanged host spcpl.set_les_state, run on
-recording LES after re-seeding.  Every test asks for equal bits and an equal numpy.random.get_state() tuple."""
+recording LES after re-seeding.  Every test asks for equal bits and an equal numpy.random.get_state() tuple.  The helpers
+and the bodies that tools/mutation_control.py --lesstate also runs on its mutant libraries live in tests/les_state_ref.py."""
 import copy
 
 import numpy
 import pytest
 import torch
 
-from sp_coupler_amd import _abi, driver, models, spcpl
+from sp_coupler_amd import driver, models, spcpl
 from sp_coupler_amd.engine import Engine
 from sp_coupler_amd.multi import MultiDeviceEngine
+from tests import les_state_ref
+from tests.les_state_ref import RecLES, _odd_start, _profiles, _run_both, _same_state
 
 pytestmark = pytest.mark.gpu
-
-
-class RecLES:
-    """an LES that records what the coupler sets"""
-
-    def __init__(self, shape):
-        self.shape = shape
-        self.calls = []
-
-    def get_itot(self):
-        return self.shape[0]
-
-    def get_jtot(self):
-        return self.shape[1]
-
-    def get_ktot(self):
-        return self.shape[2]
-
-    def set_field(self, name, values):
-        self.calls.append((name, numpy.array(values)))
-
-    def set_surface_pressure(self, ps):
-        self.calls.append(("PS", float(ps)))
 
 
 @pytest.fixture(autouse=True)
@@ -44,89 +24,34 @@ def _restore():
     numpy.random.set_state(saved)
 
 
-def _odd_start(seed=42):
-    """a state with a cached Gaussian and an odd pos"""
-    numpy.random.seed(seed)
-    numpy.random.normal()                         # draws a pair: has_gauss = 1
-    numpy.random.randint(0, 2 ** 32, size=3, dtype=numpy.uint32)
-    s = numpy.random.get_state()
-    assert s[3] == 1 and s[2] % 2 == 1
-    return s
-
-
-def _profiles(shapes, seed=3):
-    rng = numpy.random.default_rng(seed)
-    return [[rng.normal(m, 1.0, s[2]) for s in shapes] for m in (5.0, -3.0, 300.0, 0.01)]
-
-
-def _same_state(a, b):
-    assert a[0] == b[0] and numpy.array_equal(a[1], b[1]) and a[2] == b[2] and a[3] == b[3] and a[4] == b[4]
-
-
-def _same_calls(got, want):
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        assert [c[0] for c in g.calls] == [c[0] for c in w.calls]
-        for (_, x), (_, y) in zip(g.calls, w.calls):
-            assert numpy.array_equal(x, y)
-
-
-def _run_both(shapes, start, ps=None, **kw):
-    u, v, thl, qt = _profiles(shapes)
-    want = [RecLES(s) for s in shapes]
-    numpy.random.set_state(start)
-    for l, les in enumerate(want):
-        spcpl.set_les_state(les, u[l], v[l], thl[l], qt[l], None if ps is None else ps[l])
-    s_want = numpy.random.get_state()
-    got = [RecLES(s) for s in shapes]
-    numpy.random.set_state(start)
-    spcpl.set_les_state_batched(got, u, v, thl, qt, ps=ps, **kw)
-    _same_calls(got, want)
-    _same_state(numpy.random.get_state(), s_want)
-
-
 def test_mixed_shapes_odd_start_cached_gauss():
-    spcpl.set_engine(Engine("cuda:0"))
-    shapes = [(7, 5, 19), (64, 64, 160), (1, 1, 3), (3, 4, 19), (8, 8, 160)]
-    _run_both(shapes, _odd_start(), ps=[101325.0, 0.0, 99000.5, 98000.0, 100000.0])
+    les_state_ref.check_mixed_shapes(Engine("cuda:0"))
 
 
-@pytest.mark.parametrize("gens", [1, 3, 7])
+@pytest.mark.parametrize("gens", les_state_ref.FORCED_GENS)
 def test_forced_short_substreams(gens):
     """many substream boundaries, doubles whose two words straddle them, the prefix from an odd pos"""
-    spcpl.set_engine(Engine("cuda:0"))
-    shapes = [(7, 5, 19), (5, 3, 11), (16, 16, 40), (7, 5, 19)]
-    _run_both(shapes, _odd_start(7), gens_per_substream=gens)
+    les_state_ref.check_forced_short_substreams(Engine("cuda:0"), (gens,))
 
 
 def test_start_at_twist_boundary_and_no_twist():
-    spcpl.set_engine(Engine("cuda:0"))
-    numpy.random.seed(1)
-    _run_both([(4, 4, 40), (2, 2, 30)], numpy.random.get_state())          # pos 624: the first word needs a twist
-    numpy.random.seed(1)
-    numpy.random.random_sample(100)
-    _run_both([(1, 2, 3)], numpy.random.get_state())                       # 48 words from pos 200: no twist at all
-    numpy.random.seed(1)
-    numpy.random.random_sample(4)
-    _run_both([(1, 1, 1), (1, 1, 2), (1, 1, 74)], numpy.random.get_state())  # 616 words from pos 8: ends at pos 624
+    les_state_ref.check_twist_boundary(Engine("cuda:0"))
 
 
 def test_engine_les_state_equals_host_jump():
     """Engine.les_state on one shape: [n x itot x jtot x ktot] fields and the state NumPy (and the host jump) reach"""
-    eng = Engine("cuda:0")
-    shapes = [(16, 16, 32)] * 3
-    u, v, thl, qt = (numpy.stack(p) for p in _profiles(shapes))
-    s = _odd_start(5)
-    fields, (key, pos) = eng.les_state(shapes, u, v, thl, qt, s, gens_per_substream=5)
-    numpy.random.set_state(s)
-    for l in range(3):
-        for name, amp, prof in zip(("U", "V", "THL", "QT"), (0.5, 0.5, 0.1, 2.5e-5), (u, v, thl, qt)):
-            want = amp * numpy.random.uniform(-1., 1., shapes[l]) + prof[l]
-            assert numpy.array_equal(fields[name][l].cpu().numpy(), want), (l, name)
-    s1 = numpy.random.get_state()
-    assert pos == s1[2] and numpy.array_equal(key, s1[1])
-    k2, p2 = _abi.mt19937_jump(s[1], s[2], 8 * 3 * 16 * 16 * 32)
-    assert p2 == pos and numpy.array_equal(k2, key)
+    les_state_ref.check_engine_level(Engine("cuda:0"))
+
+
+def test_an_les_begins_on_the_first_element_of_a_substream():
+    """an LES of one cell, of several cells and the last LES of the list on the first element a substream emits, from an even
+    and from an odd pos, with 1 and 2 generations per substream"""
+    les_state_ref.check_seek_boundaries(Engine("cuda:0"))
+
+
+def test_substream_counts_that_are_no_power_of_two():
+    """3, 5 and 7 substreams, the last one whole and one generation short, launches that end at pos 624"""
+    les_state_ref.check_odd_substream_counts(Engine("cuda:0"))
 
 
 def test_small_chunks_and_engines_sharing_a_card(monkeypatch):

@@ -1,6 +1,6 @@
 """The mutation control's table (tools/mutation_control.py) against the current kernel sources, on the CPU: the shipped
 sources carry no mutant switch, every mutant is present and guarded by a property of tests/semantic_props.py (K10's by a
-body of tests/slab_edges.py), and every
+body of tests/slab_edges.py, K8's by one of tests/geo_edges.py, K9's by one of tests/les_state_ref.py), and every
 edit still finds its line -- a kernel edit that drops or moves a mutant's line fails here, not as a SURVIVED mutant on the
 GPU box."""
 import os
@@ -40,3 +40,38 @@ def test_mutant_edits_apply_to_the_tree(n):
     for name, text in files.items():
         with open(os.path.join(mc.CSRC, name)) as f:
             assert text != f.read(), (n, name)
+
+
+NEW_TABLES = [(mc.GEO_MUTANTS, mc.GEO, "geo_edges", 15), (mc.LESSTATE_MUTANTS, mc.LESSTATE, "les_state_ref", 13)]
+
+
+@pytest.mark.parametrize("table,source,module,count", NEW_TABLES, ids=["geo", "lesstate"])
+def test_k8_k9_mutants_are_guarded_by_a_body(table, source, module, count):
+    import importlib
+    bodies = importlib.import_module("tests." + module)
+    assert sorted(table) == list(range(1, count + 1))
+    for n, (what, guard, edits) in table.items():
+        assert what and edits and callable(guard) and all(e[0] in (source, source.replace(".hpp", "_host.hpp")) for e in edits), n
+        mod, name = guard.__name__.split(".", 1)
+        assert mod == module and hasattr(bodies, "check_" + name) and name in bodies.OLD_BODIES + bodies.NEW_BODIES, (n, guard.__name__)
+    assert set(mc.GEO_OLD_GUARDS) <= set(mc.GEO_MUTANTS) and set(mc.LESSTATE_OLD_GUARDS) <= set(mc.LESSTATE_MUTANTS)
+
+
+@pytest.mark.parametrize("table,n", [(t, n) for t in (mc.GEO_MUTANTS, mc.GEO_EQUIVALENT, mc.LESSTATE_MUTANTS, mc.LESSTATE_EQUIVALENT)
+                                     for n in sorted(t)],
+                         ids=lambda v: str(v) if not isinstance(v, dict) else
+                         {id(mc.GEO_MUTANTS): "geo", id(mc.GEO_EQUIVALENT): "geo_eq", id(mc.LESSTATE_MUTANTS): "lesstate",
+                          id(mc.LESSTATE_EQUIVALENT): "lesstate_eq"}[id(v)])
+def test_k8_k9_mutant_edits_apply_to_the_tree(table, n):
+    files = mc.patched(n, table=table)      # raises when an edit's old text does not occur exactly as often as stated
+    for name, text in files.items():
+        with open(os.path.join(mc.CSRC, name)) as f:
+            assert text != f.read(), (n, name)
+
+
+def test_libraries_of_the_tables_do_not_collide():
+    libs = [mc.lib_of(n, t) for t in (mc.MUTANTS, mc.ADVANCE_MUTANTS, mc.THERMO_MUTANTS, mc.GEO_MUTANTS, mc.GEO_EQUIVALENT,
+                                      mc.LESSTATE_MUTANTS, mc.LESSTATE_EQUIVALENT) for n in t]
+    assert len(set(libs)) == len(libs)
+    assert mc.lib_of(3).endswith("libspc_mutant3.so") and mc.lib_of(2, mc.ADVANCE_MUTANTS).endswith("libspc_advance_mutant2.so")
+    assert mc.lib_of(4, mc.THERMO_MUTANTS).endswith("libspc_thermo_mutant4.so")

@@ -13,11 +13,19 @@ ADVANCE_MUTANTS is the table of K11 (spc_advance.hpp), numbered on its own and c
 bodies of tests/les_advance_ref.py, which tests/test_les_advance_gpu.py runs on the shipped library.
 THERMO_MUTANTS is the table of K12 (spc_thermo.hpp), chosen with --thermo; its guards are the bodies of
 tests/les_thermo_ref.py, which tests/test_les_thermo_gpu.py runs on the shipped library.
+GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
+tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
+--lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
+Both runs end with the edits of *_EQUIVALENT (edits proved to change no output: expected to fail NO body) and, for K8, with
+the guards that existed before tests/geo_edges.py on the mutants the new bodies were written for; the K9 run ends with
+OLD_BODIES of tests/les_state_ref.py on mutants 12 and 13 in the same way.
 usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py > profiles/mutation_control.log
        python tools/mutation_control.py --only 28 29 30 31 32 33 34 35 > profiles/mutation_control_slab.log
        python tools/mutation_control.py --advance --build && python tools/mutation_control.py --advance > profiles/mutation_control_advance.log
-       python tools/mutation_control.py --thermo --build && python tools/mutation_control.py --thermo > profiles/mutation_control_thermo.log"""
+       python tools/mutation_control.py --thermo --build && python tools/mutation_control.py --thermo > profiles/mutation_control_thermo.log
+       python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
+       python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log"""
 import argparse
 import os
 import shutil
@@ -36,6 +44,9 @@ K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp"
 SLAB = "spc_slab.hpp"
 ADVANCE = "spc_advance.hpp"
 THERMO = "spc_thermo.hpp"
+GEO = "spc_geo.hpp"
+LESSTATE = "spc_lesstate.hpp"
+LESSTATE_HOST = "spc_lesstate_host.hpp"
 A9 = "(col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG"     # the neighbouring column of the slab (mutant 9)
 
 def slab_edges(name):
@@ -220,12 +231,175 @@ THERMO_MUTANTS = {
 }
 
 
+def geo_body(name):
+    """guard of a K8 mutant: the body ``name`` of tests/geo_edges.py on the float64 engine of the library (K8 is float64 on
+    every engine)"""
+    def guard(engine_of):
+        import torch
+        from tests import geo_edges
+        failed = geo_edges.check_everything(engine_of(torch.float64))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "geo_edges." + name
+    return guard
+
+
+# K8 (spc_geo.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches, none changes a barrier or an index; mutant 6 makes the tile loop (uniform over the workgroup) end
+# one trip earlier, mutant 9 reads ring_role[r - 1] for r >= 1, which the shipped kernel has read one ring before.
+# The bodies exact_tails, tile_seams, image_lon and non_finite_points exist for mutants 1, 6, 14 and 15.  Mutant 2 (no
+# tails at all) is also seen by the earlier naive_flips points: 18 of those 28 have a tail in b - c (24.25 - y, 17.3 - x) and
+# at 8 of them the head-only expansion has the wrong sign; none has a tail in a - c (0.5 - x, 0.5 - y are exact), which is
+# what mutant 1 drops, and none is collinear.  GEO_OLD_GUARDS names the mutants on which the run ends by showing what the
+# guards from before tests/geo_edges.py make of them.
+_STORE = "p.out[(int64_t)cur_poly * p.n_points + i] = finite ? (uint16_t)(code_p | (code_q << 8)) : (uint16_t)GEO_EXTERIOR;"
+GEO_MUTANTS = {
+    1: ("K8 exact orientation: the four two-products with the tails of a - c left out (8 of the 16 terms summed)", geo_body("exact_tails"),
+        [(GEO, "geo_two_prod(acx[i], bcy[j], t[4 * i + 2 * j], t[4 * i + 2 * j + 1]);",
+          "geo_two_prod(i ? 0.0 : acx[i], bcy[j], t[4 * i + 2 * j], t[4 * i + 2 * j + 1]);"),
+         (GEO, "geo_two_prod(-acy[i], bcx[j], t[8 + 4 * i + 2 * j], t[8 + 4 * i + 2 * j + 1]);",
+          "geo_two_prod(i ? 0.0 : -acy[i], bcx[j], t[8 + 4 * i + 2 * j], t[8 + 4 * i + 2 * j + 1]);")]),
+    2: ("K8 exact orientation: TwoDiff replaced by a plain difference (no tails)", geo_body("exact_tails"),
+        [(GEO, "    e = (a - (d + bb)) + (bb - b);", "    e = 0.0 * bb;")]),
+    3: ("K8 orientation: the filter's error bound replaced by 0 (the naive sign decides)", geo_body("naive_flips"),
+        [(GEO, "const double errbound = 3.3306690738754716e-16 * detsum;", "const double errbound = 0.0 * detsum;")]),
+    4: ("K8 segment: 'wholly to the left' with <= (a vertical edge through the point is skipped)", geo_body("adversarial"),
+        [(GEO, "if (x1 < px && x2 < px) return;", "if (x1 <= px && x2 <= px) return;")]),
+    5: ("K8 segment: upward edges include their end as well as their start (a ray through a vertex crosses both its edges)",
+        geo_body("adversarial"),
+        [(GEO, "if ((y1 > py && y2 <= py) || (y2 > py && y1 <= py)) {", "if ((y1 > py && y2 <= py) || (y2 >= py && y1 <= py)) {")]),
+    6: ("K8 tiles: a last tile that holds exactly one edge is skipped (t0 + 2 < e)", geo_body("tile_seams"),
+        [(GEO, "for (int64_t t0 = s; t0 + 1 < e; t0 += GEO_TILE) {", "for (int64_t t0 = s; t0 + 2 < e; t0 += GEO_TILE) {")]),
+    7: ("K8 segment: o = -o dropped for downward edges", geo_body("adversarial"),
+        [(GEO, "if (y2 < y1) o = -o;  ", "                      ")]),
+    8: ("K8 fold: a hole's BOUNDARY folded to INTERIOR", geo_body("adversarial"),
+        [(GEO, "ring_code == GEO_BOUNDARY ? GEO_BOUNDARY : GEO_INTERIOR;", "ring_code == GEO_BOUNDARY ? GEO_INTERIOR : GEO_INTERIOR;")]),
+    9: ("K8 fold: every hole after a polygon's first is ignored", geo_body("adversarial"),
+        [(GEO, "        code_p = geo_fold(code_p, rp, role);\n        code_q = geo_fold(code_q, rq, role);",
+          "        if (!(role == SPC_RING_HOLE && r >= 1 && p.ring_role[r - 1] == SPC_RING_HOLE)) {\n"
+          "            code_p = geo_fold(code_p, rp, role);\n            code_q = geo_fold(code_q, rq, role);\n        }")]),
+    10: ("K8 rectangle rule with <= (the bounds belong to the rectangle)", geo_body("adversarial"),
+         [(GEO, "rp = in_y && x0 < px && px < x1 ? GEO_INTERIOR : GEO_EXTERIOR;", "rp = in_y && x0 <= px && px <= x1 ? GEO_INTERIOR : GEO_EXTERIOR;")]),
+    11: ("K8 image: r += 360 dropped (C's fmod instead of Python's %)", geo_body("adversarial"),
+         [(GEO, "if (r < 0.0) r += 360.0;", "if (r < 0.0) r += 0.0;")]),
+    12: ("K8 store: q's code in the low byte, p's in the high byte", geo_body("adversarial"),
+         [(GEO, _STORE, _STORE.replace("code_p | (code_q << 8)", "code_q | (code_p << 8)"), 2)]),
+    13: ("K8 haversine: dlat and dlng swapped in the sines", geo_body("haversine"),
+         [(GEO, "const double sl = sin((lat2 - lat1) * 0.5), sg = sin((lng2 - lng1) * 0.5);",
+           "const double sl = sin((lng2 - lng1) * 0.5), sg = sin((lat2 - lat1) * 0.5);")]),
+    14: ("K8 image: formed as (lon + 180) % 360 - 180 (the sum rounds where the difference is exact)", geo_body("image_lon"),
+         [(GEO, "const double x = lon - 180.0;", "const double x = lon + 180.0;")]),
+    15: ("K8 non-finite points: only p is made EXTERIOR, q keeps the code its arithmetic gave", geo_body("non_finite_points"),
+         [(GEO, _STORE, _STORE.replace(": (uint16_t)GEO_EXTERIOR", ": (uint16_t)(code_q << 8)"), 2)]),
+}
+#: the mutants of the exact stage and of the tile loop: main_advance runs the guards that existed before tests/geo_edges.py
+#: on them once (the scale test of tests/test_geo_gpu.py included) and prints what they find; this is information, not a check
+GEO_OLD_GUARDS = (1, 2, 6)
+# edits proved to change no output (expected to fail no body).  A: r is -0.0 only after fmod(-360 k, 360); -0.0 - 180 and
+# +0.0 - 180 are the same double.  B: the crossing rule half-open at the OTHER end throughout (every edge includes its upper
+# end and excludes its lower one) is the mirrored convention: a ray through a vertex then counts the edges that leave it
+# downwards instead of those that leave it upwards, the parity is the same, and a point on a vertex or on an edge is found
+# by the tests before the rule.
+GEO_EQUIVALENT = {
+    "A": ("K8 image: a zero remainder keeps fmod's sign (r = 0.0 dropped)",
+          [(GEO, "        r = 0.0;                  // CPython", "        r = r;                    // CPython")]),
+    "B": ("K8 segment: the crossing rule half-open at the other end for upward and downward edges alike (the mirrored convention)",
+          [(GEO, "if ((y1 > py && y2 <= py) || (y2 > py && y1 <= py)) {", "if ((y1 >= py && y2 < py) || (y2 >= py && y1 < py)) {")]),
+}
+
+
+def lesstate_body(name):
+    """guard of a K9 mutant: the body ``name`` of tests/les_state_ref.py on the float64 engine of the library (K9 is float64
+    on every engine)"""
+    def guard(engine_of):
+        import torch
+        from tests import les_state_ref
+        failed = les_state_ref.check_everything(engine_of(torch.float64))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_state_ref." + name
+    return guard
+
+
+# K9 (spc_lesstate.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernels touch, none changes a barrier; mutant 6 drops a loop; mutant 13 plans one generation more when the launch
+# ends on the last word of a generation (plan, workspace size and launch all follow the same T: one more twist in LDS, no
+# word emitted from it).  Two slips one would list first are NOT here:
+# * ls_seek's binary search with < for <= : proved to change no output -- the search then ends on an earlier LES and the
+#   loop `while (4 * elem_off[l + 1] <= e) l++` behind it walks to the right one; it is LESSTATE_EQUIVALENT["A"], run to
+#   confirm that no body fails.  A search that overshoots instead is not a "wrong numbers" mutant: el = e - 4 off wraps.
+# * that loop as an `if` (one LES advanced at most): an element two LES further on gets el >= 4 V, f >= 4, and out[f] is
+#   a wild pointer.  Mutants 7 and 8 are the slips of the same lines that stay inside the fields: the level index taken as
+#   the slowest dimension, and the cursor's ktot not refreshed when the element crosses into the next LES.
+# Mutant 9 writes final_key from workgroup 0 only (its last generation) instead of "from every workgroup": the same slip
+# without the race between workgroups that would make the outcome depend on their order.
+# Mutant 11 stands for "floor(log2 K) jump rounds instead of ceil": that edit makes k_les_state read substream starts that
+# no round wrote -- inside the workspace, but what the allocator left there, possibly the RIGHT starts of an earlier launch
+# of the same process, so its outcome is not determined.  The deterministic slip of the same place: the last round applies
+# the polynomial of the round before it.  Any K >= 3 shows it, forced_short_substreams included.
+# Mutants 12 and 13 were written for the bodies seek_boundaries and odd_substream_counts; LESSTATE_OLD_GUARDS names
+# them, and the run ends by showing what the bodies from before tests/les_state_ref.py (OLD_BODIES) make of them: 13 is
+# seen by odd_substream_counts alone; 12 is ALSO seen by forced_short_substreams and twist_boundary, because the search
+# runs for every thread's first element and their small LES put an LES start there: seek_boundaries closes no demonstrated
+# gap (profiles/mutation_control_lesstate.log).
+# * 12: ls_seek's search with < is neutral only because everything the cursor holds is set AFTER the walk behind it.  The
+#   mutant is that search together with a cursor whose ktot and profile row are those of the LES the search ended on (the
+#   walk corrects l, off, end4 and V): wrong exactly when an LES begins on a workgroup's first element, and then the
+#   profile of the LES before is added, with its ktot (k < ktot <= pitch, row < n_les: inside prof).
+# * 13: T = q div 624 instead of (q - 1) div 624: wrong exactly when the launch ends on the last word of a generation
+#   (NumPy leaves pos = 624 and does not twist); the fields are right, the returned state is one twist ahead with pos 0.
+LESSTATE_MUTANTS = {
+    1: ("K9 uniform: the second word shifted by 5 instead of 6", lesstate_body("mixed_shapes"),
+        [(LESSTATE, "(double)(wb >> 6)", "(double)(wb >> 5)")]),
+    2: ("K9 straddling double: its second word taken from the current generation (G[0]) instead of the next", lesstate_body("forced_short_substreams"),
+        [(LESSTATE, "j + 1 < MT_N ? G[j + 1] : mt_mix(G[0], G[1], G[MT_M])", "j + 1 < MT_N ? G[j + 1] : G[0]")]),
+    3: ("K9 emit: the parity correction lo++ dropped (from an odd pos the pairs of later generations start one word early)",
+        lesstate_body("forced_short_substreams"),
+        [(LESSTATE, "    if ((lo - P.p) & 1) lo++;\n", "")]),
+    4: ("K9 twist: word 623 mixed with the OLD word 0 (o[0]) instead of the new one", lesstate_body("mixed_shapes"),
+        [(LESSTATE, "nw[j] = mt_mix(o[j], nw[0], nw[MT_M - 1]);", "nw[j] = mt_mix(o[j], o[0], nw[MT_M - 1]);")]),
+    5: ("K9 jump rounds: k_mt_jump always starts from key0 (the lower bits' jumps are lost)", lesstate_body("forced_short_substreams"),
+        [(LESSTATE, "? states + s * MT_N : key0;", "? key0 : key0;")]),
+    6: ("K9 jump rounds: the remainder loop over n_coef % 8 coefficients dropped", lesstate_body("forced_short_substreams"),
+        [(LESSTATE, "    for (; q < n_coef; q++) {\n        const int i = coef[q];", "    for (; q < q; q++) {\n        const int i = coef[q];")]),
+    7: ("K9 broadcast: the profile level taken as the slowest dimension of the field (idx / (itot * jtot)) instead of the fastest",
+        lesstate_body("mixed_shapes"),
+        [(LESSTATE, "const uint32_t k = idx % c.kt;", "const uint32_t k = idx / (c.V / c.kt);")]),
+    8: ("K9 cursor: ktot not refreshed when an element crosses into the next LES", lesstate_body("mixed_shapes"),
+        [(LESSTATE, "    c.kt = (uint32_t)P.ktot[c.l];", "    if (c.kt == 1) c.kt = (uint32_t)P.ktot[c.l];")]),
+    9: ("K9 final state: written by workgroup 0 after ITS last generation instead of by the workgroup that twists generation T",
+        lesstate_body("forced_short_substreams"),
+        [(LESSTATE, "if (gen == P.T)\n", "if (gen == g1 && s == 0)\n")]),
+    10: ("K9 amplitude: amp[3 - f], the amplitude of another field", lesstate_body("mixed_shapes"),
+         [(LESSTATE, "const double v = P.amp[f] * r;", "const double v = P.amp[3 - f] * r;")]),
+    11: ("K9 jump rounds: the last round applies the polynomial of the round before it (x^(624 L 2^(b-1)) for x^(624 L 2^b))",
+         lesstate_body("forced_short_substreams"),
+         [(LESSTATE_HOST, "const Gf2Poly g = mt_jump_poly(((uint64_t)MT_N * (uint64_t)pl.L) << b);",
+           "const Gf2Poly g = mt_jump_poly(((uint64_t)MT_N * (uint64_t)pl.L) << (b > 0 && b + 1 == pl.rounds ? b - 1 : b));")]),
+    12: ("K9 ls_seek: the search with <, and the cursor of a thread's first element keeps ktot and the profile row of the LES "
+         "the search ended on", lesstate_body("seek_boundaries"),
+         [(LESSTATE, "if (4 * P.elem_off[mid] <= e) lo_l = mid; else hi_l = mid - 1;", "if (4 * P.elem_off[mid] < e) lo_l = mid; else hi_l = mid - 1;"),
+          (LESSTATE, "    if (c.l < 0) {                                             // the first element",
+           "    const bool first = c.l < 0;\n    if (first) {                                             // the first element"),
+          (LESSTATE, "        c.l = lo_l;\n", "        c.l = lo_l;\n        c.kt = (uint32_t)P.ktot[c.l];\n        c.row = c.l * P.pitch;\n"),
+          (LESSTATE, "    c.kt = (uint32_t)P.ktot[c.l];\n    c.row = c.l * P.pitch;\n}",
+           "    if (!first) {\n        c.kt = (uint32_t)P.ktot[c.l];\n        c.row = c.l * P.pitch;\n    }\n}")]),
+    13: ("K9 plan: T = q div 624 instead of (q - 1) div 624 (a launch that ends on the last word of a generation twists once more)",
+         lesstate_body("odd_substream_counts"),
+         [(LESSTATE, "pl.T = q <= MT_N ? 0 : (q - 1) / MT_N;", "pl.T = q <= MT_N ? 0 : q / MT_N;")]),
+}
+#: the mutants the new bodies were written for: main_advance runs OLD_BODIES of tests/les_state_ref.py on them once
+LESSTATE_OLD_GUARDS = (12, 13)
+LESSTATE_EQUIVALENT = {
+    "A": ("K9 ls_seek: the binary search with < for <= (the loop behind it walks to the right LES)",
+          [(LESSTATE, "if (4 * P.elem_off[mid] <= e) lo_l = mid; else hi_l = mid - 1;", "if (4 * P.elem_off[mid] < e) lo_l = mid; else hi_l = mid - 1;")]),
+}
+
+
 def patched(n, src=CSRC, table=None):
     """{file: text} of the files mutant n (of ``table``, default MUTANTS) changes, its edits applied to the sources under
     `src`; ValueError when an edit's old text does not occur exactly the expected number of times (the tree has drifted from
     the table)"""
     files = {}
-    for edit in (table or MUTANTS)[n][2]:
+    for edit in (table or MUTANTS)[n][-1]:
         name, old, new = edit[:3]
         want = edit[3] if len(edit) > 3 else 1
         if name not in files:
@@ -233,17 +407,27 @@ def patched(n, src=CSRC, table=None):
                 files[name] = f.read()
         got = files[name].count(old)
         if got != want:
-            raise ValueError("mutant %d: %r occurs %d times in %s, expected %d" % (n, old, got, name, want))
+            raise ValueError("mutant %s: %r occurs %d times in %s, expected %d" % (n, old, got, name, want))
         files[name] = files[name].replace(old, new)
     return files
 
 
+def _tag(table):
+    """(library prefix, source directory prefix) of a table"""
+    for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (GEO_MUTANTS, ("geo_", "geo")),
+                   (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
+                   (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq"))):
+        if table is t:
+            return tag
+    return "", ""
+
+
 def lib_of(n, table=None):
-    return os.path.join(OUT, "libspc_%smutant%d.so" % ("advance_" if table is ADVANCE_MUTANTS else "thermo_" if table is THERMO_MUTANTS else "", n))
+    return os.path.join(OUT, "libspc_%smutant%s.so" % (_tag(table)[0], n))
 
 
 def build_one(n, table=None):
-    src = os.path.join(OUT, "src%s%d" % ("adv" if table is ADVANCE_MUTANTS else "thermo" if table is THERMO_MUTANTS else "", n))
+    src = os.path.join(OUT, "src%s%s" % (_tag(table)[1], n))
     shutil.rmtree(src, ignore_errors=True)
     shutil.copytree(CSRC, src)
     for name, text in patched(n, table=table).items():
@@ -253,7 +437,7 @@ def build_one(n, table=None):
     r = subprocess.run([HIPCC] + HIP_FLAGS + [os.path.join(src, "spc_hip.hip"), "-o", lib], cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode:
-        raise RuntimeError("mutant %d: hipcc exit status %d\n%s" % (n, r.returncode, r.stdout[-2000:]))
+        raise RuntimeError("mutant %s: hipcc exit status %d\n%s" % (n, r.returncode, r.stdout[-2000:]))
     return lib
 
 
@@ -264,9 +448,9 @@ def build(ns, jobs, table=None):
     def one(n):
         try:
             build_one(n, table)
-            return "mutant %d built" % n, 0
+            return "mutant %s built" % n, 0
         except (ValueError, RuntimeError) as e:
-            return "mutant %d FAILED: %s" % (n, e), 1
+            return "mutant %s FAILED: %s" % (n, e), 1
 
     with ThreadPoolExecutor(max(1, min(jobs, 16))) as pool:
         for line, failed in pool.map(one, ns):
@@ -296,15 +480,21 @@ def run(lib_path):
     return failed
 
 
-def main_advance(only=None, table=None, kernel="K11", ref="les_advance"):
-    """the control of ADVANCE_MUTANTS (or of THERMO_MUTANTS): the bodies of tests/les_advance_ref.py (tests/les_thermo_ref.py)
-    on the shipped library, then on every mutant"""
+def main_advance(only=None, table=None, kernel="K11", ref="les_advance", module=None, gpu_test=None, equivalent=None, old_guards=None,
+                 notes=None):
+    """the control of ADVANCE_MUTANTS (or of another table numbered on its own): the bodies of tests/les_advance_ref.py
+    (tests/``module``.py) on the shipped library, then on every mutant; then the edits of ``equivalent`` (expected to fail
+    no body) and ``old_guards(engine_of)`` -> names that failed, on the mutants it is given for (printed, not judged)"""
     import torch
     table = ADVANCE_MUTANTS if table is None else table
-    print("mutation control of tests/%s_ref.py (tests/test_%s_gpu.py) on %s" % (ref, ref, torch.cuda.get_device_name(0)))
+    module, gpu_test = module or ref + "_ref", gpu_test or "test_%s_gpu" % ref
+    print("mutation control of tests/%s.py (tests/%s.py) on %s" % (module, gpu_test, torch.cuda.get_device_name(0)))
     chosen = sorted(n for n in table if only is None or n in only)
     clean = run_guard(table[chosen[0]][1], None)[1]
-    print("shipped library: the bodies of tests/%s_ref.py on both engines, failed: %s" % (ref, clean or "none"), flush=True)
+    print("shipped library: the bodies of tests/%s.py on %s, failed: %s"
+          % (module, "the float64 engine" if equivalent is not None else "both engines", clean or "none"), flush=True)
+    for line in (notes() if notes else ()):
+        print(line, flush=True)
     bad = int(bool(clean))
     for n in chosen:
         what, guard, _ = table[n]
@@ -317,8 +507,41 @@ def main_advance(only=None, table=None, kernel="K11", ref="les_advance"):
         bad += not ok
         print("%s mutant %2d: %s\n           guarded by %s: %s; all failing: %s"
               % (kernel, n, what, guard.__name__, "DETECTED" if ok else "SURVIVED", failed or "none"), flush=True)
+    for name in sorted(equivalent or {}) if only is None else ():
+        path = lib_of(name, equivalent)
+        if not os.path.exists(path):
+            print("%s equivalent edit %s: NOT BUILT (%s)" % (kernel, name, path))
+            bad += 1
+            continue
+        failed = run_guard(table[chosen[0]][1], path)[1]
+        bad += bool(failed)
+        print("%s equivalent edit %s: %s\n           proved to change no output; every body run, failing: %s"
+              % (kernel, name, equivalent[name][0], failed or "none"), flush=True)
+    for n, guard in (old_guards or {}).items() if only is None else ():
+        failed = run_guard(lambda engine_of, g=guard: (False, g(engine_of)), lib_of(n, table))[1]
+        print("%s mutant %2d under the guards that existed before tests/%s.py (%s): %s"
+              % (kernel, n, module, guard.__doc__, "not detected" if not failed else "detected by %s" % failed), flush=True)
     print("result: %s" % ("every mutant detected, shipped library clean" if not bad else "%d problem(s)" % bad))
     return 1 if bad else 0
+
+
+def geo_old_guard(engine_of):
+    """adversarial, naive_flips, haversine and the 2^20-point scale test"""
+    import torch
+    from tests import geo_edges
+    return geo_edges.check_everything(engine_of(torch.float64), names=geo_edges.OLD_BODIES, scale=True)
+
+
+def lesstate_old_guard(engine_of):
+    """mixed_shapes, forced_short_substreams, twist_boundary and engine_level"""
+    import torch
+    from tests import les_state_ref
+    return les_state_ref.check_everything(engine_of(torch.float64), names=les_state_ref.OLD_BODIES)
+
+
+def geo_notes():
+    from tests import geo_edges
+    return ["exact_tails: " + geo_edges.exact_tails_counts()]
 
 
 def main(only=None):
@@ -363,14 +586,27 @@ if __name__ == "__main__":
     ap.add_argument("-j", type=int, default=4, help="parallel compiles for --build (at most 16)")
     ap.add_argument("--advance", action="store_true", help="the table of K11 (ADVANCE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--thermo", action="store_true", help="the table of K12 (THERMO_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
-    table = ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else MUTANTS
+    table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else GEO_MUTANTS if args.geo
+             else LESSTATE_MUTANTS if args.lesstate else MUTANTS)
+    equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
         unknown = sorted(set(args.build) - set(table))
         if unknown:
             ap.error("no mutant %s" % unknown)
-        sys.exit(build(args.build or sorted(table), args.j, table))
+        rc = build(args.build or sorted(table), args.j, table)
+        if equivalent and not args.build:
+            rc |= build(sorted(equivalent), args.j, equivalent)
+        sys.exit(rc)
     only = set(args.only) if args.only else None
+    if args.geo:
+        sys.exit(main_advance(only, GEO_MUTANTS, "K8", module="geo_edges", gpu_test="test_geo_gpu", equivalent=GEO_EQUIVALENT,
+                              old_guards={n: geo_old_guard for n in GEO_OLD_GUARDS}, notes=geo_notes))
+    if args.lesstate:
+        sys.exit(main_advance(only, LESSTATE_MUTANTS, "K9", module="les_state_ref", gpu_test="test_les_state_gpu",
+                              equivalent=LESSTATE_EQUIVALENT, old_guards={n: lesstate_old_guard for n in LESSTATE_OLD_GUARDS}))
     if args.thermo:
         sys.exit(main_advance(only, THERMO_MUTANTS, "K12", "les_thermo"))
     sys.exit((main_advance if args.advance else main)(only))
