@@ -29,6 +29,8 @@
  *   spc_les_thermo_*     <- the saturation adjustment of that ensemble (nothing of it is in the reference): Qsat, QL and
  *                           T of every cell from THL, QT and the pressure by a Newton iteration over a
  *                           saturation-pressure table, with the slab means of QL and T, in one pass
+ *   spc_les_water_paths_* <- les.get_field("LWP" | "TWP" | "RWP") (splib/spdummy.py:243-251): the column water paths of
+ *                           those fields, with the cloud top and the cloud cover, in one pass
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -470,6 +472,36 @@ typedef struct spc_les_thermo_args {
 } spc_les_thermo_args;
 int spc_les_thermo_f64(const spc_les_thermo_args *args, void *stream);
 int spc_les_thermo_f32(const spc_les_thermo_args *args, void *stream);
+
+/* ---- column water paths, cloud top and cloud cover of the device-resident LES fields (kernel family K13) ----------- */
+/* What les.get_field("LWP" | "TWP" | "RWP") (splib/spdummy.py:243-251) returns, for every LES at once, from fields
+ * [n_les][itot][jtot][ktot] of one shape (layout and offsets as K10) and ONE weight profile w [n_les x ktot] (rho * dz):
+ *   out[f][l][i][j] = numpy.add.reduce(fields[f][l, i, j, :] * w[l, :])       for f < n_fields, bit for bit:
+ * the product rounded on its own in the element type T (never an fma), then the row of ktot products summed as
+ * ndarray.sum() sums a contiguous run: 0 + pairwise blocks of at most 128 elements with eight accumulators, halves split
+ * at multiples of 8, the remainder of a block added in order; rows of fewer than 8 elements sequentially.  NaN and
+ * infinities propagate as NumPy's do (inf * 0 is NaN); a row of -0.0 products gives +0.0.
+ * With cloud_field = c >= 0 the same pass over fields[c] also gives, each where its pointer != NULL:
+ *   top[l][i][j] = the largest k with fields[c][l, i, j, k] > 0, else -1       NaN and -0.0 are not cloudy (K10's rule)
+ *   cover[l]     = T(number of (i, j) with top >= 0) / T(itot * jtot)          an integer count, one IEEE division: exact
+ * ktot > 8192 (NumPy's chunk boundary) is SPC_ERR_UNSUPPORTED.  No output may be an input or another output.          */
+#define SPC_WP_MAX_FIELDS 4
+typedef struct spc_water_path_args {
+    int64_t n_les;                 /* 0 is allowed: no-op                                                  */
+    int32_t itot, jtot, ktot;
+    int32_t n_fields;              /* 1 ... SPC_WP_MAX_FIELDS                                              */
+    const void *fields[SPC_WP_MAX_FIELDS]; /* device [n_les][itot][jtot][ktot] each, read only             */
+    void *out[SPC_WP_MAX_FIELDS];          /* device [n_les][itot][jtot] each, contiguous                  */
+    const void *w;                 /* device [n_les x ktot], rows pitch_w apart                            */
+    int64_t pitch_w;               /* >= ktot                                                              */
+    int32_t cloud_field;           /* -1, or the field the cloud outputs are taken from                    */
+    int32_t reserved;              /* 0                                                                    */
+    int32_t *top;                  /* device [n_les][itot][jtot], or NULL                                  */
+    void *cover;                   /* device [n_les], element type of the fields, or NULL                  */
+} spc_water_path_args;
+typedef spc_water_path_args SpcWaterPathArgs;
+int spc_les_water_paths_f64(const spc_water_path_args *args, void *stream);
+int spc_les_water_paths_f32(const spc_water_path_args *args, void *stream);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

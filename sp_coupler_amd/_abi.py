@@ -127,6 +127,16 @@ class LesThermoArgs(ctypes.Structure):
                 + _ptrs("qsat", "ql", "temp", "ql_mean", "t_mean") + [("pitch_mean", c_int64)])
 
 
+WP_MAX_FIELDS = 4         # SPC_WP_MAX_FIELDS
+WP_MAX_KTOT = 8192        # rows NumPy sums in one chunk: spc_les_water_paths_* refuses longer ones
+
+
+class WaterPathArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32),
+                 ("fields", c_void_p * WP_MAX_FIELDS), ("out", c_void_p * WP_MAX_FIELDS), ("w", c_void_p), ("pitch_w", c_int64),
+                 ("cloud_field", c_int32), ("reserved", c_int32)] + _ptrs("top", "cover"))
+
+
 THERMO_TABLE_LIBRARY, THERMO_TABLE_LDS, THERMO_TABLE_GLOBAL = 0, 1, 2      # spc_les_thermo_args.table_mode
 
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
@@ -171,6 +181,8 @@ PROTOTYPES = {
     "spc_les_advance_f32": (ctypes.c_int, [ctypes.POINTER(LesAdvanceArgs), c_void_p]),
     "spc_les_thermo_f64": (ctypes.c_int, [ctypes.POINTER(LesThermoArgs), c_void_p]),
     "spc_les_thermo_f32": (ctypes.c_int, [ctypes.POINTER(LesThermoArgs), c_void_p]),
+    "spc_les_water_paths_f64": (ctypes.c_int, [ctypes.POINTER(WaterPathArgs), c_void_p]),
+    "spc_les_water_paths_f32": (ctypes.c_int, [ctypes.POINTER(WaterPathArgs), c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

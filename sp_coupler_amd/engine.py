@@ -720,6 +720,63 @@ class Engine:
         self._call(fn, ctypes.byref(a), stream=stream)
         return res
 
+    # -- K13: column water paths, cloud top and cloud cover of device-resident LES fields, one launch ---------------------
+    @_on_engine_stream
+    def les_water_paths(self, fields, w, cloud=None, out=None, top=False, cover=False, stream=None):
+        """``{name: numpy.add.reduce(field * w[:, None, None, :], axis=3)}`` of device fields [n x itot x jtot x ktot] of ONE
+        shape (at most ``_abi.WP_MAX_FIELDS``) and the weight profile ``w`` [n x ktot] (rows may be pitched), bit for bit
+        (include/spc.h has the rule), in ONE launch for all of them: dict name -> [n x itot x jtot].  ``cloud``: the name of
+        the field the cloud outputs are taken from; with it ``top`` adds ``"top"`` (int32 [n x itot x jtot]: the largest k
+        with field > 0, else -1) and ``cover`` adds ``"cover"`` ([n]: the fraction of (i, j) with top >= 0, exact).  ``top``
+        and ``cover`` are True or a tensor to write into; ``out``: dict name -> contiguous [n x itot x jtot] tensors to write
+        into.  ktot > ``_abi.WP_MAX_KTOT`` is refused (SPC_ERR_UNSUPPORTED)."""
+        names = list(fields)
+        if not 1 <= len(names) <= _abi.WP_MAX_FIELDS:
+            raise ValueError("les_water_paths takes 1 ... %d fields per launch, got %d" % (_abi.WP_MAX_FIELDS, len(names)))
+        if any(k in ("top", "cover") for k in names):
+            raise ValueError("les_water_paths: 'top' and 'cover' name the cloud outputs, not fields")
+        wants = [k for k, v in (("top", top), ("cover", cover)) if v is not False and v is not None]
+        if wants and cloud is None:
+            raise ValueError("les_water_paths: %s need cloud (the name of a field)" % " and ".join(wants))
+        if cloud is not None and cloud not in fields:
+            raise ValueError("les_water_paths: cloud = %r is not one of the fields %s" % (cloud, names))
+        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_water_paths: empty field shape %s" % (shape,))
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.WaterPathArgs()
+        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
+        a.w, a.pitch_w = ck.mat("w", w, n, ktot)
+
+        def plane(name, t, dtype, shp):
+            if t is None or t is True:
+                return torch.empty(shp, dtype=dtype, device=self.device)
+            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype or tuple(t.shape) != shp or not t.is_contiguous():
+                raise ValueError("les_water_paths: %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shp, self.device))
+            return t
+        res = {}
+        for f, name in enumerate(names):
+            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            res[name] = plane("out[%s]" % name, None if out is None else out.get(name), self.dtype, (n, itot, jtot))
+            a.out[f] = res[name].data_ptr()
+        a.cloud_field = -1
+        if wants:
+            a.cloud_field = names.index(cloud)
+            if "top" in wants:
+                res["top"] = plane("top", top, torch.int32, (n, itot, jtot))
+                a.top = res["top"].data_ptr()
+            if "cover" in wants:
+                res["cover"] = plane("cover", cover, self.dtype, (n,))
+                a.cover = res["cover"].data_ptr()
+        ptrs = [t.data_ptr() for t in res.values() if t.numel()]
+        ins = [fields[k].data_ptr() for k in names] + [w.data_ptr()]
+        if len(set(ptrs)) != len(ptrs) or set(ptrs) & set(ins):
+            raise ValueError("les_water_paths: an output is an input or another output")
+        fn = self.lib.spc_les_water_paths_f32 if self.dtype == torch.float32 else self.lib.spc_les_water_paths_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

@@ -649,6 +649,14 @@ class _DeviceLESRow(_LESRow):
     def set_field(self, name, values):
         raise NotImplementedError("a DeviceLESEnsemble takes whole fields: set_fields_batched")
 
+    def get_field(self, name):
+        """les.get_field("LWP" | "TWP" | "RWP") (splib/spdummy.py:243-251): row i of the ensemble's water paths (K13) as a
+        host [itot x jtot] array; the 3-D fields themselves are not handed out row by row"""
+        if name not in DeviceLESEnsemble.WATER_PATHS:
+            raise NotImplementedError("a DeviceLESEnsemble hands out the water paths LWP, TWP and RWP per LES; its 3-D fields "
+                                      "stay on the GPU: get_fields_batched")
+        return self._e._water_path_host(name)[self._i].copy()
+
 
 class DeviceLESEnsemble(SyntheticLESEnsemble):
     """SyntheticLESEnsemble whose 3-D fields are device tensors [n x itot x jtot x nL] in the engine's dtype
@@ -659,13 +667,16 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     field, constant in time; the QL field is ``max(QT - Qsat, 0)``.  tests/slab_ref.py holds the NumPy twin of this class.
     After ``enable_thermo()`` Qsat and QL are instead the saturation adjustment of THL and QT at ``presf`` (K12,
     ``Engine.les_thermo``: DESIGN.md 7.3), redone whenever THL or QT has changed, and ``p["T"]`` is K12's slab mean of the
-    cells' temperature; tests/les_thermo_ref.py holds the NumPy twin of that mode."""
+    cells' temperature; tests/les_thermo_ref.py holds the NumPy twin of that mode.
+    ``get_water_paths_batched`` reduces the fields along k instead (K13, ``Engine.les_water_paths``): the column water paths
+    LWP, TWP and RWP, [n x itot x jtot] device tensors, and the cloud cover; tests/les_water_paths_ref.py holds their twin."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
     STEP_KEYS = ("U", "V", "THL", "QT")                # fields a step applies a tendency to
     fused_advance = True                               # evolve_model_batched: one K11 launch (False: torch ops + K10)
     FUSED_MIN_LES = 128                                # ... where a launch holds at least so many LES (DESIGN.md 7.3)
+    WATER_PATHS = {"LWP": "QL", "TWP": "QT", "RWP": "QR"}     # les.get_field(name) -> the 3-D field it is the column sum of
 
     def __init__(self, grid_indices, zf, zh, prof, itot=8, jtot=8, engine=None):
         super().__init__(grid_indices, zf, zh, prof)
@@ -673,6 +684,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.engine = engine                            # None: spcpl.get_engine() when first needed
         self.fields3d = {}
         self._means = None                              # host slab means of the fields as they are now, or None
+        self._wp, self._wp_host, self._wp_w = None, {}, None      # K13's results of the fields as they are now; its weights
 
     # -- saturation adjustment (K12), opt-in -------------------------------------------------------------------------
     thermo = False                                     # enable_thermo(): Qsat and QL follow THL, QT and presf
@@ -711,6 +723,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         with eng.on_stream():
             self._thermo_means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
         self.p.update(self._thermo_means)
+        self._drop_water_paths()                        # QL is new
         if self._means is not None:
             self._means["QL"] = self._thermo_means["QL"]
         self._thermo_stale = False
@@ -787,6 +800,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.itot, self.jtot = int(shape[1]), int(shape[2])
         self.fields3d[name] = values
         self._means = None
+        self._drop_water_paths()
         self._thermo_stale = True                       # (K12 writes Qsat and QL in place, not through here)
 
     def set_field_row(self, i, name, values):
@@ -817,6 +831,74 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                 self._means["QL"] = self._thermo_means["QL"]
             self.p.update(self._means)
         return self._means
+
+    # -- column water paths (K13) ------------------------------------------------------------------------------------------
+    def _drop_water_paths(self):
+        self._wp, self._wp_host = None, {}
+
+    def water_path_weights(self):
+        """host float64 [n x nL]: Rhobf * dz, dz the thickness of the LES layers from the half levels zh (the lower faces):
+        dz[k] = zh[k + 1] - zh[k]; the top layer has no upper half level and takes the thickness of the layer below it,
+        dz[nL - 1] = dz[nL - 2]; an LES of one level takes twice the distance of its full level from its half level"""
+        zh = numpy.asarray(self.zh_cache, dtype=numpy.float64)
+        if self.nL > 1:
+            dz = numpy.diff(zh, axis=-1)
+            dz = numpy.concatenate([dz, dz[..., -1:]], axis=-1)
+        else:
+            dz = 2.0 * (numpy.asarray(self.zf_cache, dtype=numpy.float64) - zh)
+        return numpy.asarray(self.p["Rhobf"], dtype=numpy.float64) * dz
+
+    def get_water_paths_batched(self, names=("LWP", "TWP", "RWP"), cloud_cover=False):
+        """dict name -> device tensor [n x itot x jtot] (Sharded row blocks under a MultiDeviceEngine) of the column water
+        paths ``numpy.add.reduce(field * w[:, None, None, :], axis=3)``, w = ``water_path_weights()`` in the engine's dtype:
+        LWP of the QL field (after K12 where thermo is enabled and stale), TWP of QT, RWP of an attached QR field.  A name
+        whose field the ensemble does not hold is left out; KeyError where none is left.  ``cloud_cover`` adds ``"top"``
+        (int32: the highest cloudy level of QL per column, -1 for none) and ``"cover"`` ([n]: the fraction of cloudy
+        columns).  What is not cached goes through ONE launch per device; the results are cached until a field changes."""
+        unknown = [k for k in names if k not in self.WATER_PATHS]
+        if unknown:
+            raise KeyError("no water path %s (there are %s)" % (unknown, sorted(self.WATER_PATHS)))
+        f = self.fields3d
+        if ("LWP" in names or cloud_cover) and (self.thermo or "QL" in f or ("QT" in f and "Qsat" in f)):
+            self._ensure_ql()
+        have = [k for k in names if self.WATER_PATHS[k] in f]
+        if not have or (cloud_cover and "QL" not in f):
+            raise KeyError("the ensemble holds no field for %s" % ("the cloud cover (QL)" if have else list(names)))
+        w = numpy.ascontiguousarray(self.water_path_weights())
+        if self._wp_w is None or not numpy.array_equal(self._wp_w[0], w):
+            self._wp_w = (w, self._upload(w))                       # .astype(T) of the float64 product
+            self._drop_water_paths()                                # results of other weights (p["Rhobf"] was set) are stale
+        cache = self._wp if self._wp is not None else {}
+        need = [k for k in have if k not in cache]
+        cloud = cloud_cover and "cover" not in cache
+        out = None
+        if cloud and "LWP" not in need:                             # the cloud pass walks QL: LWP comes with it, ...
+            need.insert(0, "LWP")
+            if "LWP" in cache:                                      # ... again into its cached tensor where there is one
+                out = {"LWP": cache["LWP"]}
+        if need:
+            cache.update(self._eng().les_water_paths({k: f[self.WATER_PATHS[k]] for k in need}, self._wp_w[1],
+                                                     cloud="LWP" if cloud else None, out=out, top=cloud, cover=cloud))
+            self._wp = cache
+            for k in need:
+                self._wp_host.pop(k, None)
+        return {k: cache[k] for k in have + (["top", "cover"] if cloud_cover else [])}
+
+    def _water_path_host(self, name):
+        if name not in self._wp_host or self._wp is None or name not in self._wp:
+            t = self.get_water_paths_batched((name,))[name]
+            with self._eng().on_stream():
+                self._wp_host[name] = numpy.asarray(self._host(t))
+        return self._wp_host[name]
+
+    def get_water_path_means(self, names=("LWP", "TWP", "RWP")):
+        """host dict name -> [n]: ``wp[l].mean()`` of every LES, bit for bit: K10's slab means of the 2-D result viewed as
+        [n x itot x jtot x 1] (a one-level field is one contiguous run per LES, which NumPy sums pairwise)"""
+        wp = self.get_water_paths_batched(names)
+        eng = self._eng()
+        dev = eng.slab_means({k: self._per_device(lambda t: t.unsqueeze(-1), v) for k, v in wp.items()})
+        with eng.on_stream():
+            return {k: numpy.asarray(self._host(v))[:, 0] for k, v in dev.items()}
 
     # -- batched protocol ----------------------------------------------------------------------------------------------
     @_timed
@@ -869,6 +951,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if dt <= 0:
             return
         f, p = self.fields3d, self.p
+        self._drop_water_paths()
         if self._fused_step(dt):
             pass                                          # K11: fields, QL and p[U, V, THL, QT, QL] from one launch
         else:

@@ -235,6 +235,11 @@ class MultiDeviceEngine:
         block), dict of Sharded [n x ktot] slab means of QL and T out; one launch per device that holds rows"""
         return self._run("les_thermo", thl, qt, presf, ex, n_iter=n_iter, qsat=qsat, ql=ql, temp=temp, means=means, **kw)
 
+    def les_water_paths(self, fields, w, cloud=None, out=None, top=False, cover=False, **kw):
+        """K13 on every device's LES: dict of Sharded fields and the Sharded weight profile [n x ktot] in, dict of Sharded
+        [n x itot x jtot] water paths (with ``"top"`` and ``"cover"`` [n] where asked) out; one launch per device that holds rows"""
+        return self._run("les_water_paths", fields, w, cloud=cloud, out=out, top=top, cover=cover, **kw)
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

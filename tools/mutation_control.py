@@ -13,6 +13,8 @@ ADVANCE_MUTANTS is the table of K11 (spc_advance.hpp), numbered on its own and c
 bodies of tests/les_advance_ref.py, which tests/test_les_advance_gpu.py runs on the shipped library.
 THERMO_MUTANTS is the table of K12 (spc_thermo.hpp), chosen with --thermo; its guards are the bodies of
 tests/les_thermo_ref.py, which tests/test_les_thermo_gpu.py runs on the shipped library.
+WATERPATH_MUTANTS is the table of K13 (spc_waterpath.hpp), chosen with --waterpath; its guards are the bodies of
+tests/les_water_paths_ref.py, which tests/test_les_water_paths_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
@@ -24,6 +26,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --only 28 29 30 31 32 33 34 35 > profiles/mutation_control_slab.log
        python tools/mutation_control.py --advance --build && python tools/mutation_control.py --advance > profiles/mutation_control_advance.log
        python tools/mutation_control.py --thermo --build && python tools/mutation_control.py --thermo > profiles/mutation_control_thermo.log
+       python tools/mutation_control.py --waterpath --build && python tools/mutation_control.py --waterpath > profiles/mutation_control_waterpath.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log"""
 import argparse
@@ -44,6 +47,7 @@ K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp"
 SLAB = "spc_slab.hpp"
 ADVANCE = "spc_advance.hpp"
 THERMO = "spc_thermo.hpp"
+WATERPATH = "spc_waterpath.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -231,6 +235,66 @@ THERMO_MUTANTS = {
 }
 
 
+def waterpath_body(name):
+    """guard of a K13 mutant: the body ``name`` of tests/les_water_paths_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_water_paths_ref as wpr
+        failed = []
+        for dtype in wpr.DTYPES:
+            failed += wpr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_water_paths_ref." + name
+    return guard
+
+
+# K13 (spc_waterpath.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 6 reads the weight row of the LES before, LES 0 its own; mutant 8 adds to cover[0], inside the output).  A row offset truncated to 32 bits
+# is not in the table: it shows only in a field of more than 2^31 elements, where it reads in front of the field.
+_WP_SEQ = """    if (n <= WP_MAXK) {                                      // (mutant) the k loop
+        T res = T(0);
+        for (int i = 0; i < n; ++i) {
+            const T x = ldg(a + lo + i);
+            res += x * ldg(w + lo + i);
+            top = x > T(0) ? lo + i : top;
+        }
+        return res;
+    }
+    const int n8 = n - (n % 8);"""
+WATERPATH_MUTANTS = {
+    1: ("K13 sum: the row summed in order of k instead of pairwise with eight accumulators", waterpath_body("parity"),
+        [(WATERPATH, "    const int n8 = n - (n % 8);", _WP_SEQ)]),
+    2: ("K13 product: field * w contracted into the add (one rounding, an fma, instead of two)", waterpath_body("parity"),
+        [(WATERPATH, "        rj += x * ldg(w + k);", "        rj = __builtin_fma(x, ldg(w + k), rj);"),
+         (WATERPATH, "rj += x0 * w0; rj += x1 * w1; rj += x2 * w2; rj += x3 * w3;",
+          "rj = __builtin_fma(x0, w0, rj); rj = __builtin_fma(x1, w1, rj); rj = __builtin_fma(x2, w2, rj); rj = __builtin_fma(x3, w3, rj);")]),
+    3: ("K13 tree: the split point n2 = n / 2 not rounded down to a multiple of 8", waterpath_body("parity"),
+        [(WATERPATH, "        n2 -= n2 % 8;\n        const T left", "        const T left"),
+         (WATERPATH, "                n2 -= n2 % 8;\n                s_right", "                s_right")]),
+    4: ("K13 cloud test: field >= 0 instead of field > 0 (zeros and -0.0 are cloudy)", waterpath_body("cloud"),
+        [(WATERPATH, "x > T(0) ? lo + i : top;", "x >= T(0) ? lo + i : top;", 2),
+         (WATERPATH, "top = v0 > T(0) ? lo + j : top;", "top = v0 >= T(0) ? lo + j : top;"),
+         (WATERPATH, "top = x > T(0) ? k : top;", "top = x >= T(0) ? k : top;"),
+         (WATERPATH, "top = x0 > T(0) ? k : top; top = x1 > T(0) ? k + 8 : top; top = x2 > T(0) ? k + 16 : top; top = x3 > T(0) ? k + 24 : top;",
+          "top = x0 >= T(0) ? k : top; top = x1 >= T(0) ? k + 8 : top; top = x2 >= T(0) ? k + 16 : top; top = x3 >= T(0) ? k + 24 : top;")]),
+    5: ("K13 top: taken from the lowest cloudy k instead of the highest", waterpath_body("cloud"),
+        [(WATERPATH, "x > T(0) ? lo + i : top;", "x > T(0) && top < 0 ? lo + i : top;", 2),
+         (WATERPATH, "top = v0 > T(0) ? lo + j : top;", "top = v0 > T(0) && top < 0 ? lo + j : top;"),
+         (WATERPATH, "top = x > T(0) ? k : top;", "top = x > T(0) && top < 0 ? k : top;"),
+         (WATERPATH, "top = x0 > T(0) ? k : top; top = x1 > T(0) ? k + 8 : top; top = x2 > T(0) ? k + 16 : top; top = x3 > T(0) ? k + 24 : top;",
+          "top = x0 > T(0) && top < 0 ? k : top; top = x1 > T(0) && top < 0 ? k + 8 : top; top = x2 > T(0) && top < 0 ? k + 16 : top; "
+          "top = x3 > T(0) && top < 0 ? k + 24 : top;"),
+         (WATERPATH, "    top = max(top, __shfl_xor(top, 1));\n    top = max(top, __shfl_xor(top, 2));\n    top = max(top, __shfl_xor(top, 4));",
+          "    for (int m = 1; m < 8; m <<= 1) { const int o = __shfl_xor(top, m); top = top < 0 ? o : (o < 0 ? top : min(top, o)); }")]),
+    6: ("K13 weights: the row of LES l - 1 (LES 0 keeps its own)", waterpath_body("parity"),
+        [(WATERPATH, "const T *const wr = p.w + l * p.pitch_w;", "const T *const wr = p.w + (l > 0 ? l - 1 : 0) * p.pitch_w;")]),
+    7: ("K13 cover: the count divided by itot * jtot + 1", waterpath_body("cloud"),
+        [(WATERPATH, "p.cover[l] = (T)c / (T)p.nij;", "p.cover[l] = (T)c / (T)(p.nij + 1);")]),
+    8: ("K13 cover: a dead group of a wave counts as LES 0 (the row it walks on), so a wave of fewer than 8 live rows over several "
+        "LES adds them all to the first", waterpath_body("few_rows"),
+        [(WATERPATH, "const int64_t lc = live ? l : -1;", "const int64_t lc = l;")]),
+}
+
+
 def geo_body(name):
     """guard of a K8 mutant: the body ``name`` of tests/geo_edges.py on the float64 engine of the library (K8 is float64 on
     every engine)"""
@@ -414,7 +478,8 @@ def patched(n, src=CSRC, table=None):
 
 def _tag(table):
     """(library prefix, source directory prefix) of a table"""
-    for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (GEO_MUTANTS, ("geo_", "geo")),
+    for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
+                   (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq"))):
         if table is t:
@@ -586,10 +651,11 @@ if __name__ == "__main__":
     ap.add_argument("-j", type=int, default=4, help="parallel compiles for --build (at most 16)")
     ap.add_argument("--advance", action="store_true", help="the table of K11 (ADVANCE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--thermo", action="store_true", help="the table of K12 (THERMO_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--waterpath", action="store_true", help="the table of K13 (WATERPATH_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
-    table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else GEO_MUTANTS if args.geo
+    table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -609,4 +675,6 @@ if __name__ == "__main__":
                               equivalent=LESSTATE_EQUIVALENT, old_guards={n: lesstate_old_guard for n in LESSTATE_OLD_GUARDS}))
     if args.thermo:
         sys.exit(main_advance(only, THERMO_MUTANTS, "K12", "les_thermo"))
+    if args.waterpath:
+        sys.exit(main_advance(only, WATERPATH_MUTANTS, "K13", "les_water_paths"))
     sys.exit((main_advance if args.advance else main)(only))
