@@ -503,6 +503,53 @@ typedef spc_water_path_args SpcWaterPathArgs;
 int spc_les_water_paths_f64(const spc_water_path_args *args, void *stream);
 int spc_les_water_paths_f32(const spc_water_path_args *args, void *stream);
 
+/* ---- warm-rain microphysics of the device-resident LES fields, with the slab means of what it changes (kernel family K14) --- */
+/* Cloud water turns into rain (autoconversion above the threshold qc0, accretion by the rain that is there), rain falls one
+ * upwind step and what leaves the lowest level is added to the surface rain; the cloud ice is a share of the remaining cloud
+ * water that is linear in the temperature between t_dn and t_up.  Fields are [n_les][itot][jtot][ktot] (layout and offsets as
+ * K10), element type T; every operation is rounded once in T, never an fma.  Profiles are [n_les x ktot], rows pitch_prof
+ * apart: sed_out (the share of a layer's rain that leaves it in dt, 0 ... 1), sed_in (the same flux expressed in the layer
+ * below), lcpex ((rlv / cp) / exner) and w (rho * dz, K13's weight profile); sp_coupler_amd/microphysics.py builds them.
+ * Scalars, rounded to T once: qc0 = T(qc0), ka = T(T(k_auto) * T(dt)), kc = T(T(k_acc) * T(dt)), tu = T(t_up), td = T(t_dn),
+ * den = tu - td.  Per cell (l, i, j, k), with qr_up = k + 1 < ktot ? qr[l][i][j][k + 1] : +0.0 (the OLD qr):
+ *   out  = sed_out[l][k] * qr
+ *   qs   = (qr - out) + sed_in[l][k] * qr_up                  sedimentation, upwind, the old qr on both sides
+ *   d    = ql - qc0;   x = d > 0 ? d : (d != d ? d : +0.0)    the q rule of spc_les_advance_*
+ *   s    = ka * x + (kc * ql) * qs                            autoconversion + accretion: product, product, one add
+ *   s    = s > ql ? ql : s                                    never more than the cloud water; NaN stays NaN
+ *   qt   = qt - s                                             IN PLACE
+ *   thl  = thl + lcpex[l][k] * s                              IN PLACE, where thl != NULL
+ *   qr_new[l][i][j][k] = qs + s                               a SEPARATE buffer: the neighbour below reads the old qr
+ *   rain[l][i][j] = rain[l][i][j] + (sed_out[l][0] * qr[l][i][j][0]) * w[l][0]      IN PLACE, where rain != NULL
+ *   fi   = temp >= tu ? 0 : (temp <= td ? 1 : (tu - temp) / den)                    where temp != NULL
+ *   qi   = (ql - s) * fi
+ *   qt_mean, thl_mean, qr_mean, qi_mean [l * pitch_mean + k] = the slab means of the NEW qt, the NEW thl, qr_new and qi by
+ *       spc_slab_means_*'s rule, bit for bit (sequential sum from +0 over (i, j) in row-major order in T, one division);
+ *       each where its pointer != NULL.
+ * ql, qr and temp are read only.  lcpex is required with thl, w with rain; thl_mean needs thl, qi_mean needs temp.  qr_new
+ * must not be any other argument, no written array may be another written array or an input: SPC_ERR_INVALID_ARGUMENT
+ * where two such pointers are EQUAL; arrays that overlap in part are not detected and must not be passed.
+ * ktot == 1 is SPC_ERR_UNSUPPORTED, as in spc_les_advance_*.  The rule is this library's definition.     */
+typedef struct spc_les_micro_args {
+    int64_t n_les;                 /* 0 is allowed: no-op                                                  */
+    int32_t itot, jtot, ktot;
+    int32_t reserved;              /* 0                                                                    */
+    void *qt;                      /* device [n_les][itot][jtot][ktot], updated in place                   */
+    const void *ql, *qr;           /* device [n_les][itot][jtot][ktot], read only                          */
+    void *qr_new;                  /* device [n_les][itot][jtot][ktot], written whole                      */
+    void *thl;                     /* device [n_les][itot][jtot][ktot], updated in place, or NULL          */
+    const void *temp;              /* device [n_les][itot][jtot][ktot], read only, or NULL                 */
+    void *rain;                    /* device [n_les][itot][jtot], contiguous, updated in place, or NULL    */
+    const void *sed_out, *sed_in;  /* device [n_les x ktot] each, rows pitch_prof apart                    */
+    const void *lcpex, *w;         /* the same; lcpex may be NULL without thl, w without rain              */
+    int64_t pitch_prof;            /* >= ktot                                                              */
+    double dt, qc0, k_auto, k_acc, t_up, t_dn;   /* rounded to the element type as stated above            */
+    void *qt_mean, *thl_mean, *qr_mean, *qi_mean; /* device [n_les x ktot] each, rows pitch_mean apart, or NULL */
+    int64_t pitch_mean;            /* >= ktot                                                              */
+} spc_les_micro_args;
+int spc_les_microphysics_f64(const spc_les_micro_args *args, void *stream);
+int spc_les_microphysics_f32(const spc_les_micro_args *args, void *stream);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */
 const char *spc_last_error(void);   /* text of the calling thread's last failure ("" if none)     */

@@ -137,6 +137,13 @@ class WaterPathArgs(ctypes.Structure):
                  ("cloud_field", c_int32), ("reserved", c_int32)] + _ptrs("top", "cover"))
 
 
+class LesMicroArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("reserved", c_int32)]
+                + _ptrs("qt", "ql", "qr", "qr_new", "thl", "temp", "rain", "sed_out", "sed_in", "lcpex", "w") + [("pitch_prof", c_int64)]
+                + [(k, c_double) for k in ("dt", "qc0", "k_auto", "k_acc", "t_up", "t_dn")]
+                + _ptrs("qt_mean", "thl_mean", "qr_mean", "qi_mean") + [("pitch_mean", c_int64)])
+
+
 THERMO_TABLE_LIBRARY, THERMO_TABLE_LDS, THERMO_TABLE_GLOBAL = 0, 1, 2      # spc_les_thermo_args.table_mode
 
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
@@ -183,6 +190,8 @@ PROTOTYPES = {
     "spc_les_thermo_f32": (ctypes.c_int, [ctypes.POINTER(LesThermoArgs), c_void_p]),
     "spc_les_water_paths_f64": (ctypes.c_int, [ctypes.POINTER(WaterPathArgs), c_void_p]),
     "spc_les_water_paths_f32": (ctypes.c_int, [ctypes.POINTER(WaterPathArgs), c_void_p]),
+    "spc_les_microphysics_f64": (ctypes.c_int, [ctypes.POINTER(LesMicroArgs), c_void_p]),
+    "spc_les_microphysics_f32": (ctypes.c_int, [ctypes.POINTER(LesMicroArgs), c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

@@ -23,6 +23,9 @@
 //                  saturation-pressure table) and the slab means of QL and T in one pass: spc_thermo.hpp, kernel and host side
 //   K13 k_les_water_paths  column water paths of those fields (numpy.add.reduce(field * w) along k, pairwise as ndarray.sum()),
 //                  with the cloud top and the cloud cover, in one pass: spc_waterpath.hpp, kernel and host side
+//   K14 k_les_microphysics  warm-rain microphysics of those fields (autoconversion, accretion, one upwind step of sedimentation,
+//                  the surface rain, the cloud ice) and the slab means of QT, THL, QR and QI in one pass: spc_micro.hpp, kernel
+//                  and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -74,6 +77,7 @@ namespace {
 #include "spc_advance.hpp"
 #include "spc_thermo.hpp"
 #include "spc_waterpath.hpp"
+#include "spc_micro.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -93,6 +97,9 @@ namespace {
 #define SPC_WATERPATH_HOST
 #include "spc_waterpath.hpp"
 #undef SPC_WATERPATH_HOST
+#define SPC_MICRO_HOST
+#include "spc_micro.hpp"
+#undef SPC_MICRO_HOST
 
 }  // namespace
 
@@ -165,6 +172,9 @@ int spc_les_thermo_f32(const spc_les_thermo_args *a, void *s) { return les_therm
 
 int spc_les_water_paths_f64(const spc_water_path_args *a, void *s) { return water_paths_impl<double>(a, s); }
 int spc_les_water_paths_f32(const spc_water_path_args *a, void *s) { return water_paths_impl<float>(a, s); }
+
+int spc_les_microphysics_f64(const spc_les_micro_args *a, void *s) { return les_micro_impl<double>(a, s); }
+int spc_les_microphysics_f32(const spc_les_micro_args *a, void *s) { return les_micro_impl<float>(a, s); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

@@ -777,6 +777,72 @@ class Engine:
         self._call(fn, ctypes.byref(a), stream=stream)
         return res
 
+    # -- K14: warm-rain microphysics of device-resident LES fields and the slab means of what it changes, one launch ------
+    @_on_engine_stream
+    def les_microphysics(self, qt, ql, qr, qr_new, sed_out, sed_in, lcpex, w, dt, thl=None, temp=None, rain=None, means=True,
+                         qc0=None, k_auto=None, k_acc=None, t_up=None, t_dn=None, stream=None):
+        """One step of the warm-rain microphysics (include/spc.h has the rule) on contiguous device fields
+        [n x itot x jtot x ktot]: cloud water ``ql`` (read only) above ``qc0`` and next to rain turns into rain, the rain
+        ``qr`` (read only) falls one upwind step; ``qt`` (and ``thl`` where given) are updated IN PLACE, the new rain is written
+        to ``qr_new`` (another tensor than ``qr``), what leaves level 0 is added to ``rain`` [n x itot x jtot] where given.
+        ``sed_out``, ``sed_in``, ``lcpex``, ``w`` [n x ktot] are ``microphysics.profiles`` in the engine's dtype (rows may be
+        pitched, all with one pitch).  With ``temp`` (the cells' temperature, read only) the cloud ice is formed as well.
+        Returns the slab means [n x ktot] of the new fields (``Engine.slab_means``' rule, bit for bit): ``{"QT", "QR"}``, ``"THL"``
+        with ``thl`` and ``"QI"`` with ``temp``; ``means``: True, a dict of tensors to write into (pitched as in
+        ``slab_means``), or False (no means: {}).  The constants default to those of ``microphysics``.  A written tensor that
+        STARTS where another argument starts is refused (ValueError); views that overlap in part are not detected.  One launch; ktot == 1 is
+        refused (SPC_ERR_UNSUPPORTED)."""
+        from . import microphysics as mp
+        shape = tuple(self._field4("qt", qt).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_microphysics: empty field shape %s" % (shape,))
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.LesMicroArgs()
+        a.n_les, a.itot, a.jtot, a.ktot, a.dt = n, itot, jtot, ktot, float(dt)
+        for name, v, d in (("qc0", qc0, mp.QC0), ("k_auto", k_auto, mp.K_AUTO), ("k_acc", k_acc, mp.K_ACC), ("t_up", t_up, mp.T_UP),
+                           ("t_dn", t_dn, mp.T_DN)):
+            setattr(a, name, float(d if v is None else v))
+        fields = {"qt": qt, "ql": ql, "qr": qr, "qr_new": qr_new, "thl": thl, "temp": temp}
+        for name, t in fields.items():
+            if t is not None:
+                setattr(a, name, self._field4(name, t, shape).data_ptr())
+            elif name not in ("thl", "temp"):
+                raise ValueError("les_microphysics: %s is required" % name)
+        a.sed_out, a.pitch_prof = ck.mat("sed_out", sed_out, n, ktot)
+        profs = {"sed_out": sed_out, "sed_in": sed_in, "lcpex": lcpex, "w": w}
+        for name in ("sed_in", "lcpex", "w"):
+            ptr, _ = ck.mat(name, profs[name], n, ktot, pitch=a.pitch_prof)
+            setattr(a, name, ptr)
+        if rain is not None:
+            if not isinstance(rain, torch.Tensor) or rain.device != self.device or rain.dtype != self.dtype or \
+                    tuple(rain.shape) != (n, itot, jtot) or not rain.is_contiguous():
+                raise ValueError("les_microphysics: rain must be a contiguous %s tensor of shape %s on %s" % (self.dtype, (n, itot, jtot), self.device))
+            a.rain = rain.data_ptr()
+        res, a.pitch_mean = {}, ktot
+        if means is not False and means is not None:
+            given = means if isinstance(means, dict) else {}
+            names = ["QT", "QR"] + (["THL"] if thl is not None else []) + (["QI"] if temp is not None else [])
+            unknown = [k for k in given if k not in names]
+            if unknown:
+                raise ValueError("les_microphysics: means of %s are not computed (%s are)" % (unknown, names))
+            pitch = None
+            for k in names:
+                res[k], p = self._out(given.get(k), n, ktot)
+                if pitch is not None and n > 1 and p != pitch:
+                    raise ValueError("les_microphysics: means[%s] has row pitch %d, the others %d" % (k, p, pitch))
+                pitch = p
+                setattr(a, {"QT": "qt_mean", "QR": "qr_mean", "THL": "thl_mean", "QI": "qi_mean"}[k], res[k].data_ptr())
+            a.pitch_mean = pitch
+        if n:
+            written = [t.data_ptr() for t in [qt, qr_new, thl, rain] + list(res.values()) if t is not None]
+            read = [t.data_ptr() for t in [ql, qr, temp] + list(profs.values()) if t is not None]
+            if len(set(written)) != len(written) or set(written) & set(read):
+                raise ValueError("les_microphysics: a written array is an input or another written array (qr_new must not be qr)")
+        fn = self.lib.spc_les_microphysics_f32 if self.dtype == torch.float32 else self.lib.spc_les_microphysics_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

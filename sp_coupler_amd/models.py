@@ -669,7 +669,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     ``Engine.les_thermo``: DESIGN.md 7.3), redone whenever THL or QT has changed, and ``p["T"]`` is K12's slab mean of the
     cells' temperature; tests/les_thermo_ref.py holds the NumPy twin of that mode.
     ``get_water_paths_batched`` reduces the fields along k instead (K13, ``Engine.les_water_paths``): the column water paths
-    LWP, TWP and RWP, [n x itot x jtot] device tensors, and the cloud cover; tests/les_water_paths_ref.py holds their twin."""
+    LWP, TWP and RWP, [n x itot x jtot] device tensors, and the cloud cover; tests/les_water_paths_ref.py holds their twin.
+    After ``enable_microphysics()`` every step ends with the warm-rain microphysics (K14, ``Engine.les_microphysics``): cloud
+    water turns into rain, the QR field falls, ``rain2d`` collects what reaches the ground and ``p["Rain"]`` is its plane mean;
+    tests/les_micro_ref.py holds the twin of that mode."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
@@ -718,8 +721,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         for k in ("Qsat", "QL"):
             if k not in f:
                 f[k] = self._per_device(torch.empty_like, f["QT"])          # written whole by the launch
+        if self.micro and "T" not in f:                 # K14 reads the cells' temperature for the cloud ice
+            f["T"] = self._per_device(torch.empty_like, f["QT"])
         dev = eng.les_thermo(f["THL"], f["QT"], self._thermo_prof[1], self._thermo_prof[2], n_iter=self.thermo_n_iter,
-                             qsat=f["Qsat"], ql=f["QL"])
+                             qsat=f["Qsat"], ql=f["QL"], **({"temp": f["T"]} if self.micro else {}))
         with eng.on_stream():
             self._thermo_means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
         self.p.update(self._thermo_means)
@@ -727,6 +732,88 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if self._means is not None:
             self._means["QL"] = self._thermo_means["QL"]
         self._thermo_stale = False
+
+    # -- warm-rain microphysics (K14), opt-in -------------------------------------------------------------------------
+    micro = False                                      # enable_microphysics(): QR, rain2d and p["Rain"] follow the cloud water
+    micro_par = None                                   # v_fall, qc0, k_auto, k_acc
+    rain2d = None                                      # device [n x itot x jtot]: the rain that has reached the ground, kg/m2
+    _qr_spare = None                                   # the QR buffer K14 writes next (it reads the other one)
+    _micro_prof = None                                 # ((dt, v_fall, host presf, Rhobf, zh, zf) of the upload, the four device profiles)
+
+    def enable_microphysics(self, v_fall=None, qc0=None, k_auto=None, k_acc=None):
+        """from now on every ``evolve_model_batched`` ends with ONE K14 launch per device (``Engine.les_microphysics``,
+        DESIGN.md 7.3) on the stepped fields and the current QL: cloud water turns into rain (QT and THL in place), the QR
+        field falls one upwind step, what reaches the ground is summed in ``rain2d`` [n x itot x jtot], whose plane mean is
+        ``p["Rain"]``; p["QT"], p["THL"] and p["QR"] are the launch's slab means, and with ``enable_thermo()`` p["QL_ice"] is the
+        mean of the cloud ice at the cells' temperature.  Needs a QT field and more than one level; a QR field is created,
+        zero, where none is attached.  The cloud water must be able to follow the QT the launch changes: a step needs an
+        attached Qsat field or ``enable_thermo()`` (ValueError otherwise, also with an attached QL alone).  The profiles are
+        uploaded again whenever dt, v_fall, presf, Rhobf or the grid (zh, zf) changed.  The constants default to those of ``microphysics``.  Without this call every path of
+        the ensemble is unchanged."""
+        import torch
+        from . import microphysics as mp
+        if self.nL == 1:
+            raise ValueError("the microphysics (K14) does not take LES of one level")
+        if "QT" not in self.fields3d:
+            raise ValueError("the microphysics (K14) needs a QT field (set_fields_batched)")
+        if not all(callable(getattr(e, "les_microphysics", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
+            raise ValueError("the engine has no les_microphysics (K14)")
+        f = self.fields3d
+        if "QR" not in f:
+            f["QR"] = self._per_device(torch.zeros_like, f["QT"])
+        self._qr_spare = self._per_device(torch.empty_like, f["QT"])
+        self.rain2d = self._per_device(lambda t: t.new_zeros(t.shape[:3]), f["QT"])
+        self.micro_par = {"v_fall": mp.V_FALL if v_fall is None else float(v_fall), "qc0": mp.QC0 if qc0 is None else float(qc0),
+                          "k_auto": mp.K_AUTO if k_auto is None else float(k_auto), "k_acc": mp.K_ACC if k_acc is None else float(k_acc)}
+        self.micro, self._micro_prof = True, None
+        self._thermo_stale = True                         # (K12's next launch also writes the cells' temperature)
+        self._drop_water_paths()
+
+    def _microphysics(self, dt):
+        """K14 on the stepped fields: QT, THL, QR, rain2d and their profiles; QL (and Qsat) are then those of the new QT and THL"""
+        import torch
+        from . import microphysics as mp
+        eng, f, p, par = self._eng(), self.fields3d, self.p, self.micro_par
+        if self.n == 0:
+            return
+        if not (self.thermo or "Qsat" in f):              # (an attached QL without Qsat could not follow the QT this step changes)
+            raise ValueError("the microphysics (K14) needs the cloud water of the current QT: a Qsat field, or enable_thermo()")
+        self._ensure_ql()                                 # (thermo: K12 where stale, with the cells' temperature in f["T"])
+        # everything the profiles are made of; the four [n x nL] / [nL] host arrays are copied and compared every step (kilobytes)
+        key = (float(dt), par["v_fall"]) + tuple(numpy.array(a, dtype=numpy.float64) for a in (p["presf"], p["Rhobf"], self.zh_cache, self.zf_cache))
+        if self._micro_prof is None or self._micro_prof[0][:2] != key[:2] or not all(
+                a.shape == b.shape and numpy.array_equal(a, b) for a, b in zip(self._micro_prof[0][2:], key[2:])):
+            prof = mp.profiles(key[4], key[5], key[3], key[2], dt, par["v_fall"])
+            self._micro_prof = (key, [self._upload(a) for a in prof])
+        if self._qr_spare is None or self._qr_spare is f["QR"] or tuple(self._qr_spare.shape) != tuple(f["QT"].shape):
+            self._qr_spare = self._per_device(torch.empty_like, f["QT"])
+        temp = f.get("T") if self.thermo else None
+        dev = eng.les_microphysics(f["QT"], f["QL"], f["QR"], self._qr_spare, *self._micro_prof[1], dt, thl=f.get("THL"), temp=temp,
+                                   rain=self.rain2d, qc0=par["qc0"], k_auto=par["k_auto"], k_acc=par["k_acc"])
+        f["QR"], self._qr_spare = self._qr_spare, f["QR"]
+        rain = eng.slab_means({"Rain": self._per_device(lambda t: t.unsqueeze(-1), self.rain2d)})["Rain"]
+        with eng.on_stream():
+            m = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
+            p["Rain"] = numpy.asarray(self._host(rain), dtype=numpy.float64)[:, 0]
+        p["QR"] = m["QR"]
+        if "QI" in m:
+            p["QL_ice"] = m["QI"]
+        own = {k: m[k] for k in ("QT", "THL") if k in m}
+        p.update(own)
+        if self._means is not None:
+            self._means.update(own)
+        self._drop_water_paths()
+        self._thermo_stale = True                         # thermo: the tail of the step runs K12 on the new QT and THL
+        if not self.thermo and "Qsat" in f:
+            def saturate(ql, qt, qs):
+                torch.sub(qt, qs, out=ql)
+                return ql.clamp_min_(0.0)
+            self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
+            ql = eng.slab_means({"QL": f["QL"]})["QL"]
+            with eng.on_stream():
+                p["QL"] = numpy.asarray(self._host(ql), dtype=numpy.float64)
+            if self._means is not None:
+                self._means["QL"] = p["QL"]
 
     @classmethod
     def for_gcm(cls, gcm, grid_indices, nL=160, seed=0, itot=8, jtot=8, engine=None):
@@ -973,10 +1060,13 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             self._slab_means()                            # p[U, V, THL, QT, QL] = the slab means of the new fields
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
+        if self.micro:
+            self._microphysics(dt)                        # one K14 launch: QT, THL, QR, rain2d; p[QT, THL, QR, Rain(, QL_ice)]
         if self.thermo:
             self._ensure_thermo()                         # one K12 launch: the Qsat and QL fields, p["QL"] and p["T"]
         p["QL_ice"] = numpy.minimum(p["QL_ice"], p["QL"])
         if not (self.thermo and self._thermo_means is not None):
             p["T"] = p["THL"] * (p["presf"] / 1e5) ** (287.04 / 1004.) + 2.53e6 * p["QL"] / 1004.
-        p["Rain"] = p["Rain"] + 1e-6 * dt
+        if not self.micro:
+            p["Rain"] = p["Rain"] + 1e-6 * dt
         self.model_time = float(t)

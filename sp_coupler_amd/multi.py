@@ -240,6 +240,12 @@ class MultiDeviceEngine:
         [n x itot x jtot] water paths (with ``"top"`` and ``"cover"`` [n] where asked) out; one launch per device that holds rows"""
         return self._run("les_water_paths", fields, w, cloud=cloud, out=out, top=top, cover=cover, **kw)
 
+    def les_microphysics(self, qt, ql, qr, qr_new, sed_out, sed_in, lcpex, w, dt, thl=None, temp=None, rain=None, means=True, **kw):
+        """K14 on every device's LES: Sharded fields and [n x ktot] profiles in (``qt``, ``thl``, ``qr_new`` and ``rain`` written
+        block by block), dict of Sharded [n x ktot] slab means out; one launch per device that holds rows"""
+        return self._run("les_microphysics", qt, ql, qr, qr_new, sed_out, sed_in, lcpex, w, dt, thl=thl, temp=temp, rain=rain,
+                         means=means, **kw)
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

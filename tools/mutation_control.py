@@ -15,6 +15,8 @@ THERMO_MUTANTS is the table of K12 (spc_thermo.hpp), chosen with --thermo; its g
 tests/les_thermo_ref.py, which tests/test_les_thermo_gpu.py runs on the shipped library.
 WATERPATH_MUTANTS is the table of K13 (spc_waterpath.hpp), chosen with --waterpath; its guards are the bodies of
 tests/les_water_paths_ref.py, which tests/test_les_water_paths_gpu.py runs on the shipped library.
+MICRO_MUTANTS is the table of K14 (spc_micro.hpp), chosen with --micro; its guards are the bodies of
+tests/les_micro_ref.py, which tests/test_les_micro_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
@@ -27,6 +29,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --advance --build && python tools/mutation_control.py --advance > profiles/mutation_control_advance.log
        python tools/mutation_control.py --thermo --build && python tools/mutation_control.py --thermo > profiles/mutation_control_thermo.log
        python tools/mutation_control.py --waterpath --build && python tools/mutation_control.py --waterpath > profiles/mutation_control_waterpath.log
+       python tools/mutation_control.py --micro --build && python tools/mutation_control.py --micro > profiles/mutation_control_micro.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log"""
 import argparse
@@ -48,6 +51,7 @@ SLAB = "spc_slab.hpp"
 ADVANCE = "spc_advance.hpp"
 THERMO = "spc_thermo.hpp"
 WATERPATH = "spc_waterpath.hpp"
+MICRO = "spc_micro.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -295,6 +299,42 @@ WATERPATH_MUTANTS = {
 }
 
 
+def micro_body(name):
+    """guard of a K14 mutant: the body ``name`` of tests/les_micro_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_micro_ref as lmr
+        failed = []
+        for dtype in lmr.DTYPES:
+            failed += lmr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_micro_ref." + name
+    return guard
+
+
+# K14 (spc_micro.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 3 reads level 0 of the lane's own column; mutant 2 uses the lane's own new values, so it
+# shows where a lane owns more than one element).
+MICRO_MUTANTS = {
+    1: ("K14 s: the accretion product and the sum contracted to an fma", micro_body("parity"),
+        [(MICRO, "T s = P.ka * xx + (P.kc * ql) * qs;", "T s = (T)__builtin_fma((double)(P.kc * ql), (double)qs, (double)(P.ka * xx));")]),
+    2: ("K14 sedimentation: the NEW qr of the level above on the upwind side (the lane's own elements, top down)", micro_body("parity"),
+        [(MICRO, "    for (int v = 0; v < V; ++v) {\n        const T qr = x.qr.v[v], ql = x.ql.v[v];", "    for (int v = V - 1; v >= 0; --v) {\n        const T qr = x.qr.v[v], ql = x.ql.v[v];"),
+         (MICRO, "const T qu = v + 1 < V ? x.qr.v[v + 1 < V ? v + 1 : v] : x.up;", "const T qu = v + 1 < V ? nqr.v[v + 1 < V ? v + 1 : v] : x.up;")]),
+    3: ("K14 top level: qr_up is level 0 of the same column instead of +0.0", micro_body("neighbour"),
+        [(MICRO, "x.up = top ? (T)0 : P.qr[o + V];", "x.up = P.qr[top ? o + V - P.ktot : o + V];")]),
+    4: ("K14 cap: s >= ql takes ql, so s == +0.0 against ql == -0.0 becomes -0.0", micro_body("special"),
+        [(MICRO, "s = s > ql ? ql : s;", "s = s >= ql ? ql : s;")]),
+    5: ("K14 cloud ice: ql instead of ql - s", micro_body("parity"),
+        [(MICRO, "qi.v[v] = (ql - s) * fi;", "qi.v[v] = ql * fi;")]),
+    6: ("K14 surface rain: the flux out of the lane's second element (k == 1) instead of k == 0", micro_body("parity"),
+        [(MICRO, "if (v == 0) out0 = out;", "if (v == (V > 1 ? 1 : 0)) out0 = V > 1 ? out : (T)0;")]),
+    7: ("K14 means: the sums divided by itot * jtot + 1", micro_body("parity"),
+        [(MICRO, "const T cnt = (T)nij;", "const T cnt = (T)(nij + 1);")]),
+    8: ("K14 threshold: x without the NaN branch (shows with a NaN qc0: a NaN ql reaches s through the accretion anyway)", micro_body("special"),
+        [(MICRO, "const T xx = d > (T)0 ? d : (d != d ? d : (T)0);", "const T xx = d > (T)0 ? d : (T)0;")]),
+}
+
+
 def geo_body(name):
     """guard of a K8 mutant: the body ``name`` of tests/geo_edges.py on the float64 engine of the library (K8 is float64 on
     every engine)"""
@@ -479,6 +519,7 @@ def patched(n, src=CSRC, table=None):
 def _tag(table):
     """(library prefix, source directory prefix) of a table"""
     for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
+                   (MICRO_MUTANTS, ("micro_", "micro")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq"))):
@@ -652,10 +693,12 @@ if __name__ == "__main__":
     ap.add_argument("--advance", action="store_true", help="the table of K11 (ADVANCE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--thermo", action="store_true", help="the table of K12 (THERMO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--waterpath", action="store_true", help="the table of K13 (WATERPATH_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--micro", action="store_true", help="the table of K14 (MICRO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
-    table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else GEO_MUTANTS if args.geo
+    table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
+             else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -677,4 +720,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, THERMO_MUTANTS, "K12", "les_thermo"))
     if args.waterpath:
         sys.exit(main_advance(only, WATERPATH_MUTANTS, "K13", "les_water_paths"))
+    if args.micro:
+        sys.exit(main_advance(only, MICRO_MUTANTS, "K14", "les_micro"))
     sys.exit((main_advance if args.advance else main)(only))

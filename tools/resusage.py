@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Compile spc_hip.hip with -Rpass-analysis=kernel-resource-usage and print one line per kernel
-(VGPRs, SGPRs, spills, scratch, occupancy, LDS).  usage: tools/resusage.py [filter-substring] [extra hipcc flags...]"""
+(VGPRs, SGPRs, spills, scratch, occupancy, LDS).  usage: tools/resusage.py [filter-substring | entry] [extra hipcc flags...]
+An entry of ENTRIES names a kernel family that must use no scratch and spill nothing in any instantiation: its lines are
+printed and the exit status is 1 if one of them does (tools/resusage.py microphysics)."""
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-flt = sys.argv[1] if len(sys.argv) > 1 else ""
+ENTRIES = {"microphysics": "k_les_microphysics"}             # K14: every instantiation without scratch and without spills
+entry = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ENTRIES else None
+flt = ENTRIES[entry] if entry else sys.argv[1] if len(sys.argv) > 1 else ""
 extra = sys.argv[2:]
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
        "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "sp_coupler_amd/csrc/spc_hip.hip"), "-o", "/tmp/resusage.so",
@@ -25,9 +29,16 @@ for line in err.splitlines():
     m = re.search(r"remark:\s+(\w[\w \[\]/]*?): (\d+)", line)
     if m and cur:
         rows[cur][m.group(1).strip()] = int(m.group(2))
+bad = []
 for name, r in rows.items():
     if flt in name:
+        if entry and (r.get("ScratchSize [bytes/lane]", 0) or r.get("SGPRs Spill", 0) or r.get("VGPRs Spill", 0)):
+            bad.append(name)
         print("%-62s VGPR %3d AGPR %3d SGPR %3d spillS %3d spillV %3d scratch %4d occ %2d LDS %6d" % (
             name[:62], r.get("VGPRs", -1), r.get("AGPRs", 0), r.get("TotalSGPRs", r.get("SGPRs", -1)), r.get("SGPRs Spill", 0),
             r.get("VGPRs Spill", 0), r.get("ScratchSize [bytes/lane]", 0), r.get("Occupancy [waves/SIMD]", -1),
             r.get("LDS Size [bytes/block]", 0)))
+if entry:
+    shown = [n for n in rows if flt in n]
+    print("%s: %d instantiation(s), %s" % (entry, len(shown), "scratch or spills in %s" % bad if bad else "no scratch, no spill"))
+    sys.exit(1 if bad or not shown else 0)
