@@ -550,6 +550,39 @@ typedef struct spc_les_micro_args {
 int spc_les_microphysics_f64(const spc_les_micro_args *args, void *stream);
 int spc_les_microphysics_f32(const spc_les_micro_args *args, void *stream);
 
+/* ---- implicit vertical diffusion and surface fluxes of the device-resident LES fields (kernel family K15) -------------------- */
+/* One backward-Euler step of d(x)/dt = (1 / (rho dz)) d/dz (rho_h K dx/dz) per column, the kinematic surface flux (positive
+ * upward) entering the lowest layer, solved by the Thomas algorithm.  The matrix depends on (l, k) only, so the elimination is
+ * done ONCE per LES on the host in float64 (sp_coupler_amd/diffusion.py: profiles): a is the lower diagonal, m the reciprocal
+ * pivots, cp the eliminated upper diagonal, [n_les x ktot] each, rows pitch_prof apart; s0 = dt / dz[0], [n_les].  Fields are
+ * [n_les][itot][jtot][ktot] (layout and offsets as K10), element type T; every operation is rounded once in T, never an fma,
+ * and the kernel holds no division.  Per column (l, i, j) of each field f:
+ *   d    = flux[f] != NULL ? x[0] + s0[l] * flux[f][l] : x[0]      the product rounded, then the add; no add without a flux
+ *   y[0] = d * m[l][0]
+ *   y[k] = (x[k] - a[l][k] * y[k-1]) * m[l][k]                     k = 1 ... ktot - 1: product, subtraction, product
+ *   x'[ktot-1] = y[ktot-1]
+ *   x'[k] = y[k] - cp[l][k] * x'[k+1]                              k = ktot - 2 ... 0: product, subtraction
+ * x' replaces x IN PLACE.  ktot == 1 is allowed.  Special values get no rule of their own: a NaN or an infinity spreads through
+ * its own column as the recurrence dictates and reaches no other column.  With a = 0, m = 1, cp = 0 and no flux a field keeps
+ * its bits.  Two EQUAL fields pointers, a field equal to a profile, s0 or its flux, and a flux without s0 are
+ * SPC_ERR_INVALID_ARGUMENT; arrays that overlap in part are not detected and must not be passed.  A workgroup takes
+ * spc_les_diffuse_cols_per_block(ktot, sizeof(T)) columns into LDS; above the largest ktot of which 16 columns fit (1 279 levels
+ * of 8 bytes, 2 559 of 4) the launch is SPC_ERR_UNSUPPORTED.  The rule is this library's definition.      */
+#define SPC_DIFFUSE_MAX_FIELDS 4
+typedef struct spc_les_diffuse_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_fields; /* n_fields 1 ... SPC_DIFFUSE_MAX_FIELDS                             */
+    void *fields[SPC_DIFFUSE_MAX_FIELDS];      /* device [n_les][itot][jtot][ktot], updated in place         */
+    const void *flux[SPC_DIFFUSE_MAX_FIELDS];  /* device [n_les], the kinematic surface flux, or NULL        */
+    const void *a, *m, *cp;             /* device [n_les x ktot] each, rows pitch_prof apart                 */
+    const void *s0;                     /* device [n_les]; may be NULL when every flux is NULL               */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+} spc_les_diffuse_args;
+int spc_les_diffuse_f64(const spc_les_diffuse_args *args, void *stream);
+int spc_les_diffuse_f32(const spc_les_diffuse_args *args, void *stream);
+/* columns per workgroup of k_les_diffuse for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
+int spc_les_diffuse_cols_per_block(int ktot, int elem_size);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */
 const char *spc_last_error(void);   /* text of the calling thread's last failure ("" if none)     */

@@ -144,6 +144,15 @@ class LesMicroArgs(ctypes.Structure):
                 + _ptrs("qt_mean", "thl_mean", "qr_mean", "qi_mean") + [("pitch_mean", c_int64)])
 
 
+SPC_DIFFUSE_MAX_FIELDS = 4
+
+
+class LesDiffuseArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32),
+                 ("fields", c_void_p * SPC_DIFFUSE_MAX_FIELDS), ("flux", c_void_p * SPC_DIFFUSE_MAX_FIELDS)]
+                + _ptrs("a", "m", "cp", "s0") + [("pitch_prof", c_int64)])
+
+
 THERMO_TABLE_LIBRARY, THERMO_TABLE_LDS, THERMO_TABLE_GLOBAL = 0, 1, 2      # spc_les_thermo_args.table_mode
 
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
@@ -192,6 +201,9 @@ PROTOTYPES = {
     "spc_les_water_paths_f32": (ctypes.c_int, [ctypes.POINTER(WaterPathArgs), c_void_p]),
     "spc_les_microphysics_f64": (ctypes.c_int, [ctypes.POINTER(LesMicroArgs), c_void_p]),
     "spc_les_microphysics_f32": (ctypes.c_int, [ctypes.POINTER(LesMicroArgs), c_void_p]),
+    "spc_les_diffuse_f64": (ctypes.c_int, [ctypes.POINTER(LesDiffuseArgs), c_void_p]),
+    "spc_les_diffuse_f32": (ctypes.c_int, [ctypes.POINTER(LesDiffuseArgs), c_void_p]),
+    "spc_les_diffuse_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

@@ -26,6 +26,8 @@
 //   K14 k_les_microphysics  warm-rain microphysics of those fields (autoconversion, accretion, one upwind step of sedimentation,
 //                  the surface rain, the cloud ice) and the slab means of QT, THL, QR and QI in one pass: spc_micro.hpp, kernel
 //                  and host side
+//   K15 k_les_diffuse  one backward-Euler step of the vertical diffusion of those fields with the surface fluxes (Thomas sweeps
+//                  of a tile of columns in LDS, the elimination done on the host): spc_diffuse.hpp, kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -78,6 +80,7 @@ namespace {
 #include "spc_thermo.hpp"
 #include "spc_waterpath.hpp"
 #include "spc_micro.hpp"
+#include "spc_diffuse.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -100,6 +103,9 @@ namespace {
 #define SPC_MICRO_HOST
 #include "spc_micro.hpp"
 #undef SPC_MICRO_HOST
+#define SPC_DIFFUSE_HOST
+#include "spc_diffuse.hpp"
+#undef SPC_DIFFUSE_HOST
 
 }  // namespace
 
@@ -175,6 +181,10 @@ int spc_les_water_paths_f32(const spc_water_path_args *a, void *s) { return wate
 
 int spc_les_microphysics_f64(const spc_les_micro_args *a, void *s) { return les_micro_impl<double>(a, s); }
 int spc_les_microphysics_f32(const spc_les_micro_args *a, void *s) { return les_micro_impl<float>(a, s); }
+
+int spc_les_diffuse_f64(const spc_les_diffuse_args *a, void *s) { return les_diffuse_impl<double>(a, s); }
+int spc_les_diffuse_f32(const spc_les_diffuse_args *a, void *s) { return les_diffuse_impl<float>(a, s); }
+int spc_les_diffuse_cols_per_block(int ktot, int elem_size) { return dif_cols(ktot, elem_size); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

@@ -843,6 +843,56 @@ class Engine:
         self._call(fn, ctypes.byref(a), stream=stream)
         return res
 
+    # -- K15: implicit vertical diffusion of device-resident LES fields with the surface fluxes, one launch -----------------
+    @_on_engine_stream
+    def les_diffuse(self, fields, a, m, cp, s0=None, flux=None, stream=None):
+        """One backward-Euler step of the vertical diffusion (include/spc.h has the rule) IN PLACE on every tensor of ``fields``
+        (dict name -> contiguous [n x itot x jtot x ktot], at most ``_abi.SPC_DIFFUSE_MAX_FIELDS`` of one shape).  ``a``, ``m``,
+        ``cp`` [n x ktot] and ``s0`` [n] are ``diffusion.profiles`` in the engine's dtype (rows may be pitched, all with one
+        pitch).  ``flux``: dict name -> [n], the kinematic surface flux (positive upward) that enters level 0 of that field;
+        fields without one take none, and ``s0`` may be None when no field has one.  A field that STARTS where another field,
+        a profile, ``s0`` or a flux starts is refused (ValueError); views that overlap in part are not detected.  One launch;
+        more levels than ``diffuse_cols_per_block`` carries are refused (SPC_ERR_UNSUPPORTED)."""
+        names = list(fields)
+        if not 1 <= len(names) <= _abi.SPC_DIFFUSE_MAX_FIELDS:
+            raise ValueError("les_diffuse takes 1 ... %d fields per launch, got %d" % (_abi.SPC_DIFFUSE_MAX_FIELDS, len(names)))
+        flux = {} if flux is None else flux
+        unknown = [k for k in flux if k not in fields]
+        if unknown:
+            raise ValueError("les_diffuse: fluxes %s have no field" % unknown)
+        flux = {k: v for k, v in flux.items() if v is not None}
+        if flux and s0 is None:
+            raise ValueError("les_diffuse: a flux needs s0")
+        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_diffuse: empty field shape %s" % (shape,))
+        ck = _Checker(self.device, self.dtype)
+        g = _abi.LesDiffuseArgs()
+        g.n_les, g.itot, g.jtot, g.ktot, g.n_fields = n, itot, jtot, ktot, len(names)
+        g.a, g.pitch_prof = ck.mat("a", a, n, ktot)
+        g.m, _ = ck.mat("m", m, n, ktot, pitch=g.pitch_prof)
+        g.cp, _ = ck.mat("cp", cp, n, ktot, pitch=g.pitch_prof)
+        read = [a, m, cp]
+        if s0 is not None:
+            g.s0 = ck.vec("s0", s0, n)
+            read.append(s0)
+        for f, name in enumerate(names):
+            g.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            if name in flux:
+                g.flux[f] = ck.vec("flux[%s]" % name, flux[name], n)
+                read.append(flux[name])
+        if n:
+            written = [fields[k].data_ptr() for k in names]
+            if len(set(written)) != len(written) or set(written) & set(t.data_ptr() for t in read):
+                raise ValueError("les_diffuse: a field is another field, a profile, s0 or a flux")
+        fn = self.lib.spc_les_diffuse_f32 if self.dtype == torch.float32 else self.lib.spc_les_diffuse_f64
+        self._call(fn, ctypes.byref(g), stream=stream)
+
+    def diffuse_cols_per_block(self, ktot):
+        """columns of ``ktot`` levels a workgroup of K15 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
+        return int(self.lib.spc_les_diffuse_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

@@ -672,7 +672,9 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     LWP, TWP and RWP, [n x itot x jtot] device tensors, and the cloud cover; tests/les_water_paths_ref.py holds their twin.
     After ``enable_microphysics()`` every step ends with the warm-rain microphysics (K14, ``Engine.les_microphysics``): cloud
     water turns into rain, the QR field falls, ``rain2d`` collects what reaches the ground and ``p["Rain"]`` is its plane mean;
-    tests/les_micro_ref.py holds the twin of that mode."""
+    tests/les_micro_ref.py holds the twin of that mode.
+    After ``enable_diffusion()`` every step mixes U, V, THL and QT along k and lets the surface fluxes of the coupler into THL
+    and QT (K15, ``Engine.les_diffuse``); tests/les_diffuse_ref.py holds the twin of that mode."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
@@ -814,6 +816,60 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                 p["QL"] = numpy.asarray(self._host(ql), dtype=numpy.float64)
             if self._means is not None:
                 self._means["QL"] = p["QL"]
+
+    # -- implicit vertical diffusion and surface fluxes (K15), opt-in ---------------------------------------------------------
+    diffusion = False                                  # enable_diffusion(): the columns mix and take the surface fluxes
+    diffuse_par = None                                 # k_max, h_mix, k_bg
+    DIFFUSE_KEYS = ("U", "V", "THL", "QT")             # fields a step diffuses, where they exist
+    DIFFUSE_FLUX = {"THL": "wt", "QT": "wq"}           # field -> the slot of ``tend`` that holds its kinematic surface flux
+    _diffuse_prof = None                               # ((dt, k_max, h_mix, k_bg, host Rhobf, zh, zf) of the upload, device a, m, cp, s0)
+
+    def enable_diffusion(self, k_max=None, h_mix=None, k_bg=None):
+        """from now on every ``evolve_model_batched`` runs ONE K15 launch per device (``Engine.les_diffuse``)
+        on the fields among U, V, THL and QT that exist, after the step and before K14 / K12: one backward-Euler step of the
+        vertical diffusion with the profile of ``diffusion.diffusivity``.  THL takes the surface flux ``set_wt_surf`` /
+        ``WT_surf`` handed over, QT that of ``set_wq_surf`` / ``WQ_surf`` (kinematic, positive upward; none where none was
+        set); U and V take none (no surface drag).  The profiles then are K10's means of the diffused fields and QL follows
+        the new QT.  The coefficients are uploaded again whenever dt, a parameter, Rhobf or the grid (zh, zf) changed.  The
+        parameters default to those of ``diffusion``.  Without this call every path of the ensemble is unchanged."""
+        from . import diffusion as df
+        if not any(k in self.fields3d for k in self.DIFFUSE_KEYS):
+            raise ValueError("the diffusion (K15) needs one of the fields %s (set_fields_batched)" % (self.DIFFUSE_KEYS,))
+        if not all(callable(getattr(e, "les_diffuse", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
+            raise ValueError("the engine has no les_diffuse (K15)")
+        self.diffuse_par = {"k_max": df.K_MAX if k_max is None else float(k_max), "h_mix": df.H_MIX if h_mix is None else float(h_mix),
+                            "k_bg": df.K_BG if k_bg is None else float(k_bg)}
+        self.diffusion, self._diffuse_prof = True, None
+
+    def _diffuse(self, dt):
+        """K15 on the stepped fields; QL (without thermo) and the profiles are then those of the diffused fields"""
+        import torch
+        from . import diffusion as df
+        eng, f, p, par = self._eng(), self.fields3d, self.p, self.diffuse_par
+        keys = [k for k in self.DIFFUSE_KEYS if k in f]
+        if self.n == 0 or not keys:
+            return
+        # everything the coefficients are made of; the host arrays are copied and compared every step (kilobytes)
+        key = (float(dt), par["k_max"], par["h_mix"], par["k_bg"]) + tuple(numpy.array(a, dtype=numpy.float64) for a in (p["Rhobf"], self.zh_cache, self.zf_cache))
+        if self._diffuse_prof is None or self._diffuse_prof[0][:4] != key[:4] or not all(
+                a.shape == b.shape and numpy.array_equal(a, b) for a, b in zip(self._diffuse_prof[0][4:], key[4:])):
+            prof = df.profiles(key[5], key[6], key[4], dt, par["k_max"], par["h_mix"], par["k_bg"])
+            self._diffuse_prof = (key, [self._upload(a) for a in prof])
+        a, m, cp, s0 = self._diffuse_prof[1]
+        flux = {k: self._upload(numpy.asarray(self.tend[slot], dtype=numpy.float64).reshape(self.n))
+                for k, slot in self.DIFFUSE_FLUX.items() if k in keys and slot in self.tend}
+        eng.les_diffuse({k: f[k] for k in keys}, a, m, cp, s0=s0, flux=flux)
+        self._drop_water_paths()
+        self._thermo_stale = True                         # thermo: K12 runs on the diffused THL and QT before their next use
+        if not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
+            self._ensure_ql()
+
+            def saturate(ql, qt, qs):
+                torch.sub(qt, qs, out=ql)
+                return ql.clamp_min_(0.0)
+            self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
+        self._means = None
+        self._slab_means()                                # p[U, V, THL, QT, QL] = the slab means of the diffused fields
 
     @classmethod
     def for_gcm(cls, gcm, grid_indices, nL=160, seed=0, itot=8, jtot=8, engine=None):
@@ -1049,17 +1105,22 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                         return field.add_(inc[:, None, None, :])
                     self._per_device(step, f[key], self._upload(self.tend[key]))
             self._thermo_stale = True
-            if not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
+            if self.diffusion:
+                pass                                      # (the QL field and the means follow the diffused fields: _diffuse)
+            elif not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
                 self._ensure_ql()
 
                 def saturate(ql, qt, qs):
                     torch.sub(qt, qs, out=ql)
                     return ql.clamp_min_(0.0)
                 self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
-            self._means = None
-            self._slab_means()                            # p[U, V, THL, QT, QL] = the slab means of the new fields
+            if not self.diffusion:
+                self._means = None
+                self._slab_means()                        # p[U, V, THL, QT, QL] = the slab means of the new fields
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
+        if self.diffusion:
+            self._diffuse(dt)                             # one K15 launch: U, V, THL, QT mixed along k, the surface fluxes; p[...]
         if self.micro:
             self._microphysics(dt)                        # one K14 launch: QT, THL, QR, rain2d; p[QT, THL, QR, Rain(, QL_ice)]
         if self.thermo:

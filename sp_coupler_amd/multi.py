@@ -246,6 +246,14 @@ class MultiDeviceEngine:
         return self._run("les_microphysics", qt, ql, qr, qr_new, sed_out, sed_in, lcpex, w, dt, thl=thl, temp=temp, rain=rain,
                          means=means, **kw)
 
+    def les_diffuse(self, fields, a, m, cp, s0=None, flux=None, **kw):
+        """K15 on every device's LES: dict of Sharded fields (diffused in place, block by block), Sharded [n x ktot] profiles,
+        ``s0`` [n] and dict of Sharded [n] fluxes in; one launch per device that holds rows, none on the others"""
+        ex = self._example(fields)
+        if ex is None:
+            return self.primary.les_diffuse(fields, a, m, cp, s0=s0, flux=flux, **kw)
+        self._each("les_diffuse", ex, (fields, a, m, cp), dict(kw, s0=s0, flux=flux))
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

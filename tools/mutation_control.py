@@ -17,6 +17,8 @@ WATERPATH_MUTANTS is the table of K13 (spc_waterpath.hpp), chosen with --waterpa
 tests/les_water_paths_ref.py, which tests/test_les_water_paths_gpu.py runs on the shipped library.
 MICRO_MUTANTS is the table of K14 (spc_micro.hpp), chosen with --micro; its guards are the bodies of
 tests/les_micro_ref.py, which tests/test_les_micro_gpu.py runs on the shipped library.
+DIFFUSE_MUTANTS is the table of K15 (spc_diffuse.hpp), chosen with --diffuse; its guards are the bodies of
+tests/les_diffuse_ref.py, which tests/test_les_diffuse_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
@@ -30,6 +32,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --thermo --build && python tools/mutation_control.py --thermo > profiles/mutation_control_thermo.log
        python tools/mutation_control.py --waterpath --build && python tools/mutation_control.py --waterpath > profiles/mutation_control_waterpath.log
        python tools/mutation_control.py --micro --build && python tools/mutation_control.py --micro > profiles/mutation_control_micro.log
+       python tools/mutation_control.py --diffuse --build && python tools/mutation_control.py --diffuse > profiles/mutation_control_diffuse.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log"""
 import argparse
@@ -52,6 +55,7 @@ ADVANCE = "spc_advance.hpp"
 THERMO = "spc_thermo.hpp"
 WATERPATH = "spc_waterpath.hpp"
 MICRO = "spc_micro.hpp"
+DIFFUSE = "spc_diffuse.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -335,6 +339,42 @@ MICRO_MUTANTS = {
 }
 
 
+def diffuse_body(name):
+    """guard of a K15 mutant: the body ``name`` of tests/les_diffuse_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_diffuse_ref as ldr
+        failed = []
+        for dtype in ldr.DTYPES:
+            failed += ldr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_diffuse_ref." + name
+    return guard
+
+
+# K15 (spc_diffuse.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 2 reads cp[k + 1] for k <= ktot - 2, mutant 4 the rows of the LES of the tile's first column,
+# mutant 6 cp's row in place of a's; mutants 5 and 7 leave a level of the tile as it is).
+DIFFUSE_MUTANTS = {
+    1: ("K15 forward sweep: the product and the subtraction contracted to an fma", diffuse_body("parity"),
+        [(DIFFUSE, "                const T t = ca[u] * y;\n                y = (cx[u] - t) * cm[u];",
+          "                y = (T)__builtin_fma(-(double)ca[u], (double)y, (double)cx[u]) * cm[u];")]),
+    2: ("K15 back substitution: cp[k + 1] for cp[k] (the levels behind the whole chunks)", diffuse_body("parity"),
+        [(DIFFUSE, "const T t = cp[k] * y;", "const T t = cp[k + 1] * y;")]),
+    3: ("K15 surface flux: the product and the add contracted to an fma", diffuse_body("parity"),
+        [(DIFFUSE, "            const T t = p.s0[l] * flux[l];\n            d = d + t;", "            d = (T)__builtin_fma((double)p.s0[l], (double)flux[l], (double)d);")]),
+    4: ("K15 l: the LES of the tile's first column for every lane", diffuse_body("rows"),
+        [(DIFFUSE, "const int64_t l = (col0 + c) / p.nij;", "const int64_t l = col0 / p.nij;")]),
+    5: ("K15 back substitution: started one level low (level ktot - 2 keeps y)", diffuse_body("parity"),
+        [(DIFFUSE, "    k = ktot - 2;", "    k = ktot - 3;")]),
+    6: ("K15 forward sweep: a read from cp's rows", diffuse_body("parity"),
+        [(DIFFUSE, "dif_column<T>(x, p.a + o, p.m + o, p.cp + o, d, ktot);", "dif_column<T>(x, p.cp + o, p.m + o, p.cp + o, d, ktot);")]),
+    7: ("K15 forward sweep: the levels behind the whole chunks stop one short of the top", diffuse_body("parity"),
+        [(DIFFUSE, "    for (; k < ktot; ++k) {\n        const T t = a[k] * y;", "    for (; k < ktot - 1; ++k) {\n        const T t = a[k] * y;")]),
+    8: ("K15 level 0 without a flux: + 0.0 added, so -0.0 becomes +0.0", diffuse_body("special"),
+        [(DIFFUSE, "T d = x[0];", "T d = x[0] + (T)0;")]),
+}
+
+
 def geo_body(name):
     """guard of a K8 mutant: the body ``name`` of tests/geo_edges.py on the float64 engine of the library (K8 is float64 on
     every engine)"""
@@ -519,7 +559,7 @@ def patched(n, src=CSRC, table=None):
 def _tag(table):
     """(library prefix, source directory prefix) of a table"""
     for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
-                   (MICRO_MUTANTS, ("micro_", "micro")),
+                   (MICRO_MUTANTS, ("micro_", "micro")), (DIFFUSE_MUTANTS, ("diffuse_", "diffuse")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq"))):
@@ -694,11 +734,12 @@ if __name__ == "__main__":
     ap.add_argument("--thermo", action="store_true", help="the table of K12 (THERMO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--waterpath", action="store_true", help="the table of K13 (WATERPATH_MUTANTS) instead of MUTANTS")
     ap.add_argument("--micro", action="store_true", help="the table of K14 (MICRO_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--diffuse", action="store_true", help="the table of K15 (DIFFUSE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
-             else GEO_MUTANTS if args.geo
+             else DIFFUSE_MUTANTS if args.diffuse else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -722,4 +763,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, WATERPATH_MUTANTS, "K13", "les_water_paths"))
     if args.micro:
         sys.exit(main_advance(only, MICRO_MUTANTS, "K14", "les_micro"))
+    if args.diffuse:
+        sys.exit(main_advance(only, DIFFUSE_MUTANTS, "K15", "les_diffuse"))
     sys.exit((main_advance if args.advance else main)(only))
