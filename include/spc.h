@@ -583,6 +583,45 @@ int spc_les_diffuse_f32(const spc_les_diffuse_args *args, void *stream);
 /* columns per workgroup of k_les_diffuse for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
 int spc_les_diffuse_cols_per_block(int ktot, int elem_size);
 
+/* ---- horizontal upwind advection of the device-resident LES fields on the doubly periodic plane (kernel family K16) ------------ */
+/* One explicit first-order upwind step in advective form from face Courant numbers.  Fields, u and v are
+ * [n_les][itot][jtot][ktot] (layout and offsets as K10), element type T; every operation is rounded once in T, never an fma, and
+ * the kernel holds no division.  Per LES l the caller hands in hx[l] = 0.5 * dt / dx[l] and hy[l] = 0.5 * dt / dy[l]
+ * (sp_coupler_amd/advection.py forms them in float64; they are rounded to T once).  The neighbours wrap: im = (i - 1 + itot) %
+ * itot, ip = (i + 1) % itot, jm = (j - 1 + jtot) % jtot, jp = (j + 1) % jtot (an extent of 1: the cell itself; of 2: both
+ * neighbours are the same cell).  Per cell (l, i, j, k), every array at level k of LES l:
+ *   cw = (u[im][j] + u[i][j]) * hx[l];   ce = (u[i][j] + u[ip][j]) * hx[l]        the add rounded, then the product
+ *   cs = (v[i][jm] + v[i][j]) * hy[l];   cn = (v[i][j] + v[i][jp]) * hy[l]
+ *   pw = cw > 0 ? cw : 0;   pe = ce < 0 ? -ce : 0;   ps = cs > 0 ? cs : 0;   pn = cn < 0 ? -cn : 0     a NaN face gives +0
+ *   out[f] = (((x + pw * (x[im][j] - x)) + pe * (x[ip][j] - x)) + ps * (x[i][jm] - x)) + pn * (x[i][jp] - x)     x = fields[f]
+ *   s  = ((pw + pe) + ps) + pn;          cmax[l] = the maximum of s over the cells of LES l (the launch zeroes it first)
+ * u, v and the fields are read only; a field may be u or v itself (the winds are advected by the old winds).  Every out[f] is
+ * written whole.  s is never NaN and never negative, so cmax does not depend on the order of the cells.  With s <= 1 out[f] is
+ * a convex combination of the cell and its four neighbours; a constant finite field keeps its bits (a -0.0 constant comes out
+ * +0.0).  Special values get no rule of their own: a NaN or an infinity of a field reaches at most its four neighbours, a NaN
+ * wind closes the faces it touches.  n_fields == 0 with cmax is the probe: only the winds are read.  n_fields == 0 without
+ * cmax, an out[f] EQUAL to u, v, hx, hy, cmax, a field or another out, and cmax EQUAL to an input are
+ * SPC_ERR_INVALID_ARGUMENT; arrays that overlap in part are not detected and must not be passed.  ktot == 1 is allowed.  A
+ * workgroup owns spc_les_advect_strip(jtot, ktot, sizeof(T)) consecutive cells of the run [jtot][ktot] of one row i and
+ * spc_les_advect_rows(n_les, itot, jtot, ktot) consecutive rows.  The rule is this library's definition.                          */
+#define SPC_ADVECT_MAX_FIELDS 6
+typedef struct spc_les_advect_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_fields; /* n_fields 0 ... SPC_ADVECT_MAX_FIELDS                              */
+    const void *u, *v;                  /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *fields[SPC_ADVECT_MAX_FIELDS];  /* device [n_les][itot][jtot][ktot], read only               */
+    void *out[SPC_ADVECT_MAX_FIELDS];   /* device [n_les][itot][jtot][ktot], written whole                   */
+    const void *hx, *hy;                /* device [n_les]: 0.5 dt / dx and 0.5 dt / dy                       */
+    void *cmax;                         /* device [n_les], or NULL where n_fields > 0                        */
+} spc_les_advect_args;
+int spc_les_advect_f64(const spc_les_advect_args *args, void *stream);
+int spc_les_advect_f32(const spc_les_advect_args *args, void *stream);
+/* cells of the flat run [jtot][ktot] of one row i that a workgroup of k_les_advect owns (elem_size 4 or 8); 0: bad arguments */
+int spc_les_advect_strip(int jtot, int ktot, int elem_size);
+/* consecutive rows i that a workgroup of k_les_advect walks: 32 where the launch has at least 1 024 workgroups even so, else 8;
+ * 0: bad arguments */
+int spc_les_advect_rows(int64_t n_les, int itot, int jtot, int ktot);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */
 const char *spc_last_error(void);   /* text of the calling thread's last failure ("" if none)     */

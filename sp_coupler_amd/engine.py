@@ -893,6 +893,55 @@ class Engine:
         """columns of ``ktot`` levels a workgroup of K15 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
         return int(self.lib.spc_les_diffuse_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
 
+    # -- K16: horizontal upwind advection of device-resident LES fields on the periodic plane, one launch ----------------------
+    @_on_engine_stream
+    def les_advect(self, fields, out, u, v, hx, hy, cmax=True, stream=None):
+        """One explicit upwind step of the horizontal advection (include/spc.h has the rule) of every tensor of ``fields`` (dict
+        name -> contiguous [n x itot x jtot x ktot], at most ``_abi.SPC_ADVECT_MAX_FIELDS`` of one shape, read only) by the
+        winds ``u`` and ``v`` (the same shape, read only; a field may be ``u`` or ``v`` itself) into the tensors of ``out``
+        (the same names, written whole).  ``hx`` and ``hy`` [n] are ``advection.coefficients`` in the engine's dtype.
+        ``cmax``: True (a fresh [n] tensor), a tensor [n] to write into, or False / None; returned: the largest Courant sum of
+        every LES, or None.  ``fields`` may be empty with a ``cmax``: the probe, which reads the winds only.  An ``out`` that
+        STARTS where an input, ``cmax`` or another ``out`` starts is refused (ValueError); views that overlap in part are not
+        detected.  One launch."""
+        names = list(fields)
+        if len(names) > _abi.SPC_ADVECT_MAX_FIELDS:
+            raise ValueError("les_advect takes at most %d fields per launch, got %d" % (_abi.SPC_ADVECT_MAX_FIELDS, len(names)))
+        if sorted(out) != sorted(names):
+            raise ValueError("les_advect: out holds %s, the fields are %s" % (sorted(out), sorted(names)))
+        want = cmax is not None and cmax is not False
+        if not names and not want:
+            raise ValueError("les_advect: no field and no cmax: nothing to do")
+        shape = tuple(self._field4("u", u).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_advect: empty field shape %s" % (shape,))
+        ck = _Checker(self.device, self.dtype)
+        g = _abi.LesAdvectArgs()
+        g.n_les, g.itot, g.jtot, g.ktot, g.n_fields = n, itot, jtot, ktot, len(names)
+        g.u, g.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
+        g.hx, g.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
+        res = None
+        if want:
+            res = torch.empty(n, dtype=self.dtype, device=self.device) if cmax is True else cmax
+            g.cmax = ck.vec("cmax", res, n)
+        for f, name in enumerate(names):
+            g.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            g.out[f] = self._field4("out[%s]" % name, out[name], shape).data_ptr()
+        if n:
+            read = [t.data_ptr() for t in [u, v, hx, hy] + [fields[k] for k in names]]
+            written = [out[k].data_ptr() for k in names] + ([res.data_ptr()] if want else [])
+            if len(set(written)) != len(written) or set(written) & set(read):
+                raise ValueError("les_advect: an output is an input, cmax or another output")
+        fn = self.lib.spc_les_advect_f32 if self.dtype == torch.float32 else self.lib.spc_les_advect_f64
+        self._call(fn, ctypes.byref(g), stream=stream)
+        return res
+
+    def advect_strip(self, n, itot, jtot, ktot):
+        """(cells of the run [jtot x ktot] of one row i, rows i) a workgroup of K16 owns at these extents in the engine's dtype"""
+        return (int(self.lib.spc_les_advect_strip(int(jtot), int(ktot), 4 if self.dtype == torch.float32 else 8)),
+                int(self.lib.spc_les_advect_rows(int(n), int(itot), int(jtot), int(ktot))))
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

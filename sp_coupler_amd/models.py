@@ -643,6 +643,30 @@ class _DeviceLESRow(_LESRow):
     def get_jtot(self):
         return self._e.jtot
 
+    @property
+    def dx(self):
+        """the grid spacing along i, m: the ensemble's after enable_advection(), else ``advection.DX``"""
+        from . import advection
+        return float(numpy.broadcast_to(advection.DX if self._e.dx is None else self._e.dx, (self._e.n,))[self._i])
+
+    @property
+    def dy(self):
+        from . import advection
+        return float(numpy.broadcast_to(advection.DY if self._e.dy is None else self._e.dy, (self._e.n,))[self._i])
+
+    def get_dx(self):
+        return self.dx
+
+    def get_dy(self):
+        return self.dy
+
+    def get_xsize(self):
+        """the extent of the periodic plane along i, m (splib/spio.py:104-111 asks an LES for it)"""
+        return self.dx * self._e.itot
+
+    def get_ysize(self):
+        return self.dy * self._e.jtot
+
     def get_cloudfraction(self, indices, return_request=False):
         raise NotImplementedError("a DeviceLESEnsemble answers get_cloudfraction_batched (all columns, one launch)")
 
@@ -674,7 +698,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     water turns into rain, the QR field falls, ``rain2d`` collects what reaches the ground and ``p["Rain"]`` is its plane mean;
     tests/les_micro_ref.py holds the twin of that mode.
     After ``enable_diffusion()`` every step mixes U, V, THL and QT along k and lets the surface fluxes of the coupler into THL
-    and QT (K15, ``Engine.les_diffuse``); tests/les_diffuse_ref.py holds the twin of that mode."""
+    and QT (K15, ``Engine.les_diffuse``); tests/les_diffuse_ref.py holds the twin of that mode.
+    After ``enable_advection()`` every step carries U, V, THL, QT and QR along i and j with the winds U and V on the periodic
+    plane, in as many upwind substeps as the Courant sums ask for (K16, ``Engine.les_advect``); tests/les_advect_ref.py holds
+    the twin of that mode."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
@@ -870,6 +897,115 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
         self._means = None
         self._slab_means()                                # p[U, V, THL, QT, QL] = the slab means of the diffused fields
+
+    # -- horizontal upwind advection on the periodic plane (K16), opt-in --------------------------------------------------------
+    advection = False                                  # enable_advection(): the winds carry the fields along i and j
+    advect_par = None                                  # cfl, max_substeps
+    dx = dy = None                                     # the grid spacings, m (scalars or [n]); None: those of ``advection``
+    ADVECT_KEYS = ("U", "V", "THL", "QT", "QR")        # fields a step advects, where they exist
+    advect_courant = None                              # the largest Courant sum any substep of the last step returned
+    advect_substeps = None                             # the substeps of the last step
+    _advect_spare = None                               # name -> the buffer K16 writes next (it reads the field)
+    _advect_coef = None                                # ((dt, dx, dy) of the uploads, {substeps: device (hx, hy)})
+
+    def enable_advection(self, dx=None, dy=None, cfl=None, max_substeps=None):
+        """from now on every ``evolve_model_batched`` advects the fields among U, V, THL, QT and QR that exist with the winds U
+        and V on the doubly periodic plane (K16, ``Engine.les_advect``), after the step and before K15 / K14 /
+        K12: ONE probe launch per device finds the largest Courant sum c of the whole step, n_sub = max(1, ceil(c / cfl))
+        launches of dt / n_sub follow, each into spare buffers that are swapped in (RuntimeError, the fields as the step left
+        them, where c is not finite or n_sub > max_substeps).  ``advect_substeps`` and ``advect_courant`` hold n_sub and the
+        largest Courant sum of the substeps.  The profiles then are K10's means of the advected fields and QL follows the new
+        QT.  ``dx`` and ``dy`` (m, scalars or one per LES) are also what the rows' get_dx / get_dy / get_xsize / get_ysize
+        answer.  The coefficients are uploaded again whenever dt, n_sub, dx or dy changed.  The parameters default to those of
+        ``advection``.  Needs U and V fields.  Without this call every path of the ensemble is unchanged."""
+        from . import advection as adv
+        if "U" not in self.fields3d or "V" not in self.fields3d:
+            raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
+        if not all(callable(getattr(e, "les_advect", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
+            raise ValueError("the engine has no les_advect (K16)")
+        dx, dy = adv.DX if dx is None else dx, adv.DY if dy is None else dy
+        adv.coefficients(1.0, dx, dy, n=self.n)                       # (ValueError for a spacing that is not positive, or not [n])
+        self.dx = numpy.array(dx, dtype=numpy.float64) if numpy.ndim(dx) else float(dx)
+        self.dy = numpy.array(dy, dtype=numpy.float64) if numpy.ndim(dy) else float(dy)
+        self.advect_par = {"cfl": adv.CFL if cfl is None else float(cfl),
+                           "max_substeps": adv.MAX_SUBSTEPS if max_substeps is None else int(max_substeps)}
+        if not self.advect_par["cfl"] > 0 or self.advect_par["max_substeps"] < 1:
+            raise ValueError("the advection (K16) needs cfl > 0 and max_substeps >= 1")
+        self.advection, self._advect_coef, self._advect_spare = True, None, {}
+
+    def _advect_coefs(self, dt, n_sub):
+        """device (hx, hy) of the substeps dt / n_sub; uploaded where dt, n_sub, dx or dy are not those of the last step"""
+        from . import advection as adv
+        key = (float(dt), numpy.array(self.dx, dtype=numpy.float64), numpy.array(self.dy, dtype=numpy.float64))
+        old = self._advect_coef
+        if old is None or old[0][0] != key[0] or not all(a.shape == b.shape and numpy.array_equal(a, b) for a, b in zip(old[0][1:], key[1:])):
+            old = self._advect_coef = (key, {})
+        if n_sub not in old[1]:
+            for m in [m for m in old[1] if m != 1]:               # the probe's and one other: n_sub changed
+                del old[1][m]
+            old[1][n_sub] = tuple(self._upload(a) for a in adv.coefficients(float(dt) / n_sub, self.dx, self.dy, n=self.n))
+        return old[1][n_sub]
+
+    def _device_max(self, t):
+        """the largest element of a device vector (of the blocks of a Sharded one): one number per device to the host"""
+        eng = self._eng()
+        parts = [(e, part) for e, part in zip(getattr(eng, "engines", [eng]), getattr(t, "parts", [t])) if part.numel()]
+        vals = []
+        for e, part in parts:
+            with e.on_stream():
+                vals.append(part.max())
+        return max(float(v.item()) for v in vals)
+
+    def _advect(self, dt):
+        """K16 on the stepped fields: the probe, then n_sub launches into the spare buffers; QL (without thermo) and the
+        profiles are then those of the advected fields, unless K15 follows and does both"""
+        import torch
+        from . import advection as adv
+        eng, f, par = self._eng(), self.fields3d, self.advect_par
+        if self.n == 0:
+            return
+        if "U" not in f or "V" not in f:
+            raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
+        keys = [k for k in self.ADVECT_KEYS if k in f]
+        c = self._device_max(eng.les_advect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1)))
+        try:
+            n_sub = adv.substeps(c, par["cfl"], par["max_substeps"])
+        except RuntimeError:                              # nothing has been advected: QL and the profiles of the stepped fields
+            self._follow_fields()
+            raise
+        hx, hy = self._advect_coefs(dt, n_sub)
+        spare = self._advect_spare
+        for k in keys:
+            if spare.get(k) is None or spare[k] is f[k] or tuple(spare[k].shape) != tuple(f[k].shape):
+                spare[k] = self._per_device(torch.empty_like, f[k])
+        worst = None
+        for _ in range(n_sub):
+            out = {k: spare[k] for k in keys}
+            cm = eng.les_advect({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy)
+            for k in keys:
+                f[k], spare[k] = spare[k], f[k]
+            worst = cm if worst is None else self._per_device(torch.maximum, worst, cm)
+        self.advect_substeps, self.advect_courant = n_sub, self._device_max(worst)
+        self._drop_water_paths()
+        self._thermo_stale = True                         # thermo: K12 runs on the advected THL and QT before their next use
+        if not self.diffusion:                            # (else the QL field and the means follow the diffused fields: _diffuse)
+            self._follow_fields()
+
+    def _follow_fields(self):
+        """QL = max(QT - Qsat, 0) of the QT field as it is now (without thermo) and p[U, V, THL, QT, QL] = K10's means"""
+        import torch
+        f = self.fields3d
+        self._drop_water_paths()
+        self._thermo_stale = True
+        if not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
+            self._ensure_ql()
+
+            def saturate(ql, qt, qs):
+                torch.sub(qt, qs, out=ql)
+                return ql.clamp_min_(0.0)
+            self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
+        self._means = None
+        self._slab_means()
 
     @classmethod
     def for_gcm(cls, gcm, grid_indices, nL=160, seed=0, itot=8, jtot=8, engine=None):
@@ -1105,8 +1241,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                         return field.add_(inc[:, None, None, :])
                     self._per_device(step, f[key], self._upload(self.tend[key]))
             self._thermo_stale = True
-            if self.diffusion:
-                pass                                      # (the QL field and the means follow the diffused fields: _diffuse)
+            if self.diffusion or self.advection:
+                pass                                      # (the QL field and the means follow the diffused / advected fields)
             elif not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
                 self._ensure_ql()
 
@@ -1114,11 +1250,13 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                     torch.sub(qt, qs, out=ql)
                     return ql.clamp_min_(0.0)
                 self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
-            if not self.diffusion:
+            if not (self.diffusion or self.advection):
                 self._means = None
                 self._slab_means()                        # p[U, V, THL, QT, QL] = the slab means of the new fields
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
+        if self.advection:
+            self._advect(dt)                              # 1 + n_sub K16 launches: U, V, THL, QT, QR carried along i and j; p[...]
         if self.diffusion:
             self._diffuse(dt)                             # one K15 launch: U, V, THL, QT mixed along k, the surface fluxes; p[...]
         if self.micro:

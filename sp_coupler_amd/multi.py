@@ -254,6 +254,17 @@ class MultiDeviceEngine:
             return self.primary.les_diffuse(fields, a, m, cp, s0=s0, flux=flux, **kw)
         self._each("les_diffuse", ex, (fields, a, m, cp), dict(kw, s0=s0, flux=flux))
 
+    def les_advect(self, fields, out, u, v, hx, hy, cmax=True, **kw):
+        """K16 on every device's LES: dicts of Sharded fields and outputs (written block by block), Sharded winds and ``hx``,
+        ``hy`` [n] in; the Sharded [n] Courant sums out (None without ``cmax``); one launch per device that holds rows"""
+        ex = self._example(u)
+        if ex is None:
+            return self.primary.les_advect(fields, out, u, v, hx, hy, cmax=cmax, **kw)
+        res = self._each("les_advect", ex, (fields, out, u, v, hx, hy), dict(kw, cmax=cmax))
+        if cmax is None or cmax is False:
+            return None
+        return cmax if cmax is not True else self._join(res, ex.bounds)
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

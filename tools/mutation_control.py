@@ -19,6 +19,8 @@ MICRO_MUTANTS is the table of K14 (spc_micro.hpp), chosen with --micro; its guar
 tests/les_micro_ref.py, which tests/test_les_micro_gpu.py runs on the shipped library.
 DIFFUSE_MUTANTS is the table of K15 (spc_diffuse.hpp), chosen with --diffuse; its guards are the bodies of
 tests/les_diffuse_ref.py, which tests/test_les_diffuse_gpu.py runs on the shipped library.
+ADVECT_MUTANTS is the table of K16 (spc_advect.hpp), chosen with --advect; its guards are the bodies of
+tests/les_advect_ref.py, which tests/test_les_advect_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
@@ -56,6 +58,7 @@ THERMO = "spc_thermo.hpp"
 WATERPATH = "spc_waterpath.hpp"
 MICRO = "spc_micro.hpp"
 DIFFUSE = "spc_diffuse.hpp"
+ADVECT = "spc_advect.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -351,6 +354,43 @@ def diffuse_body(name):
     return guard
 
 
+def advect_body(name):
+    """guard of a K16 mutant: the body ``name`` of tests/les_advect_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_advect_ref as lar
+        failed = []
+        for dtype in lar.DTYPES:
+            failed += lar.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_advect_ref." + name
+    return guard
+
+
+# K16 (spc_advect.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 1 reads row i for row i + 1 at the last row; mutant 2 wraps j - 1 by the SMALLER of itot and
+# jtot rows, which stays inside the run of the row -- wrapping by itot rows where itot > jtot would leave it; mutant 8 reads
+# u[ip], which the east face reads anyway).
+ADVECT_MUTANTS = {
+    1: ("K16 ip: clamped at the last row instead of wrapped to row 0", advect_body("parity"),
+        [(ADVECT, "const int ip = i + 1 == itot ? 0 : i + 1;", "const int ip = i + 1 == itot ? i : i + 1;")]),
+    2: ("K16 jm: wrapped by itot rows (where itot < jtot) instead of jtot", advect_body("parity"),
+        [(ADVECT, "        if (qs < 0) qs += row;", "        if (qs < 0) qs += (int64_t)(p.itot < p.jtot ? p.itot : p.jtot) * ktot;")]),
+    3: ("K16 pe: taken from ce > 0 (the east face lets in what leaves)", advect_body("signs"),
+        [(ADVECT, "const T pe = ce < (T)0 ? -ce : (T)0;", "const T pe = ce > (T)0 ? ce : (T)0;")]),
+    4: ("K16 east term: the product and the add contracted to an fma", advect_body("parity"),
+        [(ADVECT, "                r = r + te;", "                r = (T)__builtin_fma((double)pe, (double)de, (double)r);")]),
+    5: ("K16 sum: the south and north terms added before the west and east terms", advect_body("parity"),
+        [(ADVECT, "                T r = x + tw;\n                r = r + te;\n                r = r + ts;\n                r = r + tn;",
+          "                T r = x + ts;\n                r = r + tn;\n                r = r + tw;\n                r = r + te;")]),
+    6: ("K16 cs: hx used for hy", advect_body("rows"),
+        [(ADVECT, "const T cs = as * hy;", "const T cs = as * hx;")]),
+    7: ("K16 cmax: the sum without pn", advect_body("probe"),
+        [(ADVECT, "            s = s + pn;\n", "")]),
+    8: ("K16 west face: built from u[ip] instead of u[im]", advect_body("parity"),
+        [(ADVECT, "const T aw = uw + uc,", "const T aw = ue + uc,")]),
+}
+
+
 # K15 (spc_diffuse.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 2 reads cp[k + 1] for k <= ktot - 2, mutant 4 the rows of the LES of the tile's first column,
 # mutant 6 cp's row in place of a's; mutants 5 and 7 leave a level of the tile as it is).
@@ -560,6 +600,7 @@ def _tag(table):
     """(library prefix, source directory prefix) of a table"""
     for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
                    (MICRO_MUTANTS, ("micro_", "micro")), (DIFFUSE_MUTANTS, ("diffuse_", "diffuse")),
+                   (ADVECT_MUTANTS, ("advect_", "advect")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq"))):
@@ -735,11 +776,12 @@ if __name__ == "__main__":
     ap.add_argument("--waterpath", action="store_true", help="the table of K13 (WATERPATH_MUTANTS) instead of MUTANTS")
     ap.add_argument("--micro", action="store_true", help="the table of K14 (MICRO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--diffuse", action="store_true", help="the table of K15 (DIFFUSE_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--advect", action="store_true", help="the table of K16 (ADVECT_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
-             else DIFFUSE_MUTANTS if args.diffuse else GEO_MUTANTS if args.geo
+             else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -765,4 +807,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, MICRO_MUTANTS, "K14", "les_micro"))
     if args.diffuse:
         sys.exit(main_advance(only, DIFFUSE_MUTANTS, "K15", "les_diffuse"))
+    if args.advect:
+        sys.exit(main_advance(only, ADVECT_MUTANTS, "K16", "les_advect"))
     sys.exit((main_advance if args.advance else main)(only))

@@ -2,14 +2,16 @@
 """Compile spc_hip.hip with -Rpass-analysis=kernel-resource-usage and print one line per kernel
 (VGPRs, SGPRs, spills, scratch, occupancy, LDS).  usage: tools/resusage.py [filter-substring | entry] [extra hipcc flags...]
 An entry of ENTRIES names a kernel family that must use no scratch and spill nothing in any instantiation: its lines are
-printed and the exit status is 1 if one of them does (tools/resusage.py microphysics, tools/resusage.py diffuse)."""
+printed and the exit status is 1 if one of them does (tools/resusage.py microphysics, tools/resusage.py diffuse,
+tools/resusage.py advect)."""
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRIES = {"microphysics": "k_les_microphysics", "diffuse": "k_les_diffuse"}   # K14, K15: every instantiation without scratch and without spills
+# K14, K15, K16: every instantiation without scratch and without spills
+ENTRIES = {"microphysics": "k_les_microphysics", "diffuse": "k_les_diffuse", "advect": "k_les_advect"}
 entry = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ENTRIES else None
 flt = ENTRIES[entry] if entry else sys.argv[1] if len(sys.argv) > 1 else ""
 extra = sys.argv[2:]
