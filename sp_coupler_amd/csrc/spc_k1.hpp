@@ -36,7 +36,11 @@ constexpr int cfloor_pow2(int n) { int p = 1; while (p * 2 <= n) p *= 2; return 
 //      without them K1 fits 6 waves per SIMD instead of 5 (75 vs 94 VGPRs) -- K1's rate follows its resident waves
 //      (profiles/r02_occupancy_ab_hot.log): -7 % at 35 718 columns, +12 % at 1024 (profiles/r02_k1_occupancy6_ab.log).
 //      PRE = false is also the REACH form (phase 1 split at the LES interpolation's reach, below): one more dependent
-//      round trip per workgroup, which a multi-round launch hides behind its other resident workgroups.
+//      round trip per workgroup, which a multi-round launch hides behind its other resident workgroups.  A reach-form
+//      workgroup is bound by the round trips it makes one after another, so in the lean double kernels (FOLD) the small
+//      ones ride on phase A's: a thread's first two phase-A items, its first LES grid entries, the half levels of the
+//      index map and the f_ps inputs are ONE trip, and the index entries and f_ps are written between the two barriers
+//      of the reach search.
 template <typename T, bool FULL, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true>
 __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
 {
@@ -54,8 +58,21 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
     T *const lds = reinterpret_cast<T *>(spc_smem);
     T *const lzh = lds + (size_t)cb * 6 * nG;
     // work items after the barrier: [0, n2) LES levels to interpolate, [n2, n2 + nI) index-map entries
-    const int n1 = ncol * nG, n2 = ncol * nL, nI = p.idx ? n1 : 0, nitems = n2 + nI;
     constexpr bool REACH = !PRE;
+    // FOLD: the lean double reach form rides its small round trips on phase A's (below).  The FULL and the float reach forms keep
+    // one trip per loop round: folded, two FULL instantiations gain scalar spills and the float ones 4-14 VGPRs.
+    constexpr bool FOLD = REACH && !FULL && sizeof(T) == 8;
+    constexpr int NE = FOLD ? 2 : 0;              // phase-A items per thread whose loads are issued before the first wait
+    constexpr int HELD = NE * BLK;                // the index entries of phase-A items < HELD are written in the reach gap
+    const int n1 = ncol * nG, n2 = ncol * nL, nI = p.idx ? (n1 > HELD ? n1 - HELD : 0) : 0, nitems = n2 + nI;
+    // one fused-K2 entry (spcpl.py:764) and one f_ps (spcpl.py:332): the reach gap and the one-phase path share them
+    auto put_idx = [&](int c, int64_t col, int m, T Zh_k) {
+        const T *const zh = d.shared_grid ? lzh : lzh + (size_t)c * nL;
+        p.idx[col * pitchG + m] = ss_right(zh, nL, Zh_k);
+    };
+    auto put_f_ps = [&](int64_t col, T sc_ps, T sc_psd) {
+        stg<WT>(&p.f_ps[col], Divisor<T>(p.dt).div(p.factor * (sc_ps - sc_psd)));          // spcpl.py:332
+    };
     STAMP(0);
 
     // ---- prologue: issue every load that depends on nothing, so ONE memory round trip covers the
@@ -82,7 +99,7 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
         if constexpr (FULL)
             if (OPT(rainrate)) { sc_rain = OPT(rain)[col0 + sc]; sc_rl = OPT(rain_last)[col0 + sc]; }
     }
-    if (p.idx) {  // stage the LES half levels for the fused index map
+    if (PRE && p.idx) {  // stage the LES half levels for the fused index map (REACH: with phase A's loads, below)
         const int nz = d.shared_grid ? nL : n2;
         for (int e = tid; e < nz; e += BLK) {
             const int c = e / nL, l = e - c * nL;
@@ -98,24 +115,70 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
     // ascending-height order).  Exact for any input: upper_count is monotone in x for ANY xp (a lane with the larger x
     // takes every branch the smaller one takes), so j0(x) <= j0(hmax) and j1(x) <= min(j0(hmax) + 1, nG - 1) for every
     // non-NaN x <= hmax, and a NaN height takes level 0.  LDS above the reach is never written nor read.
+    // FOLD: phase A issues, before its first wait, every load of a thread's first items: LES half level tid (index map),
+    // phase-A items tid and tid + BLK (with their own half level when the index map is fused), LES height tid and, on the
+    // lanes that own a column's scalars, the f_ps inputs.  Later items (larger slabs, 137<->512) keep one trip per loop
+    // round.  The index entries of the held items and f_ps are written between the two barriers of the reach search, which
+    // the lanes with the fewest held items run (the LAST ncol); phase 2 carries the index entries of phase-A items >= HELD.
     int nR = nG;                                   // levels staged per column: the nR lowest (REACH) or all
     if constexpr (REACH) {
         __shared__ T s_wmax[BLK / 64];
         __shared__ int s_top;
         if (tid == 0) s_top = 0;
-        for (int e = tid; e < n1; e += BLK) {
-            const int c = e / nG, k = e - c * nG;
-            const int64_t col = col0 + c, g = col * pitchG + k;
-            const T zf_k = div_grav(ldg(&p.Zgfull[g]) - ldg(&p.Zghalf[col * pitchGh + nG]));   // spcpl.py:198
+        const int nz = d.shared_grid ? nL : n2;           // LES grid entries this slab reads
+        auto grid_at = [&](const T *q, int e) {
+            const int c = e / nL, l = e - c * nL;
+            return d.shared_grid ? ldg(&q[e]) : ldg(&q[(col0 + c) * pitchL + l]);
+        };
+        // (branch-free, so that no load waits for another: a lane without an item repeats the slab's last one, a launch
+        //  without the index map reads zf and Zghalf[nG] once more -- lines the workgroup fetches anyway)
+        T zh0 = T(0), h0 = T(0), a_zg[2] = {}, a_zs[2] = {}, a_zh[2] = {}, held[2] = {};
+        if constexpr (FOLD) {
+            const int tz = tid < nz ? tid : nz - 1;
+            zh0 = grid_at(p.idx ? p.zh : p.zf, tz);
+#pragma unroll
+            for (int u = 0; u < NE; ++u) {
+                const int e = tid + u * BLK < n1 ? tid + u * BLK : n1 - 1, c = e / nG, k = e - c * nG;
+                const int64_t col = col0 + c;
+                a_zg[u] = ldg(&p.Zgfull[col * pitchG + k]);
+                a_zs[u] = ldg(&p.Zghalf[col * pitchGh + nG]);
+                a_zh[u] = ldg(&p.Zghalf[col * pitchGh + (p.idx ? k : nG)]);
+            }
+            h0 = grid_at(p.zf, tz);
+            if (sc < ncol) {
+                sc_ps = ldg(&p.Ph[(col0 + sc) * pitchGh + nG]);                               // spcpl.py:246
+                sc_psd = ldg(&p.ps_d[col0 + sc]);
+            }
+        }
+        if (p.idx) {  // stage the LES half levels for the fused index map
+            if (FOLD && tid < nz) lzh[tid] = zh0;
+            for (int e = tid + (FOLD ? BLK : 0); e < nz; e += BLK) lzh[e] = grid_at(p.zh, e);
+        }
+        auto stage_zf = [&](int c, int k, int64_t g, T zg, T zs) {
+            const T zf_k = div_grav(zg - zs);                                                  // spcpl.py:198
             lds[(size_t)c * 6 * nG + (nG - 1 - k)] = zf_k;                                     // [::-1], spcpl.py:224
             if constexpr (FULL)
                 if (OPT(Zf)) OPT(Zf)[g] = zf_k;                                                 // spcpl.py:200
+        };
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+            const int e = tid + u * BLK;
+            if (e < n1) {
+                const int c = e / nG, k = e - c * nG;
+                stage_zf(c, k, (col0 + c) * pitchG + k, a_zg[u], a_zs[u]);
+                if (p.idx) held[u] = div_grav(a_zh[u] - a_zs[u]);                              // spcpl.py:197
+            }
+        }
+        for (int e = tid + HELD; e < n1; e += BLK) {
+            const int c = e / nG, k = e - c * nG;
+            const int64_t col = col0 + c, g = col * pitchG + k;
+            stage_zf(c, k, g, ldg(&p.Zgfull[g]), ldg(&p.Zghalf[col * pitchGh + nG]));
         }
         T hmax = T(-__builtin_huge_val());
-        for (int e = tid, nz = d.shared_grid ? nL : n2; e < nz; e += BLK) {
-            const int c = e / nL, l = e - c * nL;
-            const T h = d.shared_grid ? ldg(&p.zf[e]) : ldg(&p.zf[(col0 + c) * pitchL + l]);
-            hmax = h > hmax ? h : hmax;                                                          // NaN never wins
+        if (FOLD && tid < nz) hmax = h0 > hmax ? h0 : hmax;                                    // NaN never wins
+        for (int e = tid + (FOLD ? BLK : 0); e < nz; e += BLK) {
+            const T h = grid_at(p.zf, e);
+            hmax = h > hmax ? h : hmax;
         }
         for (int m = 32; m > 0; m >>= 1) {
             const T o = __shfl_xor(hmax, m, 64);
@@ -123,10 +186,22 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
         }
         if ((tid & 63) == 0) s_wmax[tid >> 6] = hmax;
         __syncthreads();
-        if (tid < ncol) {
+        const int rs = FOLD ? sc : tid;                   // the lane of column rs searches its reach
+        if (rs < ncol) {
             for (int w = 0; w < BLK / 64; ++w) hmax = s_wmax[w] > hmax ? s_wmax[w] : hmax;
-            const Br<T> b = bracket2(lds + (size_t)tid * 6 * nG, nG, p2G, hmax);
+            const Br<T> b = bracket2(lds + (size_t)rs * 6 * nG, nG, p2G, hmax);
             atomicMax(&s_top, b.j0 + 1 >= nG ? nG - 1 : b.j0 + 1);
+            if constexpr (FOLD) put_f_ps(col0 + sc, sc_ps, sc_psd);
+        }
+        if (FOLD && p.idx) {
+#pragma unroll
+            for (int u = 0; u < NE; ++u) {
+                const int e = tid + u * BLK;
+                if (e < n1) {
+                    const int c = e / nG, k = e - c * nG;
+                    put_idx(c, col0 + c, nG - 1 - k, held[u]);
+                }
+            }
         }
         __syncthreads();
         nR = s_top + 1;
@@ -166,14 +241,14 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
     STAMP(3);
 
     // ---- per-column scalars (inputs already in registers; stores drain behind phase 2) ----------
-    if (sc < ncol) {
+    if (!FOLD && sc < ncol) {
         const int64_t col = col0 + sc;
         if (!PRE) {
             sc_ps = ldg(&p.Ph[col * pitchGh + nG]); sc_psd = ldg(&p.ps_d[col]);             // spcpl.py:246
             if constexpr (FULL)
                 if (OPT(rainrate)) { sc_rain = OPT(rain)[col]; sc_rl = OPT(rain_last)[col]; }
         }
-        stg<WT>(&p.f_ps[col], Divisor<T>(p.dt).div(p.factor * (sc_ps - sc_psd)));          // spcpl.py:332
+        put_f_ps(col, sc_ps, sc_psd);
         if constexpr (FULL) {
             if (OPT(ps)) OPT(ps)[col] = sc_ps;
             if (OPT(rainrate)) OPT(rainrate)[col] = (sc_rain - sc_rl) / p.dt;           // spcpl.py:325
@@ -218,13 +293,13 @@ __global__ __launch_bounds__(BLK) void k_forward(const FwdP<T, FULL> p)
                 if (OPT(qt)) OPT(qt)[o] = qt;
             }
         } else {                                                                      // fused K2, spcpl.py:764
-            const int ei = e - n2, c = ei / nG, m = ei - c * nG;
+            // entry (c, m); FOLD: the entry of phase-A item ei = (c, k), m = nG - 1 - k
+            const int ei = e - n2 + HELD, c = ei / nG, r = ei - c * nG, m = FOLD ? nG - 1 - r : r;
             const int64_t col = col0 + c, gh = col * pitchGh;
             const T zgh = (PRE && e == tid) ? pre_zgh : ldg(&p.Zghalf[gh + (nG - 1 - m)]);
             const T zs = (PRE && e == tid) ? pre_zs : ldg(&p.Zghalf[gh + nG]);
             const T Zh_k = div_grav(zgh - zs);                                        // spcpl.py:197
-            const T *const zh = d.shared_grid ? lzh : lzh + (size_t)c * nL;
-            p.idx[col * pitchG + m] = ss_right(zh, nL, Zh_k);
+            put_idx(c, col, m, Zh_k);
         }
     }
     STAMP(4);

@@ -64,11 +64,24 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
         zf0 = load_zf(col0 + c, (col0 + c) * pitchG + k);
     }
     if (d.shared_grid && tid < nL) hs0 = ldg(&p.zf[tid]);
+    // SPARE (PRE, 256 threads, one item per loop round): the waves behind the last GCM item have no use for `pre`.  Where
+    // their lanes can take EVERY staging item from BLK on, they load them in this same round trip into pre's registers (one
+    // variable: no register is added) and write them to LDS behind the staging loop, which then ends at BLK: at 91<->160
+    // with two columns the second staging round, 64 items on wave 0 with three waves waiting at the barrier, is gone.
+    // (Sharing the later items between spare lanes and loop was measured too: 137<->512 at one column, +2.4 %.)
+    constexpr bool SPARE = PRE && sizeof(T) == 8 && BLK == BLOCK;   // (512 / 1024 threads: one item per thread, nothing later)
+    const int spare0 = (n1 + 63) & ~63;                                     // first lane of the waves without a GCM item
+    const bool spare = SPARE && n2 > BLK && n2 - BLK <= BLK - spare0;
+    const int n2l = spare ? BLK : n2;                                       // staging items of the loop
     GcmIn<T> pre = {};
     if (PRE && tid < n1) {
         const int c = tid / nG, k = tid - c * nG;
         const int64_t cg = (col0 + c) * pitchG;
         pre = load_gcm(p, cg + k, cg + (nG - 1 - k));
+    } else if (spare && tid >= spare0 && BLK + (tid - spare0) < n2) {
+        const int e = BLK + (tid - spare0), c = e / nL, l = e - c * nL;
+        const Stage sp = load_stage((col0 + c) * pitchL + l);
+        pre.tt = sp.t; pre.sh = sp.qt; pre.ql = sp.ql; pre.qi = sp.qi; pre.u = sp.u; pre.v = sp.v; pre.a = sp.h;
     }
     STAMP(1);
 
@@ -77,12 +90,12 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
     // -5 % at config 3 with the quotients through fp64; the same scheme in K1<float> was SLOWER (86 against 78-80 us:
     // 63 instead of 48 VGPRs and 8 scalar spills) and is not used there.
     constexpr int UF = sizeof(T) == 4 ? 2 : 1;
-    for (int e0 = tid; e0 < n2; e0 += UF * BLK) {
+    for (int e0 = tid; e0 < n2l; e0 += UF * BLK) {
         Stage st[UF];
 #pragma unroll
         for (int u = 0; u < UF; ++u) {
             const int e = e0 + u * BLK;
-            if (e < n2) {
+            if (e < n2l) {
                 const int c = e / nL, l = e - c * nL;
                 st[u] = (e == tid) ? st0 : load_stage((col0 + c) * pitchL + l);
             }
@@ -90,7 +103,7 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
 #pragma unroll
         for (int u = 0; u < UF; ++u) {
             const int e = e0 + u * BLK;
-            if (e < n2) {
+            if (e < n2l) {
                 const int c = e / nL, l = e - c * nL;
                 T *const s = lds + (size_t)c * per_col + l;
                 s[0] = st[u].t;
@@ -102,6 +115,17 @@ template <typename T, int NG, int NL, int WT, int BLK = BLOCK, bool PRE = true> 
                 if (!d.shared_grid) lh[e] = st[u].h;
             }
         }
+    }
+    if (spare && tid >= spare0 && BLK + (tid - spare0) < n2) {              // the items the spare lanes hold in `pre`
+        const int e = BLK + (tid - spare0), c = e / nL, l = e - c * nL;
+        T *const s = lds + (size_t)c * per_col + l;
+        s[0] = pre.tt;
+        s[nL] = pre.sh;
+        s[2 * nL] = pre.ql;
+        s[3 * nL] = pre.qi;
+        s[4 * nL] = pre.u;
+        s[5 * nL] = pre.v;
+        if (!d.shared_grid) lh[e] = pre.a;
     }
     if (d.shared_grid)
         for (int e = tid; e < nL; e += BLK) lh[e] = (e == tid) ? hs0 : ldg(&p.zf[e]);
