@@ -1,0 +1,1 @@
+"""stand-in package, see oracle/refshim/spc_refshim.py"""

@@ -9,15 +9,18 @@ product package ``sp_coupler_amd``.
 
 Pinning status
 --------------
-* The reference cannot be imported in the build container (``omuse``/``amuse`` are absent and stay
-  absent), so no output of the reference itself is available.
+* PINNED by numbers the reference's own unmodified functions returned under the units shim of ``oracle/refshim``
+  (``tests/golden/ref_*.npz``, recorder ``tests/golden/make_reference_goldens.py``): every function below reproduces every
+  recorded array bit for bit (``tests/test_reference_pins_cpu.py``) -- ``convert_profiles``, ``set_les_forcings`` with surface
+  coupling, ``set_gcm_tendencies`` linear and conservative, ``cloud_fraction_indices``, ``output_column_conversion``,
+  ``interp_c`` / ``interp_rho`` / ``integral`` on layers of more than 128 cells, and the helpers.
 * PINNED by the reference's own tests: ``exner``/``iexner``/``rms`` (``splib/test/sputils_test.py:10-39``)
   and the cloud-fraction level-index map (``splib/test/spcpl_test.py:10-16`` with the dummy LES grid of
   ``splib/spdummy.py:219-222,261-262,319-321``) -- see ``tests/golden/reference_known_answers.json``.
 * The interpolation/searchsorted arithmetic calls the very same third-party routines the reference
   calls (``numpy.interp`` at ``sputils.py:86`` and ``numpy.searchsorted`` at ``sputils.py:91``).
-* Everything else (interpolated profiles, forcings, tendencies) follows the reference line by line
-  but is **parity unpinned** by any reference fixture: the reference's tests hold none for it.
+* Still parity unpinned, by name: the polygon branch of ``get_mask_indices`` (shapely), the sequencing of ``splib.step``
+  and ``spio``.  ``start_index`` is internal to the reference's ``set_gcm_tendencies``: pinned through the zeroed tendencies.
 
 Per-column functions follow the reference's operation order exactly; citations are
 ``file:line`` relative to the reference root.

@@ -4,8 +4,9 @@
 itself calls -- NumPy array arithmetic, ``ndarray.sum()``, ``numpy.argmax``, ``scipy.optimize.brentq`` -- for one
 LES (one column), without AMUSE units (every unit on this path is SI-coherent with factor 1).
 
-PARITY UNPINNED: the reference's tests hold no fixture for this function; the restatement follows the source line
-by line (citations below) and the product kernel is compared with it.
+PINNED: the reference's own unmodified function, run under the units shim of oracle/refshim on the inputs of
+tests/golden/vnudge_small.npz (seed 42, constantT False and True), gave tests/golden/ref_vnudge.npz; this restatement reproduces
+qt, qt_beta, qt_alpha, qt_std and thl bit for bit (tests/test_reference_pins_cpu.py), with every branch reached.
 
 Also here, for the CPU suite: scalar restatements of the two third-party algorithms the HIP kernel re-implements,
 ``brentq_restated`` (scipy/optimize/Zeros/brentq.c of the installed scipy 1.15.3, absent from /root/reference) and

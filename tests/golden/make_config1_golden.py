@@ -4,9 +4,10 @@ column-exchange for BASELINE.json's config 1 (T21 bundled case: 2 SP columns; th
 L19, BASELINE.json states 91 -- both are kept), 160 LES levels, dt = 900 s, factor = 1.
 
 PROVENANCE: the expected outputs come from THIS repo's NumPy oracle (oracle/spcpl_oracle.py), not from the
-reference itself -- the reference cannot be imported here (omuse/amuse absent).  They pin the oracle against
-drift and give the HIP path a fixed vector; they do NOT pin parity with the reference ("parity unpinned"
-beyond tests/golden/reference_known_answers.json).  float64, stored exactly.
+reference itself.  They pin the oracle against drift and give the HIP path a fixed vector.  Parity with the
+reference is pinned elsewhere: tests/golden/ref_*.npz hold what the reference's own functions returned
+(make_reference_goldens.py), and the oracle that wrote these files reproduces them bit for bit
+(tests/test_reference_pins_cpu.py).  float64, stored exactly.
 usage: python tests/golden/make_config1_golden.py"""
 import os
 import sys

@@ -3,9 +3,10 @@
 (splib/spcpl.py:613-744) for one small synthetic LES (12 x 10 x 24), with and without constantT.
 
 PROVENANCE: the expected outputs come from THIS repo's oracle (oracle/vnudge_oracle.py: NumPy + scipy.optimize.brentq,
-the routines the reference itself calls), not from the reference -- it cannot be imported here (omuse/amuse absent) and
-its tests hold no fixture for this function.  They pin the oracle (and the installed numpy / scipy) against drift and
-give the HIP path a fixed vector; they do NOT pin parity with the reference ("parity unpinned").  float64, stored exactly.
+the routines the reference itself calls), not from the reference.  They pin the oracle (and the installed numpy / scipy)
+against drift and give the HIP path a fixed vector.  Parity with the reference is pinned by tests/golden/ref_vnudge.npz: the
+reference's own variability_nudge, run on the inputs stored HERE (make_reference_goldens.py), returned the same qt, beta,
+alpha, qt_std and thl bit for bit (tests/test_reference_pins_cpu.py).  float64, stored exactly.
 usage: python tests/golden/make_vnudge_golden.py"""
 import os
 import sys

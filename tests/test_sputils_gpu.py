@@ -4,7 +4,8 @@ spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_* of the C ABI).
 * the reference's own test file for these helpers (splib/test/sputils_test.py:10-47) restated against the GPU module:
   same numbers, same assertions, same tolerance (1e-10) -- these pin exner / iexner / rms;
 * bit parity with NumPy (numpy.interp / numpy.searchsorted are what the reference calls) and with the oracle's
-  restatement of integral / interp_c / interp_rho (parity unpinned by the reference: it holds no fixture for them)."""
+  restatement of integral / interp_c / interp_rho (itself pinned to the reference's own functions by
+  tests/golden/ref_thick_*.npz: tests/test_reference_pins_cpu.py)."""
 import json
 import os
 
