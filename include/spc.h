@@ -622,6 +622,50 @@ int spc_les_advect_strip(int jtot, int ktot, int elem_size);
  * 0: bad arguments */
 int spc_les_advect_rows(int64_t n_les, int itot, int jtot, int ktot);
 
+/* ---- vertical upwind advection of the device-resident LES fields from continuity (kernel family K17) -------------------------- */
+/* One explicit first-order upwind step along k in advective form, by the mass flux that continuity gives K16's horizontal face
+ * Courant numbers.  Fields, u and v are [n_les][itot][jtot][ktot] (layout and offsets as K10), element type T; every operation
+ * is rounded once in T, never an fma, and the kernel holds no division.  hx, hy [n_les] are K16's.  g and r are profiles
+ * [n_les x ktot], rows pitch_prof apart: g = rho * dz (DeviceLESEnsemble.water_path_weights()) and r = 1 / g, formed in float64
+ * (sp_coupler_amd/advection.py: vertical_profiles) and rounded to T once; neither depends on dt.  Per cell (l, i, j, k), with
+ * cw, ce, cs, cn EXACTLY K16's face numbers at level k:
+ *   d    = (ce - cw) + (cn - cs)                                  the Courant divergence of the cell
+ *   e    = g[l][k] * d
+ *   M[0] = +0;   M[k+1] = M[k] - e                                SEQUENTIAL in k from the ground: the mass through the upper face
+ *   cb   = M[k] * r[l][k];   ct = M[k+1] * r[l][k]
+ *   pb   = cb > 0 ? cb : 0;  pt = ct < 0 ? -ct : 0                a NaN face gives +0
+ *   km   = k ? k-1 : 0;      kp = k+1 < ktot ? k+1 : ktot-1
+ *   out[f] = (x + pb * (x[km] - x)) + pt * (x[kp] - x)            x = fields[f]
+ *   s    = pb + pt;          cmax[l] = the maximum of s over the cells of LES l (the launch zeroes it first)
+ *   mtop[l][i][j][k] = M[k+1]
+ * The ground is closed (M[0] = 0); the lid is open with zero gradient: air that enters through the top carries the top cell's
+ * own value.  u, v and the fields are read only; a field may be u or v itself.  Every out[f] and mtop is written whole.  s is
+ * never NaN and never negative.  With winds that are uniform per level every d is +0: M = 0, cmax = 0, and every finite field
+ * keeps its bits; a constant finite field keeps its bits under any winds.  Special values get no rule of their own: a NaN wind
+ * makes M NaN from its level upward in the columns whose divergence reads it, and a NaN M closes its face.  n_fields == 0 with
+ * cmax and / or mtop is the probe: only the winds and the profiles are read.  Nothing to do (no field, no cmax, no mtop),
+ * pitch_prof < ktot, and an out[f], mtop or cmax EQUAL to an input or to another output are SPC_ERR_INVALID_ARGUMENT; arrays
+ * that overlap in part are not detected and must not be passed.  ktot == 1 is allowed.  A workgroup takes
+ * spc_les_vadvect_cols_per_block(ktot, sizeof(T)) columns into LDS; above the largest ktot of which 16 columns fit (1 279 levels
+ * of 8 bytes, 2 559 of 4) the launch is SPC_ERR_UNSUPPORTED.  The rule is this library's definition.      */
+#define SPC_VADVECT_MAX_FIELDS 6
+typedef struct spc_les_vadvect_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_fields; /* n_fields 0 ... SPC_VADVECT_MAX_FIELDS                             */
+    const void *u, *v;                  /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *fields[SPC_VADVECT_MAX_FIELDS]; /* device [n_les][itot][jtot][ktot], read only               */
+    void *out[SPC_VADVECT_MAX_FIELDS];  /* device [n_les][itot][jtot][ktot], written whole                   */
+    const void *hx, *hy;                /* device [n_les]: 0.5 dt / dx and 0.5 dt / dy                       */
+    void *cmax;                         /* device [n_les], or NULL                                           */
+    const void *g, *r;                  /* device [n_les x ktot] each, rows pitch_prof apart: rho dz, 1 / g  */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+    void *mtop;                         /* device [n_les][itot][jtot][ktot], written whole, or NULL          */
+} spc_les_vadvect_args;
+int spc_les_vadvect_f64(const spc_les_vadvect_args *args, void *stream);
+int spc_les_vadvect_f32(const spc_les_vadvect_args *args, void *stream);
+/* columns per workgroup of k_les_vadvect for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
+int spc_les_vadvect_cols_per_block(int ktot, int elem_size);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */
 const char *spc_last_error(void);   /* text of the calling thread's last failure ("" if none)     */

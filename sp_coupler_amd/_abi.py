@@ -161,6 +161,15 @@ class LesAdvectArgs(ctypes.Structure):
                 + [("fields", c_void_p * SPC_ADVECT_MAX_FIELDS), ("out", c_void_p * SPC_ADVECT_MAX_FIELDS)] + _ptrs("hx", "hy", "cmax"))
 
 
+SPC_VADVECT_MAX_FIELDS = 6
+
+
+class LesVadvectArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32)] + _ptrs("u", "v")
+                + [("fields", c_void_p * SPC_VADVECT_MAX_FIELDS), ("out", c_void_p * SPC_VADVECT_MAX_FIELDS)]
+                + _ptrs("hx", "hy", "cmax", "g", "r") + [("pitch_prof", c_int64), ("mtop", c_void_p)])
+
+
 THERMO_TABLE_LIBRARY, THERMO_TABLE_LDS, THERMO_TABLE_GLOBAL = 0, 1, 2      # spc_les_thermo_args.table_mode
 
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
@@ -216,6 +225,9 @@ PROTOTYPES = {
     "spc_les_advect_f32": (ctypes.c_int, [ctypes.POINTER(LesAdvectArgs), c_void_p]),
     "spc_les_advect_strip": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "spc_les_advect_rows": (ctypes.c_int, [c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spc_les_vadvect_f64": (ctypes.c_int, [ctypes.POINTER(LesVadvectArgs), c_void_p]),
+    "spc_les_vadvect_f32": (ctypes.c_int, [ctypes.POINTER(LesVadvectArgs), c_void_p]),
+    "spc_les_vadvect_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

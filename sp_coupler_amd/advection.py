@@ -1,8 +1,10 @@
 """The constants and the coefficients of K16, the horizontal upwind advection of the device-resident LES fields on the doubly
-periodic plane (include/spc.h: spc_les_advect_*).
+periodic plane (include/spc.h: spc_les_advect_*), and the profiles of K17, their vertical advection by the mass
+flux of continuity (spc_les_vadvect_*).
 
 The kernel takes hx = 0.5 dt / dx and hy = 0.5 dt / dy per LES: formed ONCE here, in float64 NumPy, and rounded once to the
-element type on upload; the kernel and the NumPy oracle of the tests receive the same arrays, and neither divides."""
+element type on upload; the kernel and the NumPy oracle of the tests receive the same arrays, and neither divides.  K17 takes
+g = rho dz and r = 1 / g per LES and level (``vertical_profiles``), formed the same way; neither depends on dt."""
 import math
 
 import numpy
@@ -36,3 +38,22 @@ def substeps(c, cfl=CFL, max_substeps=MAX_SUBSTEPS):
         raise RuntimeError("the advection (K16) found the Courant sum c = %r: %d substeps at cfl %g, more than max_substeps = %d"
                            % (c, n_sub, float(cfl), int(max_substeps)))
     return n_sub
+
+
+def vertical_profiles(weights):
+    """float64 ``(g, r)``, the shape of ``weights``: g = rho * dz (``DeviceLESEnsemble.water_path_weights()``) and r = 1 / g, the
+    profiles of K17; ValueError unless every weight is positive and finite"""
+    g = numpy.array(weights, dtype=numpy.float64, order="C")
+    if not (numpy.isfinite(g).all() and (g > 0).all()):
+        raise ValueError("the weights rho * dz must be positive and finite")
+    return g, 1.0 / g
+
+
+def vertical_wind(mtop, rhobf, dt):
+    """W in m/s at the upper faces of the cells from K17's ``mtop`` [n x itot x jtot x nL] (the mass through the upper face in
+    a step of ``dt`` seconds, kg / m2, positive upward) and the density profile ``rhobf`` [n x nL] on the same device:
+    mtop / (rho_face * dt), rho_face[k] = 0.5 (rhobf[k] + rhobf[min(k + 1, nL - 1)]).  A torch expression, not bit-checked."""
+    import torch
+    up = torch.cat([rhobf[:, 1:], rhobf[:, -1:]], dim=1)
+    face = 0.5 * (rhobf + up)
+    return mtop / (face * float(dt))[:, None, None, :]

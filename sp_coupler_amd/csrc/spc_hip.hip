@@ -30,6 +30,8 @@
 //                  of a tile of columns in LDS, the elimination done on the host): spc_diffuse.hpp, kernel and host side
 //   K16 k_les_advect  one explicit upwind step of the horizontal advection of those fields on the periodic plane (neighbours
 //                  along i and j, separate output buffers, the Courant sums): spc_advect.hpp, kernel and host side
+//   K17 k_les_vadvect  one explicit upwind step of the vertical advection of those fields by the mass flux of continuity (K16's
+//                  face numbers, a serial chain along k per column of a tile in LDS): spc_vadvect.hpp, kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -84,6 +86,7 @@ namespace {
 #include "spc_micro.hpp"
 #include "spc_diffuse.hpp"
 #include "spc_advect.hpp"
+#include "spc_vadvect.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -112,6 +115,9 @@ namespace {
 #define SPC_ADVECT_HOST
 #include "spc_advect.hpp"
 #undef SPC_ADVECT_HOST
+#define SPC_VADVECT_HOST
+#include "spc_vadvect.hpp"
+#undef SPC_VADVECT_HOST
 
 }  // namespace
 
@@ -196,6 +202,10 @@ int spc_les_advect_f64(const spc_les_advect_args *a, void *s) { return les_advec
 int spc_les_advect_f32(const spc_les_advect_args *a, void *s) { return les_advect_impl<float>(a, s); }
 int spc_les_advect_strip(int jtot, int ktot, int elem_size) { return advect_strip(jtot, ktot, elem_size); }
 int spc_les_advect_rows(int64_t n_les, int itot, int jtot, int ktot) { return advect_rows(n_les, itot, jtot, ktot); }
+
+int spc_les_vadvect_f64(const spc_les_vadvect_args *a, void *s) { return les_vadvect_impl<double>(a, s); }
+int spc_les_vadvect_f32(const spc_les_vadvect_args *a, void *s) { return les_vadvect_impl<float>(a, s); }
+int spc_les_vadvect_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

@@ -1,0 +1,303 @@
+// spc_vadvect.hpp -- K17: one explicit first-order upwind step of the VERTICAL advection of the device-resident LES fields by
+// the mass flux that continuity gives the horizontal winds, kernel and host side.  spc_hip.hip includes it twice, like
+// spc_diffuse.hpp and spc_advect.hpp: with the kernel among the device headers, and -- SPC_VADVECT_HOST defined -- after
+// spc_launch.hpp and the host side of spc_slab.hpp (slab_check_extents).
+//
+// Fields are [n_les][itot][jtot][ktot], C order, ktot contiguous, 64-bit element offsets (spc_slab.hpp).  The rule
+// (include/spc.h) per cell (l, i, j, k), in T, one rounding per operation, never an fma (the build has FP contraction off), no
+// division, im / ip / jm / jp the periodic neighbours, g = rho dz and r = 1 / g the profiles [n_les x ktot]:
+//   cw, ce, cs, cn  K16's face Courant numbers at level k (spc_advect.hpp)
+//   d  = (ce - cw) + (cn - cs);   e = g[l][k] * d
+//   M[0] = +0;   M[k + 1] = M[k] - e                      the mass through the upper face, sequential in k from the ground
+//   cb = M[k] * r[l][k];   ct = M[k + 1] * r[l][k];   pb = cb > 0 ? cb : 0;   pt = ct < 0 ? -ct : 0
+//   x' = (x + pb * (x[km] - x)) + pt * (x[kp] - x)        km = k ? k - 1 : 0, kp = k + 1 < ktot ? k + 1 : ktot - 1
+//   s  = pb + pt;   cmax[l] = max over the cells of LES l of s;   mtop[l][i][j][k] = M[k + 1]
+// The shape joins K16's neighbours across i and j with K15's serial chain along k.  A workgroup takes C consecutive columns of
+// the flat column index (vad_cols: the largest of 64, 32, 16 whose tile fits the LDS budget of K15), a contiguous run of
+// C * ktot cells that may span rows i and LES -- l, i and j are per column:
+//   1. all VAD_THREADS lanes walk the run coalesced (a lane takes every VAD_THREADS-th cell, so a wave's accesses are one
+//      contiguous stretch whatever ktot is and a view off the 16-byte grid takes the same path), form e from the six wind
+//      values of the cell and store it to LDS, column c at c * pitch, pitch = ktot | 1: ODD, so the lanes of phase 2 that read
+//      the same k of their columns hit distinct banks;
+//   2. lane c < C runs M[k + 1] = M[k] - e[k] up its column in LDS, M[k + 1] overwriting e[k]: one dependent subtraction per
+//      level, the LDS reads of a chunk of VAD_U levels issued before its arithmetic;
+//   3. all lanes walk the run again: M[k] and M[k + 1] from LDS, x[km], x, x[kp] from global memory (the k - 1 / k + 1 values lie
+//      in the cache lines the neighbouring lanes fetch as their own cells), out[f] and mtop written coalesced.  The face
+//      numbers pb, pt of a cell are formed once and used by all NF fields (a template argument).
+// The tile is C * pitch elements whatever the number of fields.  cmax: a lane keeps the maximum of its s for the LES it is in
+// (its cells come in ascending l; it issues an atomicMax of its own when l changes, which happens only in a tile that spans
+// LES); at the end a wave whose lanes all ended in one LES reduces by shuffles and its first lane issues ONE atomicMax on the
+// unsigned bit pattern (s is never NaN and never negative: the order of the patterns is the order of the values), else every
+// lane issues its own.  The launcher zeroes cmax first.  The outputs are separate buffers written whole, so no workgroup
+// waits for another.
+#ifndef SPC_VADVECT_HOST
+
+constexpr int VAD_THREADS = 256;
+constexpr int VAD_MAXF = 6;
+constexpr int VAD_U = 8;                        // levels per chunk of the column recurrence
+constexpr int VAD_LDS_SHARED = MAX_LDS_BYTES;   // tile budget of 64 and 32 columns: at least two workgroups per CU
+
+__host__ __device__ constexpr int vad_pitch(int ktot) { return ktot | 1; }
+
+// columns per workgroup of ktot levels of esize bytes, 0: unsupported (K15's budget rule: dif_cols)
+inline int vad_cols(int ktot, int esize)
+{
+    if (ktot < 1 || (esize != 4 && esize != 8) || ktot > HARD_LDS_BYTES / 16 / esize) return 0;
+    const int64_t col = (int64_t)vad_pitch(ktot) * esize;
+    if (64 * col <= VAD_LDS_SHARED) return 64;
+    if (32 * col <= VAD_LDS_SHARED) return 32;
+    return 16 * col <= HARD_LDS_BYTES ? 16 : 0;
+}
+
+template <typename T> struct LesVadvectP {
+    const T *u, *v;
+    const T *field[VAD_MAXF];
+    T *out[VAD_MAXF];
+    const T *hx, *hy;
+    const T *g, *r;
+    T *cmax;                       // or nullptr
+    T *mtop;                       // or nullptr
+    int64_t ncols;                 // n_les * itot * jtot
+    int64_t pitch_prof;
+    int32_t itot, jtot, ktot;
+    int32_t nij;                   // itot * jtot
+    int32_t cols;                  // C: columns per workgroup
+};
+
+// where cell e of a workgroup's run lies: column c of the tile, level k, LES l, row i and j
+struct VadCell {
+    int c, k, i, j;
+    int64_t l;
+};
+
+__device__ __forceinline__ VadCell vad_cell(const int e, const int ktot, const int64_t l0, const uint32_t rem0, const uint32_t nij, const uint32_t jtot)
+{
+    VadCell w;
+    w.c = e / ktot;
+    w.k = e - w.c * ktot;
+    const uint32_t q = rem0 + (uint32_t)w.c;                     // the column within LES l0, or beyond it: a tile may span LES
+    const uint32_t dl = q / nij, rem = q - dl * nij;
+    w.l = l0 + dl;
+    w.i = (int)(rem / jtot);
+    w.j = (int)(rem - (uint32_t)w.i * jtot);
+    return w;
+}
+
+template <typename T> __device__ __forceinline__ void vad_atomic_max(T *cmax, const int64_t l, const T s)
+{
+    using U = typename AdvectBits<T>::type;
+    U bits;
+    __builtin_memcpy(&bits, &s, sizeof(T));
+    if (bits) atomicMax(reinterpret_cast<U *>(cmax) + l, bits);
+}
+
+// M[k + 1] = M[k] - e[k] up one column in LDS, M[k + 1] overwriting e[k]
+template <typename T> __device__ __forceinline__ void vad_column(T *x, const int ktot)
+{
+    T M = (T)0;
+    int k = 0;
+    for (; k + VAD_U <= ktot; k += VAD_U) {
+        T ce[VAD_U];
+#pragma unroll
+        for (int u = 0; u < VAD_U; ++u) ce[u] = x[k + u];
+#pragma unroll
+        for (int u = 0; u < VAD_U; ++u) {
+            M = M - ce[u];
+            x[k + u] = M;
+        }
+    }
+    for (; k < ktot; ++k) {
+        M = M - x[k];
+        x[k] = M;
+    }
+}
+
+// grid ceil(ncols / C); dynamic LDS: C * vad_pitch(ktot) elements
+template <typename T, int NF> __global__ __launch_bounds__(VAD_THREADS) void k_les_vadvect(const LesVadvectP<T> p)
+{
+    extern __shared__ __align__(16) unsigned char vad_lds[];
+    T *tile = reinterpret_cast<T *>(vad_lds);
+    const int ktot = p.ktot, P = vad_pitch(ktot), C = p.cols;
+    const int itot = p.itot, jtot = p.jtot;
+    const int64_t col0 = (int64_t)blockIdx.x * C;
+    const int64_t left = p.ncols - col0;
+    const int nc = left < C ? (int)left : C;                     // the last tile is partial
+    const int len = nc * ktot;
+    const int64_t l0 = col0 / p.nij;
+    const uint32_t rem0 = (uint32_t)(col0 - l0 * p.nij);
+    const int64_t run = col0 * ktot;                             // the first cell of the tile
+    const int64_t row = (int64_t)jtot * ktot;                    // cells of one row i
+    // 1. e = g * ((ce - cw) + (cn - cs)) of every cell of the run -> LDS
+    for (int e = threadIdx.x; e < len; e += VAD_THREADS) {
+        const VadCell w = vad_cell(e, ktot, l0, rem0, (uint32_t)p.nij, (uint32_t)jtot);
+        const int64_t o = run + e;
+        const int64_t ow = o + (w.i ? -row : (int64_t)(itot - 1) * row);
+        const int64_t oe = o + (w.i + 1 < itot ? row : -(int64_t)(itot - 1) * row);
+        const int64_t os = o + (w.j ? -(int64_t)ktot : (int64_t)(jtot - 1) * ktot);
+        const int64_t on = o + (w.j + 1 < jtot ? (int64_t)ktot : -(int64_t)(jtot - 1) * ktot);
+        const T uw = p.u[ow], uc = p.u[o], ue = p.u[oe];
+        const T vs = p.v[os], vc = p.v[o], vn = p.v[on];
+        const T hx = p.hx[w.l], hy = p.hy[w.l];
+        const T gk = p.g[w.l * p.pitch_prof + w.k];
+        const T aw = uw + uc, ae = uc + ue, as = vs + vc, an = vc + vn;
+        const T cw = aw * hx;
+        const T ce = ae * hx;
+        const T cs = as * hy;
+        const T cn = an * hy;
+        const T dx = ce - cw;
+        const T dy = cn - cs;
+        const T d = dx + dy;
+        tile[w.c * P + w.k] = gk * d;
+    }
+    __syncthreads();
+    // 2. the mass flux through the upper faces, one column per lane
+    if ((int)threadIdx.x < nc) vad_column<T>(tile + threadIdx.x * P, ktot);
+    __syncthreads();
+    // 3. the upwind step of every field, mtop and the Courant sums
+    T smax = (T)0;
+    int64_t lcur = -1;
+    for (int e = threadIdx.x; e < len; e += VAD_THREADS) {
+        const VadCell w = vad_cell(e, ktot, l0, rem0, (uint32_t)p.nij, (uint32_t)jtot);
+        const int64_t o = run + e;
+        const int k = w.k;
+        const T *M = tile + w.c * P;
+        const T Mb = k ? M[k - 1] : (T)0;
+        const T Mt = M[k];
+        const int64_t okm = k ? o - 1 : o;
+        const int64_t okp = k + 1 < ktot ? o + 1 : o;
+        const T rk = p.r[w.l * p.pitch_prof + k];
+        const T cb = Mb * rk;
+        const T ct = Mt * rk;
+        const T pb = cb > (T)0 ? cb : (T)0;
+        const T pt = ct < (T)0 ? -ct : (T)0;
+        const T s = pb + pt;
+        if (p.cmax) {
+            if (w.l != lcur) {                                   // the lane's cells come in ascending l
+                if (lcur >= 0) vad_atomic_max<T>(p.cmax, lcur, smax);
+                lcur = w.l;
+                smax = (T)0;
+            }
+            smax = s > smax ? s : smax;
+        }
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            const T x = p.field[f][o], xm = p.field[f][okm], xp = p.field[f][okp];
+            const T db = xm - x, dt = xp - x;
+            const T tb = pb * db;
+            const T tt = pt * dt;
+            T y = x + tb;
+            y = y + tt;
+            p.out[f][o] = y;
+        }
+        if (p.mtop) p.mtop[o] = Mt;
+    }
+    if (p.cmax) {
+        long long lw = lcur;                                     // the last LES of the wave (-1: no lane had a cell)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const long long o = __shfl_xor(lw, d, 64);
+            lw = o > lw ? o : lw;
+        }
+        if (__all(lcur < 0 || lcur == lw)) {
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                const T o = __shfl_xor(smax, d, 64);
+                smax = o > smax ? o : smax;
+            }
+            if ((threadIdx.x & 63) == 0 && lw >= 0) vad_atomic_max<T>(p.cmax, lw, smax);
+        } else if (lcur >= 0) {
+            vad_atomic_max<T>(p.cmax, lcur, smax);
+        }
+    }
+}
+
+#else  // SPC_VADVECT_HOST ---------------------------------------------------------------------------------------------------
+
+template <typename T, int NF> static int les_vadvect_launch(const LesVadvectP<T> &p, void *stream)
+{
+    const size_t smem = (size_t)p.cols * vad_pitch(p.ktot) * sizeof(T);
+    const int rc = ensure_lds(k_les_vadvect<T, NF>, smem, "k_les_vadvect");
+    if (rc) return rc;
+    const int64_t grid = (p.ncols + p.cols - 1) / p.cols;         // (checked against INT32_MAX by the caller, before cmax is zeroed)
+    hipLaunchKernelGGL((k_les_vadvect<T, NF>), dim3((unsigned)grid), dim3(VAD_THREADS), smem, (hipStream_t)stream, p);
+    return launch_status("k_les_vadvect");
+}
+
+template <typename T> static int les_vadvect_impl(const spc_les_vadvect_args *a, void *stream)
+{
+    if (!a) return fail(SPC_ERR_INVALID_ARGUMENT, "%sargs is NULL");
+    int rc = slab_check_extents("les_vadvect", a->n_les, a->itot, a->jtot, a->ktot);
+    if (rc) return rc;
+    static_assert(SPC_VADVECT_MAX_FIELDS == VAD_MAXF, "include/spc.h and spc_vadvect.hpp disagree on the fields per launch");
+    if (a->n_fields < 0 || a->n_fields > SPC_VADVECT_MAX_FIELDS)
+        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: field count %lld outside 0 ... %lld", "", (long long)a->n_fields, SPC_VADVECT_MAX_FIELDS);
+    if (a->n_fields == 0 && !a->cmax && !a->mtop)
+        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: no field, no cmax and no mtop: nothing to do");
+    if (a->pitch_prof < a->ktot)
+        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: pitch_prof %lld smaller than ktot", "", (long long)a->pitch_prof);
+    if (a->n_les == 0) return SPC_OK;
+    REQUIRE(a->u, "u"); REQUIRE(a->v, "v"); REQUIRE(a->hx, "hx"); REQUIRE(a->hy, "hy"); REQUIRE(a->g, "g"); REQUIRE(a->r, "r");
+    LesVadvectP<T> p = {};
+    // (equal base pointers are what is detected, as in K11, K14, K15 and K16: partially overlapping views are the caller's to avoid)
+    const void *in[6 + SPC_VADVECT_MAX_FIELDS] = {a->u, a->v, a->hx, a->hy, a->g, a->r};
+    const void *wr[2 + SPC_VADVECT_MAX_FIELDS];
+    int n_in = 6, n_wr = 0;
+    uintptr_t bits = 0;
+    for (int f = 0; f < a->n_fields; ++f) {
+        REQUIRE(a->fields[f], "fields[f]");
+        REQUIRE(a->out[f], "out[f]");
+        in[n_in++] = a->fields[f];
+        p.field[f] = (const T *)a->fields[f];
+        p.out[f] = (T *)a->out[f];
+    }
+    for (int f = 0; f < a->n_fields; ++f) {
+        for (int q = 0; q < n_wr; ++q)
+            if (wr[q] == a->out[f])
+                return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: out[%lld] and out[%lld] are the same array", "", q, f);
+        for (int q = 0; q < n_in; ++q)
+            if (in[q] == a->out[f])
+                return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: out[%lld] is also an input (every cell reads its neighbours' old values)", "", f);
+        wr[n_wr++] = a->out[f];
+    }
+    const void *extra[2] = {a->mtop, a->cmax};
+    for (int x = 0; x < 2; ++x) {
+        if (!extra[x]) continue;
+        for (int q = 0; q < n_wr; ++q)
+            if (wr[q] == extra[x])
+                return fail(SPC_ERR_INVALID_ARGUMENT, "les_vadvect: %s is the same array as another output", x ? "cmax" : "mtop");
+        for (int q = 0; q < n_in; ++q)
+            if (in[q] == extra[x])
+                return fail(SPC_ERR_INVALID_ARGUMENT, "les_vadvect: %s is also an input (it is written while they are read)", x ? "cmax" : "mtop");
+        wr[n_wr++] = extra[x];
+    }
+    for (int q = 0; q < n_in; ++q) bits |= (uintptr_t)in[q];
+    for (int q = 0; q < n_wr; ++q) bits |= (uintptr_t)wr[q];
+    if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: a pointer is not aligned to its element type");
+    const int C = vad_cols(a->ktot, (int)sizeof(T));
+    if (!C)
+        return fail(SPC_ERR_UNSUPPORTED, "%sles_vadvect: ktot %lld above the %lld levels of which 16 columns fit the LDS", "", (long long)a->ktot,
+                    (long long)(((HARD_LDS_BYTES / 16 / (int)sizeof(T)) - 1) | 1));
+    p.u = (const T *)a->u; p.v = (const T *)a->v; p.hx = (const T *)a->hx; p.hy = (const T *)a->hy;
+    p.g = (const T *)a->g; p.r = (const T *)a->r; p.cmax = (T *)a->cmax; p.mtop = (T *)a->mtop;
+    p.itot = a->itot; p.jtot = a->jtot; p.ktot = a->ktot;
+    p.nij = a->itot * a->jtot;
+    p.ncols = a->n_les * (int64_t)p.nij;
+    p.pitch_prof = a->pitch_prof;
+    p.cols = C;
+    if ((p.ncols + C - 1) / C > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_vadvect: too many workgroups");
+    if (a->cmax && hipMemsetAsync(a->cmax, 0, (size_t)a->n_les * sizeof(T), (hipStream_t)stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SPC_ERR_LAUNCH, "%sles_vadvect: cmax could not be zeroed");
+    }
+    switch (a->n_fields) {
+    case 0: return les_vadvect_launch<T, 0>(p, stream);
+    case 1: return les_vadvect_launch<T, 1>(p, stream);
+    case 2: return les_vadvect_launch<T, 2>(p, stream);
+    case 3: return les_vadvect_launch<T, 3>(p, stream);
+    case 4: return les_vadvect_launch<T, 4>(p, stream);
+    case 5: return les_vadvect_launch<T, 5>(p, stream);
+    default: return les_vadvect_launch<T, 6>(p, stream);
+    }
+}
+
+#endif

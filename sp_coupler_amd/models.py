@@ -701,7 +701,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     and QT (K15, ``Engine.les_diffuse``); tests/les_diffuse_ref.py holds the twin of that mode.
     After ``enable_advection()`` every step carries U, V, THL, QT and QR along i and j with the winds U and V on the periodic
     plane, in as many upwind substeps as the Courant sums ask for (K16, ``Engine.les_advect``); tests/les_advect_ref.py holds
-    the twin of that mode."""
+    the twin of that mode.  With ``vertical=True`` every substep also carries them along k by the mass flux of continuity (K17,
+    ``Engine.les_vadvect``) and ``get_vertical_wind_batched()`` returns W; tests/les_vadvect_ref.py holds that twin."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
@@ -907,8 +908,13 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     advect_substeps = None                             # the substeps of the last step
     _advect_spare = None                               # name -> the buffer K16 writes next (it reads the field)
     _advect_coef = None                                # ((dt, dx, dy) of the uploads, {substeps: device (hx, hy)})
+    advect_vertical = False                            # enable_advection(vertical=True): K17 follows every K16 substep
+    advect_courant_z = None                            # the largest vertical Courant sum any substep of the last step returned
+    _vadvect_prof = None                               # (the host weights of the upload, device (g, r))
+    _vadvect_mtop = None                               # the mass flux through the upper faces in the last substep, device
+    _vadvect_dt = None                                 # the seconds of that substep
 
-    def enable_advection(self, dx=None, dy=None, cfl=None, max_substeps=None):
+    def enable_advection(self, dx=None, dy=None, cfl=None, max_substeps=None, vertical=False):
         """from now on every ``evolve_model_batched`` advects the fields among U, V, THL, QT and QR that exist with the winds U
         and V on the doubly periodic plane (K16, ``Engine.les_advect``), after the step and before K15 / K14 /
         K12: ONE probe launch per device finds the largest Courant sum c of the whole step, n_sub = max(1, ceil(c / cfl))
@@ -917,12 +923,22 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         largest Courant sum of the substeps.  The profiles then are K10's means of the advected fields and QL follows the new
         QT.  ``dx`` and ``dy`` (m, scalars or one per LES) are also what the rows' get_dx / get_dy / get_xsize / get_ysize
         answer.  The coefficients are uploaded again whenever dt, n_sub, dx or dy changed.  The parameters default to those of
-        ``advection``.  Needs U and V fields.  Without this call every path of the ensemble is unchanged."""
+        ``advection``.  Needs U and V fields.  Without this call every path of the ensemble is unchanged.
+
+        ``vertical=True`` adds the vertical advection by the mass flux of continuity (K17, ``Engine.les_vadvect``): a K17 probe
+        follows K16's, both with the coefficients of the whole step, n_sub comes from the larger of their Courant sums, and
+        every substep is K16, a swap, K17 on the same fields (with the winds K16 just produced) into the same spare buffers and
+        a swap: 2 + 2 n_sub launches per device and step.  The profiles g = ``water_path_weights()`` and r = 1 / g are uploaded
+        once.  ``advect_courant_z`` holds the largest vertical Courant sum of the substeps (it can grow during them, so it is
+        recorded and refused only where it is not finite: RuntimeError), ``get_vertical_wind_batched()`` the vertical wind of
+        the last substep.  With the default every path, launch count and result is what it is without the argument."""
         from . import advection as adv
         if "U" not in self.fields3d or "V" not in self.fields3d:
             raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
         if not all(callable(getattr(e, "les_advect", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
             raise ValueError("the engine has no les_advect (K16)")
+        if vertical and not all(callable(getattr(e, "les_vadvect", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
+            raise ValueError("the engine has no les_vadvect (K17)")
         dx, dy = adv.DX if dx is None else dx, adv.DY if dy is None else dy
         adv.coefficients(1.0, dx, dy, n=self.n)                       # (ValueError for a spacing that is not positive, or not [n])
         self.dx = numpy.array(dx, dtype=numpy.float64) if numpy.ndim(dx) else float(dx)
@@ -932,6 +948,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if not self.advect_par["cfl"] > 0 or self.advect_par["max_substeps"] < 1:
             raise ValueError("the advection (K16) needs cfl > 0 and max_substeps >= 1")
         self.advection, self._advect_coef, self._advect_spare = True, None, {}
+        self.advect_vertical, self._vadvect_prof, self._vadvect_mtop, self._vadvect_dt = bool(vertical), None, None, None
+        self.advect_courant_z = None
 
     def _advect_coefs(self, dt, n_sub):
         """device (hx, hy) of the substeps dt / n_sub; uploaded where dt, n_sub, dx or dy are not those of the last step"""
@@ -968,6 +986,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
         keys = [k for k in self.ADVECT_KEYS if k in f]
         c = self._device_max(eng.les_advect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1)))
+        vertical = self.advect_vertical
+        if vertical:                                      # K17's probe: the vertical Courant sums of the whole step
+            g, r = self._vadvect_profiles()
+            c = max(c, self._device_max(eng.les_vadvect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1), g, r)))
         try:
             n_sub = adv.substeps(c, par["cfl"], par["max_substeps"])
         except RuntimeError:                              # nothing has been advected: QL and the profiles of the stepped fields
@@ -978,18 +1000,49 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         for k in keys:
             if spare.get(k) is None or spare[k] is f[k] or tuple(spare[k].shape) != tuple(f[k].shape):
                 spare[k] = self._per_device(torch.empty_like, f[k])
-        worst = None
+        if vertical and (self._vadvect_mtop is None or tuple(self._vadvect_mtop.shape) != tuple(f["U"].shape)):
+            self._vadvect_mtop = self._per_device(torch.empty_like, f["U"])
+        worst = worst_z = None
         for _ in range(n_sub):
             out = {k: spare[k] for k in keys}
             cm = eng.les_advect({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy)
             for k in keys:
                 f[k], spare[k] = spare[k], f[k]
             worst = cm if worst is None else self._per_device(torch.maximum, worst, cm)
+            if vertical:                                  # K17 reads the winds K16 just produced
+                out = {k: spare[k] for k in keys}
+                cz = eng.les_vadvect({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy, g, r, mtop=self._vadvect_mtop)
+                for k in keys:
+                    f[k], spare[k] = spare[k], f[k]
+                worst_z = cz if worst_z is None else self._per_device(torch.maximum, worst_z, cz)
         self.advect_substeps, self.advect_courant = n_sub, self._device_max(worst)
+        if vertical:
+            self._vadvect_dt = float(dt) / n_sub
+            self.advect_courant_z = self._device_max(worst_z)
         self._drop_water_paths()
         self._thermo_stale = True                         # thermo: K12 runs on the advected THL and QT before their next use
         if not self.diffusion:                            # (else the QL field and the means follow the diffused fields: _diffuse)
             self._follow_fields()
+        if vertical and not numpy.isfinite(self.advect_courant_z):
+            raise RuntimeError("the vertical advection (K17) found the Courant sum c = %r: the mass flux is not finite" % self.advect_courant_z)
+
+    def _vadvect_profiles(self):
+        """device (g, r) of K17: g = water_path_weights(), r = 1 / g; uploaded once, and again where the weights changed"""
+        from . import advection as adv
+        w = numpy.ascontiguousarray(self.water_path_weights())
+        if self._vadvect_prof is None or not numpy.array_equal(self._vadvect_prof[0], w):
+            self._vadvect_prof = (w, tuple(self._upload(a) for a in adv.vertical_profiles(w)))
+        return self._vadvect_prof[1]
+
+    def get_vertical_wind_batched(self):
+        """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the vertical wind W in m/s
+        at the UPPER faces of the cells, positive upward, that continuity gave the last substep of the last step
+        (``advection.vertical_wind`` of K17's mass flux); None before the first step of enable_advection(vertical=True)"""
+        from . import advection as adv
+        if not self.advect_vertical or self._vadvect_mtop is None or self._vadvect_dt is None:
+            return None
+        rho = self._upload(numpy.asarray(self.p["Rhobf"], dtype=numpy.float64))
+        return self._per_device(lambda m, rh: adv.vertical_wind(m, rh, self._vadvect_dt), self._vadvect_mtop, rho)
 
     def _follow_fields(self):
         """QL = max(QT - Qsat, 0) of the QT field as it is now (without thermo) and p[U, V, THL, QT, QL] = K10's means"""
@@ -1257,6 +1310,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             p["PS"] = p["PS"] + dt * self.tend["PS"]
         if self.advection:
             self._advect(dt)                              # 1 + n_sub K16 launches: U, V, THL, QT, QR carried along i and j; p[...]
+                                                          # (vertical: a K17 probe and a K17 launch behind every K16 substep)
         if self.diffusion:
             self._diffuse(dt)                             # one K15 launch: U, V, THL, QT mixed along k, the surface fluxes; p[...]
         if self.micro:

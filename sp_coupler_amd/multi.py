@@ -265,6 +265,18 @@ class MultiDeviceEngine:
             return None
         return cmax if cmax is not True else self._join(res, ex.bounds)
 
+    def les_vadvect(self, fields, out, u, v, hx, hy, g, r, cmax=True, mtop=None, **kw):
+        """K17 on every device's LES: dicts of Sharded fields and outputs (written block by block), Sharded winds, ``hx``, ``hy``
+        [n], the profiles ``g`` and ``r`` [n x ktot] and ``mtop`` (or None) in; the Sharded [n] vertical Courant sums out (None
+        without ``cmax``); one launch per device that holds rows"""
+        ex = self._example(u)
+        if ex is None:
+            return self.primary.les_vadvect(fields, out, u, v, hx, hy, g, r, cmax=cmax, mtop=mtop, **kw)
+        res = self._each("les_vadvect", ex, (fields, out, u, v, hx, hy, g, r), dict(kw, cmax=cmax, mtop=mtop))
+        if cmax is None or cmax is False:
+            return None
+        return cmax if cmax is not True else self._join(res, ex.bounds)
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

@@ -21,6 +21,8 @@ DIFFUSE_MUTANTS is the table of K15 (spc_diffuse.hpp), chosen with --diffuse; it
 tests/les_diffuse_ref.py, which tests/test_les_diffuse_gpu.py runs on the shipped library.
 ADVECT_MUTANTS is the table of K16 (spc_advect.hpp), chosen with --advect; its guards are the bodies of
 tests/les_advect_ref.py, which tests/test_les_advect_gpu.py runs on the shipped library.
+VADVECT_MUTANTS is the table of K17 (spc_vadvect.hpp), chosen with --vadvect; its guards are the bodies of
+tests/les_vadvect_ref.py, which tests/test_les_vadvect_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
@@ -35,6 +37,8 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --waterpath --build && python tools/mutation_control.py --waterpath > profiles/mutation_control_waterpath.log
        python tools/mutation_control.py --micro --build && python tools/mutation_control.py --micro > profiles/mutation_control_micro.log
        python tools/mutation_control.py --diffuse --build && python tools/mutation_control.py --diffuse > profiles/mutation_control_diffuse.log
+       python tools/mutation_control.py --advect --build && python tools/mutation_control.py --advect > profiles/mutation_control_advect.log
+       python tools/mutation_control.py --vadvect --build && python tools/mutation_control.py --vadvect > profiles/mutation_control_vadvect.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log"""
 import argparse
@@ -59,6 +63,7 @@ WATERPATH = "spc_waterpath.hpp"
 MICRO = "spc_micro.hpp"
 DIFFUSE = "spc_diffuse.hpp"
 ADVECT = "spc_advect.hpp"
+VADVECT = "spc_vadvect.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -391,6 +396,43 @@ ADVECT_MUTANTS = {
 }
 
 
+def vadvect_body(name):
+    """guard of a K17 mutant: the body ``name`` of tests/les_vadvect_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_vadvect_ref as lvr
+        failed = []
+        for dtype in lvr.DTYPES:
+            failed += lvr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_vadvect_ref." + name
+    return guard
+
+
+# K17 (spc_vadvect.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 1 stores M[k] where M[k + 1] belongs, in the same LDS cell; mutant 4 reads r at the clamped
+# k + 1; mutant 6 reads x[km], which the cell reads anyway, for the top cell's x[kp]; mutant 7 reads the profiles, hx, hy and
+# cmax of the LES of the tile's first column, which the tile touches anyway).
+VADVECT_MUTANTS = {
+    1: ("K17 M: started one level high (the lower face's flux stored for the upper face)", vadvect_body("parity"),
+        [(VADVECT, "            M = M - ce[u];\n            x[k + u] = M;", "            x[k + u] = M;\n            M = M - ce[u];"),
+         (VADVECT, "        M = M - x[k];\n        x[k] = M;", "        const T e1 = x[k];\n        x[k] = M;\n        M = M - e1;")]),
+    2: ("K17 M: + e for - e (convergence sends the air down)", vadvect_body("columns"),
+        [(VADVECT, "M = M - ce[u];", "M = M + ce[u];"), (VADVECT, "M = M - x[k];", "M = M + x[k];")]),
+    3: ("K17 pt: taken from ct > 0 (the upper face lets in what leaves)", vadvect_body("columns"),
+        [(VADVECT, "const T pt = ct < (T)0 ? -ct : (T)0;", "const T pt = ct > (T)0 ? ct : (T)0;")]),
+    4: ("K17 ct: r of level k + 1 (clamped) for r of level k", vadvect_body("parity"),
+        [(VADVECT, "const T ct = Mt * rk;", "const T ct = Mt * p.r[w.l * p.pitch_prof + (k + 1 < ktot ? k + 1 : k)];")]),
+    5: ("K17 upper term: the product and the add contracted to an fma", vadvect_body("parity"),
+        [(VADVECT, "            y = y + tt;", "            y = (T)__builtin_fma((double)pt, (double)dt, (double)y);")]),
+    6: ("K17 kp: the top cell takes the cell below it for the air that enters through the lid", vadvect_body("parity"),
+        [(VADVECT, "const int64_t okp = k + 1 < ktot ? o + 1 : o;", "const int64_t okp = k + 1 < ktot ? o + 1 : okm;")]),
+    7: ("K17 l: the LES of the tile's first column for every lane", vadvect_body("rows"),
+        [(VADVECT, "w.l = l0 + dl;", "w.l = l0;")]),
+    8: ("K17 cmax: the sum without pb", vadvect_body("probe"),
+        [(VADVECT, "const T s = pb + pt;", "const T s = pt;")]),
+}
+
+
 # K15 (spc_diffuse.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 2 reads cp[k + 1] for k <= ktot - 2, mutant 4 the rows of the LES of the tile's first column,
 # mutant 6 cp's row in place of a's; mutants 5 and 7 leave a level of the tile as it is).
@@ -600,7 +642,7 @@ def _tag(table):
     """(library prefix, source directory prefix) of a table"""
     for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
                    (MICRO_MUTANTS, ("micro_", "micro")), (DIFFUSE_MUTANTS, ("diffuse_", "diffuse")),
-                   (ADVECT_MUTANTS, ("advect_", "advect")),
+                   (ADVECT_MUTANTS, ("advect_", "advect")), (VADVECT_MUTANTS, ("vadvect_", "vadvect")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq"))):
@@ -777,11 +819,12 @@ if __name__ == "__main__":
     ap.add_argument("--micro", action="store_true", help="the table of K14 (MICRO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--diffuse", action="store_true", help="the table of K15 (DIFFUSE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--advect", action="store_true", help="the table of K16 (ADVECT_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--vadvect", action="store_true", help="the table of K17 (VADVECT_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
-             else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else GEO_MUTANTS if args.geo
+             else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -809,4 +852,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, DIFFUSE_MUTANTS, "K15", "les_diffuse"))
     if args.advect:
         sys.exit(main_advance(only, ADVECT_MUTANTS, "K16", "les_advect"))
+    if args.vadvect:
+        sys.exit(main_advance(only, VADVECT_MUTANTS, "K17", "les_vadvect"))
     sys.exit((main_advance if args.advance else main)(only))
