@@ -31,6 +31,9 @@
  *                           saturation-pressure table, with the slab means of QL and T, in one pass
  *   spc_les_water_paths_* <- les.get_field("LWP" | "TWP" | "RWP") (splib/spdummy.py:243-251): the column water paths of
  *                           those fields, with the cloud top and the cloud cover, in one pass
+ *   spc_les_radiate_*    <- the longwave cooling of that ensemble's cloud tops (nothing of it is in the reference): the
+ *                           GCSS / DYCOMS-II parametrised flux of every column from its liquid water and the THL tendency
+ *                           of its divergence, in one pass (kernel family K18)
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -665,6 +668,50 @@ int spc_les_vadvect_f64(const spc_les_vadvect_args *args, void *stream);
 int spc_les_vadvect_f32(const spc_les_vadvect_args *args, void *stream);
 /* columns per workgroup of k_les_vadvect for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
 int spc_les_vadvect_cols_per_block(int ktot, int elem_size);
+
+/* ---- longwave cooling and warming of the device-resident LES fields by their liquid water (kernel family K18) ----------------- */
+/* The first two terms of the GCSS / DYCOMS-II parametrised longwave flux (Stevens et al. 2005): the flux that the liquid water
+ * above and below a face lets through, and the THL tendency of its divergence.  ql and thl are [n_les][itot][jtot][ktot] (layout
+ * and offsets as K10), element type T; every operation is rounded once in T, never an fma, and the kernel holds no division and
+ * no transcendental function.  w and c are profiles [n_les x ktot], rows pitch_prof apart: w = kappa * rho * dz and
+ * c = dt / (cp * rho * dz * exner), formed in float64 (sp_coupler_amd/radiation.py: profiles) and rounded to T once.  etab is a
+ * table of exp(-x) at x = m / inv_step, m = 0 ... n_tab - 1 (radiation.py: exp_table), x_hi = (T)((n_tab - 1) / inv_step) formed
+ * in double.  f0, f1 [n_les] are the flux scales in W/m2.  Per column (l, i, j):
+ *   t[k]    = w[l][k] * ql[k]                         k = 0 ... ktot - 1
+ *   B[0]    = +0;   B[k+1] = B[k] + t[k]              SEQUENTIAL upward:   the optical depth below face k + 1
+ *   A[ktot] = +0;   A[k]   = A[k+1] + t[k]            SEQUENTIAL downward: the optical depth above face k
+ *   E(x):   xc = x < 0 ? 0 : (x > x_hi ? x_hi : x)    (a NaN passes through)
+ *           s  = xc * inv_step;  m = s >= 0 ? min((int)s, n_tab - 2) : 0;  fr = s - (T)m
+ *           E  = etab[m] + fr * (etab[m+1] - etab[m])
+ *   F[k]    = f0[l] * E(A[k]) + f1[l] * E(B[k])       k = 0 ... ktot: the net upward flux at face k; two products, one add
+ *   thl'[k] = thl[k] - c[l][k] * (F[k+1] - F[k])      IN PLACE: the difference, the product, the subtraction
+ *   flux[l][i][j][k] = F[k+1]                         optional, written whole
+ *   fsfc[l][i][j]    = F[0]                           optional, written whole
+ * ql is read only.  A column without liquid water (every ql +0) has F = f0 + f1 at every face and keeps the bits of every finite
+ * thl, -0.0 included.  A NaN in ql makes every F and every thl' of its own column NaN and reaches no other column; infinities and
+ * negative ql get no rule beyond the clamp in E.  n_tab < 2, inv_step not positive, pitch_prof < ktot, and thl, flux or fsfc
+ * EQUAL to an input or to each other are SPC_ERR_INVALID_ARGUMENT; arrays that overlap in part are not detected and must not be
+ * passed.  ktot == 1 is allowed.  A workgroup takes spc_les_radiate_cols_per_block(ktot, sizeof(T)) columns into two LDS tiles;
+ * above the largest ktot of which 16 columns fit (638 levels of 8 bytes, 1 278 of 4) the launch is SPC_ERR_UNSUPPORTED.  The
+ * third DYCOMS term (the cooling of the free troposphere above the inversion) is not part of the rule.  The rule is this
+ * library's definition.                                                                             */
+typedef struct spc_les_radiate_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_tab;    /* n_tab >= 2                                                        */
+    const void *ql;                     /* device [n_les][itot][jtot][ktot], read only                       */
+    void *thl;                          /* device [n_les][itot][jtot][ktot], updated in place                */
+    const void *w, *c;                  /* device [n_les x ktot] each, rows pitch_prof apart                 */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+    const void *f0, *f1;                /* device [n_les]                                                    */
+    const void *etab;                   /* device [n_tab]: exp(-m / inv_step)                                */
+    double inv_step;                    /* > 0: the nodes of etab per unit of optical depth                  */
+    void *flux;                         /* device [n_les][itot][jtot][ktot], written whole, or NULL          */
+    void *fsfc;                         /* device [n_les][itot][jtot], written whole, or NULL                */
+} spc_les_radiate_args;
+int spc_les_radiate_f64(const spc_les_radiate_args *args, void *stream);
+int spc_les_radiate_f32(const spc_les_radiate_args *args, void *stream);
+/* columns per workgroup of k_les_radiate for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
+int spc_les_radiate_cols_per_block(int ktot, int elem_size);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

@@ -170,6 +170,12 @@ class LesVadvectArgs(ctypes.Structure):
                 + _ptrs("hx", "hy", "cmax", "g", "r") + [("pitch_prof", c_int64), ("mtop", c_void_p)])
 
 
+class LesRadiateArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_tab", c_int32)]
+                + _ptrs("ql", "thl", "w", "c") + [("pitch_prof", c_int64)] + _ptrs("f0", "f1", "etab")
+                + [("inv_step", c_double)] + _ptrs("flux", "fsfc"))
+
+
 THERMO_TABLE_LIBRARY, THERMO_TABLE_LDS, THERMO_TABLE_GLOBAL = 0, 1, 2      # spc_les_thermo_args.table_mode
 
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
@@ -228,6 +234,9 @@ PROTOTYPES = {
     "spc_les_vadvect_f64": (ctypes.c_int, [ctypes.POINTER(LesVadvectArgs), c_void_p]),
     "spc_les_vadvect_f32": (ctypes.c_int, [ctypes.POINTER(LesVadvectArgs), c_void_p]),
     "spc_les_vadvect_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "spc_les_radiate_f64": (ctypes.c_int, [ctypes.POINTER(LesRadiateArgs), c_void_p]),
+    "spc_les_radiate_f32": (ctypes.c_int, [ctypes.POINTER(LesRadiateArgs), c_void_p]),
+    "spc_les_radiate_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

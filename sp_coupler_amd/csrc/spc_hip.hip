@@ -32,6 +32,9 @@
 //                  along i and j, separate output buffers, the Courant sums): spc_advect.hpp, kernel and host side
 //   K17 k_les_vadvect  one explicit upwind step of the vertical advection of those fields by the mass flux of continuity (K16's
 //                  face numbers, a serial chain along k per column of a tile in LDS): spc_vadvect.hpp, kernel and host side
+//   K18 k_les_radiate  the longwave flux that the liquid water of a column lets through and the THL tendency of its divergence
+//                  (two opposed running sums along k per column of two tiles in LDS, a table of exp(-x)): spc_radiate.hpp,
+//                  kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -87,6 +90,7 @@ namespace {
 #include "spc_diffuse.hpp"
 #include "spc_advect.hpp"
 #include "spc_vadvect.hpp"
+#include "spc_radiate.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -118,6 +122,9 @@ namespace {
 #define SPC_VADVECT_HOST
 #include "spc_vadvect.hpp"
 #undef SPC_VADVECT_HOST
+#define SPC_RADIATE_HOST
+#include "spc_radiate.hpp"
+#undef SPC_RADIATE_HOST
 
 }  // namespace
 
@@ -206,6 +213,10 @@ int spc_les_advect_rows(int64_t n_les, int itot, int jtot, int ktot) { return ad
 int spc_les_vadvect_f64(const spc_les_vadvect_args *a, void *s) { return les_vadvect_impl<double>(a, s); }
 int spc_les_vadvect_f32(const spc_les_vadvect_args *a, void *s) { return les_vadvect_impl<float>(a, s); }
 int spc_les_vadvect_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
+
+int spc_les_radiate_f64(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<double>(a, s); }
+int spc_les_radiate_f32(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<float>(a, s); }
+int spc_les_radiate_cols_per_block(int ktot, int elem_size) { return rad_cols(ktot, elem_size); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

@@ -225,6 +225,7 @@ class Engine:
         self.dtype = dtype
         sfx = _DTYPES[dtype]
         self._vn_work = None                    # variability_nudge's transposed-plane scratch, grown on demand
+        self._exp_tab = None                    # les_radiate's table of exp(-x) on the device, uploaded on first use
         self._es_tab = None                     # les_thermo's saturation-pressure table on the device, uploaded on first use
         self._fwd = getattr(self.lib, "spc_forward_" + sfx)
         self._bwd = getattr(self.lib, "spc_backward_" + sfx)
@@ -996,6 +997,55 @@ class Engine:
     def vadvect_cols_per_block(self, ktot):
         """columns of ``ktot`` levels a workgroup of K17 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
         return int(self.lib.spc_les_vadvect_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+
+    # -- K18: longwave cooling and warming of device-resident LES fields by their liquid water, one launch ------------------------
+    @_on_engine_stream
+    def les_radiate(self, ql, thl, w, c, f0, f1, *, flux=None, fsfc=None, stream=None):
+        """One step of the parametrised longwave flux (include/spc.h has the rule) on contiguous device fields
+        [n x itot x jtot x ktot]: the liquid water ``ql`` (read only) gives the optical depths above and below every face,
+        ``thl`` takes the divergence of the flux IN PLACE.  ``w`` and ``c`` [n x ktot] are ``radiation.profiles`` in the engine's
+        dtype (rows may be pitched, both with one pitch), ``f0`` and ``f1`` [n] the flux scales of every LES in W/m2.  ``flux``:
+        a tensor of the fields' shape that takes the flux at the upper face of every cell, or None; ``fsfc``: a tensor
+        [n x itot x jtot] that takes the flux at the ground, or None.  The table of exp(-x) (``radiation.exp_table``) is
+        uploaded once per engine.  A written tensor that STARTS where an input or another written tensor starts is refused
+        (ValueError); views that overlap in part are not detected.  One launch; more levels than ``radiate_cols_per_block``
+        carries are refused (SPC_ERR_UNSUPPORTED)."""
+        from . import radiation
+        shape = tuple(self._field4("ql", ql).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_radiate: empty field shape %s" % (shape,))
+        if self._exp_tab is None:
+            self._exp_tab = torch.from_numpy(radiation.exp_table(self.dtype)).to(self.device)
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.LesRadiateArgs()
+        a.n_les, a.itot, a.jtot, a.ktot = n, itot, jtot, ktot
+        a.ql, a.thl = ql.data_ptr(), self._field4("thl", thl, shape).data_ptr()
+        a.w, a.pitch_prof = ck.mat("w", w, n, ktot)
+        a.c, _ = ck.mat("c", c, n, ktot, pitch=a.pitch_prof)
+        a.f0, a.f1 = ck.vec("f0", f0, n), ck.vec("f1", f1, n)
+        a.etab, a.n_tab, a.inv_step = self._exp_tab.data_ptr(), int(self._exp_tab.numel()), radiation.INV_STEP
+        written = [thl]
+        if flux is not None:
+            a.flux = self._field4("flux", flux, shape).data_ptr()
+            written.append(flux)
+        if fsfc is not None:
+            if not isinstance(fsfc, torch.Tensor) or fsfc.device != self.device or fsfc.dtype != self.dtype or \
+                    tuple(fsfc.shape) != (n, itot, jtot) or not fsfc.is_contiguous():
+                raise ValueError("les_radiate: fsfc must be a contiguous %s tensor of shape %s on %s" % (self.dtype, (n, itot, jtot), self.device))
+            a.fsfc = fsfc.data_ptr()
+            written.append(fsfc)
+        if n:
+            read = [t.data_ptr() for t in (ql, w, c, f0, f1)]
+            written = [t.data_ptr() for t in written]
+            if len(set(written)) != len(written) or set(written) & set(read):
+                raise ValueError("les_radiate: thl, flux or fsfc is an input or another of them")
+        fn = self.lib.spc_les_radiate_f32 if self.dtype == torch.float32 else self.lib.spc_les_radiate_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+
+    def radiate_cols_per_block(self, ktot):
+        """columns of ``ktot`` levels a workgroup of K18 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
+        return int(self.lib.spc_les_radiate_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
 
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once

@@ -702,7 +702,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     After ``enable_advection()`` every step carries U, V, THL, QT and QR along i and j with the winds U and V on the periodic
     plane, in as many upwind substeps as the Courant sums ask for (K16, ``Engine.les_advect``); tests/les_advect_ref.py holds
     the twin of that mode.  With ``vertical=True`` every substep also carries them along k by the mass flux of continuity (K17,
-    ``Engine.les_vadvect``) and ``get_vertical_wind_batched()`` returns W; tests/les_vadvect_ref.py holds that twin."""
+    ``Engine.les_vadvect``) and ``get_vertical_wind_batched()`` returns W; tests/les_vadvect_ref.py holds that twin.
+    After ``enable_radiation()`` every step cools THL at the top of the cloud water and warms it at its base (K18,
+    ``Engine.les_radiate``) and ``get_radiative_flux_batched()`` returns the longwave flux; tests/les_radiate_ref.py holds the
+    twin of that mode."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
@@ -1044,6 +1047,70 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         rho = self._upload(numpy.asarray(self.p["Rhobf"], dtype=numpy.float64))
         return self._per_device(lambda m, rh: adv.vertical_wind(m, rh, self._vadvect_dt), self._vadvect_mtop, rho)
 
+    # -- longwave cooling and warming by the liquid water (K18), opt-in ---------------------------------------------------------
+    radiation = False                                  # enable_radiation(): the cloud water acts on THL
+    radiate_par = None                                 # f0, f1, kappa: float64 [n] each
+    _radiate_prof = None                               # ((dt, host kappa, Rhobf, presf, zh) of the upload, device w, c)
+    _radiate_scale = None                              # device (f0, f1)
+    _radiate_flux = None                               # the flux at the upper faces in the last step, device
+
+    def enable_radiation(self, f0=None, f1=None, kappa=None):
+        """from now on every ``evolve_model_batched`` runs ONE K18 launch per device (``Engine.les_radiate``) on
+        THL with the current QL and the whole step's dt, after K16 / K17 / K15 and before K14 / K12: the first two terms of the
+        GCSS / DYCOMS-II parametrised longwave flux cool the air at the top of a cloud and warm it at its base.  ``f0``, ``f1``
+        (W/m2) and ``kappa`` (m2/kg) are scalars or one value per LES and default to those of ``radiation``.  Needs a THL
+        field, more than one level, and cloud water that follows the fields: a Qsat field or ``enable_thermo()`` (ValueError
+        otherwise).  Launches per step and device: ONE K18, and one K10 for the means of the new fields; with
+        ``enable_thermo()`` one K12 more than without this call (K12 runs on the fields K18 reads QL of, and again on the new
+        THL before the means are formed).  w and c are uploaded again only where dt, kappa, Rhobf,
+        presf or the half levels changed.  ``get_radiative_flux_batched()`` returns the flux.  Without this call every path,
+        launch count and result of the ensemble is unchanged."""
+        from . import radiation as rad
+        if self.nL == 1:
+            raise ValueError("the radiation (K18) does not take LES of one level")
+        if "THL" not in self.fields3d:
+            raise ValueError("the radiation (K18) needs a THL field (set_fields_batched)")
+        if not (self.thermo or "Qsat" in self.fields3d):
+            raise ValueError("the radiation (K18) needs the cloud water of the current fields: a Qsat field, or enable_thermo()")
+        if not all(callable(getattr(e, "les_radiate", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
+            raise ValueError("the engine has no les_radiate (K18)")
+        par = {}
+        for name, v, d in (("f0", f0, rad.F0), ("f1", f1, rad.F1), ("kappa", kappa, rad.KAPPA)):
+            a = numpy.asarray(d if v is None else v, dtype=numpy.float64)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape != (self.n,)) or not numpy.isfinite(a).all():
+                raise ValueError("the radiation (K18) needs a finite %s: a scalar or one value per LES" % name)
+            par[name] = numpy.array(numpy.broadcast_to(a, (self.n,)), order="C")
+        self.radiate_par = par
+        self.radiation, self._radiate_prof, self._radiate_scale, self._radiate_flux = True, None, None, None
+
+    def _radiate(self, dt):
+        """K18 on the stepped THL with the QL of the stepped fields; the profiles are then the means of the new fields"""
+        import torch
+        from . import radiation as rad
+        eng, f, p, par = self._eng(), self.fields3d, self.p, self.radiate_par
+        if self.n == 0:
+            return
+        if "THL" not in f or not (self.thermo or "Qsat" in f):
+            raise ValueError("the radiation (K18) needs a THL field and a Qsat field or enable_thermo()")
+        self._ensure_ql()                                 # (thermo: K12 where stale)
+        # everything the profiles are made of; the host arrays are copied and compared every step (kilobytes)
+        key = (float(dt),) + tuple(numpy.array(a, dtype=numpy.float64) for a in (par["kappa"], p["Rhobf"], p["presf"], self.zh_cache))
+        if self._radiate_prof is None or self._radiate_prof[0][0] != key[0] or not all(
+                a.shape == b.shape and numpy.array_equal(a, b) for a, b in zip(self._radiate_prof[0][1:], key[1:])):
+            self._radiate_prof = (key, [self._upload(a) for a in rad.profiles(key[2], key[4], key[3], dt, key[1])])
+        if self._radiate_scale is None:
+            self._radiate_scale = (self._upload(par["f0"]), self._upload(par["f1"]))
+        if self._radiate_flux is None or tuple(self._radiate_flux.shape) != tuple(f["THL"].shape):
+            self._radiate_flux = self._per_device(torch.empty_like, f["THL"])
+        eng.les_radiate(f["QL"], f["THL"], *self._radiate_prof[1], *self._radiate_scale, flux=self._radiate_flux)
+        self._follow_fields()                             # K12 stale, QL of the QT field, p[U, V, THL, QT, QL] = K10's means
+
+    def get_radiative_flux_batched(self):
+        """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the net upward longwave
+        flux in W/m2 at the UPPER faces of the cells that the last step's K18 launch found; None before the first step of
+        enable_radiation()"""
+        return self._radiate_flux if self.radiation else None
+
     def _follow_fields(self):
         """QL = max(QT - Qsat, 0) of the QT field as it is now (without thermo) and p[U, V, THL, QT, QL] = K10's means"""
         import torch
@@ -1313,6 +1380,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                                                           # (vertical: a K17 probe and a K17 launch behind every K16 substep)
         if self.diffusion:
             self._diffuse(dt)                             # one K15 launch: U, V, THL, QT mixed along k, the surface fluxes; p[...]
+        if self.radiation:
+            self._radiate(dt)                             # one K18 launch: THL cooled at the cloud tops, warmed at the bases; p[...]
         if self.micro:
             self._microphysics(dt)                        # one K14 launch: QT, THL, QR, rain2d; p[QT, THL, QR, Rain(, QL_ice)]
         if self.thermo:

@@ -277,6 +277,15 @@ class MultiDeviceEngine:
             return None
         return cmax if cmax is not True else self._join(res, ex.bounds)
 
+    def les_radiate(self, ql, thl, w, c, f0, f1, *, flux=None, fsfc=None, **kw):
+        """K18 on every device's LES: the Sharded fields ``ql`` and ``thl`` (updated in place, block by block), the Sharded
+        profiles ``w`` and ``c`` [n x ktot], ``f0`` and ``f1`` [n] and ``flux`` / ``fsfc`` (or None) in; one launch per device
+        that holds rows, none on the others"""
+        ex = self._example(ql)
+        if ex is None:
+            return self.primary.les_radiate(ql, thl, w, c, f0, f1, flux=flux, fsfc=fsfc, **kw)
+        self._each("les_radiate", ex, (ql, thl, w, c, f0, f1), dict(kw, flux=flux, fsfc=fsfc))
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

@@ -23,6 +23,8 @@ ADVECT_MUTANTS is the table of K16 (spc_advect.hpp), chosen with --advect; its g
 tests/les_advect_ref.py, which tests/test_les_advect_gpu.py runs on the shipped library.
 VADVECT_MUTANTS is the table of K17 (spc_vadvect.hpp), chosen with --vadvect; its guards are the bodies of
 tests/les_vadvect_ref.py, which tests/test_les_vadvect_gpu.py runs on the shipped library.
+RADIATE_MUTANTS is the table of K18 (spc_radiate.hpp), chosen with --radiate; its guards are the bodies of
+tests/les_radiate_ref.py, which tests/test_les_radiate_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
@@ -39,6 +41,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --diffuse --build && python tools/mutation_control.py --diffuse > profiles/mutation_control_diffuse.log
        python tools/mutation_control.py --advect --build && python tools/mutation_control.py --advect > profiles/mutation_control_advect.log
        python tools/mutation_control.py --vadvect --build && python tools/mutation_control.py --vadvect > profiles/mutation_control_vadvect.log
+       python tools/mutation_control.py --radiate --build && python tools/mutation_control.py --radiate > profiles/mutation_control_radiate.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log"""
 import argparse
@@ -64,6 +67,7 @@ MICRO = "spc_micro.hpp"
 DIFFUSE = "spc_diffuse.hpp"
 ADVECT = "spc_advect.hpp"
 VADVECT = "spc_vadvect.hpp"
+RADIATE = "spc_radiate.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -433,6 +437,44 @@ VADVECT_MUTANTS = {
 }
 
 
+def radiate_body(name):
+    """guard of a K18 mutant: the body ``name`` of tests/les_radiate_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_radiate_ref as lrr
+        failed = []
+        for dtype in lrr.DTYPES:
+            failed += lrr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_radiate_ref." + name
+    return guard
+
+
+# K18 (spc_radiate.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 1 stores A[k + 1] where A[k] belongs, in the same LDS cell; mutant 2 reads the B of its own
+# face twice; mutant 6 keeps both table indices inside the table: with n_tab - 1 alone the upper one would leave it by one
+# entry; mutant 7 reads f0 and f1 of the tile's first LES; mutant 8 extrapolates the last segment, whose index the min() keeps).
+RADIATE_MUTANTS = {
+    1: ("K18 A: started one level off (the depth above the upper face stored for the lower face)", radiate_body("parity"),
+        [(RADIATE, "            A = A + ct[u];\n            x[k - u] = A;", "            x[k - u] = A;\n            A = A + ct[u];"),
+         (RADIATE, "        A = A + x[k];\n        x[k] = A;", "        const T t1 = x[k];\n        x[k] = A;\n        A = A + t1;")]),
+    2: ("K18 F: B for A in the f0 term (the cloud top sees the water below it)", radiate_body("parity"),
+        [(RADIATE, "const T Ea = rad_E<T>(etab, A,", "const T Ea = rad_E<T>(etab, B,")]),
+    3: ("K18 thl: + for - (a flux that diverges warms)", radiate_body("parity"),
+        [(RADIATE, "    return x - t;", "    return x + t;")]),
+    4: ("K18 flux: F[k] for F[k + 1] (the flux at the lower face)", radiate_body("outputs"),
+        [(RADIATE, "    up = F[k + 1];\n    const T dF = up - lo;", "    const T hi = F[k + 1];\n    up = lo;\n    const T dF = hi - lo;")]),
+    5: ("K18 lookup: the product and the add of the interpolation contracted to an fma", radiate_body("parity"),
+        [(RADIATE, "    const T t = fr * d;\n    return e0 + t;", "    return (T)__builtin_fma((double)fr, (double)d, (double)e0);")]),
+    6: ("K18 lookup: n_tab - 1 for n_tab - 2 (x_hi falls on the last node with fr = 0, not on the last segment with fr = 1)", radiate_body("lookup"),
+        [(RADIATE, "min((int)s, n_tab - 2)", "min((int)s, n_tab - 1)"),
+         (RADIATE, "const T d = etab[m + 1] - e0;", "const T d = etab[m + 1 < n_tab ? m + 1 : m] - e0;")]),
+    7: ("K18 l: the LES of the tile's first column for the f0 and f1 of every lane", radiate_body("rows"),
+        [(RADIATE, "const int64_t l = l0 + (rem0 + (uint32_t)c) / (uint32_t)p.nij;", "const int64_t l = l0;")]),
+    8: ("K18 lookup: the clamp at x_hi dropped (the last segment extrapolated)", radiate_body("lookup"),
+        [(RADIATE, "const T xc = x < (T)0 ? (T)0 : (x > x_hi ? x_hi : x);", "const T xc = x < (T)0 ? (T)0 : x;")]),
+}
+
+
 # K15 (spc_diffuse.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 2 reads cp[k + 1] for k <= ktot - 2, mutant 4 the rows of the LES of the tile's first column,
 # mutant 6 cp's row in place of a's; mutants 5 and 7 leave a level of the tile as it is).
@@ -643,6 +685,7 @@ def _tag(table):
     for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
                    (MICRO_MUTANTS, ("micro_", "micro")), (DIFFUSE_MUTANTS, ("diffuse_", "diffuse")),
                    (ADVECT_MUTANTS, ("advect_", "advect")), (VADVECT_MUTANTS, ("vadvect_", "vadvect")),
+                   (RADIATE_MUTANTS, ("radiate_", "radiate")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq"))):
@@ -820,11 +863,13 @@ if __name__ == "__main__":
     ap.add_argument("--diffuse", action="store_true", help="the table of K15 (DIFFUSE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--advect", action="store_true", help="the table of K16 (ADVECT_MUTANTS) instead of MUTANTS")
     ap.add_argument("--vadvect", action="store_true", help="the table of K17 (VADVECT_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--radiate", action="store_true", help="the table of K18 (RADIATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
-             else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else GEO_MUTANTS if args.geo
+             else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else RADIATE_MUTANTS if args.radiate
+             else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -854,4 +899,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, ADVECT_MUTANTS, "K16", "les_advect"))
     if args.vadvect:
         sys.exit(main_advance(only, VADVECT_MUTANTS, "K17", "les_vadvect"))
+    if args.radiate:
+        sys.exit(main_advance(only, RADIATE_MUTANTS, "K18", "les_radiate"))
     sys.exit((main_advance if args.advance else main)(only))
