@@ -682,6 +682,22 @@ class _DeviceLESRow(_LESRow):
         return self._e._water_path_host(name)[self._i].copy()
 
 
+def _device_row_getter(key):
+    """the row getter of a DeviceLESEnsemble: row i of what ``get_profiles_batched((key,))`` returns at that moment.  The 3-D
+    fields are the truth, so the profile is refreshed first (both refreshes are cached: a second read launches nothing)"""
+    plain = _row_getter(key)
+
+    def get(self, return_request=False):
+        self._e._refresh_profile(key)
+        return plain(self, return_request)
+    return get
+
+
+for _m, _k in (("get_profile_U", "U"), ("get_profile_V", "V"), ("get_profile_THL", "THL"), ("get_profile_QT", "QT"),
+               ("get_profile_QL", "QL"), ("get_profile_QL_ice", "QL_ice"), ("get_profile_QR", "QR"), ("get_profile_T", "T")):
+    setattr(_DeviceLESRow, _m, _device_row_getter(_k))
+
+
 class DeviceLESEnsemble(SyntheticLESEnsemble):
     """SyntheticLESEnsemble whose 3-D fields are device tensors [n x itot x jtot x nL] in the engine's dtype
     (``transfer.Sharded`` row blocks under a ``multi.MultiDeviceEngine``) from ``set_les_state_batched`` through every
@@ -1284,8 +1300,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         return {k: cache[k] for k in have + (["top", "cover"] if cloud_cover else [])}
 
     def _water_path_host(self, name):
-        if name not in self._wp_host or self._wp is None or name not in self._wp:
-            t = self.get_water_paths_batched((name,))[name]
+        t = self.get_water_paths_batched((name,))[name]           # (cached; it drops the host copies where p["Rhobf"] changed the weights)
+        if name not in self._wp_host:
             with self._eng().on_stream():
                 self._wp_host[name] = numpy.asarray(self._host(t))
         return self._wp_host[name]
@@ -1307,6 +1323,14 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         means = self._slab_means() if any(k in self.MEAN_KEYS and k in self.fields3d for k in keys) else {}
         for k in keys:
             numpy.copyto(out[k], means[k] if k in means else self.p[k])
+
+    def _refresh_profile(self, key):
+        """p[key] of the fields as they are now, by the rule of get_profiles_batched (the rows' getters read p: a nudge or
+        set_fields_batched leaves the means of the old fields there)"""
+        if self.thermo:
+            self._ensure_thermo()
+        if key in self.MEAN_KEYS and key in self.fields3d:
+            self._slab_means()
 
     @_timed
     def get_cloudfraction_batched(self, indices, out):

@@ -479,6 +479,7 @@ class _HostMicro:
         if "QR" not in f:
             f["QR"] = numpy.zeros_like(f["QT"])
         self.rain2d = numpy.zeros(f["QT"].shape[:3])
+        self._stale = True              # thermo: K12 runs again before the next use of QL (K14 needs the cells' temperature), at presf as it is then
         self.micro_par = {"v_fall": mp.V_FALL if v_fall is None else v_fall, "qc0": mp.QC0 if qc0 is None else qc0,
                           "k_auto": mp.K_AUTO if k_auto is None else k_auto, "k_acc": mp.K_ACC if k_acc is None else k_acc}
 

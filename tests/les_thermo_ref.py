@@ -406,6 +406,14 @@ class HostThermoLESEnsemble(slab_ref.HostFieldLESEnsemble):
             self._ensure_ql()
         return self.fields3d[name].copy()
 
+    def _slab_means(self):
+        self._ensure_ql()              # (the base class asks for QL only where a Qsat field exists: before K12's first run none does)
+        return super()._slab_means()
+
+    def _refresh_profile(self, key):
+        self._ensure_ql()
+        super()._refresh_profile(key)
+
     def get_profiles_batched(self, keys, out):
         self._ensure_ql()
         super().get_profiles_batched(keys, out)

@@ -63,6 +63,31 @@ def hand_case(dtype):
     return ql, idx, counts
 
 
+class _HostRow(models._LESRow):
+    """per-column face of the twin: a profile getter returns row i of what get_profiles_batched((key,)) returns at that
+    moment (the fields are the truth: after a nudge or set_fields_batched the raw ``p`` still holds the means of the old ones)"""
+
+    def get_itot(self):
+        return self._e.itot
+
+    def get_jtot(self):
+        return self._e.jtot
+
+
+def _host_row_getter(key):
+    plain = models._row_getter(key)
+
+    def get(self, return_request=False):
+        self._e._refresh_profile(key)
+        return plain(self, return_request)
+    return get
+
+
+for _m, _k in (("get_profile_U", "U"), ("get_profile_V", "V"), ("get_profile_THL", "THL"), ("get_profile_QT", "QT"),
+               ("get_profile_QL", "QL"), ("get_profile_QL_ice", "QL_ice"), ("get_profile_QR", "QR"), ("get_profile_T", "T")):
+    setattr(_HostRow, _m, _host_row_getter(_k))
+
+
 class HostFieldLESEnsemble(models.SyntheticLESEnsemble):
     """models.DeviceLESEnsemble with NumPy fields (float64): spcpl takes its host-field path.  The executable definition of
     what the device ensemble computes."""
@@ -81,11 +106,15 @@ class HostFieldLESEnsemble(models.SyntheticLESEnsemble):
         return ens
 
     def __getitem__(self, i):
-        row = super().__getitem__(i)
-        if not isinstance(i, slice):
-            row.get_itot = lambda: self.itot
-            row.get_jtot = lambda: self.jtot
-        return row
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(self.n))]
+        if self._rows[i] is None:
+            self._rows[i] = _HostRow(self, i)
+        return self._rows[i]
+
+    def _refresh_profile(self, key):
+        if key in self.MEAN_KEYS and key in self.fields3d:
+            self._slab_means()
 
     def attach_fields(self, fields):
         for k, v in fields.items():
