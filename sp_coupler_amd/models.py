@@ -289,7 +289,7 @@ def make_models(n_les, npoints=None, nG=91, nL=160, seed=1):
 #         set_forcings_batched(**arrays), evolve_model_batched(t); for qt_forcing='variance' additionally
 #         get_fields_batched(name) -> [n x itot x jtot x ktot], set_fields_batched(name, array), model_time;
 #         for spcpl.set_les_state_batched: set_fields_batched, and per-column faces with get_itot / get_jtot / get_ktot
-#         (and set_surface_pressure where ps is set); fields_on_device = True (optional, DeviceLESEnsemble below): the 3-D
+#         (and set_surface_pressure where ps is set); fields_on_device = True (optional, device_les.DeviceLESEnsemble): the 3-D
 #         fields are device tensors, get_fields_batched hands them out and set_fields_batched takes them as they are
 # ---------------------------------------------------------------------------------------------
 import time as _time
@@ -630,789 +630,10 @@ def make_batched_models(n_les, npoints=None, nG=91, nL=160, seed=1):
     return gcm, ens
 
 
-# ---------------------------------------------------------------------------------------------
-# An LES ensemble whose 3-D fields live on the GPU (fields_on_device)
-# ---------------------------------------------------------------------------------------------
-class _DeviceLESRow(_LESRow):
-    """per-column face of a DeviceLESEnsemble: the field extents are the ensemble's; single rows of a device field are not
-    handed out (the fields never leave the GPU through the library)"""
-
-    def get_itot(self):
-        return self._e.itot
-
-    def get_jtot(self):
-        return self._e.jtot
-
-    @property
-    def dx(self):
-        """the grid spacing along i, m: the ensemble's after enable_advection(), else ``advection.DX``"""
-        from . import advection
-        return float(numpy.broadcast_to(advection.DX if self._e.dx is None else self._e.dx, (self._e.n,))[self._i])
-
-    @property
-    def dy(self):
-        from . import advection
-        return float(numpy.broadcast_to(advection.DY if self._e.dy is None else self._e.dy, (self._e.n,))[self._i])
-
-    def get_dx(self):
-        return self.dx
-
-    def get_dy(self):
-        return self.dy
-
-    def get_xsize(self):
-        """the extent of the periodic plane along i, m (splib/spio.py:104-111 asks an LES for it)"""
-        return self.dx * self._e.itot
-
-    def get_ysize(self):
-        return self.dy * self._e.jtot
-
-    def get_cloudfraction(self, indices, return_request=False):
-        raise NotImplementedError("a DeviceLESEnsemble answers get_cloudfraction_batched (all columns, one launch)")
-
-    def set_field(self, name, values):
-        raise NotImplementedError("a DeviceLESEnsemble takes whole fields: set_fields_batched")
-
-    def get_field(self, name):
-        """les.get_field("LWP" | "TWP" | "RWP") (splib/spdummy.py:243-251): row i of the ensemble's water paths (K13) as a
-        host [itot x jtot] array; the 3-D fields themselves are not handed out row by row"""
-        if name not in DeviceLESEnsemble.WATER_PATHS:
-            raise NotImplementedError("a DeviceLESEnsemble hands out the water paths LWP, TWP and RWP per LES; its 3-D fields "
-                                      "stay on the GPU: get_fields_batched")
-        return self._e._water_path_host(name)[self._i].copy()
-
-
-def _device_row_getter(key):
-    """the row getter of a DeviceLESEnsemble: row i of what ``get_profiles_batched((key,))`` returns at that moment.  The 3-D
-    fields are the truth, so the profile is refreshed first (both refreshes are cached: a second read launches nothing)"""
-    plain = _row_getter(key)
-
-    def get(self, return_request=False):
-        self._e._refresh_profile(key)
-        return plain(self, return_request)
-    return get
-
-
-for _m, _k in (("get_profile_U", "U"), ("get_profile_V", "V"), ("get_profile_THL", "THL"), ("get_profile_QT", "QT"),
-               ("get_profile_QL", "QL"), ("get_profile_QL_ice", "QL_ice"), ("get_profile_QR", "QR"), ("get_profile_T", "T")):
-    setattr(_DeviceLESRow, _m, _device_row_getter(_k))
-
-
-class DeviceLESEnsemble(SyntheticLESEnsemble):
-    """SyntheticLESEnsemble whose 3-D fields are device tensors [n x itot x jtot x nL] in the engine's dtype
-    (``transfer.Sharded`` row blocks under a ``multi.MultiDeviceEngine``) from ``set_les_state_batched`` through every
-    variability nudge: the library never copies them to the host.  The 3-D state is the truth and the profiles follow from
-    it: U, V, THL, QT, QL are the slab means of the fields (K10, ``Engine.slab_means``: ONE launch for all of them per
-    change of the fields), the cloud fraction is ``Engine.slab_cloud_fraction`` of the QL field.  ``Qsat`` is an attached
-    field, constant in time; the QL field is ``max(QT - Qsat, 0)``.  tests/slab_ref.py holds the NumPy twin of this class.
-    After ``enable_thermo()`` Qsat and QL are instead the saturation adjustment of THL and QT at ``presf`` (K12,
-    ``Engine.les_thermo``: DESIGN.md 7.3), redone whenever THL or QT has changed, and ``p["T"]`` is K12's slab mean of the
-    cells' temperature; tests/les_thermo_ref.py holds the NumPy twin of that mode.
-    ``get_water_paths_batched`` reduces the fields along k instead (K13, ``Engine.les_water_paths``): the column water paths
-    LWP, TWP and RWP, [n x itot x jtot] device tensors, and the cloud cover; tests/les_water_paths_ref.py holds their twin.
-    After ``enable_microphysics()`` every step ends with the warm-rain microphysics (K14, ``Engine.les_microphysics``): cloud
-    water turns into rain, the QR field falls, ``rain2d`` collects what reaches the ground and ``p["Rain"]`` is its plane mean;
-    tests/les_micro_ref.py holds the twin of that mode.
-    After ``enable_diffusion()`` every step mixes U, V, THL and QT along k and lets the surface fluxes of the coupler into THL
-    and QT (K15, ``Engine.les_diffuse``); tests/les_diffuse_ref.py holds the twin of that mode.
-    After ``enable_advection()`` every step carries U, V, THL, QT and QR along i and j with the winds U and V on the periodic
-    plane, in as many upwind substeps as the Courant sums ask for (K16, ``Engine.les_advect``); tests/les_advect_ref.py holds
-    the twin of that mode.  With ``vertical=True`` every substep also carries them along k by the mass flux of continuity (K17,
-    ``Engine.les_vadvect``) and ``get_vertical_wind_batched()`` returns W; tests/les_vadvect_ref.py holds that twin.
-    After ``enable_radiation()`` every step cools THL at the top of the cloud water and warms it at its base (K18,
-    ``Engine.les_radiate``) and ``get_radiative_flux_batched()`` returns the longwave flux; tests/les_radiate_ref.py holds the
-    twin of that mode."""
-
-    fields_on_device = True
-    MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
-    STEP_KEYS = ("U", "V", "THL", "QT")                # fields a step applies a tendency to
-    fused_advance = True                               # evolve_model_batched: one K11 launch (False: torch ops + K10)
-    FUSED_MIN_LES = 128                                # ... where a launch holds at least so many LES (DESIGN.md 7.3)
-    WATER_PATHS = {"LWP": "QL", "TWP": "QT", "RWP": "QR"}     # les.get_field(name) -> the 3-D field it is the column sum of
-
-    def __init__(self, grid_indices, zf, zh, prof, itot=8, jtot=8, engine=None):
-        super().__init__(grid_indices, zf, zh, prof)
-        self.itot, self.jtot = int(itot), int(jtot)
-        self.engine = engine                            # None: spcpl.get_engine() when first needed
-        self.fields3d = {}
-        self._means = None                              # host slab means of the fields as they are now, or None
-        self._wp, self._wp_host, self._wp_w = None, {}, None      # K13's results of the fields as they are now; its weights
-
-    # -- saturation adjustment (K12), opt-in -------------------------------------------------------------------------
-    thermo = False                                     # enable_thermo(): Qsat and QL follow THL, QT and presf
-    thermo_n_iter = None
-    _thermo_stale = True                               # THL or QT changed since K12 last ran
-    _thermo_prof = None                                # (host presf the upload was made from, device presf, device ex)
-    _thermo_means = None                               # host slab means {"QL", "T"} of K12's last launch
-
-    def enable_thermo(self, n_iter=None):
-        """from now on the Qsat and QL fields are K12's saturation adjustment of THL and QT (``n_iter`` Newton iterations,
-        default ``thermo.DEFAULT_N_ITER``), run again before their next use whenever THL or QT has changed, and ``p["T"]`` is
-        the slab mean of the adjusted temperature.  Without this call every path of the ensemble is unchanged."""
-        if self.nL == 1:
-            raise ValueError("the saturation adjustment (K12) does not take LES of one level")
-        if not all(callable(getattr(e, "les_thermo", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
-            raise ValueError("the engine has no les_thermo (K12)")
-        self.thermo, self.thermo_n_iter = True, n_iter
-        self._thermo_stale, self._means = True, None
-
-    def _ensure_thermo(self):
-        """K12 where THL or QT has changed since its last launch: the Qsat and QL fields, p["QL"] and p["T"]"""
-        import torch
-        from . import thermo
-        f = self.fields3d
-        if not self._thermo_stale or "THL" not in f or "QT" not in f:
-            return
-        eng = self._eng()
-        presf = numpy.asarray(self.p["presf"], dtype=numpy.float64)
-        if self._thermo_prof is None or not numpy.array_equal(self._thermo_prof[0], presf):
-            self._thermo_prof = (presf.copy(), self._upload(presf), self._upload(thermo.exner(presf)))
-        for k in ("Qsat", "QL"):
-            if k not in f:
-                f[k] = self._per_device(torch.empty_like, f["QT"])          # written whole by the launch
-        if self.micro and "T" not in f:                 # K14 reads the cells' temperature for the cloud ice
-            f["T"] = self._per_device(torch.empty_like, f["QT"])
-        dev = eng.les_thermo(f["THL"], f["QT"], self._thermo_prof[1], self._thermo_prof[2], n_iter=self.thermo_n_iter,
-                             qsat=f["Qsat"], ql=f["QL"], **({"temp": f["T"]} if self.micro else {}))
-        with eng.on_stream():
-            self._thermo_means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
-        self.p.update(self._thermo_means)
-        self._drop_water_paths()                        # QL is new
-        if self._means is not None:
-            self._means["QL"] = self._thermo_means["QL"]
-        self._thermo_stale = False
-
-    # -- warm-rain microphysics (K14), opt-in -------------------------------------------------------------------------
-    micro = False                                      # enable_microphysics(): QR, rain2d and p["Rain"] follow the cloud water
-    micro_par = None                                   # v_fall, qc0, k_auto, k_acc
-    rain2d = None                                      # device [n x itot x jtot]: the rain that has reached the ground, kg/m2
-    _qr_spare = None                                   # the QR buffer K14 writes next (it reads the other one)
-    _micro_prof = None                                 # ((dt, v_fall, host presf, Rhobf, zh, zf) of the upload, the four device profiles)
-
-    def enable_microphysics(self, v_fall=None, qc0=None, k_auto=None, k_acc=None):
-        """from now on every ``evolve_model_batched`` ends with ONE K14 launch per device (``Engine.les_microphysics``,
-        DESIGN.md 7.3) on the stepped fields and the current QL: cloud water turns into rain (QT and THL in place), the QR
-        field falls one upwind step, what reaches the ground is summed in ``rain2d`` [n x itot x jtot], whose plane mean is
-        ``p["Rain"]``; p["QT"], p["THL"] and p["QR"] are the launch's slab means, and with ``enable_thermo()`` p["QL_ice"] is the
-        mean of the cloud ice at the cells' temperature.  Needs a QT field and more than one level; a QR field is created,
-        zero, where none is attached.  The cloud water must be able to follow the QT the launch changes: a step needs an
-        attached Qsat field or ``enable_thermo()`` (ValueError otherwise, also with an attached QL alone).  The profiles are
-        uploaded again whenever dt, v_fall, presf, Rhobf or the grid (zh, zf) changed.  The constants default to those of ``microphysics``.  Without this call every path of
-        the ensemble is unchanged."""
-        import torch
-        from . import microphysics as mp
-        if self.nL == 1:
-            raise ValueError("the microphysics (K14) does not take LES of one level")
-        if "QT" not in self.fields3d:
-            raise ValueError("the microphysics (K14) needs a QT field (set_fields_batched)")
-        if not all(callable(getattr(e, "les_microphysics", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
-            raise ValueError("the engine has no les_microphysics (K14)")
-        f = self.fields3d
-        if "QR" not in f:
-            f["QR"] = self._per_device(torch.zeros_like, f["QT"])
-        self._qr_spare = self._per_device(torch.empty_like, f["QT"])
-        self.rain2d = self._per_device(lambda t: t.new_zeros(t.shape[:3]), f["QT"])
-        self.micro_par = {"v_fall": mp.V_FALL if v_fall is None else float(v_fall), "qc0": mp.QC0 if qc0 is None else float(qc0),
-                          "k_auto": mp.K_AUTO if k_auto is None else float(k_auto), "k_acc": mp.K_ACC if k_acc is None else float(k_acc)}
-        self.micro, self._micro_prof = True, None
-        self._thermo_stale = True                         # (K12's next launch also writes the cells' temperature)
-        self._drop_water_paths()
-
-    def _microphysics(self, dt):
-        """K14 on the stepped fields: QT, THL, QR, rain2d and their profiles; QL (and Qsat) are then those of the new QT and THL"""
-        import torch
-        from . import microphysics as mp
-        eng, f, p, par = self._eng(), self.fields3d, self.p, self.micro_par
-        if self.n == 0:
-            return
-        if not (self.thermo or "Qsat" in f):              # (an attached QL without Qsat could not follow the QT this step changes)
-            raise ValueError("the microphysics (K14) needs the cloud water of the current QT: a Qsat field, or enable_thermo()")
-        self._ensure_ql()                                 # (thermo: K12 where stale, with the cells' temperature in f["T"])
-        # everything the profiles are made of; the four [n x nL] / [nL] host arrays are copied and compared every step (kilobytes)
-        key = (float(dt), par["v_fall"]) + tuple(numpy.array(a, dtype=numpy.float64) for a in (p["presf"], p["Rhobf"], self.zh_cache, self.zf_cache))
-        if self._micro_prof is None or self._micro_prof[0][:2] != key[:2] or not all(
-                a.shape == b.shape and numpy.array_equal(a, b) for a, b in zip(self._micro_prof[0][2:], key[2:])):
-            prof = mp.profiles(key[4], key[5], key[3], key[2], dt, par["v_fall"])
-            self._micro_prof = (key, [self._upload(a) for a in prof])
-        if self._qr_spare is None or self._qr_spare is f["QR"] or tuple(self._qr_spare.shape) != tuple(f["QT"].shape):
-            self._qr_spare = self._per_device(torch.empty_like, f["QT"])
-        temp = f.get("T") if self.thermo else None
-        dev = eng.les_microphysics(f["QT"], f["QL"], f["QR"], self._qr_spare, *self._micro_prof[1], dt, thl=f.get("THL"), temp=temp,
-                                   rain=self.rain2d, qc0=par["qc0"], k_auto=par["k_auto"], k_acc=par["k_acc"])
-        f["QR"], self._qr_spare = self._qr_spare, f["QR"]
-        rain = eng.slab_means({"Rain": self._per_device(lambda t: t.unsqueeze(-1), self.rain2d)})["Rain"]
-        with eng.on_stream():
-            m = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
-            p["Rain"] = numpy.asarray(self._host(rain), dtype=numpy.float64)[:, 0]
-        p["QR"] = m["QR"]
-        if "QI" in m:
-            p["QL_ice"] = m["QI"]
-        own = {k: m[k] for k in ("QT", "THL") if k in m}
-        p.update(own)
-        if self._means is not None:
-            self._means.update(own)
-        self._drop_water_paths()
-        self._thermo_stale = True                         # thermo: the tail of the step runs K12 on the new QT and THL
-        if not self.thermo and "Qsat" in f:
-            def saturate(ql, qt, qs):
-                torch.sub(qt, qs, out=ql)
-                return ql.clamp_min_(0.0)
-            self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
-            ql = eng.slab_means({"QL": f["QL"]})["QL"]
-            with eng.on_stream():
-                p["QL"] = numpy.asarray(self._host(ql), dtype=numpy.float64)
-            if self._means is not None:
-                self._means["QL"] = p["QL"]
-
-    # -- implicit vertical diffusion and surface fluxes (K15), opt-in ---------------------------------------------------------
-    diffusion = False                                  # enable_diffusion(): the columns mix and take the surface fluxes
-    diffuse_par = None                                 # k_max, h_mix, k_bg
-    DIFFUSE_KEYS = ("U", "V", "THL", "QT")             # fields a step diffuses, where they exist
-    DIFFUSE_FLUX = {"THL": "wt", "QT": "wq"}           # field -> the slot of ``tend`` that holds its kinematic surface flux
-    _diffuse_prof = None                               # ((dt, k_max, h_mix, k_bg, host Rhobf, zh, zf) of the upload, device a, m, cp, s0)
-
-    def enable_diffusion(self, k_max=None, h_mix=None, k_bg=None):
-        """from now on every ``evolve_model_batched`` runs ONE K15 launch per device (``Engine.les_diffuse``)
-        on the fields among U, V, THL and QT that exist, after the step and before K14 / K12: one backward-Euler step of the
-        vertical diffusion with the profile of ``diffusion.diffusivity``.  THL takes the surface flux ``set_wt_surf`` /
-        ``WT_surf`` handed over, QT that of ``set_wq_surf`` / ``WQ_surf`` (kinematic, positive upward; none where none was
-        set); U and V take none (no surface drag).  The profiles then are K10's means of the diffused fields and QL follows
-        the new QT.  The coefficients are uploaded again whenever dt, a parameter, Rhobf or the grid (zh, zf) changed.  The
-        parameters default to those of ``diffusion``.  Without this call every path of the ensemble is unchanged."""
-        from . import diffusion as df
-        if not any(k in self.fields3d for k in self.DIFFUSE_KEYS):
-            raise ValueError("the diffusion (K15) needs one of the fields %s (set_fields_batched)" % (self.DIFFUSE_KEYS,))
-        if not all(callable(getattr(e, "les_diffuse", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
-            raise ValueError("the engine has no les_diffuse (K15)")
-        self.diffuse_par = {"k_max": df.K_MAX if k_max is None else float(k_max), "h_mix": df.H_MIX if h_mix is None else float(h_mix),
-                            "k_bg": df.K_BG if k_bg is None else float(k_bg)}
-        self.diffusion, self._diffuse_prof = True, None
-
-    def _diffuse(self, dt):
-        """K15 on the stepped fields; QL (without thermo) and the profiles are then those of the diffused fields"""
-        import torch
-        from . import diffusion as df
-        eng, f, p, par = self._eng(), self.fields3d, self.p, self.diffuse_par
-        keys = [k for k in self.DIFFUSE_KEYS if k in f]
-        if self.n == 0 or not keys:
-            return
-        # everything the coefficients are made of; the host arrays are copied and compared every step (kilobytes)
-        key = (float(dt), par["k_max"], par["h_mix"], par["k_bg"]) + tuple(numpy.array(a, dtype=numpy.float64) for a in (p["Rhobf"], self.zh_cache, self.zf_cache))
-        if self._diffuse_prof is None or self._diffuse_prof[0][:4] != key[:4] or not all(
-                a.shape == b.shape and numpy.array_equal(a, b) for a, b in zip(self._diffuse_prof[0][4:], key[4:])):
-            prof = df.profiles(key[5], key[6], key[4], dt, par["k_max"], par["h_mix"], par["k_bg"])
-            self._diffuse_prof = (key, [self._upload(a) for a in prof])
-        a, m, cp, s0 = self._diffuse_prof[1]
-        flux = {k: self._upload(numpy.asarray(self.tend[slot], dtype=numpy.float64).reshape(self.n))
-                for k, slot in self.DIFFUSE_FLUX.items() if k in keys and slot in self.tend}
-        eng.les_diffuse({k: f[k] for k in keys}, a, m, cp, s0=s0, flux=flux)
-        self._drop_water_paths()
-        self._thermo_stale = True                         # thermo: K12 runs on the diffused THL and QT before their next use
-        if not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
-            self._ensure_ql()
-
-            def saturate(ql, qt, qs):
-                torch.sub(qt, qs, out=ql)
-                return ql.clamp_min_(0.0)
-            self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
-        self._means = None
-        self._slab_means()                                # p[U, V, THL, QT, QL] = the slab means of the diffused fields
-
-    # -- horizontal upwind advection on the periodic plane (K16), opt-in --------------------------------------------------------
-    advection = False                                  # enable_advection(): the winds carry the fields along i and j
-    advect_par = None                                  # cfl, max_substeps
-    dx = dy = None                                     # the grid spacings, m (scalars or [n]); None: those of ``advection``
-    ADVECT_KEYS = ("U", "V", "THL", "QT", "QR")        # fields a step advects, where they exist
-    advect_courant = None                              # the largest Courant sum any substep of the last step returned
-    advect_substeps = None                             # the substeps of the last step
-    _advect_spare = None                               # name -> the buffer K16 writes next (it reads the field)
-    _advect_coef = None                                # ((dt, dx, dy) of the uploads, {substeps: device (hx, hy)})
-    advect_vertical = False                            # enable_advection(vertical=True): K17 follows every K16 substep
-    advect_courant_z = None                            # the largest vertical Courant sum any substep of the last step returned
-    _vadvect_prof = None                               # (the host weights of the upload, device (g, r))
-    _vadvect_mtop = None                               # the mass flux through the upper faces in the last substep, device
-    _vadvect_dt = None                                 # the seconds of that substep
-
-    def enable_advection(self, dx=None, dy=None, cfl=None, max_substeps=None, vertical=False):
-        """from now on every ``evolve_model_batched`` advects the fields among U, V, THL, QT and QR that exist with the winds U
-        and V on the doubly periodic plane (K16, ``Engine.les_advect``), after the step and before K15 / K14 /
-        K12: ONE probe launch per device finds the largest Courant sum c of the whole step, n_sub = max(1, ceil(c / cfl))
-        launches of dt / n_sub follow, each into spare buffers that are swapped in (RuntimeError, the fields as the step left
-        them, where c is not finite or n_sub > max_substeps).  ``advect_substeps`` and ``advect_courant`` hold n_sub and the
-        largest Courant sum of the substeps.  The profiles then are K10's means of the advected fields and QL follows the new
-        QT.  ``dx`` and ``dy`` (m, scalars or one per LES) are also what the rows' get_dx / get_dy / get_xsize / get_ysize
-        answer.  The coefficients are uploaded again whenever dt, n_sub, dx or dy changed.  The parameters default to those of
-        ``advection``.  Needs U and V fields.  Without this call every path of the ensemble is unchanged.
-
-        ``vertical=True`` adds the vertical advection by the mass flux of continuity (K17, ``Engine.les_vadvect``): a K17 probe
-        follows K16's, both with the coefficients of the whole step, n_sub comes from the larger of their Courant sums, and
-        every substep is K16, a swap, K17 on the same fields (with the winds K16 just produced) into the same spare buffers and
-        a swap: 2 + 2 n_sub launches per device and step.  The profiles g = ``water_path_weights()`` and r = 1 / g are uploaded
-        once.  ``advect_courant_z`` holds the largest vertical Courant sum of the substeps (it can grow during them, so it is
-        recorded and refused only where it is not finite: RuntimeError), ``get_vertical_wind_batched()`` the vertical wind of
-        the last substep.  With the default every path, launch count and result is what it is without the argument."""
-        from . import advection as adv
-        if "U" not in self.fields3d or "V" not in self.fields3d:
-            raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
-        if not all(callable(getattr(e, "les_advect", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
-            raise ValueError("the engine has no les_advect (K16)")
-        if vertical and not all(callable(getattr(e, "les_vadvect", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
-            raise ValueError("the engine has no les_vadvect (K17)")
-        dx, dy = adv.DX if dx is None else dx, adv.DY if dy is None else dy
-        adv.coefficients(1.0, dx, dy, n=self.n)                       # (ValueError for a spacing that is not positive, or not [n])
-        self.dx = numpy.array(dx, dtype=numpy.float64) if numpy.ndim(dx) else float(dx)
-        self.dy = numpy.array(dy, dtype=numpy.float64) if numpy.ndim(dy) else float(dy)
-        self.advect_par = {"cfl": adv.CFL if cfl is None else float(cfl),
-                           "max_substeps": adv.MAX_SUBSTEPS if max_substeps is None else int(max_substeps)}
-        if not self.advect_par["cfl"] > 0 or self.advect_par["max_substeps"] < 1:
-            raise ValueError("the advection (K16) needs cfl > 0 and max_substeps >= 1")
-        self.advection, self._advect_coef, self._advect_spare = True, None, {}
-        self.advect_vertical, self._vadvect_prof, self._vadvect_mtop, self._vadvect_dt = bool(vertical), None, None, None
-        self.advect_courant_z = None
-
-    def _advect_coefs(self, dt, n_sub):
-        """device (hx, hy) of the substeps dt / n_sub; uploaded where dt, n_sub, dx or dy are not those of the last step"""
-        from . import advection as adv
-        key = (float(dt), numpy.array(self.dx, dtype=numpy.float64), numpy.array(self.dy, dtype=numpy.float64))
-        old = self._advect_coef
-        if old is None or old[0][0] != key[0] or not all(a.shape == b.shape and numpy.array_equal(a, b) for a, b in zip(old[0][1:], key[1:])):
-            old = self._advect_coef = (key, {})
-        if n_sub not in old[1]:
-            for m in [m for m in old[1] if m != 1]:               # the probe's and one other: n_sub changed
-                del old[1][m]
-            old[1][n_sub] = tuple(self._upload(a) for a in adv.coefficients(float(dt) / n_sub, self.dx, self.dy, n=self.n))
-        return old[1][n_sub]
-
-    def _device_max(self, t):
-        """the largest element of a device vector (of the blocks of a Sharded one): one number per device to the host"""
-        eng = self._eng()
-        parts = [(e, part) for e, part in zip(getattr(eng, "engines", [eng]), getattr(t, "parts", [t])) if part.numel()]
-        vals = []
-        for e, part in parts:
-            with e.on_stream():
-                vals.append(part.max())
-        return max(float(v.item()) for v in vals)
-
-    def _advect(self, dt):
-        """K16 on the stepped fields: the probe, then n_sub launches into the spare buffers; QL (without thermo) and the
-        profiles are then those of the advected fields, unless K15 follows and does both"""
-        import torch
-        from . import advection as adv
-        eng, f, par = self._eng(), self.fields3d, self.advect_par
-        if self.n == 0:
-            return
-        if "U" not in f or "V" not in f:
-            raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
-        keys = [k for k in self.ADVECT_KEYS if k in f]
-        c = self._device_max(eng.les_advect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1)))
-        vertical = self.advect_vertical
-        if vertical:                                      # K17's probe: the vertical Courant sums of the whole step
-            g, r = self._vadvect_profiles()
-            c = max(c, self._device_max(eng.les_vadvect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1), g, r)))
-        try:
-            n_sub = adv.substeps(c, par["cfl"], par["max_substeps"])
-        except RuntimeError:                              # nothing has been advected: QL and the profiles of the stepped fields
-            self._follow_fields()
-            raise
-        hx, hy = self._advect_coefs(dt, n_sub)
-        spare = self._advect_spare
-        for k in keys:
-            if spare.get(k) is None or spare[k] is f[k] or tuple(spare[k].shape) != tuple(f[k].shape):
-                spare[k] = self._per_device(torch.empty_like, f[k])
-        if vertical and (self._vadvect_mtop is None or tuple(self._vadvect_mtop.shape) != tuple(f["U"].shape)):
-            self._vadvect_mtop = self._per_device(torch.empty_like, f["U"])
-        worst = worst_z = None
-        for _ in range(n_sub):
-            out = {k: spare[k] for k in keys}
-            cm = eng.les_advect({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy)
-            for k in keys:
-                f[k], spare[k] = spare[k], f[k]
-            worst = cm if worst is None else self._per_device(torch.maximum, worst, cm)
-            if vertical:                                  # K17 reads the winds K16 just produced
-                out = {k: spare[k] for k in keys}
-                cz = eng.les_vadvect({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy, g, r, mtop=self._vadvect_mtop)
-                for k in keys:
-                    f[k], spare[k] = spare[k], f[k]
-                worst_z = cz if worst_z is None else self._per_device(torch.maximum, worst_z, cz)
-        self.advect_substeps, self.advect_courant = n_sub, self._device_max(worst)
-        if vertical:
-            self._vadvect_dt = float(dt) / n_sub
-            self.advect_courant_z = self._device_max(worst_z)
-        self._drop_water_paths()
-        self._thermo_stale = True                         # thermo: K12 runs on the advected THL and QT before their next use
-        if not self.diffusion:                            # (else the QL field and the means follow the diffused fields: _diffuse)
-            self._follow_fields()
-        if vertical and not numpy.isfinite(self.advect_courant_z):
-            raise RuntimeError("the vertical advection (K17) found the Courant sum c = %r: the mass flux is not finite" % self.advect_courant_z)
-
-    def _vadvect_profiles(self):
-        """device (g, r) of K17: g = water_path_weights(), r = 1 / g; uploaded once, and again where the weights changed"""
-        from . import advection as adv
-        w = numpy.ascontiguousarray(self.water_path_weights())
-        if self._vadvect_prof is None or not numpy.array_equal(self._vadvect_prof[0], w):
-            self._vadvect_prof = (w, tuple(self._upload(a) for a in adv.vertical_profiles(w)))
-        return self._vadvect_prof[1]
-
-    def get_vertical_wind_batched(self):
-        """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the vertical wind W in m/s
-        at the UPPER faces of the cells, positive upward, that continuity gave the last substep of the last step
-        (``advection.vertical_wind`` of K17's mass flux); None before the first step of enable_advection(vertical=True)"""
-        from . import advection as adv
-        if not self.advect_vertical or self._vadvect_mtop is None or self._vadvect_dt is None:
-            return None
-        rho = self._upload(numpy.asarray(self.p["Rhobf"], dtype=numpy.float64))
-        return self._per_device(lambda m, rh: adv.vertical_wind(m, rh, self._vadvect_dt), self._vadvect_mtop, rho)
-
-    # -- longwave cooling and warming by the liquid water (K18), opt-in ---------------------------------------------------------
-    radiation = False                                  # enable_radiation(): the cloud water acts on THL
-    radiate_par = None                                 # f0, f1, kappa: float64 [n] each
-    _radiate_prof = None                               # ((dt, host kappa, Rhobf, presf, zh) of the upload, device w, c)
-    _radiate_scale = None                              # device (f0, f1)
-    _radiate_flux = None                               # the flux at the upper faces in the last step, device
-
-    def enable_radiation(self, f0=None, f1=None, kappa=None):
-        """from now on every ``evolve_model_batched`` runs ONE K18 launch per device (``Engine.les_radiate``) on
-        THL with the current QL and the whole step's dt, after K16 / K17 / K15 and before K14 / K12: the first two terms of the
-        GCSS / DYCOMS-II parametrised longwave flux cool the air at the top of a cloud and warm it at its base.  ``f0``, ``f1``
-        (W/m2) and ``kappa`` (m2/kg) are scalars or one value per LES and default to those of ``radiation``.  Needs a THL
-        field, more than one level, and cloud water that follows the fields: a Qsat field or ``enable_thermo()`` (ValueError
-        otherwise).  Launches per step and device: ONE K18, and one K10 for the means of the new fields; with
-        ``enable_thermo()`` one K12 more than without this call (K12 runs on the fields K18 reads QL of, and again on the new
-        THL before the means are formed).  w and c are uploaded again only where dt, kappa, Rhobf,
-        presf or the half levels changed.  ``get_radiative_flux_batched()`` returns the flux.  Without this call every path,
-        launch count and result of the ensemble is unchanged."""
-        from . import radiation as rad
-        if self.nL == 1:
-            raise ValueError("the radiation (K18) does not take LES of one level")
-        if "THL" not in self.fields3d:
-            raise ValueError("the radiation (K18) needs a THL field (set_fields_batched)")
-        if not (self.thermo or "Qsat" in self.fields3d):
-            raise ValueError("the radiation (K18) needs the cloud water of the current fields: a Qsat field, or enable_thermo()")
-        if not all(callable(getattr(e, "les_radiate", None)) for e in getattr(self._eng(), "engines", [self._eng()])):
-            raise ValueError("the engine has no les_radiate (K18)")
-        par = {}
-        for name, v, d in (("f0", f0, rad.F0), ("f1", f1, rad.F1), ("kappa", kappa, rad.KAPPA)):
-            a = numpy.asarray(d if v is None else v, dtype=numpy.float64)
-            if a.ndim > 1 or (a.ndim == 1 and a.shape != (self.n,)) or not numpy.isfinite(a).all():
-                raise ValueError("the radiation (K18) needs a finite %s: a scalar or one value per LES" % name)
-            par[name] = numpy.array(numpy.broadcast_to(a, (self.n,)), order="C")
-        self.radiate_par = par
-        self.radiation, self._radiate_prof, self._radiate_scale, self._radiate_flux = True, None, None, None
-
-    def _radiate(self, dt):
-        """K18 on the stepped THL with the QL of the stepped fields; the profiles are then the means of the new fields"""
-        import torch
-        from . import radiation as rad
-        eng, f, p, par = self._eng(), self.fields3d, self.p, self.radiate_par
-        if self.n == 0:
-            return
-        if "THL" not in f or not (self.thermo or "Qsat" in f):
-            raise ValueError("the radiation (K18) needs a THL field and a Qsat field or enable_thermo()")
-        self._ensure_ql()                                 # (thermo: K12 where stale)
-        # everything the profiles are made of; the host arrays are copied and compared every step (kilobytes)
-        key = (float(dt),) + tuple(numpy.array(a, dtype=numpy.float64) for a in (par["kappa"], p["Rhobf"], p["presf"], self.zh_cache))
-        if self._radiate_prof is None or self._radiate_prof[0][0] != key[0] or not all(
-                a.shape == b.shape and numpy.array_equal(a, b) for a, b in zip(self._radiate_prof[0][1:], key[1:])):
-            self._radiate_prof = (key, [self._upload(a) for a in rad.profiles(key[2], key[4], key[3], dt, key[1])])
-        if self._radiate_scale is None:
-            self._radiate_scale = (self._upload(par["f0"]), self._upload(par["f1"]))
-        if self._radiate_flux is None or tuple(self._radiate_flux.shape) != tuple(f["THL"].shape):
-            self._radiate_flux = self._per_device(torch.empty_like, f["THL"])
-        eng.les_radiate(f["QL"], f["THL"], *self._radiate_prof[1], *self._radiate_scale, flux=self._radiate_flux)
-        self._follow_fields()                             # K12 stale, QL of the QT field, p[U, V, THL, QT, QL] = K10's means
-
-    def get_radiative_flux_batched(self):
-        """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the net upward longwave
-        flux in W/m2 at the UPPER faces of the cells that the last step's K18 launch found; None before the first step of
-        enable_radiation()"""
-        return self._radiate_flux if self.radiation else None
-
-    def _follow_fields(self):
-        """QL = max(QT - Qsat, 0) of the QT field as it is now (without thermo) and p[U, V, THL, QT, QL] = K10's means"""
-        import torch
-        f = self.fields3d
-        self._drop_water_paths()
-        self._thermo_stale = True
-        if not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
-            self._ensure_ql()
-
-            def saturate(ql, qt, qs):
-                torch.sub(qt, qs, out=ql)
-                return ql.clamp_min_(0.0)
-            self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
-        self._means = None
-        self._slab_means()
-
-    @classmethod
-    def for_gcm(cls, gcm, grid_indices, nL=160, seed=0, itot=8, jtot=8, engine=None):
-        ens = super().for_gcm(gcm, grid_indices, nL, seed)
-        ens.itot, ens.jtot, ens.engine = int(itot), int(jtot), engine
-        return ens
-
-    def __getitem__(self, i):
-        if isinstance(i, slice):
-            return [self[j] for j in range(*i.indices(self.n))]
-        if self._rows[i] is None:
-            self._rows[i] = _DeviceLESRow(self, i)
-        return self._rows[i]
-
-    # -- plumbing: one engine or one engine per device ------------------------------------------------------------------
-    def _eng(self):
-        if self.engine is None:
-            from . import spcpl
-            self.engine = spcpl.get_engine()
-        return self.engine
-
-    def _per_device(self, fn, *xs):
-        """``fn(x, ...)`` on the engine's stream; with Sharded arguments on every device's block, on that engine's stream"""
-        from .transfer import Sharded
-        eng = self._eng()
-        ex = next((x for x in xs if isinstance(x, Sharded) and x.bounds is not None), None)
-        if ex is None:
-            with eng.on_stream():
-                return fn(*xs)
-        parts = []
-        for d, e in enumerate(eng.engines):
-            with e.on_stream():
-                parts.append(fn(*[(x.parts[d] if isinstance(x, Sharded) else x) for x in xs]))
-        return Sharded(parts, ex.bounds)
-
-    def _upload(self, a, dtype=None):
-        eng = self._eng()
-        with eng.on_stream():
-            return eng.to_devices(numpy.ascontiguousarray(a), rows=self.n, dtype=dtype or eng.dtype)
-
-    @staticmethod
-    def _host(t):
-        from .transfer import Sharded
-        return t.to_host() if isinstance(t, Sharded) else t.cpu().numpy()
-
-    # -- 3-D fields --------------------------------------------------------------------------------------------------
-    def attach_fields(self, fields):
-        for k, v in fields.items():
-            self.set_fields_batched(k, v)
-
-    def get_fields_batched(self, name):
-        """the device tensor itself (no copy): what K6 and K10 work on"""
-        if name == "QL" or (self.thermo and name == "Qsat"):
-            self._ensure_ql()
-        return self.fields3d[name]
-
-    def set_fields_batched(self, name, values):
-        """a device tensor (Sharded) of the engine's is kept as it is; a NumPy array is uploaded once"""
-        import torch
-        from .transfer import Sharded
-        values = getattr(values, "number", values)
-        dt = self._eng().dtype
-        if isinstance(values, (torch.Tensor, Sharded)):
-            conv = lambda t: t if t.dtype == dt else t.to(dt)                              # noqa: E731
-            values = self._per_device(conv, values)
-        else:
-            values = self._upload(numpy.asarray(values))
-        shape = tuple(values.shape)
-        if len(shape) != 4 or shape[0] != self.n or shape[3] != self.nL:
-            raise ValueError("field %s must be [%d x itot x jtot x %d], got %s" % (name, self.n, self.nL, shape))
-        self.itot, self.jtot = int(shape[1]), int(shape[2])
-        self.fields3d[name] = values
-        self._means = None
-        self._drop_water_paths()
-        self._thermo_stale = True                       # (K12 writes Qsat and QL in place, not through here)
-
-    def set_field_row(self, i, name, values):
-        raise NotImplementedError("a DeviceLESEnsemble takes whole fields: set_fields_batched")
-
-    def _ensure_ql(self):
-        import torch
-        if self.thermo:
-            return self._ensure_thermo()
-        f = self.fields3d
-        if "QL" not in f:
-            f["QL"] = self._per_device(lambda qt, qs: torch.clamp_min(qt - qs, 0.0), f["QT"], f["Qsat"])
-            self._means = None
-
-    def _slab_means(self):
-        """host [n x nL] slab means of every field in MEAN_KEYS: one launch, cached until a field changes"""
-        if self.thermo:
-            self._ensure_thermo()
-        if self._means is None:
-            if "QT" in self.fields3d and "Qsat" in self.fields3d:
-                self._ensure_ql()
-            eng = self._eng()
-            own = self.thermo and self._thermo_means is not None      # the mean of QL came with K12's launch
-            dev = eng.slab_means({k: self.fields3d[k] for k in self.MEAN_KEYS if k in self.fields3d and not (own and k == "QL")})
-            with eng.on_stream():
-                self._means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
-            if own:
-                self._means["QL"] = self._thermo_means["QL"]
-            self.p.update(self._means)
-        return self._means
-
-    # -- column water paths (K13) ------------------------------------------------------------------------------------------
-    def _drop_water_paths(self):
-        self._wp, self._wp_host = None, {}
-
-    def water_path_weights(self):
-        """host float64 [n x nL]: Rhobf * dz, dz the thickness of the LES layers from the half levels zh (the lower faces):
-        dz[k] = zh[k + 1] - zh[k]; the top layer has no upper half level and takes the thickness of the layer below it,
-        dz[nL - 1] = dz[nL - 2]; an LES of one level takes twice the distance of its full level from its half level"""
-        zh = numpy.asarray(self.zh_cache, dtype=numpy.float64)
-        if self.nL > 1:
-            dz = numpy.diff(zh, axis=-1)
-            dz = numpy.concatenate([dz, dz[..., -1:]], axis=-1)
-        else:
-            dz = 2.0 * (numpy.asarray(self.zf_cache, dtype=numpy.float64) - zh)
-        return numpy.asarray(self.p["Rhobf"], dtype=numpy.float64) * dz
-
-    def get_water_paths_batched(self, names=("LWP", "TWP", "RWP"), cloud_cover=False):
-        """dict name -> device tensor [n x itot x jtot] (Sharded row blocks under a MultiDeviceEngine) of the column water
-        paths ``numpy.add.reduce(field * w[:, None, None, :], axis=3)``, w = ``water_path_weights()`` in the engine's dtype:
-        LWP of the QL field (after K12 where thermo is enabled and stale), TWP of QT, RWP of an attached QR field.  A name
-        whose field the ensemble does not hold is left out; KeyError where none is left.  ``cloud_cover`` adds ``"top"``
-        (int32: the highest cloudy level of QL per column, -1 for none) and ``"cover"`` ([n]: the fraction of cloudy
-        columns).  What is not cached goes through ONE launch per device; the results are cached until a field changes."""
-        unknown = [k for k in names if k not in self.WATER_PATHS]
-        if unknown:
-            raise KeyError("no water path %s (there are %s)" % (unknown, sorted(self.WATER_PATHS)))
-        f = self.fields3d
-        if ("LWP" in names or cloud_cover) and (self.thermo or "QL" in f or ("QT" in f and "Qsat" in f)):
-            self._ensure_ql()
-        have = [k for k in names if self.WATER_PATHS[k] in f]
-        if not have or (cloud_cover and "QL" not in f):
-            raise KeyError("the ensemble holds no field for %s" % ("the cloud cover (QL)" if have else list(names)))
-        w = numpy.ascontiguousarray(self.water_path_weights())
-        if self._wp_w is None or not numpy.array_equal(self._wp_w[0], w):
-            self._wp_w = (w, self._upload(w))                       # .astype(T) of the float64 product
-            self._drop_water_paths()                                # results of other weights (p["Rhobf"] was set) are stale
-        cache = self._wp if self._wp is not None else {}
-        need = [k for k in have if k not in cache]
-        cloud = cloud_cover and "cover" not in cache
-        out = None
-        if cloud and "LWP" not in need:                             # the cloud pass walks QL: LWP comes with it, ...
-            need.insert(0, "LWP")
-            if "LWP" in cache:                                      # ... again into its cached tensor where there is one
-                out = {"LWP": cache["LWP"]}
-        if need:
-            cache.update(self._eng().les_water_paths({k: f[self.WATER_PATHS[k]] for k in need}, self._wp_w[1],
-                                                     cloud="LWP" if cloud else None, out=out, top=cloud, cover=cloud))
-            self._wp = cache
-            for k in need:
-                self._wp_host.pop(k, None)
-        return {k: cache[k] for k in have + (["top", "cover"] if cloud_cover else [])}
-
-    def _water_path_host(self, name):
-        t = self.get_water_paths_batched((name,))[name]           # (cached; it drops the host copies where p["Rhobf"] changed the weights)
-        if name not in self._wp_host:
-            with self._eng().on_stream():
-                self._wp_host[name] = numpy.asarray(self._host(t))
-        return self._wp_host[name]
-
-    def get_water_path_means(self, names=("LWP", "TWP", "RWP")):
-        """host dict name -> [n]: ``wp[l].mean()`` of every LES, bit for bit: K10's slab means of the 2-D result viewed as
-        [n x itot x jtot x 1] (a one-level field is one contiguous run per LES, which NumPy sums pairwise)"""
-        wp = self.get_water_paths_batched(names)
-        eng = self._eng()
-        dev = eng.slab_means({k: self._per_device(lambda t: t.unsqueeze(-1), v) for k, v in wp.items()})
-        with eng.on_stream():
-            return {k: numpy.asarray(self._host(v))[:, 0] for k, v in dev.items()}
-
-    # -- batched protocol ----------------------------------------------------------------------------------------------
-    @_timed
-    def get_profiles_batched(self, keys, out):
-        if self.thermo:
-            self._ensure_thermo()                         # p["T"] and p["QL"] of the fields as they are now
-        means = self._slab_means() if any(k in self.MEAN_KEYS and k in self.fields3d for k in keys) else {}
-        for k in keys:
-            numpy.copyto(out[k], means[k] if k in means else self.p[k])
-
-    def _refresh_profile(self, key):
-        """p[key] of the fields as they are now, by the rule of get_profiles_batched (the rows' getters read p: a nudge or
-        set_fields_batched leaves the means of the old fields there)"""
-        if self.thermo:
-            self._ensure_thermo()
-        if key in self.MEAN_KEYS and key in self.fields3d:
-            self._slab_means()
-
-    @_timed
-    def get_cloudfraction_batched(self, indices, out):
-        import torch
-        self._ensure_ql()
-        eng = self._eng()
-        idx = self._upload(numpy.asarray(indices, dtype=numpy.int32), dtype=torch.int32)
-        A = eng.slab_cloud_fraction(self.fields3d["QL"], idx)
-        with eng.on_stream():
-            numpy.copyto(out, self._host(A))
-
-    def _fused_step(self, dt):
-        """the step of the fields, the QL field and the slab means of the new fields from ONE launch per device (K11,
-        ``Engine.les_advance``); False -- nothing done -- where the engine has no such method, the LES have one level (numpy
-        reduces a one-level plane pairwise: K10's own kernel), nothing is stepped or saturated, or ``fused_advance`` is off"""
-        import torch
-        eng, f = self._eng(), self.fields3d
-        keys = [k for k in self.STEP_KEYS if k in f]
-        sat = "QT" in f and "Qsat" in f and not self.thermo          # (thermo: QL is K12's, after the step)
-        if not (self.fused_advance and self.nL > 1 and self.n > 0 and keys and (sat or any(k in self.tend for k in keys))):
-            return False
-        if max(int(part.shape[0]) for part in getattr(f[keys[0]], "parts", [f[keys[0]]])) < self.FUSED_MIN_LES:
-            return False                                  # a launch of few LES is a latency chain: the torch path is faster
-        if ("QL" in f and not sat and not self.thermo) or not all(callable(getattr(e, "les_advance", None)) for e in getattr(eng, "engines", [eng])):
-            return False
-        tend = {k: self._upload(self.tend[k]) for k in keys if k in self.tend}
-        if sat and "QL" not in f:
-            f["QL"] = self._per_device(torch.empty_like, f["QT"])          # written whole by the launch
-        dev = eng.les_advance({k: f[k] for k in keys}, tend, dt, qsat=f["Qsat"] if sat else None, sat="QT" if sat else None,
-                              ql=f["QL"] if sat else None)
-        with eng.on_stream():
-            self._means = {k: numpy.asarray(self._host(v), dtype=numpy.float64) for k, v in dev.items()}
-        self.p.update(self._means)
-        self._thermo_stale = True
-        return True
-
-    @_timed
-    def evolve_model_batched(self, t):
-        import torch
-        dt = float(t) - self.model_time
-        if dt <= 0:
-            return
-        f, p = self.fields3d, self.p
-        self._drop_water_paths()
-        if self._fused_step(dt):
-            pass                                          # K11: fields, QL and p[U, V, THL, QT, QL] from one launch
-        else:
-            for key in self.STEP_KEYS:
-                if key in self.tend and key in f:
-                    def step(field, tend):
-                        inc = tend * dt                   # two separate ops: nothing contracts to an fma
-                        return field.add_(inc[:, None, None, :])
-                    self._per_device(step, f[key], self._upload(self.tend[key]))
-            self._thermo_stale = True
-            if self.diffusion or self.advection:
-                pass                                      # (the QL field and the means follow the diffused / advected fields)
-            elif not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
-                self._ensure_ql()
-
-                def saturate(ql, qt, qs):
-                    torch.sub(qt, qs, out=ql)
-                    return ql.clamp_min_(0.0)
-                self._per_device(saturate, f["QL"], f["QT"], f["Qsat"])
-            if not (self.diffusion or self.advection):
-                self._means = None
-                self._slab_means()                        # p[U, V, THL, QT, QL] = the slab means of the new fields
-        if "PS" in self.tend:
-            p["PS"] = p["PS"] + dt * self.tend["PS"]
-        if self.advection:
-            self._advect(dt)                              # 1 + n_sub K16 launches: U, V, THL, QT, QR carried along i and j; p[...]
-                                                          # (vertical: a K17 probe and a K17 launch behind every K16 substep)
-        if self.diffusion:
-            self._diffuse(dt)                             # one K15 launch: U, V, THL, QT mixed along k, the surface fluxes; p[...]
-        if self.radiation:
-            self._radiate(dt)                             # one K18 launch: THL cooled at the cloud tops, warmed at the bases; p[...]
-        if self.micro:
-            self._microphysics(dt)                        # one K14 launch: QT, THL, QR, rain2d; p[QT, THL, QR, Rain(, QL_ice)]
-        if self.thermo:
-            self._ensure_thermo()                         # one K12 launch: the Qsat and QL fields, p["QL"] and p["T"]
-        p["QL_ice"] = numpy.minimum(p["QL_ice"], p["QL"])
-        if not (self.thermo and self._thermo_means is not None):
-            p["T"] = p["THL"] * (p["presf"] / 1e5) ** (287.04 / 1004.) + 2.53e6 * p["QL"] / 1004.
-        if not self.micro:
-            p["Rain"] = p["Rain"] + 1e-6 * dt
-        self.model_time = float(t)
+def __getattr__(name):
+    """``models.DeviceLESEnsemble`` and ``models._DeviceLESRow`` are those of device_les.py, which imports this module: it
+    is imported when one of the two is first asked for, and this module stays pure NumPy until then"""
+    if name in ("DeviceLESEnsemble", "_DeviceLESRow"):
+        from . import device_les
+        return getattr(device_les, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,4 +1,5 @@
-"""Random operation sequences of models.DeviceLESEnsemble against its eager NumPy twin (tests/les_radiate_ref.py:
+"""Random operation sequences of models.DeviceLESEnsemble (the class lives in sp_coupler_amd/device_les.py; the name in models
+is the same object) against its eager NumPy twin (tests/les_radiate_ref.py:
 HostRadiateLESEnsemble / HostThermoRadiateLESEnsemble, the top of the chain of twins): the body of
 tests/test_ensemble_sequences_cpu.py (on oracle-backed engines) and tests/test_ensemble_sequences_gpu.py (on the card).
 

@@ -20,7 +20,7 @@ import textwrap
 import numpy
 import pytest
 
-from sp_coupler_amd import models, spcpl
+from sp_coupler_amd import device_les, models, spcpl
 from sp_coupler_amd.multi import MultiDeviceEngine
 from tests import ensemble_sequences as es
 from tests import les_micro_ref as lmr
@@ -155,7 +155,7 @@ def _edited(method, old, new):
     """``method`` of DeviceLESEnsemble with ``old`` (which occurs exactly once in its source) replaced by ``new``"""
     src = textwrap.dedent(inspect.getsource(getattr(models.DeviceLESEnsemble, method)))
     assert src.count(old) == 1, (method, old, src.count(old))
-    ns = dict(vars(models))
+    ns = dict(vars(device_les))
     exec(compile(src.replace(old, new), "<state mutant of %s>" % method, "exec"), ns)
     return ns[method]
 
@@ -164,10 +164,11 @@ MUTANTS = {
     1: ("_drop_water_paths", None, None),
     2: ("set_fields_batched", "    self._thermo_stale = True", "    pass"),
     3: ("set_fields_batched", "    self._means = None\n", "    pass\n"),
-    4: ("_diffuse", "self._diffuse_prof[0][:4] != key[:4]", "self._diffuse_prof[0][1:4] != key[1:4]"),
-    5: ("_microphysics", "zip(self._micro_prof[0][2:], key[2:])", "zip(self._micro_prof[0][3:], key[3:])"),
+    4: ("_diffuse", "_kept(self._diffuse_prof, key, ", "_kept(self._diffuse_prof, key if self._diffuse_prof is None else self._diffuse_prof[0][:1] + key[1:], "),
+    5: ("_microphysics", "_kept(self._micro_prof, key, ",
+        "_kept(self._micro_prof, key if self._micro_prof is None else key[:2] + self._micro_prof[0][2:3] + key[3:], "),
     6: ("_microphysics", 'f["QR"], self._qr_spare = self._qr_spare, f["QR"]', "pass"),
-    7: ("get_water_paths_batched", "not numpy.array_equal(self._wp_w[0], w)", "False"),
+    7: ("get_water_paths_batched", "_kept(old, w, ", "_kept(old, w if old is None else old[0], "),
     8: ("set_fields_batched", "    self.fields3d[name] = values\n    self._means = None\n",
         "    same = self.fields3d.get(name) is values\n    self.fields3d[name] = values\n    self._means = self._means if same else None\n"),
 }
