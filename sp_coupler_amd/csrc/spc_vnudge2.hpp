@@ -278,7 +278,10 @@ __global__ __launch_bounds__(VN2_THREADS, RCACHE ? 2 : 4) void k_vnudge_solve(co
     const int CW = TL < 64 ? TL : 64;
     // this lane's steps of the combine program are the same in every evaluation round: read them from the LDS tables ONCE
     // (up to two steps per lane and chunk shape: trees of <= 2 CW + 1 leaves, i.e. every plane the LDS path takes and the
-    // 128-leaf chunks of the streamed path); taller trees walk the tables
+    // 128-leaf chunks of the streamed path); taller trees walk the tables.  No launch of vnudge_impl has such a tree: it takes
+    // nl - 1 > 2 CW with nl <= VN_MAXLEAF = 128, i.e. CW = TL = 32 and more than 65 leaves, and 32 threads per level means 16
+    // levels' planes in one workgroup's LDS (8 where two workgroups share a CU; a float launch keeps the double launch's KT):
+    // planes of at most ~590 points, 8 leaves.  The walk is the general form of the two-step one and has no test of its own.
     int tq_rnd[2][2] = {{0, 0}, {0, 0}}, tq_l[2][2] = {{0, 0}, {0, 0}}, tq_r[2][2] = {{0, 0}, {0, 0}};
     bool tq_fast[2];
 #pragma unroll

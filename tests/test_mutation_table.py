@@ -1,6 +1,7 @@
 """The mutation control's table (tools/mutation_control.py) against the current kernel sources, on the CPU: the shipped
 sources carry no mutant switch, every mutant is present and guarded by a property of tests/semantic_props.py (K10's by a
-body of tests/slab_edges.py, K8's by one of tests/geo_edges.py, K9's by one of tests/les_state_ref.py), and every
+body of tests/slab_edges.py, K8's by one of tests/geo_edges.py, K9's by one of tests/les_state_ref.py, K6's own table by
+one of tests/vnudge_edges.py), and every
 edit still finds its line -- a kernel edit that drops or moves a mutant's line fails here, not as a SURVIVED mutant on the
 GPU box."""
 import os
@@ -69,9 +70,31 @@ def test_k8_k9_mutant_edits_apply_to_the_tree(table, n):
             assert text != f.read(), (n, name)
 
 
+def test_k6_mutants_are_guarded_by_a_body():
+    from tests import vnudge_edges
+    assert sorted(mc.VNUDGE_MUTANTS) == list(range(1, len(mc.VNUDGE_MUTANTS) + 1)) and len(mc.VNUDGE_MUTANTS) >= 10
+    guards = set()
+    for n, (what, guard, edits) in mc.VNUDGE_MUTANTS.items():
+        assert what and edits and callable(guard) and all(e[0] in (mc.VN, mc.VN2, mc.VN_HOST) for e in edits), n
+        mod, name = guard.__name__.split(".", 1)
+        assert mod == "vnudge_edges" and name in vnudge_edges.BODIES and callable(getattr(vnudge_edges, "check_" + name)), (n, guard.__name__)
+        guards.add(name)
+    assert guards == set(vnudge_edges.BODIES)                 # no body without a mutant written for it
+    assert mc.VNUDGE_MIN_SURVIVORS >= 6
+
+
+@pytest.mark.parametrize("n", sorted(mc.VNUDGE_MUTANTS))
+def test_k6_mutant_edits_apply_to_the_tree(n):
+    files = mc.patched(n, table=mc.VNUDGE_MUTANTS)      # raises when an edit's old text does not occur exactly as often as stated
+    for name, text in files.items():
+        with open(os.path.join(mc.CSRC, name)) as f:
+            assert text != f.read(), (n, name)
+
+
 def test_libraries_of_the_tables_do_not_collide():
     libs = [mc.lib_of(n, t) for t in (mc.MUTANTS, mc.ADVANCE_MUTANTS, mc.THERMO_MUTANTS, mc.GEO_MUTANTS, mc.GEO_EQUIVALENT,
-                                      mc.LESSTATE_MUTANTS, mc.LESSTATE_EQUIVALENT) for n in t]
+                                      mc.LESSTATE_MUTANTS, mc.LESSTATE_EQUIVALENT, mc.VNUDGE_MUTANTS) for n in t]
     assert len(set(libs)) == len(libs)
+    assert mc.lib_of(9, mc.VNUDGE_MUTANTS).endswith("libspc_vnudge_mutant9.so")
     assert mc.lib_of(3).endswith("libspc_mutant3.so") and mc.lib_of(2, mc.ADVANCE_MUTANTS).endswith("libspc_advance_mutant2.so")
     assert mc.lib_of(4, mc.THERMO_MUTANTS).endswith("libspc_thermo_mutant4.so")

@@ -132,7 +132,7 @@ class FieldLES:
 @pytest.mark.gpu
 @pytest.mark.parametrize("lds", ["1", "pair", "strided", "global"])
 @pytest.mark.parametrize("constantT", [False, True])
-def test_kernel_matches_the_numpy_scipy_oracle(constantT, lds, monkeypatch):
+def test_kernel_matches_the_numpy_scipy_oracle(constantT, lds):
     """K6 through the drop-in API against the oracle, every device path -- planes resident in LDS (the default where they
     fit: 512-thread workgroups; "pair": paired 256-thread workgroups as for many LES; "strided": loaded without the
     transposed workspace) and planes streamed from the workspace by one workgroup per level (the default for large planes;
@@ -141,41 +141,25 @@ def test_kernel_matches_the_numpy_scipy_oracle(constantT, lds, monkeypatch):
     90 x 90 (1), 92 x 92 (two 8192-element chunks in LDS), 96 x 96, 128 x 128, 200 x 170 (too large for the LDS): beta, a,
     the updated qt and qt_std BIT-exact, status equal; thl (constantT) within 8 ulp."""
     from sp_coupler_amd import spcpl
+    from tests import vnudge_edges
     spcpl.set_engine(None)
-    monkeypatch.setenv("SPC_VN_GLOBAL", "1" if lds == "global" else "0")        # planes streamed from the workspace at EVERY size
-    monkeypatch.setenv("SPC_VN_PAIR", "2" if lds == "pair" else "1")            # two 256-thread workgroups per CU
-    monkeypatch.setenv("SPC_VN_TRANSPOSE", "0" if lds == "strided" else "1")    # without the transposed workspace
-    shapes = [(16, 12, 40, 3), (9, 7, 23, 4), (64, 64, 160, 5), (96, 96, 12, 6), (32, 32, 24, 7), (64, 32, 21, 8), (90, 90, 12, 10),
-              (92, 92, 12, 11), (128, 128, 12, 12), (200, 170, 5, 13)]
-    # 92 x 92 = 8464 points: the LDS path with TWO chunks of numpy's 8192-element blocking; 96 x 96, 128 x 128 and 200 x 170
-    # (4 chunks + a ragged last one) do not fit the LDS: one workgroup per level streams the planes from the transposed
-    # workspace (k_vnudge_solve<true>; "global" runs EVERY shape that way); without a workspace ("strided") they are refused
-    for group in ([0, 1], [2], [3], [4], [5], [6], [7], [8], [9]):     # one launch per extent (a launch has one plane geometry)
-        if lds == "strided" and shapes[group[0]][0] * shapes[group[0]][1] > 9000:
-            continue
-        fs = [make_les_fields(*shapes[g][:3], seed=shapes[g][3]) for g in group]
-        if len(group) == 2:                             # same geometry needed inside one launch: pad the second to the first
-            fs[1] = make_les_fields(*shapes[group[0]][:3], seed=shapes[group[1]][3])
-        les = [FieldLES(f, f["ql_ref"].copy(), grid_index=i + 1) for i, f in enumerate(fs)]
-        numpy.random.seed(42)
-        got = spcpl.variability_nudge_batched(les, 900.0, constantT, write=False)
-        numpy.random.seed(42)
-        for m, f, g in zip(les, fs, got):
-            R = vo.make_R(m.itot, m.jtot)
-            r = vo.variability_nudge(f["qt"], f["qsat"], f["ql_av"], f["qt_av"], f["presf"], f["ql_ref"], R, 900.0,
-                                     constantT, thl=f["thl"], ql=f["ql"])
-            assert r["error"] is None
-            assert numpy.array_equal(g["status"], r["status"]), (g["status"], r["status"])
-            assert m.ktot < 12 or ((r["status"] & 1).any() and (r["status"] & 4).any())     # the data reach both root finders
-            assert numpy.array_equal(g["beta"], r["beta"]) and numpy.array_equal(g["a"], r["a"])
-            assert numpy.array_equal(m.fields.QT, r["qt"])
-            assert numpy.array_equal(g["qt_std"], r["qt_std"]) and numpy.array_equal(g["alpha"], r["alpha"])
-            if constantT:
-                err = numpy.abs(m.fields.THL - r["thl"]).max()
-                assert err <= 8 * 2.220446049250313e-16 * numpy.abs(r["thl"]).max(), err
-                assert not numpy.array_equal(m.fields.THL, f["thl"])
-            else:
-                assert not hasattr(m.fields, "THL")
+
+    def check(g, r, m, f):
+        assert r["error"] is None
+        assert numpy.array_equal(g["status"], r["status"]), (g["status"], r["status"])
+        assert m.ktot < 12 or ((r["status"] & 1).any() and (r["status"] & 4).any())     # the data reach both root finders
+        assert numpy.array_equal(g["beta"], r["beta"]) and numpy.array_equal(g["a"], r["a"])
+        assert numpy.array_equal(m.fields.QT, r["qt"])
+        assert numpy.array_equal(g["qt_std"], r["qt_std"]) and numpy.array_equal(g["alpha"], r["alpha"])
+        if constantT:
+            err = numpy.abs(m.fields.THL - r["thl"]).max()
+            assert err <= 8 * 2.220446049250313e-16 * numpy.abs(r["thl"]).max(), err
+            assert not numpy.array_equal(m.fields.THL, f["thl"])
+        else:
+            assert not hasattr(m.fields, "THL")
+    # the shapes, the launches and the environment of each route: tests/vnudge_edges.py (old_matrix), which the mutation control
+    # of K6 runs on its mutant libraries too
+    vnudge_edges.old_matrix(spcpl, constantT, lds, False, check)
 
 
 @pytest.mark.gpu

@@ -44,31 +44,17 @@ def _check(g, r, m, f, constantT):
 @pytest.mark.gpu
 @pytest.mark.parametrize("lds", ["1", "pair", "strided", "global"])
 @pytest.mark.parametrize("constantT", [False, True])
-def test_f32_kernel_matches_the_float32_numpy_scipy_restatement(constantT, lds, monkeypatch):
+def test_f32_kernel_matches_the_float32_numpy_scipy_restatement(constantT, lds):
     """the matrix of tests/test_vnudge.py::test_kernel_matches_the_numpy_scipy_oracle on a float32 engine: every device path
     (planes in LDS with 512- or paired 256-thread workgroups, loaded strided without the workspace, streamed from the
     workspace), the same ten plane shapes -- in float 128 x 128 is LDS-resident, 200 x 170 is not"""
     spcpl, _ = _f32_engine()
     try:
-        monkeypatch.setenv("SPC_VN_GLOBAL", "1" if lds == "global" else "0")
-        monkeypatch.setenv("SPC_VN_PAIR", "2" if lds == "pair" else "1")
-        monkeypatch.setenv("SPC_VN_TRANSPOSE", "0" if lds == "strided" else "1")
-        shapes = [(16, 12, 40, 3), (9, 7, 23, 4), (64, 64, 160, 5), (96, 96, 12, 6), (32, 32, 24, 7), (64, 32, 21, 8),
-                  (90, 90, 12, 10), (92, 92, 12, 11), (128, 128, 12, 12), (200, 170, 5, 13)]
-        for group in ([0, 1], [2], [3], [4], [5], [6], [7], [8], [9]):
-            if lds == "strided" and shapes[group[0]][0] * shapes[group[0]][1] > 18000:     # needs the workspace in float too
-                continue
-            fs = [make_les_fields(*shapes[g][:3], seed=shapes[g][3]) for g in group]
-            if len(group) == 2:
-                fs[1] = make_les_fields(*shapes[group[0]][:3], seed=shapes[group[1]][3])
-            les = [FieldLES(f, f["ql_ref"].copy(), grid_index=i + 1) for i, f in enumerate(fs)]
-            numpy.random.seed(42)
-            got = spcpl.variability_nudge_batched(les, 900.0, constantT, write=False)
-            numpy.random.seed(42)
-            for m, f, g in zip(les, fs, got):
-                r = _ref(f, vo.make_R(m.itot, m.jtot), constantT)
-                assert m.ktot < 12 or ((r["status"] & 1).any() and (r["status"] & 4).any())   # both root finders reached
-                _check(g, r, m, f, constantT)
+        def check(g, r, m, f):
+            assert m.ktot < 12 or ((r["status"] & 1).any() and (r["status"] & 4).any())   # both root finders reached
+            _check(g, r, m, f, constantT)
+        from tests import vnudge_edges
+        vnudge_edges.old_matrix(spcpl, constantT, lds, True, check)      # the shapes and launches of the float64 test
     finally:
         spcpl.set_engine(None)
 

@@ -28,6 +28,9 @@ tests/les_radiate_ref.py, which tests/test_les_radiate_gpu.py runs on the shippe
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
+VNUDGE_MUTANTS is the table of K6 (spc_vnudge.hpp, spc_vnudge2.hpp), chosen with --vnudge; its guards are the bodies of
+tests/vnudge_edges.py, which tests/test_vnudge_edges_gpu.py runs on the shipped library; its run ends with the shape matrix of
+tests/test_vnudge.py (the guard that existed before) on every mutant.
 Both runs end with the edits of *_EQUIVALENT (edits proved to change no output: expected to fail NO body) and, for K8, with
 the guards that existed before tests/geo_edges.py on the mutants the new bodies were written for; the K9 run ends with
 OLD_BODIES of tests/les_state_ref.py on mutants 12 and 13 in the same way.
@@ -43,7 +46,8 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --vadvect --build && python tools/mutation_control.py --vadvect > profiles/mutation_control_vadvect.log
        python tools/mutation_control.py --radiate --build && python tools/mutation_control.py --radiate > profiles/mutation_control_radiate.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
-       python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log"""
+       python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log
+       python tools/mutation_control.py --vnudge --build && python tools/mutation_control.py --vnudge > profiles/mutation_control_vnudge.log"""
 import argparse
 import os
 import shutil
@@ -59,6 +63,7 @@ from __graft_entry__ import HIPCC, HIP_FLAGS  # noqa: E402  (the shipped library
 CSRC = os.path.join(ROOT, "sp_coupler_amd", "csrc")
 OUT = os.path.join(ROOT, "build", "mutants")
 K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp", "spc_vnudge2.hpp", "spc_sputils.hpp"
+VN, VN_HOST = "spc_vnudge.hpp", "spc_vnudge_host.hpp"
 SLAB = "spc_slab.hpp"
 ADVANCE = "spc_advance.hpp"
 THERMO = "spc_thermo.hpp"
@@ -662,6 +667,72 @@ LESSTATE_EQUIVALENT = {
 }
 
 
+def vnudge_body(name):
+    """guard of a K6 mutant: the body ``name`` of tests/vnudge_edges.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import vnudge_edges as ve
+        failed = []
+        for dtype in ve.DTYPES:
+            failed += ve.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "vnudge_edges." + name
+    return guard
+
+
+# K6 (spc_vnudge.hpp, spc_vnudge2.hpp, spc_vnudge_host.hpp), numbered on its own.  Every mutant only computes wrong numbers:
+# none reads or writes outside what the shipped kernels touch, none loops without end.  Mutants 1-6 and 8 change a comparison
+# or a flag of lane 0's state machine; 7 turns brentq's early return into its sign error (vn_brent_next is never entered);
+# 9 stores "nothing to do" for the levels k >= 256 in the LDS cells the loop fills anyway (the loop itself is kept: with one
+# trip only those cells would hold what the LDS held before, and a stray thl bit would write through a null thl without
+# constantT); 10 makes k_vnudge_std<T, 256> walk fewer tiles (loads stay clamped to the plane); 11 skips one register add; 12
+# makes the chunk loop, uniform over the workgroup as before, leave out a last chunk of fewer than 8 points (and planes of
+# fewer than 8 points altogether): fewer trips, same barriers per trip; 13 reads the noise plane of the column before, column
+# 0 its own.  VNUDGE_OLD_GUARD: the run ends with the shape matrix of tests/test_vnudge.py::
+# test_kernel_matches_the_numpy_scipy_oracle and of its float32 copy (tests/vnudge_edges.py: old_guard) on EVERY mutant.
+# Expected to survive it: 1, 2 (random data has no ties), 3 (no ql_ref of exactly 1e-9), 7 (no f(0) == 0), 8 (ql there is
+# max(qt - qsat, 0): the correction of an untouched qt is 0), 9 (ktot <= 160), 10 (at most 20 workgroups), 12 (no chunk of
+# fewer than 8 points).  Expected to be caught by it as well: 4 (clear levels have ql_av == ql_ref == 0), 5 (saturated
+# means), 6 (a missing bracket sets beta = 5.0 exactly), 11 (the second chunk of 92 x 92 has four leaves), 13 (the launch of
+# two LES).  The log says what happened.
+VNUDGE_MUTANTS = {
+    1: ("K6 argmax, scan of a lane's segment: v >= bv (the LAST of equal maxima inside a segment)", vnudge_body("designed_levels"),
+        [(VN2, "if (v > bv || v != v) { bv = v; bi = ij; }", "if (v >= bv || v != v) { bv = v; bi = ij; }")]),
+    2: ("K6 argmax, merge over the lanes: v >= best (the last lane that holds the maximum)", vnudge_body("designed_levels"),
+        [(VN2, "if (qi >= 0 && (v > best || v != v)) { best = v; idx = qi; }", "if (qi >= 0 && (v >= best || v != v)) { best = v; idx = qi; }")]),
+    3: ("K6: ql_ref >= 1e-9 for > 1e-9 (spcpl.py:665)", vnudge_body("designed_levels"),
+        [(VN2, "if (ql_ref > 1e-9) { stage = VS_M0; touched = true; }", "if (ql_ref >= 1e-9) { stage = VS_M0; touched = true; }")]),
+    4: ("K6: ql_av >= ql_ref for > (spcpl.py:679)", vnudge_body("designed_levels"),
+        [(VN2, "else if (ql_av > ql_ref) { want_argmax = true; touched = true; }", "else if (ql_av >= ql_ref) { want_argmax = true; touched = true; }")]),
+    5: ("K6: beta < 0 -> 1 forgotten (spcpl.py:692-695)", vnudge_body("designed_levels"),
+        [(VN2, "            if (beta < 0) beta = 1.0;  ", "              ")]),
+    6: ("K6: beta > 5 for beta >= 5 (spcpl.py:703)", vnudge_body("designed_levels"),
+        [(VN2, "        if (beta >= 5.0) {", "        if (beta > 5.0) {")]),
+    7: ("K6 brentq: the early return for f(a) == 0 dropped (scipy's brentq.c checks both ends first)", vnudge_body("designed_levels"),
+        [(VN, "    if (fa == 0) { *root = xa; return 1; }\n", "")]),
+    8: ("K6 constantT: thl corrected on the levels whose qt was rewritten only, not on every level the nudge looked at (spcpl.py:726)",
+        vnudge_body("designed_levels"),
+        [(VN2, "const bool th = p.constantT && (stv & VN2_TOUCHED);", "const bool th = p.constantT && (stv & (VN2_APPLY_MULT | VN2_APPLY_ADD));")]),
+    9: ("K6 update: the staging of the per-level coefficients makes one trip, levels k >= 256 are left as they are", vnudge_body("tall"),
+        [(VN2, "        s_ap[k] = ap | (th ? 4 : 0);", "        s_ap[k] = k < 256 ? (ap | (th ? 4 : 0)) : 0;")]),
+    10: ("K6 qt.std: the tile count taken for 512 rows whatever ROWS", vnudge_body("std_many_workgroups"),
+         [(VN2, "const int ntile = (nij + ROWS - 1) / ROWS;", "const int ntile = (nij + 512 - 1) / 512;")]),
+    11: ("K6 balanced tree: the step over 2 leaves taken from 8 leaves on (nleaf > 4)", vnudge_body("small_trees"),
+         [(VN2, "if (nleaf > 2) v = v + vn_row_shl<2>(v);", "if (nleaf > 4) v = v + vn_row_shl<2>(v);")]),
+    12: ("K6 sum: a last chunk of fewer than 8 points is left out (c0 + 8 <= nij)", vnudge_body("chunk_edges"),
+         [(VN2, "for (int c0 = 0; c0 < nij; c0 += 8192) {", "for (int c0 = 0; c0 + 8 <= nij; c0 += 8192) {")]),
+    13: ("K6 solve: the noise plane of the column before (column 0 keeps its own)", vnudge_body("ragged_columns"),
+         [(VN2, "    const double *const R = p.R + col * (int64_t)nij;\n    const T qt_av",
+           "    const double *const R = p.R + (col > 0 ? col - 1 : 0) * (int64_t)nij;\n    const T qt_av")]),
+}
+
+
+def vnudge_old_guard(engine_of):
+    """the shape matrix of test_kernel_matches_the_numpy_scipy_oracle and of its float32 copy, every route, both constantT"""
+    from tests import vnudge_edges as ve
+    return ["%s %s" % ("f32" if "32" in str(dtype) else "f64", case) for dtype in ve.DTYPES for case in ve.old_guard(engine_of(dtype))]
+
+
+
 def patched(n, src=CSRC, table=None):
     """{file: text} of the files mutant n (of ``table``, default MUTANTS) changes, its edits applied to the sources under
     `src`; ValueError when an edit's old text does not occur exactly the expected number of times (the tree has drifted from
@@ -688,7 +759,7 @@ def _tag(table):
                    (RADIATE_MUTANTS, ("radiate_", "radiate")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
-                   (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq"))):
+                   (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq")), (VNUDGE_MUTANTS, ("vnudge_", "vnudge"))):
         if table is t:
             return tag
     return "", ""
@@ -811,6 +882,31 @@ def lesstate_old_guard(engine_of):
     return les_state_ref.check_everything(engine_of(torch.float64), names=les_state_ref.OLD_BODIES)
 
 
+def main_vnudge(only=None):
+    """the control of VNUDGE_MUTANTS (main_advance), then the old guard on every mutant: at least VNUDGE_MIN_SURVIVORS of them
+    must pass the old matrix -- they are what the bodies of tests/vnudge_edges.py add -- and each of those was detected by its
+    body above"""
+    bad = main_advance(only, VNUDGE_MUTANTS, "K6", module="vnudge_edges", gpu_test="test_vnudge_edges_gpu")
+    if only is not None:
+        return bad
+    print("old guard: %s, on the shipped library and on every mutant" % vnudge_old_guard.__doc__)
+    clean = run_guard(lambda engine_of: (False, vnudge_old_guard(engine_of)), None)[1]
+    print("shipped library under the old guard, failed: %s" % (clean or "none"), flush=True)
+    survivors = []
+    for n in sorted(VNUDGE_MUTANTS):
+        failed = run_guard(lambda engine_of: (False, vnudge_old_guard(engine_of)), lib_of(n, VNUDGE_MUTANTS))[1]
+        if not failed:
+            survivors.append(n)
+        print("K6 mutant %2d under the old guard: %s" % (n, "SURVIVES (caught by its new body alone)" if not failed else
+                                                         "caught already, %d of 16 cases: %s" % (len(failed), failed)), flush=True)
+    ok = len(survivors) >= VNUDGE_MIN_SURVIVORS and not clean
+    print("old guard: %d mutants survive it %s, at least %d asked for: %s" % (len(survivors), survivors, VNUDGE_MIN_SURVIVORS, "ok" if ok else "NOT ENOUGH"))
+    return 1 if bad or not ok else 0
+
+
+VNUDGE_MIN_SURVIVORS = 6
+
+
 def geo_notes():
     from tests import geo_edges
     return ["exact_tails: " + geo_edges.exact_tails_counts()]
@@ -866,11 +962,12 @@ if __name__ == "__main__":
     ap.add_argument("--radiate", action="store_true", help="the table of K18 (RADIATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--vnudge", action="store_true", help="the table of K6 (VNUDGE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
              else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else RADIATE_MUTANTS if args.radiate
              else GEO_MUTANTS if args.geo
-             else LESSTATE_MUTANTS if args.lesstate else MUTANTS)
+             else LESSTATE_MUTANTS if args.lesstate else VNUDGE_MUTANTS if args.vnudge else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
         unknown = sorted(set(args.build) - set(table))
@@ -887,6 +984,8 @@ if __name__ == "__main__":
     if args.lesstate:
         sys.exit(main_advance(only, LESSTATE_MUTANTS, "K9", module="les_state_ref", gpu_test="test_les_state_gpu",
                               equivalent=LESSTATE_EQUIVALENT, old_guards={n: lesstate_old_guard for n in LESSTATE_OLD_GUARDS}))
+    if args.vnudge:
+        sys.exit(main_vnudge(only))
     if args.thermo:
         sys.exit(main_advance(only, THERMO_MUTANTS, "K12", "les_thermo"))
     if args.waterpath:
