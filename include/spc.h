@@ -713,6 +713,47 @@ int spc_les_radiate_f32(const spc_les_radiate_args *args, void *stream);
 /* columns per workgroup of k_les_radiate for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
 int spc_les_radiate_cols_per_block(int ktot, int elem_size);
 
+/* ---- local cloud-water forcing of the device-resident LES fields: qt_forcing 'local' | 'strong' (kernel family K19) ---------- */
+/* What an LES does with the cloud-water forcing the coupler hands it (set_tendency_QL, set_ref_profile_QL: splib/spcpl.py:346-347;
+ * Dales.QT_FORCING_LOCAL / QT_FORCING_STRONG, splib/modfac.py:70-73): it moves its cloud water towards the GCM's without moving
+ * its mean moisture.  DALES's source is not part of the reference: the rule is this library's definition, shaped
+ * on what the coupler passes in and on the option's help text ("stimulate ql alignment with ... local forcing").
+ * Fields are [n_les][itot][jtot][ktot] with k contiguous and 64-bit offsets as in K10.  The element type is T.  Every operation
+ * is rounded once and nothing contracts to an fma.  N = itot * jtot.
+ * Per LES l and level k, the kernel reads a = A[l * pitch_prof + k] and m = QTM[l * pitch_prof + k].  a is the wanted change of
+ * the slab-mean cloud water in this step.
+ *   - If a is +0, -0 or NaN, the level keeps every bit of qt and count[l][k] = 0.
+ *   - If a > 0, a cell is wet when qt > m.  If a < 0, a cell is wet when ql > 0.  A NaN compares false, so such a cell is dry.
+ *   - c is the number of wet cells of the plane.  count[l][k] = c (int32, exact).
+ *   - If c == 0 or c == N, the level keeps every bit of qt.  There is nothing to redistribute.  An overcast level with too much
+ *     cloud is left to the uniform QT tendency.
+ *   - Otherwise s = a * T(N), dw = s / T(c) and dd = s / T(N - c).  These are two true IEEE quotients.  There are two divisions
+ *     per (LES, level) and none per cell.  Wet cells get qt' = qt + dw and dry cells get qt' = qt - dd, IN PLACE.
+ * ql is read only, and only on levels with a < 0.  The slab mean of qt is conserved up to rounding: moisture moves between the
+ * cloudy (or moister) cells and the rest.  Because c is an integer, the result does not depend on how the launch is cut: a plane
+ * may be counted by one workgroup or by several (spc_les_qt_local_split) and the bits are the same.
+ * SPC_ERR_INVALID_ARGUMENT: N > 2^24, which is not exact in float; pitch_prof < ktot or pitch_count < ktot; a NULL qt, a, qtm or
+ * count; a NULL ql (required: the caller does not know the signs); qt == ql; split < 0.  n_les == 0 is a no-op and ktot == 1 is
+ * allowed.  There is no upper limit on ktot: no whole column has to sit in LDS.  The levels between ktot and pitch_count of a
+ * count row are not written.                                                                                             */
+typedef struct spc_les_qt_local_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot;
+    int32_t split;                      /* workgroups that share a plane: 0 the library's choice, else forced (at most N are used) */
+    void *qt;                           /* device [n_les][itot][jtot][ktot], updated in place                */
+    const void *ql;                     /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *a, *qtm;                /* device [n_les x ktot] each, rows pitch_prof apart: A and QTM      */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+    int32_t *count;                     /* device [n_les x ktot], rows pitch_count apart, written whole      */
+    int64_t pitch_count;                /* >= ktot                                                           */
+} spc_les_qt_local_args;
+int spc_les_qt_local_f64(const spc_les_qt_local_args *args, void *stream);
+int spc_les_qt_local_f32(const spc_les_qt_local_args *args, void *stream);
+/* the split factor the library chooses for these extents (elem_size 4 or 8): 1 = one workgroup counts and updates a tile of
+ * levels of a whole plane in one launch; S > 1 = S workgroups take ceil(N / S) rows of it each, their integer counts meet in
+ * `count` and a second launch updates (few LES with large planes); 0: bad arguments */
+int spc_les_qt_local_split(int64_t n_les, int itot, int jtot, int ktot, int elem_size);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */
 const char *spc_last_error(void);   /* text of the calling thread's last failure ("" if none)     */

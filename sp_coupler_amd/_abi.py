@@ -176,6 +176,11 @@ class LesRadiateArgs(ctypes.Structure):
                 + [("inv_step", c_double)] + _ptrs("flux", "fsfc"))
 
 
+class LesQtLocalArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("split", c_int32)]
+                + _ptrs("qt", "ql", "a", "qtm") + [("pitch_prof", c_int64), ("count", c_void_p), ("pitch_count", c_int64)])
+
+
 THERMO_TABLE_LIBRARY, THERMO_TABLE_LDS, THERMO_TABLE_GLOBAL = 0, 1, 2      # spc_les_thermo_args.table_mode
 
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
@@ -237,6 +242,9 @@ PROTOTYPES = {
     "spc_les_radiate_f64": (ctypes.c_int, [ctypes.POINTER(LesRadiateArgs), c_void_p]),
     "spc_les_radiate_f32": (ctypes.c_int, [ctypes.POINTER(LesRadiateArgs), c_void_p]),
     "spc_les_radiate_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "spc_les_qt_local_f64": (ctypes.c_int, [ctypes.POINTER(LesQtLocalArgs), c_void_p]),
+    "spc_les_qt_local_f32": (ctypes.c_int, [ctypes.POINTER(LesQtLocalArgs), c_void_p]),
+    "spc_les_qt_local_split": (ctypes.c_int, [c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

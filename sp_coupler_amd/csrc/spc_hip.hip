@@ -35,6 +35,9 @@
 //   K18 k_les_radiate  the longwave flux that the liquid water of a column lets through and the THL tendency of its divergence
 //                  (two opposed running sums along k per column of two tiles in LDS, a table of exp(-x)): spc_radiate.hpp,
 //                  kernel and host side
+//   K19 k_les_qt_local  the local cloud-water forcing of QT (qt_forcing == 'local' | 'strong': the wet cells of every plane
+//                  counted, then moisture moved between them and the rest; integer counts through LDS, or through global
+//                  atomics where a plane is split over workgroups): spc_qtlocal.hpp, kernels and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -91,6 +94,7 @@ namespace {
 #include "spc_advect.hpp"
 #include "spc_vadvect.hpp"
 #include "spc_radiate.hpp"
+#include "spc_qtlocal.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -125,6 +129,9 @@ namespace {
 #define SPC_RADIATE_HOST
 #include "spc_radiate.hpp"
 #undef SPC_RADIATE_HOST
+#define SPC_QTLOCAL_HOST
+#include "spc_qtlocal.hpp"
+#undef SPC_QTLOCAL_HOST
 
 }  // namespace
 
@@ -217,6 +224,10 @@ int spc_les_vadvect_cols_per_block(int ktot, int elem_size) { return vad_cols(kt
 int spc_les_radiate_f64(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<double>(a, s); }
 int spc_les_radiate_f32(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<float>(a, s); }
 int spc_les_radiate_cols_per_block(int ktot, int elem_size) { return rad_cols(ktot, elem_size); }
+
+int spc_les_qt_local_f64(const spc_les_qt_local_args *a, void *s) { return les_qt_local_impl<double>(a, s); }
+int spc_les_qt_local_f32(const spc_les_qt_local_args *a, void *s) { return les_qt_local_impl<float>(a, s); }
+int spc_les_qt_local_split(int64_t n_les, int itot, int jtot, int ktot, int elem_size) { return qtl_split(n_les, itot, jtot, ktot, elem_size); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

@@ -120,7 +120,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     ``Engine.les_vadvect``) and ``get_vertical_wind_batched()`` returns W; tests/les_vadvect_ref.py holds that twin.
     After ``enable_radiation()`` every step cools THL at the top of the cloud water and warms it at its base (K18,
     ``Engine.les_radiate``) and ``get_radiative_flux_batched()`` returns the longwave flux; tests/les_radiate_ref.py holds the
-    twin of that mode."""
+    twin of that mode.
+    After ``enable_qt_forcing(kind)`` every step moves QT between the wet and the dry cells of every plane by the cloud-water
+    forcing the coupler handed over (K19, ``Engine.les_qt_local``: qt_forcing 'local' | 'strong'); tests/les_qt_local_ref.py
+    holds the twin of that mode."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
@@ -478,6 +481,55 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         enable_radiation()"""
         return self._radiate_flux if self.radiation else None
 
+    # -- local cloud-water forcing of QT (K19: qt_forcing 'local' | 'strong'), opt-in -------------------------------------------
+    qt_forcing_kind = None                             # enable_qt_forcing(): "local" or "strong"
+    _qt_counts = None                                  # device int32 [n x nL]: the wet cells per plane of the last K19 launch
+
+    def enable_qt_forcing(self, kind):
+        """from now on every ``evolve_model_batched`` runs ONE K19 launch per device (``Engine.les_qt_local``)
+        directly after the step and before K16 / K17 / K15 / K18 / K14 / K12 (the forcings first, then the physics): per level
+        the QT field takes ``qt_forcing.increments(kind, ...)`` -- ``"local"``: the cloud-water forcing ``set_tendency_QL`` /
+        ``QL`` handed over times dt, ``"strong"``: the profile of ``set_ref_profile_QL`` / ``QLp`` minus the slab mean of QL --
+        times N / c in its wet cells and gives it back in the dry ones, so the cloud water moves towards the GCM's and the slab
+        mean of QT does not.  QTM is the slab mean of the stepped QT (the cached means, else one K10 launch).  Needs a QT field
+        and cloud water that follows it: a Qsat field or ``enable_thermo()`` (ValueError otherwise).  No launch before the
+        forcing the kind reads was handed over.  ``get_qt_forcing_counts_batched()`` returns the wet cells per plane.  Calling
+        it again with the same kind changes nothing.  Without this call every path of the ensemble is unchanged."""
+        from . import qt_forcing
+        if kind not in qt_forcing.KINDS:
+            raise ValueError("the local QT forcing (K19) is one of %s, got %r" % (qt_forcing.KINDS, kind))
+        if "QT" not in self.fields3d:
+            raise ValueError("the local QT forcing (K19) needs a QT field (set_fields_batched)")
+        if not (self.thermo or "Qsat" in self.fields3d):
+            raise ValueError("the local QT forcing (K19) needs the cloud water of the current QT: a Qsat field, or enable_thermo()")
+        if not self._has("les_qt_local"):
+            raise ValueError("the engine has no les_qt_local (K19)")
+        if kind != self.qt_forcing_kind:
+            self.qt_forcing_kind, self._qt_counts = kind, None
+
+    def _qt_local(self, dt):
+        """K19 on the stepped QT with the QL and the slab means of the stepped fields; QL and the profiles then follow the new
+        QT, here or in the stages behind it"""
+        from . import qt_forcing
+        eng, f, p, kind = self._eng(), self.fields3d, self.p, self.qt_forcing_kind
+        if self.n == 0 or {"local": "QL", "strong": "QL_ref"}[kind] not in self.tend:
+            return
+        if "QT" not in f or not (self.thermo or "Qsat" in f):
+            raise ValueError("the local QT forcing (K19) needs a QT field and a Qsat field or enable_thermo()")
+        self._ensure_ql()                                 # (thermo: K12 where stale)
+        means = self._slab_means()                        # cached by the step (K11, or K10 behind the torch path), else one K10 launch
+        a = qt_forcing.increments(kind, self.tend.get("QL"), self.tend.get("QL_ref"), p["QL"], dt)
+        self._qt_counts = eng.les_qt_local(f["QT"], f["QL"], self._upload(a), self._upload(means["QT"]), count=self._qt_counts)
+        self._drop_water_paths()
+        self._thermo_stale, self._means = True, None      # thermo: K12 runs on the new QT before its next use
+        if not (self.advection or self.diffusion):        # (else the QL field and the means follow the advected / diffused fields)
+            self._follow_fields()
+
+    def get_qt_forcing_counts_batched(self):
+        """the device int32 tensor [n x nL] (Sharded row blocks under a MultiDeviceEngine) of the wet cells per plane that the
+        last step's K19 launch counted (0 on levels it left alone); None before the first such launch"""
+        return self._qt_counts if self.qt_forcing_kind else None
+
     def _saturate(self):
         """the QL field = max(QT - Qsat, 0), in place: two torch operations on each device's stream"""
         def saturate(ql, qt, qs):
@@ -747,10 +799,14 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                         return field.add_(inc[:, None, None, :])
                     self._per_device(step, f[key], self._upload(self.tend[key]))
             self._thermo_stale = True
-            if not (self.diffusion or self.advection):    # (else the QL field and the means follow the diffused / advected fields)
+            # (with diffusion or advection the QL field and the means follow the diffused / advected fields; K19 reads those of
+            # the stepped fields)
+            if not (self.diffusion or self.advection) or self.qt_forcing_kind:
                 self._follow_fields()                     # p[U, V, THL, QT, QL] = the slab means of the new fields
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
+        if self.qt_forcing_kind:
+            self._qt_local(dt)                            # one K19 launch: QT moved between the wet and the dry cells of every plane; p[...]
         if self.advection:
             self._advect(dt)                              # 1 + n_sub K16 launches: U, V, THL, QT, QR carried along i and j; p[...]
                                                           # (vertical: a K17 probe and a K17 launch behind every K16 substep)

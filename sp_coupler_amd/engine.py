@@ -1047,6 +1047,41 @@ class Engine:
         """columns of ``ktot`` levels a workgroup of K18 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
         return int(self.lib.spc_les_radiate_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
 
+    # -- K19: the local cloud-water forcing of device-resident LES moisture (qt_forcing 'local' | 'strong') ------------------------
+    @_on_engine_stream
+    def les_qt_local(self, qt, ql, a, qtm, *, count=None, split=0, stream=None):
+        """The local cloud-water forcing (include/spc.h has the rule) on contiguous device fields [n x itot x jtot x ktot]:
+        per LES and level the wet cells of the plane are counted (``qt > qtm`` where ``a > 0``, ``ql > 0`` where ``a < 0``) and
+        ``qt`` takes ``a * N / c`` in its wet cells and gives ``a * N / (N - c)`` in its dry ones IN PLACE; levels with a zero
+        or NaN ``a``, with no wet cell or with none dry keep their bits.  ``ql`` is read only.  ``a`` and ``qtm`` [n x ktot] are
+        ``qt_forcing.increments`` and the slab means of ``qt`` in the engine's dtype (rows may be pitched, both with one pitch).
+        Returns the int32 [n x ktot] counts (``count``: a tensor to write them into, rows may be pitched).  ``split``: 0 lets
+        the library choose how many workgroups share a plane (``qt_local_split``), another value forces it; the bits do not
+        depend on it.  ``qt`` STARTING where ``ql`` starts is refused (ValueError)."""
+        shape = tuple(self._field4("qt", qt).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_qt_local: empty field shape %s" % (shape,))
+        if int(split) < 0:
+            raise ValueError("les_qt_local: split must be >= 0, got %r" % (split,))
+        ck = _Checker(self.device, self.dtype)
+        args = _abi.LesQtLocalArgs()
+        args.n_les, args.itot, args.jtot, args.ktot, args.split = n, itot, jtot, ktot, int(split)
+        args.qt, args.ql = qt.data_ptr(), self._field4("ql", ql, shape).data_ptr()
+        args.a, args.pitch_prof = ck.mat("a", a, n, ktot)
+        args.qtm, _ = ck.mat("qtm", qtm, n, ktot, pitch=args.pitch_prof)
+        out, args.pitch_count = self._out(count, n, ktot, dtype=torch.int32)
+        args.count = out.data_ptr()
+        if n and qt.data_ptr() == ql.data_ptr():
+            raise ValueError("les_qt_local: qt and ql are the same tensor")
+        fn = self.lib.spc_les_qt_local_f32 if self.dtype == torch.float32 else self.lib.spc_les_qt_local_f64
+        self._call(fn, ctypes.byref(args), stream=stream)
+        return out
+
+    def qt_local_split(self, n, itot, jtot, ktot):
+        """workgroups that share a plane of K19 for these extents in the engine's dtype, as the library chooses; 0: bad extents"""
+        return int(self.lib.spc_les_qt_local_split(int(n), int(itot), int(jtot), int(ktot), 4 if self.dtype == torch.float32 else 8))
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

@@ -286,6 +286,12 @@ class MultiDeviceEngine:
             return self.primary.les_radiate(ql, thl, w, c, f0, f1, flux=flux, fsfc=fsfc, **kw)
         self._each("les_radiate", ex, (ql, thl, w, c, f0, f1), dict(kw, flux=flux, fsfc=fsfc))
 
+    def les_qt_local(self, qt, ql, a, qtm, *, count=None, split=0, **kw):
+        """K19 on every device's LES: the Sharded fields ``qt`` (updated in place, block by block) and ``ql``, the Sharded
+        profiles ``a`` and ``qtm`` [n x ktot] and ``count`` (or None) in, the Sharded int32 [n x ktot] counts out; one launch per
+        device that holds rows, none on the others"""
+        return self._run("les_qt_local", qt, ql, a, qtm, count=count, split=split, **kw)
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

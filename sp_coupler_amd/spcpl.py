@@ -763,6 +763,8 @@ def _ensemble_forcings(ens, firststep, profiles, dt_gcm, factor, couple_surface,
     if qt_forcing == 'variance' and not hasattr(ens, "get_fields_batched"):
         raise NotImplementedError("qt_forcing='variance' needs the 3-D LES fields: an ensemble must offer get_fields_batched / "
                                   "set_fields_batched (sp_coupler_amd.models docstring), or pass the LES objects as a plain list")
+    if qt_forcing in ('local', 'strong') and hasattr(ens, "enable_qt_forcing"):
+        ens.enable_qt_forcing(qt_forcing)       # K19 in the ensemble's own step, as DALES does it (splib/modfac.py:70-73); idempotent
     if firststep:                                                            # spcpl.py:302-308, 321
         if b.piecewise:
             for k in _FWD_KEYS:                 # variable by variable: each is on the wire while the next is fetched

@@ -25,6 +25,8 @@ VADVECT_MUTANTS is the table of K17 (spc_vadvect.hpp), chosen with --vadvect; it
 tests/les_vadvect_ref.py, which tests/test_les_vadvect_gpu.py runs on the shipped library.
 RADIATE_MUTANTS is the table of K18 (spc_radiate.hpp), chosen with --radiate; its guards are the bodies of
 tests/les_radiate_ref.py, which tests/test_les_radiate_gpu.py runs on the shipped library.
+QTLOCAL_MUTANTS is the table of K19 (spc_qtlocal.hpp), chosen with --qtlocal; its guards are the bodies of
+tests/les_qt_local_ref.py, which tests/test_les_qt_local_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
@@ -45,6 +47,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --advect --build && python tools/mutation_control.py --advect > profiles/mutation_control_advect.log
        python tools/mutation_control.py --vadvect --build && python tools/mutation_control.py --vadvect > profiles/mutation_control_vadvect.log
        python tools/mutation_control.py --radiate --build && python tools/mutation_control.py --radiate > profiles/mutation_control_radiate.log
+       python tools/mutation_control.py --qtlocal --build && python tools/mutation_control.py --qtlocal > profiles/mutation_control_qtlocal.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log
        python tools/mutation_control.py --vnudge --build && python tools/mutation_control.py --vnudge > profiles/mutation_control_vnudge.log"""
@@ -73,6 +76,7 @@ DIFFUSE = "spc_diffuse.hpp"
 ADVECT = "spc_advect.hpp"
 VADVECT = "spc_vadvect.hpp"
 RADIATE = "spc_radiate.hpp"
+QTLOCAL = "spc_qtlocal.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -667,6 +671,45 @@ LESSTATE_EQUIVALENT = {
 }
 
 
+def qtlocal_body(name):
+    """guard of a K19 mutant: the body ``name`` of tests/les_qt_local_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_qt_local_ref as qlr
+        failed = []
+        for dtype in qlr.DTYPES:
+            failed += qlr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_qt_local_ref." + name
+    return guard
+
+
+# K19 (spc_qtlocal.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernels touch and none can hang (mutant 2 reads ql, a field of the shape of qt, on the levels where the shipped kernel
+# reads qt; mutant 5 divides by T(0) for the dry share of a level that has no dry cell and never adds it; mutant 6 reads row 0 of
+# the two profiles; mutant 7 leaves the counts of the other parts out of the sum, the zeroed words stay zeroed).
+QTLOCAL_MUTANTS = {
+    1: ("K19 a > 0: qt >= m for qt > m, in both walks (a cell ON the mean is wet)", qtlocal_body("ties"),
+        [(QTLOCAL, "mode[v] == 1 ? x[u].v[v] > m[v]", "mode[v] == 1 ? x[u].v[v] >= m[v]"),
+         (QTLOCAL, "mode[v] == 1 ? t > m[v]", "mode[v] == 1 ? t >= m[v]")]),
+    2: ("K19 a > 0: the predicate of a < 0 (the cloudy cells, not the cells above the mean)", qtlocal_body("parity"),
+        [(QTLOCAL, "mode[v] = a[v] > (T)0 ? 1 :", "mode[v] = a[v] > (T)0 ? 2 :")]),
+    3: ("K19 shares: N - c and c swapped (the wet cells share what the dry ones should)", qtlocal_body("parity"),
+        [(QTLOCAL, "dw[v] = s / (T)c[v];", "dw[v] = s / (T)(N - c[v]);"),
+         (QTLOCAL, "dd[v] = s / (T)(N - c[v]);", "dd[v] = s / (T)c[v];")]),
+    4: ("K19 shares: s / c replaced by s * (1 / c)", qtlocal_body("parity"),
+        [(QTLOCAL, "dw[v] = s / (T)c[v];", "dw[v] = s * ((T)1 / (T)c[v]);")]),
+    5: ("K19: a level without a dry cell is not skipped (c == N takes a whole)", qtlocal_body("parity"),
+        [(QTLOCAL, "c[v] > 0 && c[v] < N;", "c[v] > 0 && c[v] <= N;")]),
+    6: ("K19 l: the profile rows of LES 0 for every LES", qtlocal_body("rows"),
+        [(QTLOCAL, "a[v] = p.A[l * p.pitch_prof + k0 + v];", "a[v] = p.A[k0 + v];"),
+         (QTLOCAL, "m[v] = p.QTM[l * p.pitch_prof + k0 + v];", "m[v] = p.QTM[k0 + v];")]),
+    7: ("K19 split: only the first workgroup's part of a plane's count arrives", qtlocal_body("shapes"),
+        [(QTLOCAL, "else if (c[v])", "else if (c[v] && part == 0)")]),
+    8: ("K19: a dry cell is given + dd", qtlocal_body("parity"),
+        [(QTLOCAL, "dn = t - dd[v];", "dn = t + dd[v];")]),
+}
+
+
 def vnudge_body(name):
     """guard of a K6 mutant: the body ``name`` of tests/vnudge_edges.py on both engines (float64, float32) of the library"""
     def guard(engine_of):
@@ -756,7 +799,7 @@ def _tag(table):
     for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
                    (MICRO_MUTANTS, ("micro_", "micro")), (DIFFUSE_MUTANTS, ("diffuse_", "diffuse")),
                    (ADVECT_MUTANTS, ("advect_", "advect")), (VADVECT_MUTANTS, ("vadvect_", "vadvect")),
-                   (RADIATE_MUTANTS, ("radiate_", "radiate")),
+                   (RADIATE_MUTANTS, ("radiate_", "radiate")), (QTLOCAL_MUTANTS, ("qtlocal_", "qtlocal")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq")), (VNUDGE_MUTANTS, ("vnudge_", "vnudge"))):
@@ -960,13 +1003,14 @@ if __name__ == "__main__":
     ap.add_argument("--advect", action="store_true", help="the table of K16 (ADVECT_MUTANTS) instead of MUTANTS")
     ap.add_argument("--vadvect", action="store_true", help="the table of K17 (VADVECT_MUTANTS) instead of MUTANTS")
     ap.add_argument("--radiate", action="store_true", help="the table of K18 (RADIATE_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--qtlocal", action="store_true", help="the table of K19 (QTLOCAL_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--vnudge", action="store_true", help="the table of K6 (VNUDGE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
              else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else RADIATE_MUTANTS if args.radiate
-             else GEO_MUTANTS if args.geo
+             else QTLOCAL_MUTANTS if args.qtlocal else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else VNUDGE_MUTANTS if args.vnudge else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -1000,4 +1044,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, VADVECT_MUTANTS, "K17", "les_vadvect"))
     if args.radiate:
         sys.exit(main_advance(only, RADIATE_MUTANTS, "K18", "les_radiate"))
+    if args.qtlocal:
+        sys.exit(main_advance(only, QTLOCAL_MUTANTS, "K19", "les_qt_local"))
     sys.exit((main_advance if args.advance else main)(only))
