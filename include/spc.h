@@ -754,6 +754,51 @@ int spc_les_qt_local_f32(const spc_les_qt_local_args *args, void *stream);
  * `count` and a second launch updates (few LES with large planes); 0: bad arguments */
 int spc_les_qt_local_split(int64_t n_les, int itot, int jtot, int ktot, int elem_size);
 
+/* ---- second moments of the device-resident LES fields: variances, covariances, resolved fluxes (kernel family K20) ----------- */
+/* Per LES and level: the mean, the variance and the standard deviation of every field of a set and the covariance of pairs of
+ * them, in ONE launch, with the bits of the NumPy statements below.
+ * Inputs and outputs:
+ *   - Fields x_f, f < n_fields, 1 <= n_fields <= SPC_MOMENTS_MAX_FIELDS.  Each is [n_les][itot][jtot][ktot] in C order, ktot
+ *     contiguous, 64-bit offsets as in K10, element type T of the entry point, read only.
+ *   - Pairs (a_p, b_p) = (pair_a[p], pair_b[p]), p < n_pairs, 0 <= n_pairs <= SPC_MOMENTS_MAX_PAIRS.  They are indices into the
+ *     fields with a_p != b_p.  A field may appear in several pairs, and (a, b) and (b, a) may both be asked for.
+ *   - face_field is -1 or the index of one field given at the UPPER faces of the cells (K17's W).  That field is first brought
+ *     to the cell centres: xc[k] = T(0.5) * (x[k - 1] + x[k]) with x[-1] := +0.0 (the closed ground; nothing in front of a row
+ *     is read).  One add and one multiply, each rounded once.  Every output of that field, its mean included, is of xc.
+ *   - Per LES l and level k, N = itot * jtot, rows r = (i, j) in row-major order:
+ *       m_f    = (sum over r, sequential from +0.0, of x_f[r]) / T(N), which is K10's rule.
+ *       d_f[r] = x_f[r] - m_f.
+ *       var_f  = (sum over r, sequential from +0.0, of (d_f[r] * d_f[r])) / T(N).  The product is rounded on its own, never an
+ *                fma.
+ *       std_f  = sqrt(var_f), IEEE correctly rounded.
+ *       cov_p  = (sum over r, sequential from +0.0, of (d_a[r] * d_b[r])) / T(N).
+ *   - The outputs are mean[f], var[f], std[f] and cov[p].  Each is [n_les x ktot] with one common row pitch pitch_out >= ktot,
+ *     and each is optional (NULL means not asked).  At least one must be non-NULL.
+ *   - Levels between ktot and pitch_out are not written.
+ *   - NaN and infinities follow IEEE.  A NaN cell makes that level's outputs of the fields it touches NaN and no other level's
+ *     (a face field: the level above it too).  A plane of -0.0 has mean +0.0.
+ * These equal, bit for bit in f64 and f32, x.mean(axis=(0, 1)), x.var(axis=(0, 1)), x.std(axis=(0, 1)) and
+ * ((x - x.mean(axis=(0, 1))) * (y - y.mean(axis=(0, 1)))).mean(axis=(0, 1)) of NumPy for ktot > 1.
+ * Refusals:
+ *   - ktot == 1 is SPC_ERR_UNSUPPORTED, as in spc_les_advance_*, because NumPy reduces a one-level plane pairwise.
+ *   - SPC_ERR_INVALID_ARGUMENT for N > 2^24; a pitch below ktot; a NULL field; no output asked for; a pair index out of range
+ *     or a_p == b_p; face_field >= n_fields; an output pointer EQUAL to a field or to another output.
+ *   - n_les == 0 is a no-op.                                                                                                  */
+#define SPC_MOMENTS_MAX_FIELDS 8
+#define SPC_MOMENTS_MAX_PAIRS 8
+typedef struct spc_les_moments_args {
+    int64_t n_les;                                  /* 0 is allowed: no-op                                              */
+    int32_t itot, jtot, ktot;
+    int32_t n_fields, n_pairs, face_field;
+    const void *fields[SPC_MOMENTS_MAX_FIELDS];     /* device [n_les][itot][jtot][ktot] each                            */
+    int32_t pair_a[SPC_MOMENTS_MAX_PAIRS], pair_b[SPC_MOMENTS_MAX_PAIRS];
+    void *mean[SPC_MOMENTS_MAX_FIELDS], *var[SPC_MOMENTS_MAX_FIELDS], *std[SPC_MOMENTS_MAX_FIELDS];
+    void *cov[SPC_MOMENTS_MAX_PAIRS];               /* device [n_les x ktot] each, rows pitch_out apart, or NULL        */
+    int64_t pitch_out;                              /* >= ktot                                                          */
+} spc_les_moments_args;
+int spc_les_moments_f64(const spc_les_moments_args *args, void *stream);
+int spc_les_moments_f32(const spc_les_moments_args *args, void *stream);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */
 const char *spc_last_error(void);   /* text of the calling thread's last failure ("" if none)     */

@@ -181,6 +181,18 @@ class LesQtLocalArgs(ctypes.Structure):
                 + _ptrs("qt", "ql", "a", "qtm") + [("pitch_prof", c_int64), ("count", c_void_p), ("pitch_count", c_int64)])
 
 
+MOMENTS_MAX_FIELDS, MOMENTS_MAX_PAIRS = 8, 8               # SPC_MOMENTS_MAX_FIELDS, SPC_MOMENTS_MAX_PAIRS
+
+
+class LesMomentsArgs(ctypes.Structure):
+    _fields_ = [("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32),
+                ("n_fields", c_int32), ("n_pairs", c_int32), ("face_field", c_int32),
+                ("fields", c_void_p * MOMENTS_MAX_FIELDS),
+                ("pair_a", c_int32 * MOMENTS_MAX_PAIRS), ("pair_b", c_int32 * MOMENTS_MAX_PAIRS),
+                ("mean", c_void_p * MOMENTS_MAX_FIELDS), ("var", c_void_p * MOMENTS_MAX_FIELDS), ("std", c_void_p * MOMENTS_MAX_FIELDS),
+                ("cov", c_void_p * MOMENTS_MAX_PAIRS), ("pitch_out", c_int64)]
+
+
 THERMO_TABLE_LIBRARY, THERMO_TABLE_LDS, THERMO_TABLE_GLOBAL = 0, 1, 2      # spc_les_thermo_args.table_mode
 
 SPC_RING_SHELL, SPC_RING_HOLE, SPC_RING_RECTANGLE = 0, 1, 2
@@ -245,6 +257,8 @@ PROTOTYPES = {
     "spc_les_qt_local_f64": (ctypes.c_int, [ctypes.POINTER(LesQtLocalArgs), c_void_p]),
     "spc_les_qt_local_f32": (ctypes.c_int, [ctypes.POINTER(LesQtLocalArgs), c_void_p]),
     "spc_les_qt_local_split": (ctypes.c_int, [c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "spc_les_moments_f64": (ctypes.c_int, [ctypes.POINTER(LesMomentsArgs), c_void_p]),
+    "spc_les_moments_f32": (ctypes.c_int, [ctypes.POINTER(LesMomentsArgs), c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

@@ -38,6 +38,9 @@
 //   K19 k_les_qt_local  the local cloud-water forcing of QT (qt_forcing == 'local' | 'strong': the wet cells of every plane
 //                  counted, then moisture moved between them and the rest; integer counts through LDS, or through global
 //                  atomics where a plane is split over workgroups): spc_qtlocal.hpp, kernels and host side
+//   K20 k_les_moments  the second moments of those fields per (LES, level): means, variances, standard deviations and the
+//                  covariances of pairs of fields (the resolved fluxes, W brought from the faces to the centres), NumPy's
+//                  sequential order, one job per field or pair in one launch: spc_moments.hpp, kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -95,6 +98,7 @@ namespace {
 #include "spc_vadvect.hpp"
 #include "spc_radiate.hpp"
 #include "spc_qtlocal.hpp"
+#include "spc_moments.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -132,6 +136,9 @@ namespace {
 #define SPC_QTLOCAL_HOST
 #include "spc_qtlocal.hpp"
 #undef SPC_QTLOCAL_HOST
+#define SPC_MOMENTS_HOST
+#include "spc_moments.hpp"
+#undef SPC_MOMENTS_HOST
 
 }  // namespace
 
@@ -228,6 +235,9 @@ int spc_les_radiate_cols_per_block(int ktot, int elem_size) { return rad_cols(kt
 int spc_les_qt_local_f64(const spc_les_qt_local_args *a, void *s) { return les_qt_local_impl<double>(a, s); }
 int spc_les_qt_local_f32(const spc_les_qt_local_args *a, void *s) { return les_qt_local_impl<float>(a, s); }
 int spc_les_qt_local_split(int64_t n_les, int itot, int jtot, int ktot, int elem_size) { return qtl_split(n_les, itot, jtot, ktot, elem_size); }
+
+int spc_les_moments_f64(const spc_les_moments_args *a, void *s) { return les_moments_impl<double>(a, s); }
+int spc_les_moments_f32(const spc_les_moments_args *a, void *s) { return les_moments_impl<float>(a, s); }
 
 int spc_abi_version(void) { return SPC_ABI_VERSION; }
 const char *spc_last_error(void) { return g_err; }

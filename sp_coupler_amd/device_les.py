@@ -80,6 +80,12 @@ class _DeviceLESRow(_LESRow):
                                       "stay on the GPU: get_fields_batched")
         return self._e._water_path_host(name)[self._i].copy()
 
+    def get_statistics(self, names=None, pairs=None):
+        """this LES's rows of the ensemble's ``get_statistics``: ``{"mean": {name: [nL]}, "var": ..., "std": ..., "cov": {(a, b):
+        [nL]}, "TKE": [nL]}``, host float64"""
+        host = self._e.get_statistics(names, pairs)
+        return {kind: (v[self._i].copy() if kind == "TKE" else {k: a[self._i].copy() for k, a in v.items()}) for kind, v in host.items()}
+
 
 def _device_row_getter(key):
     """the row getter of a DeviceLESEnsemble: row i of what ``get_profiles_batched((key,))`` returns at that moment.  The 3-D
@@ -123,7 +129,9 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     twin of that mode.
     After ``enable_qt_forcing(kind)`` every step moves QT between the wet and the dry cells of every plane by the cloud-water
     forcing the coupler handed over (K19, ``Engine.les_qt_local``: qt_forcing 'local' | 'strong'); tests/les_qt_local_ref.py
-    holds the twin of that mode."""
+    holds the twin of that mode.
+    ``get_statistics_batched`` reduces the fields to their second moments per level (K20, ``Engine.les_moments``): means,
+    variances, standard deviations and the covariances of ``statistics.PAIRS``; tests/les_moments_ref.py holds their twin."""
 
     fields_on_device = True
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")          # profiles that ARE slab means, where the field exists
@@ -139,6 +147,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.fields3d = {}
         self._means = None                              # host slab means of the fields as they are now, or None
         self._wp, self._wp_host, self._wp_w = None, {}, None      # K13's results of the fields as they are now; its weights
+        self._stats, self._stats_host = None, {}        # K20's results of the fields as they are now
 
     # -- saturation adjustment (K12), opt-in -------------------------------------------------------------------------
     thermo = False                                     # enable_thermo(): Qsat and QL follow THL, QT and presf
@@ -176,6 +185,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self._thermo_means = self._to_host(dev)
         self.p.update(self._thermo_means)
         self._drop_water_paths()                        # QL is new
+        self._drop_statistics()
         if self._means is not None:
             self._means["QL"] = self._thermo_means["QL"]
         self._thermo_stale = False
@@ -213,6 +223,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.micro, self._micro_prof = True, None
         self._thermo_stale = True                         # (K12's next launch also writes the cells' temperature)
         self._drop_water_paths()
+        self._drop_statistics()
 
     def _microphysics(self, dt):
         """K14 on the stepped fields: QT, THL, QR, rain2d and their profiles; QL (and Qsat) are then those of the new QT and THL"""
@@ -242,6 +253,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if self._means is not None:
             self._means.update(own)
         self._drop_water_paths()
+        self._drop_statistics()
         self._thermo_stale = True                         # thermo: the tail of the step runs K12 on the new QT and THL
         if not self.thermo and "Qsat" in f:
             self._saturate()
@@ -401,6 +413,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             self._vadvect_dt = float(dt) / n_sub
             self.advect_courant_z = self._device_max(worst_z)
         self._drop_water_paths()
+        self._drop_statistics()
         self._thermo_stale = True                         # thermo: K12 runs on the advected THL and QT before their next use
         if not self.diffusion:                            # (else the QL field and the means follow the diffused fields: _diffuse)
             self._follow_fields()
@@ -521,6 +534,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         a = qt_forcing.increments(kind, self.tend.get("QL"), self.tend.get("QL_ref"), p["QL"], dt)
         self._qt_counts = eng.les_qt_local(f["QT"], f["QL"], self._upload(a), self._upload(means["QT"]), count=self._qt_counts)
         self._drop_water_paths()
+        self._drop_statistics()
         self._thermo_stale, self._means = True, None      # thermo: K12 runs on the new QT before its next use
         if not (self.advection or self.diffusion):        # (else the QL field and the means follow the advected / diffused fields)
             self._follow_fields()
@@ -541,6 +555,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         """QL = max(QT - Qsat, 0) of the QT field as it is now (without thermo) and p[U, V, THL, QT, QL] = K10's means"""
         f = self.fields3d
         self._drop_water_paths()
+        self._drop_statistics()
         self._thermo_stale = True                         # thermo: K12 runs on the new THL and QT before their next use
         if not self.thermo and ("QL" in f or ("QT" in f and "Qsat" in f)):
             self._ensure_ql()
@@ -638,6 +653,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.fields3d[name] = values
         self._means = None
         self._drop_water_paths()
+        self._drop_statistics()
         self._thermo_stale = True                       # (K12 writes Qsat and QL in place, not through here)
 
     def set_field_row(self, i, name, values):
@@ -665,6 +681,86 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                 self._means["QL"] = self._thermo_means["QL"]
             self.p.update(self._means)
         return self._means
+
+    # -- second moments per level (K20) ---------------------------------------------------------------------------------------
+    _stats_w = None                                    # (W,) of the fields as they are now: the tensor handed to K20, or None
+
+    def _drop_statistics(self):
+        self._stats, self._stats_host, self._stats_w = None, {}, None
+
+    def _statistics_fields(self):
+        """name -> device field of every field of ``statistics.FIELDS`` the ensemble holds now (QL after K12 where thermo is
+        enabled and stale; W from the last step of enable_advection(vertical=True))"""
+        from . import statistics as st
+        f = self.fields3d
+        if self.thermo or "QL" in f or ("QT" in f and "Qsat" in f):
+            self._ensure_ql()
+        have = {}
+        for k in st.FIELDS:
+            if k == st.FACE:
+                if self._stats_w is None:
+                    self._stats_w = (self.get_vertical_wind_batched(),)
+                if self._stats_w[0] is not None:
+                    have[k] = self._stats_w[0]
+            elif k in f:
+                have[k] = f[k]
+        return have
+
+    def get_statistics_batched(self, names=None, pairs=None):
+        """``{"mean": {name: t}, "var": {...}, "std": {...}, "cov": {(a, b): t}}`` of device tensors [n x nL] (Sharded row blocks
+        under a MultiDeviceEngine): per LES and level the mean, the variance and the standard deviation over the plane of the
+        fields ``names`` (default: those of ``statistics.FIELDS`` the ensemble holds; W is ``get_vertical_wind_batched()``
+        brought to the cell centres) and the covariances of ``pairs`` (default: those of ``statistics.PAIRS`` whose two fields
+        are present), by NumPy's rule bit for bit (include/spc.h).  A name or a pair whose field the ensemble does not hold is
+        left out; KeyError where no name is left.  What is not cached goes through ONE launch per device; the results are
+        cached until a field changes."""
+        from . import statistics as st
+        if not self._has("les_moments"):
+            raise ValueError("the engine has no les_moments (K20)")
+        names = list(st.FIELDS if names is None else names)
+        unknown = [k for k in names if k not in st.FIELDS]
+        if unknown:
+            raise KeyError("no statistics of %s (there are %s)" % (unknown, list(st.FIELDS)))
+        fields = self._statistics_fields()                # (K12 where stale: it drops what is cached)
+        if self._stats is None:
+            self._stats = {"mean": {}, "var": {}, "std": {}, "cov": {}}
+        have = [k for k in names if k in fields]
+        if not have:
+            raise KeyError("the ensemble holds no field for %s" % (names,))
+        pairs = [tuple(p) for p in (st.PAIRS if pairs is None else pairs)]
+        pairs = [p for p in pairs if p[0] in fields and p[1] in fields]
+        cache = self._stats
+        need_pairs = [p for p in pairs if p not in cache["cov"]]
+        need = [k for k in have if k not in cache["mean"]]
+        need += [k for p in need_pairs for k in p if k not in need and k not in cache["mean"]]
+        launch = need + [k for p in need_pairs for k in p if k not in need]
+        if launch:
+            launch = [k for k in st.FIELDS if k in launch]              # one order whatever was asked for
+            todo = bool(need)
+            res = self._eng().les_moments({k: fields[k] for k in launch}, need_pairs, mean=todo, var=todo, std=todo,
+                                          face=st.FACE if st.FACE in launch else None)
+            for kind, d in res.items():                               # (a cached field that only a new pair needed keeps its tensors)
+                for key, t in d.items():
+                    cache[kind].setdefault(key, t)
+        return {"mean": {k: cache["mean"][k] for k in have}, "var": {k: cache["var"][k] for k in have},
+                "std": {k: cache["std"][k] for k in have}, "cov": {p: cache["cov"][p] for p in pairs}}
+
+    def get_statistics(self, names=None, pairs=None):
+        """``get_statistics_batched`` as host float64 arrays [n x nL], plus ``"TKE"`` (``statistics.tke`` of the variances) where
+        U and V are among the names"""
+        from . import statistics as st
+        dev = self.get_statistics_batched(names, pairs)
+        host = {}
+        with self._eng().on_stream():
+            for kind, d in dev.items():
+                host[kind] = {}
+                for key, t in d.items():
+                    if (kind, key) not in self._stats_host:
+                        self._stats_host[(kind, key)] = numpy.asarray(self._host(t), dtype=numpy.float64)
+                    host[kind][key] = self._stats_host[(kind, key)]
+        if "U" in host["var"] and "V" in host["var"]:
+            host["TKE"] = st.tke(host["var"])
+        return host
 
     # -- column water paths (K13) ------------------------------------------------------------------------------------------
     def _drop_water_paths(self):
@@ -789,6 +885,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             return
         f, p = self.fields3d, self.p
         self._drop_water_paths()
+        self._drop_statistics()
         if self._fused_step(dt):
             pass                                          # K11: fields, QL and p[U, V, THL, QT, QL] from one launch
         else:

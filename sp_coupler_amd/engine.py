@@ -1082,6 +1082,68 @@ class Engine:
         """workgroups that share a plane of K19 for these extents in the engine's dtype, as the library chooses; 0: bad extents"""
         return int(self.lib.spc_les_qt_local_split(int(n), int(itot), int(jtot), int(ktot), 4 if self.dtype == torch.float32 else 8))
 
+    # -- K20: the second moments of device-resident LES fields (variances, covariances, resolved fluxes) ---------------------------
+    @_on_engine_stream
+    def les_moments(self, fields, pairs=(), mean=True, var=True, std=False, face=None, out=None, stream=None):
+        """The moments per LES and level (include/spc.h has the rule) of contiguous device fields [n x itot x jtot x ktot] of ONE
+        shape, in ONE launch: ``fields`` is a dict name -> tensor (at most ``_abi.MOMENTS_MAX_FIELDS``), ``pairs`` a sequence of
+        ``(name, name)`` of two different fields (at most ``_abi.MOMENTS_MAX_PAIRS``), ``face`` the name of the one field that
+        is given at the upper faces of the cells (K17's W; it is brought to the centres first) or None.  Returns
+        ``{"mean": {name: t}, "var": {...}, "std": {...}, "cov": {(a, b): t}}`` with only the kinds asked for (``cov`` where
+        there are pairs), each tensor [n x ktot]: ``numpy.mean / var / std(field[l], axis=(0, 1))`` and the mean of the product
+        of the deviations of a pair, bit for bit.  ``out``: the same structure of tensors to write into (rows may be pitched,
+        all with one pitch); a kind or a name that ``out`` leaves out is allocated.  A field of one level (ktot == 1) is
+        refused (SPC_ERR_UNSUPPORTED)."""
+        names = list(fields)
+        if not 1 <= len(names) <= _abi.MOMENTS_MAX_FIELDS:
+            raise ValueError("les_moments takes 1 ... %d fields per launch, got %d" % (_abi.MOMENTS_MAX_FIELDS, len(names)))
+        pairs = [tuple(p) for p in pairs]
+        if len(pairs) > _abi.MOMENTS_MAX_PAIRS:
+            raise ValueError("les_moments takes at most %d pairs per launch, got %d" % (_abi.MOMENTS_MAX_PAIRS, len(pairs)))
+        for p in pairs:
+            if len(p) != 2 or p[0] not in fields or p[1] not in fields or p[0] == p[1]:
+                raise ValueError("les_moments: pair %r is not two different names of fields" % (p,))
+        if len(set(pairs)) != len(pairs):
+            raise ValueError("les_moments: a pair is asked for twice")
+        if face is not None and face not in fields:
+            raise ValueError("les_moments: the face field %r is not among the fields %s" % (face, names))
+        kinds = [k for k, on in (("mean", mean), ("var", var), ("std", std)) if on]
+        if not kinds and not pairs:
+            raise ValueError("les_moments: no output asked for")
+        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_moments: empty field shape %s" % (shape,))
+        a = _abi.LesMomentsArgs()
+        a.n_les, a.itot, a.jtot, a.ktot = n, itot, jtot, ktot
+        a.n_fields, a.n_pairs, a.face_field = len(names), len(pairs), -1 if face is None else names.index(face)
+        for f, name in enumerate(names):
+            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+        out = out or {}
+        wanted = [(kind, name) for kind in kinds for name in names] + [("cov", p) for p in pairs]
+        missing = [w for w in wanted if w[1] not in out.get(w[0], {})]
+        fresh = torch.empty(len(missing), n, ktot, dtype=self.dtype, device=self.device) if missing else None
+        res, pitch = {}, None
+        for kind, key in wanted:
+            if (kind, key) in missing:
+                o, p = self._out(fresh[missing.index((kind, key))], n, ktot)
+            else:
+                o, p = self._out(out[kind][key], n, ktot)
+            if pitch is not None and n > 1 and p != pitch:
+                raise ValueError("les_moments: out[%s][%s] has row pitch %d, the others %d" % (kind, key, p, pitch))
+            pitch = p
+            res.setdefault(kind, {})[key] = o
+            if kind == "cov":
+                q = pairs.index(key)
+                a.pair_a[q], a.pair_b[q] = names.index(key[0]), names.index(key[1])
+                a.cov[q] = o.data_ptr()
+            else:
+                getattr(a, kind)[names.index(key)] = o.data_ptr()
+        a.pitch_out = pitch
+        fn = self.lib.spc_les_moments_f32 if self.dtype == torch.float32 else self.lib.spc_les_moments_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

@@ -292,6 +292,23 @@ class MultiDeviceEngine:
         device that holds rows, none on the others"""
         return self._run("les_qt_local", qt, ql, a, qtm, count=count, split=split, **kw)
 
+    def les_moments(self, fields, pairs=(), mean=True, var=True, std=False, face=None, out=None, **kw):
+        """K20 on every device's LES: the dict of Sharded fields [n x itot x jtot x ktot] in, ``{kind: {name or pair: Sharded
+        [n x ktot]}}`` out (``out``: the same structure of Sharded tensors to write into); one launch per device that holds
+        rows, none on the others"""
+        ex = self._example(fields)
+        if ex is None:
+            return self.primary.les_moments(fields, pairs, mean=mean, var=var, std=std, face=face, out=out, **kw)
+        res = []
+        for d, e in enumerate(self.engines):
+            if ex.bounds[d + 1] <= ex.bounds[d]:
+                res.append(None)
+                continue
+            o = None if out is None else {kind: _parts_of(v, d) for kind, v in out.items()}
+            res.append(e.les_moments(_parts_of(fields, d), pairs, mean=mean, var=var, std=std, face=face, out=o, **kw))
+        ref = next(r for r in res if r is not None)
+        return {kind: self._join([None if r is None else r[kind] for r in res], ex.bounds) for kind in ref}
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

@@ -27,6 +27,8 @@ RADIATE_MUTANTS is the table of K18 (spc_radiate.hpp), chosen with --radiate; it
 tests/les_radiate_ref.py, which tests/test_les_radiate_gpu.py runs on the shipped library.
 QTLOCAL_MUTANTS is the table of K19 (spc_qtlocal.hpp), chosen with --qtlocal; its guards are the bodies of
 tests/les_qt_local_ref.py, which tests/test_les_qt_local_gpu.py runs on the shipped library.
+MOMENTS_MUTANTS is the table of K20 (spc_moments.hpp), chosen with --moments; its guards are the bodies of
+tests/les_moments_ref.py, which tests/test_les_moments_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
 tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
 --lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
@@ -48,6 +50,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --vadvect --build && python tools/mutation_control.py --vadvect > profiles/mutation_control_vadvect.log
        python tools/mutation_control.py --radiate --build && python tools/mutation_control.py --radiate > profiles/mutation_control_radiate.log
        python tools/mutation_control.py --qtlocal --build && python tools/mutation_control.py --qtlocal > profiles/mutation_control_qtlocal.log
+       python tools/mutation_control.py --moments --build && python tools/mutation_control.py --moments > profiles/mutation_control_moments.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log
        python tools/mutation_control.py --vnudge --build && python tools/mutation_control.py --vnudge > profiles/mutation_control_vnudge.log"""
@@ -77,6 +80,7 @@ ADVECT = "spc_advect.hpp"
 VADVECT = "spc_vadvect.hpp"
 RADIATE = "spc_radiate.hpp"
 QTLOCAL = "spc_qtlocal.hpp"
+MOMENTS = "spc_moments.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -710,6 +714,42 @@ QTLOCAL_MUTANTS = {
 }
 
 
+def moments_body(name):
+    """guard of a K20 mutant: the body ``name`` of tests/les_moments_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_moments_ref as mr
+        failed = []
+        for dtype in mr.DTYPES:
+            failed += mr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_moments_ref." + name
+    return guard
+
+
+# K20 (spc_moments.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches and none can hang (mutant 2 divides by T(0) on planes of one row; mutants 5 and 6 read the lane's own
+# vector where the shipped kernel reads the element below it or nothing; mutant 7 reads LES 0 of every field; mutant 8 leaves a
+# row out).
+MOMENTS_MUTANTS = {
+    1: ("K20 second walk: the product contracted into the sum by an fma", moments_body("special"),
+        [(MOMENTS, "acc.v[v] += q;", "acc.v[v] = fma(da, db, acc.v[v]);")]),
+    2: ("K20 second moments: division by N - 1 (the sample variance)", moments_body("parity"),
+        [(MOMENTS, "acc.v[v] = acc.v[v] / cnt;", "acc.v[v] = acc.v[v] / (cnt - (T)1);")]),
+    3: ("K20 cov: d_a * x_b for d_a * d_b (equal in exact arithmetic, not in bits)", moments_body("parity"),
+        [(MOMENTS, "c[NS - 1].v[v] - sum[NS - 1].v[v] : da;", "c[NS - 1].v[v] : da;")]),
+    4: ("K20 cov: the mean of field a taken from field b's cells", moments_body("parity"),
+        [(MOMENTS, "c[NS - 1].v[v] - sum[NS - 1].v[v] : da;", "c[NS - 1].v[v] - sum[0].v[v] : da;")]),
+    5: ("K20 face average: the lane's own first level for the level below its vector", moments_body("face"),
+        [(MOMENTS, "(v ? r.x.v[v - 1] : r.below)", "(v ? r.x.v[v - 1] : r.x.v[0])")]),
+    6: ("K20 face average: x[-1] is x[0], not +0.0", moments_body("face"),
+        [(MOMENTS, "r.below = below ? src[-1] : (T)0;", "r.below = below ? src[-1] : src[0];")]),
+    7: ("K20 l: the cells of LES 0 for every LES", moments_body("rows"),
+        [(MOMENTS, "first[s] = j.x[s] + l * p.nij * ktot + k;", "first[s] = j.x[s] + k;")]),
+    8: ("K20 walks: the last row behind the load-ahead loop is left out", moments_body("large_plane"),
+        [(MOMENTS, "for (; r < nij; ++r) {", "for (; r < nij - 1; ++r) {")]),
+}
+
+
 def vnudge_body(name):
     """guard of a K6 mutant: the body ``name`` of tests/vnudge_edges.py on both engines (float64, float32) of the library"""
     def guard(engine_of):
@@ -800,6 +840,7 @@ def _tag(table):
                    (MICRO_MUTANTS, ("micro_", "micro")), (DIFFUSE_MUTANTS, ("diffuse_", "diffuse")),
                    (ADVECT_MUTANTS, ("advect_", "advect")), (VADVECT_MUTANTS, ("vadvect_", "vadvect")),
                    (RADIATE_MUTANTS, ("radiate_", "radiate")), (QTLOCAL_MUTANTS, ("qtlocal_", "qtlocal")),
+                   (MOMENTS_MUTANTS, ("moments_", "moments")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq")), (VNUDGE_MUTANTS, ("vnudge_", "vnudge"))):
@@ -1004,13 +1045,14 @@ if __name__ == "__main__":
     ap.add_argument("--vadvect", action="store_true", help="the table of K17 (VADVECT_MUTANTS) instead of MUTANTS")
     ap.add_argument("--radiate", action="store_true", help="the table of K18 (RADIATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--qtlocal", action="store_true", help="the table of K19 (QTLOCAL_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--moments", action="store_true", help="the table of K20 (MOMENTS_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--vnudge", action="store_true", help="the table of K6 (VNUDGE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
              else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else RADIATE_MUTANTS if args.radiate
-             else QTLOCAL_MUTANTS if args.qtlocal else GEO_MUTANTS if args.geo
+             else QTLOCAL_MUTANTS if args.qtlocal else MOMENTS_MUTANTS if args.moments else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else VNUDGE_MUTANTS if args.vnudge else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -1046,4 +1088,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, RADIATE_MUTANTS, "K18", "les_radiate"))
     if args.qtlocal:
         sys.exit(main_advance(only, QTLOCAL_MUTANTS, "K19", "les_qt_local"))
+    if args.moments:
+        sys.exit(main_advance(only, MOMENTS_MUTANTS, "K20", "les_moments"))
     sys.exit((main_advance if args.advance else main)(only))
