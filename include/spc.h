@@ -34,6 +34,9 @@
  *   spc_les_radiate_*    <- the longwave cooling of that ensemble's cloud tops (nothing of it is in the reference): the
  *                           GCSS / DYCOMS-II parametrised flux of every column from its liquid water and the THL tendency
  *                           of its divergence, in one pass (kernel family K18)
+ *   spc_les_buoyancy_*   <- the hydrostatic pressure force of that ensemble (nothing of it is in the reference): the buoyancy
+ *                           of every column integrated downward to a pressure perturbation, whose horizontal gradient
+ *                           accelerates U and V in place, in two launches (kernel family K21)
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -798,6 +801,81 @@ typedef struct spc_les_moments_args {
 } spc_les_moments_args;
 int spc_les_moments_f64(const spc_les_moments_args *args, void *stream);
 int spc_les_moments_f32(const spc_les_moments_args *args, void *stream);
+
+/* ---- hydrostatic pressure force of the device-resident LES fields: buoyancy drives the winds (kernel family K21) -------------- */
+/* The model diagnoses W from continuity with a closed ground and an open lid, so its closure is the hydrostatic one: the buoyancy
+ * of every column is integrated downward from the lid to a pressure perturbation, the horizontal gradient of that pressure
+ * accelerates U and V, and continuity (K17) then turns the convergence into vertical motion.  Two launches behind one entry
+ * point.  The rule is this library's definition.
+ * General conventions:
+ *   - Fields are [n_les][itot][jtot][ktot], k contiguous, with 64-bit offsets as in K10.  The element type T is f64 or f32.
+ *   - Every operation is rounded once in T.  Nothing contracts to an fma.
+ *   - The kernels hold no division and no transcendental function.
+ *   - So every output is asked for bit for bit in both types, whatever the launch shape.
+ * Profiles:
+ *   - The profiles are [n_les x ktot], rows pitch_prof apart.
+ *   - They are formed in float64 by sp_coupler_amd/buoyancy.py (profiles(...)) and rounded to T once.
+ *   - The constants come from sputils where it has them: grav, rlv, cp, rd, rv.
+ *   - t0  = thv of the slab means: (THL + lex QL) * ((1 + c1 QT) - c2 QL) of p["THL"], p["QT"], p["QL"]: the reference virtual
+ *           potential temperature.
+ *   - lex = rlv / (cp * exner(presf)).
+ *   - s   = 0.5 * grav * dz / t0: half a layer's weight; dz from the half levels, as water_path_weights() takes it.
+ * Scalars and per-LES values:
+ *   - c1 = rv / rd - 1 and c2 = rv / rd are passed as doubles in the args and rounded to T once.
+ *   - hx, hy [n_les] are K16's: 0.5 dt / dx and 0.5 dt / dy.
+ * Per cell (l, i, j, k):
+ *   e   = lex[l][k] * ql                 (ql == NULL: e = +0 and m = 1 + c1 * qt)
+ *   tl  = thl + e
+ *   m   = (1 + c1 * qt) - c2 * ql
+ *   tv  = tl * m
+ *   b   = (tv - t0[l][k]) * s[l][k]                      half-layer buoyancy integral, m2/s2
+ *   q[ktot] = +0                                         the lid: no pressure perturbation
+ *   phi[k]  = q[k+1] - b[k];   q[k] = phi[k] - b[k]      SEQUENTIAL downward, two subtractions per level
+ *   psfc[l][i][j] = q[0]                                 optional: the perturbation at the ground
+ * Then, with ip, im, jp, jm the periodic neighbours as K16 forms them:
+ *   gx = phi[ip] - phi[im];   du = hx[l] * gx;   u' = u - du     IN PLACE
+ *   gy = phi[jp] - phi[jm];   dv = hy[l] * gy;   v' = v - dv     IN PLACE
+ *   a  = |du| + |dv|;         amax[l] = the maximum of a over the cells of LES l (optional; the launch zeroes it first;
+ *                                       K16's atomicMax on the bit pattern)
+ * phi is [n_les][itot][jtot][ktot] and is written whole.
+ *   - It is required, because it is both the workspace between the two launches and a diagnostic.
+ *   - thl, qt and ql are read only.
+ * Consequences:
+ *   - A state that is uniform on every level gives the same phi in every column.  Every gx and gy is +0, every finite u and v
+ *     keeps its bits (-0.0 included), and amax = 0.
+ *   - itot <= 2 makes every gx zero.  The same holds for jtot <= 2 and gy.
+ *   - A NaN in one thl cell makes phi NaN in its own column from that level DOWN.  It makes u' (resp. v') NaN in the two
+ *     i-neighbour (resp. j-neighbour) columns at those levels, and amax[l] a NaN (ask with isnan, not for its bits).  Every
+ *     other cell of the launch keeps the bits of the run without it.
+ *   - Infinities get no rule of their own.
+ *   - These are SPC_ERR_INVALID_ARGUMENT:
+ *       pitch_prof < ktot;
+ *       a NULL thl, qt, u, v, phi, hx, hy, t0, lex or s;
+ *       phi, u, v, psfc or amax equal to an input or to each other.
+ *   - Arrays that overlap only in part are not detected and must not be passed.
+ *   - n_les == 0 is a no-op.  ktot == 1 is allowed.
+ *   - Above the largest ktot of which 16 columns fit in LDS (1 279 levels of 8 bytes, 2 559 of 4) the launch is
+ *     SPC_ERR_UNSUPPORTED.  It is refused on the host and nothing is launched.
+ * k_les_hydrostatic: a workgroup takes spc_les_buoyancy_cols_per_block(ktot, sizeof(T)) columns into one LDS tile.  k_les_pgrad: a
+ * workgroup owns spc_les_advect_strip(...) cells of the run [jtot][ktot] of a row i and spc_les_advect_rows(...) rows.        */
+typedef struct spc_les_buoyancy_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, reserved;
+    const void *thl, *qt;               /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *ql;                     /* device [n_les][itot][jtot][ktot], read only, or NULL              */
+    void *u, *v;                        /* device [n_les][itot][jtot][ktot], updated in place                */
+    const void *hx, *hy;                /* device [n_les]: 0.5 dt / dx and 0.5 dt / dy                       */
+    const void *t0, *lex, *s;           /* device [n_les x ktot] each, rows pitch_prof apart                 */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+    double c1, c2;                      /* rv / rd - 1 and rv / rd                                           */
+    void *phi;                          /* device [n_les][itot][jtot][ktot], written whole                   */
+    void *psfc;                         /* device [n_les][itot][jtot], written whole, or NULL                */
+    void *amax;                         /* device [n_les], or NULL                                           */
+} spc_les_buoyancy_args;
+int spc_les_buoyancy_f64(const spc_les_buoyancy_args *args, void *stream);
+int spc_les_buoyancy_f32(const spc_les_buoyancy_args *args, void *stream);
+/* columns per workgroup of k_les_hydrostatic for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
+int spc_les_buoyancy_cols_per_block(int ktot, int elem_size);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

@@ -176,6 +176,12 @@ class LesRadiateArgs(ctypes.Structure):
                 + [("inv_step", c_double)] + _ptrs("flux", "fsfc"))
 
 
+class LesBuoyancyArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("reserved", c_int32)]
+                + _ptrs("thl", "qt", "ql", "u", "v", "hx", "hy", "t0", "lex", "s") + [("pitch_prof", c_int64), ("c1", c_double), ("c2", c_double)]
+                + _ptrs("phi", "psfc", "amax"))
+
+
 class LesQtLocalArgs(ctypes.Structure):
     _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("split", c_int32)]
                 + _ptrs("qt", "ql", "a", "qtm") + [("pitch_prof", c_int64), ("count", c_void_p), ("pitch_count", c_int64)])
@@ -259,6 +265,9 @@ PROTOTYPES = {
     "spc_les_qt_local_split": (ctypes.c_int, [c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "spc_les_moments_f64": (ctypes.c_int, [ctypes.POINTER(LesMomentsArgs), c_void_p]),
     "spc_les_moments_f32": (ctypes.c_int, [ctypes.POINTER(LesMomentsArgs), c_void_p]),
+    "spc_les_buoyancy_f64": (ctypes.c_int, [ctypes.POINTER(LesBuoyancyArgs), c_void_p]),
+    "spc_les_buoyancy_f32": (ctypes.c_int, [ctypes.POINTER(LesBuoyancyArgs), c_void_p]),
+    "spc_les_buoyancy_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

@@ -41,6 +41,9 @@
 //   K20 k_les_moments  the second moments of those fields per (LES, level): means, variances, standard deviations and the
 //                  covariances of pairs of fields (the resolved fluxes, W brought from the faces to the centres), NumPy's
 //                  sequential order, one job per field or pair in one launch: spc_moments.hpp, kernel and host side
+//   K21 k_les_hydrostatic, k_les_pgrad  the hydrostatic pressure force: the buoyancy of every column integrated downward to
+//                  a pressure perturbation (one chain per column of a tile in LDS), whose horizontal gradient accelerates U
+//                  and V in place (K16's neighbours along i and j): spc_buoyancy.hpp, kernels and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -99,6 +102,7 @@ namespace {
 #include "spc_radiate.hpp"
 #include "spc_qtlocal.hpp"
 #include "spc_moments.hpp"
+#include "spc_buoyancy.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -139,6 +143,9 @@ namespace {
 #define SPC_MOMENTS_HOST
 #include "spc_moments.hpp"
 #undef SPC_MOMENTS_HOST
+#define SPC_BUOYANCY_HOST
+#include "spc_buoyancy.hpp"
+#undef SPC_BUOYANCY_HOST
 
 }  // namespace
 
@@ -235,6 +242,10 @@ int spc_les_radiate_cols_per_block(int ktot, int elem_size) { return rad_cols(kt
 int spc_les_qt_local_f64(const spc_les_qt_local_args *a, void *s) { return les_qt_local_impl<double>(a, s); }
 int spc_les_qt_local_f32(const spc_les_qt_local_args *a, void *s) { return les_qt_local_impl<float>(a, s); }
 int spc_les_qt_local_split(int64_t n_les, int itot, int jtot, int ktot, int elem_size) { return qtl_split(n_les, itot, jtot, ktot, elem_size); }
+
+int spc_les_buoyancy_f64(const spc_les_buoyancy_args *a, void *s) { return les_buoyancy_impl<double>(a, s); }
+int spc_les_buoyancy_f32(const spc_les_buoyancy_args *a, void *s) { return les_buoyancy_impl<float>(a, s); }
+int spc_les_buoyancy_cols_per_block(int ktot, int elem_size) { return hyd_cols(ktot, elem_size); }
 
 int spc_les_moments_f64(const spc_les_moments_args *a, void *s) { return les_moments_impl<double>(a, s); }
 int spc_les_moments_f32(const spc_les_moments_args *a, void *s) { return les_moments_impl<float>(a, s); }

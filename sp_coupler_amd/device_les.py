@@ -6,6 +6,7 @@ import numpy
 import torch
 
 from . import advection as adv
+from . import buoyancy as buo
 from . import diffusion as df
 from . import microphysics as mp
 from . import radiation as rad
@@ -130,6 +131,9 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     After ``enable_qt_forcing(kind)`` every step moves QT between the wet and the dry cells of every plane by the cloud-water
     forcing the coupler handed over (K19, ``Engine.les_qt_local``: qt_forcing 'local' | 'strong'); tests/les_qt_local_ref.py
     holds the twin of that mode.
+    After ``enable_buoyancy()`` every advective substep starts with the hydrostatic pressure force on U and V (K21,
+    ``Engine.les_buoyancy``) and ``get_pressure_batched()`` returns the pressure perturbation; tests/les_buoyancy_ref.py holds
+    the twin of that mode.
     ``get_statistics_batched`` reduces the fields to their second moments per level (K20, ``Engine.les_moments``): means,
     variances, standard deviations and the covariances of ``statistics.PAIRS``; tests/les_moments_ref.py holds their twin."""
 
@@ -350,6 +354,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.advection, self._advect_coef, self._advect_spare = True, None, {}
         self.advect_vertical, self._vadvect_prof, self._vadvect_mtop, self._vadvect_dt = bool(vertical), None, None, None
         self.advect_courant_z = None
+        self.buoyancy = False                                         # (K21 is enabled after, and for, the advection of this call)
 
     def _advect_coefs(self, dt, n_sub):
         """device (hx, hy) of the substeps dt / n_sub; uploaded where dt, n_sub, dx or dy are not those of the last step"""
@@ -379,6 +384,13 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if "U" not in f or "V" not in f:
             raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
         keys = [k for k in self.ADVECT_KEYS if k in f]
+        buoyant = self.buoyancy
+        if buoyant:                                       # QL and p[THL, QT, QL] of the stepped fields, then t0, lex and s of those means
+            if "THL" not in f or "QT" not in f:
+                raise ValueError("the pressure force (K21) needs the fields THL and QT (set_fields_batched)")
+            self._follow_fields()
+            prof = self._buoyancy_profiles()
+            ql = f.get("QL")
         c = self._device_max(eng.les_advect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1)))
         vertical = self.advect_vertical
         if vertical:                                      # K17's probe: the vertical Courant sums of the whole step
@@ -386,6 +398,12 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             c = max(c, self._device_max(eng.les_vadvect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1), g, r)))
         try:
             n_sub = adv.substeps(c, par["cfl"], par["max_substeps"])
+            if buoyant:                                   # the fastest gravity wave asks for its own substeps
+                n_wave = buo.wave_substeps(dt, self.dx, self.dy, par["cfl"], self.buoyancy_wave_speed)
+                if n_wave > par["max_substeps"]:
+                    raise RuntimeError("the pressure force (K21) needs %d substeps for waves of %g m/s at cfl %g, more than max_substeps = %d"
+                                       % (n_wave, self.buoyancy_wave_speed, par["cfl"], par["max_substeps"]))
+                n_sub = max(n_sub, n_wave)
         except RuntimeError:                              # nothing has been advected: QL and the profiles of the stepped fields
             self._follow_fields()
             raise
@@ -395,8 +413,13 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             spare[k] = self._scratch(spare.get(k), f[k], f[k])
         if vertical:
             self._vadvect_mtop = self._scratch(self._vadvect_mtop, f["U"])
-        worst = worst_z = None
+        if buoyant:
+            self._buoyancy_phi = self._scratch(self._buoyancy_phi, f["U"])
+        worst = worst_z = worst_b = None
         for _ in range(n_sub):
+            if buoyant:                                   # forward-backward: the winds feel the pressure, then carry the fields
+                am = eng.les_buoyancy(f["THL"], f["QT"], ql, f["U"], f["V"], hx, hy, *prof, self._buoyancy_phi)
+                worst_b = am if worst_b is None else self._per_device(torch.maximum, worst_b, am)
             out = {k: spare[k] for k in keys}
             cm = eng.les_advect({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy)
             for k in keys:
@@ -412,6 +435,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if vertical:
             self._vadvect_dt = float(dt) / n_sub
             self.advect_courant_z = self._device_max(worst_z)
+        if buoyant:
+            self.buoyancy_wind_change = self._device_max(worst_b)
         self._drop_water_paths()
         self._drop_statistics()
         self._thermo_stale = True                         # thermo: K12 runs on the advected THL and QT before their next use
@@ -419,6 +444,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             self._follow_fields()
         if vertical and not numpy.isfinite(self.advect_courant_z):
             raise RuntimeError("the vertical advection (K17) found the Courant sum c = %r: the mass flux is not finite" % self.advect_courant_z)
+        if buoyant and not numpy.isfinite(self.buoyancy_wind_change):
+            raise RuntimeError("the pressure force (K21) found the wind change %r: the pressure is not finite" % self.buoyancy_wind_change)
 
     def _vadvect_profiles(self):
         """device (g, r) of K17: g = water_path_weights(), r = 1 / g; uploaded once, and again where the weights changed"""
@@ -434,6 +461,55 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             return None
         rho = self._upload(numpy.asarray(self.p["Rhobf"], dtype=numpy.float64))
         return self._per_device(lambda m, rh: adv.vertical_wind(m, rh, self._vadvect_dt), self._vadvect_mtop, rho)
+
+    # -- hydrostatic pressure force on the winds (K21), opt-in --------------------------------------------------------------------
+    buoyancy = False                                   # enable_buoyancy(): K21 in front of every advective substep
+    buoyancy_wave_speed = None                         # m/s: the gravity wave the substeps resolve
+    buoyancy_wind_change = None                        # the largest |du| + |dv| any substep of the last step returned, m/s
+    _buoyancy_prof = None                              # ((host means THL, QT, QL, presf, zh) of the upload, device (t0, lex, s))
+    _buoyancy_phi = None                               # the pressure perturbation of the last substep, device
+
+    def enable_buoyancy(self, wave_speed=None):
+        """from now on every advective substep of ``evolve_model_batched`` is K21 (``Engine.les_buoyancy``) with
+        the substep's hx and hy on the winds, then K16, then K17: the buoyancy of THL, QT and QL against the virtual potential
+        temperature of their slab means is integrated downward to a pressure perturbation whose horizontal gradient
+        accelerates U and V, and continuity turns the convergence into vertical motion (forward-backward: the order that is
+        stable for gravity waves).  Needs ``enable_advection(..., vertical=True)`` (without continuity the pressure force has
+        no feedback) and THL, QT, U and V fields (ValueError otherwise).  QL is used where the ensemble has one (K12 where
+        stale, or max(QT - Qsat, 0)), formed once per step from the stepped fields, whose slab means p[THL, QT, QL] give the
+        profiles t0, lex and s (``buoyancy.profiles``; uploaded again only where they changed): one K10 launch (and one K12
+        with ``enable_thermo()``) more per step.  n_sub is the larger of what the Courant probes ask for and
+        ceil(wave_speed * dt / (cfl * min(dx, dy))) (``wave_speed`` defaults to ``buoyancy.WAVE_SPEED``), refused above
+        ``max_substeps`` like K16's.  ``get_pressure_batched()`` returns phi of the last substep, ``buoyancy_wind_change`` holds
+        the largest wind change of the step; the step raises RuntimeError where that is not finite.  Without this call every
+        path, launch count and result of the ensemble is unchanged."""
+        if not (self.advection and self.advect_vertical):
+            raise ValueError("the pressure force (K21) needs enable_advection(..., vertical=True): continuity is its feedback")
+        missing = [k for k in ("THL", "QT", "U", "V") if k not in self.fields3d]
+        if missing:
+            raise ValueError("the pressure force (K21) needs the fields %s (set_fields_batched)" % missing)
+        if not self._has("les_buoyancy"):
+            raise ValueError("the engine has no les_buoyancy (K21)")
+        speed = buo.WAVE_SPEED if wave_speed is None else float(wave_speed)
+        if not (numpy.isfinite(speed) and speed >= 0):
+            raise ValueError("the pressure force (K21) needs a finite wave_speed >= 0")
+        self.buoyancy, self.buoyancy_wave_speed = True, speed
+        self.buoyancy_wind_change, self._buoyancy_prof, self._buoyancy_phi = None, None, None
+
+    def _buoyancy_profiles(self):
+        """device (t0, lex, s) of K21 from the host means as they are now; uploaded again where anything they are made of changed"""
+        p = self.p
+        has_ql = "QL" in self.fields3d
+        key = _f64(p["THL"], p["QT"], p["QL"] if has_ql else numpy.zeros(0), p["presf"], self.zh_cache)
+        self._buoyancy_prof = _kept(self._buoyancy_prof, key, lambda: (key, tuple(self._upload(a) for a in buo.profiles(
+            key[0], key[1], key[2] if has_ql else None, key[3], key[4], zf=self.zf_cache))))
+        return self._buoyancy_prof[1]
+
+    def get_pressure_batched(self):
+        """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the hydrostatic pressure
+        perturbation phi in m2/s2 that K21 found in the last substep of the last step; None before the first step of
+        enable_buoyancy()"""
+        return self._buoyancy_phi if self.buoyancy else None
 
     # -- longwave cooling and warming by the liquid water (K18), opt-in ---------------------------------------------------------
     radiation = False                                  # enable_radiation(): the cloud water acts on THL

@@ -1144,6 +1144,64 @@ class Engine:
         self._call(fn, ctypes.byref(a), stream=stream)
         return res
 
+    # -- K21: the hydrostatic pressure force of device-resident LES fields on their winds, two launches ---------------------------
+    @_on_engine_stream
+    def les_buoyancy(self, thl, qt, ql, u, v, hx, hy, t0, lex, s, phi, psfc=None, amax=True, stream=None):
+        """The hydrostatic pressure force (include/spc.h has the rule) on contiguous device fields [n x itot x jtot x ktot]:
+        the buoyancy of ``thl``, ``qt`` and ``ql`` (read only; ``ql`` may be None: no liquid water) against ``t0`` is integrated
+        downward from the lid into ``phi`` (written whole), and ``u`` and ``v`` take the horizontal gradient of ``phi`` IN
+        PLACE.  ``hx`` and ``hy`` [n] are ``advection.coefficients``, ``t0``, ``lex`` and ``s`` [n x ktot]
+        ``buoyancy.profiles`` in the engine's dtype (rows may be pitched, all with one pitch).  ``psfc``: a tensor
+        [n x itot x jtot] that takes the pressure perturbation at the ground, or None.  ``amax``: True (a fresh [n] tensor),
+        a tensor [n] to write into, or False / None; returned: the largest wind change |du| + |dv| of every LES (a NaN where
+        any cell's is one), or None.  A written tensor that STARTS where an input or another written tensor starts is refused
+        (ValueError); views that overlap in part are not detected.  Two launches; more levels than
+        ``buoyancy_cols_per_block`` carries are refused (SPC_ERR_UNSUPPORTED)."""
+        from . import buoyancy
+        shape = tuple(self._field4("thl", thl).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_buoyancy: empty field shape %s" % (shape,))
+        want = amax is not None and amax is not False
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.LesBuoyancyArgs()
+        a.n_les, a.itot, a.jtot, a.ktot = n, itot, jtot, ktot
+        a.thl, a.qt = thl.data_ptr(), self._field4("qt", qt, shape).data_ptr()
+        if ql is not None:
+            a.ql = self._field4("ql", ql, shape).data_ptr()
+        a.u, a.v = self._field4("u", u, shape).data_ptr(), self._field4("v", v, shape).data_ptr()
+        a.hx, a.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
+        a.t0, a.pitch_prof = ck.mat("t0", t0, n, ktot)
+        a.lex, _ = ck.mat("lex", lex, n, ktot, pitch=a.pitch_prof)
+        a.s, _ = ck.mat("s", s, n, ktot, pitch=a.pitch_prof)
+        a.c1, a.c2 = buoyancy.C1, buoyancy.C2
+        a.phi = self._field4("phi", phi, shape).data_ptr()
+        written = [phi, u, v]
+        if psfc is not None:
+            if not isinstance(psfc, torch.Tensor) or psfc.device != self.device or psfc.dtype != self.dtype or \
+                    tuple(psfc.shape) != (n, itot, jtot) or not psfc.is_contiguous():
+                raise ValueError("les_buoyancy: psfc must be a contiguous %s tensor of shape %s on %s" % (self.dtype, (n, itot, jtot), self.device))
+            a.psfc = psfc.data_ptr()
+            written.append(psfc)
+        res = None
+        if want:
+            res = torch.empty(n, dtype=self.dtype, device=self.device) if amax is True else amax
+            a.amax = ck.vec("amax", res, n)
+            written.append(res)
+        if n:
+            read = [t.data_ptr() for t in (thl, qt, ql, hx, hy, t0, lex, s) if t is not None]
+            written = [t.data_ptr() for t in written]
+            if len(set(written)) != len(written) or set(written) & set(read):
+                raise ValueError("les_buoyancy: phi, u, v, psfc or amax is an input or another of them")
+        fn = self.lib.spc_les_buoyancy_f32 if self.dtype == torch.float32 else self.lib.spc_les_buoyancy_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
+    def buoyancy_cols_per_block(self, ktot):
+        """columns of ``ktot`` levels a workgroup of K21's k_les_hydrostatic takes into LDS in the engine's dtype (64, 32 or 16);
+        0: unsupported"""
+        return int(self.lib.spc_les_buoyancy_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

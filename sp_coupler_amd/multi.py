@@ -309,6 +309,19 @@ class MultiDeviceEngine:
         ref = next(r for r in res if r is not None)
         return {kind: self._join([None if r is None else r[kind] for r in res], ex.bounds) for kind in ref}
 
+    def les_buoyancy(self, thl, qt, ql, u, v, hx, hy, t0, lex, s, phi, psfc=None, amax=True, **kw):
+        """K21 on every device's LES: the Sharded fields ``thl``, ``qt``, ``ql`` (or None), ``u`` and ``v`` (updated in place,
+        block by block), ``hx``, ``hy`` [n], the Sharded profiles ``t0``, ``lex`` and ``s`` [n x ktot], ``phi`` and ``psfc`` (or
+        None) in; the Sharded [n] largest wind changes out (None without ``amax``); two launches per device that holds rows,
+        none on the others"""
+        ex = self._example(thl)
+        if ex is None:
+            return self.primary.les_buoyancy(thl, qt, ql, u, v, hx, hy, t0, lex, s, phi, psfc=psfc, amax=amax, **kw)
+        res = self._each("les_buoyancy", ex, (thl, qt, ql, u, v, hx, hy, t0, lex, s, phi), dict(kw, psfc=psfc, amax=amax))
+        if amax is None or amax is False:
+            return None
+        return amax if amax is not True else self._join(res, ex.bounds)
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

@@ -27,6 +27,8 @@ RADIATE_MUTANTS is the table of K18 (spc_radiate.hpp), chosen with --radiate; it
 tests/les_radiate_ref.py, which tests/test_les_radiate_gpu.py runs on the shipped library.
 QTLOCAL_MUTANTS is the table of K19 (spc_qtlocal.hpp), chosen with --qtlocal; its guards are the bodies of
 tests/les_qt_local_ref.py, which tests/test_les_qt_local_gpu.py runs on the shipped library.
+BUOYANCY_MUTANTS is the table of K21 (spc_buoyancy.hpp), chosen with --buoyancy; its guards are the bodies of
+tests/les_buoyancy_ref.py, which tests/test_les_buoyancy_gpu.py runs on the shipped library.
 MOMENTS_MUTANTS is the table of K20 (spc_moments.hpp), chosen with --moments; its guards are the bodies of
 tests/les_moments_ref.py, which tests/test_les_moments_gpu.py runs on the shipped library.
 GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
@@ -51,6 +53,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --radiate --build && python tools/mutation_control.py --radiate > profiles/mutation_control_radiate.log
        python tools/mutation_control.py --qtlocal --build && python tools/mutation_control.py --qtlocal > profiles/mutation_control_qtlocal.log
        python tools/mutation_control.py --moments --build && python tools/mutation_control.py --moments > profiles/mutation_control_moments.log
+       python tools/mutation_control.py --buoyancy --build && python tools/mutation_control.py --buoyancy > profiles/mutation_control_buoyancy.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log
        python tools/mutation_control.py --vnudge --build && python tools/mutation_control.py --vnudge > profiles/mutation_control_vnudge.log"""
@@ -81,6 +84,7 @@ VADVECT = "spc_vadvect.hpp"
 RADIATE = "spc_radiate.hpp"
 QTLOCAL = "spc_qtlocal.hpp"
 MOMENTS = "spc_moments.hpp"
+BUOYANCY = "spc_buoyancy.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -488,6 +492,42 @@ RADIATE_MUTANTS = {
 }
 
 
+def buoyancy_body(name):
+    """guard of a K21 mutant: the body ``name`` of tests/les_buoyancy_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_buoyancy_ref as lbr
+        failed = []
+        for dtype in lbr.DTYPES:
+            failed += lbr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_buoyancy_ref." + name
+    return guard
+
+
+# K21 (spc_buoyancy.hpp), numbered on its own.  Every mutant changes a VALUE only: no address, loop bound, barrier or launch
+# extent differs from the shipped kernels' (mutant 5 makes the chain visit the same ktot cells of its own column of the tile
+# in the opposite order; mutant 6 uses the register that already holds phi[ip]).
+BUOYANCY_MUTANTS = {
+    1: ("K21 tv: the product and the subtraction of t0 contracted to an fma", buoyancy_body("parity"),
+        [(BUOYANCY, "    const T tv = tl * m;\n    const T d = tv - p.t0[po];", "    const T d = (T)__builtin_fma((double)tl, (double)m, -(double)p.t0[po]);")]),
+    2: ("K21 m: c1 for c2 (liquid water weighed like vapour)", buoyancy_body("parity"),
+        [(BUOYANCY, "const T w = p.c2 * ql;", "const T w = p.c1 * ql;")]),
+    3: ("K21 tl: the lex term dropped (THL for the liquid-water-free temperature)", buoyancy_body("parity"),
+        [(BUOYANCY, "const T e = QL ? p.lex[po] * ql : (T)0;", "const T e = (T)0;")]),
+    4: ("K21 chain: + b for - b in q (the lower half layer taken off again)", buoyancy_body("parity"),
+        [(BUOYANCY, "            q = f - cb[u];", "            q = f + cb[u];"),
+         (BUOYANCY, "        q = f - b;", "        q = f + b;")]),
+    5: ("K21 chain: started at k = 0 (integrated upward from the ground)", buoyancy_body("parity"),
+        [(BUOYANCY, "{ return ktot - 1 - s; }", "{ return s; }")]),
+    6: ("K21 gx: ip for im (phi[ip] - phi[ip])", buoyancy_body("parity"),
+        [(BUOYANCY, "const T gx = fp - fm;", "const T gx = fp - fp;")]),
+    7: ("K21 dv: hx for hy", buoyancy_body("rows"),
+        [(BUOYANCY, "const T dv = hy * gy;", "const T dv = hx * gy;")]),
+    8: ("K21 amax: without |dv|", buoyancy_body("parity"),
+        [(BUOYANCY, "const T a = au + av;", "const T a = au;")]),
+}
+
+
 # K15 (spc_diffuse.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 2 reads cp[k + 1] for k <= ktot - 2, mutant 4 the rows of the LES of the tile's first column,
 # mutant 6 cp's row in place of a's; mutants 5 and 7 leave a level of the tile as it is).
@@ -840,7 +880,7 @@ def _tag(table):
                    (MICRO_MUTANTS, ("micro_", "micro")), (DIFFUSE_MUTANTS, ("diffuse_", "diffuse")),
                    (ADVECT_MUTANTS, ("advect_", "advect")), (VADVECT_MUTANTS, ("vadvect_", "vadvect")),
                    (RADIATE_MUTANTS, ("radiate_", "radiate")), (QTLOCAL_MUTANTS, ("qtlocal_", "qtlocal")),
-                   (MOMENTS_MUTANTS, ("moments_", "moments")),
+                   (MOMENTS_MUTANTS, ("moments_", "moments")), (BUOYANCY_MUTANTS, ("buoyancy_", "buoyancy")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq")), (VNUDGE_MUTANTS, ("vnudge_", "vnudge"))):
@@ -1046,13 +1086,14 @@ if __name__ == "__main__":
     ap.add_argument("--radiate", action="store_true", help="the table of K18 (RADIATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--qtlocal", action="store_true", help="the table of K19 (QTLOCAL_MUTANTS) instead of MUTANTS")
     ap.add_argument("--moments", action="store_true", help="the table of K20 (MOMENTS_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--buoyancy", action="store_true", help="the table of K21 (BUOYANCY_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--vnudge", action="store_true", help="the table of K6 (VNUDGE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
              else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else RADIATE_MUTANTS if args.radiate
-             else QTLOCAL_MUTANTS if args.qtlocal else MOMENTS_MUTANTS if args.moments else GEO_MUTANTS if args.geo
+             else QTLOCAL_MUTANTS if args.qtlocal else MOMENTS_MUTANTS if args.moments else BUOYANCY_MUTANTS if args.buoyancy else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else VNUDGE_MUTANTS if args.vnudge else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -1088,6 +1129,8 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, RADIATE_MUTANTS, "K18", "les_radiate"))
     if args.qtlocal:
         sys.exit(main_advance(only, QTLOCAL_MUTANTS, "K19", "les_qt_local"))
+    if args.buoyancy:
+        sys.exit(main_advance(only, BUOYANCY_MUTANTS, "K21", "les_buoyancy"))
     if args.moments:
         sys.exit(main_advance(only, MOMENTS_MUTANTS, "K20", "les_moments"))
     sys.exit((main_advance if args.advance else main)(only))
