@@ -672,6 +672,66 @@ int spc_les_vadvect_f32(const spc_les_vadvect_args *args, void *stream);
 /* columns per workgroup of k_les_vadvect for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
 int spc_les_vadvect_cols_per_block(int ktot, int elem_size);
 
+/* ---- conservative flux-form transport of the device-resident LES fields along i, j and k in one launch (kernel family K22) ---- */
+/* One UNSPLIT first-order donor-cell step in FLUX form, consistent with K17's continuity: what K16 followed by K17 do in advective
+ * form and two launches, done in one so that sum_ijk g x changes only by what passes the lid.  The layout, the offsets, hx, hy,
+ * g = rho dz, r = 1 / g and pitch_prof are K17's; im, ip, jm, jp are the periodic neighbours as K16 forms them.  Element type T;
+ * every operation is rounded once in T, never an fma, and the kernel holds no division.  Per cell (l, i, j, k), every array at
+ * level k of LES l unless indexed otherwise:
+ *   cw, ce, cs, cn                                                K16's face Courant numbers, bit for bit
+ *   d    = (ce - cw) + (cn - cs);   e = g[l][k] * d
+ *   M[0] = +0;   M[k+1] = M[k] - e                                K17's chain, bit for bit; mtop[l][i][j][k] = M[k+1] is K17's mtop
+ *   pw   = cw > 0 ? cw : 0;   qw = cw < 0 ? cw : 0                likewise (pe, qe), (ps, qs), (pn, qn); a NaN face gives +0 twice
+ *   Mb   = M[k];   Mt = M[k+1]
+ *   pb   = Mb > 0 ? Mb : 0;   qb = Mb < 0 ? Mb : 0;               pt, qt of Mt likewise
+ *   km   = k ? k-1 : 0;   kp = k+1 < ktot ? k+1 : ktot-1          closed ground; open lid with zero gradient
+ *   Fw   = pw * x[im] + qw * x                                    two products, each rounded, then the add; x = fields[f]
+ *   Fe   = pe * x     + qe * x[ip]
+ *   Fs   = ps * x[jm] + qs * x
+ *   Fn   = pn * x     + qn * x[jp]
+ *   Fb   = pb * x[km] + qb * x
+ *   Ft   = pt * x     + qt * x[kp]
+ *   h    = (Fe - Fw) + (Fn - Fs)
+ *   z    = r[l][k] * (Ft - Fb)
+ *   out[f] = (x - h) - z
+ *   s    = ((pe - qw) + (pn - qs)) + r[l][k] * (pt - qb)          the outflow Courant sum; cmax[l] = its maximum over the cells of
+ *                                                                 LES l (the launch zeroes it first)
+ *   ftop[f][l][i][j] = Ft at k = ktot-1                           optional: what left through the lid, in units of g x
+ * Shared faces: the flux through a face has the same bits in both cells that share it -- Fe of (i) is Fw of (ip), Fn of (j) is
+ * Fs of (jp), Ft of k is Fb of k + 1 (the ground face has M[0] = +0: Fb of k = 0 is +0 for a finite field).
+ * Conservation: sum_ijk g x' + sum_ij ftop = sum_ijk g x to rounding, per LES and field.  A constant field stays constant TO
+ * ROUNDING -- not bit for bit, unlike K16 and K17: the six fluxes of a constant cancel only as far as continuity holds in T.
+ * With s <= 1 out[f] is a convex combination of the cell and its six neighbours.  Winds that are uniform per level give M = 0
+ * and the rule reduces to horizontal transport.  An extent of 1 makes the two fluxes of that axis equal: their difference is +0.
+ * Special values get no rule of their own: a NaN or an infinity of a field reaches at most itself and its six neighbours (a
+ * closed face still multiplies it by +0); a NaN wind closes the faces it touches and makes M NaN from its level upward, as in
+ * K17.  s is never NaN and never negative.  u, v and the fields are read only; a field may be u or v itself.  Every out[f], mtop
+ * and ftop is written whole.  n_fields == 0 with cmax and / or mtop is the probe: only the winds and the profiles are read (an
+ * ftop is then ignored).  Nothing to do (no field, no cmax, no mtop), pitch_prof < ktot, a required array that is NULL, an
+ * out[f], mtop, cmax or ftop EQUAL to an input or to another output, and a pointer that is not aligned to T are
+ * SPC_ERR_INVALID_ARGUMENT; arrays that overlap in part are not detected and must not be passed.  n_les == 0 is a no-op; ktot == 1
+ * is allowed.  A workgroup takes spc_les_transport_cols_per_block(ktot, sizeof(T)) columns into LDS (K17's tile); above the
+ * largest ktot of which 16 columns fit (1 279 levels of 8 bytes, 2 559 of 4) the call is SPC_ERR_UNSUPPORTED on the host, before
+ * any launch.  The rule is this library's definition.                                                   */
+#define SPC_TRANSPORT_MAX_FIELDS 6
+typedef struct spc_les_transport_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_fields; /* n_fields 0 ... SPC_TRANSPORT_MAX_FIELDS                           */
+    const void *u, *v;                  /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *fields[SPC_TRANSPORT_MAX_FIELDS]; /* device [n_les][itot][jtot][ktot], read only             */
+    void *out[SPC_TRANSPORT_MAX_FIELDS];/* device [n_les][itot][jtot][ktot], written whole                   */
+    const void *hx, *hy;                /* device [n_les]: 0.5 dt / dx and 0.5 dt / dy                       */
+    void *cmax;                         /* device [n_les], or NULL                                           */
+    const void *g, *r;                  /* device [n_les x ktot] each, rows pitch_prof apart: rho dz, 1 / g  */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+    void *mtop;                         /* device [n_les][itot][jtot][ktot], written whole, or NULL          */
+    void *ftop;                         /* device [n_fields][n_les][itot][jtot], written whole, or NULL      */
+} spc_les_transport_args;
+int spc_les_transport_f64(const spc_les_transport_args *args, void *stream);
+int spc_les_transport_f32(const spc_les_transport_args *args, void *stream);
+/* columns per workgroup of k_les_transport for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
+int spc_les_transport_cols_per_block(int ktot, int elem_size);
+
 /* ---- longwave cooling and warming of the device-resident LES fields by their liquid water (kernel family K18) ----------------- */
 /* The first two terms of the GCSS / DYCOMS-II parametrised longwave flux (Stevens et al. 2005): the flux that the liquid water
  * above and below a face lets through, and the THL tendency of its divergence.  ql and thl are [n_les][itot][jtot][ktot] (layout

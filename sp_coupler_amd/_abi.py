@@ -170,6 +170,15 @@ class LesVadvectArgs(ctypes.Structure):
                 + _ptrs("hx", "hy", "cmax", "g", "r") + [("pitch_prof", c_int64), ("mtop", c_void_p)])
 
 
+SPC_TRANSPORT_MAX_FIELDS = 6
+
+
+class LesTransportArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32)] + _ptrs("u", "v")
+                + [("fields", c_void_p * SPC_TRANSPORT_MAX_FIELDS), ("out", c_void_p * SPC_TRANSPORT_MAX_FIELDS)]
+                + _ptrs("hx", "hy", "cmax", "g", "r") + [("pitch_prof", c_int64), ("mtop", c_void_p), ("ftop", c_void_p)])
+
+
 class LesRadiateArgs(ctypes.Structure):
     _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_tab", c_int32)]
                 + _ptrs("ql", "thl", "w", "c") + [("pitch_prof", c_int64)] + _ptrs("f0", "f1", "etab")
@@ -257,6 +266,9 @@ PROTOTYPES = {
     "spc_les_vadvect_f64": (ctypes.c_int, [ctypes.POINTER(LesVadvectArgs), c_void_p]),
     "spc_les_vadvect_f32": (ctypes.c_int, [ctypes.POINTER(LesVadvectArgs), c_void_p]),
     "spc_les_vadvect_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "spc_les_transport_f64": (ctypes.c_int, [ctypes.POINTER(LesTransportArgs), c_void_p]),
+    "spc_les_transport_f32": (ctypes.c_int, [ctypes.POINTER(LesTransportArgs), c_void_p]),
+    "spc_les_transport_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_les_radiate_f64": (ctypes.c_int, [ctypes.POINTER(LesRadiateArgs), c_void_p]),
     "spc_les_radiate_f32": (ctypes.c_int, [ctypes.POINTER(LesRadiateArgs), c_void_p]),
     "spc_les_radiate_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),

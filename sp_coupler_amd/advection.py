@@ -1,10 +1,24 @@
 """The constants and the coefficients of K16, the horizontal upwind advection of the device-resident LES fields on the doubly
 periodic plane (include/spc.h: spc_les_advect_*), and the profiles of K17, their vertical advection by the mass
-flux of continuity (spc_les_vadvect_*).
+flux of continuity (spc_les_vadvect_*), and of K22, their conservative transport along all three axes in one launch
+(spc_les_transport_*).
 
 The kernel takes hx = 0.5 dt / dx and hy = 0.5 dt / dy per LES: formed ONCE here, in float64 NumPy, and rounded once to the
 element type on upload; the kernel and the NumPy oracle of the tests receive the same arrays, and neither divides.  K17 takes
-g = rho dz and r = 1 / g per LES and level (``vertical_profiles``), formed the same way; neither depends on dt."""
+g = rho dz and r = 1 / g per LES and level (``vertical_profiles``), formed the same way; neither depends on dt.
+
+K22 (``Engine.les_transport``) takes the same hx, hy, g and r.  Its rule, per cell (l, i, j, k) in the element type, one
+rounding per operation, no fma, no division (include/spc.h is the definition):
+    cw, ce, cs, cn                      K16's face Courant numbers
+    d = (ce - cw) + (cn - cs);  e = g * d;  M[0] = +0;  M[k+1] = M[k] - e        K17's chain; mtop = M[k+1]
+    pw = cw > 0 ? cw : 0;  qw = cw < 0 ? cw : 0       likewise (pe, qe), (ps, qs), (pn, qn), (pb, qb) of M[k], (pt, qt) of M[k+1]
+    Fw = pw * x[im] + qw * x;   Fe = pe * x + qe * x[ip];   Fs = ps * x[jm] + qs * x;   Fn = pn * x + qn * x[jp]
+    Fb = pb * x[km] + qb * x;   Ft = pt * x + qt * x[kp]                         km, kp clamped: closed ground, open lid
+    x' = (x - ((Fe - Fw) + (Fn - Fs))) - r * (Ft - Fb)
+    s  = ((pe - qw) + (pn - qs)) + r * (pt - qb)      the outflow Courant sum: x' is a convex combination where s <= 1
+    ftop = Ft at the top level                        what left through the lid, in units of g x
+Both cells that share a face form its flux from the same operands, so sum(g x') + sum(ftop) = sum(g x) to rounding
+(``lid_budget``); a constant stays constant to rounding, not bit for bit."""
 import math
 
 import numpy
@@ -57,3 +71,20 @@ def vertical_wind(mtop, rhobf, dt):
     up = torch.cat([rhobf[:, 1:], rhobf[:, -1:]], dim=1)
     face = 0.5 * (rhobf + up)
     return mtop / (face * float(dt))[:, None, None, :]
+
+
+def lid_budget(g, x_old, x_new, ftop):
+    """float64 ``(residual, scale)``, [n] each, of one K22 step (or of several, ``ftop`` their sum) on the host:
+    residual = sum_ijk g x_new + sum_ij ftop - sum_ijk g x_old and scale = sum_ijk g |x_old| per LES, every sum formed with
+    ``math.fsum`` of float64 products (exact for float32 inputs), so the residual holds the step's own roundings only.
+    ``g`` [n x ktot], the fields [n x itot x jtot x ktot], ``ftop`` [n x itot x jtot] or None (a closed lid)"""
+    g = numpy.asarray(g, dtype=numpy.float64)
+    a, b = numpy.asarray(x_old, dtype=numpy.float64), numpy.asarray(x_new, dtype=numpy.float64)
+    n = a.shape[0]
+    res, scale = numpy.zeros(n), numpy.zeros(n)
+    for l in range(n):
+        w = g[l][None, None, :]
+        lid = [] if ftop is None else list(numpy.asarray(ftop[l], dtype=numpy.float64).ravel())
+        res[l] = math.fsum(list((w * b[l]).ravel()) + lid + list(-(w * a[l]).ravel()))
+        scale[l] = math.fsum((w * numpy.abs(a[l])).ravel())
+    return res, scale

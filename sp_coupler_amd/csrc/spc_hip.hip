@@ -44,6 +44,9 @@
 //   K21 k_les_hydrostatic, k_les_pgrad  the hydrostatic pressure force: the buoyancy of every column integrated downward to
 //                  a pressure perturbation (one chain per column of a tile in LDS), whose horizontal gradient accelerates U
 //                  and V in place (K16's neighbours along i and j): spc_buoyancy.hpp, kernels and host side
+//   K22 k_les_transport  one unsplit donor-cell step in flux form of the transport of those fields along i, j and k (K16's face
+//                  numbers, K17's chain and tile; every face flux formed alike by the two cells that share it, so the mass
+//                  of a field changes only through the lid): spc_transport.hpp, kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -99,6 +102,7 @@ namespace {
 #include "spc_diffuse.hpp"
 #include "spc_advect.hpp"
 #include "spc_vadvect.hpp"
+#include "spc_transport.hpp"
 #include "spc_radiate.hpp"
 #include "spc_qtlocal.hpp"
 #include "spc_moments.hpp"
@@ -134,6 +138,9 @@ namespace {
 #define SPC_VADVECT_HOST
 #include "spc_vadvect.hpp"
 #undef SPC_VADVECT_HOST
+#define SPC_TRANSPORT_HOST
+#include "spc_transport.hpp"
+#undef SPC_TRANSPORT_HOST
 #define SPC_RADIATE_HOST
 #include "spc_radiate.hpp"
 #undef SPC_RADIATE_HOST
@@ -234,6 +241,9 @@ int spc_les_advect_rows(int64_t n_les, int itot, int jtot, int ktot) { return ad
 int spc_les_vadvect_f64(const spc_les_vadvect_args *a, void *s) { return les_vadvect_impl<double>(a, s); }
 int spc_les_vadvect_f32(const spc_les_vadvect_args *a, void *s) { return les_vadvect_impl<float>(a, s); }
 int spc_les_vadvect_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
+int spc_les_transport_f64(const spc_les_transport_args *a, void *s) { return les_transport_impl<double>(a, s); }
+int spc_les_transport_f32(const spc_les_transport_args *a, void *s) { return les_transport_impl<float>(a, s); }
+int spc_les_transport_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
 
 int spc_les_radiate_f64(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<double>(a, s); }
 int spc_les_radiate_f32(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<float>(a, s); }

@@ -318,8 +318,11 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     _vadvect_prof = None                               # (the host weights of the upload, device (g, r))
     _vadvect_mtop = None                               # the mass flux through the upper faces in the last substep, device
     _vadvect_dt = None                                 # the seconds of that substep
+    advect_conservative = False                        # enable_advection(vertical=True, conservative=True): K22 is every substep
+    _transport_ftop = None                             # what K22 writes per substep: [fields x n x itot x jtot], device
+    _transport_lid = None                              # (the names of the transported fields, the sum of ftop over the substeps)
 
-    def enable_advection(self, dx=None, dy=None, cfl=None, max_substeps=None, vertical=False):
+    def enable_advection(self, dx=None, dy=None, cfl=None, max_substeps=None, vertical=False, conservative=False):
         """from now on every ``evolve_model_batched`` advects the fields among U, V, THL, QT and QR that exist with the winds U
         and V on the doubly periodic plane (K16, ``Engine.les_advect``), after the step and before K15 / K14 /
         K12: ONE probe launch per device finds the largest Courant sum c of the whole step, n_sub = max(1, ceil(c / cfl))
@@ -336,13 +339,27 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         a swap: 2 + 2 n_sub launches per device and step.  The profiles g = ``water_path_weights()`` and r = 1 / g are uploaded
         once.  ``advect_courant_z`` holds the largest vertical Courant sum of the substeps (it can grow during them, so it is
         recorded and refused only where it is not finite: RuntimeError), ``get_vertical_wind_batched()`` the vertical wind of
-        the last substep.  With the default every path, launch count and result is what it is without the argument."""
+        the last substep.  With the default every path, launch count and result is what it is without the argument.
+
+        ``conservative=True`` (with ``vertical=True``; ValueError otherwise, or where the engine has no ``les_transport``)
+        replaces the split pair by K22 (``Engine.les_transport``): one unsplit donor-cell step in flux form that conserves
+        sum(rho dz x) of every field up to what passes the lid.  Per step ONE K22 probe with the coefficients of the whole dt
+        gives the largest outflow Courant sum c and n_sub = ``advection.substeps(c, cfl, max_substeps)`` (with
+        ``enable_buoyancy()`` at least the gravity wave's); every substep is K21 where enabled, then ONE K22 on the fields
+        into the spare buffers, then a swap: 1 + n_sub launches per device and step.  ``advect_courant`` holds the largest
+        outflow sum of the substeps (RuntimeError where it is not finite), ``advect_courant_z`` is None,
+        ``get_vertical_wind_batched()`` works from K22's mass flux and ``get_lid_flux_batched()`` returns what left through
+        the lid.  With the default every path, launch count and result is what it is without the argument."""
         if "U" not in self.fields3d or "V" not in self.fields3d:
             raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
         if not self._has("les_advect"):
             raise ValueError("the engine has no les_advect (K16)")
         if vertical and not self._has("les_vadvect"):
             raise ValueError("the engine has no les_vadvect (K17)")
+        if conservative and not vertical:
+            raise ValueError("the conservative transport (K22) is the horizontal and the vertical advection in one: it needs vertical=True")
+        if conservative and not self._has("les_transport"):
+            raise ValueError("the engine has no les_transport (K22)")
         dx, dy = adv.DX if dx is None else dx, adv.DY if dy is None else dy
         adv.coefficients(1.0, dx, dy, n=self.n)                       # (ValueError for a spacing that is not positive, or not [n])
         self.dx = numpy.array(dx, dtype=numpy.float64) if numpy.ndim(dx) else float(dx)
@@ -354,6 +371,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.advection, self._advect_coef, self._advect_spare = True, None, {}
         self.advect_vertical, self._vadvect_prof, self._vadvect_mtop, self._vadvect_dt = bool(vertical), None, None, None
         self.advect_courant_z = None
+        self.advect_conservative, self._transport_ftop, self._transport_lid = bool(conservative), None, None
         self.buoyancy = False                                         # (K21 is enabled after, and for, the advection of this call)
 
     def _advect_coefs(self, dt, n_sub):
@@ -378,35 +396,23 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     def _advect(self, dt):
         """K16 on the stepped fields: the probe, then n_sub launches into the spare buffers; QL (without thermo) and the
         profiles are then those of the advected fields, unless K15 follows and does both"""
-        eng, f, par = self._eng(), self.fields3d, self.advect_par
+        if self.advect_conservative:
+            return self._transport(dt)
+        eng, f = self._eng(), self.fields3d
         if self.n == 0:
             return
         if "U" not in f or "V" not in f:
             raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
         keys = [k for k in self.ADVECT_KEYS if k in f]
         buoyant = self.buoyancy
-        if buoyant:                                       # QL and p[THL, QT, QL] of the stepped fields, then t0, lex and s of those means
-            if "THL" not in f or "QT" not in f:
-                raise ValueError("the pressure force (K21) needs the fields THL and QT (set_fields_batched)")
-            self._follow_fields()
-            prof = self._buoyancy_profiles()
-            ql = f.get("QL")
+        if buoyant:
+            prof, ql = self._buoyancy_inputs()
         c = self._device_max(eng.les_advect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1)))
         vertical = self.advect_vertical
         if vertical:                                      # K17's probe: the vertical Courant sums of the whole step
             g, r = self._vadvect_profiles()
             c = max(c, self._device_max(eng.les_vadvect({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1), g, r)))
-        try:
-            n_sub = adv.substeps(c, par["cfl"], par["max_substeps"])
-            if buoyant:                                   # the fastest gravity wave asks for its own substeps
-                n_wave = buo.wave_substeps(dt, self.dx, self.dy, par["cfl"], self.buoyancy_wave_speed)
-                if n_wave > par["max_substeps"]:
-                    raise RuntimeError("the pressure force (K21) needs %d substeps for waves of %g m/s at cfl %g, more than max_substeps = %d"
-                                       % (n_wave, self.buoyancy_wave_speed, par["cfl"], par["max_substeps"]))
-                n_sub = max(n_sub, n_wave)
-        except RuntimeError:                              # nothing has been advected: QL and the profiles of the stepped fields
-            self._follow_fields()
-            raise
+        n_sub = self._advect_substeps(c, dt)
         hx, hy = self._advect_coefs(dt, n_sub)
         spare = self._advect_spare
         for k in keys:
@@ -447,6 +453,96 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if buoyant and not numpy.isfinite(self.buoyancy_wind_change):
             raise RuntimeError("the pressure force (K21) found the wind change %r: the pressure is not finite" % self.buoyancy_wind_change)
 
+    def _buoyancy_inputs(self):
+        """(device (t0, lex, s), the QL field or None) of K21 for this step: QL and p[THL, QT, QL] of the stepped fields, then
+        the profiles of those means"""
+        f = self.fields3d
+        if "THL" not in f or "QT" not in f:
+            raise ValueError("the pressure force (K21) needs the fields THL and QT (set_fields_batched)")
+        self._follow_fields()
+        return self._buoyancy_profiles(), f.get("QL")
+
+    def _advect_substeps(self, c, dt):
+        """the substeps of a step of ``dt`` whose probes found the Courant sum ``c``, at least the gravity wave's with
+        enable_buoyancy(); RuntimeError, after QL and the profiles have followed the stepped fields (nothing has been advected),
+        where c is not finite or more than max_substeps would be needed"""
+        par = self.advect_par
+        try:
+            n_sub = adv.substeps(c, par["cfl"], par["max_substeps"])
+            if self.buoyancy:                             # the fastest gravity wave asks for its own substeps
+                n_wave = buo.wave_substeps(dt, self.dx, self.dy, par["cfl"], self.buoyancy_wave_speed)
+                if n_wave > par["max_substeps"]:
+                    raise RuntimeError("the pressure force (K21) needs %d substeps for waves of %g m/s at cfl %g, more than max_substeps = %d"
+                                       % (n_wave, self.buoyancy_wave_speed, par["cfl"], par["max_substeps"]))
+                n_sub = max(n_sub, n_wave)
+        except RuntimeError:
+            self._follow_fields()
+            raise
+        return n_sub
+
+    def _transport(self, dt):
+        """K22 on the stepped fields: the probe, then n_sub launches into the spare buffers, each the whole transport of its
+        substep; what follows the substeps is what follows them in ``_advect``"""
+        eng, f = self._eng(), self.fields3d
+        if self.n == 0:
+            return
+        if "U" not in f or "V" not in f:
+            raise ValueError("the advection (K22) needs the fields U and V (set_fields_batched)")
+        keys = [k for k in self.ADVECT_KEYS if k in f]
+        buoyant = self.buoyancy
+        if buoyant:
+            prof, ql = self._buoyancy_inputs()
+        g, r = self._vadvect_profiles()
+        c = self._device_max(eng.les_transport({}, {}, f["U"], f["V"], *self._advect_coefs(dt, 1), g, r))
+        n_sub = self._advect_substeps(c, dt)
+        hx, hy = self._advect_coefs(dt, n_sub)
+        spare = self._advect_spare
+        for k in keys:
+            spare[k] = self._scratch(spare.get(k), f[k], f[k])
+        self._vadvect_mtop = self._scratch(self._vadvect_mtop, f["U"])
+        if buoyant:
+            self._buoyancy_phi = self._scratch(self._buoyancy_phi, f["U"])
+        shapes = lambda t, lead=(): [lead + tuple(part.shape) for part in getattr(t, "parts", [t])]          # noqa: E731
+        if self._transport_ftop is None or shapes(self._transport_ftop) != [s[:4] for s in shapes(f["U"], (len(keys),))]:
+            self._transport_ftop = self._per_device(lambda w: w.new_empty((len(keys),) + tuple(w.shape[:3])), f["U"])
+        ftop = self._transport_ftop
+        worst = worst_b = total = None
+        for _ in range(n_sub):
+            if buoyant:                                   # forward-backward: the winds feel the pressure, then carry the fields
+                am = eng.les_buoyancy(f["THL"], f["QT"], ql, f["U"], f["V"], hx, hy, *prof, self._buoyancy_phi)
+                worst_b = am if worst_b is None else self._per_device(torch.maximum, worst_b, am)
+            out = {k: spare[k] for k in keys}
+            cm = eng.les_transport({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy, g, r, mtop=self._vadvect_mtop, ftop=ftop)
+            for k in keys:
+                f[k], spare[k] = spare[k], f[k]
+            worst = cm if worst is None else self._per_device(torch.maximum, worst, cm)
+            # (elementwise adds in substep order: a NumPy twin has the same bits)
+            total = self._per_device(torch.clone, ftop) if total is None else self._per_device(torch.add, total, ftop)
+        self.advect_substeps, self.advect_courant, self.advect_courant_z = n_sub, self._device_max(worst), None
+        self._vadvect_dt, self._transport_lid = float(dt) / n_sub, (tuple(keys), total)
+        if buoyant:
+            self.buoyancy_wind_change = self._device_max(worst_b)
+        self._drop_water_paths()
+        self._drop_statistics()
+        self._thermo_stale = True                         # thermo: K12 runs on the transported THL and QT before their next use
+        if not self.diffusion:                            # (else the QL field and the means follow the diffused fields: _diffuse)
+            self._follow_fields()
+        if not numpy.isfinite(self.advect_courant):
+            raise RuntimeError("the conservative transport (K22) found the Courant sum c = %r: the winds or the mass flux are not finite" % self.advect_courant)
+        if buoyant and not numpy.isfinite(self.buoyancy_wind_change):
+            raise RuntimeError("the pressure force (K21) found the wind change %r: the pressure is not finite" % self.buoyancy_wind_change)
+
+    def get_lid_flux_batched(self):
+        """dict name -> device tensor [n x itot x jtot] (Sharded row blocks under a MultiDeviceEngine): per transported field
+        the sum over the substeps of the last step of K22's ``ftop``, what left every column through the lid in units of
+        rho dz x (negative: it entered); None before the first step of enable_advection(vertical=True, conservative=True)"""
+        if not self.advect_conservative or self._transport_lid is None:
+            return None
+        keys, total = self._transport_lid
+        if isinstance(total, Sharded):
+            return {k: Sharded([part[q] for part in total.parts], total.bounds) for q, k in enumerate(keys)}
+        return {k: total[q] for q, k in enumerate(keys)}
+
     def _vadvect_profiles(self):
         """device (g, r) of K17: g = water_path_weights(), r = 1 / g; uploaded once, and again where the weights changed"""
         w = numpy.ascontiguousarray(self.water_path_weights())
@@ -474,7 +570,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         the substep's hx and hy on the winds, then K16, then K17: the buoyancy of THL, QT and QL against the virtual potential
         temperature of their slab means is integrated downward to a pressure perturbation whose horizontal gradient
         accelerates U and V, and continuity turns the convergence into vertical motion (forward-backward: the order that is
-        stable for gravity waves).  Needs ``enable_advection(..., vertical=True)`` (without continuity the pressure force has
+        stable for gravity waves); after ``enable_advection(..., vertical=True, conservative=True)`` it is K21, then K22.  Needs ``enable_advection(..., vertical=True)`` (without continuity the pressure force has
         no feedback) and THL, QT, U and V fields (ValueError otherwise).  QL is used where the ensemble has one (K12 where
         stale, or max(QT - Qsat, 0)), formed once per step from the stepped fields, whose slab means p[THL, QT, QL] give the
         profiles t0, lex and s (``buoyancy.profiles``; uploaded again only where they changed): one K10 launch (and one K12

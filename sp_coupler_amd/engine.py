@@ -998,6 +998,66 @@ class Engine:
         """columns of ``ktot`` levels a workgroup of K17 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
         return int(self.lib.spc_les_vadvect_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
 
+    # -- K22: conservative flux-form transport of device-resident LES fields along i, j and k, one launch -------------------------
+    @_on_engine_stream
+    def les_transport(self, fields, out, u, v, hx, hy, g, r, cmax=True, mtop=None, ftop=None, stream=None):
+        """One unsplit donor-cell step in flux form (include/spc.h has the rule) of every tensor of ``fields`` (dict name ->
+        contiguous [n x itot x jtot x ktot], at most ``_abi.SPC_TRANSPORT_MAX_FIELDS`` of one shape, read only) by the winds
+        ``u`` and ``v`` (the same shape, read only; a field may be ``u`` or ``v`` itself) and the mass flux that continuity
+        gives them, into the tensors of ``out`` (the same names, written whole).  ``hx``, ``hy``, ``g`` and ``r`` are those of
+        ``les_vadvect``.  ``cmax``: True (a fresh [n] tensor), a tensor [n] to write into, or False / None; returned: the
+        largest outflow Courant sum of every LES, or None.  ``mtop``: a tensor of the fields' shape that takes the mass flux
+        through the upper face of every cell (K17's, bit for bit), or None.  ``ftop``: a contiguous tensor
+        [len(fields) x n x itot x jtot] that takes, in the order of ``fields``, what left every column through the lid in
+        units of g x, or None.  ``fields`` may be empty with ``cmax`` and / or ``mtop``: the probe.  A written tensor that
+        STARTS where an input or another written tensor starts is refused (ValueError); views that overlap in part are not
+        detected.  One launch; more levels than ``transport_cols_per_block`` carries are refused (SPC_ERR_UNSUPPORTED)."""
+        names = list(fields)
+        if len(names) > _abi.SPC_TRANSPORT_MAX_FIELDS:
+            raise ValueError("les_transport takes at most %d fields per launch, got %d" % (_abi.SPC_TRANSPORT_MAX_FIELDS, len(names)))
+        if sorted(out) != sorted(names):
+            raise ValueError("les_transport: out holds %s, the fields are %s" % (sorted(out), sorted(names)))
+        want = cmax is not None and cmax is not False
+        if not names and not want and mtop is None:
+            raise ValueError("les_transport: no field, no cmax and no mtop: nothing to do")
+        if not names and ftop is not None:
+            raise ValueError("les_transport: ftop without a field")
+        shape = tuple(self._field4("u", u).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_transport: empty field shape %s" % (shape,))
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.LesTransportArgs()
+        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
+        a.u, a.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
+        a.hx, a.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
+        a.g, a.pitch_prof = ck.mat("g", g, n, ktot)
+        a.r, _ = ck.mat("r", r, n, ktot, pitch=a.pitch_prof)
+        res = None
+        if want:
+            res = torch.empty(n, dtype=self.dtype, device=self.device) if cmax is True else cmax
+            a.cmax = ck.vec("cmax", res, n)
+        if mtop is not None:
+            a.mtop = self._field4("mtop", mtop, shape).data_ptr()
+        if ftop is not None:
+            a.ftop = self._field4("ftop", ftop, (len(names), n, itot, jtot)).data_ptr()
+        for f, name in enumerate(names):
+            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            a.out[f] = self._field4("out[%s]" % name, out[name], shape).data_ptr()
+        if n:
+            read = [t.data_ptr() for t in [u, v, hx, hy, g, r] + [fields[k] for k in names]]
+            written = ([out[k].data_ptr() for k in names] + ([res.data_ptr()] if want else [])
+                       + [t.data_ptr() for t in (mtop, ftop) if t is not None])
+            if len(set(written)) != len(written) or set(written) & set(read):
+                raise ValueError("les_transport: an output is an input, cmax, mtop, ftop or another output")
+        fn = self.lib.spc_les_transport_f32 if self.dtype == torch.float32 else self.lib.spc_les_transport_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
+    def transport_cols_per_block(self, ktot):
+        """columns of ``ktot`` levels a workgroup of K22 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
+        return int(self.lib.spc_les_transport_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+
     # -- K18: longwave cooling and warming of device-resident LES fields by their liquid water, one launch ------------------------
     @_on_engine_stream
     def les_radiate(self, ql, thl, w, c, f0, f1, *, flux=None, fsfc=None, stream=None):

@@ -277,6 +277,19 @@ class MultiDeviceEngine:
             return None
         return cmax if cmax is not True else self._join(res, ex.bounds)
 
+    def les_transport(self, fields, out, u, v, hx, hy, g, r, cmax=True, mtop=None, ftop=None, **kw):
+        """K22 on every device's LES: dicts of Sharded fields and outputs (written block by block), Sharded winds, ``hx``, ``hy``
+        [n], the profiles ``g`` and ``r`` [n x ktot], ``mtop`` (or None) and ``ftop`` (or None: a Sharded whose part on device
+        d is [len(fields) x that device's rows x itot x jtot]) in; the Sharded [n] outflow Courant sums out (None without
+        ``cmax``); one launch per device that holds rows"""
+        ex = self._example(u)
+        if ex is None:
+            return self.primary.les_transport(fields, out, u, v, hx, hy, g, r, cmax=cmax, mtop=mtop, ftop=ftop, **kw)
+        res = self._each("les_transport", ex, (fields, out, u, v, hx, hy, g, r), dict(kw, cmax=cmax, mtop=mtop, ftop=ftop))
+        if cmax is None or cmax is False:
+            return None
+        return cmax if cmax is not True else self._join(res, ex.bounds)
+
     def les_radiate(self, ql, thl, w, c, f0, f1, *, flux=None, fsfc=None, **kw):
         """K18 on every device's LES: the Sharded fields ``ql`` and ``thl`` (updated in place, block by block), the Sharded
         profiles ``w`` and ``c`` [n x ktot], ``f0`` and ``f1`` [n] and ``flux`` / ``fsfc`` (or None) in; one launch per device

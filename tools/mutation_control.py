@@ -23,6 +23,8 @@ ADVECT_MUTANTS is the table of K16 (spc_advect.hpp), chosen with --advect; its g
 tests/les_advect_ref.py, which tests/test_les_advect_gpu.py runs on the shipped library.
 VADVECT_MUTANTS is the table of K17 (spc_vadvect.hpp), chosen with --vadvect; its guards are the bodies of
 tests/les_vadvect_ref.py, which tests/test_les_vadvect_gpu.py runs on the shipped library.
+TRANSPORT_MUTANTS is the table of K22 (spc_transport.hpp), chosen with --transport; its guards are the bodies of
+tests/les_transport_ref.py, which tests/test_les_transport_gpu.py runs on the shipped library.
 RADIATE_MUTANTS is the table of K18 (spc_radiate.hpp), chosen with --radiate; its guards are the bodies of
 tests/les_radiate_ref.py, which tests/test_les_radiate_gpu.py runs on the shipped library.
 QTLOCAL_MUTANTS is the table of K19 (spc_qtlocal.hpp), chosen with --qtlocal; its guards are the bodies of
@@ -54,6 +56,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --qtlocal --build && python tools/mutation_control.py --qtlocal > profiles/mutation_control_qtlocal.log
        python tools/mutation_control.py --moments --build && python tools/mutation_control.py --moments > profiles/mutation_control_moments.log
        python tools/mutation_control.py --buoyancy --build && python tools/mutation_control.py --buoyancy > profiles/mutation_control_buoyancy.log
+       python tools/mutation_control.py --transport --build && python tools/mutation_control.py --transport > profiles/mutation_control_transport.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log
        python tools/mutation_control.py --vnudge --build && python tools/mutation_control.py --vnudge > profiles/mutation_control_vnudge.log"""
@@ -85,6 +88,7 @@ RADIATE = "spc_radiate.hpp"
 QTLOCAL = "spc_qtlocal.hpp"
 MOMENTS = "spc_moments.hpp"
 BUOYANCY = "spc_buoyancy.hpp"
+TRANSPORT = "spc_transport.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -874,6 +878,42 @@ def patched(n, src=CSRC, table=None):
     return files
 
 
+def transport_body(name):
+    """guard of a K22 mutant: the body ``name`` of tests/les_transport_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_transport_ref as ltr
+        failed = []
+        for dtype in ltr.DTYPES:
+            failed += ltr.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_transport_ref." + name
+    return guard
+
+
+# K22 (spc_transport.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
+# shipped kernel touches (mutant 1 reads x, which the cell reads anyway, for x[ip]; mutant 5 starts K17's chain, which K22 calls,
+# from 1 in the same LDS cells; mutant 6 reads x[km], which the cell reads anyway, for the top cell's x[kp]; mutant 8 stores Fb
+# where Ft belongs).
+TRANSPORT_MUTANTS = {
+    1: ("K22 Fe: x for x[ip] (the air that enters through the east face carries the cell's own value)", transport_body("parity"),
+        [(TRANSPORT, "const T e1 = pe * x, e2 = qe * xe;", "const T e1 = pe * x, e2 = qe * x;")]),
+    2: ("K22 Fw: pw for qw (the west face gives the cell what it takes from it)", transport_body("signs"),
+        [(TRANSPORT, "const T w1 = pw * xw, w2 = qw * x;", "const T w1 = pw * xw, w2 = pw * x;")]),
+    3: ("K22 h: Fe + Fw for Fe - Fw", transport_body("parity"),
+        [(TRANSPORT, "const T hi = Fe - Fw;", "const T hi = Fe + Fw;")]),
+    4: ("K22 z: the vertical flux difference without r", transport_body("rows"),
+        [(TRANSPORT, "const T z = rk * dz;", "const T z = dz;")]),
+    5: ("K22 M: the chain started from M[0] = 1 (the ground leaks)", transport_body("signs"),
+        [(VADVECT, "    T M = (T)0;\n    int k = 0;", "    T M = (T)1;\n    int k = 0;")]),
+    6: ("K22 kp: the top cell takes the cell below it for the air that enters through the lid", transport_body("parity"),
+        [(TRANSPORT, "const int64_t okp = k + 1 < ktot ? o + 1 : o;", "const int64_t okp = k + 1 < ktot ? o + 1 : okm;")]),
+    7: ("K22 cmax: the outflow sum without its vertical part", transport_body("probe"),
+        [(TRANSPORT, "const T s = sh + sv;", "const T s = sh;")]),
+    8: ("K22 ftop: taken from Fb (what entered the top cell from below)", transport_body("fields"),
+        [(TRANSPORT, "p.ftop[f * p.ncols + col0 + w.c] = Ft;", "p.ftop[f * p.ncols + col0 + w.c] = Fb;")]),
+}
+
+
 def _tag(table):
     """(library prefix, source directory prefix) of a table"""
     for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
@@ -881,6 +921,7 @@ def _tag(table):
                    (ADVECT_MUTANTS, ("advect_", "advect")), (VADVECT_MUTANTS, ("vadvect_", "vadvect")),
                    (RADIATE_MUTANTS, ("radiate_", "radiate")), (QTLOCAL_MUTANTS, ("qtlocal_", "qtlocal")),
                    (MOMENTS_MUTANTS, ("moments_", "moments")), (BUOYANCY_MUTANTS, ("buoyancy_", "buoyancy")),
+                   (TRANSPORT_MUTANTS, ("transport_", "transport")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq")), (VNUDGE_MUTANTS, ("vnudge_", "vnudge"))):
@@ -1087,13 +1128,14 @@ if __name__ == "__main__":
     ap.add_argument("--qtlocal", action="store_true", help="the table of K19 (QTLOCAL_MUTANTS) instead of MUTANTS")
     ap.add_argument("--moments", action="store_true", help="the table of K20 (MOMENTS_MUTANTS) instead of MUTANTS")
     ap.add_argument("--buoyancy", action="store_true", help="the table of K21 (BUOYANCY_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--transport", action="store_true", help="the table of K22 (TRANSPORT_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--vnudge", action="store_true", help="the table of K6 (VNUDGE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
              else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else RADIATE_MUTANTS if args.radiate
-             else QTLOCAL_MUTANTS if args.qtlocal else MOMENTS_MUTANTS if args.moments else BUOYANCY_MUTANTS if args.buoyancy else GEO_MUTANTS if args.geo
+             else QTLOCAL_MUTANTS if args.qtlocal else MOMENTS_MUTANTS if args.moments else BUOYANCY_MUTANTS if args.buoyancy else TRANSPORT_MUTANTS if args.transport else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else VNUDGE_MUTANTS if args.vnudge else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -1133,4 +1175,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, BUOYANCY_MUTANTS, "K21", "les_buoyancy"))
     if args.moments:
         sys.exit(main_advance(only, MOMENTS_MUTANTS, "K20", "les_moments"))
+    if args.transport:
+        sys.exit(main_advance(only, TRANSPORT_MUTANTS, "K22", "les_transport"))
     sys.exit((main_advance if args.advance else main)(only))
