@@ -732,6 +732,61 @@ int spc_les_transport_f32(const spc_les_transport_args *args, void *stream);
 /* columns per workgroup of k_les_transport for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
 int spc_les_transport_cols_per_block(int ktot, int elem_size);
 
+/* ---- second-order limited flux-form transport of the device-resident LES fields in one launch (kernel family K23) ------------- */
+/* K22's step with a SECOND-ORDER face value.  The layout, hx, hy, g, r, pitch_prof, the face Courant numbers, the chain M, the
+ * twelve numbers pw, qw, ..., pt, qt, the six donor fluxes Fw ... Ft, mtop and cmax are K22's, bit for bit (so cmax of K23 equals
+ * cmax of K22, and n_fields == 0 is the same probe).  Every operation is rounded once in T, never an fma; there is no division and
+ * no fmin / fmax: selects only, spelled as below, so that what a NaN does is defined.  Per field x and axis the SLOPE of a cell,
+ * m / p its neighbours along that axis (periodic along i and j; along k the slope is +0 at k == 0 and at k == ktot-1):
+ *   a  = x - x[m];   b = x[p] - x;   t = a + b;   c0 = 0.5 * t
+ *   SPC_LIMITER_NONE:  s = c0
+ *   SPC_LIMITER_MC:    a2 = 2 * a;   b2 = 2 * b
+ *                      a > 0 && b > 0:  lo = a2 < b2 ? a2 : b2;   s = c0 < lo ? c0 : lo
+ *                      a < 0 && b < 0:  hi = a2 > b2 ? a2 : b2;   s = c0 > hi ? c0 : hi
+ *                      otherwise (an extremum, a zero or a NaN difference):  s = +0
+ * Every face adds to K22's donor flux a correction from the slope of its upwind cell, centred in time (si, sj, sk the slopes
+ * along i, j, k):
+ *   tw = 1 - pw;   gw = pw * tw;   uw = 1 + qw;   hw = qw * uw
+ *   m1 = gw * si[im];   m2 = hw * si[i];   dw = m1 - m2;   Aw = 0.5 * dw;   Fw2 = Fw + Aw
+ *   Ae = 0.5 * (pe * (1 - pe) * si[i] - qe * (1 + qe) * si[ip]),   As and An likewise with sj, each in the order of Aw
+ *   ct = pt * r[k];    dt = qt * r[kp];   gt = pt * (1 - ct);   ht = qt * (1 + dt)       the Courant number of the upwind cell
+ *   At = 0.5 * (gt * sk[k] - ht * (k+1 < ktot ? sk[k+1] : +0))
+ *   cb = pb * r[km];   db = qb * r[k];    gb = pb * (1 - cb);   hb = qb * (1 + db)
+ *   Ab = 0.5 * (gb * (k ? sk[k-1] : +0) - hb * sk[k])
+ *   out[f] = (x - ((Fe2 - Fw2) + (Fn2 - Fs2))) - r[l][k] * (Ft2 - Fb2)
+ *   ftop[f][l][i][j] = Ft2 at k = ktot-1
+ * As in K22 the two cells that share a face form its flux from the same operands in the same order (At of k is Ab of k+1, operand
+ * for operand; the slope of a neighbour is formed as the neighbour forms its own), so sum_ijk g x' + sum_ij ftop = sum_ijk g x to
+ * rounding, and a constant stays constant to rounding.  With SPC_LIMITER_MC and a Courant number of at most 1 a 1-D step creates no
+ * value outside the range of the cell and its two neighbours; SPC_LIMITER_NONE (Fromm's scheme) is second order and not
+ * monotone.  A cell reads x at distance up to 2 along each axis, 13 values per field; the neighbours of neighbours are periodic
+ * again (imm of itot = 3 is ip, of itot = 2 the cell itself), so an extent of 1 or 2 gives a = -b or 0 and a zero MC slope.  Along
+ * k every index is clamped before the load: nothing is read outside the field.  A NaN or an infinity of a field reaches at most
+ * two cells along each axis.  The slope is taken in INDEX space: on a stretched vertical grid the scheme stays conservative and
+ * limited, but is second order only where dz is uniform.  The refusals, the aliasing rules, the alignment, n_les == 0, the
+ * columns per workgroup and the largest ktot are K22's; a limiter other than the two below is SPC_ERR_INVALID_ARGUMENT.  The rule
+ * is this library's definition.                                                                         */
+#define SPC_LIMITER_NONE 0
+#define SPC_LIMITER_MC 1
+typedef struct spc_les_transport2_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_fields; /* n_fields 0 ... SPC_TRANSPORT_MAX_FIELDS                           */
+    const void *u, *v;                  /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *fields[SPC_TRANSPORT_MAX_FIELDS]; /* device [n_les][itot][jtot][ktot], read only             */
+    void *out[SPC_TRANSPORT_MAX_FIELDS];/* device [n_les][itot][jtot][ktot], written whole                   */
+    const void *hx, *hy;                /* device [n_les]: 0.5 dt / dx and 0.5 dt / dy                       */
+    void *cmax;                         /* device [n_les], or NULL                                           */
+    const void *g, *r;                  /* device [n_les x ktot] each, rows pitch_prof apart: rho dz, 1 / g  */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+    void *mtop;                         /* device [n_les][itot][jtot][ktot], written whole, or NULL          */
+    void *ftop;                         /* device [n_fields][n_les][itot][jtot], written whole, or NULL      */
+    int32_t limiter;                    /* SPC_LIMITER_NONE or SPC_LIMITER_MC                                */
+} spc_les_transport2_args;
+int spc_les_transport2_f64(const spc_les_transport2_args *args, void *stream);
+int spc_les_transport2_f32(const spc_les_transport2_args *args, void *stream);
+/* columns per workgroup of k_les_transport2 for ktot levels of elem_size (4 or 8) bytes: K22's; 0: unsupported */
+int spc_les_transport2_cols_per_block(int ktot, int elem_size);
+
 /* ---- longwave cooling and warming of the device-resident LES fields by their liquid water (kernel family K18) ----------------- */
 /* The first two terms of the GCSS / DYCOMS-II parametrised longwave flux (Stevens et al. 2005): the flux that the liquid water
  * above and below a face lets through, and the THL tendency of its divergence.  ql and thl are [n_les][itot][jtot][ktot] (layout

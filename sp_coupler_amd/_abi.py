@@ -179,6 +179,14 @@ class LesTransportArgs(ctypes.Structure):
                 + _ptrs("hx", "hy", "cmax", "g", "r") + [("pitch_prof", c_int64), ("mtop", c_void_p), ("ftop", c_void_p)])
 
 
+SPC_LIMITER_NONE, SPC_LIMITER_MC = 0, 1
+LIMITERS = {"none": SPC_LIMITER_NONE, "mc": SPC_LIMITER_MC}
+
+
+class LesTransport2Args(ctypes.Structure):
+    _fields_ = LesTransportArgs._fields_ + [("limiter", c_int32)]
+
+
 class LesRadiateArgs(ctypes.Structure):
     _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_tab", c_int32)]
                 + _ptrs("ql", "thl", "w", "c") + [("pitch_prof", c_int64)] + _ptrs("f0", "f1", "etab")
@@ -269,6 +277,9 @@ PROTOTYPES = {
     "spc_les_transport_f64": (ctypes.c_int, [ctypes.POINTER(LesTransportArgs), c_void_p]),
     "spc_les_transport_f32": (ctypes.c_int, [ctypes.POINTER(LesTransportArgs), c_void_p]),
     "spc_les_transport_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "spc_les_transport2_f64": (ctypes.c_int, [ctypes.POINTER(LesTransport2Args), c_void_p]),
+    "spc_les_transport2_f32": (ctypes.c_int, [ctypes.POINTER(LesTransport2Args), c_void_p]),
+    "spc_les_transport2_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_les_radiate_f64": (ctypes.c_int, [ctypes.POINTER(LesRadiateArgs), c_void_p]),
     "spc_les_radiate_f32": (ctypes.c_int, [ctypes.POINTER(LesRadiateArgs), c_void_p]),
     "spc_les_radiate_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),

@@ -18,7 +18,11 @@ rounding per operation, no fma, no division (include/spc.h is the definition):
     s  = ((pe - qw) + (pn - qs)) + r * (pt - qb)      the outflow Courant sum: x' is a convex combination where s <= 1
     ftop = Ft at the top level                        what left through the lid, in units of g x
 Both cells that share a face form its flux from the same operands, so sum(g x') + sum(ftop) = sum(g x) to rounding
-(``lid_budget``); a constant stays constant to rounding, not bit for bit."""
+(``lid_budget``); a constant stays constant to rounding, not bit for bit.
+
+K23 (``Engine.les_transport2``) is K22 with a second-order face value: every face adds to its donor flux a correction from
+the slope of its upwind cell, 0.5 * (p * (1 - p) * s[upwind of p] - q * (1 + q) * s[upwind of q]), the slope
+0.5 * ((x - x[m]) + (x[p] - x)) unlimited or MC-limited (include/spc.h); hx, hy, g, r, cmax, mtop and the budget are K22's."""
 import math
 
 import numpy

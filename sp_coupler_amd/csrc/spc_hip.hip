@@ -47,6 +47,9 @@
 //   K22 k_les_transport  one unsplit donor-cell step in flux form of the transport of those fields along i, j and k (K16's face
 //                  numbers, K17's chain and tile; every face flux formed alike by the two cells that share it, so the mass
 //                  of a field changes only through the lid): spc_transport.hpp, kernel and host side
+//   K23 k_les_transport2  K22's step with a second-order face value: every face adds to K22's donor flux a correction from the
+//                  (MC-limited or unlimited) slope of its upwind cell, centred in time; 13 values per cell and field for 7, the
+//                  same shared faces and lid budget: spc_transport2.hpp, kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -103,6 +106,7 @@ namespace {
 #include "spc_advect.hpp"
 #include "spc_vadvect.hpp"
 #include "spc_transport.hpp"
+#include "spc_transport2.hpp"
 #include "spc_radiate.hpp"
 #include "spc_qtlocal.hpp"
 #include "spc_moments.hpp"
@@ -141,6 +145,9 @@ namespace {
 #define SPC_TRANSPORT_HOST
 #include "spc_transport.hpp"
 #undef SPC_TRANSPORT_HOST
+#define SPC_TRANSPORT2_HOST
+#include "spc_transport2.hpp"
+#undef SPC_TRANSPORT2_HOST
 #define SPC_RADIATE_HOST
 #include "spc_radiate.hpp"
 #undef SPC_RADIATE_HOST
@@ -244,6 +251,9 @@ int spc_les_vadvect_cols_per_block(int ktot, int elem_size) { return vad_cols(kt
 int spc_les_transport_f64(const spc_les_transport_args *a, void *s) { return les_transport_impl<double>(a, s); }
 int spc_les_transport_f32(const spc_les_transport_args *a, void *s) { return les_transport_impl<float>(a, s); }
 int spc_les_transport_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
+int spc_les_transport2_f64(const spc_les_transport2_args *a, void *s) { return les_transport2_impl<double>(a, s); }
+int spc_les_transport2_f32(const spc_les_transport2_args *a, void *s) { return les_transport2_impl<float>(a, s); }
+int spc_les_transport2_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
 
 int spc_les_radiate_f64(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<double>(a, s); }
 int spc_les_radiate_f32(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<float>(a, s); }

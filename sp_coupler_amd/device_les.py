@@ -321,8 +321,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     advect_conservative = False                        # enable_advection(vertical=True, conservative=True): K22 is every substep
     _transport_ftop = None                             # what K22 writes per substep: [fields x n x itot x jtot], device
     _transport_lid = None                              # (the names of the transported fields, the sum of ftop over the substeps)
+    advect_order = 1                                   # enable_advection(..., conservative=True, order=2): K23 is every substep
+    advect_limiter = "mc"                              # the limiter of K23's slopes: "mc" or "none"
 
-    def enable_advection(self, dx=None, dy=None, cfl=None, max_substeps=None, vertical=False, conservative=False):
+    def enable_advection(self, dx=None, dy=None, cfl=None, max_substeps=None, vertical=False, conservative=False, order=1, limiter="mc"):
         """from now on every ``evolve_model_batched`` advects the fields among U, V, THL, QT and QR that exist with the winds U
         and V on the doubly periodic plane (K16, ``Engine.les_advect``), after the step and before K15 / K14 /
         K12: ONE probe launch per device finds the largest Courant sum c of the whole step, n_sub = max(1, ceil(c / cfl))
@@ -349,7 +351,13 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         into the spare buffers, then a swap: 1 + n_sub launches per device and step.  ``advect_courant`` holds the largest
         outflow sum of the substeps (RuntimeError where it is not finite), ``advect_courant_z`` is None,
         ``get_vertical_wind_batched()`` works from K22's mass flux and ``get_lid_flux_batched()`` returns what left through
-        the lid.  With the default every path, launch count and result is what it is without the argument."""
+        the lid.  With the default every path, launch count and result is what it is without the argument.
+
+        ``order=2`` (with ``conservative=True``; ValueError otherwise, for an order other than 1 or 2, for a ``limiter`` other
+        than ``"mc"`` or ``"none"``, or where the engine has no ``les_transport2``) gives every substep a second-order face value:
+        K23 (``Engine.les_transport2``) with the limiter in K22's place.  The probe stays K22's (the outflow Courant sums are
+        the same bits), the launch count stays 1 + n_sub, and everything else of the conservative mode is unchanged.  With the
+        default ``order=1`` every path, launch and bit is what it is without the argument."""
         if "U" not in self.fields3d or "V" not in self.fields3d:
             raise ValueError("the advection (K16) needs the fields U and V (set_fields_batched)")
         if not self._has("les_advect"):
@@ -360,6 +368,14 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             raise ValueError("the conservative transport (K22) is the horizontal and the vertical advection in one: it needs vertical=True")
         if conservative and not self._has("les_transport"):
             raise ValueError("the engine has no les_transport (K22)")
+        if order not in (1, 2):
+            raise ValueError("the order of the advection is 1 (donor cell) or 2 (K23), not %r" % (order,))
+        if limiter not in ("mc", "none"):
+            raise ValueError("the limiter of the second-order transport (K23) is 'mc' or 'none', not %r" % (limiter,))
+        if order == 2 and not conservative:
+            raise ValueError("the second-order transport (K23) is the conservative transport with another face value: it needs conservative=True")
+        if order == 2 and not self._has("les_transport2"):
+            raise ValueError("the engine has no les_transport2 (K23)")
         dx, dy = adv.DX if dx is None else dx, adv.DY if dy is None else dy
         adv.coefficients(1.0, dx, dy, n=self.n)                       # (ValueError for a spacing that is not positive, or not [n])
         self.dx = numpy.array(dx, dtype=numpy.float64) if numpy.ndim(dx) else float(dx)
@@ -372,6 +388,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         self.advect_vertical, self._vadvect_prof, self._vadvect_mtop, self._vadvect_dt = bool(vertical), None, None, None
         self.advect_courant_z = None
         self.advect_conservative, self._transport_ftop, self._transport_lid = bool(conservative), None, None
+        self.advect_order, self.advect_limiter = int(order), limiter
         self.buoyancy = False                                         # (K21 is enabled after, and for, the advection of this call)
 
     def _advect_coefs(self, dt, n_sub):
@@ -512,7 +529,11 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
                 am = eng.les_buoyancy(f["THL"], f["QT"], ql, f["U"], f["V"], hx, hy, *prof, self._buoyancy_phi)
                 worst_b = am if worst_b is None else self._per_device(torch.maximum, worst_b, am)
             out = {k: spare[k] for k in keys}
-            cm = eng.les_transport({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy, g, r, mtop=self._vadvect_mtop, ftop=ftop)
+            if self.advect_order == 2:
+                cm = eng.les_transport2({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy, g, r, limiter=self.advect_limiter,
+                                        mtop=self._vadvect_mtop, ftop=ftop)
+            else:
+                cm = eng.les_transport({k: f[k] for k in keys}, out, f["U"], f["V"], hx, hy, g, r, mtop=self._vadvect_mtop, ftop=ftop)
             for k in keys:
                 f[k], spare[k] = spare[k], f[k]
             worst = cm if worst is None else self._per_device(torch.maximum, worst, cm)
@@ -528,7 +549,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if not self.diffusion:                            # (else the QL field and the means follow the diffused fields: _diffuse)
             self._follow_fields()
         if not numpy.isfinite(self.advect_courant):
-            raise RuntimeError("the conservative transport (K22) found the Courant sum c = %r: the winds or the mass flux are not finite" % self.advect_courant)
+            raise RuntimeError("the conservative transport (%s) found the Courant sum c = %r: the winds or the mass flux are not finite"
+                               % ("K23" if self.advect_order == 2 else "K22", self.advect_courant))
         if buoyant and not numpy.isfinite(self.buoyancy_wind_change):
             raise RuntimeError("the pressure force (K21) found the wind change %r: the pressure is not finite" % self.buoyancy_wind_change)
 

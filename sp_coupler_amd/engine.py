@@ -1058,6 +1058,62 @@ class Engine:
         """columns of ``ktot`` levels a workgroup of K22 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
         return int(self.lib.spc_les_transport_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
 
+    # -- K23: second-order limited flux-form transport of device-resident LES fields, one launch ----------------------------------
+    @_on_engine_stream
+    def les_transport2(self, fields, out, u, v, hx, hy, g, r, limiter="mc", cmax=True, mtop=None, ftop=None, stream=None):
+        """``les_transport`` with a second-order face value (include/spc.h has the rule): every face adds to K22's donor flux a
+        correction from the slope of its upwind cell, ``limiter`` ``"mc"`` (monotonized central: no new extremum in 1-D) or
+        ``"none"`` (the unlimited slope); anything else is a ValueError.  Every argument, refusal and return value is
+        ``les_transport``'s; ``cmax`` and ``mtop`` are K22's bit for bit, ``ftop`` takes the second-order lid flux, and empty
+        ``fields`` are the same probe.  One launch; more levels than ``transport2_cols_per_block`` carries are refused."""
+        if limiter not in _abi.LIMITERS:
+            raise ValueError("les_transport2: limiter %r is none of %s" % (limiter, sorted(_abi.LIMITERS)))
+        names = list(fields)
+        if len(names) > _abi.SPC_TRANSPORT_MAX_FIELDS:
+            raise ValueError("les_transport2 takes at most %d fields per launch, got %d" % (_abi.SPC_TRANSPORT_MAX_FIELDS, len(names)))
+        if sorted(out) != sorted(names):
+            raise ValueError("les_transport2: out holds %s, the fields are %s" % (sorted(out), sorted(names)))
+        want = cmax is not None and cmax is not False
+        if not names and not want and mtop is None:
+            raise ValueError("les_transport2: no field, no cmax and no mtop: nothing to do")
+        if not names and ftop is not None:
+            raise ValueError("les_transport2: ftop without a field")
+        shape = tuple(self._field4("u", u).shape)
+        n, itot, jtot, ktot = (int(x) for x in shape)
+        if min(itot, jtot, ktot) < 1:
+            raise ValueError("les_transport2: empty field shape %s" % (shape,))
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.LesTransport2Args()
+        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields, a.limiter = n, itot, jtot, ktot, len(names), _abi.LIMITERS[limiter]
+        a.u, a.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
+        a.hx, a.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
+        a.g, a.pitch_prof = ck.mat("g", g, n, ktot)
+        a.r, _ = ck.mat("r", r, n, ktot, pitch=a.pitch_prof)
+        res = None
+        if want:
+            res = torch.empty(n, dtype=self.dtype, device=self.device) if cmax is True else cmax
+            a.cmax = ck.vec("cmax", res, n)
+        if mtop is not None:
+            a.mtop = self._field4("mtop", mtop, shape).data_ptr()
+        if ftop is not None:
+            a.ftop = self._field4("ftop", ftop, (len(names), n, itot, jtot)).data_ptr()
+        for f, name in enumerate(names):
+            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            a.out[f] = self._field4("out[%s]" % name, out[name], shape).data_ptr()
+        if n:
+            read = [t.data_ptr() for t in [u, v, hx, hy, g, r] + [fields[k] for k in names]]
+            written = ([out[k].data_ptr() for k in names] + ([res.data_ptr()] if want else [])
+                       + [t.data_ptr() for t in (mtop, ftop) if t is not None])
+            if len(set(written)) != len(written) or set(written) & set(read):
+                raise ValueError("les_transport2: an output is an input, cmax, mtop, ftop or another output")
+        fn = self.lib.spc_les_transport2_f32 if self.dtype == torch.float32 else self.lib.spc_les_transport2_f64
+        self._call(fn, ctypes.byref(a), stream=stream)
+        return res
+
+    def transport2_cols_per_block(self, ktot):
+        """columns of ``ktot`` levels a workgroup of K23 takes into LDS in the engine's dtype (K22's: 64, 32 or 16); 0: unsupported"""
+        return int(self.lib.spc_les_transport2_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+
     # -- K18: longwave cooling and warming of device-resident LES fields by their liquid water, one launch ------------------------
     @_on_engine_stream
     def les_radiate(self, ql, thl, w, c, f0, f1, *, flux=None, fsfc=None, stream=None):

@@ -290,6 +290,17 @@ class MultiDeviceEngine:
             return None
         return cmax if cmax is not True else self._join(res, ex.bounds)
 
+    def les_transport2(self, fields, out, u, v, hx, hy, g, r, limiter="mc", cmax=True, mtop=None, ftop=None, **kw):
+        """K23 on every device's LES: the arguments and the result of ``les_transport`` with the ``limiter`` of
+        ``Engine.les_transport2``; one launch per device that holds rows"""
+        ex = self._example(u)
+        if ex is None:
+            return self.primary.les_transport2(fields, out, u, v, hx, hy, g, r, limiter=limiter, cmax=cmax, mtop=mtop, ftop=ftop, **kw)
+        res = self._each("les_transport2", ex, (fields, out, u, v, hx, hy, g, r), dict(kw, limiter=limiter, cmax=cmax, mtop=mtop, ftop=ftop))
+        if cmax is None or cmax is False:
+            return None
+        return cmax if cmax is not True else self._join(res, ex.bounds)
+
     def les_radiate(self, ql, thl, w, c, f0, f1, *, flux=None, fsfc=None, **kw):
         """K18 on every device's LES: the Sharded fields ``ql`` and ``thl`` (updated in place, block by block), the Sharded
         profiles ``w`` and ``c`` [n x ktot], ``f0`` and ``f1`` [n] and ``flux`` / ``fsfc`` (or None) in; one launch per device

@@ -25,6 +25,8 @@ VADVECT_MUTANTS is the table of K17 (spc_vadvect.hpp), chosen with --vadvect; it
 tests/les_vadvect_ref.py, which tests/test_les_vadvect_gpu.py runs on the shipped library.
 TRANSPORT_MUTANTS is the table of K22 (spc_transport.hpp), chosen with --transport; its guards are the bodies of
 tests/les_transport_ref.py, which tests/test_les_transport_gpu.py runs on the shipped library.
+TRANSPORT2_MUTANTS is the table of K23 (spc_transport2.hpp), chosen with --transport2; its guards are the bodies of
+tests/les_transport2_ref.py, which tests/test_les_transport2_gpu.py runs on the shipped library.
 RADIATE_MUTANTS is the table of K18 (spc_radiate.hpp), chosen with --radiate; its guards are the bodies of
 tests/les_radiate_ref.py, which tests/test_les_radiate_gpu.py runs on the shipped library.
 QTLOCAL_MUTANTS is the table of K19 (spc_qtlocal.hpp), chosen with --qtlocal; its guards are the bodies of
@@ -57,6 +59,7 @@ usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py --moments --build && python tools/mutation_control.py --moments > profiles/mutation_control_moments.log
        python tools/mutation_control.py --buoyancy --build && python tools/mutation_control.py --buoyancy > profiles/mutation_control_buoyancy.log
        python tools/mutation_control.py --transport --build && python tools/mutation_control.py --transport > profiles/mutation_control_transport.log
+       python tools/mutation_control.py --transport2 --build && python tools/mutation_control.py --transport2 > profiles/mutation_control_transport2.log
        python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
        python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log
        python tools/mutation_control.py --vnudge --build && python tools/mutation_control.py --vnudge > profiles/mutation_control_vnudge.log"""
@@ -89,6 +92,7 @@ QTLOCAL = "spc_qtlocal.hpp"
 MOMENTS = "spc_moments.hpp"
 BUOYANCY = "spc_buoyancy.hpp"
 TRANSPORT = "spc_transport.hpp"
+TRANSPORT2 = "spc_transport2.hpp"
 GEO = "spc_geo.hpp"
 LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
@@ -914,6 +918,41 @@ TRANSPORT_MUTANTS = {
 }
 
 
+def transport2_body(name):
+    """guard of a K23 mutant: the body ``name`` of tests/les_transport2_ref.py on both engines (float64, float32) of the library"""
+    def guard(engine_of):
+        from tests import les_transport2_ref as lt2
+        failed = []
+        for dtype in lt2.DTYPES:
+            failed += lt2.check_everything(engine_of(dtype))
+        return name in failed, sorted(set(failed))
+    guard.__name__ = "les_transport2_ref." + name
+    return guard
+
+
+# K23 (spc_transport2.hpp), numbered on its own.  Every mutant only computes wrong numbers from values the shipped kernel loads
+# anyway: none changes an index that is loaded from or stored to, except mutant 8, whose imm becomes im, a row the cell reads
+# already; mutant 6 lets the top cell form a slope from x[km], x and x[kp], where kp is clamped to the cell itself.
+TRANSPORT2_MUTANTS = {
+    1: ("K23 Aw: si[i] for si[im] (the west face takes the slope of the cell downwind of it)", transport2_body("signs"),
+        [(TRANSPORT2, "const T Aw = trn2_hface<T>(pw, qw, siw, sic);", "const T Aw = trn2_hface<T>(pw, qw, sic, sic);")]),
+    2: ("K23 gw: 1 + pw for 1 - pw (the correction grows with the Courant number instead of vanishing at 1)", transport2_body("parity"),
+        [(TRANSPORT2, "const T tp = one - p;", "const T tp = one + p;")]),
+    3: ("K23 MC: 2 * a left out of the minimum (the limiter looks downwind only)", transport2_body("parity"),
+        [(TRANSPORT2, "const T lo = a2 < b2 ? a2 : b2;", "const T lo = b2;")]),
+    4: ("K23 MC: the extremum branch returns c0 (no limiting at an extremum)", transport2_body("special"),
+        [(TRANSPORT2, "    T s = zero;  ", "    T s = c0;    ")]),
+    5: ("K23 dt: r[k] for r[kp] (the downward flux takes the Courant number of the cell below the face)", transport2_body("rows"),
+        [(TRANSPORT2, "const T At = trn2_vface<T>(pt, qt, rk, rp, skc, skt);", "const T At = trn2_vface<T>(pt, qt, rk, rk, skc, skt);")]),
+    6: ("K23 sk: not zeroed at k == ktot - 1 (the top cell has a slope towards the lid)", transport2_body("parity"),
+        [(TRANSPORT2, "const bool inner = k > 0 && k + 1 < ktot;", "const bool inner = k > 0;")]),
+    7: ("K23 Fe2: Aw added to Fe (the east face takes the west face's correction)", transport2_body("fields"),
+        [(TRANSPORT2, "const T Fe2 = Fe + Ae;", "const T Fe2 = Fe + Aw;")]),
+    8: ("K23 imm: taken as im (the slope of the west neighbour looks at the neighbour itself)", transport2_body("alignment"),
+        [(TRANSPORT2, "const int imm = im ? im - 1 : itot - 1;", "const int imm = im;")]),
+}
+
+
 def _tag(table):
     """(library prefix, source directory prefix) of a table"""
     for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
@@ -921,7 +960,7 @@ def _tag(table):
                    (ADVECT_MUTANTS, ("advect_", "advect")), (VADVECT_MUTANTS, ("vadvect_", "vadvect")),
                    (RADIATE_MUTANTS, ("radiate_", "radiate")), (QTLOCAL_MUTANTS, ("qtlocal_", "qtlocal")),
                    (MOMENTS_MUTANTS, ("moments_", "moments")), (BUOYANCY_MUTANTS, ("buoyancy_", "buoyancy")),
-                   (TRANSPORT_MUTANTS, ("transport_", "transport")),
+                   (TRANSPORT_MUTANTS, ("transport_", "transport")), (TRANSPORT2_MUTANTS, ("transport2_", "transport2")),
                    (GEO_MUTANTS, ("geo_", "geo")),
                    (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
                    (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq")), (VNUDGE_MUTANTS, ("vnudge_", "vnudge"))):
@@ -1129,13 +1168,14 @@ if __name__ == "__main__":
     ap.add_argument("--moments", action="store_true", help="the table of K20 (MOMENTS_MUTANTS) instead of MUTANTS")
     ap.add_argument("--buoyancy", action="store_true", help="the table of K21 (BUOYANCY_MUTANTS) instead of MUTANTS")
     ap.add_argument("--transport", action="store_true", help="the table of K22 (TRANSPORT_MUTANTS) instead of MUTANTS")
+    ap.add_argument("--transport2", action="store_true", help="the table of K23 (TRANSPORT2_MUTANTS) instead of MUTANTS")
     ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
     ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
     ap.add_argument("--vnudge", action="store_true", help="the table of K6 (VNUDGE_MUTANTS) instead of MUTANTS")
     args = ap.parse_args()
     table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
              else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else RADIATE_MUTANTS if args.radiate
-             else QTLOCAL_MUTANTS if args.qtlocal else MOMENTS_MUTANTS if args.moments else BUOYANCY_MUTANTS if args.buoyancy else TRANSPORT_MUTANTS if args.transport else GEO_MUTANTS if args.geo
+             else QTLOCAL_MUTANTS if args.qtlocal else MOMENTS_MUTANTS if args.moments else BUOYANCY_MUTANTS if args.buoyancy else TRANSPORT_MUTANTS if args.transport else TRANSPORT2_MUTANTS if args.transport2 else GEO_MUTANTS if args.geo
              else LESSTATE_MUTANTS if args.lesstate else VNUDGE_MUTANTS if args.vnudge else MUTANTS)
     equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
     if args.build is not None:
@@ -1177,4 +1217,6 @@ if __name__ == "__main__":
         sys.exit(main_advance(only, MOMENTS_MUTANTS, "K20", "les_moments"))
     if args.transport:
         sys.exit(main_advance(only, TRANSPORT_MUTANTS, "K22", "les_transport"))
+    if args.transport2:
+        sys.exit(main_advance(only, TRANSPORT2_MUTANTS, "K23", "les_transport2"))
     sys.exit((main_advance if args.advance else main)(only))
