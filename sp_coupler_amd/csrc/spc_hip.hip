@@ -61,6 +61,7 @@
 // FP contraction OFF so no FMA changes a rounding: level indices are bit-exact, interpolated
 // values differ from the CPU only through pow().
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>

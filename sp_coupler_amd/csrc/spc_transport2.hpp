@@ -236,98 +236,32 @@ template <typename T, int NF, bool LIMITED> __global__ __launch_bounds__(TRN_THR
 
 #else  // SPC_TRANSPORT2_HOST ------------------------------------------------------------------------------------------------
 
-template <typename T, int NF, bool LIMITED> static int les_transport2_launch(const LesTransportP<T> &p, void *stream)
-{
-    const size_t smem = (size_t)p.cols * vad_pitch(p.ktot) * sizeof(T);
-    const int rc = ensure_lds(k_les_transport2<T, NF, LIMITED>, smem, "k_les_transport2");
-    if (rc) return rc;
-    const int64_t grid = (p.ncols + p.cols - 1) / p.cols;         // (checked against INT32_MAX by the caller, before cmax is zeroed)
-    hipLaunchKernelGGL((k_les_transport2<T, NF, LIMITED>), dim3((unsigned)grid), dim3(TRN_THREADS), smem, (hipStream_t)stream, p);
-    return launch_status("k_les_transport2");
-}
-
+// (the checks, the parameter block and the launch geometry are K17's: vad_family_args and vad_family_launch in spc_vadvect.hpp)
 template <typename T, bool LIMITED> static int les_transport2_fields(const LesTransportP<T> &p, int n_fields, void *stream)
 {
     switch (n_fields) {
-    case 0: return les_transport_launch<T, 0>(p, stream);         // K22's probe: the limiter has nothing to act on
-    case 1: return les_transport2_launch<T, 1, LIMITED>(p, stream);
-    case 2: return les_transport2_launch<T, 2, LIMITED>(p, stream);
-    case 3: return les_transport2_launch<T, 3, LIMITED>(p, stream);
-    case 4: return les_transport2_launch<T, 4, LIMITED>(p, stream);
-    case 5: return les_transport2_launch<T, 5, LIMITED>(p, stream);
-    default: return les_transport2_launch<T, 6, LIMITED>(p, stream);
+    case 0: return les_transport_probe<T>(p, stream);              // K22's probe: the limiter has nothing to act on
+    case 1: return vad_family_launch(k_les_transport2<T, 1, LIMITED>, "k_les_transport2", p, stream);
+    case 2: return vad_family_launch(k_les_transport2<T, 2, LIMITED>, "k_les_transport2", p, stream);
+    case 3: return vad_family_launch(k_les_transport2<T, 3, LIMITED>, "k_les_transport2", p, stream);
+    case 4: return vad_family_launch(k_les_transport2<T, 4, LIMITED>, "k_les_transport2", p, stream);
+    case 5: return vad_family_launch(k_les_transport2<T, 5, LIMITED>, "k_les_transport2", p, stream);
+    default: return vad_family_launch(k_les_transport2<T, 6, LIMITED>, "k_les_transport2", p, stream);
     }
+}
+
+static int les_transport2_limiter(const spc_les_transport2_args *a)
+{
+    if (a->limiter != SPC_LIMITER_NONE && a->limiter != SPC_LIMITER_MC)
+        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_transport2: limiter %lld is neither SPC_LIMITER_NONE nor SPC_LIMITER_MC", "", (long long)a->limiter);
+    return SPC_OK;
 }
 
 template <typename T> static int les_transport2_impl(const spc_les_transport2_args *a, void *stream)
 {
-    if (!a) return fail(SPC_ERR_INVALID_ARGUMENT, "%sargs is NULL");
-    int rc = slab_check_extents("les_transport2", a->n_les, a->itot, a->jtot, a->ktot);
-    if (rc) return rc;
-    if (a->n_fields < 0 || a->n_fields > SPC_TRANSPORT_MAX_FIELDS)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_transport2: field count %lld outside 0 ... %lld", "", (long long)a->n_fields, SPC_TRANSPORT_MAX_FIELDS);
-    if (a->limiter != SPC_LIMITER_NONE && a->limiter != SPC_LIMITER_MC)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_transport2: limiter %lld is neither SPC_LIMITER_NONE nor SPC_LIMITER_MC", "", (long long)a->limiter);
-    if (a->n_fields == 0 && !a->cmax && !a->mtop)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_transport2: no field, no cmax and no mtop: nothing to do");
-    if (a->pitch_prof < a->ktot)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_transport2: pitch_prof %lld smaller than ktot", "", (long long)a->pitch_prof);
-    if (a->n_les == 0) return SPC_OK;
-    REQUIRE(a->u, "u"); REQUIRE(a->v, "v"); REQUIRE(a->hx, "hx"); REQUIRE(a->hy, "hy"); REQUIRE(a->g, "g"); REQUIRE(a->r, "r");
     LesTransportP<T> p = {};
-    // (equal base pointers are what is detected, as in K22: partially overlapping views are the caller's to avoid)
-    const void *in[6 + SPC_TRANSPORT_MAX_FIELDS] = {a->u, a->v, a->hx, a->hy, a->g, a->r};
-    const void *wr[3 + SPC_TRANSPORT_MAX_FIELDS];
-    int n_in = 6, n_wr = 0;
-    uintptr_t bits = 0;
-    for (int f = 0; f < a->n_fields; ++f) {
-        REQUIRE(a->fields[f], "fields[f]");
-        REQUIRE(a->out[f], "out[f]");
-        in[n_in++] = a->fields[f];
-        p.field[f] = (const T *)a->fields[f];
-        p.out[f] = (T *)a->out[f];
-    }
-    for (int f = 0; f < a->n_fields; ++f) {
-        for (int q = 0; q < n_wr; ++q)
-            if (wr[q] == a->out[f])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_transport2: out[%lld] and out[%lld] are the same array", "", q, f);
-        for (int q = 0; q < n_in; ++q)
-            if (in[q] == a->out[f])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_transport2: out[%lld] is also an input (every cell reads its neighbours' old values)", "", f);
-        wr[n_wr++] = a->out[f];
-    }
-    void *ftop = a->n_fields ? a->ftop : nullptr;                 // (no field: nothing of ftop to write)
-    const void *extra[3] = {a->mtop, a->cmax, ftop};
-    static const char *const extra_name[3] = {"mtop", "cmax", "ftop"};
-    for (int x = 0; x < 3; ++x) {
-        if (!extra[x]) continue;
-        for (int q = 0; q < n_wr; ++q)
-            if (wr[q] == extra[x])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "les_transport2: %s is the same array as another output", extra_name[x]);
-        for (int q = 0; q < n_in; ++q)
-            if (in[q] == extra[x])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "les_transport2: %s is also an input (it is written while they are read)", extra_name[x]);
-        wr[n_wr++] = extra[x];
-    }
-    for (int q = 0; q < n_in; ++q) bits |= (uintptr_t)in[q];
-    for (int q = 0; q < n_wr; ++q) bits |= (uintptr_t)wr[q];
-    if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_transport2: a pointer is not aligned to its element type");
-    const int C = vad_cols(a->ktot, (int)sizeof(T));
-    if (!C)
-        return fail(SPC_ERR_UNSUPPORTED, "%sles_transport2: ktot %lld above the %lld levels of which 16 columns fit the LDS", "", (long long)a->ktot,
-                    (long long)(((HARD_LDS_BYTES / 16 / (int)sizeof(T)) - 1) | 1));
-    p.u = (const T *)a->u; p.v = (const T *)a->v; p.hx = (const T *)a->hx; p.hy = (const T *)a->hy;
-    p.g = (const T *)a->g; p.r = (const T *)a->r; p.cmax = (T *)a->cmax; p.mtop = (T *)a->mtop; p.ftop = (T *)ftop;
-    p.itot = a->itot; p.jtot = a->jtot; p.ktot = a->ktot;
-    p.nij = a->itot * a->jtot;
-    p.ncols = a->n_les * (int64_t)p.nij;
-    p.pitch_prof = a->pitch_prof;
-    p.cols = C;
-    if ((p.ncols + C - 1) / C > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_transport2: too many workgroups");
-    if (a->cmax && hipMemsetAsync(a->cmax, 0, (size_t)a->n_les * sizeof(T), (hipStream_t)stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SPC_ERR_LAUNCH, "%sles_transport2: cmax could not be zeroed");
-    }
+    const int rc = vad_family_args<T>("les_transport2", a, p, stream, les_transport2_limiter);
+    if (rc || !p.cols) return rc;
     return a->limiter == SPC_LIMITER_MC ? les_transport2_fields<T, true>(p, a->n_fields, stream) : les_transport2_fields<T, false>(p, a->n_fields, stream);
 }
 

@@ -213,34 +213,43 @@ template <typename T, int NF> __global__ __launch_bounds__(VAD_THREADS) void k_l
 
 #else  // SPC_VADVECT_HOST ---------------------------------------------------------------------------------------------------
 
-template <typename T, int NF> static int les_vadvect_launch(const LesVadvectP<T> &p, void *stream)
-{
-    const size_t smem = (size_t)p.cols * vad_pitch(p.ktot) * sizeof(T);
-    const int rc = ensure_lds(k_les_vadvect<T, NF>, smem, "k_les_vadvect");
-    if (rc) return rc;
-    const int64_t grid = (p.ncols + p.cols - 1) / p.cols;         // (checked against INT32_MAX by the caller, before cmax is zeroed)
-    hipLaunchKernelGGL((k_les_vadvect<T, NF>), dim3((unsigned)grid), dim3(VAD_THREADS), smem, (hipStream_t)stream, p);
-    return launch_status("k_les_vadvect");
-}
+// ---- the host path that K17, K22 and K23 share ----------------------------------------------------------------------------------
+// The three kernels take one tile (vad_cols, vad_pitch), one grid and the same arrays; their argument blocks are ONE layout that
+// grew at its end (K22 added ftop, K23 the limiter), which include/spc.h spells out three times.  The shared code reads the
+// members by name, so it does not depend on that, but the Python side builds the blocks from one another (_abi.py):
+#define VAD_SAME_OFFSET(m)                                                                                                 \
+    static_assert(offsetof(spc_les_vadvect_args, m) == offsetof(spc_les_transport_args, m) &&                             \
+                      offsetof(spc_les_transport_args, m) == offsetof(spc_les_transport2_args, m),                        \
+                  "spc_les_vadvect_args, spc_les_transport_args and spc_les_transport2_args disagree on " #m)
+VAD_SAME_OFFSET(n_les); VAD_SAME_OFFSET(itot); VAD_SAME_OFFSET(jtot); VAD_SAME_OFFSET(ktot); VAD_SAME_OFFSET(n_fields);
+VAD_SAME_OFFSET(u); VAD_SAME_OFFSET(v); VAD_SAME_OFFSET(fields); VAD_SAME_OFFSET(out); VAD_SAME_OFFSET(hx); VAD_SAME_OFFSET(hy);
+VAD_SAME_OFFSET(cmax); VAD_SAME_OFFSET(g); VAD_SAME_OFFSET(r); VAD_SAME_OFFSET(pitch_prof); VAD_SAME_OFFSET(mtop);
+#undef VAD_SAME_OFFSET
+static_assert(offsetof(spc_les_transport_args, ftop) == offsetof(spc_les_transport2_args, ftop), "spc_les_transport_args and spc_les_transport2_args disagree on ftop");
+static_assert(sizeof(spc_les_vadvect_args) == offsetof(spc_les_transport_args, ftop) && sizeof(spc_les_transport_args) == offsetof(spc_les_transport2_args, limiter),
+              "each argument block of the family is the one before it with members added at its end");
 
-template <typename T> static int les_vadvect_impl(const spc_les_vadvect_args *a, void *stream)
+// Every check of the argument block ``a`` of kernel ``name`` (the name in the texts of spc_last_error()), in the order a caller
+// can observe, then the parameter block ``p`` filled and cmax zeroed on ``stream``.  A is one of the three args structs, P the
+// kernel's LesVadvectP<T> / LesTransportP<T>; ftop is taken where A has one (every A but K17's).  ``more`` is a check of the
+// kernel's own that is made after the field count and before "nothing to do" (K23's limiter), or nullptr.  After SPC_OK the
+// caller launches its kernel -- unless p.cols is still 0: an ensemble without LES, for which no pointer was looked at.
+template <typename T, typename A, typename P> static int vad_family_args(const char *name, const A *a, P &p, void *stream, int (*more)(const A *) = nullptr)
 {
+    constexpr bool HAS_FTOP = !std::is_same<A, spc_les_vadvect_args>::value;
     if (!a) return fail(SPC_ERR_INVALID_ARGUMENT, "%sargs is NULL");
-    int rc = slab_check_extents("les_vadvect", a->n_les, a->itot, a->jtot, a->ktot);
+    int rc = slab_check_extents(name, a->n_les, a->itot, a->jtot, a->ktot);
     if (rc) return rc;
-    static_assert(SPC_VADVECT_MAX_FIELDS == VAD_MAXF, "include/spc.h and spc_vadvect.hpp disagree on the fields per launch");
-    if (a->n_fields < 0 || a->n_fields > SPC_VADVECT_MAX_FIELDS)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: field count %lld outside 0 ... %lld", "", (long long)a->n_fields, SPC_VADVECT_MAX_FIELDS);
-    if (a->n_fields == 0 && !a->cmax && !a->mtop)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: no field, no cmax and no mtop: nothing to do");
-    if (a->pitch_prof < a->ktot)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: pitch_prof %lld smaller than ktot", "", (long long)a->pitch_prof);
+    if (a->n_fields < 0 || a->n_fields > VAD_MAXF)
+        return fail(SPC_ERR_INVALID_ARGUMENT, "%s: field count %lld outside 0 ... %lld", name, (long long)a->n_fields, (long long)VAD_MAXF);
+    if (more && (rc = more(a)) != SPC_OK) return rc;
+    if (a->n_fields == 0 && !a->cmax && !a->mtop) return fail(SPC_ERR_INVALID_ARGUMENT, "%s: no field, no cmax and no mtop: nothing to do", name);
+    if (a->pitch_prof < a->ktot) return fail(SPC_ERR_INVALID_ARGUMENT, "%s: pitch_prof %lld smaller than ktot", name, (long long)a->pitch_prof);
     if (a->n_les == 0) return SPC_OK;
     REQUIRE(a->u, "u"); REQUIRE(a->v, "v"); REQUIRE(a->hx, "hx"); REQUIRE(a->hy, "hy"); REQUIRE(a->g, "g"); REQUIRE(a->r, "r");
-    LesVadvectP<T> p = {};
     // (equal base pointers are what is detected, as in K11, K14, K15 and K16: partially overlapping views are the caller's to avoid)
-    const void *in[6 + SPC_VADVECT_MAX_FIELDS] = {a->u, a->v, a->hx, a->hy, a->g, a->r};
-    const void *wr[2 + SPC_VADVECT_MAX_FIELDS];
+    const void *in[6 + VAD_MAXF] = {a->u, a->v, a->hx, a->hy, a->g, a->r};
+    const void *wr[3 + VAD_MAXF];
     int n_in = 6, n_wr = 0;
     uintptr_t bits = 0;
     for (int f = 0; f < a->n_fields; ++f) {
@@ -253,50 +262,74 @@ template <typename T> static int les_vadvect_impl(const spc_les_vadvect_args *a,
     for (int f = 0; f < a->n_fields; ++f) {
         for (int q = 0; q < n_wr; ++q)
             if (wr[q] == a->out[f])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: out[%lld] and out[%lld] are the same array", "", q, f);
+                return fail(SPC_ERR_INVALID_ARGUMENT, "%s: out[%lld] and out[%lld] are the same array", name, (long long)q, (long long)f);
         for (int q = 0; q < n_in; ++q)
             if (in[q] == a->out[f])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: out[%lld] is also an input (every cell reads its neighbours' old values)", "", f);
+                return fail(SPC_ERR_INVALID_ARGUMENT, "%s: out[%lld] is also an input (every cell reads its neighbours' old values)", name, (long long)f);
         wr[n_wr++] = a->out[f];
     }
-    const void *extra[2] = {a->mtop, a->cmax};
-    for (int x = 0; x < 2; ++x) {
+    void *ftop = nullptr;
+    if constexpr (HAS_FTOP) ftop = a->n_fields ? a->ftop : nullptr;   // (no field: nothing of ftop to write)
+    const void *extra[3] = {a->mtop, a->cmax, ftop};
+    static const char *const extra_name[3] = {"mtop", "cmax", "ftop"};
+    for (int x = 0; x < 3; ++x) {
         if (!extra[x]) continue;
+        char who[64];                                                 // "<kernel>: <array>": fail() takes one string
+        snprintf(who, sizeof(who), "%s: %s", name, extra_name[x]);
         for (int q = 0; q < n_wr; ++q)
-            if (wr[q] == extra[x])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "les_vadvect: %s is the same array as another output", x ? "cmax" : "mtop");
+            if (wr[q] == extra[x]) return fail(SPC_ERR_INVALID_ARGUMENT, "%s is the same array as another output", who);
         for (int q = 0; q < n_in; ++q)
-            if (in[q] == extra[x])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "les_vadvect: %s is also an input (it is written while they are read)", x ? "cmax" : "mtop");
+            if (in[q] == extra[x]) return fail(SPC_ERR_INVALID_ARGUMENT, "%s is also an input (it is written while they are read)", who);
         wr[n_wr++] = extra[x];
     }
     for (int q = 0; q < n_in; ++q) bits |= (uintptr_t)in[q];
     for (int q = 0; q < n_wr; ++q) bits |= (uintptr_t)wr[q];
-    if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vadvect: a pointer is not aligned to its element type");
+    if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%s: a pointer is not aligned to its element type", name);
     const int C = vad_cols(a->ktot, (int)sizeof(T));
     if (!C)
-        return fail(SPC_ERR_UNSUPPORTED, "%sles_vadvect: ktot %lld above the %lld levels of which 16 columns fit the LDS", "", (long long)a->ktot,
+        return fail(SPC_ERR_UNSUPPORTED, "%s: ktot %lld above the %lld levels of which 16 columns fit the LDS", name, (long long)a->ktot,
                     (long long)(((HARD_LDS_BYTES / 16 / (int)sizeof(T)) - 1) | 1));
     p.u = (const T *)a->u; p.v = (const T *)a->v; p.hx = (const T *)a->hx; p.hy = (const T *)a->hy;
     p.g = (const T *)a->g; p.r = (const T *)a->r; p.cmax = (T *)a->cmax; p.mtop = (T *)a->mtop;
+    if constexpr (HAS_FTOP) p.ftop = (T *)ftop;
     p.itot = a->itot; p.jtot = a->jtot; p.ktot = a->ktot;
     p.nij = a->itot * a->jtot;
     p.ncols = a->n_les * (int64_t)p.nij;
     p.pitch_prof = a->pitch_prof;
-    p.cols = C;
-    if ((p.ncols + C - 1) / C > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_vadvect: too many workgroups");
+    if ((p.ncols + C - 1) / C > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%s: too many workgroups", name);
     if (a->cmax && hipMemsetAsync(a->cmax, 0, (size_t)a->n_les * sizeof(T), (hipStream_t)stream) != hipSuccess) {
         (void)hipGetLastError();
-        return fail(SPC_ERR_LAUNCH, "%sles_vadvect: cmax could not be zeroed");
+        return fail(SPC_ERR_LAUNCH, "%s: cmax could not be zeroed", name);
     }
+    p.cols = C;
+    return SPC_OK;
+}
+
+// one workgroup of VAD_THREADS per p.cols columns, the tile of vad_pitch(ktot) elements per column in dynamic LDS
+template <typename K, typename P> static int vad_family_launch(K kernel, const char *kernel_name, const P &p, void *stream)
+{
+    const size_t smem = (size_t)p.cols * vad_pitch(p.ktot) * sizeof(*p.u);
+    const int rc = ensure_lds(kernel, smem, kernel_name);
+    if (rc) return rc;
+    const int64_t grid = (p.ncols + p.cols - 1) / p.cols;         // (checked against INT32_MAX by vad_family_args, before cmax is zeroed)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(VAD_THREADS), smem, (hipStream_t)stream, p);
+    return launch_status(kernel_name);
+}
+
+template <typename T> static int les_vadvect_impl(const spc_les_vadvect_args *a, void *stream)
+{
+    static_assert(SPC_VADVECT_MAX_FIELDS == VAD_MAXF, "include/spc.h and spc_vadvect.hpp disagree on the fields per launch");
+    LesVadvectP<T> p = {};
+    const int rc = vad_family_args<T>("les_vadvect", a, p, stream);
+    if (rc || !p.cols) return rc;
     switch (a->n_fields) {
-    case 0: return les_vadvect_launch<T, 0>(p, stream);
-    case 1: return les_vadvect_launch<T, 1>(p, stream);
-    case 2: return les_vadvect_launch<T, 2>(p, stream);
-    case 3: return les_vadvect_launch<T, 3>(p, stream);
-    case 4: return les_vadvect_launch<T, 4>(p, stream);
-    case 5: return les_vadvect_launch<T, 5>(p, stream);
-    default: return les_vadvect_launch<T, 6>(p, stream);
+    case 0: return vad_family_launch(k_les_vadvect<T, 0>, "k_les_vadvect", p, stream);
+    case 1: return vad_family_launch(k_les_vadvect<T, 1>, "k_les_vadvect", p, stream);
+    case 2: return vad_family_launch(k_les_vadvect<T, 2>, "k_les_vadvect", p, stream);
+    case 3: return vad_family_launch(k_les_vadvect<T, 3>, "k_les_vadvect", p, stream);
+    case 4: return vad_family_launch(k_les_vadvect<T, 4>, "k_les_vadvect", p, stream);
+    case 5: return vad_family_launch(k_les_vadvect<T, 5>, "k_les_vadvect", p, stream);
+    default: return vad_family_launch(k_les_vadvect<T, 6>, "k_les_vadvect", p, stream);
     }
 }
 

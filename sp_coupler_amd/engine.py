@@ -543,10 +543,7 @@ class Engine:
             self._vn_work = None
             self._vn_work = torch.empty(need, dtype=torch.uint8, device=self.device)
         a.work, a.work_bytes = self._vn_work.data_ptr(), self._vn_work.numel()
-        fn = self.lib.spc_variability_nudge_f32 if f32 else self.lib.spc_variability_nudge_f64
-        with torch.cuda.device(self.device):
-            rc = fn(ctypes.byref(a), _stream_ptr(stream if stream is not None else self.stream, self.device))
-        _abi.check(self.lib, rc)
+        self._call(self._sym("variability_nudge"), ctypes.byref(a), stream=stream)
         return res
 
     # -- K10: horizontal reductions of device-resident LES fields (les.get_profile_*, les.get_cloudfraction) ----------
@@ -561,6 +558,56 @@ class Engine:
                                 t.dtype, tuple(t.shape), t.device))
         return t
 
+    # -- one copy of what the K10 - K23 methods below have in common ---------------------------------------------------------------
+    @property
+    def _esize(self):
+        return 4 if self.dtype == torch.float32 else 8
+
+    def _sym(self, name):
+        """the library's entry point ``spc_<name>_f32`` / ``_f64`` of the engine's dtype"""
+        return getattr(self.lib, "spc_%s_%s" % (name, _DTYPES[self.dtype]))
+
+    def _geometry(self, name, *extents):
+        """what the library's ``spc_les_<name>(extents ..., element size)`` says of a launch at these extents in the engine's dtype"""
+        return int(getattr(self.lib, "spc_les_" + name)(*(int(x) for x in extents), self._esize))
+
+    def _extents(self, what, name, t):
+        """(n, itot, jtot, ktot) of the 4-D field ``t`` (``_field4``'s checks under ``name``); an empty plane or column is refused"""
+        shape = tuple(int(x) for x in self._field4(name, t).shape)
+        if min(shape[1:]) < 1:
+            raise ValueError("%s: empty field shape %s" % (what, shape))
+        return shape
+
+    def _plane(self, name, t, shape, dtype=None):
+        """``t``, a contiguous tensor of ``shape`` and ``dtype`` (default: the engine's) on the engine's device"""
+        dtype = dtype or self.dtype
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), self.device))
+        return t
+
+    def _largest(self, ck, name, want, n):
+        """the optional [n] output ``name``: a fresh tensor for True, the caller's (checked) tensor, None for False / None"""
+        if want is None or want is False:
+            return None
+        res = torch.empty(n, dtype=self.dtype, device=self.device) if want is True else want
+        ck.vec(name, res, n)
+        return res
+
+    @staticmethod
+    def _no_alias(text, written, read, n=1):
+        """refuse with ``text`` a written tensor that STARTS where a read tensor or another written one starts (None: not
+        given); views that overlap in part are not detected, and with ``n == 0`` nothing is"""
+        written = [t.data_ptr() for t in written if t is not None]
+        if n and (len(set(written)) != len(written) or set(written) & set(t.data_ptr() for t in read if t is not None)):
+            raise ValueError(text)
+
+    @staticmethod
+    def _same_pitch(what, p, pitch, n, others="the others"):
+        """the row pitch ``p`` of the output ``what``, which is the pitch of those before it (``pitch``; None: it is the first)"""
+        if pitch is not None and n > 1 and p != pitch:
+            raise ValueError("%s has row pitch %d, %s %d" % (what, p, others, pitch))
+        return p
+
     @_on_engine_stream
     def slab_means(self, fields, out=None, stream=None):
         """``{name: numpy.mean(field[l], axis=(0, 1)) for every LES l}`` of device fields [n x itot x jtot x ktot] of ONE
@@ -569,24 +616,18 @@ class Engine:
         names = list(fields)
         if not 1 <= len(names) <= _abi.SLAB_MAX_FIELDS:
             raise ValueError("slab_means takes 1 ... %d fields per launch, got %d" % (_abi.SLAB_MAX_FIELDS, len(names)))
-        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("slab_means: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("slab_means", names[0], fields[names[0]])
         a = _abi.SlabMeansArgs()
         a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
         res, pitch = {}, None
         for f, name in enumerate(names):
             a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
             o, p = self._out(None if out is None else out[name], n, ktot)
-            if pitch is not None and n > 1 and p != pitch:
-                raise ValueError("slab_means: out[%s] has row pitch %d, the others %d" % (name, p, pitch))
-            pitch = p
+            pitch = self._same_pitch("slab_means: out[%s]" % name, p, pitch, n)
             a.out[f] = o.data_ptr()
             res[name] = o
         a.pitch_out = pitch
-        fn = self.lib.spc_slab_means_f32 if self.dtype == torch.float32 else self.lib.spc_slab_means_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+        self._call(self._sym("slab_means"), ctypes.byref(a), stream=stream)
         return res
 
     @_on_engine_stream
@@ -594,9 +635,7 @@ class Engine:
         """les.get_cloudfraction(indices) (splib/spcpl.py:764-765) of every LES from its device-resident QL field
         [n x itot x jtot x ktot] and K2's index map ``idx`` [n x nG] int32 (``cloud_indices`` / the fused K1 output): the
         fraction of (i, j) columns with ql > 0 at some LES level of GCM layer r (include/spc.h), [n x nG], exact."""
-        n, itot, jtot, ktot = (int(x) for x in self._field4("ql", ql).shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("slab_cloud_fraction: empty field shape %s" % (tuple(ql.shape),))
+        n, itot, jtot, ktot = self._extents("slab_cloud_fraction", "ql", ql)
         if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.shape[0] != n:
             raise ValueError("idx must be an [n x nG] tensor with n = %d" % n)
         nG = int(idx.shape[1])
@@ -606,8 +645,7 @@ class Engine:
         a.idx, a.pitch_idx = ck.mat("idx", idx, n, nG, dtype=torch.int32)
         o, a.pitch_out = self._out(out, n, nG)
         a.ql, a.out = ql.data_ptr(), o.data_ptr()
-        fn = self.lib.spc_slab_cloud_fraction_f32 if self.dtype == torch.float32 else self.lib.spc_slab_cloud_fraction_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+        self._call(self._sym("slab_cloud_fraction"), ctypes.byref(a), stream=stream)
         return o
 
     # -- K11: one step of device-resident LES fields and the slab means of the stepped fields, one launch ---------------
@@ -635,10 +673,7 @@ class Engine:
             raise ValueError("les_advance: ql needs sat and qsat")
         if sat is not None and ql_mean and "QL" in fields:
             raise ValueError("les_advance: the mean of q is returned as 'QL', which is also the name of a field")
-        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_advance: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("les_advance", names[0], fields[names[0]])
         ck = _Checker(self.device, self.dtype)
         a = _abi.LesAdvanceArgs()
         a.n_les, a.itot, a.jtot, a.ktot, a.n_fields, a.dt = n, itot, jtot, ktot, len(names), float(dt)
@@ -648,9 +683,7 @@ class Engine:
         def mean_of(name):
             nonlocal pitch
             o, p = self._out(None if means is None or name not in means else means[name], n, ktot)
-            if pitch is not None and n > 1 and p != pitch:
-                raise ValueError("les_advance: means[%s] has row pitch %d, the others %d" % (name, p, pitch))
-            pitch = p
+            pitch = self._same_pitch("les_advance: means[%s]" % name, p, pitch, n)
             res[name] = o
             return o.data_ptr()
         for f, name in enumerate(names):
@@ -669,8 +702,7 @@ class Engine:
         a.pitch_mean = pitch
         if pitch_t is not None:
             a.pitch_tend = pitch_t
-        fn = self.lib.spc_les_advance_f32 if self.dtype == torch.float32 else self.lib.spc_les_advance_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+        self._call(self._sym("les_advance"), ctypes.byref(a), stream=stream)
         return res
 
     # -- K12: saturation adjustment of device-resident LES fields and the slab means of QL and T, one launch -------------
@@ -686,10 +718,7 @@ class Engine:
         ``table_mode``: ``_abi.THERMO_TABLE_*`` (0: the library's choice).  One launch; ktot == 1 is refused
         (SPC_ERR_UNSUPPORTED)."""
         from . import thermo
-        shape = tuple(self._field4("thl", thl).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_thermo: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("les_thermo", "thl", thl)
         n_iter = thermo.DEFAULT_N_ITER if n_iter is None else int(n_iter)
         if n_iter < 0:
             raise ValueError("les_thermo: n_iter = %d < 0" % n_iter)
@@ -714,11 +743,9 @@ class Engine:
                 raise ValueError("les_thermo: means of %s are not computed (QL and T are)" % unknown)
             res["QL"], pitch = self._out(given.get("QL"), n, ktot)
             res["T"], pitch_t = self._out(given.get("T"), n, ktot)
-            if n > 1 and pitch != pitch_t:
-                raise ValueError("les_thermo: means[T] has row pitch %d, means[QL] %d" % (pitch_t, pitch))
+            self._same_pitch("les_thermo: means[T]", pitch_t, pitch, n, others="means[QL]")
             a.ql_mean, a.t_mean, a.pitch_mean = res["QL"].data_ptr(), res["T"].data_ptr(), pitch
-        fn = self.lib.spc_les_thermo_f32 if self.dtype == torch.float32 else self.lib.spc_les_thermo_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+        self._call(self._sym("les_thermo"), ctypes.byref(a), stream=stream)
         return res
 
     # -- K13: column water paths, cloud top and cloud cover of device-resident LES fields, one launch ---------------------
@@ -741,10 +768,7 @@ class Engine:
             raise ValueError("les_water_paths: %s need cloud (the name of a field)" % " and ".join(wants))
         if cloud is not None and cloud not in fields:
             raise ValueError("les_water_paths: cloud = %r is not one of the fields %s" % (cloud, names))
-        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_water_paths: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("les_water_paths", names[0], fields[names[0]])
         ck = _Checker(self.device, self.dtype)
         a = _abi.WaterPathArgs()
         a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
@@ -753,9 +777,7 @@ class Engine:
         def plane(name, t, dtype, shp):
             if t is None or t is True:
                 return torch.empty(shp, dtype=dtype, device=self.device)
-            if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype or tuple(t.shape) != shp or not t.is_contiguous():
-                raise ValueError("les_water_paths: %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shp, self.device))
-            return t
+            return self._plane("les_water_paths: " + name, t, shp, dtype)
         res = {}
         for f, name in enumerate(names):
             a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
@@ -770,12 +792,9 @@ class Engine:
             if "cover" in wants:
                 res["cover"] = plane("cover", cover, self.dtype, (n,))
                 a.cover = res["cover"].data_ptr()
-        ptrs = [t.data_ptr() for t in res.values() if t.numel()]
-        ins = [fields[k].data_ptr() for k in names] + [w.data_ptr()]
-        if len(set(ptrs)) != len(ptrs) or set(ptrs) & set(ins):
-            raise ValueError("les_water_paths: an output is an input or another output")
-        fn = self.lib.spc_les_water_paths_f32 if self.dtype == torch.float32 else self.lib.spc_les_water_paths_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+        self._no_alias("les_water_paths: an output is an input or another output", [t for t in res.values() if t.numel()],
+                       [fields[k] for k in names] + [w])
+        self._call(self._sym("les_water_paths"), ctypes.byref(a), stream=stream)
         return res
 
     # -- K14: warm-rain microphysics of device-resident LES fields and the slab means of what it changes, one launch ------
@@ -794,10 +813,7 @@ class Engine:
         STARTS where another argument starts is refused (ValueError); views that overlap in part are not detected.  One launch; ktot == 1 is
         refused (SPC_ERR_UNSUPPORTED)."""
         from . import microphysics as mp
-        shape = tuple(self._field4("qt", qt).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_microphysics: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("les_microphysics", "qt", qt)
         ck = _Checker(self.device, self.dtype)
         a = _abi.LesMicroArgs()
         a.n_les, a.itot, a.jtot, a.ktot, a.dt = n, itot, jtot, ktot, float(dt)
@@ -816,10 +832,7 @@ class Engine:
             ptr, _ = ck.mat(name, profs[name], n, ktot, pitch=a.pitch_prof)
             setattr(a, name, ptr)
         if rain is not None:
-            if not isinstance(rain, torch.Tensor) or rain.device != self.device or rain.dtype != self.dtype or \
-                    tuple(rain.shape) != (n, itot, jtot) or not rain.is_contiguous():
-                raise ValueError("les_microphysics: rain must be a contiguous %s tensor of shape %s on %s" % (self.dtype, (n, itot, jtot), self.device))
-            a.rain = rain.data_ptr()
+            a.rain = self._plane("les_microphysics: rain", rain, (n, itot, jtot)).data_ptr()
         res, a.pitch_mean = {}, ktot
         if means is not False and means is not None:
             given = means if isinstance(means, dict) else {}
@@ -830,18 +843,12 @@ class Engine:
             pitch = None
             for k in names:
                 res[k], p = self._out(given.get(k), n, ktot)
-                if pitch is not None and n > 1 and p != pitch:
-                    raise ValueError("les_microphysics: means[%s] has row pitch %d, the others %d" % (k, p, pitch))
-                pitch = p
+                pitch = self._same_pitch("les_microphysics: means[%s]" % k, p, pitch, n)
                 setattr(a, {"QT": "qt_mean", "QR": "qr_mean", "THL": "thl_mean", "QI": "qi_mean"}[k], res[k].data_ptr())
             a.pitch_mean = pitch
-        if n:
-            written = [t.data_ptr() for t in [qt, qr_new, thl, rain] + list(res.values()) if t is not None]
-            read = [t.data_ptr() for t in [ql, qr, temp] + list(profs.values()) if t is not None]
-            if len(set(written)) != len(written) or set(written) & set(read):
-                raise ValueError("les_microphysics: a written array is an input or another written array (qr_new must not be qr)")
-        fn = self.lib.spc_les_microphysics_f32 if self.dtype == torch.float32 else self.lib.spc_les_microphysics_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+        self._no_alias("les_microphysics: a written array is an input or another written array (qr_new must not be qr)",
+                       [qt, qr_new, thl, rain] + list(res.values()), [ql, qr, temp] + list(profs.values()), n)
+        self._call(self._sym("les_microphysics"), ctypes.byref(a), stream=stream)
         return res
 
     # -- K15: implicit vertical diffusion of device-resident LES fields with the surface fluxes, one launch -----------------
@@ -864,10 +871,7 @@ class Engine:
         flux = {k: v for k, v in flux.items() if v is not None}
         if flux and s0 is None:
             raise ValueError("les_diffuse: a flux needs s0")
-        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_diffuse: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("les_diffuse", names[0], fields[names[0]])
         ck = _Checker(self.device, self.dtype)
         g = _abi.LesDiffuseArgs()
         g.n_les, g.itot, g.jtot, g.ktot, g.n_fields = n, itot, jtot, ktot, len(names)
@@ -883,16 +887,12 @@ class Engine:
             if name in flux:
                 g.flux[f] = ck.vec("flux[%s]" % name, flux[name], n)
                 read.append(flux[name])
-        if n:
-            written = [fields[k].data_ptr() for k in names]
-            if len(set(written)) != len(written) or set(written) & set(t.data_ptr() for t in read):
-                raise ValueError("les_diffuse: a field is another field, a profile, s0 or a flux")
-        fn = self.lib.spc_les_diffuse_f32 if self.dtype == torch.float32 else self.lib.spc_les_diffuse_f64
-        self._call(fn, ctypes.byref(g), stream=stream)
+        self._no_alias("les_diffuse: a field is another field, a profile, s0 or a flux", [fields[k] for k in names], read, n)
+        self._call(self._sym("les_diffuse"), ctypes.byref(g), stream=stream)
 
     def diffuse_cols_per_block(self, ktot):
         """columns of ``ktot`` levels a workgroup of K15 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
-        return int(self.lib.spc_les_diffuse_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+        return self._geometry("diffuse_cols_per_block", ktot)
 
     # -- K16: horizontal upwind advection of device-resident LES fields on the periodic plane, one launch ----------------------
     @_on_engine_stream
@@ -905,43 +905,57 @@ class Engine:
         every LES, or None.  ``fields`` may be empty with a ``cmax``: the probe, which reads the winds only.  An ``out`` that
         STARTS where an input, ``cmax`` or another ``out`` starts is refused (ValueError); views that overlap in part are not
         detected.  One launch."""
+        return self._les_transport_step("les_advect", _abi.LesAdvectArgs, _abi.SPC_ADVECT_MAX_FIELDS, fields, out, u, v, hx, hy, None, cmax, {},
+                                        None, stream)
+
+    def _les_transport_step(self, name, args, cap, fields, out, u, v, hx, hy, profiles, cmax, extras, limiter, stream):
+        """the one body of ``les_advect``, ``les_vadvect``, ``les_transport`` and ``les_transport2``: ``name`` is the public
+        method's (in every message, and ``spc_<name>_*`` is the library's symbol), ``args`` the class of its argument block,
+        ``cap`` its fields per launch, ``profiles`` (g, r) or None for a kernel without them, ``extras`` the optional written
+        tensors beyond ``cmax`` in the block's order ({"mtop": ...} / {"mtop": ..., "ftop": ...}; None: not given), ``limiter`` the
+        code of the block's limiter or None for a kernel without one.  Returns ``cmax``'s tensor or None."""
         names = list(fields)
-        if len(names) > _abi.SPC_ADVECT_MAX_FIELDS:
-            raise ValueError("les_advect takes at most %d fields per launch, got %d" % (_abi.SPC_ADVECT_MAX_FIELDS, len(names)))
+        if len(names) > cap:
+            raise ValueError("%s takes at most %d fields per launch, got %d" % (name, cap, len(names)))
         if sorted(out) != sorted(names):
-            raise ValueError("les_advect: out holds %s, the fields are %s" % (sorted(out), sorted(names)))
+            raise ValueError("%s: out holds %s, the fields are %s" % (name, sorted(out), sorted(names)))
         want = cmax is not None and cmax is not False
-        if not names and not want:
-            raise ValueError("les_advect: no field and no cmax: nothing to do")
-        shape = tuple(self._field4("u", u).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_advect: empty field shape %s" % (shape,))
+        if not names and not want and extras.get("mtop") is None:
+            probes = ["field", "cmax"] + [k for k in extras if k == "mtop"]               # what a launch without a field can be for
+            raise ValueError("%s: no %s and no %s: nothing to do" % (name, ", no ".join(probes[:-1]), probes[-1]))
+        if not names and extras.get("ftop") is not None:
+            raise ValueError("%s: ftop without a field" % name)
+        shape = n, itot, jtot, ktot = self._extents(name, "u", u)
         ck = _Checker(self.device, self.dtype)
-        g = _abi.LesAdvectArgs()
-        g.n_les, g.itot, g.jtot, g.ktot, g.n_fields = n, itot, jtot, ktot, len(names)
-        g.u, g.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
-        g.hx, g.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
-        res = None
+        a = args()
+        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
+        if limiter is not None:
+            a.limiter = limiter
+        a.u, a.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
+        a.hx, a.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
+        read = [u, v, hx, hy]
+        if profiles is not None:
+            g, r = profiles
+            a.g, a.pitch_prof = ck.mat("g", g, n, ktot)
+            a.r, _ = ck.mat("r", r, n, ktot, pitch=a.pitch_prof)
+            read += [g, r]
+        res = self._largest(ck, "cmax", cmax, n)
         if want:
-            res = torch.empty(n, dtype=self.dtype, device=self.device) if cmax is True else cmax
-            g.cmax = ck.vec("cmax", res, n)
-        for f, name in enumerate(names):
-            g.fields[f] = self._field4(name, fields[name], shape).data_ptr()
-            g.out[f] = self._field4("out[%s]" % name, out[name], shape).data_ptr()
-        if n:
-            read = [t.data_ptr() for t in [u, v, hx, hy] + [fields[k] for k in names]]
-            written = [out[k].data_ptr() for k in names] + ([res.data_ptr()] if want else [])
-            if len(set(written)) != len(written) or set(written) & set(read):
-                raise ValueError("les_advect: an output is an input, cmax or another output")
-        fn = self.lib.spc_les_advect_f32 if self.dtype == torch.float32 else self.lib.spc_les_advect_f64
-        self._call(fn, ctypes.byref(g), stream=stream)
+            a.cmax = res.data_ptr()
+        for k, t in extras.items():
+            if t is not None:
+                setattr(a, k, self._field4(k, t, shape if k == "mtop" else (len(names), n, itot, jtot)).data_ptr())
+        for f, k in enumerate(names):
+            a.fields[f] = self._field4(k, fields[k], shape).data_ptr()
+            a.out[f] = self._field4("out[%s]" % k, out[k], shape).data_ptr()
+        self._no_alias("%s: an output is an input, %s or another output" % (name, ", ".join(["cmax"] + list(extras))),
+                       [out[k] for k in names] + [res] + list(extras.values()), read + [fields[k] for k in names], n)
+        self._call(self._sym(name), ctypes.byref(a), stream=stream)
         return res
 
     def advect_strip(self, n, itot, jtot, ktot):
         """(cells of the run [jtot x ktot] of one row i, rows i) a workgroup of K16 owns at these extents in the engine's dtype"""
-        return (int(self.lib.spc_les_advect_strip(int(jtot), int(ktot), 4 if self.dtype == torch.float32 else 8)),
-                int(self.lib.spc_les_advect_rows(int(n), int(itot), int(jtot), int(ktot))))
+        return self._geometry("advect_strip", jtot, ktot), int(self.lib.spc_les_advect_rows(int(n), int(itot), int(jtot), int(ktot)))
 
     # -- K17: vertical upwind advection of device-resident LES fields from continuity, one launch ---------------------------------
     @_on_engine_stream
@@ -957,46 +971,12 @@ class Engine:
         the probe.  A written tensor that STARTS where an input or another written tensor starts is refused (ValueError);
         views that overlap in part are not detected.  One launch; more levels than ``vadvect_cols_per_block`` carries are
         refused (SPC_ERR_UNSUPPORTED)."""
-        names = list(fields)
-        if len(names) > _abi.SPC_VADVECT_MAX_FIELDS:
-            raise ValueError("les_vadvect takes at most %d fields per launch, got %d" % (_abi.SPC_VADVECT_MAX_FIELDS, len(names)))
-        if sorted(out) != sorted(names):
-            raise ValueError("les_vadvect: out holds %s, the fields are %s" % (sorted(out), sorted(names)))
-        want = cmax is not None and cmax is not False
-        if not names and not want and mtop is None:
-            raise ValueError("les_vadvect: no field, no cmax and no mtop: nothing to do")
-        shape = tuple(self._field4("u", u).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_vadvect: empty field shape %s" % (shape,))
-        ck = _Checker(self.device, self.dtype)
-        a = _abi.LesVadvectArgs()
-        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
-        a.u, a.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
-        a.hx, a.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
-        a.g, a.pitch_prof = ck.mat("g", g, n, ktot)
-        a.r, _ = ck.mat("r", r, n, ktot, pitch=a.pitch_prof)
-        res = None
-        if want:
-            res = torch.empty(n, dtype=self.dtype, device=self.device) if cmax is True else cmax
-            a.cmax = ck.vec("cmax", res, n)
-        if mtop is not None:
-            a.mtop = self._field4("mtop", mtop, shape).data_ptr()
-        for f, name in enumerate(names):
-            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
-            a.out[f] = self._field4("out[%s]" % name, out[name], shape).data_ptr()
-        if n:
-            read = [t.data_ptr() for t in [u, v, hx, hy, g, r] + [fields[k] for k in names]]
-            written = [out[k].data_ptr() for k in names] + ([res.data_ptr()] if want else []) + ([mtop.data_ptr()] if mtop is not None else [])
-            if len(set(written)) != len(written) or set(written) & set(read):
-                raise ValueError("les_vadvect: an output is an input, cmax, mtop or another output")
-        fn = self.lib.spc_les_vadvect_f32 if self.dtype == torch.float32 else self.lib.spc_les_vadvect_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
-        return res
+        return self._les_transport_step("les_vadvect", _abi.LesVadvectArgs, _abi.SPC_VADVECT_MAX_FIELDS, fields, out, u, v, hx, hy, (g, r), cmax,
+                                        {"mtop": mtop}, None, stream)
 
     def vadvect_cols_per_block(self, ktot):
         """columns of ``ktot`` levels a workgroup of K17 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
-        return int(self.lib.spc_les_vadvect_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+        return self._geometry("vadvect_cols_per_block", ktot)
 
     # -- K22: conservative flux-form transport of device-resident LES fields along i, j and k, one launch -------------------------
     @_on_engine_stream
@@ -1012,51 +992,12 @@ class Engine:
         units of g x, or None.  ``fields`` may be empty with ``cmax`` and / or ``mtop``: the probe.  A written tensor that
         STARTS where an input or another written tensor starts is refused (ValueError); views that overlap in part are not
         detected.  One launch; more levels than ``transport_cols_per_block`` carries are refused (SPC_ERR_UNSUPPORTED)."""
-        names = list(fields)
-        if len(names) > _abi.SPC_TRANSPORT_MAX_FIELDS:
-            raise ValueError("les_transport takes at most %d fields per launch, got %d" % (_abi.SPC_TRANSPORT_MAX_FIELDS, len(names)))
-        if sorted(out) != sorted(names):
-            raise ValueError("les_transport: out holds %s, the fields are %s" % (sorted(out), sorted(names)))
-        want = cmax is not None and cmax is not False
-        if not names and not want and mtop is None:
-            raise ValueError("les_transport: no field, no cmax and no mtop: nothing to do")
-        if not names and ftop is not None:
-            raise ValueError("les_transport: ftop without a field")
-        shape = tuple(self._field4("u", u).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_transport: empty field shape %s" % (shape,))
-        ck = _Checker(self.device, self.dtype)
-        a = _abi.LesTransportArgs()
-        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
-        a.u, a.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
-        a.hx, a.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
-        a.g, a.pitch_prof = ck.mat("g", g, n, ktot)
-        a.r, _ = ck.mat("r", r, n, ktot, pitch=a.pitch_prof)
-        res = None
-        if want:
-            res = torch.empty(n, dtype=self.dtype, device=self.device) if cmax is True else cmax
-            a.cmax = ck.vec("cmax", res, n)
-        if mtop is not None:
-            a.mtop = self._field4("mtop", mtop, shape).data_ptr()
-        if ftop is not None:
-            a.ftop = self._field4("ftop", ftop, (len(names), n, itot, jtot)).data_ptr()
-        for f, name in enumerate(names):
-            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
-            a.out[f] = self._field4("out[%s]" % name, out[name], shape).data_ptr()
-        if n:
-            read = [t.data_ptr() for t in [u, v, hx, hy, g, r] + [fields[k] for k in names]]
-            written = ([out[k].data_ptr() for k in names] + ([res.data_ptr()] if want else [])
-                       + [t.data_ptr() for t in (mtop, ftop) if t is not None])
-            if len(set(written)) != len(written) or set(written) & set(read):
-                raise ValueError("les_transport: an output is an input, cmax, mtop, ftop or another output")
-        fn = self.lib.spc_les_transport_f32 if self.dtype == torch.float32 else self.lib.spc_les_transport_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
-        return res
+        return self._les_transport_step("les_transport", _abi.LesTransportArgs, _abi.SPC_TRANSPORT_MAX_FIELDS, fields, out, u, v, hx, hy, (g, r), cmax,
+                                        {"mtop": mtop, "ftop": ftop}, None, stream)
 
     def transport_cols_per_block(self, ktot):
         """columns of ``ktot`` levels a workgroup of K22 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
-        return int(self.lib.spc_les_transport_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+        return self._geometry("transport_cols_per_block", ktot)
 
     # -- K23: second-order limited flux-form transport of device-resident LES fields, one launch ----------------------------------
     @_on_engine_stream
@@ -1068,51 +1009,12 @@ class Engine:
         ``fields`` are the same probe.  One launch; more levels than ``transport2_cols_per_block`` carries are refused."""
         if limiter not in _abi.LIMITERS:
             raise ValueError("les_transport2: limiter %r is none of %s" % (limiter, sorted(_abi.LIMITERS)))
-        names = list(fields)
-        if len(names) > _abi.SPC_TRANSPORT_MAX_FIELDS:
-            raise ValueError("les_transport2 takes at most %d fields per launch, got %d" % (_abi.SPC_TRANSPORT_MAX_FIELDS, len(names)))
-        if sorted(out) != sorted(names):
-            raise ValueError("les_transport2: out holds %s, the fields are %s" % (sorted(out), sorted(names)))
-        want = cmax is not None and cmax is not False
-        if not names and not want and mtop is None:
-            raise ValueError("les_transport2: no field, no cmax and no mtop: nothing to do")
-        if not names and ftop is not None:
-            raise ValueError("les_transport2: ftop without a field")
-        shape = tuple(self._field4("u", u).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_transport2: empty field shape %s" % (shape,))
-        ck = _Checker(self.device, self.dtype)
-        a = _abi.LesTransport2Args()
-        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields, a.limiter = n, itot, jtot, ktot, len(names), _abi.LIMITERS[limiter]
-        a.u, a.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
-        a.hx, a.hy = ck.vec("hx", hx, n), ck.vec("hy", hy, n)
-        a.g, a.pitch_prof = ck.mat("g", g, n, ktot)
-        a.r, _ = ck.mat("r", r, n, ktot, pitch=a.pitch_prof)
-        res = None
-        if want:
-            res = torch.empty(n, dtype=self.dtype, device=self.device) if cmax is True else cmax
-            a.cmax = ck.vec("cmax", res, n)
-        if mtop is not None:
-            a.mtop = self._field4("mtop", mtop, shape).data_ptr()
-        if ftop is not None:
-            a.ftop = self._field4("ftop", ftop, (len(names), n, itot, jtot)).data_ptr()
-        for f, name in enumerate(names):
-            a.fields[f] = self._field4(name, fields[name], shape).data_ptr()
-            a.out[f] = self._field4("out[%s]" % name, out[name], shape).data_ptr()
-        if n:
-            read = [t.data_ptr() for t in [u, v, hx, hy, g, r] + [fields[k] for k in names]]
-            written = ([out[k].data_ptr() for k in names] + ([res.data_ptr()] if want else [])
-                       + [t.data_ptr() for t in (mtop, ftop) if t is not None])
-            if len(set(written)) != len(written) or set(written) & set(read):
-                raise ValueError("les_transport2: an output is an input, cmax, mtop, ftop or another output")
-        fn = self.lib.spc_les_transport2_f32 if self.dtype == torch.float32 else self.lib.spc_les_transport2_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
-        return res
+        return self._les_transport_step("les_transport2", _abi.LesTransport2Args, _abi.SPC_TRANSPORT_MAX_FIELDS, fields, out, u, v, hx, hy, (g, r), cmax,
+                                        {"mtop": mtop, "ftop": ftop}, _abi.LIMITERS[limiter], stream)
 
     def transport2_cols_per_block(self, ktot):
         """columns of ``ktot`` levels a workgroup of K23 takes into LDS in the engine's dtype (K22's: 64, 32 or 16); 0: unsupported"""
-        return int(self.lib.spc_les_transport2_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+        return self._geometry("transport2_cols_per_block", ktot)
 
     # -- K18: longwave cooling and warming of device-resident LES fields by their liquid water, one launch ------------------------
     @_on_engine_stream
@@ -1127,10 +1029,7 @@ class Engine:
         (ValueError); views that overlap in part are not detected.  One launch; more levels than ``radiate_cols_per_block``
         carries are refused (SPC_ERR_UNSUPPORTED)."""
         from . import radiation
-        shape = tuple(self._field4("ql", ql).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_radiate: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("les_radiate", "ql", ql)
         if self._exp_tab is None:
             self._exp_tab = torch.from_numpy(radiation.exp_table(self.dtype)).to(self.device)
         ck = _Checker(self.device, self.dtype)
@@ -1141,27 +1040,16 @@ class Engine:
         a.c, _ = ck.mat("c", c, n, ktot, pitch=a.pitch_prof)
         a.f0, a.f1 = ck.vec("f0", f0, n), ck.vec("f1", f1, n)
         a.etab, a.n_tab, a.inv_step = self._exp_tab.data_ptr(), int(self._exp_tab.numel()), radiation.INV_STEP
-        written = [thl]
         if flux is not None:
             a.flux = self._field4("flux", flux, shape).data_ptr()
-            written.append(flux)
         if fsfc is not None:
-            if not isinstance(fsfc, torch.Tensor) or fsfc.device != self.device or fsfc.dtype != self.dtype or \
-                    tuple(fsfc.shape) != (n, itot, jtot) or not fsfc.is_contiguous():
-                raise ValueError("les_radiate: fsfc must be a contiguous %s tensor of shape %s on %s" % (self.dtype, (n, itot, jtot), self.device))
-            a.fsfc = fsfc.data_ptr()
-            written.append(fsfc)
-        if n:
-            read = [t.data_ptr() for t in (ql, w, c, f0, f1)]
-            written = [t.data_ptr() for t in written]
-            if len(set(written)) != len(written) or set(written) & set(read):
-                raise ValueError("les_radiate: thl, flux or fsfc is an input or another of them")
-        fn = self.lib.spc_les_radiate_f32 if self.dtype == torch.float32 else self.lib.spc_les_radiate_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+            a.fsfc = self._plane("les_radiate: fsfc", fsfc, (n, itot, jtot)).data_ptr()
+        self._no_alias("les_radiate: thl, flux or fsfc is an input or another of them", (thl, flux, fsfc), (ql, w, c, f0, f1), n)
+        self._call(self._sym("les_radiate"), ctypes.byref(a), stream=stream)
 
     def radiate_cols_per_block(self, ktot):
         """columns of ``ktot`` levels a workgroup of K18 takes into LDS in the engine's dtype (64, 32 or 16); 0: unsupported"""
-        return int(self.lib.spc_les_radiate_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+        return self._geometry("radiate_cols_per_block", ktot)
 
     # -- K19: the local cloud-water forcing of device-resident LES moisture (qt_forcing 'local' | 'strong') ------------------------
     @_on_engine_stream
@@ -1174,10 +1062,7 @@ class Engine:
         Returns the int32 [n x ktot] counts (``count``: a tensor to write them into, rows may be pitched).  ``split``: 0 lets
         the library choose how many workgroups share a plane (``qt_local_split``), another value forces it; the bits do not
         depend on it.  ``qt`` STARTING where ``ql`` starts is refused (ValueError)."""
-        shape = tuple(self._field4("qt", qt).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_qt_local: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("les_qt_local", "qt", qt)
         if int(split) < 0:
             raise ValueError("les_qt_local: split must be >= 0, got %r" % (split,))
         ck = _Checker(self.device, self.dtype)
@@ -1188,15 +1073,13 @@ class Engine:
         args.qtm, _ = ck.mat("qtm", qtm, n, ktot, pitch=args.pitch_prof)
         out, args.pitch_count = self._out(count, n, ktot, dtype=torch.int32)
         args.count = out.data_ptr()
-        if n and qt.data_ptr() == ql.data_ptr():
-            raise ValueError("les_qt_local: qt and ql are the same tensor")
-        fn = self.lib.spc_les_qt_local_f32 if self.dtype == torch.float32 else self.lib.spc_les_qt_local_f64
-        self._call(fn, ctypes.byref(args), stream=stream)
+        self._no_alias("les_qt_local: qt and ql are the same tensor", [qt], [ql], n)
+        self._call(self._sym("les_qt_local"), ctypes.byref(args), stream=stream)
         return out
 
     def qt_local_split(self, n, itot, jtot, ktot):
         """workgroups that share a plane of K19 for these extents in the engine's dtype, as the library chooses; 0: bad extents"""
-        return int(self.lib.spc_les_qt_local_split(int(n), int(itot), int(jtot), int(ktot), 4 if self.dtype == torch.float32 else 8))
+        return self._geometry("qt_local_split", n, itot, jtot, ktot)
 
     # -- K20: the second moments of device-resident LES fields (variances, covariances, resolved fluxes) ---------------------------
     @_on_engine_stream
@@ -1226,10 +1109,7 @@ class Engine:
         kinds = [k for k, on in (("mean", mean), ("var", var), ("std", std)) if on]
         if not kinds and not pairs:
             raise ValueError("les_moments: no output asked for")
-        shape = tuple(self._field4(names[0], fields[names[0]]).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_moments: empty field shape %s" % (shape,))
+        shape = n, itot, jtot, ktot = self._extents("les_moments", names[0], fields[names[0]])
         a = _abi.LesMomentsArgs()
         a.n_les, a.itot, a.jtot, a.ktot = n, itot, jtot, ktot
         a.n_fields, a.n_pairs, a.face_field = len(names), len(pairs), -1 if face is None else names.index(face)
@@ -1245,9 +1125,7 @@ class Engine:
                 o, p = self._out(fresh[missing.index((kind, key))], n, ktot)
             else:
                 o, p = self._out(out[kind][key], n, ktot)
-            if pitch is not None and n > 1 and p != pitch:
-                raise ValueError("les_moments: out[%s][%s] has row pitch %d, the others %d" % (kind, key, p, pitch))
-            pitch = p
+            pitch = self._same_pitch("les_moments: out[%s][%s]" % (kind, key), p, pitch, n)
             res.setdefault(kind, {})[key] = o
             if kind == "cov":
                 q = pairs.index(key)
@@ -1256,8 +1134,7 @@ class Engine:
             else:
                 getattr(a, kind)[names.index(key)] = o.data_ptr()
         a.pitch_out = pitch
-        fn = self.lib.spc_les_moments_f32 if self.dtype == torch.float32 else self.lib.spc_les_moments_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+        self._call(self._sym("les_moments"), ctypes.byref(a), stream=stream)
         return res
 
     # -- K21: the hydrostatic pressure force of device-resident LES fields on their winds, two launches ---------------------------
@@ -1274,11 +1151,7 @@ class Engine:
         (ValueError); views that overlap in part are not detected.  Two launches; more levels than
         ``buoyancy_cols_per_block`` carries are refused (SPC_ERR_UNSUPPORTED)."""
         from . import buoyancy
-        shape = tuple(self._field4("thl", thl).shape)
-        n, itot, jtot, ktot = (int(x) for x in shape)
-        if min(itot, jtot, ktot) < 1:
-            raise ValueError("les_buoyancy: empty field shape %s" % (shape,))
-        want = amax is not None and amax is not False
+        shape = n, itot, jtot, ktot = self._extents("les_buoyancy", "thl", thl)
         ck = _Checker(self.device, self.dtype)
         a = _abi.LesBuoyancyArgs()
         a.n_les, a.itot, a.jtot, a.ktot = n, itot, jtot, ktot
@@ -1292,31 +1165,20 @@ class Engine:
         a.s, _ = ck.mat("s", s, n, ktot, pitch=a.pitch_prof)
         a.c1, a.c2 = buoyancy.C1, buoyancy.C2
         a.phi = self._field4("phi", phi, shape).data_ptr()
-        written = [phi, u, v]
         if psfc is not None:
-            if not isinstance(psfc, torch.Tensor) or psfc.device != self.device or psfc.dtype != self.dtype or \
-                    tuple(psfc.shape) != (n, itot, jtot) or not psfc.is_contiguous():
-                raise ValueError("les_buoyancy: psfc must be a contiguous %s tensor of shape %s on %s" % (self.dtype, (n, itot, jtot), self.device))
-            a.psfc = psfc.data_ptr()
-            written.append(psfc)
-        res = None
-        if want:
-            res = torch.empty(n, dtype=self.dtype, device=self.device) if amax is True else amax
-            a.amax = ck.vec("amax", res, n)
-            written.append(res)
-        if n:
-            read = [t.data_ptr() for t in (thl, qt, ql, hx, hy, t0, lex, s) if t is not None]
-            written = [t.data_ptr() for t in written]
-            if len(set(written)) != len(written) or set(written) & set(read):
-                raise ValueError("les_buoyancy: phi, u, v, psfc or amax is an input or another of them")
-        fn = self.lib.spc_les_buoyancy_f32 if self.dtype == torch.float32 else self.lib.spc_les_buoyancy_f64
-        self._call(fn, ctypes.byref(a), stream=stream)
+            a.psfc = self._plane("les_buoyancy: psfc", psfc, (n, itot, jtot)).data_ptr()
+        res = self._largest(ck, "amax", amax, n)
+        if res is not None:
+            a.amax = res.data_ptr()
+        self._no_alias("les_buoyancy: phi, u, v, psfc or amax is an input or another of them", (phi, u, v, psfc, res),
+                       (thl, qt, ql, hx, hy, t0, lex, s), n)
+        self._call(self._sym("les_buoyancy"), ctypes.byref(a), stream=stream)
         return res
 
     def buoyancy_cols_per_block(self, ktot):
         """columns of ``ktot`` levels a workgroup of K21's k_les_hydrostatic takes into LDS in the engine's dtype (64, 32 or 16);
         0: unsupported"""
-        return int(self.lib.spc_les_buoyancy_cols_per_block(int(ktot), 4 if self.dtype == torch.float32 else 8))
+        return self._geometry("buoyancy_cols_per_block", ktot)
 
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
@@ -1384,7 +1246,7 @@ class Engine:
             out = torch.empty_like(p)
         elif not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != self.dtype or out.shape != p.shape or not out.is_contiguous():
             raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (self.dtype, tuple(p.shape), self.device))
-        fn = getattr(self.lib, "spc_exner_" + _DTYPES[self.dtype])
+        fn = self._sym("exner")
         return OperatorPlan(self, fn, (p.numel(), p.data_ptr(), out.data_ptr(), 1 if inverse else 0), [p, out], {"out": out}, result=out,
                             refresh=refresh)
 
@@ -1411,7 +1273,7 @@ class Engine:
             raise ValueError("fp and xp are not of the same length")          # numpy.interp's message
         out, pitch_out = self._out(out, n_rows, n_x)
         a = _abi.InterpArgs(n_rows, n_x, n_xp, pitch_x, pitch_xp, pitch_fp, pitch_out, p_x, p_xp, p_fp, out.data_ptr())
-        fn = getattr(self.lib, "spc_interp_" + _DTYPES[self.dtype])
+        fn = self._sym("interp")
         return OperatorPlan(self, fn, (ctypes.byref(a),), [fp2, xp2, x2, out, a], {"out": out}, result=out[0] if one else out, refresh=refresh)
 
     def interp(self, x, xp, fp, stream=None, out=None):
@@ -1429,7 +1291,7 @@ class Engine:
         v2, p_v, pitch_v, n_v = self._rows("v", v, n_rows, shared_ok=True, refresh=refresh)
         out, pitch_out = self._out(out, n_rows, n_v, dtype=torch.int64)
         args = _abi.SearchsortedArgs(n_rows, n_a, n_v, pitch_a, pitch_v, pitch_out, p_a, p_v, out.data_ptr(), 1 if side == "right" else 0, 0)
-        fn = getattr(self.lib, "spc_searchsorted_" + _DTYPES[self.dtype])
+        fn = self._sym("searchsorted")
         return OperatorPlan(self, fn, (ctypes.byref(args),), [a2, v2, out, args], {"out": out}, result=out[0] if one else out, refresh=refresh)
 
     def searchsorted(self, a, v, side="left", stream=None, out=None):
@@ -1470,7 +1332,7 @@ class Engine:
         nG = nGh - 1
         out, pitch_out = self._out(out, n_rows, max(nG, 0))
         a = _abi.InterpCArgs(n_rows, nG, nL, pitch_Zh, pitch_zh, pitch_q, pitch_out, p_Zh, p_zh, p_q, p_rho, out.data_ptr(), modes[mode], 0)
-        fn = getattr(self.lib, "spc_interp_c_" + _DTYPES[self.dtype])
+        fn = self._sym("interp_c")
         return OperatorPlan(self, fn, (ctypes.byref(a),), [Zh2, zh2, q2, rho2, out, a], {"out": out}, result=out[0] if one else out, refresh=refresh)
 
     def interp_c(self, Zh, zh, q, rho=None, mode="interp_c", stream=None, out=None):
@@ -1488,7 +1350,7 @@ class Engine:
         elif not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != self.dtype or tuple(out.shape) != (n_rows,) \
                 or not out.is_contiguous():
             raise ValueError("out must be a contiguous %s vector of %d on %s" % (self.dtype, n_rows, self.device))
-        fn = getattr(self.lib, "spc_rms_" + _DTYPES[self.dtype])
+        fn = self._sym("rms")
         return OperatorPlan(self, fn, (n_rows, n, max(pitch, n), p_a, out.data_ptr()), [a2, out], {"out": out}, result=out[0] if one else out,
                             refresh=refresh)
 
@@ -1507,7 +1369,7 @@ class Engine:
         wthl = out["wthl"] if "wthl" in out else self.empty(n)
         wqt = out["wqt"] if "wqt" in out else self.empty(n)
         optr = [ck.vec("wthl", wthl, n), ck.vec("wqt", wqt, n)]
-        fn = getattr(self.lib, "spc_surface_fluxes_" + _DTYPES[self.dtype])
+        fn = self._sym("surface_fluxes")
         return SurfacePlan(self, fn, [n] + ptrs + optr, ck.keep, {"wthl": wthl, "wqt": wqt})
 
     @_on_engine_stream

@@ -254,52 +254,42 @@ class MultiDeviceEngine:
             return self.primary.les_diffuse(fields, a, m, cp, s0=s0, flux=flux, **kw)
         self._each("les_diffuse", ex, (fields, a, m, cp), dict(kw, s0=s0, flux=flux))
 
+    def _largest(self, name, key, ex, args, kw):
+        """``engine.<name>(*args, **kw)`` for the methods that return the largest value of every LES where ``kw[key]`` asks for
+        it (``cmax``, ``amax``): on the primary engine when ``ex`` is no Sharded, else on every device that holds rows of it.
+        Returns None for False / None, the caller's own (Sharded) tensor where one was given, the joined results for True"""
+        ex = self._example(ex)
+        if ex is None:
+            return getattr(self.primary, name)(*args, **kw)
+        res = self._each(name, ex, args, kw)
+        top = kw[key]
+        if top is None or top is False:
+            return None
+        return top if top is not True else self._join(res, ex.bounds)
+
     def les_advect(self, fields, out, u, v, hx, hy, cmax=True, **kw):
         """K16 on every device's LES: dicts of Sharded fields and outputs (written block by block), Sharded winds and ``hx``,
         ``hy`` [n] in; the Sharded [n] Courant sums out (None without ``cmax``); one launch per device that holds rows"""
-        ex = self._example(u)
-        if ex is None:
-            return self.primary.les_advect(fields, out, u, v, hx, hy, cmax=cmax, **kw)
-        res = self._each("les_advect", ex, (fields, out, u, v, hx, hy), dict(kw, cmax=cmax))
-        if cmax is None or cmax is False:
-            return None
-        return cmax if cmax is not True else self._join(res, ex.bounds)
+        return self._largest("les_advect", "cmax", u, (fields, out, u, v, hx, hy), dict(kw, cmax=cmax))
 
     def les_vadvect(self, fields, out, u, v, hx, hy, g, r, cmax=True, mtop=None, **kw):
         """K17 on every device's LES: dicts of Sharded fields and outputs (written block by block), Sharded winds, ``hx``, ``hy``
         [n], the profiles ``g`` and ``r`` [n x ktot] and ``mtop`` (or None) in; the Sharded [n] vertical Courant sums out (None
         without ``cmax``); one launch per device that holds rows"""
-        ex = self._example(u)
-        if ex is None:
-            return self.primary.les_vadvect(fields, out, u, v, hx, hy, g, r, cmax=cmax, mtop=mtop, **kw)
-        res = self._each("les_vadvect", ex, (fields, out, u, v, hx, hy, g, r), dict(kw, cmax=cmax, mtop=mtop))
-        if cmax is None or cmax is False:
-            return None
-        return cmax if cmax is not True else self._join(res, ex.bounds)
+        return self._largest("les_vadvect", "cmax", u, (fields, out, u, v, hx, hy, g, r), dict(kw, cmax=cmax, mtop=mtop))
 
     def les_transport(self, fields, out, u, v, hx, hy, g, r, cmax=True, mtop=None, ftop=None, **kw):
         """K22 on every device's LES: dicts of Sharded fields and outputs (written block by block), Sharded winds, ``hx``, ``hy``
         [n], the profiles ``g`` and ``r`` [n x ktot], ``mtop`` (or None) and ``ftop`` (or None: a Sharded whose part on device
         d is [len(fields) x that device's rows x itot x jtot]) in; the Sharded [n] outflow Courant sums out (None without
         ``cmax``); one launch per device that holds rows"""
-        ex = self._example(u)
-        if ex is None:
-            return self.primary.les_transport(fields, out, u, v, hx, hy, g, r, cmax=cmax, mtop=mtop, ftop=ftop, **kw)
-        res = self._each("les_transport", ex, (fields, out, u, v, hx, hy, g, r), dict(kw, cmax=cmax, mtop=mtop, ftop=ftop))
-        if cmax is None or cmax is False:
-            return None
-        return cmax if cmax is not True else self._join(res, ex.bounds)
+        return self._largest("les_transport", "cmax", u, (fields, out, u, v, hx, hy, g, r), dict(kw, cmax=cmax, mtop=mtop, ftop=ftop))
 
     def les_transport2(self, fields, out, u, v, hx, hy, g, r, limiter="mc", cmax=True, mtop=None, ftop=None, **kw):
         """K23 on every device's LES: the arguments and the result of ``les_transport`` with the ``limiter`` of
         ``Engine.les_transport2``; one launch per device that holds rows"""
-        ex = self._example(u)
-        if ex is None:
-            return self.primary.les_transport2(fields, out, u, v, hx, hy, g, r, limiter=limiter, cmax=cmax, mtop=mtop, ftop=ftop, **kw)
-        res = self._each("les_transport2", ex, (fields, out, u, v, hx, hy, g, r), dict(kw, limiter=limiter, cmax=cmax, mtop=mtop, ftop=ftop))
-        if cmax is None or cmax is False:
-            return None
-        return cmax if cmax is not True else self._join(res, ex.bounds)
+        return self._largest("les_transport2", "cmax", u, (fields, out, u, v, hx, hy, g, r),
+                             dict(kw, limiter=limiter, cmax=cmax, mtop=mtop, ftop=ftop))
 
     def les_radiate(self, ql, thl, w, c, f0, f1, *, flux=None, fsfc=None, **kw):
         """K18 on every device's LES: the Sharded fields ``ql`` and ``thl`` (updated in place, block by block), the Sharded
@@ -338,13 +328,7 @@ class MultiDeviceEngine:
         block by block), ``hx``, ``hy`` [n], the Sharded profiles ``t0``, ``lex`` and ``s`` [n x ktot], ``phi`` and ``psfc`` (or
         None) in; the Sharded [n] largest wind changes out (None without ``amax``); two launches per device that holds rows,
         none on the others"""
-        ex = self._example(thl)
-        if ex is None:
-            return self.primary.les_buoyancy(thl, qt, ql, u, v, hx, hy, t0, lex, s, phi, psfc=psfc, amax=amax, **kw)
-        res = self._each("les_buoyancy", ex, (thl, qt, ql, u, v, hx, hy, t0, lex, s, phi), dict(kw, psfc=psfc, amax=amax))
-        if amax is None or amax is False:
-            return None
-        return amax if amax is not True else self._join(res, ex.bounds)
+        return self._largest("les_buoyancy", "amax", thl, (thl, qt, ql, u, v, hx, hy, t0, lex, s, phi), dict(kw, psfc=psfc, amax=amax))
 
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""

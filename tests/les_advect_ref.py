@@ -364,6 +364,33 @@ def check_special(eng):
     assert not qr.any() and not numpy.signbit(qr).any()
 
 
+def elsewhere(eng, t):
+    """``t`` on another device than the engine's: the host for an engine on a GPU, the meta device for a stand-in on the host"""
+    return t.cpu() if eng.device.type == "cuda" else t.to("meta")
+
+
+def bad_calls(eng, t, o, u, v, hx, hy):
+    """the calls of ``Engine.les_advect`` that are refused, as callables: ``check_refusals`` makes them on a device,
+    tests/test_engine_les_args_cpu.py on a stand-in that launches nothing, where it pins their texts"""
+    many = {("F%d" % i): t["QT"].clone() for i in range(7)}
+    other = torch.float64 if eng.dtype == torch.float32 else torch.float32
+    return [lambda: eng.les_advect({}, {}, u, v, hx, hy, cmax=False),
+            lambda: eng.les_advect({}, {}, u, v, hx, hy, cmax=None),
+            lambda: eng.les_advect(t, dict(o, QT=t["THL"]), u, v, hx, hy),
+            lambda: eng.les_advect(t, dict(o, QT=u), u, v, hx, hy),
+            lambda: eng.les_advect(t, dict(o, QT=o["THL"]), u, v, hx, hy),
+            lambda: eng.les_advect({"QT": t["QT"]}, {"QT": hx.view(2, 1, 1, 1).expand(2, 2, 3, 8)}, u, v, hx, hy),
+            lambda: eng.les_advect(t, {k: x for k, x in o.items() if k != "QT"}, u, v, hx, hy),
+            lambda: eng.les_advect(many, {k: torch.empty_like(x) for k, x in many.items()}, u, v, hx, hy),
+            lambda: eng.les_advect(t, o, u, v[:, :1], hx, hy),
+            lambda: eng.les_advect(t, o, u, v, hx[:1], hy),
+            lambda: eng.les_advect(t, o, u, v, hx, hy, cmax=hx),
+            lambda: eng.les_advect(t, o, u, v, hx, hy, cmax=torch.empty(3, dtype=eng.dtype, device=eng.device)),
+            lambda: eng.les_advect({"QT": t["QT"][..., ::2]}, {"QT": o["QT"][..., ::2]}, u, v, hx, hy),
+            lambda: eng.les_advect({"QT": t["QT"].to(other)}, {"QT": o["QT"]}, u, v, hx, hy),
+            lambda: eng.les_advect({"QT": elsewhere(eng, t["QT"])}, {"QT": o["QT"]}, u, v, hx, hy)]
+
+
 def check_refusals(eng):
     """n = 0 is a no-op; no field without cmax, an output that is an input, cmax or another output and an extent below 1 are
     refused by the library and by the engine, and no refused call touches anything"""
@@ -386,23 +413,7 @@ def check_refusals(eng):
     o = {k: torch.full_like(x, OUT_FILL) for k, x in t.items()}
     got = eng.les_advect({k: x[:0] for k, x in t.items()}, {k: x[:0] for k, x in o.items()}, u[:0], v[:0], hx[:0], hy[:0])
     assert tuple(got.shape) == (0,)
-    many = {("F%d" % i): t["QT"].clone() for i in range(7)}
-    other = torch.float64 if eng.dtype == torch.float32 else torch.float32
-    for bad in (lambda: eng.les_advect({}, {}, u, v, hx, hy, cmax=False),
-                lambda: eng.les_advect({}, {}, u, v, hx, hy, cmax=None),
-                lambda: eng.les_advect(t, dict(o, QT=t["THL"]), u, v, hx, hy),
-                lambda: eng.les_advect(t, dict(o, QT=u), u, v, hx, hy),
-                lambda: eng.les_advect(t, dict(o, QT=o["THL"]), u, v, hx, hy),
-                lambda: eng.les_advect({"QT": t["QT"]}, {"QT": hx.view(2, 1, 1, 1).expand(2, 2, 3, 8)}, u, v, hx, hy),
-                lambda: eng.les_advect(t, {k: x for k, x in o.items() if k != "QT"}, u, v, hx, hy),
-                lambda: eng.les_advect(many, {k: torch.empty_like(x) for k, x in many.items()}, u, v, hx, hy),
-                lambda: eng.les_advect(t, o, u, v[:, :1], hx, hy),
-                lambda: eng.les_advect(t, o, u, v, hx[:1], hy),
-                lambda: eng.les_advect(t, o, u, v, hx, hy, cmax=hx),
-                lambda: eng.les_advect(t, o, u, v, hx, hy, cmax=torch.empty(3, dtype=eng.dtype, device=eng.device)),
-                lambda: eng.les_advect({"QT": t["QT"][..., ::2]}, {"QT": o["QT"][..., ::2]}, u, v, hx, hy),
-                lambda: eng.les_advect({"QT": t["QT"].to(other)}, {"QT": o["QT"]}, u, v, hx, hy),
-                lambda: eng.les_advect({"QT": t["QT"].cpu()}, {"QT": o["QT"]}, u, v, hx, hy)):
+    for bad in bad_calls(eng, t, o, u, v, hx, hy):
         try:
             bad()
         except ValueError:

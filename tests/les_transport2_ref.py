@@ -452,6 +452,42 @@ def check_special(eng):
         assert not numpy.isfinite(want["THL"][mask]).all() and numpy.isfinite(want["THL"][~mask]).all()
 
 
+def bad_calls(eng, t, o, u, v, hx, hy, g, r, m, ft):
+    """the calls of ``Engine.les_transport2`` that are refused, as callables: ``check_refusals`` makes them on a device,
+    tests/test_engine_les_args_cpu.py on a stand-in that launches nothing, where it pins their texts"""
+    many = {("F%d" % i): t["QT"].clone() for i in range(7)}
+    other = torch.float64 if eng.dtype == torch.float32 else torch.float32
+    V = eng.les_transport2
+    return [lambda: V(t, o, u, v, hx, hy, g, r, limiter="minmod"),
+            lambda: V(t, o, u, v, hx, hy, g, r, limiter=1),
+            lambda: V(t, o, u, v, hx, hy, g, r, limiter=None),
+            lambda: V({}, {}, u, v, hx, hy, g, r, limiter="superbee"),
+            lambda: V({}, {}, u, v, hx, hy, g, r, cmax=False),
+            lambda: V({}, {}, u, v, hx, hy, g, r, cmax=None, mtop=None),
+            lambda: V({}, {}, u, v, hx, hy, g, r, ftop=ft[:0]),
+            lambda: V(t, dict(o, QT=t["THL"]), u, v, hx, hy, g, r),
+            lambda: V(t, dict(o, QT=u), u, v, hx, hy, g, r),
+            lambda: V(t, dict(o, QT=o["THL"]), u, v, hx, hy, g, r),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=o["QT"]),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=u),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=m[:, :1]),
+            lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft[:3]),
+            lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft[:, :1]),
+            lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft.to(other)),
+            lambda: V(t, {k: x for k, x in o.items() if k != "QT"}, u, v, hx, hy, g, r),
+            lambda: V(many, {k: torch.empty_like(x) for k, x in many.items()}, u, v, hx, hy, g, r),
+            lambda: V(t, o, u, v[:, :1], hx, hy, g, r),
+            lambda: V(t, o, u, v, hx[:1], hy, g, r),
+            lambda: V(t, o, u, v, hx, hy, g[:1], r),
+            lambda: V(t, o, u, v, hx, hy, g, r[:, :7]),
+            lambda: V(t, o, u, v, hx, hy, g, None),
+            lambda: V(t, o, u, v, hx, hy, g, r, cmax=hx),
+            lambda: V(t, o, u, v, hx, hy, g, r, cmax=torch.empty(3, dtype=eng.dtype, device=eng.device)),
+            lambda: V({"QT": t["QT"][..., ::2]}, {"QT": o["QT"][..., ::2]}, u, v, hx, hy, g, r),
+            lambda: V({"QT": t["QT"].to(other)}, {"QT": o["QT"]}, u, v, hx, hy, g, r),
+            lambda: V({"QT": lvr.elsewhere(eng, t["QT"])}, {"QT": o["QT"]}, u, v, hx, hy, g, r)]
+
+
 def check_refusals(eng):
     """K22's refusals through spc_les_transport2_* and ``Engine.les_transport2``, and the limiter that is neither: no refused
     call touches anything"""
@@ -500,37 +536,7 @@ def check_refusals(eng):
     got = eng.les_transport2({k: x[:0] for k, x in t.items()}, {k: x[:0] for k, x in o.items()}, u[:0], v[:0], hx[:0], hy[:0], g[:0], r[:0],
                              mtop=m[:0], ftop=ft[:, :0])
     assert tuple(got.shape) == (0,)
-    many = {("F%d" % i): t["QT"].clone() for i in range(7)}
-    other = torch.float64 if eng.dtype == torch.float32 else torch.float32
-    V = eng.les_transport2
-    for bad in (lambda: V(t, o, u, v, hx, hy, g, r, limiter="minmod"),
-                lambda: V(t, o, u, v, hx, hy, g, r, limiter=1),
-                lambda: V(t, o, u, v, hx, hy, g, r, limiter=None),
-                lambda: V({}, {}, u, v, hx, hy, g, r, limiter="superbee"),
-                lambda: V({}, {}, u, v, hx, hy, g, r, cmax=False),
-                lambda: V({}, {}, u, v, hx, hy, g, r, cmax=None, mtop=None),
-                lambda: V({}, {}, u, v, hx, hy, g, r, ftop=ft[:0]),
-                lambda: V(t, dict(o, QT=t["THL"]), u, v, hx, hy, g, r),
-                lambda: V(t, dict(o, QT=u), u, v, hx, hy, g, r),
-                lambda: V(t, dict(o, QT=o["THL"]), u, v, hx, hy, g, r),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=o["QT"]),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=u),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=m[:, :1]),
-                lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft[:3]),
-                lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft[:, :1]),
-                lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft.to(other)),
-                lambda: V(t, {k: x for k, x in o.items() if k != "QT"}, u, v, hx, hy, g, r),
-                lambda: V(many, {k: torch.empty_like(x) for k, x in many.items()}, u, v, hx, hy, g, r),
-                lambda: V(t, o, u, v[:, :1], hx, hy, g, r),
-                lambda: V(t, o, u, v, hx[:1], hy, g, r),
-                lambda: V(t, o, u, v, hx, hy, g[:1], r),
-                lambda: V(t, o, u, v, hx, hy, g, r[:, :7]),
-                lambda: V(t, o, u, v, hx, hy, g, None),
-                lambda: V(t, o, u, v, hx, hy, g, r, cmax=hx),
-                lambda: V(t, o, u, v, hx, hy, g, r, cmax=torch.empty(3, dtype=eng.dtype, device=eng.device)),
-                lambda: V({"QT": t["QT"][..., ::2]}, {"QT": o["QT"][..., ::2]}, u, v, hx, hy, g, r),
-                lambda: V({"QT": t["QT"].to(other)}, {"QT": o["QT"]}, u, v, hx, hy, g, r),
-                lambda: V({"QT": t["QT"].cpu()}, {"QT": o["QT"]}, u, v, hx, hy, g, r)):
+    for bad in bad_calls(eng, t, o, u, v, hx, hy, g, r, m, ft):
         try:
             bad()
         except (ValueError, TypeError):

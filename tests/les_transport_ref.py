@@ -458,6 +458,38 @@ def check_special(eng):
     assert numpy.isnan(mtop[mask]).all() and numpy.isfinite(cmax).all() and not numpy.signbit(cmax).any()
 
 
+def bad_calls(eng, t, o, u, v, hx, hy, g, r, m, ft):
+    """the calls of ``Engine.les_transport`` that are refused, as callables: ``check_refusals`` makes them on a device,
+    tests/test_engine_les_args_cpu.py on a stand-in that launches nothing, where it pins their texts"""
+    many = {("F%d" % i): t["QT"].clone() for i in range(7)}
+    other = torch.float64 if eng.dtype == torch.float32 else torch.float32
+    V = eng.les_transport
+    return [lambda: V({}, {}, u, v, hx, hy, g, r, cmax=False),
+            lambda: V({}, {}, u, v, hx, hy, g, r, cmax=None, mtop=None),
+            lambda: V({}, {}, u, v, hx, hy, g, r, ftop=ft[:0]),
+            lambda: V(t, dict(o, QT=t["THL"]), u, v, hx, hy, g, r),
+            lambda: V(t, dict(o, QT=u), u, v, hx, hy, g, r),
+            lambda: V(t, dict(o, QT=o["THL"]), u, v, hx, hy, g, r),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=o["QT"]),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=u),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=m[:, :1]),
+            lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft[:3]),
+            lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft[:, :1]),
+            lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft.to(other)),
+            lambda: V(t, {k: x for k, x in o.items() if k != "QT"}, u, v, hx, hy, g, r),
+            lambda: V(many, {k: torch.empty_like(x) for k, x in many.items()}, u, v, hx, hy, g, r),
+            lambda: V(t, o, u, v[:, :1], hx, hy, g, r),
+            lambda: V(t, o, u, v, hx[:1], hy, g, r),
+            lambda: V(t, o, u, v, hx, hy, g[:1], r),
+            lambda: V(t, o, u, v, hx, hy, g, r[:, :7]),
+            lambda: V(t, o, u, v, hx, hy, g, None),
+            lambda: V(t, o, u, v, hx, hy, g, r, cmax=hx),
+            lambda: V(t, o, u, v, hx, hy, g, r, cmax=torch.empty(3, dtype=eng.dtype, device=eng.device)),
+            lambda: V({"QT": t["QT"][..., ::2]}, {"QT": o["QT"][..., ::2]}, u, v, hx, hy, g, r),
+            lambda: V({"QT": t["QT"].to(other)}, {"QT": o["QT"]}, u, v, hx, hy, g, r),
+            lambda: V({"QT": lvr.elsewhere(eng, t["QT"])}, {"QT": o["QT"]}, u, v, hx, hy, g, r)]
+
+
 def check_refusals(eng):
     """n = 0 is a no-op; nothing to do, a NULL required array, pitch_prof < ktot, an output that is an input or another output,
     a misaligned pointer, a field count outside 0 ... 6 and an extent below 1 are refused by the library and by the engine, and
@@ -506,33 +538,7 @@ def check_refusals(eng):
     got = eng.les_transport({k: x[:0] for k, x in t.items()}, {k: x[:0] for k, x in o.items()}, u[:0], v[:0], hx[:0], hy[:0], g[:0], r[:0],
                             mtop=m[:0], ftop=ft[:, :0])
     assert tuple(got.shape) == (0,)
-    many = {("F%d" % i): t["QT"].clone() for i in range(7)}
-    other = torch.float64 if eng.dtype == torch.float32 else torch.float32
-    V = eng.les_transport
-    for bad in (lambda: V({}, {}, u, v, hx, hy, g, r, cmax=False),
-                lambda: V({}, {}, u, v, hx, hy, g, r, cmax=None, mtop=None),
-                lambda: V({}, {}, u, v, hx, hy, g, r, ftop=ft[:0]),
-                lambda: V(t, dict(o, QT=t["THL"]), u, v, hx, hy, g, r),
-                lambda: V(t, dict(o, QT=u), u, v, hx, hy, g, r),
-                lambda: V(t, dict(o, QT=o["THL"]), u, v, hx, hy, g, r),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=o["QT"]),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=u),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=m[:, :1]),
-                lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft[:3]),
-                lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft[:, :1]),
-                lambda: V(t, o, u, v, hx, hy, g, r, ftop=ft.to(other)),
-                lambda: V(t, {k: x for k, x in o.items() if k != "QT"}, u, v, hx, hy, g, r),
-                lambda: V(many, {k: torch.empty_like(x) for k, x in many.items()}, u, v, hx, hy, g, r),
-                lambda: V(t, o, u, v[:, :1], hx, hy, g, r),
-                lambda: V(t, o, u, v, hx[:1], hy, g, r),
-                lambda: V(t, o, u, v, hx, hy, g[:1], r),
-                lambda: V(t, o, u, v, hx, hy, g, r[:, :7]),
-                lambda: V(t, o, u, v, hx, hy, g, None),
-                lambda: V(t, o, u, v, hx, hy, g, r, cmax=hx),
-                lambda: V(t, o, u, v, hx, hy, g, r, cmax=torch.empty(3, dtype=eng.dtype, device=eng.device)),
-                lambda: V({"QT": t["QT"][..., ::2]}, {"QT": o["QT"][..., ::2]}, u, v, hx, hy, g, r),
-                lambda: V({"QT": t["QT"].to(other)}, {"QT": o["QT"]}, u, v, hx, hy, g, r),
-                lambda: V({"QT": t["QT"].cpu()}, {"QT": o["QT"]}, u, v, hx, hy, g, r)):
+    for bad in bad_calls(eng, t, o, u, v, hx, hy, g, r, m, ft):
         try:
             bad()
         except (ValueError, TypeError):

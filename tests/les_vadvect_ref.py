@@ -419,6 +419,39 @@ def check_special(eng):
         assert_bits("a constant keeps its bits: " + name, r.out[name].cpu().numpy(), k["fields"][name])
 
 
+def elsewhere(eng, t):
+    """``t`` on another device than the engine's: the host for an engine on a GPU, the meta device for a stand-in on the host"""
+    return t.cpu() if eng.device.type == "cuda" else t.to("meta")
+
+
+def bad_calls(eng, t, o, u, v, hx, hy, g, r, m):
+    """the calls of ``Engine.les_vadvect`` that are refused, as callables: ``check_refusals`` makes them on a device,
+    tests/test_engine_les_args_cpu.py on a stand-in that launches nothing, where it pins their texts"""
+    many = {("F%d" % i): t["QT"].clone() for i in range(7)}
+    other = torch.float64 if eng.dtype == torch.float32 else torch.float32
+    V = eng.les_vadvect
+    return [lambda: V({}, {}, u, v, hx, hy, g, r, cmax=False),
+            lambda: V({}, {}, u, v, hx, hy, g, r, cmax=None, mtop=None),
+            lambda: V(t, dict(o, QT=t["THL"]), u, v, hx, hy, g, r),
+            lambda: V(t, dict(o, QT=u), u, v, hx, hy, g, r),
+            lambda: V(t, dict(o, QT=o["THL"]), u, v, hx, hy, g, r),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=o["QT"]),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=u),
+            lambda: V(t, o, u, v, hx, hy, g, r, mtop=m[:, :1]),
+            lambda: V(t, {k: x for k, x in o.items() if k != "QT"}, u, v, hx, hy, g, r),
+            lambda: V(many, {k: torch.empty_like(x) for k, x in many.items()}, u, v, hx, hy, g, r),
+            lambda: V(t, o, u, v[:, :1], hx, hy, g, r),
+            lambda: V(t, o, u, v, hx[:1], hy, g, r),
+            lambda: V(t, o, u, v, hx, hy, g[:1], r),
+            lambda: V(t, o, u, v, hx, hy, g, r[:, :7]),
+            lambda: V(t, o, u, v, hx, hy, g, None),
+            lambda: V(t, o, u, v, hx, hy, g, r, cmax=hx),
+            lambda: V(t, o, u, v, hx, hy, g, r, cmax=torch.empty(3, dtype=eng.dtype, device=eng.device)),
+            lambda: V({"QT": t["QT"][..., ::2]}, {"QT": o["QT"][..., ::2]}, u, v, hx, hy, g, r),
+            lambda: V({"QT": t["QT"].to(other)}, {"QT": o["QT"]}, u, v, hx, hy, g, r),
+            lambda: V({"QT": elsewhere(eng, t["QT"])}, {"QT": o["QT"]}, u, v, hx, hy, g, r)]
+
+
 def check_refusals(eng):
     """n = 0 is a no-op; nothing to do, a NULL g or r, pitch_prof < ktot, an output that is an input or another output and an
     extent below 1 are refused by the library and by the engine, and no refused call touches anything"""
@@ -447,29 +480,7 @@ def check_refusals(eng):
     m = torch.full_like(u, OUT_FILL)
     got = eng.les_vadvect({k: x[:0] for k, x in t.items()}, {k: x[:0] for k, x in o.items()}, u[:0], v[:0], hx[:0], hy[:0], g[:0], r[:0], mtop=m[:0])
     assert tuple(got.shape) == (0,)
-    many = {("F%d" % i): t["QT"].clone() for i in range(7)}
-    other = torch.float64 if eng.dtype == torch.float32 else torch.float32
-    V = eng.les_vadvect
-    for bad in (lambda: V({}, {}, u, v, hx, hy, g, r, cmax=False),
-                lambda: V({}, {}, u, v, hx, hy, g, r, cmax=None, mtop=None),
-                lambda: V(t, dict(o, QT=t["THL"]), u, v, hx, hy, g, r),
-                lambda: V(t, dict(o, QT=u), u, v, hx, hy, g, r),
-                lambda: V(t, dict(o, QT=o["THL"]), u, v, hx, hy, g, r),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=o["QT"]),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=u),
-                lambda: V(t, o, u, v, hx, hy, g, r, mtop=m[:, :1]),
-                lambda: V(t, {k: x for k, x in o.items() if k != "QT"}, u, v, hx, hy, g, r),
-                lambda: V(many, {k: torch.empty_like(x) for k, x in many.items()}, u, v, hx, hy, g, r),
-                lambda: V(t, o, u, v[:, :1], hx, hy, g, r),
-                lambda: V(t, o, u, v, hx[:1], hy, g, r),
-                lambda: V(t, o, u, v, hx, hy, g[:1], r),
-                lambda: V(t, o, u, v, hx, hy, g, r[:, :7]),
-                lambda: V(t, o, u, v, hx, hy, g, None),
-                lambda: V(t, o, u, v, hx, hy, g, r, cmax=hx),
-                lambda: V(t, o, u, v, hx, hy, g, r, cmax=torch.empty(3, dtype=eng.dtype, device=eng.device)),
-                lambda: V({"QT": t["QT"][..., ::2]}, {"QT": o["QT"][..., ::2]}, u, v, hx, hy, g, r),
-                lambda: V({"QT": t["QT"].to(other)}, {"QT": o["QT"]}, u, v, hx, hy, g, r),
-                lambda: V({"QT": t["QT"].cpu()}, {"QT": o["QT"]}, u, v, hx, hy, g, r)):
+    for bad in bad_calls(eng, t, o, u, v, hx, hy, g, r, m):
         try:
             bad()
         except (ValueError, TypeError):
