@@ -32,8 +32,8 @@ from sp_coupler_amd import radiation as rad
 from tests import les_diffuse_ref as ldr
 from tests import les_radiate_ref as lrr
 from tests import les_vadvect_ref as lvr
-from tests import les_water_paths_ref as wpr
 from tests.gpu_util import assert_bits
+from tests.les_harness import host_of
 from tests.test_vnudge import make_les_fields
 
 MODES = ("thermo", "diffuse", "micro", "advect", "vertical", "radiate")
@@ -267,7 +267,7 @@ def _row_equals_batched(ens, i, method, got):
 def apply(ens, op, device, modes, on):
     """``op`` on the device ensemble or on the twin; ``on``: the modes enabled now (updated).  Returns None for a mutation, a
     dict name -> host array for an observation"""
-    n, kind, host = ens.n, op[0], wpr._host
+    n, kind = ens.n, op[0]
     if kind == "step":
         return ens.evolve_model_batched(ens.model_time + op[1])
     if kind == "step0":
@@ -285,7 +285,7 @@ def apply(ens, op, device, modes, on):
                                         V=rng.normal(0, 1e-4, (n, NL)), SP=rng.normal(0, 1e-2, n), WT_surf=ldr.WT * (0.5 + rng.random(n)),
                                         WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
     if kind == "set_field":
-        cur = numpy.array(host(ens.get_fields_batched(op[1])))
+        cur = numpy.array(host_of(ens.get_fields_batched(op[1])))
         noise = numpy.random.default_rng(op[2]).normal(0, 1e-2 if op[1] == "QT" else 1e-4, cur.shape)
         return ens.set_fields_batched(op[1], cur * (1.0 + noise))
     if kind == "presf":
@@ -308,9 +308,9 @@ def apply(ens, op, device, modes, on):
         _row_equals_batched(ens, i, op[2], got)
         return {op[2]: got}
     if kind == "field":
-        return {op[1]: numpy.array(host(ens.get_fields_batched(op[1])))}          # (the device tensor itself: copied at once)
+        return {op[1]: numpy.array(host_of(ens.get_fields_batched(op[1])))}          # (the device tensor itself: copied at once)
     if kind == "wp":
-        return {k: numpy.array(host(v)) for k, v in ens.get_water_paths_batched(op[1], cloud_cover=op[2]).items()}
+        return {k: numpy.array(host_of(v)) for k, v in ens.get_water_paths_batched(op[1], cloud_cover=op[2]).items()}
     if kind == "wp_means":
         return {k: numpy.array(v) for k, v in ens.get_water_path_means(op[1]).items()}
     if kind == "row_wp":
@@ -323,9 +323,9 @@ def apply(ens, op, device, modes, on):
         ens.get_cloudfraction_batched(idx, out)
         return {"A": out}
     if kind == "flux":
-        return {"flux": numpy.array(host(ens.get_radiative_flux_batched()))}
+        return {"flux": numpy.array(host_of(ens.get_radiative_flux_batched()))}
     if kind == "w":
-        return {"W": numpy.array(host(ens.get_vertical_wind_batched()))}
+        return {"W": numpy.array(host_of(ens.get_vertical_wind_batched()))}
     if kind == "courant":
         rec = {"substeps": numpy.array([float(ens.advect_substeps)]), "courant": numpy.array([ens.advect_courant])}
         if "vertical" in on:
@@ -335,22 +335,22 @@ def apply(ens, op, device, modes, on):
     rec = {"got " + k: v for k, v in _all_profiles(ens).items()}
     rec.update({"p " + k: numpy.array(v) for k, v in ens.p.items()})              # (read above: p is that of the fields as they are)
     names = ("LWP", "TWP") + (("RWP",) if "micro" in modes else ())
-    rec.update({"field " + k: numpy.array(host(ens.get_fields_batched(k)))
+    rec.update({"field " + k: numpy.array(host_of(ens.get_fields_batched(k)))
                 for k in ("U", "V", "THL", "QT", "QL", "Qsat") + (("QR",) if "micro" in modes else ())})
-    rec.update({k: numpy.array(host(v)) for k, v in ens.get_water_paths_batched(names, cloud_cover=True).items()})
+    rec.update({k: numpy.array(host_of(v)) for k, v in ens.get_water_paths_batched(names, cloud_cover=True).items()})
     rec.update({"mean " + k: numpy.array(v) for k, v in ens.get_water_path_means(names).items()})
     if "micro" in on:
-        rec["rain2d"] = numpy.array(host(ens.rain2d))
+        rec["rain2d"] = numpy.array(host_of(ens.rain2d))
     if "radiate" in on:
         flux = ens.get_radiative_flux_batched()
-        rec["flux"] = numpy.zeros((n, ITOT, JTOT, NL)) if flux is None else numpy.array(host(flux))
+        rec["flux"] = numpy.zeros((n, ITOT, JTOT, NL)) if flux is None else numpy.array(host_of(flux))
     if "advect" in on:
         rec["substeps"] = numpy.array([-1.0 if ens.advect_substeps is None else float(ens.advect_substeps)])
         rec["courant"] = numpy.array([-1.0 if ens.advect_courant is None else ens.advect_courant])
     if "vertical" in on:
         rec["courant z"] = numpy.array([-1.0 if ens.advect_courant_z is None else ens.advect_courant_z])
         if ens.get_vertical_wind_batched() is not None:
-            rec["W"] = numpy.array(host(ens.get_vertical_wind_batched()))
+            rec["W"] = numpy.array(host_of(ens.get_vertical_wind_batched()))
     for i in range(n):
         for method in sorted(ROW_GETTERS):
             _row_equals_batched(ens, i, method, numpy.array(getattr(ens[i], method)()))

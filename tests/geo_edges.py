@@ -11,6 +11,7 @@ import numpy
 import torch
 
 from tests import geo_ref
+from tests.les_harness import run_bodies
 
 INF, NAN = float("inf"), float("nan")
 TILE = 1024                      # GEO_TILE of spc_geo.hpp: edges per LDS tile
@@ -406,13 +407,15 @@ OLD_BODIES = ("adversarial", "naive_flips", "haversine")
 NEW_BODIES = ("exact_tails", "tile_seams", "image_lon", "point_counts", "non_finite_points")
 
 
-def check_everything(eng, names=OLD_BODIES + NEW_BODIES, scale=False):
+BODIES = OLD_BODIES + NEW_BODIES
+
+
+def jobs(eng, names=BODIES):
+    return [(name, lambda name=name: globals()["check_" + name](eng)) for name in names]
+
+
+def check_everything(eng, names=BODIES, scale=False):
     """the bodies ``names`` (and the 2^20-point size test with ``scale``) on one engine: what tools/mutation_control.py runs on
     a mutant library.  Returns the names of the bodies that failed (AssertionError) in the order they ran."""
-    failed = []
-    for name in tuple(names) + (("scale",) if scale else ()):
-        try:
-            globals()["check_" + name](eng)
-        except AssertionError:
-            failed.append(name)
-    return failed
+    names = tuple(names) + (("scale",) if scale else ())
+    return run_bodies(names, jobs(eng, names))

@@ -2,17 +2,16 @@
 tests/test_les_advance_gpu.py (each takes an engine: tools/mutation_control.py hands them the engines of its mutant
 libraries) and an oracle-backed engine with ``les_advance`` for the CPU suite.
 
-Every device array of the bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes behind it
+Every device array of the bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes behind it
 (and in front of a view off the 16-byte grid) are checked after the launch."""
 import numpy
 import torch
 
-from tests import slab_edges, slab_ref
+from tests import slab_ref
 from tests.fake_engine import OracleEngine, _t
 from tests.gpu_util import assert_bits
+from tests.les_harness import DTYPES, NP, Poisoned, blocks_of, np_of, on_both, run_bodies  # noqa: F401  (DTYPES, NP: for the tests)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 SHAPES = [(1, 1, 1, 2), (3, 3, 3, 5), (2, 5, 7, 64), (2, 4, 4, 66), (1, 9, 1, 130), (2, 8, 8, 160)]
 #: itot * jtot = 1 ... 17: every remainder of the row look-ahead (batches of 8 rows, of 4 for the lanes of QT), one, two and
 #: more whole batches, with and without single rows behind them
@@ -81,18 +80,9 @@ class Run:
         dtype = next(iter(fields.values())).dtype
         shape = next(iter(fields.values())).shape
         n, ktot = shape[0], shape[-1]
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=0):
-            v, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (v, b, lead, poison)
-            return v
-
-        def rows(tag, a, poison, lead):
-            """[n x ktot] as the leading columns of a [n x (ktot + pad)] block ``lead`` elements into a poisoned buffer"""
-            wide = numpy.full((n, ktot + pad), poison, dtype=dtype)
-            wide[:, :ktot] = a
-            return put(tag, wide, poison, lead)[:, :ktot]
+        self.mem = Poisoned(eng)
+        put = self.mem.put
+        rows = lambda tag, a, poison, lead: self.mem.rows(tag, a, poison, lead, pad)        # noqa: E731
         self.dev = {k: put("field " + k, v, float("nan"), lead) for k, v in fields.items()}
         self.dtend = {k: rows("tend " + k, v, 1e30, lead_rows) for k, v in tend.items()}
         self.dmeans = {k: rows("mean " + k, numpy.full((n, ktot), -1.0, dtype), -7.0, lead_rows)
@@ -121,22 +111,13 @@ class Run:
         return new, q, means
 
     def check_surroundings(self, what=""):
-        ktot = next(iter(self.host.values())).shape[-1]
-        for tag, (v, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + v.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
-            if self.pad and tag.startswith(("mean", "tend")):
-                assert bool((v[:, ktot:] == poison).all()), (what, tag, "written between the rows")
-
-
-def _np(eng):
-    return NP[eng.dtype]
+        self.mem.check_around(what)
 
 
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, shape, dt=900.0):
     """every field, ql and every mean against the oracle; the step changed every field and every mean"""
-    fields, tend, qsat = case(shape, _np(eng))
+    fields, tend, qsat = case(shape, np_of(eng))
     new, q, means = Run(eng, fields, tend, dt, qsat, "QT").check(str(shape))
     for k in fields:
         assert (new[k] != fields[k]).any() and (means[k] != mean_rows(fields[k])).any(), k
@@ -148,25 +129,25 @@ def check_planes(eng, ktot):
     """itot * jtot = 1 ... 17: whole batches of the look-ahead, single rows behind them, fewer rows than one batch.
     ktot picks the instantiation (160: 16-byte accesses; 33: one element per lane)"""
     for plane in PLANES:
-        fields, tend, qsat = case((2,) + plane + (ktot,), _np(eng), n_fields=2, seed=3)
+        fields, tend, qsat = case((2,) + plane + (ktot,), np_of(eng), n_fields=2, seed=3)
         fields = {"THL": fields["U"], "QT": numpy.abs(fields["V"])}
         tend = {"THL": tend["U"], "QT": tend["V"]}
-        qsat = (fields["QT"] * _np(eng)(1.01)).astype(_np(eng))
-        qsat[:, ::2] = fields["QT"][:, ::2] * _np(eng)(0.75)
+        qsat = (fields["QT"] * np_of(eng)(1.01)).astype(np_of(eng))
+        qsat[:, ::2] = fields["QT"][:, ::2] * np_of(eng)(0.75)
         Run(eng, fields, tend, 60.0, qsat, "QT").check("plane %s ktot %d" % (plane, ktot))
 
 
 def check_alignment(eng, lead, lead_rows, pad):
     """views off the 16-byte grid (``lead`` elements into the buffers of the 3-D arrays, ``lead_rows`` into those of the
     tendencies and means) and pitched tendencies / means (``pad`` elements between the rows)"""
-    fields, tend, qsat = case((3, 5, 7, 160), _np(eng), seed=lead + 10 * lead_rows + 100 * pad)
+    fields, tend, qsat = case((3, 5, 7, 160), np_of(eng), seed=lead + 10 * lead_rows + 100 * pad)
     Run(eng, fields, tend, 300.0, qsat, "QT", lead=lead, lead_rows=lead_rows, pad=pad).check("lead %d %d pad %d" % (lead, lead_rows, pad))
 
 
 def check_optional(eng):
     """a subset of tendencies missing (those fields keep their bits, -0.0 included); no saturation; ql without its mean and
     the mean without ql; 1 and 8 fields"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     fields, tend, qsat = case((2, 5, 7, 64), dtype, seed=5)
     fields["U"][0, 0, 0, :8] = -0.0                              # a field without a tendency is not touched: -0.0 + 0.0 would be +0.0
     fields["U"][1, 3, 3, 5] = numpy.nan
@@ -227,33 +208,31 @@ def special_case(dtype):
 
 
 def check_special(eng):
-    fields, tend, qsat = special_case(_np(eng))
+    fields, tend, qsat = special_case(np_of(eng))
     new, q, means = Run(eng, fields, tend, 900.0, qsat, "QT").check("special values")
     # what the oracle itself says to these inputs is asserted in tests/test_les_advance_cpu.py; here: the levels next to a
     # NaN tendency stay finite on the device (the oracle's answer, compared above, has them finite)
     assert numpy.isnan(new["QT"][:, :, :, 8]).all() and numpy.isfinite(new["QT"][:, :, :, [7, 9]]).all()
     assert numpy.isnan(means["THL"][:, 7]).all() and numpy.isfinite(means["THL"][:, [6, 8]]).all()
-    neg = (fields["QT"] * _np(eng)(3)).astype(_np(eng))
-    new, q, means = Run(eng, fields, {k: numpy.zeros_like(v) for k, v in tend.items()}, 900.0, numpy.abs(numpy.nan_to_num(neg)) + _np(eng)(1), "QT").check("negative everywhere")
+    neg = (fields["QT"] * np_of(eng)(3)).astype(np_of(eng))
+    new, q, means = Run(eng, fields, {k: numpy.zeros_like(v) for k, v in tend.items()}, 900.0, numpy.abs(numpy.nan_to_num(neg)) + np_of(eng)(1), "QT").check("negative everywhere")
     assert (q[~numpy.isnan(q)] == 0).all() and not numpy.signbit(q[~numpy.isnan(q)]).any()
 
 
 def check_multi(one, multi, n, min_rows_expected=None):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    dtype = _np(one)
+    dtype = np_of(one)
     fields, tend, qsat = case((n, 6, 5, 40), dtype, seed=n)
     want_new, want_q, want_means = les_advance(fields, tend, 450.0, qsat, "QT")
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
+    (_, _, dev), (_, _, sh) = on_both(one, multi, n)
     f1 = {k: dev(v) for k, v in fields.items()}
     ql1 = torch.full_like(f1["QT"], -3.0)
     m1 = one.les_advance(f1, {k: dev(v) for k, v in tend.items()}, 450.0, qsat=dev(qsat), sat="QT", ql=ql1)
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
     fm = {k: sh(v) for k, v in fields.items()}
     qlm = sh(numpy.full(qsat.shape, -3.0, dtype=dtype))
     mm = multi.les_advance(fm, {k: sh(v) for k, v in tend.items()}, 450.0, qsat=sh(qsat), sat="QT", ql=qlm)
     multi.synchronize()
-    blocks = [int(p.shape[0]) for p in fm["QT"].parts]
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
+    blocks = blocks_of(fm["QT"], multi, n)
     for k in fields:
         assert_bits("multi field " + k, fm[k].to_host(), want_new[k])
         assert_bits("one field " + k, f1[k].cpu().numpy(), want_new[k])
@@ -269,21 +248,18 @@ def check_multi(one, multi, n, min_rows_expected=None):
 BODIES = ("parity", "planes", "alignment", "optional", "special")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, s) for s in SHAPES]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, s) for s in SHAPES]),
             ("planes", lambda: [check_planes(eng, k) for k in (160, 33)]),
             ("alignment", lambda: [check_alignment(eng, *a) for a in ((1, 0, 0), (0, 1, 0), (0, 0, 4), (0, 0, 3))]),
             ("optional", lambda: check_optional(eng)),
             ("special", lambda: check_special(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_advance (CPU suite) ------------------------------------------------------------------

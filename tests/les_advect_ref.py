@@ -4,25 +4,22 @@ libraries), the host twins of models.DeviceLESEnsemble's advection mode and an o
 CPU suite.
 
 The oracle spells the rule out one operation per NumPy call in the element type, the neighbours by numpy.roll, so nothing
-fuses.  Every device array of the bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes
+fuses.  Every device array of the bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes
 behind it (and in front of a view off the 16-byte grid) are checked after the launch, the inputs against what was uploaded."""
-import ctypes
 
 import numpy
 import torch
 
-from sp_coupler_amd import _abi, models, spcpl
+from sp_coupler_amd import _abi, models
 from sp_coupler_amd import advection as adv
 from tests import les_diffuse_ref as ldr
 from tests import les_micro_ref as lmr
 from tests import les_thermo_ref as ltr
-from tests import les_water_paths_ref as wpr
-from tests import slab_edges, slab_ref
+from tests import slab_ref
 from tests.gpu_util import assert_bits
-from tests.test_vnudge import make_les_fields
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, ensemble_case, host_of, np_of, on_both, run_bodies)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 #: a cell that is its own four neighbours (1 x 1), one extent of 1 either way, both neighbours the same cell (2 x 2, 2 x 3),
 #: itot < jtot (3 x 5), exactly one workgroup's rows (8 x 8), one row more than that (9 x 9)
 PLANES = [(1, 1), (1, 5), (5, 1), (2, 2), (2, 3), (3, 5), (8, 8), (9, 9)]
@@ -131,12 +128,8 @@ class Run:
 
     def __init__(self, eng, c, lead=0, cmax=True):
         self.eng, self.c = eng, c
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=lead):
-            t, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (t, b, lead, poison)
-            return t
+        self.mem = Poisoned(eng)
+        put = lambda tag, a, poison: self.mem.put(tag, a, poison, lead)                    # noqa: E731
         self.du, self.dv = put("u", c["u"], float("nan")), put("v", c["v"], float("nan"))
         self.dev = {k: (self.du if x is c["u"] else self.dv if x is c["v"] else put(k, x, float("nan"))) for k, x in c["fields"].items()}
         self.out = {k: put("out " + k, numpy.full_like(x, OUT_FILL), 1e30) for k, x in c["fields"].items()}
@@ -156,13 +149,10 @@ class Run:
         else:
             assert self.got is self.dcmax
             assert_bits("%s cmax" % what, self.dcmax.cpu().numpy(), cmax)
-        same = lambda t, a: numpy.array_equal(t.cpu().numpy().view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))   # noqa: E731
         for tag, t, a in [("u", self.du, c["u"]), ("v", self.dv, c["v"]), ("hx", self.dhx, c["hx"]), ("hy", self.dhy, c["hy"])] + \
                 [(k, self.dev[k], x) for k, x in c["fields"].items()]:
-            assert same(t, a), (what, tag, "read only")
-        for tag, (t, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + t.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
+            assert Poisoned.read_only(t, a), (what, tag, "read only")
+        self.mem.check_around(what)
         return want, cmax
 
 
@@ -189,22 +179,15 @@ def raw_launch(eng, c, names=None, cmax=True, alias=None, extents=None):
         g.fields[f], g.out[f] = t[k].data_ptr(), t["out " + k].data_ptr()
     for slot, key in (alias or ()):
         g.out[slot] = t[key].data_ptr()
-    fn = eng.lib.spc_les_advect_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_advect_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(g), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
+    rc = abi_call(eng, "spc_les_advect", g)
     return rc, {k: t["out " + k].cpu().numpy() for k in names}, t["cmax"].cpu().numpy() if cmax else None
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, n=3):
     """U, V (the winds themselves), THL and QT against the oracle, cmax included; the answer is not the input where a cell has
     another cell as its neighbour"""
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     want, cmax = Run(eng, c).check("n %d plane %s ktot %d" % (n, plane, ktot))
     assert (cmax >= 0).all() and not numpy.signbit(cmax).any()
     if min(plane) > 2 or (max(plane) > 2 and ktot > 1):          # (every face of level 0 of a plane of 2 cancels: winds())
@@ -214,7 +197,7 @@ def check_parity(eng, plane, ktot, n=3):
 def check_rows(eng, ktot):
     """n = 1, 2, 5 at 3 x 5: hx and hy differ per LES and from each other, so a wrong l or a swapped coefficient shows"""
     for n in NS:
-        c = case((n, 3, 5, ktot), _np(eng), seed=1)
+        c = case((n, 3, 5, ktot), np_of(eng), seed=1)
         assert (c["hx"] != c["hy"]).all() and (n == 1 or c["hx"][0] != c["hx"][1])
         Run(eng, c).check("rows n %d ktot %d" % (n, ktot))
 
@@ -246,13 +229,13 @@ def check_strips(eng):
     assert strip >= 64 and 1 <= rows < many_rows
     for n, itot, jtot, ktot in strip_shapes(strip, rows, many_rows):
         assert eng.advect_strip(n, itot, jtot, ktot) == (strip, many_rows if n == MANY else rows)
-        Run(eng, case((n, itot, jtot, ktot), _np(eng), seed=2, names=("U", "QT"))).check("strip %d x %d x %d x %d" % (n, itot, jtot, ktot))
+        Run(eng, case((n, itot, jtot, ktot), np_of(eng), seed=2, names=("U", "QT"))).check("strip %d x %d x %d x %d" % (n, itot, jtot, ktot))
     return strip, rows, many_rows
 
 
 def check_fields(eng):
     """1 to 6 fields with U and V among them, 1 to 6 without, and without cmax"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for nf in range(1, 7):
         Run(eng, case((2, 3, 5, 65), dtype, seed=3, names=ALL_NAMES[:nf])).check("%d fields with the winds" % nf)
         c = case((2, 3, 5, 65), dtype, seed=4, names=ALL_NAMES[:nf])
@@ -271,7 +254,7 @@ def check_fields(eng):
 def check_probe(eng):
     """n_fields == 0 with cmax: the Courant sums of the winds alone, bit-equal to those of a full launch and to the oracle's;
     a wind that blows north only (pn alone carries the sum)"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for shape in ((1, 1, 1, 1), (2, 3, 5, 64), (5, 9, 9, 161)):
         c = case(shape, dtype, seed=6)
         want = oracle(c)[1]
@@ -290,13 +273,13 @@ def check_probe(eng):
 
 def check_alignment(eng, lead, ktot=65):
     """views one (or more) elements off the 16-byte grid"""
-    Run(eng, case((3, 3, 5, ktot), _np(eng), seed=10 + lead), lead=lead).check("lead %d ktot %d" % (lead, ktot))
+    Run(eng, case((3, 3, 5, ktot), np_of(eng), seed=10 + lead), lead=lead).check("lead %d ktot %d" % (lead, ktot))
 
 
 def check_signs(eng):
     """winds of one sign each way (the upwind side is the same at every face), all four combinations, and no wind at all: the
     fields keep their bits and cmax is +0"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for su in (1, -1):
         for sv in (1, -1):
             c = case((2, 3, 5, 9), dtype, seed=8, names=("THL", "QT"))
@@ -342,7 +325,7 @@ def check_special(eng):
     """NaN, +-inf and -0.0 planted in single cells of a field and a NaN in one wind cell: every output is the oracle's, the cells
     further than one step away hold the bits of a run without them (QT feels only the NaN wind); a constant field keeps its
     bits and a -0.0 constant comes out +0.0"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c, s, mask = special_case(dtype)
     clean, clean_cmax = Run(eng, c).check("clean")
     r = Run(eng, s)
@@ -394,7 +377,7 @@ def bad_calls(eng, t, o, u, v, hx, hy):
 def check_refusals(eng):
     """n = 0 is a no-op; no field without cmax, an output that is an input, cmax or another output and an extent below 1 are
     refused by the library and by the engine, and no refused call touches anything"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=11)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     E = _abi.SPC_ERR_INVALID_ARGUMENT
@@ -430,36 +413,28 @@ def check_refusals(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle, cmax included"""
-    c = case((n, 3, 5, 40), _np(one), seed=n)
+    c = case((n, 3, 5, 40), np_of(one), seed=n)
     want, cmax = oracle(c)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
-    for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+    for tag, eng, up in on_both(one, multi, n):
         u, v = up(c["u"]), up(c["v"])
         t = {k: (u if x is c["u"] else v if x is c["v"] else up(x)) for k, x in c["fields"].items()}
         o = {k: up(numpy.full_like(x, OUT_FILL)) for k, x in c["fields"].items()}
         got = eng.les_advect(t, o, u, v, up(c["hx"]), up(c["hy"]))
         multi.synchronize()
-        if tag == "multi":
-            blocks = [int(p.shape[0]) for p in o["QT"].parts]
         for k in NAMES:
-            assert_bits("%s %s" % (tag, k), wpr._host(o[k]), want[k])
-        assert_bits("%s cmax" % tag, wpr._host(got), cmax)
+            assert_bits("%s %s" % (tag, k), host_of(o[k]), want[k])
+        assert_bits("%s cmax" % tag, host_of(got), cmax)
         probe = eng.les_advect({}, {}, u, v, up(c["hx"]), up(c["hy"]))
         multi.synchronize()
-        assert_bits("%s probe" % tag, wpr._host(probe), cmax)
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+        assert_bits("%s probe" % tag, host_of(probe), cmax)
+    return blocks_of(o["QT"], multi, n)
 
 
 BODIES = ("parity", "rows", "strips", "fields", "probe", "alignment", "signs", "special", "refusals")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 3, 64, 161)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 3, 64, 161)]),
             ("rows", lambda: [check_rows(eng, k) for k in (1, 65)]),
             ("strips", lambda: check_strips(eng)),
             ("fields", lambda: check_fields(eng)),
@@ -468,13 +443,12 @@ def check_everything(eng):
             ("signs", lambda: check_signs(eng)),
             ("special", lambda: check_special(eng)),
             ("refusals", lambda: check_refusals(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_advect (CPU suite) -------------------------------------------------------------------------
@@ -587,61 +561,26 @@ def ensemble_run(engine, n, thermo, device, micro=False, diffuse=False, advect=T
     evolve_model_batched with one variability nudge (constantT) before the last; after each of them every profile and the
     fields.  ``dx``: the grid spacing along i (the winds are about 5 m/s and -2 m/s and a step is 900 s: the default 200 m asks
     for tens of substeps); ``spike``: QT raised in one column of every LES.  Returns (ens, list of records)"""
-    spcpl.set_engine(engine)
-    cls = models.DeviceLESEnsemble if device else (HostThermoAdvectLESEnsemble if thermo else HostAdvectLESEnsemble)
-    fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
-    stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
-    gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
-    rng = numpy.random.default_rng(n + 100)
-    fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
-              "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}
-    if thermo:
-        del fields["Qsat"]
-        fields["THL"] = fields["THL"] - 25.0
-        fields["QT"] = fields["QT"] * 0.35
-        fields["QT"][:, 2, 1, :] *= 2.0
-    if spike:
-        fields["QT"][:, 1, 3, :] *= 1.5
-    if micro:
-        fields["QR"] = numpy.random.default_rng(n).random((n, itot, jtot, nL)) * 1e-5
-    ens.attach_fields({k: v.copy() for k, v in fields.items()})
-    ens.p["presf"] = stack("presf")
-    ens.ql_ref = stack("ql_ref")
-    ens.model_time = 900.0
-    if thermo:
-        ens.enable_thermo()
-    if diffuse:
-        ens.enable_diffusion()
-    if micro:
-        ens.enable_microphysics(qc0=1e-4, v_fall=0.05)
-    if advect:
-        ens.enable_advection(dx=dx, dy=None if dx is None else 1.5 * numpy.asarray(dx))
-    rng = numpy.random.default_rng(5)
-    ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, nL)), QT=rng.normal(0, 2e-7, (n, nL)), U=rng.normal(0, 1e-4, (n, nL)),
-                             WT_surf=ldr.WT * (0.5 + rng.random(n)), WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
-    log = []
+    def spiked(fields):
+        if spike:
+            fields["QT"][:, 1, 3, :] *= 1.5
 
-    def record():
-        prof = {k: numpy.empty((n, nL)) for k in ("U", "V", "THL", "QT", "QL")}
-        ens.get_profiles_batched(tuple(prof), prof)
-        rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("U", "V", "QT", "THL", "QL") + (("QR",) if micro else ())})
-        rec["TWP"] = numpy.array(wpr._host(ens.get_water_paths_batched(("TWP",))["TWP"]))
+    def record(ens, rec):
+        rec["TWP"] = numpy.array(host_of(ens.get_water_paths_batched(("TWP",))["TWP"]))
         if advect:
-            rec["substeps"] = numpy.array([-1 if ens.advect_substeps is None else ens.advect_substeps], dtype=numpy.float64)
-            rec["courant"] = numpy.array([-1.0 if ens.advect_courant is None else ens.advect_courant])
-        log.append(rec)
-    record()
-    for step in range(steps):
-        if step == steps - 1:
-            numpy.random.seed(11)
-            spcpl.variability_nudge_ensemble(ens, 900.0, True, write=False)
-            record()
-        ens.evolve_model_batched(1800.0 + 900.0 * step)
-        record()
-    return ens, log
+            record_substeps(ens, rec)
+    return ensemble_case(engine, n, models.DeviceLESEnsemble if device else (HostThermoAdvectLESEnsemble if thermo else HostAdvectLESEnsemble),
+                         thermo=thermo, micro=micro, diffuse=diffuse, edit=spiked,
+                         advection=dict(dx=dx, dy=None if dx is None else 1.5 * numpy.asarray(dx)) if advect else None, record=record,
+                         itot=itot, jtot=jtot, nL=nL, steps=steps)
+
+
+def record_substeps(ens, rec, z=False):
+    """the substeps and the Courant sum (``z``: and the vertical one) of the last step into a record of ensemble_case"""
+    rec["substeps"] = numpy.array([-1 if ens.advect_substeps is None else ens.advect_substeps], dtype=numpy.float64)
+    rec["courant"] = numpy.array([-1.0 if ens.advect_courant is None else ens.advect_courant])
+    if z:
+        rec["courant z"] = numpy.array([-1.0 if ens.advect_courant_z is None else ens.advect_courant_z])
 
 
 DX_ONE = 60000.0                                                  # c = 0.5 * 900 / 60000 * 2 |u| of at most ~9 m/s: below cfl, one substep

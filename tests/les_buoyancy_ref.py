@@ -5,29 +5,23 @@ CPU suite.
 
 The oracle spells the rule out one operation per NumPy call in the element type with dtype-typed scalars, vectorised over the
 columns, a Python loop over k with two ``numpy.subtract`` per level for the chain, so nothing fuses.  Every device array of the
-bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes behind it (and in front of a view off
+bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes behind it (and in front of a view off
 the 16-byte grid) are checked after the launch."""
-import ctypes
 
 import numpy
 import torch
 
-from sp_coupler_amd import _abi, models, spcpl
+from sp_coupler_amd import _abi, models
 from sp_coupler_amd import advection as adv
 from sp_coupler_amd import buoyancy as buo
-from sp_coupler_amd import radiation as rad
 from tests import les_advect_ref as lar
-from tests import les_diffuse_ref as ldr
 from tests import les_micro_ref as lmr
 from tests import les_radiate_ref as lrr
 from tests import les_vadvect_ref as lvr
-from tests import les_water_paths_ref as wpr
-from tests import slab_edges
 from tests.gpu_util import assert_bits
-from tests.test_vnudge import make_les_fields
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, cols_table, ensemble_case, fill_args, host_of, np_of, on_both, run_bodies)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 #: no neighbour at all, planes of two along one axis and along both (gx or gy +0), an odd plane, the flagship's, and one wider
 #: than a wave along j
 PLANES = [(1, 1), (1, 2), (2, 1), (2, 2), (3, 5), (8, 8), (5, 33)]
@@ -124,10 +118,6 @@ def oracle(c, ql=True):
 
 
 # -- device plumbing ---------------------------------------------------------------------------------------------------------
-def _same(t, a):
-    return numpy.array_equal(numpy.ascontiguousarray(t.cpu().numpy()).view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))
-
-
 class Run:
     """one call of ``eng.les_buoyancy`` with every array inside a poisoned buffer; ``check`` compares phi, psfc, u, v and amax
     with the oracle bit for bit (amax: a NaN where the oracle's is one), the read-only inputs with what was uploaded, and looks
@@ -135,18 +125,9 @@ class Run:
     ``pad``: elements between the rows of t0, lex and s (pitched profiles)"""
 
     def __init__(self, eng, c, leads=(0, 0, 0, 0), pad=0, ql=True, psfc=True, amax=True):
-        self.eng, self.c, self.pad, self.ql = eng, c, pad, ql
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=0):
-            t, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (t, b, lead, poison)
-            return t
-
-        def prof(tag, a):
-            wide = numpy.full((a.shape[0], a.shape[1] + pad), 1e30, dtype=a.dtype)
-            wide[:, :a.shape[1]] = a
-            return put(tag, wide, 1e30)[:, :a.shape[1]]
+        self.eng, self.c, self.ql = eng, c, ql
+        self.mem = Poisoned(eng)
+        put, prof = self.mem.put, lambda tag, a: self.mem.rows(tag, a, 1e30, pad=pad)          # noqa: E731
         nan = float("nan")
         self.dthl, self.dqt = put("thl", c["thl"], nan, leads[0]), put("qt", c["qt"], nan, leads[1])
         self.dql = put("ql", c["ql"], nan, leads[2]) if ql else None
@@ -176,13 +157,8 @@ class Run:
             assert_bits("%s amax" % what, self.damax.cpu().numpy(), amax)
         for tag, t, a in (("thl", self.dthl, c["thl"]), ("qt", self.dqt, c["qt"]), ("ql", self.dql, c["ql"]), ("hx", self.dhx, c["hx"]),
                           ("hy", self.dhy, c["hy"]), ("t0", self.dt0, c["t0"]), ("lex", self.dlex, c["lex"]), ("s", self.ds, c["s"])):
-            assert t is None or _same(t, a), (what, tag, "read only")
-        ktot = c["thl"].shape[-1]
-        for tag, (t, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + t.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
-            if self.pad and tag in ("t0", "lex", "s"):
-                assert bool((t[:, ktot:] == poison).all()), (what, tag, "written between the rows")
+            assert t is None or Poisoned.read_only(t, a), (what, tag, "read only")
+        self.mem.check_around(what)
         return want
 
 
@@ -203,23 +179,9 @@ def raw_launch(eng, c, alias=None, extents=None, null=()):
     t["amax"] = dev(numpy.full_like(c["hx"], -5.0))
     a = _abi.LesBuoyancyArgs()
     a.n_les, a.itot, a.jtot, a.ktot, a.pitch_prof, a.c1, a.c2 = n, itot, jtot, ktot, ktot, buo.C1, buo.C2
-    for k in PTRS:
-        setattr(a, k, t[k].data_ptr())
-    for member, key in (alias or ()):
-        setattr(a, member, t[key].data_ptr())
-    for key, val in (extents or {}).items():
-        setattr(a, key, val)
-    for key in null:
-        setattr(a, key, None)
-    fn = eng.lib.spc_les_buoyancy_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_buoyancy_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
+    fill_args(a, t, PTRS, alias, extents, null)
+    rc = abi_call(eng, "spc_les_buoyancy", a)
     return rc, {k: t[k].cpu().numpy() for k in PTRS}
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 def derived_cols(ktot, esize):
@@ -229,26 +191,11 @@ def derived_cols(ktot, esize):
     return 64 if 64 * col <= 64 * 1024 else 32 if 32 * col <= 64 * 1024 else 16 if 16 * col <= 160 * 1024 else 0
 
 
-def cols_table(cols_of, top=3000):
-    """(dict C -> the smallest ktot with that many columns per workgroup, the ktot at which the count changes, the first
-    unsupported ktot) of ``cols_of(ktot)``"""
-    first, changes, last = {}, [], None
-    for ktot in range(1, top):
-        C = cols_of(ktot)
-        if C != last and last is not None:
-            changes.append(ktot)
-        last = C
-        if C == 0:
-            return first, changes[:-1], ktot
-        first.setdefault(C, ktot)
-    raise AssertionError("no unsupported ktot below %d" % top)
-
-
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, n=3):
     """phi, psfc, u, v and amax against the oracle with everything asked for and with no ql, psfc and amax; the answer is not the
     input where a cell has two different neighbours"""
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     assert (c["ql"] > 0).any() and (c["ql"] == 0).any() and (c["hx"] != c["hy"]).all()
     what = "n %d plane %s ktot %d" % (n, plane, ktot)
     phi, psfc, un, vn, amax = Run(eng, c).check(what)
@@ -271,7 +218,7 @@ def check_rows(eng, ktot):
     the same with pitched profiles"""
     for n in NS:
         for pad in (0, 3):
-            c = case((n, 3, 5, ktot), _np(eng), seed=1)
+            c = case((n, 3, 5, ktot), np_of(eng), seed=1)
             assert (c["hx"] != c["hy"]).all()
             if n > 1:
                 assert not numpy.array_equal(c["t0"][0], c["t0"][1]) and c["hx"][0] != c["hx"][1] and not numpy.array_equal(c["s"][0], c["s"][1])
@@ -283,7 +230,7 @@ def check_tiles(eng):
     tile ends inside a row), as cols LES of one column (l per lane) and as LES of 1 x 3 (a tile ends inside an LES); ktot on
     both sides of every change of C; 17 columns at the last supported ktot; the first unsupported ktot refused.  The thresholds
     the library reports are the ones that follow from the LDS and the pitch (derived_cols)."""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     esize = numpy.dtype(dtype).itemsize
     first, changes, bad = table = cols_table(eng.buoyancy_cols_per_block)
     assert table == cols_table(lambda k: derived_cols(k, esize))
@@ -323,7 +270,7 @@ def check_strips(eng):
     strip, rows = eng.advect_strip(2, 8, 8, 160)
     assert strip >= 64 and 1 <= rows < 33
     for shape in strip_shapes(strip):
-        Run(eng, case(shape, _np(eng), seed=2)).check("strip %d x %d x %d x %d" % shape)
+        Run(eng, case(shape, np_of(eng), seed=2)).check("strip %d x %d x %d x %d" % shape)
     return strip, rows
 
 
@@ -331,7 +278,7 @@ def check_outputs(eng):
     """with and without ql, psfc and amax: phi, u and v do not depend on psfc and amax, and what is not asked for is not written;
     the C entry point itself"""
     for ktot in (2, 65):
-        c = case((2, 3, 4, ktot), _np(eng), seed=6)
+        c = case((2, 3, 4, ktot), np_of(eng), seed=6)
         for ql in (True, False):
             for psfc in (True, False):
                 for amax in (True, False):
@@ -345,7 +292,7 @@ def check_outputs(eng):
 
 def check_alignment(eng, leads, ktot=65, pad=0):
     """views off the 16-byte grid: all equally (the 16-byte mover with a head and a tail) or each on its own (single elements)"""
-    c = case((3, 2, 3, ktot), _np(eng), seed=sum(leads) + 10 * pad)
+    c = case((3, 2, 3, ktot), np_of(eng), seed=sum(leads) + 10 * pad)
     Run(eng, c, leads=leads, pad=pad).check("leads %s pad %d ktot %d" % (leads, pad, ktot))
 
 
@@ -399,7 +346,7 @@ def check_nan_reach(clean, got, shape):
 
 def check_special(eng):
     """the uniform state (every wind keeps its bits, -0.0 included, amax = +0, phi the same in every column) and the NaN's reach"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = uniform_case(dtype)
     phi, psfc, un, vn, amax = Run(eng, c).check("uniform")
     assert_bits("uniform: u", un, c["u"])
@@ -417,7 +364,7 @@ def check_special(eng):
 def check_refusals(eng):
     """n = 0 is a no-op; pitch_prof < ktot, a NULL required pointer, and phi, u, v, psfc or amax equal to an input or to each other
     are refused by the library; the engine refuses the same aliases and bad shapes; no refused call writes"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=13)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
 
@@ -472,31 +419,23 @@ def check_refusals(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    c = case((n, 3, 4, 40), _np(one), seed=n)
+    c = case((n, 3, 4, 40), np_of(one), seed=n)
     want = oracle(c)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
-    for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+    for tag, eng, up in on_both(one, multi, n):
         t = {k: up(c[k]) for k in ("thl", "qt", "ql", "u", "v", "hx", "hy", "t0", "lex", "s")}
         phi, psfc = up(numpy.full_like(c["thl"], OUT_FILL)), up(numpy.full(c["thl"].shape[:3], OUT_FILL, dtype=c["thl"].dtype))
         amax = eng.les_buoyancy(*[t[k] for k in ("thl", "qt", "ql", "u", "v", "hx", "hy", "t0", "lex", "s")], phi, psfc=psfc)
         multi.synchronize()
-        if tag == "multi":
-            blocks = [int(p.shape[0]) for p in t["u"].parts]
         for k, got, w in zip(("phi", "psfc", "u", "v", "amax"), (phi, psfc, t["u"], t["v"], amax), want):
-            assert_bits("%s %s" % (tag, k), wpr._host(got), w)
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+            assert_bits("%s %s" % (tag, k), host_of(got), w)
+    return blocks_of(t["u"], multi, n)
 
 
 BODIES = ("parity", "rows", "tiles", "strips", "outputs", "alignment", "special", "refusals")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 65)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 65)]),
             ("rows", lambda: [check_rows(eng, k) for k in (2, 65)]),
             ("tiles", lambda: check_tiles(eng)),
             ("strips", lambda: check_strips(eng)),
@@ -504,13 +443,12 @@ def check_everything(eng):
             ("alignment", lambda: [check_alignment(eng, *a) for a in (((1, 1, 1, 1), 65, 0), ((1, 0, 3, 2), 64, 0), ((3, 3, 3, 1), 7, 5))]),
             ("special", lambda: check_special(eng)),
             ("refusals", lambda: check_refusals(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_buoyancy (CPU suite) -----------------------------------------------------------------------
@@ -613,72 +551,34 @@ def ensemble_run(engine, n, device, buoyancy=True, thermo=False, micro=False, di
     and enable_buoyancy() (``buoyancy`` None: never called, and the host twin is the one of the K18 tests) through ``steps`` calls
     of evolve_model_batched and one variability nudge (constantT) before the last; after each of them every profile, the fields,
     the substeps, phi and the largest wind change.  Returns (ens, list of records)"""
-    spcpl.set_engine(engine)
     if device:
         cls = models.DeviceLESEnsemble
     elif buoyancy:
         cls = HostThermoBuoyancyLESEnsemble if thermo else HostBuoyancyLESEnsemble
     else:
         cls = lrr.HostThermoRadiateLESEnsemble if thermo else lrr.HostRadiateLESEnsemble
-    fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
-    stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
-    gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
-    rng = numpy.random.default_rng(n + 100)
-    fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
-              "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}
-    fields["U"][:, lvr.RAISED[0], lvr.RAISED[1], :] += 2.0
-    if thermo:
-        del fields["Qsat"]
-        fields["THL"] = fields["THL"] - 25.0
-        fields["QT"] = fields["QT"] * 0.35
-        fields["QT"][:, 2, 1, :] *= 2.0
-    if micro:
-        fields["QR"] = numpy.random.default_rng(n).random((n, itot, jtot, nL)) * 1e-5
-    ens.attach_fields({k: v.copy() for k, v in fields.items()})
-    ens.p["presf"] = stack("presf")
-    ens.ql_ref = stack("ql_ref")
-    ens.model_time = 900.0
-    if thermo:
-        ens.enable_thermo()
-    if diffuse:
-        ens.enable_diffusion()
-    if micro:
-        ens.enable_microphysics(qc0=1e-4, v_fall=0.05)
-    ens.enable_advection(dx=DX, dy=1.5 * DX, vertical=True)
-    if radiate:
-        ens.enable_radiation(f0=rad.F0 * (1.0 + 0.05 * numpy.arange(n)), f1=rad.F1 * (1.0 + 0.1 * (numpy.arange(n) % 3)))
-    if buoyancy:
-        ens.enable_buoyancy(**({} if wave_speed is None else {"wave_speed": wave_speed}))
-    rng = numpy.random.default_rng(5)
-    ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, nL)), QT=rng.normal(0, 2e-7, (n, nL)), U=rng.normal(0, 1e-4, (n, nL)),
-                             WT_surf=ldr.WT * (0.5 + rng.random(n)), WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
-    log = []
 
-    def record():
-        prof = {k: numpy.empty((n, nL)) for k in ("U", "V", "THL", "QT", "QL")}
-        ens.get_profiles_batched(tuple(prof), prof)
-        rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("U", "V", "QT", "THL", "QL") + (("QR",) if micro else ())})
-        rec["substeps"] = numpy.array([-1 if ens.advect_substeps is None else ens.advect_substeps], dtype=numpy.float64)
-        rec["courant"] = numpy.array([-1.0 if ens.advect_courant is None else ens.advect_courant])
-        rec["courant z"] = numpy.array([-1.0 if ens.advect_courant_z is None else ens.advect_courant_z])
+    def enable(ens):
         if buoyancy:
-            phi = ens.get_pressure_batched()
-            rec["phi"] = numpy.zeros((n, itot, jtot, nL)) if phi is None else numpy.array(wpr._host(phi))
-            rec["wind change"] = numpy.array([-1.0 if ens.buoyancy_wind_change is None else ens.buoyancy_wind_change])
-        log.append(rec)
-    assert not buoyancy or ens.get_pressure_batched() is None
-    record()
-    for step in range(steps):
-        if step == steps - 1:
-            numpy.random.seed(11)
-            spcpl.variability_nudge_ensemble(ens, 900.0, True, write=False)
-            record()
-        ens.evolve_model_batched(1800.0 + 900.0 * step)
-        record()
-    return ens, log
+            ens.enable_buoyancy(**({} if wave_speed is None else {"wave_speed": wave_speed}))
+
+    def record(ens, rec):
+        lar.record_substeps(ens, rec, z=True)
+        if buoyancy:
+            record_pressure(ens, rec)
+
+    def before(ens):
+        assert not buoyancy or ens.get_pressure_batched() is None
+    return ensemble_case(engine, n, cls, thermo=thermo, micro=micro, diffuse=diffuse, edit=lvr.raise_u, advection=dict(dx=DX, dy=1.5 * DX, vertical=True),
+                         radiation=lrr.radiation_of(n, "f0", "f1") if radiate else None, enable=enable, record=record, before=before,
+                         itot=itot, jtot=jtot, nL=nL, steps=steps)
+
+
+def record_pressure(ens, rec):
+    """phi (zeros before the first step) and the largest wind change of the last step into a record of ensemble_case"""
+    phi = ens.get_pressure_batched()
+    rec["phi"] = numpy.zeros(rec["field U"].shape) if phi is None else numpy.array(host_of(phi))
+    rec["wind change"] = numpy.array([-1.0 if ens.buoyancy_wind_change is None else ens.buoyancy_wind_change])
 
 
 def check_ensemble(one, engines, n, variant):

@@ -5,23 +5,20 @@ the CPU suite.
 
 The oracle spells the rule out one operation per NumPy call in the element type, vectorised over the columns, a Python loop
 over k, so nothing fuses.  Every device array of the bodies is the LEADING part of a poisoned buffer
-(tests/slab_edges.with_tail); the bytes behind it (and in front of a view off the 16-byte grid) are checked after the launch."""
-import ctypes
+(tests/les_harness.Poisoned); the bytes behind it (and in front of a view off the 16-byte grid) are checked after the launch."""
 
 import numpy
 import torch
 
-from sp_coupler_amd import _abi, models, spcpl
+from sp_coupler_amd import _abi, models
 from sp_coupler_amd import diffusion as df
 from tests import les_micro_ref as lmr
 from tests import les_thermo_ref as ltr
-from tests import les_water_paths_ref as wpr
-from tests import slab_edges, slab_ref
+from tests import slab_ref
 from tests.gpu_util import assert_bits
-from tests.test_vnudge import make_les_fields
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, WQ, WT, abi_call, blocks_of, ensemble_case, host_of, np_of, on_both, run_bodies)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 #: tiles that hold many LES (1 x 1), tiles that straddle LES (3 x 5), a tile that is exactly one LES (8 x 8 at 64 columns per
 #: workgroup), an LES of more than one tile plus a partial one (9 x 9)
 PLANES = [(1, 1), (3, 5), (8, 8), (9, 9)]
@@ -111,17 +108,9 @@ class Run:
         self.eng, self.c, self.pad = eng, c, pad
         first = next(iter(c["fields"].values()))
         dtype, (n, ktot) = first.dtype, (first.shape[0], first.shape[-1])
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=0):
-            v, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (v, b, lead, poison)
-            return v
-
-        def rows(tag, a, poison, lead):
-            wide = numpy.full((n, ktot + pad), poison, dtype=dtype)
-            wide[:, :ktot] = a
-            return put(tag, wide, poison, lead)[:, :ktot]
+        self.mem = Poisoned(eng)
+        put = self.mem.put
+        rows = lambda tag, a, poison, lead: self.mem.rows(tag, a, poison, lead, pad)        # noqa: E731
         self.dev = {k: put(k, x, float("nan"), lead) for k, x in c["fields"].items()}
         self.dprof = [rows("prof %d" % i, a, 1e30, lead_rows) for i, a in enumerate(c["prof"][:3])]
         self.ds0 = put("s0", c["prof"][3], 1e30, lead_rows) if with_s0 else None
@@ -136,18 +125,13 @@ class Run:
         assert self.got is None
         for k in c["fields"]:
             assert_bits("%s %s" % (what, k), self.dev[k].cpu().numpy(), want[k])
-        same = lambda t, a: numpy.array_equal(t.cpu().numpy().view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))   # noqa: E731
+        same = Poisoned.read_only
         for t, a in zip(self.dprof, c["prof"]):
             assert same(t, a), (what, "a profile", "read only")
         assert self.ds0 is None or same(self.ds0, c["prof"][3]), (what, "s0", "read only")
         for k, t in self.dflux.items():
             assert same(t, c["flux"][k]), (what, "flux " + k, "read only")
-        ktot = next(iter(c["fields"].values())).shape[-1]
-        for tag, (v, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + v.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
-            if self.pad and v.dim() == 2:
-                assert bool((v[:, ktot:] == poison).all()), (what, tag, "written between the rows")
+        self.mem.check_around(what)
         return want
 
 
@@ -172,15 +156,8 @@ def raw_launch(eng, c, names=None, flux=None, s0=True, alias=None):
             g.flux[f] = fl[k].data_ptr()
     for slot, key in (alias or ()):
         g.fields[slot] = t[key].data_ptr()
-    fn = eng.lib.spc_les_diffuse_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_diffuse_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(g), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
+    rc = abi_call(eng, "spc_les_diffuse", g)
     return rc, {k: t[k].cpu().numpy() for k in names}
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 def boundaries(cols_of):
@@ -205,7 +182,7 @@ def boundaries(cols_of):
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, n=3):
     """four fields, THL and QT with a flux, against the oracle; the answer is not the input"""
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     want = Run(eng, c).check("n %d plane %s ktot %d" % (n, plane, ktot))
     assert all((want[k] != c["fields"][k]).any() for k in (NAMES if ktot > 1 else ("THL", "QT")))       # (one level: only a flux changes it)
     assert (want["THL"][..., 0] > c["fields"]["THL"][..., 0]).any()
@@ -214,7 +191,7 @@ def check_parity(eng, plane, ktot, n=3):
 def check_rows(eng, ktot):
     """n = 1, 2, 5 at 3 x 5: the coefficient rows differ per LES (another density and another mixed layer), so a wrong l shows"""
     for n in NS:
-        c = case((n, 3, 5, ktot), _np(eng), seed=1)
+        c = case((n, 3, 5, ktot), np_of(eng), seed=1)
         if n > 1 and ktot > 1:
             assert not numpy.array_equal(c["prof"][1][0], c["prof"][1][1])
         Run(eng, c).check("rows n %d ktot %d" % (n, ktot))
@@ -226,7 +203,7 @@ def check_boundaries(eng):
     bounds = boundaries(eng.diffuse_cols_per_block)
     assert [c for _, c in bounds] == [64, 32, 32, 16, 16, 0], bounds
     for ktot, cols in bounds:
-        c = case((2, 3, 5, ktot), _np(eng), seed=2, names=("THL", "QT"))
+        c = case((2, 3, 5, ktot), np_of(eng), seed=2, names=("THL", "QT"))
         if cols:
             Run(eng, c).check("boundary ktot %d C %d" % (ktot, cols))
             continue
@@ -244,12 +221,12 @@ def check_tiles(eng, ktot):
     C = eng.diffuse_cols_per_block(ktot)
     for cols in (1, C - 1, C, C + 1, 2 * C - 1, 2 * C, 2 * C + 1, 3 * C - 1):
         for shape in ((1, 1, cols, ktot), (cols, 1, 1, ktot)):
-            Run(eng, case(shape, _np(eng), seed=3, names=("THL",))).check("tiles %s C %d" % (shape, C))
+            Run(eng, case(shape, np_of(eng), seed=3, names=("THL",))).check("tiles %s C %d" % (shape, C))
 
 
 def check_fields(eng):
     """1 to 4 fields; each flux NULL on its own; all NULL with s0 NULL; a flux for U as well"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for nf in (1, 2, 3, 4):
         Run(eng, case((2, 3, 5, 64), dtype, seed=4, names=NAMES[-nf:])).check("%d fields" % nf)
     for fluxes in (("THL",), ("QT",), (), ("U", "V", "THL", "QT")):
@@ -265,14 +242,14 @@ def check_fields(eng):
 
 def check_alignment(eng, lead, lead_rows, pad, ktot=65):
     """views one (or more) elements off the 16-byte grid and pitched profiles"""
-    c = case((3, 3, 5, ktot), _np(eng), seed=lead + 10 * lead_rows + 100 * pad)
+    c = case((3, 3, 5, ktot), np_of(eng), seed=lead + 10 * lead_rows + 100 * pad)
     Run(eng, c, lead=lead, lead_rows=lead_rows, pad=pad).check("lead %d %d pad %d ktot %d" % (lead, lead_rows, pad, ktot))
 
 
 def check_long_step(eng):
     """dt = 3600: |a| in the hundreds"""
     for ktot in (7, 160):
-        c = case((2, 3, 5, ktot), _np(eng), seed=7, dt=3600.0)
+        c = case((2, 3, 5, ktot), np_of(eng), seed=7, dt=3600.0)
         assert numpy.abs(c["prof"][0]).max() > 50
         Run(eng, c).check("dt 3600 ktot %d" % ktot)
 
@@ -304,7 +281,7 @@ def identity_case(dtype, ktot):
 def check_special(eng):
     """-0.0, NaN and +-inf planted in single columns: they spread through their column as the oracle says, and the bits of every
     other column equal a run without them; the identity coefficients keep every bit, -0.0 included"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for ktot in (7, 64):
         c, s, cols = special_case(dtype, ktot)
         clean = Run(eng, c).check("clean ktot %d" % ktot)
@@ -325,7 +302,7 @@ def check_special(eng):
 def check_refusals(eng):
     """n = 0 is a no-op; two equal fields, a field that is a profile and a flux without s0 are refused by the library and by
     the engine, and no refused call touches anything"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=9)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     t = {k: dev(v) for k, v in c["fields"].items()}
@@ -364,31 +341,23 @@ def check_refusals(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    c = case((n, 3, 5, 40), _np(one), seed=n)
+    c = case((n, 3, 5, 40), np_of(one), seed=n)
     want = oracle(c)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
-    for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+    for tag, eng, up in on_both(one, multi, n):
         t = {k: up(v) for k, v in c["fields"].items()}
         a, m, cp, s0 = (up(p) for p in c["prof"])
         assert eng.les_diffuse(t, a, m, cp, s0=s0, flux={k: up(v) for k, v in c["flux"].items()}) is None
         multi.synchronize()
-        if tag == "multi":
-            blocks = [int(p.shape[0]) for p in t["QT"].parts]
         for k in NAMES:
-            assert_bits("%s %s" % (tag, k), wpr._host(t[k]), want[k])
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+            assert_bits("%s %s" % (tag, k), host_of(t[k]), want[k])
+    return blocks_of(t["QT"], multi, n)
 
 
 BODIES = ("parity", "rows", "boundaries", "tiles", "fields", "alignment", "long_step", "special", "refusals")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 9, 64, 65, 160)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 9, 64, 65, 160)]),
             ("rows", lambda: [check_rows(eng, k) for k in (1, 7, 160)]),
             ("boundaries", lambda: check_boundaries(eng)),
             ("tiles", lambda: [check_tiles(eng, k) for k in (7, 300)]),
@@ -397,13 +366,12 @@ def check_everything(eng):
             ("long_step", lambda: check_long_step(eng)),
             ("special", lambda: check_special(eng)),
             ("refusals", lambda: check_refusals(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_diffuse (CPU suite) ----------------------------------------------------------------------
@@ -495,54 +463,10 @@ def ensemble_run(engine, n, thermo, device, micro=False, diffuse=True, itot=4, j
     """an ensemble with attached U, V, THL, QT (and Qsat, or thermo; QR with the microphysics) through ``steps`` calls of
     evolve_model_batched with non-zero wt and wq and one variability nudge (constantT) before the last; after each of them
     every profile and the fields.  Returns (ens, list of records)"""
-    spcpl.set_engine(engine)
-    cls = models.DeviceLESEnsemble if device else (HostThermoDiffuseLESEnsemble if thermo else HostDiffuseLESEnsemble)
-    fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
-    stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
-    gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
-    rng = numpy.random.default_rng(n + 100)
-    fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
-              "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}
-    if thermo:
-        del fields["Qsat"]
-        fields["THL"] = fields["THL"] - 25.0
-        fields["QT"] = fields["QT"] * 0.35
-        fields["QT"][:, 2, 1, :] *= 2.0
-    if micro:
-        fields["QR"] = numpy.random.default_rng(n).random((n, itot, jtot, nL)) * 1e-5
-    ens.attach_fields({k: v.copy() for k, v in fields.items()})
-    ens.p["presf"] = stack("presf")
-    ens.ql_ref = stack("ql_ref")
-    ens.model_time = 900.0
-    if thermo:
-        ens.enable_thermo()
-    if diffuse:
-        ens.enable_diffusion()
-    if micro:
-        ens.enable_microphysics(qc0=1e-4, v_fall=0.05)
-    rng = numpy.random.default_rng(5)
-    ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, nL)), QT=rng.normal(0, 2e-7, (n, nL)), U=rng.normal(0, 1e-4, (n, nL)),
-                             WT_surf=WT * (0.5 + rng.random(n)), WQ_surf=WQ * (0.5 + rng.random(n)))
-    log = []
-
-    def record():
-        prof = {k: numpy.empty((n, nL)) for k in ("U", "V", "THL", "QT", "QL")}
-        ens.get_profiles_batched(tuple(prof), prof)
-        rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("U", "V", "QT", "THL", "QL") + (("QR",) if micro else ())})
-        rec["TWP"] = numpy.array(wpr._host(ens.get_water_paths_batched(("TWP",))["TWP"]))
-        log.append(rec)
-    record()
-    for step in range(steps):
-        if step == steps - 1:
-            numpy.random.seed(11)
-            spcpl.variability_nudge_ensemble(ens, 900.0, True, write=False)
-            record()
-        ens.evolve_model_batched(1800.0 + 900.0 * step)
-        record()
-    return ens, log
+    def record(ens, rec):
+        rec["TWP"] = numpy.array(host_of(ens.get_water_paths_batched(("TWP",))["TWP"]))
+    return ensemble_case(engine, n, models.DeviceLESEnsemble if device else (HostThermoDiffuseLESEnsemble if thermo else HostDiffuseLESEnsemble),
+                         thermo=thermo, micro=micro, diffuse=diffuse, record=record, itot=itot, jtot=jtot, nL=nL, steps=steps)
 
 
 def check_ensemble(one, engines, n, thermo, micro=False, **kw):

@@ -4,10 +4,9 @@ libraries), the host twin of models.DeviceLESEnsemble's microphysics mode and an
 ``les_microphysics`` for the CPU suite.
 
 The oracle spells the rule out one operation per NumPy call in the element type, so nothing fuses.  Every device array of the
-bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes behind it (and in front of a view
+bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes behind it (and in front of a view
 off the 16-byte grid) are checked after the launch."""
 import contextlib
-import ctypes
 import os
 
 import numpy
@@ -18,12 +17,12 @@ from sp_coupler_amd import microphysics as mp
 from tests import les_advance_ref as lar
 from tests import les_thermo_ref as ltr
 from tests import les_water_paths_ref as wpr
-from tests import slab_edges, slab_ref
+from tests import slab_ref
 from tests.gpu_util import assert_bits
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, host_of, np_of, on_both, run_bodies)
 from tests.test_vnudge import make_les_fields
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 PLANES = [(1, 1), (3, 5), (8, 8)]
 #: the k + 1 neighbour inside a lane's vector, in the next lane and in the next wave (64 lanes of 2 doubles / 4 floats, or of
 #: one element), odd sizes (one element per lane) and multiples of 4 (16-byte accesses in both types)
@@ -161,17 +160,9 @@ class Run:
         self.opt = dict(thl=want_thl, temp=want_temp, rain=want_rain)
         dtype, shape = c["qt"].dtype, c["qt"].shape
         n, ktot = shape[0], shape[-1]
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=0):
-            v, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (v, b, lead, poison)
-            return v
-
-        def rows(tag, a, poison, lead):
-            wide = numpy.full((n, ktot + pad), poison, dtype=dtype)
-            wide[:, :ktot] = a
-            return put(tag, wide, poison, lead)[:, :ktot]
+        self.mem = Poisoned(eng)
+        put = self.mem.put
+        rows = lambda tag, a, poison, lead: self.mem.rows(tag, a, poison, lead, pad)        # noqa: E731
         self.dev = {k: put(k, c[k], float("nan"), lead) for k in ("qt", "ql", "qr") + (("thl",) if want_thl else ()) + (("temp",) if want_temp else ())}
         self.dev["qr_new"] = put("qr_new", numpy.full(shape, -3.0, dtype), -5.0, lead)
         self.drain = put("rain", c["rain"], float("nan"), lead) if want_rain else None
@@ -197,17 +188,12 @@ class Run:
                 assert_bits("%s %s" % (what, MEAN_KEYS[k]), t.cpu().numpy(), want[MEAN_KEYS[k]])
         else:
             assert self.got == {}, (what, self.got)
-        same = lambda t, a: numpy.array_equal(t.cpu().numpy().view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))   # noqa: E731
+        same = Poisoned.read_only
         for k in ("ql", "qr") + (("temp",) if self.opt["temp"] else ()):
             assert same(self.dev[k], c[k]), (what, k, "read only")
         for t, a in zip(self.dprof, c["prof"]):
             assert same(t, a), (what, "a profile", "read only")
-        ktot = c["qt"].shape[-1]
-        for tag, (v, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + v.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
-            if self.pad and v.dim() == 2:
-                assert bool((v[:, ktot:] == poison).all()), (what, tag, "written between the rows")
+        self.mem.check_around(what)
         return want
 
 
@@ -228,21 +214,14 @@ def raw_launch(eng, c, null=(), **consts):
     for k, v in t.items():
         if k not in null:
             setattr(a, k, v.data_ptr())
-    fn = eng.lib.spc_les_microphysics_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_microphysics_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
+    rc = abi_call(eng, "spc_les_microphysics", a)
     return rc, {k: (None if k in null else v.cpu().numpy()) for k, v in t.items()}
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, n=3):
     """qt, thl, qr_new, rain and the four means against the oracle; rain forms, falls and reaches the ground"""
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     want = Run(eng, c).check("n %d plane %s ktot %d" % (n, plane, ktot))
     if c["qt"].size >= 1000:
         assert (want["s"] > 0).any() and (want["s"] == 0).any() and (want["rain"] != c["rain"]).any()
@@ -252,7 +231,7 @@ def check_parity(eng, plane, ktot, n=3):
 def check_neighbour(eng, ktot, n):
     """the top level of every column is followed in memory by a level 0 that holds large qr (for the last column of LES l:
     level 0 of LES l + 1; behind the last LES: the NaN tail of the buffer)"""
-    c = case((n, 3, 5, ktot), _np(eng), seed=1, neighbour=True)
+    c = case((n, 3, 5, ktot), np_of(eng), seed=1, neighbour=True)
     want = Run(eng, c).check("neighbour n %d ktot %d" % (n, ktot))
     assert numpy.isfinite(want["qr_new"]).all() and (want["qr_new"][..., ktot - 1] < 4e-3).all() and (c["qr"][..., 0] >= 0.3).all()
 
@@ -261,18 +240,18 @@ def check_rows(eng, ktot):
     """itot * jtot = 1 ... 17: whole batches of the look-ahead, single rows behind them, fewer rows than one batch.
     ktot picks the instantiation (160: 16-byte accesses; 33: one element per lane)"""
     for plane in ROW_PLANES:
-        Run(eng, case((2,) + plane + (ktot,), _np(eng), seed=3)).check("plane %s ktot %d" % (plane, ktot))
+        Run(eng, case((2,) + plane + (ktot,), np_of(eng), seed=3)).check("plane %s ktot %d" % (plane, ktot))
 
 
 def check_alignment(eng, lead, lead_rows, pad):
     """views one (or more) elements off the 16-byte grid and pitched profiles / means: one element per lane"""
-    c = case((3, 3, 5, 64), _np(eng), seed=lead + 10 * lead_rows + 100 * pad, neighbour=True)
+    c = case((3, 3, 5, 64), np_of(eng), seed=lead + 10 * lead_rows + 100 * pad, neighbour=True)
     Run(eng, c, lead=lead, lead_rows=lead_rows, pad=pad).check("lead %d %d pad %d" % (lead, lead_rows, pad))
 
 
 def check_optional(eng):
     """thl, temp and rain NULL through the engine, no means; each optional pointer NULL on its own through the C ABI"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 3, 5, 64), dtype, seed=5)
     Run(eng, c, want_thl=False).check("thl NULL")
     Run(eng, c, want_temp=False).check("temp NULL")
@@ -297,11 +276,11 @@ def check_optional(eng):
 def check_special(eng):
     """NaN, +-inf and -0.0 in ql, qr and temp; temp exactly t_up and t_dn; ql = qt = -0.0; a NaN threshold"""
     for ktot in (7, 64):
-        c = case((3, 3, 5, ktot), _np(eng), seed=2, special=True)
+        c = case((3, 3, 5, ktot), np_of(eng), seed=2, special=True)
         want = Run(eng, c).check("special ktot %d" % ktot)
         assert numpy.isnan(want["qt"][:, 0, 0]).all() and numpy.isnan(want["qr_new"][:, 0, 1]).all() and numpy.isnan(want["qi_mean"]).all()
         assert numpy.signbit(want["qt"][:, 1, 4]).all() and (want["qt"][:, 1, 4] == 0).all()         # pt(9) of a 3 x 5 plane
-        c = case((3, 3, 5, ktot), _np(eng), seed=4)
+        c = case((3, 3, 5, ktot), np_of(eng), seed=4)
         want = Run(eng, c, qc0=float("nan")).check("qc0 NaN, ktot %d" % ktot)
         assert numpy.isnan(want["s"]).all()
 
@@ -309,14 +288,14 @@ def check_special(eng):
 def check_cap(eng):
     """dt = 3600: s reaches ql"""
     for ktot in (7, 160):
-        c = cap_case((2, 3, 5, ktot), _np(eng))
+        c = cap_case((2, 3, 5, ktot), np_of(eng))
         want = Run(eng, c).check("cap ktot %d" % ktot)
         assert ((want["s"] == c["ql"]) & (c["ql"] > 0)).any()
 
 
 def check_refusals(eng):
     """n = 0 is a no-op, ktot = 1 is refused, so is every aliased pair that is written"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=9)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     t = {k: dev(c[k]) for k in ("qt", "ql", "qr", "thl", "temp", "rain")}
@@ -362,27 +341,23 @@ def check_refusals(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    c = case((n, 3, 5, 40), _np(one), seed=n, neighbour=True)
+    c = case((n, 3, 5, 40), np_of(one), seed=n, neighbour=True)
     want = oracle(c)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
     res = {}
-    for tag, up in (("one", dev), ("multi", sh)):
+    for tag, eng, up in on_both(one, multi, n):
         t = {k: up(c[k]) for k in ("qt", "ql", "qr", "thl", "temp", "rain")}
         t["qr_new"] = up(numpy.full(c["qt"].shape, -3.0, dtype=c["qt"].dtype))
-        eng = one if tag == "one" else multi
         m = eng.les_microphysics(t["qt"], t["ql"], t["qr"], t["qr_new"], *[up(a) for a in c["prof"]], c["dt"], thl=t["thl"], temp=t["temp"],
                                  rain=t["rain"])
         res[tag] = (t, m)
     multi.synchronize()
-    blocks = [int(p.shape[0]) for p in res["multi"][0]["qt"].parts]
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
+    blocks = blocks_of(res["multi"][0]["qt"], multi, n)
     for tag, (t, m) in res.items():
         assert sorted(m) == ["QI", "QR", "QT", "THL"]
         for k in FIELD_OUTS:
-            assert_bits("%s %s" % (tag, k), wpr._host(t[k]), want[k])
+            assert_bits("%s %s" % (tag, k), host_of(t[k]), want[k])
         for k, name in MEAN_KEYS.items():
-            assert_bits("%s %s" % (tag, name), wpr._host(m[k]), want[name])
+            assert_bits("%s %s" % (tag, name), host_of(m[k]), want[name])
     return blocks
 
 
@@ -413,8 +388,8 @@ def check_many_waves(eng):
             check_neighbour(eng, ktot, 5)
         for ktot in (160, 65):
             for plane in ROW_PLANES:
-                Run(eng, case((5,) + plane + (ktot,), _np(eng), seed=8, neighbour=True)).check("many waves: plane %s ktot %d" % (plane, ktot))
-        c = case((5, 3, 5, 128), _np(eng), seed=12, neighbour=True)
+                Run(eng, case((5,) + plane + (ktot,), np_of(eng), seed=8, neighbour=True)).check("many waves: plane %s ktot %d" % (plane, ktot))
+        c = case((5, 3, 5, 128), np_of(eng), seed=12, neighbour=True)
         Run(eng, c, lead=1, lead_rows=1, pad=3).check("many waves: off the grid")
         check_special(eng)
 
@@ -422,10 +397,8 @@ def check_many_waves(eng):
 BODIES = ("parity", "neighbour", "rows", "alignment", "optional", "special", "cap", "refusals", "many_waves")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (2, 7, 64, 65, 160)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (2, 7, 64, 65, 160)]),
             ("neighbour", lambda: [check_neighbour(eng, k, n) for k in (3, 64, 66, 128) for n in (1, 5)]),
             ("rows", lambda: [check_rows(eng, k) for k in (160, 33)]),
             ("alignment", lambda: [check_alignment(eng, *a) for a in ((1, 0, 0), (0, 1, 0), (0, 0, 4), (0, 0, 3))]),
@@ -434,13 +407,12 @@ def check_everything(eng):
             ("cap", lambda: check_cap(eng)),
             ("refusals", lambda: check_refusals(eng)),
             ("many_waves", lambda: check_many_waves(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_microphysics (CPU suite) ---------------------------------------------------------------
@@ -587,10 +559,10 @@ def ensemble_run(engine, n, thermo, device, itot=4, jtot=5, nL=20, steps=3, micr
         ens.get_profiles_batched(tuple(prof), prof)
         rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
         rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("QT", "THL", "QL") + (("QR",) if micro else ())})
+        rec.update({"field " + k: numpy.array(host_of(ens.get_fields_batched(k))) for k in ("QT", "THL", "QL") + (("QR",) if micro else ())})
         if micro:
-            rec["rain2d"] = numpy.array(wpr._host(ens.rain2d))
-            rec["RWP"] = numpy.array(wpr._host(ens.get_water_paths_batched(("RWP",))["RWP"]))
+            rec["rain2d"] = numpy.array(host_of(ens.rain2d))
+            rec["RWP"] = numpy.array(host_of(ens.get_water_paths_batched(("RWP",))["RWP"]))
             rec["row RWP"] = numpy.array(ens[n - 1].get_field("RWP") if device else ens.row_field(n - 1, "RWP"))
         log.append(rec)
     record()

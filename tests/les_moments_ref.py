@@ -7,7 +7,6 @@ The oracle is the rule with a literal Python loop over (i, j), one NumPy call pe
 fuses.  Every device array of the bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes behind
 it (and in front of a view off the 16-byte grid, and between pitched rows) are checked after the launch, and the inputs are
 compared with what was uploaded."""
-import ctypes
 
 import numpy
 import torch
@@ -15,12 +14,11 @@ import torch
 from sp_coupler_amd import _abi, models, spcpl
 from sp_coupler_amd import statistics as st
 from tests import les_qt_local_ref as qlr
-from tests import les_water_paths_ref as wpr
 from tests import slab_edges
 from tests.gpu_util import assert_bits
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, host_of, np_of, on_both, run_bodies)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 #: one row (every deviation is zero), fewer rows than the loads in flight (2 x 3), whole rounds of loads (8 x 8: 64 rows) and a
 #: ragged last round (17 x 5: 85 rows)
 PLANES = [(1, 1), (2, 3), (8, 8), (17, 5)]
@@ -118,11 +116,7 @@ def pick(res, kinds, pairs):
 
 
 # -- device plumbing ---------------------------------------------------------------------------------------------------------
-_same, _sync = qlr._same, qlr._sync
-
-
-def _np(eng):
-    return NP[eng.dtype]
+_same, _sync = Poisoned.read_only, qlr._sync
 
 
 class Run:
@@ -203,10 +197,7 @@ def raw_launch(eng, fields, pairs=(), face=-1, kinds=KINDS, extents=None, alias=
             setattr(a, key, val)
     for member, i in null:
         getattr(a, member)[i] = None
-    fn = eng.lib.spc_les_moments_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_moments_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
+    rc = abi_call(eng, "spc_les_moments", a)
     for f, k in enumerate(names):
         assert _same(t[("fields", f)], fields[k])
     return rc, {key: v.cpu().numpy() for key, v in t.items() if key[0] != "fields"}
@@ -215,7 +206,7 @@ def raw_launch(eng, fields, pairs=(), face=-1, kinds=KINDS, extents=None, alias=
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, n=3):
     """five fields, three pairs, the face field in two of them, all four kinds; a plane of one row has no variance at all"""
-    fields = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    fields = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     res = Run(eng, fields, PAIRS3, "C").check("n %d plane %s ktot %d" % (n, plane, ktot))
     if tuple(plane) == (1, 1):
         for kind in ("var", "std", "cov"):
@@ -227,7 +218,7 @@ def check_parity(eng, plane, ktot, n=3):
 
 def check_counts(eng):
     """one field and eight, no pair and eight, a field in four pairs, (a, b) and (b, a), each kind alone, only the covariances"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for ktot in (7, 64):
         shape = (2, 2, 3, ktot)
         Run(eng, case(shape, dtype, 1, 1)).check("one field ktot %d" % ktot)
@@ -251,7 +242,7 @@ def check_rows(eng, ktot):
     8 all LES of a launch share one wave"""
     for n in NS:
         for pad in (0, 3, 4):
-            fields = case((n, 2, 3, ktot), _np(eng), seed=4 + n, n_fields=3)
+            fields = case((n, 2, 3, ktot), np_of(eng), seed=4 + n, n_fields=3)
             if n > 1:
                 assert not numpy.array_equal(fields["A"][0], fields["A"][1])
             Run(eng, fields, (("A", "C"),), "C", pad=pad).check("rows n %d ktot %d pad %d" % (n, ktot, pad))
@@ -260,7 +251,7 @@ def check_rows(eng, ktot):
 def check_face(eng):
     """the face field first, last and in the middle of the list; k = 0 and the seams between the vectors; NaN directly in front
     of every field's first element (x[-1] is never read); without ``face`` the bits are others"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     on_grid = 16 // numpy.dtype(dtype).itemsize
     for ktot in (2, 3, 8, 65):
         fields = case((2, 2, 3, ktot), dtype, seed=ktot, n_fields=3)
@@ -303,7 +294,7 @@ def special_cases(dtype, ktot=9):
 
 
 def check_special(eng):
-    dtype = _np(eng)
+    dtype = np_of(eng)
     cases = special_cases(dtype)
     res = {name: Run(eng, *c).check("special " + name) for name, c in cases.items()}
     clean, nan, inf, zero = res["clean"], res["nan"], res["inf"], res["zeros"]
@@ -337,7 +328,7 @@ def check_special(eng):
 def check_alignment(eng, ktot, pad=0, plane=(17, 5)):
     """views one, two and three elements off the 16-byte grid, every field differently (single elements whatever ktot), and
     all on it with a pitch that is off it"""
-    fields = case((2,) + plane + (ktot,), _np(eng), seed=ktot + pad)
+    fields = case((2,) + plane + (ktot,), np_of(eng), seed=ktot + pad)
     for leads in ({"A": 1, "B": 2, "C": 0, "D": 3, "E": 1}, {"A": 0, "B": 0, "C": 1, "D": 0, "E": 0}, {}):
         Run(eng, fields, PAIRS3, "C", leads=leads, pad=pad).check("leads %s ktot %d pad %d" % (leads, ktot, pad))
 
@@ -346,7 +337,7 @@ def check_refusals(eng):
     """n = 0 is a no-op; ktot == 1 is unsupported; N > 2^24, a pitch below ktot, a NULL field, no output, a bad pair, a bad
     face_field and an output that is a field or another output are refused by the library; the engine refuses the same and bad
     shapes; no refused call writes"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     fields = case((2, 2, 3, 8), dtype, seed=6, n_fields=3)
     pairs = ((0, 2), (1, 0))
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
@@ -421,7 +412,7 @@ def check_refusals(eng):
 def check_same_as_k10_k6(eng):
     """``mean`` is K10's slab mean of the same fields; ``std`` of a QT field K6 has nudged is K6's own qt_std"""
     from tests.test_vnudge import make_les_fields
-    dtype = _np(eng)
+    dtype = np_of(eng)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     for ktot in (7, 64):
         fields = case((3, 8, 8, ktot), dtype, seed=ktot)
@@ -447,40 +438,32 @@ def check_same_as_k10_k6(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    fields = case((n, 2, 3, 40), _np(one), seed=n, n_fields=3)
+    fields = case((n, 2, 3, 40), np_of(one), seed=n, n_fields=3)
     pairs = (("A", "C"), ("C", "B"))
     want = pick(les_moments(fields, pairs, "C"), KINDS, pairs)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
-    for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+    for tag, eng, up in on_both(one, multi, n):
         t = {k: up(v) for k, v in fields.items()}
         got = eng.les_moments(t, pairs, std=True, face="C")
         multi.synchronize()
-        if tag == "multi":
-            blocks = [int(p.shape[0]) for p in t["A"].parts]
-        same_results(tag, {kind: {key: wpr._host(v) for key, v in d.items()} for kind, d in got.items()}, want)
+        same_results(tag, {kind: {key: host_of(v) for key, v in d.items()} for kind, d in got.items()}, want)
         for k in fields:
-            assert qlr._same_host(wpr._host(t[k]), fields[k])
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+            assert qlr._same_host(host_of(t[k]), fields[k])
+    return blocks_of(t["A"], multi, n)
 
 
 def check_large_plane(eng):
     """ONE LES of 64 x 64 x 2 (4 096 rows: whole rounds of the long-plane launch) and of 33 x 31 x 5 (1 023 rows: the ragged
     tail of the load-ahead loop)"""
     for shape in ((1, 64, 64, 2), (1, 33, 31, 5)):
-        fields = case(shape, _np(eng), seed=shape[1], n_fields=2)
+        fields = case(shape, np_of(eng), seed=shape[1], n_fields=2)
         Run(eng, fields, (("B", "A"),), "A").check("large plane %s" % (shape,))
 
 
 BODIES = ("parity", "counts", "rows", "face", "special", "alignment", "refusals", "same_as_k10_k6", "large_plane")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (2, 7, 64, 65)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (2, 7, 64, 65)]),
             ("counts", lambda: check_counts(eng)),
             ("rows", lambda: [check_rows(eng, k) for k in (7, 8)]),
             ("face", lambda: check_face(eng)),
@@ -489,13 +472,12 @@ def check_everything(eng):
             ("refusals", lambda: check_refusals(eng)),
             ("same_as_k10_k6", lambda: check_same_as_k10_k6(eng)),
             ("large_plane", lambda: check_large_plane(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_moments (CPU suite) ------------------------------------------------------------------------
@@ -539,7 +521,7 @@ def twin_statistics(ens, w=None, names=None, pairs=None):
             if w is not None:
                 have[k] = numpy.asarray(w)
         elif k in f:
-            have[k] = numpy.asarray(wpr._host(ens.get_fields_batched(k)))
+            have[k] = numpy.asarray(host_of(ens.get_fields_batched(k)))
     pairs = [tuple(p) for p in (st.PAIRS if pairs is None else pairs) if p[0] in have and p[1] in have]
     keep = [k for k in names if k in have]
     need = {k: have[k] for k in st.FIELDS if k in keep or any(k in p for p in pairs)}
@@ -585,13 +567,13 @@ def ensemble_run(engine, n, calls=None, **kw):
         mid = launches()
         again = ens.get_statistics()
         ens.get_statistics_batched(("U", "QT"), (("THL", "QT"),))
-        want = twin_statistics(ens, None if w is None else wpr._host(w))
+        want = twin_statistics(ens, None if w is None else host_of(w))
         rec, ref = flat(host), flat(want)
         assert set(rec) == set(ref) and "TKE" in rec and "var QL" in rec and ("cov W-THL" in rec) == (w is not None), sorted(rec)
         for k in ref:
             assert_bits("statistics %s" % k, rec[k], ref[k])
             assert rec[k].dtype == numpy.float64 and rec[k].shape == (ens.n, ens.nL)
-        assert_bits("batched getter", wpr._host(dev["var"]["QT"]).astype(numpy.float64), host["var"]["QT"])
+        assert_bits("batched getter", host_of(dev["var"]["QT"]).astype(numpy.float64), host["var"]["QT"])
         for k, v in flat(again).items():
             assert_bits("second read %s" % k, v, rec[k])
         for i in sorted({0, ens.n - 1}):

@@ -4,27 +4,23 @@ libraries), the host twins of models.DeviceLESEnsemble's enable_qt_forcing() mod
 ``les_qt_local`` for the CPU suite.
 
 The oracle is the rule with a Python loop per (LES, level), one NumPy call per operation in the element type, so nothing fuses.
-Every device array of the bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes behind it (and
+Every device array of the bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes behind it (and
 in front of a view off the 16-byte grid, and between pitched rows) are checked after the launch."""
-import ctypes
 
 import numpy
 import torch
 
 from sp_coupler_amd import _abi, driver, models, spcpl
 from sp_coupler_amd import qt_forcing as qf
-from sp_coupler_amd import radiation as rad
-from tests import les_diffuse_ref as ldr
 from tests import les_micro_ref as lmr
 from tests import les_radiate_ref as lrr
 from tests import les_vadvect_ref as lvr
-from tests import les_water_paths_ref as wpr
-from tests import slab_edges, slab_ref
+from tests import slab_ref
 from tests.gpu_util import assert_bits
-from tests.test_vnudge import make_les_fields
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, ensemble_case, fill_args, host_of, np_of, on_both, run_bodies)
+from tests.test_vnudge import make_les_fields  # noqa: F401  (for the tests)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 #: one cell per plane (c is 0 or N: nothing may change), planes smaller than the row-lanes of a workgroup (2 x 3), of 64 rows
 #: (8 x 8: 4 or 16 rows per row-lane) and of 85 (17 x 5: the last round of loads is partial)
 PLANES = [(1, 1), (2, 3), (8, 8), (17, 5)]
@@ -151,10 +147,6 @@ def oracle(c):
 
 
 # -- device plumbing ---------------------------------------------------------------------------------------------------------
-def _same(t, a):
-    return numpy.array_equal(numpy.ascontiguousarray(t.cpu().numpy()).view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))
-
-
 def _sync(eng):
     if eng.device.type == "cuda":
         torch.cuda.synchronize(eng.device)
@@ -167,17 +159,9 @@ class Run:
 
     def __init__(self, eng, c, leads=(0, 0), pad=0, pad_count=0, split=0):
         self.eng, self.c, self.pad, self.pad_count = eng, c, pad, pad_count
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=0):
-            t, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (t, b, lead, poison)
-            return t
-
-        def rows(tag, a, fill, extra):
-            wide = numpy.full((a.shape[0], a.shape[1] + extra), fill, dtype=a.dtype)
-            wide[:, :a.shape[1]] = a
-            return put(tag, wide, fill)[:, :a.shape[1]]
+        self.mem = Poisoned(eng)
+        put = self.mem.put
+        rows = lambda tag, a, fill, extra: self.mem.rows(tag, a, fill, pad=extra)           # noqa: E731
         self.dqt = put("qt", c["qt"], float("nan"), leads[0])
         self.dql = put("ql", c["ql"], float("nan"), leads[1])
         self.da, self.dm = rows("a", c["a"], 1e30, pad), rows("qtm", c["qtm"], 1e30, pad)
@@ -193,13 +177,8 @@ class Run:
         got = self.dcount.cpu().numpy()
         assert numpy.array_equal(got, count), (what, "count", got[got != count][:8], count[got != count][:8])
         for tag, t, a in (("ql", self.dql, c["ql"]), ("a", self.da, c["a"]), ("qtm", self.dm, c["qtm"])):
-            assert _same(t, a), (what, tag, "read only")
-        ktot = c["qt"].shape[-1]
-        for tag, (t, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + t.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
-            if tag in ("a", "qtm", "count") and t.shape[1] > ktot:
-                assert bool((t[:, ktot:] == poison).all()), (what, tag, "written between the rows")
+            assert Poisoned.read_only(t, a), (what, tag, "read only")
+        self.mem.check_around(what)
         return new, count
 
 
@@ -215,30 +194,16 @@ def raw_launch(eng, c, alias=None, extents=None, null=()):
     t["count"] = dev(numpy.full((n, ktot), COUNT_FILL, dtype=numpy.int32))
     a = _abi.LesQtLocalArgs()
     a.n_les, a.itot, a.jtot, a.ktot, a.split, a.pitch_prof, a.pitch_count = n, itot, jtot, ktot, 0, ktot, ktot
-    for k in PTRS:
-        setattr(a, k, t[k].data_ptr())
-    for member, key in (alias or ()):
-        setattr(a, member, t[key].data_ptr())
-    for key, val in (extents or {}).items():
-        setattr(a, key, val)
-    for key in null:
-        setattr(a, key, None)
-    fn = eng.lib.spc_les_qt_local_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_qt_local_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
-    assert _same(t["ql"], c["ql"]) and _same(t["a"], c["a"]) and _same(t["qtm"], c["qtm"])
+    fill_args(a, t, PTRS, alias, extents, null)
+    rc = abi_call(eng, "spc_les_qt_local", a)
+    assert Poisoned.read_only(t["ql"], c["ql"]) and Poisoned.read_only(t["a"], c["a"]) and Poisoned.read_only(t["qtm"], c["qtm"])
     return rc, t["qt"].cpu().numpy(), t["count"].cpu().numpy()
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, n=3):
     """every class of level against the oracle; where a plane can be mixed the answer is not the input, else it is"""
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     new, count = Run(eng, c).check("n %d plane %s ktot %d" % (n, plane, ktot))
     N = plane[0] * plane[1]
     mixed = (count > 0) & (count < N)
@@ -250,7 +215,7 @@ def check_rows(eng, ktot):
     """n = 1, 2, 5 at 2 x 3: A and QTM differ per LES, so a wrong l shows; with and without a pitch on the profiles and on count"""
     for n in NS:
         for pad, pad_count in ((0, 0), (3, 0), (0, 5), (3, 5)):
-            c = case((n, 2, 3, ktot), _np(eng), seed=1)
+            c = case((n, 2, 3, ktot), np_of(eng), seed=1)
             if n > 1 and ktot > 1:
                 assert not numpy.array_equal(c["a"][0], c["a"][1]) and not numpy.array_equal(c["qtm"][0], c["qtm"][1])
             Run(eng, c, pad=pad, pad_count=pad_count).check("rows n %d ktot %d pad %d %d" % (n, ktot, pad, pad_count))
@@ -260,7 +225,7 @@ def check_shapes(eng):
     """every forced split factor among 1, 2, 3 and one larger than the number of rows against the unforced launch, the oracle
     and each other: qt and count bit-equal; what the library chooses for the sizes of the benchmark"""
     for shape in ((3, 2, 3, 7), (2, 8, 8, 65), (1, 17, 5, 160), (2, 1, 1, 64)):
-        c = case(shape, _np(eng), seed=2)
+        c = case(shape, np_of(eng), seed=2)
         N = shape[1] * shape[2]
         free = Run(eng, c)
         free.check("split 0 %s" % (shape,))
@@ -268,10 +233,10 @@ def check_shapes(eng):
         for split in SPLITS + [N + 3]:
             r = Run(eng, c, split=split)
             r.check("split %d %s" % (split, shape))
-            assert _same(r.dqt, free.dqt.cpu().numpy()) and _same(r.dcount, free.dcount.cpu().numpy()), (shape, split)
+            assert Poisoned.read_only(r.dqt, free.dqt.cpu().numpy()) and Poisoned.read_only(r.dcount, free.dcount.cpu().numpy()), (shape, split)
     assert eng.qt_local_split(256, 8, 8, 160) == 1 and eng.qt_local_split(16, 64, 64, 160) == 22 and eng.qt_local_split(1, 128, 128, 160) == 256
     assert eng.qt_local_split(0, 8, 8, 160) == 0 and eng.qt_local_split(4, 0, 8, 160) == 0 and eng.qt_local_split(4, 4097, 4097, 16) == 0
-    c = case((2, 16, 16, 70), _np(eng), seed=3)                   # the library's own choice of a split: 4 parts of 64 rows
+    c = case((2, 16, 16, 70), np_of(eng), seed=3)                   # the library's own choice of a split: 4 parts of 64 rows
     assert eng.qt_local_split(2, 16, 16, 70) == 4
     Run(eng, c).check("the library's split")
 
@@ -306,7 +271,7 @@ def check_skipped(eng):
     """untouched levels keep every BYTE of qt, special values included; a NaN qt cell on a mixed level stays NaN and counts as
     dry where qt decides; a NaN ql cell is dry"""
     for ktot in (21, 64):
-        c, keep = skipped_case(_np(eng), ktot)
+        c, keep = skipped_case(np_of(eng), ktot)
         before = c["qt"].copy()
         r = Run(eng, c)
         new, count = r.check("skipped ktot %d" % ktot)
@@ -336,7 +301,7 @@ def ties_case(dtype, ktot=9):
 
 
 def check_ties(eng):
-    c, inv = ties_case(_np(eng))
+    c, inv = ties_case(np_of(eng))
     new, count = Run(eng, c).check("ties")
     l, k = inv["pos_mixed"]
     assert count[l, k] == 3 and (c["qt"][l, :, :, k] == c["qtm"][l, k]).sum() == 1
@@ -346,14 +311,14 @@ def check_ties(eng):
 
 def check_alignment(eng, leads, ktot=65, pad=0):
     """views off the 16-byte grid: qt and ql equally or each on its own (the narrow path whatever ktot), and on it (wide)"""
-    c = case((3, 2, 3, ktot), _np(eng), seed=sum(leads) + 10 * pad)
+    c = case((3, 2, 3, ktot), np_of(eng), seed=sum(leads) + 10 * pad)
     Run(eng, c, leads=leads, pad=pad, pad_count=pad).check("leads %s pad %d ktot %d" % (leads, pad, ktot))
 
 
 def check_refusals(eng):
     """n = 0 is a no-op; N > 2^24, pitch_prof < ktot, pitch_count < ktot, a NULL qt, ql, a, qtm or count, qt == ql and a
     negative split are refused by the library; the engine refuses the same alias and bad shapes; no refused call writes"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=6)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     t = {k: dev(c[k]) for k in ("qt", "ql", "a", "qtm")}
@@ -400,22 +365,16 @@ def check_refusals(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    c = case((n, 2, 3, 40), _np(one), seed=n)
+    c = case((n, 2, 3, 40), np_of(one), seed=n)
     new, count = oracle(c)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
-    for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+    for tag, eng, up in on_both(one, multi, n):
         t = {k: up(c[k]) for k in ("qt", "ql", "a", "qtm")}
         got = eng.les_qt_local(t["qt"], t["ql"], t["a"], t["qtm"])
         multi.synchronize()
-        if tag == "multi":
-            blocks = [int(p.shape[0]) for p in t["qt"].parts]
-        assert_bits("%s qt" % tag, wpr._host(t["qt"]), new)
-        assert numpy.array_equal(wpr._host(got), count), tag
-        assert _same_host(wpr._host(t["ql"]), c["ql"])
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+        assert_bits("%s qt" % tag, host_of(t["qt"]), new)
+        assert numpy.array_equal(host_of(got), count), tag
+        assert _same_host(host_of(t["ql"]), c["ql"])
+    return blocks_of(t["qt"], multi, n)
 
 
 def _same_host(a, b):
@@ -425,23 +384,20 @@ def _same_host(a, b):
 BODIES = ("parity", "rows", "shapes", "skipped", "ties", "alignment", "refusals")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 7, 65, 160)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 7, 65, 160)]),
             ("rows", lambda: [check_rows(eng, k) for k in (2, 65)]),
             ("shapes", lambda: check_shapes(eng)),
             ("skipped", lambda: check_skipped(eng)),
             ("ties", lambda: check_ties(eng)),
             ("alignment", lambda: [check_alignment(eng, *a) for a in (((1, 1), 65, 0), ((1, 0), 64, 0), ((3, 3), 160, 5), ((0, 0), 160, 0))]),
             ("refusals", lambda: check_refusals(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_qt_local (CPU suite) ---------------------------------------------------------------------
@@ -517,67 +473,24 @@ def ensemble_run(engine, n, device, kind="local", thermo=False, micro=False, dif
     """tests/les_radiate_ref.ensemble_run with enable_qt_forcing(kind) (``kind`` None: never called) and the cloud-water
     forcing and reference profile of the coupler handed over: ``steps`` calls of evolve_model_batched and one variability nudge
     (constantT) before the last; after each of them every profile, the fields and the counts.  Returns (ens, list of records)"""
-    spcpl.set_engine(engine)
-    cls = models.DeviceLESEnsemble if device else (HostThermoQtLocalLESEnsemble if thermo else HostQtLocalLESEnsemble)
-    fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
-    stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
-    gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
-    rng = numpy.random.default_rng(n + 100)
-    fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
-              "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}
-    if vertical:
-        fields["U"][:, lvr.RAISED[0], lvr.RAISED[1], :] += 2.0
-    if thermo:
-        del fields["Qsat"]
-        fields["THL"] = fields["THL"] - 25.0
-        fields["QT"] = fields["QT"] * 0.35
-        fields["QT"][:, 2, 1, :] *= 2.0
-    if micro:
-        fields["QR"] = numpy.random.default_rng(n).random((n, itot, jtot, nL)) * 1e-5
-    ens.attach_fields({k: v.copy() for k, v in fields.items()})
-    ens.p["presf"] = stack("presf")
-    ens.ql_ref = stack("ql_ref")
-    ens.model_time = 900.0
-    if thermo:
-        ens.enable_thermo()
-    if diffuse:
-        ens.enable_diffusion()
-    if micro:
-        ens.enable_microphysics(qc0=1e-4, v_fall=0.05)
-    if vertical:
-        ens.enable_advection(dx=lvr.DX, dy=1.5 * lvr.DX, vertical=True)
-    if radiate:
-        ens.enable_radiation(f0=rad.F0 * (1.0 + 0.05 * numpy.arange(n)), kappa=rad.KAPPA * (1.0 + 0.02 * (numpy.arange(n) % 5)))
-    if kind:
-        ens.enable_qt_forcing(kind)
-        ens.enable_qt_forcing(kind)                               # (idempotent)
-    rng = numpy.random.default_rng(5)
-    ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, nL)), QT=rng.normal(0, 2e-7, (n, nL)), U=rng.normal(0, 1e-4, (n, nL)),
-                             WT_surf=ldr.WT * (0.5 + rng.random(n)), WQ_surf=ldr.WQ * (0.5 + rng.random(n)),
-                             QL=rng.normal(0, 2e-8, (n, nL)), QLp=stack("ql_ref") * (0.5 + rng.random((n, nL))))
-    log = []
+    def enable(ens):
+        if kind:
+            ens.enable_qt_forcing(kind)
+            ens.enable_qt_forcing(kind)                           # (idempotent)
 
-    def record():
-        prof = {k: numpy.empty((n, nL)) for k in ("U", "V", "THL", "QT", "QL")}
-        ens.get_profiles_batched(tuple(prof), prof)
-        rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("U", "V", "QT", "THL", "QL") + (("QR",) if micro else ())})
+    def record(ens, rec):
         if kind:
             counts = ens.get_qt_forcing_counts_batched()
-            rec["counts"] = numpy.zeros((n, nL)) if counts is None else numpy.array(wpr._host(counts), dtype=numpy.float64)
-        log.append(rec)
-    assert not kind or ens.get_qt_forcing_counts_batched() is None
-    record()
-    for step in range(steps):
-        if step == steps - 1:
-            numpy.random.seed(11)
-            spcpl.variability_nudge_ensemble(ens, 900.0, True, write=False)
-            record()
-        ens.evolve_model_batched(1800.0 + 900.0 * step)
-        record()
-    return ens, log
+            rec["counts"] = numpy.zeros((n, nL)) if counts is None else numpy.array(host_of(counts), dtype=numpy.float64)
+
+    def before(ens):
+        assert not kind or ens.get_qt_forcing_counts_batched() is None
+    return ensemble_case(engine, n, models.DeviceLESEnsemble if device else (HostThermoQtLocalLESEnsemble if thermo else HostQtLocalLESEnsemble),
+                         thermo=thermo, micro=micro, diffuse=diffuse, edit=lvr.raise_u if vertical else None,
+                         advection=dict(dx=lvr.DX, dy=1.5 * lvr.DX, vertical=True) if vertical else None,
+                         radiation=lrr.radiation_of(n, "f0", "kappa") if radiate else None, enable=enable,
+                         forcings=lambda rng, stack: dict(QL=rng.normal(0, 2e-8, (n, nL)), QLp=stack("ql_ref") * (0.5 + rng.random((n, nL)))),
+                         record=record, before=before, itot=itot, jtot=jtot, nL=nL, steps=steps)
 
 
 def check_ensemble(one, engines, n, variant, kind):
@@ -616,9 +529,9 @@ def coupler_run(engine, cls, qt_forcing, n=4, nG=19, nL=24, itot=4, jtot=4):
 
     def record():
         rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("QT", "QL")})
+        rec.update({"field " + k: numpy.array(host_of(ens.get_fields_batched(k))) for k in ("QT", "QL")})
         counts = ens.get_qt_forcing_counts_batched()
-        rec["counts"] = numpy.zeros((n, nL)) if counts is None else numpy.array(wpr._host(counts), dtype=numpy.float64)
+        rec["counts"] = numpy.zeros((n, nL)) if counts is None else numpy.array(host_of(counts), dtype=numpy.float64)
         rec["ql_ref"] = numpy.array(ens.tend["QL_ref"])
         rec["f_ql"] = numpy.array(ens.tend["QL"])
         log.append(rec)

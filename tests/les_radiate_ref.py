@@ -5,25 +5,23 @@ CPU suite.
 
 The oracle spells the rule out one operation per NumPy call in the element type, vectorised over the columns, Python loops
 over k for both running sums, so nothing fuses.  Every device array of the bodies is the LEADING part of a poisoned buffer
-(tests/slab_edges.with_tail); the bytes behind it (and in front of a view off the 16-byte grid) are checked after the launch."""
-import ctypes
+(tests/les_harness.Poisoned); the bytes behind it (and in front of a view off the 16-byte grid) are checked after the launch."""
 
 import numpy
 import torch
 
-from sp_coupler_amd import _abi, models, spcpl
+from sp_coupler_amd import _abi, models
 from sp_coupler_amd import radiation as rad
 from tests import les_diffuse_ref as ldr
 from tests import les_micro_ref as lmr
 from tests import les_thermo_ref as ltr
 from tests import les_vadvect_ref as lvr
-from tests import les_water_paths_ref as wpr
-from tests import slab_edges, slab_ref
+from tests import slab_ref
 from tests.gpu_util import assert_bits
-from tests.test_vnudge import make_les_fields
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, cols_table, ensemble_case, fill_args, host_of, np_of, on_both, run_bodies,
+    with_tail)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 #: one column per LES (1 x 1: a tile holds many LES), tiles that straddle LES (2 x 3), a tile that is exactly one LES (8 x 8)
 PLANES = [(1, 1), (2, 3), (8, 8)]
 #: no chain (1), one add (2), shorter than one chunk of 8 levels (7), the flagship's 160 (whole chunks) and 161 (one more)
@@ -152,10 +150,6 @@ def oracle(c):
 
 
 # -- device plumbing ---------------------------------------------------------------------------------------------------------
-def _same(t, a):
-    return numpy.array_equal(numpy.ascontiguousarray(t.cpu().numpy()).view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))
-
-
 class Run:
     """one launch through ``eng.les_radiate`` with every array inside a poisoned buffer; ``check`` compares thl, flux and fsfc
     with the oracle bit for bit, the read-only inputs with what was uploaded, and looks at the bytes around every array.
@@ -163,18 +157,11 @@ class Run:
 
     def __init__(self, eng, c, leads=(0, 0, 0), pad=0, flux=True, fsfc=True):
         self.eng, self.c, self.pad = eng, c, pad
-        self.bufs = {}
+        self.mem = Poisoned(eng)
         assert numpy.array_equal(c["etab"], rad.exp_table(c["ql"].dtype)) and c["inv_step"] == rad.INV_STEP     # (the engine's table)
 
-        def put(tag, a, poison, lead=0):
-            t, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (t, b, lead, poison)
-            return t
-
-        def prof(tag, a):
-            wide = numpy.full((a.shape[0], a.shape[1] + pad), 1e30, dtype=a.dtype)
-            wide[:, :a.shape[1]] = a
-            return put(tag, wide, 1e30)[:, :a.shape[1]]
+        put = self.mem.put
+        prof = lambda tag, a: self.mem.rows(tag, a, 1e30, pad=pad)                          # noqa: E731
         self.dql = put("ql", c["ql"], float("nan"), leads[0])
         self.dthl = put("thl", c["thl"], float("nan"), leads[1])
         self.dw, self.dc = prof("w", c["w"]), prof("c", c["c"])
@@ -195,13 +182,8 @@ class Run:
         if self.dfsfc is not None:
             assert_bits("%s fsfc" % what, self.dfsfc.cpu().numpy(), fsfc)
         for tag, t, a in (("ql", self.dql, c["ql"]), ("w", self.dw, c["w"]), ("c", self.dc, c["c"]), ("f0", self.df0, c["f0"]), ("f1", self.df1, c["f1"])):
-            assert _same(t, a), (what, tag, "read only")
-        ktot = c["ql"].shape[-1]
-        for tag, (t, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + t.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
-            if self.pad and tag in ("w", "c"):
-                assert bool((t[:, ktot:] == poison).all()), (what, tag, "written between the rows")
+            assert Poisoned.read_only(t, a), (what, tag, "read only")
+        self.mem.check_around(what)
         return thl, flux, fsfc
 
 
@@ -215,52 +197,22 @@ def raw_launch(eng, c, alias=None, extents=None, null=(), flux=True, fsfc=True):
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     n, itot, jtot, ktot = c["ql"].shape
     t = {k: dev(c[k]) for k in ("ql", "thl", "w", "c", "f0", "f1")}
-    t["etab"] = slab_edges.with_tail(eng, c["etab"], float("nan"), tail_elems=64)[0]
+    t["etab"] = with_tail(eng, c["etab"], float("nan"), tail_elems=64)[0]
     t["flux"] = dev(numpy.full_like(c["ql"], OUT_FILL))
     t["fsfc"] = dev(numpy.full(c["ql"].shape[:3], OUT_FILL, dtype=c["ql"].dtype))
     a = _abi.LesRadiateArgs()
     a.n_les, a.itot, a.jtot, a.ktot, a.n_tab, a.pitch_prof, a.inv_step = n, itot, jtot, ktot, c["etab"].shape[0], ktot, c["inv_step"]
-    for k in PTRS:
-        if (k != "flux" or flux) and (k != "fsfc" or fsfc):
-            setattr(a, k, t[k].data_ptr())
-    for member, key in (alias or ()):
-        setattr(a, member, t[key].data_ptr())
-    for key, val in (extents or {}).items():
-        setattr(a, key, val)
-    for key in null:
-        setattr(a, key, None)
-    fn = eng.lib.spc_les_radiate_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_radiate_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
-    assert _same(t["ql"], c["ql"]) and _same(t["etab"], c["etab"])
+    fill_args(a, t, [k for k in PTRS if (k != "flux" or flux) and (k != "fsfc" or fsfc)], alias, extents, null)
+    rc = abi_call(eng, "spc_les_radiate", a)
+    assert Poisoned.read_only(t["ql"], c["ql"]) and Poisoned.read_only(t["etab"], c["etab"])
     return rc, t["thl"].cpu().numpy(), t["flux"].cpu().numpy() if flux else None, t["fsfc"].cpu().numpy() if fsfc else None
-
-
-def _np(eng):
-    return NP[eng.dtype]
-
-
-def cols_table(eng, top=3000):
-    """(dict C -> the smallest ktot with that many columns per workgroup, the ktot at which the count changes, the first
-    unsupported ktot), asked from the library"""
-    first, changes, last = {}, [], None
-    for ktot in range(1, top):
-        C = eng.radiate_cols_per_block(ktot)
-        if C != last and last is not None:
-            changes.append(ktot)
-        last = C
-        if C == 0:
-            return first, changes[:-1], ktot
-        first.setdefault(C, ktot)
-    raise AssertionError("no unsupported ktot below %d" % top)
 
 
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, n=3):
     """mixed columns (clear ones and decks of another base, depth and water) against the oracle; the answer is not the input"""
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
-    c["ql"][0, 0, 0, :] = _np(eng)(5e-4) * (numpy.arange(ktot) >= ktot // 2)            # (at least one cloudy column)
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
+    c["ql"][0, 0, 0, :] = np_of(eng)(5e-4) * (numpy.arange(ktot) >= ktot // 2)            # (at least one cloudy column)
     thl, flux, fsfc = Run(eng, c).check("n %d plane %s ktot %d" % (n, plane, ktot))
     assert (thl != c["thl"]).any() and (thl[0, 0, 0, ktot - 1] < c["thl"][0, 0, 0, ktot - 1])
     assert (flux[0, 0, 0, -1] > fsfc[0, 0, 0]) if ktot > 1 else True
@@ -270,7 +222,7 @@ def check_rows(eng, ktot):
     """n = 1, 2, 5 at 2 x 3: w, c, f0 and f1 differ per LES, so a wrong l shows; then the same with pitched profiles"""
     for n in NS:
         for pad in (0, 3):
-            c = case((n, 2, 3, ktot), _np(eng), seed=1, kind="deck")
+            c = case((n, 2, 3, ktot), np_of(eng), seed=1, kind="deck")
             if n > 1:
                 assert not numpy.array_equal(c["w"][0], c["w"][1]) and c["f0"][0] != c["f0"][1] and c["f1"][0] != c["f1"][1]
             Run(eng, c, pad=pad).check("rows n %d ktot %d pad %d" % (n, ktot, pad))
@@ -280,8 +232,8 @@ def check_tiles(eng):
     """for every C of spc_les_radiate_cols_per_block: C - 1, C, C + 1 and 2 C + 1 columns, as one LES of 1 x cols columns (a
     tile ends inside a row), as cols LES of one column (l per lane) and as LES of 1 x 3 (a tile ends inside an LES); ktot on
     both sides of every change of C; 17 columns at the last supported ktot; the first unsupported ktot refused"""
-    dtype = _np(eng)
-    first, changes, bad = cols_table(eng)
+    dtype = np_of(eng)
+    first, changes, bad = cols_table(eng.radiate_cols_per_block)
     assert sorted(first) == [16, 32, 64] and len(changes) == 2
     for C, k0 in first.items():
         ktot = 7 if C == 64 else k0
@@ -306,7 +258,7 @@ def check_tiles(eng):
 def check_outputs(eng):
     """with and without flux and fsfc: thl does not depend on them, and what is not asked for is not written"""
     for ktot in (2, 65):
-        c = case((2, 2, 3, ktot), _np(eng), seed=6, kind="deck")
+        c = case((2, 2, 3, ktot), np_of(eng), seed=6, kind="deck")
         for flux in (True, False):
             for fsfc in (True, False):
                 Run(eng, c, flux=flux, fsfc=fsfc).check("flux %s fsfc %s ktot %d" % (flux, fsfc, ktot))
@@ -319,7 +271,7 @@ def check_outputs(eng):
 
 def check_alignment(eng, leads, ktot=65, pad=0):
     """views off the 16-byte grid: all equally (the 16-byte mover with a head and a tail) or each on its own (single elements)"""
-    c = case((3, 2, 3, ktot), _np(eng), seed=sum(leads) + 10 * pad)
+    c = case((3, 2, 3, ktot), np_of(eng), seed=sum(leads) + 10 * pad)
     Run(eng, c, leads=leads, pad=pad).check("leads %s pad %d ktot %d" % (leads, pad, ktot))
 
 
@@ -327,7 +279,7 @@ def check_clouds(eng):
     """a clear sky keeps every bit of thl (-0.0 included) and F = f0 + f1 everywhere; one cloudy cell at the bottom, at the top
     and in the middle and a deck: the topmost cloudy cell cools; with f0 = 0 and cloud from k0 up the cells below k0 keep
     their bits, cell k0 warms and no cell cools"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for ktot in (2, 7, 64):
         c = case((2, 2, 3, ktot), dtype, seed=7, kind="clear")
         c["thl"][0, 0, 0, :] = -0.0
@@ -386,7 +338,7 @@ def coarse_case(dtype, ktot=5):
 
 def check_lookup(eng):
     """optical depths exactly on table nodes, one just below x_hi, one far beyond it (the clamp); a coarse table of the caller's"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = node_case(dtype)
     A, B = optical_depths(c["ql"], c["w"])
     assert ((A[1] * 64) % 1 == 0).all() and A[0, 0, 1, 0] == dtype(32 - 2.0 ** -10) and A[0, 1, 0, 0] > 1e4 and A[0, 1, 1, 0] == 32
@@ -416,7 +368,7 @@ def special_case(dtype, ktot=7):
 def check_special(eng):
     """a negative ql, NaN, +-inf and -0.0 in one ql cell and in one thl cell each: they act on their own column as the oracle
     says (a NaN in ql makes every thl of its column NaN), and every other column is bit-equal to the run without them"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for ktot in (7, 64):
         c, s, cols = special_case(dtype, ktot)
         clean = Run(eng, c).check("clean ktot %d" % ktot)
@@ -434,7 +386,7 @@ def check_special(eng):
 def check_refusals(eng):
     """n = 0 is a no-op; n_tab < 2, inv_step <= 0 (and NaN), pitch_prof < ktot, and thl, flux or fsfc equal to an input or to
     each other are refused by the library; the engine refuses the same aliases and bad shapes; no refused call writes"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=13, kind="deck")
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     t = {k: dev(c[k]) for k in ("ql", "thl", "w", "c", "f0", "f1")}
@@ -483,31 +435,23 @@ def check_refusals(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    c = case((n, 2, 3, 40), _np(one), seed=n, kind="deck")
+    c = case((n, 2, 3, 40), np_of(one), seed=n, kind="deck")
     want = oracle(c)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
-    for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+    for tag, eng, up in on_both(one, multi, n):
         t = {k: up(c[k]) for k in ("ql", "thl", "w", "c", "f0", "f1")}
         flux, fsfc = up(numpy.full_like(c["ql"], OUT_FILL)), up(numpy.full(c["ql"].shape[:3], OUT_FILL, dtype=c["ql"].dtype))
         assert eng.les_radiate(t["ql"], t["thl"], t["w"], t["c"], t["f0"], t["f1"], flux=flux, fsfc=fsfc) is None
         multi.synchronize()
-        if tag == "multi":
-            blocks = [int(p.shape[0]) for p in t["thl"].parts]
         for k, got, w in (("thl", t["thl"], want[0]), ("flux", flux, want[1]), ("fsfc", fsfc, want[2])):
-            assert_bits("%s %s" % (tag, k), wpr._host(got), w)
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+            assert_bits("%s %s" % (tag, k), host_of(got), w)
+    return blocks_of(t["thl"], multi, n)
 
 
 BODIES = ("parity", "rows", "tiles", "outputs", "alignment", "clouds", "lookup", "special", "refusals")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 7, 161)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 7, 161)]),
             ("rows", lambda: [check_rows(eng, k) for k in (2, 65)]),
             ("tiles", lambda: check_tiles(eng)),
             ("outputs", lambda: check_outputs(eng)),
@@ -516,13 +460,12 @@ def check_everything(eng):
             ("lookup", lambda: check_lookup(eng)),
             ("special", lambda: check_special(eng)),
             ("refusals", lambda: check_refusals(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_radiate (CPU suite) ------------------------------------------------------------------------
@@ -629,63 +572,25 @@ def ensemble_run(engine, n, device, radiate=True, thermo=False, micro=False, dif
     another f0, f1 and kappa per LES (``radiate`` None: never called) through ``steps`` calls of evolve_model_batched and one
     variability nudge (constantT) before the last; after each of them every profile, the fields and the flux.  Returns (ens,
     list of records)"""
-    spcpl.set_engine(engine)
-    cls = models.DeviceLESEnsemble if device else (HostThermoRadiateLESEnsemble if thermo else HostRadiateLESEnsemble)
-    fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
-    stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
-    gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
-    rng = numpy.random.default_rng(n + 100)
-    fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
-              "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}
-    if vertical:
-        fields["U"][:, lvr.RAISED[0], lvr.RAISED[1], :] += 2.0
-    if thermo:
-        del fields["Qsat"]
-        fields["THL"] = fields["THL"] - 25.0
-        fields["QT"] = fields["QT"] * 0.35
-        fields["QT"][:, 2, 1, :] *= 2.0
-    if micro:
-        fields["QR"] = numpy.random.default_rng(n).random((n, itot, jtot, nL)) * 1e-5
-    ens.attach_fields({k: v.copy() for k, v in fields.items()})
-    ens.p["presf"] = stack("presf")
-    ens.ql_ref = stack("ql_ref")
-    ens.model_time = 900.0
-    if thermo:
-        ens.enable_thermo()
-    if diffuse:
-        ens.enable_diffusion()
-    if micro:
-        ens.enable_microphysics(qc0=1e-4, v_fall=0.05)
-    if vertical:
-        ens.enable_advection(dx=lvr.DX, dy=1.5 * lvr.DX, vertical=True)
-    if radiate:
-        ens.enable_radiation(f0=rad.F0 * (1.0 + 0.05 * numpy.arange(n)), f1=rad.F1 * (1.0 + 0.1 * (numpy.arange(n) % 3)), kappa=rad.KAPPA * (1.0 + 0.02 * (numpy.arange(n) % 5)))
-    rng = numpy.random.default_rng(5)
-    ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, nL)), QT=rng.normal(0, 2e-7, (n, nL)), U=rng.normal(0, 1e-4, (n, nL)),
-                             WT_surf=ldr.WT * (0.5 + rng.random(n)), WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
-    log = []
-
-    def record():
-        prof = {k: numpy.empty((n, nL)) for k in ("U", "V", "THL", "QT", "QL")}
-        ens.get_profiles_batched(tuple(prof), prof)
-        rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("U", "V", "QT", "THL", "QL") + (("QR",) if micro else ())})
+    def record(ens, rec):
         if radiate:
             flux = ens.get_radiative_flux_batched()
-            rec["flux"] = numpy.zeros((n, itot, jtot, nL)) if flux is None else numpy.array(wpr._host(flux))
-        log.append(rec)
-    assert not radiate or ens.get_radiative_flux_batched() is None
-    record()
-    for step in range(steps):
-        if step == steps - 1:
-            numpy.random.seed(11)
-            spcpl.variability_nudge_ensemble(ens, 900.0, True, write=False)
-            record()
-        ens.evolve_model_batched(1800.0 + 900.0 * step)
-        record()
-    return ens, log
+            rec["flux"] = numpy.zeros((n, itot, jtot, nL)) if flux is None else numpy.array(host_of(flux))
+
+    def before(ens):
+        assert not radiate or ens.get_radiative_flux_batched() is None
+    return ensemble_case(engine, n, models.DeviceLESEnsemble if device else (HostThermoRadiateLESEnsemble if thermo else HostRadiateLESEnsemble),
+                         thermo=thermo, micro=micro, diffuse=diffuse, edit=lvr.raise_u if vertical else None,
+                         advection=dict(dx=lvr.DX, dy=1.5 * lvr.DX, vertical=True) if vertical else None,
+                         radiation=radiation_of(n, "f0", "f1", "kappa") if radiate else None, record=record, before=before,
+                         itot=itot, jtot=jtot, nL=nL, steps=steps)
+
+
+def radiation_of(n, *names):
+    """the arguments ``names`` of enable_radiation of the ensemble runs: another f0, f1 and kappa per LES"""
+    par = {"f0": rad.F0 * (1.0 + 0.05 * numpy.arange(n)), "f1": rad.F1 * (1.0 + 0.1 * (numpy.arange(n) % 3)),
+           "kappa": rad.KAPPA * (1.0 + 0.02 * (numpy.arange(n) % 5))}
+    return {k: par[k] for k in names}
 
 
 def check_ensemble(one, engines, n, variant):

@@ -12,6 +12,7 @@ import contextlib
 import numpy
 
 from sp_coupler_amd import _abi, spcpl
+from tests.les_harness import run_bodies
 
 MT_N = 624
 
@@ -247,13 +248,14 @@ OLD_BODIES = ("mixed_shapes", "forced_short_substreams", "twist_boundary", "engi
 NEW_BODIES = ("seek_boundaries", "odd_substream_counts")
 
 
-def check_everything(eng, names=OLD_BODIES + NEW_BODIES):
+BODIES = OLD_BODIES + NEW_BODIES
+
+
+def jobs(eng, names=BODIES):
+    return [(name, lambda name=name: globals()["check_" + name](eng)) for name in names]
+
+
+def check_everything(eng, names=BODIES):
     """the bodies ``names`` on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the names of
     the bodies that failed (AssertionError) in the order they ran."""
-    failed = []
-    for name in names:
-        try:
-            globals()["check_" + name](eng)
-        except AssertionError:
-            failed.append(name)
-    return failed
+    return run_bodies(names, jobs(eng, names))

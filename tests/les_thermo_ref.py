@@ -4,20 +4,19 @@ libraries), the host twin of models.DeviceLESEnsemble's thermo mode and an oracl
 CPU suite.
 
 The oracle spells the rule out one operation per NumPy call in the element type, so nothing fuses.  Every device array of the
-bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes behind it (and in front of a view
+bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes behind it (and in front of a view
 off the 16-byte grid) are checked after the launch."""
-import ctypes
 
 import numpy
 import torch
 
 from sp_coupler_amd import _abi, driver, models, spcpl, sputils, thermo
 from tests import les_advance_ref as lar
-from tests import slab_edges, slab_ref
+from tests import slab_ref
 from tests.gpu_util import assert_bits
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, fill_args, np_of, on_both, run_bodies)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 #: n = 3; planes 1 x 1, 3 x 5 (15 rows: three batches of 4 and single rows behind them) and 8 x 8; ktot 2 and 7 (one element per
 #: lane), 64 and 160 (16-byte accesses), 65 (odd again, beyond one wave)
 PLANES = [(1, 1), (3, 5), (8, 8)]
@@ -149,17 +148,9 @@ class Run:
         self.eng, self.host, self.n_iter, self.pad = eng, (thl, qt, presf, ex), n_iter, pad
         dtype, shape = thl.dtype, thl.shape
         n, ktot = shape[0], shape[-1]
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=0):
-            v, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (v, b, lead, poison)
-            return v
-
-        def rows(tag, a, poison, lead):
-            wide = numpy.full((n, ktot + pad), poison, dtype=dtype)
-            wide[:, :ktot] = a
-            return put(tag, wide, poison, lead)[:, :ktot]
+        self.mem = Poisoned(eng)
+        put = self.mem.put
+        rows = lambda tag, a, poison, lead: self.mem.rows(tag, a, poison, lead, pad)        # noqa: E731
         self.dthl, self.dqt = put("thl", thl, float("nan"), lead), put("qt", qt, float("nan"), lead)
         self.dpresf, self.dex = rows("presf", presf, 1e30, lead_rows), rows("ex", ex, 1e30, lead_rows)
         self.out = {k: put(k, numpy.full(shape, -3.0, dtype), -5.0, lead) for k in ("qsat", "ql") + (("temp",) if want_temp else ())}
@@ -182,13 +173,8 @@ class Run:
         else:
             assert self.got == {}, (what, self.got)
         for name, t, a in (("thl", self.dthl, thl), ("qt", self.dqt, qt), ("presf", self.dpresf, presf), ("ex", self.dex, ex)):
-            assert numpy.array_equal(t.cpu().numpy().view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8)), (what, name, "read only")
-        ktot = thl.shape[-1]
-        for tag, (v, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + v.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
-            if self.pad and v.dim() == 2:
-                assert bool((v[:, ktot:] == poison).all()), (what, tag, "written between the rows")
+            assert Poisoned.read_only(t, a), (what, name, "read only")
+        self.mem.check_around(what)
         return want
 
 
@@ -204,17 +190,9 @@ def raw_launch(eng, thl, qt, presf, ex, tab, t_lo, inv_step, n_iter):
     a.thl, a.qt, a.presf, a.ex, a.es_tab = (t.data_ptr() for t in ins)
     a.pitch_prof = a.pitch_mean = ktot
     a.n_tab, a.t_lo, a.inv_step = len(tab), t_lo, inv_step
-    for k, t in outs.items():
-        setattr(a, k, t.data_ptr())
-    fn = eng.lib.spc_les_thermo_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_thermo_f64
-    with torch.cuda.device(eng.device):
-        _abi.check(eng.lib, fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream)))
-    torch.cuda.synchronize(eng.device)
+    fill_args(a, outs)
+    _abi.check(eng.lib, abi_call(eng, "spc_les_thermo", a))
     return {k: t.cpu().numpy() for k, t in outs.items()}
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 # -- a table of the test's own: exact coincidences that thermo.saturation_table does not offer -----------------------------
@@ -265,7 +243,7 @@ def zero_case(dtype):
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, n_iter=None):
     """qsat, ql, temp and both means against the oracle on cells on both sides of saturation"""
-    thl, qt, presf, ex = case((3,) + tuple(plane) + (ktot,), _np(eng))
+    thl, qt, presf, ex = case((3,) + tuple(plane) + (ktot,), np_of(eng))
     want = Run(eng, thl, qt, presf, ex, n_iter).check("plane %s ktot %d" % (plane, ktot))
     if want["ql"].size >= 100:
         assert (want["ql"] > 0).any() and (want["ql"] == 0).any()
@@ -274,7 +252,7 @@ def check_parity(eng, plane, ktot, n_iter=None):
 def check_special(eng, ktot, n_iter=None):
     """the mix of the issue in one field: unsaturated and saturated cells, qt == qs, Tl outside the table on either side and
     on its knots, NaN in thl and in qt, qt = -0.0"""
-    thl, qt, presf, ex = case((3, 3, 5, ktot), _np(eng), seed=1, special=True)
+    thl, qt, presf, ex = case((3, 3, 5, ktot), np_of(eng), seed=1, special=True)
     want = Run(eng, thl, qt, presf, ex, n_iter).check("special ktot %d n_iter %s" % (ktot, n_iter))
     assert numpy.isnan(want["ql"][:, 1, 0]).all() and numpy.isnan(want["ql"][:, 1, 1]).all()
     assert numpy.isnan(want["t_mean"]).all() and (want["qsat"][:, 0, 1] > 0).all()
@@ -282,13 +260,13 @@ def check_special(eng, ktot, n_iter=None):
 
 def check_alignment(eng, lead, lead_rows, pad):
     """views one (or more) elements off the 16-byte grid and pitched profiles / means"""
-    thl, qt, presf, ex = case((3, 3, 5, 64), _np(eng), seed=lead + 10 * lead_rows + 100 * pad)
+    thl, qt, presf, ex = case((3, 3, 5, 64), np_of(eng), seed=lead + 10 * lead_rows + 100 * pad)
     Run(eng, thl, qt, presf, ex, lead=lead, lead_rows=lead_rows, pad=pad).check("lead %d %d pad %d" % (lead, lead_rows, pad))
 
 
 def check_options(eng):
     """n_iter 0, 1 and the default; temp NULL; no means; the table staged in LDS and read from global memory"""
-    thl, qt, presf, ex = case((3, 3, 5, 160), _np(eng), seed=4, special=True)
+    thl, qt, presf, ex = case((3, 3, 5, 160), np_of(eng), seed=4, special=True)
     wants = {n: Run(eng, thl, qt, presf, ex, n).check("n_iter %s" % n) for n in (0, 1, None)}
     assert not numpy.array_equal(wants[0]["ql"], wants[1]["ql"], equal_nan=True)
     assert not numpy.array_equal(wants[1]["ql"], wants[None]["ql"], equal_nan=True)
@@ -301,7 +279,7 @@ def check_options(eng):
 
 def check_table(eng):
     """the C ABI with tables of the test's own: a Newton step that lands on a knot where qs == qt exactly, and dq == -0.0"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for n_iter in (1, 2, 3):
         thl, qt, presf, ex, tab = knot_case(dtype)
         want = les_thermo(thl, qt, presf, ex, n_iter, tab, TAB_T_LO, TAB_INV_STEP)
@@ -317,17 +295,15 @@ def check_table(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    thl, qt, presf, ex = case((n, 3, 5, 40), _np(one), seed=n, special=True)
+    thl, qt, presf, ex = case((n, 3, 5, 40), np_of(one), seed=n, special=True)
     want = les_thermo(thl, qt, presf, ex)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
+    (_, _, dev), (_, _, sh) = on_both(one, multi, n)
     o1 = {k: torch.full(thl.shape, -3.0, dtype=one.dtype, device=one.device) for k in OUTS[:3]}
     m1 = one.les_thermo(dev(thl), dev(qt), dev(presf), dev(ex), **o1)
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
     om = {k: sh(numpy.full(thl.shape, -3.0, dtype=thl.dtype)) for k in OUTS[:3]}
     mm = multi.les_thermo(sh(thl), sh(qt), sh(presf), sh(ex), **om)
     multi.synchronize()
-    blocks = [int(p.shape[0]) for p in om["ql"].parts]
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
+    blocks = blocks_of(om["ql"], multi, n)
     for k in OUTS[:3]:
         assert_bits("multi " + k, om[k].to_host(), want[k])
         assert_bits("one " + k, o1[k].cpu().numpy(), want[k])
@@ -341,21 +317,18 @@ def check_multi(one, multi, n):
 BODIES = ("parity", "special", "alignment", "options", "table")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in KTOTS]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in KTOTS]),
             ("special", lambda: [check_special(eng, k, n) for k in (7, 64) for n in (0, 1, None)]),
             ("alignment", lambda: [check_alignment(eng, *a) for a in ((1, 0, 0), (0, 1, 0), (0, 0, 4), (0, 0, 3))]),
             ("options", lambda: check_options(eng)),
             ("table", lambda: check_table(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_thermo (CPU suite) ---------------------------------------------------------------------

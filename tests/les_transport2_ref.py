@@ -5,29 +5,26 @@ enable_advection(vertical=True, conservative=True, order=2).
 
 The oracle spells the rule out in the statement order of include/spc.h, one operation per NumPy call in the element type,
 ``numpy.where`` for the selects; the face numbers and the donor fluxes are K22's own (tests/les_transport_ref.face_numbers,
-fluxes).  Every device array of the bodies is the LEADING part of a buffer whose poison is NaN (tests/slab_edges.with_tail): a
+fluxes).  Every device array of the bodies is the LEADING part of a buffer whose poison is NaN (tests/les_harness.Poisoned): a
 read of it would show up in a finite result, a write in the bytes that are checked after the launch."""
 import ctypes
 
 import numpy
 import torch
 
-from sp_coupler_amd import _abi, models, spcpl
+from sp_coupler_amd import _abi, models
 from sp_coupler_amd import advection as adv
 from sp_coupler_amd import buoyancy as buo
-from sp_coupler_amd import radiation as rad
+from tests import les_advect_ref as lar
 from tests import les_buoyancy_ref as lbr
-from tests import les_diffuse_ref as ldr
 from tests import les_micro_ref as lmr
+from tests import les_radiate_ref as lrr
 from tests import les_transport_ref as ltr
 from tests import les_vadvect_ref as lvr
-from tests import les_water_paths_ref as wpr
-from tests import slab_edges
 from tests.gpu_util import assert_bits
-from tests.test_vnudge import make_les_fields
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, cols_table, ensemble_case, fill_args, host_of, np_of, on_both, run_bodies)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 LIMITERS = ("mc", "none")
 #: the extents at which the distance-2 neighbours fold onto each other (1, 2, 3, 4) or the boundary slopes meet (ktot 1 ... 5)
 PLANES = [(1, 1), (1, 2), (2, 1), (2, 2), (3, 5), (4, 3), (8, 8), (5, 33)]
@@ -39,7 +36,6 @@ OUT_FILL = ltr.OUT_FILL
 field_like = ltr.field_like
 case = ltr.case
 split = ltr.split
-cols_table = ltr.cols_table
 derived_cols = ltr.derived_cols
 face_numbers = ltr.face_numbers
 fluxes = ltr.fluxes
@@ -174,18 +170,9 @@ class Run:
 
     def __init__(self, eng, c, limiter, lead=0, cmax=True, mtop=True, ftop=True, pad=0):
         self.eng, self.c, self.limiter = eng, c, limiter
-        self.bufs = {}
-        nan = float("nan")
-
-        def put(tag, a, lead=lead):
-            t, b = slab_edges.with_tail(eng, a, nan, lead=lead)
-            self.bufs[tag] = (t, b, lead, nan)
-            return t
-
-        def prof(tag, a):
-            wide = numpy.full((a.shape[0], a.shape[1] + pad), nan, dtype=a.dtype)
-            wide[:, :a.shape[1]] = a
-            return put(tag, wide)[:, :a.shape[1]]
+        self.mem = Poisoned(eng)
+        put = lambda tag, a: self.mem.put(tag, a, float("nan"), lead)                      # noqa: E731
+        prof = lambda tag, a: self.mem.rows(tag, a, float("nan"), lead, pad)               # noqa: E731
         self.du, self.dv = put("u", c["u"]), put("v", c["v"])
         self.dev = {k: (self.du if x is c["u"] else self.dv if x is c["v"] else put(k, x)) for k, x in c["fields"].items()}
         self.out = {k: put("out " + k, numpy.full_like(x, OUT_FILL)) for k, x in c["fields"].items()}
@@ -217,13 +204,10 @@ class Run:
             got = self.dftop.cpu().numpy()
             for q, k in enumerate(c["fields"]):
                 assert_bits("%s ftop %s" % (what, k), got[q], ftop[k])
-        same = lambda t, a: numpy.array_equal(numpy.ascontiguousarray(t.cpu().numpy()).view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))   # noqa: E731
         for tag, t, a in [("u", self.du, c["u"]), ("v", self.dv, c["v"]), ("hx", self.dhx, c["hx"]), ("hy", self.dhy, c["hy"]),
                           ("g", self.dg, c["g"]), ("r", self.dr, c["r"])] + [(k, self.dev[k], x) for k, x in c["fields"].items()]:
-            assert same(t, a), (what, tag, "read only")
-        for tag, (t, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + t.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
+            assert Poisoned.read_only(t, a), (what, tag, "read only")
+        self.mem.check_around(what)
         return want, cmax, mtop, ftop
 
 
@@ -253,20 +237,10 @@ def raw_launch(eng, c, limiter=_abi.SPC_LIMITER_MC, names=None, cmax=True, mtop=
             setattr(a, slot, t[key].data_ptr())
         else:
             a.out[slot] = t[key].data_ptr()
-    for key, val in (extents or {}).items():
-        setattr(a, key, val)
-    for key in null:
-        setattr(a, key, None)
-    fn = eng.lib.spc_les_transport2_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_transport2_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
+    fill_args(a, t, (), extents=extents, null=null)
+    rc = abi_call(eng, "spc_les_transport2", a)
     host = lambda flag, k: t[k].cpu().numpy() if flag else None                             # noqa: E731
     return rc, {k: t["out " + k].cpu().numpy() for k in names}, host(cmax, "cmax"), host(mtop, "mtop"), host(ftop, "ftop")
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 def differs(c, want, limiter):
@@ -279,7 +253,7 @@ def differs(c, want, limiter):
 def check_parity(eng, plane, ktot, n=3):
     """U, V (the winds themselves), THL and QT against the oracle with both limiters, cmax, mtop and ftop included"""
     n = ltr._n_for(plane, ktot, n)
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     for limiter in LIMITERS:
         want, cmax, mtop, ftop = Run(eng, c, limiter).check("n %d plane %s ktot %d" % (n, plane, ktot))
         if min(plane) > 2:
@@ -288,7 +262,7 @@ def check_parity(eng, plane, ktot, n=3):
 
 def check_outputs(eng):
     """cmax and mtop of K23 are K22's outputs bit for bit, from a full launch and from the probe, which is K22's probe"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for shape in ((1, 1, 1, 1), (2, 3, 5, 64), (5, 9, 9, 65)):
         c = case(shape, dtype, seed=6)
         _, want, mwant, _ = ltr.oracle(c)
@@ -311,7 +285,7 @@ def check_outputs(eng):
 def check_rows(eng, ktot):
     """n = 1, 2, 5 at 3 x 5: hx, hy, g and r differ per LES, with and without a pitch"""
     for n in NS:
-        c = case((n, 3, 5, ktot), _np(eng), seed=1)
+        c = case((n, 3, 5, ktot), np_of(eng), seed=1)
         for limiter in LIMITERS:
             Run(eng, c, limiter).check("rows n %d ktot %d" % (n, ktot))
             Run(eng, c, limiter, pad=3).check("rows n %d ktot %d pitched" % (n, ktot))
@@ -321,7 +295,7 @@ def check_tiles(eng):
     """every boundary of the workgroups, derived as tests/les_transport_ref.check_tiles derives them: C - 1, C, C + 1 and
     2 C + 1 columns for every C, ktot on both sides of every change of C, 17 columns at the last supported ktot, and the first
     unsupported ktot refused without a write"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     esize = numpy.dtype(dtype).itemsize
     first, changes, bad = table = cols_table(eng.transport2_cols_per_block)
     assert table == cols_table(lambda k: derived_cols(k, esize)) == cols_table(eng.transport_cols_per_block)
@@ -347,7 +321,7 @@ def check_tiles(eng):
 
 def check_fields(eng):
     """0 to 6 fields with U and V among them, 1 to 6 without, with and without cmax, mtop and ftop, and the C ABI"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for limiter in LIMITERS:
         for nf in range(0, 7):
             Run(eng, case((2, 3, 5, 65), dtype, seed=3, names=ALL_NAMES[:nf]), limiter).check("%d fields with the winds" % nf)
@@ -373,13 +347,13 @@ def check_fields(eng):
 def check_alignment(eng, lead, ktot=65):
     """views one (or more) elements off the 16-byte grid"""
     for limiter in LIMITERS:
-        Run(eng, case((3, 3, 5, ktot), _np(eng), seed=10 + lead), limiter, lead=lead).check("lead %d ktot %d" % (lead, ktot))
+        Run(eng, case((3, 3, 5, ktot), np_of(eng), seed=10 + lead), limiter, lead=lead).check("lead %d ktot %d" % (lead, ktot))
 
 
 def check_signs(eng):
     """winds of either sign in all combinations (every horizontal face an inflow or an outflow face everywhere: each of the two
     products of a correction is the live one somewhere), convergent and divergent columns, and still air, which keeps every bit"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for limiter in LIMITERS:
         for su in (1, -1):
             for sv in (1, -1):
@@ -404,7 +378,7 @@ def check_signs(eng):
 def check_constant(eng):
     """a constant field (and one that is constant along one axis only) equals the oracle; how far the oracle moves a constant
     is the CPU suite's to bound"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for limiter in LIMITERS:
         c = case((2, 4, 5, 9), dtype, seed=12, names=("THL", "QT"))
         c["fields"]["THL"][...] = dtype(287.3)
@@ -439,7 +413,7 @@ def special_case(dtype, ktot=9):
 def check_special(eng):
     """NaN, +-inf and -0.0 planted in single cells of a field: every output is the oracle's, and the cells further than two
     steps away along each axis hold the bits of a run without them"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c, s, mask = special_case(dtype)
     for limiter in LIMITERS:
         clean, _, _, clean_ftop = Run(eng, c, limiter).check("clean")
@@ -491,7 +465,7 @@ def bad_calls(eng, t, o, u, v, hx, hy, g, r, m, ft):
 def check_refusals(eng):
     """K22's refusals through spc_les_transport2_* and ``Engine.les_transport2``, and the limiter that is neither: no refused
     call touches anything"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=11)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     E = _abi.SPC_ERR_INVALID_ARGUMENT
@@ -555,13 +529,10 @@ def check_refusals(eng):
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle, cmax, mtop and ftop included"""
     from sp_coupler_amd.transfer import Sharded
-    c = case((n, 3, 5, 40), _np(one), seed=n)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
+    c = case((n, 3, 5, 40), np_of(one), seed=n)
     for limiter in LIMITERS:
         want, cmax, mtop, ftop = oracle(c, limiter)
-        for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+        for tag, eng, up in on_both(one, multi, n):
             u, v = up(c["u"]), up(c["v"])
             t = {k: (u if x is c["u"] else v if x is c["v"] else up(x)) for k, x in c["fields"].items()}
             o = {k: up(numpy.full_like(x, OUT_FILL)) for k, x in c["fields"].items()}
@@ -571,28 +542,23 @@ def check_multi(one, multi, n):
             prof = [up(c[k]) for k in ("hx", "hy", "g", "r")]
             got = eng.les_transport2(t, o, u, v, *prof, limiter=limiter, mtop=m, ftop=ft)
             multi.synchronize()
-            if tag == "multi":
-                blocks = [int(p.shape[0]) for p in o["QT"].parts]
             for q, k in enumerate(NAMES):
-                assert_bits("%s %s %s" % (limiter, tag, k), wpr._host(o[k]), want[k])
+                assert_bits("%s %s %s" % (limiter, tag, k), host_of(o[k]), want[k])
                 lidk = numpy.concatenate([p[q].cpu().numpy() for p in ft.parts]) if tag == "multi" else ft[q].cpu().numpy()
                 assert_bits("%s %s ftop %s" % (limiter, tag, k), lidk, ftop[k])
-            assert_bits("%s cmax" % tag, wpr._host(got), cmax)
-            assert_bits("%s mtop" % tag, wpr._host(m), mtop)
+            assert_bits("%s cmax" % tag, host_of(got), cmax)
+            assert_bits("%s mtop" % tag, host_of(m), mtop)
             probe = eng.les_transport2({}, {}, u, v, *prof, limiter=limiter)
             multi.synchronize()
-            assert_bits("%s probe" % tag, wpr._host(probe), cmax)
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+            assert_bits("%s probe" % tag, host_of(probe), cmax)
+    return blocks_of(o["QT"], multi, n)
 
 
 BODIES = ("parity", "outputs", "rows", "tiles", "fields", "alignment", "signs", "constant", "special", "refusals")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 3, 4, 5, 64, 160)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 3, 4, 5, 64, 160)]),
             ("outputs", lambda: check_outputs(eng)),
             ("rows", lambda: [check_rows(eng, k) for k in (1, 65)]),
             ("tiles", lambda: check_tiles(eng)),
@@ -602,13 +568,12 @@ def check_everything(eng):
             ("constant", lambda: check_constant(eng)),
             ("special", lambda: check_special(eng)),
             ("refusals", lambda: check_refusals(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_transport2 (CPU suite) ---------------------------------------------------------------------
@@ -715,74 +680,21 @@ def ensemble_run(engine, n, device, order=2, limiter="mc", buoyancy=False, therm
                  nL=20, steps=3):
     """tests/les_transport_ref.ensemble_run with enable_advection(vertical=True, conservative=True, order=..., limiter=...);
     ``order=None``: the call as it was before K23.  Returns (ens, list of records)"""
-    spcpl.set_engine(engine)
-    cls = models.DeviceLESEnsemble if device else (HostThermoTransport2LESEnsemble if thermo else HostTransport2LESEnsemble)
-    fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
-    stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
-    gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
-    rng = numpy.random.default_rng(n + 100)
-    fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
-              "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}
-    fields["U"][:, lvr.RAISED[0], lvr.RAISED[1], :] += 2.0
-    if thermo:
-        del fields["Qsat"]
-        fields["THL"] = fields["THL"] - 25.0
-        fields["QT"] = fields["QT"] * 0.35
-        fields["QT"][:, 2, 1, :] *= 2.0
-    if micro:
-        fields["QR"] = numpy.random.default_rng(n).random((n, itot, jtot, nL)) * 1e-5
-    ens.attach_fields({k: v.copy() for k, v in fields.items()})
-    ens.p["presf"] = stack("presf")
-    ens.ql_ref = stack("ql_ref")
-    ens.model_time = 900.0
-    if thermo:
-        ens.enable_thermo()
-    if diffuse:
-        ens.enable_diffusion()
-    if micro:
-        ens.enable_microphysics(qc0=1e-4, v_fall=0.05)
-    if order is None:
-        ens.enable_advection(dx=DX, dy=1.5 * DX, vertical=True, conservative=True)              # the call as it was before K23
-    else:
-        ens.enable_advection(dx=DX, dy=1.5 * DX, vertical=True, conservative=True, order=order, limiter=limiter)
-    if radiate:
-        ens.enable_radiation(f0=rad.F0 * (1.0 + 0.05 * numpy.arange(n)), f1=rad.F1 * (1.0 + 0.1 * (numpy.arange(n) % 3)))
-    if buoyancy:
-        ens.enable_buoyancy()
-    rng = numpy.random.default_rng(5)
-    ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, nL)), QT=rng.normal(0, 2e-7, (n, nL)), U=rng.normal(0, 1e-4, (n, nL)),
-                             WT_surf=ldr.WT * (0.5 + rng.random(n)), WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
-    log = []
     keys = ("U", "V", "THL", "QT") + (("QR",) if micro else ())
 
-    def record():
-        prof = {k: numpy.empty((n, nL)) for k in ("U", "V", "THL", "QT", "QL")}
-        ens.get_profiles_batched(tuple(prof), prof)
-        rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("U", "V", "QT", "THL", "QL") + (("QR",) if micro else ())})
-        rec["substeps"] = numpy.array([-1 if ens.advect_substeps is None else ens.advect_substeps], dtype=numpy.float64)
-        rec["courant"] = numpy.array([-1.0 if ens.advect_courant is None else ens.advect_courant])
-        lid = ens.get_lid_flux_batched()
-        assert lid is None or tuple(lid) == keys
-        for k in keys:
-            rec["lid " + k] = numpy.zeros((n, itot, jtot)) if lid is None else numpy.array(wpr._host(lid[k]))
+    def record(ens, rec):
+        lar.record_substeps(ens, rec)
+        ltr.record_lid(ens, rec, keys)
         if buoyancy:
-            phi = ens.get_pressure_batched()
-            rec["phi"] = numpy.zeros((n, itot, jtot, nL)) if phi is None else numpy.array(wpr._host(phi))
-            rec["wind change"] = numpy.array([-1.0 if ens.buoyancy_wind_change is None else ens.buoyancy_wind_change])
-        log.append(rec)
-    assert ens.get_vertical_wind_batched() is None and ens.get_lid_flux_batched() is None
-    record()
-    for step in range(steps):
-        if step == steps - 1:
-            numpy.random.seed(11)
-            spcpl.variability_nudge_ensemble(ens, 900.0, True, write=False)
-            record()
-        ens.evolve_model_batched(1800.0 + 900.0 * step)
-        record()
-    return ens, log
+            lbr.record_pressure(ens, rec)
+
+    def before(ens):
+        assert ens.get_vertical_wind_batched() is None and ens.get_lid_flux_batched() is None
+    return ensemble_case(engine, n, models.DeviceLESEnsemble if device else (HostThermoTransport2LESEnsemble if thermo else HostTransport2LESEnsemble),
+                         thermo=thermo, micro=micro, diffuse=diffuse, edit=lvr.raise_u,
+                         advection=dict(dx=DX, dy=1.5 * DX, vertical=True, conservative=True, **({} if order is None else {"order": order, "limiter": limiter})),
+                         radiation=lrr.radiation_of(n, "f0", "f1") if radiate else None, enable=lambda ens: buoyancy and ens.enable_buoyancy(),
+                         record=record, before=before, itot=itot, jtot=jtot, nL=nL, steps=steps)
 
 
 def check_ensemble(one, engines, n, variant, limiter="mc"):

@@ -5,29 +5,25 @@ oracle-backed engine with ``les_transport`` for the CPU suite.
 
 The oracle spells the rule out in the statement order of include/spc.h, one operation per NumPy call in the element type, the
 neighbours by numpy.roll, the mass flux by a Python loop over the levels (tests/les_vadvect_ref.mass_flux), so nothing fuses.
-Every device array of the bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes behind it
+Every device array of the bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes behind it
 (and in front of a view off the 16-byte grid) are checked after the launch, the inputs against what was uploaded."""
 import ctypes
 
 import numpy
 import torch
 
-from sp_coupler_amd import _abi, models, spcpl
+from sp_coupler_amd import _abi, models
 from sp_coupler_amd import advection as adv
 from sp_coupler_amd import buoyancy as buo
-from sp_coupler_amd import radiation as rad
 from tests import les_advect_ref as lar
 from tests import les_buoyancy_ref as lbr
-from tests import les_diffuse_ref as ldr
 from tests import les_micro_ref as lmr
+from tests import les_radiate_ref as lrr
 from tests import les_vadvect_ref as lvr
-from tests import les_water_paths_ref as wpr
-from tests import slab_edges
 from tests.gpu_util import assert_bits
-from tests.test_vnudge import make_les_fields
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, cols_table, ensemble_case, fill_args, host_of, np_of, on_both, run_bodies)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 #: a cell that is its own four neighbours, one extent of 1 either way, both neighbours the same cell, itot < jtot, a plane of
 #: exactly 64 columns, and a row longer than a wave
 PLANES = [(1, 1), (1, 2), (2, 1), (2, 2), (3, 5), (8, 8), (5, 33)]
@@ -39,7 +35,6 @@ OUT_FILL = lar.OUT_FILL
 MAX_CELLS = 130 * 4 * 5 * 20                                       # no case is larger
 field_like = lar.field_like
 derived_cols = lbr.derived_cols
-cols_table = lbr.cols_table
 split = lvr.split
 profiles = lvr.profiles
 case = lvr.case
@@ -170,17 +165,9 @@ class Run:
 
     def __init__(self, eng, c, lead=0, cmax=True, mtop=True, ftop=True, pad=0):
         self.eng, self.c = eng, c
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=lead):
-            t, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (t, b, lead, poison)
-            return t
-
-        def prof(tag, a):
-            wide = numpy.full((a.shape[0], a.shape[1] + pad), 1e30, dtype=a.dtype)
-            wide[:, :a.shape[1]] = a
-            return put(tag, wide, 1e30)[:, :a.shape[1]]
+        self.mem = Poisoned(eng)
+        put = lambda tag, a, poison: self.mem.put(tag, a, poison, lead)                    # noqa: E731
+        prof = lambda tag, a: self.mem.rows(tag, a, 1e30, lead, pad)                        # noqa: E731
         self.du, self.dv = put("u", c["u"], float("nan")), put("v", c["v"], float("nan"))
         self.dev = {k: (self.du if x is c["u"] else self.dv if x is c["v"] else put(k, x, float("nan"))) for k, x in c["fields"].items()}
         self.out = {k: put("out " + k, numpy.full_like(x, OUT_FILL), 1e30) for k, x in c["fields"].items()}
@@ -211,13 +198,10 @@ class Run:
             got = self.dftop.cpu().numpy()
             for q, k in enumerate(c["fields"]):
                 assert_bits("%s ftop %s" % (what, k), got[q], ftop[k])
-        same = lambda t, a: numpy.array_equal(numpy.ascontiguousarray(t.cpu().numpy()).view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))   # noqa: E731
         for tag, t, a in [("u", self.du, c["u"]), ("v", self.dv, c["v"]), ("hx", self.dhx, c["hx"]), ("hy", self.dhy, c["hy"]),
                           ("g", self.dg, c["g"]), ("r", self.dr, c["r"])] + [(k, self.dev[k], x) for k, x in c["fields"].items()]:
-            assert same(t, a), (what, tag, "read only")
-        for tag, (t, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + t.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
+            assert Poisoned.read_only(t, a), (what, tag, "read only")
+        self.mem.check_around(what)
         return want, cmax, mtop, ftop
 
 
@@ -249,20 +233,10 @@ def raw_launch(eng, c, names=None, cmax=True, mtop=True, ftop=True, alias=None, 
             setattr(a, slot, t[key].data_ptr())
         else:
             a.out[slot] = t[key].data_ptr()
-    for key, val in (extents or {}).items():
-        setattr(a, key, val)
-    for key in null:
-        setattr(a, key, None)
-    fn = eng.lib.spc_les_transport_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_transport_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
+    fill_args(a, t, (), extents=extents, null=null)
+    rc = abi_call(eng, "spc_les_transport", a)
     host = lambda flag, k: t[k].cpu().numpy() if flag else None                             # noqa: E731
     return rc, {k: t["out " + k].cpu().numpy() for k in names}, host(cmax, "cmax"), host(mtop, "mtop"), host(ftop, "ftop")
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 def _n_for(plane, ktot, n=3):
@@ -275,7 +249,7 @@ def check_parity(eng, plane, ktot, n=3):
     """U, V (the winds themselves), THL and QT against the oracle, cmax, mtop and ftop included; mtop is K17's oracle's; the
     answer is not the input where the plane has a gradient"""
     n = _n_for(plane, ktot, n)
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     want, cmax, mtop, ftop = Run(eng, c).check("n %d plane %s ktot %d" % (n, plane, ktot))
     assert_bits("mtop is K17's", mtop, lvr.oracle(c)[2])
     assert (cmax >= 0).all() and not numpy.signbit(cmax).any() and not numpy.isnan(cmax).any()
@@ -289,7 +263,7 @@ def check_rows(eng, ktot):
     """n = 1, 2, 5 at 3 x 5: hx, hy, g and r differ per LES (and hx from hy), so a wrong l or a swapped profile shows; then the
     same with pitched profiles"""
     for n in NS:
-        c = case((n, 3, 5, ktot), _np(eng), seed=1)
+        c = case((n, 3, 5, ktot), np_of(eng), seed=1)
         assert (c["hx"] != c["hy"]).all() and (n == 1 or (c["hx"][0] != c["hx"][1] and (c["g"][0] != c["g"][1]).all() and (c["r"][0] != c["r"][1]).all()))
         Run(eng, c).check("rows n %d ktot %d" % (n, ktot))
         Run(eng, c, pad=3).check("rows n %d ktot %d pitched" % (n, ktot))
@@ -301,7 +275,7 @@ def check_tiles(eng):
     both sides of every change of spc_les_transport_cols_per_block, and 17 columns at the last supported ktot; the first
     unsupported ktot is refused (SPC_ERR_UNSUPPORTED) and writes nothing.  The thresholds the library reports are the ones that
     follow from the LDS budget and the pitch (derived_cols)"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     esize = numpy.dtype(dtype).itemsize
     first, changes, bad = table = cols_table(eng.transport_cols_per_block)
     assert table == cols_table(lambda k: derived_cols(k, esize))
@@ -324,7 +298,7 @@ def check_tiles(eng):
 
 def check_fields(eng):
     """0 to 6 fields with U and V among them, 1 to 6 without, with and without cmax, mtop and ftop, and the C ABI"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for nf in range(0, 7):
         Run(eng, case((2, 3, 5, 65), dtype, seed=3, names=ALL_NAMES[:nf])).check("%d fields with the winds" % nf)
         if nf:
@@ -348,7 +322,7 @@ def check_fields(eng):
 
 def check_probe(eng):
     """n_fields == 0 with cmax and / or mtop: bit-equal to those of a full launch and to the oracle's"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for shape in ((1, 1, 1, 1), (2, 3, 5, 64), (5, 9, 9, 65)):
         c = case(shape, dtype, seed=6)
         _, want, mwant, _ = oracle(c)
@@ -367,14 +341,14 @@ def check_probe(eng):
 
 def check_alignment(eng, lead, ktot=65):
     """views one (or more) elements off the 16-byte grid"""
-    Run(eng, case((3, 3, 5, ktot), _np(eng), seed=10 + lead), lead=lead).check("lead %d ktot %d" % (lead, ktot))
+    Run(eng, case((3, 3, 5, ktot), np_of(eng), seed=10 + lead), lead=lead).check("lead %d ktot %d" % (lead, ktot))
 
 
 def check_signs(eng):
     """winds of either sign in all combinations (u, v each +, - per LES, so every horizontal face is an inflow or an outflow
     face everywhere), convergent and divergent columns (M of one sign up a column), exact zeros, and winds uniform per level
     (M = 0, mtop = 0, ftop = 0: the rule is horizontal transport, and the oracle of the horizontal fluxes alone agrees)"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for su in (1, -1):
         for sv in (1, -1):
             c = case((2, 4, 5, 9), dtype, seed=7, names=("THL", "QT"))
@@ -436,7 +410,7 @@ def check_special(eng):
     """NaN, +-inf and -0.0 planted in single cells of a field: every output is the oracle's and the cells further than one
     step away hold the bits of a run without them.  A NaN in one wind cell u[l][i][j][k]: every cell outside the columns
     (i - 1 ... i + 1, j) at the levels >= k is bit-equal to the run without it, mtop is NaN there, and cmax stays finite"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c, s, mask = special_case(dtype)
     clean, _, clean_mtop, clean_ftop = Run(eng, c).check("clean")
     r = Run(eng, s)
@@ -494,7 +468,7 @@ def check_refusals(eng):
     """n = 0 is a no-op; nothing to do, a NULL required array, pitch_prof < ktot, an output that is an input or another output,
     a misaligned pointer, a field count outside 0 ... 6 and an extent below 1 are refused by the library and by the engine, and
     no refused call touches anything"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=11)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     E = _abi.SPC_ERR_INVALID_ARGUMENT
@@ -557,12 +531,9 @@ def check_refusals(eng):
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle, cmax, mtop and ftop included"""
     from sp_coupler_amd.transfer import Sharded
-    c = case((n, 3, 5, 40), _np(one), seed=n)
+    c = case((n, 3, 5, 40), np_of(one), seed=n)
     want, cmax, mtop, ftop = oracle(c)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
-    for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+    for tag, eng, up in on_both(one, multi, n):
         u, v = up(c["u"]), up(c["v"])
         t = {k: (u if x is c["u"] else v if x is c["v"] else up(x)) for k, x in c["fields"].items()}
         o = {k: up(numpy.full_like(x, OUT_FILL)) for k, x in c["fields"].items()}
@@ -572,28 +543,23 @@ def check_multi(one, multi, n):
         prof = [up(c[k]) for k in ("hx", "hy", "g", "r")]
         got = eng.les_transport(t, o, u, v, *prof, mtop=m, ftop=ft)
         multi.synchronize()
-        if tag == "multi":
-            blocks = [int(p.shape[0]) for p in o["QT"].parts]
         for q, k in enumerate(NAMES):
-            assert_bits("%s %s" % (tag, k), wpr._host(o[k]), want[k])
+            assert_bits("%s %s" % (tag, k), host_of(o[k]), want[k])
             lidk = numpy.concatenate([p[q].cpu().numpy() for p in ft.parts]) if tag == "multi" else ft[q].cpu().numpy()
             assert_bits("%s ftop %s" % (tag, k), lidk, ftop[k])
-        assert_bits("%s cmax" % tag, wpr._host(got), cmax)
-        assert_bits("%s mtop" % tag, wpr._host(m), mtop)
+        assert_bits("%s cmax" % tag, host_of(got), cmax)
+        assert_bits("%s mtop" % tag, host_of(m), mtop)
         probe = eng.les_transport({}, {}, u, v, *prof)
         multi.synchronize()
-        assert_bits("%s probe" % tag, wpr._host(probe), cmax)
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+        assert_bits("%s probe" % tag, host_of(probe), cmax)
+    return blocks_of(o["QT"], multi, n)
 
 
 BODIES = ("parity", "rows", "tiles", "fields", "probe", "alignment", "signs", "special", "refusals")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 3, 64, 160)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 3, 64, 160)]),
             ("rows", lambda: [check_rows(eng, k) for k in (1, 65)]),
             ("tiles", lambda: check_tiles(eng)),
             ("fields", lambda: check_fields(eng)),
@@ -602,13 +568,12 @@ def check_everything(eng):
             ("signs", lambda: check_signs(eng)),
             ("special", lambda: check_special(eng)),
             ("refusals", lambda: check_refusals(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_transport (CPU suite) ----------------------------------------------------------------------
@@ -720,76 +685,31 @@ def ensemble_run(engine, n, device, conservative=True, buoyancy=False, thermo=Fa
     """tests/les_buoyancy_ref.ensemble_run with enable_advection(vertical=True, conservative=...): after every step every
     profile, the fields, the substeps, the Courant sum, the lid flux of every transported field, and (with buoyancy) phi and
     the largest wind change.  Returns (ens, list of records)"""
-    spcpl.set_engine(engine)
-    cls = models.DeviceLESEnsemble if device else (HostThermoTransportLESEnsemble if thermo else HostTransportLESEnsemble)
-    fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
-    stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
-    gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
-    rng = numpy.random.default_rng(n + 100)
-    fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
-              "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}
-    fields["U"][:, lvr.RAISED[0], lvr.RAISED[1], :] += 2.0
-    if thermo:
-        del fields["Qsat"]
-        fields["THL"] = fields["THL"] - 25.0
-        fields["QT"] = fields["QT"] * 0.35
-        fields["QT"][:, 2, 1, :] *= 2.0
-    if micro:
-        fields["QR"] = numpy.random.default_rng(n).random((n, itot, jtot, nL)) * 1e-5
-    ens.attach_fields({k: v.copy() for k, v in fields.items()})
-    ens.p["presf"] = stack("presf")
-    ens.ql_ref = stack("ql_ref")
-    ens.model_time = 900.0
-    if thermo:
-        ens.enable_thermo()
-    if diffuse:
-        ens.enable_diffusion()
-    if micro:
-        ens.enable_microphysics(qc0=1e-4, v_fall=0.05)
-    if conservative is None:
-        ens.enable_advection(dx=DX, dy=1.5 * DX, vertical=True)                                # the call as it was before K22
-    else:
-        ens.enable_advection(dx=DX, dy=1.5 * DX, vertical=True, conservative=conservative)
-    if radiate:
-        ens.enable_radiation(f0=rad.F0 * (1.0 + 0.05 * numpy.arange(n)), f1=rad.F1 * (1.0 + 0.1 * (numpy.arange(n) % 3)))
-    if buoyancy:
-        ens.enable_buoyancy()
-    rng = numpy.random.default_rng(5)
-    ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, nL)), QT=rng.normal(0, 2e-7, (n, nL)), U=rng.normal(0, 1e-4, (n, nL)),
-                             WT_surf=ldr.WT * (0.5 + rng.random(n)), WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
-    log = []
     keys = ("U", "V", "THL", "QT") + (("QR",) if micro else ())
 
-    def record():
-        prof = {k: numpy.empty((n, nL)) for k in ("U", "V", "THL", "QT", "QL")}
-        ens.get_profiles_batched(tuple(prof), prof)
-        rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("U", "V", "QT", "THL", "QL") + (("QR",) if micro else ())})
-        rec["substeps"] = numpy.array([-1 if ens.advect_substeps is None else ens.advect_substeps], dtype=numpy.float64)
-        rec["courant"] = numpy.array([-1.0 if ens.advect_courant is None else ens.advect_courant])
-        rec["courant z"] = numpy.array([-1.0 if ens.advect_courant_z is None else ens.advect_courant_z])
+    def record(ens, rec):
+        lar.record_substeps(ens, rec, z=True)
         if conservative:
-            lid = ens.get_lid_flux_batched()
-            assert lid is None or tuple(lid) == keys
-            for k in keys:
-                rec["lid " + k] = numpy.zeros((n, itot, jtot)) if lid is None else numpy.array(wpr._host(lid[k]))
+            record_lid(ens, rec, keys)
         if buoyancy:
-            phi = ens.get_pressure_batched()
-            rec["phi"] = numpy.zeros((n, itot, jtot, nL)) if phi is None else numpy.array(wpr._host(phi))
-            rec["wind change"] = numpy.array([-1.0 if ens.buoyancy_wind_change is None else ens.buoyancy_wind_change])
-        log.append(rec)
-    assert ens.get_vertical_wind_batched() is None and (not conservative or ens.get_lid_flux_batched() is None)
-    record()
-    for step in range(steps):
-        if step == steps - 1:
-            numpy.random.seed(11)
-            spcpl.variability_nudge_ensemble(ens, 900.0, True, write=False)
-            record()
-        ens.evolve_model_batched(1800.0 + 900.0 * step)
-        record()
-    return ens, log
+            lbr.record_pressure(ens, rec)
+
+    def before(ens):
+        assert ens.get_vertical_wind_batched() is None and (not conservative or ens.get_lid_flux_batched() is None)
+    # (``conservative`` None: the call as it was before K22)
+    return ensemble_case(engine, n, models.DeviceLESEnsemble if device else (HostThermoTransportLESEnsemble if thermo else HostTransportLESEnsemble),
+                         thermo=thermo, micro=micro, diffuse=diffuse, edit=lvr.raise_u,
+                         advection=dict(dx=DX, dy=1.5 * DX, vertical=True, **({} if conservative is None else {"conservative": conservative})),
+                         radiation=lrr.radiation_of(n, "f0", "f1") if radiate else None, enable=lambda ens: buoyancy and ens.enable_buoyancy(),
+                         record=record, before=before, itot=itot, jtot=jtot, nL=nL, steps=steps)
+
+
+def record_lid(ens, rec, keys):
+    """the lid flux of every transported field (zeros before the first step) into a record of ensemble_case"""
+    lid = ens.get_lid_flux_batched()
+    assert lid is None or tuple(lid) == keys
+    for k in keys:
+        rec["lid " + k] = numpy.zeros(rec["field U"].shape[:3]) if lid is None else numpy.array(host_of(lid[k]))
 
 
 def check_ensemble(one, engines, n, variant):

@@ -5,25 +5,20 @@ libraries), the host twins of models.DeviceLESEnsemble's enable_advection(vertic
 
 The oracle spells the rule out one operation per NumPy call in the element type, the neighbours by numpy.roll, the mass flux by
 a Python loop over the levels, so nothing fuses.  Every device array of the bodies is the LEADING part of a poisoned buffer
-(tests/slab_edges.with_tail); the bytes behind it (and in front of a view off the 16-byte grid) are checked after the launch,
+(tests/les_harness.Poisoned); the bytes behind it (and in front of a view off the 16-byte grid) are checked after the launch,
 the inputs against what was uploaded."""
-import ctypes
 
 import numpy
 import torch
 
-from sp_coupler_amd import _abi, models, spcpl
+from sp_coupler_amd import _abi, models
 from sp_coupler_amd import advection as adv
 from tests import les_advect_ref as lar
-from tests import les_diffuse_ref as ldr
 from tests import les_micro_ref as lmr
-from tests import les_water_paths_ref as wpr
-from tests import slab_edges
 from tests.gpu_util import assert_bits
-from tests.test_vnudge import make_les_fields
+from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, cols_table, ensemble_case, fill_args, host_of, np_of, on_both, run_bodies)
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 PLANES = lar.PLANES
 KTOTS = lar.KTOTS
 NS = lar.NS
@@ -132,17 +127,9 @@ class Run:
 
     def __init__(self, eng, c, lead=0, cmax=True, mtop=True, pad=0):
         self.eng, self.c = eng, c
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=lead):
-            t, b = slab_edges.with_tail(eng, a, poison, lead=lead)
-            self.bufs[tag] = (t, b, lead, poison)
-            return t
-
-        def prof(tag, a):
-            wide = numpy.full((a.shape[0], a.shape[1] + pad), 1e30, dtype=a.dtype)
-            wide[:, :a.shape[1]] = a
-            return put(tag, wide, 1e30)[:, :a.shape[1]]
+        self.mem = Poisoned(eng)
+        put = lambda tag, a, poison: self.mem.put(tag, a, poison, lead)                    # noqa: E731
+        prof = lambda tag, a: self.mem.rows(tag, a, 1e30, lead, pad)                        # noqa: E731
         self.du, self.dv = put("u", c["u"], float("nan")), put("v", c["v"], float("nan"))
         self.dev = {k: (self.du if x is c["u"] else self.dv if x is c["v"] else put(k, x, float("nan"))) for k, x in c["fields"].items()}
         self.out = {k: put("out " + k, numpy.full_like(x, OUT_FILL), 1e30) for k, x in c["fields"].items()}
@@ -167,13 +154,10 @@ class Run:
             assert_bits("%s cmax" % what, self.dcmax.cpu().numpy(), cmax)
         if self.dmtop is not None:
             assert_bits("%s mtop" % what, self.dmtop.cpu().numpy(), mtop)
-        same = lambda t, a: numpy.array_equal(numpy.ascontiguousarray(t.cpu().numpy()).view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8))   # noqa: E731
         for tag, t, a in [("u", self.du, c["u"]), ("v", self.dv, c["v"]), ("hx", self.dhx, c["hx"]), ("hy", self.dhy, c["hy"]),
                           ("g", self.dg, c["g"]), ("r", self.dr, c["r"])] + [(k, self.dev[k], x) for k, x in c["fields"].items()]:
-            assert same(t, a), (what, tag, "read only")
-        for tag, (t, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + t.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
+            assert Poisoned.read_only(t, a), (what, tag, "read only")
+        self.mem.check_around(what)
         return want, cmax, mtop
 
 
@@ -205,34 +189,9 @@ def raw_launch(eng, c, names=None, cmax=True, mtop=True, alias=None, extents=Non
             setattr(a, slot, t[key].data_ptr())
         else:
             a.out[slot] = t[key].data_ptr()
-    for key, val in (extents or {}).items():
-        setattr(a, key, val)
-    for key in null:
-        setattr(a, key, None)
-    fn = eng.lib.spc_les_vadvect_f32 if eng.dtype == torch.float32 else eng.lib.spc_les_vadvect_f64
-    with torch.cuda.device(eng.device):
-        rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
-    torch.cuda.synchronize(eng.device)
+    fill_args(a, t, (), extents=extents, null=null)
+    rc = abi_call(eng, "spc_les_vadvect", a)
     return rc, {k: t["out " + k].cpu().numpy() for k in names}, t["cmax"].cpu().numpy() if cmax else None, t["mtop"].cpu().numpy() if mtop else None
-
-
-def _np(eng):
-    return NP[eng.dtype]
-
-
-def cols_table(eng, top=3000):
-    """(dict C -> the smallest ktot with that many columns per workgroup, the ktot at which the count changes, the first
-    unsupported ktot), asked from the library"""
-    first, changes, last = {}, [], None
-    for ktot in range(1, top):
-        C = eng.vadvect_cols_per_block(ktot)
-        if C != last and last is not None:
-            changes.append(ktot)
-        last = C
-        if C == 0:
-            return first, changes[:-1], ktot
-        first.setdefault(C, ktot)
-    raise AssertionError("no unsupported ktot below %d" % top)
 
 
 def split(ncols):
@@ -246,7 +205,7 @@ def split(ncols):
 def check_parity(eng, plane, ktot, n=3):
     """U, V (the winds themselves), THL and QT against the oracle, cmax and mtop included; the answer is not the input where the
     plane has a divergence"""
-    c = case((n,) + tuple(plane) + (ktot,), _np(eng))
+    c = case((n,) + tuple(plane) + (ktot,), np_of(eng))
     want, cmax, mtop = Run(eng, c).check("n %d plane %s ktot %d" % (n, plane, ktot))
     assert (cmax >= 0).all() and not numpy.signbit(cmax).any()
     if min(plane) > 2 and ktot > 1:
@@ -256,7 +215,7 @@ def check_parity(eng, plane, ktot, n=3):
 def check_rows(eng, ktot):
     """n = 1, 2, 5 at 3 x 5: hx, hy, g and r differ per LES, so a wrong l or a swapped profile shows"""
     for n in NS:
-        c = case((n, 3, 5, ktot), _np(eng), seed=1)
+        c = case((n, 3, 5, ktot), np_of(eng), seed=1)
         assert (c["hx"] != c["hy"]).all() and (n == 1 or (c["hx"][0] != c["hx"][1] and (c["g"][0] != c["g"][1]).all() and (c["r"][0] != c["r"][1]).all()))
         Run(eng, c).check("rows n %d ktot %d" % (n, ktot))
 
@@ -266,18 +225,18 @@ def check_tiles(eng):
     tile ends inside a row, inside an LES, and is one column), ktot on both sides of every change of
     spc_les_vadvect_cols_per_block, and one tall case of 17 columns at the last supported ktot; the first unsupported ktot is
     refused (SPC_ERR_UNSUPPORTED) and writes nothing"""
-    first, changes, bad = cols_table(eng)
+    first, changes, bad = cols_table(eng.vadvect_cols_per_block)
     assert sorted(first) == [16, 32, 64] and len(changes) == 2, (first, changes)
     for C, ktot in first.items():
         for ncols in (C - 1, C, C + 1, 2 * C + 1):
             n, itot, jtot = split(ncols)
             assert eng.vadvect_cols_per_block(ktot) == C
-            Run(eng, case((n, itot, jtot, ktot), _np(eng), seed=2, names=("U", "QT"))).check("C %d: %d x %d x %d x %d" % (C, n, itot, jtot, ktot))
+            Run(eng, case((n, itot, jtot, ktot), np_of(eng), seed=2, names=("U", "QT"))).check("C %d: %d x %d x %d x %d" % (C, n, itot, jtot, ktot))
     for k in changes:
         for ktot in (k - 1, k):
-            Run(eng, case((1, 3, 23, ktot), _np(eng), seed=3, names=("THL",))).check("change at %d: ktot %d" % (k, ktot))
-    Run(eng, case((1, 1, 17, bad - 1), _np(eng), seed=4, names=("V", "QT"))).check("tall: 17 columns of %d" % (bad - 1))
-    rc, got, cmax, mtop = raw_launch(eng, case((1, 1, 2, bad), _np(eng), seed=4, names=("QT",)))
+            Run(eng, case((1, 3, 23, ktot), np_of(eng), seed=3, names=("THL",))).check("change at %d: ktot %d" % (k, ktot))
+    Run(eng, case((1, 1, 17, bad - 1), np_of(eng), seed=4, names=("V", "QT"))).check("tall: 17 columns of %d" % (bad - 1))
+    rc, got, cmax, mtop = raw_launch(eng, case((1, 1, 2, bad), np_of(eng), seed=4, names=("QT",)))
     assert rc == _abi.SPC_ERR_UNSUPPORTED and b"levels" in eng.lib.spc_last_error()
     assert (got["QT"] == OUT_FILL).all() and (cmax == -5.0).all() and (mtop == OUT_FILL).all()
     return first, changes, bad
@@ -285,7 +244,7 @@ def check_tiles(eng):
 
 def check_fields(eng):
     """0 to 6 fields with U and V among them, 1 to 6 without, with and without cmax and mtop, a pitched g / r, and the C ABI"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for nf in range(0, 7):
         Run(eng, case((2, 3, 5, 65), dtype, seed=3, names=ALL_NAMES[:nf])).check("%d fields with the winds" % nf)
         if nf:
@@ -308,7 +267,7 @@ def check_fields(eng):
 
 def check_probe(eng):
     """n_fields == 0 with cmax and / or mtop: bit-equal to those of a full launch and to the oracle's"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for shape in ((1, 1, 1, 1), (2, 3, 5, 64), (5, 9, 9, 161)):
         c = case(shape, dtype, seed=6)
         _, want, mwant = oracle(c)
@@ -327,7 +286,7 @@ def check_probe(eng):
 
 def check_alignment(eng, lead, ktot=65):
     """views one (or more) elements off the 16-byte grid"""
-    Run(eng, case((3, 3, 5, ktot), _np(eng), seed=10 + lead), lead=lead).check("lead %d ktot %d" % (lead, ktot))
+    Run(eng, case((3, 3, 5, ktot), np_of(eng), seed=10 + lead), lead=lead).check("lead %d ktot %d" % (lead, ktot))
 
 
 def column_winds(c, sign, level=None):
@@ -346,7 +305,7 @@ def column_winds(c, sign, level=None):
 def check_columns(eng):
     """all-convergent and all-divergent columns (pb alone or pt alone carries a column), a divergence at one level only (M is
     constant above it), winds uniform per level (M = 0: cmax = +0, every field keeps its bits) and exact zeros"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     for sign in (1, -1):
         c = column_winds(case((2, 4, 3, 9), dtype, seed=8, names=("THL", "QT")), sign)
         want, cmax, mtop = Run(eng, c).check("sign %d" % sign)
@@ -391,7 +350,7 @@ def check_special(eng):
     level away hold the bits of a run without them.  A NaN in one wind cell u[l][i][j][k]: every cell outside the columns
     (i - 1 ... i + 1, j) at the levels >= k is bit-equal to the run without it, and cmax stays finite.  A constant field keeps
     its bits under any winds"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c, s, mask = special_case(dtype)
     clean, _, clean_mtop = Run(eng, c).check("clean")
     r = Run(eng, s)
@@ -455,7 +414,7 @@ def bad_calls(eng, t, o, u, v, hx, hy, g, r, m):
 def check_refusals(eng):
     """n = 0 is a no-op; nothing to do, a NULL g or r, pitch_prof < ktot, an output that is an input or another output and an
     extent below 1 are refused by the library and by the engine, and no refused call touches anything"""
-    dtype = _np(eng)
+    dtype = np_of(eng)
     c = case((2, 2, 3, 8), dtype, seed=11)
     dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(eng.device)              # noqa: E731
     E = _abi.SPC_ERR_INVALID_ARGUMENT
@@ -498,12 +457,9 @@ def check_refusals(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle, cmax and mtop included"""
-    c = case((n, 3, 5, 40), _np(one), seed=n)
+    c = case((n, 3, 5, 40), np_of(one), seed=n)
     want, cmax, mtop = oracle(c)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
-    blocks = None
-    for tag, up, eng in (("one", dev, one), ("multi", sh, multi)):
+    for tag, eng, up in on_both(one, multi, n):
         u, v = up(c["u"]), up(c["v"])
         t = {k: (u if x is c["u"] else v if x is c["v"] else up(x)) for k, x in c["fields"].items()}
         o = {k: up(numpy.full_like(x, OUT_FILL)) for k, x in c["fields"].items()}
@@ -511,26 +467,21 @@ def check_multi(one, multi, n):
         prof = [up(c[k]) for k in ("hx", "hy", "g", "r")]
         got = eng.les_vadvect(t, o, u, v, *prof, mtop=m)
         multi.synchronize()
-        if tag == "multi":
-            blocks = [int(p.shape[0]) for p in o["QT"].parts]
         for k in NAMES:
-            assert_bits("%s %s" % (tag, k), wpr._host(o[k]), want[k])
-        assert_bits("%s cmax" % tag, wpr._host(got), cmax)
-        assert_bits("%s mtop" % tag, wpr._host(m), mtop)
+            assert_bits("%s %s" % (tag, k), host_of(o[k]), want[k])
+        assert_bits("%s cmax" % tag, host_of(got), cmax)
+        assert_bits("%s mtop" % tag, host_of(m), mtop)
         probe = eng.les_vadvect({}, {}, u, v, *prof)
         multi.synchronize()
-        assert_bits("%s probe" % tag, wpr._host(probe), cmax)
-    assert sum(blocks) == n and len(blocks) == len(multi.engines)
-    return blocks
+        assert_bits("%s probe" % tag, host_of(probe), cmax)
+    return blocks_of(o["QT"], multi, n)
 
 
 BODIES = ("parity", "rows", "tiles", "fields", "probe", "alignment", "columns", "special", "refusals")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 3, 64, 161)]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 3, 64, 161)]),
             ("rows", lambda: [check_rows(eng, k) for k in (1, 65)]),
             ("tiles", lambda: check_tiles(eng)),
             ("fields", lambda: check_fields(eng)),
@@ -539,13 +490,12 @@ def check_everything(eng):
             ("columns", lambda: check_columns(eng)),
             ("special", lambda: check_special(eng)),
             ("refusals", lambda: check_refusals(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_vadvect (CPU suite) ------------------------------------------------------------------------
@@ -631,68 +581,22 @@ def ensemble_run(engine, n, thermo, device, micro=False, diffuse=False, vertical
     """tests/les_advect_ref.ensemble_run with U raised by 2 m/s in the column RAISED of every LES (air converges on one side
     of it and diverges on the other) and enable_advection(vertical=...): after every step every profile, the fields, the
     substeps, both Courant sums and W.  Returns (ens, list of records)"""
-    spcpl.set_engine(engine)
-    cls = models.DeviceLESEnsemble if device else (HostThermoVadvectLESEnsemble if thermo else HostVadvectLESEnsemble)
-    fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
-    stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
-    gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
-    rng = numpy.random.default_rng(n + 100)
-    fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
-              "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}
-    fields["U"][:, RAISED[0], RAISED[1], :] += 2.0
-    if thermo:
-        del fields["Qsat"]
-        fields["THL"] = fields["THL"] - 25.0
-        fields["QT"] = fields["QT"] * 0.35
-        fields["QT"][:, 2, 1, :] *= 2.0
-    if micro:
-        fields["QR"] = numpy.random.default_rng(n).random((n, itot, jtot, nL)) * 1e-5
-    ens.attach_fields({k: v.copy() for k, v in fields.items()})
-    ens.p["presf"] = stack("presf")
-    ens.ql_ref = stack("ql_ref")
-    ens.model_time = 900.0
-    if thermo:
-        ens.enable_thermo()
-    if diffuse:
-        ens.enable_diffusion()
-    if micro:
-        ens.enable_microphysics(qc0=1e-4, v_fall=0.05)
-    if vertical is None:
-        ens.enable_advection(dx=dx, dy=1.5 * numpy.asarray(dx))                            # the call as it was before K17
-    else:
-        ens.enable_advection(dx=dx, dy=1.5 * numpy.asarray(dx), vertical=vertical)
-    rng = numpy.random.default_rng(5)
-    ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, nL)), QT=rng.normal(0, 2e-7, (n, nL)), U=rng.normal(0, 1e-4, (n, nL)),
-                             WT_surf=ldr.WT * (0.5 + rng.random(n)), WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
-    log = []
+    def before(ens):
+        assert not vertical or ens.get_vertical_wind_batched() is None
+    # (``vertical`` None: the call as it was before K17)
+    return ensemble_case(engine, n, models.DeviceLESEnsemble if device else (HostThermoVadvectLESEnsemble if thermo else HostVadvectLESEnsemble),
+                         thermo=thermo, micro=micro, diffuse=diffuse, edit=raise_u,
+                         advection=dict(dx=dx, dy=1.5 * numpy.asarray(dx), **({} if vertical is None else {"vertical": vertical})),
+                         record=lambda ens, rec: lar.record_substeps(ens, rec, z=vertical), before=before, itot=itot, jtot=jtot, nL=nL, steps=steps)
 
-    def record():
-        prof = {k: numpy.empty((n, nL)) for k in ("U", "V", "THL", "QT", "QL")}
-        ens.get_profiles_batched(tuple(prof), prof)
-        rec = {"p " + k: numpy.array(v) for k, v in ens.p.items()}
-        rec.update({"got " + k: v for k, v in prof.items()})
-        rec.update({"field " + k: numpy.array(wpr._host(ens.get_fields_batched(k))) for k in ("U", "V", "QT", "THL", "QL") + (("QR",) if micro else ())})
-        rec["substeps"] = numpy.array([-1 if ens.advect_substeps is None else ens.advect_substeps], dtype=numpy.float64)
-        rec["courant"] = numpy.array([-1.0 if ens.advect_courant is None else ens.advect_courant])
-        if vertical:
-            rec["courant z"] = numpy.array([-1.0 if ens.advect_courant_z is None else ens.advect_courant_z])
-        log.append(rec)
-    assert not vertical or ens.get_vertical_wind_batched() is None
-    record()
-    for step in range(steps):
-        if step == steps - 1:
-            numpy.random.seed(11)
-            spcpl.variability_nudge_ensemble(ens, 900.0, True, write=False)
-            record()
-        ens.evolve_model_batched(1800.0 + 900.0 * step)
-        record()
-    return ens, log
+
+def raise_u(fields):
+    fields["U"][:, RAISED[0], RAISED[1], :] += 2.0
 
 
 def check_w(ens, twin):
     """the device W against the twin's: a torch expression, so within a few roundings (4 eps of the largest |W|)"""
-    w, want = wpr._host(ens.get_vertical_wind_batched()), twin.get_vertical_wind_batched()
+    w, want = host_of(ens.get_vertical_wind_batched()), twin.get_vertical_wind_batched()
     assert w.shape == want.shape and numpy.isfinite(want).all() and numpy.abs(want).max() > 0
     assert numpy.abs(w - want).max() <= 4 * numpy.finfo(numpy.float64).eps * numpy.abs(want).max()
 

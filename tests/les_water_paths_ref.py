@@ -3,19 +3,18 @@ tests/test_les_water_paths_gpu.py (each takes an engine: tools/mutation_control.
 mutant libraries), the host twin of models.DeviceLESEnsemble's water-path methods and an oracle-backed engine with
 ``les_water_paths`` for the CPU suite.
 
-Every device array of the bodies is the LEADING part of a poisoned buffer (tests/slab_edges.with_tail); the bytes behind it
+Every device array of the bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes behind it
 (and in front of a view off the 16-byte grid) are checked after the launch."""
 import numpy
 import torch
 
 from sp_coupler_amd import _abi, models, spcpl
 from tests import les_thermo_ref as ltr
-from tests import slab_edges, slab_ref
+from tests import slab_ref
 from tests.gpu_util import assert_bits
+from tests.les_harness import DTYPES, NP, Poisoned, np_of, on_both, run_bodies  # noqa: F401  (DTYPES: for the tests)
 from tests.test_vnudge import make_les_fields
 
-NP = slab_edges.NP
-DTYPES = slab_edges.DTYPES
 PLANES = [(1, 1), (3, 5), (8, 8)]
 #: below, on and above 8 (the sequential rows), 128 (one pairwise block), 256 / 512 (splits that halve exactly); 160 the LES
 #: of the benchmark; 300 splits at 150 -> 144 on the unrolled recursion (the other lengths below 968 split at multiples of 8
@@ -113,17 +112,11 @@ class Run:
         self.eng, self.fields, self.w, self.cloud, self.pad = eng, fields, w, cloud, pad
         dtype, shape = w.dtype, fields[0].shape
         n, ktot = shape[0], shape[-1]
-        self.bufs = {}
-
-        def put(tag, a, poison, lead=0):
-            v, b = slab_edges.with_tail(eng, a, poison, lead=lead, tail_elems=max(64, 4 * ktot))
-            self.bufs[tag] = (v, b, lead, poison)
-            return v
+        self.mem = Poisoned(eng, tail_elems=max(64, 4 * ktot))
+        put = self.mem.put
         self.names = ["F%d" % f for f in range(len(fields))]
         self.dfields = {k: put(k, a, float("nan"), lead) for k, a in zip(self.names, fields)}
-        wide = numpy.full((n, ktot + pad), 1e30, dtype=dtype)
-        wide[:, :ktot] = w
-        self.dw = put("w", wide, 1e30, lead_w)[:, :ktot]
+        self.dw = self.mem.rows("w", w, 1e30, lead_w, pad)
         self.out = {k: put("out " + k, numpy.full(shape[:3], -3.0, dtype), -5.0, lead) for k in self.names}
         self.dtop = put("top", numpy.full(shape[:3], -9, numpy.int32), -11, lead) if top else False
         self.dcover = put("cover", numpy.full((n,), -3.0, dtype), -5.0, lead) if cover else False
@@ -148,26 +141,17 @@ class Run:
             assert self.got[k].cpu().numpy().dtype == want[k].dtype, (what, k)
             assert_bits("%s %s" % (what, k), self.got[k].cpu().numpy(), want[k])
         for k, a in zip(self.names, self.fields):
-            assert numpy.array_equal(self.dfields[k].cpu().numpy().view(numpy.uint8), numpy.ascontiguousarray(a).view(numpy.uint8)), (what, k, "read only")
+            assert Poisoned.read_only(self.dfields[k], a), (what, k, "read only")
         assert numpy.array_equal(self.dw.cpu().numpy(), self.w), (what, "w read only")
-        ktot = self.w.shape[-1]
-        for tag, (v, b, lead, poison) in self.bufs.items():
-            around = torch.cat([b[:lead], b[lead + v.numel():]])
-            assert bool((torch.isnan(around) if poison != poison else around == poison).all()), (what, tag, "written around the array")
-            if self.pad and tag == "w":
-                assert bool((v[:, ktot:] == poison).all()), (what, tag, "written between the rows")
+        self.mem.check_around(what)
         return want
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 # -- bodies ------------------------------------------------------------------------------------------------------------------
 def check_parity(eng, plane, ktot, nf=1, n=3):
     """n x plane rows (3, 45 and 192 rows with n = 3: less than one workgroup of 32 rows, one and a part, six whole ones) of nf
     fields against the oracle; from ktot = 8 on the inputs tell the pairwise order from the k loop"""
-    fields, w = case((n,) + tuple(plane) + (ktot,), _np(eng), nf)
+    fields, w = case((n,) + tuple(plane) + (ktot,), np_of(eng), nf)
     want = Run(eng, fields, w).check("plane %s ktot %d nf %d" % (plane, ktot, nf))
     if ktot >= 8 and plane != (1, 1):
         assert not numpy.array_equal(want["F0"], sequential(fields[0], w))
@@ -178,7 +162,7 @@ def check_rows(eng):
     eight rows span two LES: the cover's per-row atomics); 3 LES of 33 rows, with the cloud outputs"""
     for n, plane in ((1, (1, 1)), (1, (3, 5)), (1, (5, 7)), (5, (7, 1)), (3, (3, 11))):
         assert (n * plane[0] * plane[1]) % ROWS_PER_WORKGROUP
-        fields, w = case((n,) + plane + (24,), _np(eng), 2, seed=n)
+        fields, w = case((n,) + plane + (24,), np_of(eng), 2, seed=n)
         fields[1] = numpy.where(fields[1] > 30.0, fields[1], 0).astype(fields[1].dtype)             # a sparse cloud field
         want = Run(eng, fields, w, cloud=1, top=True, cover=True).check("n %d plane %s" % (n, plane))
         assert n * plane[0] * plane[1] < 15 or ((want["top"] >= 0).any() and (want["top"] < 0).any())
@@ -188,7 +172,7 @@ def check_few_rows(eng):
     """fewer than 8 rows over several LES, so that ONE wave holds live rows of several LES and dead groups behind them: 2 ... 7
     LES of 1 x 1 and 2 LES of 1 x 3, every row cloudy (cover 1 in EVERY LES, not their sum in the first), then one LES clear"""
     for n, plane in [(n, (1, 1)) for n in range(2, 8)] + [(2, (1, 3))]:
-        fields, w = case((n,) + plane + (12,), _np(eng), 1, seed=20 + n)
+        fields, w = case((n,) + plane + (12,), np_of(eng), 1, seed=20 + n)
         q = numpy.abs(fields[0]) + fields[0].dtype.type(1e-3)
         want = Run(eng, [q], w, cloud=0, top=True, cover=True).check("few rows, all cloudy: n %d plane %s" % (n, plane))
         assert (want["cover"] == 1).all() and len(want["cover"]) == n
@@ -200,7 +184,7 @@ def check_few_rows(eng):
 def check_four_fields(eng):
     """four fields in one launch, the cloud outputs taken from the third; ktot on both sides of the first split"""
     for ktot in (7, 129, 160):
-        fields, w = case((3, 3, 5, ktot), _np(eng), 4, seed=9)
+        fields, w = case((3, 3, 5, ktot), np_of(eng), 4, seed=9)
         fields[2] = numpy.where(fields[2] > 20.0, fields[2], 0).astype(fields[2].dtype)
         want = Run(eng, fields, w, cloud=2, top=True, cover=True).check("four fields ktot %d" % ktot)
         assert len({want[k].tobytes() for k in ("F0", "F1", "F2", "F3")}) == 4
@@ -208,14 +192,14 @@ def check_four_fields(eng):
 
 def check_alignment(eng, lead, lead_w, pad):
     """views one (or more) elements off the 16-byte grid and a pitched w"""
-    fields, w = case((3, 3, 5, 65), _np(eng), 2, seed=lead + 10 * lead_w + 100 * pad)
+    fields, w = case((3, 3, 5, 65), np_of(eng), 2, seed=lead + 10 * lead_w + 100 * pad)
     Run(eng, fields, w, cloud=0, top=True, cover=True, lead=lead, lead_w=lead_w, pad=pad).check("lead %d %d pad %d" % (lead, lead_w, pad))
 
 
 def check_cloud(eng):
     """cloudy only at k = 0, only at k = ktot - 1, nowhere; NaN and -0.0 cells; cover 0 and 1; top alone, cover alone, both"""
     for ktot in (5, 40, 130):
-        q, w = cloud_case(_np(eng), ktot)
+        q, w = cloud_case(np_of(eng), ktot)
         want = Run(eng, [q], w, cloud=0, top=True, cover=True).check("cloud ktot %d" % ktot)
         assert want["cover"][0] == 0 and want["cover"][1] == 1 and 0 < want["cover"][2] < 1
         assert want["top"][2, 0].tolist() == [0, ktot - 1, -1, -1, -1] and (want["top"][0] == -1).all()
@@ -226,7 +210,7 @@ def check_cloud(eng):
 def check_nonfinite(eng):
     """a row holding inf against w = 0 (NaN), inf against w > 0 (inf), both signs of inf (NaN), NaN, and rows of -0.0 (+0.0)"""
     for ktot in (5, 8, 200):
-        fields, w = case((2, 3, 5, ktot), _np(eng), 1, seed=3)
+        fields, w = case((2, 3, 5, ktot), np_of(eng), 1, seed=3)
         f = fields[0]
         w[:, 2] = 0.0
         f[:, 0, 0, 2] = numpy.inf
@@ -276,10 +260,9 @@ def check_refusals(eng):
 
 def check_multi(one, multi, n):
     """a MultiDeviceEngine with Sharded row blocks gives the bits of one engine and of the oracle"""
-    fields, w = case((n, 3, 5, 40), _np(one), 2, seed=n)
+    fields, w = case((n, 3, 5, 40), np_of(one), 2, seed=n)
     fields[1] = numpy.where(fields[1] > 20.0, fields[1], 0).astype(fields[1].dtype)
-    dev = lambda a: torch.from_numpy(numpy.ascontiguousarray(a)).to(one.device)          # noqa: E731
-    sh = lambda a: multi.to_devices(numpy.ascontiguousarray(a), rows=n)                    # noqa: E731
+    (_, _, dev), (_, _, sh) = on_both(one, multi, n)
     r1 = one.les_water_paths({"A": dev(fields[0]), "B": dev(fields[1])}, dev(w), cloud="B", top=True, cover=True)
     rm = multi.les_water_paths({"A": sh(fields[0]), "B": sh(fields[1])}, sh(w), cloud="B", top=True, cover=True)
     multi.synchronize()
@@ -295,23 +278,20 @@ def check_multi(one, multi, n):
 BODIES = ("parity", "rows", "few_rows", "four_fields", "alignment", "cloud", "nonfinite")
 
 
-def check_everything(eng):
-    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
-    names of the bodies that failed (AssertionError)."""
-    jobs = [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in KTOTS]),
+def jobs(eng):
+    return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in KTOTS]),
             ("rows", lambda: check_rows(eng)),
             ("few_rows", lambda: check_few_rows(eng)),
             ("four_fields", lambda: check_four_fields(eng)),
             ("alignment", lambda: [check_alignment(eng, *a) for a in ((1, 0, 0), (0, 1, 0), (0, 0, 3), (3, 1, 5))]),
             ("cloud", lambda: check_cloud(eng)),
             ("nonfinite", lambda: check_nonfinite(eng))]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """every single-engine body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the
+    names of the bodies that failed (AssertionError)."""
+    return run_bodies(BODIES, jobs(eng))
 
 
 # -- an oracle-backed engine with les_water_paths (CPU suite) ----------------------------------------------------------------

@@ -10,9 +10,9 @@ import torch
 
 from tests import slab_ref
 from tests.gpu_util import assert_bits
+from tests.les_harness import (  # noqa: F401  (NP, DTYPES, TAIL_ROWS, with_tail: K10's own tests)
+    DTYPES, NP, TAIL_ROWS, np_of as _np, run_bodies, with_tail)
 
-NP = {torch.float64: numpy.float64, torch.float32: numpy.float32}
-DTYPES = (torch.float64, torch.float32)
 
 #: itot x jtot: every residue of nij mod 4 (SLAB_CF_RB rows per wave) and mod 8 (SLAB_U rows of loads in flight), below and
 #: above one workgroup's 256 rows (260: a second workgroup with 4 rows; 257: one with a single row), nij < 8, nij == 1
@@ -21,7 +21,6 @@ QL_KINDS = ("sparse", "all", "last")
 NGS = (1, 5, 63, 64, 65, 257, 600)
 KTOTS = (1, 7, 63, 64, 65, 128, 130, 512)
 K1_SIZES = (1, 7, 8, 9, 127, 128, 129, 255, 256, 257, 8191, 8192, 8193, 20000)
-TAIL_ROWS = 4
 
 
 # -- inputs (NumPy) --------------------------------------------------------------------------------------------------------
@@ -99,18 +98,6 @@ def k1_field(size, dtype, n=3):
 
 
 # -- device plumbing -------------------------------------------------------------------------------------------------------
-def with_tail(eng, a, poison, lead=0, tail_elems=None):
-    """``a`` on the device as a view of a larger buffer: ``lead`` elements of poison in front, then the array, then a poisoned
-    tail of at least TAIL_ROWS rows (at least one LES).  Returns (view, buffer)."""
-    a = numpy.ascontiguousarray(a)
-    row = int(numpy.prod(a.shape[1:])) if a.ndim > 1 else 1
-    tail = tail_elems if tail_elems is not None else max(row, TAIL_ROWS * int(a.shape[-1]))
-    buf = torch.full((lead + a.size + tail,), poison, dtype=torch.from_numpy(a).dtype, device=eng.device)
-    view = buf[lead:lead + a.size].view(a.shape)
-    view.copy_(torch.from_numpy(a).to(eng.device))
-    return view, buf
-
-
 def run_cloud(eng, ql, idx):
     q, qbuf = with_tail(eng, ql, 1.0)
     i, _ = with_tail(eng, idx, int(ql.shape[-1]), tail_elems=max(256, idx.shape[1]))
@@ -130,10 +117,6 @@ def run_means(eng, fields, lead=0, lead_out=0):
         assert got[k].data_ptr() == o.data_ptr()
         assert (buf[:lead_out] == -7.0).all() and (buf[lead_out + o.numel():] == -7.0).all(), k      # nothing written around out
     return {k: v.cpu().numpy() for k, v in got.items()}
-
-
-def _np(eng):
-    return NP[eng.dtype]
 
 
 # -- bodies ----------------------------------------------------------------------------------------------------------------
@@ -238,18 +221,18 @@ def check_means_k1(eng, size):
 MEANS_KTOTS = (160, 33, 2, 4, 8)
 
 
-def check_everything(eng):
-    """every body above on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the names of the
-    bodies that failed (AssertionError) in the order they ran."""
-    jobs = [("cloud_plane", lambda: [check_cloud_plane(eng, p, k) for p in PLANES for k in QL_KINDS]),
+BODIES = ("cloud_plane", "cloud_layers", "cloud_opt_in_lds", "means_plane", "means_k1")
+
+
+def jobs(eng):
+    return [("cloud_plane", lambda: [check_cloud_plane(eng, p, k) for p in PLANES for k in QL_KINDS]),
             ("cloud_layers", lambda: [check_cloud_layers(eng, g, k) for g in NGS for k in KTOTS]),
             ("cloud_opt_in_lds", lambda: check_cloud_opt_in_lds(eng)),
             ("means_plane", lambda: [check_means_plane(eng, p, k) for p in PLANES for k in MEANS_KTOTS]),
             ("means_k1", lambda: [check_means_k1(eng, s) for s in K1_SIZES])]
-    failed = []
-    for name, job in jobs:
-        try:
-            job()
-        except AssertionError:
-            failed.append(name)
-    return failed
+
+
+def check_everything(eng):
+    """the bodies BODIES on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the names of the
+    bodies that failed (AssertionError) in the order they ran."""
+    return run_bodies(BODIES, jobs(eng))

@@ -4,6 +4,7 @@ other table's."""
 import os
 
 from tests import les_buoyancy_ref as lbr
+from tests.les_harness import check_jobs_are_bodies, check_library_names
 from tools import mutation_control as mc
 
 
@@ -30,14 +31,8 @@ def test_edits_change_values_only():
 
 
 def test_library_names_do_not_collide():
-    tables = (mc.MUTANTS, mc.ADVANCE_MUTANTS, mc.THERMO_MUTANTS, mc.WATERPATH_MUTANTS, mc.MICRO_MUTANTS, mc.DIFFUSE_MUTANTS, mc.ADVECT_MUTANTS,
-              mc.VADVECT_MUTANTS, mc.RADIATE_MUTANTS, mc.QTLOCAL_MUTANTS, mc.MOMENTS_MUTANTS, mc.BUOYANCY_MUTANTS, mc.GEO_MUTANTS, mc.LESSTATE_MUTANTS)
-    libs = [mc.lib_of(n, t) for t in tables for n in t]
-    assert len(set(libs)) == len(libs) and mc.lib_of(2, mc.BUOYANCY_MUTANTS).endswith("libspc_buoyancy_mutant2.so")
+    check_library_names(mc.BUOYANCY_MUTANTS, "libspc_buoyancy_mutant2.so")
 
 
 def test_every_body_is_run_by_the_control():
-    """check_everything runs each name of BODIES (a body left out would guard nothing)"""
-    import inspect
-    src = inspect.getsource(lbr.check_everything)
-    assert all('("%s",' % name in src for name in lbr.BODIES)
+    check_jobs_are_bodies(lbr)

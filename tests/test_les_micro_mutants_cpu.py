@@ -1,32 +1,17 @@
 """The K14 table of tools/mutation_control.py (--micro) without a GPU: every edit still applies to the tree, every guard names
 a body of tests/les_micro_ref.py, and the mutant libraries' names collide with no other table's."""
-import os
-
 from tests import les_micro_ref as lmr
+from tests.les_harness import check_jobs_are_bodies, check_library_names, check_mutant_table
 from tools import mutation_control as mc
 
 
 def test_micro_mutants_apply_to_the_tree_and_name_their_guards():
-    table = mc.MICRO_MUTANTS
-    assert sorted(table) == list(range(1, 9))
-    for n, (what, guard, edits) in table.items():
-        assert what and edits and callable(guard) and all(e[0] == mc.MICRO for e in edits), n
-        mod, name = guard.__name__.split(".", 1)
-        assert mod == "les_micro_ref" and name in lmr.BODIES and hasattr(lmr, "check_" + name), (n, guard.__name__)
-        files = mc.patched(n, table=table)
-        for fname, text in files.items():
-            with open(os.path.join(mc.CSRC, fname)) as f:
-                assert text != f.read(), (n, fname)
+    check_mutant_table(mc.MICRO_MUTANTS, (mc.MICRO,), lmr)
 
 
 def test_library_names_do_not_collide():
-    tables = (mc.MUTANTS, mc.ADVANCE_MUTANTS, mc.THERMO_MUTANTS, mc.WATERPATH_MUTANTS, mc.MICRO_MUTANTS, mc.GEO_MUTANTS, mc.LESSTATE_MUTANTS)
-    libs = [mc.lib_of(n, t) for t in tables for n in t]
-    assert len(set(libs)) == len(libs) and mc.lib_of(2, mc.MICRO_MUTANTS).endswith("libspc_micro_mutant2.so")
+    check_library_names(mc.MICRO_MUTANTS, "libspc_micro_mutant2.so")
 
 
 def test_every_body_is_run_by_the_control():
-    """check_everything runs each name of BODIES (a body left out would guard nothing)"""
-    import inspect
-    src = inspect.getsource(lmr.check_everything)
-    assert all('("%s",' % name in src for name in lmr.BODIES)
+    check_jobs_are_bodies(lmr)

@@ -22,10 +22,9 @@ import torch
 
 from oracle import vnudge_oracle as vo
 from tests import vnudge_f32_ref as v32
+from tests.les_harness import DTYPES, NP, run_bodies  # noqa: F401  (DTYPES: for the tests)
 from tests.test_vnudge import FieldLES, make_les_fields
 
-NP = {torch.float64: numpy.float64, torch.float32: numpy.float32}
-DTYPES = (torch.float64, torch.float32)
 BODIES = ("designed_levels", "tall", "std_many_workgroups", "small_trees", "chunk_edges", "ragged_columns")
 EPS64, EPS32 = float(numpy.finfo(numpy.float64).eps), float(numpy.finfo(numpy.float32).eps)
 THL_ULP = {torch.float64: 8, torch.float32: 4}      # the bounds of tests/test_vnudge.py and tests/test_vnudge_f32_gpu.py (THL_ULP)
@@ -355,15 +354,13 @@ def check_ragged_columns(eng):
     check_body(eng, "ragged_columns")
 
 
+def jobs(eng, names=BODIES):
+    return [(name, lambda name=name: globals()["check_" + name](eng)) for name in names]
+
+
 def check_everything(eng, names=BODIES):
     """the bodies on one engine: what tools/mutation_control.py runs on a mutant library.  Returns the names that failed."""
-    failed = []
-    for name in names:
-        try:
-            globals()["check_" + name](eng)
-        except AssertionError:
-            failed.append(name)
-    return failed
+    return run_bodies(names, jobs(eng, names))
 
 
 # -- the old matrix ----------------------------------------------------------------------------------------------------------

@@ -7,69 +7,26 @@ cross-compiles gfx950).  A run without --build (GPU) runs the properties of test
 the shipped library and of every mutant library, in ONE process (Engine(lib_path=...)).  Expected: the shipped library passes
 all, every mutant fails at least the property that guards its line.  Prints a table; exit status 1 if a mutant survives or
 the shipped library fails.  tests/test_mutation_table.py checks on the CPU that every edit still applies to the tree.
-Mutants 28 ... are slips of K10 (spc_slab.hpp); their guards are the bodies of tests/slab_edges.py, which the GPU tests of
-tests/test_slab_gpu.py run on the shipped library.
-ADVANCE_MUTANTS is the table of K11 (spc_advance.hpp), numbered on its own and chosen with --advance; its guards are the
-bodies of tests/les_advance_ref.py, which tests/test_les_advance_gpu.py runs on the shipped library.
-THERMO_MUTANTS is the table of K12 (spc_thermo.hpp), chosen with --thermo; its guards are the bodies of
-tests/les_thermo_ref.py, which tests/test_les_thermo_gpu.py runs on the shipped library.
-WATERPATH_MUTANTS is the table of K13 (spc_waterpath.hpp), chosen with --waterpath; its guards are the bodies of
-tests/les_water_paths_ref.py, which tests/test_les_water_paths_gpu.py runs on the shipped library.
-MICRO_MUTANTS is the table of K14 (spc_micro.hpp), chosen with --micro; its guards are the bodies of
-tests/les_micro_ref.py, which tests/test_les_micro_gpu.py runs on the shipped library.
-DIFFUSE_MUTANTS is the table of K15 (spc_diffuse.hpp), chosen with --diffuse; its guards are the bodies of
-tests/les_diffuse_ref.py, which tests/test_les_diffuse_gpu.py runs on the shipped library.
-ADVECT_MUTANTS is the table of K16 (spc_advect.hpp), chosen with --advect; its guards are the bodies of
-tests/les_advect_ref.py, which tests/test_les_advect_gpu.py runs on the shipped library.
-VADVECT_MUTANTS is the table of K17 (spc_vadvect.hpp), chosen with --vadvect; its guards are the bodies of
-tests/les_vadvect_ref.py, which tests/test_les_vadvect_gpu.py runs on the shipped library.
-TRANSPORT_MUTANTS is the table of K22 (spc_transport.hpp), chosen with --transport; its guards are the bodies of
-tests/les_transport_ref.py, which tests/test_les_transport_gpu.py runs on the shipped library.
-TRANSPORT2_MUTANTS is the table of K23 (spc_transport2.hpp), chosen with --transport2; its guards are the bodies of
-tests/les_transport2_ref.py, which tests/test_les_transport2_gpu.py runs on the shipped library.
-RADIATE_MUTANTS is the table of K18 (spc_radiate.hpp), chosen with --radiate; its guards are the bodies of
-tests/les_radiate_ref.py, which tests/test_les_radiate_gpu.py runs on the shipped library.
-QTLOCAL_MUTANTS is the table of K19 (spc_qtlocal.hpp), chosen with --qtlocal; its guards are the bodies of
-tests/les_qt_local_ref.py, which tests/test_les_qt_local_gpu.py runs on the shipped library.
-BUOYANCY_MUTANTS is the table of K21 (spc_buoyancy.hpp), chosen with --buoyancy; its guards are the bodies of
-tests/les_buoyancy_ref.py, which tests/test_les_buoyancy_gpu.py runs on the shipped library.
-MOMENTS_MUTANTS is the table of K20 (spc_moments.hpp), chosen with --moments; its guards are the bodies of
-tests/les_moments_ref.py, which tests/test_les_moments_gpu.py runs on the shipped library.
-GEO_MUTANTS is the table of K8 (spc_geo.hpp), chosen with --geo; its guards are the bodies of tests/geo_edges.py, which
-tests/test_geo_gpu.py runs on the shipped library.  LESSTATE_MUTANTS is the table of K9 (spc_lesstate.hpp), chosen with
---lesstate; its guards are the bodies of tests/les_state_ref.py, which tests/test_les_state_gpu.py runs on the shipped library.
-VNUDGE_MUTANTS is the table of K6 (spc_vnudge.hpp, spc_vnudge2.hpp), chosen with --vnudge; its guards are the bodies of
-tests/vnudge_edges.py, which tests/test_vnudge_edges_gpu.py runs on the shipped library; its run ends with the shape matrix of
-tests/test_vnudge.py (the guard that existed before) on every mutant.
-Both runs end with the edits of *_EQUIVALENT (edits proved to change no output: expected to fail NO body) and, for K8, with
-the guards that existed before tests/geo_edges.py on the mutants the new bodies were written for; the K9 run ends with
-OLD_BODIES of tests/les_state_ref.py on mutants 12 and 13 in the same way.
+Mutants 28 ... are slips of K10 (spc_slab.hpp); their guards are the bodies of tests/slab_edges.py.
+Every other kernel has a table numbered on its own, chosen with its flag; TABLES below lists them: the flag, the kernel, the
+module under tests/ whose bodies guard the table, and the GPU test that runs those bodies on the shipped library.  A run of
+such a table ends with the edits of its *_EQUIVALENT table where it has one (edits proved to change no output: expected to
+fail NO body) and with the guards that existed before its module on the mutants the new bodies were written for (K8: the
+earlier bodies of tests/geo_edges.py; K9: OLD_BODIES of tests/les_state_ref.py; K6: the shape matrix of tests/test_vnudge.py
+on every mutant).
 usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py > profiles/mutation_control.log
        python tools/mutation_control.py --only 28 29 30 31 32 33 34 35 > profiles/mutation_control_slab.log
-       python tools/mutation_control.py --advance --build && python tools/mutation_control.py --advance > profiles/mutation_control_advance.log
-       python tools/mutation_control.py --thermo --build && python tools/mutation_control.py --thermo > profiles/mutation_control_thermo.log
-       python tools/mutation_control.py --waterpath --build && python tools/mutation_control.py --waterpath > profiles/mutation_control_waterpath.log
-       python tools/mutation_control.py --micro --build && python tools/mutation_control.py --micro > profiles/mutation_control_micro.log
-       python tools/mutation_control.py --diffuse --build && python tools/mutation_control.py --diffuse > profiles/mutation_control_diffuse.log
-       python tools/mutation_control.py --advect --build && python tools/mutation_control.py --advect > profiles/mutation_control_advect.log
-       python tools/mutation_control.py --vadvect --build && python tools/mutation_control.py --vadvect > profiles/mutation_control_vadvect.log
-       python tools/mutation_control.py --radiate --build && python tools/mutation_control.py --radiate > profiles/mutation_control_radiate.log
-       python tools/mutation_control.py --qtlocal --build && python tools/mutation_control.py --qtlocal > profiles/mutation_control_qtlocal.log
-       python tools/mutation_control.py --moments --build && python tools/mutation_control.py --moments > profiles/mutation_control_moments.log
-       python tools/mutation_control.py --buoyancy --build && python tools/mutation_control.py --buoyancy > profiles/mutation_control_buoyancy.log
-       python tools/mutation_control.py --transport --build && python tools/mutation_control.py --transport > profiles/mutation_control_transport.log
-       python tools/mutation_control.py --transport2 --build && python tools/mutation_control.py --transport2 > profiles/mutation_control_transport2.log
-       python tools/mutation_control.py --geo --build && python tools/mutation_control.py --geo > profiles/mutation_control_geo.log
-       python tools/mutation_control.py --lesstate --build && python tools/mutation_control.py --lesstate > profiles/mutation_control_lesstate.log
-       python tools/mutation_control.py --vnudge --build && python tools/mutation_control.py --vnudge > profiles/mutation_control_vnudge.log"""
+       python tools/mutation_control.py --<flag> --build && python tools/mutation_control.py --<flag> > profiles/mutation_control_<flag>.log"""
 import argparse
+import collections
 import os
 import shutil
 import subprocess
 import sys
 import traceback
 from concurrent.futures import ThreadPoolExecutor
+from functools import partial
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -98,16 +55,39 @@ LESSTATE = "spc_lesstate.hpp"
 LESSTATE_HOST = "spc_lesstate_host.hpp"
 A9 = "(col0 + ((c ^ 1) < ncol ? (c ^ 1) : c)) * pitchG"     # the neighbouring column of the slab (mutant 9)
 
-def slab_edges(name):
-    """guard of a K10 mutant: the body ``name`` of tests/slab_edges.py on both engines (float64, float32) of the library"""
+
+def body_guard(module, name, dtypes=None):
+    """guard of a mutant: the body ``name`` of tests/``module``.py on the engines of the library, one per dtype (``dtypes``:
+    names of torch dtypes; default the module's DTYPES, float64 and float32)"""
     def guard(engine_of):
-        from tests import slab_edges as se
+        import importlib
+        import torch
+        m = importlib.import_module("tests." + module)
         failed = []
-        for dtype in se.DTYPES:
-            failed += se.check_everything(engine_of(dtype))
+        for dtype in (m.DTYPES if dtypes is None else [getattr(torch, d) for d in dtypes]):
+            failed += m.check_everything(engine_of(dtype))
         return name in failed, sorted(set(failed))
-    guard.__name__ = "slab_edges." + name
+    guard.__name__ = module + "." + name
     return guard
+
+
+slab_edges = partial(body_guard, "slab_edges")
+advance_body = partial(body_guard, "les_advance_ref")
+thermo_body = partial(body_guard, "les_thermo_ref")
+waterpath_body = partial(body_guard, "les_water_paths_ref")
+micro_body = partial(body_guard, "les_micro_ref")
+diffuse_body = partial(body_guard, "les_diffuse_ref")
+advect_body = partial(body_guard, "les_advect_ref")
+vadvect_body = partial(body_guard, "les_vadvect_ref")
+radiate_body = partial(body_guard, "les_radiate_ref")
+buoyancy_body = partial(body_guard, "les_buoyancy_ref")
+geo_body = partial(body_guard, "geo_edges", dtypes=("float64",))
+lesstate_body = partial(body_guard, "les_state_ref", dtypes=("float64",))
+qtlocal_body = partial(body_guard, "les_qt_local_ref")
+moments_body = partial(body_guard, "les_moments_ref")
+vnudge_body = partial(body_guard, "vnudge_edges")
+transport_body = partial(body_guard, "les_transport_ref")
+transport2_body = partial(body_guard, "les_transport2_ref")
 
 
 # n: (the slip, the property of tests/semantic_props.py that guards it -- or a callable guard(engine_of) -> (detected, names of
@@ -208,17 +188,6 @@ MUTANTS = {
 }
 
 
-def advance_body(name):
-    """guard of a K11 mutant: the body ``name`` of tests/les_advance_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_advance_ref as lar
-        failed = []
-        for dtype in lar.DTYPES:
-            failed += lar.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_advance_ref." + name
-    return guard
-
 
 # K11 (spc_advance.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 6 stores the rows of the batch before once more, inside the field).
@@ -244,17 +213,6 @@ ADVANCE_MUTANTS = {
 }
 
 
-def thermo_body(name):
-    """guard of a K12 mutant: the body ``name`` of tests/les_thermo_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_thermo_ref as ltr
-        failed = []
-        for dtype in ltr.DTYPES:
-            failed += ltr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_thermo_ref." + name
-    return guard
-
 
 # K12 (spc_thermo.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 1 keeps the index inside the table).
@@ -279,17 +237,6 @@ THERMO_MUTANTS = {
         [(THERMO, "if (DQS) dqs = (epsp * (d * P.inv_step)) / (den * den);", "if (DQS) dqs = (epsp * d) / (den * den);")]),
 }
 
-
-def waterpath_body(name):
-    """guard of a K13 mutant: the body ``name`` of tests/les_water_paths_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_water_paths_ref as wpr
-        failed = []
-        for dtype in wpr.DTYPES:
-            failed += wpr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_water_paths_ref." + name
-    return guard
 
 
 # K13 (spc_waterpath.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
@@ -340,17 +287,6 @@ WATERPATH_MUTANTS = {
 }
 
 
-def micro_body(name):
-    """guard of a K14 mutant: the body ``name`` of tests/les_micro_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_micro_ref as lmr
-        failed = []
-        for dtype in lmr.DTYPES:
-            failed += lmr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_micro_ref." + name
-    return guard
-
 
 # K14 (spc_micro.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 3 reads level 0 of the lane's own column; mutant 2 uses the lane's own new values, so it
@@ -376,28 +312,6 @@ MICRO_MUTANTS = {
 }
 
 
-def diffuse_body(name):
-    """guard of a K15 mutant: the body ``name`` of tests/les_diffuse_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_diffuse_ref as ldr
-        failed = []
-        for dtype in ldr.DTYPES:
-            failed += ldr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_diffuse_ref." + name
-    return guard
-
-
-def advect_body(name):
-    """guard of a K16 mutant: the body ``name`` of tests/les_advect_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_advect_ref as lar
-        failed = []
-        for dtype in lar.DTYPES:
-            failed += lar.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_advect_ref." + name
-    return guard
 
 
 # K16 (spc_advect.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
@@ -425,17 +339,6 @@ ADVECT_MUTANTS = {
 }
 
 
-def vadvect_body(name):
-    """guard of a K17 mutant: the body ``name`` of tests/les_vadvect_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_vadvect_ref as lvr
-        failed = []
-        for dtype in lvr.DTYPES:
-            failed += lvr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_vadvect_ref." + name
-    return guard
-
 
 # K17 (spc_vadvect.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 1 stores M[k] where M[k + 1] belongs, in the same LDS cell; mutant 4 reads r at the clamped
@@ -461,17 +364,6 @@ VADVECT_MUTANTS = {
         [(VADVECT, "const T s = pb + pt;", "const T s = pt;")]),
 }
 
-
-def radiate_body(name):
-    """guard of a K18 mutant: the body ``name`` of tests/les_radiate_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_radiate_ref as lrr
-        failed = []
-        for dtype in lrr.DTYPES:
-            failed += lrr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_radiate_ref." + name
-    return guard
 
 
 # K18 (spc_radiate.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
@@ -499,17 +391,6 @@ RADIATE_MUTANTS = {
         [(RADIATE, "const T xc = x < (T)0 ? (T)0 : (x > x_hi ? x_hi : x);", "const T xc = x < (T)0 ? (T)0 : x;")]),
 }
 
-
-def buoyancy_body(name):
-    """guard of a K21 mutant: the body ``name`` of tests/les_buoyancy_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_buoyancy_ref as lbr
-        failed = []
-        for dtype in lbr.DTYPES:
-            failed += lbr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_buoyancy_ref." + name
-    return guard
 
 
 # K21 (spc_buoyancy.hpp), numbered on its own.  Every mutant changes a VALUE only: no address, loop bound, barrier or launch
@@ -560,17 +441,6 @@ DIFFUSE_MUTANTS = {
 }
 
 
-def geo_body(name):
-    """guard of a K8 mutant: the body ``name`` of tests/geo_edges.py on the float64 engine of the library (K8 is float64 on
-    every engine)"""
-    def guard(engine_of):
-        import torch
-        from tests import geo_edges
-        failed = geo_edges.check_everything(engine_of(torch.float64))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "geo_edges." + name
-    return guard
-
 
 # K8 (spc_geo.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches, none changes a barrier or an index; mutant 6 makes the tile loop (uniform over the workgroup) end
@@ -620,7 +490,7 @@ GEO_MUTANTS = {
     15: ("K8 non-finite points: only p is made EXTERIOR, q keeps the code its arithmetic gave", geo_body("non_finite_points"),
          [(GEO, _STORE, _STORE.replace(": (uint16_t)GEO_EXTERIOR", ": (uint16_t)(code_q << 8)"), 2)]),
 }
-#: the mutants of the exact stage and of the tile loop: main_advance runs the guards that existed before tests/geo_edges.py
+#: the mutants of the exact stage and of the tile loop: main_table runs the guards that existed before tests/geo_edges.py
 #: on them once (the scale test of tests/test_geo_gpu.py included) and prints what they find; this is information, not a check
 GEO_OLD_GUARDS = (1, 2, 6)
 # edits proved to change no output (expected to fail no body).  A: r is -0.0 only after fmod(-360 k, 360); -0.0 - 180 and
@@ -635,17 +505,6 @@ GEO_EQUIVALENT = {
           [(GEO, "if ((y1 > py && y2 <= py) || (y2 > py && y1 <= py)) {", "if ((y1 >= py && y2 < py) || (y2 >= py && y1 < py)) {")]),
 }
 
-
-def lesstate_body(name):
-    """guard of a K9 mutant: the body ``name`` of tests/les_state_ref.py on the float64 engine of the library (K9 is float64
-    on every engine)"""
-    def guard(engine_of):
-        import torch
-        from tests import les_state_ref
-        failed = les_state_ref.check_everything(engine_of(torch.float64))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_state_ref." + name
-    return guard
 
 
 # K9 (spc_lesstate.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
@@ -715,24 +574,13 @@ LESSTATE_MUTANTS = {
          lesstate_body("odd_substream_counts"),
          [(LESSTATE, "pl.T = q <= MT_N ? 0 : (q - 1) / MT_N;", "pl.T = q <= MT_N ? 0 : q / MT_N;")]),
 }
-#: the mutants the new bodies were written for: main_advance runs OLD_BODIES of tests/les_state_ref.py on them once
+#: the mutants the new bodies were written for: main_table runs OLD_BODIES of tests/les_state_ref.py on them once
 LESSTATE_OLD_GUARDS = (12, 13)
 LESSTATE_EQUIVALENT = {
     "A": ("K9 ls_seek: the binary search with < for <= (the loop behind it walks to the right LES)",
           [(LESSTATE, "if (4 * P.elem_off[mid] <= e) lo_l = mid; else hi_l = mid - 1;", "if (4 * P.elem_off[mid] < e) lo_l = mid; else hi_l = mid - 1;")]),
 }
 
-
-def qtlocal_body(name):
-    """guard of a K19 mutant: the body ``name`` of tests/les_qt_local_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_qt_local_ref as qlr
-        failed = []
-        for dtype in qlr.DTYPES:
-            failed += qlr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_qt_local_ref." + name
-    return guard
 
 
 # K19 (spc_qtlocal.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
@@ -762,17 +610,6 @@ QTLOCAL_MUTANTS = {
 }
 
 
-def moments_body(name):
-    """guard of a K20 mutant: the body ``name`` of tests/les_moments_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_moments_ref as mr
-        failed = []
-        for dtype in mr.DTYPES:
-            failed += mr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_moments_ref." + name
-    return guard
-
 
 # K20 (spc_moments.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches and none can hang (mutant 2 divides by T(0) on planes of one row; mutants 5 and 6 read the lane's own
@@ -797,17 +634,6 @@ MOMENTS_MUTANTS = {
         [(MOMENTS, "for (; r < nij; ++r) {", "for (; r < nij - 1; ++r) {")]),
 }
 
-
-def vnudge_body(name):
-    """guard of a K6 mutant: the body ``name`` of tests/vnudge_edges.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import vnudge_edges as ve
-        failed = []
-        for dtype in ve.DTYPES:
-            failed += ve.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "vnudge_edges." + name
-    return guard
 
 
 # K6 (spc_vnudge.hpp, spc_vnudge2.hpp, spc_vnudge_host.hpp), numbered on its own.  Every mutant only computes wrong numbers:
@@ -882,17 +708,6 @@ def patched(n, src=CSRC, table=None):
     return files
 
 
-def transport_body(name):
-    """guard of a K22 mutant: the body ``name`` of tests/les_transport_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_transport_ref as ltr
-        failed = []
-        for dtype in ltr.DTYPES:
-            failed += ltr.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_transport_ref." + name
-    return guard
-
 
 # K22 (spc_transport.hpp), numbered on its own.  Every mutant only computes wrong numbers: none reads or writes outside what the
 # shipped kernel touches (mutant 1 reads x, which the cell reads anyway, for x[ip]; mutant 5 starts K17's chain, which K22 calls,
@@ -917,17 +732,6 @@ TRANSPORT_MUTANTS = {
         [(TRANSPORT, "p.ftop[f * p.ncols + col0 + w.c] = Ft;", "p.ftop[f * p.ncols + col0 + w.c] = Fb;")]),
 }
 
-
-def transport2_body(name):
-    """guard of a K23 mutant: the body ``name`` of tests/les_transport2_ref.py on both engines (float64, float32) of the library"""
-    def guard(engine_of):
-        from tests import les_transport2_ref as lt2
-        failed = []
-        for dtype in lt2.DTYPES:
-            failed += lt2.check_everything(engine_of(dtype))
-        return name in failed, sorted(set(failed))
-    guard.__name__ = "les_transport2_ref." + name
-    return guard
 
 
 # K23 (spc_transport2.hpp), numbered on its own.  Every mutant only computes wrong numbers from values the shipped kernel loads
@@ -955,17 +759,11 @@ TRANSPORT2_MUTANTS = {
 
 def _tag(table):
     """(library prefix, source directory prefix) of a table"""
-    for t, tag in ((ADVANCE_MUTANTS, ("advance_", "adv")), (THERMO_MUTANTS, ("thermo_", "thermo")), (WATERPATH_MUTANTS, ("waterpath_", "waterpath")),
-                   (MICRO_MUTANTS, ("micro_", "micro")), (DIFFUSE_MUTANTS, ("diffuse_", "diffuse")),
-                   (ADVECT_MUTANTS, ("advect_", "advect")), (VADVECT_MUTANTS, ("vadvect_", "vadvect")),
-                   (RADIATE_MUTANTS, ("radiate_", "radiate")), (QTLOCAL_MUTANTS, ("qtlocal_", "qtlocal")),
-                   (MOMENTS_MUTANTS, ("moments_", "moments")), (BUOYANCY_MUTANTS, ("buoyancy_", "buoyancy")),
-                   (TRANSPORT_MUTANTS, ("transport_", "transport")), (TRANSPORT2_MUTANTS, ("transport2_", "transport2")),
-                   (GEO_MUTANTS, ("geo_", "geo")),
-                   (GEO_EQUIVALENT, ("geo_eq_", "geoeq")), (LESSTATE_MUTANTS, ("lesstate_", "lesstate")),
-                   (LESSTATE_EQUIVALENT, ("lesstate_eq_", "lesstateeq")), (VNUDGE_MUTANTS, ("vnudge_", "vnudge"))):
-        if table is t:
-            return tag
+    for t in TABLES:
+        if table is t.table:
+            return t.lib, t.src
+        if table is not None and table is t.equivalent:
+            return t.lib[:-1] + "_eq_", t.src + "eq"
     return "", ""
 
 
@@ -1027,14 +825,12 @@ def run(lib_path):
     return failed
 
 
-def main_advance(only=None, table=None, kernel="K11", ref="les_advance", module=None, gpu_test=None, equivalent=None, old_guards=None,
-                 notes=None):
-    """the control of ADVANCE_MUTANTS (or of another table numbered on its own): the bodies of tests/les_advance_ref.py
-    (tests/``module``.py) on the shipped library, then on every mutant; then the edits of ``equivalent`` (expected to fail
-    no body) and ``old_guards(engine_of)`` -> names that failed, on the mutants it is given for (printed, not judged)"""
+def main_table(only, t):
+    """the control of a table numbered on its own (an entry of TABLES): the bodies of tests/``module``.py on the shipped
+    library, then on every mutant; then the edits of ``equivalent`` (expected to fail no body) and
+    ``old_guards[n](engine_of)`` -> names that failed, on the mutants it is given for (printed, not judged)"""
     import torch
-    table = ADVANCE_MUTANTS if table is None else table
-    module, gpu_test = module or ref + "_ref", gpu_test or "test_%s_gpu" % ref
+    table, kernel, module, gpu_test, equivalent, old_guards, notes = t.table, t.kernel, t.module, t.gpu_test, t.equivalent, t.old_guards, t.notes
     print("mutation control of tests/%s.py (tests/%s.py) on %s" % (module, gpu_test, torch.cuda.get_device_name(0)))
     chosen = sorted(n for n in table if only is None or n in only)
     clean = run_guard(table[chosen[0]][1], None)[1]
@@ -1086,11 +882,11 @@ def lesstate_old_guard(engine_of):
     return les_state_ref.check_everything(engine_of(torch.float64), names=les_state_ref.OLD_BODIES)
 
 
-def main_vnudge(only=None):
-    """the control of VNUDGE_MUTANTS (main_advance), then the old guard on every mutant: at least VNUDGE_MIN_SURVIVORS of them
+def main_vnudge(only, t):
+    """the control of VNUDGE_MUTANTS (main_table), then the old guard on every mutant: at least VNUDGE_MIN_SURVIVORS of them
     must pass the old matrix -- they are what the bodies of tests/vnudge_edges.py add -- and each of those was detected by its
     body above"""
-    bad = main_advance(only, VNUDGE_MUTANTS, "K6", module="vnudge_edges", gpu_test="test_vnudge_edges_gpu")
+    bad = main_table(only, t)
     if only is not None:
         return bad
     print("old guard: %s, on the shipped library and on every mutant" % vnudge_old_guard.__doc__)
@@ -1116,7 +912,7 @@ def geo_notes():
     return ["exact_tails: " + geo_edges.exact_tails_counts()]
 
 
-def main(only=None):
+def main(only=None, t=None):
     import torch
     print("mutation control of tests/test_semantic_gpu.py and tests/slab_edges.py on %s" % torch.cuda.get_device_name(0))
     bad = 0
@@ -1150,73 +946,48 @@ def main(only=None):
     return 1 if bad else 0
 
 
+#: every table in the order of its flag on the command line (the first one set is run); the unnumbered MUTANTS first, without a
+#: flag.  lib, src: what the names of a mutant's library and of its source directory under build/mutants/ carry
+Table = collections.namedtuple("Table", "flag table kernel lib src module gpu_test equivalent old_guards notes main",
+                               defaults=(None, None, None, main_table))
+TABLES = (
+    Table(None, MUTANTS, None, "", "", "slab_edges", "test_slab_gpu", main=main),
+    Table("advance", ADVANCE_MUTANTS, "K11", "advance_", "adv", "les_advance_ref", "test_les_advance_gpu"),
+    Table("thermo", THERMO_MUTANTS, "K12", "thermo_", "thermo", "les_thermo_ref", "test_les_thermo_gpu"),
+    Table("waterpath", WATERPATH_MUTANTS, "K13", "waterpath_", "waterpath", "les_water_paths_ref", "test_les_water_paths_gpu"),
+    Table("micro", MICRO_MUTANTS, "K14", "micro_", "micro", "les_micro_ref", "test_les_micro_gpu"),
+    Table("diffuse", DIFFUSE_MUTANTS, "K15", "diffuse_", "diffuse", "les_diffuse_ref", "test_les_diffuse_gpu"),
+    Table("advect", ADVECT_MUTANTS, "K16", "advect_", "advect", "les_advect_ref", "test_les_advect_gpu"),
+    Table("vadvect", VADVECT_MUTANTS, "K17", "vadvect_", "vadvect", "les_vadvect_ref", "test_les_vadvect_gpu"),
+    Table("radiate", RADIATE_MUTANTS, "K18", "radiate_", "radiate", "les_radiate_ref", "test_les_radiate_gpu"),
+    Table("qtlocal", QTLOCAL_MUTANTS, "K19", "qtlocal_", "qtlocal", "les_qt_local_ref", "test_les_qt_local_gpu"),
+    Table("moments", MOMENTS_MUTANTS, "K20", "moments_", "moments", "les_moments_ref", "test_les_moments_gpu"),
+    Table("buoyancy", BUOYANCY_MUTANTS, "K21", "buoyancy_", "buoyancy", "les_buoyancy_ref", "test_les_buoyancy_gpu"),
+    Table("transport", TRANSPORT_MUTANTS, "K22", "transport_", "transport", "les_transport_ref", "test_les_transport_gpu"),
+    Table("transport2", TRANSPORT2_MUTANTS, "K23", "transport2_", "transport2", "les_transport2_ref", "test_les_transport2_gpu"),
+    Table("geo", GEO_MUTANTS, "K8", "geo_", "geo", "geo_edges", "test_geo_gpu", GEO_EQUIVALENT, {n: geo_old_guard for n in GEO_OLD_GUARDS}, geo_notes),
+    Table("lesstate", LESSTATE_MUTANTS, "K9", "lesstate_", "lesstate", "les_state_ref", "test_les_state_gpu", LESSTATE_EQUIVALENT,
+          {n: lesstate_old_guard for n in LESSTATE_OLD_GUARDS}),
+    Table("vnudge", VNUDGE_MUTANTS, "K6", "vnudge_", "vnudge", "vnudge_edges", "test_vnudge_edges_gpu", main=main_vnudge),
+)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description="mutation control of the semantic tests")
     ap.add_argument("--build", nargs="*", type=int, metavar="n",
                     help="build the mutant libraries n ... (default: all) instead of running the control")
     ap.add_argument("--only", nargs="+", type=int, metavar="n", help="run the control for the mutants n ... only")
     ap.add_argument("-j", type=int, default=4, help="parallel compiles for --build (at most 16)")
-    ap.add_argument("--advance", action="store_true", help="the table of K11 (ADVANCE_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--thermo", action="store_true", help="the table of K12 (THERMO_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--waterpath", action="store_true", help="the table of K13 (WATERPATH_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--micro", action="store_true", help="the table of K14 (MICRO_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--diffuse", action="store_true", help="the table of K15 (DIFFUSE_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--advect", action="store_true", help="the table of K16 (ADVECT_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--vadvect", action="store_true", help="the table of K17 (VADVECT_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--radiate", action="store_true", help="the table of K18 (RADIATE_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--qtlocal", action="store_true", help="the table of K19 (QTLOCAL_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--moments", action="store_true", help="the table of K20 (MOMENTS_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--buoyancy", action="store_true", help="the table of K21 (BUOYANCY_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--transport", action="store_true", help="the table of K22 (TRANSPORT_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--transport2", action="store_true", help="the table of K23 (TRANSPORT2_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--geo", action="store_true", help="the table of K8 (GEO_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--lesstate", action="store_true", help="the table of K9 (LESSTATE_MUTANTS) instead of MUTANTS")
-    ap.add_argument("--vnudge", action="store_true", help="the table of K6 (VNUDGE_MUTANTS) instead of MUTANTS")
+    for t in TABLES[1:]:
+        ap.add_argument("--" + t.flag, action="store_true", help="the table of %s (%s_MUTANTS) instead of MUTANTS" % (t.kernel, t.flag.upper()))
     args = ap.parse_args()
-    table = (ADVANCE_MUTANTS if args.advance else THERMO_MUTANTS if args.thermo else WATERPATH_MUTANTS if args.waterpath else MICRO_MUTANTS if args.micro
-             else DIFFUSE_MUTANTS if args.diffuse else ADVECT_MUTANTS if args.advect else VADVECT_MUTANTS if args.vadvect else RADIATE_MUTANTS if args.radiate
-             else QTLOCAL_MUTANTS if args.qtlocal else MOMENTS_MUTANTS if args.moments else BUOYANCY_MUTANTS if args.buoyancy else TRANSPORT_MUTANTS if args.transport else TRANSPORT2_MUTANTS if args.transport2 else GEO_MUTANTS if args.geo
-             else LESSTATE_MUTANTS if args.lesstate else VNUDGE_MUTANTS if args.vnudge else MUTANTS)
-    equivalent = GEO_EQUIVALENT if args.geo else LESSTATE_EQUIVALENT if args.lesstate else None
+    t = next((t for t in TABLES[1:] if getattr(args, t.flag)), TABLES[0])
     if args.build is not None:
-        unknown = sorted(set(args.build) - set(table))
+        unknown = sorted(set(args.build) - set(t.table))
         if unknown:
             ap.error("no mutant %s" % unknown)
-        rc = build(args.build or sorted(table), args.j, table)
-        if equivalent and not args.build:
-            rc |= build(sorted(equivalent), args.j, equivalent)
+        rc = build(args.build or sorted(t.table), args.j, t.table)
+        if t.equivalent and not args.build:
+            rc |= build(sorted(t.equivalent), args.j, t.equivalent)
         sys.exit(rc)
-    only = set(args.only) if args.only else None
-    if args.geo:
-        sys.exit(main_advance(only, GEO_MUTANTS, "K8", module="geo_edges", gpu_test="test_geo_gpu", equivalent=GEO_EQUIVALENT,
-                              old_guards={n: geo_old_guard for n in GEO_OLD_GUARDS}, notes=geo_notes))
-    if args.lesstate:
-        sys.exit(main_advance(only, LESSTATE_MUTANTS, "K9", module="les_state_ref", gpu_test="test_les_state_gpu",
-                              equivalent=LESSTATE_EQUIVALENT, old_guards={n: lesstate_old_guard for n in LESSTATE_OLD_GUARDS}))
-    if args.vnudge:
-        sys.exit(main_vnudge(only))
-    if args.thermo:
-        sys.exit(main_advance(only, THERMO_MUTANTS, "K12", "les_thermo"))
-    if args.waterpath:
-        sys.exit(main_advance(only, WATERPATH_MUTANTS, "K13", "les_water_paths"))
-    if args.micro:
-        sys.exit(main_advance(only, MICRO_MUTANTS, "K14", "les_micro"))
-    if args.diffuse:
-        sys.exit(main_advance(only, DIFFUSE_MUTANTS, "K15", "les_diffuse"))
-    if args.advect:
-        sys.exit(main_advance(only, ADVECT_MUTANTS, "K16", "les_advect"))
-    if args.vadvect:
-        sys.exit(main_advance(only, VADVECT_MUTANTS, "K17", "les_vadvect"))
-    if args.radiate:
-        sys.exit(main_advance(only, RADIATE_MUTANTS, "K18", "les_radiate"))
-    if args.qtlocal:
-        sys.exit(main_advance(only, QTLOCAL_MUTANTS, "K19", "les_qt_local"))
-    if args.buoyancy:
-        sys.exit(main_advance(only, BUOYANCY_MUTANTS, "K21", "les_buoyancy"))
-    if args.moments:
-        sys.exit(main_advance(only, MOMENTS_MUTANTS, "K20", "les_moments"))
-    if args.transport:
-        sys.exit(main_advance(only, TRANSPORT_MUTANTS, "K22", "les_transport"))
-    if args.transport2:
-        sys.exit(main_advance(only, TRANSPORT2_MUTANTS, "K23", "les_transport2"))
-    sys.exit((main_advance if args.advance else main)(only))
+    sys.exit(t.main(set(args.only) if args.only else None, t))
