@@ -877,10 +877,19 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         return self._means
 
     # -- second moments per level (K20) ---------------------------------------------------------------------------------------
-    _stats_w = None                                    # (W,) of the fields as they are now: the tensor handed to K20, or None
+    _stats_w = None                                    # ((the substep's seconds, host Rhobf) W was made of, W: the tensor handed to K20, or None)
 
     def _drop_statistics(self):
         self._stats, self._stats_host, self._stats_w = None, {}, None
+
+    def _drop_w_statistics(self):
+        """what depends on W alone: its moments and the pairs that hold it; the moments of the other fields stay cached"""
+        from . import statistics as st
+        holds = lambda key: st.FACE in (key if isinstance(key, tuple) else (key,))                # noqa: E731
+        for d in (self._stats or {}).values():
+            for key in [key for key in d if holds(key)]:
+                del d[key]
+        self._stats_host = {kk: a for kk, a in self._stats_host.items() if not holds(kk[1])}
 
     def _statistics_fields(self):
         """name -> device field of every field of ``statistics.FIELDS`` the ensemble holds now (QL after K12 where thermo is
@@ -892,10 +901,15 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         have = {}
         for k in st.FIELDS:
             if k == st.FACE:
-                if self._stats_w is None:
-                    self._stats_w = (self.get_vertical_wind_batched(),)
-                if self._stats_w[0] is not None:
-                    have[k] = self._stats_w[0]
+                # W is a torch expression of K17's mass flux (new only in a step, which drops everything), the substep's seconds
+                # and p["Rhobf"]: keyed as get_water_paths_batched keys its weights
+                key = (self._vadvect_dt,) + (_f64(self.p["Rhobf"]) if self.advect_vertical else ())
+                old = self._stats_w
+                self._stats_w = _kept(old, key, lambda: (key, self.get_vertical_wind_batched()))
+                if self._stats_w is not old:
+                    self._drop_w_statistics()                     # moments of another W (p["Rhobf"] was set) are stale
+                if self._stats_w[1] is not None:
+                    have[k] = self._stats_w[1]
             elif k in f:
                 have[k] = f[k]
         return have

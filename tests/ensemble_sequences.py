@@ -1,50 +1,76 @@
 """Random operation sequences of models.DeviceLESEnsemble (the class lives in sp_coupler_amd/device_les.py; the name in models
-is the same object) against its eager NumPy twin (tests/les_radiate_ref.py:
-HostRadiateLESEnsemble / HostThermoRadiateLESEnsemble, the top of the chain of twins): the body of
-tests/test_ensemble_sequences_cpu.py (on oracle-backed engines) and tests/test_ensemble_sequences_gpu.py (on the card).
+is the same object) against its eager NumPy twin (tests/les_full_ref.py: HostFullLESEnsemble / HostThermoFullLESEnsemble, the
+top of the chain of twins): the body of tests/test_ensemble_sequences_cpu.py (on oracle-backed engines) and
+tests/test_ensemble_sequences_gpu.py (on the card).
 
-The device ensemble is a lazy, cached state machine (_thermo_stale, _means, _wp / _wp_host / _wp_w, _thermo_means, four profile
-uploads keyed on their inputs, the ping-pong buffers of K14 / K16 / K17, the fused K11 step); the twin computes everything
-eagerly from its fields.  ``generate`` draws a list of operations that are all valid in the state they meet, mutations and
-sparse observations mixed; ``replay`` applies the list to both and compares every observation bit for bit
-(gpu_util.assert_bits), W alone within the bound of les_vadvect_ref.check_w (a torch expression).
+The device ensemble is a lazy, cached state machine (_thermo_stale, _means, _wp / _wp_host / _wp_w, _thermo_means, the profile
+uploads keyed on their inputs, the ping-pong buffers of K14 / K16 / K17 / K22, the fused K11 step, K19's count buffer and its wait
+for the forcing, K20's partial cache _stats / _stats_host / _stats_w, K21's profiles and pressure, K22's lid flux summed over the
+substeps); the twin computes everything eagerly from its fields.  ``generate`` draws a list of operations that are all valid in
+the state they meet, mutations and sparse observations mixed; ``replay`` applies the list to both and compares every observation
+bit for bit (gpu_util.assert_bits), with two exceptions: W within the bound of les_vadvect_ref.check_w (a torch expression), and
+the moments that hold W (its mean, variance and standard deviation, its covariances, TKE with it) bit for bit against NumPy's
+moments (the oracle of K20) of the device's OWN get_vertical_wind_batched() read at that operation, the rule of
+les_moments_ref.ensemble_run: the twin's W differs in its last bits.
+
+The modes: the six of the first version (thermo, diffuse, micro, advect, vertical, radiate), then "qt" (K19; the kind local /
+strong comes from ``params``), "buoyancy" (K21; needs vertical), "conservative" (K22; needs vertical), "order2" (K23; needs
+conservative; the limiter comes from ``params``) and "stats" (K20: statistics observations are drawn only with it).  The new modes
+stand at the END of MODES: the bit mask that seeds the generator, and so every sequence of the 48 old subsets, is what it was
+(tests/test_ensemble_sequences_cpu.py holds their digest).
 
 Conditions, asserted here and not left to the callers:
   * every sequence has its full length, runs to its end on both sides and ends with a full record: every profile (batched,
-    raw and through every row), every field, the water paths with the cloud cover and their means, rain2d, the flux, W and
-    the Courant numbers of what is enabled;
+    raw and through every row), every field, the water paths with the cloud cover and their means, rain2d, the flux, W, the
+    Courant numbers, the counts, the lid flux, the pressure, the wind change and the statistics (whole and through every row) of
+    what is enabled;
   * every sequence holds a step that no read precedes and two consecutive mutations;
-  * every mode a sequence enables launches its engine method at least once on the device side (``check_launched``);
-  * over a set of cases every kind of operation occurs (``check_kinds``).
+  * every mode a sequence enables launches its engine method at least once on the device side (``check_launched``); K19 launches
+    only behind the ``qt_forcings`` that every "qt" sequence holds between two steps, and never before it;
+  * over a set of cases every kind of operation occurs that their modes allow (``check_kinds``).
 Properties of the device ensemble (and of the twin, where it has the method) that need no twin:
   (a) a row getter of key k returns row i of what get_profiles_batched((k,)) returns at that moment: checked at every ``row``
-      operation, the row getter FIRST (so it has to refresh p itself), and for every row and key at the final record;
+      operation, the row getter FIRST (so it has to refresh p itself), and for every row and key at the final record; a row's
+      get_statistics returns row i of the ensemble's get_statistics: at every ``row_stats`` and for every row at the record;
   (b) reading anything twice in a row gives the same bits and launches nothing the second time: checked at every observation.
       Two readers hold no cache of their own and launch their own reduction every time, and only that: the cloud fraction
-      (slab_cloud_fraction) and the water path means (slab_means of the cached paths)."""
+      (slab_cloud_fraction) and the water path means (slab_means of the cached paths);
+  (c) statistics that were read since the last mutation launch nothing (K20's cache is partial: what is new goes through a
+      launch, what is cached does not), and a new p["Rhobf"] alone costs only the moments that hold W."""
 import itertools
 
 import numpy
 
 from sp_coupler_amd import diffusion as df
 from sp_coupler_amd import models, spcpl
+from sp_coupler_amd import qt_forcing as qf
 from sp_coupler_amd import radiation as rad
+from sp_coupler_amd import statistics as st
 from tests import les_diffuse_ref as ldr
-from tests import les_radiate_ref as lrr
+from tests import les_full_ref as lfr
+from tests import les_moments_ref as lmo
 from tests import les_vadvect_ref as lvr
 from tests.gpu_util import assert_bits
 from tests.les_harness import host_of
 from tests.test_vnudge import make_les_fields
 
-MODES = ("thermo", "diffuse", "micro", "advect", "vertical", "radiate")
-LATE = ("diffuse", "micro", "advect", "radiate")                  # may be enabled mid-sequence (vertical comes with advect)
+OLD_MODES = ("thermo", "diffuse", "micro", "advect", "vertical", "radiate")
+NEW_MODES = ("qt", "buoyancy", "conservative", "order2", "stats")
+MODES = OLD_MODES + NEW_MODES
+LATE = ("diffuse", "micro", "advect", "radiate", "qt", "buoyancy")  # may be enabled mid-sequence (vertical, conservative and order2 come with advect)
+WITH_ADVECT = ("vertical", "conservative", "order2")
 METHOD = {"thermo": "les_thermo", "diffuse": "les_diffuse", "micro": "les_microphysics", "advect": "les_advect",
-          "vertical": "les_vadvect", "radiate": "les_radiate"}
+          "vertical": "les_vadvect", "radiate": "les_radiate", "qt": "les_qt_local", "buoyancy": "les_buoyancy",
+          "conservative": "les_transport", "order2": "les_transport2", "stats": "les_moments"}
 COUNTED = ("slab_means", "slab_cloud_fraction", "variability_nudge", "les_advance", "les_thermo", "les_water_paths", "les_microphysics",
-           "les_diffuse", "les_advect", "les_vadvect", "les_radiate")
-MUTATIONS = ("step", "step0", "row_step", "nudge", "forcings", "set_field", "presf", "rhobf", "enable")
-OBSERVATIONS = ("profiles", "row", "field", "wp", "wp_means", "row_wp", "cloudfrac", "flux", "w", "courant")
+           "les_diffuse", "les_advect", "les_vadvect", "les_radiate", "les_moments", "les_qt_local", "les_buoyancy", "les_transport",
+           "les_transport2")
+MUTATIONS = ("step", "step0", "row_step", "nudge", "forcings", "set_field", "presf", "rhobf", "enable", "qt_forcings", "qt_kind", "readvect")
+OBSERVATIONS = ("profiles", "row", "field", "wp", "wp_means", "row_wp", "cloudfrac", "flux", "w", "courant", "counts", "lid", "pressure",
+                "stats", "row_stats")
 KINDS = MUTATIONS + OBSERVATIONS + ("record",)
+NEEDS = {"qt_forcings": "qt", "qt_kind": "qt", "readvect": "buoyancy", "counts": "qt", "lid": "conservative", "pressure": "buoyancy",
+         "stats": "stats", "row_stats": "stats"}                  # the mode without which a kind of operation is never drawn
 RELAUNCH = {"cloudfrac": {"slab_cloud_fraction"}, "wp_means": {"slab_means"}, "record": {"slab_means"}}      # property (b)
 PROFILE_KEYS = ("U", "V", "THL", "QT", "QL", "T", "QL_ice", "QR", "presf", "Rhobf", "Rain", "PS")
 ROW_GETTERS = {"get_profile_U": "U", "get_profile_V": "V", "get_profile_THL": "THL", "get_profile_QT": "QT", "get_profile_QL": "QL",
@@ -52,30 +78,68 @@ ROW_GETTERS = {"get_profile_U": "U", "get_profile_V": "V", "get_profile_THL": "T
 DTS = (300.0, 450.0, 900.0, 900.0)
 ITOT, JTOT, NL, NG = 4, 5, 20, 19
 LENGTH = 14
+LIMITERS = ("mc", "none")
+ALWAYS = ("U", "V", "THL", "QT", "QL")                            # the fields of statistics.FIELDS every ensemble of ``build`` holds
+# the gravity wave of K21 and the spacings and Courant limits of ``enable``: the most wave substeps a step of DTS asks for is
+# ceil(30 * 900 / (0.3 * 24000)) = 4, far below advection.MAX_SUBSTEPS (tests/test_ensemble_sequences_cpu.py checks every case)
+LATE_WAVE_SPEED = 24.0
+READVECT = dict(dx=0.8 * lvr.DX, cfl=0.3)
+DEFAULT = {"kind": "local", "limiter": "mc"}
+
+
+def valid(modes):
+    m = set(modes)
+    return m <= set(MODES) and ("advect" in m or "vertical" not in m) and ("vertical" in m or not m & {"buoyancy", "conservative"}) and \
+        ("conservative" in m or "order2" not in m)
 
 
 def combinations():
-    """the 48 valid subsets of MODES (vertical needs advect), in a fixed order"""
-    out = [c for r in range(len(MODES) + 1) for c in itertools.combinations(MODES, r) if "advect" in c or "vertical" not in c]
+    """the 48 valid subsets of the six old modes (vertical needs advect), in a fixed order"""
+    out = [c for r in range(len(OLD_MODES) + 1) for c in itertools.combinations(OLD_MODES, r) if "advect" in c or "vertical" not in c]
     assert len(out) == 48
     return out
+
+
+def new_combinations(background):
+    """the non-empty subsets of the five new modes that are valid on top of ``background``, in a fixed order"""
+    return [tuple(background) + c for r in range(1, len(NEW_MODES) + 1) for c in itertools.combinations(NEW_MODES, r)
+            if valid(tuple(background) + c)]
 
 
 def name_of(modes):
     return "+".join(modes) or "plain"
 
 
+def _mask(modes):
+    return sum(1 << MODES.index(m) for m in modes)
+
+
+def params(seed, modes):
+    """the kind of K19 and the limiter of K23 of the sequence ``generate(seed, modes)``: pure functions of (seed, modes)"""
+    bits = bin(_mask(modes)).count("1")
+    return {"kind": qf.KINDS[(int(seed) + bits) % 2], "limiter": LIMITERS[(int(seed) + bits // 2) % 2]}
+
+
 # -- the ensemble ------------------------------------------------------------------------------------------------------------
-def enable(ens, mode, modes, late=False):
-    """one of the four opt-in modes: with the parameters of les_radiate_ref.ensemble_run, or, ``late``, with others"""
+def enable(ens, mode, modes, late=False, par=DEFAULT):
+    """one of the opt-in modes: with the parameters of les_radiate_ref.ensemble_run, or, ``late``, with others"""
     n = ens.n
     if mode == "diffuse":
         ens.enable_diffusion(**(dict(k_max=0.5 * df.K_MAX, h_mix=1.25 * df.H_MIX, k_bg=2.0 * df.K_BG) if late else {}))
     elif mode == "micro":
         ens.enable_microphysics(**(dict(qc0=8e-5, v_fall=0.04, k_acc=3.0) if late else dict(qc0=1e-4, v_fall=0.05)))
-    elif mode == "advect":
-        dx = 1.25 * lvr.DX if late else lvr.DX
-        ens.enable_advection(dx=dx, dy=1.5 * dx, vertical="vertical" in modes, **(dict(cfl=0.4) if late else {}))
+    elif mode in ("advect", "readvect"):
+        dx = READVECT["dx"] if mode == "readvect" else 1.25 * lvr.DX if late else lvr.DX
+        kw = dict(cfl=READVECT["cfl"]) if mode == "readvect" else dict(cfl=0.4) if late else {}
+        if "conservative" in modes:
+            kw["conservative"] = True
+        if "order2" in modes:
+            kw.update(order=2, limiter=par["limiter"])
+        ens.enable_advection(dx=dx, dy=1.5 * dx, vertical="vertical" in modes, **kw)
+    elif mode == "qt":
+        ens.enable_qt_forcing(par["kind"])
+    elif mode == "buoyancy":
+        ens.enable_buoyancy(**(dict(wave_speed=LATE_WAVE_SPEED) if late else {}))
     else:
         assert mode == "radiate", mode
         s = 0.9 if late else 1.0
@@ -83,15 +147,24 @@ def enable(ens, mode, modes, late=False):
                              kappa=rad.KAPPA * (1.0 + 0.02 * (numpy.arange(n) % 5)))
 
 
-def build(engine, device, n, modes, late=()):
+def _comes_with(mode, modes):
+    """what an ``enable`` of ``mode`` switches on"""
+    return {mode} | ({m for m in WITH_ADVECT if m in modes} if mode == "advect" else set())
+
+
+def _on_at_start(modes, late):
+    return set(modes) - set(late) - ({m for m in WITH_ADVECT} if "advect" in late else set())
+
+
+def build(engine, device, n, modes, late=(), par=DEFAULT):
     """the ensemble of les_radiate_ref.ensemble_run (fields of make_les_fields at 4 x 5 x 20, the thermo variant's THL and QT,
     U raised in lvr.RAISED with the vertical advection, QR with the microphysics, presf, ql_ref, model_time = 900) on
     ``engine``: the device ensemble or the twin (thermo is the twin's class, so it is enabled here), with every mode of
     ``modes`` enabled that is not in ``late``"""
-    assert set(modes) <= set(MODES) and ("advect" in modes or "vertical" not in modes) and set(late) <= set(LATE) & set(modes)
+    assert valid(modes) and set(late) <= set(LATE) & set(modes)
     spcpl.set_engine(engine)
     thermo = "thermo" in modes
-    cls = models.DeviceLESEnsemble if device else (lrr.HostThermoRadiateLESEnsemble if thermo else lrr.HostRadiateLESEnsemble)
+    cls = models.DeviceLESEnsemble if device else (lfr.HostThermoFullLESEnsemble if thermo else lfr.HostFullLESEnsemble)
     fs = [make_les_fields(ITOT, JTOT, NL, seed=60 + (i % 7)) for i in range(n)]
     stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
     gcm = models.BatchedSyntheticGCM(n + 4, NG, 21)
@@ -116,7 +189,7 @@ def build(engine, device, n, modes, late=()):
         ens.enable_thermo()
     for mode in LATE:
         if mode in modes and mode not in late:
-            enable(ens, mode, modes)
+            enable(ens, mode, modes, par=par)
     rng = numpy.random.default_rng(5)
     ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, NL)), QT=rng.normal(0, 2e-7, (n, NL)), U=rng.normal(0, 1e-4, (n, NL)),
                              WT_surf=ldr.WT * (0.5 + rng.random(n)), WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
@@ -142,13 +215,23 @@ def _is_step(op):
 def generate(seed, modes, length=LENGTH):
     """``length`` operations, the last a full record, every one valid in the state it meets (the generator tracks what exists:
     RWP needs the QR field, the flux, W and the Courant numbers a step of their mode).  Plain tuples of Python values: a
-    printed list can be pasted into ``replay``.  A row is given as any integer, taken modulo n."""
+    printed list can be pasted into ``replay``.  A row is given as any integer, taken modulo n.  A kind of operation that
+    belongs to a mode the sequence does not have has weight 0 and consumes no draw."""
     modes = tuple(m for m in MODES if m in modes)
-    rng = numpy.random.default_rng([int(seed), sum(1 << MODES.index(m) for m in modes)])
+    assert valid(modes), modes
+    rng = numpy.random.default_rng([int(seed), _mask(modes)])
     pending = [m for m in LATE if m in modes and rng.random() < 0.5]
-    on = set(modes) - set(pending) - ({"vertical"} if "advect" in pending else set())
+    if "buoyancy" in modes and "advect" in pending and "buoyancy" not in pending:
+        pending.append("buoyancy")                                 # (K21 is enabled after, and for, the advection)
+    on = _on_at_start(modes, pending)
     stepped = set()                                                # modes that have seen a step since they were enabled
     lag = [False]                                                  # without thermo the QL field follows a new QT at the next step only
+    handed = [False]                                               # qt_forcings has been drawn
+    counted = [False]                                              # K19 has launched: there are counts a change of kind has to drop
+    dropped = [False]                                              # the last mutation was a readvect: a step now runs without the buoyancy
+    wread = [False]                                                # the moments of W have been read since the last mutation but a new Rhobf
+    hint = [None]                                                  # the observation that would notice a stale cache behind the last mutation
+    ops = []
     small = lambda: int(rng.integers(0, 1 << 16))                                         # noqa: E731
     wp_names = ("LWP", "TWP") + (("RWP",) if "micro" in modes else ())
     field_names = ("U", "V", "THL", "QT", "QL", "Qsat") + (("QR",) if "micro" in modes else ())
@@ -157,37 +240,74 @@ def generate(seed, modes, length=LENGTH):
         k = int(rng.integers(1, min(most, len(names)) + 1))
         return tuple(names[i] for i in sorted(rng.choice(len(names), k, replace=False)))
 
+    def todo():
+        """the operations that are still to come whatever is drawn: the late enables and, with "qt", the forcing"""
+        return len(pending) + (1 if "qt" in modes and not handed[0] else 0)
+
     def mutation(kind=None, room=True):
         # (a nudge whose ql_av is not that of its QT is refused, "f(a) and f(b) must have different signs": none is drawn there)
+        # (readvect puts the buoyancy back among the late enables: it needs the room for one more forced operation)
+        again = "buoyancy" in on and length - 1 - len(ops) >= todo() + 3
         kind = kind or _choose(rng, [("step", 5), ("step0", 1), ("row_step", 1), ("nudge", 0 if lag[0] else 2), ("forcings", 1.5), ("set_field", 1.5), ("presf", 1),
-                                     ("rhobf", 1), ("enable", 2.5 if pending and room else 0)])
+                                     ("rhobf", 1), ("enable", 2.5 if pending and room else 0), ("qt_forcings", 0 if "qt" not in modes or not room else 0.7 if handed[0] else 2),
+                                     ("qt_kind", 0 if "qt" not in on else 2.5 if counted[0] else 0.5), ("readvect", 2.5 if again else 0),
+                                     ("rhobf", 12 if wread[0] else 0),                               # (W and its moments are made of Rhobf, ...
+                                     ("presf", 2.5 if "buoyancy" in stepped else 0)])                # ... K21's profiles of presf: more of both there)
         if kind == "step":
             op = ("step", DTS[int(rng.integers(len(DTS)))])
         elif kind == "row_step":
             op = ("row_step", small(), DTS[int(rng.integers(len(DTS)))])
         elif kind == "nudge":
             op = ("nudge", bool(rng.integers(2)), 1 + small())
-        elif kind in ("forcings", "cloudfrac"):
+        elif kind in ("forcings", "cloudfrac", "qt_forcings"):
             op = (kind, small())
+            handed[0] = handed[0] or kind == "qt_forcings"
         elif kind == "set_field":
             op = ("set_field", ("QT", "THL")[int(rng.integers(2))], small())
         elif kind == "enable":
-            mode = pending.pop(int(rng.integers(len(pending))))
-            on.update({mode} | ({"vertical"} if mode == "advect" and "vertical" in modes else set()))
+            able = [m for m in pending if not (m == "buoyancy" and "advect" in pending)]
+            mode = able[int(rng.integers(len(able)))]
+            pending.remove(mode)
+            on.update(_comes_with(mode, modes))
             op = ("enable", mode)
+        elif kind == "readvect":
+            on.discard("buoyancy")
+            stepped.difference_update(("advect", "buoyancy") + WITH_ADVECT)
+            pending.append("buoyancy")
+            op = ("readvect",)
         else:
             op = (kind,)
+        hint[0] = ("counts",) if kind == "qt_kind" else ("lid",) if kind == "readvect" and "conservative" in on else \
+            ("stats", ("U", "W"), (("W", "THL"),)) if kind == "rhobf" and wread[0] else \
+            ("stats", ("W", "QT"), (("U", "W"),)) if kind == "step" and "stats" in modes and "vertical" in on else None
+        wread[0] = wread[0] and kind == "rhobf"
+        dropped[0] = kind == "readvect"
         if _is_step(op):
             stepped.update(on)
             lag[0] = False
+            counted[0] = counted[0] or ("qt" in on and handed[0])
         elif op[0] == "nudge" or op[:2] == ("set_field", "QT"):
             lag[0] = "thermo" not in modes
         return op
 
+    def stat_args():
+        """a drawn subset of statistics.FIELDS (fields the ensemble does not hold among them: they are left out) with at least one
+        it holds, and a drawn subset of statistics.PAIRS; one draw in four asks for everything (None, None): TKE is among it"""
+        if rng.random() < 0.25:
+            return None, None
+        names = subset(st.FIELDS, 4)
+        if not set(names) & set(ALWAYS):
+            names = ("U",) + names
+        if rng.random() < 0.3:
+            names = tuple(k for k in st.FIELDS if k in names or k in ("U", "V"))          # (TKE)
+        return names, (subset(st.PAIRS, 3) if rng.random() < 0.7 else ())
+
     def observation():
         kind = _choose(rng, [("profiles", 3), ("row", 3), ("field", 1.5), ("wp", 3), ("wp_means", 1), ("row_wp", 1), ("cloudfrac", 1),
                              ("flux", 3 if "radiate" in stepped else 0), ("w", 3 if "vertical" in stepped else 0),
-                             ("courant", 2 if "advect" in stepped else 0)])
+                             ("courant", 2 if "advect" in stepped else 0), ("counts", 3 if "qt" in on else 0),
+                             ("lid", 3 if "conservative" in on else 0), ("pressure", 4 if "buoyancy" in on else 0),
+                             ("stats", 5 if "stats" in modes else 0), ("row_stats", 1.5 if "stats" in modes else 0)])
         if kind == "profiles":
             return ("profiles", subset(PROFILE_KEYS, 3))
         if kind == "row":
@@ -202,54 +322,78 @@ def generate(seed, modes, length=LENGTH):
             return ("row_wp", small(), wp_names[int(rng.integers(len(wp_names)))])
         if kind == "cloudfrac":
             return ("cloudfrac", small())
+        if kind in ("stats", "row_stats"):
+            names, pairs = stat_args()
+            wread[0] = wread[0] or ("vertical" in stepped and (names is None or st.FACE in names))
+            return ((kind,) if kind == "stats" else (kind, small())) + (names, pairs)
         return (kind,)
 
     # the head: a step that no read precedes, and two consecutive mutations
     head = int(rng.integers(3))
     if head == 0:
-        ops = [mutation("step"), mutation(room=False)]
+        ops += [mutation("step")]
+        ops += [mutation(room=False)]
     elif head == 1:
-        ops = [mutation(("forcings", "set_field", "presf", "rhobf")[int(rng.integers(4))]), mutation("step")]
+        ops += [mutation(("forcings", "set_field", "presf", "rhobf")[int(rng.integers(4))])]
+        ops += [mutation("step")]
     else:
-        ops = [mutation("enable" if pending else "forcings"), mutation("step")]
+        ops += [mutation("enable" if pending else "forcings")]
+        ops += [mutation("step")]
     while len(ops) < length - 1:
         room = len(ops) < length - 3
-        if pending and length - 1 - len(ops) <= len(pending) + 1:  # a mode that is to be enabled late is, with a step behind it
-            ops.append(mutation("enable"))
+        if todo() and length - 1 - len(ops) <= todo() + 1:         # a mode that is to be enabled late is, with a step behind it
+            ops.append(mutation("enable" if pending else "qt_forcings"))
+        elif hint[0] is not None and rng.random() < 0.7:           # (no mutation of the old modes leaves a hint: no draw there)
+            ops.append(hint[0])
+            wread[0] = wread[0] or (hint[0][0] == "stats" and "vertical" in stepped)
+            hint[0] = None
+        elif dropped[0] and rng.random() < 0.7:
+            ops.append(mutation("step"))
         elif rng.random() < 0.4:
             ops.append(observation())
         else:
             ops.append(mutation(room=room))
-    last = max([i for i, op in enumerate(ops) if op[0] == "enable"], default=-1)
+    last = max([i for i, op in enumerate(ops) if op[0] in ("enable", "qt_forcings")], default=-1)
     if not any(_is_step(op) for op in ops[last + 1:]):
-        ops[-1] = mutation("step")
         assert last < len(ops) - 1
+        ops[-1] = mutation("step")
     ops.append(("record",))
+    assert not pending and todo() == 0
     check_sequence(ops, modes, length)
     return ops
 
 
 def check_sequence(ops, modes, length=None):
-    """the conditions every sequence meets, whoever made it"""
+    """the conditions every sequence meets, whoever made it; returns the modes that are enabled late (an enable of the buoyancy
+    behind a ``readvect`` is the second one)"""
     assert length is None or len(ops) == length, (len(ops), length)
     assert ops[-1] == ("record",) and all(op[0] in KINDS for op in ops)
+    assert all(NEEDS.get(op[0]) is None or NEEDS[op[0]] in modes for op in ops), "an operation of a mode the sequence does not have"
     first = next(i for i, op in enumerate(ops) if _is_step(op))
     assert not any(_reads(op) for op in ops[:first]), "a read precedes every step"
     assert any(a[0] in MUTATIONS and b[0] in MUTATIONS for a, b in zip(ops, ops[1:])), "no two mutations follow each other"
-    late = [op[1] for op in ops if op[0] == "enable"]
+    again = next((i for i, op in enumerate(ops) if op[0] == "readvect"), len(ops))
+    late = [op[1] for i, op in enumerate(ops) if op[0] == "enable" and not (op[1] == "buoyancy" and i > again)]
     assert len(set(late)) == len(late) and set(late) <= set(LATE) & set(modes)
-    last = max([i for i, op in enumerate(ops) if op[0] == "enable"], default=-1)
+    last = max([i for i, op in enumerate(ops) if op[0] in ("enable", "qt_forcings")], default=-1)
     assert any(_is_step(op) for op in ops[last + 1:]), "no step after the last enable"
+    if "qt" in modes and any(op[0] == "qt_forcings" for op in ops):
+        at = next(i for i, op in enumerate(ops) if op[0] == "qt_forcings")
+        assert any(_is_step(op) for op in ops[:at]), "no step before the cloud-water forcing is handed over"
     return late
 
 
-def check_kinds(cases):
-    """over the (seed, modes) of ``cases`` every kind of operation occurs"""
-    seen = {op[0] for seed, modes in cases for op in generate(seed, modes)}
-    assert seen == set(KINDS), sorted(set(KINDS) - seen)
+def check_kinds(cases, length=LENGTH):
+    """over the (seed, modes) of ``cases`` every kind of operation occurs that the modes of the cases allow"""
+    seen = {op[0] for seed, modes in cases for op in generate(seed, modes, length)}
+    want = {k for k in KINDS if NEEDS.get(k) is None or any(NEEDS[k] in modes for seed, modes in cases)}
+    assert seen == want, (sorted(want - seen), sorted(seen - want))
 
 
 # -- one operation -----------------------------------------------------------------------------------------------------------
+NONE = numpy.zeros(0)                                              # what a getter that returns None is recorded as
+
+
 def _all_profiles(ens):
     out = {k: numpy.empty_like(numpy.asarray(ens.p[k], dtype=numpy.float64)) for k in PROFILE_KEYS}
     ens.get_profiles_batched(PROFILE_KEYS, out)
@@ -264,7 +408,48 @@ def _row_equals_batched(ens, i, method, got):
     assert_bits("(a) row %d %s against get_profiles_batched((%r,))" % (i, method, key), got, out[key][i])
 
 
-def apply(ens, op, device, modes, on):
+def _flat(stats):
+    return {"stat " + k: v for k, v in lmo.flat(stats).items()}
+
+
+def _statistics(ens, device, names, pairs):
+    """get_statistics as one dict of host arrays; on the device through get_statistics_batched as well: the same bits"""
+    host = ens.get_statistics(names, pairs)
+    if device:
+        dev = ens.get_statistics_batched(names, pairs)
+        assert sorted(dev) == ["cov", "mean", "std", "var"] and all(list(dev[kind]) == list(host[kind]) for kind in dev)
+        for kind, d in dev.items():
+            for key, t in d.items():
+                assert_bits("get_statistics_batched %s %s against get_statistics" % (kind, key), numpy.asarray(host_of(t), dtype=numpy.float64), host[kind][key])
+    return _flat(host)
+
+
+def _row_statistics(ens, device, i, names, pairs):
+    """a row's get_statistics, the row FIRST; property (a) on the device"""
+    if not device:
+        return _flat(ens.row_statistics(i, names, pairs))
+    got = _flat(ens[i].get_statistics(names, pairs))
+    whole = _flat(ens.get_statistics(names, pairs))
+    assert list(got) == list(whole)
+    for k in got:
+        assert_bits("(a) row %d get_statistics %s against row %d of get_statistics" % (i, k, i), got[k], whole[k][i])
+    return got
+
+
+def _optional(t, dtype=None):
+    return NONE if t is None else numpy.array(host_of(t), dtype=dtype)
+
+
+def _lid(ens):
+    lid = ens.get_lid_flux_batched()
+    return {"lid": NONE} if lid is None else {"lid " + k: numpy.array(host_of(v)) for k, v in lid.items()}
+
+
+def _number(x):
+    return numpy.array([-1.0 if x is None else float(x)])
+
+
+def apply(ens, op, device, modes, on, par=DEFAULT):
     """``op`` on the device ensemble or on the twin; ``on``: the modes enabled now (updated).  Returns None for a mutation, a
     dict name -> host array for an observation"""
     n, kind = ens.n, op[0]
@@ -284,6 +469,16 @@ def apply(ens, op, device, modes, on):
         return ens.set_forcings_batched(THL=rng.normal(0, 2e-4, (n, NL)), QT=rng.normal(0, 2e-7, (n, NL)), U=rng.normal(0, 1e-4, (n, NL)),
                                         V=rng.normal(0, 1e-4, (n, NL)), SP=rng.normal(0, 1e-2, n), WT_surf=ldr.WT * (0.5 + rng.random(n)),
                                         WQ_surf=ldr.WQ * (0.5 + rng.random(n)))
+    if kind == "qt_forcings":                                      # the cloud-water forcing and the reference profile of the coupler
+        rng = numpy.random.default_rng(op[1])
+        return ens.set_forcings_batched(QL=rng.normal(0, 2e-8, (n, NL)), QLp=numpy.asarray(ens.ql_ref) * (0.5 + rng.random((n, NL))))
+    if kind == "qt_kind":
+        ens.enable_qt_forcing(qf.KINDS[1 - qf.KINDS.index(ens.qt_forcing_kind)])
+        return None
+    if kind == "readvect":                                         # enable_advection again: the buoyancy is dropped until it is enabled again
+        enable(ens, "readvect", modes, par=par)
+        on.discard("buoyancy")
+        return None
     if kind == "set_field":
         cur = numpy.array(host_of(ens.get_fields_batched(op[1])))
         noise = numpy.random.default_rng(op[2]).normal(0, 1e-2 if op[1] == "QT" else 1e-4, cur.shape)
@@ -295,8 +490,8 @@ def apply(ens, op, device, modes, on):
         ens.p["Rhobf"] *= 1.01
         return None
     if kind == "enable":
-        enable(ens, op[1], modes, late=True)
-        on.update({op[1]} | ({"vertical"} if op[1] == "advect" and "vertical" in modes else set()))
+        enable(ens, op[1], modes, late=True, par=par)
+        on.update(_comes_with(op[1], modes))
         return None
     if kind == "profiles":
         out = {k: numpy.empty_like(numpy.asarray(ens.p[k], dtype=numpy.float64)) for k in op[1]}
@@ -329,8 +524,20 @@ def apply(ens, op, device, modes, on):
     if kind == "courant":
         rec = {"substeps": numpy.array([float(ens.advect_substeps)]), "courant": numpy.array([ens.advect_courant])}
         if "vertical" in on:
-            rec["courant z"] = numpy.array([ens.advect_courant_z])
+            rec["courant z"] = _number(ens.advect_courant_z)       # (None in the conservative mode)
+        if "buoyancy" in on:
+            rec["wind change"] = _number(ens.buoyancy_wind_change)
         return rec
+    if kind == "counts":
+        return {"counts": _optional(ens.get_qt_forcing_counts_batched(), numpy.float64)}
+    if kind == "lid":
+        return _lid(ens)
+    if kind == "pressure":
+        return {"phi": _optional(ens.get_pressure_batched())}
+    if kind == "stats":
+        return _statistics(ens, device, op[1], op[2])
+    if kind == "row_stats":
+        return _row_statistics(ens, device, op[1] % n, op[2], op[3])
     assert kind == "record", op
     rec = {"got " + k: v for k, v in _all_profiles(ens).items()}
     rec.update({"p " + k: numpy.array(v) for k, v in ens.p.items()})              # (read above: p is that of the fields as they are)
@@ -351,9 +558,20 @@ def apply(ens, op, device, modes, on):
         rec["courant z"] = numpy.array([-1.0 if ens.advect_courant_z is None else ens.advect_courant_z])
         if ens.get_vertical_wind_batched() is not None:
             rec["W"] = numpy.array(host_of(ens.get_vertical_wind_batched()))
+    if "qt" in on:
+        rec["counts"] = _optional(ens.get_qt_forcing_counts_batched(), numpy.float64)
+    if "conservative" in on:
+        rec.update(_lid(ens))
+    if "buoyancy" in on:
+        rec["phi"] = _optional(ens.get_pressure_batched())
+        rec["wind change"] = _number(ens.buoyancy_wind_change)
+    if "stats" in modes:
+        rec.update(_statistics(ens, device, None, None))
     for i in range(n):
         for method in sorted(ROW_GETTERS):
             _row_equals_batched(ens, i, method, numpy.array(getattr(ens[i], method)()))
+        if "stats" in modes and device:
+            _row_statistics(ens, device, i, None, None)
     return rec
 
 
@@ -378,8 +596,12 @@ class Counter:
 
 
 def check_launched(calls, modes):
+    """every enabled mode launched its method; the conservative transport stands in the place of the split pair"""
     for mode in modes:
-        assert METHOD[mode] in calls, "%s was enabled and %s never launched" % (mode, METHOD[mode])
+        if "conservative" in modes and mode in ("advect", "vertical"):
+            assert METHOD[mode] not in calls, "the conservative transport is enabled and %s launched" % METHOD[mode]
+        else:
+            assert METHOD[mode] in calls, "%s was enabled and %s never launched" % (mode, METHOD[mode])
 
 
 # -- a whole sequence ----------------------------------------------------------------------------------------------------------
@@ -392,50 +614,89 @@ def _compare(key, got, want):
         assert_bits(key, got, want)
 
 
-def replay(ops, modes, n, engine_for_twin, engine_for_device, what=""):
+def _holds_w(key):
+    """a statistics entry that W enters: "stat mean W", "stat cov W-THL", "stat cov U-W", ... (TKE: where there is a variance of W)"""
+    return key.startswith("stat ") and st.FACE in key.split(" ")[-1].split("-")
+
+
+def _of_the_own_w(ens, got, want, row=None):
+    """``want`` (the twin's record) with the moments that hold W replaced by the oracle of K20 on the device's own W and its own
+    partner fields, as they are at this operation"""
+    keys = [k for k in got if _holds_w(k)]
+    if not keys:
+        return want
+    pairs = [tuple(k.split(" ")[-1].split("-")) for k in keys if k.startswith("stat cov ")]
+    names = [k for k in st.FIELDS if k == st.FACE or any(k in p for p in pairs)]
+    fields = {k: numpy.asarray(host_of(ens.get_vertical_wind_batched() if k == st.FACE else ens.get_fields_batched(k))) for k in names}
+    own = _flat({kind: {k: numpy.asarray(a, dtype=numpy.float64) for k, a in d.items()} for kind, d in lmo.les_moments(fields, pairs, st.FACE).items()})
+    want = dict(want)
+    for k in keys:
+        want[k] = own[k] if row is None else own[k][row]
+    if "stat TKE" in got and "stat var W" in got:
+        want["stat TKE"] = st.tke({"U": want["stat var U"], "V": want["stat var V"], "W": want["stat var W"]})
+    return want
+
+
+def replay(ops, modes, n, engine_for_twin, engine_for_device, what="", par=DEFAULT):
     """the list ``ops`` on the twin (NumPy fields; its nudge runs on ``engine_for_twin``) and on the device ensemble on
-    ``engine_for_device``; every observation compared, properties (a) and (b) checked on the way.  An AssertionError names
-    ``what``, the modes, the index of the operation and the operations up to it.  Returns the launches of the device side."""
+    ``engine_for_device``; every observation compared, properties (a), (b) and (c) checked on the way.  ``par``: the kind of K19
+    and the limiter of K23 (``params``).  An AssertionError names ``what``, the modes, the index of the operation and the
+    operations up to it.  Returns the launches of the device side."""
     modes = tuple(m for m in MODES if m in modes)
     late = check_sequence(ops, modes)
 
     def told(i, side, e):
-        return AssertionError("%s modes %s n %d, operation %d %r on the %s: %s\nthe operations up to it (ensemble_sequences.replay(ops, %r, %d, ...)):\n%r"
-                              % (what, name_of(modes), n, i, ops[i], side, e, modes, n, list(ops[:i + 1])))
-    twin, on, want = build(engine_for_twin, False, n, modes, late), set(modes) - set(late) - ({"vertical"} if "advect" in late else set()), []
+        return AssertionError("%s modes %s n %d, operation %d %r on the %s: %s\nthe operations up to it (ensemble_sequences.replay(ops, %r, %d, ..., par=%r)):\n%r"
+                              % (what, name_of(modes), n, i, ops[i], side, e, modes, n, par, list(ops[:i + 1])))
+    twin, on, want = build(engine_for_twin, False, n, modes, late, par), _on_at_start(modes, late), []
     for i, op in enumerate(ops):
         try:
-            want.append(apply(twin, op, False, modes, on))
+            want.append(apply(twin, op, False, modes, on, par))
         except AssertionError as e:
             raise told(i, "twin", e) from e
     assert len(want) == len(ops)
     counter = Counter(engine_for_device)
     done = 0
+    cached = set()                                                 # property (c): the statistics read since the last mutation
+    handed = None                                                  # the launches before the first qt_forcings
     try:
-        ens, on = build(engine_for_device, True, n, modes, late), set(modes) - set(late) - ({"vertical"} if "advect" in late else set())
+        ens, on = build(engine_for_device, True, n, modes, late, par), _on_at_start(modes, late)
         for i, op in enumerate(ops):
             try:
-                got = apply(ens, op, True, modes, on)
+                if op[0] == "qt_forcings" and handed is None:
+                    handed = len(counter.calls)
+                mark = len(counter.calls)
+                got = apply(ens, op, True, modes, on, par)
                 assert (got is None) == (want[i] is None) and (got is None or list(got) == list(want[i])), (got and list(got), want[i] and list(want[i]))
-                for k in got or ():
-                    _compare(k, got[k], want[i][k])
-                if got is not None:                                # property (b)
-                    mark = len(counter.calls)
-                    again = apply(ens, op, True, modes, on)
+                if got is not None:
+                    stats = {k for k in got if k.startswith("stat ") and k != "stat TKE"}
+                    if stats and stats <= cached:                  # property (c)
+                        assert "les_moments" not in counter.calls[mark:], "(c) K20 launched for statistics that were cached: %s" % sorted(stats)
+                    cached |= stats
+                    ref = _of_the_own_w(ens, got, want[i], row=op[1] % n if op[0] == "row_stats" else None)
+                    for k in got:
+                        _compare(k, got[k], ref[k])
+                    mark = len(counter.calls)                      # property (b)
+                    again = apply(ens, op, True, modes, on, par)
                     extra = set(counter.calls[mark:]) - RELAUNCH.get(op[0], set())
                     assert not extra, "(b) the second read launched %s" % sorted(extra)
                     for k in got:
                         assert_bits("(b) the second read of " + k, again[k], got[k])
+                elif op[0] == "rhobf":
+                    cached = {k for k in cached if not _holds_w(k)}
+                else:
+                    cached = set()
             except AssertionError as e:
                 raise told(i, "device ensemble", e) from e
             done += 1
     finally:
         counter.restore()
     assert done == len(ops) and ens.model_time == twin.model_time
-    check_launched(counter.calls, modes)
+    assert "les_qt_local" not in counter.calls[:handed], "K19 launched before the cloud-water forcing was handed over"
+    check_launched(counter.calls, [m for m in modes if m != "qt" or handed is not None])
     return counter.calls
 
 
 def run(engine_for_twin, engine_for_device, seed, modes, n, length=LENGTH):
     """``generate(seed, modes)`` through ``replay``"""
-    return replay(generate(seed, modes, length), modes, n, engine_for_twin, engine_for_device, what="seed %d" % seed)
+    return replay(generate(seed, modes, length), modes, n, engine_for_twin, engine_for_device, what="seed %d" % seed, par=params(seed, modes))

@@ -2,8 +2,11 @@
 tests/ensemble_sequences.py; the conditions, the properties (a) and (b) and the list of state mutants are in its docstring and
 in tests/test_ensemble_sequences_cpu.py).  The device ensemble runs on Engine("cuda:0") in float64 at n = 3, 4 x 5 x 20; the
 twin computes in NumPy on the host (its variability nudge alone goes through an engine).  Everything is bit-equality
-(gpu_util.assert_bits), W alone keeps the bound of les_vadvect_ref.check_w: there is no tolerance to choose and nothing is
-measured.  Every case runs two seeds; nothing but the ensemble is mutated."""
+(gpu_util.assert_bits), W alone keeps the bound of les_vadvect_ref.check_w, and the moments that hold W are compared bit for
+bit with NumPy's moments of the device's own W: there is no tolerance to choose and nothing is measured.  Every case runs two
+seeds; nothing but the ensemble is mutated.  Twelve cases of the six old modes and twelve with the five new ones (K19 to K23 and
+the statistics of K20); four of each through two and three engines that share the card and behind the fused step.  4 x 5 x 20 at
+n = 3 is the smallest shape at which every cache and launch switch of the ensemble is still reached."""
 import numpy
 import pytest
 import torch
@@ -18,9 +21,15 @@ pytestmark = pytest.mark.gpu
 SEEDS = (1, 3)                                                    # (over these every kind of operation occurs in the twelve cases: asserted)
 #: all six modes, each mode alone (the vertical advection with the horizontal it needs), the pairs and triples that share a
 #: cache (K12's temperature for K14, the spare buffers of K16 / K17 in front of K15, QL for K18 and K14), and two mixes
-TWELVE = [es.MODES, ("thermo",), ("diffuse",), ("micro",), ("advect",), ("advect", "vertical"), ("radiate",), ("thermo", "micro"),
+TWELVE = [es.OLD_MODES, ("thermo",), ("diffuse",), ("micro",), ("advect",), ("advect", "vertical"), ("radiate",), ("thermo", "micro"),
           ("diffuse", "advect", "vertical"), ("micro", "radiate"), ("thermo", "diffuse", "advect", "radiate"), ("thermo", "micro", "advect", "vertical")]
-FOUR = [es.MODES, ("thermo", "micro"), ("diffuse", "advect", "vertical"), ("micro", "radiate")]
+FOUR = [es.OLD_MODES, ("thermo", "micro"), ("diffuse", "advect", "vertical"), ("micro", "radiate")]
+AV = ("advect", "vertical")
+#: each new mode alone over its smallest valid background, the pairs that share state (K19's QT under K22, K21 in front of K23, W
+#: and its moments, K19 dropping K20's cache), K12 on both sides of K19, K19 and K21 under the statistics, and everything at once
+NEW_TWELVE = [("qt",), AV + ("buoyancy",), AV + ("conservative",), AV + ("conservative", "order2"), ("stats",), AV + ("qt", "conservative"),
+              AV + ("buoyancy", "conservative", "order2"), AV + ("stats",), ("qt", "stats"), ("thermo", "qt"), AV + ("qt", "buoyancy", "stats"), es.MODES]
+NEW_FOUR = [es.MODES, AV + ("qt", "conservative"), AV + ("buoyancy", "conservative", "order2"), ("qt", "stats")]
 
 
 @pytest.fixture(autouse=True)
@@ -39,6 +48,13 @@ def test_the_cases_are_valid_combinations():
     valid = es.combinations()
     assert len(TWELVE) == len(set(TWELVE)) == 12 and all(c in valid for c in TWELVE + FOUR)
     es.check_kinds([(seed, modes) for modes in TWELVE for seed in SEEDS])
+    assert len(NEW_TWELVE) == len(set(NEW_TWELVE)) == 12 and all(es.valid(c) and c == tuple(m for m in es.MODES if m in c) and c not in valid
+                                                                  for c in NEW_TWELVE)
+    assert all(c in NEW_TWELVE for c in NEW_FOUR) and len(set(NEW_FOUR)) == 4
+    es.check_kinds([(seed, modes) for modes in NEW_TWELVE for seed in SEEDS])
+    par = [(modes, es.params(seed, modes)) for modes in NEW_TWELVE for seed in SEEDS]
+    assert {p["kind"] for modes, p in par if "qt" in modes} == {"local", "strong"}
+    assert {p["limiter"] for modes, p in par if "order2" in modes} == {"mc", "none"}
 
 
 @pytest.mark.parametrize("modes", TWELVE, ids=es.name_of)
@@ -64,6 +80,34 @@ def test_three_engines_sharing_the_card_one_without_rows(modes):
 @pytest.mark.parametrize("modes", FOUR, ids=es.name_of)
 def test_fused_step_then_every_later_stage(monkeypatch, modes):
     """FUSED_MIN_LES patched to 0: K11 steps the fields, whatever is enabled follows"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    for seed in SEEDS:
+        assert "les_advance" in es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", NEW_TWELVE, ids=es.name_of)
+def test_sequences_of_the_new_modes_equal_the_twin(modes):
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", NEW_FOUR, ids=es.name_of)
+def test_new_modes_on_two_engines_sharing_the_card(modes):
+    """n = 5: Sharded row blocks 3 + 2, each engine on its own stream"""
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), _sharing(2), seed, modes, 5)
+
+
+@pytest.mark.parametrize("modes", NEW_FOUR, ids=es.name_of)
+def test_new_modes_on_three_engines_sharing_the_card_one_without_rows(modes):
+    """n = 2: row blocks 1 + 1 + 0"""
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), _sharing(3), seed, modes, 2)
+
+
+@pytest.mark.parametrize("modes", NEW_FOUR, ids=es.name_of)
+def test_new_modes_behind_the_fused_step(monkeypatch, modes):
+    """FUSED_MIN_LES patched to 0: K11 steps the fields and K19 reads its cached means"""
     monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
     for seed in SEEDS:
         assert "les_advance" in es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
