@@ -37,6 +37,9 @@
  *   spc_les_buoyancy_*   <- the hydrostatic pressure force of that ensemble (nothing of it is in the reference): the buoyancy
  *                           of every column integrated downward to a pressure perturbation, whose horizontal gradient
  *                           accelerates U and V in place, in two launches (kernel family K21)
+ *   spc_les_mix_*        <- the Smagorinsky-Lilly subgrid closure of that ensemble (nothing of it is in the reference): an eddy
+ *                           viscosity per cell from the resolved deformation and the stratification, and the horizontal
+ *                           mixing of the carried fields by it in flux form, in two launches (kernel family K24)
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -991,6 +994,79 @@ int spc_les_buoyancy_f64(const spc_les_buoyancy_args *args, void *stream);
 int spc_les_buoyancy_f32(const spc_les_buoyancy_args *args, void *stream);
 /* columns per workgroup of k_les_hydrostatic for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
 int spc_les_buoyancy_cols_per_block(int ktot, int elem_size);
+
+/* ---- Smagorinsky-Lilly subgrid mixing of the device-resident LES fields (kernel family K24) ----------------------------------- */
+/* An eddy viscosity per cell from the resolved deformation and the stratification, and one explicit step in flux form of the
+ * horizontal mixing of the carried fields by that viscosity.  Two launches behind one entry point.  The rule is this library's
+ * definition.
+ * General conventions:
+ *   - Fields are [n_les][itot][jtot][ktot], k contiguous, with 64-bit offsets as in K10.  The element type T is f64 or f32.
+ *   - Every operation is rounded once in T.  Nothing contracts to an fma.
+ *   - There is no division and no transcendental function; there is one correctly rounded sqrt per cell, as K20's std.
+ *   - So every output is asked for bit for bit in both types, whatever the launch shape.
+ * Neighbours:
+ *   - im, ip, jm, jp are K16's periodic neighbours: an extent of 1 is the cell itself, an extent of 2 has both neighbours the
+ *     same cell.
+ *   - kp = k + 1 < ktot ? k + 1 : k and kq = k > 0 ? k - 1 : k.  The index is clamped before the load.
+ * Per-LES values and profiles (formed in float64 by sp_coupler_amd/mixing.py and rounded to T once):
+ *   - gx = 0.5 / dx, gy = 0.5 / dy and kcap [n_les]; gz = 1 / (zf[kp] - zf[kq]), bz = grav / (prandtl theta_ref) * gz and
+ *     l2 (the squared mixing length, > 0 and finite: the caller's duty) [n_les x ktot], rows pitch_prof apart.
+ *   - ax[f], ay[f] [n_les]: 0.5 dt / dx^2 and 0.5 dt / dy^2 for a wind, the same divided by the Prandtl number for a scalar:
+ *     one pointer per field, so that the kernel needs no extra rounding; fields may share a pointer.
+ * Launch 1, k_les_eddy, per cell (l, i, j, k):
+ *   ux = (u[ip] - u[im]) * gx[l];        vx = (v[ip] - v[im]) * gx[l]
+ *   uy = (u[jp] - u[jm]) * gy[l];        vy = (v[jp] - v[jm]) * gy[l]
+ *   uz = (u[kp] - u[kq]) * gz[l][k];     vz = (v[kp] - v[kq]) * gz[l][k]
+ *   a  = ux * ux + vy * vy;   sh = uy + vx
+ *   d  = (a + a) + sh * sh;   d = d + (uz * uz + vz * vz)
+ *   d  = d - (theta[kp] - theta[kq]) * bz[l][k]          only where theta != NULL
+ *   e  = d > 0 ? d : +0                                   a NaN gives +0
+ *   kk = l2[l][k] * sqrt(e)
+ *   kmax[l] = the maximum of kk over the cells of LES l   optional; K16's atomicMax on the bit pattern, zeroed by the launch
+ *   km = kk < kcap[l] ? kk : kcap[l]                      written whole; required: the workspace between the launches AND a
+ *                                                         diagnostic
+ * The gradients of W are left out: W is diagnosed from continuity under the hydrostatic closure of K21.
+ * Launch 2, k_les_hmix, per cell and per field f with x = fields[f]:
+ *   kw = km[im] + km;  ke = km + km[ip];  ks = km[jm] + km;  kn = km + km[jp]
+ *   fw = (kw * ax[f][l]) * (x - x[im]);   fe = (ke * ax[f][l]) * (x[ip] - x)
+ *   fs = (ks * ay[f][l]) * (x - x[jm]);   fn = (kn * ay[f][l]) * (x[jp] - x)
+ *   out[f] = x + ((fe - fw) + (fn - fs))
+ * n_fields == 0 runs launch 1 only (the probe / the diagnostic).
+ * Consequences:
+ *   - km is never negative, never NaN and at most kcap[l], given l2 > 0 finite.  A NaN in u, v or theta makes km = +0 in the
+ *     cells whose stencil reads it and touches nothing else.  A NaN in a field reaches that cell and its four neighbours.
+ *   - Both cells of a face form its flux from the same operands: fe of a cell equals fw of its ip neighbour bit for bit, fn of
+ *     a cell fs of its jp neighbour.  The plane sum of every field is conserved to rounding.
+ *   - A constant finite field keeps its bits; a -0.0 constant comes out +0.0, as in K16.
+ *   - Winds that are uniform on every level (and without shear from level to level) under a stable or neutral theta give
+ *     km = +0 everywhere, and every field keeps its bits.
+ *   - With (kw + ke) ax + (ks + kn) ay <= 1, which kcap = CAP / (4 max(ax + ay)), CAP <= 1, guarantees, out is a convex
+ *     combination of the cell and its four neighbours.
+ *   - These are SPC_ERR_INVALID_ARGUMENT: pitch_prof < ktot; a NULL u, v, gx, gy, kcap, gz, l2, km, or a NULL fields[f],
+ *     out[f], ax[f], ay[f] of f < n_fields; theta without bz; km, kmax or an out[f] equal to an input or to each other;
+ *     n_fields outside 0 ... SPC_MIX_MAX_FIELDS.
+ *   - Arrays that overlap only in part are not detected and must not be passed.  n_les == 0 is a no-op.  ktot == 1 is allowed
+ *     (gz = bz = 0).
+ * Both kernels: a workgroup owns spc_les_advect_strip(...) cells of the run [jtot][ktot] of a row i and
+ * spc_les_advect_rows(...) rows.                                                                                          */
+#define SPC_MIX_MAX_FIELDS 6
+typedef struct spc_les_mix_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_fields; /* n_fields 0 ... SPC_MIX_MAX_FIELDS                                 */
+    const void *u, *v;                  /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *theta;                  /* device [n_les][itot][jtot][ktot], read only, or NULL              */
+    const void *gx, *gy, *kcap;         /* device [n_les]                                                    */
+    const void *gz, *bz, *l2;           /* device [n_les x ktot] each, rows pitch_prof apart; bz NULL only without theta */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+    void *km;                           /* device [n_les][itot][jtot][ktot], written whole                   */
+    void *kmax;                         /* device [n_les], or NULL                                           */
+    const void *fields[SPC_MIX_MAX_FIELDS]; /* device [n_les][itot][jtot][ktot], read only                   */
+    void *out[SPC_MIX_MAX_FIELDS];      /* device [n_les][itot][jtot][ktot], written whole                   */
+    const void *ax[SPC_MIX_MAX_FIELDS]; /* device [n_les] per field                                          */
+    const void *ay[SPC_MIX_MAX_FIELDS]; /* device [n_les] per field                                          */
+} spc_les_mix_args;
+int spc_les_mix_f64(const spc_les_mix_args *args, void *stream);
+int spc_les_mix_f32(const spc_les_mix_args *args, void *stream);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

@@ -199,6 +199,16 @@ class LesBuoyancyArgs(ctypes.Structure):
                 + _ptrs("phi", "psfc", "amax"))
 
 
+SPC_MIX_MAX_FIELDS = 6
+
+
+class LesMixArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32)]
+                + _ptrs("u", "v", "theta", "gx", "gy", "kcap", "gz", "bz", "l2") + [("pitch_prof", c_int64)] + _ptrs("km", "kmax")
+                + [("fields", c_void_p * SPC_MIX_MAX_FIELDS), ("out", c_void_p * SPC_MIX_MAX_FIELDS),
+                   ("ax", c_void_p * SPC_MIX_MAX_FIELDS), ("ay", c_void_p * SPC_MIX_MAX_FIELDS)])
+
+
 class LesQtLocalArgs(ctypes.Structure):
     _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("split", c_int32)]
                 + _ptrs("qt", "ql", "a", "qtm") + [("pitch_prof", c_int64), ("count", c_void_p), ("pitch_count", c_int64)])
@@ -291,6 +301,8 @@ PROTOTYPES = {
     "spc_les_buoyancy_f64": (ctypes.c_int, [ctypes.POINTER(LesBuoyancyArgs), c_void_p]),
     "spc_les_buoyancy_f32": (ctypes.c_int, [ctypes.POINTER(LesBuoyancyArgs), c_void_p]),
     "spc_les_buoyancy_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "spc_les_mix_f64": (ctypes.c_int, [ctypes.POINTER(LesMixArgs), c_void_p]),
+    "spc_les_mix_f32": (ctypes.c_int, [ctypes.POINTER(LesMixArgs), c_void_p]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

@@ -50,6 +50,10 @@
 //   K23 k_les_transport2  K22's step with a second-order face value: every face adds to K22's donor flux a correction from the
 //                  (MC-limited or unlimited) slope of its upwind cell, centred in time; 13 values per cell and field for 7, the
 //                  same shared faces and lid budget: spc_transport2.hpp, kernel and host side
+//   K24 k_les_eddy, k_les_hmix  the Smagorinsky-Lilly subgrid closure: an eddy viscosity per cell from the resolved deformation
+//                  and the stratification (one sqrt per cell), and the horizontal mixing of the carried fields by it in flux
+//                  form (K16's shape and neighbours, every face flux formed alike by its two cells): spc_mix.hpp, kernels and
+//                  host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -112,6 +116,7 @@ namespace {
 #include "spc_qtlocal.hpp"
 #include "spc_moments.hpp"
 #include "spc_buoyancy.hpp"
+#include "spc_mix.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -161,6 +166,9 @@ namespace {
 #define SPC_BUOYANCY_HOST
 #include "spc_buoyancy.hpp"
 #undef SPC_BUOYANCY_HOST
+#define SPC_MIX_HOST
+#include "spc_mix.hpp"
+#undef SPC_MIX_HOST
 
 }  // namespace
 
@@ -267,6 +275,9 @@ int spc_les_qt_local_split(int64_t n_les, int itot, int jtot, int ktot, int elem
 int spc_les_buoyancy_f64(const spc_les_buoyancy_args *a, void *s) { return les_buoyancy_impl<double>(a, s); }
 int spc_les_buoyancy_f32(const spc_les_buoyancy_args *a, void *s) { return les_buoyancy_impl<float>(a, s); }
 int spc_les_buoyancy_cols_per_block(int ktot, int elem_size) { return hyd_cols(ktot, elem_size); }
+
+int spc_les_mix_f64(const spc_les_mix_args *a, void *s) { return les_mix_impl<double>(a, s); }
+int spc_les_mix_f32(const spc_les_mix_args *a, void *s) { return les_mix_impl<float>(a, s); }
 
 int spc_les_moments_f64(const spc_les_moments_args *a, void *s) { return les_moments_impl<double>(a, s); }
 int spc_les_moments_f32(const spc_les_moments_args *a, void *s) { return les_moments_impl<float>(a, s); }

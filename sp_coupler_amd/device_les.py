@@ -9,6 +9,7 @@ from . import advection as adv
 from . import buoyancy as buo
 from . import diffusion as df
 from . import microphysics as mp
+from . import mixing as mix
 from . import radiation as rad
 from . import thermo as th
 from .models import SyntheticLESEnsemble, _LESRow, _row_getter, _timed
@@ -134,6 +135,9 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     After ``enable_buoyancy()`` every advective substep starts with the hydrostatic pressure force on U and V (K21,
     ``Engine.les_buoyancy``) and ``get_pressure_batched()`` returns the pressure perturbation; tests/les_buoyancy_ref.py holds
     the twin of that mode.
+    After ``enable_mixing()`` every step mixes U, V, THL, QT and QR along i and j by the Smagorinsky-Lilly eddy viscosity of the
+    flow (K24, ``Engine.les_mix``), after the advection and before K15, whose diffusivity it can supply (``vertical=True``);
+    ``get_eddy_viscosity_batched()`` returns the viscosity; tests/les_mix_ref.py holds the twin of that mode.
     ``get_statistics_batched`` reduces the fields to their second moments per level (K20, ``Engine.les_moments``): means,
     variances, standard deviations and the covariances of ``statistics.PAIRS``; tests/les_moments_ref.py holds their twin."""
 
@@ -296,8 +300,11 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             return
         # everything the coefficients are made of; the host arrays are copied and compared every step (kilobytes)
         key = (float(dt), par["k_max"], par["h_mix"], par["k_bg"]) + _f64(p["Rhobf"], self.zh_cache, self.zf_cache)
+        kd = self._mix_kd if self.mixing and self.mix_par["vertical"] else None      # K24's slab-mean viscosity at the faces
+        if kd is not None:
+            key += (kd,)
         self._diffuse_prof = _kept(self._diffuse_prof, key, lambda: (
-            key, [self._upload(a) for a in df.profiles(key[5], key[6], key[4], dt, par["k_max"], par["h_mix"], par["k_bg"])]))
+            key, [self._upload(a) for a in df.profiles(key[5], key[6], key[4], dt, par["k_max"], par["h_mix"], par["k_bg"], kd=kd)]))
         a, m, cp, s0 = self._diffuse_prof[1]
         flux = {k: self._upload(numpy.asarray(self.tend[slot], dtype=numpy.float64).reshape(self.n))
                 for k, slot in self.DIFFUSE_FLUX.items() if k in keys and slot in self.tend}
@@ -628,6 +635,107 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         perturbation phi in m2/s2 that K21 found in the last substep of the last step; None before the first step of
         enable_buoyancy()"""
         return self._buoyancy_phi if self.buoyancy else None
+
+    # -- Smagorinsky-Lilly subgrid mixing (K24), opt-in ---------------------------------------------------------------------------
+    mixing = False                                     # enable_mixing(): an eddy viscosity of the flow mixes the fields along i and j
+    mix_par = None                                     # cs, prandtl, cap, theta_ref, stability, vertical, dx, dy
+    MIX_KEYS = ("U", "V", "THL", "QT", "QR")           # fields a step mixes, where they exist
+    MIX_WINDS = ("U", "V")                             # ... with the winds' coefficients; the others take the scalars'
+    mixing_k_max = None                                # the largest uncapped viscosity of the last step, m2/s
+    mixing_capped = None                               # ... lies above the smallest cap: the cap bound somewhere
+    _mix_prof = None                                   # ((cs, prandtl, theta_ref, dx, dy, zf, zh) of the upload, device (gz, bz, l2))
+    _mix_coef = None                                   # ((dt, prandtl, cap, dx, dy) of the upload, device gx, gy, kcap, winds' and scalars' (ax, ay), min kcap)
+    _mix_km = None                                     # the eddy viscosity of the last step, device
+    _mix_spare = None                                  # name -> the buffer K24 writes next (it reads the field)
+    _mix_kd = None                                     # vertical=True: host [n x nL], K15's face diffusivity of this step
+
+    def enable_mixing(self, cs=None, prandtl=None, cap=None, theta_ref=None, stability=True, dx=None, dy=None, vertical=False):
+        """from now on every ``evolve_model_batched`` runs ONE ``Engine.les_mix`` per device (K24, DESIGN.md 7.3: two launches)
+        after K16 / K17 / K22 / K23 and before K15: the Smagorinsky-Lilly eddy viscosity km of the winds U and V and, with
+        ``stability=True``, of theta = THL (the moist correction of the stability is left out), capped at
+        ``mixing.cap`` so that a mixed value is a convex combination of a cell and its four neighbours, mixes the fields among
+        U and V (the winds' coefficients) and THL, QT and QR (the scalars': the winds' divided by ``prandtl``) that exist along
+        i and j in flux form, into scratch buffers that are swapped in.  The profiles then are K10's means of the mixed fields
+        and QL follows the new QT.  ``dx`` and ``dy`` default to those of ``enable_advection()`` where it was called, else to
+        ``advection.DX`` / ``DY``; ``cs``, ``prandtl``, ``cap`` and ``theta_ref`` to those of ``mixing``.  The profiles gz, bz
+        and l2 are uploaded once, and again only where the grid, dx, dy or a parameter changed; the coefficients again where dt
+        changed.  ``get_eddy_viscosity_batched()`` returns km, ``mixing_k_max`` holds the largest uncapped viscosity of the
+        step and ``mixing_capped`` whether it lies above the smallest cap (no substeps: where the cap binds, the mixing is
+        weaker than the closure asks for).  ``vertical=True`` (after ``enable_diffusion()``; ValueError otherwise) makes K15's
+        face diffusivity of the step k_bg + 0.5 (m[k-1] + m[k]) with m the slab mean of km (one K10 launch more), in place of
+        the profile of ``diffusion.diffusivity``.  Needs U and V fields.  Without this call every path, launch and bit of the
+        ensemble is unchanged."""
+        if "U" not in self.fields3d or "V" not in self.fields3d:
+            raise ValueError("the mixing (K24) needs the fields U and V (set_fields_batched)")
+        if not self._has("les_mix"):
+            raise ValueError("the engine has no les_mix (K24)")
+        if vertical and not self.diffusion:
+            raise ValueError("the mixing (K24) with vertical=True hands its viscosity to K15: it needs enable_diffusion()")
+        if dx is None:
+            dx = self.dx if self.advection else adv.DX
+        if dy is None:
+            dy = self.dy if self.advection else adv.DY
+        par = {"cs": mix.CS if cs is None else float(cs), "prandtl": mix.PRANDTL if prandtl is None else float(prandtl),
+               "cap": mix.CAP if cap is None else float(cap), "theta_ref": mix.THETA_REF if theta_ref is None else float(theta_ref),
+               "stability": bool(stability), "vertical": bool(vertical),
+               "dx": numpy.array(dx, dtype=numpy.float64) if numpy.ndim(dx) else float(dx),
+               "dy": numpy.array(dy, dtype=numpy.float64) if numpy.ndim(dy) else float(dy)}
+        _, _, wind, scalar = mix.coefficients(1.0, par["dx"], par["dy"], par["prandtl"], n=self.n)       # (ValueError for what is not positive, or not [n])
+        mix.cap(wind, scalar, par["cap"])
+        mix.profiles(self.zf_cache, self.zh_cache, par["dx"], par["dy"], par["cs"], par["prandtl"], par["theta_ref"], n=self.n)
+        self.mixing, self.mix_par = True, par
+        self.mixing_k_max = self.mixing_capped = None
+        self._mix_prof = self._mix_coef = self._mix_km = self._mix_kd = None
+        self._mix_spare = {}
+
+    def _mix(self, dt):
+        """K24 on the stepped (and advected) fields; QL (without thermo) and the profiles are then those of the mixed fields,
+        unless K15 follows and does both"""
+        eng, f, par = self._eng(), self.fields3d, self.mix_par
+        if self.n == 0:
+            return
+        if "U" not in f or "V" not in f:
+            raise ValueError("the mixing (K24) needs the fields U and V (set_fields_batched)")
+        keys = [k for k in self.MIX_KEYS if k in f]
+        # everything the profiles and the coefficients are made of; the host arrays are copied and compared every step (kilobytes)
+        key = (par["cs"], par["prandtl"], par["theta_ref"]) + _f64(par["dx"], par["dy"], self.zf_cache, self.zh_cache)
+        self._mix_prof = _kept(self._mix_prof, key, lambda: (key, tuple(self._upload(a) for a in mix.profiles(
+            key[5], key[6], key[3], key[4], par["cs"], par["prandtl"], par["theta_ref"], n=self.n))))
+        ckey = (float(dt), par["prandtl"], par["cap"]) + _f64(par["dx"], par["dy"])
+
+        def coefficients():
+            gx, gy, wind, scalar = mix.coefficients(dt, ckey[3], ckey[4], par["prandtl"], n=self.n)
+            kcap = self._upload(mix.cap(wind, scalar, par["cap"]))
+            up = lambda pair: tuple(self._upload(a) for a in pair)                            # noqa: E731
+            return ckey, self._upload(gx), self._upload(gy), kcap, up(wind), up(scalar), float(self._host(kcap).min())
+        self._mix_coef = _kept(self._mix_coef, ckey, coefficients)
+        _, gx, gy, kcap, wind, scalar, lowest = self._mix_coef
+        gz, bz, l2 = self._mix_prof[1]
+        theta = f["THL"] if par["stability"] and "THL" in f else None
+        spare = self._mix_spare
+        for k in keys:
+            spare[k] = self._scratch(spare.get(k), f[k], f[k])
+        self._mix_km = self._scratch(self._mix_km, f["U"])
+        coef = {k: wind if k in self.MIX_WINDS else scalar for k in keys}
+        top = eng.les_mix({k: f[k] for k in keys}, {k: spare[k] for k in keys}, f["U"], f["V"], theta, gx, gy, gz, bz if theta is not None else None,
+                          l2, kcap, self._mix_km, {k: coef[k][0] for k in keys}, {k: coef[k][1] for k in keys})
+        for k in keys:
+            f[k], spare[k] = spare[k], f[k]
+        self.mixing_k_max = self._device_max(top)
+        self.mixing_capped = self.mixing_k_max > lowest
+        if par["vertical"]:
+            m = self._to_host(eng.slab_means({"km": self._mix_km}))["km"]
+            self._mix_kd = mix.face_diffusivity(m, self.diffuse_par["k_bg"])
+        self._drop_water_paths()
+        self._drop_statistics()
+        self._thermo_stale = True                         # thermo: K12 runs on the mixed THL and QT before their next use
+        if not self.diffusion:                            # (else the QL field and the means follow the diffused fields: _diffuse)
+            self._follow_fields()
+
+    def get_eddy_viscosity_batched(self):
+        """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the capped eddy viscosity
+        km in m2/s that K24 found in the last step; None before the first step of enable_mixing()"""
+        return self._mix_km if self.mixing else None
 
     # -- longwave cooling and warming by the liquid water (K18), opt-in ---------------------------------------------------------
     radiation = False                                  # enable_radiation(): the cloud water acts on THL
@@ -1115,6 +1223,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         if self.advection:
             self._advect(dt)                              # 1 + n_sub K16 launches: U, V, THL, QT, QR carried along i and j; p[...]
                                                           # (vertical: a K17 probe and a K17 launch behind every K16 substep)
+        if self.mixing:
+            self._mix(dt)                                 # one K24 call, two launches: km of the flow; U, V, THL, QT, QR mixed along i and j; p[...]
         if self.diffusion:
             self._diffuse(dt)                             # one K15 launch: U, V, THL, QT mixed along k, the surface fluxes; p[...]
         if self.radiation:

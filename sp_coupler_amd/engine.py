@@ -1180,6 +1180,54 @@ class Engine:
         0: unsupported"""
         return self._geometry("buoyancy_cols_per_block", ktot)
 
+    # -- K24: the Smagorinsky-Lilly subgrid mixing of device-resident LES fields, two launches --------------------------------------
+    @_on_engine_stream
+    def les_mix(self, fields, out, u, v, theta, gx, gy, gz, bz, l2, kcap, km, ax, ay, kmax=True, stream=None):
+        """The Smagorinsky-Lilly closure (include/spc.h has the rule) on contiguous device fields [n x itot x jtot x ktot]: the
+        eddy viscosity of the winds ``u`` and ``v`` and of ``theta`` (read only; ``theta`` may be None: no stratification
+        term, ``bz`` may then be None too) is written whole into ``km``, and every tensor of ``fields`` (dict name -> tensor, at
+        most ``_abi.SPC_MIX_MAX_FIELDS`` of one shape, read only; a field may be ``u``, ``v`` or ``theta`` itself) is mixed
+        along i and j by it into the tensors of ``out`` (the same names, written whole).  ``gx``, ``gy`` and ``kcap`` [n] and
+        ``gz``, ``bz`` and ``l2`` [n x ktot] are ``mixing.coefficients`` / ``cap`` / ``profiles`` in the engine's dtype (rows may be
+        pitched, all with one pitch); ``ax`` and ``ay`` are dicts name -> [n] with the names of ``fields`` (fields may share a
+        tensor).  ``kmax``: True (a fresh [n] tensor), a tensor [n] to write into, or False / None; returned: the largest
+        uncapped viscosity of every LES, or None.  ``fields`` may be empty: the probe / the diagnostic, one launch.  A written
+        tensor that STARTS where an input or another written tensor starts is refused (ValueError); views that overlap in part
+        are not detected.  Two launches."""
+        names = list(fields)
+        if len(names) > _abi.SPC_MIX_MAX_FIELDS:
+            raise ValueError("les_mix takes at most %d fields per launch, got %d" % (_abi.SPC_MIX_MAX_FIELDS, len(names)))
+        for what, d in (("out", out), ("ax", ax), ("ay", ay)):
+            if sorted(d) != sorted(names):
+                raise ValueError("les_mix: %s holds %s, the fields are %s" % (what, sorted(d), sorted(names)))
+        if theta is not None and bz is None:
+            raise ValueError("les_mix: theta without bz")
+        shape = n, itot, jtot, ktot = self._extents("les_mix", "u", u)
+        ck = _Checker(self.device, self.dtype)
+        a = _abi.LesMixArgs()
+        a.n_les, a.itot, a.jtot, a.ktot, a.n_fields = n, itot, jtot, ktot, len(names)
+        a.u, a.v = u.data_ptr(), self._field4("v", v, shape).data_ptr()
+        if theta is not None:
+            a.theta = self._field4("theta", theta, shape).data_ptr()
+        a.gx, a.gy, a.kcap = ck.vec("gx", gx, n), ck.vec("gy", gy, n), ck.vec("kcap", kcap, n)
+        a.gz, a.pitch_prof = ck.mat("gz", gz, n, ktot)
+        if bz is not None:
+            a.bz, _ = ck.mat("bz", bz, n, ktot, pitch=a.pitch_prof)
+        a.l2, _ = ck.mat("l2", l2, n, ktot, pitch=a.pitch_prof)
+        a.km = self._field4("km", km, shape).data_ptr()
+        res = self._largest(ck, "kmax", kmax, n)
+        if res is not None:
+            a.kmax = res.data_ptr()
+        for f, k in enumerate(names):
+            a.fields[f] = self._field4(k, fields[k], shape).data_ptr()
+            a.out[f] = self._field4("out[%s]" % k, out[k], shape).data_ptr()
+            a.ax[f], a.ay[f] = ck.vec("ax[%s]" % k, ax[k], n), ck.vec("ay[%s]" % k, ay[k], n)
+        self._no_alias("les_mix: km, kmax or an output is an input or another of them", [km, res] + [out[k] for k in names],
+                       [u, v, theta, gx, gy, kcap, gz, bz if theta is not None else None, l2] + [fields[k] for k in names]
+                       + [ax[k] for k in names] + [ay[k] for k in names], n)
+        self._call(self._sym("les_mix"), ctypes.byref(a), stream=stream)
+        return res
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

@@ -330,6 +330,13 @@ class MultiDeviceEngine:
         none on the others"""
         return self._largest("les_buoyancy", "amax", thl, (thl, qt, ql, u, v, hx, hy, t0, lex, s, phi), dict(kw, psfc=psfc, amax=amax))
 
+    def les_mix(self, fields, out, u, v, theta, gx, gy, gz, bz, l2, kcap, km, ax, ay, kmax=True, **kw):
+        """K24 on every device's LES: dicts of Sharded fields and outputs (written block by block), the Sharded winds, ``theta``
+        (or None), ``gx``, ``gy``, ``kcap`` [n], the Sharded profiles ``gz``, ``bz`` (or None) and ``l2`` [n x ktot], ``km`` and the
+        dicts ``ax`` and ``ay`` of Sharded [n] in; the Sharded [n] largest uncapped viscosities out (None without ``kmax``); two
+        launches per device that holds rows, none on the others"""
+        return self._largest("les_mix", "kmax", u, (fields, out, u, v, theta, gx, gy, gz, bz, l2, kcap, km, ax, ay), dict(kw, kmax=kmax))
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)
