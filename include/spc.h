@@ -40,6 +40,9 @@
  *   spc_les_mix_*        <- the Smagorinsky-Lilly subgrid closure of that ensemble (nothing of it is in the reference): an eddy
  *                           viscosity per cell from the resolved deformation and the stratification, and the horizontal
  *                           mixing of the carried fields by it in flux form, in two launches (kernel family K24)
+ *   spc_les_vmix_*       <- the implicit vertical mixing of that ensemble by each column's own eddy viscosity (nothing of it is
+ *                           in the reference): the Thomas elimination per column in the kernel, K15's surface fluxes and a
+ *                           neutral bulk drag on the lowest wind level, in two launches (kernel family K25)
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -1067,6 +1070,73 @@ typedef struct spc_les_mix_args {
 } spc_les_mix_args;
 int spc_les_mix_f64(const spc_les_mix_args *args, void *stream);
 int spc_les_mix_f32(const spc_les_mix_args *args, void *stream);
+
+/* ---- implicit vertical mixing of the device-resident LES fields by each column's own eddy viscosity (kernel family K25) ------- */
+/* One backward-Euler step of d(x)/dt = (1 / (rho dz)) d/dz (rho_h K dx/dz) per column, K at a face from THAT column's km (K24),
+ * the kinematic surface fluxes of K15 entering the lowest layer and a neutral bulk drag on the lowest wind level.  The matrix
+ * depends on the column, so the Thomas elimination runs in the kernel.  The rule is this library's definition.
+ * General conventions:
+ *   - Fields, km are [n_les][itot][jtot][ktot], k contiguous, with 64-bit offsets as in K10; speed is [n_les][itot][jtot].  The
+ *     element type T is f64 or f32.
+ *   - Every operation is rounded once in T.  Nothing contracts to an fma.
+ *   - There is ONE correctly rounded IEEE division per level and ONE correctly rounded sqrt per column.
+ *   - So every output is asked for bit for bit in both types, whatever the launch shape.
+ * Per-LES values and profiles (formed in float64 by sp_coupler_amd/vertical_mixing.py and rounded to T once), profiles
+ * [n_les x ktot] with rows pitch_prof apart, w = Rhobf dz, rho_h[k] the mean of Rhobf[k-1] and Rhobf[k]:
+ *   - el[f], eu[f]: one pointer pair per field, as K24's ax / ay, so that the Prandtl number costs the kernel no rounding:
+ *     el[k] = 0.5 dt rho_h[k] / (w[k] (zf[k] - zf[k-1])), eu[k] = 0.5 dt rho_h[k+1] / (w[k] (zf[k+1] - zf[k])) for a wind, the
+ *     same divided by the Prandtl number for a scalar.  el[0] and eu[ktot-1] are never read by the elimination.
+ *   - kb: twice the background diffusivity at face k (kb[0] is never read).
+ *   - kv2 [n_les]: twice the largest face diffusivity allowed: a sanity bound that keeps the matrix finite, no stability cap.
+ *   - s0 [n_les] = dt / dz[0]; flux[f] [n_les] or NULL, exactly as in K15.
+ *   - dr[f] [n_les] or NULL: dt cd / dz[0] with cd = (kappa / ln(zf[0] / z0m))^2; NULL for scalars.
+ * Launch 1, k_les_speed, only where some dr[f] != NULL, per column (l, i, j):
+ *   sp = sqrt(u[0] * u[0] + v[0] * v[0])                  products, add, sqrt, each rounded; written whole into speed
+ * (the winds are updated in place by other workgroups, so launch 2 must not read them).
+ * Launch 2, k_les_vmix, per column and per field f with x = fields[f]:
+ *   t     = (km[k-1] + km[k]) + kb[l][k]                  face k = 1 ... ktot-1
+ *   s[k]  = t > 0 ? t : +0                                a NaN or a negative sum gives +0
+ *   s[k]  = s[k] < kv2[l] ? s[k] : kv2[l]
+ *   lo[k] = el[f][l][k] * s[k]    (lo[0] = +0)            up[k] = eu[f][l][k] * s[k+1]    (up[ktot-1] = +0)
+ *   b[k]  = (1 + lo[k]) + up[k];  b[0] = b[0] + dr[f][l] * sp                  the drag only where dr[f] != NULL
+ *   d[0]  = flux[f] != NULL ? x[0] + s0[l] * flux[f][l] : x[0];                d[k] = x[k]
+ *   m[0]  = 1 / b[0];                     q[0] = up[0] * m[0];   y[0] = d[0] * m[0]
+ *   m[k]  = 1 / (b[k] - lo[k] * q[k-1]);  q[k] = up[k] * m[k];   y[k] = (d[k] + lo[k] * y[k-1]) * m[k]
+ *   x'[ktot-1] = y[ktot-1];               x'[k] = y[k] + q[k] * x'[k+1]
+ * x' replaces x IN PLACE.
+ * Consequences:
+ *   - Both cells of a face form s[k] from the same operands.  The form is all positive: lo, up and q are never negative, the
+ *     matrix is an M-matrix, and every pivot is at least about 1 (b[k] >= 1 + lo[k] while lo[k] q[k-1] < lo[k]), so the
+ *     division is always safe.
+ *   - ktot == 1 is allowed.  Special values in a field get no rule of their own: they stay in their own column, as in K15.
+ *   - With km = 0, kb = 0, no flux and no drag a finite column keeps every value.
+ *   - These are SPC_ERR_INVALID_ARGUMENT: n_fields outside 1 ... SPC_VMIX_MAX_FIELDS; pitch_prof < ktot; a NULL km, kb, kv2, or
+ *     a NULL fields[f], el[f], eu[f] of f < n_fields; two EQUAL fields pointers; a field equal to km, speed, a profile, kv2, s0,
+ *     a drag or a flux; a flux without s0; a dr without u, v and speed; speed equal to an input; a misaligned pointer.
+ *   - Arrays that overlap only in part are not detected and must not be passed.  n_les == 0 is a no-op.
+ * A workgroup takes spc_les_vmix_cols_per_block(ktot, sizeof(T)) columns of km and of one field into LDS; above the largest
+ * ktot of which 16 columns fit twice (639 levels of 8 bytes, 1 279 of 4) the launch is SPC_ERR_UNSUPPORTED.                */
+#define SPC_VMIX_MAX_FIELDS 6
+typedef struct spc_les_vmix_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_fields; /* n_fields 1 ... SPC_VMIX_MAX_FIELDS                                */
+    void *fields[SPC_VMIX_MAX_FIELDS];       /* device [n_les][itot][jtot][ktot], updated in place           */
+    const void *flux[SPC_VMIX_MAX_FIELDS];   /* device [n_les], the kinematic surface flux, or NULL          */
+    const void *dr[SPC_VMIX_MAX_FIELDS];     /* device [n_les], the drag of a wind, or NULL                  */
+    const void *el[SPC_VMIX_MAX_FIELDS];     /* device [n_les x ktot] per field, rows pitch_prof apart       */
+    const void *eu[SPC_VMIX_MAX_FIELDS];     /* device [n_les x ktot] per field, rows pitch_prof apart       */
+    const void *km;                     /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *kb;                     /* device [n_les x ktot], rows pitch_prof apart                      */
+    const void *kv2;                    /* device [n_les]                                                    */
+    const void *s0;                     /* device [n_les]; may be NULL when every flux is NULL               */
+    const void *u, *v;                  /* device [n_les][itot][jtot][ktot], read by launch 1; NULL without a dr */
+    void *speed;                        /* device [n_les][itot][jtot], written whole by launch 1; NULL without a dr */
+    int64_t pitch_prof;                 /* >= ktot                                                           */
+} spc_les_vmix_args;
+int spc_les_vmix_f64(const spc_les_vmix_args *args, void *stream);
+int spc_les_vmix_f32(const spc_les_vmix_args *args, void *stream);
+/* columns per workgroup of k_les_vmix for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
+int spc_les_vmix_cols_per_block(int ktot, int elem_size);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

@@ -209,6 +209,16 @@ class LesMixArgs(ctypes.Structure):
                    ("ax", c_void_p * SPC_MIX_MAX_FIELDS), ("ay", c_void_p * SPC_MIX_MAX_FIELDS)])
 
 
+SPC_VMIX_MAX_FIELDS = 6
+
+
+class LesVmixArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32),
+                 ("fields", c_void_p * SPC_VMIX_MAX_FIELDS), ("flux", c_void_p * SPC_VMIX_MAX_FIELDS),
+                 ("dr", c_void_p * SPC_VMIX_MAX_FIELDS), ("el", c_void_p * SPC_VMIX_MAX_FIELDS), ("eu", c_void_p * SPC_VMIX_MAX_FIELDS)]
+                + _ptrs("km", "kb", "kv2", "s0", "u", "v", "speed") + [("pitch_prof", c_int64)])
+
+
 class LesQtLocalArgs(ctypes.Structure):
     _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("split", c_int32)]
                 + _ptrs("qt", "ql", "a", "qtm") + [("pitch_prof", c_int64), ("count", c_void_p), ("pitch_count", c_int64)])
@@ -303,6 +313,9 @@ PROTOTYPES = {
     "spc_les_buoyancy_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_les_mix_f64": (ctypes.c_int, [ctypes.POINTER(LesMixArgs), c_void_p]),
     "spc_les_mix_f32": (ctypes.c_int, [ctypes.POINTER(LesMixArgs), c_void_p]),
+    "spc_les_vmix_f64": (ctypes.c_int, [ctypes.POINTER(LesVmixArgs), c_void_p]),
+    "spc_les_vmix_f32": (ctypes.c_int, [ctypes.POINTER(LesVmixArgs), c_void_p]),
+    "spc_les_vmix_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

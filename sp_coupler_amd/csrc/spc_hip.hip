@@ -54,6 +54,9 @@
 //                  and the stratification (one sqrt per cell), and the horizontal mixing of the carried fields by it in flux
 //                  form (K16's shape and neighbours, every face flux formed alike by its two cells): spc_mix.hpp, kernels and
 //                  host side
+//   K25 k_les_speed, k_les_vmix  one backward-Euler step of the vertical mixing by each column's own eddy viscosity: the Thomas
+//                  elimination in the kernel (one division per level), K15's tile, surface fluxes and a neutral bulk drag on the
+//                  lowest wind level from a plane of wind speeds: spc_vmix.hpp, kernels and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
@@ -117,6 +120,7 @@ namespace {
 #include "spc_moments.hpp"
 #include "spc_buoyancy.hpp"
 #include "spc_mix.hpp"
+#include "spc_vmix.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -169,6 +173,9 @@ namespace {
 #define SPC_MIX_HOST
 #include "spc_mix.hpp"
 #undef SPC_MIX_HOST
+#define SPC_VMIX_HOST
+#include "spc_vmix.hpp"
+#undef SPC_VMIX_HOST
 
 }  // namespace
 
@@ -278,6 +285,9 @@ int spc_les_buoyancy_cols_per_block(int ktot, int elem_size) { return hyd_cols(k
 
 int spc_les_mix_f64(const spc_les_mix_args *a, void *s) { return les_mix_impl<double>(a, s); }
 int spc_les_mix_f32(const spc_les_mix_args *a, void *s) { return les_mix_impl<float>(a, s); }
+int spc_les_vmix_f64(const spc_les_vmix_args *a, void *s) { return les_vmix_impl<double>(a, s); }
+int spc_les_vmix_f32(const spc_les_vmix_args *a, void *s) { return les_vmix_impl<float>(a, s); }
+int spc_les_vmix_cols_per_block(int ktot, int elem_size) { return vmix_cols(ktot, elem_size); }
 
 int spc_les_moments_f64(const spc_les_moments_args *a, void *s) { return les_moments_impl<double>(a, s); }
 int spc_les_moments_f32(const spc_les_moments_args *a, void *s) { return les_moments_impl<float>(a, s); }

@@ -10,6 +10,7 @@ from . import buoyancy as buo
 from . import diffusion as df
 from . import microphysics as mp
 from . import mixing as mix
+from . import vertical_mixing as vmix
 from . import radiation as rad
 from . import thermo as th
 from .models import SyntheticLESEnsemble, _LESRow, _row_getter, _timed
@@ -138,6 +139,10 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     After ``enable_mixing()`` every step mixes U, V, THL, QT and QR along i and j by the Smagorinsky-Lilly eddy viscosity of the
     flow (K24, ``Engine.les_mix``), after the advection and before K15, whose diffusivity it can supply (``vertical=True``);
     ``get_eddy_viscosity_batched()`` returns the viscosity; tests/les_mix_ref.py holds the twin of that mode.
+    After ``enable_vertical_mixing()`` (behind ``enable_mixing()``) every step mixes U, V, THL, QT and QR along k by each
+    column's own uncapped eddy viscosity, with the surface fluxes into THL and QT and a neutral bulk drag on U and V (K25,
+    ``Engine.les_vmix``), where K15 stands; ``get_vertical_viscosity_batched()`` returns that viscosity; tests/les_vmix_ref.py
+    holds the twin of that mode.
     ``get_statistics_batched`` reduces the fields to their second moments per level (K20, ``Engine.les_moments``): means,
     variances, standard deviations and the covariances of ``statistics.PAIRS``; tests/les_moments_ref.py holds their twin."""
 
@@ -288,6 +293,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             raise ValueError("the diffusion (K15) needs one of the fields %s (set_fields_batched)" % (self.DIFFUSE_KEYS,))
         if not self._has("les_diffuse"):
             raise ValueError("the engine has no les_diffuse (K15)")
+        if self.vertical_mixing:
+            raise ValueError("the diffusion (K15) and the vertical mixing (K25) exclude each other: a step has one vertical diffusion")
         self.diffuse_par = {"k_max": df.K_MAX if k_max is None else float(k_max), "h_mix": df.H_MIX if h_mix is None else float(h_mix),
                             "k_bg": df.K_BG if k_bg is None else float(k_bg)}
         self.diffusion, self._diffuse_prof = True, None
@@ -669,6 +676,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             raise ValueError("the mixing (K24) needs the fields U and V (set_fields_batched)")
         if not self._has("les_mix"):
             raise ValueError("the engine has no les_mix (K24)")
+        if vertical and self.vertical_mixing:
+            raise ValueError("the mixing (K24) with vertical=True and the vertical mixing (K25) exclude each other: a step has one vertical diffusion")
         if vertical and not self.diffusion:
             raise ValueError("the mixing (K24) with vertical=True hands its viscosity to K15: it needs enable_diffusion()")
         if dx is None:
@@ -717,25 +726,110 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             spare[k] = self._scratch(spare.get(k), f[k], f[k])
         self._mix_km = self._scratch(self._mix_km, f["U"])
         coef = {k: wind if k in self.MIX_WINDS else scalar for k in keys}
+        u, v = f["U"], f["V"]                             # (the swap below leaves them in the spare buffers, unchanged)
         top = eng.les_mix({k: f[k] for k in keys}, {k: spare[k] for k in keys}, f["U"], f["V"], theta, gx, gy, gz, bz if theta is not None else None,
                           l2, kcap, self._mix_km, {k: coef[k][0] for k in keys}, {k: coef[k][1] for k in keys})
         for k in keys:
             f[k], spare[k] = spare[k], f[k]
         self.mixing_k_max = self._device_max(top)
         self.mixing_capped = self.mixing_k_max > lowest
+        if self.vertical_mixing and self.mixing_capped:   # K25 mixes by the UNCAPPED viscosity: the probe again under a cap that never binds
+            self._vmix_km = self._scratch(self._vmix_km, self._mix_km, self._mix_km)
+            if self._vmix_huge is None:
+                self._vmix_huge = self._upload(numpy.full(self.n, float(torch.finfo(eng.dtype).max)))
+            eng.les_mix({}, {}, u, v, theta, gx, gy, gz, bz if theta is not None else None, l2, self._vmix_huge, self._vmix_km, {}, {}, kmax=False)
         if par["vertical"]:
             m = self._to_host(eng.slab_means({"km": self._mix_km}))["km"]
             self._mix_kd = mix.face_diffusivity(m, self.diffuse_par["k_bg"])
         self._drop_water_paths()
         self._drop_statistics()
         self._thermo_stale = True                         # thermo: K12 runs on the mixed THL and QT before their next use
-        if not self.diffusion:                            # (else the QL field and the means follow the diffused fields: _diffuse)
+        if not (self.diffusion or self.vertical_mixing):  # (else the QL field and the means follow the diffused fields: _diffuse, _vmix)
             self._follow_fields()
 
     def get_eddy_viscosity_batched(self):
         """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the capped eddy viscosity
         km in m2/s that K24 found in the last step; None before the first step of enable_mixing()"""
         return self._mix_km if self.mixing else None
+
+    # -- implicit vertical mixing by each column's own eddy viscosity (K25), opt-in ----------------------------------------------
+    vertical_mixing = False                            # enable_vertical_mixing(): every column mixes along k by its own km
+    vmix_par = None                                    # kv_cap, k_bg, drag
+    VMIX_FLUX = DIFFUSE_FLUX                           # field -> the slot of ``tend`` that holds its kinematic surface flux
+    VMIX_Z0M = "z0m"                                   # the slot of ``tend`` that holds the roughness length of the drag
+    _vmix_coef = None                                  # ((dt, prandtl, k_bg, kv_cap, host Rhobf, zh, zf) of the upload, device winds' and scalars' (el, eu), kb, kv2, s0)
+    _vmix_drag = None                                  # ((dt, host z0m, zh, zf) of the upload, device dr)
+    _vmix_km = None                                    # the uncapped eddy viscosity of the last step where K24's cap bound, device
+    _vmix_huge = None                                  # device [n]: the type's largest finite value, the cap of that probe
+    _vmix_speed = None                                 # device [n x itot x jtot]: the wind speed of the lowest level, K25's workspace
+
+    def enable_vertical_mixing(self, kv_cap=None, k_bg=None, drag=True):
+        """from now on every ``evolve_model_batched`` runs ONE ``Engine.les_vmix`` per device (K25, DESIGN.md 7.3: two launches)
+        after K24 and where K15 stands: one backward-Euler step of the vertical mixing of every column by ITS OWN eddy viscosity,
+        the UNCAPPED km of K24 (where this step's ``mixing_capped`` is True one more ``les_mix`` without fields writes it into a
+        second buffer; else K24's km is that value bit for bit), plus the background ``k_bg``, bounded by ``kv_cap``.  U and V mix
+        with the winds' coefficients and, with ``drag``, feel a neutral bulk drag at the lowest level where a roughness length
+        was handed over (``set_z0m_surf`` / ``Z0M_surf``; none where none was set); THL, QT and QR mix with the scalars'
+        coefficients, and THL and QT take K15's surface fluxes (``WT_surf``, ``WQ_surf``).  The profiles then are K10's means of
+        the mixed fields and QL follows the new QT.  The coefficients are uploaded again whenever dt, ``prandtl`` (that of
+        ``enable_mixing()``), a parameter, Rhobf or the grid changed; the drag whenever z0m or dt did.  Needs ``enable_mixing()``
+        first; ValueError with ``enable_diffusion()`` in either order and with ``enable_mixing(vertical=True)``: a step has
+        one vertical diffusion.  ``get_vertical_viscosity_batched()`` returns the viscosity.  Without this call every path,
+        launch and bit of the ensemble is unchanged."""
+        if not self.mixing:
+            raise ValueError("the vertical mixing (K25) mixes by the eddy viscosity of K24: it needs enable_mixing() first")
+        if self.diffusion:
+            raise ValueError("the vertical mixing (K25) and the diffusion (K15) exclude each other: a step has one vertical diffusion")
+        if self.mix_par["vertical"]:
+            raise ValueError("the vertical mixing (K25) and enable_mixing(vertical=True) exclude each other: a step has one vertical diffusion")
+        if not self._has("les_vmix"):
+            raise ValueError("the engine has no les_vmix (K25)")
+        par = {"kv_cap": vmix.KV_CAP if kv_cap is None else float(kv_cap), "k_bg": vmix.K_BG if k_bg is None else float(k_bg),
+               "drag": bool(drag)}
+        vmix.background(self.n, 1, par["k_bg"], par["kv_cap"])                                 # (ValueError for what is out of range)
+        self.vertical_mixing, self.vmix_par = True, par
+        self._vmix_coef = self._vmix_drag = self._vmix_km = self._vmix_huge = self._vmix_speed = None
+
+    def _vmix(self, dt):
+        """K25 on the mixed fields; QL (without thermo) and the profiles are then those of the vertically mixed fields"""
+        eng, f, p, par = self._eng(), self.fields3d, self.p, self.vmix_par
+        keys = [k for k in self.MIX_KEYS if k in f]
+        if self.n == 0 or not keys:
+            return
+        # everything the coefficients are made of; the host arrays are copied and compared every step (kilobytes)
+        key = (float(dt), self.mix_par["prandtl"], par["k_bg"], par["kv_cap"]) + _f64(p["Rhobf"], self.zh_cache, self.zf_cache)
+
+        def coefficients():
+            wind, scalar, s0 = vmix.coefficients(key[5], key[6], key[4], dt, key[1])
+            kb, kv2 = vmix.background(self.n, wind[0].shape[-1], key[2], key[3])
+            up = lambda pair: tuple(self._upload(a) for a in pair)                            # noqa: E731
+            return key, up(wind), up(scalar), self._upload(kb), self._upload(kv2), self._upload(s0)
+        self._vmix_coef = _kept(self._vmix_coef, key, coefficients)
+        _, wind, scalar, kb, kv2, s0 = self._vmix_coef
+        coef = {k: wind if k in self.MIX_WINDS else scalar for k in keys}
+        flux = {k: self._upload(numpy.asarray(self.tend[slot], dtype=numpy.float64).reshape(self.n))
+                for k, slot in self.VMIX_FLUX.items() if k in keys and slot in self.tend}
+        drag, speed = {}, None
+        if par["drag"] and self.VMIX_Z0M in self.tend:
+            dkey = (float(dt),) + _f64(numpy.asarray(self.tend[self.VMIX_Z0M], dtype=numpy.float64).reshape(self.n), self.zh_cache, self.zf_cache)
+            self._vmix_drag = _kept(self._vmix_drag, dkey, lambda: (dkey, self._upload(vmix.drag(
+                dkey[1], dkey[3], mp.layer_thickness(dkey[2], dkey[3]), dt))))
+            drag = {k: self._vmix_drag[1] for k in self.MIX_WINDS if k in keys}
+            if self._vmix_speed is None or tuple(self._vmix_speed.shape) != tuple(f["U"].shape[:3]):
+                self._vmix_speed = self._per_device(lambda u: torch.empty(u.shape[:3], dtype=u.dtype, device=u.device), f["U"])
+            speed = self._vmix_speed
+        eng.les_vmix({k: f[k] for k in keys}, self.get_vertical_viscosity_batched(), {k: coef[k][0] for k in keys},
+                     {k: coef[k][1] for k in keys}, kb, kv2, s0=s0, flux=flux, drag=drag,
+                     u=f["U"] if drag else None, v=f["V"] if drag else None, speed=speed)
+        self._follow_fields()                             # K12 stale, QL of the mixed QT, p[U, V, THL, QT, QL] = K10's means
+
+    def get_vertical_viscosity_batched(self):
+        """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the UNCAPPED eddy viscosity
+        in m2/s by which K25 mixed in the last step: K24's own km where its cap did not bind, else the second buffer; None
+        before the first step of enable_vertical_mixing()"""
+        if not self.vertical_mixing or self._mix_km is None:
+            return None
+        return self._vmix_km if self.mixing_capped else self._mix_km
 
     # -- longwave cooling and warming by the liquid water (K18), opt-in ---------------------------------------------------------
     radiation = False                                  # enable_radiation(): the cloud water acts on THL
@@ -1227,6 +1321,8 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             self._mix(dt)                                 # one K24 call, two launches: km of the flow; U, V, THL, QT, QR mixed along i and j; p[...]
         if self.diffusion:
             self._diffuse(dt)                             # one K15 launch: U, V, THL, QT mixed along k, the surface fluxes; p[...]
+        if self.vertical_mixing:
+            self._vmix(dt)                                # one K25 call, two launches: U, V, THL, QT, QR mixed along k by each column's km; p[...]
         if self.radiation:
             self._radiate(dt)                             # one K18 launch: THL cooled at the cloud tops, warmed at the bases; p[...]
         if self.micro:

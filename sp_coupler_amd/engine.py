@@ -1228,6 +1228,71 @@ class Engine:
         self._call(self._sym("les_mix"), ctypes.byref(a), stream=stream)
         return res
 
+    # -- K25: implicit vertical mixing of device-resident LES fields by each column's own eddy viscosity, two launches ---------------
+    @_on_engine_stream
+    def les_vmix(self, fields, km, el, eu, kb, kv2, s0=None, flux=None, drag=None, u=None, v=None, speed=None, stream=None):
+        """One backward-Euler step of the vertical mixing (include/spc.h has the rule) IN PLACE on every tensor of ``fields``
+        (dict name -> contiguous [n x itot x jtot x ktot], at most ``_abi.SPC_VMIX_MAX_FIELDS`` of one shape) by the eddy
+        viscosity ``km`` (the same shape, read only).  ``el`` and ``eu`` are dicts name -> [n x ktot] with the names of
+        ``fields`` (fields may share a tensor), ``kb`` [n x ktot] and ``kv2``, ``s0`` [n] are ``vertical_mixing``'s arrays in the
+        engine's dtype (rows may be pitched, all with one pitch).  ``flux``: dict name -> [n], the kinematic surface flux that
+        enters level 0 of that field (needs ``s0``).  ``drag``: dict name -> [n], ``vertical_mixing.drag`` of that wind; it
+        needs the winds ``u`` and ``v`` (which may be fields) and the plane ``speed`` [n x itot x jtot], which is written whole
+        with the speed of the lowest level BEFORE any field changes.  A field that STARTS where another field, ``km``,
+        ``speed``, a profile, a flux or a drag starts is refused (ValueError); views that overlap in part are not detected.  Two
+        launches (one without a drag); more levels than ``vmix_cols_per_block`` carries are refused (SPC_ERR_UNSUPPORTED)."""
+        names = list(fields)
+        if not 1 <= len(names) <= _abi.SPC_VMIX_MAX_FIELDS:
+            raise ValueError("les_vmix takes 1 ... %d fields per launch, got %d" % (_abi.SPC_VMIX_MAX_FIELDS, len(names)))
+        for what, d in (("el", el), ("eu", eu)):
+            if sorted(d) != sorted(names):
+                raise ValueError("les_vmix: %s holds %s, the fields are %s" % (what, sorted(d), sorted(names)))
+        flux = {} if flux is None else {k: t for k, t in flux.items() if t is not None}
+        drag = {} if drag is None else {k: t for k, t in drag.items() if t is not None}
+        for what, d in (("fluxes", flux), ("drags", drag)):
+            unknown = [k for k in d if k not in fields]
+            if unknown:
+                raise ValueError("les_vmix: %s %s have no field" % (what, unknown))
+        if flux and s0 is None:
+            raise ValueError("les_vmix: a flux needs s0")
+        if drag and (u is None or v is None or speed is None):
+            raise ValueError("les_vmix: a drag needs u, v and speed")
+        shape = n, itot, jtot, ktot = self._extents("les_vmix", names[0], fields[names[0]])
+        ck = _Checker(self.device, self.dtype)
+        g = _abi.LesVmixArgs()
+        g.n_les, g.itot, g.jtot, g.ktot, g.n_fields = n, itot, jtot, ktot, len(names)
+        g.km = self._field4("km", km, shape).data_ptr()
+        g.kb, g.pitch_prof = ck.mat("kb", kb, n, ktot)
+        g.kv2 = ck.vec("kv2", kv2, n)
+        read = [km, kb, kv2]
+        if s0 is not None:
+            g.s0 = ck.vec("s0", s0, n)
+            read.append(s0)
+        written = [fields[k] for k in names]
+        if drag:
+            g.u, g.v = self._field4("u", u, shape).data_ptr(), self._field4("v", v, shape).data_ptr()
+            g.speed = self._plane("speed", speed, shape[:3]).data_ptr()
+            self._no_alias("les_vmix: speed is an input", [speed], [u, v], n)
+            written.append(speed)
+        for f, name in enumerate(names):
+            g.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            g.el[f], _ = ck.mat("el[%s]" % name, el[name], n, ktot, pitch=g.pitch_prof)
+            g.eu[f], _ = ck.mat("eu[%s]" % name, eu[name], n, ktot, pitch=g.pitch_prof)
+            read += [el[name], eu[name]]
+            if name in flux:
+                g.flux[f] = ck.vec("flux[%s]" % name, flux[name], n)
+                read.append(flux[name])
+            if name in drag:
+                g.dr[f] = ck.vec("drag[%s]" % name, drag[name], n)
+                read.append(drag[name])
+        self._no_alias("les_vmix: a field or speed is another field, km, a profile, s0, a flux or a drag", written, read, n)
+        self._call(self._sym("les_vmix"), ctypes.byref(g), stream=stream)
+
+    def vmix_cols_per_block(self, ktot):
+        """columns of ``ktot`` levels a workgroup of K25's k_les_vmix takes into LDS in the engine's dtype (64, 32 or 16);
+        0: unsupported"""
+        return self._geometry("vmix_cols_per_block", ktot)
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

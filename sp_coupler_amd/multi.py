@@ -337,6 +337,16 @@ class MultiDeviceEngine:
         launches per device that holds rows, none on the others"""
         return self._largest("les_mix", "kmax", u, (fields, out, u, v, theta, gx, gy, gz, bz, l2, kcap, km, ax, ay), dict(kw, kmax=kmax))
 
+    def les_vmix(self, fields, km, el, eu, kb, kv2, s0=None, flux=None, drag=None, u=None, v=None, speed=None, **kw):
+        """K25 on every device's LES: dict of Sharded fields (mixed in place, block by block), the Sharded ``km``, the dicts ``el``
+        and ``eu`` of Sharded [n x ktot], ``kb`` [n x ktot], ``kv2`` and ``s0`` [n], the dicts of Sharded [n] fluxes and drags, the
+        Sharded winds and the Sharded plane ``speed`` [n x itot x jtot] in; two launches per device that holds rows, none on the
+        others"""
+        ex = self._example(fields)
+        if ex is None:
+            return self.primary.les_vmix(fields, km, el, eu, kb, kv2, s0=s0, flux=flux, drag=drag, u=u, v=v, speed=speed, **kw)
+        self._each("les_vmix", ex, (fields, km, el, eu, kb, kv2), dict(kw, s0=s0, flux=flux, drag=drag, u=u, v=v, speed=speed))
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

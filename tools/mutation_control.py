@@ -49,6 +49,7 @@ QTLOCAL = "spc_qtlocal.hpp"
 MOMENTS = "spc_moments.hpp"
 BUOYANCY = "spc_buoyancy.hpp"
 MIX = "spc_mix.hpp"
+VMIX = "spc_vmix.hpp"
 TRANSPORT = "spc_transport.hpp"
 TRANSPORT2 = "spc_transport2.hpp"
 GEO = "spc_geo.hpp"
@@ -83,6 +84,7 @@ vadvect_body = partial(body_guard, "les_vadvect_ref")
 radiate_body = partial(body_guard, "les_radiate_ref")
 buoyancy_body = partial(body_guard, "les_buoyancy_ref")
 mix_body = partial(body_guard, "les_mix_ref")
+vmix_body = partial(body_guard, "les_vmix_ref")
 geo_body = partial(body_guard, "geo_edges", dtypes=("float64",))
 lesstate_body = partial(body_guard, "les_state_ref", dtypes=("float64",))
 qtlocal_body = partial(body_guard, "les_qt_local_ref")
@@ -781,6 +783,29 @@ TRANSPORT2_MUTANTS = {
         [(TRANSPORT2, "const int imm = im ? im - 1 : itot - 1;", "const int imm = im;")]),
 }
 
+# K25 (spc_vmix.hpp), numbered on its own.  Every mutant changes a VALUE only: no loop bound, barrier or launch extent differs from
+# the shipped kernel, and every index stays inside the column's LDS cells and the rows the shipped kernel reads (mutant 2 reads
+# eu[ktot - 1], an entry of the array that the rule never uses; mutant 5 reads the cell of q[ktot - 1], which holds km[ktot - 1]).
+VMIX_MUTANTS = {
+    1: ("K25 s: the upper cell's km taken twice (km[k] for km[k-1]: a face no longer belongs to both its cells alike)", vmix_body("parity"),
+        [(VMIX, "const T h = ka + kn;", "const T h = kn + kn;")]),
+    2: ("K25 lo: eu for el", vmix_body("parity"),
+        [(VMIX, "const T lo = ce[u] * slo;", "const T lo = cu[u] * slo;"), (VMIX, "const T lo = el[k] * slo;", "const T lo = eu[k] * slo;"),
+         (VMIX, "const T lo = el[top] * slo;", "const T lo = eu[top] * slo;")]),
+    3: ("K25 s: the comparison of the cap reversed (the larger of s and kv2)", vmix_body("viscosity"),
+        [(VMIX, "return s < cap ? s : cap;", "return s > cap ? s : cap;")]),
+    4: ("K25 b: 1 - lo for 1 + lo", vmix_body("parity"),
+        [(VMIX, "const T b1 = (T)1 + lo;", "const T b1 = (T)1 - lo;", 2), (VMIX, "const T bk = (T)1 + lo; ", "const T bk = (T)1 - lo; ")]),
+    5: ("K25 back substitution: q of the level above (q[k] for q[k-1], seen from the level that is known)", vmix_body("parity"),
+        [(VMIX, "cq[u] = kq[k - u];", "cq[u] = kq[k - u + 1];"), (VMIX, "const T t = kq[k] * y;", "const T t = kq[k + 1] * y;")]),
+    6: ("K25 drag: a field without a drag takes that of the launch's first field (the drag on a scalar)", vmix_body("boundary"),
+        [(VMIX, "const T *dr = p.dr[f];", "const T *dr = p.dr[f] ? p.dr[f] : p.dr[0];")]),
+    7: ("K25 d[0]: s0 left out (the flux enters as if dt / dz[0] were 1)", vmix_body("boundary"),
+        [(VMIX, "const T t = p.s0[l] * flux[l];", "const T t = flux[l];")]),
+    8: ("K25 sp: without v (the drag sees the wind along i only)", vmix_body("boundary"),
+        [(VMIX, "const T e = uu + vv;", "const T e = uu;")]),
+}
+
 
 def _tag(table):
     """(library prefix, source directory prefix) of a table"""
@@ -1000,6 +1025,7 @@ TABLES = (
 #: that adds a kernel leaves as it is): same rows, same handling; fold them into TABLES when that count is next revised
 LATER_TABLES = (
     Table("mix", MIX_MUTANTS, "K24", "mix_", "mix", "les_mix_ref", "test_les_mix_gpu"),
+    Table("vmix", VMIX_MUTANTS, "K25", "vmix_", "vmix", "les_vmix_ref", "test_les_vmix_gpu"),
 )
 ALL_TABLES = TABLES + LATER_TABLES
 
