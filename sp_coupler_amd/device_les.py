@@ -762,6 +762,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     _vmix_km = None                                    # the uncapped eddy viscosity of the last step where K24's cap bound, device
     _vmix_huge = None                                  # device [n]: the type's largest finite value, the cap of that probe
     _vmix_speed = None                                 # device [n x itot x jtot]: the wind speed of the lowest level, K25's workspace
+    _vmix_stepped = False                              # K25 has run since enable_vertical_mixing(): there is a viscosity it mixed by
 
     def enable_vertical_mixing(self, kv_cap=None, k_bg=None, drag=True):
         """from now on every ``evolve_model_batched`` runs ONE ``Engine.les_vmix`` per device (K25, DESIGN.md 7.3: two launches)
@@ -789,6 +790,7 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         vmix.background(self.n, 1, par["k_bg"], par["kv_cap"])                                 # (ValueError for what is out of range)
         self.vertical_mixing, self.vmix_par = True, par
         self._vmix_coef = self._vmix_drag = self._vmix_km = self._vmix_huge = self._vmix_speed = None
+        self._vmix_stepped = False                        # (K24's km of a step before this call is no viscosity K25 mixed by)
 
     def _vmix(self, dt):
         """K25 on the mixed fields; QL (without thermo) and the profiles are then those of the vertically mixed fields"""
@@ -818,18 +820,23 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             if self._vmix_speed is None or tuple(self._vmix_speed.shape) != tuple(f["U"].shape[:3]):
                 self._vmix_speed = self._per_device(lambda u: torch.empty(u.shape[:3], dtype=u.dtype, device=u.device), f["U"])
             speed = self._vmix_speed
-        eng.les_vmix({k: f[k] for k in keys}, self.get_vertical_viscosity_batched(), {k: coef[k][0] for k in keys},
+        eng.les_vmix({k: f[k] for k in keys}, self._vmix_viscosity(), {k: coef[k][0] for k in keys},
                      {k: coef[k][1] for k in keys}, kb, kv2, s0=s0, flux=flux, drag=drag,
                      u=f["U"] if drag else None, v=f["V"] if drag else None, speed=speed)
+        self._vmix_stepped = True
         self._follow_fields()                             # K12 stale, QL of the mixed QT, p[U, V, THL, QT, QL] = K10's means
+
+    def _vmix_viscosity(self):
+        """what K25 mixes by in this step: K24's km where its cap did not bind, else the second buffer"""
+        return self._vmix_km if self.mixing_capped else self._mix_km
 
     def get_vertical_viscosity_batched(self):
         """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the UNCAPPED eddy viscosity
         in m2/s by which K25 mixed in the last step: K24's own km where its cap did not bind, else the second buffer; None
-        before the first step of enable_vertical_mixing()"""
-        if not self.vertical_mixing or self._mix_km is None:
+        before the first step of enable_vertical_mixing(), and of an enable_mixing() behind it"""
+        if not (self.vertical_mixing and self._vmix_stepped) or self._mix_km is None:
             return None
-        return self._vmix_km if self.mixing_capped else self._mix_km
+        return self._vmix_viscosity()
 
     # -- longwave cooling and warming by the liquid water (K18), opt-in ---------------------------------------------------------
     radiation = False                                  # enable_radiation(): the cloud water acts on THL

@@ -1,12 +1,14 @@
 """Random operation sequences of models.DeviceLESEnsemble (the class lives in sp_coupler_amd/device_les.py; the name in models
-is the same object) against its eager NumPy twin (tests/les_full_ref.py: HostFullLESEnsemble / HostThermoFullLESEnsemble, the
+is the same object) against its eager NumPy twin (tests/les_vmix_ref.py: HostVmixLESEnsemble / HostThermoVmixLESEnsemble, the
 top of the chain of twins): the body of tests/test_ensemble_sequences_cpu.py (on oracle-backed engines) and
 tests/test_ensemble_sequences_gpu.py (on the card).
 
 The device ensemble is a lazy, cached state machine (_thermo_stale, _means, _wp / _wp_host / _wp_w, _thermo_means, the profile
 uploads keyed on their inputs, the ping-pong buffers of K14 / K16 / K17 / K22, the fused K11 step, K19's count buffer and its wait
 for the forcing, K20's partial cache _stats / _stats_host / _stats_w, K21's profiles and pressure, K22's lid flux summed over the
-substeps); the twin computes everything eagerly from its fields.  ``generate`` draws a list of operations that are all valid in
+substeps, K24's profiles, coefficients, ping-pong buffers and viscosity, K25's coefficients, drag and second viscosity buffer
+with the switch between the two on ``mixing_capped``); the twin computes everything eagerly from its fields.
+``generate`` draws a list of operations that are all valid in
 the state they meet, mutations and sparse observations mixed; ``replay`` applies the list to both and compares every observation
 bit for bit (gpu_util.assert_bits), with two exceptions: W within the bound of les_vadvect_ref.check_w (a torch expression), and
 the moments that hold W (its mean, variance and standard deviation, its covariances, TKE with it) bit for bit against NumPy's
@@ -15,9 +17,12 @@ les_moments_ref.ensemble_run: the twin's W differs in its last bits.
 
 The modes: the six of the first version (thermo, diffuse, micro, advect, vertical, radiate), then "qt" (K19; the kind local /
 strong comes from ``params``), "buoyancy" (K21; needs vertical), "conservative" (K22; needs vertical), "order2" (K23; needs
-conservative; the limiter comes from ``params``) and "stats" (K20: statistics observations are drawn only with it).  The new modes
-stand at the END of MODES: the bit mask that seeds the generator, and so every sequence of the 48 old subsets, is what it was
-(tests/test_ensemble_sequences_cpu.py holds their digest).
+conservative; the limiter comes from ``params``) and "stats" (K20: statistics observations are drawn only with it), then "mix"
+(K24, enable_mixing), "vmix" (K25, enable_vertical_mixing; needs mix, excludes diffuse) and "kmix" (enable_mixing once more with
+vertical=True: K24's slab-mean viscosity in K15; needs mix and diffuse, excludes vmix); the cap, the stability switch, the
+spacings of K24 and the drag of K25 come from ``params``.  Every newer set of modes stands at the END of MODES: the bit mask
+that seeds the generator, and so every sequence of the 48 old subsets and of the 55 combinations of ELEVEN, is what it was
+(tests/test_ensemble_sequences_cpu.py holds both digests).
 
 Conditions, asserted here and not left to the callers:
   * every sequence has its full length, runs to its end on both sides and ends with a full record: every profile (batched,
@@ -27,6 +32,9 @@ Conditions, asserted here and not left to the callers:
   * every sequence holds a step that no read precedes and two consecutive mutations;
   * every mode a sequence enables launches its engine method at least once on the device side (``check_launched``); K19 launches
     only behind the ``qt_forcings`` that every "qt" sequence holds between two steps, and never before it;
+  * a "vmix" sequence with the drag holds a ``z0m`` between two steps; in a step with K25 ``les_mix`` is called twice exactly where
+    the step's ``mixing_capped`` is True, else once; between ``les_mix`` and K15 stands one ``slab_means`` (of km) with "kmix", else nothing;
+  * a ``refused`` call raises ValueError on both sides, and what follows it shows that it changed nothing;
   * over a set of cases every kind of operation occurs that their modes allow (``check_kinds``).
 Properties of the device ensemble (and of the twin, where it has the method) that need no twin:
   (a) a row getter of key k returns row i of what get_profiles_batched((k,)) returns at that moment: checked at every ``row``
@@ -47,30 +55,37 @@ from sp_coupler_amd import qt_forcing as qf
 from sp_coupler_amd import radiation as rad
 from sp_coupler_amd import statistics as st
 from tests import les_diffuse_ref as ldr
-from tests import les_full_ref as lfr
 from tests import les_moments_ref as lmo
 from tests import les_vadvect_ref as lvr
+from tests import les_vmix_ref as lvm
 from tests.gpu_util import assert_bits
 from tests.les_harness import host_of
 from tests.test_vnudge import make_les_fields
 
 OLD_MODES = ("thermo", "diffuse", "micro", "advect", "vertical", "radiate")
 NEW_MODES = ("qt", "buoyancy", "conservative", "order2", "stats")
-MODES = OLD_MODES + NEW_MODES
-LATE = ("diffuse", "micro", "advect", "radiate", "qt", "buoyancy")  # may be enabled mid-sequence (vertical, conservative and order2 come with advect)
+MIX_MODES = ("mix", "vmix", "kmix")
+ELEVEN = OLD_MODES + NEW_MODES                                    # everything but the mixing: what "all modes" meant before K24
+MODES = ELEVEN + MIX_MODES
+# may be enabled mid-sequence (vertical, conservative and order2 come with advect; vmix and kmix behind mix, kmix behind diffuse)
+LATE = ("diffuse", "micro", "advect", "radiate", "qt", "buoyancy") + MIX_MODES
+AFTER = {"buoyancy": ("advect",), "vmix": ("mix",), "kmix": ("mix", "diffuse")}      # a late enable waits for the late enables of these
 WITH_ADVECT = ("vertical", "conservative", "order2")
 METHOD = {"thermo": "les_thermo", "diffuse": "les_diffuse", "micro": "les_microphysics", "advect": "les_advect",
           "vertical": "les_vadvect", "radiate": "les_radiate", "qt": "les_qt_local", "buoyancy": "les_buoyancy",
-          "conservative": "les_transport", "order2": "les_transport2", "stats": "les_moments"}
+          "conservative": "les_transport", "order2": "les_transport2", "stats": "les_moments", "mix": "les_mix", "vmix": "les_vmix",
+          "kmix": "les_mix"}
 COUNTED = ("slab_means", "slab_cloud_fraction", "variability_nudge", "les_advance", "les_thermo", "les_water_paths", "les_microphysics",
            "les_diffuse", "les_advect", "les_vadvect", "les_radiate", "les_moments", "les_qt_local", "les_buoyancy", "les_transport",
-           "les_transport2")
-MUTATIONS = ("step", "step0", "row_step", "nudge", "forcings", "set_field", "presf", "rhobf", "enable", "qt_forcings", "qt_kind", "readvect")
+           "les_transport2", "les_mix", "les_vmix")
+MUTATIONS = ("step", "step0", "row_step", "nudge", "forcings", "set_field", "presf", "rhobf", "enable", "qt_forcings", "qt_kind", "readvect",
+             "remix", "revmix", "z0m", "set_wind", "refused")
 OBSERVATIONS = ("profiles", "row", "field", "wp", "wp_means", "row_wp", "cloudfrac", "flux", "w", "courant", "counts", "lid", "pressure",
-                "stats", "row_stats")
+                "stats", "row_stats", "viscosity")
 KINDS = MUTATIONS + OBSERVATIONS + ("record",)
 NEEDS = {"qt_forcings": "qt", "qt_kind": "qt", "readvect": "buoyancy", "counts": "qt", "lid": "conservative", "pressure": "buoyancy",
-         "stats": "stats", "row_stats": "stats"}                  # the mode without which a kind of operation is never drawn
+         "stats": "stats", "row_stats": "stats", "remix": "mix", "revmix": "vmix", "z0m": "vmix", "set_wind": "mix", "refused": "mix",
+         "viscosity": "mix"}                                      # the mode without which a kind of operation is never drawn
 RELAUNCH = {"cloudfrac": {"slab_cloud_fraction"}, "wp_means": {"slab_means"}, "record": {"slab_means"}}      # property (b)
 PROFILE_KEYS = ("U", "V", "THL", "QT", "QL", "T", "QL_ice", "QR", "presf", "Rhobf", "Rain", "PS")
 ROW_GETTERS = {"get_profile_U": "U", "get_profile_V": "V", "get_profile_THL": "THL", "get_profile_QT": "QT", "get_profile_QL": "QL",
@@ -84,13 +99,24 @@ ALWAYS = ("U", "V", "THL", "QT", "QL")                            # the fields o
 # ceil(30 * 900 / (0.3 * 24000)) = 4, far below advection.MAX_SUBSTEPS (tests/test_ensemble_sequences_cpu.py checks every case)
 LATE_WAVE_SPEED = 24.0
 READVECT = dict(dx=0.8 * lvr.DX, cfl=0.3)
-DEFAULT = {"kind": "local", "limiter": "mc"}
+DEFAULT = {"kind": "local", "limiter": "mc", "cap": None, "stability": True, "drag": True, "dx": None}
+# K24 and K25.  The spacings of enable_mixing: None (those of the advection at the moment of the call, else advection.DX: with the
+# 200 m of the latter the cap binds in every step of DTS, with the 30 km of ``enable`` it does not), 250 m (binds) and 20 km (does
+# not); the caps of ``remix`` lie on both sides of either (tests/test_ensemble_sequences_cpu.py asserts that both occur)
+MIX_DX = (None, 250.0, 20000.0)
+MIX_CAPS = (None, 0.25)
+REMIX_CAPS = (1e-3, 0.1, 1.0)
+REMIX_PRANDTL = (0.5, 0.8)
+REVMIX = dict(k_bg=(0.05, 0.3), kv_cap=(50.0, 400.0))
+REFUSED = ("diffusion", "kmix", "vmix")
+Z0M = lvm.Z0M
 
 
 def valid(modes):
     m = set(modes)
     return m <= set(MODES) and ("advect" in m or "vertical" not in m) and ("vertical" in m or not m & {"buoyancy", "conservative"}) and \
-        ("conservative" in m or "order2" not in m)
+        ("conservative" in m or "order2" not in m) and ("mix" in m or not m & {"vmix", "kmix"}) and \
+        ("vmix" not in m or not m & {"diffuse", "kmix"}) and ("kmix" not in m or "diffuse" in m)
 
 
 def combinations():
@@ -106,6 +132,12 @@ def new_combinations(background):
             if valid(tuple(background) + c)]
 
 
+def mix_combinations(background):
+    """the non-empty subsets of the three mixing modes that are valid on top of ``background``, in a fixed order"""
+    return [tuple(background) + c for r in range(1, len(MIX_MODES) + 1) for c in itertools.combinations(MIX_MODES, r)
+            if valid(tuple(background) + c)]
+
+
 def name_of(modes):
     return "+".join(modes) or "plain"
 
@@ -115,9 +147,12 @@ def _mask(modes):
 
 
 def params(seed, modes):
-    """the kind of K19 and the limiter of K23 of the sequence ``generate(seed, modes)``: pure functions of (seed, modes)"""
+    """the kind of K19, the limiter of K23, the cap, the stability switch and the spacings of K24 (``dx``: dx = dy / 1.5, None for
+    the default) and the drag of K25 of the sequence ``generate(seed, modes)``: pure functions of (seed, modes)"""
     bits = bin(_mask(modes)).count("1")
-    return {"kind": qf.KINDS[(int(seed) + bits) % 2], "limiter": LIMITERS[(int(seed) + bits // 2) % 2]}
+    pick = numpy.random.default_rng([int(seed), _mask(modes), 24]).integers(0, 1 << 16, 4)
+    return {"kind": qf.KINDS[(int(seed) + bits) % 2], "limiter": LIMITERS[(int(seed) + bits // 2) % 2],
+            "cap": MIX_CAPS[int(pick[0]) % 2], "stability": bool(pick[1] % 2), "drag": bool(pick[2] % 2), "dx": MIX_DX[int(pick[3]) % 3]}
 
 
 # -- the ensemble ------------------------------------------------------------------------------------------------------------
@@ -140,11 +175,23 @@ def enable(ens, mode, modes, late=False, par=DEFAULT):
         ens.enable_qt_forcing(par["kind"])
     elif mode == "buoyancy":
         ens.enable_buoyancy(**(dict(wave_speed=LATE_WAVE_SPEED) if late else {}))
+    elif mode in ("mix", "kmix"):                                  # (kmix: enable_mixing once more, now with K15 behind it)
+        ens.enable_mixing(vertical=mode == "kmix", **mixing(par, **(dict(cs=0.2) if late else {})))
+    elif mode == "vmix":
+        ens.enable_vertical_mixing(drag=par["drag"], **(dict(k_bg=0.2, kv_cap=500.0) if late else {}))
     else:
         assert mode == "radiate", mode
         s = 0.9 if late else 1.0
         ens.enable_radiation(f0=s * rad.F0 * (1.0 + 0.05 * numpy.arange(n)), f1=rad.F1 * (1.0 + 0.1 * (numpy.arange(n) % 3)),
                              kappa=rad.KAPPA * (1.0 + 0.02 * (numpy.arange(n) % 5)))
+
+
+def mixing(par, **kw):
+    """the arguments of enable_mixing that ``params`` sets: the cap, the stability switch and, where given, the spacings"""
+    kw.update(cap=par["cap"], stability=par["stability"])
+    if par["dx"] is not None:
+        kw.update(dx=par["dx"], dy=1.5 * par["dx"])
+    return kw
 
 
 def _comes_with(mode, modes):
@@ -164,7 +211,7 @@ def build(engine, device, n, modes, late=(), par=DEFAULT):
     assert valid(modes) and set(late) <= set(LATE) & set(modes)
     spcpl.set_engine(engine)
     thermo = "thermo" in modes
-    cls = models.DeviceLESEnsemble if device else (lfr.HostThermoFullLESEnsemble if thermo else lfr.HostFullLESEnsemble)
+    cls = models.DeviceLESEnsemble if device else (lvm.HostThermoVmixLESEnsemble if thermo else lvm.HostVmixLESEnsemble)
     fs = [make_les_fields(ITOT, JTOT, NL, seed=60 + (i % 7)) for i in range(n)]
     stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
     gcm = models.BatchedSyntheticGCM(n + 4, NG, 21)
@@ -220,9 +267,14 @@ def generate(seed, modes, length=LENGTH):
     modes = tuple(m for m in MODES if m in modes)
     assert valid(modes), modes
     rng = numpy.random.default_rng([int(seed), _mask(modes)])
-    pending = [m for m in LATE if m in modes and rng.random() < 0.5]
+    pending = [m for m in LATE if m in modes and rng.random() < (0.35 if m in MIX_MODES else 0.5)]     # (the mixing more often from the start)
     if "buoyancy" in modes and "advect" in pending and "buoyancy" not in pending:
         pending.append("buoyancy")                                 # (K21 is enabled after, and for, the advection)
+    for m in ("vmix", "kmix"):                                     # (K25 and K24's vertical=True come behind enable_mixing, the latter behind K15)
+        if m in modes and m not in pending and any(a in pending for a in AFTER[m]):
+            pending.append(m)
+    par = params(seed, modes)
+    rough = [0, True]                                              # the z0m drawn; a step has followed the last one
     on = _on_at_start(modes, pending)
     stepped = set()                                                # modes that have seen a step since they were enabled
     lag = [False]                                                  # without thermo the QL field follows a new QT at the next step only
@@ -242,7 +294,15 @@ def generate(seed, modes, length=LENGTH):
 
     def todo():
         """the operations that are still to come whatever is drawn: the late enables and, with "qt", the forcing"""
-        return len(pending) + (1 if "qt" in modes and not handed[0] else 0)
+        return len(pending) + (1 if "qt" in modes and not handed[0] else 0) + z0m_todo()
+
+    def z0m_todo():
+        """a sequence of K25 with the drag holds two roughness lengths with a step behind each: the drag's key has something to miss"""
+        return {0: 3, 1: 1}.get(rough[0], 0) + (0 if rough[1] else 1) if "vmix" in modes and par["drag"] else 0
+
+    def refusable():
+        """the calls that have to raise now: K15 and vertical=True beside K25, K25 beside K15 or vertical=True"""
+        return [] if "mix" not in modes else (["diffusion", "kmix"] if "vmix" in on else []) + (["vmix"] if on & {"diffuse", "kmix"} else [])
 
     def mutation(kind=None, room=True):
         # (a nudge whose ql_av is not that of its QT is refused, "f(a) and f(b) must have different signs": none is drawn there)
@@ -252,20 +312,41 @@ def generate(seed, modes, length=LENGTH):
                                      ("rhobf", 1), ("enable", 2.5 if pending and room else 0), ("qt_forcings", 0 if "qt" not in modes or not room else 0.7 if handed[0] else 2),
                                      ("qt_kind", 0 if "qt" not in on else 2.5 if counted[0] else 0.5), ("readvect", 2.5 if again else 0),
                                      ("rhobf", 12 if wread[0] else 0),                               # (W and its moments are made of Rhobf, ...
-                                     ("presf", 2.5 if "buoyancy" in stepped else 0)])                # ... K21's profiles of presf: more of both there)
-        if kind == "step":
+                                     ("presf", 2.5 if "buoyancy" in stepped else 0),                 # ... K21's profiles of presf: more of both there)
+                                     ("remix", 2.5 if "mix" in on else 0), ("revmix", 6 if "vmix" in on else 0),
+                                     ("z0m", 0 if "vmix" not in on or not room else 2 if rough[1] else 0.5), ("set_wind", 1.5 if "mix" in modes else 0),
+                                     ("refused", 3 if refusable() else 0), ("rhobf", 1.5 if "vmix" in stepped else 0),
+                                     # (the mixing early, so that steps follow it, and more of what the older modes draw rarely)
+                                     ("enable", 8 if room and set(pending) & set(MIX_MODES) else 0), ("readvect", 4 if again and "mix" in on else 0),
+                                     ("qt_kind", 2 if "qt" in on and "mix" in modes else 0),
+                                     ("step", 3 if "kmix" in on else 0)])                            # (K15's key holds K24's viscosity: steps of one dt)
+        if kind == "step" and "kmix" in on and ops and _is_step(ops[-1]) and rng.random() < 0.6:
+            op = ("step", ops[-1][-1])                             # (K15's key holds K24's viscosity: two steps of one dt show a key without it)
+        elif kind == "step":
             op = ("step", DTS[int(rng.integers(len(DTS)))])
         elif kind == "row_step":
             op = ("row_step", small(), DTS[int(rng.integers(len(DTS)))])
         elif kind == "nudge":
             op = ("nudge", bool(rng.integers(2)), 1 + small())
-        elif kind in ("forcings", "cloudfrac", "qt_forcings"):
+        elif kind in ("forcings", "cloudfrac", "qt_forcings", "z0m"):
             op = (kind, small())
             handed[0] = handed[0] or kind == "qt_forcings"
+            if kind == "z0m":
+                rough[:] = [rough[0] + 1, False]
+        elif kind == "set_wind":
+            op = ("set_wind", ("U", "V")[int(rng.integers(2))], small())
+        elif kind == "remix":
+            op = ("remix", REMIX_CAPS[int(rng.integers(len(REMIX_CAPS)))], REMIX_PRANDTL[int(rng.integers(len(REMIX_PRANDTL)))])
+        elif kind == "revmix":
+            op = ("revmix", REVMIX["k_bg"][int(rng.integers(2))], REVMIX["kv_cap"][int(rng.integers(2))], bool(rng.integers(2)))
+        elif kind == "refused":
+            able = refusable()
+            op = ("refused", able[int(rng.integers(len(able)))])
         elif kind == "set_field":
             op = ("set_field", ("QT", "THL")[int(rng.integers(2))], small())
         elif kind == "enable":
-            able = [m for m in pending if not (m == "buoyancy" and "advect" in pending)]
+            able = [m for m in pending if not any(a in pending for a in AFTER.get(m, ()))]
+            able = [m for m in able if m in MIX_MODES] or able     # (the mixing first: the steps behind it are what its sequences are for)
             mode = able[int(rng.integers(len(able)))]
             pending.remove(mode)
             on.update(_comes_with(mode, modes))
@@ -279,11 +360,13 @@ def generate(seed, modes, length=LENGTH):
             op = (kind,)
         hint[0] = ("counts",) if kind == "qt_kind" else ("lid",) if kind == "readvect" and "conservative" in on else \
             ("stats", ("U", "W"), (("W", "THL"),)) if kind == "rhobf" and wread[0] else \
-            ("stats", ("W", "QT"), (("U", "W"),)) if kind == "step" and "stats" in modes and "vertical" in on else None
+            ("stats", ("W", "QT"), (("U", "W"),)) if kind == "step" and "stats" in modes and "vertical" in on else \
+            ("viscosity",) if kind in ("remix", "revmix") or (kind == "enable" and op[1] in MIX_MODES) else None
         wread[0] = wread[0] and kind == "rhobf"
-        dropped[0] = kind == "readvect"
+        dropped[0] = kind in ("readvect", "z0m")                  # (and a step behind a new roughness length: the drag's key)
         if _is_step(op):
             stepped.update(on)
+            rough[1] = True
             lag[0] = False
             counted[0] = counted[0] or ("qt" in on and handed[0])
         elif op[0] == "nudge" or op[:2] == ("set_field", "QT"):
@@ -307,7 +390,10 @@ def generate(seed, modes, length=LENGTH):
                              ("flux", 3 if "radiate" in stepped else 0), ("w", 3 if "vertical" in stepped else 0),
                              ("courant", 2 if "advect" in stepped else 0), ("counts", 3 if "qt" in on else 0),
                              ("lid", 3 if "conservative" in on else 0), ("pressure", 4 if "buoyancy" in on else 0),
-                             ("stats", 5 if "stats" in modes else 0), ("row_stats", 1.5 if "stats" in modes else 0)])
+                             ("stats", 5 if "stats" in modes else 0), ("row_stats", 1.5 if "stats" in modes else 0),
+                             ("viscosity", 3 if "mix" in modes else 0)] + ([] if "mix" not in modes else [
+                                 ("flux", 2 if "radiate" in stepped else 0), ("courant", 2 if "advect" in stepped else 0), ("counts", 4 if "qt" in on else 0),
+                                 ("lid", 2 if "conservative" in on else 0), ("stats", 3 if "stats" in modes else 0), ("row_stats", 3 if "stats" in modes else 0)]))
         if kind == "profiles":
             return ("profiles", subset(PROFILE_KEYS, 3))
         if kind == "row":
@@ -342,7 +428,7 @@ def generate(seed, modes, length=LENGTH):
     while len(ops) < length - 1:
         room = len(ops) < length - 3
         if todo() and length - 1 - len(ops) <= todo() + 1:         # a mode that is to be enabled late is, with a step behind it
-            ops.append(mutation("enable" if pending else "qt_forcings"))
+            ops.append(mutation("enable" if pending else "qt_forcings" if "qt" in modes and not handed[0] else "z0m" if rough[1] else "step"))
         elif hint[0] is not None and rng.random() < 0.7:           # (no mutation of the old modes leaves a hint: no draw there)
             ops.append(hint[0])
             wread[0] = wread[0] or (hint[0][0] == "stats" and "vertical" in stepped)
@@ -353,17 +439,22 @@ def generate(seed, modes, length=LENGTH):
             ops.append(observation())
         else:
             ops.append(mutation(room=room))
-    last = max([i for i, op in enumerate(ops) if op[0] in ("enable", "qt_forcings")], default=-1)
+    last = _last_forced(ops)
     if not any(_is_step(op) for op in ops[last + 1:]):
         assert last < len(ops) - 1
         ops[-1] = mutation("step")
     ops.append(("record",))
     assert not pending and todo() == 0
-    check_sequence(ops, modes, length)
+    check_sequence(ops, modes, length, par)
     return ops
 
 
-def check_sequence(ops, modes, length=None):
+def _last_forced(ops):
+    """the index of the last operation that wants a step behind it: an enable, the cloud-water forcing, the first two roughness lengths"""
+    return max([i for i, op in enumerate(ops) if op[0] in ("enable", "qt_forcings")] + [i for i, op in enumerate(ops) if op[0] == "z0m"][:2], default=-1)
+
+
+def check_sequence(ops, modes, length=None, par=None):
     """the conditions every sequence meets, whoever made it; returns the modes that are enabled late (an enable of the buoyancy
     behind a ``readvect`` is the second one)"""
     assert length is None or len(ops) == length, (len(ops), length)
@@ -375,8 +466,19 @@ def check_sequence(ops, modes, length=None):
     again = next((i for i, op in enumerate(ops) if op[0] == "readvect"), len(ops))
     late = [op[1] for i, op in enumerate(ops) if op[0] == "enable" and not (op[1] == "buoyancy" and i > again)]
     assert len(set(late)) == len(late) and set(late) <= set(LATE) & set(modes)
-    last = max([i for i, op in enumerate(ops) if op[0] in ("enable", "qt_forcings")], default=-1)
+    on = _on_at_start(modes, late)                                 # the mixing modes: each call meets the state it needs
+    for i, op in enumerate(ops):
+        if op[0] == "enable":
+            assert all(a in on for a in AFTER.get(op[1], ()) if a in modes and a != "advect"), "%r before what it needs" % (op,)
+            on |= _comes_with(op[1], modes)
+        assert op[0] != "remix" or "mix" in on, "remix before enable_mixing"
+        assert op[0] != "revmix" or "vmix" in on, "revmix before enable_vertical_mixing"
+        assert op[0] != "refused" or (op[1] in REFUSED and ("vmix" in on if op[1] != "vmix" else on & {"diffuse", "kmix"})), "%r would not raise" % (op,)
+    last = _last_forced(ops)
     assert any(_is_step(op) for op in ops[last + 1:]), "no step after the last enable"
+    if par is not None and "vmix" in modes and par["drag"]:
+        at = next((i for i, op in enumerate(ops) if op[0] == "z0m"), None)
+        assert at is not None and any(_is_step(op) for op in ops[:at]), "no roughness length behind a step in a sequence of K25 with the drag"
     if "qt" in modes and any(op[0] == "qt_forcings" for op in ops):
         at = next(i for i, op in enumerate(ops) if op[0] == "qt_forcings")
         assert any(_is_step(op) for op in ops[:at]), "no step before the cloud-water forcing is handed over"
@@ -449,6 +551,12 @@ def _number(x):
     return numpy.array([-1.0 if x is None else float(x)])
 
 
+def _viscosity(ens):
+    """K24's capped km, the viscosity K25 mixed by, the largest uncapped viscosity and whether the cap bound (None: -1)"""
+    return {"km": _optional(ens.get_eddy_viscosity_batched()), "kv": _optional(ens.get_vertical_viscosity_batched()),
+            "k max": _number(ens.mixing_k_max), "capped": _number(ens.mixing_capped)}
+
+
 def apply(ens, op, device, modes, on, par=DEFAULT):
     """``op`` on the device ensemble or on the twin; ``on``: the modes enabled now (updated).  Returns None for a mutation, a
     dict name -> host array for an observation"""
@@ -479,10 +587,25 @@ def apply(ens, op, device, modes, on, par=DEFAULT):
         enable(ens, "readvect", modes, par=par)
         on.discard("buoyancy")
         return None
-    if kind == "set_field":
+    if kind in ("set_field", "set_wind"):
         cur = numpy.array(host_of(ens.get_fields_batched(op[1])))
-        noise = numpy.random.default_rng(op[2]).normal(0, 1e-2 if op[1] == "QT" else 1e-4, cur.shape)
+        noise = numpy.random.default_rng(op[2]).normal(0, 1e-2 if op[1] in ("QT", "U", "V") else 1e-4, cur.shape)
         return ens.set_fields_batched(op[1], cur * (1.0 + noise))
+    if kind == "z0m":                                              # the roughness length of K25's drag
+        return ens.set_forcings_batched(Z0M_surf=Z0M * (0.5 + numpy.random.default_rng(op[1]).random(n)))
+    if kind == "remix":                                            # enable_mixing again: another cap and Prandtl number, vertical as it is
+        ens.enable_mixing(vertical="kmix" in on, **mixing(dict(par, cap=op[1]), prandtl=op[2]))
+        return None
+    if kind == "revmix":
+        ens.enable_vertical_mixing(k_bg=op[1], kv_cap=op[2], drag=op[3])
+        return None
+    if kind == "refused":
+        call = {"diffusion": ens.enable_diffusion, "kmix": lambda: ens.enable_mixing(vertical=True), "vmix": ens.enable_vertical_mixing}[op[1]]
+        try:
+            call()
+        except ValueError:
+            return None
+        raise AssertionError("%r was not refused" % (op,))
     if kind == "presf":
         ens.p["presf"] *= 1.002
         return None
@@ -534,6 +657,8 @@ def apply(ens, op, device, modes, on, par=DEFAULT):
         return _lid(ens)
     if kind == "pressure":
         return {"phi": _optional(ens.get_pressure_batched())}
+    if kind == "viscosity":
+        return _viscosity(ens)
     if kind == "stats":
         return _statistics(ens, device, op[1], op[2])
     if kind == "row_stats":
@@ -565,6 +690,8 @@ def apply(ens, op, device, modes, on, par=DEFAULT):
     if "buoyancy" in on:
         rec["phi"] = _optional(ens.get_pressure_batched())
         rec["wind change"] = _number(ens.buoyancy_wind_change)
+    if "mix" in modes:
+        rec.update(_viscosity(ens))
     if "stats" in modes:
         rec.update(_statistics(ens, device, None, None))
     for i in range(n):
@@ -593,6 +720,22 @@ class Counter:
         for e, name in self._wrapped:
             delattr(e, name)
         self._wrapped = []
+
+
+def check_step(calls, ens, on):
+    """the launches of one step of the device ensemble with the mixing: with K25 ``les_mix`` ran twice (the probe again under a cap
+    that never binds) exactly where the step's cap bound, else once, per ``les_vmix`` (one per engine that holds rows); with
+    K15 enabled as well nothing stands between ``les_mix`` and ``les_diffuse`` but, with vertical=True, one ``slab_means`` (of km) per
+    engine"""
+    if "vmix" in on:
+        per = 2 if ens.mixing_capped else 1
+        assert calls.count("les_vmix") >= 1 and calls.count("les_mix") == per * calls.count("les_vmix"), \
+            "mixing_capped is %r and the step launched %r" % (ens.mixing_capped, [c for c in calls if c in ("les_mix", "les_vmix")])
+    elif "mix" in on:
+        assert "les_mix" in calls and "les_vmix" not in calls, calls
+    if "mix" in on and "diffuse" in on:
+        between = calls[max(i for i, c in enumerate(calls) if c == "les_mix") + 1:calls.index("les_diffuse")]
+        assert between == (["slab_means"] * calls.count("les_mix") if "kmix" in on else []), calls
 
 
 def check_launched(calls, modes):
@@ -639,11 +782,12 @@ def _of_the_own_w(ens, got, want, row=None):
 
 def replay(ops, modes, n, engine_for_twin, engine_for_device, what="", par=DEFAULT):
     """the list ``ops`` on the twin (NumPy fields; its nudge runs on ``engine_for_twin``) and on the device ensemble on
-    ``engine_for_device``; every observation compared, properties (a), (b) and (c) checked on the way.  ``par``: the kind of K19
-    and the limiter of K23 (``params``).  An AssertionError names ``what``, the modes, the index of the operation and the
+    ``engine_for_device``; every observation compared, properties (a), (b) and (c) checked on the way.  ``par``: the kind of K19,
+    the limiter of K23 and the parameters of K24 and K25 (``params``).  An AssertionError names ``what``, the modes, the index of
+    the operation and the
     operations up to it.  Returns the launches of the device side."""
     modes = tuple(m for m in MODES if m in modes)
-    late = check_sequence(ops, modes)
+    late = check_sequence(ops, modes, par=par)
 
     def told(i, side, e):
         return AssertionError("%s modes %s n %d, operation %d %r on the %s: %s\nthe operations up to it (ensemble_sequences.replay(ops, %r, %d, ..., par=%r)):\n%r"
@@ -686,6 +830,8 @@ def replay(ops, modes, n, engine_for_twin, engine_for_device, what="", par=DEFAU
                     cached = {k for k in cached if not _holds_w(k)}
                 else:
                     cached = set()
+                if _is_step(op) and "mix" in on and len(counter.calls) > mark:
+                    check_step(counter.calls[mark:], ens, on)
             except AssertionError as e:
                 raise told(i, "device ensemble", e) from e
             done += 1

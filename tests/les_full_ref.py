@@ -1,5 +1,6 @@
-"""The top of the chain of host twins of models.DeviceLESEnsemble and of the oracle-backed engines: every opt-in mode in one
-class, for tests/ensemble_sequences.py.  Nothing is defined a second time: the mixins of tests/les_qt_local_ref.py (K19),
+"""The host twins of models.DeviceLESEnsemble and the oracle-backed engine with every opt-in mode up to K23 and the statistics in
+one class.  The twins of K24 (tests/les_mix_ref.py) and, on those, of K25 (tests/les_vmix_ref.py: the top of the chain, what
+tests/ensemble_sequences.py runs) stand on these.  Nothing is defined a second time: the mixins of tests/les_qt_local_ref.py (K19),
 tests/les_transport2_ref.py (K23, and K22 below it) and tests/les_buoyancy_ref.py (K21, on the twins of K18 and everything
 before it) stay the definitions; this module composes them and adds what only a sequence of operations needs:
 

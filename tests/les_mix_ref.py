@@ -601,6 +601,7 @@ class _HostMix:
                             dx=dx if dx is not None else adv_par["dx"] if adv_par else adv.DX,
                             dy=dy if dy is not None else adv_par["dy"] if adv_par else adv.DY)
         self._km = self._mix_kd = None
+        self.mixing_k_max = self.mixing_capped = None             # (a second call forgets the last step of the earlier one)
 
     def _mix(self, dt):
         f, par = self.fields3d, self.mix_par

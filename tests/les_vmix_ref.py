@@ -558,6 +558,10 @@ class _HostVmix:
         self.vmix_par = dict(kv_cap=vm.KV_CAP if kv_cap is None else kv_cap, k_bg=vm.K_BG if k_bg is None else k_bg, drag=drag)
         self._kv = None
 
+    def enable_mixing(self, *a, **kw):
+        super().enable_mixing(*a, **kw)
+        self._kv = None                                            # (a second call forgets the viscosity of the earlier one's last step)
+
     def enable_diffusion(self, *a, **kw):
         if self.vmix_par is not None:
             raise ValueError("a step has one vertical diffusion")

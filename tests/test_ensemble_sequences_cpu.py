@@ -1,8 +1,8 @@
 """Random operation sequences of models.DeviceLESEnsemble on oracle-backed engines against its NumPy twin, without a GPU
-(the body: tests/ensemble_sequences.py): all 48 valid combinations of the six old modes and 55 with the five new ones (K19
-to K23 and the statistics of K20) with two seeds, row blocks 1 + 1 + 0 of a MultiDeviceEngine, the fused K11 step in front of
-every later stage, sequences of 30 operations, the digest of the old sequences (they are what they were before the new modes),
-the named regression sequences of what the sequences found, and the state mutants: faults of the ensemble's caches, patched in, that a committed sequence has to notice.
+(the body: tests/ensemble_sequences.py): all 48 valid combinations of the six old modes, 55 with the five of K19 to K23 and the
+statistics of K20 and 14 with the three mixing modes (K24, K25 and K24 with vertical=True) with two seeds, row blocks 1 + 1 + 0 of
+a MultiDeviceEngine, the fused K11 step in front of every later stage, sequences of 30 operations, the two digests of the older
+sequences (they are what they were before the modes that came after them), the named regression sequences of what the sequences found, and the state mutants: faults of the ensemble's caches, patched in, that a committed sequence has to notice.
 
 Which committed sequence (seed, modes; n = 3 on one engine) notices which state mutant:
   1  _drop_water_paths does nothing                              seed 1 plain, seed 1 thermo
@@ -24,10 +24,24 @@ Which committed sequence (seed, modes; n = 3 on one engine) notices which state 
   16 enable_advection keeps the buoyancy enabled                 seed 2 advect+vertical+buoyancy, seed 2 advect+vertical+buoyancy+conservative+order2
   17 a new Rhobf keeps the host copies of the moments of W       seed 1 and seed 2 advect+vertical+buoyancy+stats
   18 the key of the statistics' W ignores Rhobf                  seed 1 and seed 2 advect+vertical+buoyancy+stats
+  19 _mix does not swap the fields with _mix_spare               seed 1 mix, seed 2 mix+vmix
+  20 _mix_coef's key ignores dt                                  seed 1 mix, seed 2 mix+vmix
+  21 _vmix_coef's key ignores Rhobf                              seed 1 qt+stats+mix+vmix, seed 2 advect+vertical+buoyancy+stats+mix+vmix
+  22 _vmix_drag keeps the z0m of its first upload                seed 2 mix+vmix, seed 1 advect+vertical+buoyancy+conservative+order2+mix+vmix
+  23 _mix never runs the uncapped probe: K25 mixes by the        seed 1 and seed 2 mix+vmix
+     capped km
+  24 the probe reads f["U"], f["V"] after the swap               seed 1 and seed 2 mix+vmix
+  25 enable_mixing keeps _mix_km of the earlier call             seed 1 mix, seed 2 diffuse+mix+kmix
+  26 _diffuse keeps the kd of its first upload with one          seed 1 diffuse+mix+kmix, seed 2 diffuse+advect+vertical+buoyancy+conservative+order2+mix+kmix
 (test_state_mutants_fail_a_committed_sequence asserts every line of this table.  Mutant 11 takes the call of _follow_fields
 with the assignment: the assignment alone is redundant, every path behind K19 ends in _follow_fields, which sets both.  Mutant
 12 reads the presf of the last upload into the key AND the profiles; a key that only COMPARES without presf never shows,
-because the slab means in the same key change with every step.)"""
+because the slab means in the same key change with every step.  Mutants 22 and 26 are widened the same way: a key that only
+compares without z0m, or without kd, shows in ONE committed sequence each, because dt stands in the same key and two steps in a
+row seldom share it; so mutant 22 reads the z0m of the first upload into the key and the drag, mutant 26 the kd of the first
+upload with one into the key and the profiles.  Mutant 23 leaves the launch out and hands K24's capped km to K25; what fails
+first is the count of les_mix launches of a step whose cap bound.  _mix's own _drop_statistics and _drop_water_paths are followed
+by those of _follow_fields in every path and are no mutants of their own.)"""
 import hashlib
 import inspect
 import itertools
@@ -42,10 +56,10 @@ from sp_coupler_amd import buoyancy as buo
 from sp_coupler_amd import device_les, models, spcpl
 from sp_coupler_amd.multi import MultiDeviceEngine
 from tests import ensemble_sequences as es
-from tests import les_full_ref as lfr
 from tests import les_micro_ref as lmr
 from tests import les_thermo_ref as ltr
 from tests import les_vadvect_ref as lvr
+from tests import les_vmix_ref as lvm
 from tests import slab_ref
 
 SEEDS = (1, 2)
@@ -57,11 +71,23 @@ NEW_COMBINATIONS = es.new_combinations(("advect", "vertical")) + es.new_combinat
     [bg + c for bg in ((), ("thermo",), ("diffuse", "micro")) for c in (("qt",), ("stats",), ("qt", "stats"))]
 ALL_COMBINATIONS = COMBINATIONS + NEW_COMBINATIONS
 NEW_SIX = [("advect", "vertical", "qt", "conservative"), ("advect", "vertical", "buoyancy", "order2", "conservative"), ("advect", "vertical", "stats"),
-           ("thermo", "qt", "stats"), ("diffuse", "micro", "qt"), es.MODES]
+           ("thermo", "qt", "stats"), ("diffuse", "micro", "qt"), es.ELEVEN]
 NEW_SIX = [tuple(m for m in es.MODES if m in c) for c in NEW_SIX]
 #: sha256 over repr((seed, modes, generate(seed, modes, length))) of the 48 old combinations, seeds 1, 2 and 3 at length 14 and seed
 #: 101 at length 30, computed from tests/ensemble_sequences.py as it was before the five new modes
 OLD_SEQUENCES = "d5ab020b0faa71f622d7b6a095a2e44e9c9e763bb95676f71aad60aaf78766eb"
+#: the same over the 55 NEW_COMBINATIONS, computed from tests/ensemble_sequences.py as it was before the three mixing modes
+NEW_SEQUENCES = "ece619774f522f90b8fe31b246e58ff697b4d110f57a4c5aa31ef29ab48e4ae8"
+TRANSPORT = ("advect", "vertical", "conservative", "order2", "buoyancy")
+MOIST = ("thermo", "micro", "radiate", "qt", "stats")
+#: K24, K25 and K24 with vertical=True: every valid non-empty subset of the three over the smallest background that takes it and
+#: over the whole transport with K21 (the diffusion joins where vertical=True needs it; mix alone meets it as well: K15 behind K24
+#: without its viscosity, and the refusal of K25 beside it), mix and mix+vmix over the moist modes with K19 and K20, and over two
+#: smaller backgrounds in which the operations of K19, K20 and K21 are not crowded out by the late enables: 14 combinations
+MIX_COMBINATIONS = [tuple(m for m in es.MODES if m in c) for bg in ((), ("diffuse",), TRANSPORT, TRANSPORT + ("diffuse",), MOIST, ("qt", "stats"),
+                                                                      ("advect", "vertical", "buoyancy", "stats")) for c in es.mix_combinations(bg)]
+MIX_SIX = [("mix",), ("mix", "vmix"), ("diffuse", "mix", "kmix"), TRANSPORT + ("mix", "vmix"), TRANSPORT + ("diffuse", "mix", "kmix"), MOIST + ("mix", "vmix")]
+MIX_SIX = [tuple(m for m in es.MODES if m in c) for c in MIX_SIX]
 
 
 @pytest.fixture(autouse=True)
@@ -73,7 +99,7 @@ def _restore():
 
 
 def _oracle():
-    return lfr.FullOracleEngine()
+    return lvm.VmixOracleEngine()
 
 
 def test_the_combinations_and_the_generator():
@@ -104,6 +130,16 @@ def test_the_old_sequences_are_unchanged():
         for seed, length in ((1, 14), (2, 14), (3, 14), (101, 30)):
             h.update(repr((seed, modes, es.generate(seed, modes, length))).encode())
     assert h.hexdigest() == OLD_SEQUENCES
+
+
+def test_the_sequences_of_the_eleven_modes_are_unchanged():
+    """the same for the 55 combinations with K19 to K23 and the statistics, now that the three mixing modes stand behind them
+    (CAUGHT_BY rows 9 to 18 depend on it)"""
+    h = hashlib.sha256()
+    for modes in NEW_COMBINATIONS:
+        for seed, length in ((1, 14), (2, 14), (3, 14), (101, 30)):
+            h.update(repr((seed, modes, es.generate(seed, modes, length))).encode())
+    assert h.hexdigest() == NEW_SEQUENCES
 
 
 def test_the_new_combinations_and_their_generator():
@@ -170,6 +206,76 @@ def test_new_modes_in_longer_sequences(modes):
     es.run(_oracle(), _oracle(), 101, modes, 3, length=30)
 
 
+def _capped_steps(seed, modes, length=es.LENGTH):
+    """the twin's ``mixing_capped`` of every step of the sequence that K25 follows"""
+    ops, par = es.generate(seed, modes, length), es.params(seed, modes)
+    late = es.check_sequence(ops, modes, par=par)
+    twin, on, out = es.build(_oracle(), False, 3, modes, late, par), es._on_at_start(modes, late), []
+    for op in ops:
+        before = twin.model_time
+        es.apply(twin, op, False, modes, on, par)
+        if es._is_step(op) and "vmix" in on and twin.model_time > before:
+            out.append(bool(twin.mixing_capped))
+    return out
+
+
+def test_the_mixing_combinations_and_their_generator():
+    """14 combinations; over the committed cases every kind of operation occurs that their modes allow; the generator and the
+    parameters are pure functions of (seed, modes); with K25 every pair of {stability on, off} x {drag on, off} occurs, the
+    spacings of enable_mixing are defaulted and given, and there are steps whose cap binds and steps whose cap does not (one
+    sequence and more holds both: the switch between the two viscosity buffers); a sequence of K25 with the drag holds a
+    roughness length between two steps; each of the three refusals and a late enable of each mode occur"""
+    assert len(MIX_COMBINATIONS) == len(set(MIX_COMBINATIONS)) == 14 and not set(MIX_COMBINATIONS) & set(ALL_COMBINATIONS)
+    assert all(es.valid(c) and "mix" in c for c in MIX_COMBINATIONS) and all(c in MIX_COMBINATIONS for c in MIX_SIX) and len(set(MIX_SIX)) == 6
+    assert es.mix_combinations(()) == [("mix",), ("mix", "vmix")] and es.mix_combinations(("diffuse",)) == [("diffuse", "mix"), ("diffuse", "mix", "kmix")]
+    assert not es.valid(("mix", "vmix", "kmix", "diffuse")) and not es.valid(("vmix",)) and not es.valid(("mix", "kmix")) and not es.valid(("diffuse", "mix", "vmix"))
+    cases = [(seed, modes) for modes in MIX_COMBINATIONS for seed in SEEDS]
+    es.check_kinds(cases)
+    for modes in MIX_COMBINATIONS:
+        for seed, length in [(s, es.LENGTH) for s in SEEDS] + [(101, 30)]:
+            ops = es.generate(seed, modes, length)
+            assert ops == es.generate(seed, modes, length) and len(ops) == length and es.params(seed, modes) == es.params(seed, modes)
+    par = {case: es.params(*case) for case in cases}
+    with_k25 = [case for case in cases if "vmix" in case[1]]
+    assert {(par[c]["stability"], par[c]["drag"]) for c in with_k25} == {(s, d) for s in (True, False) for d in (True, False)}
+    assert {par[c]["dx"] for c in cases} == set(es.MIX_DX) and {par[c]["cap"] for c in cases} == set(es.MIX_CAPS)
+    capped = [_capped_steps(*c) for c in with_k25]
+    assert all(capped) and any(True in c and False in c for c in capped) and any(all(c) for c in capped) and any(not any(c) for c in capped)
+    for seed, modes in with_k25:
+        ops = es.generate(seed, modes)
+        assert par[seed, modes]["drag"] <= any(op[0] == "z0m" for op in ops)
+    seen = [op for seed, modes in cases for op in es.generate(seed, modes)]
+    assert {op[1] for op in seen if op[0] == "refused"} == set(es.REFUSED)
+    assert set(es.MIX_MODES) <= {op[1] for op in seen if op[0] == "enable"}
+
+
+@pytest.mark.parametrize("modes", MIX_COMBINATIONS, ids=es.name_of)
+def test_every_mixing_combination(modes):
+    for seed in SEEDS:
+        es.run(_oracle(), _oracle(), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", MIX_SIX, ids=es.name_of)
+def test_mixing_on_row_blocks_with_an_empty_device(modes):
+    """three oracle engines, n = 2: blocks 1 + 1 + 0 (one les_vmix per engine that holds rows, les_mix once or twice per each)"""
+    for seed in SEEDS:
+        multi = MultiDeviceEngine([_oracle() for _ in range(3)], min_cols_per_device=1)
+        es.run(_oracle(), multi, seed, modes, 2)
+
+
+@pytest.mark.parametrize("modes", MIX_SIX, ids=es.name_of)
+def test_mixing_behind_the_fused_step(monkeypatch, modes):
+    """FUSED_MIN_LES patched to 0: K11 steps the fields, K24 and K25 follow"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    for seed in SEEDS:
+        calls = es.run(_oracle(), _oracle(), seed, modes, 3)
+        assert "les_advance" in calls
+
+
+@pytest.mark.parametrize("modes", MIX_SIX, ids=es.name_of)
+def test_mixing_in_longer_sequences(modes):
+    es.run(_oracle(), _oracle(), 101, modes, 3, length=30)
+
 
 @pytest.mark.parametrize("modes", SIX, ids=es.name_of)
 def test_row_blocks_with_an_empty_device(modes):
@@ -211,15 +317,54 @@ W_STATISTICS_AFTER_RHOBF = (("advect", "vertical", "stats"), [("forcings", 1), (
 ONLY_W_STATISTICS_AFTER_RHOBF = (("advect", "vertical", "stats"), [
     ("forcings", 1), ("step", 300.0), ("stats", ("U", "W"), (("W", "THL"), ("THL", "QT"))), ("rhobf",), ("stats", ("U",), (("THL", "QT"),)),
     ("row_stats", 2, ("U", "W"), (("W", "THL"),)), ("record",)])
-REGRESSIONS = {"unobserved first step": UNOBSERVED_FIRST_STEP, "row after nudge": ROW_AFTER_NUDGE, "row after set_fields": ROW_AFTER_SET_FIELDS,
+#: enable_mixing() a second time forgets the last step of the first: both viscosities, mixing_k_max and mixing_capped are None
+#: until the next step (the twin kept them; a third element: the parameters that differ from es.DEFAULT)
+SECOND_ENABLE_MIXING = (("mix", "vmix"), [("step", 300.0), ("remix", 0.1, 0.8), ("viscosity",), ("z0m", 3), ("step", 300.0), ("viscosity",), ("record",)])
+#: enable_vertical_mixing() behind a step of K24 whose cap did not bind: there is no viscosity K25 mixed by before its first step
+#: (the device ensemble returned K24's km there, and None where the cap had bound)
+LATE_VERTICAL_MIXING = (("mix", "vmix"), [("step", 300.0), ("enable", "vmix"), ("viscosity",), ("z0m", 3), ("step", 300.0), ("viscosity",), ("record",)],
+                        {"dx": 20000.0})
+#: ... and the same behind enable_vertical_mixing() called again
+SECOND_ENABLE_VERTICAL_MIXING = (("mix", "vmix"), [("step", 300.0), ("z0m", 3), ("revmix", 0.3, 400.0, True), ("viscosity",), ("step", 300.0), ("viscosity",),
+                                                    ("record",)], {"dx": 20000.0})
+REGRESSIONS = {"second enable_mixing": SECOND_ENABLE_MIXING, "late vertical mixing": LATE_VERTICAL_MIXING,
+               "second enable_vertical_mixing": SECOND_ENABLE_VERTICAL_MIXING, "unobserved first step": UNOBSERVED_FIRST_STEP, "row after nudge": ROW_AFTER_NUDGE, "row after set_fields": ROW_AFTER_SET_FIELDS,
                "row water path after Rhobf": ROW_WATER_PATH_AFTER_RHOBF, "late microphysics after presf": LATE_MICRO_AFTER_PRESF,
                "statistics of W after Rhobf": W_STATISTICS_AFTER_RHOBF, "only the statistics of W after Rhobf": ONLY_W_STATISTICS_AFTER_RHOBF}
 
 
 @pytest.mark.parametrize("name", sorted(REGRESSIONS))
 def test_named_regressions(name):
-    modes, ops = REGRESSIONS[name]
-    es.replay(ops, modes, 3, _oracle(), _oracle(), what=name)
+    modes, ops, par = _regression(name)
+    es.replay(ops, modes, 3, _oracle(), _oracle(), what=name, par=par)
+
+
+def _regression(name):
+    modes, ops = REGRESSIONS[name][:2]
+    return modes, ops, dict(es.DEFAULT, **(REGRESSIONS[name][2] if len(REGRESSIONS[name]) > 2 else {}))
+
+
+def test_without_the_twin_fix_a_second_enable_mixing_keeps_the_last_step(monkeypatch):
+    inner = lvm._HostVmix.enable_mixing
+
+    def old(self, *a, **kw):
+        kept = self.mixing_k_max, self.mixing_capped, self._kv
+        inner(self, *a, **kw)
+        self.mixing_k_max, self.mixing_capped, self._kv = kept
+    monkeypatch.setattr(lvm._HostVmix, "enable_mixing", old)
+    modes, ops, par = _regression("second enable_mixing")
+    with pytest.raises(AssertionError, match=r"operation 2 .*kv"):
+        es.replay(ops, modes, 3, _oracle(), _oracle(), par=par)
+
+
+@pytest.mark.parametrize("name", ["late vertical mixing", "second enable_vertical_mixing"])
+def test_without_the_flag_k24s_viscosity_is_taken_for_that_of_k25(monkeypatch, name):
+    """get_vertical_viscosity_batched() as it was: K24's km of a step that ran before enable_vertical_mixing()"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "get_vertical_viscosity_batched",
+                        _edited("get_vertical_viscosity_batched", "self.vertical_mixing and self._vmix_stepped", "self.vertical_mixing"))
+    modes, ops, par = _regression(name)
+    with pytest.raises(AssertionError, match=r"operation 3 .*kv" if name.startswith("second") else r"operation 2 .*kv"):
+        es.replay(ops, modes, 3, _oracle(), _oracle(), par=par)
 
 
 def test_without_the_twin_fix_the_unobserved_first_step_fails(monkeypatch):
@@ -319,6 +464,17 @@ MUTANTS = {
     16: ("enable_advection", "self.buoyancy = False", "pass"),
     17: ("_drop_w_statistics", "self._stats_host = {kk: a for kk, a in self._stats_host.items() if not holds(kk[1])}", "pass"),
     18: ("_statistics_fields", "_kept(old, key, ", "_kept(old, key if old is None else old[0], "),
+    19: ("_mix", "        f[k], spare[k] = spare[k], f[k]\n", "        pass\n"),
+    20: ("_mix", "_kept(self._mix_coef, ckey, ", "_kept(self._mix_coef, ckey if self._mix_coef is None else self._mix_coef[0][:1] + ckey[1:], "),
+    21: ("_vmix", "_kept(self._vmix_coef, key, ", "_kept(self._vmix_coef, key if self._vmix_coef is None else key[:4] + self._vmix_coef[0][4:5] + key[5:], "),
+    22: ("_vmix", "_f64(numpy.asarray(self.tend[self.VMIX_Z0M], dtype=numpy.float64).reshape(self.n), ",
+         "_f64(numpy.asarray(self.tend[self.VMIX_Z0M], dtype=numpy.float64).reshape(self.n) if self._vmix_drag is None else self._vmix_drag[0][1], "),
+    23: ("_mix", "eng.les_mix({}, {}, u, v, theta, gx, gy, gz, bz if theta is not None else None, l2, self._vmix_huge, self._vmix_km, {}, {}, kmax=False)",
+         "self._vmix_km = self._mix_km"),
+    24: ("_mix", "eng.les_mix({}, {}, u, v, theta, ", 'eng.les_mix({}, {}, f["U"], f["V"], theta, '),
+    25: ("enable_mixing", "self._mix_prof = self._mix_coef = self._mix_km = self._mix_kd = None", "self._mix_prof = self._mix_coef = self._mix_kd = None"),
+    26: ("_diffuse", "        key += (kd,)\n",
+         "        kd = kd if self._diffuse_prof is None or len(self._diffuse_prof[0]) == len(key) else self._diffuse_prof[0][-1]\n        key += (kd,)\n"),
 }
 AV = ("advect", "vertical")
 CAUGHT_BY = {
@@ -340,6 +496,14 @@ CAUGHT_BY = {
     16: [(2, AV + ("buoyancy",)), (2, AV + ("buoyancy", "conservative", "order2"))],
     17: [(1, AV + ("buoyancy", "stats")), (2, AV + ("buoyancy", "stats"))],
     18: [(1, AV + ("buoyancy", "stats")), (2, AV + ("buoyancy", "stats"))],
+    19: [(1, ("mix",)), (2, ("mix", "vmix"))],
+    20: [(1, ("mix",)), (2, ("mix", "vmix"))],
+    21: [(1, ("qt", "stats", "mix", "vmix")), (2, AV + ("buoyancy", "stats", "mix", "vmix"))],
+    22: [(2, ("mix", "vmix")), (1, AV + ("buoyancy", "conservative", "order2", "mix", "vmix"))],
+    23: [(1, ("mix", "vmix")), (2, ("mix", "vmix"))],
+    24: [(1, ("mix", "vmix")), (2, ("mix", "vmix"))],
+    25: [(1, ("mix",)), (2, ("diffuse", "mix", "kmix"))],
+    26: [(1, ("diffuse", "mix", "kmix")), (2, ("diffuse",) + AV + ("buoyancy", "conservative", "order2", "mix", "kmix"))],
 }
 
 
@@ -351,9 +515,11 @@ def plant(monkeypatch, mutant):
 @pytest.mark.parametrize("mutant", sorted(MUTANTS))
 def test_state_mutants_fail_a_committed_sequence(monkeypatch, mutant):
     """each fault of the ensemble's caches, patched into DeviceLESEnsemble, fails the sequences the table names (all of them
-    among those of test_every_mode_combination, those of the mutants 9 and up among those of test_every_new_mode_combination,
-    two and more each); the same sequences pass without it"""
-    assert all(seed in SEEDS and modes in (COMBINATIONS if mutant <= 8 else NEW_COMBINATIONS) for seed, modes in CAUGHT_BY[mutant])
+    among those of test_every_mode_combination, those of the mutants 9 to 18 among those of test_every_new_mode_combination,
+    those of the mutants 19 and up among those of test_every_mixing_combination, two and more each); the same sequences pass
+    without it"""
+    assert all(seed in SEEDS and modes in (COMBINATIONS if mutant <= 8 else NEW_COMBINATIONS if mutant <= 18 else MIX_COMBINATIONS)
+               for seed, modes in CAUGHT_BY[mutant])
     assert len(set(CAUGHT_BY[mutant])) == len(CAUGHT_BY[mutant]) >= (1 if mutant <= 8 else 2)
     for seed, modes in CAUGHT_BY[mutant]:
         es.run(_oracle(), _oracle(), seed, modes, 3)

@@ -4,9 +4,11 @@ in tests/test_ensemble_sequences_cpu.py).  The device ensemble runs on Engine("c
 twin computes in NumPy on the host (its variability nudge alone goes through an engine).  Everything is bit-equality
 (gpu_util.assert_bits), W alone keeps the bound of les_vadvect_ref.check_w, and the moments that hold W are compared bit for
 bit with NumPy's moments of the device's own W: there is no tolerance to choose and nothing is measured.  Every case runs two
-seeds; nothing but the ensemble is mutated.  Twelve cases of the six old modes and twelve with the five new ones (K19 to K23 and
-the statistics of K20); four of each through two and three engines that share the card and behind the fused step.  4 x 5 x 20 at
-n = 3 is the smallest shape at which every cache and launch switch of the ensemble is still reached."""
+seeds; nothing but the ensemble is mutated.  Twelve cases of the six old modes, twelve with the five of K19 to K23 and the
+statistics of K20 and twelve with the three mixing modes (K24, K25, K24 with vertical=True); four of each through two and three
+engines that share the card and behind the fused step.  4 x 5 x 20 at n = 3 is the smallest shape at which every cache and
+launch switch of the ensemble is still reached; K24's row walk and K25's LDS tiles have their edge shapes in
+tests/test_les_mix_gpu.py and tests/test_les_vmix_gpu.py."""
 import numpy
 import pytest
 import torch
@@ -28,8 +30,18 @@ AV = ("advect", "vertical")
 #: each new mode alone over its smallest valid background, the pairs that share state (K19's QT under K22, K21 in front of K23, W
 #: and its moments, K19 dropping K20's cache), K12 on both sides of K19, K19 and K21 under the statistics, and everything at once
 NEW_TWELVE = [("qt",), AV + ("buoyancy",), AV + ("conservative",), AV + ("conservative", "order2"), ("stats",), AV + ("qt", "conservative"),
-              AV + ("buoyancy", "conservative", "order2"), AV + ("stats",), ("qt", "stats"), ("thermo", "qt"), AV + ("qt", "buoyancy", "stats"), es.MODES]
-NEW_FOUR = [es.MODES, AV + ("qt", "conservative"), AV + ("buoyancy", "conservative", "order2"), ("qt", "stats")]
+              AV + ("buoyancy", "conservative", "order2"), AV + ("stats",), ("qt", "stats"), ("thermo", "qt"), AV + ("qt", "buoyancy", "stats"), es.ELEVEN]
+NEW_FOUR = [es.ELEVEN, AV + ("qt", "conservative"), AV + ("buoyancy", "conservative", "order2"), ("qt", "stats")]
+TRANSPORT = ("advect", "vertical", "conservative", "order2", "buoyancy")
+MOIST = ("thermo", "micro", "radiate", "qt", "stats")
+#: K24 alone, with K25, in front of K15 without and with its viscosity (vertical=True); the same behind the split advection (the
+#: default spacings are the advection's) and behind the whole transport with K21; K25 with K12 and K18, with every moist mode,
+#: with K19 and K20 alone, and with K21 under the statistics
+MIX_TWELVE = [("mix",), ("mix", "vmix"), ("diffuse", "mix"), ("diffuse", "mix", "kmix"), AV + ("mix",), AV + ("mix", "vmix"), TRANSPORT + ("mix", "vmix"),
+              ("diffuse",) + TRANSPORT + ("mix", "kmix"), ("thermo", "radiate", "mix", "vmix"), MOIST + ("mix", "vmix"), ("qt", "stats", "mix", "vmix"),
+              AV + ("buoyancy", "stats", "mix", "vmix")]
+MIX_TWELVE = [tuple(m for m in es.MODES if m in c) for c in MIX_TWELVE]
+MIX_FOUR = [MIX_TWELVE[i] for i in (1, 3, 6, 9)]
 
 
 @pytest.fixture(autouse=True)
@@ -55,6 +67,12 @@ def test_the_cases_are_valid_combinations():
     par = [(modes, es.params(seed, modes)) for modes in NEW_TWELVE for seed in SEEDS]
     assert {p["kind"] for modes, p in par if "qt" in modes} == {"local", "strong"}
     assert {p["limiter"] for modes, p in par if "order2" in modes} == {"mc", "none"}
+    assert len(MIX_TWELVE) == len(set(MIX_TWELVE)) == 12 and all(es.valid(c) and "mix" in c for c in MIX_TWELVE) and len(set(MIX_FOUR)) == 4
+    assert {"vmix" in c for c in MIX_FOUR} == {"kmix" in c for c in MIX_FOUR} == {True, False}
+    es.check_kinds([(seed, modes) for modes in MIX_TWELVE for seed in SEEDS])
+    par = [es.params(seed, modes) for modes in MIX_TWELVE for seed in SEEDS if "vmix" in modes]
+    assert {(p["stability"], p["drag"]) for p in par} == {(s, d) for s in (True, False) for d in (True, False)}
+    assert {p["dx"] for p in par} == set(es.MIX_DX)
 
 
 @pytest.mark.parametrize("modes", TWELVE, ids=es.name_of)
@@ -108,6 +126,34 @@ def test_new_modes_on_three_engines_sharing_the_card_one_without_rows(modes):
 @pytest.mark.parametrize("modes", NEW_FOUR, ids=es.name_of)
 def test_new_modes_behind_the_fused_step(monkeypatch, modes):
     """FUSED_MIN_LES patched to 0: K11 steps the fields and K19 reads its cached means"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    for seed in SEEDS:
+        assert "les_advance" in es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", MIX_TWELVE, ids=es.name_of)
+def test_sequences_of_the_mixing_modes_equal_the_twin(modes):
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", MIX_FOUR, ids=es.name_of)
+def test_mixing_on_two_engines_sharing_the_card(modes):
+    """n = 5: Sharded row blocks 3 + 2, each engine on its own stream"""
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), _sharing(2), seed, modes, 5)
+
+
+@pytest.mark.parametrize("modes", MIX_FOUR, ids=es.name_of)
+def test_mixing_on_three_engines_sharing_the_card_one_without_rows(modes):
+    """n = 2: row blocks 1 + 1 + 0"""
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), _sharing(3), seed, modes, 2)
+
+
+@pytest.mark.parametrize("modes", MIX_FOUR, ids=es.name_of)
+def test_mixing_behind_the_fused_step(monkeypatch, modes):
+    """FUSED_MIN_LES patched to 0: K11 steps the fields, K24 and K25 follow"""
     monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
     for seed in SEEDS:
         assert "les_advance" in es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
