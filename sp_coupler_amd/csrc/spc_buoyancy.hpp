@@ -18,16 +18,12 @@
 //   gx = phi[ip] - phi[im];   du = hx[l] * gx;   u' = u - du
 //   gy = phi[jp] - phi[jm];   dv = hy[l] * gy;   v' = v - dv
 //   a  = |du| + |dv|;         amax[l] = max over the cells of LES l of a
-// k_les_hydrostatic has K18's shape with ONE chain.  A workgroup takes C consecutive columns of the flat column index (hyd_cols:
-// the largest of 64, 32, 16 whose tile fits K15's LDS budget), a contiguous run of C * ktot cells that may span rows i and LES
-// -- l is per column:
-//   1. all HYD_THREADS lanes load the thl, qt and ql runs coalesced (K15's mover: 16-byte loads from the first 16-byte
-//      boundary on, single elements around them, so views off the 16-byte grid take the same path) and store b into ONE LDS
-//      tile, column c at c * pitch, pitch = ktot | 1: ODD, so the lanes of phase 2 that work on the same k of their columns hit
-//      distinct banks;
+// k_les_hydrostatic is the column tile of spc_coltile.hpp with (tiles, faces) = (1, 0) and ONE chain -- l is per column:
+//   1. all HYD_THREADS lanes walk the thl, qt and ql runs (hyd_load, on col_split: 16-byte loads where the three lie
+//      equally on the 16-byte grid) and store b into the tile;
 //   2. lane c runs the chain down its column, phi[k] overwriting b[k], the LDS reads of a chunk of HYD_U levels issued before
 //      its arithmetic, and writes psfc (consecutive lanes, consecutive columns);
-//   3. all lanes write phi of the run back with the mover.
+//   3. all lanes write phi of the run back (hyd_store: one vector per lane and iteration).
 // k_les_pgrad has K16's shape: a workgroup owns ADVECT_THREADS consecutive cells q = j * ktot + k of the contiguous run of a row
 // i and advect_rows() consecutive rows; a lane walks its rows with a three-row register window of phi, so each phi is fetched
 // once for the i direction and rows i0 - 1 and i1 (wrapped) once more per workgroup.  phi at j - 1 and j + 1 is ktot cells away
@@ -40,27 +36,6 @@
 constexpr int HYD_THREADS = 256;
 constexpr int HYD_U = 8;                        // levels per chunk of the chain
 constexpr int HYD_UB = 4;                       // 16-byte vectors per lane, array and batch of the load and store phases
-constexpr int HYD_LDS_SHARED = MAX_LDS_BYTES;   // tile budget of 64 and 32 columns: at least two workgroups per CU
-
-__host__ __device__ constexpr int hyd_pitch(int ktot) { return ktot | 1; }
-
-// the largest ktot of which 16 columns fit the LDS
-inline int hyd_max_ktot(int esize)
-{
-    int P = HARD_LDS_BYTES / 16 / esize;
-    if (!(P & 1)) --P;
-    return P;
-}
-
-// columns per workgroup of ktot levels of esize bytes, 0: unsupported (K15's budget rule on one tile)
-inline int hyd_cols(int ktot, int esize)
-{
-    if (ktot < 1 || (esize != 4 && esize != 8) || ktot > hyd_max_ktot(esize)) return 0;
-    const int64_t col = (int64_t)hyd_pitch(ktot) * esize;
-    if (64 * col <= HYD_LDS_SHARED) return 64;
-    if (32 * col <= HYD_LDS_SHARED) return 32;
-    return 16;
-}
 
 template <typename T> struct LesBuoyancyP {
     const T *thl, *qt, *ql;        // ql or nullptr
@@ -124,21 +99,6 @@ template <typename T> __device__ __forceinline__ T hyd_chain(T *x, const int kto
     return q;
 }
 
-// where the mover's vectors lie in a run of len elements that starts at g: head single elements, then nv whole vectors
-template <typename T> __device__ __forceinline__ void hyd_split(const T *g, const int len, const int vec, int &head, int &nv)
-{
-    constexpr int V = 16 / (int)sizeof(T);
-    if (!vec) {                                                     // the arrays lie differently on the grid: single elements
-        head = len;
-        nv = 0;
-        return;
-    }
-    const int mis = (int)(((uintptr_t)g / sizeof(T)) % V);         // elements past a 16-byte boundary
-    head = mis ? V - mis : 0;
-    if (head > len) head = len;
-    nv = (len - head) / V;
-}
-
 // phase 1: b of the run -> the tile
 template <typename T, bool QL>
 __device__ __forceinline__ void hyd_load(const LesBuoyancyP<T> &p, const T *thl, const T *qt, const T *ql, T *tile, const int len, const int P,
@@ -149,7 +109,7 @@ __device__ __forceinline__ void hyd_load(const LesBuoyancyP<T> &p, const T *thl,
     const int tid = threadIdx.x, ktot = p.ktot;
     const uint32_t nij = (uint32_t)p.nij;
     int head, nv;
-    hyd_split<T>(thl, len, p.vec, head, nv);
+    col_split<T>(thl, len, p.vec, head, nv);
     const int tail0 = head + nv * V;
     for (int s = tid; s < head + (len - tail0); s += HYD_THREADS) {
         const int e = s < head ? s : tail0 + (s - head);
@@ -200,7 +160,7 @@ template <typename T> __device__ __forceinline__ void hyd_store(T *g, const T *t
     using Vec = SlabVec<T, V>;
     const int tid = threadIdx.x;
     int head, nv;
-    hyd_split<T>(g, len, 1, head, nv);
+    col_split<T>(g, len, 1, head, nv);
     const int tail0 = head + nv * V;
     for (int s = tid; s < head + (len - tail0); s += HYD_THREADS) {
         const int e = s < head ? s : tail0 + (s - head);
@@ -221,30 +181,24 @@ template <typename T> __device__ __forceinline__ void hyd_store(T *g, const T *t
     }
 }
 
-// grid ceil(ncols / C); dynamic LDS: C * hyd_pitch(ktot) elements
+// grid ceil(ncols / C); dynamic LDS: C * col_pitch(ktot, 0) elements
 template <typename T, bool QL> __global__ __launch_bounds__(HYD_THREADS) void k_les_hydrostatic(const LesBuoyancyP<T> p)
 {
     extern __shared__ __align__(16) unsigned char hyd_lds[];
-    const int ktot = p.ktot, P = hyd_pitch(ktot), C = p.cols;
+    const int ktot = p.ktot, P = col_pitch(ktot, 0);
     T *tile = reinterpret_cast<T *>(hyd_lds);                     // b, then phi
-    const int64_t col0 = (int64_t)blockIdx.x * C;
-    const int64_t left = p.ncols - col0;
-    const int nc = left < C ? (int)left : C;                     // the last tile is partial
-    const int len = nc * ktot;
-    const int64_t l0 = col0 / p.nij;
-    const uint32_t rem0 = (uint32_t)(col0 - l0 * p.nij);
-    const int64_t run = col0 * ktot;                             // the first cell of the tile
+    const ColRun tr(blockIdx.x, p.cols, p.ncols, p.nij, ktot);
     // 1. b of every cell of the run -> the tile
-    hyd_load<T, QL>(p, p.thl + run, p.qt + run, QL ? p.ql + run : nullptr, tile, len, P, l0, rem0);
+    hyd_load<T, QL>(p, p.thl + tr.run, p.qt + tr.run, QL ? p.ql + tr.run : nullptr, tile, tr.len, P, tr.l0, tr.rem0);
     __syncthreads();
     // 2. the chain down every column, one column per lane; q[0] is the perturbation at the ground
-    if ((int)threadIdx.x < nc) {
+    if ((int)threadIdx.x < tr.nc) {
         const T q0 = hyd_chain<T>(tile + threadIdx.x * P, ktot);
-        if (p.psfc) p.psfc[col0 + threadIdx.x] = q0;
+        if (p.psfc) p.psfc[tr.col0 + threadIdx.x] = q0;
     }
     __syncthreads();
     // 3. phi of every cell of the run
-    hyd_store<T>(p.phi + run, tile, len, P, ktot);
+    hyd_store<T>(p.phi + tr.run, tile, tr.len, P, ktot);
 }
 
 template <typename T> struct BuoyancyBits;
@@ -325,20 +279,12 @@ template <typename T> static int les_buoyancy_impl(const spc_les_buoyancy_args *
     const void *wr[5] = {a->phi, a->u, a->v, a->psfc, a->amax};
     static const char *const wname[5] = {"phi", "u", "v", "psfc", "amax"};
     uintptr_t bits = 0;
-    for (int x = 0; x < 5; ++x) {
-        if (!wr[x]) continue;
-        for (int q = 0; q < 8; ++q)
-            if (in[q] && in[q] == wr[x]) return fail(SPC_ERR_INVALID_ARGUMENT, "les_buoyancy: %s is also an input (it is written while they are read)", wname[x]);
-        for (int q = 0; q < x; ++q)
-            if (wr[q] == wr[x]) return fail(SPC_ERR_INVALID_ARGUMENT, "les_buoyancy: %s is the same array as another output", wname[x]);
-        bits |= (uintptr_t)wr[x];
-    }
-    for (int q = 0; q < 8; ++q) bits |= (uintptr_t)in[q];
+    if ((rc = col_alias("les_buoyancy", in, 8, wr, 5, wname, bits))) return rc;
     if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_buoyancy: a pointer is not aligned to its element type");
-    const int C = hyd_cols(a->ktot, (int)sizeof(T));
+    const int C = col_cols(a->ktot, (int)sizeof(T), 1, 0);
     if (!C)
         return fail(SPC_ERR_UNSUPPORTED, "%sles_buoyancy: ktot %lld above the %lld levels of which 16 columns fit the LDS", "", (long long)a->ktot,
-                    (long long)hyd_max_ktot((int)sizeof(T)));
+                    (long long)col_max_ktot((int)sizeof(T), 1, 0));
     LesBuoyancyP<T> p = {};
     p.thl = (const T *)a->thl; p.qt = (const T *)a->qt; p.ql = (const T *)a->ql;
     p.u = (T *)a->u; p.v = (T *)a->v; p.hx = (const T *)a->hx; p.hy = (const T *)a->hy;
@@ -352,12 +298,13 @@ template <typename T> static int les_buoyancy_impl(const spc_les_buoyancy_args *
     p.row = (int64_t)a->jtot * a->ktot;
     p.vec = (uintptr_t)a->qt % 16 == (uintptr_t)a->thl % 16 && (!a->ql || (uintptr_t)a->ql % 16 == (uintptr_t)a->thl % 16);
     p.rows = advect_rows(a->n_les, a->itot, a->jtot, a->ktot);
-    const int64_t hgrid = (p.ncols + C - 1) / C;
+    int64_t hgrid;
+    if ((rc = col_grid("les_buoyancy", p.ncols, C, hgrid))) return rc;
     const int64_t nchunk = (p.row + ADVECT_THREADS - 1) / ADVECT_THREADS, nseg = (a->itot + p.rows - 1) / p.rows;
-    if (hgrid > INT32_MAX || nchunk > INT32_MAX || (double)nchunk * (double)nseg * (double)a->n_les > (double)INT32_MAX)
+    if (nchunk > INT32_MAX || (double)nchunk * (double)nseg * (double)a->n_les > (double)INT32_MAX)
         return fail(SPC_ERR_UNSUPPORTED, "%sles_buoyancy: too many workgroups");
     p.nchunk = (int32_t)nchunk; p.nseg = (int32_t)nseg;
-    const size_t smem = (size_t)C * hyd_pitch(a->ktot) * sizeof(T);
+    const size_t smem = (size_t)C * col_pitch(a->ktot, 0) * sizeof(T);
     void (*const kernel)(const LesBuoyancyP<T>) = a->ql ? k_les_hydrostatic<T, true> : k_les_hydrostatic<T, false>;
     if ((rc = ensure_lds(kernel, smem, "k_les_hydrostatic"))) return rc;
     if (a->amax && hipMemsetAsync(a->amax, 0, (size_t)a->n_les * sizeof(T), (hipStream_t)stream) != hipSuccess) {

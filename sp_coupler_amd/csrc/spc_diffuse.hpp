@@ -11,45 +11,25 @@
 //   d    = flux[f] ? x[0] + s0[l] * flux[f][l] : x[0]
 //   y[0] = d * m[l][0];   y[k] = (x[k] - a[l][k] * y[k - 1]) * m[l][k]      k = 1 ... ktot - 1
 //   x'[ktot - 1] = y[ktot - 1];   x'[k] = y[k] - cp[l][k] * x'[k + 1]       k = ktot - 2 ... 0
-// The shape is the first of this project with a recurrence along k, the contiguous axis: one serial chain per column.  A
-// workgroup takes C consecutive columns of one field (blockIdx.y), a contiguous run of C * ktot elements:
-//   1. all DIF_THREADS lanes load the run coalesced -- 16-byte loads from the first 16-byte boundary on, single elements
-//      before it and after the last whole vector, so views off the 16-byte grid take the same path -- and store it to LDS
-//      element by element, column c at c * pitch, pitch = ktot | 1: ODD, so the 32 lanes of a ds_read group that read the
-//      same k of 32 columns hit 32 distinct banks (f32: (pitch c + k) mod 32; f64: 2 (pitch c + k) mod 64, pairs of banks);
+// The shape is the first of this project with a recurrence along k, the contiguous axis: one serial chain per column.  It is the
+// column tile of spc_coltile.hpp with (tiles, faces) = (1, 0), one field per blockIdx.y:
+//   1. all DIF_THREADS lanes copy the run into the tile (col_move);
 //   2. lane c < C of the first wave runs both sweeps of column c in LDS, y overwriting x, x' overwriting y.  l is per lane:
 //      a tile may span several LES.  a and m (forward) and cp (backward) do not depend on the chain: the reads of chunk
 //      j + 1 (DIF_U levels) are issued before the arithmetic of chunk j, as are the LDS reads of x.  Where a tile spans at
-//      most DIF_STAGE = 2 LES (every tile of an LES of 64 or more columns) and the LDS budget has room, phase 1 also copies
-//      those rows of a, m and cp into LDS behind the columns and the sweeps read them there (one address per LES: a
-//      broadcast, no bank conflict): read from global memory one chunk ahead, each of the 2 * ktot / DIF_U chunks waited a
-//      memory round trip, which was the whole time of a tile (measured: DESIGN.md 7.3).  Tiles of more LES read them from
-//      global memory, where the lanes of one LES share an address;
+//      most DIF_STAGE = 2 LES (every tile of an LES of 64 or more columns) and the LDS budget has room, phase 1 also stages
+//      those rows of a, m and cp in LDS behind the columns and the sweeps read them there.  Tiles of more LES
+//      read them from global memory, where the lanes of one LES share an address;
 //   3. all lanes write the run back the way it came.
 // A workgroup stores only what it loaded, so the in-place update needs no ordering beyond program order.  The phases of one
-// tile do not overlap each other; they overlap those of the other workgroups of the CU: C is the largest of 64, 32, 16 whose
-// tile fits DIF_LDS_SHARED = 64 KiB (at least two workgroups per CU, three at 160 levels in either dtype), and 16 columns
-// may take the whole 160 KiB (dynamic-LDS opt-in) so that f64 columns of up to 1 279 levels are carried.
+// tile do not overlap each other; they overlap those of the other workgroups of the CU (three at 160 levels in either dtype);
+// 16 columns may take the whole 160 KiB so that f64 columns of up to 1 279 levels are carried.
 #ifndef SPC_DIFFUSE_HOST
 
 constexpr int DIF_THREADS = 256;
 constexpr int DIF_MAXF = 4;
 constexpr int DIF_U = 8;                        // levels per chunk of a sweep
 constexpr int DIF_UB = 4;                       // 16-byte vectors per lane and batch of the load and store phases
-constexpr int DIF_LDS_SHARED = MAX_LDS_BYTES;   // tile budget of 64 and 32 columns: at least two workgroups per CU
-constexpr int DIF_STAGE = 2;                    // LES whose rows of a, m and cp a tile keeps in LDS behind its columns
-
-__host__ __device__ constexpr int dif_pitch(int ktot) { return ktot | 1; }
-
-// columns per workgroup of ktot levels of esize bytes, 0: unsupported
-inline int dif_cols(int ktot, int esize)
-{
-    if (ktot < 1 || (esize != 4 && esize != 8) || ktot > HARD_LDS_BYTES / 16 / esize) return 0;
-    const int64_t col = (int64_t)dif_pitch(ktot) * esize;
-    if (64 * col <= DIF_LDS_SHARED) return 64;
-    if (32 * col <= DIF_LDS_SHARED) return 32;
-    return 16 * col <= HARD_LDS_BYTES ? 16 : 0;
-}
 
 template <typename T> struct LesDiffuseP {
     T *field[DIF_MAXF];
@@ -60,54 +40,6 @@ template <typename T> struct LesDiffuseP {
     int32_t nij, ktot;
     int32_t stage;                 // DIF_STAGE where the rows fit the LDS budget behind the tile, else 0
 };
-
-// the run g[0 ... len) <-> the tile (column c at c * P), by all lanes of the workgroup; STORE: tile -> g
-template <typename T, bool STORE> __device__ __forceinline__ void dif_move(T *g, T *tile, const int len, const int ktot, const int P)
-{
-    constexpr int V = 16 / (int)sizeof(T);
-    using Vec = SlabVec<T, V>;
-    const int tid = threadIdx.x;
-    const int mis = (int)(((uintptr_t)g / sizeof(T)) % V);         // elements past a 16-byte boundary
-    int head = mis ? V - mis : 0;
-    if (head > len) head = len;
-    const int nv = (len - head) / V;
-    const int tail0 = head + nv * V;
-    // the elements before the first and after the last whole vector: fewer than 2 V
-    {
-        const int e = tid < head ? tid : tail0 + (tid - head);
-        if (e < len) {
-            const int c = e / ktot, k = e - c * ktot;
-            if (STORE) g[e] = tile[c * P + k];
-            else tile[c * P + k] = g[e];
-        }
-    }
-    T *gv = g + head;
-    for (int i0 = 0; i0 < nv; i0 += DIF_THREADS * DIF_UB) {
-        Vec x[DIF_UB];
-        if (!STORE) {
-#pragma unroll
-            for (int u = 0; u < DIF_UB; ++u) {
-                const int i = i0 + u * DIF_THREADS + tid;
-                if (i < nv) x[u] = *reinterpret_cast<const Vec *>(gv + (int64_t)i * V);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < DIF_UB; ++u) {
-            const int i = i0 + u * DIF_THREADS + tid;
-            if (i < nv) {
-                const int e = head + i * V;
-                int c = e / ktot, k = e - c * ktot;
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    if (STORE) x[u].v[v] = tile[c * P + k];
-                    else tile[c * P + k] = x[u].v[v];
-                    if (++k == ktot) { k = 0; ++c; }
-                }
-                if (STORE) *reinterpret_cast<Vec *>(gv + (int64_t)i * V) = x[u];
-            }
-        }
-    }
-}
 
 // both sweeps of one column in LDS; a, m, cp: the rows of the column's LES
 template <typename T> __device__ __forceinline__ void dif_column(T *x, const T *a, const T *m, const T *cp, const T d, const int ktot)
@@ -179,18 +111,18 @@ template <typename T> __device__ __forceinline__ void dif_column(T *x, const T *
     }
 }
 
-// grid (ceil(ncols / C), n_fields); dynamic LDS: C * dif_pitch(ktot) elements, and 3 * DIF_STAGE * ktot more where p.stage
+// grid (ceil(ncols / C), n_fields); dynamic LDS: C * col_pitch(ktot, 0) elements, and 3 * DIF_STAGE * ktot more where p.stage
 template <typename T, int C> __global__ __launch_bounds__(DIF_THREADS) void k_les_diffuse(const LesDiffuseP<T> p)
 {
     extern __shared__ __align__(16) unsigned char dif_lds[];
     T *tile = reinterpret_cast<T *>(dif_lds);
     const int f = blockIdx.y;
-    const int ktot = p.ktot, P = dif_pitch(ktot);
+    const int ktot = p.ktot, P = col_pitch(ktot, 0);
     const int64_t col0 = (int64_t)blockIdx.x * C;
     const int64_t left = p.ncols - col0;
     const int nc = left < C ? (int)left : C;                     // the last tile is partial
     T *run = p.field[f] + col0 * ktot;
-    dif_move<T, false>(run, tile, nc * ktot, ktot, P);
+    col_move<T, DIF_THREADS, DIF_UB, false>(run, tile, nc * ktot, ktot, P);
     // the rows of a, m and cp of the tile's LES, [3][DIF_STAGE][ktot] behind the columns, where the tile spans at most p.stage LES
     const int64_t l0 = col0 / p.nij;
     const int nl = (int)((col0 + nc - 1) / p.nij - l0) + 1;
@@ -224,24 +156,10 @@ template <typename T, int C> __global__ __launch_bounds__(DIF_THREADS) void k_le
         }
     }
     __syncthreads();
-    dif_move<T, true>(run, tile, nc * ktot, ktot, P);
+    col_move<T, DIF_THREADS, DIF_UB, true>(run, tile, nc * ktot, ktot, P);
 }
 
 #else  // SPC_DIFFUSE_HOST ---------------------------------------------------------------------------------------------------
-
-template <typename T, int C> static int les_diffuse_launch(const LesDiffuseP<T> &p, int n_fields, void *stream)
-{
-    const size_t tile = (size_t)C * dif_pitch(p.ktot) * sizeof(T), rows = (size_t)3 * DIF_STAGE * p.ktot * sizeof(T);
-    LesDiffuseP<T> q = p;
-    q.stage = tile + rows <= (size_t)(C == 16 ? HARD_LDS_BYTES : DIF_LDS_SHARED) ? DIF_STAGE : 0;
-    const size_t smem = tile + (q.stage ? rows : 0);
-    const int rc = ensure_lds(k_les_diffuse<T, C>, smem, "k_les_diffuse");
-    if (rc) return rc;
-    const int64_t grid = (p.ncols + C - 1) / C;
-    if (grid > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_diffuse: too many workgroups");
-    hipLaunchKernelGGL((k_les_diffuse<T, C>), dim3((unsigned)grid, (unsigned)n_fields), dim3(DIF_THREADS), smem, (hipStream_t)stream, q);
-    return launch_status("k_les_diffuse");
-}
 
 template <typename T> static int les_diffuse_impl(const spc_les_diffuse_args *a, void *stream)
 {
@@ -272,17 +190,18 @@ template <typename T> static int les_diffuse_impl(const spc_les_diffuse_args *a,
         bits |= (uintptr_t)a->fields[f] | (uintptr_t)a->flux[f];
     }
     if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_diffuse: a pointer is not aligned to its element type");
-    const int C = dif_cols(a->ktot, (int)sizeof(T));
+    const int C = col_cols(a->ktot, (int)sizeof(T), 1, 0);
     if (!C)
         return fail(SPC_ERR_UNSUPPORTED, "%sles_diffuse: ktot %lld above the %lld levels of which 16 columns fit the LDS", "", (long long)a->ktot,
-                    (long long)(((HARD_LDS_BYTES / 16 / (int)sizeof(T)) - 1) | 1));
+                    (long long)col_max_ktot((int)sizeof(T), 1, 0));
     p.a = (const T *)a->a; p.m = (const T *)a->m; p.cp = (const T *)a->cp; p.s0 = (const T *)a->s0;
     p.nij = a->itot * a->jtot;
     p.ncols = a->n_les * (int64_t)p.nij;
     p.pitch_prof = a->pitch_prof;
     p.ktot = a->ktot;
-    return C == 64 ? les_diffuse_launch<T, 64>(p, a->n_fields, stream) : C == 32 ? les_diffuse_launch<T, 32>(p, a->n_fields, stream)
-                                                                                 : les_diffuse_launch<T, 16>(p, a->n_fields, stream);
+    return col_dispatch(C, [&](auto c) {
+        return col_stage_launch<T>(k_les_diffuse<T, decltype(c)::value>, "k_les_diffuse", "les_diffuse", p, C, 1, a->n_fields, DIF_THREADS, stream);
+    });
 }
 
 #endif

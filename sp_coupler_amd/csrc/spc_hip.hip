@@ -57,7 +57,9 @@
 //   K25 k_les_speed, k_les_vmix  one backward-Euler step of the vertical mixing by each column's own eddy viscosity: the Thomas
 //                  elimination in the kernel (one division per level), K15's tile, surface fluxes and a neutral bulk drag on the
 //                  lowest wind level from a plane of wind speeds: spc_vmix.hpp, kernels and host side
-// Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp.  Host side of K1-K5 (launch
+// Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp; the LDS column tile of the
+// kernels with a serial chain along k (K15, K17, K18, K21, K22, K23, K25: its geometry, the run of a workgroup, the split of a
+// run into 16-byte vectors, the plain mover, their host checks and launches): spc_coltile.hpp.  Host side of K1-K5 (launch
 // heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
 // a 256-thread workgroup owns CB consecutive columns; the source profiles of those columns are
@@ -110,6 +112,7 @@ namespace {
 #include "spc_thermo.hpp"
 #include "spc_waterpath.hpp"
 #include "spc_micro.hpp"
+#include "spc_coltile.hpp"
 #include "spc_diffuse.hpp"
 #include "spc_advect.hpp"
 #include "spc_vadvect.hpp"
@@ -124,6 +127,9 @@ namespace {
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
+#define SPC_COLTILE_HOST
+#include "spc_coltile.hpp"
+#undef SPC_COLTILE_HOST
 #include "spc_sputils_host.hpp"
 #include "spc_vnudge_host.hpp"
 #include "spc_geo_host.hpp"
@@ -254,7 +260,7 @@ int spc_les_microphysics_f32(const spc_les_micro_args *a, void *s) { return les_
 
 int spc_les_diffuse_f64(const spc_les_diffuse_args *a, void *s) { return les_diffuse_impl<double>(a, s); }
 int spc_les_diffuse_f32(const spc_les_diffuse_args *a, void *s) { return les_diffuse_impl<float>(a, s); }
-int spc_les_diffuse_cols_per_block(int ktot, int elem_size) { return dif_cols(ktot, elem_size); }
+int spc_les_diffuse_cols_per_block(int ktot, int elem_size) { return col_cols(ktot, elem_size, 1, 0); }
 
 int spc_les_advect_f64(const spc_les_advect_args *a, void *s) { return les_advect_impl<double>(a, s); }
 int spc_les_advect_f32(const spc_les_advect_args *a, void *s) { return les_advect_impl<float>(a, s); }
@@ -263,17 +269,17 @@ int spc_les_advect_rows(int64_t n_les, int itot, int jtot, int ktot) { return ad
 
 int spc_les_vadvect_f64(const spc_les_vadvect_args *a, void *s) { return les_vadvect_impl<double>(a, s); }
 int spc_les_vadvect_f32(const spc_les_vadvect_args *a, void *s) { return les_vadvect_impl<float>(a, s); }
-int spc_les_vadvect_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
+int spc_les_vadvect_cols_per_block(int ktot, int elem_size) { return col_cols(ktot, elem_size, 1, 0); }
 int spc_les_transport_f64(const spc_les_transport_args *a, void *s) { return les_transport_impl<double>(a, s); }
 int spc_les_transport_f32(const spc_les_transport_args *a, void *s) { return les_transport_impl<float>(a, s); }
-int spc_les_transport_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
+int spc_les_transport_cols_per_block(int ktot, int elem_size) { return col_cols(ktot, elem_size, 1, 0); }
 int spc_les_transport2_f64(const spc_les_transport2_args *a, void *s) { return les_transport2_impl<double>(a, s); }
 int spc_les_transport2_f32(const spc_les_transport2_args *a, void *s) { return les_transport2_impl<float>(a, s); }
-int spc_les_transport2_cols_per_block(int ktot, int elem_size) { return vad_cols(ktot, elem_size); }
+int spc_les_transport2_cols_per_block(int ktot, int elem_size) { return col_cols(ktot, elem_size, 1, 0); }
 
 int spc_les_radiate_f64(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<double>(a, s); }
 int spc_les_radiate_f32(const spc_les_radiate_args *a, void *s) { return les_radiate_impl<float>(a, s); }
-int spc_les_radiate_cols_per_block(int ktot, int elem_size) { return rad_cols(ktot, elem_size); }
+int spc_les_radiate_cols_per_block(int ktot, int elem_size) { return col_cols(ktot, elem_size, 2, 1); }
 
 int spc_les_qt_local_f64(const spc_les_qt_local_args *a, void *s) { return les_qt_local_impl<double>(a, s); }
 int spc_les_qt_local_f32(const spc_les_qt_local_args *a, void *s) { return les_qt_local_impl<float>(a, s); }
@@ -281,13 +287,13 @@ int spc_les_qt_local_split(int64_t n_les, int itot, int jtot, int ktot, int elem
 
 int spc_les_buoyancy_f64(const spc_les_buoyancy_args *a, void *s) { return les_buoyancy_impl<double>(a, s); }
 int spc_les_buoyancy_f32(const spc_les_buoyancy_args *a, void *s) { return les_buoyancy_impl<float>(a, s); }
-int spc_les_buoyancy_cols_per_block(int ktot, int elem_size) { return hyd_cols(ktot, elem_size); }
+int spc_les_buoyancy_cols_per_block(int ktot, int elem_size) { return col_cols(ktot, elem_size, 1, 0); }
 
 int spc_les_mix_f64(const spc_les_mix_args *a, void *s) { return les_mix_impl<double>(a, s); }
 int spc_les_mix_f32(const spc_les_mix_args *a, void *s) { return les_mix_impl<float>(a, s); }
 int spc_les_vmix_f64(const spc_les_vmix_args *a, void *s) { return les_vmix_impl<double>(a, s); }
 int spc_les_vmix_f32(const spc_les_vmix_args *a, void *s) { return les_vmix_impl<float>(a, s); }
-int spc_les_vmix_cols_per_block(int ktot, int elem_size) { return vmix_cols(ktot, elem_size); }
+int spc_les_vmix_cols_per_block(int ktot, int elem_size) { return col_cols(ktot, elem_size, 2, 0); }
 
 int spc_les_moments_f64(const spc_les_moments_args *a, void *s) { return les_moments_impl<double>(a, s); }
 int spc_les_moments_f32(const spc_les_moments_args *a, void *s) { return les_moments_impl<float>(a, s); }

@@ -13,19 +13,15 @@
 //   E(x)    = K12's table lookup (spc_thermo.hpp: th_sat) of x clamped to [0, x_hi]
 //   F[k]    = f0[l] * E(A[k]) + f1[l] * E(B[k])         k = 0 ... ktot: the net upward flux at face k
 //   thl'[k] = thl[k] - c[l][k] * (F[k + 1] - F[k]);   flux[k] = F[k + 1];   fsfc = F[0]
-// The shape is K15's and K17's with TWO opposed chains.  A workgroup takes C consecutive columns of the flat column index
-// (rad_cols: the largest of 64, 32, 16 whose two tiles fit the LDS budget of K15), a contiguous run of C * ktot cells that may
-// span rows i and LES -- l is per column:
-//   1. all RAD_THREADS lanes load the ql run coalesced (K15's mover: 16-byte loads from the first 16-byte boundary on, single
-//      elements around them, so views off the 16-byte grid take the same path) and store t into two LDS tiles, column c at
-//      c * pitch, pitch = (ktot + 1) | 1: ODD, so the lanes of phase 2 that work on the same k of their columns hit distinct
-//      banks, and one element longer than K15's because phase 3 keeps the ktot + 1 faces of a column in one row;
+// The shape is the column tile of spc_coltile.hpp with (tiles, faces) = (2, 1) and TWO opposed chains; the pitch is one element
+// longer than K15's because phase 3 keeps the ktot + 1 faces of a column in one row -- l is per column:
+//   1. all RAD_THREADS lanes walk the ql run (rad_load, on col_split) and store t into both tiles;
 //   2. lane c of wave 0 runs B up its column of one tile, B[k + 1] overwriting t[k]; lane c of wave 1 runs A down its column
 //      of the other, A[k] overwriting t[k]: the two chains of a column run at once on two waves, the LDS reads of a chunk of
 //      RAD_U levels issued before its arithmetic;
 //   3. all lanes form F of the C * (ktot + 1) faces, two lookups per face, F[k] overwriting A[k] (a face reads and writes only
-//      its own slots); then all lanes walk the run again with the mover: thl read, updated and written, flux written, the lane
-//      of level 0 writes fsfc.
+//      its own slots); then all lanes walk the run again: thl read, updated and written, flux written, the lane of level 0
+//      writes fsfc.
 // A workgroup writes only the cells it read, so the in-place update of thl needs no ordering beyond program order.  The table
 // (16 KB of doubles at the 2 049 nodes of radiation.py) is read at data-dependent indices: LDS_TAB stages it once per workgroup
 // in LDS behind the tiles where the budget has room and the CU keeps as many resident workgroups as without it; otherwise it is
@@ -35,27 +31,6 @@
 constexpr int RAD_THREADS = 256;
 constexpr int RAD_U = 8;                        // levels per chunk of a chain
 constexpr int RAD_UB = 4;                       // 16-byte vectors per lane and batch of the load and store phases
-constexpr int RAD_LDS_SHARED = MAX_LDS_BYTES;   // budget of 64 and 32 columns: at least two workgroups per CU
-
-__host__ __device__ constexpr int rad_pitch(int ktot) { return (ktot + 1) | 1; }
-
-// the largest ktot of which 16 columns (two tiles) fit the LDS
-inline int rad_max_ktot(int esize)
-{
-    int P = HARD_LDS_BYTES / 32 / esize;
-    if (!(P & 1)) --P;
-    return P - 1;
-}
-
-// columns per workgroup of ktot levels of esize bytes, 0: unsupported (K15's budget rule on two tiles)
-inline int rad_cols(int ktot, int esize)
-{
-    if (ktot < 1 || (esize != 4 && esize != 8) || ktot > rad_max_ktot(esize)) return 0;
-    const int64_t col = (int64_t)2 * rad_pitch(ktot) * esize;
-    if (64 * col <= RAD_LDS_SHARED) return 64;
-    if (32 * col <= RAD_LDS_SHARED) return 32;
-    return 16;
-}
 
 template <typename T> struct LesRadiateP {
     const T *ql;
@@ -126,21 +101,6 @@ template <typename T> __device__ __forceinline__ void rad_down(T *x, const int k
     }
 }
 
-// where the mover's vectors lie in a run of len elements that starts at g: head single elements, then nv whole vectors
-template <typename T> __device__ __forceinline__ void rad_split(const T *g, const int len, const int vec, int &head, int &nv)
-{
-    constexpr int V = 16 / (int)sizeof(T);
-    if (!vec) {                                                     // the arrays lie differently on the grid: single elements
-        head = len;
-        nv = 0;
-        return;
-    }
-    const int mis = (int)(((uintptr_t)g / sizeof(T)) % V);         // elements past a 16-byte boundary
-    head = mis ? V - mis : 0;
-    if (head > len) head = len;
-    nv = (len - head) / V;
-}
-
 // phase 1: t = w * ql of the run -> both tiles
 template <typename T>
 __device__ __forceinline__ void rad_load(const LesRadiateP<T> &p, const T *g, T *ta, T *tb, const int len, const int P, const int64_t l0, const uint32_t rem0)
@@ -150,7 +110,7 @@ __device__ __forceinline__ void rad_load(const LesRadiateP<T> &p, const T *g, T 
     const int tid = threadIdx.x, ktot = p.ktot;
     const uint32_t nij = (uint32_t)p.nij;
     int head, nv;
-    rad_split<T>(g, len, p.vec, head, nv);
+    col_split<T>(g, len, p.vec, head, nv);
     const int tail0 = head + nv * V;
     for (int s = tid; s < head + (len - tail0); s += RAD_THREADS) {
         const int e = s < head ? s : tail0 + (s - head);
@@ -213,7 +173,7 @@ __device__ __forceinline__ void rad_store(const LesRadiateP<T> &p, T *g, T *fl, 
     const int tid = threadIdx.x, ktot = p.ktot;
     const uint32_t nij = (uint32_t)p.nij;
     int head, nv;
-    rad_split<T>(g, len, p.vec, head, nv);
+    col_split<T>(g, len, p.vec, head, nv);
     const int tail0 = head + nv * V;
     for (int s = tid; s < head + (len - tail0); s += RAD_THREADS) {
         const int e = s < head ? s : tail0 + (s - head);
@@ -261,11 +221,11 @@ __device__ __forceinline__ void rad_store(const LesRadiateP<T> &p, T *g, T *fl, 
     }
 }
 
-// grid ceil(ncols / C); dynamic LDS: 2 * C * rad_pitch(ktot) elements, and n_tab more where LDS_TAB
+// grid ceil(ncols / C); dynamic LDS: 2 * C * col_pitch(ktot, 1) elements, and n_tab more where LDS_TAB
 template <typename T, bool LDS_TAB> __global__ __launch_bounds__(RAD_THREADS) void k_les_radiate(const LesRadiateP<T> p)
 {
     extern __shared__ __align__(16) unsigned char rad_lds[];
-    const int ktot = p.ktot, P = rad_pitch(ktot), C = p.cols;
+    const int ktot = p.ktot, P = col_pitch(ktot, 1), C = p.cols;
     T *ta = reinterpret_cast<T *>(rad_lds);                       // t, then A, then F
     T *tb = ta + C * P;                                            // t, then B
     const T *etab = p.etab;
@@ -274,28 +234,22 @@ template <typename T, bool LDS_TAB> __global__ __launch_bounds__(RAD_THREADS) vo
         for (int i = threadIdx.x; i < p.n_tab; i += RAD_THREADS) tab[i] = p.etab[i];
         etab = tab;
     }
-    const int64_t col0 = (int64_t)blockIdx.x * C;
-    const int64_t left = p.ncols - col0;
-    const int nc = left < C ? (int)left : C;                     // the last tile is partial
-    const int len = nc * ktot;
-    const int64_t l0 = col0 / p.nij;
-    const uint32_t rem0 = (uint32_t)(col0 - l0 * p.nij);
-    const int64_t run = col0 * ktot;                             // the first cell of the tile
+    const ColRun tr(blockIdx.x, C, p.ncols, p.nij, ktot);
     // 1. t = w * ql of every cell of the run -> both tiles
-    rad_load<T>(p, p.ql + run, ta, tb, len, P, l0, rem0);
+    rad_load<T>(p, p.ql + tr.run, ta, tb, tr.len, P, tr.l0, tr.rem0);
     __syncthreads();
     // 2. the optical depths below (wave 0) and above (wave 1) the faces, one column per lane
     {
         const int wave = threadIdx.x >> 6, c = threadIdx.x & 63;
-        if (wave == 0 && c < nc) rad_up<T>(tb + c * P, ktot);
-        if (wave == 1 && c < nc) rad_down<T>(ta + c * P, ktot);
+        if (wave == 0 && c < tr.nc) rad_up<T>(tb + c * P, ktot);
+        if (wave == 1 && c < tr.nc) rad_down<T>(ta + c * P, ktot);
     }
     __syncthreads();
     // 3. F of every face, then thl, flux and fsfc of every cell
     const int nf = ktot + 1;
-    for (int e = threadIdx.x; e < nc * nf; e += RAD_THREADS) {
+    for (int e = threadIdx.x; e < tr.nc * nf; e += RAD_THREADS) {
         const int c = e / nf, k = e - c * nf;
-        const int64_t l = l0 + (rem0 + (uint32_t)c) / (uint32_t)p.nij;
+        const int64_t l = tr.l0 + (tr.rem0 + (uint32_t)c) / (uint32_t)p.nij;
         const T A = k < ktot ? ta[c * P + k] : (T)0;
         const T B = k ? tb[c * P + k - 1] : (T)0;
         const T Ea = rad_E<T>(etab, A, p.x_hi, p.inv_step, p.n_tab);
@@ -305,7 +259,7 @@ template <typename T, bool LDS_TAB> __global__ __launch_bounds__(RAD_THREADS) vo
         ta[c * P + k] = Fa + Fb;
     }
     __syncthreads();
-    rad_store<T>(p, p.thl + run, p.flux ? p.flux + run : nullptr, p.fsfc ? p.fsfc + col0 : nullptr, ta, len, P, l0, rem0);
+    rad_store<T>(p, p.thl + tr.run, p.flux ? p.flux + tr.run : nullptr, p.fsfc ? p.fsfc + tr.col0 : nullptr, ta, tr.len, P, tr.l0, tr.rem0);
 }
 
 #else  // SPC_RADIATE_HOST ---------------------------------------------------------------------------------------------------
@@ -327,20 +281,12 @@ template <typename T> static int les_radiate_impl(const spc_les_radiate_args *a,
     const void *wr[3] = {a->thl, a->flux, a->fsfc};
     static const char *const wname[3] = {"thl", "flux", "fsfc"};
     uintptr_t bits = 0;
-    for (int x = 0; x < 3; ++x) {
-        if (!wr[x]) continue;
-        for (int q = 0; q < 6; ++q)
-            if (in[q] == wr[x]) return fail(SPC_ERR_INVALID_ARGUMENT, "les_radiate: %s is also an input (it is written while they are read)", wname[x]);
-        for (int q = 0; q < x; ++q)
-            if (wr[q] == wr[x]) return fail(SPC_ERR_INVALID_ARGUMENT, "les_radiate: %s is the same array as another output", wname[x]);
-        bits |= (uintptr_t)wr[x];
-    }
-    for (int q = 0; q < 6; ++q) bits |= (uintptr_t)in[q];
+    if ((rc = col_alias("les_radiate", in, 6, wr, 3, wname, bits))) return rc;
     if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_radiate: a pointer is not aligned to its element type");
-    const int C = rad_cols(a->ktot, (int)sizeof(T));
+    const int C = col_cols(a->ktot, (int)sizeof(T), 2, 1);
     if (!C)
         return fail(SPC_ERR_UNSUPPORTED, "%sles_radiate: ktot %lld above the %lld levels of which 16 columns fit the LDS", "", (long long)a->ktot,
-                    (long long)rad_max_ktot((int)sizeof(T)));
+                    (long long)col_max_ktot((int)sizeof(T), 2, 1));
     LesRadiateP<T> p = {};
     p.ql = (const T *)a->ql; p.thl = (T *)a->thl; p.w = (const T *)a->w; p.c = (const T *)a->c;
     p.f0 = (const T *)a->f0; p.f1 = (const T *)a->f1; p.etab = (const T *)a->etab;
@@ -352,12 +298,12 @@ template <typename T> static int les_radiate_impl(const spc_les_radiate_args *a,
     p.inv_step = (T)a->inv_step;
     p.x_hi = (T)((double)(a->n_tab - 1) / a->inv_step);
     p.vec = (uintptr_t)a->ql % 16 == (uintptr_t)a->thl % 16 && (!a->flux || (uintptr_t)a->flux % 16 == (uintptr_t)a->thl % 16);
-    const int64_t grid = (p.ncols + C - 1) / C;
-    if (grid > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_radiate: too many workgroups");
-    const size_t tiles = (size_t)2 * C * rad_pitch(a->ktot) * sizeof(T), tab = (size_t)a->n_tab * sizeof(T);
+    int64_t grid;
+    if ((rc = col_grid("les_radiate", p.ncols, C, grid))) return rc;
+    const size_t tiles = (size_t)2 * C * col_pitch(a->ktot, 1) * sizeof(T), tab = (size_t)a->n_tab * sizeof(T);
     // the table goes behind the tiles where the budget has room AND it costs the CU no resident workgroup: the launch is bound
     // by the latency of a tile's phases, which only other workgroups hide (measured: DESIGN.md 7.3)
-    const bool lds_tab = tiles + tab <= (size_t)(C == 16 ? HARD_LDS_BYTES : RAD_LDS_SHARED) && HARD_LDS_BYTES / (tiles + tab) == HARD_LDS_BYTES / tiles;
+    const bool lds_tab = tiles + tab <= (size_t)(C == 16 ? HARD_LDS_BYTES : MAX_LDS_BYTES) && HARD_LDS_BYTES / (tiles + tab) == HARD_LDS_BYTES / tiles;
     const size_t smem = tiles + (lds_tab ? tab : 0);
     void (*const kernel)(const LesRadiateP<T>) = lds_tab ? k_les_radiate<T, true> : k_les_radiate<T, false>;
     if ((rc = ensure_lds(kernel, smem, "k_les_radiate"))) return rc;

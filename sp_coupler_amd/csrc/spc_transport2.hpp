@@ -74,26 +74,20 @@ template <typename T> __device__ __forceinline__ T trn2_vface(const T p, const T
     return (T)0.5 * d;
 }
 
-// grid ceil(ncols / C); dynamic LDS: C * vad_pitch(ktot) elements; NF >= 1
+// grid ceil(ncols / C); dynamic LDS: C * col_pitch(ktot, 0) elements; NF >= 1
 template <typename T, int NF, bool LIMITED> __global__ __launch_bounds__(TRN_THREADS) void k_les_transport2(const LesTransportP<T> p)
 {
     extern __shared__ __align__(16) unsigned char trn2_lds[];
     T *tile = reinterpret_cast<T *>(trn2_lds);
     constexpr int TRN2_UNROLL = NF <= 2 ? NF : 1;                // the fields of a cell unrolled, or one after the other
-    const int ktot = p.ktot, P = vad_pitch(ktot), C = p.cols;
+    const int ktot = p.ktot, P = col_pitch(ktot, 0), C = p.cols;
     const int itot = p.itot, jtot = p.jtot;
-    const int64_t col0 = (int64_t)blockIdx.x * C;
-    const int64_t left = p.ncols - col0;
-    const int nc = left < C ? (int)left : C;                     // the last tile is partial
-    const int len = nc * ktot;
-    const int64_t l0 = col0 / p.nij;
-    const uint32_t rem0 = (uint32_t)(col0 - l0 * p.nij);
-    const int64_t run = col0 * ktot;                             // the first cell of the tile
+    const ColRun tr(blockIdx.x, C, p.ncols, p.nij, ktot);
     const int64_t row = (int64_t)jtot * ktot;                    // cells of one row i
     // 1. e = g * ((ce - cw) + (cn - cs)) of every cell of the run -> LDS (K22's phase 1)
-    for (int e = threadIdx.x; e < len; e += TRN_THREADS) {
-        const VadCell w = vad_cell(e, ktot, l0, rem0, (uint32_t)p.nij, (uint32_t)jtot);
-        const int64_t o = run + e;
+    for (int e = threadIdx.x; e < tr.len; e += TRN_THREADS) {
+        const VadCell w = vad_cell(e, ktot, tr.l0, tr.rem0, (uint32_t)p.nij, (uint32_t)jtot);
+        const int64_t o = tr.run + e;
         const TrnNb nb = trn_neighbours(o, w.i, w.j, itot, jtot, ktot, row);
         const TrnFaces<T> c = trn_faces<T>(p.u, p.v, o, nb, p.hx[w.l], p.hy[w.l]);
         const T gk = p.g[w.l * p.pitch_prof + w.k];
@@ -104,15 +98,15 @@ template <typename T, int NF, bool LIMITED> __global__ __launch_bounds__(TRN_THR
     }
     __syncthreads();
     // 2. the mass flux through the upper faces, one column per lane
-    if ((int)threadIdx.x < nc) vad_column<T>(tile + threadIdx.x * P, ktot);
+    if ((int)threadIdx.x < tr.nc) vad_column<T>(tile + threadIdx.x * P, ktot);
     __syncthreads();
     // 3. the six second-order fluxes of every cell of every field, mtop, ftop and the outflow Courant sums
     const T zero = (T)0;
     T smax = zero;
     int64_t lcur = -1;
-    for (int e = threadIdx.x; e < len; e += TRN_THREADS) {
-        const VadCell w = vad_cell(e, ktot, l0, rem0, (uint32_t)p.nij, (uint32_t)jtot);
-        const int64_t o = run + e;
+    for (int e = threadIdx.x; e < tr.len; e += TRN_THREADS) {
+        const VadCell w = vad_cell(e, ktot, tr.l0, tr.rem0, (uint32_t)p.nij, (uint32_t)jtot);
+        const int64_t o = tr.run + e;
         const int k = w.k;
         const T *M = tile + w.c * P;
         const T Mb = k ? M[k - 1] : zero;
@@ -211,7 +205,7 @@ template <typename T, int NF, bool LIMITED> __global__ __launch_bounds__(TRN_THR
             T y = x - h;
             y = y - z;
             p.out[f][o] = y;
-            if (p.ftop && k == ktot - 1) p.ftop[f * p.ncols + col0 + w.c] = Ft2;
+            if (p.ftop && k == ktot - 1) p.ftop[f * p.ncols + tr.col0 + w.c] = Ft2;
         }
     }
     if (p.cmax) {

@@ -13,7 +13,7 @@
 //   x' = (x + pb * (x[km] - x)) + pt * (x[kp] - x)        km = k ? k - 1 : 0, kp = k + 1 < ktot ? k + 1 : ktot - 1
 //   s  = pb + pt;   cmax[l] = max over the cells of LES l of s;   mtop[l][i][j][k] = M[k + 1]
 // The shape joins K16's neighbours across i and j with K15's serial chain along k.  A workgroup takes C consecutive columns of
-// the flat column index (vad_cols: the largest of 64, 32, 16 whose tile fits the LDS budget of K15), a contiguous run of
+// the flat column index (the column tile of spc_coltile.hpp with (tiles, faces) = (1, 0): geometry and ColRun), a contiguous run of
 // C * ktot cells that may span rows i and LES -- l, i and j are per column:
 //   1. all VAD_THREADS lanes walk the run coalesced (a lane takes every VAD_THREADS-th cell, so a wave's accesses are one
 //      contiguous stretch whatever ktot is and a view off the 16-byte grid takes the same path), form e from the six wind
@@ -35,19 +35,6 @@
 constexpr int VAD_THREADS = 256;
 constexpr int VAD_MAXF = 6;
 constexpr int VAD_U = 8;                        // levels per chunk of the column recurrence
-constexpr int VAD_LDS_SHARED = MAX_LDS_BYTES;   // tile budget of 64 and 32 columns: at least two workgroups per CU
-
-__host__ __device__ constexpr int vad_pitch(int ktot) { return ktot | 1; }
-
-// columns per workgroup of ktot levels of esize bytes, 0: unsupported (K15's budget rule: dif_cols)
-inline int vad_cols(int ktot, int esize)
-{
-    if (ktot < 1 || (esize != 4 && esize != 8) || ktot > HARD_LDS_BYTES / 16 / esize) return 0;
-    const int64_t col = (int64_t)vad_pitch(ktot) * esize;
-    if (64 * col <= VAD_LDS_SHARED) return 64;
-    if (32 * col <= VAD_LDS_SHARED) return 32;
-    return 16 * col <= HARD_LDS_BYTES ? 16 : 0;
-}
 
 template <typename T> struct LesVadvectP {
     const T *u, *v;
@@ -112,25 +99,19 @@ template <typename T> __device__ __forceinline__ void vad_column(T *x, const int
     }
 }
 
-// grid ceil(ncols / C); dynamic LDS: C * vad_pitch(ktot) elements
+// grid ceil(ncols / C); dynamic LDS: C * col_pitch(ktot, 0) elements
 template <typename T, int NF> __global__ __launch_bounds__(VAD_THREADS) void k_les_vadvect(const LesVadvectP<T> p)
 {
     extern __shared__ __align__(16) unsigned char vad_lds[];
     T *tile = reinterpret_cast<T *>(vad_lds);
-    const int ktot = p.ktot, P = vad_pitch(ktot), C = p.cols;
+    const int ktot = p.ktot, P = col_pitch(ktot, 0), C = p.cols;
     const int itot = p.itot, jtot = p.jtot;
-    const int64_t col0 = (int64_t)blockIdx.x * C;
-    const int64_t left = p.ncols - col0;
-    const int nc = left < C ? (int)left : C;                     // the last tile is partial
-    const int len = nc * ktot;
-    const int64_t l0 = col0 / p.nij;
-    const uint32_t rem0 = (uint32_t)(col0 - l0 * p.nij);
-    const int64_t run = col0 * ktot;                             // the first cell of the tile
+    const ColRun tr(blockIdx.x, C, p.ncols, p.nij, ktot);
     const int64_t row = (int64_t)jtot * ktot;                    // cells of one row i
     // 1. e = g * ((ce - cw) + (cn - cs)) of every cell of the run -> LDS
-    for (int e = threadIdx.x; e < len; e += VAD_THREADS) {
-        const VadCell w = vad_cell(e, ktot, l0, rem0, (uint32_t)p.nij, (uint32_t)jtot);
-        const int64_t o = run + e;
+    for (int e = threadIdx.x; e < tr.len; e += VAD_THREADS) {
+        const VadCell w = vad_cell(e, ktot, tr.l0, tr.rem0, (uint32_t)p.nij, (uint32_t)jtot);
+        const int64_t o = tr.run + e;
         const int64_t ow = o + (w.i ? -row : (int64_t)(itot - 1) * row);
         const int64_t oe = o + (w.i + 1 < itot ? row : -(int64_t)(itot - 1) * row);
         const int64_t os = o + (w.j ? -(int64_t)ktot : (int64_t)(jtot - 1) * ktot);
@@ -151,14 +132,14 @@ template <typename T, int NF> __global__ __launch_bounds__(VAD_THREADS) void k_l
     }
     __syncthreads();
     // 2. the mass flux through the upper faces, one column per lane
-    if ((int)threadIdx.x < nc) vad_column<T>(tile + threadIdx.x * P, ktot);
+    if ((int)threadIdx.x < tr.nc) vad_column<T>(tile + threadIdx.x * P, ktot);
     __syncthreads();
     // 3. the upwind step of every field, mtop and the Courant sums
     T smax = (T)0;
     int64_t lcur = -1;
-    for (int e = threadIdx.x; e < len; e += VAD_THREADS) {
-        const VadCell w = vad_cell(e, ktot, l0, rem0, (uint32_t)p.nij, (uint32_t)jtot);
-        const int64_t o = run + e;
+    for (int e = threadIdx.x; e < tr.len; e += VAD_THREADS) {
+        const VadCell w = vad_cell(e, ktot, tr.l0, tr.rem0, (uint32_t)p.nij, (uint32_t)jtot);
+        const int64_t o = tr.run + e;
         const int k = w.k;
         const T *M = tile + w.c * P;
         const T Mb = k ? M[k - 1] : (T)0;
@@ -214,7 +195,7 @@ template <typename T, int NF> __global__ __launch_bounds__(VAD_THREADS) void k_l
 #else  // SPC_VADVECT_HOST ---------------------------------------------------------------------------------------------------
 
 // ---- the host path that K17, K22 and K23 share ----------------------------------------------------------------------------------
-// The three kernels take one tile (vad_cols, vad_pitch), one grid and the same arrays; their argument blocks are ONE layout that
+// The three kernels take one tile (spc_coltile.hpp, (tiles, faces) = (1, 0)), one grid and the same arrays; their argument blocks are ONE layout that
 // grew at its end (K22 added ftop, K23 the limiter), which include/spc.h spells out three times.  The shared code reads the
 // members by name, so it does not depend on that, but the Python side builds the blocks from one another (_abi.py):
 #define VAD_SAME_OFFSET(m)                                                                                                 \
@@ -285,10 +266,10 @@ template <typename T, typename A, typename P> static int vad_family_args(const c
     for (int q = 0; q < n_in; ++q) bits |= (uintptr_t)in[q];
     for (int q = 0; q < n_wr; ++q) bits |= (uintptr_t)wr[q];
     if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%s: a pointer is not aligned to its element type", name);
-    const int C = vad_cols(a->ktot, (int)sizeof(T));
+    const int C = col_cols(a->ktot, (int)sizeof(T), 1, 0);
     if (!C)
         return fail(SPC_ERR_UNSUPPORTED, "%s: ktot %lld above the %lld levels of which 16 columns fit the LDS", name, (long long)a->ktot,
-                    (long long)(((HARD_LDS_BYTES / 16 / (int)sizeof(T)) - 1) | 1));
+                    (long long)col_max_ktot((int)sizeof(T), 1, 0));
     p.u = (const T *)a->u; p.v = (const T *)a->v; p.hx = (const T *)a->hx; p.hy = (const T *)a->hy;
     p.g = (const T *)a->g; p.r = (const T *)a->r; p.cmax = (T *)a->cmax; p.mtop = (T *)a->mtop;
     if constexpr (HAS_FTOP) p.ftop = (T *)ftop;
@@ -296,7 +277,8 @@ template <typename T, typename A, typename P> static int vad_family_args(const c
     p.nij = a->itot * a->jtot;
     p.ncols = a->n_les * (int64_t)p.nij;
     p.pitch_prof = a->pitch_prof;
-    if ((p.ncols + C - 1) / C > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%s: too many workgroups", name);
+    int64_t grid;
+    if ((rc = col_grid(name, p.ncols, C, grid))) return rc;
     if (a->cmax && hipMemsetAsync(a->cmax, 0, (size_t)a->n_les * sizeof(T), (hipStream_t)stream) != hipSuccess) {
         (void)hipGetLastError();
         return fail(SPC_ERR_LAUNCH, "%s: cmax could not be zeroed", name);
@@ -305,10 +287,10 @@ template <typename T, typename A, typename P> static int vad_family_args(const c
     return SPC_OK;
 }
 
-// one workgroup of VAD_THREADS per p.cols columns, the tile of vad_pitch(ktot) elements per column in dynamic LDS
+// one workgroup of VAD_THREADS per p.cols columns, the tile of col_pitch(ktot, 0) elements per column in dynamic LDS
 template <typename K, typename P> static int vad_family_launch(K kernel, const char *kernel_name, const P &p, void *stream)
 {
-    const size_t smem = (size_t)p.cols * vad_pitch(p.ktot) * sizeof(*p.u);
+    const size_t smem = (size_t)p.cols * col_pitch(p.ktot, 0) * sizeof(*p.u);
     const int rc = ensure_lds(kernel, smem, kernel_name);
     if (rc) return rc;
     const int64_t grid = (p.ncols + p.cols - 1) / p.cols;         // (checked against INT32_MAX by vad_family_args, before cmax is zeroed)

@@ -1,7 +1,7 @@
 // spc_vmix.hpp -- K25: one backward-Euler step of the vertical mixing of the device-resident LES fields by each column's OWN eddy
 // viscosity (K24's km), with the kinematic surface fluxes of K15 and a neutral bulk drag on the lowest wind level, kernels and
 // host side.  spc_hip.hip includes it twice, like spc_diffuse.hpp: with the kernels among the device headers (after
-// spc_diffuse.hpp, whose dif_move and dif_pitch it reuses), and -- SPC_VMIX_HOST defined -- after spc_launch.hpp and the host
+// spc_diffuse.hpp, whose DIF_U and DIF_UB it reuses), and -- SPC_VMIX_HOST defined -- after spc_launch.hpp and the host
 // side of spc_slab.hpp (slab_check_extents).
 //
 // Fields are [n_les][itot][jtot][ktot], C order, ktot contiguous, 64-bit element offsets (spc_slab.hpp).  The matrix of the step
@@ -19,29 +19,19 @@
 // The winds are updated in place by other workgroups, so the speed of the drag is not read from u and v during the solve: the
 // entry point is TWO launches, as K21's and K24's.  k_les_speed (one lane per column) writes sp whole into the caller's plane
 // speed [n_les][itot][jtot]; then k_les_vmix runs.
-// k_les_vmix has K15's shape: a workgroup takes C consecutive columns of one field (blockIdx.y), loads the km run and the field
-// run coalesced (dif_move) into TWO LDS tiles of the odd pitch ktot | 1, and lane c < C eliminates column c: in the forward sweep
-// q[k] overwrites km[k] once km[k+1] is in a register, and y overwrites x; the back substitution reads both.  l is per lane: a
-// tile may span several LES.  el, eu and kb do not depend on the chain: the reads of chunk j + 1 (8 levels, 4 in f64) are issued
-// before the arithmetic of chunk j, as are the LDS reads of x and km; where a tile spans at most DIF_STAGE LES and the LDS
-// budget has room, their rows are copied into LDS behind the tiles (K15's staging).  Every field of a launch repeats the
-// elimination of its class (the division runs in lanes that would otherwise idle) so that no pivot travels through memory.
-// C is the largest of 64, 32, 16 whose two tiles fit K15's budgets (160 levels: 32 columns of f32, 16 of f64).
+// k_les_vmix is the column tile of spc_coltile.hpp with (tiles, faces) = (2, 0), one field per blockIdx.y: the km run and the
+// field run are copied into the two tiles (col_move), and lane c < C eliminates column c: in the forward sweep q[k] overwrites
+// km[k] once km[k+1] is in a register, and y overwrites x; the back substitution reads both.  l is per lane: a tile may span
+// several LES.  el, eu and kb do not depend on the chain: the reads of chunk j + 1 (8 levels, 4 in f64) are issued before the
+// arithmetic of chunk j, as are the LDS reads of x and km; where a tile spans at most DIF_STAGE LES and the LDS budget has room,
+// their rows are staged in LDS behind the tiles (K15's staging).  Every field of a launch repeats the elimination of its class (the
+// division runs in lanes that would otherwise idle) so that no pivot travels through memory.  At 160 levels: 32 columns of f32,
+// 16 of f64.
 #ifndef SPC_VMIX_HOST
 
 constexpr int VMIX_MAXF = 6;
 constexpr int VMIX_THREADS = 256;
 constexpr int VMIX_U64 = 4;                     // levels per chunk of a sweep in f64: three workgroups per CU need at most 168 VGPRs
-
-// columns per workgroup of ktot levels of esize bytes, 0: unsupported
-inline int vmix_cols(int ktot, int esize)
-{
-    if (ktot < 1 || (esize != 4 && esize != 8) || ktot > HARD_LDS_BYTES / 32 / esize) return 0;
-    const int64_t col = (int64_t)2 * dif_pitch(ktot) * esize;
-    if (64 * col <= DIF_LDS_SHARED) return 64;
-    if (32 * col <= DIF_LDS_SHARED) return 32;
-    return 16 * col <= HARD_LDS_BYTES ? 16 : 0;
-}
 
 template <typename T> struct LesVmixP {
     T *field[VMIX_MAXF];
@@ -185,21 +175,20 @@ __device__ __forceinline__ void vmix_column(T *x, T *kq, const T *el, const T *e
     }
 }
 
-// grid (ceil(ncols / C), n_fields); dynamic LDS: 2 * C * dif_pitch(ktot) elements, and 3 * DIF_STAGE * ktot more where p.stage
+// grid (ceil(ncols / C), n_fields); dynamic LDS: 2 * C * col_pitch(ktot, 0) elements, and 3 * DIF_STAGE * ktot more where p.stage
 template <typename T, int C> __global__ __launch_bounds__(VMIX_THREADS, 3) void k_les_vmix(const LesVmixP<T> p)
 {
-    static_assert(VMIX_THREADS == DIF_THREADS, "dif_move walks the run with DIF_THREADS lanes");
     extern __shared__ __align__(16) unsigned char vmix_lds[];
     const int f = blockIdx.y;
-    const int ktot = p.ktot, P = dif_pitch(ktot);
+    const int ktot = p.ktot, P = col_pitch(ktot, 0);
     T *xt = reinterpret_cast<T *>(vmix_lds);
     T *kt = xt + C * P;
     const int64_t col0 = (int64_t)blockIdx.x * C;
     const int64_t left = p.ncols - col0;
     const int nc = left < C ? (int)left : C;                         // the last tile is partial
     T *run = p.field[f] + col0 * ktot;
-    dif_move<T, false>(run, xt, nc * ktot, ktot, P);
-    dif_move<T, false>(const_cast<T *>(p.km) + col0 * ktot, kt, nc * ktot, ktot, P);      // a load: km is not written
+    col_move<T, VMIX_THREADS, DIF_UB, false>(run, xt, nc * ktot, ktot, P);
+    col_move<T, VMIX_THREADS, DIF_UB, false>(const_cast<T *>(p.km) + col0 * ktot, kt, nc * ktot, ktot, P);      // a load: km is not written
     // the rows of el, eu and kb of the tile's LES, [3][DIF_STAGE][ktot] behind the tiles, where the tile spans at most p.stage LES
     const int64_t l0 = col0 / p.nij;
     const int nl = (int)((col0 + nc - 1) / p.nij - l0) + 1;
@@ -241,24 +230,10 @@ template <typename T, int C> __global__ __launch_bounds__(VMIX_THREADS, 3) void 
         }
     }
     __syncthreads();
-    dif_move<T, true>(run, xt, nc * ktot, ktot, P);
+    col_move<T, VMIX_THREADS, DIF_UB, true>(run, xt, nc * ktot, ktot, P);
 }
 
 #else  // SPC_VMIX_HOST ------------------------------------------------------------------------------------------------------
-
-template <typename T, int C> static int les_vmix_launch(const LesVmixP<T> &p, int n_fields, void *stream)
-{
-    const size_t tiles = (size_t)2 * C * dif_pitch(p.ktot) * sizeof(T), rows = (size_t)3 * DIF_STAGE * p.ktot * sizeof(T);
-    LesVmixP<T> q = p;
-    q.stage = tiles + rows <= (size_t)(C == 16 ? HARD_LDS_BYTES : DIF_LDS_SHARED) ? DIF_STAGE : 0;
-    const size_t smem = tiles + (q.stage ? rows : 0);
-    const int rc = ensure_lds(k_les_vmix<T, C>, smem, "k_les_vmix");
-    if (rc) return rc;
-    const int64_t grid = (p.ncols + C - 1) / C;
-    if (grid > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_vmix: too many workgroups");
-    hipLaunchKernelGGL((k_les_vmix<T, C>), dim3((unsigned)grid, (unsigned)n_fields), dim3(VMIX_THREADS), smem, (hipStream_t)stream, q);
-    return launch_status("k_les_vmix");
-}
 
 template <typename T> static int les_vmix_impl(const spc_les_vmix_args *a, void *stream)
 {
@@ -305,10 +280,10 @@ template <typename T> static int les_vmix_impl(const spc_les_vmix_args *a, void 
         bits |= (uintptr_t)a->u | (uintptr_t)a->v | (uintptr_t)a->speed;
     }
     if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_vmix: a pointer is not aligned to its element type");
-    const int C = vmix_cols(a->ktot, (int)sizeof(T));
+    const int C = col_cols(a->ktot, (int)sizeof(T), 2, 0);
     if (!C)
         return fail(SPC_ERR_UNSUPPORTED, "%sles_vmix: ktot %lld above the %lld levels of which 16 columns fit the LDS twice", "", (long long)a->ktot,
-                    (long long)(((HARD_LDS_BYTES / 32 / (int)sizeof(T)) - 1) | 1));
+                    (long long)col_max_ktot((int)sizeof(T), 2, 0));
     p.km = (const T *)a->km; p.kb = (const T *)a->kb; p.kv2 = (const T *)a->kv2; p.s0 = (const T *)a->s0;
     p.u = (const T *)a->u; p.v = (const T *)a->v; p.speed = (T *)a->speed;
     p.nij = a->itot * a->jtot;
@@ -321,8 +296,9 @@ template <typename T> static int les_vmix_impl(const spc_les_vmix_args *a, void 
         hipLaunchKernelGGL((k_les_speed<T>), dim3((unsigned)grid), dim3(VMIX_THREADS), 0, (hipStream_t)stream, p);
         if ((rc = launch_status("k_les_speed"))) return rc;
     }
-    return C == 64 ? les_vmix_launch<T, 64>(p, a->n_fields, stream) : C == 32 ? les_vmix_launch<T, 32>(p, a->n_fields, stream)
-                                                                             : les_vmix_launch<T, 16>(p, a->n_fields, stream);
+    return col_dispatch(C, [&](auto c) {
+        return col_stage_launch<T>(k_les_vmix<T, decltype(c)::value>, "k_les_vmix", "les_vmix", p, C, 2, a->n_fields, VMIX_THREADS, stream);
+    });
 }
 
 #endif

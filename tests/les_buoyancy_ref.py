@@ -296,6 +296,26 @@ def check_alignment(eng, leads, ktot=65, pad=0):
     Run(eng, c, leads=leads, pad=pad).check("leads %s pad %d ktot %d" % (leads, pad, ktot))
 
 
+COLTILE_KTOTS = (1, 2, 7, 8, 9, 17)
+
+
+def check_coltile(eng):
+    """the cases of the column tile (spc_coltile.hpp) together: 3 LES of 3 x 5 (one partial tile that spans three LES, more than
+    DIF_STAGE) and 6 of them (a whole 64-column tile that spans five LES, then a partial one); ktot 1, 2, 7, 8, 9 and 17, and at
+    n = 3 the last ktot of every C and the first of the next; thl, qt, ql and phi led by 0 ... V - 1 elements, equally and each on its own (coltile_leads of les_radiate_ref);
+    the bytes around every array are looked at by Run.check"""
+    dtype = np_of(eng)
+    V = 16 // numpy.dtype(dtype).itemsize
+    for n in (3, 6):
+        for ktot in COLTILE_KTOTS:
+            for leads in lrr.coltile_leads(V, 4):
+                Run(eng, case((n, 3, 5, ktot), dtype, seed=11 + sum(leads)), leads=leads).check("coltile n %d ktot %d leads %s" % (n, ktot, leads))
+    first, changes, bad = cols_table(eng.buoyancy_cols_per_block)
+    for ktot in [k for c in changes for k in (c - 1, c)] + [bad - 1]:
+        for leads in ((0, 0, 0, 0), (1, 1, 1, 1), (0, 1, 0, 0)):
+            Run(eng, case((3, 3, 5, ktot), dtype, seed=12), leads=leads).check("coltile C %d ktot %d leads %s" % (eng.buoyancy_cols_per_block(ktot), ktot, leads))
+
+
 def uniform_case(dtype, shape=(2, 3, 4, 9)):
     """a state that is uniform on every level of every LES; some winds are -0.0"""
     c = case(shape, dtype, seed=7)
@@ -431,13 +451,14 @@ def check_multi(one, multi, n):
     return blocks_of(t["u"], multi, n)
 
 
-BODIES = ("parity", "rows", "tiles", "strips", "outputs", "alignment", "special", "refusals")
+BODIES = ("parity", "rows", "tiles", "coltile", "strips", "outputs", "alignment", "special", "refusals")
 
 
 def jobs(eng):
     return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 65)]),
             ("rows", lambda: [check_rows(eng, k) for k in (2, 65)]),
             ("tiles", lambda: check_tiles(eng)),
+            ("coltile", lambda: check_coltile(eng)),
             ("strips", lambda: check_strips(eng)),
             ("outputs", lambda: check_outputs(eng)),
             ("alignment", lambda: [check_alignment(eng, *a) for a in (((1, 1, 1, 1), 65, 0), ((1, 0, 3, 2), 64, 0), ((3, 3, 3, 1), 7, 5))]),

@@ -246,6 +246,25 @@ def check_alignment(eng, lead, lead_rows, pad, ktot=65):
     Run(eng, c, lead=lead, lead_rows=lead_rows, pad=pad).check("lead %d %d pad %d ktot %d" % (lead, lead_rows, pad, ktot))
 
 
+COLTILE_KTOTS = (1, 2, 7, 8, 9, 17)
+
+
+def check_coltile(eng):
+    """the cases of the column tile (spc_coltile.hpp) together: 3 LES of 3 x 5 (one partial tile that spans three LES, more than
+    DIF_STAGE) and 6 of them (a whole 64-column tile that spans five LES, then a partial one); ktot 1, 2, 7, 8, 9 and 17, and at
+    n = 3 the last ktot of every C and the first of the next; every field 0 ... V - 1 elements off the 16-byte grid (V elements are 16 bytes);
+    the bytes around every array are looked at by Run.check"""
+    dtype = np_of(eng)
+    V = 16 // numpy.dtype(dtype).itemsize
+    for n in (3, 6):
+        for ktot in COLTILE_KTOTS:
+            for lead in range(V):
+                Run(eng, case((n, 3, 5, ktot), dtype, seed=11 + lead), lead=lead).check("coltile n %d ktot %d lead %d" % (n, ktot, lead))
+    for ktot, cols in boundaries(eng.diffuse_cols_per_block):
+        for lead in (0, 1) if cols else ():
+            Run(eng, case((3, 3, 5, ktot), dtype, seed=12, names=("THL", "QT")), lead=lead).check("coltile C %d ktot %d lead %d" % (cols, ktot, lead))
+
+
 def check_long_step(eng):
     """dt = 3600: |a| in the hundreds"""
     for ktot in (7, 160):
@@ -353,7 +372,7 @@ def check_multi(one, multi, n):
     return blocks_of(t["QT"], multi, n)
 
 
-BODIES = ("parity", "rows", "boundaries", "tiles", "fields", "alignment", "long_step", "special", "refusals")
+BODIES = ("parity", "rows", "boundaries", "tiles", "coltile", "fields", "alignment", "long_step", "special", "refusals")
 
 
 def jobs(eng):
@@ -361,6 +380,7 @@ def jobs(eng):
             ("rows", lambda: [check_rows(eng, k) for k in (1, 7, 160)]),
             ("boundaries", lambda: check_boundaries(eng)),
             ("tiles", lambda: [check_tiles(eng, k) for k in (7, 300)]),
+            ("coltile", lambda: check_coltile(eng)),
             ("fields", lambda: check_fields(eng)),
             ("alignment", lambda: [check_alignment(eng, *a) for a in ((1, 0, 0), (0, 1, 0), (0, 0, 3), (3, 1, 5))]),
             ("long_step", lambda: check_long_step(eng)),

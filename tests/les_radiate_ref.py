@@ -275,6 +275,34 @@ def check_alignment(eng, leads, ktot=65, pad=0):
     Run(eng, c, leads=leads, pad=pad).check("leads %s pad %d ktot %d" % (leads, pad, ktot))
 
 
+COLTILE_KTOTS = (1, 2, 7, 8, 9, 17)
+
+
+def coltile_leads(V, arrays):
+    """leads of ``arrays`` 4-D arrays: all equal, 0 ... V - 1 (the 16-byte walk with a head and a tail), then one array at a time
+    1 ... V - 1 off the others, and all different (vec == 0: single elements)"""
+    equal = [(lead,) * arrays for lead in range(V)]
+    one = [tuple(lead if a == b else 0 for b in range(arrays)) for a in range(arrays) for lead in range(1, V)]
+    return equal + one + [tuple((a + 1) % V for a in range(arrays))]
+
+
+def check_coltile(eng):
+    """the cases of the column tile (spc_coltile.hpp) together: 3 LES of 3 x 5 (one partial tile that spans three LES, more than
+    DIF_STAGE) and 6 of them (a whole 64-column tile that spans five LES, then a partial one); ktot 1, 2, 7, 8, 9 and 17, and at
+    n = 3 the last ktot of every C and the first of the next; ql, thl and flux led by 0 ... V - 1 elements, equally and each on its own (coltile_leads);
+    the bytes around every array are looked at by Run.check"""
+    dtype = np_of(eng)
+    V = 16 // numpy.dtype(dtype).itemsize
+    for n in (3, 6):
+        for ktot in COLTILE_KTOTS:
+            for leads in coltile_leads(V, 3):
+                Run(eng, case((n, 3, 5, ktot), dtype, seed=11 + sum(leads)), leads=leads).check("coltile n %d ktot %d leads %s" % (n, ktot, leads))
+    first, changes, bad = cols_table(eng.radiate_cols_per_block)
+    for ktot in [k for c in changes for k in (c - 1, c)] + [bad - 1]:
+        for leads in ((0, 0, 0), (1, 1, 1), (1, 0, 0)):
+            Run(eng, case((3, 3, 5, ktot), dtype, seed=12), leads=leads).check("coltile C %d ktot %d leads %s" % (eng.radiate_cols_per_block(ktot), ktot, leads))
+
+
 def check_clouds(eng):
     """a clear sky keeps every bit of thl (-0.0 included) and F = f0 + f1 everywhere; one cloudy cell at the bottom, at the top
     and in the middle and a deck: the topmost cloudy cell cools; with f0 = 0 and cloud from k0 up the cells below k0 keep
@@ -447,13 +475,14 @@ def check_multi(one, multi, n):
     return blocks_of(t["thl"], multi, n)
 
 
-BODIES = ("parity", "rows", "tiles", "outputs", "alignment", "clouds", "lookup", "special", "refusals")
+BODIES = ("parity", "rows", "tiles", "coltile", "outputs", "alignment", "clouds", "lookup", "special", "refusals")
 
 
 def jobs(eng):
     return [("parity", lambda: [check_parity(eng, p, k) for p in PLANES for k in (1, 2, 7, 161)]),
             ("rows", lambda: [check_rows(eng, k) for k in (2, 65)]),
             ("tiles", lambda: check_tiles(eng)),
+            ("coltile", lambda: check_coltile(eng)),
             ("outputs", lambda: check_outputs(eng)),
             ("alignment", lambda: [check_alignment(eng, *a) for a in (((1, 1, 1), 65, 0), ((1, 0, 3), 64, 0), ((3, 3, 3), 7, 5))]),
             ("clouds", lambda: check_clouds(eng)),

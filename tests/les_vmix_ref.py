@@ -292,6 +292,26 @@ def check_alignment(eng, leads, ktot=65, pad=0):
     Run(eng, c, ("U", "THL", "X"), leads=leads, pad=pad).check("leads %s pad %d ktot %d" % (leads, pad, ktot))
 
 
+COLTILE_KTOTS = (1, 2, 7, 8, 9, 17)
+
+
+def check_coltile(eng):
+    """the cases of the column tile (spc_coltile.hpp) together: 3 LES of 3 x 5 (one partial tile that spans three LES, more than
+    DIF_STAGE) and 6 of them (a whole 64-column tile that spans five LES, then a partial one); ktot 1, 2, 7, 8, 9 and 17, and at
+    n = 3 the last ktot of every C and the first of the next; the six fields and km led by 0 ... V - 1 elements, equally and each another way;
+    the bytes around every array are looked at by Run.check"""
+    dtype = np_of(eng)
+    V = 16 // numpy.dtype(dtype).itemsize
+    for n in (3, 6):
+        for ktot in COLTILE_KTOTS:
+            for leads in [(lead,) for lead in range(V)] + [tuple(range(1, V)) + (0,)]:
+                Run(eng, case((n, 3, 5, ktot), dtype, seed=11 + sum(leads)), leads=leads).check("coltile n %d ktot %d leads %s" % (n, ktot, leads))
+    first, changes, bad = cols_table(eng.vmix_cols_per_block)
+    for ktot in [k for c in changes for k in (c - 1, c)] + [bad - 1]:
+        for leads in ((0,), (1,)):
+            Run(eng, case((3, 3, 5, ktot), dtype, seed=12), ("U", "THL", "X"), leads=leads).check("coltile C %d ktot %d leads %s" % (eng.vmix_cols_per_block(ktot), ktot, leads))
+
+
 COLUMN = (1, 2, 1)                                                 # (l, i, j) of the column that is special
 
 
@@ -480,13 +500,14 @@ def check_multi(one, multi, n):
     return blocks_of(t["U"], multi, n)
 
 
-BODIES = ("parity", "tiles", "alignment", "viscosity", "boundary", "special", "fields", "refusals")
+BODIES = ("parity", "tiles", "coltile", "alignment", "viscosity", "boundary", "special", "fields", "refusals")
 ALIGNMENTS = [((1, 2, 3), 65, 0), ((3, 3, 3), 64, 0), ((1, 0, 2, 3), 161, 2), ((2, 1), 7, 5)]
 
 
 def jobs(eng):
     return [("parity", lambda: [check_parity(eng, k) for k in (1, 2, 3, 7, 64)]),
             ("tiles", lambda: check_tiles(eng)),
+            ("coltile", lambda: check_coltile(eng)),
             ("alignment", lambda: [check_alignment(eng, *a) for a in ALIGNMENTS]),
             ("viscosity", lambda: check_viscosity(eng)),
             ("boundary", lambda: check_boundary(eng)),

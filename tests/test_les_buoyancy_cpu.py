@@ -376,3 +376,10 @@ def test_without_enable_buoyancy_nothing_changes(variant):
     old = lbr.ensemble_run(lbr.lrr.RadiateOracleEngine(), 4, True, buoyancy=None, **lbr.VARIANTS[variant])[1]
     lbr.lmr.same_logs(old, new)
     assert "les_buoyancy" not in calls
+
+
+def test_the_column_tile_cases_on_the_oracle_backed_engine(lib):
+    """the plumbing of the coltile body runs without a GPU; the columns per workgroup are the library's"""
+    eng = lbr.BuoyancyOracleEngine()
+    eng.buoyancy_cols_per_block = lambda ktot: lib.spc_les_buoyancy_cols_per_block(ktot, numpy.dtype(lbr.np_of(eng)).itemsize)
+    lbr.check_coltile(eng)

@@ -49,6 +49,12 @@ def test_every_boundary_of_the_tiles(dtype):
 
 
 @pytest.mark.parametrize("dtype", lbr.DTYPES)
+def test_the_column_tile_cases(dtype):
+    """tiles that span three and five LES, ktot 1 ... 17 and at every change of C, every lead off the 16-byte grid"""
+    lbr.check_coltile(Engine("cuda:0", dtype=dtype))
+
+
+@pytest.mark.parametrize("dtype", lbr.DTYPES)
 def test_strip_seams_of_the_gradient_kernel(dtype):
     """jtot * ktot one below, at and one above a strip of k_les_pgrad, at itot = 1, 2, 3, 8, 9, 33"""
     strip, rows = lbr.check_strips(Engine("cuda:0", dtype=dtype))

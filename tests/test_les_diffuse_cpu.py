@@ -315,3 +315,10 @@ def test_enable_diffusion_refuses_what_it_cannot_take_and_uploads_only_what_chan
     old.set_fields_batched("QT", numpy.zeros((2, 2, 2, 6)))
     with pytest.raises(ValueError, match="les_diffuse"):
         old.enable_diffusion()
+
+
+def test_the_column_tile_cases_on_the_oracle_backed_engine(lib):
+    """the plumbing of the coltile body runs without a GPU; the columns per workgroup are the library's"""
+    eng = ldr.DiffuseOracleEngine()
+    eng.diffuse_cols_per_block = lambda ktot: lib.spc_les_diffuse_cols_per_block(ktot, numpy.dtype(ldr.np_of(eng)).itemsize)
+    ldr.check_coltile(eng)

@@ -52,6 +52,12 @@ def test_whole_and_partial_tiles(ktot, dtype):
 
 
 @pytest.mark.parametrize("dtype", ldr.DTYPES)
+def test_the_column_tile_cases(dtype):
+    """tiles that span three and five LES, ktot 1 ... 17 and at every change of C, every lead off the 16-byte grid"""
+    ldr.check_coltile(Engine("cuda:0", dtype=dtype))
+
+
+@pytest.mark.parametrize("dtype", ldr.DTYPES)
 def test_field_counts_and_optional_fluxes(dtype):
     ldr.check_fields(Engine("cuda:0", dtype=dtype))
 

@@ -413,3 +413,10 @@ def test_without_enable_radiation_nothing_changes(variant):
     old = lrr.ensemble_run(lrr.lvr.VadvectOracleEngine(), 4, True, radiate=None, **lrr.VARIANTS[variant])[1]
     lrr.lmr.same_logs(old, new)
     assert "les_radiate" not in calls
+
+
+def test_the_column_tile_cases_on_the_oracle_backed_engine(lib):
+    """the plumbing of the coltile body runs without a GPU; the columns per workgroup are the library's"""
+    eng = lrr.RadiateOracleEngine()
+    eng.radiate_cols_per_block = lambda ktot: lib.spc_les_radiate_cols_per_block(ktot, numpy.dtype(lrr.np_of(eng)).itemsize)
+    lrr.check_coltile(eng)

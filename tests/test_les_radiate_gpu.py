@@ -47,6 +47,12 @@ def test_every_boundary_of_the_tiles(dtype):
 
 
 @pytest.mark.parametrize("dtype", lrr.DTYPES)
+def test_the_column_tile_cases(dtype):
+    """tiles that span three and five LES, ktot 1 ... 17 and at every change of C, every lead off the 16-byte grid"""
+    lrr.check_coltile(Engine("cuda:0", dtype=dtype))
+
+
+@pytest.mark.parametrize("dtype", lrr.DTYPES)
 def test_with_and_without_flux_and_fsfc(dtype):
     lrr.check_outputs(Engine("cuda:0", dtype=dtype))
 

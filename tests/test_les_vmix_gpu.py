@@ -31,6 +31,12 @@ def test_vertical_mixing_equals_the_oracle(ktot, dtype):
 
 
 @pytest.mark.parametrize("dtype", lvr.DTYPES)
+def test_the_column_tile_cases(dtype):
+    """tiles that span three and five LES, ktot 1 ... 17 and at every change of C, every lead off the 16-byte grid"""
+    lvr.check_coltile(Engine("cuda:0", dtype=dtype))
+
+
+@pytest.mark.parametrize("dtype", lvr.DTYPES)
 def test_tiles_of_64_32_and_16_columns(dtype):
     """42 columns in LES of 6 around every change of the columns per workgroup, the largest supported ktot, the refusal above it"""
     first, changes, bad = lvr.check_tiles(Engine("cuda:0", dtype=dtype))

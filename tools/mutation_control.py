@@ -390,7 +390,7 @@ RADIATE_MUTANTS = {
         [(RADIATE, "min((int)s, n_tab - 2)", "min((int)s, n_tab - 1)"),
          (RADIATE, "const T d = etab[m + 1] - e0;", "const T d = etab[m + 1 < n_tab ? m + 1 : m] - e0;")]),
     7: ("K18 l: the LES of the tile's first column for the f0 and f1 of every lane", radiate_body("rows"),
-        [(RADIATE, "const int64_t l = l0 + (rem0 + (uint32_t)c) / (uint32_t)p.nij;", "const int64_t l = l0;")]),
+        [(RADIATE, "const int64_t l = tr.l0 + (tr.rem0 + (uint32_t)c) / (uint32_t)p.nij;", "const int64_t l = tr.l0;")]),
     8: ("K18 lookup: the clamp at x_hi dropped (the last segment extrapolated)", radiate_body("lookup"),
         [(RADIATE, "const T xc = x < (T)0 ? (T)0 : (x > x_hi ? x_hi : x);", "const T xc = x < (T)0 ? (T)0 : x;")]),
 }
@@ -756,7 +756,7 @@ TRANSPORT_MUTANTS = {
     7: ("K22 cmax: the outflow sum without its vertical part", transport_body("probe"),
         [(TRANSPORT, "const T s = sh + sv;", "const T s = sh;")]),
     8: ("K22 ftop: taken from Fb (what entered the top cell from below)", transport_body("fields"),
-        [(TRANSPORT, "p.ftop[f * p.ncols + col0 + w.c] = Ft;", "p.ftop[f * p.ncols + col0 + w.c] = Fb;")]),
+        [(TRANSPORT, "p.ftop[f * p.ncols + tr.col0 + w.c] = Ft;", "p.ftop[f * p.ncols + tr.col0 + w.c] = Fb;")]),
 }
 
 
