@@ -231,7 +231,11 @@ int spc_variability_nudge_f32(const spc_vnudge_args *args, void *stream);
  * (one column); arrays are [n_rows x n] with an element pitch between rows; where stated a pitch of 0 means ONE row
  * shared by all rows (the LES grid).  Results are bit-identical to NumPy for interp / searchsorted / integral /
  * interp_c / interp_rho / rms; exner / iexner agree with numpy.power to <= 2 ulp.  Row pitches must stay below 2^24
- * elements (SPC_ERR_UNSUPPORTED otherwise): the kernels address a slab of rows with 24-bit multiplies.                */
+ * elements (SPC_ERR_UNSUPPORTED otherwise): the kernels address a slab of rows with 24-bit multiplies.  A launch of ONE
+ * row is exempt (its pitch is never multiplied), but the row itself must stay below 2^32 bytes, because elements are
+ * addressed with 32-bit byte offsets: interp serves one row of up to 2^29 - 1 points (float: 2^30 - 1), searchsorted of up to
+ * 2^29 - 1 keys (its indices are int64), interp_c of up to 2^29 - 2 layers (float: 2^30 - 2); SPC_ERR_UNSUPPORTED beyond.
+ * spc_sputils_describe_launch (below, beside spc_describe_launch) tells which kernel and slab height a launch takes.   */
 
 /* sputils.exner (inverse == 0) / iexner (inverse != 0), splib/sputils.py:28-34: out[i] = (p[i]/pref0)**(+-rd/cp)   */
 int spc_exner_f64(int64_t n, const void *p, void *out, int32_t inverse, void *stream);
@@ -1157,6 +1161,21 @@ int spc_pick_cols_per_block(const spc_dims *dims, int pass);
  * dispatch table and require that every instantiation it reaches is bit-checked (tests/test_dispatch_gpu.py).
  * Writes at most buflen-1 characters + NUL; returns the length of the full text or a negative spc_status. */
 int spc_describe_launch(const spc_dims *dims, int pass, int flags, int elem_size, char *buf, int buflen);
+/* The same for the K7 operators above: which instantiation a launch of spc_exner_* ... spc_rms_* takes, with how many rows per
+ * workgroup (the slab height `rb`; 32 for rms, 0 for exner), e.g.
+ *   "k_interp<f64,sl=7,wt=1> rb=8 grid=4465 lds=14144 cus=256"
+ *   "k_interp_c<f64,pd=1,sl=8,w=1,wt=1> rb=9 ..."   "k_searchsorted<f32,sl=0,wt=0> ..."   "k_rms<f64,pd=2,wt=1> ..."   "k_exner<f32,wt=1> ..."
+ * (template arguments as the kernel tables index them: sl = unrolled search depth, 0 run-time trip count, -1 rows read from
+ *  global memory; pd = unrolled depth of numpy's pairwise sum, -1 explicit stack; w = weighted; wt = write-through stores;
+ *  "none": nothing to launch).  op: SPC_SU_*; elem_size 8 or 4; args: the operator's own argument block (spc_interp_args,
+ * spc_searchsorted_args, spc_interp_c_args; NULL for exner and rms), of which only the extents, pitches, mode and whether rho is
+ * NULL are read -- no pointer is dereferenced and no device is needed; n_rows, n, pitch: the scalars of spc_rms_* (n: those of
+ * spc_exner_*), ignored otherwise.  The text comes from the very functions the launchers choose with (tests/sputils_slabs.py
+ * asserts the slab height of every launch it checks).  Refusals of the launchers that are no pointer checks are returned
+ * here too.  Writes at most buflen-1 characters + NUL; returns the length of the full text or a negative spc_status. */
+enum { SPC_SU_EXNER = 0, SPC_SU_INTERP = 1, SPC_SU_SEARCHSORTED = 2, SPC_SU_INTERP_C = 3, SPC_SU_RMS = 4 };
+int spc_sputils_describe_launch(int32_t op, int32_t elem_size, const void *args, int64_t n_rows, int64_t n, int64_t pitch,
+                                char *buf, int32_t buflen);
 /* Bytes of spc_vnudge_args.work spc_variability_nudge_f64 wants for these extents (n_cols*2*itot*jtot*ktot*8: qt and
  * qsat transposed to contiguous planes; required for planes of more than ~9 000 points); negative spc_status on bad
  * extents. */

@@ -322,6 +322,7 @@ PROTOTYPES = {
     "spc_pick_cols_per_block": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int]),
     "spc_describe_launch": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
                                            ctypes.c_int]),
+    "spc_sputils_describe_launch": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, ctypes.c_char_p, c_int32]),
     "spc_vnudge_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
     "spc_vnudge_workspace_bytes_f32": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
 }
@@ -366,6 +367,20 @@ def describe_launch(lib, dims, pass_, flags=1, elem_size=8):
     """text of spc_describe_launch (include/spc.h): the kernel instantiation + launch shape chosen for ``dims``"""
     buf = ctypes.create_string_buffer(256)
     rc = lib.spc_describe_launch(ctypes.byref(dims), pass_, flags, elem_size, buf, len(buf))
+    if rc < 0:
+        check(lib, rc)
+    return buf.value.decode()
+
+
+SPC_SU_EXNER, SPC_SU_INTERP, SPC_SU_SEARCHSORTED, SPC_SU_INTERP_C, SPC_SU_RMS = range(5)
+
+
+def sputils_describe_launch(lib, op, elem_size=8, args=None, n_rows=0, n=0, pitch=0):
+    """text of spc_sputils_describe_launch (include/spc.h): the K7 kernel instantiation and slab height a launch takes; ``args``
+    the operator's argument block (InterpArgs, SearchsortedArgs, InterpCArgs), or the scalars of rms (``n``: of exner)"""
+    buf = ctypes.create_string_buffer(256)
+    rc = lib.spc_sputils_describe_launch(op, elem_size, None if args is None else ctypes.cast(ctypes.pointer(args), c_void_p),
+                                         n_rows, n, pitch, buf, len(buf))
     if rc < 0:
         check(lib, rc)
     return buf.value.decode()

@@ -213,6 +213,10 @@ int spc_interp_c_f64(const spc_interp_c_args *a, void *s) { return interp_c_impl
 int spc_interp_c_f32(const spc_interp_c_args *a, void *s) { return interp_c_impl<float>(a, s); }
 int spc_rms_f64(int64_t nr, int64_t n, int64_t pitch, const void *a, void *out, void *s) { return rms_impl<double>(nr, n, pitch, a, out, s); }
 int spc_rms_f32(int64_t nr, int64_t n, int64_t pitch, const void *a, void *out, void *s) { return rms_impl<float>(nr, n, pitch, a, out, s); }
+int spc_sputils_describe_launch(int32_t op, int32_t es, const void *a, int64_t nr, int64_t n, int64_t pitch, char *buf, int32_t len)
+{
+    return sputils_describe_launch_impl(op, es, a, nr, n, pitch, buf, len);
+}
 
 int spc_point_in_polygon_f64(const spc_pip_args *a, void *s) { return pip_impl(a, s); }
 int spc_haversine_f64(int64_t n, const void *lon, const void *lat, double lon0, double lat0, void *out, void *s)

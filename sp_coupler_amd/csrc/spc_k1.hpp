@@ -23,7 +23,7 @@ __device__ __forceinline__ LesIn<T> load_les(const P &p, int l, int64_t o)
     return r;
 }
 
-constexpr int cfloor_pow2(int n) { int p = 1; while (p * 2 <= n) p *= 2; return p; }
+constexpr int cfloor_pow2(int n) { int p = 1; while (p <= n / 2) p *= 2; return p; }   // (p * 2 <= n overflows from n = 2^30 on: the loop never ended)
 
 // NG / NL != 0: level counts fixed at compile time and contiguous columns (pitch == level count): the
 // flat-index divisions become multiply-shifts, the searches unroll, no pitch registers (hot geometries

@@ -3,6 +3,7 @@ buffers of a ``Run``, the call of a C entry point, the loop over a module's bodi
 mutant library, the two uploads of ``check_multi`` and the ensemble run that the twins and models.DeviceLESEnsemble are
 compared on.  A module supplies what is particular to its kernel: the oracle, ``case``, ``Run``'s call and comparison, its
 bodies, and ``BODIES`` with ``jobs``."""
+import contextlib
 import ctypes
 import os
 
@@ -95,6 +96,22 @@ def abi_call(eng, stem, a):
         rc = fn(ctypes.byref(a), ctypes.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream))
     torch.cuda.synchronize(eng.device)
     return rc
+
+
+@contextlib.contextmanager
+def counted_cus(n):
+    """the library counts ``n`` compute units for the duration (SPC_CUS, read at every launch): with 1 a launch of a few rows
+    gets what thousands get on a whole card -- K14's kernels for MANY waves (tests/les_micro_ref.py), K7's slabs of several rows
+    (tests/sputils_slabs.py)"""
+    old = os.environ.get("SPC_CUS")
+    os.environ["SPC_CUS"] = str(n)
+    try:
+        yield
+    finally:
+        if old is None:
+            del os.environ["SPC_CUS"]
+        else:
+            os.environ["SPC_CUS"] = old
 
 
 # -- bodies ------------------------------------------------------------------------------------------------------------------

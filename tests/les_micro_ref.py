@@ -6,9 +6,6 @@ libraries), the host twin of models.DeviceLESEnsemble's microphysics mode and an
 The oracle spells the rule out one operation per NumPy call in the element type, so nothing fuses.  Every device array of the
 bodies is the LEADING part of a poisoned buffer (tests/les_harness.Poisoned); the bytes behind it (and in front of a view
 off the 16-byte grid) are checked after the launch."""
-import contextlib
-import os
-
 import numpy
 import torch
 
@@ -20,7 +17,7 @@ from tests import les_water_paths_ref as wpr
 from tests import slab_ref
 from tests.gpu_util import assert_bits
 from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
-    DTYPES, NP, Poisoned, abi_call, blocks_of, host_of, np_of, on_both, run_bodies)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, counted_cus, host_of, np_of, on_both, run_bodies)
 from tests.test_vnudge import make_les_fields
 
 PLANES = [(1, 1), (3, 5), (8, 8)]
@@ -359,21 +356,6 @@ def check_multi(one, multi, n):
         for k, name in MEAN_KEYS.items():
             assert_bits("%s %s" % (tag, name), host_of(m[k]), want[name])
     return blocks
-
-
-@contextlib.contextmanager
-def counted_cus(n):
-    """the library counts ``n`` compute units (SPC_CUS, read at every launch): with 1 every launch of more than 4 waves is one
-    of MANY waves and takes the kernels with 2 rows per batch; the tests' sizes otherwise all take those with 4"""
-    old = os.environ.get("SPC_CUS")
-    os.environ["SPC_CUS"] = str(n)
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ["SPC_CUS"]
-        else:
-            os.environ["SPC_CUS"] = old
 
 
 def check_many_waves(eng):

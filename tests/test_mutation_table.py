@@ -91,6 +91,23 @@ def test_k6_mutant_edits_apply_to_the_tree(n):
             assert text != f.read(), (n, name)
 
 
+def test_k7_mutants_are_guarded_by_a_slab_body():
+    from tests import sputils_slabs
+    assert sorted(mc.SPUTILS_MUTANTS) == list(range(1, len(mc.SPUTILS_MUTANTS) + 1)) and len(mc.SPUTILS_MUTANTS) >= 10
+    for n, (what, guard, edits) in mc.SPUTILS_MUTANTS.items():
+        assert what and edits and callable(guard) and all(e[0] in (mc.SU, mc.SU_HOST) for e in edits), n
+        mod, name = guard.__name__.split(".", 1)
+        assert mod == "sputils_slabs" and name in sputils_slabs.BODIES and callable(getattr(sputils_slabs, "check_" + name)), (n, guard.__name__)
+
+
+@pytest.mark.parametrize("n", sorted(mc.SPUTILS_MUTANTS))
+def test_k7_mutant_edits_apply_to_the_tree(n):
+    files = mc.patched(n, table=mc.SPUTILS_MUTANTS)      # raises when an edit's old text does not occur exactly as often as stated
+    for name, text in files.items():
+        with open(os.path.join(mc.CSRC, name)) as f:
+            assert text != f.read(), (n, name)
+
+
 def test_libraries_of_the_tables_do_not_collide():
     libs = [mc.lib_of(n, t) for t in (mc.MUTANTS, mc.ADVANCE_MUTANTS, mc.THERMO_MUTANTS, mc.GEO_MUTANTS, mc.GEO_EQUIVALENT,
                                       mc.LESSTATE_MUTANTS, mc.LESSTATE_EQUIVALENT, mc.VNUDGE_MUTANTS) for n in t]

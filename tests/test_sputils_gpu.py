@@ -174,7 +174,8 @@ def test_row_pitches_of_2_pow_24_elements_are_refused():
     assert numpy.array_equal(got, numpy.interp(long_x.cpu().numpy(), [0.0, 1.0, 2.0], [10.0, 20.0, 30.0]))
     idx = eng.searchsorted(xp, long_x, side="right").cpu().numpy()
     assert numpy.array_equal(idx, numpy.searchsorted([0.0, 1.0, 2.0], long_x.cpu().numpy(), side="right"))
-    # rows padded to millions of elements: the slab height is cut so that 32-bit byte offsets hold (rb * pitch * 8 < 2^32)
+    # rows padded to millions of elements are served.  (With 4 rows a workgroup owns one row, so the cut of the slab height that keeps
+    # rb * pitch * 8 below 2^32 is not reached here: tests/test_sputils_slabs_cpu.py checks it from the launch description.)
     pad = wide.view(-1)[:4 * (2 ** 23)].view(4, 2 ** 23)
     pad[:, :3] = torch.tensor([[10.0, 20.0, 30.0], [1.0, 2.0, 3.0], [5.0, 6.0, 7.0], [-1.0, -2.0, -3.0]], dtype=torch.float64, device="cuda")
     x4 = torch.tensor([[0.5], [1.5], [0.25], [2.0]], dtype=torch.float64, device="cuda")
@@ -444,7 +445,8 @@ def host_(t):
 @pytest.mark.parametrize("nG,nL,per_col,pad", [(91, 160, False, 0), (19, 160, True, 3), (31, 2000, False, 1),
                                                (137, 512, False, 2)])
 def test_float32_interp_c_interp_rho_integral_and_rms(nG, nL, per_col, pad):
-    """the float32 K7 helpers on padded pitches and multi-row slabs (300 rows), against tests/f32_ref.py bit for bit:
+    """the float32 K7 helpers on padded pitches, 300 rows at one row per workgroup (slabs of several rows need 2 048 rows on a
+    whole card: tests/test_sputils_slabs_gpu.py), against tests/f32_ref.py bit for bit:
     interp_c / interp_rho (splib/sputils.py:173-197), integral with and without weights (94-161), rms (23-24, NumPy's own
     lines on float32 data)"""
     from sp_coupler_amd.engine import Engine

@@ -36,6 +36,7 @@ CSRC = os.path.join(ROOT, "sp_coupler_amd", "csrc")
 OUT = os.path.join(ROOT, "build", "mutants")
 K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp", "spc_vnudge2.hpp", "spc_sputils.hpp"
 VN, VN_HOST = "spc_vnudge.hpp", "spc_vnudge_host.hpp"
+SU_HOST = "spc_sputils_host.hpp"
 SLAB = "spc_slab.hpp"
 ADVANCE = "spc_advance.hpp"
 THERMO = "spc_thermo.hpp"
@@ -92,6 +93,7 @@ moments_body = partial(body_guard, "les_moments_ref")
 vnudge_body = partial(body_guard, "vnudge_edges")
 transport_body = partial(body_guard, "les_transport_ref")
 transport2_body = partial(body_guard, "les_transport2_ref")
+sputils_body = partial(body_guard, "sputils_slabs")
 
 
 # n: (the slip, the property of tests/semantic_props.py that guards it -- or a callable guard(engine_of) -> (detected, names of
@@ -807,6 +809,52 @@ VMIX_MUTANTS = {
 }
 
 
+# K7 (spc_sputils.hpp, spc_sputils_host.hpp), numbered on its own; the guards are the slab bodies of tests/sputils_slabs.py.  Every
+# mutant only computes wrong numbers: none reads or writes outside what the shipped kernel touches.
+#  1: the element whose carry is lost stays in its row at entry 0, which the row's walk visits anyway (i > n alone would leave the
+#     row by one entry: not the mutant).  2, 3: row 0 of the slab's own LDS.  4: the x of the thread's CURRENT output once more.
+#  5, 14: element e < nrow * n of a slab whose rows are pitch >= n apart lies in front of the slab's last element.
+#  6: lout[k * nrow + r] is a permutation of lout[r * nG + k] over the slab's nrow * nG results.  7, 8: row 0 of the slab's LDS;
+#     the cell counts stay below nL - 1 because row 0's padded grid ends in NaN like every row's.  9: only the stored VALUE grows
+#     (the count over the NaN padding, at most 2 p2 - 1).  10: a row index is used only below n_rows (`live`), rows of the next
+#     workgroup included, which writes its own values there: wrong either way.  11: the same eight lanes in another order.
+#  12: host only; the launch is right, the height the body asserts is not.  13: r * n_x + i <= r * pitch_out + i.
+SPUTILS_MUTANTS = {
+    1: ("K7 SuWalk::next: the carry lost where the entry lands exactly on n (i > n for i >= n; the entry wraps, the row does not)",
+        sputils_body("walk"),
+        [(SU, "        if (i >= n) { i -= n; ++r; }", "        if (i > n) { i -= n; ++r; } else if (i == n) i = 0;")]),
+    2: ("K7 k_interp: the LDS row of xp of the slab's first row for every row although xp is per row", sputils_body("rows_differ"),
+        [(SU, "const T *const xpr = q.pitch_xp ? lxp + su_mul(r, stride) : lxp;", "const T *const xpr = lxp;")]),
+    3: ("K7 k_interp: fp of the slab's first row for every row", sputils_body("rows_differ"),
+        [(SU, "res = su_interp_pad<SL>(xpr, lfp + su_mul(r, n_xp), n_xp, q.p2, xv);", "res = su_interp_pad<SL>(xpr, lfp, n_xp, q.p2, xv);")]),
+    4: ("K7 k_interp: the one-ahead load of x taken before next() (every later output of a thread sees the x before it)", sputils_body("heights"),
+        [(SU, "        w.next();\n        if (e + SU_THREADS < cnt) xn = ldg(su_at(xb, su_mul(w.r, px) + w.i));",
+          "        if (e + SU_THREADS < cnt) xn = ldg(su_at(xb, su_mul(w.r, px) + w.i));\n        w.next();")]),
+    5: ("K7 su_stage_slab: a pitched slab staged as if its rows were contiguous", sputils_body("last_slab"),
+        [(SU, "    const bool flat = pitch == n;", "    const bool flat = true;")]),
+    6: ("K7 k_interp_c: the results laid out layer-major in LDS, where the store reads them row-major", sputils_body("rows_differ"),
+        [(SU, "if constexpr (STAGE) lout[su_mul(r, nG) + k] = res;", "if constexpr (STAGE) lout[su_mul(k, nrow) + r] = res;")]),
+    7: ("K7 k_interp_c: the weight terms td of the slab's first row for every row", sputils_body("rows_differ"),
+        [(SU, ", *const td = ltd + su_mul(r, nc) + ia;", ", *const td = ltd + ia;")]),
+    8: ("K7 k_interp_c: the staged grid of the slab's first row for every row although zh is per row", sputils_body("rows_differ"),
+        [(SU, "const T *const z = STAGE ? lz + (p.pitch_zh ? su_mul(r, zstride) : 0) : zg + (row0 + r) * p.pitch_zh;",
+          "const T *const z = STAGE ? lz : zg + (row0 + r) * p.pitch_zh;")]),
+    9: ("K7 k_searchsorted: no clamp to n_a (a NaN key counts the NaN padding too)", sputils_body("specials_in_the_slab"),
+        [(SU, "            idx = idx < n_a ? idx : n_a;\n", "")]),
+    10: ("K7 k_rms: the row taken from threadIdx.x >> 2 (four lanes per row where the leaf has eight accumulators)", sputils_body("rms_groups"),
+         [(SU, "(SU_THREADS / 8) + (threadIdx.x >> 3);", "(SU_THREADS / 8) + (threadIdx.x >> 2);")]),
+    11: ("K7 su_leaf8: the eight accumulators combined as ((r0+r4)+(r2+r6))+((r1+r5)+(r3+r7))", sputils_body("rms_groups"),
+         [(SU, "    T s = rj + __shfl_xor(rj, 1);\n    s = s + __shfl_xor(s, 2);\n    s = s + __shfl_xor(s, 4);",
+           "    T s = rj + __shfl_xor(rj, 4);\n    s = s + __shfl_xor(s, 2);\n    s = s + __shfl_xor(s, 1);")]),
+    12: ("K7 su_rows (host): without the fit_rounds step (91 -> 160: 7 rows for 8)", sputils_body("heights"),
+         [(SU_HOST, "    if (fit_rounds && n_out > 0) {", "    if (false && fit_rounds && n_out > 0) {")]),
+    13: ("K7 k_interp: the results stored as if out were contiguous (r * n_x for r * pitch_out)", sputils_body("last_slab"),
+         [(SU, "stg<WT>(su_at(ob, su_mul(r, po) + i), res);", "stg<WT>(su_at(ob, su_mul(r, n_x) + i), res);")]),
+    14: ("K7 k_interp_c: the slab's results stored as if out were contiguous", sputils_body("last_slab"),
+         [(SU, "const bool flat = p.pitch_out == nG;", "const bool flat = true;")]),
+}
+
+
 def _tag(table):
     """(library prefix, source directory prefix) of a table"""
     for t in ALL_TABLES:
@@ -1027,7 +1075,13 @@ LATER_TABLES = (
     Table("mix", MIX_MUTANTS, "K24", "mix_", "mix", "les_mix_ref", "test_les_mix_gpu"),
     Table("vmix", VMIX_MUTANTS, "K25", "vmix_", "vmix", "les_vmix_ref", "test_les_vmix_gpu"),
 )
-ALL_TABLES = TABLES + LATER_TABLES
+#: K7's table stands in a tuple of its own, not at the end of LATER_TABLES: tests/test_les_vmix_mutants_cpu.py pins K25's row as
+#: LATER_TABLES[-1], and tests/test_les_mix_mutants_cpu.py imports the guard module of every row of LATER_TABLES (existing test
+#: files, which a pull request that adds a table leaves as they are).  Same rows, same handling.
+SPUTILS_TABLES = (
+    Table("sputils", SPUTILS_MUTANTS, "K7", "sputils_", "sputils", "sputils_slabs", "test_sputils_slabs_gpu"),
+)
+ALL_TABLES = TABLES + LATER_TABLES + SPUTILS_TABLES
 
 
 if __name__ == "__main__":
