@@ -10,8 +10,7 @@
 //   mean[f]  = numpy.mean(new field[l], axis=(0, 1))[k]  k_slab_means' rule: acc = +0; acc += x over (i, j) in row-major
 //              order in T; one IEEE division by T(itot * jtot).  ql_mean likewise, of q.
 // The sequential sum fixes one dependent add chain of itot * jtot per (f, l, k), as in K10; the chains of different fields are
-// independent: blockIdx.y is the field, a lane owns V adjacent k of one (f, l) (V = 16 B / sizeof(T) where ktot, the pitches
-// and every pointer allow 16-byte accesses, else 1), consecutive lanes consecutive k.  The lanes of sat_field carry the
+// independent: blockIdx.y is the field, a lane owns V adjacent k of one (f, l) (spc_chain.hpp).  The lanes of sat_field carry the
 // QT chain AND the q chain: two input streams (QT, qsat), two output streams (QT, ql), two sums.  A lane stores only the
 // elements it loaded itself, so the in-place update needs no ordering beyond program order.
 // Loads do not depend on the adds: a lane holds TWO batches of rows -- the loads of batch b + 1 are issued before the adds
@@ -61,14 +60,14 @@ __device__ __forceinline__ void adv_row(SlabVec<T, V> x, const SlabVec<T, V> &s,
     }
 }
 
-template <typename T, int V, bool SAT> __device__ __forceinline__ void adv_chain(const LesAdvanceP<T> &p, int f, int64_t l, int k)
+template <typename T, int V, bool SAT> __device__ __forceinline__ void adv_chain(const LesAdvanceP<T> &p, int f, const ChainLane<V> &lane)
 {
     using Vec = SlabVec<T, V>;
     constexpr int U = SAT ? ADV_US : ADV_U;
     const int64_t ktot = p.ktot;
     const int nij = p.nij;
     const bool upd = p.tend[f] != nullptr;
-    const int64_t off = l * nij * ktot + k;
+    const int64_t off = lane.cell(nij, ktot);
     T *dst = p.field[f] + off;
     const T *qs = SAT ? p.qsat + off : nullptr;
     T *ql = SAT && p.ql ? p.ql + off : nullptr;
@@ -76,7 +75,7 @@ template <typename T, int V, bool SAT> __device__ __forceinline__ void adv_chain
 #pragma unroll
     for (int v = 0; v < V; ++v) inc.v[v] = acc.v[v] = accq.v[v] = (T)0;      // numpy starts a sum from add's identity, +0.0
     if (upd) {
-        const Vec t = *reinterpret_cast<const Vec *>(p.tend[f] + l * p.pitch_tend + k);
+        const Vec t = *reinterpret_cast<const Vec *>(lane.row(p.tend[f], p.pitch_tend));
 #pragma unroll
         for (int v = 0; v < V; ++v) inc.v[v] = t.v[v] * p.dt;
     }
@@ -124,16 +123,8 @@ template <typename T, int V, bool SAT> __device__ __forceinline__ void adv_chain
         if (ql) ql += ktot;
     }
     const T cnt = (T)nij;
-    if (p.mean[f]) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) acc.v[v] = acc.v[v] / cnt;  // IEEE division (the build has no fast-math)
-        *reinterpret_cast<Vec *>(p.mean[f] + l * p.pitch_mean + k) = acc;
-    }
-    if (SAT && p.ql_mean) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) accq.v[v] = accq.v[v] / cnt;
-        *reinterpret_cast<Vec *>(p.ql_mean + l * p.pitch_mean + k) = accq;
-    }
+    if (p.mean[f]) *reinterpret_cast<Vec *>(lane.row(p.mean[f], p.pitch_mean)) = chain_mean<T, V>(acc, cnt);
+    if (SAT && p.ql_mean) *reinterpret_cast<Vec *>(lane.row(p.ql_mean, p.pitch_mean)) = chain_mean<T, V>(accq, cnt);
 }
 
 // grid (ceil(chains / ADV_THREADS), n_fields)
@@ -142,13 +133,11 @@ template <typename T, int V> __global__ __launch_bounds__(ADV_THREADS) void k_le
     const int64_t g = (int64_t)blockIdx.x * ADV_THREADS + threadIdx.x;
     if (g >= p.chains) return;
     const int f = blockIdx.y;
-    const int kv = p.ktot / V;
-    const int64_t l = g / kv;
-    const int k = (int)(g - l * kv) * V;
+    const ChainLane<V> lane(g, p.ktot);
     if (f == p.sat_field)
-        adv_chain<T, V, true>(p, f, l, k);
+        adv_chain<T, V, true>(p, f, lane);
     else if (p.tend[f] || p.mean[f])                             // else: nothing of this field is asked for
-        adv_chain<T, V, false>(p, f, l, k);
+        adv_chain<T, V, false>(p, f, lane);
 }
 
 #else  // SPC_ADVANCE_HOST ---------------------------------------------------------------------------------------------------
@@ -161,9 +150,7 @@ template <typename T> static int les_advance_impl(const spc_les_advance_args *a,
     static_assert(SPC_ADVANCE_MAX_FIELDS == ADV_MAXF, "include/spc.h and spc_advance.hpp disagree on the fields per launch");
     if (a->n_fields < 1 || a->n_fields > SPC_ADVANCE_MAX_FIELDS)
         return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_advance: field count %lld outside 1 ... %lld", "", (long long)a->n_fields, SPC_ADVANCE_MAX_FIELDS);
-    if (a->pitch_tend < a->ktot || a->pitch_mean < a->ktot)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_advance: pitch_tend %lld or pitch_mean %lld smaller than ktot", "",
-                    (long long)a->pitch_tend, (long long)a->pitch_mean);
+    if ((rc = chain_pitch(a->ktot, a->pitch_tend, a->pitch_mean, "%sles_advance: pitch_tend %lld or pitch_mean %lld smaller than ktot"))) return rc;
     if (a->sat_field < -1 || a->sat_field >= a->n_fields)
         return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_advance: sat_field %lld outside -1 ... %lld", "", (long long)a->sat_field, (long long)a->n_fields - 1);
     if (a->n_les == 0) return SPC_OK;
@@ -189,21 +176,17 @@ template <typename T> static int les_advance_impl(const spc_les_advance_args *a,
         p.mean[f] = (T *)a->mean[f];
         bits |= (uintptr_t)a->fields[f] | (uintptr_t)a->tend[f] | (uintptr_t)a->mean[f];
     }
-    if (bits % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_advance: a pointer is not aligned to its element type");
-    if (a->ktot == 1)
-        return fail(SPC_ERR_UNSUPPORTED, "%sles_advance: ktot == 1 (numpy reduces a one-level plane pairwise: step the field and call slab_means)");
-    constexpr int VMAX = 16 / (int)sizeof(T);
-    const bool wide = bits % 16 == 0;                 // every row of every field, tendency and mean starts on a 16-byte boundary
+    bool wide; int64_t grid;
+    if ((rc = chain_geometry<T>("les_advance", bits, 0, a->n_les, a->ktot, ADV_THREADS,
+                                "les_advance: ktot == 1 (numpy reduces a one-level plane pairwise: step the field and call slab_means)", wide, p.chains, grid)))
+        return rc;
     p.nij = a->itot * a->jtot;
     p.ktot = a->ktot;
     p.sat_field = a->sat_field;
     p.pitch_tend = a->pitch_tend;
     p.pitch_mean = a->pitch_mean;
     p.dt = (T)a->dt;
-    p.chains = a->n_les * (int64_t)(wide ? a->ktot / VMAX : a->ktot);
-    const int64_t grid = (p.chains + ADV_THREADS - 1) / ADV_THREADS;
-    if (grid > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_advance: too many workgroups");
-    void (*const kern)(const LesAdvanceP<T>) = wide ? k_les_advance<T, VMAX> : k_les_advance<T, 1>;
+    void (*const kern)(const LesAdvanceP<T>) = wide ? k_les_advance<T, CHAIN_V<T>> : k_les_advance<T, 1>;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)a->n_fields), dim3(ADV_THREADS), 0, (hipStream_t)stream, p);
     return launch_status("k_les_advance");
 }

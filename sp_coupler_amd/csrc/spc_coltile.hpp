@@ -1,5 +1,5 @@
 // spc_coltile.hpp -- the LDS column tile of the kernels with a serial chain along k (K15, K17, K18, K21, K22, K23, K25), device
-// and host side.  spc_hip.hip includes it twice: among the device headers before spc_diffuse.hpp (after spc_slab.hpp: SlabVec),
+// and host side.  spc_hip.hip includes it twice: among the device headers before spc_diffuse.hpp (after spc_chain.hpp: SlabVec),
 // and -- SPC_COLTILE_HOST defined -- after spc_launch.hpp (fail, ensure_lds, launch_status).
 //
 // Fields are [n_les][itot][jtot][ktot], C order, ktot contiguous.  A workgroup takes C consecutive columns of the flat column

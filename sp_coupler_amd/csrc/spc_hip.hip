@@ -59,8 +59,10 @@
 //                  lowest wind level from a plane of wind speeds: spc_vmix.hpp, kernels and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp; the LDS column tile of the
 // kernels with a serial chain along k (K15, K17, K18, K21, K22, K23, K25: its geometry, the run of a workgroup, the split of a
-// run into 16-byte vectors, the plain mover, their host checks and launches): spc_coltile.hpp.  Host side of K1-K5 (launch
-// heuristics, kernel tables, launchers, spc_describe_launch's text): spc_launch.hpp.
+// run into 16-byte vectors, the plain mover, their host checks and launches): spc_coltile.hpp; the slab chain of the kernels
+// that sum along (i, j) per (LES, level) (K10, K11, K12, K14, K20: the lane, the zero and the mean of a sum, their host checks
+// and launch geometry): spc_chain.hpp.  Host side of K1-K5 (launch heuristics, kernel tables, launchers,
+// spc_describe_launch's text): spc_launch.hpp.
 // The path is 1-D interpolation over short columns: HBM-bound, no MFMA.  Design:
 // a 256-thread workgroup owns CB consecutive columns; the source profiles of those columns are
 // loaded with flat, fully coalesced accesses over the contiguous [CB x n_lev] slab, converted and
@@ -107,6 +109,7 @@ namespace {
 #include "spc_sputils.hpp"
 #include "spc_geo.hpp"
 #include "spc_lesstate.hpp"
+#include "spc_chain.hpp"
 #include "spc_slab.hpp"
 #include "spc_advance.hpp"
 #include "spc_thermo.hpp"
@@ -134,6 +137,9 @@ namespace {
 #include "spc_vnudge_host.hpp"
 #include "spc_geo_host.hpp"
 #include "spc_lesstate_host.hpp"
+#define SPC_CHAIN_HOST
+#include "spc_chain.hpp"
+#undef SPC_CHAIN_HOST
 #define SPC_SLAB_HOST
 #include "spc_slab.hpp"
 #undef SPC_SLAB_HOST

@@ -12,8 +12,7 @@
 //   qt -= s;   thl += lcpex[l][k] * s;   qr_new = qs + s;   rain[l][i][j] += (so[l][0] * qr[k = 0]) * w[l][0]
 //   fi = temp >= tu ? 0 : (temp <= td ? 1 : (tu - temp) / den);   qi = (ql - s) * fi
 //   means of the new qt, the new thl, qr_new and qi by k_slab_means' rule
-// K11's shape: a lane owns V adjacent k of one LES (V = 16 B / sizeof(T) where ktot, the pitches and every pointer allow
-// 16-byte accesses, else 1), consecutive lanes consecutive k, and walks the itot * jtot rows in row-major order: the
+// K11's shape: a lane owns V adjacent k of one LES (spc_chain.hpp) and walks the itot * jtot rows in row-major order: the
 // sequential slab sums fix that chain.  ONE lane carries all four sums, since they hang on the same s.  qr_up is the lane's
 // own next element for v < V - 1; for its last element it is one extra load of qr[k + V] (nothing for the lane at the top).
 // The lane at k == 0 also carries rain: it loads and stores rain[l][r] with row r.  A lane stores only the elements of qt, thl
@@ -116,20 +115,18 @@ template <typename T, int V, int U> __global__ __launch_bounds__(MIC_THREADS) vo
     using Row = MicRow<T, V>;
     const int64_t g = (int64_t)blockIdx.x * MIC_THREADS + threadIdx.x;
     if (g >= P.chains) return;
-    const int kv = P.ktot / V;
-    const int64_t l = g / kv;
-    const int k = (int)(g - l * kv) * V;
+    const ChainLane<V> lane(g, P.ktot);
     const int64_t ktot = P.ktot;
     const int nij = P.nij;
-    const bool top = k + V >= P.ktot;
-    int64_t off = l * nij * ktot + k;
-    T *rain = k == 0 && P.rain ? P.rain + l * nij : nullptr;
+    const bool top = lane.k + V >= P.ktot;
+    int64_t off = lane.cell(nij, ktot);
+    T *rain = lane.k == 0 && P.rain ? P.rain + lane.l * nij : nullptr;
     MicProf<T, V> f;
-    f.so = *reinterpret_cast<const Vec *>(P.sed_out + l * P.pitch_prof + k);
-    f.si = *reinterpret_cast<const Vec *>(P.sed_in + l * P.pitch_prof + k);
+    f.so = *reinterpret_cast<const Vec *>(lane.row(P.sed_out, P.pitch_prof));
+    f.si = *reinterpret_cast<const Vec *>(lane.row(P.sed_in, P.pitch_prof));
     f.lc = f.so;
-    if (P.thl) f.lc = *reinterpret_cast<const Vec *>(P.lcpex + l * P.pitch_prof + k);
-    f.w0 = rain ? P.w[l * P.pitch_prof] : (T)0;
+    if (P.thl) f.lc = *reinterpret_cast<const Vec *>(lane.row(P.lcpex, P.pitch_prof));
+    f.w0 = rain ? P.w[lane.l * P.pitch_prof] : (T)0;
     Vec aqt, athl, aqr, aqi;
 #pragma unroll
     for (int v = 0; v < V; ++v) aqt.v[v] = athl.v[v] = aqr.v[v] = aqi.v[v] = (T)0;      // numpy starts a sum from add's identity, +0.0
@@ -163,27 +160,11 @@ template <typename T, int V, int U> __global__ __launch_bounds__(MIC_THREADS) vo
         if (rain) ++rain;
     }
     const T cnt = (T)nij;
-    const int64_t m = l * P.pitch_mean + k;
-    if (P.qt_mean) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) aqt.v[v] = aqt.v[v] / cnt;    // IEEE division (the build has no fast-math)
-        *reinterpret_cast<Vec *>(P.qt_mean + m) = aqt;
-    }
-    if (P.thl_mean) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) athl.v[v] = athl.v[v] / cnt;
-        *reinterpret_cast<Vec *>(P.thl_mean + m) = athl;
-    }
-    if (P.qr_mean) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) aqr.v[v] = aqr.v[v] / cnt;
-        *reinterpret_cast<Vec *>(P.qr_mean + m) = aqr;
-    }
-    if (P.qi_mean) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) aqi.v[v] = aqi.v[v] / cnt;
-        *reinterpret_cast<Vec *>(P.qi_mean + m) = aqi;
-    }
+    const int64_t m = lane.row(P.pitch_mean);
+    if (P.qt_mean) *reinterpret_cast<Vec *>(P.qt_mean + m) = chain_mean<T, V>(aqt, cnt);
+    if (P.thl_mean) *reinterpret_cast<Vec *>(P.thl_mean + m) = chain_mean<T, V>(athl, cnt);
+    if (P.qr_mean) *reinterpret_cast<Vec *>(P.qr_mean + m) = chain_mean<T, V>(aqr, cnt);
+    if (P.qi_mean) *reinterpret_cast<Vec *>(P.qi_mean + m) = chain_mean<T, V>(aqi, cnt);
 }
 
 #else  // SPC_MICRO_HOST -----------------------------------------------------------------------------------------------------
@@ -193,9 +174,7 @@ template <typename T> static int les_micro_impl(const spc_les_micro_args *a, voi
     if (!a) return fail(SPC_ERR_INVALID_ARGUMENT, "%sargs is NULL");
     int rc = slab_check_extents("les_microphysics", a->n_les, a->itot, a->jtot, a->ktot);
     if (rc) return rc;
-    if (a->pitch_prof < a->ktot || a->pitch_mean < a->ktot)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_microphysics: pitch_prof %lld or pitch_mean %lld smaller than ktot", "",
-                    (long long)a->pitch_prof, (long long)a->pitch_mean);
+    if ((rc = chain_pitch(a->ktot, a->pitch_prof, a->pitch_mean, "%sles_microphysics: pitch_prof %lld or pitch_mean %lld smaller than ktot"))) return rc;
     if (a->n_les == 0) return SPC_OK;
     REQUIRE(a->qt, "qt"); REQUIRE(a->ql, "ql"); REQUIRE(a->qr, "qr"); REQUIRE(a->qr_new, "qr_new");
     REQUIRE(a->sed_out, "sed_out"); REQUIRE(a->sed_in, "sed_in");
@@ -206,23 +185,18 @@ template <typename T> static int les_micro_impl(const spc_les_micro_args *a, voi
     // (equal base pointers are what is detected, as in K11: partially overlapping views are the caller's to avoid)
     const void *in[7] = {a->ql, a->qr, a->temp, a->sed_out, a->sed_in, a->thl ? a->lcpex : nullptr, a->rain ? a->w : nullptr};
     const void *out[8] = {a->qr_new, a->qt, a->thl, a->rain, a->qt_mean, a->thl_mean, a->qr_mean, a->qi_mean};
-    for (int o = 0; o < 8; ++o) {
-        if (!out[o]) continue;
-        for (int i = 0; i < 7; ++i)
-            if (out[o] == in[i])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_microphysics: a written array is also an input (qr_new must not be qr: the level below reads the old qr)");
-        for (int q = 0; q < o; ++q)
-            if (out[o] == out[q]) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_microphysics: two written arrays are the same array");
-    }
+    if ((rc = chain_alias(in, 7, out, 8, "les_microphysics: a written array is also an input (qr_new must not be qr: the level below reads the old qr)",
+                          "les_microphysics: two written arrays are the same array")))
+        return rc;
     uintptr_t bits = (uintptr_t)(a->ktot * sizeof(T)) | (uintptr_t)(a->pitch_prof * sizeof(T)) | (uintptr_t)(a->pitch_mean * sizeof(T));
     for (int i = 0; i < 6; ++i) bits |= (uintptr_t)in[i];                  // (w and rain are read and written one element at a time)
     for (int o = 0; o < 8; ++o)
         if (o != 3) bits |= (uintptr_t)out[o];
-    if (bits % sizeof(T) || (uintptr_t)a->w % sizeof(T) || (uintptr_t)a->rain % sizeof(T))
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_microphysics: a pointer is not aligned to its element type");
-    if (a->ktot == 1)
-        return fail(SPC_ERR_UNSUPPORTED, "%sles_microphysics: ktot == 1 (numpy reduces a one-level plane pairwise; as in les_advance)");
     LesMicroP<T> p = {};
+    bool wide; int64_t grid;
+    if ((rc = chain_geometry<T>("les_microphysics", bits, (uintptr_t)a->w | (uintptr_t)a->rain, a->n_les, a->ktot, MIC_THREADS,
+                                "les_microphysics: ktot == 1 (numpy reduces a one-level plane pairwise; as in les_advance)", wide, p.chains, grid)))
+        return rc;
     p.qt = (T *)a->qt; p.thl = (T *)a->thl; p.qr_new = (T *)a->qr_new; p.rain = (T *)a->rain;
     p.ql = (const T *)a->ql; p.qr = (const T *)a->qr; p.temp = (const T *)a->temp;
     p.sed_out = (const T *)a->sed_out; p.sed_in = (const T *)a->sed_in; p.lcpex = (const T *)a->lcpex; p.w = (const T *)a->w;
@@ -234,14 +208,9 @@ template <typename T> static int les_micro_impl(const spc_les_micro_args *a, voi
     p.tu = (T)a->t_up; p.td = (T)a->t_dn;
     p.den = p.tu - p.td;
     p.nij = a->itot * a->jtot; p.ktot = a->ktot;
-    constexpr int VMAX = 16 / (int)sizeof(T);
-    const bool wide = bits % 16 == 0;                 // every row of every field, profile and mean starts on a 16-byte boundary
-    p.chains = a->n_les * (int64_t)(wide ? a->ktot / VMAX : a->ktot);
-    const int64_t grid = (p.chains + MIC_THREADS - 1) / MIC_THREADS;
-    if (grid > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_microphysics: too many workgroups");
     const bool few = grid <= (int64_t)device_cus() * 4;   // a workgroup is one wave: at most one wave per SIMD
-    void (*const kern)(const LesMicroP<T>) = few ? (wide ? k_les_microphysics<T, VMAX, MIC_U_FEW> : k_les_microphysics<T, 1, MIC_U_FEW>)
-                                                 : (wide ? k_les_microphysics<T, VMAX, MIC_U_MANY> : k_les_microphysics<T, 1, MIC_U_MANY>);
+    void (*const kern)(const LesMicroP<T>) = few ? (wide ? k_les_microphysics<T, CHAIN_V<T>, MIC_U_FEW> : k_les_microphysics<T, 1, MIC_U_FEW>)
+                                                 : (wide ? k_les_microphysics<T, CHAIN_V<T>, MIC_U_MANY> : k_les_microphysics<T, 1, MIC_U_MANY>);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(MIC_THREADS), 0, (hipStream_t)stream, p);
     return launch_status("k_les_microphysics");
 }

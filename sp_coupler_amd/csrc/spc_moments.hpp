@@ -1,6 +1,6 @@
 // spc_moments.hpp -- K20: the second moments of the LES 3-D fields per (LES, level): means, variances, standard deviations of a
 // set of fields and the covariances of pairs of them, in ONE launch, kernel and host side.  spc_hip.hip includes it twice, like
-// spc_qtlocal.hpp: with the kernel among the device headers (after spc_slab.hpp: SlabVec), and -- SPC_MOMENTS_HOST defined --
+// spc_qtlocal.hpp: with the kernel among the device headers (after spc_chain.hpp: SlabVec), and -- SPC_MOMENTS_HOST defined --
 // after spc_launch.hpp and the host side of spc_slab.hpp (slab_check_extents).
 //
 // Fields are [n_les][itot][jtot][ktot], C order, ktot contiguous, 64-bit element offsets (spc_slab.hpp).  The rule (include/spc.h)
@@ -122,7 +122,7 @@ __device__ __forceinline__ void mom_walk(const T *const (&first)[NS], const bool
 }
 
 template <typename T, int V, int U, int NS>
-__device__ __forceinline__ void mom_job(const LesMomentsP<T> &p, const MomJob<T> &j, const int64_t l, const int k)
+__device__ __forceinline__ void mom_job(const LesMomentsP<T> &p, const MomJob<T> &j, const ChainLane<V> &lane)
 {
     using Vec = SlabVec<T, V>;
     const int64_t ktot = p.ktot;
@@ -130,15 +130,13 @@ __device__ __forceinline__ void mom_job(const LesMomentsP<T> &p, const MomJob<T>
     bool face[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        first[s] = j.x[s] + l * p.nij * ktot + k;
+        first[s] = lane.cell(j.x[s], p.nij, ktot);
         face[s] = j.face[s] != 0;
     }
-    const bool low = k > 0;
-    Vec sum[NS];                                                   // numpy starts from add's identity: a plane of -0.0 sums to +0.0
+    const bool low = lane.k > 0;
+    Vec sum[NS];
 #pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < V; ++v) sum[s].v[v] = (T)0;
+    for (int s = 0; s < NS; ++s) chain_zero(sum[s]);
     mom_walk<T, V, U, NS>(first, face, low, p.nij, ktot, [&](const Vec (&c)[NS]) {
 #pragma unroll
         for (int s = 0; s < NS; ++s)
@@ -147,15 +145,12 @@ __device__ __forceinline__ void mom_job(const LesMomentsP<T> &p, const MomJob<T>
     });
     const T cnt = (T)p.nij;
 #pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < V; ++v) sum[s].v[v] = sum[s].v[v] / cnt;   // the means; IEEE division (the build has no fast-math)
-    const int64_t o = l * p.pitch_out + k;
+    for (int s = 0; s < NS; ++s) chain_mean<T, V>(sum[s], cnt);
+    const int64_t o = lane.row(p.pitch_out);
     if (j.mean) *reinterpret_cast<Vec *>(j.mean + o) = sum[0];
     if (!j.var && !j.std) return;
     Vec acc;
-#pragma unroll
-    for (int v = 0; v < V; ++v) acc.v[v] = (T)0;
+    chain_zero(acc);
     mom_walk<T, V, U, NS>(first, face, low, p.nij, ktot, [&](const Vec (&c)[NS]) {
 #pragma unroll
         for (int v = 0; v < V; ++v) {
@@ -165,8 +160,7 @@ __device__ __forceinline__ void mom_job(const LesMomentsP<T> &p, const MomJob<T>
             acc.v[v] += q;
         }
     });
-#pragma unroll
-    for (int v = 0; v < V; ++v) acc.v[v] = acc.v[v] / cnt;
+    chain_mean<T, V>(acc, cnt);
     if (j.var) *reinterpret_cast<Vec *>(j.var + o) = acc;
     if (j.std) {
 #pragma unroll
@@ -181,14 +175,12 @@ template <typename T, int V> __global__ __launch_bounds__(MOM_THREADS) void k_le
     constexpr int U = V == 1 ? MOM_U_NARROW : MOM_U_WIDE;
     const int64_t g = (int64_t)blockIdx.x * MOM_THREADS + threadIdx.x;
     if (g >= p.chains) return;
-    const int kv = p.ktot / V;
-    const int64_t l = g / kv;
-    const int k = (int)(g - l * kv) * V;
+    const ChainLane<V> lane(g, p.ktot);
     const MomJob<T> &j = p.job[blockIdx.y];
     if (j.x[1])
-        mom_job<T, V, U / 2, 2>(p, j, l, k);                 // a pair: the same bytes in flight, over two fields
+        mom_job<T, V, U / 2, 2>(p, j, lane);                 // a pair: the same bytes in flight, over two fields
     else
-        mom_job<T, V, U, 1>(p, j, l, k);
+        mom_job<T, V, U, 1>(p, j, lane);
 }
 
 #else  // SPC_MOMENTS_HOST ---------------------------------------------------------------------------------------------------
@@ -209,32 +201,26 @@ template <typename T> static int les_moments_impl(const spc_les_moments_args *a,
         return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_moments: pair count %lld outside 0 ... %lld", "", (long long)a->n_pairs, (long long)MOM_MAXP);
     if (a->face_field < -1 || a->face_field >= a->n_fields)
         return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_moments: face_field %lld is neither -1 nor a field index", "", (long long)a->face_field);
-    if (a->pitch_out < a->ktot)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_moments: pitch_out %lld smaller than ktot", "", (long long)a->pitch_out);
+    if ((rc = chain_pitch(a->ktot, a->pitch_out, a->pitch_out, "%sles_moments: pitch_out %lld smaller than ktot"))) return rc;
     for (int q = 0; q < a->n_pairs; ++q)
         if (a->pair_a[q] < 0 || a->pair_a[q] >= a->n_fields || a->pair_b[q] < 0 || a->pair_b[q] >= a->n_fields || a->pair_a[q] == a->pair_b[q])
             return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_moments: pair %lld is not two different field indices", "", (long long)q);
-    // every output asked for, with the fields in front: no two of them may START at the same address
-    const void *seen[MOM_MAXF * 4 + MOM_MAXP];
-    int n_seen = 0, n_out = 0;
+    // every output asked for: none may START at the same address as a field or as another of them
+    const void *out[MOM_MAXF * 3 + MOM_MAXP];
+    int n_out = 0;
     uintptr_t bits = (uintptr_t)((size_t)a->ktot * sizeof(T)) | (uintptr_t)((size_t)a->pitch_out * sizeof(T));
-    for (int f = 0; f < a->n_fields; ++f) seen[n_seen++] = a->fields[f];
     for (int f = 0; f < a->n_fields; ++f)
         for (void *const o : {a->mean[f], a->var[f], a->std[f]})
-            if (o) seen[n_seen++] = o, ++n_out;
+            if (o) out[n_out++] = o;
     for (int q = 0; q < a->n_pairs; ++q)
-        if (a->cov[q]) seen[n_seen++] = a->cov[q], ++n_out;
+        if (a->cov[q]) out[n_out++] = a->cov[q];
     if (a->n_les == 0) return SPC_OK;
     if (!n_out) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_moments: no output asked for");
     for (int f = 0; f < a->n_fields; ++f) REQUIRE(a->fields[f], "fields[f]");
-    for (int i = a->n_fields; i < n_seen; ++i)
-        for (int h = 0; h < i; ++h)
-            if (seen[i] == seen[h])
-                return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_moments: an output is the same array as a field or as another output");
-    for (int i = 0; i < n_seen; ++i) {
-        if ((uintptr_t)seen[i] % sizeof(T)) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_moments: a pointer is not aligned to its element type");
-        bits |= (uintptr_t)seen[i];
-    }
+    const char *const same = "les_moments: an output is the same array as a field or as another output";
+    if ((rc = chain_alias(a->fields, a->n_fields, out, n_out, same, same))) return rc;
+    for (int f = 0; f < a->n_fields; ++f) bits |= (uintptr_t)a->fields[f];
+    for (int o = 0; o < n_out; ++o) bits |= (uintptr_t)out[o];
     LesMomentsP<T> p = {};
     int jobs = 0;
     for (int f = 0; f < a->n_fields; ++f)
@@ -253,16 +239,14 @@ template <typename T> static int les_moments_impl(const spc_les_moments_args *a,
             j.face[1] = a->pair_b[q] == a->face_field;
             j.var = (T *)a->cov[q];
         }
-    constexpr int VMAX = 16 / (int)sizeof(T);
     p.nij = a->itot * a->jtot;
     p.ktot = a->ktot;
     p.pitch_out = a->pitch_out;
-    bool wide = bits % 16 == 0;       // every row of every field and of every output starts on a 16-byte boundary
-    if (wide && p.nij >= MOM_LONG_PLANE && a->n_les * (int64_t)(a->ktot / VMAX) * jobs < MOM_FEW_LANES) wide = false;
-    p.chains = a->n_les * (int64_t)(wide ? a->ktot / VMAX : a->ktot);
-    const int64_t grid = (p.chains + MOM_THREADS - 1) / MOM_THREADS;
-    if (grid > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_moments: too many workgroups");
-    void (*const kern)(const LesMomentsP<T>) = wide ? k_les_moments<T, VMAX> : k_les_moments<T, 1>;
+    // a long plane in a launch of few waves goes narrow (above); (ktot == 1 was refused before the fields were looked at)
+    const bool narrow = p.nij >= MOM_LONG_PLANE && a->n_les * (int64_t)(a->ktot / CHAIN_V<T>) * jobs < MOM_FEW_LANES;
+    bool wide; int64_t grid;
+    if ((rc = chain_geometry<T>("les_moments", bits, 0, a->n_les, a->ktot, MOM_THREADS, nullptr, wide, p.chains, grid, narrow))) return rc;
+    void (*const kern)(const LesMomentsP<T>) = wide ? k_les_moments<T, CHAIN_V<T>> : k_les_moments<T, 1>;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)jobs), dim3(MOM_THREADS), 0, (hipStream_t)stream, p);
     return launch_status("k_les_moments");
 }

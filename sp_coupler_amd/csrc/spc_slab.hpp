@@ -32,24 +32,17 @@ template <typename T> struct SlabMeansP {
     int32_t nij, ktot;
 };
 
-template <typename T, int V> struct alignas(sizeof(T) * V) SlabVec {
-    T v[V];
-};
-
 template <typename T, int V> __global__ __launch_bounds__(SLAB_THREADS) void k_slab_means(const SlabMeansP<T> p)
 {
     const int64_t g = (int64_t)blockIdx.x * SLAB_THREADS + threadIdx.x;
     if (g >= p.chains) return;
     using Vec = SlabVec<T, V>;
-    const int kv = p.ktot / V;
-    const int64_t l = g / kv;
-    const int k = (int)(g - l * kv) * V;
+    const ChainLane<V> lane(g, p.ktot);
     const int f = blockIdx.y;
     const int64_t ktot = p.ktot;
-    const T *src = p.field[f] + l * p.nij * ktot + k;
-    Vec acc;                                                     // numpy starts from add's identity: a plane of -0.0 sums to +0.0
-#pragma unroll
-    for (int v = 0; v < V; ++v) acc.v[v] = (T)0;
+    const T *src = lane.cell(p.field[f], p.nij, ktot);
+    Vec acc;
+    chain_zero(acc);
     int r = 0;
     for (; r + SLAB_U <= p.nij; r += SLAB_U) {
         Vec x[SLAB_U];
@@ -67,10 +60,7 @@ template <typename T, int V> __global__ __launch_bounds__(SLAB_THREADS) void k_s
 #pragma unroll
         for (int v = 0; v < V; ++v) acc.v[v] += x.v[v];
     }
-    const T cnt = (T)p.nij;
-#pragma unroll
-    for (int v = 0; v < V; ++v) acc.v[v] = acc.v[v] / cnt;      // IEEE division (the build has no fast-math)
-    *reinterpret_cast<Vec *>(p.out[f] + l * p.pitch_out + k) = acc;
+    *reinterpret_cast<Vec *>(lane.row(p.out[f], p.pitch_out)) = chain_mean<T, V>(acc, (T)p.nij);
 }
 
 // ktot == 1: the field of one LES is ONE contiguous run and numpy reduces it as ndarray.sum() does (pairwise blocks, vn_npsum of
@@ -218,8 +208,7 @@ template <typename T> static int slab_means_impl(const spc_slab_means_args *a, v
     static_assert(SPC_SLAB_MAX_FIELDS == SLAB_MAXF, "include/spc.h and spc_slab.hpp disagree on the fields per launch");
     if (a->n_fields < 1 || a->n_fields > SPC_SLAB_MAX_FIELDS)
         return fail(SPC_ERR_INVALID_ARGUMENT, "%sslab_means: field count %lld outside 1 ... %lld", "", (long long)a->n_fields, SPC_SLAB_MAX_FIELDS);
-    if (a->pitch_out < a->ktot)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sslab_means: pitch_out %lld smaller than ktot %lld", "", (long long)a->pitch_out, a->ktot);
+    if ((rc = chain_pitch(a->ktot, a->pitch_out, a->ktot, "%sslab_means: pitch_out %lld smaller than ktot %lld"))) return rc;
     if (a->n_les == 0) return SPC_OK;
     SlabMeansP<T> p = {};
     uintptr_t bits = (uintptr_t)(a->ktot * sizeof(T)) | (uintptr_t)(a->pitch_out * sizeof(T));
@@ -232,15 +221,12 @@ template <typename T> static int slab_means_impl(const spc_slab_means_args *a, v
         p.out[f] = (T *)a->out[f];
         bits |= (uintptr_t)a->fields[f] | (uintptr_t)a->out[f];
     }
-    constexpr int VMAX = 16 / (int)sizeof(T);
-    const bool wide = bits % 16 == 0;                 // every row of every field and of out starts on a 16-byte boundary
+    bool wide; int64_t grid;                          // (ktot == 1 is this kernel's own: k_slab_means_k1)
+    if ((rc = chain_geometry<T>("slab_means", bits, 0, a->n_les, a->ktot, SLAB_THREADS, nullptr, wide, p.chains, grid))) return rc;
     p.nij = a->itot * a->jtot;
     p.ktot = a->ktot;
     p.pitch_out = a->pitch_out;
-    p.chains = a->n_les * (int64_t)(wide ? a->ktot / VMAX : a->ktot);
-    const int64_t grid = (p.chains + SLAB_THREADS - 1) / SLAB_THREADS;
-    if (grid > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sslab_means: too many workgroups");
-    void (*const kern)(const SlabMeansP<T>) = a->ktot == 1 ? k_slab_means_k1<T> : (wide ? k_slab_means<T, VMAX> : k_slab_means<T, 1>);
+    void (*const kern)(const SlabMeansP<T>) = a->ktot == 1 ? k_slab_means_k1<T> : (wide ? k_slab_means<T, CHAIN_V<T>> : k_slab_means<T, 1>);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)a->n_fields), dim3(SLAB_THREADS), 0, (hipStream_t)stream, p);
     return launch_status("k_slab_means");
 }

@@ -10,9 +10,8 @@
 //   qs = th_sat(Tk);   dq = qt - qs;   q = dq > 0 ? dq : (dq != dq ? dq : +0.0);   t = Tl + (rlv * q) / cp
 // th_sat is a linear interpolation in a saturation-pressure table the caller hands in: no transcendental function is called,
 // so every output has one right answer in T.  3 n_iter + 2 IEEE divisions per cell.
-// The means follow K11's scheme (k_slab_means' rule): a lane owns V adjacent k of one LES (V = 16 B / sizeof(T) where ktot, the
-// pitches and every pointer allow 16-byte accesses, else 1), walks the (i, j) rows in row-major order and carries the two
-// sums; their bits do not depend on the grid.  The loads do not depend on the arithmetic: the loads of TH_U rows are issued
+// The means follow K11's scheme (k_slab_means' rule): a lane owns V adjacent k of one LES (spc_chain.hpp), walks the (i, j) rows
+// in row-major order and carries the two sums; their bits do not depend on the grid.  The loads do not depend on the arithmetic: the loads of TH_U rows are issued
 // before the arithmetic of the TH_U rows before them.  ex, p and eps * p are per (l, k): formed once per lane (eps * p is an
 // operand of the rule as it stands, so hoisting it keeps the operation order).
 // The table (n_tab entries, 16 KB of doubles at the 2 000 of thermo.py) is read by every lane at data-dependent indices:
@@ -100,21 +99,18 @@ template <typename T, int V, bool LDS_TAB> __global__ __launch_bounds__(TH_THREA
     const int64_t g = (int64_t)blockIdx.x * TH_THREADS + threadIdx.x;
     if (g >= P.chains) return;
     constexpr int U = TH_U;
-    const int kv = P.ktot / V;
-    const int64_t l = g / kv;
-    const int k = (int)(g - l * kv) * V;
+    const ChainLane<V> lane(g, P.ktot);
     const int64_t ktot = P.ktot;
     const int nij = P.nij;
-    int64_t off = l * nij * ktot + k;
+    int64_t off = lane.cell(nij, ktot);
     const T *thl = P.thl + off, *qt = P.qt + off;
-    const Vec ex = *reinterpret_cast<const Vec *>(P.ex + l * P.pitch_prof + k);
-    const Vec pr = *reinterpret_cast<const Vec *>(P.presf + l * P.pitch_prof + k);
+    const Vec ex = *reinterpret_cast<const Vec *>(lane.row(P.ex, P.pitch_prof));
+    const Vec pr = *reinterpret_cast<const Vec *>(lane.row(P.presf, P.pitch_prof));
     Vec epsp, accq, acct;
 #pragma unroll
-    for (int v = 0; v < V; ++v) {
-        epsp.v[v] = ThermoK<T>::eps * pr.v[v];
-        accq.v[v] = acct.v[v] = (T)0;                            // numpy starts a sum from add's identity, +0.0
-    }
+    for (int v = 0; v < V; ++v) accq.v[v] = acct.v[v] = (T)0;      // numpy starts a sum from add's identity, +0.0
+#pragma unroll
+    for (int v = 0; v < V; ++v) epsp.v[v] = ThermoK<T>::eps * pr.v[v];
     Vec a[U], b[U];
     int r = 0;
     if (U <= nij) {
@@ -154,16 +150,8 @@ template <typename T, int V, bool LDS_TAB> __global__ __launch_bounds__(TH_THREA
         off += ktot;
     }
     const T cnt = (T)nij;
-    if (P.ql_mean) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) accq.v[v] = accq.v[v] / cnt;  // IEEE division (the build has no fast-math)
-        *reinterpret_cast<Vec *>(P.ql_mean + l * P.pitch_mean + k) = accq;
-    }
-    if (P.t_mean) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) acct.v[v] = acct.v[v] / cnt;
-        *reinterpret_cast<Vec *>(P.t_mean + l * P.pitch_mean + k) = acct;
-    }
+    if (P.ql_mean) *reinterpret_cast<Vec *>(lane.row(P.ql_mean, P.pitch_mean)) = chain_mean<T, V>(accq, cnt);
+    if (P.t_mean) *reinterpret_cast<Vec *>(lane.row(P.t_mean, P.pitch_mean)) = chain_mean<T, V>(acct, cnt);
 }
 
 #else  // SPC_THERMO_HOST ----------------------------------------------------------------------------------------------------
@@ -175,9 +163,7 @@ template <typename T> static int les_thermo_impl(const spc_les_thermo_args *a, v
     if (!a) return fail(SPC_ERR_INVALID_ARGUMENT, "%sargs is NULL");
     int rc = slab_check_extents("les_thermo", a->n_les, a->itot, a->jtot, a->ktot);
     if (rc) return rc;
-    if (a->pitch_prof < a->ktot || a->pitch_mean < a->ktot)
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_thermo: pitch_prof %lld or pitch_mean %lld smaller than ktot", "",
-                    (long long)a->pitch_prof, (long long)a->pitch_mean);
+    if ((rc = chain_pitch(a->ktot, a->pitch_prof, a->pitch_mean, "%sles_thermo: pitch_prof %lld or pitch_mean %lld smaller than ktot"))) return rc;
     if (a->n_tab < 2) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_thermo: n_tab = %lld < 2", "", (long long)a->n_tab);
     if (a->n_iter < 0) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_thermo: n_iter = %lld < 0", "", (long long)a->n_iter);
     if (a->table_mode < TH_TAB_LIBRARY || a->table_mode > TH_TAB_GLOBAL)
@@ -188,37 +174,28 @@ template <typename T> static int les_thermo_impl(const spc_les_thermo_args *a, v
     REQUIRE(a->qsat, "qsat"); REQUIRE(a->ql, "ql");
     const void *in[5] = {a->thl, a->qt, a->presf, a->ex, a->es_tab};
     const void *out[5] = {a->qsat, a->ql, a->temp, a->ql_mean, a->t_mean};
-    for (int o = 0; o < 5; ++o) {
-        if (!out[o]) continue;
-        for (int i = 0; i < 5; ++i)
-            if (out[o] == in[i]) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_thermo: an output is also an input (thl, qt, presf, ex and es_tab are read while it is written)");
-        for (int q = 0; q < o; ++q)
-            if (out[o] == out[q]) return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_thermo: two outputs are the same array");
-    }
+    if ((rc = chain_alias(in, 5, out, 5, "les_thermo: an output is also an input (thl, qt, presf, ex and es_tab are read while it is written)",
+                          "les_thermo: two outputs are the same array")))
+        return rc;
     uintptr_t bits = (uintptr_t)(a->ktot * sizeof(T)) | (uintptr_t)(a->pitch_prof * sizeof(T)) | (uintptr_t)(a->pitch_mean * sizeof(T));
     for (int i = 0; i < 4; ++i) bits |= (uintptr_t)in[i];                  // (the table is read one element at a time)
     for (int o = 0; o < 5; ++o) bits |= (uintptr_t)out[o];
-    if (bits % sizeof(T) || (uintptr_t)a->es_tab % sizeof(T))
-        return fail(SPC_ERR_INVALID_ARGUMENT, "%sles_thermo: a pointer is not aligned to its element type");
-    if (a->ktot == 1)
-        return fail(SPC_ERR_UNSUPPORTED, "%sles_thermo: ktot == 1 (numpy reduces a one-level plane pairwise; as in les_advance)");
     LesThermoP<T> p = {};
+    bool wide; int64_t grid;
+    if ((rc = chain_geometry<T>("les_thermo", bits, (uintptr_t)a->es_tab, a->n_les, a->ktot, TH_THREADS,
+                                "les_thermo: ktot == 1 (numpy reduces a one-level plane pairwise; as in les_advance)", wide, p.chains, grid)))
+        return rc;
     p.thl = (const T *)a->thl; p.qt = (const T *)a->qt; p.presf = (const T *)a->presf; p.ex = (const T *)a->ex; p.es = (const T *)a->es_tab;
     p.qsat = (T *)a->qsat; p.ql = (T *)a->ql; p.temp = (T *)a->temp; p.ql_mean = (T *)a->ql_mean; p.t_mean = (T *)a->t_mean;
     p.pitch_prof = a->pitch_prof; p.pitch_mean = a->pitch_mean;
     p.t_lo = (T)a->t_lo; p.inv_step = (T)a->inv_step;
     p.t_hi = (T)(a->t_lo + (double)(a->n_tab - 1) / a->inv_step);
     p.nij = a->itot * a->jtot; p.ktot = a->ktot; p.n_tab = a->n_tab; p.n_iter = a->n_iter;
-    constexpr int VMAX = 16 / (int)sizeof(T);
-    const bool wide = bits % 16 == 0;                 // every row of every field, profile and mean starts on a 16-byte boundary
-    p.chains = a->n_les * (int64_t)(wide ? a->ktot / VMAX : a->ktot);
-    const int64_t grid = (p.chains + TH_THREADS - 1) / TH_THREADS;
-    if (grid > INT32_MAX) return fail(SPC_ERR_UNSUPPORTED, "%sles_thermo: too many workgroups");
     const size_t tab_bytes = (size_t)a->n_tab * sizeof(T);
     // the library's choice: LDS where the table fits the default limit (measured: DESIGN.md 7.3)
     const bool lds = a->table_mode == TH_TAB_LDS || (a->table_mode == TH_TAB_LIBRARY && tab_bytes <= (size_t)MAX_LDS_BYTES);
-    void (*const kern)(const LesThermoP<T>) = lds ? (wide ? k_les_thermo<T, VMAX, true> : k_les_thermo<T, 1, true>)
-                                                  : (wide ? k_les_thermo<T, VMAX, false> : k_les_thermo<T, 1, false>);
+    void (*const kern)(const LesThermoP<T>) = lds ? (wide ? k_les_thermo<T, CHAIN_V<T>, true> : k_les_thermo<T, 1, true>)
+                                                  : (wide ? k_les_thermo<T, CHAIN_V<T>, false> : k_les_thermo<T, 1, false>);
     if (lds && (rc = ensure_lds(kern, tab_bytes, "les_thermo"))) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(TH_THREADS), lds ? tab_bytes : 0, (hipStream_t)stream, p);
     return launch_status("k_les_thermo");

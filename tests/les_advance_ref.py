@@ -10,7 +10,7 @@ import torch
 from tests import slab_ref
 from tests.fake_engine import OracleEngine, _t
 from tests.gpu_util import assert_bits
-from tests.les_harness import DTYPES, NP, Poisoned, blocks_of, np_of, on_both, run_bodies  # noqa: F401  (DTYPES, NP: for the tests)
+from tests.les_harness import DTYPES, NP, Poisoned, blocks_of, chain_cases, np_of, on_both, run_bodies  # noqa: F401  (DTYPES, NP: for the tests)
 
 SHAPES = [(1, 1, 1, 2), (3, 3, 3, 5), (2, 5, 7, 64), (2, 4, 4, 66), (1, 9, 1, 130), (2, 8, 8, 160)]
 #: itot * jtot = 1 ... 17: every remainder of the row look-ahead (batches of 8 rows, of 4 for the lanes of QT), one, two and
@@ -245,7 +245,20 @@ def check_multi(one, multi, n, min_rows_expected=None):
     return blocks
 
 
-BODIES = ("parity", "planes", "alignment", "optional", "special")
+def check_chain(eng):
+    """the cases of the lane's walk (les_harness.chain_cases) for batches of 8 rows, which hold those of the 4 rows of the lanes
+    of QT: a field with one input stream and QT with its two, every array in poison"""
+    dtype = np_of(eng)
+    for shape, lead in chain_cases(8, dtype):
+        fields, tend, _ = case(shape, dtype, n_fields=2, seed=9)
+        fields = {"THL": fields["U"], "QT": numpy.abs(fields["V"])}
+        tend = {"THL": tend["U"], "QT": tend["V"]}
+        qsat = (fields["QT"] * dtype(1.01)).astype(dtype)
+        qsat[..., ::2] = fields["QT"][..., ::2] * dtype(0.75)
+        Run(eng, fields, tend, 60.0, qsat, "QT", lead=lead, lead_rows=lead).check("chain %s lead %d" % (shape, lead))
+
+
+BODIES = ("parity", "planes", "alignment", "optional", "special", "chain")
 
 
 def jobs(eng):
@@ -253,7 +266,8 @@ def jobs(eng):
             ("planes", lambda: [check_planes(eng, k) for k in (160, 33)]),
             ("alignment", lambda: [check_alignment(eng, *a) for a in ((1, 0, 0), (0, 1, 0), (0, 0, 4), (0, 0, 3))]),
             ("optional", lambda: check_optional(eng)),
-            ("special", lambda: check_special(eng))]
+            ("special", lambda: check_special(eng)),
+            ("chain", lambda: check_chain(eng))]
 
 
 def check_everything(eng):

@@ -128,6 +128,21 @@ def run_bodies(bodies, jobs):
     return failed
 
 
+def chain_cases(U, dtype, nijs=None):
+    """(shape, lead) of the cases that hold the walk of a slab-chain lane (spc_chain.hpp; K10, K11, K12, K14, K20) in batches of
+    U rows together: n_les = 2, planes 1 x nij for every nij = 1 ... 2 U + 1 (``nijs``: others) -- the tail alone, one whole
+    batch with no successor, a batch that has a successor and one that has none, a batch with a tail behind it --, each at ktot 8
+    (16-byte accesses in both dtypes: four and two lanes per LES), at ktot 7 (one element per lane) and at ktot 8 with every array
+    ``lead`` = 1 element off the 16-byte grid (one element per lane at an even ktot); then n_les = 5, ktot = 7 V with a batch and a
+    tail, on and off the grid: 35 and 35 V lanes, so a wave holds lanes of several LES and lanes past the last chain"""
+    V = 16 // numpy.dtype(dtype).itemsize
+    for nij in (range(1, 2 * U + 2) if nijs is None else nijs):
+        for ktot, lead in ((8, 0), (7, 0), (8, 1)):
+            yield (2, 1, nij, ktot), lead
+    for lead in (0, 1):
+        yield (5, 1, U + 1, 7 * V), lead
+
+
 def cols_table(cols_of, top=3000):
     """(dict C -> the smallest ktot with that many columns per workgroup, the ktot at which the count changes, the first
     unsupported ktot) of ``cols_of(ktot)``"""

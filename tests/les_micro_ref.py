@@ -17,7 +17,7 @@ from tests import les_water_paths_ref as wpr
 from tests import slab_ref
 from tests.gpu_util import assert_bits
 from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
-    DTYPES, NP, Poisoned, abi_call, blocks_of, counted_cus, host_of, np_of, on_both, run_bodies)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, chain_cases, counted_cus, host_of, np_of, on_both, run_bodies)
 from tests.test_vnudge import make_les_fields
 
 PLANES = [(1, 1), (3, 5), (8, 8)]
@@ -376,7 +376,20 @@ def check_many_waves(eng):
         check_special(eng)
 
 
-BODIES = ("parity", "neighbour", "rows", "alignment", "optional", "special", "cap", "refusals", "many_waves")
+def check_chain(eng):
+    """the cases of the lane's walk (les_harness.chain_cases) for the batches of 4 rows of a launch of few waves; then, with one
+    compute unit counted as in many_waves, nij = 1 ... 5 for the batches of 2 rows at five LES of 256 and 255 levels (5 to 20
+    waves: above one wave per SIMD), on and off the 16-byte grid"""
+    dtype = np_of(eng)
+    for shape, lead in chain_cases(4, dtype):
+        Run(eng, case(shape, dtype, seed=9, neighbour=True), lead=lead, lead_rows=lead).check("chain %s lead %d" % (shape, lead))
+    with counted_cus(1):
+        for nij in range(1, 6):
+            for ktot, lead in ((256, 0), (255, 0), (256, 1)):
+                Run(eng, case((5, 1, nij, ktot), dtype, seed=10, neighbour=True), lead=lead, lead_rows=lead).check("chain, many waves: nij %d ktot %d lead %d" % (nij, ktot, lead))
+
+
+BODIES = ("parity", "neighbour", "rows", "alignment", "optional", "special", "cap", "refusals", "many_waves", "chain")
 
 
 def jobs(eng):
@@ -388,7 +401,8 @@ def jobs(eng):
             ("special", lambda: check_special(eng)),
             ("cap", lambda: check_cap(eng)),
             ("refusals", lambda: check_refusals(eng)),
-            ("many_waves", lambda: check_many_waves(eng))]
+            ("many_waves", lambda: check_many_waves(eng)),
+            ("chain", lambda: check_chain(eng))]
 
 
 def check_everything(eng):

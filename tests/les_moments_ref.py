@@ -17,7 +17,7 @@ from tests import les_qt_local_ref as qlr
 from tests import slab_edges
 from tests.gpu_util import assert_bits
 from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
-    DTYPES, NP, Poisoned, abi_call, blocks_of, host_of, np_of, on_both, run_bodies)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, chain_cases, host_of, np_of, on_both, run_bodies)
 
 #: one row (every deviation is zero), fewer rows than the loads in flight (2 x 3), whole rounds of loads (8 x 8: 64 rows) and a
 #: ragged last round (17 x 5: 85 rows)
@@ -459,7 +459,18 @@ def check_large_plane(eng):
         Run(eng, fields, (("B", "A"),), "A").check("large plane %s" % (shape,))
 
 
-BODIES = ("parity", "counts", "rows", "face", "special", "alignment", "refusals", "same_as_k10_k6", "large_plane")
+def check_chain(eng):
+    """the cases of the lane's walk (les_harness.chain_cases) for the 8 rows in flight of the 16-byte form and, at ktot 7 and with
+    every field off the 16-byte grid, for the 32 of the other (nij = 1 ... 17 and 31 ... 33, 63 ... 65); a pair walks with half
+    of either, the face field is in the pair and a field job of its own"""
+    dtype = np_of(eng)
+    long = (31, 32, 33, 63, 64, 65)
+    for shape, lead in list(chain_cases(8, dtype)) + [c for c in chain_cases(32, dtype, long) if c[0][-1] == 7 or c[1]]:
+        fields = case(shape, dtype, seed=9, n_fields=3)
+        Run(eng, fields, (("A", "C"),), "C", leads={k: lead for k in fields}).check("chain %s lead %d" % (shape, lead))
+
+
+BODIES = ("parity", "counts", "rows", "face", "special", "alignment", "refusals", "same_as_k10_k6", "large_plane", "chain")
 
 
 def jobs(eng):
@@ -471,7 +482,8 @@ def jobs(eng):
             ("alignment", lambda: [check_alignment(eng, *a) for a in ((65, 0), (64, 0), (160, 1))]),
             ("refusals", lambda: check_refusals(eng)),
             ("same_as_k10_k6", lambda: check_same_as_k10_k6(eng)),
-            ("large_plane", lambda: check_large_plane(eng))]
+            ("large_plane", lambda: check_large_plane(eng)),
+            ("chain", lambda: check_chain(eng))]
 
 
 def check_everything(eng):

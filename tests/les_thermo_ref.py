@@ -15,7 +15,7 @@ from tests import les_advance_ref as lar
 from tests import slab_ref
 from tests.gpu_util import assert_bits
 from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
-    DTYPES, NP, Poisoned, abi_call, blocks_of, fill_args, np_of, on_both, run_bodies)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, chain_cases, fill_args, np_of, on_both, run_bodies)
 
 #: n = 3; planes 1 x 1, 3 x 5 (15 rows: three batches of 4 and single rows behind them) and 8 x 8; ktot 2 and 7 (one element per
 #: lane), 64 and 160 (16-byte accesses), 65 (odd again, beyond one wave)
@@ -314,7 +314,15 @@ def check_multi(one, multi, n):
     return blocks
 
 
-BODIES = ("parity", "special", "alignment", "options", "table")
+def check_chain(eng):
+    """the cases of the lane's walk (les_harness.chain_cases) for batches of 4 rows, which PLANES does not hold: the tail alone,
+    one whole batch with no successor, a batch with a successor and then one without, a batch with a tail behind it"""
+    for shape, lead in chain_cases(4, np_of(eng)):
+        thl, qt, presf, ex = case(shape, np_of(eng), seed=9)
+        Run(eng, thl, qt, presf, ex, lead=lead, lead_rows=lead).check("chain %s lead %d" % (shape, lead))
+
+
+BODIES = ("parity", "special", "alignment", "options", "table", "chain")
 
 
 def jobs(eng):
@@ -322,7 +330,8 @@ def jobs(eng):
             ("special", lambda: [check_special(eng, k, n) for k in (7, 64) for n in (0, 1, None)]),
             ("alignment", lambda: [check_alignment(eng, *a) for a in ((1, 0, 0), (0, 1, 0), (0, 0, 4), (0, 0, 3))]),
             ("options", lambda: check_options(eng)),
-            ("table", lambda: check_table(eng))]
+            ("table", lambda: check_table(eng)),
+            ("chain", lambda: check_chain(eng))]
 
 
 def check_everything(eng):

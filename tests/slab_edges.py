@@ -11,7 +11,7 @@ import torch
 from tests import slab_ref
 from tests.gpu_util import assert_bits
 from tests.les_harness import (  # noqa: F401  (NP, DTYPES, TAIL_ROWS, with_tail: K10's own tests)
-    DTYPES, NP, TAIL_ROWS, np_of as _np, run_bodies, with_tail)
+    DTYPES, NP, TAIL_ROWS, chain_cases, np_of as _np, run_bodies, with_tail)
 
 
 #: itot x jtot: every residue of nij mod 4 (SLAB_CF_RB rows per wave) and mod 8 (SLAB_U rows of loads in flight), below and
@@ -218,10 +218,20 @@ def check_means_k1(eng, size):
     assert numpy.array_equal(run_means(eng, {"f": f2})["f"], want)
 
 
+def check_chain(eng):
+    """the cases of the lane's walk (les_harness.chain_cases) for the 8 rows a lane has in flight, the fields and the means in
+    poison (run_means)"""
+    for shape, lead in chain_cases(8, _np(eng)):
+        fields = means_fields(shape[1:], shape[0], 2, _np(eng), seed=900 + shape[2] + shape[3] + lead)
+        got = run_means(eng, fields, lead=lead, lead_out=lead)
+        for k, v in fields.items():
+            assert_bits("chain %s lead %d %s" % (shape, lead, k), got[k], slab_ref.slab_means(v))
+
+
 MEANS_KTOTS = (160, 33, 2, 4, 8)
 
 
-BODIES = ("cloud_plane", "cloud_layers", "cloud_opt_in_lds", "means_plane", "means_k1")
+BODIES = ("cloud_plane", "cloud_layers", "cloud_opt_in_lds", "means_plane", "means_k1", "chain")
 
 
 def jobs(eng):
@@ -229,7 +239,8 @@ def jobs(eng):
             ("cloud_layers", lambda: [check_cloud_layers(eng, g, k) for g in NGS for k in KTOTS]),
             ("cloud_opt_in_lds", lambda: check_cloud_opt_in_lds(eng)),
             ("means_plane", lambda: [check_means_plane(eng, p, k) for p in PLANES for k in MEANS_KTOTS]),
-            ("means_k1", lambda: [check_means_k1(eng, s) for s in K1_SIZES])]
+            ("means_k1", lambda: [check_means_k1(eng, s) for s in K1_SIZES]),
+            ("chain", lambda: check_chain(eng))]
 
 
 def check_everything(eng):

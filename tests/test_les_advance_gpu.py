@@ -173,3 +173,9 @@ def test_closed_loop_fused_in_row_blocks_equals_the_host_twin(monkeypatch):
     multi = MultiDeviceEngine([Engine("cuda:0", stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
     dfm.check_closed_loop(Engine("cuda:0"), multi, 2, 5)
     assert len(calls) >= 6 and not any(calls)
+
+
+@pytest.mark.parametrize("dtype", lar.DTYPES)
+def test_the_chain_cases(dtype):
+    """the cases of the lane's walk that spc_chain.hpp's kernels share, held together (les_advance_ref.check_chain)"""
+    lar.check_chain(Engine("cuda:0", dtype=dtype))

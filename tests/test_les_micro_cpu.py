@@ -295,3 +295,9 @@ def test_enable_microphysics_creates_what_it_needs_and_refuses_what_it_cannot_ta
     old.set_fields_batched("QT", numpy.zeros((2, 2, 2, 6)))
     with pytest.raises(ValueError, match="les_microphysics"):
         old.enable_microphysics()
+
+
+def test_the_chain_cases_on_the_oracle_backed_engine():
+    """the oracle alone handles every case of the chain body, none skipped; its plumbing runs without a GPU"""
+    lmr.check_chain(lmr.MicroOracleEngine())
+    assert "chain" in lmr.BODIES

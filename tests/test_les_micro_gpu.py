@@ -104,3 +104,9 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, thermo):
     lmr.check_ensemble(Engine("cuda:0"), [one, multi], n, thermo)
     assert launches == [(n, thermo)] * 3 + [(n // 2, thermo)] * 6
     assert steps == [None if thermo else "QT"] * 9
+
+
+@pytest.mark.parametrize("dtype", lmr.DTYPES)
+def test_the_chain_cases(dtype):
+    """the cases of the lane's walk that spc_chain.hpp's kernels share, held together, for both batch sizes (les_micro_ref.check_chain)"""
+    lmr.check_chain(Engine("cuda:0", dtype=dtype))

@@ -307,3 +307,9 @@ def test_names_without_a_field_and_engines_without_the_kernel():
     for k in ("U", "V", "THL", "QT", "QL"):
         assert_bits(k, models.DeviceLESEnsemble._host(new.get_fields_batched(k)), models.DeviceLESEnsemble._host(old.get_fields_batched(k)))
         assert_bits("p " + k, new.p[k], old.p[k])
+
+
+def test_the_chain_cases_on_the_oracle_backed_engine():
+    """the oracle alone handles every case of the chain body, none skipped; its plumbing runs without a GPU"""
+    mr.check_chain(mr.MomentsOracleEngine())
+    assert "chain" in mr.BODIES

@@ -106,3 +106,9 @@ def test_ensemble_statistics_equal_the_twin(monkeypatch, n, variant):
     mlog = mr.ensemble_run(multi, n, calls, **mr.VARIANTS[variant])[1]
     assert len(calls) == 10 and {i for i, _ in calls} == {id(e) for e in multi.engines}
     mr.qlr.lmr.same_logs(log, mlog)
+
+
+@pytest.mark.parametrize("dtype", mr.DTYPES)
+def test_the_chain_cases(dtype):
+    """the cases of the lane's walk that spc_chain.hpp's kernels share, held together, for both forms (les_moments_ref.check_chain)"""
+    mr.check_chain(Engine("cuda:0", dtype=dtype))

@@ -352,3 +352,9 @@ def test_thermo_mutants_apply_to_the_tree_and_name_their_guards():
         for name, text in files.items():
             with open(os.path.join(mc.CSRC, name)) as f:
                 assert text != f.read(), (n, name)
+
+
+def test_the_chain_cases_on_the_oracle_backed_engine():
+    """the oracle alone handles every case of the chain body, none skipped; its plumbing runs without a GPU"""
+    ltr.check_chain(ltr.ThermoOracleEngine())
+    assert "chain" in ltr.BODIES

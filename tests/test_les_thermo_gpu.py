@@ -107,3 +107,9 @@ def test_closed_loop_of_the_thermo_ensemble_equals_the_host_twin(monkeypatch, n)
     assert launches.count(n) >= 5 and launches.count(n // 2) >= 10
     assert models.DeviceLESEnsemble.FUSED_MIN_LES == 128
     assert steps == ([] if n < 128 else [(n, None)] * len(steps)) and (n < 128 or len(steps) >= 3)
+
+
+@pytest.mark.parametrize("dtype", ltr.DTYPES)
+def test_the_chain_cases(dtype):
+    """the cases of the lane's walk that spc_chain.hpp's kernels share, held together (les_thermo_ref.check_chain)"""
+    ltr.check_chain(Engine("cuda:0", dtype=dtype))

@@ -225,3 +225,10 @@ def test_edge_means_notice_a_dropped_row(dtype):
             short = numpy.stack([slab_ref.sequential_mean(r[:-1, None, :]) * dtype(rows.shape[1] - 1) / dtype(rows.shape[1]) for r in rows])
             assert (short != slab_ref.slab_means(f)).all(), plane
 
+
+
+def test_the_chain_cases_on_the_oracle_backed_engine():
+    """the oracle alone handles every case of the chain body, none skipped; its plumbing runs without a GPU"""
+    from tests.fake_engine import OracleEngine
+    slab_edges.check_chain(OracleEngine())
+    assert "chain" in slab_edges.BODIES and len(list(slab_edges.chain_cases(8, numpy.float64))) == 17 * 3 + 2

@@ -226,3 +226,9 @@ def test_slab_means_of_sixteen_fields_and_not_seventeen(dtype):
 @pytest.mark.parametrize("size", slab_edges.K1_SIZES)
 def test_slab_means_of_one_level_at_the_pairwise_block_sizes(size, dtype):
     slab_edges.check_means_k1(Engine("cuda:0", dtype=dtype), size)
+
+
+@pytest.mark.parametrize("dtype", slab_edges.DTYPES)
+def test_the_chain_cases(dtype):
+    """the cases of the lane's walk that spc_chain.hpp's kernels share, held together (slab_edges.check_chain)"""
+    slab_edges.check_chain(Engine("cuda:0", dtype=dtype))

@@ -13,7 +13,8 @@ module under tests/ whose bodies guard the table, and the GPU test that runs tho
 such a table ends with the edits of its *_EQUIVALENT table where it has one (edits proved to change no output: expected to
 fail NO body) and with the guards that existed before its module on the mutants the new bodies were written for (K8: the
 earlier bodies of tests/geo_edges.py; K9: OLD_BODIES of tests/les_state_ref.py; K6: the shape matrix of tests/test_vnudge.py
-on every mutant).
+on every mutant).  CHAIN_MUTANTS (--chain) holds slips of what K10, K11, K12, K14 and K20 share (spc_chain.hpp and their walks); its guards
+are the ``chain`` bodies of all five modules.
 usage: python tools/mutation_control.py --build [n ...] [-j N]
        python tools/mutation_control.py > profiles/mutation_control.log
        python tools/mutation_control.py --only 28 29 30 31 32 33 34 35 > profiles/mutation_control_slab.log
@@ -38,6 +39,7 @@ K1, K3, K5, K4, VN2, SU = "spc_k1.hpp", "spc_k3.hpp", "spc_k5.hpp", "spc_k4.hpp"
 VN, VN_HOST = "spc_vnudge.hpp", "spc_vnudge_host.hpp"
 SU_HOST = "spc_sputils_host.hpp"
 SLAB = "spc_slab.hpp"
+CHAIN = "spc_chain.hpp"
 ADVANCE = "spc_advance.hpp"
 THERMO = "spc_thermo.hpp"
 WATERPATH = "spc_waterpath.hpp"
@@ -648,7 +650,7 @@ MOMENTS_MUTANTS = {
     1: ("K20 second walk: the product contracted into the sum by an fma", moments_body("special"),
         [(MOMENTS, "acc.v[v] += q;", "acc.v[v] = fma(da, db, acc.v[v]);")]),
     2: ("K20 second moments: division by N - 1 (the sample variance)", moments_body("parity"),
-        [(MOMENTS, "acc.v[v] = acc.v[v] / cnt;", "acc.v[v] = acc.v[v] / (cnt - (T)1);")]),
+        [(MOMENTS, "    chain_mean<T, V>(acc, cnt);\n", "    chain_mean<T, V>(acc, cnt - (T)1);\n")]),
     3: ("K20 cov: d_a * x_b for d_a * d_b (equal in exact arithmetic, not in bits)", moments_body("parity"),
         [(MOMENTS, "c[NS - 1].v[v] - sum[NS - 1].v[v] : da;", "c[NS - 1].v[v] : da;")]),
     4: ("K20 cov: the mean of field a taken from field b's cells", moments_body("parity"),
@@ -658,7 +660,7 @@ MOMENTS_MUTANTS = {
     6: ("K20 face average: x[-1] is x[0], not +0.0", moments_body("face"),
         [(MOMENTS, "r.below = below ? src[-1] : (T)0;", "r.below = below ? src[-1] : src[0];")]),
     7: ("K20 l: the cells of LES 0 for every LES", moments_body("rows"),
-        [(MOMENTS, "first[s] = j.x[s] + l * p.nij * ktot + k;", "first[s] = j.x[s] + k;")]),
+        [(MOMENTS, "first[s] = lane.cell(j.x[s], p.nij, ktot);", "first[s] = j.x[s] + lane.k;")]),
     8: ("K20 walks: the last row behind the load-ahead loop is left out", moments_body("large_plane"),
         [(MOMENTS, "for (; r < nij; ++r) {", "for (; r < nij - 1; ++r) {")]),
 }
@@ -852,6 +854,41 @@ SPUTILS_MUTANTS = {
          [(SU, "stg<WT>(su_at(ob, su_mul(r, po) + i), res);", "stg<WT>(su_at(ob, su_mul(r, n_x) + i), res);")]),
     14: ("K7 k_interp_c: the slab's results stored as if out were contiguous", sputils_body("last_slab"),
          [(SU, "const bool flat = p.pitch_out == nG;", "const bool flat = true;")]),
+}
+
+
+# What the slab-chain kernels share (spc_chain.hpp; K10, K11, K12, K14, K20), numbered on its own: slips of the header, and the same
+# slip made in every kernel's own walk.  Every mutant only computes wrong numbers: none reads or writes outside what the shipped
+# kernels touch (mutant 1 sends the lanes of an LES to its first ktot / V levels; mutants 3 and 4 visit fewer rows or the same rows
+# of a batch again).  The guard of each is the body ``chain`` of EVERY kernel it changes, on both engines.
+def chain_guard(*modules):
+    """the body ``chain`` of each of tests/``modules``.py: (every one of them failed, everything that failed anywhere)"""
+    def guard(engine_of):
+        caught, failed = True, []
+        for module in modules:
+            ok, names = body_guard(module, "chain")(engine_of)
+            caught, failed = caught and ok, failed + ["%s.%s" % (module, n) for n in names]
+        return caught, failed
+    guard.__name__ = "chain of " + ", ".join(modules)
+    return guard
+
+
+_CHAIN_ALL = ("slab_edges", "les_advance_ref", "les_thermo_ref", "les_micro_ref", "les_moments_ref")
+_CHAIN_WALK2 = ("les_advance_ref", "les_thermo_ref", "les_micro_ref")
+_MORE = ("const bool more = r + 2 * U <= nij;", "const bool more = r + 3 * U <= nij;")
+CHAIN_MUTANTS = {
+    1: ("chain lane: k without * V (the lanes of an LES crowd into its first ktot / V levels)", chain_guard(*_CHAIN_ALL),
+        [(CHAIN, "k = (int)(g - l * kv) * V;", "k = (int)(g - l * kv);")]),
+    2: ("chain mean: the sums divided by itot * jtot - 1", chain_guard(*_CHAIN_ALL),
+        [(CHAIN, "acc.v[v] = acc.v[v] / cnt;", "acc.v[v] = acc.v[v] / (cnt - (T)1);")]),
+    3: ("double-buffered walks: `more` off by one batch (the last batch that has a successor works on the rows before it again)",
+        chain_guard(*_CHAIN_WALK2), [(ADVANCE,) + _MORE, (THERMO,) + _MORE, (MICRO,) + _MORE]),
+    4: ("every walk: the single rows behind the last whole batch dropped", chain_guard(*_CHAIN_ALL),
+        [(SLAB, "    for (; r < p.nij; ++r) {", "    for (; r < p.nij && false; ++r) {"),
+         (ADVANCE, "    for (; r < nij; ++r) {", "    for (; r < nij && false; ++r) {"),
+         (THERMO, "    for (; r < nij; ++r) {", "    for (; r < nij && false; ++r) {"),
+         (MICRO, "    for (; r < nij; ++r) {", "    for (; r < nij && false; ++r) {"),
+         (MOMENTS, "    for (; r < nij; ++r) {", "    for (; r < nij && false; ++r) {")]),
 }
 
 
@@ -1081,7 +1118,11 @@ LATER_TABLES = (
 SPUTILS_TABLES = (
     Table("sputils", SPUTILS_MUTANTS, "K7", "sputils_", "sputils", "sputils_slabs", "test_sputils_slabs_gpu"),
 )
-ALL_TABLES = TABLES + LATER_TABLES + SPUTILS_TABLES
+#: what spc_chain.hpp's kernels share: the guards are the ``chain`` bodies of five modules, tests/les_harness.py holds their cases
+CHAIN_TABLES = (
+    Table("chain", CHAIN_MUTANTS, "K10/K11/K12/K14/K20", "chain_", "chain", "les_harness", "test_*_gpu.py::test_the_chain_cases"),
+)
+ALL_TABLES = TABLES + LATER_TABLES + SPUTILS_TABLES + CHAIN_TABLES
 
 
 if __name__ == "__main__":
