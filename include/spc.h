@@ -43,6 +43,9 @@
  *   spc_les_vmix_*       <- the implicit vertical mixing of that ensemble by each column's own eddy viscosity (nothing of it is
  *                           in the reference): the Thomas elimination per column in the kernel, K15's surface fluxes and a
  *                           neutral bulk drag on the lowest wind level, in two launches (kernel family K25)
+ *   spc_les_hmix_*       <- the implicit horizontal mixing of that ensemble by each line's own eddy viscosity (nothing of it is
+ *                           in the reference), without K24's cap: a cyclic tridiagonal elimination per periodic grid line in
+ *                           the kernel, along i and then along j, in place, in two launches (kernel family K26)
  *   spc_exner_* / spc_interp_* / spc_searchsorted_* / spc_interp_c_* / spc_rms_*
  *                        <- the helpers of splib/sputils.py on their own (exner, iexner :28-34; interp :82-86;
  *                           searchsorted :88-91; integral, interp_c, interp_rho :94-197; rms :23-24), batched over rows
@@ -1141,6 +1144,74 @@ int spc_les_vmix_f64(const spc_les_vmix_args *args, void *stream);
 int spc_les_vmix_f32(const spc_les_vmix_args *args, void *stream);
 /* columns per workgroup of k_les_vmix for ktot levels of elem_size (4 or 8) bytes: 64, 32 or 16; 0: unsupported */
 int spc_les_vmix_cols_per_block(int ktot, int elem_size);
+
+/* ---- implicit horizontal mixing of the device-resident LES fields by each line's own eddy viscosity (kernel family K26) ------- */
+/* One backward-Euler step of d(x)/dt = d/dx (K dx/dx) + d/dy (K dx/dy), K at a face the mean of K24's km of its two cells, IN
+ * PLACE and without K24's stability cap: first every line along i, then every line along j, which reads what the first sweep
+ * wrote (Lie splitting; each sweep is one backward-Euler step, unconditionally stable).  A line is periodic, so its system is a
+ * cyclic tridiagonal one: the last cell is condensed out and the others are eliminated with two right-hand sides.  The matrix
+ * differs from line to line, so the elimination runs in the kernel.  The rule is this library's definition.
+ * General conventions:
+ *   - Fields and km are [n_les][itot][jtot][ktot], k contiguous, with 64-bit offsets as in K10.  The element type T is f64 or f32.
+ *   - Every operation is rounded once in T.  Nothing contracts to an fma.
+ *   - There is ONE correctly rounded IEEE division per cell of a line and per sweep, plus ONE per line for the closing unknown.
+ *     There is no transcendental function.
+ *   - So every output is asked for bit for bit in both types, whatever the launch shape.
+ * Per-LES values (formed in float64 by sp_coupler_amd/horizontal_mixing.py and rounded to T once):
+ *   - ax[f], ay[f] [n_les]: K24's, 0.5 dt / dx^2 and 0.5 dt / dy^2 for a wind, the same divided by the Prandtl number for a
+ *     scalar; one pointer per field, fields may share a pointer.
+ *   - kh2 [n_les]: twice the largest face viscosity allowed: a sanity bound that keeps the matrix finite, no stability cap.
+ * For one line of length n (itot in the first sweep, jtot in the second) with the cells x[0 .. n-1], the line's km[0 .. n-1],
+ * a = ax[f][l] (ay[f][l] in the second sweep), ip = (i + 1) mod n and im = (i - 1) mod n:
+ *   n == 1:  the line keeps every bit (nothing is loaded or stored)
+ *   t[i]  = km[i] + km[ip]                                face between i and ip
+ *   s[i]  = t[i] > 0 ? t[i] : +0                          a NaN or a negative sum decouples the face
+ *   s[i]  = s[i] < kh2[l] ? s[i] : kh2[l]
+ *   w[i]  = a * s[i];   up[i] = w[i];   lo[i] = w[im]
+ *   b[i]  = (1 + lo[i]) + up[i]
+ *   m = n - 1 unknowns 0 .. n-2 are condensed on x[n-1]:
+ *   c[i]  = (i == 0 ? lo[0] : +0) + (i == n-2 ? up[n-2] : +0)            (n == 2: c[0] = lo[0] + up[0])
+ *   p     = 1 / b[0];                     q[0] = up[0] * p;   y[0] = x[0] * p;   z[0] = c[0] * p
+ *   p     = 1 / (b[i] - lo[i] * q[i-1]);  q[i] = up[i] * p
+ *   y[i]  = (x[i] + lo[i] * y[i-1]) * p;  z[i] = (c[i] + lo[i] * z[i-1]) * p             i = 1 .. n-2
+ *   y[i]  = y[i] + q[i] * y[i+1];         z[i] = z[i] + q[i] * z[i+1]                    i = n-3 .. 0
+ *   num   = (x[n-1] + up[n-1] * y[0]) + lo[n-1] * y[n-2]
+ *   den   = (b[n-1] - up[n-1] * z[0]) - lo[n-1] * z[n-2]
+ *   x'[n-1] = num / den;                  x'[i] = y[i] + z[i] * x'[n-1]                  i = 0 .. n-2
+ * x' replaces x IN PLACE.  axes: bit 0 runs the sweep along i, bit 1 the sweep along j; 3 runs both, i first.
+ * Consequences:
+ *   - w is the same number for both cells of a face: the matrix is symmetric with unit column sums, so the sum of a line is
+ *     conserved to rounding, and after both sweeps the plane sum of every field.
+ *   - The matrix is an M-matrix: lo, up, q and z are never negative, 0 <= z <= 1, every pivot and den are at least about 1, so
+ *     every division is safe.
+ *   - A mixed line stays within its minimum and maximum up to the rounding of the solve (tests/test_les_hmix_cpu.py derives
+ *     the slack).  A constant finite line stays constant to rounding; it does not keep its bits.
+ *   - With km = 0 a finite line keeps every value; the sign of a zero is not kept (a -0.0 whose neighbours in the walk are not
+ *     all -0.0 comes out +0.0).
+ *   - A NaN in a field stays in its line in the first sweep and spreads only along the j lines of those cells in the second.
+ *     A NaN or negative km touches nothing but its two faces (per direction).
+ *   - These are SPC_ERR_INVALID_ARGUMENT: n_fields outside 1 ... SPC_HMIX_MAX_FIELDS; axes outside 1 ... 3; a NULL km, kh2, or
+ *     a NULL fields[f], ax[f], ay[f] of f < n_fields; two EQUAL fields pointers; a field equal to km, kh2 or a coefficient; a
+ *     misaligned pointer.  SPC_ERR_UNSUPPORTED: a swept extent above the largest supported line (641 cells of 8 bytes, 1 281
+ *     of 4); too many workgroups.  Both sweeps are checked before the first is launched.
+ *   - Arrays that overlap only in part are not detected and must not be passed.  n_les == 0 is a no-op after the scalar checks.
+ * One lane owns one line; a workgroup takes spc_les_hmix_lines_per_block(n, sizeof(T)) lines, whose q and z (2 (n - 1)
+ * elements per line) live in LDS while y lives in the field itself.  Nothing is allocated inside the library.             */
+#define SPC_HMIX_MAX_FIELDS 6
+typedef struct spc_les_hmix_args {
+    int64_t n_les;                      /* 0 is allowed: no-op                                               */
+    int32_t itot, jtot, ktot, n_fields; /* n_fields 1 ... SPC_HMIX_MAX_FIELDS                                */
+    int32_t axes, reserved;             /* axes: bit 0 the sweep along i, bit 1 along j; 1 ... 3             */
+    void *fields[SPC_HMIX_MAX_FIELDS];       /* device [n_les][itot][jtot][ktot], updated in place           */
+    const void *ax[SPC_HMIX_MAX_FIELDS];     /* device [n_les] per field                                     */
+    const void *ay[SPC_HMIX_MAX_FIELDS];     /* device [n_les] per field                                     */
+    const void *km;                     /* device [n_les][itot][jtot][ktot], read only                       */
+    const void *kh2;                    /* device [n_les]                                                    */
+} spc_les_hmix_args;
+int spc_les_hmix_f64(const spc_les_hmix_args *args, void *stream);
+int spc_les_hmix_f32(const spc_les_hmix_args *args, void *stream);
+/* lines per workgroup of k_les_hline for lines of n cells of elem_size (4 or 8) bytes: 256 ... 16; 0: unsupported */
+int spc_les_hmix_lines_per_block(int n, int elem_size);
 
 /* ---- misc ----------------------------------------------------------------------------------- */
 int spc_abi_version(void);          /* == SPC_ABI_VERSION                                          */

@@ -219,6 +219,16 @@ class LesVmixArgs(ctypes.Structure):
                 + _ptrs("km", "kb", "kv2", "s0", "u", "v", "speed") + [("pitch_prof", c_int64)])
 
 
+SPC_HMIX_MAX_FIELDS = 6
+
+
+class LesHmixArgs(ctypes.Structure):
+    _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("n_fields", c_int32),
+                 ("axes", c_int32), ("reserved", c_int32),
+                 ("fields", c_void_p * SPC_HMIX_MAX_FIELDS), ("ax", c_void_p * SPC_HMIX_MAX_FIELDS), ("ay", c_void_p * SPC_HMIX_MAX_FIELDS)]
+                + _ptrs("km", "kh2"))
+
+
 class LesQtLocalArgs(ctypes.Structure):
     _fields_ = ([("n_les", c_int64), ("itot", c_int32), ("jtot", c_int32), ("ktot", c_int32), ("split", c_int32)]
                 + _ptrs("qt", "ql", "a", "qtm") + [("pitch_prof", c_int64), ("count", c_void_p), ("pitch_count", c_int64)])
@@ -316,6 +326,9 @@ PROTOTYPES = {
     "spc_les_vmix_f64": (ctypes.c_int, [ctypes.POINTER(LesVmixArgs), c_void_p]),
     "spc_les_vmix_f32": (ctypes.c_int, [ctypes.POINTER(LesVmixArgs), c_void_p]),
     "spc_les_vmix_cols_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "spc_les_hmix_f64": (ctypes.c_int, [ctypes.POINTER(LesHmixArgs), c_void_p]),
+    "spc_les_hmix_f32": (ctypes.c_int, [ctypes.POINTER(LesHmixArgs), c_void_p]),
+    "spc_les_hmix_lines_per_block": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "spc_abi_version": (ctypes.c_int, []),
     "spc_last_error": (ctypes.c_char_p, []),
     "spc_device_count": (ctypes.c_int, []),

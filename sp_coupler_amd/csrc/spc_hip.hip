@@ -57,6 +57,9 @@
 //   K25 k_les_speed, k_les_vmix  one backward-Euler step of the vertical mixing by each column's own eddy viscosity: the Thomas
 //                  elimination in the kernel (one division per level), K15's tile, surface fluxes and a neutral bulk drag on the
 //                  lowest wind level from a plane of wind speeds: spc_vmix.hpp, kernels and host side
+//   K26 k_les_hline  one backward-Euler step of the horizontal mixing by each line's own eddy viscosity, in place and without
+//                  K24's cap: one lane eliminates one periodic grid line (a cyclic tridiagonal system, one division per cell),
+//                  first every line along i, then every line along j: spc_hmix.hpp, kernel and host side
 // Shared device code (constants, pow, searches, numpy.interp, parameter blocks): spc_device.hpp; the LDS column tile of the
 // kernels with a serial chain along k (K15, K17, K18, K21, K22, K23, K25: its geometry, the run of a workgroup, the split of a
 // run into 16-byte vectors, the plain mover, their host checks and launches): spc_coltile.hpp; the slab chain of the kernels
@@ -127,6 +130,7 @@ namespace {
 #include "spc_buoyancy.hpp"
 #include "spc_mix.hpp"
 #include "spc_vmix.hpp"
+#include "spc_hmix.hpp"
 #include "spc_k5.hpp"
 
 #include "spc_launch.hpp"
@@ -188,6 +192,9 @@ namespace {
 #define SPC_VMIX_HOST
 #include "spc_vmix.hpp"
 #undef SPC_VMIX_HOST
+#define SPC_HMIX_HOST
+#include "spc_hmix.hpp"
+#undef SPC_HMIX_HOST
 
 }  // namespace
 
@@ -304,6 +311,9 @@ int spc_les_mix_f32(const spc_les_mix_args *a, void *s) { return les_mix_impl<fl
 int spc_les_vmix_f64(const spc_les_vmix_args *a, void *s) { return les_vmix_impl<double>(a, s); }
 int spc_les_vmix_f32(const spc_les_vmix_args *a, void *s) { return les_vmix_impl<float>(a, s); }
 int spc_les_vmix_cols_per_block(int ktot, int elem_size) { return col_cols(ktot, elem_size, 2, 0); }
+int spc_les_hmix_f64(const spc_les_hmix_args *a, void *s) { return les_hmix_impl<double>(a, s); }
+int spc_les_hmix_f32(const spc_les_hmix_args *a, void *s) { return les_hmix_impl<float>(a, s); }
+int spc_les_hmix_lines_per_block(int n, int elem_size) { return hline_lines(n, elem_size); }
 
 int spc_les_moments_f64(const spc_les_moments_args *a, void *s) { return les_moments_impl<double>(a, s); }
 int spc_les_moments_f32(const spc_les_moments_args *a, void *s) { return les_moments_impl<float>(a, s); }

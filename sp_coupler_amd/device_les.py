@@ -9,6 +9,7 @@ from . import advection as adv
 from . import buoyancy as buo
 from . import diffusion as df
 from . import microphysics as mp
+from . import horizontal_mixing as hmx
 from . import mixing as mix
 from . import vertical_mixing as vmix
 from . import radiation as rad
@@ -138,7 +139,9 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     the twin of that mode.
     After ``enable_mixing()`` every step mixes U, V, THL, QT and QR along i and j by the Smagorinsky-Lilly eddy viscosity of the
     flow (K24, ``Engine.les_mix``), after the advection and before K15, whose diffusivity it can supply (``vertical=True``);
-    ``get_eddy_viscosity_batched()`` returns the viscosity; tests/les_mix_ref.py holds the twin of that mode.
+    ``get_eddy_viscosity_batched()`` returns the viscosity; tests/les_mix_ref.py holds the twin of that mode.  With
+    ``implicit=True`` the mixing is one backward-Euler step per grid line by the uncapped viscosity, in place (K26,
+    ``Engine.les_hmix``); tests/les_hmix_ref.py holds the twin of that mode.
     After ``enable_vertical_mixing()`` (behind ``enable_mixing()``) every step mixes U, V, THL, QT and QR along k by each
     column's own uncapped eddy viscosity, with the surface fluxes into THL and QT and a neutral bulk drag on U and V (K25,
     ``Engine.les_vmix``), where K15 stands; ``get_vertical_viscosity_batched()`` returns that viscosity; tests/les_vmix_ref.py
@@ -655,8 +658,11 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     _mix_km = None                                     # the eddy viscosity of the last step, device
     _mix_spare = None                                  # name -> the buffer K24 writes next (it reads the field)
     _mix_kd = None                                     # vertical=True: host [n x nL], K15's face diffusivity of this step
+    _hmix_huge = None                                  # implicit=True: device [n], the type's largest finite value, the cap of K24's probe
+    _hmix_kh2 = None                                   # implicit=True: ((kh_cap,) of the upload, device kh2)
 
-    def enable_mixing(self, cs=None, prandtl=None, cap=None, theta_ref=None, stability=True, dx=None, dy=None, vertical=False):
+    def enable_mixing(self, cs=None, prandtl=None, cap=None, theta_ref=None, stability=True, dx=None, dy=None, vertical=False,
+                      implicit=False, kh_cap=None):
         """from now on every ``evolve_model_batched`` runs ONE ``Engine.les_mix`` per device (K24, DESIGN.md 7.3: two launches)
         after K16 / K17 / K22 / K23 and before K15: the Smagorinsky-Lilly eddy viscosity km of the winds U and V and, with
         ``stability=True``, of theta = THL (the moist correction of the stability is left out), capped at
@@ -670,8 +676,13 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         step and ``mixing_capped`` whether it lies above the smallest cap (no substeps: where the cap binds, the mixing is
         weaker than the closure asks for).  ``vertical=True`` (after ``enable_diffusion()``; ValueError otherwise) makes K15's
         face diffusivity of the step k_bg + 0.5 (m[k-1] + m[k]) with m the slab mean of km (one K10 launch more), in place of
-        the profile of ``diffusion.diffusivity``.  Needs U and V fields.  Without this call every path, launch and bit of the
-        ensemble is unchanged."""
+        the profile of ``diffusion.diffusivity``.  ``implicit=True`` mixes by the closure's OWN viscosity instead (K26,
+        ``Engine.les_hmix``; ValueError where the engine has none): ``les_mix`` runs without fields under a cap that never binds
+        (the type's largest finite value), so km is uncapped and ``mixing_capped`` False, and ONE ``les_hmix`` per device takes
+        one backward-Euler step of every periodic line along i and then along j IN PLACE (no scratch buffers are swapped), the
+        face viscosity bounded by ``kh_cap`` (default ``horizontal_mixing.KH_CAP``: a sanity bound, no stability cap; uploaded
+        again where it changed); ``cap`` is then not used.  Needs U and V fields.  Without this call, and with
+        ``implicit=False``, every path, launch and bit of the ensemble is unchanged."""
         if "U" not in self.fields3d or "V" not in self.fields3d:
             raise ValueError("the mixing (K24) needs the fields U and V (set_fields_batched)")
         if not self._has("les_mix"):
@@ -680,21 +691,26 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             raise ValueError("the mixing (K24) with vertical=True and the vertical mixing (K25) exclude each other: a step has one vertical diffusion")
         if vertical and not self.diffusion:
             raise ValueError("the mixing (K24) with vertical=True hands its viscosity to K15: it needs enable_diffusion()")
+        if implicit and not self._has("les_hmix"):
+            raise ValueError("the engine has no les_hmix (K26)")
         if dx is None:
             dx = self.dx if self.advection else adv.DX
         if dy is None:
             dy = self.dy if self.advection else adv.DY
         par = {"cs": mix.CS if cs is None else float(cs), "prandtl": mix.PRANDTL if prandtl is None else float(prandtl),
                "cap": mix.CAP if cap is None else float(cap), "theta_ref": mix.THETA_REF if theta_ref is None else float(theta_ref),
-               "stability": bool(stability), "vertical": bool(vertical),
+               "stability": bool(stability), "vertical": bool(vertical), "implicit": bool(implicit),
+               "kh_cap": hmx.KH_CAP if kh_cap is None else float(kh_cap),
                "dx": numpy.array(dx, dtype=numpy.float64) if numpy.ndim(dx) else float(dx),
                "dy": numpy.array(dy, dtype=numpy.float64) if numpy.ndim(dy) else float(dy)}
         _, _, wind, scalar = mix.coefficients(1.0, par["dx"], par["dy"], par["prandtl"], n=self.n)       # (ValueError for what is not positive, or not [n])
         mix.cap(wind, scalar, par["cap"])
+        hmx.bound(self.n, par["kh_cap"])
         mix.profiles(self.zf_cache, self.zh_cache, par["dx"], par["dy"], par["cs"], par["prandtl"], par["theta_ref"], n=self.n)
         self.mixing, self.mix_par = True, par
         self.mixing_k_max = self.mixing_capped = None
         self._mix_prof = self._mix_coef = self._mix_km = self._mix_kd = None
+        self._hmix_huge = self._hmix_kh2 = None
         self._mix_spare = {}
 
     def _mix(self, dt):
@@ -721,11 +737,13 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
         _, gx, gy, kcap, wind, scalar, lowest = self._mix_coef
         gz, bz, l2 = self._mix_prof[1]
         theta = f["THL"] if par["stability"] and "THL" in f else None
+        coef = {k: wind if k in self.MIX_WINDS else scalar for k in keys}
+        if par["implicit"]:
+            return self._mix_implicit(keys, theta, gx, gy, gz, bz, l2, coef)
         spare = self._mix_spare
         for k in keys:
             spare[k] = self._scratch(spare.get(k), f[k], f[k])
         self._mix_km = self._scratch(self._mix_km, f["U"])
-        coef = {k: wind if k in self.MIX_WINDS else scalar for k in keys}
         u, v = f["U"], f["V"]                             # (the swap below leaves them in the spare buffers, unchanged)
         top = eng.les_mix({k: f[k] for k in keys}, {k: spare[k] for k in keys}, f["U"], f["V"], theta, gx, gy, gz, bz if theta is not None else None,
                           l2, kcap, self._mix_km, {k: coef[k][0] for k in keys}, {k: coef[k][1] for k in keys})
@@ -738,6 +756,26 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
             if self._vmix_huge is None:
                 self._vmix_huge = self._upload(numpy.full(self.n, float(torch.finfo(eng.dtype).max)))
             eng.les_mix({}, {}, u, v, theta, gx, gy, gz, bz if theta is not None else None, l2, self._vmix_huge, self._vmix_km, {}, {}, kmax=False)
+        self._mix_tail()
+
+    def _mix_implicit(self, keys, theta, gx, gy, gz, bz, l2, coef):
+        """K26 for K24's second launch: km of the flow under a cap that never binds (one les_mix without fields), then ONE
+        les_hmix on every field in place"""
+        eng, f, par = self._eng(), self.fields3d, self.mix_par
+        self._mix_km = self._scratch(self._mix_km, f["U"])
+        if self._hmix_huge is None:
+            self._hmix_huge = self._upload(numpy.full(self.n, float(torch.finfo(eng.dtype).max)))
+        hkey = (par["kh_cap"],)
+        self._hmix_kh2 = _kept(self._hmix_kh2, hkey, lambda: (hkey, self._upload(hmx.bound(self.n, par["kh_cap"]))))
+        top = eng.les_mix({}, {}, f["U"], f["V"], theta, gx, gy, gz, bz if theta is not None else None, l2, self._hmix_huge, self._mix_km, {}, {})
+        eng.les_hmix({k: f[k] for k in keys}, self._mix_km, {k: coef[k][0] for k in keys}, {k: coef[k][1] for k in keys}, self._hmix_kh2[1])
+        self.mixing_k_max = self._device_max(top)
+        self.mixing_capped = False                        # (so K25 mixes by this km, without a second probe)
+        self._mix_tail()
+
+    def _mix_tail(self):
+        """what follows the horizontal mixing of a step, explicit or implicit"""
+        eng, par = self._eng(), self.mix_par
         if par["vertical"]:
             m = self._to_host(eng.slab_means({"km": self._mix_km}))["km"]
             self._mix_kd = mix.face_diffusivity(m, self.diffuse_par["k_bg"])

@@ -1293,6 +1293,43 @@ class Engine:
         0: unsupported"""
         return self._geometry("vmix_cols_per_block", ktot)
 
+    # -- K26: implicit horizontal mixing of device-resident LES fields by each line's own eddy viscosity, two launches ---------------
+    @_on_engine_stream
+    def les_hmix(self, fields, km, ax, ay, kh2, axes=3, stream=None):
+        """One backward-Euler step of the horizontal mixing (include/spc.h has the rule) IN PLACE on every tensor of ``fields``
+        (dict name -> contiguous [n x itot x jtot x ktot], at most ``_abi.SPC_HMIX_MAX_FIELDS`` of one shape) by the eddy
+        viscosity ``km`` (the same shape, read only): every periodic line along i, then every line along j.  ``ax`` and ``ay``
+        are dicts name -> [n] with the names of ``fields`` (``mixing.coefficients``; fields may share a tensor) and ``kh2`` [n]
+        is ``horizontal_mixing.bound`` in the engine's dtype.  ``axes``: 1 the sweep along i alone, 2 the sweep along j alone, 3
+        both.  A field that STARTS where another field, ``km``, ``kh2`` or a coefficient starts is refused (ValueError); views
+        that overlap in part are not detected.  Two launches; longer lines than ``hmix_lines_per_block`` carries are refused
+        (SPC_ERR_UNSUPPORTED)."""
+        names = list(fields)
+        if not 1 <= len(names) <= _abi.SPC_HMIX_MAX_FIELDS:
+            raise ValueError("les_hmix takes 1 ... %d fields per launch, got %d" % (_abi.SPC_HMIX_MAX_FIELDS, len(names)))
+        for what, d in (("ax", ax), ("ay", ay)):
+            if sorted(d) != sorted(names):
+                raise ValueError("les_hmix: %s holds %s, the fields are %s" % (what, sorted(d), sorted(names)))
+        if axes not in (1, 2, 3):
+            raise ValueError("les_hmix: axes %r is none of 1 (along i), 2 (along j) and 3 (both)" % (axes,))
+        shape = n, itot, jtot, ktot = self._extents("les_hmix", names[0], fields[names[0]])
+        ck = _Checker(self.device, self.dtype)
+        g = _abi.LesHmixArgs()
+        g.n_les, g.itot, g.jtot, g.ktot, g.n_fields, g.axes = n, itot, jtot, ktot, len(names), axes
+        g.km = self._field4("km", km, shape).data_ptr()
+        g.kh2 = ck.vec("kh2", kh2, n)
+        read = [km, kh2]
+        for f, name in enumerate(names):
+            g.fields[f] = self._field4(name, fields[name], shape).data_ptr()
+            g.ax[f], g.ay[f] = ck.vec("ax[%s]" % name, ax[name], n), ck.vec("ay[%s]" % name, ay[name], n)
+            read += [ax[name], ay[name]]
+        self._no_alias("les_hmix: a field is another field, km, kh2 or a coefficient", [fields[k] for k in names], read, n)
+        self._call(self._sym("les_hmix"), ctypes.byref(g), stream=stream)
+
+    def hmix_lines_per_block(self, n):
+        """lines of ``n`` cells a workgroup of K26's k_les_hline takes in the engine's dtype (256 ... 16); 0: unsupported"""
+        return self._geometry("hmix_lines_per_block", n)
+
     # -- K7: the helpers of splib/sputils.py as batched operators (sp_coupler_amd/sputils.py keeps their names) -------
     # Each operator has a ``plan_*`` form (arguments checked and the C argument block frozen ONCE, output allocated once
     # or taken from ``out=``: ``plan.run()`` is then one foreign call, no allocation) and a convenience form that builds

@@ -6,7 +6,8 @@ Everything the kernels multiply by is computed ONCE in float64 NumPy and rounded
 and the NumPy oracle of the tests receive the same arrays, so neither divides and neither takes a cube root.  The winds and the
 scalars differ by the Prandtl number in ``ax`` and ``ay`` alone: one pair of vectors per set, so the kernel needs no extra
 rounding.  Left out of the rule: the gradients of W (diagnosed from continuity under the hydrostatic closure of K21), the moist
-correction of the stability (theta is THL), and substeps where the cap binds."""
+correction of the stability (theta is THL), and substeps where the cap binds: the cap-free way is the implicit step of K26
+(horizontal_mixing.py; ``enable_mixing(implicit=True)``), which mixes by the closure's own viscosity in one call."""
 import numpy
 
 from . import microphysics, sputils

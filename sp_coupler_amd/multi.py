@@ -347,6 +347,14 @@ class MultiDeviceEngine:
             return self.primary.les_vmix(fields, km, el, eu, kb, kv2, s0=s0, flux=flux, drag=drag, u=u, v=v, speed=speed, **kw)
         self._each("les_vmix", ex, (fields, km, el, eu, kb, kv2), dict(kw, s0=s0, flux=flux, drag=drag, u=u, v=v, speed=speed))
 
+    def les_hmix(self, fields, km, ax, ay, kh2, axes=3, **kw):
+        """K26 on every device's LES: dict of Sharded fields (mixed in place, block by block), the Sharded ``km``, the dicts ``ax``
+        and ``ay`` of Sharded [n] and ``kh2`` [n] in; two launches per device that holds rows, none on the others"""
+        ex = self._example(fields)
+        if ex is None:
+            return self.primary.les_hmix(fields, km, ax, ay, kh2, axes=axes, **kw)
+        self._each("les_hmix", ex, (fields, km, ax, ay, kh2), dict(kw, axes=axes))
+
     def slab_cloud_fraction(self, ql, idx, out=None, **kw):
         """K10's cloud fraction on every device's LES: Sharded QL field and index map in, Sharded [n x nG] out"""
         return self._run("slab_cloud_fraction", ql, idx, out=out, **kw)

@@ -53,6 +53,7 @@ MOMENTS = "spc_moments.hpp"
 BUOYANCY = "spc_buoyancy.hpp"
 MIX = "spc_mix.hpp"
 VMIX = "spc_vmix.hpp"
+HMIX = "spc_hmix.hpp"
 TRANSPORT = "spc_transport.hpp"
 TRANSPORT2 = "spc_transport2.hpp"
 GEO = "spc_geo.hpp"
@@ -88,6 +89,7 @@ radiate_body = partial(body_guard, "les_radiate_ref")
 buoyancy_body = partial(body_guard, "les_buoyancy_ref")
 mix_body = partial(body_guard, "les_mix_ref")
 vmix_body = partial(body_guard, "les_vmix_ref")
+hmix_body = partial(body_guard, "les_hmix_ref")
 geo_body = partial(body_guard, "geo_edges", dtypes=("float64",))
 lesstate_body = partial(body_guard, "les_state_ref", dtypes=("float64",))
 qtlocal_body = partial(body_guard, "les_qt_local_ref")
@@ -861,6 +863,29 @@ SPUTILS_MUTANTS = {
 # slip made in every kernel's own walk.  Every mutant only computes wrong numbers: none reads or writes outside what the shipped
 # kernels touch (mutant 1 sends the lanes of an LES to its first ktot / V levels; mutants 3 and 4 visit fewer rows or the same rows
 # of a batch again).  The guard of each is the body ``chain`` of EVERY kernel it changes, on both engines.
+# K26 (spc_hmix.hpp), numbered on its own.  Every mutant changes a VALUE only: no loop bound, barrier or launch extent differs from
+# the shipped kernel, and every index stays inside the line and the LDS of its lane.
+HMIX_MUTANTS = {
+    1: ("K26 t: the cell's own km taken twice (km[i] for km[ip]: a face no longer belongs to both its cells alike)", hmix_body("parity"),
+        [(HMIX, "const T t = ka + kn;", "const T t = ka + ka;")]),
+    2: ("K26 a: ay for ax (the sweep along i takes the coefficient of j, and the other way round)", hmix_body("parity"),
+        [(HMIX, "(axis ? a->ay[f] : a->ax[f])", "(axis ? a->ax[f] : a->ay[f])")]),
+    3: ("K26 s: the comparison of the bound reversed (the larger of s and kh2)", hmix_body("viscosity"),
+        [(HMIX, "const T sc = s < cap ? s : cap;", "const T sc = s > cap ? s : cap;")]),
+    4: ("K26 b: 1 - lo for 1 + lo", hmix_body("parity"),
+        [(HMIX, "const T b1 = (T)1 + wl;", "const T b1 = (T)1 - wl;"), (HMIX, "const T b1 = (T)1 + lo;", "const T b1 = (T)1 - lo;", 2)]),
+    5: ("K26 c: c[n-2] left out (the last eliminated cell forgets its face to the condensed one)", hmix_body("lines"),
+        [(HMIX, "const T c = wl + (m == 1 ? up : (T)0);", "const T c = wl + (T)0;"),
+         (HMIX, "const T c = (T)0 + (i + u == m - 1 ? up : (T)0);", "const T c = (T)0 + (T)0;")]),
+    6: ("K26 back substitution: the q of the neighbouring cell (q[i+1] for q[i])", hmix_body("parity"),
+        [(HMIX, "cq[u] = q[(i - u) * L];", "cq[u] = q[(i - u + 1) * L];")]),
+    7: ("K26 num: lo[n-1] and up[n-1] swapped", hmix_body("parity"),
+        [(HMIX, "const T n1 = wl * yv;", "const T n1 = lo * yv;"), (HMIX, "const T n3 = lo * yl;", "const T n3 = wl * yl;")]),
+    8: ("K26 den: z left out (the condensed cell forgets what the others hand back)", hmix_body("parity"),
+        [(HMIX, "const T den = d2 - d3;", "const T den = bl;")]),
+}
+
+
 def chain_guard(*modules):
     """the body ``chain`` of each of tests/``modules``.py: (every one of them failed, everything that failed anywhere)"""
     def guard(engine_of):
@@ -1122,7 +1147,11 @@ SPUTILS_TABLES = (
 CHAIN_TABLES = (
     Table("chain", CHAIN_MUTANTS, "K10/K11/K12/K14/K20", "chain_", "chain", "les_harness", "test_*_gpu.py::test_the_chain_cases"),
 )
-ALL_TABLES = TABLES + LATER_TABLES + SPUTILS_TABLES + CHAIN_TABLES
+#: K26's table stands in a tuple of its own as well, for the same reason
+HMIX_TABLES = (
+    Table("hmix", HMIX_MUTANTS, "K26", "hmix_", "hmix", "les_hmix_ref", "test_les_hmix_gpu"),
+)
+ALL_TABLES = TABLES + LATER_TABLES + SPUTILS_TABLES + CHAIN_TABLES + HMIX_TABLES
 
 
 if __name__ == "__main__":

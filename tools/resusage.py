@@ -3,17 +3,17 @@
 (VGPRs, SGPRs, spills, scratch, occupancy, LDS).  usage: tools/resusage.py [filter-substring | entry] [extra hipcc flags...]
 An entry of ENTRIES names a kernel family that must use no scratch and spill nothing in any instantiation: its lines are
 printed and the exit status is 1 if one of them does (tools/resusage.py microphysics, tools/resusage.py diffuse,
-tools/resusage.py advect, tools/resusage.py vadvect, tools/resusage.py radiate, tools/resusage.py qtlocal, tools/resusage.py moments, tools/resusage.py transport, tools/resusage.py transport2, tools/resusage.py eddy, tools/resusage.py hmix, tools/resusage.py speed, tools/resusage.py vmix)."""
+tools/resusage.py advect, tools/resusage.py vadvect, tools/resusage.py radiate, tools/resusage.py qtlocal, tools/resusage.py moments, tools/resusage.py transport, tools/resusage.py transport2, tools/resusage.py eddy, tools/resusage.py hmix, tools/resusage.py speed, tools/resusage.py vmix, tools/resusage.py hline)."""
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# K14, K15, K16, K17, K18, K19, K20, K22, K23, K24 (eddy, hmix), K25 (speed, vmix): every instantiation without scratch and without spills
+# K14, K15, K16, K17, K18, K19, K20, K22, K23, K24 (eddy, hmix), K25 (speed, vmix), K26 (hline): every instantiation without scratch and without spills
 ENTRIES = {"microphysics": "k_les_microphysics", "diffuse": "k_les_diffuse", "advect": "k_les_advect", "vadvect": "k_les_vadvect",
            "radiate": "k_les_radiate", "qtlocal": "k_les_qt_local", "moments": "k_les_moments", "transport": "k_les_transport", "transport2": "k_les_transport2",
-           "eddy": "k_les_eddy", "hmix": "k_les_hmix", "speed": "k_les_speed", "vmix": "k_les_vmix"}
+           "eddy": "k_les_eddy", "hmix": "k_les_hmix", "speed": "k_les_speed", "vmix": "k_les_vmix", "hline": "k_les_hline"}
 entry = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ENTRIES else None
 flt = ENTRIES[entry] if entry else sys.argv[1] if len(sys.argv) > 1 else ""
 extra = sys.argv[2:]
