@@ -787,7 +787,9 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
 
     def get_eddy_viscosity_batched(self):
         """the device tensor [n x itot x jtot x nL] (Sharded row blocks under a MultiDeviceEngine) of the capped eddy viscosity
-        km in m2/s that K24 found in the last step; None before the first step of enable_mixing()"""
+        km in m2/s that K24 found in the last step; behind a step of enable_mixing(implicit=True) the UNCAPPED km by which K26
+        mixed (its probe runs under a cap that never binds; ``kh_cap`` bounds the face means inside K26 and is not applied to
+        this tensor); None before the first step of enable_mixing(), and of every later call of it"""
         return self._mix_km if self.mixing else None
 
     # -- implicit vertical mixing by each column's own eddy viscosity (K25), opt-in ----------------------------------------------

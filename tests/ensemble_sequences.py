@@ -1,13 +1,16 @@
 """Random operation sequences of models.DeviceLESEnsemble (the class lives in sp_coupler_amd/device_les.py; the name in models
-is the same object) against its eager NumPy twin (tests/les_vmix_ref.py: HostVmixLESEnsemble / HostThermoVmixLESEnsemble, the
-top of the chain of twins): the body of tests/test_ensemble_sequences_cpu.py (on oracle-backed engines) and
+is the same object) against its eager NumPy twin (tests/les_hmix_ref.py: HostHmixLESEnsemble / HostThermoHmixLESEnsemble, the
+top of the chain of twins; with implicit=False their step is that of tests/les_vmix_ref.py): the body of tests/test_ensemble_sequences_cpu.py (on oracle-backed engines) and
 tests/test_ensemble_sequences_gpu.py (on the card).
 
 The device ensemble is a lazy, cached state machine (_thermo_stale, _means, _wp / _wp_host / _wp_w, _thermo_means, the profile
 uploads keyed on their inputs, the ping-pong buffers of K14 / K16 / K17 / K22, the fused K11 step, K19's count buffer and its wait
 for the forcing, K20's partial cache _stats / _stats_host / _stats_w, K21's profiles and pressure, K22's lid flux summed over the
 substeps, K24's profiles, coefficients, ping-pong buffers and viscosity, K25's coefficients, drag and second viscosity buffer
-with the switch between the two on ``mixing_capped``); the twin computes everything eagerly from its fields.
+with the switch between the two on ``mixing_capped``, K26's path ``_mix_implicit`` behind enable_mixing(implicit=True): the probe under
+``_hmix_huge``, ONE in-place ``les_hmix`` under the bound ``_hmix_kh2`` keyed on ``kh_cap``, ``mixing_capped`` False and the
+shared ``_mix_tail``, and the switch between that path and K24's ping-pong buffers at every later enable_mixing); the twin computes
+everything eagerly from its fields.
 ``generate`` draws a list of operations that are all valid in
 the state they meet, mutations and sparse observations mixed; ``replay`` applies the list to both and compares every observation
 bit for bit (gpu_util.assert_bits), with two exceptions: W within the bound of les_vadvect_ref.check_w (a torch expression), and
@@ -20,9 +23,12 @@ strong comes from ``params``), "buoyancy" (K21; needs vertical), "conservative" 
 conservative; the limiter comes from ``params``) and "stats" (K20: statistics observations are drawn only with it), then "mix"
 (K24, enable_mixing), "vmix" (K25, enable_vertical_mixing; needs mix, excludes diffuse) and "kmix" (enable_mixing once more with
 vertical=True: K24's slab-mean viscosity in K15; needs mix and diffuse, excludes vmix); the cap, the stability switch, the
-spacings of K24 and the drag of K25 come from ``params``.  Every newer set of modes stands at the END of MODES: the bit mask
-that seeds the generator, and so every sequence of the 48 old subsets and of the 55 combinations of ELEVEN, is what it was
-(tests/test_ensemble_sequences_cpu.py holds both digests).
+spacings of K24 and the drag of K25 come from ``params``; last "imix" (K26; needs mix): the first enable_mixing of the sequence, at
+``build`` or at a late ("enable", "mix"), passes implicit=True and the ``kh_cap`` of ``params``; every later call (a late kmix, a
+``remix``) passes the switch as it stands, and the mutation ("implicit", flag, kh_cap) calls enable_mixing with the switch flipped
+or kept and a drawn bound.  Whether K26 is on now is "imix" in the set of enabled modes.  Every newer set of modes stands at the
+END of MODES: the bit mask that seeds the generator, and so every sequence of the 48 old subsets, of the 55 combinations of
+ELEVEN and of the 14 with the mixing modes, is what it was (tests/test_ensemble_sequences_cpu.py holds the three digests).
 
 Conditions, asserted here and not left to the callers:
   * every sequence has its full length, runs to its end on both sides and ends with a full record: every profile (batched,
@@ -34,6 +40,9 @@ Conditions, asserted here and not left to the callers:
     only behind the ``qt_forcings`` that every "qt" sequence holds between two steps, and never before it;
   * a "vmix" sequence with the drag holds a ``z0m`` between two steps; in a step with K25 ``les_mix`` is called twice exactly where
     the step's ``mixing_capped`` is True, else once; between ``les_mix`` and K15 stands one ``slab_means`` (of km) with "kmix", else nothing;
+  * a step with K26 on launches exactly one ``les_mix`` per engine that holds rows, K25 or not, one ``les_hmix`` directly behind it
+    (it stands between ``les_mix`` and K15, in front of the ``slab_means``) and leaves ``mixing_capped`` False; a step with K26 off
+    launches no ``les_hmix``; an "imix" sequence launches ``les_hmix`` at least once;
   * a ``refused`` call raises ValueError on both sides, and what follows it shows that it changed nothing;
   * over a set of cases every kind of operation occurs that their modes allow (``check_kinds``).
 Properties of the device ensemble (and of the twin, where it has the method) that need no twin:
@@ -50,11 +59,13 @@ import itertools
 import numpy
 
 from sp_coupler_amd import diffusion as df
+from sp_coupler_amd import horizontal_mixing as hmx
 from sp_coupler_amd import models, spcpl
 from sp_coupler_amd import qt_forcing as qf
 from sp_coupler_amd import radiation as rad
 from sp_coupler_amd import statistics as st
 from tests import les_diffuse_ref as ldr
+from tests import les_hmix_ref as lhr
 from tests import les_moments_ref as lmo
 from tests import les_vadvect_ref as lvr
 from tests import les_vmix_ref as lvm
@@ -66,7 +77,8 @@ OLD_MODES = ("thermo", "diffuse", "micro", "advect", "vertical", "radiate")
 NEW_MODES = ("qt", "buoyancy", "conservative", "order2", "stats")
 MIX_MODES = ("mix", "vmix", "kmix")
 ELEVEN = OLD_MODES + NEW_MODES                                    # everything but the mixing: what "all modes" meant before K24
-MODES = ELEVEN + MIX_MODES
+IMIX = "imix"                                                     # K26: the first enable_mixing of the sequence passes implicit=True
+MODES = ELEVEN + MIX_MODES + (IMIX,)
 # may be enabled mid-sequence (vertical, conservative and order2 come with advect; vmix and kmix behind mix, kmix behind diffuse)
 LATE = ("diffuse", "micro", "advect", "radiate", "qt", "buoyancy") + MIX_MODES
 AFTER = {"buoyancy": ("advect",), "vmix": ("mix",), "kmix": ("mix", "diffuse")}      # a late enable waits for the late enables of these
@@ -74,18 +86,18 @@ WITH_ADVECT = ("vertical", "conservative", "order2")
 METHOD = {"thermo": "les_thermo", "diffuse": "les_diffuse", "micro": "les_microphysics", "advect": "les_advect",
           "vertical": "les_vadvect", "radiate": "les_radiate", "qt": "les_qt_local", "buoyancy": "les_buoyancy",
           "conservative": "les_transport", "order2": "les_transport2", "stats": "les_moments", "mix": "les_mix", "vmix": "les_vmix",
-          "kmix": "les_mix"}
+          "kmix": "les_mix", IMIX: "les_hmix"}
 COUNTED = ("slab_means", "slab_cloud_fraction", "variability_nudge", "les_advance", "les_thermo", "les_water_paths", "les_microphysics",
            "les_diffuse", "les_advect", "les_vadvect", "les_radiate", "les_moments", "les_qt_local", "les_buoyancy", "les_transport",
-           "les_transport2", "les_mix", "les_vmix")
+           "les_transport2", "les_mix", "les_vmix", "les_hmix")
 MUTATIONS = ("step", "step0", "row_step", "nudge", "forcings", "set_field", "presf", "rhobf", "enable", "qt_forcings", "qt_kind", "readvect",
-             "remix", "revmix", "z0m", "set_wind", "refused")
+             "remix", "revmix", "z0m", "set_wind", "refused", "implicit")
 OBSERVATIONS = ("profiles", "row", "field", "wp", "wp_means", "row_wp", "cloudfrac", "flux", "w", "courant", "counts", "lid", "pressure",
                 "stats", "row_stats", "viscosity")
 KINDS = MUTATIONS + OBSERVATIONS + ("record",)
 NEEDS = {"qt_forcings": "qt", "qt_kind": "qt", "readvect": "buoyancy", "counts": "qt", "lid": "conservative", "pressure": "buoyancy",
          "stats": "stats", "row_stats": "stats", "remix": "mix", "revmix": "vmix", "z0m": "vmix", "set_wind": "mix", "refused": "mix",
-         "viscosity": "mix"}                                      # the mode without which a kind of operation is never drawn
+         "viscosity": "mix", "implicit": IMIX}                                   # the mode without which a kind of operation is never drawn
 RELAUNCH = {"cloudfrac": {"slab_cloud_fraction"}, "wp_means": {"slab_means"}, "record": {"slab_means"}}      # property (b)
 PROFILE_KEYS = ("U", "V", "THL", "QT", "QL", "T", "QL_ice", "QR", "presf", "Rhobf", "Rain", "PS")
 ROW_GETTERS = {"get_profile_U": "U", "get_profile_V": "V", "get_profile_THL": "THL", "get_profile_QT": "QT", "get_profile_QL": "QL",
@@ -99,7 +111,7 @@ ALWAYS = ("U", "V", "THL", "QT", "QL")                            # the fields o
 # ceil(30 * 900 / (0.3 * 24000)) = 4, far below advection.MAX_SUBSTEPS (tests/test_ensemble_sequences_cpu.py checks every case)
 LATE_WAVE_SPEED = 24.0
 READVECT = dict(dx=0.8 * lvr.DX, cfl=0.3)
-DEFAULT = {"kind": "local", "limiter": "mc", "cap": None, "stability": True, "drag": True, "dx": None}
+DEFAULT = {"kind": "local", "limiter": "mc", "cap": None, "stability": True, "drag": True, "dx": None, "kh_cap": None}
 # K24 and K25.  The spacings of enable_mixing: None (those of the advection at the moment of the call, else advection.DX: with the
 # 200 m of the latter the cap binds in every step of DTS, with the 30 km of ``enable`` it does not), 250 m (binds) and 20 km (does
 # not); the caps of ``remix`` lie on both sides of either (tests/test_ensemble_sequences_cpu.py asserts that both occur)
@@ -109,6 +121,12 @@ REMIX_CAPS = (1e-3, 0.1, 1.0)
 REMIX_PRANDTL = (0.5, 0.8)
 REVMIX = dict(k_bg=(0.05, 0.3), kv_cap=(50.0, 400.0))
 REFUSED = ("diffusion", "kmix", "vmix")
+# K26.  The bounds of the face viscosity: None (horizontal_mixing.KH_CAP, 1000 m2/s), 10 m2/s and 1e5 m2/s.  The twin's largest
+# viscosity of a step is 3 to 121 m2/s at the 250 m spacing and at the default spacings without advection and up to about 2000 m2/s
+# at 20 km: 10 binds in most steps of the former, 1e5 in none at all, the default only at 20 km (tests/test_ensemble_sequences_cpu.py
+# asserts steps on both sides of the bound in force, measured on the twin by ``mixing_steps``)
+KH_CAPS = (None, 10.0, 1e5)
+KH_BINDS, KH_NEVER = KH_CAPS[1], KH_CAPS[2]
 Z0M = lvm.Z0M
 
 
@@ -116,7 +134,7 @@ def valid(modes):
     m = set(modes)
     return m <= set(MODES) and ("advect" in m or "vertical" not in m) and ("vertical" in m or not m & {"buoyancy", "conservative"}) and \
         ("conservative" in m or "order2" not in m) and ("mix" in m or not m & {"vmix", "kmix"}) and \
-        ("vmix" not in m or not m & {"diffuse", "kmix"}) and ("kmix" not in m or "diffuse" in m)
+        ("vmix" not in m or not m & {"diffuse", "kmix"}) and ("kmix" not in m or "diffuse" in m) and ("mix" in m or IMIX not in m)
 
 
 def combinations():
@@ -148,16 +166,19 @@ def _mask(modes):
 
 def params(seed, modes):
     """the kind of K19, the limiter of K23, the cap, the stability switch and the spacings of K24 (``dx``: dx = dy / 1.5, None for
-    the default) and the drag of K25 of the sequence ``generate(seed, modes)``: pure functions of (seed, modes)"""
+    the default) and the drag of K25 of the sequence ``generate(seed, modes)``, and with "imix" the bound ``kh_cap`` of K26 of its first
+    enable_mixing (a generator of its own: the four older draws are what they were): pure functions of (seed, modes)"""
     bits = bin(_mask(modes)).count("1")
     pick = numpy.random.default_rng([int(seed), _mask(modes), 24]).integers(0, 1 << 16, 4)
-    return {"kind": qf.KINDS[(int(seed) + bits) % 2], "limiter": LIMITERS[(int(seed) + bits // 2) % 2],
+    kh_cap = KH_CAPS[int(numpy.random.default_rng([int(seed), _mask(modes), 26]).integers(0, 1 << 16)) % 3] if IMIX in modes else None
+    return {"kh_cap": kh_cap, "kind": qf.KINDS[(int(seed) + bits) % 2], "limiter": LIMITERS[(int(seed) + bits // 2) % 2],
             "cap": MIX_CAPS[int(pick[0]) % 2], "stability": bool(pick[1] % 2), "drag": bool(pick[2] % 2), "dx": MIX_DX[int(pick[3]) % 3]}
 
 
 # -- the ensemble ------------------------------------------------------------------------------------------------------------
-def enable(ens, mode, modes, late=False, par=DEFAULT):
-    """one of the opt-in modes: with the parameters of les_radiate_ref.ensemble_run, or, ``late``, with others"""
+def enable(ens, mode, modes, late=False, par=DEFAULT, implicit=None):
+    """one of the opt-in modes: with the parameters of les_radiate_ref.ensemble_run, or, ``late``, with others; ``implicit``: what
+    enable_mixing passes as such (None: whether the sequence has "imix", which is what its first call passes)"""
     n = ens.n
     if mode == "diffuse":
         ens.enable_diffusion(**(dict(k_max=0.5 * df.K_MAX, h_mix=1.25 * df.H_MIX, k_bg=2.0 * df.K_BG) if late else {}))
@@ -176,7 +197,7 @@ def enable(ens, mode, modes, late=False, par=DEFAULT):
     elif mode == "buoyancy":
         ens.enable_buoyancy(**(dict(wave_speed=LATE_WAVE_SPEED) if late else {}))
     elif mode in ("mix", "kmix"):                                  # (kmix: enable_mixing once more, now with K15 behind it)
-        ens.enable_mixing(vertical=mode == "kmix", **mixing(par, **(dict(cs=0.2) if late else {})))
+        ens.enable_mixing(vertical=mode == "kmix", **mixing(par, IMIX in modes if implicit is None else implicit, **(dict(cs=0.2) if late else {})))
     elif mode == "vmix":
         ens.enable_vertical_mixing(drag=par["drag"], **(dict(k_bg=0.2, kv_cap=500.0) if late else {}))
     else:
@@ -186,21 +207,24 @@ def enable(ens, mode, modes, late=False, par=DEFAULT):
                              kappa=rad.KAPPA * (1.0 + 0.02 * (numpy.arange(n) % 5)))
 
 
-def mixing(par, **kw):
-    """the arguments of enable_mixing that ``params`` sets: the cap, the stability switch and, where given, the spacings"""
+def mixing(par, implicit=False, **kw):
+    """the arguments of enable_mixing that ``params`` sets: the cap, the stability switch and, where given, the spacings; with
+    ``implicit`` the switch of K26 and its bound (else neither is passed: the call is what it was before K26)"""
     kw.update(cap=par["cap"], stability=par["stability"])
+    if implicit:
+        kw.update(implicit=True, kh_cap=par["kh_cap"])
     if par["dx"] is not None:
         kw.update(dx=par["dx"], dy=1.5 * par["dx"])
     return kw
 
 
 def _comes_with(mode, modes):
-    """what an ``enable`` of ``mode`` switches on"""
-    return {mode} | ({m for m in WITH_ADVECT if m in modes} if mode == "advect" else set())
+    """what an ``enable`` of ``mode`` switches on ("imix" in the set of enabled modes: enable_mixing was last called with implicit=True)"""
+    return {mode} | ({m for m in WITH_ADVECT if m in modes} if mode == "advect" else {IMIX} & set(modes) if mode == "mix" else set())
 
 
 def _on_at_start(modes, late):
-    return set(modes) - set(late) - ({m for m in WITH_ADVECT} if "advect" in late else set())
+    return set(modes) - set(late) - ({m for m in WITH_ADVECT} if "advect" in late else set()) - ({IMIX} if "mix" in late else set())
 
 
 def build(engine, device, n, modes, late=(), par=DEFAULT):
@@ -211,7 +235,7 @@ def build(engine, device, n, modes, late=(), par=DEFAULT):
     assert valid(modes) and set(late) <= set(LATE) & set(modes)
     spcpl.set_engine(engine)
     thermo = "thermo" in modes
-    cls = models.DeviceLESEnsemble if device else (lvm.HostThermoVmixLESEnsemble if thermo else lvm.HostVmixLESEnsemble)
+    cls = models.DeviceLESEnsemble if device else (lhr.HostThermoHmixLESEnsemble if thermo else lhr.HostHmixLESEnsemble)
     fs = [make_les_fields(ITOT, JTOT, NL, seed=60 + (i % 7)) for i in range(n)]
     stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
     gcm = models.BatchedSyntheticGCM(n + 4, NG, 21)
@@ -263,7 +287,8 @@ def generate(seed, modes, length=LENGTH):
     """``length`` operations, the last a full record, every one valid in the state it meets (the generator tracks what exists:
     RWP needs the QR field, the flux, W and the Courant numbers a step of their mode).  Plain tuples of Python values: a
     printed list can be pasted into ``replay``.  A row is given as any integer, taken modulo n.  A kind of operation that
-    belongs to a mode the sequence does not have has weight 0 and consumes no draw."""
+    belongs to a mode the sequence does not have has weight 0 and consumes no draw; the two branches of the loop that belong to
+    "imix" (the switch of K26, and the kinds of single modes that its switches would crowd out) test for the mode first."""
     modes = tuple(m for m in MODES if m in modes)
     assert valid(modes), modes
     rng = numpy.random.default_rng([int(seed), _mask(modes)])
@@ -283,6 +308,8 @@ def generate(seed, modes, length=LENGTH):
     dropped = [False]                                              # the last mutation was a readvect: a step now runs without the buoyancy
     wread = [False]                                                # the moments of W have been read since the last mutation but a new Rhobf
     hint = [None]                                                  # the observation that would notice a stale cache behind the last mutation
+    mixed = [False]                                                # a step of the mixing has followed the last switch of K26 (at first: enable_mixing)
+    flipped = [False]                                              # the switch of K26 has been flipped
     ops = []
     small = lambda: int(rng.integers(0, 1 << 16))                                         # noqa: E731
     wp_names = ("LWP", "TWP") + (("RWP",) if "micro" in modes else ())
@@ -319,7 +346,10 @@ def generate(seed, modes, length=LENGTH):
                                      # (the mixing early, so that steps follow it, and more of what the older modes draw rarely)
                                      ("enable", 8 if room and set(pending) & set(MIX_MODES) else 0), ("readvect", 4 if again and "mix" in on else 0),
                                      ("qt_kind", 2 if "qt" in on and "mix" in modes else 0),
-                                     ("step", 3 if "kmix" in on else 0)])                            # (K15's key holds K24's viscosity: steps of one dt)
+                                     ("step", 3 if "kmix" in on else 0),                             # (K15's key holds K24's viscosity: steps of one dt)
+                                     # (K26: most "imix" sequences switch, and a step of the mixing stands between two switches: both
+                                     # paths run, the implicit one first, so ``les_hmix`` is launched whatever follows)
+                                     ("implicit", 8 if IMIX in modes and mixed[0] else 0), ("step", 5 if IMIX in modes and "mix" in on and not mixed[0] else 0)])
         if kind == "step" and "kmix" in on and ops and _is_step(ops[-1]) and rng.random() < 0.6:
             op = ("step", ops[-1][-1])                             # (K15's key holds K24's viscosity: two steps of one dt show a key without it)
         elif kind == "step":
@@ -342,6 +372,11 @@ def generate(seed, modes, length=LENGTH):
         elif kind == "refused":
             able = refusable()
             op = ("refused", able[int(rng.integers(len(able)))])
+        elif kind == "implicit":                                   # (the first flips the switch, of the later ones three in four; the others keep it: a new kh_cap alone)
+            op = ("implicit", (IMIX in on) != (rng.random() < 0.75 or not flipped[0]), KH_CAPS[int(rng.integers(len(KH_CAPS)))])
+            flipped[0] = flipped[0] or (IMIX in on) != op[1]
+            (on.add if op[1] else on.discard)(IMIX)
+            mixed[0] = False
         elif kind == "set_field":
             op = ("set_field", ("QT", "THL")[int(rng.integers(2))], small())
         elif kind == "enable":
@@ -361,11 +396,12 @@ def generate(seed, modes, length=LENGTH):
         hint[0] = ("counts",) if kind == "qt_kind" else ("lid",) if kind == "readvect" and "conservative" in on else \
             ("stats", ("U", "W"), (("W", "THL"),)) if kind == "rhobf" and wread[0] else \
             ("stats", ("W", "QT"), (("U", "W"),)) if kind == "step" and "stats" in modes and "vertical" in on else \
-            ("viscosity",) if kind in ("remix", "revmix") or (kind == "enable" and op[1] in MIX_MODES) else None
+            ("viscosity",) if kind in ("remix", "revmix", "implicit") or (kind == "enable" and op[1] in MIX_MODES) else None
         wread[0] = wread[0] and kind == "rhobf"
         dropped[0] = kind in ("readvect", "z0m")                  # (and a step behind a new roughness length: the drag's key)
         if _is_step(op):
             stepped.update(on)
+            mixed[0] = mixed[0] or (kind != "step0" and "mix" in on)
             rough[1] = True
             lag[0] = False
             counted[0] = counted[0] or ("qt" in on and handed[0])
@@ -385,8 +421,16 @@ def generate(seed, modes, length=LENGTH):
             names = tuple(k for k in st.FIELDS if k in names or k in ("U", "V"))          # (TKE)
         return names, (subset(st.PAIRS, 3) if rng.random() < 0.7 else ())
 
-    def observation():
-        kind = _choose(rng, [("profiles", 3), ("row", 3), ("field", 1.5), ("wp", 3), ("wp_means", 1), ("row_wp", 1), ("cloudfrac", 1),
+    def unseen():
+        """the observations and mutations of single modes that can be drawn now and have not been: the switches of K26 crowd them
+        out of 14 operations, and ``check_kinds`` wants each of them over a few cases"""
+        able = (("flux", "radiate" in stepped), ("w", "vertical" in stepped), ("courant", "advect" in stepped), ("pressure", "buoyancy" in on),
+                ("lid", "conservative" in on), ("counts", "qt" in on), ("row_stats", "stats" in modes), ("qt_kind", "qt" in on), ("revmix", "vmix" in on),
+                ("readvect", "buoyancy" in on and length - 1 - len(ops) >= todo() + 3))
+        return [k for k, ok in able if ok and not any(op[0] == k for op in ops)]
+
+    def observation(kind=None):
+        kind = kind or _choose(rng, [("profiles", 3), ("row", 3), ("field", 1.5), ("wp", 3), ("wp_means", 1), ("row_wp", 1), ("cloudfrac", 1),
                              ("flux", 3 if "radiate" in stepped else 0), ("w", 3 if "vertical" in stepped else 0),
                              ("courant", 2 if "advect" in stepped else 0), ("counts", 3 if "qt" in on else 0),
                              ("lid", 3 if "conservative" in on else 0), ("pressure", 4 if "buoyancy" in on else 0),
@@ -435,6 +479,11 @@ def generate(seed, modes, length=LENGTH):
             hint[0] = None
         elif dropped[0] and rng.random() < 0.7:
             ops.append(mutation("step"))
+        elif IMIX in modes and mixed[0] and (not flipped[0] or IMIX not in on) and rng.random() < 0.5:
+            # (most sequences of K26 leave it once, behind a step of it, and come back behind a step of K24)
+            ops.append(mutation("implicit"))
+        elif IMIX in modes and unseen() and rng.random() < 0.4:
+            ops.append(mutation(unseen()[0]) if unseen()[0] in MUTATIONS else observation(unseen()[0]))
         elif rng.random() < 0.4:
             ops.append(observation())
         else:
@@ -473,6 +522,9 @@ def check_sequence(ops, modes, length=None, par=None):
             on |= _comes_with(op[1], modes)
         assert op[0] != "remix" or "mix" in on, "remix before enable_mixing"
         assert op[0] != "revmix" or "vmix" in on, "revmix before enable_vertical_mixing"
+        if op[0] == "implicit":
+            assert "mix" in on and isinstance(op[1], bool) and (op[2] is None or op[2] > 0), "%r before enable_mixing, or no switch and bound" % (op,)
+            (on.add if op[1] else on.discard)(IMIX)
         assert op[0] != "refused" or (op[1] in REFUSED and ("vmix" in on if op[1] != "vmix" else on & {"diffuse", "kmix"})), "%r would not raise" % (op,)
     last = _last_forced(ops)
     assert any(_is_step(op) for op in ops[last + 1:]), "no step after the last enable"
@@ -552,7 +604,10 @@ def _number(x):
 
 
 def _viscosity(ens):
-    """K24's capped km, the viscosity K25 mixed by, the largest uncapped viscosity and whether the cap bound (None: -1)"""
+    """K24's capped km (behind a step of K26, enable_mixing(implicit=True), the UNCAPPED km that ``les_hmix`` mixed by: the probe
+    ran under ``_hmix_huge``; the bound ``_hmix_kh2`` acts on the faces inside the kernel and shows in the fields alone), the
+    viscosity K25 mixed by (under K26 the same km: ``mixing_capped`` is False and there is no second probe), the largest uncapped
+    viscosity and whether the cap bound (None: -1)"""
     return {"km": _optional(ens.get_eddy_viscosity_batched()), "kv": _optional(ens.get_vertical_viscosity_batched()),
             "k max": _number(ens.mixing_k_max), "capped": _number(ens.mixing_capped)}
 
@@ -593,8 +648,12 @@ def apply(ens, op, device, modes, on, par=DEFAULT):
         return ens.set_fields_batched(op[1], cur * (1.0 + noise))
     if kind == "z0m":                                              # the roughness length of K25's drag
         return ens.set_forcings_batched(Z0M_surf=Z0M * (0.5 + numpy.random.default_rng(op[1]).random(n)))
-    if kind == "remix":                                            # enable_mixing again: another cap and Prandtl number, vertical as it is
-        ens.enable_mixing(vertical="kmix" in on, **mixing(dict(par, cap=op[1]), prandtl=op[2]))
+    if kind == "remix":                                            # enable_mixing again: another cap and Prandtl number, vertical and implicit as they are
+        ens.enable_mixing(vertical="kmix" in on, **mixing(dict(par, cap=op[1]), IMIX in on, prandtl=op[2]))
+        return None
+    if kind == "implicit":                                         # enable_mixing again: K26 switched on or off, another bound, vertical as it is
+        ens.enable_mixing(vertical="kmix" in on, implicit=op[1], kh_cap=op[2], **mixing(par))
+        (on.add if op[1] else on.discard)(IMIX)
         return None
     if kind == "revmix":
         ens.enable_vertical_mixing(k_bg=op[1], kv_cap=op[2], drag=op[3])
@@ -613,7 +672,7 @@ def apply(ens, op, device, modes, on, par=DEFAULT):
         ens.p["Rhobf"] *= 1.01
         return None
     if kind == "enable":
-        enable(ens, op[1], modes, late=True, par=par)
+        enable(ens, op[1], modes, late=True, par=par, implicit=IMIX in on if op[1] == "kmix" else None)
         on.update(_comes_with(op[1], modes))
         return None
     if kind == "profiles":
@@ -726,7 +785,20 @@ def check_step(calls, ens, on):
     """the launches of one step of the device ensemble with the mixing: with K25 ``les_mix`` ran twice (the probe again under a cap
     that never binds) exactly where the step's cap bound, else once, per ``les_vmix`` (one per engine that holds rows); with
     K15 enabled as well nothing stands between ``les_mix`` and ``les_diffuse`` but, with vertical=True, one ``slab_means`` (of km) per
-    engine"""
+    engine.  With K26 (enable_mixing was last called with implicit=True) every engine that holds rows launched exactly ONE ``les_mix``, K25
+    or not, one ``les_hmix`` directly behind them and ``mixing_capped`` is False; then the ``les_hmix`` stand between ``les_mix`` and
+    ``les_diffuse`` in front of the ``slab_means``.  Without K26 no ``les_hmix`` is launched at all"""
+    hmix = []
+    if IMIX in on:
+        rows = len([t for t in getattr(ens.fields3d["U"], "parts", [ens.fields3d["U"]]) if t.numel()])
+        hmix = ["les_hmix"] * rows
+        assert rows >= 1 and calls.count("les_mix") == calls.count("les_hmix") == rows, \
+            "%d engines hold rows and the implicit step launched %r" % (rows, [c for c in calls if c in ("les_mix", "les_hmix")])
+        at = calls.index("les_mix")
+        assert calls[at:at + 2 * rows] == ["les_mix"] * rows + hmix, calls
+        assert ens.mixing_capped is False, "mixing_capped is %r behind an implicit step" % (ens.mixing_capped,)
+    else:
+        assert "les_hmix" not in calls, calls
     if "vmix" in on:
         per = 2 if ens.mixing_capped else 1
         assert calls.count("les_vmix") >= 1 and calls.count("les_mix") == per * calls.count("les_vmix"), \
@@ -735,7 +807,7 @@ def check_step(calls, ens, on):
         assert "les_mix" in calls and "les_vmix" not in calls, calls
     if "mix" in on and "diffuse" in on:
         between = calls[max(i for i, c in enumerate(calls) if c == "les_mix") + 1:calls.index("les_diffuse")]
-        assert between == (["slab_means"] * calls.count("les_mix") if "kmix" in on else []), calls
+        assert between == hmix + (["slab_means"] * calls.count("les_mix") if "kmix" in on else []), calls
 
 
 def check_launched(calls, modes):
@@ -841,6 +913,66 @@ def replay(ops, modes, n, engine_for_twin, engine_for_device, what="", par=DEFAU
     assert "les_qt_local" not in counter.calls[:handed], "K19 launched before the cloud-water forcing was handed over"
     check_launched(counter.calls, [m for m in modes if m != "qt" or handed is not None])
     return counter.calls
+
+
+def mixing_steps(engine_for_twin, seed, modes, n=3, length=LENGTH):
+    """what the twin alone shows of every step of ``generate(seed, modes, length)`` that K24 or K26 ran in: a list of dicts with
+    ``implicit`` (K26 ran), ``vmix`` (K25 followed), ``capped`` (the twin's mixing_capped), ``k_max`` (its mixing_k_max) and
+    ``kh_cap`` (the bound of K26 in force)"""
+    modes = tuple(m for m in MODES if m in modes)
+    ops, par = generate(seed, modes, length), params(seed, modes)
+    late = check_sequence(ops, modes, par=par)
+    twin, on, out = build(engine_for_twin, False, n, modes, late, par), _on_at_start(modes, late), []
+    for op in ops:
+        before = twin.model_time
+        apply(twin, op, False, modes, on, par)
+        if _is_step(op) and "mix" in on and twin.model_time > before:
+            assert twin.mix_par["implicit"] == (IMIX in on)
+            out.append({"implicit": IMIX in on, "vmix": "vmix" in on, "capped": bool(twin.mixing_capped), "k_max": twin.mixing_k_max,
+                        "kh_cap": twin.mix_par["kh_cap"]})
+    return out
+
+
+def implicit_conditions(cases, engine, length=LENGTH):
+    """the conditions on a set of "imix" cases (seed, modes), measured on the twin and on the generated lists; returns the counts:
+    switches implicit -> explicit and explicit -> implicit, sequences that hold steps of both paths, late enables of mix with
+    implicit and of kmix behind an implicit mix, "vmix" sequences with a step of two ``les_mix`` (the explicit cap bound) and an
+    implicit step, and the implicit steps whose largest viscosity lies above and below the ``kh_cap`` in force"""
+    count = dict.fromkeys(("to explicit", "to implicit", "both paths", "late mix", "late kmix", "vmix both", "above", "below", "switching"), 0)
+    for seed, modes in cases:
+        ops, par = generate(seed, modes, length), params(seed, modes)
+        assert IMIX in modes and ops == generate(seed, modes, length) and par == params(seed, modes) and par["kh_cap"] in KH_CAPS
+        late = check_sequence(ops, modes, par=par)
+        on = _on_at_start(modes, late)
+        assert (IMIX in on) == ("mix" not in late)
+        switched = False
+        for op in ops:
+            if op[0] == "implicit":
+                assert op[2] in KH_CAPS
+                count["to explicit"] += IMIX in on and not op[1]
+                count["to implicit"] += IMIX not in on and op[1]
+                switched = switched or (IMIX in on) != op[1]
+                (on.add if op[1] else on.discard)(IMIX)
+            elif op[0] == "enable":
+                on |= _comes_with(op[1], modes)
+                count["late mix"] += op[1] == "mix" and IMIX in on
+                count["late kmix"] += op[1] == "kmix" and IMIX in on
+        count["switching"] += switched
+        steps = mixing_steps(engine, seed, modes, length=length)
+        assert any(s["implicit"] for s in steps), "no implicit step in seed %d %s" % (seed, name_of(modes))
+        assert all(s["capped"] is False for s in steps if s["implicit"])
+        count["both paths"] += len({s["implicit"] for s in steps}) == 2
+        count["vmix both"] += any(s["vmix"] and s["implicit"] for s in steps) and any(s["vmix"] and not s["implicit"] and s["capped"] for s in steps)
+        bound = lambda s: hmx.KH_CAP if s["kh_cap"] is None else s["kh_cap"]                  # noqa: E731
+        count["above"] += sum(s["implicit"] and s["k_max"] > bound(s) for s in steps)
+        count["below"] += sum(s["implicit"] and s["k_max"] <= bound(s) for s in steps)
+        # the drawn bounds are what ensemble_sequences says of them: one binds nowhere, one in most steps of the 250 m spacing
+        assert all(s["k_max"] < KH_NEVER for s in steps)
+    fine = [s for seed, modes in cases if params(seed, modes)["dx"] == 250.0 for s in mixing_steps(engine, seed, modes, length=length)]
+    assert fine and sum(s["k_max"] > KH_BINDS for s in fine) > len(fine) / 2, [s["k_max"] for s in fine]
+    assert all(count[k] >= 1 for k in count), count
+    assert count["switching"] > len(cases) / 2, (count, len(cases))                         # most sequences switch at least once
+    return count
 
 
 def run(engine_for_twin, engine_for_device, seed, modes, n, length=LENGTH):

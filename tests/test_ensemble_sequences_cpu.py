@@ -1,7 +1,8 @@
 """Random operation sequences of models.DeviceLESEnsemble on oracle-backed engines against its NumPy twin, without a GPU
 (the body: tests/ensemble_sequences.py): all 48 valid combinations of the six old modes, 55 with the five of K19 to K23 and the
-statistics of K20 and 14 with the three mixing modes (K24, K25 and K24 with vertical=True) with two seeds, row blocks 1 + 1 + 0 of
-a MultiDeviceEngine, the fused K11 step in front of every later stage, sequences of 30 operations, the two digests of the older
+statistics of K20, 14 with the three mixing modes (K24, K25 and K24 with vertical=True) and the same 14 with "imix" (K26:
+enable_mixing(implicit=True), switched off and on again) with two seeds, row blocks 1 + 1 + 0 of
+a MultiDeviceEngine, the fused K11 step in front of every later stage, sequences of 30 operations, the three digests of the older
 sequences (they are what they were before the modes that came after them), the named regression sequences of what the sequences found, and the state mutants: faults of the ensemble's caches, patched in, that a committed sequence has to notice.
 
 Which committed sequence (seed, modes; n = 3 on one engine) notices which state mutant:
@@ -33,6 +34,14 @@ Which committed sequence (seed, modes; n = 3 on one engine) notices which state 
   24 the probe reads f["U"], f["V"] after the swap               seed 1 and seed 2 mix+vmix
   25 enable_mixing keeps _mix_km of the earlier call             seed 1 mix, seed 2 diffuse+mix+kmix
   26 _diffuse keeps the kd of its first upload with one          seed 1 diffuse+mix+kmix, seed 2 diffuse+advect+vertical+buoyancy+conservative+order2+mix+kmix
+  27 K26 mixes by the capped km: its probe runs under kcap,      seed 2 mix+imix, seed 2 mix+vmix+imix
+     not under _hmix_huge
+  28 _mix_implicit ends without _mix_tail()                      seed 1 mix+imix, seed 1 diffuse+mix+kmix+imix
+  29 _mix_implicit does not set mixing_capped = False            seed 1 mix+imix, seed 1 mix+vmix+imix
+  30 kh_cap ignored: the upload of kh2 uses the default          seed 1 mix+imix, seed 2 mix+vmix+imix
+  31 enable_mixing never switches K26 off again                  seed 1 mix+imix, seed 2 diffuse+mix+kmix+imix
+  32 _mix_implicit does not set mixing_k_max                     seed 1 mix+imix, seed 2 mix+vmix+imix
+  (20 and 25 on the path of K26 as well: seed 2 mix+vmix+imix and seed 1 mix+imix)
 (test_state_mutants_fail_a_committed_sequence asserts every line of this table.  Mutant 11 takes the call of _follow_fields
 with the assignment: the assignment alone is redundant, every path behind K19 ends in _follow_fields, which sets both.  Mutant
 12 reads the presf of the last upload into the key AND the profiles; a key that only COMPARES without presf never shows,
@@ -41,7 +50,13 @@ compares without z0m, or without kd, shows in ONE committed sequence each, becau
 row seldom share it; so mutant 22 reads the z0m of the first upload into the key and the drag, mutant 26 the kd of the first
 upload with one into the key and the profiles.  Mutant 23 leaves the launch out and hands K24's capped km to K25; what fails
 first is the count of les_mix launches of a step whose cap bound.  _mix's own _drop_statistics and _drop_water_paths are followed
-by those of _follow_fields in every path and are no mutants of their own.)"""
+by those of _follow_fields in every path and are no mutants of their own.  Mutant 29 fails first at check_step's own
+``mixing_capped is False``; without that assertion K25 would mix by the stale second buffer.  Mutant 30 shows only where a
+kh_cap other than the default is in force: its sequences hold one.  Three faults of K26's state are guarded twice and show in
+NO committed sequence (TWICE_GUARDED; test_twice_guarded_faults_do_not_show runs every "imix" case with each planted):
+enable_mixing keeping _hmix_kh2 (the key of the upload still compares kh_cap), keeping _hmix_huge (the value depends on the
+engine's type and n alone, and neither changes) and keeping _mix_spare (``_scratch`` hands a spare buffer back only where it
+still fits the field, and K24 overwrites every cell of it before the swap).)"""
 import hashlib
 import inspect
 import itertools
@@ -56,6 +71,7 @@ from sp_coupler_amd import buoyancy as buo
 from sp_coupler_amd import device_les, models, spcpl
 from sp_coupler_amd.multi import MultiDeviceEngine
 from tests import ensemble_sequences as es
+from tests import les_hmix_ref as lhr
 from tests import les_micro_ref as lmr
 from tests import les_thermo_ref as ltr
 from tests import les_vadvect_ref as lvr
@@ -88,6 +104,15 @@ MIX_COMBINATIONS = [tuple(m for m in es.MODES if m in c) for bg in ((), ("diffus
                                                                       ("advect", "vertical", "buoyancy", "stats")) for c in es.mix_combinations(bg)]
 MIX_SIX = [("mix",), ("mix", "vmix"), ("diffuse", "mix", "kmix"), TRANSPORT + ("mix", "vmix"), TRANSPORT + ("diffuse", "mix", "kmix"), MOIST + ("mix", "vmix")]
 MIX_SIX = [tuple(m for m in es.MODES if m in c) for c in MIX_SIX]
+#: the same over the 14 MIX_COMBINATIONS, computed from tests/ensemble_sequences.py as it was before "imix" (K26)
+MIX_SEQUENCES = "e0fe19100e85e51b37b76e170d39e147c9e40aabd5056940320881c0965afef3"
+#: K26: every mixing combination once more with "imix" (the first enable_mixing passes implicit=True, the mutation "implicit"
+#: switches between K26 and K24's explicit path), and the counterparts of MIX_SIX
+#: sha256 over the kind, limiter, cap, stability, drag and dx of ``params`` of all 117 older combinations, seeds 1, 2, 3 and 101,
+#: computed from tests/ensemble_sequences.py as it was before ``params`` drew the kh_cap of K26
+OLD_PARAMS = "dca1b238c3cd940b9a347b9964c9beb5799a2b4c43e30c65c69c0d1230676763"
+IMIX_COMBINATIONS = [c + (es.IMIX,) for c in MIX_COMBINATIONS]
+IMIX_SIX = [c + (es.IMIX,) for c in MIX_SIX]
 
 
 @pytest.fixture(autouse=True)
@@ -99,7 +124,7 @@ def _restore():
 
 
 def _oracle():
-    return lvm.VmixOracleEngine()
+    return lhr.HmixOracleEngine()
 
 
 def test_the_combinations_and_the_generator():
@@ -140,6 +165,23 @@ def test_the_sequences_of_the_eleven_modes_are_unchanged():
         for seed, length in ((1, 14), (2, 14), (3, 14), (101, 30)):
             h.update(repr((seed, modes, es.generate(seed, modes, length))).encode())
     assert h.hexdigest() == NEW_SEQUENCES
+
+
+def test_the_sequences_of_the_mixing_modes_are_unchanged():
+    """the same for the 14 combinations with K24 and K25, now that "imix" stands behind them: the mutation "implicit" has weight 0
+    and consumes no draw without it, and the bound of K26 in ``params`` comes from a generator of its own (CAUGHT_BY rows 19 to 26
+    depend on it)"""
+    h = hashlib.sha256()
+    for modes in MIX_COMBINATIONS:
+        for seed, length in ((1, 14), (2, 14), (3, 14), (101, 30)):
+            h.update(repr((seed, modes, es.generate(seed, modes, length))).encode())
+    assert h.hexdigest() == MIX_SEQUENCES
+    h = hashlib.sha256()                                           # the six older entries of ``params``: the draw of kh_cap is not among theirs
+    for modes in ALL_COMBINATIONS + MIX_COMBINATIONS:
+        for seed in (1, 2, 3, 101):
+            par = es.params(seed, modes)
+            h.update(repr((seed, modes, [(k, par[k]) for k in ("kind", "limiter", "cap", "stability", "drag", "dx")])).encode())
+    assert h.hexdigest() == OLD_PARAMS
 
 
 def test_the_new_combinations_and_their_generator():
@@ -274,6 +316,57 @@ def test_mixing_behind_the_fused_step(monkeypatch, modes):
 
 @pytest.mark.parametrize("modes", MIX_SIX, ids=es.name_of)
 def test_mixing_in_longer_sequences(modes):
+    es.run(_oracle(), _oracle(), 101, modes, 3, length=30)
+
+
+def test_the_implicit_combinations_and_their_generator():
+    """14 combinations with "imix" and the six of the other runs; over the committed cases every kind of operation occurs; the
+    generator and the parameters are pure; K26 is switched off and on again, one sequence and more holds steps of both paths and
+    most switch; mix is enabled late with implicit=True and kmix behind an implicit mix; with K25 one sequence and more holds
+    a step whose explicit cap binds (two les_mix) and an implicit step (one); there are implicit steps whose largest viscosity
+    lies above the kh_cap in force and steps below it (ensemble_sequences.implicit_conditions asserts every count >= 1 and that
+    more than half of the sequences switch; the counts observed with SEEDS over the 28 cases: 23 switches to explicit, 5 to
+    implicit, 23 sequences that switch and 21 with steps of both paths, 9 late mix and 2 late kmix, 2 with K25 on both paths, 20
+    implicit steps above the bound and 18 below)"""
+    assert len(IMIX_COMBINATIONS) == len(set(IMIX_COMBINATIONS)) == 14 and not set(IMIX_COMBINATIONS) & set(ALL_COMBINATIONS + MIX_COMBINATIONS)
+    assert all(es.valid(c) and c == tuple(m for m in es.MODES if m in c) for c in IMIX_COMBINATIONS) and not es.valid(("imix",)) and not es.valid(("diffuse", "imix"))
+    assert all(c in IMIX_COMBINATIONS for c in IMIX_SIX) and len(set(IMIX_SIX)) == 6 and es.MODES[-1] == es.IMIX
+    cases = [(seed, modes) for modes in IMIX_COMBINATIONS for seed in SEEDS]
+    es.check_kinds(cases)
+    es.check_kinds([(seed, modes) for modes in MIX_COMBINATIONS + IMIX_COMBINATIONS for seed in SEEDS])
+    for modes in IMIX_COMBINATIONS:
+        ops = es.generate(101, modes, 30)
+        assert ops == es.generate(101, modes, 30) and len(ops) == 30
+    assert {es.params(*c)["kh_cap"] for c in cases} == set(es.KH_CAPS)
+    assert all(es.params(seed, modes)["kh_cap"] is None for modes in MIX_COMBINATIONS for seed in SEEDS)
+    es.implicit_conditions(cases, _oracle())
+
+
+@pytest.mark.parametrize("modes", IMIX_COMBINATIONS, ids=es.name_of)
+def test_every_implicit_combination(modes):
+    for seed in SEEDS:
+        es.run(_oracle(), _oracle(), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", IMIX_SIX, ids=es.name_of)
+def test_implicit_mixing_on_row_blocks_with_an_empty_device(modes):
+    """three oracle engines, n = 2: blocks 1 + 1 + 0 (one les_mix and one les_hmix per engine that holds rows)"""
+    for seed in SEEDS:
+        multi = MultiDeviceEngine([_oracle() for _ in range(3)], min_cols_per_device=1)
+        es.run(_oracle(), multi, seed, modes, 2)
+
+
+@pytest.mark.parametrize("modes", IMIX_SIX, ids=es.name_of)
+def test_implicit_mixing_behind_the_fused_step(monkeypatch, modes):
+    """FUSED_MIN_LES patched to 0: K11 steps the fields, K26 and K25 follow"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    for seed in SEEDS:
+        calls = es.run(_oracle(), _oracle(), seed, modes, 3)
+        assert "les_advance" in calls
+
+
+@pytest.mark.parametrize("modes", IMIX_SIX, ids=es.name_of)
+def test_implicit_mixing_in_longer_sequences(modes):
     es.run(_oracle(), _oracle(), 101, modes, 3, length=30)
 
 
@@ -475,6 +568,18 @@ MUTANTS = {
     25: ("enable_mixing", "self._mix_prof = self._mix_coef = self._mix_km = self._mix_kd = None", "self._mix_prof = self._mix_coef = self._mix_kd = None"),
     26: ("_diffuse", "        key += (kd,)\n",
          "        kd = kd if self._diffuse_prof is None or len(self._diffuse_prof[0]) == len(key) else self._diffuse_prof[0][-1]\n        key += (kd,)\n"),
+    27: ("_mix_implicit", "l2, self._hmix_huge, self._mix_km, ", "l2, self._mix_coef[3], self._mix_km, "),
+    28: ("_mix_implicit", "    self._mix_tail()\n", "    pass\n"),
+    29: ("_mix_implicit", "self.mixing_capped = False", "pass"),
+    30: ("_mix_implicit", 'self._upload(hmx.bound(self.n, par["kh_cap"]))', "self._upload(hmx.bound(self.n))"),
+    31: ("enable_mixing", '"implicit": bool(implicit),', '"implicit": bool(implicit) or bool(self.mix_par and self.mix_par["implicit"]),'),
+    32: ("_mix_implicit", "self.mixing_k_max = self._device_max(top)", "pass"),
+}
+#: faults of K26's state that are guarded twice and show in NO committed sequence (test_twice_guarded_faults_do_not_show)
+TWICE_GUARDED = {
+    "enable_mixing keeps _hmix_kh2": ("enable_mixing", "self._hmix_huge = self._hmix_kh2 = None", "self._hmix_huge = None"),
+    "enable_mixing keeps _hmix_huge": ("enable_mixing", "self._hmix_huge = self._hmix_kh2 = None", "self._hmix_kh2 = None"),
+    "enable_mixing keeps _mix_spare": ("enable_mixing", "    self._mix_spare = {}\n", "    self._mix_spare = self._mix_spare or {}\n"),
 }
 AV = ("advect", "vertical")
 CAUGHT_BY = {
@@ -497,13 +602,19 @@ CAUGHT_BY = {
     17: [(1, AV + ("buoyancy", "stats")), (2, AV + ("buoyancy", "stats"))],
     18: [(1, AV + ("buoyancy", "stats")), (2, AV + ("buoyancy", "stats"))],
     19: [(1, ("mix",)), (2, ("mix", "vmix"))],
-    20: [(1, ("mix",)), (2, ("mix", "vmix"))],
+    20: [(1, ("mix",)), (2, ("mix", "vmix")), (2, ("mix", "vmix", "imix"))],
     21: [(1, ("qt", "stats", "mix", "vmix")), (2, AV + ("buoyancy", "stats", "mix", "vmix"))],
     22: [(2, ("mix", "vmix")), (1, AV + ("buoyancy", "conservative", "order2", "mix", "vmix"))],
     23: [(1, ("mix", "vmix")), (2, ("mix", "vmix"))],
     24: [(1, ("mix", "vmix")), (2, ("mix", "vmix"))],
-    25: [(1, ("mix",)), (2, ("diffuse", "mix", "kmix"))],
+    25: [(1, ("mix",)), (2, ("diffuse", "mix", "kmix")), (1, ("mix", "imix"))],
     26: [(1, ("diffuse", "mix", "kmix")), (2, ("diffuse",) + AV + ("buoyancy", "conservative", "order2", "mix", "kmix"))],
+    27: [(2, ("mix", "imix")), (2, ("mix", "vmix", "imix"))],
+    28: [(1, ("mix", "imix")), (1, ("diffuse", "mix", "kmix", "imix"))],
+    29: [(1, ("mix", "imix")), (1, ("mix", "vmix", "imix"))],
+    30: [(1, ("mix", "imix")), (2, ("mix", "vmix", "imix"))],
+    31: [(1, ("mix", "imix")), (2, ("diffuse", "mix", "kmix", "imix"))],
+    32: [(1, ("mix", "imix")), (2, ("mix", "vmix", "imix"))],
 }
 
 
@@ -516,16 +627,29 @@ def plant(monkeypatch, mutant):
 def test_state_mutants_fail_a_committed_sequence(monkeypatch, mutant):
     """each fault of the ensemble's caches, patched into DeviceLESEnsemble, fails the sequences the table names (all of them
     among those of test_every_mode_combination, those of the mutants 9 to 18 among those of test_every_new_mode_combination,
-    those of the mutants 19 and up among those of test_every_mixing_combination, two and more each); the same sequences pass
-    without it"""
-    assert all(seed in SEEDS and modes in (COMBINATIONS if mutant <= 8 else NEW_COMBINATIONS if mutant <= 18 else MIX_COMBINATIONS)
-               for seed, modes in CAUGHT_BY[mutant])
+    those of the mutants 19 to 26 among those of test_every_mixing_combination, those of the mutants 27 and up among those of
+    test_every_implicit_combination, two and more each; the rows of the mutants 20 and 25 hold a third with "imix": the same fault
+    shows on the path of K26); the same sequences pass without it"""
+    assert all(seed in SEEDS and modes in (COMBINATIONS if mutant <= 8 else NEW_COMBINATIONS if mutant <= 18 else MIX_COMBINATIONS if mutant <= 26 else
+                                           IMIX_COMBINATIONS) for seed, modes in CAUGHT_BY[mutant][:2])
+    assert all(seed in SEEDS and modes in IMIX_COMBINATIONS for seed, modes in CAUGHT_BY[mutant][2:])
+    assert len(CAUGHT_BY[mutant]) == (3 if mutant in (20, 25) else 2) or mutant <= 8
     assert len(set(CAUGHT_BY[mutant])) == len(CAUGHT_BY[mutant]) >= (1 if mutant <= 8 else 2)
     for seed, modes in CAUGHT_BY[mutant]:
         es.run(_oracle(), _oracle(), seed, modes, 3)
     plant(monkeypatch, mutant)
     for seed, modes in CAUGHT_BY[mutant]:
         with pytest.raises(AssertionError, match="operation"):
+            es.run(_oracle(), _oracle(), seed, modes, 3)
+
+
+@pytest.mark.parametrize("name", sorted(TWICE_GUARDED))
+def test_twice_guarded_faults_do_not_show(monkeypatch, name):
+    """what the docstring of this module says of them: every committed sequence with "imix" passes with the fault planted"""
+    method, old, new = TWICE_GUARDED[name]
+    monkeypatch.setattr(models.DeviceLESEnsemble, method, _edited(method, old, new))
+    for modes in IMIX_COMBINATIONS:
+        for seed in SEEDS:
             es.run(_oracle(), _oracle(), seed, modes, 3)
 
 

@@ -5,10 +5,11 @@ twin computes in NumPy on the host (its variability nudge alone goes through an 
 (gpu_util.assert_bits), W alone keeps the bound of les_vadvect_ref.check_w, and the moments that hold W are compared bit for
 bit with NumPy's moments of the device's own W: there is no tolerance to choose and nothing is measured.  Every case runs two
 seeds; nothing but the ensemble is mutated.  Twelve cases of the six old modes, twelve with the five of K19 to K23 and the
-statistics of K20 and twelve with the three mixing modes (K24, K25, K24 with vertical=True); four of each through two and three
-engines that share the card and behind the fused step.  4 x 5 x 20 at n = 3 is the smallest shape at which every cache and
-launch switch of the ensemble is still reached; K24's row walk and K25's LDS tiles have their edge shapes in
-tests/test_les_mix_gpu.py and tests/test_les_vmix_gpu.py."""
+statistics of K20, twelve with the three mixing modes (K24, K25, K24 with vertical=True) and the same twelve with "imix" (K26:
+enable_mixing(implicit=True), switched off and on again and its kh_cap changed by the mutation "implicit"); four of each through
+two and three engines that share the card and behind the fused step.  4 x 5 x 20 at n = 3 is the smallest shape at which every
+cache and launch switch of the ensemble is still reached; K24's row walk, K25's LDS tiles and K26's line lengths and LDS edges
+have their edge shapes in tests/test_les_mix_gpu.py, tests/test_les_vmix_gpu.py and tests/test_les_hmix_gpu.py."""
 import numpy
 import pytest
 import torch
@@ -17,6 +18,7 @@ from sp_coupler_amd import models, spcpl
 from sp_coupler_amd.engine import Engine
 from sp_coupler_amd.multi import MultiDeviceEngine
 from tests import ensemble_sequences as es
+from tests import les_hmix_ref as lhr
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +44,11 @@ MIX_TWELVE = [("mix",), ("mix", "vmix"), ("diffuse", "mix"), ("diffuse", "mix", 
               AV + ("buoyancy", "stats", "mix", "vmix")]
 MIX_TWELVE = [tuple(m for m in es.MODES if m in c) for c in MIX_TWELVE]
 MIX_FOUR = [MIX_TWELVE[i] for i in (1, 3, 6, 9)]
+#: K26 in the place of K24's second launch in each of them: alone, with K25, in front of K15 without and with its viscosity, behind
+#: the split advection and behind the whole transport with K21, with K12 and K18, with every moist mode, with K19 and K20 and with
+#: K21 under the statistics
+IMIX_TWELVE = [c + (es.IMIX,) for c in MIX_TWELVE]
+IMIX_FOUR = [IMIX_TWELVE[i] for i in (1, 3, 6, 9)]
 
 
 @pytest.fixture(autouse=True)
@@ -73,6 +80,13 @@ def test_the_cases_are_valid_combinations():
     par = [es.params(seed, modes) for modes in MIX_TWELVE for seed in SEEDS if "vmix" in modes]
     assert {(p["stability"], p["drag"]) for p in par} == {(s, d) for s in (True, False) for d in (True, False)}
     assert {p["dx"] for p in par} == set(es.MIX_DX)
+    assert len(IMIX_TWELVE) == len(set(IMIX_TWELVE)) == 12 and all(es.valid(c) and c == tuple(m for m in es.MODES if m in c) for c in IMIX_TWELVE)
+    assert not set(IMIX_TWELVE) & set(MIX_TWELVE) and len(set(IMIX_FOUR)) == 4 and all(c in IMIX_TWELVE for c in IMIX_FOUR)
+    assert {"vmix" in c for c in IMIX_FOUR} == {"kmix" in c for c in IMIX_FOUR} == {True, False}
+    cases = [(seed, modes) for modes in IMIX_TWELVE for seed in SEEDS]
+    es.check_kinds(cases)
+    assert {es.params(*c)["kh_cap"] for c in cases} == set(es.KH_CAPS)
+    es.implicit_conditions(cases, lhr.HmixOracleEngine())         # (the twin alone, in NumPy: switches both ways, late enables, kh_cap on both sides)
 
 
 @pytest.mark.parametrize("modes", TWELVE, ids=es.name_of)
@@ -154,6 +168,34 @@ def test_mixing_on_three_engines_sharing_the_card_one_without_rows(modes):
 @pytest.mark.parametrize("modes", MIX_FOUR, ids=es.name_of)
 def test_mixing_behind_the_fused_step(monkeypatch, modes):
     """FUSED_MIN_LES patched to 0: K11 steps the fields, K24 and K25 follow"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    for seed in SEEDS:
+        assert "les_advance" in es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", IMIX_TWELVE, ids=es.name_of)
+def test_sequences_of_the_implicit_mixing_equal_the_twin(modes):
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", IMIX_FOUR, ids=es.name_of)
+def test_implicit_mixing_on_two_engines_sharing_the_card(modes):
+    """n = 5: Sharded row blocks 3 + 2, each engine on its own stream"""
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), _sharing(2), seed, modes, 5)
+
+
+@pytest.mark.parametrize("modes", IMIX_FOUR, ids=es.name_of)
+def test_implicit_mixing_on_three_engines_sharing_the_card_one_without_rows(modes):
+    """n = 2: row blocks 1 + 1 + 0"""
+    for seed in SEEDS:
+        es.run(Engine("cuda:0"), _sharing(3), seed, modes, 2)
+
+
+@pytest.mark.parametrize("modes", IMIX_FOUR, ids=es.name_of)
+def test_implicit_mixing_behind_the_fused_step(monkeypatch, modes):
+    """FUSED_MIN_LES patched to 0: K11 steps the fields, K26 and K25 follow"""
     monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
     for seed in SEEDS:
         assert "les_advance" in es.run(Engine("cuda:0"), Engine("cuda:0"), seed, modes, 3)
