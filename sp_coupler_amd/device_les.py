@@ -421,11 +421,14 @@ class DeviceLESEnsemble(SyntheticLESEnsemble):
     def _device_max(self, t):
         """the largest element of a device vector (of the blocks of a Sharded one): one number per device to the host"""
         parts = [(e, part) for e, part in zip(self._engines(), getattr(t, "parts", [t])) if part.numel()]
-        vals = []
+        vals, out = [], []
         for e, part in parts:
             with e.on_stream():
                 vals.append(part.max())
-        return max(float(v.item()) for v in vals)
+        for (e, _), v in zip(parts, vals):                # (read on the stream that made it: torch's current stream does not wait for an engine's own)
+            with e.on_stream():
+                out.append(float(v.item()))
+        return max(out)
 
     def _advect(self, dt):
         """K16 on the stepped fields: the probe, then n_sub launches into the spare buffers; QL (without thermo) and the

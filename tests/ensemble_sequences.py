@@ -70,7 +70,7 @@ from tests import les_moments_ref as lmo
 from tests import les_vadvect_ref as lvr
 from tests import les_vmix_ref as lvm
 from tests.gpu_util import assert_bits
-from tests.les_harness import host_of
+from tests.les_harness import host_of, twin_kw
 from tests.test_vnudge import make_les_fields
 
 OLD_MODES = ("thermo", "diffuse", "micro", "advect", "vertical", "radiate")
@@ -239,7 +239,7 @@ def build(engine, device, n, modes, late=(), par=DEFAULT):
     fs = [make_les_fields(ITOT, JTOT, NL, seed=60 + (i % 7)) for i in range(n)]
     stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
     gcm = models.BatchedSyntheticGCM(n + 4, NG, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=NL, seed=21, itot=ITOT, jtot=JTOT)
+    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=NL, seed=21, itot=ITOT, jtot=JTOT, **twin_kw(cls, engine))
     rng = numpy.random.default_rng(n + 100)
     fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, ITOT, JTOT, NL)),
               "V": -2.0 + rng.standard_normal((n, ITOT, JTOT, NL))}
@@ -823,10 +823,11 @@ def check_launched(calls, modes):
 def _compare(key, got, want):
     if key == "W":                                                 # a torch expression: the bound of les_vadvect_ref.check_w
         assert got.shape == want.shape and numpy.isfinite(want).all() and numpy.abs(want).max() > 0
-        err, bound = numpy.abs(got - want).max(), 4 * numpy.finfo(numpy.float64).eps * numpy.abs(want).max()
+        assert got.dtype == want.dtype, "W: dtype %s, expected %s" % (got.dtype, want.dtype)
+        err, bound = numpy.abs(got - want).max(), 4 * numpy.finfo(want.dtype).eps * numpy.abs(want).max()
         assert err <= bound, "W: max abs err %.3e > %.3e" % (err, bound)
     else:
-        assert_bits(key, got, want)
+        assert_bits(key, got, want, dtypes=True)
 
 
 def _holds_w(key):
@@ -978,3 +979,54 @@ def implicit_conditions(cases, engine, length=LENGTH):
 def run(engine_for_twin, engine_for_device, seed, modes, n, length=LENGTH):
     """``generate(seed, modes)`` through ``replay``"""
     return replay(generate(seed, modes, length), modes, n, engine_for_twin, engine_for_device, what="seed %d" % seed, par=params(seed, modes))
+
+
+def dtype_conditions(cases, engine, n=3, length=LENGTH):
+    """what the twin alone, in the dtype of ``engine`` (les_harness.np_of: the twin's nudge runs on it), reaches over the
+    ``cases`` (seed, modes): the counts of advective steps of more than one substep and of one, of steps of K24 whose cap binds
+    and whose cap does not, of levels with a positive and with a negative increment ``a`` handed to K19, of implicit steps whose
+    largest viscosity lies above and below the ``kh_cap`` in force, and of steps of K14 behind which rain has reached the ground
+    in every LES.  Every count is asserted to be 1 or more where a case holds the mode it belongs to, and every field of every
+    twin to be of that dtype at the end"""
+    from tests import les_qt_local_ref as qlr
+    from tests.les_harness import np_of
+    T = numpy.dtype(np_of(engine))
+    count = dict.fromkeys(("substeps > 1", "substeps 1", "capped", "uncapped", "a > 0", "a < 0", "above kh_cap", "below kh_cap", "rain"), 0)
+    inner = qlr.les_qt_local
+
+    def counted(qt, ql, A, QTM):
+        assert A.dtype == T
+        count["a > 0"] += int((A > 0).sum())
+        count["a < 0"] += int((A < 0).sum())
+        return inner(qt, ql, A, QTM)
+    qlr.les_qt_local = counted
+    try:
+        for seed, modes in cases:
+            modes = tuple(m for m in MODES if m in modes)
+            ops, par = generate(seed, modes, length), params(seed, modes)
+            late = check_sequence(ops, modes, par=par)
+            twin, on = build(engine, False, n, modes, late, par), _on_at_start(modes, late)
+            assert twin.dtype == T.type
+            for op in ops:
+                before = twin.model_time
+                apply(twin, op, False, modes, on, par)
+                if not (_is_step(op) and twin.model_time > before):
+                    continue
+                if "advect" in on:
+                    count["substeps > 1" if twin.advect_substeps > 1 else "substeps 1"] += 1
+                if "mix" in on and IMIX not in on:
+                    count["capped" if twin.mixing_capped else "uncapped"] += 1
+                if IMIX in on:
+                    bound = hmx.KH_CAP if twin.mix_par["kh_cap"] is None else twin.mix_par["kh_cap"]
+                    count["above kh_cap" if twin.mixing_k_max > bound else "below kh_cap"] += 1
+                if "micro" in on:
+                    count["rain"] += bool((twin.p["Rain"] > 0).all() and (twin.rain2d > 0).any())
+            assert all(a.dtype == T for a in twin.fields3d.values()), {k: a.dtype for k, a in twin.fields3d.items()}
+            assert all(numpy.asarray(v).dtype == numpy.float64 for k, v in twin.p.items()), {k: numpy.asarray(v).dtype for k, v in twin.p.items()}
+    finally:
+        qlr.les_qt_local = inner
+    has = lambda mode: any(mode in modes for seed, modes in cases)                          # noqa: E731
+    needs = {"substeps > 1": "advect", "substeps 1": "advect", "capped": "mix", "uncapped": "mix", "a > 0": "qt", "a < 0": "qt",
+             "above kh_cap": IMIX, "below kh_cap": IMIX, "rain": "micro"}
+    assert all(count[k] >= 1 for k, mode in needs.items() if has(mode)), count
+    return count

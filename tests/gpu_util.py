@@ -38,10 +38,12 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
-def assert_bits(name, got, want):
-    """bit-exact including the sign of zero and NaN positions"""
+def assert_bits(name, got, want, dtypes=False):
+    """bit-exact including the sign of zero and NaN positions; ``dtypes``: of one dtype as well (where a device tensor is
+    compared: a float64 array that happens to hold float32 values is no field of a float32 ensemble)"""
     got, want = numpy.asarray(got), numpy.asarray(want)
     assert got.shape == want.shape, (name, got.shape, want.shape)
+    assert not dtypes or got.dtype == want.dtype, "%s: dtype %s, expected %s" % (name, got.dtype, want.dtype)
     same = (got == want) | (numpy.isnan(got) & numpy.isnan(want))
     assert same.all(), "%s: %d of %d elements differ (max abs %.3e)" % (
         name, (~same).sum(), same.size, numpy.nanmax(numpy.abs(got - want)))

@@ -22,6 +22,17 @@ def np_of(eng):
     return NP[eng.dtype]
 
 
+def f32_of(engine_cls):
+    """the float32 form of an oracle-backed engine class (tests/fake_engine.OracleEngine has ``dtype`` as a class attribute)"""
+    return type(engine_cls.__name__ + "F32", (engine_cls,), {"dtype": torch.float32, "__doc__": engine_cls.__doc__})
+
+
+def twin_kw(cls, engine):
+    """the arguments of ``cls.for_gcm`` that give a host twin the dtype of ``engine``; none for the device ensemble, which takes it
+    from its engine"""
+    return {} if cls is models.DeviceLESEnsemble else {"dtype": np_of(engine)}
+
+
 def host_of(t):
     return t if isinstance(t, numpy.ndarray) else models.DeviceLESEnsemble._host(t)
 
@@ -208,7 +219,7 @@ def ensemble_case(engine, n, cls, thermo=False, micro=False, diffuse=False, edit
                   forcings=None, record=None, before=None, itot=4, jtot=5, nL=20, steps=3):
     """an ensemble of class ``cls`` with attached U, V, THL, QT (and Qsat, or thermo; QR with the microphysics) through ``steps``
     calls of evolve_model_batched with non-zero wt and wq and one variability nudge (constantT) before the last; after each of
-    them every profile and the fields.  The hooks of a module: ``edit(fields)`` on the host fields; ``advection`` and
+    them every profile and the fields; a twin takes the dtype of ``engine`` (np_of), the engine its nudge runs on.  The hooks of a module: ``edit(fields)`` on the host fields; ``advection`` and
     ``radiation``: the arguments of enable_advection and enable_radiation (None: never called); ``enable(ens)`` behind them;
     ``forcings(rng, stack)``: more arguments of set_forcings_batched; ``record(ens, rec)``: more entries of a record;
     ``before(ens)``: what holds before the first step.  Returns (ens, list of records)"""
@@ -216,7 +227,7 @@ def ensemble_case(engine, n, cls, thermo=False, micro=False, diffuse=False, edit
     fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
     stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
     gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
+    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot, **twin_kw(cls, engine))
     rng = numpy.random.default_rng(n + 100)
     fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "U": 5.0 + rng.standard_normal((n, itot, jtot, nL)),
               "V": -2.0 + rng.standard_normal((n, itot, jtot, nL))}

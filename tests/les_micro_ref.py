@@ -17,7 +17,7 @@ from tests import les_water_paths_ref as wpr
 from tests import slab_ref
 from tests.gpu_util import assert_bits
 from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
-    DTYPES, NP, Poisoned, abi_call, blocks_of, chain_cases, counted_cus, host_of, np_of, on_both, run_bodies)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, chain_cases, counted_cus, host_of, np_of, on_both, run_bodies, twin_kw)
 from tests.test_vnudge import make_les_fields
 
 PLANES = [(1, 1), (3, 5), (8, 8)]
@@ -446,7 +446,7 @@ class _HostMicro:
             raise ValueError("the microphysics (K14) needs a QT field")
         if "QR" not in f:
             f["QR"] = numpy.zeros_like(f["QT"])
-        self.rain2d = numpy.zeros(f["QT"].shape[:3])
+        self.rain2d = numpy.zeros(f["QT"].shape[:3], dtype=f["QT"].dtype)
         self._stale = True              # thermo: K12 runs again before the next use of QL (K14 needs the cells' temperature), at presf as it is then
         self.micro_par = {"v_fall": mp.V_FALL if v_fall is None else v_fall, "qc0": mp.QC0 if qc0 is None else qc0,
                           "k_auto": mp.K_AUTO if k_auto is None else k_auto, "k_acc": mp.K_ACC if k_acc is None else k_acc}
@@ -455,15 +455,15 @@ class _HostMicro:
         """the oracle on the stepped fields and the current QL; returns its result"""
         f, p, par = self.fields3d, self.p, self.micro_par
         prof = mp.profiles(self.zh_cache, self.zf_cache, p["Rhobf"], p["presf"], dt, par["v_fall"])
-        r = les_micro(f["QT"], f["QL"], f["QR"], *[numpy.ascontiguousarray(a) for a in prof], dt, thl=f.get("THL"), temp=temp, rain=self.rain2d,
+        r = les_micro(f["QT"], f["QL"], f["QR"], *[self._r(a) for a in prof], dt, thl=f.get("THL"), temp=temp, rain=self.rain2d,
                       qc0=par["qc0"], k_auto=par["k_auto"], k_acc=par["k_acc"])
         f["QT"], f["QR"], self.rain2d = r["qt"], r["qr_new"], r["rain"]
-        p["QT"], p["QR"] = r["qt_mean"], r["qr_mean"]
+        p["QT"], p["QR"] = self._w(r["qt_mean"]), self._w(r["qr_mean"])
         if "thl" in r:
-            f["THL"], p["THL"] = r["thl"], r["thl_mean"]
+            f["THL"], p["THL"] = r["thl"], self._w(r["thl_mean"])
         if "qi_mean" in r:
-            p["QL_ice"] = r["qi_mean"]
-        p["Rain"] = numpy.array([x.mean() for x in self.rain2d])
+            p["QL_ice"] = self._w(r["qi_mean"])
+        p["Rain"] = self._w(numpy.array([x.mean() for x in self.rain2d], dtype=self.dtype))
         return r
 
 
@@ -477,17 +477,14 @@ class HostMicroLESEnsemble(_HostMicro, wpr.HostWaterPathLESEnsemble):
         if self.micro_par is None:
             return super().evolve_model_batched(t)
         f, p = self.fields3d, self.p
-        for key in ("U", "V", "THL", "QT"):
-            if key in self.tend and key in f:
-                inc = self.tend[key] * dt
-                f[key] = f[key] + inc[:, None, None, :]
+        self._step(dt)
         f["QL"] = numpy.maximum(f["QT"] - f["Qsat"], 0.0)
         self._slab_means()
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
         self._micro_step(dt, None)
         f["QL"] = numpy.maximum(f["QT"] - f["Qsat"], 0.0)
-        p["QL"] = slab_ref.slab_means(f["QL"])
+        p["QL"] = self._w(slab_ref.slab_means(f["QL"]))
         p["QL_ice"] = numpy.minimum(p["QL_ice"], p["QL"])
         p["T"] = p["THL"] * (p["presf"] / 1e5) ** (287.04 / 1004.) + 2.53e6 * p["QL"] / 1004.
         self.model_time = float(t)
@@ -504,16 +501,13 @@ class HostThermoMicroLESEnsemble(_HostMicro, wpr.HostThermoWaterPathLESEnsemble)
         if self.micro_par is None:
             return super().evolve_model_batched(t)
         f, p = self.fields3d, self.p
-        for key in ("U", "V", "THL", "QT"):
-            if key in self.tend and key in f:
-                inc = self.tend[key] * dt
-                f[key] = f[key] + inc[:, None, None, :]
+        self._step(dt)
         self._stale = True
         self._slab_means()
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
         presf = numpy.asarray(p["presf"], dtype=numpy.float64)
-        temp = ltr.les_thermo(f["THL"], f["QT"], presf, thermo.exner(presf), self.n_iter)["temp"]
+        temp = ltr.les_thermo(f["THL"], f["QT"], self._r(presf), self._r(thermo.exner(presf)), self.n_iter)["temp"]
         self._micro_step(dt, temp)
         self._stale = True
         self._ensure_ql()
@@ -530,7 +524,7 @@ def ensemble_run(engine, n, thermo, device, itot=4, jtot=5, nL=20, steps=3, micr
     fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
     stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
     gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
+    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot, **twin_kw(cls, engine))
     fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl")}
     if thermo:
         del fields["Qsat"]
@@ -578,7 +572,7 @@ def same_logs(host, dev):
         assert set(a) == set(b), (step, sorted(a), sorted(b))
         for k in a:
             assert a[k].shape == b[k].shape, (step, k)
-            assert_bits("step %d %s" % (step, k), b[k], a[k])
+            assert_bits("step %d %s" % (step, k), b[k], a[k], dtypes=True)
 
 
 def check_ensemble(one, engines, n, thermo, **kw):

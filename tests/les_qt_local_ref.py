@@ -18,7 +18,7 @@ from tests import les_vadvect_ref as lvr
 from tests import slab_ref
 from tests.gpu_util import assert_bits
 from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
-    DTYPES, NP, Poisoned, abi_call, blocks_of, ensemble_case, fill_args, host_of, np_of, on_both, run_bodies)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, ensemble_case, fill_args, host_of, np_of, on_both, run_bodies, twin_kw)
 from tests.test_vnudge import make_les_fields  # noqa: F401  (for the tests)
 
 #: one cell per plane (c is 0 or N: nothing may change), planes smaller than the row-lanes of a workgroup (2 x 3), of 64 rows
@@ -443,13 +443,10 @@ class _HostQtLocal:
         if kind is None or {"local": "QL", "strong": "QL_ref"}[kind] not in self.tend:
             return super().evolve_model_batched(t)
         f, p = self.fields3d, self.p
-        for key in self.STEP_KEYS:
-            if key in self.tend and key in f:
-                inc = self.tend[key] * dt
-                f[key] = f[key] + inc[:, None, None, :]
+        self._step(dt, self.STEP_KEYS)
         self._follow()                                            # QL and the means of the stepped fields
         a = qf.increments(kind, self.tend.get("QL"), self.tend.get("QL_ref"), p["QL"], dt)
-        f["QT"], self._counts = les_qt_local(f["QT"], f["QL"], numpy.ascontiguousarray(a), numpy.ascontiguousarray(slab_ref.slab_means(f["QT"])))
+        f["QT"], self._counts = les_qt_local(f["QT"], f["QL"], self._r(a), numpy.ascontiguousarray(slab_ref.slab_means(f["QT"])))
         stepped = {k: self.tend.pop(k) for k in self.STEP_KEYS if k in self.tend}
         try:
             super().evolve_model_batched(t)                       # (its step finds nothing to add; QL and the means follow the new QT)
@@ -506,7 +503,8 @@ def check_ensemble(one, engines, n, variant, kind):
     if variant == "plain":
         touched = (host[1]["field QT"] != plain[1]["field QT"]).any(axis=(1, 2))
         assert numpy.array_equal(touched, mixed)
-        numpy.testing.assert_allclose(host[1]["p QT"], plain[1]["p QT"], rtol=1e-13, atol=0)
+        scale = numpy.finfo(host[1]["field QT"].dtype).eps / numpy.finfo(numpy.float64).eps          # (the same count of roundings, of T)
+        numpy.testing.assert_allclose(host[1]["p QT"], plain[1]["p QT"], rtol=1e-13 * scale, atol=0)
     for engine in engines:
         lmr.same_logs(host, ensemble_run(engine, n, True, kind=kind, **kw)[1])
     lmr.same_logs(plain, ensemble_run(engines[0], n, True, kind=None, **kw)[1])
@@ -519,7 +517,7 @@ def coupler_run(engine, cls, qt_forcing, n=4, nG=19, nL=24, itot=4, jtot=4):
     profiles, the QT and QL fields and the counts after each.  Returns (ens, log)"""
     spcpl.set_engine(engine)
     gcm = models.BatchedSyntheticGCM(n + 7, nG, 3)
-    ens = cls.for_gcm(gcm, numpy.arange(1, 2 * n + 1, 2), nL=nL, seed=4, itot=itot, jtot=jtot)
+    ens = cls.for_gcm(gcm, numpy.arange(1, 2 * n + 1, 2), nL=nL, seed=4, itot=itot, jtot=jtot, **twin_kw(cls, engine))
     rng = numpy.random.default_rng(8)
     ens.attach_fields({"Qsat": ens.p["QT"][:, None, None, :] * (1.0 + 2e-3 * rng.normal(size=(n, itot, jtot, nL)))})
     cpl = driver.Coupler(gcm, ens, cplsurf=True, qt_forcing=qt_forcing)

@@ -550,33 +550,30 @@ class _HostRadiate:
         if self.radiate_par is None:
             return super().evolve_model_batched(t)
         f, p, par = self.fields3d, self.p, self.radiate_par
-        for key in ("U", "V", "THL", "QT"):
-            if key in self.tend and key in f:
-                inc = self.tend[key] * dt
-                f[key] = f[key] + inc[:, None, None, :]
+        self._step(dt)
         if "PS" in self.tend:
             p["PS"] = p["PS"] + dt * self.tend["PS"]
         if self.advect_par is not None:
             self._advect(dt)
         if self.diffuse_par is not None:
-            a, m, cp, s0 = (numpy.ascontiguousarray(x) for x in ldr.df.profiles(self.zh_cache, self.zf_cache, p["Rhobf"], dt, **self.diffuse_par))
+            a, m, cp, s0 = (self._r(x) for x in ldr.df.profiles(self.zh_cache, self.zf_cache, p["Rhobf"], dt, **self.diffuse_par))
             for key, slot in (("U", None), ("V", None), ("THL", "wt"), ("QT", "wq")):
                 if key in f:
-                    flux = numpy.asarray(self.tend[slot], dtype=numpy.float64).reshape(self.n) if slot in self.tend else None
+                    flux = self._r(numpy.asarray(self.tend[slot], dtype=numpy.float64).reshape(self.n)) if slot in self.tend else None
                     f[key] = ldr.les_diffuse(f[key], a, m, cp, s0 if flux is not None else None, flux)
         self._follow()
-        w, c = rad.profiles(p["Rhobf"], self.zh_cache, p["presf"], dt, par["kappa"])
-        f["THL"], self._flux, _ = les_radiate(f["QL"], f["THL"], w, c, par["f0"], par["f1"], rad.exp_table(numpy.float64))
+        w, c = (self._r(x) for x in rad.profiles(p["Rhobf"], self.zh_cache, p["presf"], dt, par["kappa"]))
+        f["THL"], self._flux, _ = les_radiate(f["QL"], f["THL"], w, c, self._r(par["f0"]), self._r(par["f1"]), rad.exp_table(self.dtype))
         self._follow()
         if self.micro_par is not None and self.THERMO:
             presf = numpy.asarray(p["presf"], dtype=numpy.float64)
-            self._micro_step(dt, ltr.les_thermo(f["THL"], f["QT"], presf, thermo.exner(presf), self.n_iter)["temp"])
+            self._micro_step(dt, ltr.les_thermo(f["THL"], f["QT"], self._r(presf), self._r(thermo.exner(presf)), self.n_iter)["temp"])
             self._stale = True
             self._ensure_ql()
         elif self.micro_par is not None:
             self._micro_step(dt, None)
             f["QL"] = numpy.maximum(f["QT"] - f["Qsat"], 0.0)
-            p["QL"] = slab_ref.slab_means(f["QL"])
+            p["QL"] = self._w(slab_ref.slab_means(f["QL"]))
         p["QL_ice"] = numpy.minimum(p["QL_ice"], p["QL"])
         if not self.THERMO:
             p["T"] = p["THL"] * (p["presf"] / 1e5) ** (287.04 / 1004.) + 2.53e6 * p["QL"] / 1004.

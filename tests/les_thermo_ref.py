@@ -15,7 +15,7 @@ from tests import les_advance_ref as lar
 from tests import slab_ref
 from tests.gpu_util import assert_bits
 from tests.les_harness import (  # noqa: F401  (DTYPES, NP: for the tests)
-    DTYPES, NP, Poisoned, abi_call, blocks_of, chain_cases, fill_args, np_of, on_both, run_bodies)
+    DTYPES, NP, Poisoned, abi_call, blocks_of, chain_cases, fill_args, np_of, on_both, run_bodies, twin_kw)
 
 #: n = 3; planes 1 x 1, 3 x 5 (15 rows: three batches of 4 and single rows behind them) and 8 x 8; ktot 2 and 7 (one element per
 #: lane), 64 and 160 (16-byte accesses), 65 (odd again, beyond one wave)
@@ -378,9 +378,9 @@ class HostThermoLESEnsemble(slab_ref.HostFieldLESEnsemble):
         if not self._stale or "THL" not in f or "QT" not in f:
             return
         presf = numpy.asarray(self.p["presf"], dtype=numpy.float64)
-        r = les_thermo(f["THL"], f["QT"], presf, thermo.exner(presf), self.n_iter)
+        r = les_thermo(f["THL"], f["QT"], self._r(presf), self._r(thermo.exner(presf)), self.n_iter)     # (the Exner factor of the float64 presf)
         f["Qsat"], f["QL"] = r["qsat"], r["ql"]
-        self.p["QL"], self.p["T"] = r["ql_mean"], r["t_mean"]
+        self.p["QL"], self.p["T"] = self._w(r["ql_mean"]), self._w(r["t_mean"])
         self._stale = False
 
     def get_fields_batched(self, name):
@@ -405,10 +405,7 @@ class HostThermoLESEnsemble(slab_ref.HostFieldLESEnsemble):
         if dt <= 0:
             return
         f, p = self.fields3d, self.p
-        for key in ("U", "V", "THL", "QT"):
-            if key in self.tend and key in f:
-                inc = self.tend[key] * dt
-                f[key] = f[key] + inc[:, None, None, :]
+        self._step(dt)
         self._stale = True
         self._slab_means()                                        # (runs _ensure_ql: the oracle, p["QL"], p["T"])
         if "PS" in self.tend:
@@ -424,7 +421,7 @@ def loop(engine, cls, n, nG=19, nL=24, itot=4, jtot=4, steps=3):
     constantT=True; a log of every tendency and profile after each of them, the fields, and numpy's generator state"""
     spcpl.set_engine(engine)
     gcm = models.BatchedSyntheticGCM(max(2 * n + 3, 11), nG, 3)          # (columns 1, 3, ... 2 n - 1 hold the LES)
-    ens = cls.for_gcm(gcm, numpy.arange(1, 2 * n + 1, 2), nL=nL, seed=4, itot=itot, jtot=jtot)
+    ens = cls.for_gcm(gcm, numpy.arange(1, 2 * n + 1, 2), nL=nL, seed=4, itot=itot, jtot=jtot, **twin_kw(cls, engine))
     ens.enable_thermo()
     cpl = driver.Coupler(gcm, ens, cplsurf=True, qt_forcing="variance")
     numpy.random.seed(42)

@@ -562,7 +562,8 @@ class _HostVadvect:
             return None
         rho = numpy.asarray(self.p["Rhobf"], dtype=numpy.float64)
         face = 0.5 * (rho + numpy.concatenate([rho[:, 1:], rho[:, -1:]], axis=1))
-        return self._mtop / (face * self._mtop_dt)[:, None, None, :]
+        # (float64 from the T mass flux, rounded once: within 3 roundings of the device's expression in T, bound of check_w: 4)
+        return (self._mtop / (face * self._mtop_dt)[:, None, None, :]).astype(self.dtype)
 
 
 class HostVadvectLESEnsemble(_HostVadvect, lar.HostAdvectLESEnsemble):
@@ -598,7 +599,7 @@ def check_w(ens, twin):
     """the device W against the twin's: a torch expression, so within a few roundings (4 eps of the largest |W|)"""
     w, want = host_of(ens.get_vertical_wind_batched()), twin.get_vertical_wind_batched()
     assert w.shape == want.shape and numpy.isfinite(want).all() and numpy.abs(want).max() > 0
-    assert numpy.abs(w - want).max() <= 4 * numpy.finfo(numpy.float64).eps * numpy.abs(want).max()
+    assert w.dtype == want.dtype and numpy.abs(w - want).max() <= 4 * numpy.finfo(want.dtype).eps * numpy.abs(want).max()
 
 
 def check_ensemble(one, engines, n, thermo, micro=False, diffuse=False, **kw):

@@ -12,7 +12,7 @@ from sp_coupler_amd import _abi, models, spcpl
 from tests import les_thermo_ref as ltr
 from tests import slab_ref
 from tests.gpu_util import assert_bits
-from tests.les_harness import DTYPES, NP, Poisoned, np_of, on_both, run_bodies  # noqa: F401  (DTYPES: for the tests)
+from tests.les_harness import DTYPES, NP, Poisoned, np_of, on_both, run_bodies, twin_kw  # noqa: F401  (DTYPES: for the tests)
 from tests.test_vnudge import make_les_fields
 
 PLANES = [(1, 1), (3, 5), (8, 8)]
@@ -335,15 +335,15 @@ class _HostWaterPaths:
         have = [k for k in names if WATER_PATHS[k] in f]
         if not have:
             raise KeyError(names)
-        w = numpy.ascontiguousarray(self.water_path_weights())
+        w = self._r(self.water_path_weights())                     # .astype(T) of the float64 product
         res = {k: water_paths(numpy.ascontiguousarray(f[WATER_PATHS[k]]), w) for k in have}
         if cloud_cover:
             res["top"] = cloud_top(f["QL"])
-            res["cover"] = cover_of(res["top"], numpy.float64)
+            res["cover"] = cover_of(res["top"], self.dtype)
         return res
 
     def get_water_path_means(self, names=("LWP", "TWP", "RWP")):
-        return {k: numpy.array([x.mean() for x in v]) for k, v in self.get_water_paths_batched(names).items()}
+        return {k: numpy.array([x.mean() for x in v], dtype=self.dtype) for k, v in self.get_water_paths_batched(names).items()}
 
     def row_field(self, i, name):
         return self.get_water_paths_batched((name,))[name][i]
@@ -369,7 +369,7 @@ def ensemble_run(engine, n, thermo, device, itot=4, jtot=5, nL=20, with_qr=True)
     fs = [make_les_fields(itot, jtot, nL, seed=60 + (i % 7)) for i in range(n)]
     stack = lambda k: numpy.stack([f[k] for f in fs])                                      # noqa: E731
     gcm = models.BatchedSyntheticGCM(n + 4, 19, 21)
-    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot)
+    ens = cls.for_gcm(gcm, numpy.arange(1, n + 1), nL=nL, seed=21, itot=itot, jtot=jtot, **twin_kw(cls, engine))
     fields = {"Qsat": stack("qsat"), "QT": stack("qt"), "THL": stack("thl"), "QL": stack("ql")}
     for i, j in ((0, 0), (1, 2)):                                  # two clear columns: top == -1, cover < 1
         fields["QT"][:, i, j, :] *= 0.3

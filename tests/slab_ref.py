@@ -89,10 +89,38 @@ for _m, _k in (("get_profile_U", "U"), ("get_profile_V", "V"), ("get_profile_THL
 
 
 class HostFieldLESEnsemble(models.SyntheticLESEnsemble):
-    """models.DeviceLESEnsemble with NumPy fields (float64): spcpl takes its host-field path.  The executable definition of
-    what the device ensemble computes."""
+    """models.DeviceLESEnsemble with NumPy fields of ``dtype`` T (float64, or float32 for the twin of an ensemble on a float32
+    engine): spcpl takes its host-field path.  The executable definition of what the device ensemble computes.  The rule of T,
+    stated here and in every twin above this one without a helper of device_les.py (with T = float64 every ``astype`` below is
+    the identity):
+      * the fields and every kernel output are T (km, phi, counts' partners, water paths, fluxes, mtop, statistics);
+      * a quantity the host forms is formed in float64 from float64 inputs and rounded ONCE, ``_r``: .astype(T), where a kernel
+        takes it (hx, hy, a, m, cp, s0, gx ... l2, kcap, kh2, w, c, tables, t0, lex, s, g, r, the surface fluxes);
+      * the step is (tend.astype(T) * T(dt)).astype(T), then one add in T (``_step``);
+      * what comes back from a kernel enters ``p`` widened exactly, ``_w``; the host arithmetic on p (PS, T, QL_ice, Rain
+        without the microphysics) stays float64;
+      * a comparison the host makes uses the rounded value on both sides (mixing_capped, the substeps from the Courant maximum)."""
 
     MEAN_KEYS = ("U", "V", "THL", "QT", "QL")
+    STEP_KEYS = ("U", "V", "THL", "QT")
+    dtype = numpy.float64                                          # T: a class attribute, or the ``dtype`` of for_gcm
+
+    def _r(self, a):
+        """a float64 quantity of the host rounded once to T, contiguous: what a kernel takes"""
+        return numpy.ascontiguousarray(numpy.asarray(a, dtype=numpy.float64).astype(self.dtype))
+
+    @staticmethod
+    def _w(a):
+        """what came back from a kernel, widened exactly: what enters p"""
+        return numpy.asarray(a, dtype=numpy.float64)
+
+    def _step(self, dt, keys=STEP_KEYS):
+        """every field of ``keys`` that has a tendency takes (tend.astype(T) * T(dt)).astype(T) in one add in T"""
+        f, T = self.fields3d, numpy.dtype(self.dtype).type
+        for key in keys:
+            if key in self.tend and key in f:
+                inc = (self._r(self.tend[key]) * T(dt)).astype(self.dtype)
+                f[key] = f[key] + inc[:, None, None, :]
 
     def __init__(self, grid_indices, zf, zh, prof, itot=8, jtot=8):
         super().__init__(grid_indices, zf, zh, prof)
@@ -100,9 +128,11 @@ class HostFieldLESEnsemble(models.SyntheticLESEnsemble):
         self.fields3d = {}
 
     @classmethod
-    def for_gcm(cls, gcm, grid_indices, nL=160, seed=0, itot=8, jtot=8):
+    def for_gcm(cls, gcm, grid_indices, nL=160, seed=0, itot=8, jtot=8, dtype=None):
         ens = super().for_gcm(gcm, grid_indices, nL, seed)
         ens.itot, ens.jtot = itot, jtot
+        if dtype is not None:
+            ens.dtype = numpy.dtype(dtype).type
         return ens
 
     def __getitem__(self, i):
@@ -120,6 +150,11 @@ class HostFieldLESEnsemble(models.SyntheticLESEnsemble):
         for k, v in fields.items():
             self.set_fields_batched(k, v)
 
+    def set_fields_batched(self, name, values):
+        """the field rounded to T: what the upload of the device ensemble does"""
+        super().set_fields_batched(name, values)
+        self.fields3d[name] = self.fields3d[name].astype(self.dtype)
+
     def _ensure_ql(self):
         f = self.fields3d
         if "QL" not in f:
@@ -133,7 +168,7 @@ class HostFieldLESEnsemble(models.SyntheticLESEnsemble):
     def _slab_means(self):
         if "QT" in self.fields3d and "Qsat" in self.fields3d:
             self._ensure_ql()
-        m = {k: slab_means(self.fields3d[k]) for k in self.MEAN_KEYS if k in self.fields3d}
+        m = {k: self._w(slab_means(self.fields3d[k])) for k in self.MEAN_KEYS if k in self.fields3d}
         self.p.update(m)
         return m
 
@@ -144,17 +179,14 @@ class HostFieldLESEnsemble(models.SyntheticLESEnsemble):
 
     def get_cloudfraction_batched(self, indices, out):
         self._ensure_ql()
-        numpy.copyto(out, cloud_fraction(self.fields3d["QL"], numpy.asarray(indices)))
+        numpy.copyto(out, cloud_fraction(self.fields3d["QL"], numpy.asarray(indices)))          # (T, widened exactly)
 
     def evolve_model_batched(self, t):
         dt = float(t) - self.model_time
         if dt <= 0:
             return
         f, p = self.fields3d, self.p
-        for key in ("U", "V", "THL", "QT"):
-            if key in self.tend and key in f:
-                inc = self.tend[key] * dt
-                f[key] = f[key] + inc[:, None, None, :]
+        self._step(dt)
         if "QL" in f or ("QT" in f and "Qsat" in f):
             f["QL"] = numpy.maximum(f["QT"] - f["Qsat"], 0.0)
         self._slab_means()

@@ -65,18 +65,21 @@ import textwrap
 
 import numpy
 import pytest
+import torch
 
 from sp_coupler_amd import advection as adv
 from sp_coupler_amd import buoyancy as buo
 from sp_coupler_amd import device_les, models, spcpl
 from sp_coupler_amd.multi import MultiDeviceEngine
 from tests import ensemble_sequences as es
+from tests import gpu_util
 from tests import les_hmix_ref as lhr
 from tests import les_micro_ref as lmr
 from tests import les_thermo_ref as ltr
 from tests import les_vadvect_ref as lvr
 from tests import les_vmix_ref as lvm
 from tests import slab_ref
+from tests.les_harness import NP, f32_of
 
 SEEDS = (1, 2)
 COMBINATIONS = es.combinations()
@@ -420,7 +423,12 @@ LATE_VERTICAL_MIXING = (("mix", "vmix"), [("step", 300.0), ("enable", "vmix"), (
 #: ... and the same behind enable_vertical_mixing() called again
 SECOND_ENABLE_VERTICAL_MIXING = (("mix", "vmix"), [("step", 300.0), ("z0m", 3), ("revmix", 0.3, 400.0, True), ("viscosity",), ("step", 300.0), ("viscosity",),
                                                     ("record",)], {"dx": 20000.0})
-REGRESSIONS = {"second enable_mixing": SECOND_ENABLE_MIXING, "late vertical mixing": LATE_VERTICAL_MIXING,
+#: the Courant numbers of engines that launch on streams of their own: _device_max read each engine's maximum on torch's current
+#: stream, which does not wait for the engine's, so under a MultiDeviceEngine whose engines share a card the substeps and the
+#: recorded sums were now and then those of recycled memory (seen at 130 LES, where the launches are long enough; the GPU module
+#: replays this case there, test_the_courant_maximum_is_read_on_the_stream_that_made_it holds the ordering without a GPU)
+COURANT_ON_OWN_STREAMS = (("advect", "vertical", "buoyancy"), [("forcings", 1), ("step", 900.0), ("courant",), ("step", 900.0), ("courant",), ("w",), ("record",)])
+REGRESSIONS = {"courant on own streams": COURANT_ON_OWN_STREAMS, "second enable_mixing": SECOND_ENABLE_MIXING, "late vertical mixing": LATE_VERTICAL_MIXING,
                "second enable_vertical_mixing": SECOND_ENABLE_VERTICAL_MIXING, "unobserved first step": UNOBSERVED_FIRST_STEP, "row after nudge": ROW_AFTER_NUDGE, "row after set_fields": ROW_AFTER_SET_FIELDS,
                "row water path after Rhobf": ROW_WATER_PATH_AFTER_RHOBF, "late microphysics after presf": LATE_MICRO_AFTER_PRESF,
                "statistics of W after Rhobf": W_STATISTICS_AFTER_RHOBF, "only the statistics of W after Rhobf": ONLY_W_STATISTICS_AFTER_RHOBF}
@@ -435,6 +443,50 @@ def test_named_regressions(name):
 def _regression(name):
     modes, ops = REGRESSIONS[name][:2]
     return modes, ops, dict(es.DEFAULT, **(REGRESSIONS[name][2] if len(REGRESSIONS[name]) > 2 else {}))
+
+
+def test_the_courant_maximum_is_read_on_the_stream_that_made_it():
+    """_device_max forms every engine's maximum AND reads it to the host inside that engine's on_stream(): a read on torch's
+    current stream would not wait for an engine that launches on a stream of its own"""
+    import contextlib
+    active, events = [], []
+
+    class Scalar:
+        def __init__(self, owner, value):
+            self.owner, self.value = owner, value
+
+        def item(self):
+            events.append(("item", self.owner.name, list(active)))
+            return self.value
+
+    class Part:
+        def __init__(self, owner, value):
+            self.owner, self.value = owner, value
+
+        def numel(self):
+            return 1
+
+        def max(self):
+            events.append(("max", self.owner.name, list(active)))
+            return Scalar(self.owner, self.value)
+
+    class StreamEngine:
+        def __init__(self, name):
+            self.name = name
+
+        @contextlib.contextmanager
+        def on_stream(self):
+            active.append(self.name)
+            try:
+                yield
+            finally:
+                active.pop()
+    a, b = StreamEngine("a"), StreamEngine("b")
+    ens = models.DeviceLESEnsemble.__new__(models.DeviceLESEnsemble)
+    ens.engine = type("Two", (), {"engines": [a, b]})()
+    got = ens._device_max(type("Blocks", (), {"parts": [Part(a, 0.25), Part(b, 0.75)]})())
+    assert got == 0.75 and sorted(e[:2] for e in events) == [("item", "a"), ("item", "b"), ("max", "a"), ("max", "b")]
+    assert all(on == [name] for _, name, on in events), events
 
 
 def test_without_the_twin_fix_a_second_enable_mixing_keeps_the_last_step(monkeypatch):
@@ -526,8 +578,11 @@ def test_without_the_partial_drop_a_new_rhobf_costs_every_moment(monkeypatch):
 
 # -- state mutants ---------------------------------------------------------------------------------------------------------------
 def _edited(method, old, new):
-    """``method`` of DeviceLESEnsemble with ``old`` (which occurs exactly once in its source) replaced by ``new``"""
-    src = textwrap.dedent(inspect.getsource(getattr(models.DeviceLESEnsemble, method)))
+    """``method`` of DeviceLESEnsemble with ``old`` (which occurs exactly once in its source) replaced by ``new``; of a method
+    under ``models._timed`` the function inside the wrapper is edited and wrapped again (its source holds the decorator)"""
+    fn = getattr(models.DeviceLESEnsemble, method)
+    fn = next((c.cell_contents for c in fn.__closure__ or () if getattr(c.cell_contents, "__name__", None) == method), fn)
+    src = textwrap.dedent(inspect.getsource(fn))
     assert src.count(old) == 1, (method, old, src.count(old))
     ns = dict(vars(device_les))
     exec(compile(src.replace(old, new), "<state mutant of %s>" % method, "exec"), ns)
@@ -668,3 +723,158 @@ def test_a_failure_names_its_sequence_and_replay_reproduces_it(monkeypatch):
     assert printed == list(ops[:at + 1])
     with pytest.raises(AssertionError, match="operation %d " % at):
         es.replay(ops, modes, 3, _oracle(), _oracle())
+
+
+# -- float32: the same sequences on float32 engines against the float32 twin ------------------------------------------------------
+#: The twin has a dtype T (tests/slab_ref.HostFieldLESEnsemble states the rule: fields and kernel outputs are T; what the host forms
+#: is float64 and rounded once where a kernel takes it; the step is (tend.astype(T) * T(dt)).astype(T) and one add; what comes back
+#: enters p widened exactly; a comparison of the host uses the rounded value on both sides).  ensemble_sequences.build hands the
+#: twin the dtype of the engine its nudge runs on, and every comparison of a device tensor requires one dtype (assert_bits(...,
+#: dtypes=True)).  The generator, the seeds and the 24 combinations are those of the float64 runs above.
+F32_CASES = SIX + NEW_SIX + MIX_SIX + IMIX_SIX
+OracleEngine32 = f32_of(lhr.HmixOracleEngine)
+
+
+def _oracle32():
+    return OracleEngine32()
+
+
+def test_the_float32_twin_is_float32_and_is_not_the_float64_twin():
+    """the fields of the float32 twin are float32 at the end of a sequence, its profiles float64 holding float32 values where a
+    kernel made them, and they differ from the float64 twin's; with dtype=float64 every astype of the rule is the identity"""
+    modes = ("thermo", "diffuse", "micro", "advect", "vertical", "radiate")
+    ops, par = es.generate(1, modes), es.params(1, modes)
+    late = es.check_sequence(ops, modes, par=par)
+    rec = {}
+    for eng in (_oracle(), _oracle32()):
+        twin, on = es.build(eng, False, 3, modes, late, par), es._on_at_start(modes, late)
+        assert twin.dtype == NP[eng.dtype]
+        for op in ops:
+            got = es.apply(twin, op, False, modes, on, par)
+        rec[eng.dtype] = got
+        assert all(a.dtype == NP[eng.dtype] for a in twin.fields3d.values()) and twin.rain2d.dtype == NP[eng.dtype]
+    lo, hi = rec[torch.float32], rec[torch.float64]
+    assert list(lo) == list(hi)
+    for k in ("field U", "field QT", "field QL", "field QR", "LWP", "rain2d", "flux", "W"):
+        assert lo[k].dtype == numpy.float32 and hi[k].dtype == numpy.float64, k
+        assert not numpy.array_equal(lo[k], hi[k]) and numpy.allclose(lo[k], hi[k], rtol=1e-2, atol=1e-5 * numpy.abs(hi[k]).max()), k
+    for k in ("p THL", "p QT", "p QR", "p Rain", "got U", "mean TWP"):
+        assert numpy.asarray(lo[k]).dtype in (numpy.float64, numpy.float32) and numpy.array_equal(lo[k], numpy.asarray(lo[k]).astype(numpy.float32)), k
+    assert lo["p PS"].dtype == numpy.float64 and not numpy.array_equal(lo["p PS"], lo["p PS"].astype(numpy.float32))    # host arithmetic stays float64
+
+
+def test_float32_generator_conditions():
+    """measured on the float32 twin alone and asserted (ensemble_sequences.dtype_conditions): the float32 runs of F32_CASES with
+    SEEDS reach steps of more than one substep and of one, a cap of K24 that binds and one that does not, both signs of K19's a,
+    implicit steps above and below kh_cap and rain on the ground.  The counts observed, the same on the float64 twin: 30 steps of
+    more than one substep and 31 of one, 37 capped and 11 uncapped, 285 levels with a > 0 and 563 with a < 0, 10 implicit steps
+    above the bound and 8 below, 38 steps of K14 with rain on the ground: no committed seed loses a condition in float32"""
+    cases = [(seed, modes) for modes in F32_CASES for seed in SEEDS]
+    assert len(set(F32_CASES)) == 24
+    count = es.dtype_conditions(cases, _oracle32())
+    assert all(v >= 1 for v in count.values()), count
+    for table in (SIX, NEW_SIX, MIX_SIX, IMIX_SIX):               # (each family alone reaches what its modes allow: asserted inside)
+        es.dtype_conditions([(seed, modes) for modes in table for seed in SEEDS], _oracle32())
+
+
+@pytest.mark.parametrize("modes", F32_CASES, ids=es.name_of)
+def test_float32_sequences_equal_the_float32_twin(modes):
+    for seed in SEEDS:
+        es.run(_oracle32(), _oracle32(), seed, modes, 3)
+
+
+@pytest.mark.parametrize("modes", F32_CASES, ids=es.name_of)
+def test_float32_on_row_blocks_with_an_empty_device(modes):
+    """three float32 oracle engines, n = 2: blocks 1 + 1 + 0"""
+    for seed in SEEDS:
+        multi = MultiDeviceEngine([_oracle32() for _ in range(3)], min_cols_per_device=1)
+        es.run(_oracle32(), multi, seed, modes, 2)
+
+
+@pytest.mark.parametrize("name", sorted(REGRESSIONS))
+def test_float32_named_regressions(name):
+    modes, ops, par = _regression(name)
+    es.replay(ops, modes, 3, _oracle32(), _oracle32(), what=name + " (float32)", par=par)
+
+
+def test_a_float64_array_of_float32_values_is_no_float32_field():
+    """assert_bits(..., dtypes=True), the comparison of every device tensor of a sequence: equal values of another dtype fail"""
+    a = numpy.arange(6, dtype=numpy.float32) / 3
+    gpu_util.assert_bits("same", a, a.copy(), dtypes=True)
+    gpu_util.assert_bits("values alone", a.astype(numpy.float64), a)
+    with pytest.raises(AssertionError, match="dtype float64, expected float32"):
+        gpu_util.assert_bits("widened", a.astype(numpy.float64), a, dtypes=True)
+    with pytest.raises(AssertionError, match="W: dtype"):
+        es._compare("W", a.astype(numpy.float64), a)
+
+
+# -- slips of the rounding rule ----------------------------------------------------------------------------------------------------
+#: (method, old, new) edits of device_les.py as in MUTANTS.  Each leaves every float64 bit where it is (the float64 sequences of
+#: its DTYPE_CAUGHT_BY entry pass with it planted: asserted) and fails those sequences in float32 (asserted).
+#:   1  the step as (tend64 * dt).to(T): the product formed in float64 and rounded once
+#:   2  K15's face diffusivity from a float64 mean of km (the launch of K10 still runs; its result is not used)
+#:   3  K21's profiles t0, lex and s from a presf that was rounded to T first
+#:   4  the weights Rhobf dz (K13's w, K17's g and r) as the product of two rounded factors
+#:   5  K12's Exner factor from a presf that was rounded to T first
+#:   6  K15's a, m, cp and s0 from a Rhobf that was rounded to T first
+#:   7  K14's profiles from a presf that was rounded to T first
+_ROUNDED = "numpy.asarray(self._host(self._upload(%s)), dtype=numpy.float64)"
+DTYPE_MUTANTS = {
+    1: ("evolve_model_batched", "self._per_device(step, f[key], self._upload(self.tend[key]))",
+        "self._per_device(lambda field, inc: field.add_(inc[:, None, None, :]), f[key], self._upload(numpy.asarray(self.tend[key], dtype=numpy.float64) * dt))"),
+    2: ("_mix_tail", 'm = self._to_host(eng.slab_means({"km": self._mix_km}))["km"]',
+        'm = self._to_host(eng.slab_means({"km": self._mix_km}))["km"]\n'
+        '        m = numpy.stack([x.mean(axis=(0, 1)) for x in numpy.asarray(self._host(self._mix_km), dtype=numpy.float64)])'),
+    3: ("_buoyancy_profiles", "key[0], key[1], key[2] if has_ql else None, key[3], key[4]",
+        "key[0], key[1], key[2] if has_ql else None, " + _ROUNDED % "key[3]" + ", key[4]"),
+    4: ("water_path_weights", 'return numpy.asarray(self.p["Rhobf"], dtype=numpy.float64) * dz',
+        "return " + _ROUNDED % 'numpy.asarray(self.p["Rhobf"], dtype=numpy.float64)' + " * " + _ROUNDED % "dz"),
+    5: ("_ensure_thermo", "self._upload(th.exner(presf))", "self._upload(th.exner(" + _ROUNDED % "presf" + "))"),
+    6: ("_diffuse", "df.profiles(key[5], key[6], key[4], dt, ", "df.profiles(key[5], key[6], " + _ROUNDED % "key[4]" + ", dt, "),
+    7: ("_microphysics", "mp.profiles(key[4], key[5], key[3], key[2], dt, ", "mp.profiles(key[4], key[5], key[3], " + _ROUNDED % "key[2]" + ", dt, "),
+}
+KMIX = ("diffuse", "mix", "kmix")
+DTYPE_CAUGHT_BY = {
+    1: [(1, ()), (2, ("micro", "radiate"))],
+    2: [(1, KMIX), (2, KMIX + (es.IMIX,))],
+    3: [(1, AV + ("buoyancy", "conservative", "order2")), (2, es.ELEVEN)],
+    4: [(1, ()), (2, ("diffuse", "advect", "vertical"))],
+    5: [(1, ("thermo", "micro")), (2, ("thermo", "diffuse", "advect", "radiate"))],
+    6: [(1, ("diffuse", "advect", "vertical")), (2, ("diffuse", "micro", "qt"))],
+    7: [(2, ("diffuse", "micro", "qt")), (1, es.ELEVEN)],
+}
+#: edits that are NOT counted among the slips.  The first changes no float32 bit: under K26 the probe's cap becomes +inf in
+#: float32 (finfo(float64).max rounds to it), and min(k, +inf) is k for every k the closure forms; NaN passes either cap.  The
+#: second is a slip that no committed sequence shows: ``mixing_capped`` differs only where the largest viscosity of a step lies
+#: between the float64 cap and its rounding, an interval of half an ulp.
+DTYPE_EQUIVALENT = {
+    "the cap that never binds from finfo(float64)": ("_mix_implicit", "float(torch.finfo(eng.dtype).max)", "float(torch.finfo(torch.float64).max)"),
+    "lowest from the float64 mix.cap": ("_mix", "float(self._host(kcap).min())", 'float(mix.cap(wind, scalar, par["cap"]).min())'),
+}
+
+
+@pytest.mark.parametrize("mutant", sorted(DTYPE_MUTANTS))
+def test_rounding_slips_pass_float64_and_fail_float32(monkeypatch, mutant):
+    """each slip of the rounding rule, patched into DeviceLESEnsemble: the float64 sequences of its DTYPE_CAUGHT_BY entry stay
+    bit-equal to the twin, the same sequences in float32 fail; without it both pass (all among F32_CASES and SEEDS)"""
+    method, old, new = DTYPE_MUTANTS[mutant]
+    cases = [(seed, tuple(m for m in es.MODES if m in modes)) for seed, modes in DTYPE_CAUGHT_BY[mutant]]
+    assert len(set(cases)) >= 2 and all(seed in SEEDS and modes in F32_CASES for seed, modes in cases)
+    for seed, modes in cases:
+        es.run(_oracle32(), _oracle32(), seed, modes, 3)
+    monkeypatch.setattr(models.DeviceLESEnsemble, method, _edited(method, old, new))
+    for seed, modes in cases:
+        es.run(_oracle(), _oracle(), seed, modes, 3)
+        with pytest.raises(AssertionError, match="operation"):
+            es.run(_oracle32(), _oracle32(), seed, modes, 3)
+
+
+@pytest.mark.parametrize("name", sorted(DTYPE_EQUIVALENT))
+def test_equivalent_edits_change_no_committed_bit(monkeypatch, name):
+    """what DTYPE_EQUIVALENT says of them: every float32 and float64 sequence with the mixing passes with the edit planted"""
+    method, old, new = DTYPE_EQUIVALENT[name]
+    monkeypatch.setattr(models.DeviceLESEnsemble, method, _edited(method, old, new))
+    for modes in MIX_SIX + IMIX_SIX:
+        for seed in SEEDS:
+            es.run(_oracle32(), _oracle32(), seed, modes, 3)
+            es.run(_oracle(), _oracle(), seed, modes, 3)

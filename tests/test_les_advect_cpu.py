@@ -14,6 +14,7 @@ from sp_coupler_amd import _abi, models, spcpl
 from sp_coupler_amd import advection as adv
 from tests import les_advect_ref as lar
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = {numpy.float64: 2.0 ** -52, numpy.float32: 2.0 ** -23}
@@ -347,3 +348,45 @@ def test_a_refused_step_leaves_the_fields_untouched():
     ens.set_fields_batched("U", bad)
     ens.evolve_model_batched(900.0)
     assert ens.model_time == 900.0 and ens.advect_substeps == 1
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("thermo,micro,diffuse", [(False, False, False), (False, False, True), (True, False, False), (True, True, True),
+                                                  (False, True, True)])
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(thermo, micro, diffuse):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    calls = []
+    n_sub = lar.check_ensemble(f32_of(lar.AdvectOracleEngine)(), [_counted(f32_of(lar.AdvectOracleEngine)(), calls)], 4, thermo, micro=micro, diffuse=diffuse)
+    keys = ["QT", "THL", "U", "V"] + (["QR"] if micro else [])
+    probes = [c for c in calls if not c[0]]
+    assert n_sub in (2, 3) and len(probes) == 3 and all(c == (sorted(keys), 4) for c in calls if c[0])
+    assert calls[:1 + n_sub] == [([], 4)] + [(sorted(keys), 4)] * n_sub               # one probe, then the substeps
+
+
+def test_float32_ensemble_with_one_substep():
+    """test_ensemble_with_one_substep on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    calls = []
+    assert lar.check_ensemble(f32_of(lar.AdvectOracleEngine)(), [_counted(f32_of(lar.AdvectOracleEngine)(), calls)], 3, False, dx=lar.DX_ONE) == 1
+    assert calls == [([], 3), (["QT", "THL", "U", "V"], 3)] * 3
+
+
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_ensemble_as_row_blocks_with_an_empty_device(thermo):
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(lar.AdvectOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    n_sub = lar.check_ensemble(f32_of(lar.AdvectOracleEngine)(), [multi], 2, thermo, micro=thermo, diffuse=True)
+    assert all(c[1] == 1 for c in calls) and len([c for c in calls if not c[0]]) == 6      # blocks 1 + 1 + 0: two probes per step
+    assert n_sub in (2, 3)
+
+
+def test_float32_fused_step_then_advection(monkeypatch):
+    """test_fused_step_then_advection on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    steps = []
+    eng = f32_of(lar.AdvectOracleEngine)()
+    inner = eng.les_advance
+    eng.les_advance = lambda *a, **kw: (steps.append(kw.get("sat")), inner(*a, **kw))[1]
+    lar.check_ensemble(f32_of(lar.AdvectOracleEngine)(), [eng], 3, False)
+    assert steps == ["QT"] * 3

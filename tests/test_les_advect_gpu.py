@@ -109,3 +109,26 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, diffuse, thermo, micro, d
         assert len(probes) == 3 and all(r == rows for r, _ in mine)                       # one probe per device and step ...
         assert mine[:1 + n_sub] == [(rows, 0)] + [(rows, nf)] * n_sub                     # ... and n_sub launches behind it
         assert all(f == nf for k, (r, f) in enumerate(mine) if k not in probes)
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("diffuse,thermo,micro,dx", [(False, False, False, lar.DX_FEW), (True, False, False, lar.DX_FEW),
+                                                     (True, True, True, lar.DX_FEW), (False, False, False, lar.DX_ONE)])
+@pytest.mark.parametrize("n", [4, 130])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, diffuse, thermo, micro, dx):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    inner = Engine.les_advect
+    monkeypatch.setattr(Engine, "les_advect", lambda self, fields, out, u, *a, **kw: (launches.append((id(self), int(u.shape[0]), len(fields))),
+                                                                                    inner(self, fields, out, u, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    n_sub = lar.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, thermo, micro=micro, diffuse=diffuse, dx=dx)
+    assert (n_sub == 1) if dx == lar.DX_ONE else n_sub in (2, 3)
+    nf = 5 if micro else 4
+    for eng, rows in [(one, n)] + [(e, n // 2) for e in multi.engines]:
+        mine = [(r, f) for i, r, f in launches if i == id(eng)]
+        probes = [k for k, (r, f) in enumerate(mine) if f == 0]
+        assert len(probes) == 3 and all(r == rows for r, _ in mine)                       # one probe per device and step ...
+        assert mine[:1 + n_sub] == [(rows, 0)] + [(rows, nf)] * n_sub                     # ... and n_sub launches behind it
+        assert all(f == nf for k, (r, f) in enumerate(mine) if k not in probes)

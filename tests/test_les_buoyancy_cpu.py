@@ -16,6 +16,7 @@ from sp_coupler_amd import buoyancy as buo
 from sp_coupler_amd import sputils
 from tests import les_buoyancy_ref as lbr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [p + (k,) for p in lbr.PLANES for k in (1, 2, 7, 65)]     # itot x jtot x ktot
@@ -383,3 +384,28 @@ def test_the_column_tile_cases_on_the_oracle_backed_engine(lib):
     eng = lbr.BuoyancyOracleEngine()
     eng.buoyancy_cols_per_block = lambda ktot: lib.spc_les_buoyancy_cols_per_block(ktot, numpy.dtype(lbr.np_of(eng)).itemsize)
     lbr.check_coltile(eng)
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", list(lbr.VARIANTS))
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(variant):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    subs = lbr.check_ensemble(f32_of(lbr.BuoyancyOracleEngine)(), [f32_of(lbr.BuoyancyOracleEngine)()], 4, variant)
+    calls, without = [], []
+    lbr.ensemble_run(_counted(f32_of(lbr.BuoyancyOracleEngine)(), calls), 4, True, **lbr.VARIANTS[variant])
+    lbr.ensemble_run(_counted(f32_of(lbr.BuoyancyOracleEngine)(), without), 4, True, buoyancy=None, **lbr.VARIANTS[variant])
+    assert len(subs) == 4 and subs[2] == subs[3]                       # (the record after the nudge repeats the second step's)
+    want = []
+    for n_sub in subs[:2] + subs[3:]:
+        want += ["les_advect", "les_vadvect"] + ["les_buoyancy", "les_advect", "les_vadvect"] * n_sub
+    assert substep_calls(calls) == want
+    assert "les_buoyancy" not in without
+
+
+def test_float32_ensemble_as_row_blocks_with_an_empty_device():
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(lbr.BuoyancyOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    subs = lbr.check_ensemble(f32_of(lbr.BuoyancyOracleEngine)(), [multi], 2, "plain")
+    assert calls.count("les_buoyancy") == 2 * sum(subs[:2] + subs[3:])          # blocks 1 + 1 + 0: two devices

@@ -119,3 +119,24 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, variant):
         assert [k for i, k in launches if i == id(eng)] == want
     mine = [k for i, k in launches if i == id(one)]                   # (then the run without enable_buoyancy(): on `one` only)
     assert mine[:len(want)] == want and len(mine) > len(want) and "les_buoyancy" not in mine[len(want):]
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", list(lbr.VARIANTS))
+@pytest.mark.parametrize("n", [4, 130])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, variant):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    for name in ("les_buoyancy", "les_advect", "les_vadvect"):
+        inner = getattr(Engine, name)
+        monkeypatch.setattr(Engine, name, lambda self, *a, _n=name, _f=inner, **kw: (launches.append((id(self), _n)), _f(self, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    subs = lbr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, variant)
+    want = []
+    for n_sub in subs[:2] + subs[3:]:                                 # (the record after the nudge repeats the second step's)
+        want += ["les_advect", "les_vadvect"] + ["les_buoyancy", "les_advect", "les_vadvect"] * n_sub
+    for eng in multi.engines:
+        assert [k for i, k in launches if i == id(eng)] == want
+    mine = [k for i, k in launches if i == id(one)]                   # (then the run without enable_buoyancy(): on `one` only)
+    assert mine[:len(want)] == want and len(mine) > len(want) and "les_buoyancy" not in mine[len(want):]

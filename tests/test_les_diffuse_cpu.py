@@ -15,6 +15,7 @@ from sp_coupler_amd import diffusion as df
 from sp_coupler_amd import microphysics as mp
 from tests import les_diffuse_ref as ldr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 2.0 ** -52
@@ -322,3 +323,35 @@ def test_the_column_tile_cases_on_the_oracle_backed_engine(lib):
     eng = ldr.DiffuseOracleEngine()
     eng.diffuse_cols_per_block = lambda ktot: lib.spc_les_diffuse_cols_per_block(ktot, numpy.dtype(ldr.np_of(eng)).itemsize)
     ldr.check_coltile(eng)
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("micro", [False, True])
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(thermo, micro):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    calls = []
+    ldr.check_ensemble(f32_of(ldr.DiffuseOracleEngine)(), [_counted(f32_of(ldr.DiffuseOracleEngine)(), calls)], 4, thermo, micro=micro)
+    assert calls == [(["QT", "THL", "U", "V"], 4, ["QT", "THL"])] * 3                     # one launch per step
+
+
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_ensemble_as_row_blocks_with_an_empty_device(thermo):
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(ldr.DiffuseOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    ldr.check_ensemble(f32_of(ldr.DiffuseOracleEngine)(), [multi], 2, thermo, micro=thermo)
+    assert calls == [(["QT", "THL", "U", "V"], 1, ["QT", "THL"])] * 6                     # blocks 1 + 1 + 0: the device without rows launches nothing
+
+
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_fused_step_then_diffusion(monkeypatch, thermo):
+    """test_fused_step_then_diffusion on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    steps = []
+    eng = f32_of(ldr.DiffuseOracleEngine)()
+    inner = eng.les_advance
+    eng.les_advance = lambda *a, **kw: (steps.append(kw.get("sat")), inner(*a, **kw))[1]
+    ldr.check_ensemble(f32_of(ldr.DiffuseOracleEngine)(), [eng], 3, thermo)
+    assert steps == [None if thermo else "QT"] * 3

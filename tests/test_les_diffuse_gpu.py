@@ -109,3 +109,18 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, thermo, micro):
     multi = MultiDeviceEngine([Engine("cuda:0", stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
     ldr.check_ensemble(Engine("cuda:0"), [one, multi], n, thermo, micro=micro)
     assert launches == [(n, ["QT", "THL"])] * 3 + [(n // 2, ["QT", "THL"])] * 6
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("thermo,micro", [(False, False), (True, False), (True, True)])
+@pytest.mark.parametrize("n", [4, 130])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, thermo, micro):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    dif = Engine.les_diffuse
+    monkeypatch.setattr(Engine, "les_diffuse", lambda self, fields, *a, **kw: (launches.append((int(fields["THL"].shape[0]), sorted(kw["flux"]))),
+                                                                              dif(self, fields, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    ldr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, thermo, micro=micro)
+    assert launches == [(n, ["QT", "THL"])] * 3 + [(n // 2, ["QT", "THL"])] * 6

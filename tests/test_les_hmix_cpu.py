@@ -21,6 +21,7 @@ from tests import les_hmix_ref as lhr
 from tests import les_micro_ref as lmr
 from tests import les_mix_ref as lxr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NPS = [numpy.float64, numpy.float32]
@@ -405,3 +406,11 @@ def test_nan_stays_in_its_line_then_in_its_plane():
     hit[1, :, :, 1] = True
     assert numpy.array_equal(numpy.isnan(both), hit)
     assert_bits("n == 1 keeps every bit", lhr.sweep(c["X"][:, :1], lhr.weights(c["km"][:, :1], c["coef"]["X"][0], c["kh2"], 1), 1), c["X"][:, :1])
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", sorted(lhr.VARIANTS))
+def test_float32_ensemble_equals_the_host_twin(variant):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    host = lhr.check_ensemble(f32_of(lhr.HmixOracleEngine)(), [f32_of(lhr.HmixOracleEngine)()], 3, variant)
+    assert variant != "forced" or host[-1]["counts"].sum() > 0

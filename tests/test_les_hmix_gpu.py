@@ -113,3 +113,21 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, variant):
     want = ([("les_mix", 0), ("les_hmix", None)] + ([("les_vmix", None)] if vmix else [])) * 3
     for eng in multi.engines + [one]:
         assert [(k, c) for i, k, c in launches if i == id(eng)] == want
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("n,variant", [(4, "plain"), (4, "all"), (4, "forced"), (4, "k15"), (130, "plain")])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, variant):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    for name in ("les_mix", "les_hmix", "les_vmix"):
+        inner = getattr(Engine, name)
+        monkeypatch.setattr(Engine, name, lambda self, *a, _n=name, _f=inner, **kw: (
+            launches.append((id(self), _n, len(a[0]) if _n == "les_mix" else None)), _f(self, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    lhr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, variant)
+    vmix = lhr.VARIANTS[variant].get("vmix", False)
+    want = ([("les_mix", 0), ("les_hmix", None)] + ([("les_vmix", None)] if vmix else [])) * 3
+    for eng in multi.engines + [one]:
+        assert [(k, c) for i, k, c in launches if i == id(eng)] == want

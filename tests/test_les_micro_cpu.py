@@ -13,6 +13,7 @@ from sp_coupler_amd import _abi, models, spcpl
 from sp_coupler_amd import microphysics as mp
 from tests import les_micro_ref as lmr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = {numpy.float64: 2.0 ** -52, numpy.float32: 2.0 ** -23}
@@ -301,3 +302,34 @@ def test_the_chain_cases_on_the_oracle_backed_engine():
     """the oracle alone handles every case of the chain body, none skipped; its plumbing runs without a GPU"""
     lmr.check_chain(lmr.MicroOracleEngine())
     assert "chain" in lmr.BODIES
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(thermo):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    calls = []
+    lmr.check_ensemble(f32_of(lmr.MicroOracleEngine)(), [_counted(f32_of(lmr.MicroOracleEngine)(), calls)], 4, thermo)
+    assert calls == [(4, thermo)] * 3                            # one launch per step
+
+
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_ensemble_as_row_blocks_with_an_empty_device(thermo):
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(lmr.MicroOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    lmr.check_ensemble(f32_of(lmr.MicroOracleEngine)(), [multi], 2, thermo)
+    assert calls == [(1, thermo)] * 6                            # blocks 1 + 1 + 0: the device without rows launches nothing
+
+
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_fused_step_then_microphysics(monkeypatch, thermo):
+    """test_fused_step_then_microphysics on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    steps = []
+    eng = f32_of(lmr.MicroOracleEngine)()
+    inner = eng.les_advance
+    eng.les_advance = lambda *a, **kw: (steps.append(kw.get("sat")), inner(*a, **kw))[1]
+    lmr.check_ensemble(f32_of(lmr.MicroOracleEngine)(), [eng], 3, thermo)
+    assert steps == [None if thermo else "QT"] * 3

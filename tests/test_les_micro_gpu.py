@@ -110,3 +110,20 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, thermo):
 def test_the_chain_cases(dtype):
     """the cases of the lane's walk that spc_chain.hpp's kernels share, held together, for both batch sizes (les_micro_ref.check_chain)"""
     lmr.check_chain(Engine("cuda:0", dtype=dtype))
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("thermo", [False, True])
+@pytest.mark.parametrize("n", [4, 130])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, thermo):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    monkeypatch.setattr(models.DeviceLESEnsemble, "FUSED_MIN_LES", 0)
+    launches, steps = [], []
+    mic, adv = Engine.les_microphysics, Engine.les_advance
+    monkeypatch.setattr(Engine, "les_microphysics", lambda self, qt, *a, **kw: (launches.append((int(qt.shape[0]), kw.get("temp") is not None)), mic(self, qt, *a, **kw))[1])
+    monkeypatch.setattr(Engine, "les_advance", lambda self, *a, **kw: (steps.append(kw.get("sat")), adv(self, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    lmr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, thermo)
+    assert launches == [(n, thermo)] * 3 + [(n // 2, thermo)] * 6
+    assert steps == [None if thermo else "QT"] * 9

@@ -16,6 +16,7 @@ from tests import les_full_ref as lfr
 from tests import les_mix_ref as lxr
 from tests import test_engine_les_args_cpu as args_cpu
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 SHAPES = [(3, 8, 8, 20), (2, 2, 2, 5), (2, 3, 5, 7), (1, 1, 4, 3), (2, 33, 5, 65)]
 NPS = [numpy.float64, numpy.float32]
@@ -307,3 +308,12 @@ def test_never_enabled_is_the_full_twin():
     lxr.lmr.same_logs(lxr.ensemble_run(lfr.FullOracleEngine(), 2, False, mixing=None, **lxr.VARIANTS["all"])[1], log)
     ens, log = lxr.ensemble_run(Spy(), 2, True, **lxr.VARIANTS["all"])
     assert calls == ["les_mix"] * 3
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant,vertical", [("plain", False), ("all", False), ("all", True), ("forced", True)])
+def test_float32_ensemble_equals_the_host_twin(variant, vertical):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    host = lxr.check_ensemble(f32_of(lxr.MixOracleEngine)(), [f32_of(lxr.MixOracleEngine)()], 3, variant, vertical)
+    assert host[-1]["k max"][1] in (0.0, 1.0)
+    assert variant != "forced" or host[-1]["counts"].sum() > 0        # K19 ran, in the twin and (bit-equal) on the device

@@ -114,3 +114,29 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, variant, vertical):
             assert mine == ["les_mix"] * 3
     mine = [k for i, k in launches if i == id(one)]                   # (then the run without enable_mixing(): on `one` only)
     assert mine.count("les_mix") == 3 and (variant == "plain" or mine.count("les_diffuse") == 6)
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("n,variant,vertical", [(4, "plain", False), (4, "all", False), (4, "all", True), (4, "forced", True), (130, "plain", False),
+                                                 (130, "all", True)])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, variant, vertical):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    for name in ("les_transport", "les_transport2", "les_mix", "les_diffuse"):
+        inner = getattr(Engine, name)
+        monkeypatch.setattr(Engine, name, lambda self, *a, _n=name, _f=inner, **kw: (launches.append((id(self), _n)), _f(self, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    lxr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, variant, vertical)
+    for eng in multi.engines:
+        mine = [k for i, k in launches if i == id(eng)]
+        steps = [i for i, k in enumerate(mine) if k == "les_mix"]
+        assert len(steps) == 3
+        if variant != "plain":                                        # per step: the probe (K22), the substeps (K23), K24, K15
+            for i in steps:
+                assert mine[i - 1] == "les_transport2" and mine[i + 1] == "les_diffuse"
+            assert mine[0] == "les_transport" and mine.count("les_diffuse") == 3 and mine.count("les_transport") == 3
+        else:
+            assert mine == ["les_mix"] * 3
+    mine = [k for i, k in launches if i == id(one)]                   # (then the run without enable_mixing(): on `one` only)
+    assert mine.count("les_mix") == 3 and (variant == "plain" or mine.count("les_diffuse") == 6)

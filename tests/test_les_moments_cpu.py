@@ -8,6 +8,7 @@ import subprocess
 
 import numpy
 import pytest
+import torch
 
 import __graft_entry__ as ge
 from sp_coupler_amd import _abi, models, spcpl
@@ -15,6 +16,7 @@ from sp_coupler_amd import statistics as st
 from tests import les_moments_ref as mr
 from tests import les_qt_local_ref as qlr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NPS = [numpy.float64, numpy.float32]
@@ -313,3 +315,25 @@ def test_the_chain_cases_on_the_oracle_backed_engine():
     """the oracle alone handles every case of the chain body, none skipped; its plumbing runs without a GPU"""
     mr.check_chain(mr.MomentsOracleEngine())
     assert "chain" in mr.BODIES
+
+
+# -- the same on float32 engines -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", list(mr.VARIANTS))
+def test_float32_ensemble_on_one_engine_equals_the_twin(variant):
+    """test_ensemble_on_one_engine_equals_the_twin on a float32 engine: the statistics are K20's float32 results, widened exactly"""
+    calls = []
+    ens, log = mr.ensemble_run(_counted(f32_of(mr.MomentsOracleEngine)(), calls), 4, calls, **mr.VARIANTS[variant])
+    assert len(calls) == 5 and all(t.dtype == torch.float32 for t in ens.get_statistics_batched()["var"].values())
+    assert ("cov W-THL" in log[-1]) == (variant == "all") and ("var W" in log[0]) is False
+    assert not numpy.array_equal(log[1]["var QT"], log[2]["var QT"]) and (log[-1]["TKE"] > 0).all()
+    assert all(numpy.array_equal(v, v.astype(numpy.float32)) for k, v in log[-1].items() if k != "TKE")
+
+
+def test_float32_ensemble_as_row_blocks_with_an_empty_device():
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(mr.MomentsOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    one = mr.ensemble_run(f32_of(mr.MomentsOracleEngine)(), 2, **mr.VARIANTS["all"])[1]
+    log = mr.ensemble_run(multi, 2, calls, **mr.VARIANTS["all"])[1]
+    assert len(calls) == 10
+    qlr.lmr.same_logs(one, log)

@@ -17,6 +17,7 @@ from sp_coupler_amd import qt_forcing as qf
 from tests import les_qt_local_ref as qlr
 from tests import slab_ref
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = {numpy.float64: 2.0 ** -52, numpy.float32: 2.0 ** -23}
@@ -369,3 +370,33 @@ def test_an_ensemble_without_the_method_behaves_as_before():
             assert_bits(kind + " " + k, other.fields3d[k], sp.fields3d[k])
         for k in sp.p:
             assert_bits(kind + " p " + k, other.p[k], sp.p[k])
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", qf.KINDS)
+@pytest.mark.parametrize("variant", list(qlr.VARIANTS))
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(variant, kind):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    qlr.check_ensemble(f32_of(qlr.QtLocalOracleEngine)(), [f32_of(qlr.QtLocalOracleEngine)()], 4, variant, kind)
+    calls = []
+    qlr.ensemble_run(_counted(f32_of(qlr.QtLocalOracleEngine)(), calls), 4, True, kind=kind, **qlr.VARIANTS[variant])
+    assert calls.count("les_qt_local") == 3
+    if variant == "plain":
+        assert calls == ["les_qt_local"] * 3
+    else:
+        at = [i for i, k in enumerate(calls) if k == "les_qt_local"] + [len(calls)]
+        for lo, hi in zip(at[:-1], at[1:]):
+            step = calls[lo:hi]
+            physics = [k for k in step if k not in ("les_qt_local", "les_thermo")]
+            assert physics[0] == "les_advect" and physics.index("les_diffuse") < physics.index("les_radiate") < physics.index("les_microphysics")
+            assert calls[lo - 1] == "les_thermo"                  # (K12 made the QL that K19 reads)
+
+
+@pytest.mark.parametrize("kind", qf.KINDS)
+def test_float32_ensemble_as_row_blocks_with_an_empty_device(kind):
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(qlr.QtLocalOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    qlr.check_ensemble(f32_of(qlr.QtLocalOracleEngine)(), [multi], 2, "all", kind)
+    assert calls.count("les_qt_local") == 6                        # blocks 1 + 1 + 0: two devices, three steps

@@ -111,3 +111,19 @@ def test_coupler_with_a_local_qt_forcing_is_not_sp():
             assert set(a) == set(b)
             for k in a:
                 assert_bits("%s %s" % (kind, k), b[k], a[k])
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", qf.KINDS)
+@pytest.mark.parametrize("variant", list(qlr.VARIANTS))
+@pytest.mark.parametrize("n", [4, 130])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, variant, kind):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    inner = Engine.les_qt_local
+    monkeypatch.setattr(Engine, "les_qt_local", lambda self, qt, *a, **kw: (launches.append((id(self), int(qt.shape[0]))), inner(self, qt, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    qlr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, variant, kind)
+    for eng, rows in [(one, n)] + [(e, n // 2) for e in multi.engines]:
+        assert [r for i, r in launches if i == id(eng)] == [rows] * 3          # three steps: three launches

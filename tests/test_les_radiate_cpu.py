@@ -16,6 +16,7 @@ from sp_coupler_amd import _abi, models, spcpl
 from sp_coupler_amd import radiation as rad
 from tests import les_radiate_ref as lrr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = {numpy.float64: 2.0 ** -52, numpy.float32: 2.0 ** -23}
@@ -420,3 +421,31 @@ def test_the_column_tile_cases_on_the_oracle_backed_engine(lib):
     eng = lrr.RadiateOracleEngine()
     eng.radiate_cols_per_block = lambda ktot: lib.spc_les_radiate_cols_per_block(ktot, numpy.dtype(lrr.np_of(eng)).itemsize)
     lrr.check_coltile(eng)
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", list(lrr.VARIANTS))
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(variant):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    lrr.check_ensemble(f32_of(lrr.RadiateOracleEngine)(), [f32_of(lrr.RadiateOracleEngine)()], 4, variant)
+    with_rad, without = [], []
+    lrr.ensemble_run(_counted(f32_of(lrr.RadiateOracleEngine)(), with_rad), 4, True, **lrr.VARIANTS[variant])
+    lrr.ensemble_run(_counted(f32_of(lrr.RadiateOracleEngine)(), without), 4, True, radiate=None, **lrr.VARIANTS[variant])
+    assert with_rad.count("les_radiate") == 3 and "les_radiate" not in without
+    if variant in STEP_CALLS:
+        assert with_rad == STEP_CALLS[variant] * 3
+    else:
+        first = with_rad.index("les_diffuse")
+        step = with_rad[first:with_rad.index("les_diffuse", first + 1)]
+        assert [k for k in step if k != "les_vadvect"] == ["les_diffuse", "les_thermo", "les_radiate", "les_thermo", "les_microphysics", "les_thermo"]
+        assert with_rad.count("les_thermo") - without.count("les_thermo") == 3
+
+
+@pytest.mark.parametrize("variant", ["plain", "all"])
+def test_float32_ensemble_as_row_blocks_with_an_empty_device(variant):
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(lrr.RadiateOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    lrr.check_ensemble(f32_of(lrr.RadiateOracleEngine)(), [multi], 2, variant)
+    assert calls.count("les_radiate") == 6                         # blocks 1 + 1 + 0: two devices, three steps

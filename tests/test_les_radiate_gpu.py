@@ -112,3 +112,18 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, variant):
     lrr.check_ensemble(Engine("cuda:0"), [one, multi], n, variant)
     for eng, rows in [(one, n)] + [(e, n // 2) for e in multi.engines]:
         assert [r for i, r in launches if i == id(eng)] == [rows] * 3          # three steps: three launches
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", list(lrr.VARIANTS))
+@pytest.mark.parametrize("n", [4, 130])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, variant):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    inner = Engine.les_radiate
+    monkeypatch.setattr(Engine, "les_radiate", lambda self, ql, *a, **kw: (launches.append((id(self), int(ql.shape[0]))), inner(self, ql, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    lrr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, variant)
+    for eng, rows in [(one, n)] + [(e, n // 2) for e in multi.engines]:
+        assert [r for i, r in launches if i == id(eng)] == [rows] * 3          # three steps: three launches

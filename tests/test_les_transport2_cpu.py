@@ -16,6 +16,7 @@ from sp_coupler_amd import advection as adv
 from tests import les_transport2_ref as lt2
 from tests import les_transport_ref as ltr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = {numpy.float64: 2.0 ** -52, numpy.float32: 2.0 ** -23}
@@ -426,3 +427,29 @@ def test_a_courant_sum_that_is_not_finite_raises():
     with pytest.raises(RuntimeError, match="Courant sum"):
         ens.evolve_model_batched(100.0)
     assert ens.advect_courant == float("inf")
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant,limiter", [("plain", "mc"), ("plain", "none"), ("buoyancy", "mc"), ("all buoyant", "mc")])
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(variant, limiter):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    calls = []
+    subs = lt2.check_ensemble(f32_of(lt2.Transport2OracleEngine)(), [_counted(f32_of(lt2.Transport2OracleEngine)(), calls)], 4, variant, limiter)
+    kw = lt2.VARIANTS[variant]
+    keys = sorted(["QT", "THL", "U", "V"] + (["QR"] if kw.get("micro") else []))
+    assert len(subs) == 3 and all(s >= 1 for s in subs)
+    want = []
+    for n_sub in subs:
+        want += [("les_transport", [], 4)] + (([("les_buoyancy", None, 4)] if kw.get("buoyancy") else []) + [("les_transport2", keys, 4)]) * n_sub
+    assert calls[:len(want)] == want                               # the second-order run came first
+    rest = calls[len(want):]                                       # then order=1 and the call without the arguments
+    assert rest and all(c[0] in ("les_transport", "les_buoyancy") for c in rest) and any(c[0] == "les_transport" and c[1] for c in rest)
+
+
+def test_float32_ensemble_as_row_blocks_with_an_empty_device():
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(lt2.Transport2OracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    subs = lt2.check_ensemble(f32_of(lt2.Transport2OracleEngine)(), [multi], 2, "plain")
+    assert all(c[2] == 1 for c in calls) and len([c for c in calls if c[0] == "les_transport2"]) == 2 * sum(subs)   # blocks 1 + 1 + 0

@@ -131,3 +131,36 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, variant):
             assert rest and all(m[0] in ("les_transport", "les_buoyancy") for m in rest) and any(m[0] == "les_transport" and m[2] for m in rest)
         else:
             assert len(mine) == len(want)
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", ["plain", "buoyancy", "all"])
+@pytest.mark.parametrize("n", [4, 130])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, variant):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    for name in ("les_advect", "les_vadvect", "les_transport", "les_transport2"):
+        inner = getattr(Engine, name)
+        monkeypatch.setattr(Engine, name, lambda self, fields, out, u, *a, _n=name, _f=inner, **kw: (
+            launches.append((id(self), _n, int(u.shape[0]), len(fields))), _f(self, fields, out, u, *a, **kw))[1])
+    inner_b = Engine.les_buoyancy
+    monkeypatch.setattr(Engine, "les_buoyancy", lambda self, thl, *a, **kw: (
+        launches.append((id(self), "les_buoyancy", int(thl.shape[0]), -1)), inner_b(self, thl, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    subs = lt2.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, variant)
+    assert len(subs) == 3 and all(s >= 1 for s in subs)
+    kw = lt2.VARIANTS[variant]
+    nf = 5 if kw.get("micro") else 4
+    for eng, rows in [(one, n)] + [(e, n // 2) for e in multi.engines]:
+        mine = [(k, r, f) for i, k, r, f in launches if i == id(eng)]
+        assert all(r == rows for _, r, _ in mine)
+        want = []
+        for n_sub in subs:                                            # the probe, then (K21 and) K23 per substep
+            want += [("les_transport", rows, 0)] + (([("les_buoyancy", rows, -1)] if kw.get("buoyancy") else []) + [("les_transport2", rows, nf)]) * n_sub
+        assert mine[:len(want)] == want                               # the second-order run came first
+        if eng is one:                                                # then the runs with order=1 and without the arguments: K22's
+            rest = mine[len(want):]
+            assert rest and all(m[0] in ("les_transport", "les_buoyancy") for m in rest) and any(m[0] == "les_transport" and m[2] for m in rest)
+        else:
+            assert len(mine) == len(want)

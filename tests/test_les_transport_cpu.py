@@ -18,6 +18,7 @@ from sp_coupler_amd import advection as adv
 from tests import les_transport_ref as ltr
 from tests import les_vadvect_ref as lvr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = {numpy.float64: 2.0 ** -52, numpy.float32: 2.0 ** -23}
@@ -421,3 +422,30 @@ def test_a_courant_sum_that_is_not_finite_raises():
     with pytest.raises(RuntimeError, match="K22"):
         ens.evolve_model_batched(100.0)
     assert ens.advect_courant == float("inf")
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", ["plain", "buoyancy", "all", "all buoyant"])
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(variant):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    calls = []
+    subs = ltr.check_ensemble(f32_of(ltr.TransportOracleEngine)(), [_counted(f32_of(ltr.TransportOracleEngine)(), calls)], 4, variant)
+    kw = ltr.VARIANTS[variant]
+    keys = sorted(["QT", "THL", "U", "V"] + (["QR"] if kw.get("micro") else []))
+    assert len(subs) == 3 and all(s >= 1 for s in subs)
+    want = []
+    for n_sub in subs:
+        want += _step_calls(keys, 4, n_sub, bool(kw.get("buoyancy")))
+    assert calls[:len(want)] == want                               # the conservative run came first: no K16, no K17 in it
+    assert all(c[0] != "les_transport" for c in calls[len(want):]) and any(c[0] == "les_vadvect" for c in calls[len(want):])
+
+
+@pytest.mark.parametrize("variant", ["plain", "all buoyant"])
+def test_float32_ensemble_as_row_blocks_with_an_empty_device(variant):
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(ltr.TransportOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    subs = ltr.check_ensemble(f32_of(ltr.TransportOracleEngine)(), [multi], 2, variant)
+    assert all(c[2] == 1 for c in calls) and len([c for c in calls if c[0] == "les_transport" and not c[1]]) == 6   # blocks 1 + 1 + 0, three steps
+    assert len([c for c in calls if c[0] == "les_transport" and c[1]]) == 2 * sum(subs)

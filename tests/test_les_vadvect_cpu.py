@@ -16,6 +16,7 @@ from sp_coupler_amd import _abi, models, spcpl
 from sp_coupler_amd import advection as adv
 from tests import les_vadvect_ref as lvr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = {numpy.float64: 2.0 ** -52, numpy.float32: 2.0 ** -23}
@@ -353,3 +354,27 @@ def test_a_mass_flux_that_is_not_finite_raises():
     with pytest.raises(RuntimeError, match="K17"):
         ens.evolve_model_batched(100.0)
     assert ens.advect_courant_z == float("inf")
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("thermo,micro,diffuse", [(False, False, False), (False, False, True), (True, True, True)])
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(thermo, micro, diffuse):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    calls = []
+    n_sub = lvr.check_ensemble(f32_of(lvr.VadvectOracleEngine)(), [_counted(f32_of(lvr.VadvectOracleEngine)(), calls)], 4, thermo, micro=micro, diffuse=diffuse)
+    keys = sorted(["QT", "THL", "U", "V"] + (["QR"] if micro else []))
+    assert n_sub in (2, 3) and calls[:2 + 2 * n_sub] == _step_calls(keys, 4, n_sub)      # the probes, then K16 and K17 per substep
+    vertical = calls[:[i for i, c in enumerate(calls) if c[0] == "les_vadvect"][-1] + 1]   # (the runs with vertical=False follow)
+    assert len([c for c in vertical if c[0] == "les_vadvect" and not c[1]]) == 3 and all(c[0] == "les_advect" for c in calls[len(vertical):])
+    assert len([c for c in vertical if c[0] == "les_advect"]) == len([c for c in vertical if c[0] == "les_vadvect"])
+
+
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_ensemble_as_row_blocks_with_an_empty_device(thermo):
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(lvr.VadvectOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    n_sub = lvr.check_ensemble(f32_of(lvr.VadvectOracleEngine)(), [multi], 2, thermo, micro=thermo, diffuse=True)
+    assert all(c[2] == 1 for c in calls) and len([c for c in calls if c[0] == "les_vadvect" and not c[1]]) == 6   # blocks 1 + 1 + 0
+    assert n_sub in (2, 3)

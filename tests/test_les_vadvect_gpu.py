@@ -115,3 +115,28 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, diffuse, thermo, micro):
         last = max(k for k, m in enumerate(mine) if m[0] == "les_vadvect")
         assert len([m for m in mine[:last + 1] if m == ("les_vadvect", rows, 0)]) == 3      # the run with vertical=True came first
         assert len([m for m in mine[:last + 1] if m[0] == "les_advect"]) == len([m for m in mine[:last + 1] if m[0] == "les_vadvect"])
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("diffuse,thermo,micro", [(False, False, False), (True, False, False), (True, True, True)])
+@pytest.mark.parametrize("n", [4, 130])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, diffuse, thermo, micro):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    for name in ("les_advect", "les_vadvect"):
+        inner = getattr(Engine, name)
+        monkeypatch.setattr(Engine, name, lambda self, fields, out, u, *a, _n=name, _f=inner, **kw: (
+            launches.append((id(self), _n, int(u.shape[0]), len(fields))), _f(self, fields, out, u, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    n_sub = lvr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, thermo, micro=micro, diffuse=diffuse)
+    assert n_sub in (2, 3)
+    nf = 5 if micro else 4
+    for eng, rows in [(one, n)] + [(e, n // 2) for e in multi.engines]:
+        mine = [(k, r, f) for i, k, r, f in launches if i == id(eng)]
+        assert all(r == rows for _, r, _ in mine)
+        want = [("les_advect", rows, 0), ("les_vadvect", rows, 0)] + [("les_advect", rows, nf), ("les_vadvect", rows, nf)] * n_sub
+        assert mine[:2 + 2 * n_sub] == want                           # the two probes, then K16 and K17 per substep
+        last = max(k for k, m in enumerate(mine) if m[0] == "les_vadvect")
+        assert len([m for m in mine[:last + 1] if m == ("les_vadvect", rows, 0)]) == 3      # the run with vertical=True came first
+        assert len([m for m in mine[:last + 1] if m[0] == "les_advect"]) == len([m for m in mine[:last + 1] if m[0] == "les_vadvect"])

@@ -16,6 +16,7 @@ from tests import les_diffuse_ref as ldr
 from tests import les_micro_ref as lmr
 from tests import les_vmix_ref as lvr
 from tests.gpu_util import assert_bits
+from tests.les_harness import f32_of
 
 SHAPES = [(3, 8, 8, 20), (2, 2, 2, 5), (2, 3, 5, 7), (1, 1, 4, 2), (2, 3, 5, 65)]
 NPS = [numpy.float64, numpy.float32]
@@ -351,3 +352,12 @@ def test_launches_per_step_and_a_second_read_launches_nothing():
         ens.get_profiles_batched(tuple(prof), prof)
         assert ens.get_vertical_viscosity_batched() is kv and not calls
         assert (kv is ens.get_eddy_viscosity_batched()) == (cap is not None)
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("variant,cap,z0m", [("plain", None, True), ("plain", 1e6, True), ("plain", None, False), ("all", None, True), ("forced", None, True)])
+def test_float32_ensemble_equals_the_host_twin(variant, cap, z0m):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    host, capped = lvr.check_ensemble(f32_of(lvr.VmixOracleEngine)(), [f32_of(lvr.VmixOracleEngine)()], 3, variant, cap=cap, z0m=z0m)
+    assert (cap is None or not any(capped)) and (cap is not None or variant != "plain" or all(capped))
+    assert variant != "forced" or host[-1]["counts"].sum() > 0

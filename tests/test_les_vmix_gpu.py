@@ -107,3 +107,21 @@ def test_ensemble_equals_the_host_twin(monkeypatch, n, variant, cap):
     want = [k for c in steps for k in (["les_mix"] * (2 if c else 1) + ["les_vmix"])]
     for eng in multi.engines + [one]:
         assert [k for i, k in launches if i == id(eng)] == want
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("n,variant,cap", [(4, "plain", None), (4, "plain", 1e6), (4, "all", None), (4, "forced", None), (130, "plain", None)])
+def test_float32_ensemble_equals_the_host_twin(monkeypatch, n, variant, cap):
+    """test_ensemble_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    launches = []
+    for name in ("les_mix", "les_vmix"):
+        inner = getattr(Engine, name)
+        monkeypatch.setattr(Engine, name, lambda self, *a, _n=name, _f=inner, **kw: (launches.append((id(self), _n)), _f(self, *a, **kw))[1])
+    one = Engine("cuda:0", dtype=torch.float32)
+    multi = MultiDeviceEngine([Engine("cuda:0", dtype=torch.float32, stream=torch.cuda.Stream("cuda:0")) for _ in range(2)], min_cols_per_device=1)
+    host, capped = lvr.check_ensemble(Engine("cuda:0", dtype=torch.float32), [one, multi], n, variant, cap=cap)
+    steps = [capped[0], capped[1], capped[3]]                         # (capped[2]: the record behind the nudge repeats step 2)
+    assert all(steps) if cap is None and variant == "plain" else cap is None or not any(steps)
+    want = [k for c in steps for k in (["les_mix"] * (2 if c else 1) + ["les_vmix"])]
+    for eng in multi.engines + [one]:
+        assert [k for i, k in launches if i == id(eng)] == want

@@ -11,6 +11,7 @@ import pytest
 import __graft_entry__ as ge
 from sp_coupler_amd import _abi, models, spcpl
 from tests import les_water_paths_ref as wpr
+from tests.les_harness import f32_of
 from tools import mutation_control as mc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -250,3 +251,22 @@ def test_water_path_mutants_apply_to_the_tree_and_name_their_guards():
                 assert text != f.read(), (n, fname)
     libs = [mc.lib_of(n, t) for t in (mc.MUTANTS, mc.ADVANCE_MUTANTS, mc.THERMO_MUTANTS, mc.WATERPATH_MUTANTS) for n in t]
     assert len(set(libs)) == len(libs) and mc.lib_of(2, table).endswith("libspc_waterpath_mutant2.so")
+
+
+# -- the same on float32 engines against the float32 twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_ensemble_on_one_engine_equals_the_host_twin(thermo):
+    """test_ensemble_on_one_engine_equals_the_host_twin on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    calls = []
+    wpr.check_ensemble(f32_of(wpr.WaterPathOracleEngine)(), [_counted(f32_of(wpr.WaterPathOracleEngine)(), calls)], 4, thermo)
+    assert calls == [(("LWP", "TWP", "RWP"), 4)] * 3              # one launch per state of the fields: everything else is cached
+
+
+@pytest.mark.parametrize("thermo", [False, True])
+def test_float32_ensemble_as_row_blocks_with_an_empty_device(thermo):
+    """test_ensemble_as_row_blocks_with_an_empty_device on float32 engines against the float32 twin (tests/slab_ref.py: the rule of T)"""
+    from sp_coupler_amd.multi import MultiDeviceEngine
+    calls = []
+    multi = MultiDeviceEngine([_counted(f32_of(wpr.WaterPathOracleEngine)(), calls) for _ in range(3)], min_cols_per_device=1)
+    wpr.check_ensemble(f32_of(wpr.WaterPathOracleEngine)(), [multi], 2, thermo)
+    assert calls == [(("LWP", "TWP", "RWP"), 1)] * 6              # blocks 1 + 1 + 0: the device without rows launches nothing
